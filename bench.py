@@ -8,15 +8,22 @@ One "step" = one pass of the hot path over one batch: BATCH (256) fp32 NCHW fram
 resident in HBM, -> (BATCH, 2048) fp32 features (= backbone(x).flatten(1),
 /root/reference/src/preprocess_resnet_features.py:296); for N > 1 each rank owns its own frames
 (weak scaling) and the features return to rank 0 with one RCCL gather per step.
-Prints ONE JSON line on rank 0 (contract in the task statement), including:
-  roofline     — the implicit-GEMM conv kernel class: algorithmic FLOPs / HIP-event time of those launches,
-                 measured live on the launch stream.
-  cpu_baseline — the CPU restatement of the reference's fp32 path (oracle/) timed on the host cores.
+Prints ONE JSON line on rank 0: metric, value (frames/s), unit, higher_is_better, dtype, ms_per_step (milliseconds of one
+timed step), plus:
   preheat      — an untimed >= 1 s run of the same step right before the timed region (steady clocks), with its rate.
-  checked      — the timed output is finite and frames 0 / B-1 equal the same frames run alone (outside the timed region).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; nothing else.  --full adds,
+after the timed region:
+  single_lane  — the same K steps strictly one batch at a time on lane 0 (a second timed run).
+  checked      — the timed output is finite and frames 0 / B-1 equal the same frames run alone.
+  roofline, kernels — per-kernel-class HIP-event timing of a second pass over the same steps (--dump-layers needs it).
+  cpu_baseline — the CPU restatement of the reference's fp32 path (oracle/) timed on the host cores.
   fp16_b256, fp8_b512 — SECONDARY measurements appended after the headline one (N = 1 only): the mode that meets
                  north_star's 1e-3 and BASELINE configs[4]; each with frames/s, its igemm class against its MFMA peak, and its
                  accuracy against the oracle's emulation and fp64 view (computed inside the cpu_baseline leg).
+
+--dump-outputs DIR: the (N*B, 2048) fp32 features the last timed step returned (on rank 0: gathered over the ranks) as
+DIR/features.npy; inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -41,6 +48,7 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0         # dense bf16, /opt/skills/guides/MI355X_M
 MFMA_FP8_PEAK_TFLOPS = 5000.0          # dense fp8 on the scaled K = 128 MFMA, same guide (--precision fp8 prices its igemm class against this)
 HBM_PEAK_GBPS = 8000.0                  # HBM3E, same guide
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20             # --dump-outputs: all files together at most this size
 
 
 def host_cores() -> int:
@@ -182,6 +190,33 @@ def timed_steps(step, fence, steps: int, warmup: int, preheat_s: float, frames_p
     return time.perf_counter() - t0, pre_rate
 
 
+def dump_outputs(out_dir, arrays: dict, limit_bytes: int = DUMP_LIMIT_BYTES) -> dict:
+    """Write every array of ``arrays`` (name -> tensor) as ``out_dir/<name>.npy`` in float32 (float64 stays float64).  If they
+    would exceed ``limit_bytes`` together, each keeps a fixed, seeded sample of rows (sorted, the same rows in every run) that fits
+    its share.  Returns name -> {shape, rows} of what was written."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t if t.dtype == torch.float64 else t.float()
+    total = sum(t.numel() * t.element_size() for t in host.values())
+    written = {}
+    for name, t in host.items():
+        rows = None
+        if total > limit_bytes and t.dim() > 0 and t.shape[0] > 1:
+            row_bytes = max(1, t[0].numel() * t.element_size())
+            share = limit_bytes * (t.numel() * t.element_size()) // total
+            keep = max(1, min(t.shape[0], share // row_bytes))
+            g = torch.Generator().manual_seed(0)
+            rows = torch.randperm(t.shape[0], generator=g)[:keep].sort().values
+            t = t.index_select(0, rows)
+        np.save(out_dir / f"{name}.npy", t.contiguous().numpy())
+        written[name] = {"shape": list(t.shape), "rows": None if rows is None else f"seeded sample of {len(rows)} rows"}
+    return written
+
+
 def secondary_mode(precision: str, batch: int, steps: int, warmup: int, preheat_s: float, dev, sd, n_lanes: int = 1) -> dict:
     """A secondary, clearly labelled measurement after the headline one: the same step in another precision / batch
     (fp16 at batch 256 = the mode inside north_star's 1e-3; fp8 at batch 512 = BASELINE configs[4])."""
@@ -300,7 +335,16 @@ def main() -> None:
     ap.add_argument("--stream-frames", type=int, default=0,
                     help="fixed-stream mode (SURVEY 8d): this many frames IN TOTAL (e.g. 163840 = 4096 clips x 40), cut into contiguous "
                          "ranges per rank (strong scaling); --steps is then derived and reported.  0 = weak scaling, --batch per rank per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check: single-lane figure, output checks, per-kernel-class profile "
+                         "(roofline, kernels, --dump-layers), secondary precisions, CPU baseline.  Off: the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the features of the last timed step (rank 0: gathered over the ranks) as DIR/features.npy (fp32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers needs the per-kernel-class profile of --full")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -474,8 +518,19 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- what the last timed step returned, before anything below reuses the output buffers ----
+    if args.dump_outputs and rank == 0:
+        if lanes is not None:
+            last = feats_l[(lane_state["k"] - 1) % n_lanes]
+        else:
+            last = feats
+        if dist is not None and not rehearsal:
+            last = torch.cat(gathered, dim=0)       # what rank 0's caller receives: every rank's block, in rank order
+        torch.cuda.synchronize(dev)
+        dump_outputs(args.dump_outputs, {"features": last})
+
     single_lane = None
-    if lanes is not None:
+    if lanes is not None and args.full:
         torch.cuda.synchronize(dev)
         lanes_agree = all(bool(torch.equal(feats_l[0], f)) for f in feats_l[1:n_lanes])
         if dist is None:                   # the same K steps strictly one after the other on lane 0 (no second batch in flight)
@@ -491,8 +546,8 @@ def main() -> None:
     #      alone as a batch of 2 (the kernels' tile choice, persistent tile streams and ragged last tiles differ between the two runs;
     #      the arithmetic per frame must not)
     checked = None
-    headline_feats = feats[:2].cpu() if (args.input == "f32" and not args.from_host and rank == 0) else None
-    if args.input == "f32" and not args.from_host:
+    headline_feats = feats[:2].cpu() if (args.full and args.input == "f32" and not args.from_host and rank == 0) else None
+    if args.full and args.input == "f32" and not args.from_host:
         failure = None
         finite = bool(torch.isfinite(feats).all())
         if not finite:
@@ -520,7 +575,7 @@ def main() -> None:
     # ---- per-kernel-class HIP-event timing on the launch stream (rank 0, same steps again) ----
     roofline = None
     kernels = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_streams = bb.get_option("streams")
         bb.set_option("streams", 1)          # one stream: event brackets must not interleave with another stream's kernels
         bb.set_option("profile", 1)
@@ -560,7 +615,7 @@ def main() -> None:
 
     secondary = {}
     acc_in = {}
-    if rank == 0 and world == 1 and not args.no_secondary and args.precision == "bf16" and args.input == "f32" and not args.from_host:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.precision == "bf16" and args.input == "f32" and not args.from_host:
         (lanes or bb).close()         # frees the headline handles' workspaces before the secondary ones are created
         torch.cuda.empty_cache()
         for prec, b in (("fp16", 256), ("fp8", 512)):
@@ -568,7 +623,7 @@ def main() -> None:
 
     cpu = None
     accuracy = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if headline_feats is not None and args.precision in ("bf16", "fp16") and args.batch >= 2:
             acc_in["headline"] = {"feats": headline_feats, "precision": args.precision}
         cpu = cpu_baseline(accuracy_of=acc_in)
@@ -590,7 +645,7 @@ def main() -> None:
         out = {
             "metric": "H36M frames/sec ResNet-50 feature extraction",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong" if args.stream_frames else "weak",
+            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "full": args.full, "scaling": "strong" if args.stream_frames else "weak",
             "vs_baseline": None, "dtype": {"bf16": "bf16", "fp16": "fp16", "bf16w2": "bf16 (weights as bf16 head+tail pairs)",
                                             "fp32x": "bf16x3 (fp32-class)", "fp8": "fp8 e4m3 (layer2-4; stem + layer1 bf16)"}[args.precision],
             "data": "synthetic" + (" (REHEARSAL: all ranks on one GPU, gloo; not a measurement)" if rehearsal else ""),

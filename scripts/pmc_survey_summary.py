@@ -1,9 +1,10 @@
 """Per-kernel summary of scripts/pmc_survey.sh: share of wave cycles waiting / issuing, instruction mix per MFMA, LDS conflicts."""
-import csv, glob, collections
+import csv, glob, collections, sys
+OUT = sys.argv[1] if len(sys.argv) > 1 else "prof_out"           # the directory pmc_survey.sh wrote to
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
 calls = collections.Counter()
 for i in (1, 2, 3):
-    fs = glob.glob(f"gpurun_out/pmcs_p{i}/**/*counter_collection.csv", recursive=True)
+    fs = glob.glob(f"{OUT}/pmcs_p{i}/**/*counter_collection.csv", recursive=True)
     if not fs: continue
     seen = set()
     for r in csv.DictReader(open(fs[0])):

@@ -132,3 +132,21 @@ def test_roofline_object_describes_the_largest_class(bench):
     ig = r["classes"]["igemm"]
     assert ig["bound"] == "mfma" and ig["frac"] == pytest.approx(1.97e12 / 2.2e-3 / 1e12 / 2500.0) and ig["launches_per_step"] == 19
     assert set(r["classes"]) == {"igemm", "bneck_tail3", "conv1", "avgpool"}
+
+
+def test_dump_outputs_writes_fp32_npy_and_samples_the_same_rows_past_the_limit(bench, tmp_path):
+    """--dump-outputs: every array as DIR/<name>.npy in float32; over the size limit a fixed, seeded sample of rows is kept."""
+    import numpy as np
+    import torch
+    feats = torch.arange(64 * 8, dtype=torch.float32).reshape(64, 8)
+    info = bench.dump_outputs(tmp_path / "a", {"features": feats.to(torch.bfloat16)})
+    got = np.load(tmp_path / "a" / "features.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 8) and info["features"]["rows"] is None
+    assert np.array_equal(got, feats.to(torch.bfloat16).float().numpy())
+    limit = 16 * 8 * 4                                   # room for 16 of the 64 rows
+    bench.dump_outputs(tmp_path / "b", {"features": feats}, limit_bytes=limit)
+    bench.dump_outputs(tmp_path / "c", {"features": feats}, limit_bytes=limit)
+    b, c = np.load(tmp_path / "b" / "features.npy"), np.load(tmp_path / "c" / "features.npy")
+    assert b.shape == (16, 8) and b.nbytes <= limit and np.array_equal(b, c)
+    rows = b[:, 0] / 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(b, feats.numpy()[rows.astype(int)])

@@ -267,7 +267,7 @@ def test_bench_under_torchrun_runs_gather_barrier_and_fence_on_rccl(tmp_path, li
     """bench.py --gpus 1 as one torchrun rank: init_process_group("nccl", device_id=...), the per-step gather of the (256, 2048)
     feature block, the all-reduced pre-heat / elapsed times and the barrier + synchronize fences all execute on RCCL."""
     import json
-    out = _torchrun_one_rank(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "0.2", "--no-secondary",
+    out = _torchrun_one_rank(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "0.2", "--full", "--no-secondary",
                               "--no-cpu-baseline"], tmp_path)
     line = [ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]
     rec = json.loads(line)
@@ -285,9 +285,43 @@ def test_bench_two_ranks_rehearsal_runs_the_same_collective_sequence(tmp_path, l
     per-step gather behind the lane's event, MAX-reduced failure flag, barriers -- or the run hangs / fails: rc 0 inside the timeout is the
     assertion.  Its numbers mean nothing (the line says REHEARSAL); no scaling figure is derived from it."""
     import json
-    out = _torchrun_one_rank(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "0.2", "--no-secondary", "--no-cpu-baseline"],
+    out = _torchrun_one_rank(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "0.2", "--full", "--no-secondary", "--no-cpu-baseline"],
                              tmp_path, timeout=900, nproc=2, extra_env={"R50_BENCH_REHEARSAL": "1"})
     line = [ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]
     rec = json.loads(line)
     assert rec["n_gpus"] == 2 and "REHEARSAL" in rec["data"] and rec["steps"] == 3
     assert rec["checked"]["finite"] and rec["checked"]["equal_to_batch2_run"] and rec["config"]["lanes_requested"] == 2
+
+
+def test_plain_bench_dumps_the_features_of_its_last_timed_step(tmp_path, lib_built):
+    """A plain bench.py run (no --full): the headline fields only, and --dump-outputs holds exactly the features the backbone returns
+    for the seeded synthetic frames of the benchmark (the lanes compute the same bits as one backbone)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import numpy as np
+    from implementation_phd_lab_vision_amd.backbone import ResNet50Backbone
+    from implementation_phd_lab_vision_amd.weights import synthetic_frames, synthetic_state_dict
+    root = Path(__file__).resolve().parents[1]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dump = tmp_path / "dump"
+    res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "0.2",
+                          "--dump-outputs", str(dump)], env=env, cwd=str(root), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = res.stdout.decode(errors="replace")
+    assert res.returncode == 0, out[-4000:]
+    rec = json.loads([ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
+    assert rec["full"] is False and rec["steps"] == 3 and rec["value"] > 1000 and rec["unit"] == "frames/s" and rec["dtype"] == "bf16"
+    assert rec["ms_per_step"] == pytest.approx(1e3 * 256 / rec["value"]) and rec["higher_is_better"] is True
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["checked"] is None and "fp16_b256" not in rec
+    assert sorted(p.name for p in dump.iterdir()) == ["features.npy"]
+    got = np.load(dump / "features.npy")
+    assert got.dtype == np.float32 and got.shape == (256, 2048)
+    bb = ResNet50Backbone(state_dict=synthetic_state_dict(0), max_batch=256).to("cuda:0").eval()
+    want = bb.features(synthetic_frames(256, seed=1234).to("cuda:0")).cpu().numpy()
+    bb.close()
+    assert np.array_equal(got, want)
