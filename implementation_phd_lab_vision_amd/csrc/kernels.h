@@ -4143,6 +4143,34 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const float* __restr
     if (threadIdx.x == 0) { loss[0] = red[0][0] / (float)n; loss[1] = red[1][0] / (float)(n / 3); }
 }
 
+// Pose metrics of one evaluation batch (src/train.py:219-280): l3d = mean((p - g)^2) over nj*3 elements (:259) and
+// MPJPE = mean |p - g|_2 over nj joints (:42-45), ADDED to acc = [sum l3d, sum mpjpe, batches] so that the mean over per-batch
+// means needs one host read per pass.  Per joint fp32 (d, d^2 summed x, y, z, sqrtf); per-thread fp64 partial sums over a fixed
+// strided slice, then a fixed fp64 tree: the same bits on every run, no atomics.  ONE workgroup of 1024 threads: an eval batch
+// is at most ~1e5 joints (train.py's 32 x 40 x 17 = 21,760), ~100 joints per thread; the launch is latency-bound.
+__global__ __launch_bounds__(1024) void pose_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt, long long nj,
+                                                            double* __restrict__ acc) {
+    __shared__ double red[2][1024];
+    double s = 0.0, e = 0.0;
+    for (long long j = threadIdx.x; j < nj; j += 1024) {
+        const float dx = pred[3 * j] - gt[3 * j], dy = pred[3 * j + 1] - gt[3 * j + 1], dz = pred[3 * j + 2] - gt[3 * j + 2];
+        const float d2 = dx * dx + dy * dy + dz * dz;
+        s += (double)d2;
+        e += (double)sqrtf(d2);
+    }
+    red[0][threadIdx.x] = s; red[1][threadIdx.x] = e;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        acc[0] += red[0][0] / (3.0 * (double)nj);
+        acc[1] += red[1][0] / (double)nj;
+        acc[2] += 1.0;
+    }
+}
+
 // Backward of gn_relu_causal3_kernel.  dr (B*T, 3C): gradient of the causal-conv input rows; x (B, T, C): the GroupNorm input
 // saved by the forward.  da(s, c) = sum of dr over the (row, tap) pairs that read frame s (replicate padding: frame 0 also
 // collects the clamped taps), dy = da * (y > 0), and with xh = (x - mean) * rstd, g = dy * gamma over the (C/groups x T) slab:

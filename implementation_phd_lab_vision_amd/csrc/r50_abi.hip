@@ -2361,6 +2361,13 @@ int r50_op_mse_loss_grad(const float* y, const float* gt, int64_t n, float loss_
     return ew_done("r50_op_mse_loss_grad");
 }
 
+int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int joints, double* acc, void* stream) {
+    if (!pred || !gt || !acc || rows < 1 || joints < 1 || rows > INT64_MAX / 3 / joints)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_metrics: invalid arguments");
+    hipLaunchKernelGGL(pose_metrics_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, (long long)(rows * joints), acc);
+    return ew_done("r50_op_pose_metrics");
+}
+
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,
                                float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et, void* stream) {
     if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part || b < 1 || t < 1 || c < 1 || groups < 1 || c % groups ||

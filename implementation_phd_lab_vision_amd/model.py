@@ -234,5 +234,28 @@ class PHDFor3DJoints:
 
     forward = __call__
 
+    def joints(self, feats: torch.Tensor) -> torch.Tensor:
+        """``self(feats)[2]`` (joints_phi, (B,T,J,3) fp32) without f_AR: the evaluation pass (src/train.py:247) uses only joints_phi,
+        and f_AR's output feeds phi_hat alone.  The same launches in the same order as ``__call__`` on this path, so the result is
+        bit-equal."""
+        if self._device is None or not self._dev:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') before running the head")
+        if feats.dim() != 3 or feats.shape[-1] != 2048:
+            raise ValueError(f"expected (B,T,2048) features, got {tuple(feats.shape)}")
+        if feats.device != self._device:
+            raise ValueError(f"features are on {feats.device}, head on {self._device}")
+        b, t, _ = feats.shape
+        if b * t == 0:
+            raise ValueError("empty batch")
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            f = feats.to(torch.float32).contiguous()
+            x0 = torch.empty((b * t, 2048), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * t, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None,
+                       "r50_op_cast_rows")
+            x = self._gemm(x0, "input_proj", relu=False)
+            phi = self._temporal_net(x, b, t, "f_movie", self.number_blocks)
+            return self._regressor(phi, b, t)
+
 
 PHD = PHDFor3DJoints       # the name src/train.py imports it under

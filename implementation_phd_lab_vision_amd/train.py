@@ -25,16 +25,26 @@ reference's keys) and adds ``train_step(feats, joints3d, optim, scaler)``.  Arit
   (35.8 M parameters x 4 B = 67.6 MB at train.py's configuration; 16.9 M trainable) instead of nn.DataParallel's scatter /
   replicate / gather (:381-383).
 
-PyTorch is used for device memory, the stream, the dropout masks' random bits and torch.distributed.  No CPU fallback.
+The driver (src/train.py:219-465; ``python -m implementation_phd_lab_vision_amd.train``): ``evaluate`` (the validation pass, metrics
+by ``r50_op_pose_metrics``), ``samplers.MixedShardBatchSampler`` over ``DeviceFeatureStore``, ``CosineLR`` (torch's
+CosineAnnealingLR in the reference's order), ``save_checkpoint`` / ``load_checkpoint`` in the reference's format
+(``AdamW.state_dict`` in torch.optim.AdamW's layout), early stopping and the reference's CLI.
+
+PyTorch is used for device memory, the stream, the dropout masks' random bits, the LR schedule and torch.distributed.  No CPU fallback.
 """
 from __future__ import annotations
 
+import argparse
+import hashlib
+import json
+import os
+import time
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from .model import _GN_EPS, _GROUPS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints, _round_up
+from .model import _GN_EPS, _GROUPS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints, _round_up, expected_keys
 
 DROPOUT_P = 0.5        # ResidualBlock(dropout=0.5), JointRegressor(dropout=0.5): src/model.py:39,87
 
@@ -71,6 +81,7 @@ class AdamW:
     def __init__(self, head: "TrainableHead", lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2):
         self.head, self.lr, self.betas, self.eps, self.weight_decay = head, lr, betas, eps, weight_decay
+        self.initial_lr = lr                 # what CosineAnnealingLR records in the param group (saved in checkpoints)
         self.step_count = 0
         self.exp_avg = torch.zeros_like(head.flat_master)
         self.exp_avg_sq = torch.zeros_like(head.flat_master)
@@ -84,6 +95,69 @@ class AdamW:
                                               self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
                                               found_inf_flag.data_ptr() if found_inf_flag is not None else None, h._et, h._stream())
         _lib.check(rc, None, "r50_op_adamw")
+
+    def _param_group(self, n: int) -> dict:
+        """torch.optim.AdamW's param group for these hyperparameters, with the flags of the installed torch (taken from a
+        throwaway instance rather than restated), ``initial_lr`` as CosineAnnealingLR sets it, parameter ids 0..n-1."""
+        probe = torch.optim.AdamW([torch.zeros(1, requires_grad=True)], lr=self.lr, betas=self.betas, eps=self.eps,
+                                  weight_decay=self.weight_decay)
+        group = probe.state_dict()["param_groups"][0]
+        group["initial_lr"] = self.initial_lr
+        group["params"] = list(range(n))
+        return group
+
+    def state_dict(self) -> dict:
+        """What ``torch.optim.AdamW(trainable, lr, weight_decay=1e-2).state_dict()`` of the reference holds (src/train.py:70,389):
+        parameter ``i`` is ``trainable_names()[i]`` in the reference's layout, ``state[i] = {step: fp32 scalar tensor, exp_avg,
+        exp_avg_sq}`` (CPU, fp32; empty before the first applied step, as torch's lazy state)."""
+        names = trainable_names(self.head.number_blocks)
+        state = {}
+        if self.step_count > 0:
+            m, v = self.head.flat_to_reference(self.exp_avg), self.head.flat_to_reference(self.exp_avg_sq)
+            state = {i: {"step": torch.tensor(float(self.step_count), dtype=torch.float32), "exp_avg": m[n], "exp_avg_sq": v[n]}
+                     for i, n in enumerate(names)}
+        return {"state": state, "param_groups": [self._param_group(len(names))]}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        """Inverse of ``state_dict``; accepts what torch.optim.AdamW over the reference's trainable parameters saved.  Takes the
+        group's hyperparameters (lr, initial_lr, betas, eps, weight_decay) as torch does, the moments and the step, then refreshes
+        the head's 16-bit weights and their transposes from its fp32 master."""
+        names = trainable_names(self.head.number_blocks)
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(names):
+            raise ValueError(f"expected one param group of {len(names)} parameters (the reference's phase-1 trainable set)")
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("amsgrad / maximize AdamW states are not supported")
+        ids = g["params"]
+        state = state_dict["state"]
+        if not state:
+            step, m, v = 0, torch.zeros_like(self.exp_avg), torch.zeros_like(self.exp_avg_sq)
+        else:
+            steps = {float(state[i]["step"]) for i in ids}
+            if len(steps) != 1:
+                raise ValueError(f"the phase-1 parameters step together; found steps {sorted(steps)}")
+            step = int(steps.pop())
+            m = self.head.flat_from_reference({n: state[i]["exp_avg"] for n, i in zip(names, ids)})
+            v = self.head.flat_from_reference({n: state[i]["exp_avg_sq"] for n, i in zip(names, ids)})
+        self.lr, self.eps, self.weight_decay = float(g["lr"]), float(g["eps"]), float(g["weight_decay"])
+        self.betas = (float(g["betas"][0]), float(g["betas"][1]))
+        self.initial_lr = float(g.get("initial_lr", self.lr))
+        self.exp_avg, self.exp_avg_sq, self.step_count = m, v, step
+        self.head.refresh_weights16()
+
+
+def trainable_names(number_blocks: int) -> List[str]:
+    """``[n for n, p in model.named_parameters() if p.requires_grad]`` of the reference's ``PHDFor3DJoints`` with f_AR frozen
+    (src/train.py:375-388): the module registers f_movie, f_AR, f_3D and then input_proj (src/model.py:142-146), a ResidualBlock
+    gn1, conv1, gn2, conv2 (:39-44).  ``f_3D.y0`` is a buffer.  This is the numbering of the optimizer's state."""
+    names: List[str] = []
+    for i in range(number_blocks):
+        for m in ("gn1", "conv1.conv", "gn2", "conv2.conv"):
+            names += [f"f_movie.blocks.{i}.{m}.weight", f"f_movie.blocks.{i}.{m}.bias"]
+    for j in (0, 3, 5):
+        names += [f"f_3D.mlp.{j}.weight", f"f_3D.mlp.{j}.bias"]
+    return names + ["input_proj.weight", "input_proj.bias"]
 
 
 def all_reduce_gradients(flat_grad: torch.Tensor, group=None) -> None:
@@ -209,27 +283,20 @@ class TrainableHead(PHDFor3DJoints):
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's keys and layouts (fp32, CPU) from the flat master buffer; frozen entries as loaded."""
-        d, o = self.latent_dim, self.out_dim
         out = {k: v.clone() for k, v in self._sd.items()}
-        get = lambda name: self.flat_master[self._off[name][0]: self._off[name][0] + int(torch.Size(self._off[name][1]).numel())] \
-            .view(self._off[name][1]).cpu()
-        out["input_proj.weight"], out["input_proj.bias"] = get("input_proj.w"), get("input_proj.b")
-        for i in range(self.number_blocks):
-            p = f"f_movie.blocks.{i}"
-            for gn in ("gn1", "gn2"):
-                out[f"{p}.{gn}.weight"], out[f"{p}.{gn}.bias"] = get(f"{p}.{gn}.g"), get(f"{p}.{gn}.b")
-            for cv in ("conv1", "conv2"):
-                out[f"{p}.{cv}.conv.weight"] = get(f"{p}.{cv}.w").view(d, 3, d).permute(0, 2, 1).contiguous()
-                out[f"{p}.{cv}.conv.bias"] = get(f"{p}.{cv}.b")
-        out["f_3D.mlp.0.weight"], out["f_3D.mlp.0.bias"] = get("mlp0.w")[:, : d + o].contiguous(), get("mlp0.b")
-        out["f_3D.mlp.3.weight"], out["f_3D.mlp.3.bias"] = get("mlp3.w"), get("mlp3.b")
-        out["f_3D.mlp.5.weight"], out["f_3D.mlp.5.bias"] = get("mlp5.w")[:o].contiguous(), get("mlp5.b")[:o].contiguous()
+        out.update(self.flat_to_reference(self.flat_master))
         return out
 
     def named_gradients(self) -> Dict[str, torch.Tensor]:
         """flat_grad under the reference's parameter names and layouts (fp32, CPU): what ``p.grad`` holds after ``backward()``."""
+        return self.flat_to_reference(self.flat_grad)
+
+    def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """A buffer in the flat parameter layout (master, gradient, AdamW moments) under the reference's names and layouts of the
+        trainable parameters (fp32, CPU); the GEMM padding is dropped."""
         d, o = self.latent_dim, self.out_dim
-        g = lambda name: self.grad_view(name).cpu()
+        g = lambda name: flat[self._off[name][0]: self._off[name][0] + int(torch.Size(self._off[name][1]).numel())] \
+            .view(self._off[name][1]).cpu()
         out = {"input_proj.weight": g("input_proj.w"), "input_proj.bias": g("input_proj.b")}
         for i in range(self.number_blocks):
             p = f"f_movie.blocks.{i}"
@@ -242,6 +309,39 @@ class TrainableHead(PHDFor3DJoints):
         out["f_3D.mlp.3.weight"], out["f_3D.mlp.3.bias"] = g("mlp3.w"), g("mlp3.b")
         out["f_3D.mlp.5.weight"], out["f_3D.mlp.5.bias"] = g("mlp5.w")[:o].contiguous(), g("mlp5.b")[:o].contiguous()
         return out
+
+    def flat_from_reference(self, named: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """Inverse of ``flat_to_reference``: a new device buffer in the flat layout, zero in the GEMM padding."""
+        d, o = self.latent_dim, self.out_dim
+        flat = torch.zeros_like(self.flat_master)
+
+        def v(name):
+            o_, shape = self._off[name]
+            return flat[o_: o_ + int(torch.Size(shape).numel())].view(shape)
+
+        def put(dst, key, shape=None):
+            t = named[key].detach().to(torch.float32)
+            if tuple(t.shape) != tuple(shape if shape is not None else dst.shape):
+                raise ValueError(f"{key}: shape {tuple(t.shape)}, expected {tuple(shape if shape is not None else dst.shape)}")
+            dst.copy_(t)
+
+        put(v("input_proj.w"), "input_proj.weight"); put(v("input_proj.b"), "input_proj.bias")
+        for i in range(self.number_blocks):
+            p = f"f_movie.blocks.{i}"
+            for gn in ("gn1", "gn2"):
+                put(v(f"{p}.{gn}.g"), f"{p}.{gn}.weight"); put(v(f"{p}.{gn}.b"), f"{p}.{gn}.bias")
+            for cv in ("conv1", "conv2"):
+                put(v(f"{p}.{cv}.w").view(d, 3, d).permute(0, 2, 1), f"{p}.{cv}.conv.weight")
+                put(v(f"{p}.{cv}.b"), f"{p}.{cv}.conv.bias")
+        put(v("mlp0.w")[:, : d + o], "f_3D.mlp.0.weight"); put(v("mlp0.b"), "f_3D.mlp.0.bias")
+        put(v("mlp3.w"), "f_3D.mlp.3.weight"); put(v("mlp3.b"), "f_3D.mlp.3.bias")
+        put(v("mlp5.w")[:o], "f_3D.mlp.5.weight"); put(v("mlp5.b")[:o], "f_3D.mlp.5.bias")
+        return flat
+
+    def refresh_weights16(self) -> None:
+        """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
+        self.flat_w16.copy_(self.flat_master.to(self._dtype))
+        self._refresh_transposes()
 
     # ---- launch helpers -----------------------------------------------------------------------
     def _mm(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -482,3 +582,229 @@ def train(model: TrainableHead, loader, optim: AdamW, scaler: Optional[GradScale
         if log_every > 0 and (it + 1) % log_every == 0:
             print(f"[3D]  iter {it + 1:05d} | loss {running_loss / n_batches:.6f} | mpjpe {running_mpjpe / n_batches:.3f}")
     return running_loss / max(n_batches, 1), running_mpjpe / max(n_batches, 1)
+
+
+# ---- the phase-1 driver: src/train.py:219-465 (evaluate, checkpoints, LR schedule, early stopping, CLI) -----------------------
+H36M_ROOT = "/home/s26ldeso/Human3.6M_preprocessed_resnet_features"    # the reference's defaults (src/config.py)
+SEQ_LEN, BATCH_SIZE, LR, EPOCHS, JOINTS_NUM = 40, 32, 1e-4, 50, 17
+TRAIN_SUBJECTS, VAL_SUBJECTS = [1, 6, 7, 8], [5]                          # hard-coded at src/train.py:312,318
+
+
+def default_state_dict(latent_dim: int = 1024, joints_num: int = JOINTS_NUM, number_blocks: int = 2,
+                       seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Initial weights with the distribution of torch's default initialisation of the reference module: nn.Linear / nn.Conv1d
+    weight and bias U(-1/sqrt(fan_in), 1/sqrt(fan_in)) (kaiming_uniform with a = sqrt(5)), GroupNorm weight 1 / bias 0, y0 zero.
+    Drawn from ``torch.Generator().manual_seed(seed)``; the reference draws from the unseeded global generator."""
+    gen = torch.Generator().manual_seed(seed)
+    keys = expected_keys(latent_dim, joints_num, number_blocks)
+    sd: Dict[str, torch.Tensor] = {}
+    for k, shape in keys.items():
+        if k == "f_3D.y0" or (".gn" in k and k.endswith(".bias")):
+            sd[k] = torch.zeros(shape)
+        elif ".gn" in k:
+            sd[k] = torch.ones(shape)
+        else:
+            w = keys[k[: -len("bias")] + "weight"] if k.endswith(".bias") else shape
+            bound = (w[1] * (w[2] if len(w) == 3 else 1)) ** -0.5
+            sd[k] = torch.empty(shape).uniform_(-bound, bound, generator=gen)
+    return sd
+
+
+def dropout_generator(seed: int, epoch: int, it: int, device) -> torch.Generator:
+    """The generator of one step's dropout masks: seeded from (seed, epoch, iteration) alone, so an epoch draws the same masks
+    whether the run was resumed or not."""
+    key = int.from_bytes(hashlib.sha256(f"{seed}/{epoch}/{it}".encode()).digest()[:8], "little") & ((1 << 63) - 1)
+    return torch.Generator(device=device).manual_seed(key)
+
+
+class CosineLR:
+    """The reference's per-epoch learning rate: a real ``torch.optim.lr_scheduler.CosineAnnealingLR(optim, T_max=epochs)``
+    (src/train.py:395) on a proxy ``torch.optim.AdamW`` holding the hyperparameters, driven in the reference's order: built
+    fresh, THEN the checkpoint's param group loaded into the optimizer (:400-405, ``load_group``), ``step()`` after each epoch's
+    evaluation (:425).  So a resumed run restarts the scheduler's counter at 0 from the loaded LR and applies the recursive
+    cosine factor from there: its LRs are not those of an uninterrupted run.  That is the reference's behaviour, kept on purpose."""
+
+    def __init__(self, lr: float, epochs: int):
+        self.proxy = torch.optim.AdamW([torch.zeros(1, requires_grad=True)], lr=lr, weight_decay=1e-2)
+        self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.proxy, T_max=epochs)
+
+    @property
+    def lr(self) -> float:
+        return float(self.proxy.param_groups[0]["lr"])
+
+    @property
+    def initial_lr(self) -> float:
+        return float(self.proxy.param_groups[0]["initial_lr"])
+
+    def load_group(self, optim_state: dict) -> None:
+        """What ``optim.load_state_dict(ckpt["optim"])`` does to the param group: the saved hyperparameters replace the current ones."""
+        self.proxy.param_groups[0].update({k: v for k, v in optim_state["param_groups"][0].items() if k != "params"})
+
+    def step(self) -> None:
+        self.proxy.step()             # no gradients, so nothing changes; it tells the scheduler the optimizer stepped first
+        self.scheduler.step()
+
+
+@torch.no_grad()
+def evaluate(head: PHDFor3DJoints, store, batch_size: int, test_set: bool = False) -> Tuple[float, float, float, float]:
+    """src/train.py:219-280: (loss, mpjpe, l3d, 0.0), each the mean over batches of the per-batch mean.  The items of ``store``
+    in order, ``batch_size`` at a time, the last batch kept even if short (the reference's val loader: shuffle=False,
+    drop_last=False).  The head runs in eval mode through ``joints()`` (no f_AR); one ``r50_op_pose_metrics`` launch per batch
+    adds into a device accumulator, read once at the end.  The head's mode is restored; its weights are not touched.
+    ``test_set``: the store yields the meta list as a fifth field (ignored here), as the reference's flag says."""
+    del test_set                      # only changes the batch tuple's length in the reference; get_batch's first two fields serve
+    was_training = head.training
+    head.train(False)
+    lib = _lib.load_library()
+    dev = head._device
+    try:
+        with torch.cuda.device(dev):
+            acc = torch.zeros(3, dtype=torch.float64, device=dev)
+            for s in range(0, len(store), batch_size):
+                batch = store.get_batch(list(range(s, min(s + batch_size, len(store)))))
+                pred = head.joints(batch[0])
+                gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
+                rows = pred.shape[0] * pred.shape[1]
+                _lib.check(lib.r50_op_pose_metrics(pred.data_ptr(), gt.data_ptr(), rows, head.joints_num, acc.data_ptr(),
+                                                   head._stream()), None, "r50_op_pose_metrics")
+            l3d, mpjpe, n = acc.tolist()
+    finally:
+        head.train(was_training)
+    n = max(n, 1.0)
+    return l3d / n, mpjpe / n, l3d / n, 0.0
+
+
+def train_epoch(head: TrainableHead, store, sampler, optim: AdamW, scaler: Optional[GradScaler], seed: int, epoch: int,
+                log_every: int = 500) -> Tuple[float, float, int, int]:
+    """One training epoch of the driver (src/train.py:114-215): the batches of ``sampler`` (its epoch already set) drawn from
+    ``store``, one ``train_step`` each with the masks of ``dropout_generator(seed, epoch, it)``.
+    Returns (mean loss, mean mpjpe, applied steps, skipped steps)."""
+    head.train()
+    running_loss = running_mpjpe = 0.0
+    n_batches = skipped = 0
+    for it, idx in enumerate(sampler):
+        feats, joints3d = store.get_batch(idx)[:2]
+        masks = head.make_dropout_masks(feats.shape[0], feats.shape[1], generator=dropout_generator(seed, epoch, it, head._device))
+        loss, mpjpe, found = head.train_step(feats, joints3d, optim, scaler, masks=masks)
+        running_loss += loss
+        running_mpjpe += mpjpe
+        n_batches += 1
+        skipped += int(found)
+        if log_every > 0 and (it + 1) % log_every == 0:
+            print(f"[3D]  iter {it + 1:05d}/{len(sampler):05d} | loss {running_loss / n_batches:.6f} | mpjpe {running_mpjpe / n_batches:.3f}")
+    return running_loss / max(n_batches, 1), running_mpjpe / max(n_batches, 1), n_batches - skipped, skipped
+
+
+def save_checkpoint(path: str, head: TrainableHead, optim: AdamW, epoch: int, best_val: float, args) -> None:
+    """src/train.py:61-76: {"epoch", "best_val", "model" (the reference's state-dict keys), "optim" (torch.optim.AdamW's
+    layout), "args"}.  Tensors, numbers, strings and lists only: it loads with ``torch.load(weights_only=True)``."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save({"epoch": epoch, "best_val": best_val, "model": head.state_dict(), "optim": optim.state_dict(),
+                "args": dict(vars(args)) if isinstance(args, argparse.Namespace) else dict(args)}, path)
+
+
+def load_checkpoint(path: str, head: TrainableHead, optim: AdamW) -> dict:
+    """Load a checkpoint of ``save_checkpoint`` (or of the reference) into ``head`` and ``optim``; returns the whole dict."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    head.load_state_dict(ckpt["model"], strict=True)
+    optim.load_state_dict(ckpt["optim"])
+    return ckpt
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """The reference's flags and defaults (src/train.py:283-299, src/config.py), then this project's extras."""
+    p = argparse.ArgumentParser("Phase-1 training: freeze ResNet, train f_movie + f_3D (3D joints + 2D reprojection)")
+    p.add_argument("--train", type=str, default=H36M_ROOT)
+    p.add_argument("--val", type=str, default=H36M_ROOT)
+    p.add_argument("--seq-len", type=int, default=SEQ_LEN, help="accepted, no effect (as in the reference)")
+    p.add_argument("--batch-size", type=int, default=BATCH_SIZE)
+    p.add_argument("--lr", type=float, default=LR)
+    p.add_argument("--epochs", type=int, default=EPOCHS)
+    p.add_argument("--num-workers", type=int, default=2, help="accepted, no effect: batches come from HBM")
+    p.add_argument("--lambda-2d", type=float, default=1e-6, help="2D reprojection loss weight (accepted, no effect, as in the reference)")
+    p.add_argument("--outdir", type=str, default="./runs/phase1")
+    p.add_argument("--resume", type=str, default=None)
+    p.add_argument("--log-every", type=int, default=500)
+    p.add_argument("--early-stop-patience", type=int, default=10,
+                   help="Stop if val MPJPE doesn't improve for this many epochs (0 disables).")
+    p.add_argument("--early-stop-min-delta", type=float, default=0.0, help="Minimum MPJPE improvement to reset patience.")
+    p.add_argument("--precision", choices=("fp16", "bf16"), default="fp16", help="16-bit type of the head's GEMMs")
+    p.add_argument("--seed", type=int, default=0, help="seeds the initial weights and the dropout masks")
+    p.add_argument("--train-subjects", type=int, nargs="+", default=list(TRAIN_SUBJECTS))
+    p.add_argument("--val-subjects", type=int, nargs="+", default=list(VAL_SUBJECTS))
+    return p
+
+
+def main(argv: Optional[List[str]] = None) -> float:
+    """``python src/train.py`` (src/train.py:283-465) on one MI355X.  Per epoch, in the reference's order: train, evaluate,
+    scheduler step, ``last.pt``, ``best.pt`` when val MPJPE improved by more than ``--early-stop-min-delta``, patience counter.
+    ``--resume`` loads model and optimizer (a missing file is ignored; GradScaler state is not saved), as the reference does.
+    Also prints one JSON line per epoch.  Returns the best val MPJPE."""
+    from .feature_store import DeviceFeatureStore
+    from .samplers import MixedShardBatchSampler
+
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    os.makedirs(args.outdir, exist_ok=True)
+    train_set = DeviceFeatureStore(args.train, subjects=args.train_subjects, augment=True, device=device)
+    val_set = DeviceFeatureStore(args.val, subjects=args.val_subjects, device=device)
+    sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
+
+    head = TrainableHead(1024, JOINTS_NUM, 2, precision=args.precision)
+    head.load_state_dict(default_state_dict(1024, JOINTS_NUM, 2, seed=args.seed))
+    head.to(device)
+    optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
+    scaler = GradScaler()
+    schedule = CosineLR(args.lr, args.epochs)
+
+    start_epoch, best_val, no_improve_epochs = 0, float("inf"), 0
+    if args.resume and os.path.isfile(args.resume):
+        ckpt = load_checkpoint(args.resume, head, optim)
+        schedule.load_group(ckpt["optim"])
+        start_epoch = int(ckpt.get("epoch", 0)) + 1
+        best_val = float(ckpt.get("best_val", best_val))
+        print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
+
+    print("===== Phase-1 training =====")
+    print(f"Device: {device} ({args.precision})")
+    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
+    print(f"Batch size: {args.batch_size} | LR: {args.lr} | seed: {args.seed}")
+    print("============================")
+    for epoch in range(start_epoch, args.epochs):
+        sampler.set_epoch(epoch)
+        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
+        print(f"\nEpoch {epoch + 1}/{args.epochs}")
+        t0 = time.time()
+        epoch_lr = optim.lr
+        tr_loss, tr_mpjpe, steps, skipped = train_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every)
+        va_loss, va_mpjpe, va_l3d, va_l2d = evaluate(head, val_set, args.batch_size)
+        schedule.step()
+        optim.lr = schedule.lr            # the saved optimizer state carries the scheduler's next LR, as torch's does
+        print(f"Train: loss={tr_loss:.6f} | mpjpe={tr_mpjpe:.3f}")
+        print(f"Val:   loss={va_loss:.6f} (3d {va_l3d:.6f} + {args.lambda_2d:.3g}*2d {va_l2d:.6f}) | mpjpe={va_mpjpe:.3f}")
+        print(f"Epoch time: {time.time() - t0:.2f}s")
+        print(json.dumps({"epoch": epoch, "lr": epoch_lr, "train_loss": tr_loss, "train_mpjpe": tr_mpjpe, "steps": steps,
+                          "skipped": skipped, "val_loss": va_loss, "val_mpjpe": va_mpjpe}))
+
+        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
+        if (best_val - va_mpjpe) > args.early_stop_min_delta:
+            best_val = va_mpjpe
+            no_improve_epochs = 0
+            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
+            print(f"New best val MPJPE: {best_val:.3f} (saved best.pt)")
+        else:
+            no_improve_epochs += 1
+            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
+                  f"(best {best_val:.3f}, current {va_mpjpe:.3f})")
+        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
+            print(f"Early stopping triggered at epoch {epoch + 1}. Best val MPJPE: {best_val:.3f}")
+            break
+    print("\nDone.")
+    print(f"Best val MPJPE: {best_val:.3f}")
+    return best_val
+
+
+if __name__ == "__main__":
+    main()

@@ -322,6 +322,12 @@ int r50_op_check_overflow16(const void* x, int64_t n, int* found, int et, void* 
 int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, const int* found_inf, int et, void* stream);
 
+/* Lifting head, evaluation (`evaluate()`, src/train.py:219-280): pred, gt (rows, joints, 3) fp32 -> acc[0] += mean((pred-gt)^2)
+ * (l3d, :259), acc[1] += mean over the rows*joints joints of |pred-gt|_2 (MPJPE, :42-45), acc[2] += 1; acc: 3 doubles of device
+ * memory, so the mean over per-batch means is acc[0..1] / acc[2].  fp32 per joint, fp64 sums in a fixed order (no atomics: the
+ * same bits on every run).  One launch of one workgroup, sized for up to ~1e5 joints per batch. */
+int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int joints, double* acc, void* stream);
+
 /* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
 int r50_op_avgpool(const void* x_nhwc_bf16, int n, int hw, int c, float* y_f32, void* stream);
 
