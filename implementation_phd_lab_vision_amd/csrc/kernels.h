@@ -3852,6 +3852,52 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const ResizeArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
+// Whole-frame resize of the results dump (src/results.py:65-116): `_pad_or_trim_video` of `frames[::skip][start:end]`
+// as an index map into the uploaded frames, then `_resize_video_hw` = (F.interpolate(u8 / 255, bilinear,
+// align_corners=False).clamp(0, 1) * 255).byte() with C = 3.  ATen runs that through its generic separable CPU loop
+// (horizontal taps inside, vertical outside; GCC contracts each two-term sum into one FMA), so this kernel evaluates
+// fma(ly0, fma(lx0, p00, lx1 * p01), ly1 * fma(lx0, p10, lx1 * p11)) with explicit roundings.  Taps: resize_taps float
+// mode (the fma source index of area_pixel_compute_source_index, identity when in == out).  The result truncates.
+// One workgroup = one output row of one frame; the two full-width source rows are staged in LDS as bytes.
+// Output is HWC uint8, (t, out, out, 3) contiguous.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void resize_frames_u8_kernel(const unsigned char* __restrict__ src, const int* __restrict__ src_idx,
+                                                               int H, int W, int out, unsigned char* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
+    const int t = blockIdx.x / out, yo = blockIdx.x - t * out;
+    int y0, wy0, wy1;
+    resize_taps(yo, H, out, 1, true, y0, wy0, wy1);
+    const int y1 = y0 + (y0 < H - 1 ? 1 : 0);
+    const int row_bytes = W * 3;
+    const unsigned char* f = src + (size_t)src_idx[t] * H * row_bytes;       // the host checked every index against n
+    const unsigned char* g0 = f + (size_t)y0 * row_bytes;
+    const unsigned char* g1 = f + (size_t)y1 * row_bytes;
+    unsigned char* r0 = rf_smem;
+    unsigned char* r1 = rf_smem + row_bytes;
+    for (int i = threadIdx.x; i < row_bytes; i += 256) {
+        r0[i] = g0[i];
+        r1[i] = g1[i];
+    }
+    __syncthreads();
+    const float ly0 = __int_as_float(wy0), ly1 = __int_as_float(wy1);
+    unsigned char* d = dst + ((size_t)t * out + yo) * (size_t)out * 3;
+    for (int item = threadIdx.x; item < out * 3; item += 256) {
+        const int xo = item / 3, c = item - xo * 3;
+        int x0, wx0, wx1;
+        resize_taps(xo, W, out, 1, true, x0, wx0, wx1);
+        const int x1 = x0 + (x0 < W - 1 ? 1 : 0);
+        const float lx0 = __int_as_float(wx0), lx1 = __int_as_float(wx1);
+        const float p00 = __fdiv_rn((float)r0[x0 * 3 + c], 255.0f), p01 = __fdiv_rn((float)r0[x1 * 3 + c], 255.0f);
+        const float p10 = __fdiv_rn((float)r1[x0 * 3 + c], 255.0f), p11 = __fdiv_rn((float)r1[x1 * 3 + c], 255.0f);
+        const float h0 = __fmaf_rn(lx0, p00, __fmul_rn(lx1, p01));
+        const float h1 = __fmaf_rn(lx0, p10, __fmul_rn(lx1, p11));
+        float v = __fmaf_rn(ly0, h0, __fmul_rn(ly1, h1));
+        v = fminf(fmaxf(v, 0.0f), 1.0f);
+        d[item] = (unsigned char)(int)__fmul_rn(v, 255.0f);                 // Tensor.byte(): truncation toward zero
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Lifting head (forward only): the non-GEMM pieces of PHDFor3DJoints.forward (src/model.py).  Every
 // Linear and causal conv1d of the head runs on the igemm kernels as a 1x1 convolution over the B*T "pixels":
 // a causal conv1d with kernel 3 and replicate left padding (:20-35) is a GEMM with K = 3*C against the row

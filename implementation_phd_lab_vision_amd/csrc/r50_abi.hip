@@ -2233,6 +2233,30 @@ int r50_op_crop_resize_u8(const void* frames, int t, int h, int w, int top, int 
     return R50_OK;
 }
 
+int r50_op_resize_frames_u8(const void* frames, int n, int h, int w, const int* src_idx, int t, void* out, int out_size, void* stream) {
+    if (!frames || !src_idx || !out || n < 1 || h < 1 || w < 1 || t < 1 || out_size < 1 || out_size > 16384 ||
+        (long long)n * h * w * 3 >= (1ll << 40) || (long long)t * out_size >= (1ll << 31))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_resize_frames_u8: invalid arguments");
+    const size_t lds = 2 * (size_t)w * 3;                               // the two full-width source rows
+    if (lds > 160 * 1024) return fail(nullptr, R50_ERR_INVALID, "r50_op_resize_frames_u8: frames too wide");
+    // the map lives on the device: read it back once (t ints, one stream synchronisation) so no index can reach past the frames
+    std::vector<int> idx((size_t)t);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(nullptr, hipMemcpyAsync(idx.data(), src_idx, (size_t)t * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(nullptr, hipStreamSynchronize(s));
+    for (int i = 0; i < t; ++i)
+        if (idx[i] < 0 || idx[i] >= n)
+            return fail(nullptr, R50_ERR_INVALID, "r50_op_resize_frames_u8: src_idx[" + std::to_string(i) + "] = " +
+                                                      std::to_string(idx[i]) + " is outside [0, " + std::to_string(n) + ")");
+    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(resize_frames_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_resize_frames_u8: ") + hipGetErrorString(ea));
+    hipLaunchKernelGGL(resize_frames_u8_kernel, dim3((unsigned)(t * out_size)), dim3(256), lds, s, (const unsigned char*)frames, src_idx,
+                       h, w, out_size, (unsigned char*)out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_resize_frames_u8: ") + hipGetErrorString(e));
+    return R50_OK;
+}
+
 // ---- lifting head pieces (kernels.h: cast_rows_kernel, concat_pad_kernel, gn_relu_causal3_kernel); et: 0 = bf16, 1 = fp16
 int r50_op_cast_rows(const float* src, int64_t rows, int c, void* dst, int cpad, int et, void* stream) {
     if (!src || !dst || rows < 1 || c < 1 || cpad < c || (cpad & 1) || (et != 0 && et != 1))

@@ -1,0 +1,228 @@
+"""Test-subject results of a trained lifting head on one MI355X: ``python -m implementation_phd_lab_vision_amd.results``, the
+counterpart of ``python src/results.py`` (src/results.py:137-239).
+
+It scores a checkpoint on the test subject (S9) with ``train.evaluate`` over the reference's shuffled test loader
+(``shuffle=True, drop_last=True``, :162-170), prints the reference's metrics line, and dumps ONE batch to an ``.npz`` for the
+visualisation scripts: the clips' video, ground-truth and predicted 3D joints, 2D joints, intrinsics, meta and the test metrics.
+
+Two differences from running the reference's script as it stands:
+
+* the head's dimensions come from the checkpoint (``infer_head_dims``): the reference builds ``PHD(joints_num=17)`` with its
+  default dims (latent 2048, 3 blocks, :175), so its strict ``load_state_dict`` fails on the ``PHD(1024, 17, 2)`` checkpoints
+  its own src/train.py writes (:370).  Here both load.
+* frame selection.  Shard metas carry no ``frame_skip``, so the reference's ``frames[::meta.get("frame_skip", 1)][start:end]``
+  (:101-105) slices the full-rate video with clip indices that count every ``frame_skip``-th frame: the video it dumps covers
+  another, shorter span than the clip's joints.  That stays the default, kept on purpose and documented (INTEGRATION.md,
+  section H); ``--aligned-video`` takes the clip's own frames, ``[::index.pt frame_skip][start:end]``.
+
+Video decode stays on the host (``--video-reader``, torchvision's ``read_video`` by default, as the reference).  The frames a
+clip names are uploaded once and ``_pad_or_trim_video`` + ``_resize_video_hw`` (:65-93) are one ``r50_op_resize_frames_u8``
+launch per clip into the batch buffer.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import importlib
+import os
+import time
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+SEQ_LEN = 40                              # src/config.py
+TEST_SUBJECTS = [9]                       # hard-coded at src/results.py:159
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """The reference's flags and defaults (src/results.py:138-150), then this project's extras."""
+    p = argparse.ArgumentParser("Test Subject 9 + dump ONE BATCH to NPZ")
+    p.add_argument("--features_root", type=str, required=True)
+    p.add_argument("--preprocessed_root", type=str, required=True)
+    p.add_argument("--seq-len", type=int, default=SEQ_LEN)
+    p.add_argument("--batch-size", type=int, default=16)
+    p.add_argument("--num-workers", type=int, default=4, help="accepted, no effect: the feature store is resident in HBM")
+    p.add_argument("--model_path", type=str, required=True)
+    p.add_argument("--out", type=str, default="outputs/batch_result_S9.npz")
+    p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--save-n", type=int, default=16, help="How many samples from the batch to save")
+    p.add_argument("--video-size", type=int, default=224,
+                   help="Resize saved videos to video_size x video_size before stacking (use 0 to disable).")
+    p.add_argument("--seed", type=int, default=0, help="torch.manual_seed before the test loader draws its two orders")
+    p.add_argument("--precision", choices=("fp16", "bf16"), default="fp16", help="16-bit type of the head's GEMMs")
+    p.add_argument("--test-subjects", type=int, nargs="+", default=list(TEST_SUBJECTS))
+    p.add_argument("--aligned-video", action="store_true",
+                   help="dump the clip's own frames, [::index.pt frame_skip][start:end] (default: the reference's "
+                        "[::meta.get('frame_skip', 1)][start:end])")
+    p.add_argument("--video-reader", type=str, default=None,
+                   help="module:function, a callable path -> (N,H,W,3) uint8 (default: torchvision.io.read_video(path, pts_unit='sec')[0])")
+    return p
+
+
+# ---- host pieces ------------------------------------------------------------------------------------------------------------
+def find_video_path(preprocessed_root: str, meta: dict) -> str:
+    """``_find_video_path`` (src/results.py:31-42): the first of the sorted ``*.mp4`` under ``S{subject}/{action}/cam_{cam}``."""
+    cam = str(meta["cam"])
+    if not cam.startswith("cam_"):
+        cam = f"cam_{cam}"
+    cam_dir = os.path.join(preprocessed_root, f"S{int(meta['subject'])}", str(meta["action"]), cam)
+    mp4s = sorted(glob.glob(os.path.join(cam_dir, "*.mp4")))
+    if not mp4s:
+        raise FileNotFoundError(f"No mp4 found under {cam_dir}")
+    return mp4s[0]
+
+
+def frame_index_map(n_frames: int, start: int, end: int, frame_skip: int, seq_len: int) -> List[int]:
+    """Indices into the decoded video of the ``seq_len`` frames the reference dumps: ``frames[::frame_skip][start:end]``
+    (src/results.py:103-105), then ``_pad_or_trim_video`` (:65-79: trim, or repeat the last frame).  RuntimeError when the
+    selection is empty, as the reference raises (:107-110)."""
+    sel = list(range(n_frames))[::frame_skip][start:end]
+    if not sel:
+        raise RuntimeError(f"Loaded 0 frames with start={start}, end={end}, frame_skip={frame_skip} from a video of {n_frames} frames")
+    return sel[:seq_len] + [sel[-1]] * max(seq_len - len(sel), 0)
+
+
+def infer_head_dims(state: Dict[str, torch.Tensor]) -> Tuple[int, int, int]:
+    """(latent_dim, joints_num, number_blocks) of a reference-layout state dict: ``input_proj.weight`` is (latent_dim, 2048),
+    ``f_3D.y0`` holds joints_num * 3 values, ``f_movie.blocks.<i>.*`` counts the blocks."""
+    latent_dim = int(state["input_proj.weight"].shape[0])
+    joints_num = int(state["f_3D.y0"].numel()) // 3
+    blocks = {int(k.split(".")[2]) for k in state if k.startswith("f_movie.blocks.")}
+    return latent_dim, joints_num, (max(blocks) + 1 if blocks else 0)
+
+
+def load_head_state(path: str) -> Dict[str, torch.Tensor]:
+    """The state dict of a checkpoint: ``ckpt["model"]`` of a training checkpoint (``train.save_checkpoint``, src/train.py:61-76),
+    or the file itself when it is a plain state dict (src/results.py:181-182).  ``weights_only=True``."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    return ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
+
+
+def build_head(state: Dict[str, torch.Tensor], device, precision: str = "fp16"):
+    """A ``model.PHDFor3DJoints`` with the checkpoint's own dimensions, loaded strictly, on ``device``, in eval mode."""
+    from .model import PHDFor3DJoints
+    latent_dim, joints_num, number_blocks = infer_head_dims(state)
+    head = PHDFor3DJoints(latent_dim, joints_num, number_blocks, precision=precision)
+    head.load_state_dict(state, strict=True)
+    return head.to(device).eval()
+
+
+def loader_batch_order(n: int, batch_size: int, seed: int) -> Tuple[List[List[int]], List[int]]:
+    """The reference's test loader over ``n`` items (``DataLoader(test_set, batch_size, shuffle=True, drop_last=True)``,
+    src/results.py:162-170), drawn by torch's own DataLoader after ``torch.manual_seed(seed)``: the batches of one full pass
+    (the evaluation, :190) and the first batch of a second iterator (the dump, :197).  Each iterator draws a base seed and then
+    its sampler's seed from the global generator, as the reference's loader does; worker processes do not change that."""
+    from torch.utils.data import DataLoader
+    torch.manual_seed(seed)
+    loader = DataLoader(range(n), batch_size=batch_size, shuffle=True, drop_last=True)
+    eval_batches = [b.tolist() for b in loader]
+    return eval_batches, next(iter(loader)).tolist()
+
+
+def resolve_video_reader(spec: Optional[str]) -> Callable:
+    """``--video-reader``: ``module:function``, or None for ``torchvision.io.read_video(path, pts_unit="sec")[0]`` (:101).
+    Raises SystemExit with a message when it cannot be imported."""
+    if spec is None:
+        try:
+            tv_io = importlib.import_module("torchvision.io")
+        except ImportError as e:
+            raise SystemExit(f"results: the default video reader needs torchvision ({e}); install it or pass "
+                             "--video-reader module:function") from None
+        return lambda path: tv_io.read_video(path, pts_unit="sec")[0]
+    mod, sep, fn = spec.partition(":")
+    if not sep or not mod or not fn:
+        raise SystemExit(f"results: --video-reader must be module:function, got {spec!r}")
+    try:
+        reader = getattr(importlib.import_module(mod), fn)
+    except (ImportError, AttributeError) as e:
+        raise SystemExit(f"results: cannot load --video-reader {spec!r}: {e}") from None
+    if not callable(reader):
+        raise SystemExit(f"results: --video-reader {spec!r} is not callable")
+    return reader
+
+
+def dump_videos(metas: Sequence[dict], preprocessed_root: str, reader: Callable, seq_len: int, video_size: int,
+                frame_skip_of: Callable[[dict], int], device) -> np.ndarray:
+    """(B, seq_len, H, W, 3) uint8: per clip, decode on the host, select (``frame_index_map``), then one
+    ``r50_op_resize_frames_u8`` launch into the batch buffer; ``video_size == 0`` keeps the decoded size (host pad / trim only)."""
+    from .frames import resize_frames_uint8
+    host_clips, buf = [], None
+    if video_size > 0:
+        buf = torch.empty((len(metas), seq_len, video_size, video_size, 3), dtype=torch.uint8, device=device)
+    for b, meta in enumerate(metas):
+        if not isinstance(meta, dict):
+            raise RuntimeError(f"Expected meta[{b}] to be dict, got {type(meta)}")
+        path = find_video_path(preprocessed_root, meta)
+        frames = torch.as_tensor(reader(path))
+        if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+            raise RuntimeError(f"video reader returned {tuple(frames.shape)} {frames.dtype} for {path}; expected (N,H,W,3) uint8")
+        sel = frame_index_map(frames.shape[0], int(meta["start"]), int(meta["end"]), frame_skip_of(meta), seq_len)
+        if buf is None:
+            host_clips.append(frames[sel].numpy())
+            continue
+        used = sorted(set(sel))                                   # upload only the frames the map names, once each
+        pos = {f: i for i, f in enumerate(used)}
+        clip = frames[used].contiguous().to(device)
+        resize_frames_uint8(clip, [pos[f] for f in sel], video_size, out=buf[b])
+    if buf is not None:
+        return buf.cpu().numpy()
+    if len({c.shape for c in host_clips}) > 1:
+        raise RuntimeError(f"--video-size 0 keeps each video's own frame size, and this batch mixes "
+                           f"{sorted({c.shape[1:3] for c in host_clips})}: pass --video-size > 0")
+    return np.stack(host_clips, axis=0)
+
+
+def main(argv: Optional[List[str]] = None) -> str:
+    """``python src/results.py`` on one MI355X.  Returns the path of the written ``.npz``."""
+    from .feature_store import DeviceFeatureStore
+    from .train import evaluate
+
+    args = build_parser().parse_args(argv)
+    reader = resolve_video_reader(args.video_reader)             # before the evaluation pass: fail early
+    device = torch.device(args.device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.R50Error("the results pass runs on an MI355X only; there is no CPU fallback")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t0 = time.time()
+    test_set = DeviceFeatureStore(args.features_root, subjects=args.test_subjects, test_set=True, device=device)
+    if len(test_set) < args.batch_size:
+        raise SystemExit(f"results: the test set has {len(test_set)} clips, fewer than one batch of {args.batch_size} "
+                         "(the loader drops the last incomplete batch); lower --batch-size")
+    index_skip = int(torch.load(os.path.join(args.features_root, "index.pt"), map_location="cpu", weights_only=True).get("frame_skip", 1))
+    head = build_head(load_head_state(args.model_path), device, args.precision)
+    print(f"Head: latent_dim={head.latent_dim} joints={head.joints_num} blocks={head.number_blocks} ({args.precision}) | "
+          f"test clips: {len(test_set)}")
+
+    eval_batches, dump_idx = loader_batch_order(len(test_set), args.batch_size, args.seed)
+    avg_loss, avg_mpjpe, avg_l3d, avg_l2d = evaluate(head, test_set, args.batch_size, test_set=True, batches=eval_batches)
+    print(f"Test metrics | loss: {avg_loss:.6f} | mpjpe (m): {avg_mpjpe:.6f} "
+          f"| mpjpe (mm): {avg_mpjpe * 1000.0:.2f} | l3d: {avg_l3d:.6f} | l2d: {avg_l2d:.6f}")
+
+    feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
+    n_save = min(feats.shape[0], args.save_n)
+    pred = head.joints(feats)[:n_save].cpu().numpy()
+    if args.aligned_video:
+        frame_skip_of = lambda meta: index_skip                   # noqa: E731
+    else:
+        frame_skip_of = lambda meta: int(meta.get("frame_skip", 1))   # noqa: E731  (the reference's behaviour, kept on purpose)
+    videos = dump_videos(metas[:n_save], args.preprocessed_root, reader, args.seq_len, args.video_size, frame_skip_of, device)
+    joints3d_np = joints3d[:n_save].cpu().numpy()
+
+    out_path = args.out
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    np.savez_compressed(out_path, video=videos, joints3d=joints3d_np, predicted3djoints=pred,
+                        joints2d=joints2d[:n_save].cpu().numpy(), K=k[:n_save].to(torch.float32).cpu().numpy(),
+                        meta=np.array(list(metas[:n_save]), dtype=object),
+                        test_metrics=np.array([avg_loss, avg_mpjpe, avg_l3d, avg_l2d], dtype=np.float32))
+    print(f"[OK] Saved batch to: {out_path}")
+    print(f"video shape: {videos.shape} | joints3d: {joints3d_np.shape} | pred: {pred.shape}")
+    print(f"Results time: {time.time() - t0:.2f}s")
+    return out_path
+
+
+if __name__ == "__main__":
+    main()

@@ -646,13 +646,17 @@ class CosineLR:
 
 
 @torch.no_grad()
-def evaluate(head: PHDFor3DJoints, store, batch_size: int, test_set: bool = False) -> Tuple[float, float, float, float]:
+def evaluate(head: PHDFor3DJoints, store, batch_size: int, test_set: bool = False, batches=None) -> Tuple[float, float, float, float]:
     """src/train.py:219-280: (loss, mpjpe, l3d, 0.0), each the mean over batches of the per-batch mean.  The items of ``store``
     in order, ``batch_size`` at a time, the last batch kept even if short (the reference's val loader: shuffle=False,
     drop_last=False).  The head runs in eval mode through ``joints()`` (no f_AR); one ``r50_op_pose_metrics`` launch per batch
     adds into a device accumulator, read once at the end.  The head's mode is restored; its weights are not touched.
-    ``test_set``: the store yields the meta list as a fifth field (ignored here), as the reference's flag says."""
+    ``test_set``: the store yields the meta list as a fifth field (ignored here), as the reference's flag says.
+    ``batches``: an iterable of index lists to evaluate instead, in its order (e.g. the reference's shuffled test loader,
+    src/results.py:162-170); ``batch_size`` is then unused."""
     del test_set                      # only changes the batch tuple's length in the reference; get_batch's first two fields serve
+    if batches is None:
+        batches = (list(range(s, min(s + batch_size, len(store)))) for s in range(0, len(store), batch_size))
     was_training = head.training
     head.train(False)
     lib = _lib.load_library()
@@ -660,8 +664,8 @@ def evaluate(head: PHDFor3DJoints, store, batch_size: int, test_set: bool = Fals
     try:
         with torch.cuda.device(dev):
             acc = torch.zeros(3, dtype=torch.float64, device=dev)
-            for s in range(0, len(store), batch_size):
-                batch = store.get_batch(list(range(s, min(s + batch_size, len(store)))))
+            for idx in batches:
+                batch = store.get_batch(idx)
                 pred = head.joints(batch[0])
                 gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
                 rows = pred.shape[0] * pred.shape[1]

@@ -267,6 +267,16 @@ int r50_op_bneck_block1(const void* t1_bf16, int n, const void* w2_bf16, const f
 int r50_op_crop_resize_u8(const void* frames_thwc_u8, int t, int h, int w, int top, int left, int hh, int ww,
                           void* out_tchw_u8, int out_size, int mode, int flags, void* stream);
 
+/* Results dump (`src/results.py`): whole-frame resize of one clip's video.  frames (n,h,w,3) uint8 HWC on the device, the decoded
+ * frames the clip names; src_idx (t) int32 on the device, output frame i = frames[src_idx[i]] (the host folds `[::skip][start:end]`
+ * and `_pad_or_trim_video`'s repeat-the-last-frame padding into the map, :65-79,96-116) -> out (t,out_size,out_size,3) uint8 HWC,
+ * contiguous (may be one clip's slice of a (B,t,out_size,out_size,3) buffer).  Arithmetic of `_resize_video_hw` (:81-93): fp32
+ * u8 / 255 (IEEE division), bilinear with align_corners=False and no antialias as F.interpolate's CPU path evaluates it for 3
+ * channels, clamp(0,1) * 255, truncated to uint8 (not rounded: unlike both R50_RESIZE_* modes).  Any out_size >= 1.  src_idx is
+ * read back once to check every index lies in [0,n) (R50_ERR_INVALID otherwise): the call synchronises `stream` once. */
+int r50_op_resize_frames_u8(const void* frames_nhwc_u8, int n, int h, int w, const int* src_idx, int t, void* out_tssc_u8,
+                            int out_size, void* stream);
+
 /* ColorJitter augmentation variant: `_aug_color_jitter` (src/dataset.py:188-197) = torchvision.transforms.v2
  * ColorJitter(brightness=0.3, contrast=0.3, saturation=0.2, hue=0.05) on the float clip in [0,1], followed (normalize != 0) by
  * `frame_tf` = Normalize(ImageNet mean, std) (:242-245).  frames_u8: (t,3,hw) uint8 resized crops on the device (the output of
