@@ -4217,6 +4217,108 @@ __global__ __launch_bounds__(1024) void pose_metrics_kernel(const float* __restr
     }
 }
 
+// ---- Phase 2: training f_AR (DESIGN.md "f next #2") ----------------------------------------------------
+// Future-pose loss of the phase-2 step: l3d_hat = mean over frames s >= 1 of (y_hat - gt)^2.  Frame 0 has no prediction (phi_hat[:, 0]
+// is the constant 0), so dy = 0 there and dy = 2 (y_hat - gt) / n * loss_scale elsewhere, n = b*(t-1)*joints*3 (the arithmetic of
+// mse_loss_grad_kernel); loss[0] = l3d_hat, loss[1] = MPJPE over the same frames.  y, gt, dy: (b*t, joints, 3) fp32.  Per joint fp32,
+// per-thread fp64 partials over a fixed strided slice, then a fixed fp64 tree (pose_metrics_kernel's pattern): the same bits on every
+// run, no atomics.  ONE workgroup of 1024: a batch is ~2e4 joints (32 x 40 x 17), the launch is latency-bound.
+__global__ __launch_bounds__(1024) void future_pose_loss_grad_kernel(const float* __restrict__ y, const float* __restrict__ gt, long long rows,
+                                                                     int t, int joints, float loss_scale, float* __restrict__ dy,
+                                                                     float* __restrict__ loss) {
+    __shared__ double red[2][1024];
+    const long long nj = rows * joints;
+    const long long npred = (rows / t) * (t - 1) * joints;               // joints with a prediction
+    const float n = (float)(3 * npred);
+    double s = 0.0, e = 0.0;
+    for (long long j = threadIdx.x; j < nj; j += 1024) {
+        const long long r = j / joints;
+        if (r % t == 0) {
+            dy[3 * j] = 0.f; dy[3 * j + 1] = 0.f; dy[3 * j + 2] = 0.f;
+            continue;
+        }
+        float d2 = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const float d = y[3 * j + k] - gt[3 * j + k];
+            dy[3 * j + k] = 2.f * d / n * loss_scale;
+            d2 += d * d;
+        }
+        s += (double)d2;
+        e += (double)sqrtf(d2);
+    }
+    red[0][threadIdx.x] = s; red[1][threadIdx.x] = e;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = (float)(red[0][0] / (3.0 * (double)npred));
+        loss[1] = (float)(red[1][0] / (double)npred);
+    }
+}
+
+// Latent loss + f_AR's output gradient, one pass over ar (b*t, d): phi_hat[b, s+1] = ar[b, s] (the shift, src/model.py:159-160), so
+//   dar[b, s]   = cast16(dphi_hat[b, s+1] + coef * (ar[b, s] - phi[b, s+1])),  s <= t-2,   coef = lambda * 2 / n_l * loss_scale
+//   dar[b, t-1] = 0                                                              (ar's last frame feeds nothing)
+//   part[row]   = sum over d of (ar[b, s] - phi[b, s+1])^2  (0 on s = t-1)
+// i.e. the backward of the shift, the gradient of lambda * mean((phi_hat[:, 1:] - phi[:, 1:])^2) and the cast to the 16-bit arena
+// together.  ar, phi, dar: et elements; dphi_hat fp32 (the regressor's dX accumulated in fp32).  One workgroup of 128 (two waves) per
+// row, 8 elements per lane per iteration: 16-byte loads of ar / phi / dar, two 16-byte loads of dphi_hat; d % 8 == 0, rows 16-byte
+// aligned.  The row sum is a fixed wave64 butterfly then the two waves in order; sum_parts_kernel adds the rows in a fixed order.
+template <int ET>
+__global__ __launch_bounds__(128) void ar_latent_grad_kernel(const unsigned short* __restrict__ ar, const unsigned short* __restrict__ phi,
+                                                             const float* __restrict__ dphi_hat, int t, int d, float coef,
+                                                             unsigned short* __restrict__ dar, float* __restrict__ part) {
+    __shared__ float red[2];
+    const long long r = blockIdx.x;
+    const int s = (int)(r % t), nv = d >> 3;
+    u32x4* out = reinterpret_cast<u32x4*>(dar + r * d);
+    if (s == t - 1) {                                                      // uniform over the workgroup
+        for (int v = threadIdx.x; v < nv; v += 128) out[v] = (u32x4){0u, 0u, 0u, 0u};
+        if (threadIdx.x == 0) part[r] = 0.f;
+        return;
+    }
+    const u32x4* a = reinterpret_cast<const u32x4*>(ar + r * d);
+    const u32x4* p = reinterpret_cast<const u32x4*>(phi + (r + 1) * d);
+    const f32x4* g = reinterpret_cast<const f32x4*>(dphi_hat + (r + 1) * d);
+    float ss = 0.f;
+    for (int v = threadIdx.x; v < nv; v += 128) {
+        const u32x4 av = a[v], pv = p[v];
+        const f32x4 g0 = g[2 * v], g1 = g[2 * v + 1];
+        const float gg[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
+        unsigned o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float dl = unpack_lo_e<ET>(av[k]) - unpack_lo_e<ET>(pv[k]);
+            const float dh = unpack_hi_e<ET>(av[k]) - unpack_hi_e<ET>(pv[k]);
+            ss += dl * dl;
+            ss += dh * dh;
+            o[k] = pack2_e<ET>(gg[2 * k] + coef * dl, gg[2 * k + 1] + coef * dh);
+        }
+        out[v] = (u32x4){o[0], o[1], o[2], o[3]};
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) part[r] = red[0] + red[1];
+}
+
+// out[0] = scale * sum of part (n) fp32: per-thread fp64 partials over a fixed strided slice, then a fixed fp64 tree (one workgroup)
+__global__ __launch_bounds__(1024) void sum_parts_kernel(const float* __restrict__ part, long long n, double scale, float* __restrict__ out) {
+    __shared__ double red[1024];
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 1024) s += (double)part[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
+}
+
 // Backward of gn_relu_causal3_kernel.  dr (B*T, 3C): gradient of the causal-conv input rows; x (B, T, C): the GroupNorm input
 // saved by the forward.  da(s, c) = sum of dr over the (row, tap) pairs that read frame s (replicate padding: frame 0 also
 // collects the clamped taps), dy = da * (y > 0), and with xh = (x - mean) * rstd, g = dy * gamma over the (C/groups x T) slab:

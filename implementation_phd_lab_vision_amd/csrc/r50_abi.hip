@@ -2392,6 +2392,36 @@ int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int jo
     return ew_done("r50_op_pose_metrics");
 }
 
+int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,
+                                 void* stream) {
+    if (!y_hat || !gt || !dy || !loss2 || b < 1 || t < 2 || joints < 1 || (int64_t)b * t > INT64_MAX / 3 / joints)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_future_pose_loss_grad: invalid arguments (null pointer, b < 1, t < 2 or joints < 1)");
+    hipLaunchKernelGGL(future_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, y_hat, gt, (long long)b * t, t, joints,
+                       loss_scale, dy, loss2);
+    return ew_done("r50_op_future_pose_loss_grad");
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
+                          void* dar, float* loss_lat, float* row_part, int et, void* stream) {
+    if (!ar || !phi || !dphi_hat || !dar || !loss_lat || !row_part)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: null pointer");
+    if (b < 1 || t < 2 || (int64_t)b * t > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: need b >= 1, t >= 2 (b*t within int range)");
+    if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: d must be a positive multiple of 8");
+    if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: et must be 0 (bf16) or 1 (fp16)");
+    if (!aligned16(ar) || !aligned16(phi) || !aligned16(dphi_hat) || !aligned16(dar))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: ar, phi, dphi_hat and dar must be 16-byte aligned");
+    const long long rows = (long long)b * t;
+    const double n_l = (double)b * (t - 1) * d;
+    const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
+    R50_ET_LAUNCH(ar_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)ar, (const unsigned short*)phi,
+                  dphi_hat, t, d, coef, (unsigned short*)dar, row_part);
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, rows, 1.0 / n_l, loss_lat);
+    return ew_done("r50_op_ar_latent_grad");
+}
+
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,
                                float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et, void* stream) {
     if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part || b < 1 || t < 1 || c < 1 || groups < 1 || c % groups ||

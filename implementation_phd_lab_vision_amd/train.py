@@ -110,7 +110,7 @@ class AdamW:
         """What ``torch.optim.AdamW(trainable, lr, weight_decay=1e-2).state_dict()`` of the reference holds (src/train.py:70,389):
         parameter ``i`` is ``trainable_names()[i]`` in the reference's layout, ``state[i] = {step: fp32 scalar tensor, exp_avg,
         exp_avg_sq}`` (CPU, fp32; empty before the first applied step, as torch's lazy state)."""
-        names = trainable_names(self.head.number_blocks)
+        names = self.head.trainable_parameter_names()
         state = {}
         if self.step_count > 0:
             m, v = self.head.flat_to_reference(self.exp_avg), self.head.flat_to_reference(self.exp_avg_sq)
@@ -122,10 +122,10 @@ class AdamW:
         """Inverse of ``state_dict``; accepts what torch.optim.AdamW over the reference's trainable parameters saved.  Takes the
         group's hyperparameters (lr, initial_lr, betas, eps, weight_decay) as torch does, the moments and the step, then refreshes
         the head's 16-bit weights and their transposes from its fp32 master."""
-        names = trainable_names(self.head.number_blocks)
+        names = self.head.trainable_parameter_names()
         groups = state_dict["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(names):
-            raise ValueError(f"expected one param group of {len(names)} parameters (the reference's phase-1 trainable set)")
+            raise ValueError(f"expected one param group of {len(names)} parameters (the head's trainable set)")
         g = groups[0]
         if g.get("amsgrad") or g.get("maximize"):
             raise ValueError("amsgrad / maximize AdamW states are not supported")
@@ -136,7 +136,7 @@ class AdamW:
         else:
             steps = {float(state[i]["step"]) for i in ids}
             if len(steps) != 1:
-                raise ValueError(f"the phase-1 parameters step together; found steps {sorted(steps)}")
+                raise ValueError(f"the trainable parameters step together; found steps {sorted(steps)}")
             step = int(steps.pop())
             m = self.head.flat_from_reference({n: state[i]["exp_avg"] for n, i in zip(names, ids)})
             v = self.head.flat_from_reference({n: state[i]["exp_avg_sq"] for n, i in zip(names, ids)})
@@ -209,7 +209,76 @@ class _Arena:
         return self.chunks[-1][o: o + rows * cols].view(rows, cols)
 
 
-class TrainableHead(PHDFor3DJoints):
+class _BackwardLaunches:
+    """The launches of a lifting-head backward pass, shared by the phase-1 (``TrainableHead``) and phase-2 (``train_ar.ARTrainableHead``)
+    heads.  The head provides ``flat_grad`` / ``_off`` (its flat gradient layout), ``_arena``, ``_zero_bias`` and the ``PHDFor3DJoints``
+    members (device, element type, stream, weights)."""
+
+    def grad_view(self, name: str) -> torch.Tensor:
+        o_, shape = self._off[name]
+        return self.flat_grad[o_: o_ + int(torch.Size(shape).numel())].view(shape)
+
+    # ---- launch helpers -----------------------------------------------------------------------
+    def _mm(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+        """x (R, K) @ w (N, K)^T -> (R, N), 16-bit out, fp32 accumulation, no bias: one igemm launch."""
+        rows, k = x.shape
+        n = w.shape[0]
+        assert w.shape[1] == k and x.is_contiguous() and w.is_contiguous() and k % 64 == 0 and n % 64 == 0
+        y = self._arena.take(rows, n)
+        lib = _lib.load_library()
+        fn = lib.r50_op_conv2d_f16 if self._et else lib.r50_op_conv2d
+        _lib.check(fn(x.data_ptr(), rows, 1, 1, k, w.data_ptr(), self._zero_bias.data_ptr(), None, y.data_ptr(), n, 1, 1, 0, 0, 0,
+                      self._stream()), None, "r50_op_conv2d (lifting head backward)")
+        return y
+
+    def _t(self, x: torch.Tensor) -> torch.Tensor:
+        """(R, C) -> (C, Rp) transposed, Rp = R rounded up to 64 with zero padding (the K of a dW product)."""
+        rows, cols = x.shape
+        rp = _round_up(rows, 64)
+        out = torch.zeros((cols, rp), dtype=self._dtype, device=self._device) if rp != rows else \
+            torch.empty((cols, rp), dtype=self._dtype, device=self._device)
+        _lib.check(_lib.load_library().r50_op_transpose16(x.data_ptr(), rows, cols, out.data_ptr(), rp, self._stream()), None,
+                   "r50_op_transpose16")
+        return out
+
+    def _wgrad(self, name: str, dy: torch.Tensor, x: torch.Tensor, inv_scale: float, accumulate: bool, bias: Optional[str] = None) -> None:
+        """flat_grad[name] (N, K) [+]= inv_scale * dy (R, N)^T x (R, K); flat_grad[bias] (N) [+]= inv_scale * column sums of dy."""
+        lib = _lib.load_library()
+        dw = self._mm(self._t(dy), self._t(x))                    # (N, Rp) @ (K, Rp)^T -> (N, K)
+        gv = self.grad_view(name)
+        assert tuple(dw.shape) == tuple(gv.shape)
+        _lib.check(lib.r50_op_grad_accum(dw.data_ptr(), inv_scale, gv.data_ptr(), dw.numel(), int(accumulate), self._et, self._stream()),
+                   None, "r50_op_grad_accum")
+        if bias is not None:
+            gb = self.grad_view(bias)
+            _lib.check(lib.r50_op_colsum(dy.data_ptr(), dy.shape[0], dy.shape[1], dy.shape[1], inv_scale, gb.data_ptr(), int(accumulate),
+                                         self._et, self._stream()), None, "r50_op_colsum")
+
+    def _mask_scale(self, x: torch.Tensor, mask: torch.Tensor, scale: float) -> None:
+        assert mask.dtype == torch.uint8 and mask.numel() == x.numel() and mask.is_contiguous()
+        _lib.check(_lib.load_library().r50_op_mask_scale(x.data_ptr(), mask.data_ptr(), scale, x.numel(), self._et, self._stream()), None,
+                   "r50_op_mask_scale")
+
+    def _relu_bwd(self, dy: torch.Tensor, act: torch.Tensor, scale: float) -> None:
+        _lib.check(_lib.load_library().r50_op_relu_bwd(dy.data_ptr(), act.data_ptr(), scale, dy.numel(), self._et, self._stream()), None,
+                   "r50_op_relu_bwd")
+
+    def _gn_bwd(self, dr: torch.Tensor, x: torch.Tensor, b: int, t: int, prefix: str, add: Optional[torch.Tensor], inv_scale: float) -> torch.Tensor:
+        d = self.latent_dim
+        lib = _lib.load_library()
+        dx = torch.empty((b * t, d), dtype=self._dtype, device=self._device)
+        part = torch.empty((2, b, d), dtype=torch.float32, device=self._device)
+        _lib.check(lib.r50_op_gn_relu_causal3_bwd(dr.data_ptr(), x.data_ptr(), b, t, d, _GROUPS, self._dev[prefix + ".g"].data_ptr(),
+                                                  self._dev[prefix + ".b"].data_ptr(), _GN_EPS, add.data_ptr() if add is not None else None,
+                                                  dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), self._et, self._stream()), None,
+                   "r50_op_gn_relu_causal3_bwd")
+        for j, suffix in ((0, ".g"), (1, ".b")):
+            _lib.check(lib.r50_op_colsum_f32(part[j].data_ptr(), b, d, inv_scale, self.grad_view(prefix + suffix).data_ptr(), 0,
+                                             self._stream()), None, "r50_op_colsum_f32")
+        return dx
+
+
+class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
     """``PHDFor3DJoints`` with the phase-1 trainable parameters (input_proj, f_movie, f_3D) in flat fp32 / 16-bit buffers."""
 
     def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16"):
@@ -277,9 +346,9 @@ class TrainableHead(PHDFor3DJoints):
             _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
                        "r50_op_transpose16")
 
-    def grad_view(self, name: str) -> torch.Tensor:
-        o_, shape = self._off[name]
-        return self.flat_grad[o_: o_ + int(torch.Size(shape).numel())].view(shape)
+    def trainable_parameter_names(self) -> List[str]:
+        """The names of the optimizer's parameters, in its numbering: ``trainable_names(number_blocks)``."""
+        return trainable_names(self.number_blocks)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's keys and layouts (fp32, CPU) from the flat master buffer; frozen entries as loaded."""
@@ -342,65 +411,6 @@ class TrainableHead(PHDFor3DJoints):
         """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
         self.flat_w16.copy_(self.flat_master.to(self._dtype))
         self._refresh_transposes()
-
-    # ---- launch helpers -----------------------------------------------------------------------
-    def _mm(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-        """x (R, K) @ w (N, K)^T -> (R, N), 16-bit out, fp32 accumulation, no bias: one igemm launch."""
-        rows, k = x.shape
-        n = w.shape[0]
-        assert w.shape[1] == k and x.is_contiguous() and w.is_contiguous() and k % 64 == 0 and n % 64 == 0
-        y = self._arena.take(rows, n)
-        lib = _lib.load_library()
-        fn = lib.r50_op_conv2d_f16 if self._et else lib.r50_op_conv2d
-        _lib.check(fn(x.data_ptr(), rows, 1, 1, k, w.data_ptr(), self._zero_bias.data_ptr(), None, y.data_ptr(), n, 1, 1, 0, 0, 0,
-                      self._stream()), None, "r50_op_conv2d (lifting head backward)")
-        return y
-
-    def _t(self, x: torch.Tensor) -> torch.Tensor:
-        """(R, C) -> (C, Rp) transposed, Rp = R rounded up to 64 with zero padding (the K of a dW product)."""
-        rows, cols = x.shape
-        rp = _round_up(rows, 64)
-        out = torch.zeros((cols, rp), dtype=self._dtype, device=self._device) if rp != rows else \
-            torch.empty((cols, rp), dtype=self._dtype, device=self._device)
-        _lib.check(_lib.load_library().r50_op_transpose16(x.data_ptr(), rows, cols, out.data_ptr(), rp, self._stream()), None,
-                   "r50_op_transpose16")
-        return out
-
-    def _wgrad(self, name: str, dy: torch.Tensor, x: torch.Tensor, inv_scale: float, accumulate: bool, bias: Optional[str] = None) -> None:
-        """flat_grad[name] (N, K) [+]= inv_scale * dy (R, N)^T x (R, K); flat_grad[bias] (N) [+]= inv_scale * column sums of dy."""
-        lib = _lib.load_library()
-        dw = self._mm(self._t(dy), self._t(x))                    # (N, Rp) @ (K, Rp)^T -> (N, K)
-        gv = self.grad_view(name)
-        assert tuple(dw.shape) == tuple(gv.shape)
-        _lib.check(lib.r50_op_grad_accum(dw.data_ptr(), inv_scale, gv.data_ptr(), dw.numel(), int(accumulate), self._et, self._stream()),
-                   None, "r50_op_grad_accum")
-        if bias is not None:
-            gb = self.grad_view(bias)
-            _lib.check(lib.r50_op_colsum(dy.data_ptr(), dy.shape[0], dy.shape[1], dy.shape[1], inv_scale, gb.data_ptr(), int(accumulate),
-                                         self._et, self._stream()), None, "r50_op_colsum")
-
-    def _mask_scale(self, x: torch.Tensor, mask: torch.Tensor, scale: float) -> None:
-        assert mask.dtype == torch.uint8 and mask.numel() == x.numel() and mask.is_contiguous()
-        _lib.check(_lib.load_library().r50_op_mask_scale(x.data_ptr(), mask.data_ptr(), scale, x.numel(), self._et, self._stream()), None,
-                   "r50_op_mask_scale")
-
-    def _relu_bwd(self, dy: torch.Tensor, act: torch.Tensor, scale: float) -> None:
-        _lib.check(_lib.load_library().r50_op_relu_bwd(dy.data_ptr(), act.data_ptr(), scale, dy.numel(), self._et, self._stream()), None,
-                   "r50_op_relu_bwd")
-
-    def _gn_bwd(self, dr: torch.Tensor, x: torch.Tensor, b: int, t: int, prefix: str, add: Optional[torch.Tensor], inv_scale: float) -> torch.Tensor:
-        d = self.latent_dim
-        lib = _lib.load_library()
-        dx = torch.empty((b * t, d), dtype=self._dtype, device=self._device)
-        part = torch.empty((2, b, d), dtype=torch.float32, device=self._device)
-        _lib.check(lib.r50_op_gn_relu_causal3_bwd(dr.data_ptr(), x.data_ptr(), b, t, d, _GROUPS, self._dev[prefix + ".g"].data_ptr(),
-                                                  self._dev[prefix + ".b"].data_ptr(), _GN_EPS, add.data_ptr() if add is not None else None,
-                                                  dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), self._et, self._stream()), None,
-                   "r50_op_gn_relu_causal3_bwd")
-        for j, suffix in ((0, ".g"), (1, ".b")):
-            _lib.check(lib.r50_op_colsum_f32(part[j].data_ptr(), b, d, inv_scale, self.grad_view(prefix + suffix).data_ptr(), 0,
-                                             self._stream()), None, "r50_op_colsum_f32")
-        return dx
 
     def make_dropout_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
         """Byte keep-masks (1 = keep, probability 1 - p) for the dropout sites of one step: one per f_movie block (src/model.py:52)

@@ -1,0 +1,475 @@
+"""Phase 2: training the autoregressive predictor f_AR of the lifting head on one MI355X (DESIGN.md "f next #2", INTEGRATION.md
+section I).  ``python -m implementation_phd_lab_vision_amd.train_ar``.
+
+The reference stops at phase 1: it freezes f_AR and never runs it (src/train.py:375-376), while its model computes ``phi_hat`` /
+``joints_hat`` for a later phase (src/model.py:158-166).  This project defines phase 2 as the following program, written in the
+reference's idiom (tests/golden/make_golden_train_ar.py runs it on the reference module itself)::
+
+    model = PHD(latent_dim, 17, number_blocks)                  # weights: a phase-1 checkpoint's "model"
+    for p in model.parameters(): p.requires_grad = False
+    for p in model.f_AR.parameters(): p.requires_grad = True
+    optim = torch.optim.AdamW(f_AR parameters, lr=args.lr, weight_decay=1e-2); scaler = torch.amp.GradScaler("cuda")
+    model.train(); model.f_movie.eval(); model.f_3D.eval()
+    with torch.autocast("cuda", dtype=torch.float16):
+        phi, phi_hat, _joints_phi, joints_hat = model(feats, predict_future=True)
+        l3d_hat = (joints_hat[:, 1:] - joints3d[:, 1:]).pow(2).mean()
+        l_lat   = (phi_hat[:, 1:] - phi[:, 1:].detach()).pow(2).mean()
+        loss    = l3d_hat + args.lambda_latent * l_lat
+    scaler.scale(loss).backward(); scaler.step(optim); scaler.update()
+
+Two choices are this project's, not the paper's: the frozen modules run in eval mode (the teacher ``phi`` is the one evaluation
+sees, f_3D is a fixed decoder; only f_AR's dropout is active), and frame 0 is excluded from both terms (its ``phi_hat`` is the
+constant 0, it carries no gradient).  ``--lambda-latent`` defaults to 1.0; no run has measured a good value.
+
+``ARTrainableHead`` keeps f_AR's 24 parameters in flat fp32 master / 16-bit / gradient buffers (as ``train.TrainableHead`` does for
+the phase-1 set); everything else stays as ``PHDFor3DJoints`` uploaded it.  One step, eager launches through the C ABI: input_proj
+and f_movie forward (nothing saved), f_AR forward (saved, dropout masks after each block's conv1), the ``phi_hat`` shift, the
+regressor on ``phi_hat``; ``r50_op_future_pose_loss_grad``; the regressor's backward for dX only; ``r50_op_ar_latent_grad`` (shift
+backward + latent-loss gradient + cast into the step's 16-bit arena); f_AR's backward with weight gradients (the launches of
+phase 1's f_movie backward); one overflow check over the arena; then ``all_reduce_gradients``, ``check_finite``, ``train.AdamW``,
+``train.GradScaler``.  ``joints_phi`` is not computed in the step: it does not enter the loss.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from . import _lib
+from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
+from .train import (DROPOUT_P, AdamW, CosineLR, GradScaler, _Arena, _BackwardLaunches, all_reduce_gradients, build_parser as _phase1_parser,
+                    save_checkpoint, load_checkpoint, sync_overflow_flag, train_epoch)
+
+LAMBDA_LATENT = 1.0
+
+
+def ar_trainable_names() -> List[str]:
+    """``[n for n, p in model.named_parameters() if p.requires_grad]`` with only f_AR trainable: its blocks in order, a
+    ResidualBlock registering gn1, conv1, gn2, conv2 (src/model.py:39-44).  This is the numbering of the optimizer's state."""
+    names: List[str] = []
+    for i in range(_AR_BLOCKS):
+        for m in ("gn1", "conv1.conv", "gn2", "conv2.conv"):
+            names += [f"f_AR.blocks.{i}.{m}.weight", f"f_AR.blocks.{i}.{m}.bias"]
+    return names
+
+
+class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
+    """``PHDFor3DJoints`` with f_AR trainable (phase 2) in flat fp32 / 16-bit buffers; input_proj, f_movie and f_3D frozen."""
+
+    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
+                 lambda_latent: float = LAMBDA_LATENT):
+        super().__init__(latent_dim, joints_num, number_blocks, precision)
+        self.lambda_latent = float(lambda_latent)
+        self.flat_master: Optional[torch.Tensor] = None
+        self._layout: List[Tuple[str, int, Tuple[int, ...]]] = []
+        self.last_losses: Dict[str, float] = {}
+
+    def train(self, mode: bool = True):
+        self.training = bool(mode)
+        return self
+
+    # ---- flat parameter buffers (GEMM layout) -------------------------------------------------
+    def _upload(self) -> None:
+        super()._upload()                      # every weight eval() needs; the f_AR entries are re-pointed into the flat buffers below
+        sd, dev, d = self._sd, self._device, self.latent_dim
+        items: List[Tuple[str, torch.Tensor]] = []
+        for i in range(_AR_BLOCKS):
+            p = f"f_AR.blocks.{i}"
+            for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
+                items += [(f"{p}.{gn}.g", sd[f"{p}.{gn}.weight"]), (f"{p}.{gn}.b", sd[f"{p}.{gn}.bias"]),
+                          (f"{p}.{cv}.w", sd[f"{p}.{cv}.conv.weight"].permute(0, 2, 1).reshape(d, 3 * d)),
+                          (f"{p}.{cv}.b", sd[f"{p}.{cv}.conv.bias"])]
+        self._layout, off = [], 0
+        for name, t in items:
+            assert t.numel() % 64 == 0
+            self._layout.append((name, off, tuple(t.shape)))
+            off += t.numel()
+        self.flat_master = torch.cat([t.reshape(-1).to(torch.float32) for _, t in items]).to(dev)
+        self.flat_w16 = self.flat_master.to(self._dtype)
+        self.flat_grad = torch.zeros_like(self.flat_master)
+        self._off = {name: (o_, shape) for name, o_, shape in self._layout}
+        for name, o_, shape in self._layout:       # weights: the 16-bit copy; biases and GroupNorm parameters: the fp32 master itself
+            n = int(torch.Size(shape).numel())
+            src = self.flat_w16 if name.endswith(".w") else self.flat_master
+            self._dev[name] = src[o_: o_ + n].view(shape)
+        self._wt: Dict[str, torch.Tensor] = {}     # transposed 16-bit weights for the dX products
+        lib = _lib.load_library()
+        for name in ("mlp0.w", "mlp3.w", "mlp5.w"):   # the frozen regressor's, once
+            n, k = self._dev[name].shape
+            self._wt[name] = torch.empty((k, n), dtype=self._dtype, device=dev)
+            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
+                       "r50_op_transpose16")
+        self._refresh_transposes()
+        self._zero_bias = torch.zeros(max(3 * d, 2048, self._dp, _REG_HIDDEN), dtype=torch.float32, device=dev)
+        self._found = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._arena = _Arena(dev, self._dtype)
+
+    def _refresh_transposes(self) -> None:
+        lib = _lib.load_library()
+        for name, _, shape in self._layout:
+            if not name.endswith(".w"):
+                continue
+            n, k = shape
+            if name not in self._wt:
+                self._wt[name] = torch.zeros((k, n), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
+                       "r50_op_transpose16")
+
+    def trainable_parameter_names(self) -> List[str]:
+        return ar_trainable_names()
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The reference's keys and layouts (fp32, CPU): f_AR from the flat master buffer, every other entry as loaded."""
+        out = {k: v.clone() for k, v in self._sd.items()}
+        out.update(self.flat_to_reference(self.flat_master))
+        return out
+
+    def named_gradients(self) -> Dict[str, torch.Tensor]:
+        """flat_grad under the reference's names and layouts (fp32, CPU): what ``p.grad`` of the f_AR parameters holds."""
+        return self.flat_to_reference(self.flat_grad)
+
+    def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """A buffer in the flat layout (master, gradient, AdamW moments) under the reference's f_AR names and layouts (fp32, CPU)."""
+        d = self.latent_dim
+
+        def g(name):
+            o_, shape = self._off[name]
+            return flat[o_: o_ + int(torch.Size(shape).numel())].view(shape).cpu()
+        out = {}
+        for i in range(_AR_BLOCKS):
+            p = f"f_AR.blocks.{i}"
+            for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
+                out[f"{p}.{gn}.weight"], out[f"{p}.{gn}.bias"] = g(f"{p}.{gn}.g"), g(f"{p}.{gn}.b")
+                out[f"{p}.{cv}.conv.weight"] = g(f"{p}.{cv}.w").view(d, 3, d).permute(0, 2, 1).contiguous()
+                out[f"{p}.{cv}.conv.bias"] = g(f"{p}.{cv}.b")
+        return out
+
+    def flat_from_reference(self, named: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """Inverse of ``flat_to_reference``: a new device buffer in the flat layout."""
+        d = self.latent_dim
+        flat = torch.zeros_like(self.flat_master)
+
+        def put(name, key, view=lambda v: v):
+            o_, shape = self._off[name]
+            dst = view(flat[o_: o_ + int(torch.Size(shape).numel())].view(shape))
+            t = named[key].detach().to(torch.float32)
+            if tuple(t.shape) != tuple(dst.shape):
+                raise ValueError(f"{key}: shape {tuple(t.shape)}, expected {tuple(dst.shape)}")
+            dst.copy_(t)
+
+        for i in range(_AR_BLOCKS):
+            p = f"f_AR.blocks.{i}"
+            for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
+                put(f"{p}.{gn}.g", f"{p}.{gn}.weight"); put(f"{p}.{gn}.b", f"{p}.{gn}.bias")
+                put(f"{p}.{cv}.w", f"{p}.{cv}.conv.weight", lambda v: v.view(d, 3, d).permute(0, 2, 1))
+                put(f"{p}.{cv}.b", f"{p}.{cv}.conv.bias")
+        return flat
+
+    def refresh_weights16(self) -> None:
+        """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
+        self.flat_w16.copy_(self.flat_master.to(self._dtype))
+        self._refresh_transposes()
+
+    def make_dropout_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """Byte keep-masks (1 = keep, probability 1 - p) for the dropout sites of one phase-2 step: one per f_AR block, after its
+        conv1 (src/model.py:52).  f_movie and f_3D run in eval mode."""
+        return {f"f_AR.blocks.{i}": (torch.rand(b * t, self.latent_dim, device=self._device, generator=generator) >= DROPOUT_P)
+                .to(torch.uint8) for i in range(_AR_BLOCKS)}
+
+    # ---- launches -------------------------------------------------------------------------------
+    def _check_batch(self, feats: torch.Tensor, joints3d: torch.Tensor) -> Tuple[int, int]:
+        if self.flat_master is None:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') first")
+        if feats.dim() != 3 or feats.shape[-1] != 2048 or feats.device != self._device:
+            raise ValueError("feats: expected (B,T,2048) on the head's device")
+        b, t, _ = feats.shape
+        if tuple(joints3d.shape) != (b, t, self.joints_num, 3) or joints3d.device != self._device:
+            raise ValueError("joints3d: expected (B,T,J,3) on the head's device")
+        if b < 1 or t < 2:
+            raise ValueError("phase 2 needs clips of at least 2 frames (frame 0 has no prediction)")
+        return b, t
+
+    def _phi(self, feats: torch.Tensor, b: int, t: int) -> torch.Tensor:
+        """input_proj + f_movie, nothing saved: the teacher phi (B*T, D) 16-bit."""
+        lib = _lib.load_library()
+        f = feats.to(torch.float32).contiguous()
+        x0 = torch.empty((b * t, 2048), dtype=self._dtype, device=self._device)
+        _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * t, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None, "r50_op_cast_rows")
+        return self._temporal_net(self._gemm(x0, "input_proj", relu=False), b, t, "f_movie", self.number_blocks)
+
+    def _shift(self, ar: torch.Tensor, b: int, t: int) -> torch.Tensor:
+        """phi_hat[:, 1:] = ar[:, :-1], phi_hat[:, 0] = 0 (src/model.py:159-160)."""
+        d = self.latent_dim
+        phi_hat = torch.zeros((b * t, d), dtype=self._dtype, device=self._device)
+        phi_hat.view(b, t, d)[:, 1:, :] = ar.view(b, t, d)[:, :-1, :]
+        return phi_hat
+
+    def _pose_loss(self, y: torch.Tensor, gt: torch.Tensor, b: int, t: int, loss_scale: float, dy: torch.Tensor, out: torch.Tensor) -> None:
+        """out[0:2] = [l3d_hat, mpjpe_hat] over frames s >= 1; dy (B*T, J*3) fp32 = their gradient * loss_scale (0 on frame 0)."""
+        _lib.check(_lib.load_library().r50_op_future_pose_loss_grad(y.data_ptr(), gt.data_ptr(), b, t, self.joints_num, loss_scale,
+                                                                     dy.data_ptr(), out.data_ptr(), self._stream()), None,
+                   "r50_op_future_pose_loss_grad")
+
+    def _latent_loss(self, ar: torch.Tensor, phi: torch.Tensor, dphi_hat: torch.Tensor, b: int, t: int, lambda_latent: float,
+                     loss_scale: float, dar: torch.Tensor, out: torch.Tensor) -> None:
+        """out[2] = l_lat; dar (B*T, D) 16-bit = f_AR's output gradient: dphi_hat shifted back + lambda_latent * dl_lat, * loss_scale."""
+        part = torch.empty(b * t, dtype=torch.float32, device=self._device)
+        _lib.check(_lib.load_library().r50_op_ar_latent_grad(ar.data_ptr(), phi.data_ptr(), dphi_hat.data_ptr(), b, t, self.latent_dim,
+                                                              lambda_latent, loss_scale, dar.data_ptr(), out[2:].data_ptr(), part.data_ptr(),
+                                                              self._et, self._stream()), None, "r50_op_ar_latent_grad")
+
+    def forward_backward(self, feats: torch.Tensor, joints3d: torch.Tensor, loss_scale: float = 1.0,
+                         masks: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The phase-2 forward (f_AR in train mode when ``masks`` is given or ``self.training``; else dropout is identity), the loss
+        l3d_hat + lambda_latent * l_lat, backward into ``flat_grad`` (UNSCALED: the 16-bit backward runs on loss_scale * loss, the fp32
+        buffer receives grad / loss_scale).  ``self._found`` is raised when a 16-bit gradient overflowed.
+        Returns (joints_hat (B,T,J,3) fp32, losses = [l3d_hat, mpjpe_hat, l_lat] fp32 device tensor)."""
+        b, t = self._check_batch(feats, joints3d)
+        if masks is None and self.training:
+            masks = self.make_dropout_masks(b, t)
+        keep_scale = 1.0 / (1.0 - DROPOUT_P)
+        lib = _lib.load_library()
+        rows, d, o = b * t, self.latent_dim, self.out_dim
+        inv = 1.0 / loss_scale
+        self._arena.reset()
+        self._found.zero_()
+        with torch.cuda.device(self._device):
+            # ---------------- forward: phi (frozen, nothing saved), then f_AR keeping what its backward needs ----------------
+            phi = self._phi(feats, b, t)
+            x, saved = phi, []
+            for i in range(_AR_BLOCKS):
+                p = f"f_AR.blocks.{i}"
+                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
+                h = self._gemm(r1, p + ".conv1", relu=False)
+                m = masks[p] if masks is not None else None
+                if m is not None:
+                    self._mask_scale(h, m, keep_scale)
+                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
+                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x)
+                saved.append((x, r1, h, r2, m))
+                x = xo
+            ar = x
+            phi_hat = self._shift(ar, b, t)
+            # ---------------- the frozen regressor on phi_hat (eval mode: no dropout) ----------------
+            y = self._dev["y0"].view(1, o).expand(rows, o).contiguous()
+            reg = []
+            for _ in range(_REG_ITERS):
+                inp = torch.empty((rows, self._dp), dtype=self._dtype, device=self._device)
+                _lib.check(lib.r50_op_concat_pad(phi_hat.data_ptr(), d, y.data_ptr(), o, rows, inp.data_ptr(), self._dp, self._et,
+                                                 self._stream()), None, "r50_op_concat_pad")
+                h1 = self._gemm(inp, "mlp0", relu=True)
+                h2 = self._gemm(h1, "mlp3", relu=True)
+                dy = self._gemm(h2, "mlp5", relu=False)
+                _lib.check(lib.r50_op_add_rows(y.data_ptr(), o, dy.data_ptr(), self._op, rows, self._et, self._stream()), None, "r50_op_add_rows")
+                reg.append((h1, h2))
+            # ---------------- future-pose loss and its gradient ----------------
+            gt = joints3d.to(torch.float32).contiguous()
+            dyacc = torch.empty((rows, o), dtype=torch.float32, device=self._device)
+            losses = torch.empty(3, dtype=torch.float32, device=self._device)
+            self._pose_loss(y, gt, b, t, loss_scale, dyacc, losses)
+            # ---------------- backward through the regressor: dX only (its weights are frozen) ----------------
+            dphi_hat = torch.zeros((rows, d), dtype=torch.float32, device=self._device)
+            g5 = torch.empty((rows, self._op), dtype=self._dtype, device=self._device)
+            for i in reversed(range(_REG_ITERS)):
+                h1, h2 = reg[i]
+                _lib.check(lib.r50_op_cast_rows(dyacc.data_ptr(), rows, o, g5.data_ptr(), self._op, self._et, self._stream()), None, "r50_op_cast_rows")
+                dh2 = self._mm(g5, self._wt["mlp5.w"])                         # (rows, H)
+                self._relu_bwd(dh2, h2, 1.0)
+                dh1 = self._mm(dh2, self._wt["mlp3.w"])
+                self._relu_bwd(dh1, h1, 1.0)
+                dinp = self._mm(dh1, self._wt["mlp0.w"])                       # (rows, Dp) = [dphi_hat | dy | 0]
+                _lib.check(lib.r50_op_add_rows(dphi_hat.data_ptr(), d, dinp.data_ptr(), self._dp, rows, self._et, self._stream()), None,
+                           "r50_op_add_rows")
+                if i > 0:
+                    _lib.check(lib.r50_op_add_rows(dyacc.data_ptr(), o, dinp.data_ptr() + 2 * d, self._dp, rows, self._et, self._stream()),
+                               None, "r50_op_add_rows")
+            # ---------------- shift backward + latent loss + cast: f_AR's output gradient, in the arena ----------------
+            dx = self._arena.take(rows, d)
+            self._latent_loss(ar, phi, dphi_hat, b, t, self.lambda_latent, loss_scale, dx, losses)
+            # ---------------- backward: f_AR blocks, last first (phase 1's f_movie launches) ----------------
+            for i in reversed(range(_AR_BLOCKS)):
+                p = f"f_AR.blocks.{i}"
+                xin, r1, h, r2, m = saved[i]
+                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
+                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])                   # (rows, 3D)
+                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
+                if m is not None:
+                    self._mask_scale(dh, m, keep_scale)
+                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
+                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
+                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)         # + the skip connection's gradient (unused after block 0)
+            for chunk, used in zip(self._arena.chunks, self._arena.used):     # every 16-bit gradient the GEMMs and the latent kernel wrote
+                if used:
+                    _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
+                               "r50_op_check_overflow16")
+        return y.view(b, t, self.joints_num, 3), losses
+
+    def train_step(self, feats: torch.Tensor, joints3d: torch.Tensor, optim: AdamW, scaler: Optional[GradScaler] = None,
+                   masks: Optional[Dict[str, torch.Tensor]] = None, group=None) -> Tuple[float, float, bool]:
+        """One phase-2 step: forward + loss, scaled backward, inf check, AdamW over f_AR, scale update (``TrainableHead.train_step``'s
+        contract).  Returns (loss, mpjpe_hat, skipped); ``last_losses`` holds loss, l3d_hat, l_lat and mpjpe_hat of the step."""
+        scale = scaler.get_scale() if scaler is not None else 1.0
+        _, losses = self.forward_backward(feats, joints3d, scale, masks)
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            all_reduce_gradients(self.flat_grad, group)
+            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
+                       "r50_op_check_finite")
+            sync_overflow_flag(self._found, group)
+            found = bool(self._found.item())
+            if not found:
+                optim.step(self._found)
+                self._refresh_transposes()
+            if scaler is not None:
+                scaler.update(found)
+            l3d_hat, mpjpe_hat, l_lat = losses.tolist()
+        loss = l3d_hat + self.lambda_latent * l_lat
+        self.last_losses = {"loss": loss, "l3d_hat": l3d_hat, "l_lat": l_lat, "mpjpe_hat": mpjpe_hat}
+        return loss, mpjpe_hat, found
+
+    def future_losses(self, feats: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Eval-mode forward of one batch: ([l3d_hat, mpjpe_hat, l_lat] fp32 device tensor, joints_phi (B,T,J,3) fp32).  The launches
+        of ``__call__(feats, predict_future=True)``; the losses by the phase-2 loss kernels (their gradients go to scratch)."""
+        b, t = self._check_batch(feats, gt)
+        rows, d = b * t, self.latent_dim
+        with torch.cuda.device(self._device):
+            phi = self._phi(feats, b, t)
+            ar = self._temporal_net(phi, b, t, "f_AR", _AR_BLOCKS)
+            joints_phi = self._regressor(phi, b, t)
+            joints_hat = self._regressor(self._shift(ar, b, t), b, t)
+            losses = torch.empty(3, dtype=torch.float32, device=self._device)
+            self._pose_loss(joints_hat, gt, b, t, 1.0, torch.empty((rows, self.out_dim), dtype=torch.float32, device=self._device), losses)
+            self._latent_loss(ar, phi, torch.zeros((rows, d), dtype=torch.float32, device=self._device), b, t, 1.0, 1.0,
+                              torch.empty((rows, d), dtype=self._dtype, device=self._device), losses)
+        return losses, joints_phi
+
+
+@torch.no_grad()
+def evaluate_future(head: ARTrainableHead, store, batch_size: int) -> Tuple[float, float, float, float]:
+    """The phase-2 validation pass: (l3d_hat, mpjpe_hat, l_lat, mpjpe), each the mean over batches of the per-batch mean, the items
+    of ``store`` in order, ``batch_size`` at a time, the last batch kept even if short (as ``train.evaluate``).  l3d_hat and mpjpe_hat
+    over frames s >= 1; mpjpe is phase 1's MPJPE of joints_phi (``r50_op_pose_metrics``, the numbers ``train.evaluate`` reports).
+    The sums stay on the device and are read once per pass.  The head's mode is restored; its weights are not touched."""
+    was_training = head.training
+    head.train(False)
+    lib = _lib.load_library()
+    dev = head._device
+    try:
+        with torch.cuda.device(dev):
+            acc = torch.zeros(6, dtype=torch.float64, device=dev)        # [sum l3d_hat, sum mpjpe_hat, sum l_lat | l3d, mpjpe, batches]
+            for s in range(0, len(store), batch_size):
+                batch = store.get_batch(list(range(s, min(s + batch_size, len(store)))))
+                gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
+                losses, joints_phi = head.future_losses(batch[0], gt)
+                acc[:3] += losses.double()
+                _lib.check(lib.r50_op_pose_metrics(joints_phi.data_ptr(), gt.data_ptr(), gt.shape[0] * gt.shape[1], head.joints_num,
+                                                   acc[3:].data_ptr(), head._stream()), None, "r50_op_pose_metrics")
+            l3d_hat, mpjpe_hat, l_lat, _, mpjpe, n = acc.tolist()
+    finally:
+        head.train(was_training)
+    n = max(n, 1.0)
+    return l3d_hat / n, mpjpe_hat / n, l_lat / n, mpjpe / n
+
+
+# ---- the phase-2 driver -----------------------------------------------------------------------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    """Phase 1's flags and defaults (``train.build_parser``), ``--outdir ./runs/phase2``, plus ``--init`` and ``--lambda-latent``."""
+    p = argparse.ArgumentParser("Phase-2 training: freeze input_proj, f_movie and f_3D, train f_AR (future 3D joints + latent strips)",
+                                parents=[_phase1_parser()], add_help=False)
+    p.set_defaults(outdir="./runs/phase2")
+    p.add_argument("--init", type=str, default=None,
+                   help="phase-1 checkpoint (its 'model') or plain state dict to start from; required unless --resume names an existing file")
+    p.add_argument("--lambda-latent", type=float, default=LAMBDA_LATENT,
+                   help="weight of the latent loss mean((phi_hat - phi)^2) over frames >= 1 (no run has measured a good value)")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    p = build_parser()
+    args = p.parse_args(argv)
+    if not args.init and not (args.resume and os.path.isfile(args.resume)):
+        p.error("--init is required unless --resume names an existing checkpoint")
+    return args
+
+
+def main(argv: Optional[List[str]] = None) -> float:
+    """Phase 2 on one MI355X.  Per epoch, in ``train.main``'s order: train, evaluate, scheduler step, ``last.pt``, ``best.pt`` when the
+    validation future MPJPE improved by more than ``--early-stop-min-delta``, patience counter.  ``--resume`` loads model and
+    optimizer; the head's dimensions come from the checkpoint.  Prints one JSON line per epoch.  Returns the best val future MPJPE."""
+    from .feature_store import DeviceFeatureStore
+    from .results import infer_head_dims, load_head_state
+    from .samplers import MixedShardBatchSampler
+
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    os.makedirs(args.outdir, exist_ok=True)
+    train_set = DeviceFeatureStore(args.train, subjects=args.train_subjects, augment=True, device=device)
+    val_set = DeviceFeatureStore(args.val, subjects=args.val_subjects, device=device)
+    sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
+
+    resume = bool(args.resume and os.path.isfile(args.resume))
+    state = load_head_state(args.init if args.init else args.resume)
+    latent_dim, joints_num, number_blocks = infer_head_dims(state)
+    head = ARTrainableHead(latent_dim, joints_num, number_blocks, precision=args.precision, lambda_latent=args.lambda_latent)
+    head.load_state_dict(state, strict=True)
+    head.to(device)
+    optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
+    scaler = GradScaler()
+    schedule = CosineLR(args.lr, args.epochs)
+
+    start_epoch, best_val, no_improve_epochs = 0, float("inf"), 0
+    if resume:
+        ckpt = load_checkpoint(args.resume, head, optim)
+        schedule.load_group(ckpt["optim"])
+        start_epoch = int(ckpt.get("epoch", 0)) + 1
+        best_val = float(ckpt.get("best_val", best_val))
+        print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
+
+    print("===== Phase-2 training (f_AR) =====")
+    print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
+    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
+    print(f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_latent: {args.lambda_latent} | seed: {args.seed}")
+    print("===================================")
+    for epoch in range(start_epoch, args.epochs):
+        sampler.set_epoch(epoch)
+        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
+        print(f"\nEpoch {epoch + 1}/{args.epochs}")
+        t0 = time.time()
+        epoch_lr = optim.lr
+        tr_loss, tr_mpjpe_hat, steps, skipped = train_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every)
+        va_l3d_hat, va_mpjpe_hat, va_l_lat, va_mpjpe = evaluate_future(head, val_set, args.batch_size)
+        schedule.step()
+        optim.lr = schedule.lr
+        print(f"Train: loss={tr_loss:.6f} | future mpjpe={tr_mpjpe_hat:.3f}")
+        print(f"Val:   l3d_hat={va_l3d_hat:.6f} | l_lat={va_l_lat:.6f} | future mpjpe={va_mpjpe_hat:.3f} | mpjpe={va_mpjpe:.3f}")
+        print(f"Epoch time: {time.time() - t0:.2f}s")
+        print(json.dumps({"epoch": epoch, "lr": epoch_lr, "train_loss": tr_loss, "train_mpjpe_hat": tr_mpjpe_hat, "steps": steps,
+                          "skipped": skipped, "val_l3d_hat": va_l3d_hat, "val_mpjpe_hat": va_mpjpe_hat, "val_l_lat": va_l_lat,
+                          "val_mpjpe": va_mpjpe}))
+
+        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
+        if (best_val - va_mpjpe_hat) > args.early_stop_min_delta:
+            best_val = va_mpjpe_hat
+            no_improve_epochs = 0
+            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
+            print(f"New best val future MPJPE: {best_val:.3f} (saved best.pt)")
+        else:
+            no_improve_epochs += 1
+            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
+                  f"(best {best_val:.3f}, current {va_mpjpe_hat:.3f})")
+        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
+            print(f"Early stopping triggered at epoch {epoch + 1}. Best val future MPJPE: {best_val:.3f}")
+            break
+    print("\nDone.")
+    print(f"Best val future MPJPE: {best_val:.3f}")
+    return best_val
+
+
+if __name__ == "__main__":
+    main()

@@ -338,6 +338,20 @@ int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_
  * same bits on every run).  One launch of one workgroup, sized for up to ~1e5 joints per batch. */
 int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int joints, double* acc, void* stream);
 
+/* Lifting head, phase 2 (training f_AR; DESIGN.md "f next #2").  The reference has no phase 2; this
+ * project's definition: f_movie / f_3D frozen and run as at inference, loss = l3d_hat + lambda * l_lat over frames s >= 1.
+ *  r50_op_future_pose_loss_grad: y_hat, gt, dy (b*t, joints, 3) fp32: dy = 2 (y_hat-gt) / n * loss_scale with n = b*(t-1)*joints*3,
+ *    dy = 0 on frame 0 of every clip; loss2[0] = l3d_hat = mean over s >= 1 of (y_hat-gt)^2, loss2[1] = MPJPE over s >= 1.
+ *  r50_op_ar_latent_grad: ar (b,t,d) et = f_AR's output, phi (b,t,d) et = the teacher, dphi_hat (b,t,d) fp32 = the gradient that
+ *    reached phi_hat (the regressor's dX).  dar (b,t,d) et = cast16(dphi_hat[b,s+1] + lambda * 2 (ar[b,s] - phi[b,s+1]) / n_l *
+ *    loss_scale) for s <= t-2 and 0 for s = t-1, n_l = b*(t-1)*d; loss_lat[0] = mean (ar[b,s] - phi[b,s+1])^2 (fp32, one value);
+ *    row_part: b*t floats of device scratch.  Needs t >= 2, d % 8 == 0, ar / phi / dphi_hat / dar 16-byte aligned.
+ * Both reductions sum in a fixed order without atomics: the same bits on every run.  Arguments are checked before any launch. */
+int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,
+                                 void* stream);
+int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
+                          void* dar, float* loss_lat, float* row_part, int et, void* stream);
+
 /* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
 int r50_op_avgpool(const void* x_nhwc_bf16, int n, int hw, int c, float* y_f32, void* stream);
 
