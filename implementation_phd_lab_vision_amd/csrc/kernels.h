@@ -3990,6 +3990,55 @@ __global__ __launch_bounds__(256) void gn_relu_causal3_kernel(const unsigned sho
     }
 }
 
+// gn_relu_causal3_kernel on a TIME-MAJOR x (T, B, C), emitting only the rows t' in [t0, T): out ((T - t0) * B, 3C), row
+// (t' - t0) * B + b = [y(t'-2) | y(t'-1) | y(t')] of sample b, indices clamped at 0.  The statistics still cover all T rows.
+// The layout of the autoregressive rollout: appending a frame appends B rows, and t0 = T - 1 makes
+// the last block's conv2 a GEMM over B rows.  The same grid, slab order (element i = (t = i / cg, c = i % cg)), thread stride
+// and tree as gn_relu_causal3_kernel, so with t0 = 0 the values are bit-equal to it on the batch-major transpose.
+template <int ET>
+__global__ __launch_bounds__(256) void gn_relu_causal3_tm_kernel(const unsigned short* __restrict__ x, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, unsigned short* __restrict__ out,
+                                                                 int B, int T, int t0, int C, int groups, float eps) {
+    __shared__ float red[2][256];
+    const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
+    const int cg = C / groups, n = cg * T;
+    const unsigned short* xb = x + (size_t)b * C + g * cg;
+    auto ld = [&](int i) -> float {                       // element i of the slab: (t = i / cg, c = i % cg)
+        const int t = i / cg, c = i - t * cg;
+        const unsigned u = xb[(size_t)t * B * C + c];
+        return ET == 0 ? bf16_bits_to_f32(u) : (float)__builtin_bit_cast(_Float16, (unsigned short)u);
+    };
+    float s = 0.f, ss = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) { const float v = ld(i); s += v; ss += v * v; }
+    red[0][threadIdx.x] = s; red[1][threadIdx.x] = ss;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    const float mean = red[0][0] / (float)n;
+    const float var = fmaxf(red[1][0] / (float)n - mean * mean, 0.f);
+    const float rstd = 1.0f / sqrtf(var + eps);
+    const size_t ld_out = (size_t)3 * C;
+    auto row = [&](int r) -> unsigned short* { return out + ((size_t)(r - t0) * B + b) * ld_out; };
+    const int first = t0 >= 2 ? (t0 - 2) * cg : 0;         // frames before t0 - 2 feed no emitted row
+    for (int i = first + (int)threadIdx.x; i < n; i += 256) {
+        const int t = i / cg, c = i - t * cg, ch = g * cg + c;
+        float v = (ld(i) - mean) * rstd * gamma[ch] + beta[ch];
+        v = fmaxf(v, 0.f);
+        const unsigned short e = (unsigned short)(pack2_e<ET>(v, 0.f) & 0xffffu);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int r = t + 2 - k;
+            if (r >= t0 && r < T) row(r)[k * C + ch] = e;
+        }
+        if (t == 0) {                                     // replicate padding: row 0 taps 0, 1 and row 1 tap 0 read y(0)
+            if (t0 == 0) { row(0)[0 * C + ch] = e; row(0)[1 * C + ch] = e; }
+            if (t0 <= 1 && T > 1) row(1)[0 * C + ch] = e;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // ColorJitter variant (`_aug_color_jitter`, src/dataset.py:188-197 = torchvision.transforms.v2.ColorJitter
 // on the float clip in [0,1]): brightness / contrast / saturation / hue in a sampled order, one set of factors per clip.
@@ -4214,6 +4263,39 @@ __global__ __launch_bounds__(1024) void pose_metrics_kernel(const float* __restr
         acc[0] += red[0][0] / (3.0 * (double)nj);
         acc[1] += red[1][0] / (double)nj;
         acc[2] += 1.0;
+    }
+}
+
+// Per-horizon forecasting metrics of one batch: pred (B, P, J, 3) predicts frames i0 .. i0+P-1 of
+// gt (B, Tgt, J, 3).  Workgroup k ADDS acc[k] += sum over clips and joints of |pred[b,k,j] - gt[b,i0+k,j]|_2 and acc[P+k] += the sum
+// of squared errors; workgroup 0 adds acc[2P] += B (the clip count).  So the per-clip weighting holds over a whole pass and the host
+// reads the sums once.  Per joint fp32 (pose_metrics_kernel's arithmetic), per-thread fp64 partials over a fixed strided slice,
+// then a fixed fp64 tree: every workgroup owns its slots, no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void horizon_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int B, int P,
+                                                              int Tgt, int i0, int J, double* __restrict__ acc) {
+    __shared__ double red[2][256];
+    const int k = blockIdx.x;
+    const int n = B * J;
+    double s = 0.0, e = 0.0;
+    for (int q = threadIdx.x; q < n; q += 256) {
+        const int b = q / J, j = q - b * J;
+        const float* p = pred + (((size_t)b * P + k) * J + j) * 3;
+        const float* g = gt + (((size_t)b * Tgt + i0 + k) * J + j) * 3;
+        const float dx = p[0] - g[0], dy = p[1] - g[1], dz = p[2] - g[2];
+        const float d2 = dx * dx + dy * dy + dz * dz;
+        s += (double)d2;
+        e += (double)sqrtf(d2);
+    }
+    red[0][threadIdx.x] = s; red[1][threadIdx.x] = e;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        acc[k] += red[1][0];
+        acc[P + k] += red[0][0];
+        if (k == 0) acc[2 * P] += (double)B;
     }
 }
 

@@ -2301,6 +2301,17 @@ int r50_op_gn_relu_causal3(const void* x, int b, int t, int c, int groups, const
     return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_gn_relu_causal3: ") + hipGetErrorString(e));
 }
 
+int r50_op_gn_relu_causal3_tm(const void* x, int b, int t, int t0, int c, int groups, const float* gamma, const float* beta, float eps,
+                              void* out, int et, void* stream) {
+    if (!x || !gamma || !beta || !out || b < 1 || t < 1 || t0 < 0 || t0 >= t || c < 1 || groups < 1 || c % groups ||
+        (et != 0 && et != 1) || (int64_t)b * groups > INT32_MAX || (int64_t)t * (c / groups) > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_tm: invalid arguments (need 0 <= t0 < t, c % groups == 0)");
+    if (et) hipLaunchKernelGGL(gn_relu_causal3_tm_kernel<1>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, b, t, t0, c, groups, eps);
+    else hipLaunchKernelGGL(gn_relu_causal3_tm_kernel<0>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, b, t, t0, c, groups, eps);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_gn_relu_causal3_tm: ") + hipGetErrorString(e));
+}
+
 // ---- ColorJitter variant (kernels.h: cj_*_kernel) ----
 int r50_op_color_jitter_u8(const void* frames_u8, int t, int hw, const int* order4, float brightness, float contrast, float saturation,
                            float hue, int normalize, float* out_f32, float* scratch_means, void* stream) {
@@ -2390,6 +2401,14 @@ int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int jo
         return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_metrics: invalid arguments");
     hipLaunchKernelGGL(pose_metrics_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, (long long)(rows * joints), acc);
     return ew_done("r50_op_pose_metrics");
+}
+
+int r50_op_horizon_metrics(const float* pred, const float* gt, int b, int p, int t_gt, int i0, int joints, double* acc, void* stream) {
+    if (!pred || !gt || !acc || b < 1 || p < 1 || joints < 1 || i0 < 0 || t_gt < 1 || (int64_t)i0 + p > t_gt ||
+        (int64_t)b * joints > INT32_MAX || (int64_t)b * t_gt * joints > INT64_MAX / 3)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_horizon_metrics: invalid arguments (need b, p, joints >= 1 and 0 <= i0, i0 + p <= t_gt)");
+    hipLaunchKernelGGL(horizon_metrics_kernel, dim3((unsigned)p), dim3(256), 0, (hipStream_t)stream, pred, gt, b, p, t_gt, i0, joints, acc);
+    return ew_done("r50_op_horizon_metrics");
 }
 
 int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,

@@ -161,13 +161,19 @@ class PHDFor3DJoints:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._device).cuda_stream
 
-    def _gemm(self, x: torch.Tensor, wname: str, relu: bool, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """rows (R, K) element @ W (cout, K)^T + bias [+ residual] [ReLU] -> (R, cout) element: a 1x1 convolution over R pixels."""
+    def _gemm(self, x: torch.Tensor, wname: str, relu: bool, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rows (R, K) element @ W (cout, K)^T + bias [+ residual] [ReLU] -> (R, cout) element: a 1x1 convolution over R pixels.
+        ``out``: a contiguous (R, cout) view to store into (the rollout's append), else a new tensor."""
         wt, b = self._dev[wname + ".w"], self._dev[wname + ".b"]
         rows, k = x.shape
         cout = wt.shape[0]
         assert wt.shape[1] == k and x.is_contiguous()
-        y = torch.empty((rows, cout), dtype=self._dtype, device=self._device)
+        if out is None:
+            y = torch.empty((rows, cout), dtype=self._dtype, device=self._device)
+        else:
+            assert out.is_contiguous() and tuple(out.shape) == (rows, cout) and out.dtype == self._dtype
+            y = out
         lib = _lib.load_library()
         fn = lib.r50_op_conv2d_f16 if self._et else lib.r50_op_conv2d
         rc = fn(x.data_ptr(), rows, 1, 1, k, wt.data_ptr(), b.data_ptr(), residual.data_ptr() if residual is not None else None,
@@ -182,6 +188,16 @@ class PHDFor3DJoints:
                                                         self._dev[prefix + ".b"].data_ptr(), _GN_EPS, out.data_ptr(), self._et,
                                                         self._stream())
         _lib.check(rc, None, "r50_op_gn_relu_causal3")
+        return out
+
+    def _gn_relu_rows_tm(self, x: torch.Tensor, b: int, t: int, t0: int, prefix: str) -> torch.Tensor:
+        """``_gn_relu_rows`` on a time-major x (t*b, D), emitting the rows of frames t0 .. t-1 only: ((t-t0)*b, 3D), time-major."""
+        d = self.latent_dim
+        out = torch.empty(((t - t0) * b, 3 * d), dtype=self._dtype, device=self._device)
+        rc = _lib.load_library().r50_op_gn_relu_causal3_tm(x.data_ptr(), b, t, t0, d, _GROUPS, self._dev[prefix + ".g"].data_ptr(),
+                                                           self._dev[prefix + ".b"].data_ptr(), _GN_EPS, out.data_ptr(), self._et,
+                                                           self._stream())
+        _lib.check(rc, None, "r50_op_gn_relu_causal3_tm")
         return out
 
     def _temporal_net(self, x: torch.Tensor, b: int, t: int, net: str, nb: int) -> torch.Tensor:   # CausalTemporalNet, :69-78
@@ -256,6 +272,56 @@ class PHDFor3DJoints:
             x = self._gemm(x0, "input_proj", relu=False)
             phi = self._temporal_net(x, b, t, "f_movie", self.number_blocks)
             return self._regressor(phi, b, t)
+
+    @torch.no_grad()
+    def rollout(self, feats: torch.Tensor, input_len: int = 15, pred_len: int = 25) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Autoregressive forecast: f_movie over the first ``input_len`` frames only, then ``pred_len``
+        times the next strip ``f_AR(seq)[:, -1]`` appended to ``seq``, then f_3D on the appended strips.  Returns (future_phi
+        (B, P, D) fp32, future_joints (B, P, J, 3) fp32).  Only ``feats[:, :input_len]`` is read.  Eval-mode arithmetic (dropout
+        is the identity) with the current weights; the mode and the weights are left as they are.
+
+        The sequence lives in ONE time-major 16-bit buffer of (I+P)*B rows: frame t of sample b is row t*B + b, so the L frames
+        seen at step k = L - I are its first L*B rows.  f_AR is recomputed over all of them (GroupNorm's statistics change with
+        every frame, so no per-layer cache is exact), except the last block's conv2, which only the new frame needs: its
+        GroupNorm emits that frame's rows alone (t0 = L-1) and its GEMM over B rows stores straight into rows L*B .. (L+1)*B-1,
+        which is the append.  12 launches per step, no copies."""
+        if self._device is None or not self._dev:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') before running the head")
+        if feats.dim() != 3 or feats.shape[-1] != 2048:
+            raise ValueError(f"expected (B,T,2048) features, got {tuple(feats.shape)}")
+        if feats.device != self._device:
+            raise ValueError(f"features are on {feats.device}, head on {self._device}")
+        b, t, _ = feats.shape
+        i_len, p_len = int(input_len), int(pred_len)
+        if b < 1 or not 1 <= i_len <= t:
+            raise ValueError(f"rollout needs B >= 1 and 1 <= input_len <= T (got B={b}, input_len={i_len}, T={t})")
+        if p_len < 1:
+            raise ValueError(f"rollout needs pred_len >= 1 (got {p_len})")
+        d = self.latent_dim
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            f = feats[:, :i_len].to(torch.float32).contiguous()
+            x0 = torch.empty((b * i_len, 2048), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * i_len, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None,
+                       "r50_op_cast_rows")
+            phi = self._temporal_net(self._gemm(x0, "input_proj", relu=False), b, i_len, "f_movie", self.number_blocks)
+            seq = torch.empty(((i_len + p_len) * b, d), dtype=self._dtype, device=self._device)
+            seq[: i_len * b].view(i_len, b, d).copy_(phi.view(b, i_len, d).transpose(0, 1))        # batch-major -> time-major
+            last = _AR_BLOCKS - 1
+            for k in range(p_len):
+                n = i_len + k
+                x = seq[: n * b]
+                for i in range(_AR_BLOCKS):
+                    p = f"f_AR.blocks.{i}"
+                    h = self._gemm(self._gn_relu_rows_tm(x, b, n, 0, p + ".gn1"), p + ".conv1", relu=False)
+                    if i < last:
+                        x = self._gemm(self._gn_relu_rows_tm(h, b, n, 0, p + ".gn2"), p + ".conv2", relu=False, residual=x)
+                    else:
+                        self._gemm(self._gn_relu_rows_tm(h, b, n, n - 1, p + ".gn2"), p + ".conv2", relu=False,
+                                   residual=x[(n - 1) * b:], out=seq[n * b: (n + 1) * b])
+            future = seq[i_len * b:]                                                      # (P*B, D) time-major
+            joints = self._regressor(future, p_len, b)                                    # (P, B, J, 3)
+            return future.view(p_len, b, d).transpose(0, 1).float(), joints.transpose(0, 1).contiguous()
 
 
 PHD = PHDFor3DJoints       # the name src/train.py imports it under

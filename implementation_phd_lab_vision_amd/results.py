@@ -4,6 +4,9 @@ counterpart of ``python src/results.py`` (src/results.py:137-239).
 It scores a checkpoint on the test subject (S9) with ``train.evaluate`` over the reference's shuffled test loader
 (``shuffle=True, drop_last=True``, :162-170), prints the reference's metrics line, and dumps ONE batch to an ``.npz`` for the
 visualisation scripts: the clips' video, ground-truth and predicted 3D joints, 2D joints, intrinsics, meta and the test metrics.
+With ``--pred-len P`` (default 0: off) it also forecasts: ``forecast.evaluate_rollout`` over the test set
+prints MPJPE per horizon, and the ``.npz`` gains ``predicted_future3djoints`` (the dumped clips' P future poses after
+``--input-len`` observed frames), ``future_mpjpe`` (P,) and ``rollout_lens`` [I, P].
 
 Two differences from running the reference's script as it stands:
 
@@ -34,6 +37,7 @@ import torch
 from . import _lib
 
 SEQ_LEN = 40                              # src/config.py
+INPUT_LEN = 15                            # src/config.py: the rollout's observed frames (--input-len)
 TEST_SUBJECTS = [9]                       # hard-coded at src/results.py:159
 
 
@@ -59,7 +63,25 @@ def build_parser() -> argparse.ArgumentParser:
                         "[::meta.get('frame_skip', 1)][start:end])")
     p.add_argument("--video-reader", type=str, default=None,
                    help="module:function, a callable path -> (N,H,W,3) uint8 (default: torchvision.io.read_video(path, pts_unit='sec')[0])")
+    p.add_argument("--input-len", type=int, default=INPUT_LEN, help="observed frames of the rollout (src/config.py INPUT_LEN)")
+    p.add_argument("--pred-len", type=int, default=0,
+                   help="frames to forecast with f_AR and score per horizon (INTEGRATION.md section J); 0 = off")
     return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    """``build_parser().parse_args`` plus the rollout flags' checks: --pred-len >= 0 and, when it is on, 1 <= --input-len and
+    --input-len + --pred-len <= --seq-len."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.pred_len < 0:
+        p.error(f"--pred-len must be >= 0 (0 = no rollout), got {args.pred_len}")
+    if args.pred_len > 0:
+        if args.input_len < 1:
+            p.error(f"--input-len must be >= 1, got {args.input_len}")
+        if args.input_len + args.pred_len > args.seq_len:
+            p.error(f"--input-len + --pred-len = {args.input_len + args.pred_len} exceeds --seq-len {args.seq_len}")
+    return args
 
 
 # ---- host pieces ------------------------------------------------------------------------------------------------------------
@@ -180,7 +202,7 @@ def main(argv: Optional[List[str]] = None) -> str:
     from .feature_store import DeviceFeatureStore
     from .train import evaluate
 
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     reader = resolve_video_reader(args.video_reader)             # before the evaluation pass: fail early
     device = torch.device(args.device)
     if device.type != "cuda" or not torch.cuda.is_available():
@@ -201,6 +223,14 @@ def main(argv: Optional[List[str]] = None) -> str:
     avg_loss, avg_mpjpe, avg_l3d, avg_l2d = evaluate(head, test_set, args.batch_size, test_set=True, batches=eval_batches)
     print(f"Test metrics | loss: {avg_loss:.6f} | mpjpe (m): {avg_mpjpe:.6f} "
           f"| mpjpe (mm): {avg_mpjpe * 1000.0:.2f} | l3d: {avg_l3d:.6f} | l2d: {avg_l2d:.6f}")
+    rollout = None
+    if args.pred_len > 0:
+        from .forecast import evaluate_rollout
+        rollout = evaluate_rollout(head, test_set, args.input_len, args.pred_len)
+        mm = rollout["mpjpe"]
+        at = " | ".join(f"@{k}: {mm[k - 1] * 1000.0:.2f}" for k in sorted({h for h in (1, 5, 10, args.pred_len) if h <= args.pred_len}))
+        print(f"Rollout metrics | input {args.input_len} | pred {args.pred_len} | clips {rollout['clips']} | mpjpe (mm) {at} "
+              f"| mean: {rollout['mpjpe_mean'] * 1000.0:.2f}")
 
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
@@ -214,10 +244,15 @@ def main(argv: Optional[List[str]] = None) -> str:
 
     out_path = args.out
     os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    extra = {}
+    if rollout is not None:                  # the dumped clips' forecast: observe input_len frames, predict pred_len
+        extra = {"predicted_future3djoints": head.rollout(feats[:n_save], args.input_len, args.pred_len)[1].cpu().numpy(),
+                 "future_mpjpe": np.array(rollout["mpjpe"], dtype=np.float32),
+                 "rollout_lens": np.array([args.input_len, args.pred_len], dtype=np.int64)}
     np.savez_compressed(out_path, video=videos, joints3d=joints3d_np, predicted3djoints=pred,
                         joints2d=joints2d[:n_save].cpu().numpy(), K=k[:n_save].to(torch.float32).cpu().numpy(),
                         meta=np.array(list(metas[:n_save]), dtype=object),
-                        test_metrics=np.array([avg_loss, avg_mpjpe, avg_l3d, avg_l2d], dtype=np.float32))
+                        test_metrics=np.array([avg_loss, avg_mpjpe, avg_l3d, avg_l2d], dtype=np.float32), **extra)
     print(f"[OK] Saved batch to: {out_path}")
     print(f"video shape: {videos.shape} | joints3d: {joints3d_np.shape} | pred: {pred.shape}")
     print(f"Results time: {time.time() - t0:.2f}s")

@@ -302,6 +302,14 @@ int r50_op_add_rows(float* y_f32, int ny, const void* dy, int dp, int64_t rows, 
 int r50_op_gn_relu_causal3(const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta, float eps,
                            void* out, int et, void* stream);
 
+/* Lifting head, autoregressive rollout: f_AR over a TIME-MAJOR sequence that grows by one frame per step.
+ *  r50_op_gn_relu_causal3_tm: r50_op_gn_relu_causal3 on x (t,b,c) time-major, statistics over all t rows of each sample and
+ *    group, emitting only the rows t' in [t0, t): out ((t-t0)*b, 3c), row (t'-t0)*b + b' = [y(t'-2) | y(t'-1) | y(t')] of sample b',
+ *    indices clamped at 0.  0 <= t0 < t.  With t0 = 0 the values are bit-equal to r50_op_gn_relu_causal3 on the batch-major
+ *    transpose (same grid, summation order and tree); t0 = t-1 emits the last row of each sample only. */
+int r50_op_gn_relu_causal3_tm(const void* x, int b, int t, int t0, int c, int groups, const float* gamma, const float* beta, float eps,
+                              void* out, int et, void* stream);
+
 /* Lifting head, backward + optimizer: the training step of `train()` (src/train.py:137-176: fp16 autocast forward, `l3d` MSE
  * loss, GradScaler, AdamW).  Every matrix product of the backward pass (dX = dY W, dW = dY^T X) is an r50_op_conv2d(_f16) launch
  * on operands transposed by r50_op_transpose16; these are the pieces around them.  16-bit tensors are `et` elements (0 bf16, 1 fp16).
@@ -337,6 +345,12 @@ int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_
  * memory, so the mean over per-batch means is acc[0..1] / acc[2].  fp32 per joint, fp64 sums in a fixed order (no atomics: the
  * same bits on every run).  One launch of one workgroup, sized for up to ~1e5 joints per batch. */
 int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int joints, double* acc, void* stream);
+
+/* Lifting head, forecasting metrics of a rollout: pred (b,p,joints,3) fp32 predicts frames i0 .. i0+p-1
+ * of gt (b,t_gt,joints,3) fp32; i0 + p <= t_gt.  ADDS acc[k] += sum over clips and joints of |pred[:,k]-gt[:,i0+k]|_2 (MPJPE sum),
+ * acc[p+k] += the sum of squared errors, acc[2p] += b; acc: 2p+1 doubles of device memory.  One workgroup per horizon, fp32 per
+ * joint, fp64 sums in a fixed order (no atomics: the same bits on every run). */
+int r50_op_horizon_metrics(const float* pred, const float* gt, int b, int p, int t_gt, int i0, int joints, double* acc, void* stream);
 
 /* Lifting head, phase 2 (training f_AR; DESIGN.md "f next #2").  The reference has no phase 2; this
  * project's definition: f_movie / f_3D frozen and run as at inference, loss = l3d_hat + lambda * l_lat over frames s >= 1.
