@@ -4482,6 +4482,160 @@ __global__ __launch_bounds__(256) void gn_relu_causal3_bwd_kernel(const unsigned
     }
 }
 
+// ---- Rollout training: f_AR trained on its own multi-step rollouts ------------------------------------
+// Backward of gn_relu_causal3_tm_kernel.  x, dx, add: (T, B, C) time-major; dr ((T - t0) * B, 3C): the gradient of exactly the rows
+// the forward emitted (row (r - t0) * B + b = frame r of sample b, r >= t0).  dx covers ALL T frames: the statistics couple every
+// frame of the slab to the emitted rows.  Per frame s, da(s, c) sums the emitted (row, tap) pairs that read s, in the batch-major
+// kernel's order (taps k = 0, 1, 2, then the replicate-padding taps of rows 0 and 1), and everything else is
+// gn_relu_causal3_bwd_kernel's arithmetic with the tm forward's slab order and tree: with t0 = 0 the result is bit-equal to
+// gn_relu_causal3_bwd_kernel on the batch-major transpose.  One workgroup per (sample, group); dgamma_part / dbeta_part (B, C).
+template <int ET>
+__global__ __launch_bounds__(256) void gn_relu_causal3_tm_bwd_kernel(const unsigned short* __restrict__ dr,
+                                                                     const unsigned short* __restrict__ x, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, const unsigned short* __restrict__ add,
+                                                                     unsigned short* __restrict__ dx, float* __restrict__ dgamma_part,
+                                                                     float* __restrict__ dbeta_part, int B, int T, int t0, int C,
+                                                                     int groups, float eps) {
+    __shared__ float red[2][256];
+    const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
+    const int cg = C / groups, n = cg * T;
+    const size_t ldx = (size_t)B * C, ldr = (size_t)3 * C;
+    const unsigned short* xb = x + (size_t)b * C + g * cg;
+    auto block_sum2 = [&](float a, float c2, float& oa, float& oc) {
+        red[0][threadIdx.x] = a; red[1][threadIdx.x] = c2;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+            __syncthreads();
+        }
+        oa = red[0][0]; oc = red[1][0];
+        __syncthreads();
+    };
+    float s = 0.f, ss = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) { const int t = i / cg, c = i - t * cg; const float v = ld_e<ET>(xb + (size_t)t * ldx + c); s += v; ss += v * v; }
+    float S, SS;
+    block_sum2(s, ss, S, SS);
+    const float mean = S / (float)n;
+    const float var = fmaxf(SS / (float)n - mean * mean, 0.f);
+    const float rstd = 1.0f / sqrtf(var + eps);
+    auto row = [&](int r) -> const unsigned short* { return dr + ((size_t)(r - t0) * B + b) * ldr; };
+    auto dy_of = [&](int t, int c, float& xh) -> float {       // dy and xh of slab element (t, c)
+        const int ch = g * cg + c;
+        xh = (ld_e<ET>(xb + (size_t)t * ldx + c) - mean) * rstd;
+        if (xh * gamma[ch] + beta[ch] <= 0.f) return 0.f;
+        float da = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const int r = t + 2 - k;
+            if (r >= t0 && r < T) da += ld_e<ET>(row(r) + k * C + ch);
+        }
+        if (t == 0) {
+            if (t0 == 0) da += ld_e<ET>(row(0) + 0 * C + ch) + ld_e<ET>(row(0) + 1 * C + ch);
+            if (t0 <= 1 && T > 1) da += ld_e<ET>(row(1) + 0 * C + ch);
+        }
+        return da;
+    };
+    float sg = 0.f, sgx = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int t = i / cg, c = i - t * cg;
+        float xh;
+        const float dy = dy_of(t, c, xh);
+        const float gg = dy * gamma[g * cg + c];
+        sg += gg; sgx += gg * xh;
+    }
+    float SG, SGX;
+    block_sum2(sg, sgx, SG, SGX);
+    const float mg = SG / (float)n, mgx = SGX / (float)n;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int t = i / cg, c = i - t * cg;
+        float xh;
+        const float dy = dy_of(t, c, xh);
+        float v = rstd * (dy * gamma[g * cg + c] - mg - xh * mgx);
+        const size_t o = (size_t)t * ldx + (size_t)b * C + g * cg + c;
+        if (add) v += ld_e<ET>(add + o);
+        dx[o] = st_e<ET>(v);
+    }
+    for (int c = threadIdx.x; c < cg; c += 256) {
+        float a = 0.f, bb = 0.f;
+        for (int t = 0; t < T; ++t) { float xh; const float dy = dy_of(t, c, xh); a += dy * xh; bb += dy; }
+        dgamma_part[(size_t)b * C + g * cg + c] = a;
+        dbeta_part[(size_t)b * C + g * cg + c] = bb;
+    }
+}
+
+// Future-pose loss of a rollout: pred (K*B, joints, 3) fp32 time-major (row h*B + b predicts frame i0 + h of sample b), gt (B, T, joints,
+// 3) fp32.  dy (K*B, joints, 3) = 2 (pred - gt) / n * loss_scale, n = K*B*joints*3; loss[0] = mean squared error, loss[1] = MPJPE, over
+// all K horizons.  future_pose_loss_grad_kernel's reduction: per-thread fp64 partials over a fixed strided slice, a fixed fp64 tree,
+// one workgroup of 1024, no atomics.
+__global__ __launch_bounds__(1024) void rollout_pose_loss_grad_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int B,
+                                                                      int K, int T, int i0, int joints, float loss_scale,
+                                                                      float* __restrict__ dy, float* __restrict__ loss) {
+    __shared__ double red[2][1024];
+    const long long nj = (long long)K * B * joints;
+    const float n = (float)(3 * nj);
+    double s = 0.0, e = 0.0;
+    for (long long j = threadIdx.x; j < nj; j += 1024) {
+        const long long r = j / joints;
+        const int jj = (int)(j - r * joints);
+        const int h = (int)(r / B), b = (int)(r - (long long)h * B);
+        const float* g = gt + (((long long)b * T + i0 + h) * joints + jj) * 3;
+        float d2 = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const float d = pred[3 * j + k] - g[k];
+            dy[3 * j + k] = 2.f * d / n * loss_scale;
+            d2 += d * d;
+        }
+        s += (double)d2;
+        e += (double)sqrtf(d2);
+    }
+    red[0][threadIdx.x] = s; red[1][threadIdx.x] = e;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = (float)(red[0][0] / (3.0 * (double)nj));
+        loss[1] = (float)(red[1][0] / (double)nj);
+    }
+}
+
+// Latent loss of a rollout: fut (K*B, d) et time-major (row h*B + b = the strip predicted for frame i0 + h), phi (B, T, d) et batch-major
+// (the teacher).  dfut (K*B, d) fp32 += coef * (fut - phi[b, i0 + h]), coef = lambda * 2 / n_l * loss_scale; part[row] = the row's sum of
+// squares.  ar_latent_grad_kernel's shape: one workgroup of 128 per row, 8 elements per lane (16-byte loads; d % 8 == 0, rows 16-byte
+// aligned), a fixed wave64 butterfly then the two waves in order; sum_parts_kernel adds the rows in a fixed order.
+template <int ET>
+__global__ __launch_bounds__(128) void rollout_latent_grad_kernel(const unsigned short* __restrict__ fut, const unsigned short* __restrict__ phi,
+                                                                  int B, int T, int i0, int d, float coef, float* __restrict__ dfut,
+                                                                  float* __restrict__ part) {
+    __shared__ float red[2];
+    const long long r = blockIdx.x;
+    const int h = (int)(r / B), b = (int)(r - (long long)h * B), nv = d >> 3;
+    const u32x4* a = reinterpret_cast<const u32x4*>(fut + r * d);
+    const u32x4* p = reinterpret_cast<const u32x4*>(phi + ((long long)b * T + i0 + h) * d);
+    f32x4* o = reinterpret_cast<f32x4*>(dfut + r * d);
+    float ss = 0.f;
+    for (int v = threadIdx.x; v < nv; v += 128) {
+        const u32x4 av = a[v], pv = p[v];
+        f32x4 o0 = o[2 * v], o1 = o[2 * v + 1];
+        float dd[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            dd[2 * k] = unpack_lo_e<ET>(av[k]) - unpack_lo_e<ET>(pv[k]);
+            dd[2 * k + 1] = unpack_hi_e<ET>(av[k]) - unpack_hi_e<ET>(pv[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ss += dd[k] * dd[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { o0[k] += coef * dd[k]; o1[k] += coef * dd[4 + k]; }
+        o[2 * v] = o0; o[2 * v + 1] = o1;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) part[r] = red[0] + red[1];
+}
+
 // found[0] = 1 if any of g (n) is not finite (GradScaler's inf check, src/train.py:172-174)
 __global__ __launch_bounds__(256) void check_finite_kernel(const float* __restrict__ g, long long n, int* __restrict__ found) {
     int bad = 0;

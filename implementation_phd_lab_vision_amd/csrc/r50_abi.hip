@@ -2452,6 +2452,52 @@ int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int 
     return ew_done("r50_op_gn_relu_causal3_bwd");
 }
 
+int r50_op_gn_relu_causal3_tm_bwd(const void* dr, const void* x, int b, int t, int t0, int c, int groups, const float* gamma,
+                                  const float* beta, float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et,
+                                  void* stream) {
+    if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_tm_bwd: null pointer");
+    if (b < 1 || t < 1 || t0 < 0 || t0 >= t || c < 1 || groups < 1 || c % groups || c / groups > 256 || (et != 0 && et != 1) ||
+        (int64_t)b * groups > INT32_MAX || (int64_t)t * (c / groups) > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID,
+                    "r50_op_gn_relu_causal3_tm_bwd: invalid arguments (need b, t >= 1, 0 <= t0 < t, c % groups == 0, c / groups <= 256, et 0 or 1)");
+    R50_ET_LAUNCH(gn_relu_causal3_tm_bwd_kernel, dim3((unsigned)(b * groups)), dim3(256), stream, (const unsigned short*)dr,
+                  (const unsigned short*)x, gamma, beta, (const unsigned short*)add, (unsigned short*)dx, dgamma_part, dbeta_part, b, t, t0,
+                  c, groups, eps);
+    return ew_done("r50_op_gn_relu_causal3_tm_bwd");
+}
+
+int r50_op_rollout_pose_loss_grad(const float* pred, const float* gt, int b, int k, int t_gt, int i0, int joints, float loss_scale,
+                                  float* dy, float* loss2, void* stream) {
+    if (!pred || !gt || !dy || !loss2)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_pose_loss_grad: null pointer");
+    if (b < 1 || k < 1 || joints < 1 || i0 < 0 || (int64_t)i0 + k > t_gt || (int64_t)b * t_gt > INT32_MAX ||
+        (int64_t)k * b * joints > INT64_MAX / 3)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_pose_loss_grad: invalid arguments (need b, k, joints >= 1 and 0 <= i0, i0 + k <= t_gt)");
+    hipLaunchKernelGGL(rollout_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, b, k, t_gt, i0, joints,
+                       loss_scale, dy, loss2);
+    return ew_done("r50_op_rollout_pose_loss_grad");
+}
+
+int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, int t_phi, int i0, int d, float lambda, float loss_scale,
+                               float* dfut, float* loss_lat, float* row_part, int et, void* stream) {
+    if (!fut || !phi || !dfut || !loss_lat || !row_part)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: null pointer");
+    if (b < 1 || k < 1 || i0 < 0 || (int64_t)i0 + k > t_phi || (int64_t)b * k > INT32_MAX || (int64_t)b * t_phi > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: need b, k >= 1 and 0 <= i0, i0 + k <= t_phi");
+    if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: d must be a positive multiple of 8");
+    if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: et must be 0 (bf16) or 1 (fp16)");
+    if (!aligned16(fut) || !aligned16(phi) || !aligned16(dfut))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: fut, phi and dfut must be 16-byte aligned");
+    const long long rows = (long long)b * k;
+    const double n_l = (double)rows * d;
+    const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
+    R50_ET_LAUNCH(rollout_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)fut, (const unsigned short*)phi,
+                  b, t_phi, i0, d, coef, dfut, row_part);
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, rows, 1.0 / n_l, loss_lat);
+    return ew_done("r50_op_rollout_latent_grad");
+}
+
 int r50_op_check_finite(const float* g, int64_t n, int* found, void* stream) {
     if (!g || !found || n < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_check_finite: invalid arguments");
     hipLaunchKernelGGL(check_finite_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, g, (long long)n, found);

@@ -28,6 +28,33 @@ regressor on ``phi_hat``; ``r50_op_future_pose_loss_grad``; the regressor's back
 backward + latent-loss gradient + cast into the step's 16-bit arena); f_AR's backward with weight gradients (the launches of
 phase 1's f_movie backward); one overflow check over the arena; then ``all_reduce_gradients``, ``check_finite``, ``train.AdamW``,
 ``train.GradScaler``.  ``joints_phi`` is not computed in the step: it does not enter the loss.  No CPU fallback.
+
+``--objective rollout`` trains f_AR on its own multi-step rollouts instead.  The reference names the step
+(src/config.py ``CURRICULUM_STEPS = 25``) but never uses it; this project's definition
+(tests/golden/make_golden_train_rollout.py runs it on the reference module itself)::
+
+    # model: PHD(latent_dim, 17, number_blocks) from a phase-1 or phase-2 checkpoint; only f_AR trains
+    model.train(); model.f_movie.eval(); model.f_3D.eval()              # as phase 2: only f_AR's dropout is active
+    with torch.autocast("cuda", dtype=torch.float16):
+        with torch.no_grad():
+            phi_obs = model.f_movie(model.input_proj(feats[:, :I]))      # observed strips only (as rollout(): no future leak)
+            phi_all = model.f_movie(model.input_proj(feats))             # latent teacher = phase 2's teacher
+        seq = phi_obs
+        for _ in range(k):                                               # k = curriculum steps this epoch, 1 <= k <= P
+            seq = torch.cat([seq, model.f_AR(seq)[:, -1:]], dim=1)       # f_AR recomputed over the whole sequence, dropout each call
+        fut = seq[:, I:]                                                 # (B, k, D)
+        l3d  = (model.f_3D(fut) - joints3d[:, I:I + k]).pow(2).mean()
+        l_lat = (fut - phi_all[:, I:I + k]).pow(2).mean()
+        loss = l3d + args.lambda_latent * l_lat
+    scaler.scale(loss).backward(); scaler.step(optim); scaler.update()
+
+Full backpropagation through time: the gradient flows through every appended strip into all later steps, no truncation, no
+detach.  Curriculum: in epoch e (0-based) k(e) = min(P, 1 + (e * P) // C), C = ``--curriculum-steps`` (C = 0: k = P throughout);
+on ``--resume`` k follows the epoch number.  Validation is ``forecast.evaluate_rollout`` at the full P, and ``best.pt`` / early
+stopping follow its ``mpjpe_mean``.  ``ARTrainableHead.rollout_train_step`` runs ``rollout``'s launches on its time-major sequence
+buffer, keeping each (step, block)'s activations, then walks the steps last first: ``r50_op_rollout_pose_loss_grad`` and
+``r50_op_rollout_latent_grad`` put the loss gradients into an fp32 time-major buffer, and each step's strip gradient, cast to 16 bits,
+runs back through f_AR with ``r50_op_gn_relu_causal3_tm_bwd`` (t0 = L-1 for the last block's conv2, which only the new frame needs).
 """
 from __future__ import annotations
 
@@ -40,11 +67,14 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
+from .model import _AR_BLOCKS, _GN_EPS, _GROUPS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
 from .train import (DROPOUT_P, AdamW, CosineLR, GradScaler, _Arena, _BackwardLaunches, all_reduce_gradients, build_parser as _phase1_parser,
-                    save_checkpoint, load_checkpoint, sync_overflow_flag, train_epoch)
+                    dropout_generator, save_checkpoint, load_checkpoint, sync_overflow_flag, train_epoch)
 
 LAMBDA_LATENT = 1.0
+INPUT_LEN = 15             # src/config.py
+PRED_LEN = 25
+CURRICULUM_STEPS = 25      # src/config.py: "Slowly increase autoregressive steps from 1 to 25"
 
 
 def ar_trainable_names() -> List[str]:
@@ -331,6 +361,191 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         self.last_losses = {"loss": loss, "l3d_hat": l3d_hat, "l_lat": l_lat, "mpjpe_hat": mpjpe_hat}
         return loss, mpjpe_hat, found
 
+    # ---- the rollout objective -------------------------------------------------------------------
+    def make_rollout_dropout_masks(self, b: int, input_len: int, k: int,
+                                   generator: Optional[torch.Generator] = None) -> List[Dict[str, torch.Tensor]]:
+        """Byte keep-masks of one rollout step: masks[j]["f_AR.blocks.i"] ((I+j)*B, D), time-major like the sequence, after block i's
+        conv1 at rollout step j; drawn in (step, block) order."""
+        return [{f"f_AR.blocks.{i}": (torch.rand((input_len + j) * b, self.latent_dim, device=self._device, generator=generator)
+                                      >= DROPOUT_P).to(torch.uint8) for i in range(_AR_BLOCKS)} for j in range(k)]
+
+    def _gn_bwd_tm(self, dr: torch.Tensor, x: torch.Tensor, b: int, t: int, t0: int, prefix: str, add: Optional[torch.Tensor],
+                   inv_scale: float, accumulate: bool) -> torch.Tensor:
+        """``r50_op_gn_relu_causal3_tm_bwd``: dx (t*b, D) time-major; the GroupNorm parameter gradients [+]= into flat_grad."""
+        d = self.latent_dim
+        lib = _lib.load_library()
+        dx = torch.empty((b * t, d), dtype=self._dtype, device=self._device)
+        part = torch.empty((2, b, d), dtype=torch.float32, device=self._device)
+        _lib.check(lib.r50_op_gn_relu_causal3_tm_bwd(dr.data_ptr(), x.data_ptr(), b, t, t0, d, _GROUPS, self._dev[prefix + ".g"].data_ptr(),
+                                                     self._dev[prefix + ".b"].data_ptr(), _GN_EPS, add.data_ptr() if add is not None else None,
+                                                     dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), self._et, self._stream()), None,
+                   "r50_op_gn_relu_causal3_tm_bwd")
+        for j, suffix in ((0, ".g"), (1, ".b")):
+            _lib.check(lib.r50_op_colsum_f32(part[j].data_ptr(), b, d, inv_scale, self.grad_view(prefix + suffix).data_ptr(),
+                                             int(accumulate), self._stream()), None, "r50_op_colsum_f32")
+        return dx
+
+    def _check_arena(self) -> None:
+        lib = _lib.load_library()
+        for chunk, used in zip(self._arena.chunks, self._arena.used):
+            if used:
+                _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
+                           "r50_op_check_overflow16")
+
+    def rollout_forward_backward(self, feats: torch.Tensor, joints3d: torch.Tensor, input_len: int, k: int, loss_scale: float = 1.0,
+                                 masks: Optional[List[Dict[str, torch.Tensor]]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The rollout objective's forward (f_AR in train mode when ``masks`` is given or ``self.training``; else dropout is identity),
+        loss l3d + lambda_latent * l_lat over the k rolled-out frames, and full backpropagation through time into ``flat_grad``
+        (UNSCALED, as ``forward_backward``).  ``self._found`` is raised when a 16-bit gradient overflowed.
+        Returns (future joints (B,k,J,3) fp32, losses = [l3d, mpjpe, l_lat] fp32 device tensor).
+
+        The sequence is ``rollout``'s time-major buffer of (I+k)*B rows and the forward issues ``rollout``'s launches, keeping each
+        (step, block)'s input, GroupNorm rows, conv1 output and mask.  The backward walks the steps last first: the gradient of the
+        strip step j appended (fp32 rows of ``dseq``, which every later step has already added into) is cast to 16 bits, runs back
+        through the last block (conv2 over B rows, GroupNorm with t0 = L-1, the skip connection onto frame L-1 only) and the two
+        blocks before it, and what reaches the sequence is added into ``dseq``'s predicted rows (the observed ones feed frozen
+        f_movie only).  The 16-bit arena is checked for overflow and reused once per step."""
+        b, t = self._check_batch(feats, joints3d)
+        i_len, k = int(input_len), int(k)
+        if i_len < 1 or k < 1 or i_len + k > t:
+            raise ValueError(f"rollout training needs 1 <= input_len, 1 <= k and input_len + k <= T (got {i_len}, {k}, T={t})")
+        if masks is None and self.training:
+            masks = self.make_rollout_dropout_masks(b, i_len, k)
+        if masks is not None and len(masks) != k:
+            raise ValueError(f"expected {k} per-step dropout mask sets, got {len(masks)}")
+        keep_scale = 1.0 / (1.0 - DROPOUT_P)
+        lib = _lib.load_library()
+        d, o = self.latent_dim, self.out_dim
+        rows = k * b
+        inv = 1.0 / loss_scale
+        last = _AR_BLOCKS - 1
+        self._arena.reset()
+        self._found.zero_()
+        with torch.cuda.device(self._device):
+            # ---------------- forward: the observed strips, the teacher, then the rollout keeping what BPTT needs ----------------
+            phi_obs = self._phi(feats[:, :i_len], b, i_len)
+            phi_all = self._phi(feats, b, t)
+            seq = torch.empty(((i_len + k) * b, d), dtype=self._dtype, device=self._device)
+            seq[: i_len * b].view(i_len, b, d).copy_(phi_obs.view(b, i_len, d).transpose(0, 1))
+            saved: List[List[tuple]] = []
+            for j in range(k):
+                n = i_len + j
+                x, step = seq[: n * b], []
+                for i in range(_AR_BLOCKS):
+                    p = f"f_AR.blocks.{i}"
+                    r1 = self._gn_relu_rows_tm(x, b, n, 0, p + ".gn1")
+                    h = self._gemm(r1, p + ".conv1", relu=False)
+                    m = masks[j][p] if masks is not None else None
+                    if m is not None:
+                        self._mask_scale(h, m, keep_scale)
+                    if i < last:
+                        r2 = self._gn_relu_rows_tm(h, b, n, 0, p + ".gn2")
+                        xo = self._gemm(r2, p + ".conv2", relu=False, residual=x)
+                    else:
+                        r2 = self._gn_relu_rows_tm(h, b, n, n - 1, p + ".gn2")
+                        xo = self._gemm(r2, p + ".conv2", relu=False, residual=x[(n - 1) * b:], out=seq[n * b: (n + 1) * b])
+                    step.append((x, r1, h, r2, m))
+                    x = xo
+                saved.append(step)
+            fut = seq[i_len * b:]                                                 # (k*B, D) time-major
+            # ---------------- the frozen regressor on the predicted strips ----------------
+            y = self._dev["y0"].view(1, o).expand(rows, o).contiguous()
+            reg = []
+            for _ in range(_REG_ITERS):
+                inp = torch.empty((rows, self._dp), dtype=self._dtype, device=self._device)
+                _lib.check(lib.r50_op_concat_pad(fut.data_ptr(), d, y.data_ptr(), o, rows, inp.data_ptr(), self._dp, self._et,
+                                                 self._stream()), None, "r50_op_concat_pad")
+                h1 = self._gemm(inp, "mlp0", relu=True)
+                h2 = self._gemm(h1, "mlp3", relu=True)
+                dy = self._gemm(h2, "mlp5", relu=False)
+                _lib.check(lib.r50_op_add_rows(y.data_ptr(), o, dy.data_ptr(), self._op, rows, self._et, self._stream()), None, "r50_op_add_rows")
+                reg.append((h1, h2))
+            # ---------------- losses and their gradients into dseq (fp32, time-major) ----------------
+            gt = joints3d.to(torch.float32).contiguous()
+            dyacc = torch.empty((rows, o), dtype=torch.float32, device=self._device)
+            losses = torch.empty(3, dtype=torch.float32, device=self._device)
+            _lib.check(lib.r50_op_rollout_pose_loss_grad(y.data_ptr(), gt.data_ptr(), b, k, t, i_len, self.joints_num, loss_scale,
+                                                         dyacc.data_ptr(), losses.data_ptr(), self._stream()), None,
+                       "r50_op_rollout_pose_loss_grad")
+            dseq = torch.zeros(((i_len + k) * b, d), dtype=torch.float32, device=self._device)
+            dfut = dseq[i_len * b:]
+            g5 = torch.empty((rows, self._op), dtype=self._dtype, device=self._device)
+            for i in reversed(range(_REG_ITERS)):
+                h1, h2 = reg[i]
+                _lib.check(lib.r50_op_cast_rows(dyacc.data_ptr(), rows, o, g5.data_ptr(), self._op, self._et, self._stream()), None, "r50_op_cast_rows")
+                dh2 = self._mm(g5, self._wt["mlp5.w"])
+                self._relu_bwd(dh2, h2, 1.0)
+                dh1 = self._mm(dh2, self._wt["mlp3.w"])
+                self._relu_bwd(dh1, h1, 1.0)
+                dinp = self._mm(dh1, self._wt["mlp0.w"])                       # (rows, Dp) = [dfut | dy | 0]
+                _lib.check(lib.r50_op_add_rows(dfut.data_ptr(), d, dinp.data_ptr(), self._dp, rows, self._et, self._stream()), None,
+                           "r50_op_add_rows")
+                if i > 0:
+                    _lib.check(lib.r50_op_add_rows(dyacc.data_ptr(), o, dinp.data_ptr() + 2 * d, self._dp, rows, self._et, self._stream()),
+                               None, "r50_op_add_rows")
+            part = torch.empty(rows, dtype=torch.float32, device=self._device)
+            _lib.check(lib.r50_op_rollout_latent_grad(fut.data_ptr(), phi_all.data_ptr(), b, k, t, i_len, d, self.lambda_latent, loss_scale,
+                                                      dfut.data_ptr(), losses[2:].data_ptr(), part.data_ptr(), self._et, self._stream()),
+                       None, "r50_op_rollout_latent_grad")
+            # ---------------- BPTT: the steps last first ----------------
+            for j in reversed(range(k)):
+                n = i_len + j
+                acc = j < k - 1                                                # the first step processed writes the gradients
+                self._check_arena()
+                self._arena.reset()
+                dnew = self._arena.take(b, d)                                  # the appended strip's gradient, 16-bit
+                _lib.check(lib.r50_op_cast_rows(dseq[n * b:].data_ptr(), b, d, dnew.data_ptr(), d, self._et, self._stream()), None,
+                           "r50_op_cast_rows")
+                dx = None
+                for i in reversed(range(_AR_BLOCKS)):
+                    p = f"f_AR.blocks.{i}"
+                    xin, r1, h, r2, m = saved[j][i]
+                    if i == last:
+                        self._wgrad(p + ".conv2.w", dnew, r2, inv, acc, bias=p + ".conv2.b")
+                        dr2 = self._mm(dnew, self._wt[p + ".conv2.w"])         # (B, 3D)
+                        dh = self._gn_bwd_tm(dr2, h, b, n, n - 1, p + ".gn2", None, inv, acc)
+                        skip = torch.zeros((n * b, d), dtype=self._dtype, device=self._device)
+                        skip[(n - 1) * b:].copy_(dnew)                          # the residual reaches frame L-1 only
+                    else:
+                        self._wgrad(p + ".conv2.w", dx, r2, inv, acc, bias=p + ".conv2.b")
+                        dr2 = self._mm(dx, self._wt[p + ".conv2.w"])
+                        dh = self._gn_bwd_tm(dr2, h, b, n, 0, p + ".gn2", None, inv, acc)
+                        skip = dx
+                    if m is not None:
+                        self._mask_scale(dh, m, keep_scale)
+                    self._wgrad(p + ".conv1.w", dh, r1, inv, acc, bias=p + ".conv1.b")
+                    dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
+                    dx = self._gn_bwd_tm(dr1, xin, b, n, 0, p + ".gn1", skip, inv, acc)
+                if j > 0:                                                      # rows of predicted strips; the observed ones are frozen
+                    _lib.check(lib.r50_op_add_rows(dseq[i_len * b:].data_ptr(), d, dx[i_len * b:].data_ptr(), d, (n - i_len) * b, self._et,
+                                                   self._stream()), None, "r50_op_add_rows")
+            self._check_arena()
+        return y.view(k, b, self.joints_num, 3).transpose(0, 1).contiguous(), losses
+
+    def rollout_train_step(self, feats: torch.Tensor, joints3d: torch.Tensor, input_len: int, k: int, optim: AdamW,
+                           scaler: Optional[GradScaler] = None, masks: Optional[List[Dict[str, torch.Tensor]]] = None,
+                           group=None) -> Tuple[float, float, bool]:
+        """One step of the rollout objective (``train_step``'s contract): forward + loss, scaled BPTT, inf check, AdamW over f_AR,
+        scale update.  Returns (loss, mpjpe, skipped); ``last_losses`` holds loss, l3d, l_lat and mpjpe of the step."""
+        scale = scaler.get_scale() if scaler is not None else 1.0
+        _, losses = self.rollout_forward_backward(feats, joints3d, input_len, k, scale, masks)
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            all_reduce_gradients(self.flat_grad, group)
+            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
+                       "r50_op_check_finite")
+            sync_overflow_flag(self._found, group)
+            found = bool(self._found.item())
+            if not found:
+                optim.step(self._found)
+                self._refresh_transposes()
+            if scaler is not None:
+                scaler.update(found)
+            l3d, mpjpe, l_lat = losses.tolist()
+        loss = l3d + self.lambda_latent * l_lat
+        self.last_losses = {"loss": loss, "l3d": l3d, "l_lat": l_lat, "mpjpe": mpjpe}
+        return loss, mpjpe, found
+
     def future_losses(self, feats: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Eval-mode forward of one batch: ([l3d_hat, mpjpe_hat, l_lat] fp32 device tensor, joints_phi (B,T,J,3) fp32).  The launches
         of ``__call__(feats, predict_future=True)``; the losses by the phase-2 loss kernels (their gradients go to scratch)."""
@@ -385,15 +600,69 @@ def build_parser() -> argparse.ArgumentParser:
                    help="phase-1 checkpoint (its 'model') or plain state dict to start from; required unless --resume names an existing file")
     p.add_argument("--lambda-latent", type=float, default=LAMBDA_LATENT,
                    help="weight of the latent loss mean((phi_hat - phi)^2) over frames >= 1 (no run has measured a good value)")
+    # The rollout objective's flags.  Their defaults are applied by parse_args only for --objective rollout,
+    # so a teacher run's namespace -- and the "args" its checkpoints record -- is what it was before these flags existed.
+    p.add_argument("--objective", choices=("teacher", "rollout"), default=argparse.SUPPRESS,
+                   help="teacher (default): one teacher-forced step over the clip (section I); rollout: f_AR on its own k-step rollouts")
+    p.add_argument("--input-len", type=int, default=argparse.SUPPRESS, help=f"rollout: observed frames I (default {INPUT_LEN})")
+    p.add_argument("--pred-len", type=int, default=argparse.SUPPRESS, help=f"rollout: predicted frames P (default {PRED_LEN})")
+    p.add_argument("--curriculum-steps", type=int, default=argparse.SUPPRESS,
+                   help=f"rollout: epochs over which k grows from 1 to P, 0 = k = P throughout (default {CURRICULUM_STEPS})")
     return p
 
 
+ROLLOUT_DEFAULTS = {"objective": "teacher", "input_len": INPUT_LEN, "pred_len": PRED_LEN, "curriculum_steps": CURRICULUM_STEPS}
+
+
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    """The driver's arguments.  With ``--objective rollout`` the namespace holds objective, input_len, pred_len and
+    curriculum_steps (defaults ``ROLLOUT_DEFAULTS``); without it, none of them."""
     p = build_parser()
     args = p.parse_args(argv)
     if not args.init and not (args.resume and os.path.isfile(args.resume)):
         p.error("--init is required unless --resume names an existing checkpoint")
+    if getattr(args, "objective", "teacher") == "rollout":
+        for k, v in ROLLOUT_DEFAULTS.items():
+            if not hasattr(args, k):
+                setattr(args, k, v)
+        if args.input_len < 1 or args.pred_len < 1 or args.curriculum_steps < 0:
+            p.error("--input-len and --pred-len must be >= 1, --curriculum-steps >= 0")
+    else:
+        extra = [k for k in ("input_len", "pred_len", "curriculum_steps") if hasattr(args, k)]
+        if extra:
+            p.error(f"--{extra[0].replace('_', '-')} applies to --objective rollout only")
     return args
+
+
+def curriculum_k(epoch: int, pred_len: int, curriculum_steps: int) -> int:
+    """Rollout steps of epoch ``epoch`` (0-based): min(P, 1 + (e * P) // C), and P throughout for C = 0."""
+    p, c = int(pred_len), int(curriculum_steps)
+    if c <= 0:
+        return p
+    return min(p, 1 + (int(epoch) * p) // c)
+
+
+def train_rollout_epoch(head: ARTrainableHead, store, sampler, optim: AdamW, scaler: Optional[GradScaler], seed: int, epoch: int,
+                        input_len: int, k: int, log_every: int = 500) -> Tuple[float, float, int, int, Dict[str, float]]:
+    """``train.train_epoch`` for the rollout objective: one ``rollout_train_step`` per batch of ``sampler`` (its epoch already set),
+    masks from ``make_rollout_dropout_masks`` with ``dropout_generator(seed, epoch, it)``.  Returns (mean loss, mean mpjpe, applied
+    steps, skipped steps, means of l3d / l_lat / mpjpe)."""
+    head.train()
+    sums = {"loss": 0.0, "l3d": 0.0, "l_lat": 0.0, "mpjpe": 0.0}
+    n_batches = skipped = 0
+    for it, idx in enumerate(sampler):
+        feats, joints3d = store.get_batch(idx)[:2]
+        masks = head.make_rollout_dropout_masks(feats.shape[0], input_len, k, generator=dropout_generator(seed, epoch, it, head._device))
+        _, _, found = head.rollout_train_step(feats, joints3d, input_len, k, optim, scaler, masks=masks)
+        for key in sums:
+            sums[key] += head.last_losses[key]
+        n_batches += 1
+        skipped += int(found)
+        if log_every > 0 and (it + 1) % log_every == 0:
+            print(f"[AR]  iter {it + 1:05d}/{len(sampler):05d} | k {k} | loss {sums['loss'] / n_batches:.6f} | "
+                  f"mpjpe {sums['mpjpe'] / n_batches:.3f}")
+    means = {key: v / max(n_batches, 1) for key, v in sums.items()}
+    return means["loss"], means["mpjpe"], n_batches - skipped, skipped, means
 
 
 def main(argv: Optional[List[str]] = None) -> float:
@@ -405,6 +674,11 @@ def main(argv: Optional[List[str]] = None) -> float:
     from .samplers import MixedShardBatchSampler
 
     args = parse_args(argv)
+    rollout = getattr(args, "objective", "teacher") == "rollout"
+    if rollout:                                # the clip length rule of forecast.evaluate_rollout, before any other work
+        clip_len = int(DeviceFeatureStore(args.val, subjects=args.val_subjects, max_clips=1, device="cpu").feats.shape[1])
+        if args.input_len + args.pred_len > clip_len:
+            raise ValueError(f"--input-len + --pred-len = {args.input_len + args.pred_len} exceeds the stores' clip length {clip_len}")
     if not torch.cuda.is_available():
         raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -431,6 +705,9 @@ def main(argv: Optional[List[str]] = None) -> float:
         best_val = float(ckpt.get("best_val", best_val))
         print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
 
+    if rollout:
+        return _main_rollout(args, head, optim, scaler, schedule, train_set, val_set, sampler, start_epoch, best_val, device,
+                             latent_dim, number_blocks)
     print("===== Phase-2 training (f_AR) =====")
     print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
     print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
@@ -468,6 +745,58 @@ def main(argv: Optional[List[str]] = None) -> float:
             break
     print("\nDone.")
     print(f"Best val future MPJPE: {best_val:.3f}")
+    return best_val
+
+
+def _main_rollout(args, head, optim, scaler, schedule, train_set, val_set, sampler, start_epoch, best_val, device, latent_dim,
+                  number_blocks) -> float:
+    """``main``'s epoch loop for the rollout objective: training with k(e) steps, validation by ``forecast.evaluate_rollout`` at the
+    full P, ``best.pt`` and early stopping on the validation rollout's mpjpe_mean."""
+    from .forecast import evaluate_rollout
+    i_len, p_len, c = args.input_len, args.pred_len, args.curriculum_steps
+    no_improve_epochs = 0
+    print("===== Phase-2 training (f_AR), rollout objective =====")
+    print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
+    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
+    print(f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_latent: {args.lambda_latent} | seed: {args.seed}")
+    print(f"Input len: {i_len} | pred len: {p_len} | curriculum steps: {c}")
+    print("======================================================")
+    for epoch in range(start_epoch, args.epochs):
+        k = curriculum_k(epoch, p_len, c)
+        sampler.set_epoch(epoch)
+        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
+        print(f"\nEpoch {epoch + 1}/{args.epochs} (k = {k})")
+        t0 = time.time()
+        epoch_lr = optim.lr
+        tr_loss, tr_mpjpe, steps, skipped, tr = train_rollout_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, i_len, k,
+                                                                    args.log_every)
+        va = evaluate_rollout(head, val_set, i_len, p_len, args.batch_size)
+        schedule.step()
+        optim.lr = schedule.lr
+        va_mean = va["mpjpe_mean"]
+        print(f"Train: loss={tr_loss:.6f} | l3d={tr['l3d']:.6f} | l_lat={tr['l_lat']:.6f} | mpjpe={tr_mpjpe:.3f}")
+        print(f"Val:   rollout mpjpe @1={va['mpjpe'][0]:.3f} | @{min(10, p_len)}={va['mpjpe'][min(10, p_len) - 1]:.3f} | "
+              f"@{p_len}={va['mpjpe'][-1]:.3f} | mean={va_mean:.3f}")
+        print(f"Epoch time: {time.time() - t0:.2f}s")
+        print(json.dumps({"epoch": epoch, "lr": epoch_lr, "k": k, "train_loss": tr_loss, "train_l3d": tr["l3d"], "train_l_lat": tr["l_lat"],
+                          "train_mpjpe": tr_mpjpe, "steps": steps, "skipped": skipped, "val_mpjpe_1": va["mpjpe"][0],
+                          "val_mpjpe_10": va["mpjpe"][min(10, p_len) - 1], f"val_mpjpe_{p_len}": va["mpjpe"][-1], "val_mpjpe_mean": va_mean}))
+
+        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
+        if (best_val - va_mean) > args.early_stop_min_delta:
+            best_val = va_mean
+            no_improve_epochs = 0
+            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
+            print(f"New best val rollout MPJPE: {best_val:.3f} (saved best.pt)")
+        else:
+            no_improve_epochs += 1
+            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
+                  f"(best {best_val:.3f}, current {va_mean:.3f})")
+        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
+            print(f"Early stopping triggered at epoch {epoch + 1}. Best val rollout MPJPE: {best_val:.3f}")
+            break
+    print("\nDone.")
+    print(f"Best val rollout MPJPE: {best_val:.3f}")
     return best_val
 
 

@@ -366,6 +366,26 @@ int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int
 int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
                           void* dar, float* loss_lat, float* row_part, int et, void* stream);
 
+/* Lifting head, rollout training (f_AR trained on its own multi-step rollouts).  Time-major buffers: row
+ * h*b + b' is frame (or horizon) h of sample b'.
+ *  r50_op_gn_relu_causal3_tm_bwd: backward of r50_op_gn_relu_causal3_tm.  dr ((t-t0)*b, 3c) = the gradient of exactly the rows the
+ *    forward emitted; x, dx (t*b, c) time-major, dx over ALL t frames [+ add (t*b, c)]; dgamma_part / dbeta_part (b,c) fp32 as in
+ *    r50_op_gn_relu_causal3_bwd.  0 <= t0 < t, c % groups == 0, c / groups <= 256.  With t0 = 0 the result is bit-equal to
+ *    r50_op_gn_relu_causal3_bwd on the batch-major transpose.
+ *  r50_op_rollout_pose_loss_grad: pred (k*b, joints, 3) fp32 time-major against gt (b, t_gt, joints, 3) fp32 at frames i0 .. i0+k-1:
+ *    dy (k*b, joints, 3) = 2 (pred - gt) / n * loss_scale, n = k*b*joints*3; loss2 = [mean squared error, MPJPE] over the k horizons.
+ *  r50_op_rollout_latent_grad: fut (k*b, d) et time-major against the teacher phi (b, t_phi, d) et batch-major at frames i0 ..:
+ *    dfut (k*b, d) fp32 += lambda * 2 (fut - phi) / n_l * loss_scale, n_l = k*b*d; loss_lat[0] = mean (fut - phi)^2; row_part: k*b
+ *    floats of device scratch.  d % 8 == 0; fut, phi and dfut 16-byte aligned.
+ * The reductions sum in a fixed order without atomics: the same bits on every run.  Arguments are checked before any launch. */
+int r50_op_gn_relu_causal3_tm_bwd(const void* dr, const void* x, int b, int t, int t0, int c, int groups, const float* gamma,
+                                  const float* beta, float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et,
+                                  void* stream);
+int r50_op_rollout_pose_loss_grad(const float* pred, const float* gt, int b, int k, int t_gt, int i0, int joints, float loss_scale,
+                                  float* dy, float* loss2, void* stream);
+int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, int t_phi, int i0, int d, float lambda, float loss_scale,
+                               float* dfut, float* loss_lat, float* row_part, int et, void* stream);
+
 /* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
 int r50_op_avgpool(const void* x_nhwc_bf16, int n, int hw, int c, float* y_f32, void* stream);
 
