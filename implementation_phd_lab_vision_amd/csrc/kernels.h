@@ -4299,6 +4299,171 @@ __global__ __launch_bounds__(256) void horizon_metrics_kernel(const float* __res
     }
 }
 
+// ---- Evaluation protocols ----------------------------------------------------------------------------------
+// Per pose, X the ground truth and Y the prediction (J x 3 fp32, computed in fp64): P1 = (1/J) sum_j |(Y_j - Y_r) - (X_j - X_r)| and
+// P2 = (1/J) sum_j |a R (Y_j - muY) + muX - X_j| with (a, R) the least-squares proper similarity (Umeyama 1991).  R comes from Horn's
+// quaternion form: with S_uv = sum_j Y0_j[u] X0_j[v] of the centred poses, the unit eigenvector q of the largest eigenvalue lambda of the
+// symmetric, traceless 4x4 matrix N(S) is the optimal proper rotation, and lambda = max over proper R of sum_j X0_j . R Y0_j = tr(D S) of
+// the SVD form, so a = lambda / sum_j |Y0_j|^2.  No reflection handling and no completion of U: a rank-deficient S (a collinear or
+// planar pose, joints that coincide) still gives an optimal proper R.  a = 0 when either pose has no spread (the least-squares limit).
+// The eigen-solve is a cyclic Jacobi in fp64, at most POSE_JACOBI_SWEEPS sweeps of the six pairs, left once the off-diagonal mass is
+// below 1e-34 of N's squared Frobenius norm (it converges quadratically: a few sweeps).  Loops are bounded by J and the sweep limit.
+#define POSE_JACOBI_SWEEPS 16
+
+// One Jacobi rotation of the symmetric a on the pair (P, Q), zeroing a[P][Q]; v (columns: eigenvectors) accumulates it.
+template <int P, int Q>
+__host__ __device__ inline void jacobi4_rotate(double (&a)[4][4], double (&v)[4][4]) {
+    const double apq = a[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));          // the smaller root, |angle| <= pi/4; theta = inf gives t = 0
+    if (theta < 0.0) t = -t;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    a[P][P] -= t * apq;
+    a[Q][Q] += t * apq;
+    a[P][Q] = 0.0;
+    a[Q][P] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r != P && r != Q) {
+            const double arp = a[r][P], arq = a[r][Q];
+            a[r][P] = a[P][r] = c * arp - s * arq;
+            a[r][Q] = a[Q][r] = s * arp + c * arq;
+        }
+        const double vrp = v[r][P], vrq = v[r][Q];
+        v[r][P] = c * vrp - s * vrq;
+        v[r][Q] = s * vrp + c * vrq;
+    }
+}
+
+// P1 and P2 of one pose: y (prediction) and x (ground truth) point at J x 3 fp32 values, 0 <= root < J.
+__host__ __device__ inline void pose_protocol_errors(const float* __restrict__ y, const float* __restrict__ x, int J, int root, double& p1,
+                                                     double& p2) {
+    double my[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < J; ++j) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            my[c] += (double)y[3 * j + c];
+            mx[c] += (double)x[3 * j + c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        my[c] /= (double)J;
+        mx[c] /= (double)J;
+    }
+    const double yr[3] = {(double)y[3 * root], (double)y[3 * root + 1], (double)y[3 * root + 2]};
+    const double xr[3] = {(double)x[3 * root], (double)x[3 * root + 1], (double)x[3 * root + 2]};
+    double s[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    double sy = 0.0, sx = 0.0, e1 = 0.0;
+    for (int j = 0; j < J; ++j) {
+        double y0[3], x0[3], d2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double yv = (double)y[3 * j + c], xv = (double)x[3 * j + c];
+            const double d = (yv - yr[c]) - (xv - xr[c]);
+            d2 += d * d;
+            y0[c] = yv - my[c];
+            x0[c] = xv - mx[c];
+            sy += y0[c] * y0[c];
+            sx += x0[c] * x0[c];
+        }
+        e1 += sqrt(d2);
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+            for (int v = 0; v < 3; ++v) s[u][v] += y0[u] * x0[v];
+    }
+    double n[4][4] = {{s[0][0] + s[1][1] + s[2][2], s[1][2] - s[2][1], s[2][0] - s[0][2], s[0][1] - s[1][0]},
+                      {s[1][2] - s[2][1], s[0][0] - s[1][1] - s[2][2], s[0][1] + s[1][0], s[2][0] + s[0][2]},
+                      {s[2][0] - s[0][2], s[0][1] + s[1][0], -s[0][0] + s[1][1] - s[2][2], s[1][2] + s[2][1]},
+                      {s[0][1] - s[1][0], s[2][0] + s[0][2], s[1][2] + s[2][1], -s[0][0] - s[1][1] + s[2][2]}};
+    double ev[4][4] = {{1.0, 0.0, 0.0, 0.0}, {0.0, 1.0, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};
+    double fro2 = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) fro2 += n[u][v] * n[u][v];
+    for (int sweep = 0; sweep < POSE_JACOBI_SWEEPS; ++sweep) {
+        const double off = n[0][1] * n[0][1] + n[0][2] * n[0][2] + n[0][3] * n[0][3] + n[1][2] * n[1][2] + n[1][3] * n[1][3] +
+                           n[2][3] * n[2][3];
+        if (off <= 1e-34 * fro2) break;
+        jacobi4_rotate<0, 1>(n, ev);
+        jacobi4_rotate<0, 2>(n, ev);
+        jacobi4_rotate<0, 3>(n, ev);
+        jacobi4_rotate<1, 2>(n, ev);
+        jacobi4_rotate<1, 3>(n, ev);
+        jacobi4_rotate<2, 3>(n, ev);
+    }
+    double lam = n[0][0], q[4] = {ev[0][0], ev[1][0], ev[2][0], ev[3][0]};       // the largest eigenvalue (first on ties)
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+        if (n[i][i] > lam) {
+            lam = n[i][i];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = ev[u][i];
+        }
+    }
+    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q[u] /= qn;
+    const double w = q[0], qx = q[1], qy = q[2], qz = q[3];
+    const double r[3][3] = {{w * w + qx * qx - qy * qy - qz * qz, 2.0 * (qx * qy - w * qz), 2.0 * (qx * qz + w * qy)},
+                            {2.0 * (qx * qy + w * qz), w * w - qx * qx + qy * qy - qz * qz, 2.0 * (qy * qz - w * qx)},
+                            {2.0 * (qx * qz - w * qy), 2.0 * (qy * qz + w * qx), w * w - qx * qx - qy * qy + qz * qz}};
+    const double a = (sy > 0.0 && sx > 0.0) ? lam / sy : 0.0;
+    double e2 = 0.0;
+    for (int j = 0; j < J; ++j) {
+        const double y0[3] = {(double)y[3 * j] - my[0], (double)y[3 * j + 1] - my[1], (double)y[3 * j + 2] - my[2]};
+        double d2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double h = a * (r[c][0] * y0[0] + r[c][1] * y0[1] + r[c][2] * y0[2]) + mx[c] - (double)x[3 * j + c];
+            d2 += h * h;
+        }
+        e2 += sqrt(d2);
+    }
+    p1 = e1 / (double)J;
+    p2 = e2 / (double)J;
+}
+
+// The grouped protocol sums of one batch: pred (B, P, J, 3) scores frames i0 .. i0+P-1 of gt (B, Tgt, J, 3), group (B) in [0, G).
+// Workgroup (k, g) = blockIdx.x (k fastest) ADDS acc[(g*P + k)*2 + 0] += the P1 sum and acc[(g*P + k)*2 + 1] += the P2 sum over the
+// clips of group g at frame k; workgroup (0, g) adds acc[2*G*P + g] += the clip count.  Thread t aligns the poses of the clips
+// b = t (mod 256) with group[b] == g, one whole pose at a time, so every pose is aligned exactly once across the grid; per-thread fp64
+// partials, then a fixed fp64 tree: every workgroup owns its slots, no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void pose_protocols_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                             const int* __restrict__ group, int B, int P, int Tgt, int i0, int J, int root,
+                                                             int G, double* __restrict__ acc) {
+    __shared__ double red[3][256];
+    const int k = blockIdx.x % P, g = blockIdx.x / P;
+    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        if (group[b] != g) continue;
+        double e1, e2;
+        pose_protocol_errors(pred + ((size_t)b * P + k) * J * 3, gt + ((size_t)b * Tgt + i0 + k) * J * 3, J, root, e1, e2);
+        s1 += e1;
+        s2 += e2;
+        cnt += 1.0;
+    }
+    red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2; red[2][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+            red[2][threadIdx.x] += red[2][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const size_t slot = ((size_t)g * P + k) * 2;
+        acc[slot] += red[0][0];
+        acc[slot + 1] += red[1][0];
+        if (k == 0) acc[2 * (size_t)G * P + g] += red[2][0];
+    }
+}
+
 // ---- Phase 2: training f_AR (DESIGN.md "f next #2") ----------------------------------------------------
 // Future-pose loss of the phase-2 step: l3d_hat = mean over frames s >= 1 of (y_hat - gt)^2.  Frame 0 has no prediction (phi_hat[:, 0]
 // is the constant 0), so dy = 0 there and dy = 2 (y_hat - gt) / n * loss_scale elsewhere, n = b*(t-1)*joints*3 (the arithmetic of

@@ -72,6 +72,10 @@ class DeviceFeatureStore:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in (self.feats, self.joints3d, self.joints2d, self.K))
 
+    def item_actions(self) -> List[str]:
+        """Item i's ``action`` from the index entry of its clip (the name as stored, trial suffix included), in item order."""
+        return [str(c["action"]) for c, _ in self._items]
+
     def __getitem__(self, idx: int):
         """The reference dataset's item (src/dataset_features.py:112-126), tensors on ``self.device``."""
         row = self._row_host[idx]

@@ -6,7 +6,10 @@ It scores a checkpoint on the test subject (S9) with ``train.evaluate`` over the
 visualisation scripts: the clips' video, ground-truth and predicted 3D joints, 2D joints, intrinsics, meta and the test metrics.
 With ``--pred-len P`` (default 0: off) it also forecasts: ``forecast.evaluate_rollout`` over the test set
 prints MPJPE per horizon, and the ``.npz`` gains ``predicted_future3djoints`` (the dumped clips' P future poses after
-``--input-len`` observed frames), ``future_mpjpe`` (P,) and ``rollout_lens`` [I, P].
+``--input-len`` observed frames), ``future_mpjpe`` (P,) and ``rollout_lens`` [I, P].  With ``--protocols`` (default off) it also scores
+the H3.6M protocols per action: ``protocols.evaluate_protocols`` over every test clip once, in store order
+(not the loader's ``drop_last`` batches), prints root-relative MPJPE (P1) and PA-MPJPE (P2) for all clips, the action mean and each
+action (and per horizon with ``--pred-len``), and the ``.npz`` gains the ``protocol_*`` keys.
 
 Two differences from running the reference's script as it stands:
 
@@ -66,6 +69,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--input-len", type=int, default=INPUT_LEN, help="observed frames of the rollout (src/config.py INPUT_LEN)")
     p.add_argument("--pred-len", type=int, default=0,
                    help="frames to forecast with f_AR and score per horizon (INTEGRATION.md section J); 0 = off")
+    p.add_argument("--protocols", action="store_true",
+                   help="also score root-relative MPJPE (P1) and PA-MPJPE (P2) per action over every test clip, and per horizon "
+                        "with --pred-len (INTEGRATION.md section L)")
     return p
 
 
@@ -197,6 +203,39 @@ def dump_videos(metas: Sequence[dict], preprocessed_root: str, reader: Callable,
     return np.stack(host_clips, axis=0)
 
 
+def protocol_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--protocols`` from an ``evaluate_protocols`` result: the ``Protocol metrics`` line (all clips and the
+    action mean), one indented line per action, and with ``pred_len > 0`` the ``Rollout protocol metrics`` line (all clips, horizons
+    1, 5, 10 and P as the ``Rollout metrics`` line).  Millimetres."""
+    clips = res["clips"]
+    ra, rm = res["recon_all"], res["recon_mean"]
+    lines = [f"Protocol metrics | clips {int(clips.sum())} | actions {len(res['group_names'])} | all: p1 (mm) {ra[0] * 1000.0:.2f} "
+             f"| p2 (mm) {ra[1] * 1000.0:.2f} | action mean: p1 (mm) {rm[0] * 1000.0:.2f} | p2 (mm) {rm[1] * 1000.0:.2f}"]
+    for name, c, (p1, p2) in zip(res["group_names"], clips, res["recon"]):
+        lines.append(f"  {name} | clips {int(c)} | p1 (mm) {p1 * 1000.0:.2f} | p2 (mm) {p2 * 1000.0:.2f}")
+    if pred_len > 0:
+        fa = res["future_all"]
+        hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+        at = [" | ".join(f"@{h}: {fa[h - 1, m] * 1000.0:.2f}" for h in hs) for m in (0, 1)]
+        lines.append(f"Rollout protocol metrics | input {input_len} | pred {pred_len} | clips {int(clips.sum())} | p1 (mm) {at[0]} "
+                     f"| p2 (mm) {at[1]}")
+    return lines
+
+
+def protocol_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--protocols``: ``protocol_actions`` (G,) str, ``protocol_clips`` (G,) int64, ``protocol_recon`` (G, 2)
+    and ``protocol_recon_all`` (2,) fp32 [p1, p2] in metres; with a rollout ``protocol_future`` (G, P, 2), ``protocol_future_all``
+    (P, 2)."""
+    out = {"protocol_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "protocol_clips": np.asarray(res["clips"], dtype=np.int64),
+           "protocol_recon": np.asarray(res["recon"], dtype=np.float32),
+           "protocol_recon_all": np.asarray(res["recon_all"], dtype=np.float32)}
+    if "future" in res:
+        out["protocol_future"] = np.asarray(res["future"], dtype=np.float32)
+        out["protocol_future_all"] = np.asarray(res["future_all"], dtype=np.float32)
+    return out
+
+
 def main(argv: Optional[List[str]] = None) -> str:
     """``python src/results.py`` on one MI355X.  Returns the path of the written ``.npz``."""
     from .feature_store import DeviceFeatureStore
@@ -231,6 +270,13 @@ def main(argv: Optional[List[str]] = None) -> str:
         at = " | ".join(f"@{k}: {mm[k - 1] * 1000.0:.2f}" for k in sorted({h for h in (1, 5, 10, args.pred_len) if h <= args.pred_len}))
         print(f"Rollout metrics | input {args.input_len} | pred {args.pred_len} | clips {rollout['clips']} | mpjpe (mm) {at} "
               f"| mean: {rollout['mpjpe_mean'] * 1000.0:.2f}")
+    protocols = None
+    if args.protocols:                       # every test clip once, in store order (not the loader's drop_last batches)
+        from .protocols import action_groups, evaluate_protocols
+        names, ids = action_groups(test_set.item_actions())
+        protocols = evaluate_protocols(head, test_set, ids, names, args.input_len if args.pred_len > 0 else 0, args.pred_len)
+        for line in protocol_lines(protocols, args.input_len, args.pred_len):
+            print(line)
 
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
@@ -249,6 +295,8 @@ def main(argv: Optional[List[str]] = None) -> str:
         extra = {"predicted_future3djoints": head.rollout(feats[:n_save], args.input_len, args.pred_len)[1].cpu().numpy(),
                  "future_mpjpe": np.array(rollout["mpjpe"], dtype=np.float32),
                  "rollout_lens": np.array([args.input_len, args.pred_len], dtype=np.int64)}
+    if protocols is not None:
+        extra.update(protocol_arrays(protocols))
     np.savez_compressed(out_path, video=videos, joints3d=joints3d_np, predicted3djoints=pred,
                         joints2d=joints2d[:n_save].cpu().numpy(), K=k[:n_save].to(torch.float32).cpu().numpy(),
                         meta=np.array(list(metas[:n_save]), dtype=object),

@@ -352,6 +352,17 @@ int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int jo
  * joint, fp64 sums in a fixed order (no atomics: the same bits on every run). */
 int r50_op_horizon_metrics(const float* pred, const float* gt, int b, int p, int t_gt, int i0, int joints, double* acc, void* stream);
 
+/* Lifting head, the H3.6M evaluation protocols per group: pred (b,p,joints,3) fp32 scores frames
+ * i0 .. i0+p-1 of gt (b,t_gt,joints,3) fp32 (r50_op_horizon_metrics' indexing); group (b) int32 device values in [0,n_groups).  Per
+ * pose, in fp64: P1 = mean over joints of |(pred_j - pred_root) - (gt_j - gt_root)|, P2 = the same distance after the least-squares
+ * proper similarity fit of pred onto gt (Umeyama 1991; scale 0 when either pose has no spread).  ADDS acc[(g*p + k)*2 + 0] += the P1
+ * sum and acc[(g*p + k)*2 + 1] += the P2 sum over the clips of group g at frame k, acc[2*n_groups*p + g] += the clips of group g;
+ * acc: 2*n_groups*p + n_groups doubles of device memory.  Needs b, p, n_groups >= 1, 1 <= joints <= 64, 0 <= root < joints,
+ * 0 <= i0, i0 + p <= t_gt; checked before any launch.  One workgroup per (frame, group), one whole pose per thread, fp64 sums in a
+ * fixed order (no atomics: the same bits on every run). */
+int r50_op_pose_protocols(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
+                          int n_groups, double* acc, void* stream);
+
 /* Lifting head, phase 2 (training f_AR; DESIGN.md "f next #2").  The reference has no phase 2; this
  * project's definition: f_movie / f_3D frozen and run as at inference, loss = l3d_hat + lambda * l_lat over frames s >= 1.
  *  r50_op_future_pose_loss_grad: y_hat, gt, dy (b*t, joints, 3) fp32: dy = 2 (y_hat-gt) / n * loss_scale with n = b*(t-1)*joints*3,

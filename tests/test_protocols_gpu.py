@@ -1,0 +1,321 @@
+"""The H3.6M evaluation protocols on the MI355X: ``r50_op_pose_protocols`` against the numpy fp64 oracle
+(tests/protocols_reference.py, an SVD where the kernel runs Horn's quaternion form), its degenerate and invariance cases pose by pose,
+determinism, accumulation and refusals; ``protocols.evaluate_protocols`` against the oracle on the device's own head outputs and on the
+fp64 reference head; the results CLI's ``--protocols``.  CLI runs are fresh child processes under a time limit."""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from tests import protocols_reference as pr
+from tests import results_data as rd
+from tests.rollout_reference import rollout_reference
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = Path(__file__).resolve().parents[1]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from implementation_phd_lab_vision_amd import _lib
+    _lib.build_library()
+    return _lib.load_library()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _call(lib, pred, gt, i0, group, n_groups, root, acc):
+    b, p, j, _ = pred.shape
+    return lib.r50_op_pose_protocols(pred.data_ptr(), gt.data_ptr(), group.data_ptr(), b, p, gt.shape[1], i0, j, root, n_groups,
+                                     acc.data_ptr(), _stream())
+
+
+def _run(lib, pred, gt, i0, group, n_groups, root=0):
+    """One launch into a fresh accumulator; pred / gt / group numpy or CPU tensors.  Returns the fp64 sums on the host."""
+    pd, gd = torch.as_tensor(pred).to(DEV).contiguous(), torch.as_tensor(gt).to(DEV).contiguous()
+    grp = torch.as_tensor(np.asarray(group), dtype=torch.int32).to(DEV)
+    acc = torch.zeros(2 * n_groups * pd.shape[1] + n_groups, dtype=torch.float64, device=DEV)
+    assert _call(lib, pd, gd, i0, grp, n_groups, root, acc) == 0, lib.r50_last_error(None)
+    return acc.cpu().numpy()
+
+
+def _clips(rng, b, t, j):
+    """(B, T, J, 3) fp32 ground truth: a person a few metres from the camera, joints spread ~0.3 m, moving a little per frame."""
+    centre = rng.standard_normal((b, 1, 1, 3)) * np.array([1.0, 0.5, 0.5]) + np.array([0.0, 0.0, 4.5])
+    body = rng.standard_normal((b, 1, j, 3)) * 0.3
+    return (centre + body + rng.standard_normal((b, t, j, 3)) * 0.02).astype(np.float32)
+
+
+def _predictions(rng, gt, i0, p):
+    """Predictions of frames i0 .. i0+p-1: a per-clip similarity of the ground truth plus joint noise, so P1 and P2 both differ
+    from plain MPJPE."""
+    b, j = gt.shape[0], gt.shape[2]
+    out = np.empty((b, p, j, 3), dtype=np.float64)
+    for i in range(b):
+        r, a = pr.random_rotation(rng), rng.uniform(0.8, 1.25)
+        x = gt[i, i0:i0 + p].astype(np.float64)
+        c = x.mean(axis=(0, 1))
+        out[i] = a * (x - c) @ r.T + c + rng.standard_normal(3) * 0.1 + rng.standard_normal((p, j, 3)) * 0.04
+    return out.astype(np.float32)
+
+
+# ------------------------------------------------------------------ kernel ----------------------------------------------------
+@pytest.mark.parametrize("b,p,t_gt,i0,j,n_groups,root", [(5, 3, 7, 2, 17, 4, 0), (300, 2, 4, 1, 3, 3, 2), (7, 4, 4, 0, 1, 2, 0),
+                                                          (33, 5, 9, 4, 32, 6, 31), (2, 1, 1, 0, 17, 1, 0), (40, 40, 40, 0, 17, 15, 0)])
+def test_kernel_matches_oracle(lib, b, p, t_gt, i0, j, n_groups, root):
+    rng = np.random.default_rng(b * 1000 + j * 10 + p)
+    gt = _clips(rng, b, t_gt, j)
+    pred = _predictions(rng, gt, i0, p)
+    used = rng.permutation(n_groups)[:max(1, n_groups - 2)] if n_groups > 2 else np.arange(n_groups)   # some groups stay empty
+    group = rng.choice(used, size=b)
+    got = _run(lib, pred, gt, i0, group, n_groups, root)
+    want = pr.protocol_sums(pred, gt, i0, group, n_groups, root)
+    np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12)
+    counts = np.bincount(group, minlength=n_groups)
+    assert np.array_equal(got[2 * n_groups * p:], counts.astype(np.float64))
+    empty = np.flatnonzero(counts == 0)
+    assert np.all(got[:2 * n_groups * p].reshape(n_groups, p, 2)[empty] == 0.0)
+    if j > 3:                                       # the similarity fit removes the random rotations: P2 well below P1
+        sums = got[:2 * n_groups * p].reshape(n_groups, p, 2).sum(axis=(0, 1))
+        assert sums[1] < sums[0]
+
+
+def _degenerate_cases(rng, j=17):
+    """(name, pred, gt) single poses whose optimum is unique: degenerate predictions, an exact mirror, similarity transforms."""
+    gt = _clips(rng, 1, 1, j)[0, 0]
+    k = np.arange(j, dtype=np.float64) - 8.0
+    cases = [("zero", np.zeros((j, 3), np.float32), gt),
+             ("all_equal", np.tile(np.float32([0.25, -0.5, 3.75]), (j, 1)), gt),
+             ("collinear", (np.float32([1.0, 2.0, 3.0]) + np.outer(k / 8.0, [1.0, 2.0, -1.0])).astype(np.float32), gt),   # exact in fp32
+             ("planar", np.concatenate([rng.standard_normal((j, 2)), np.full((j, 1), 4.5)], axis=1).astype(np.float32), gt),
+             ("mirror", gt * np.float32([-1.0, 1.0, 1.0]), gt),
+             ("gt_all_equal", gt, np.tile(np.float32([0.1, 0.2, 4.0]), (j, 1)))]
+    for s in range(6):
+        r, a, t = pr.random_rotation(rng), rng.uniform(0.5, 2.0), rng.standard_normal(3)
+        cases.append((f"similarity{s}", (a * gt.astype(np.float64) @ r.T + t).astype(np.float32), gt))
+    return cases
+
+
+@pytest.mark.parametrize("root", [0, 9])
+def test_degenerate_and_invariance_cases_pose_by_pose(lib, root):
+    """One pose per group, so every slot of the accumulator is one pose's value; compared with the oracle within 1e-8 m."""
+    cases = _degenerate_cases(np.random.default_rng(7 + root))
+    n = len(cases)
+    pred = np.stack([c[1] for c in cases])[:, None]                 # (n, 1, J, 3)
+    gt = np.stack([c[2] for c in cases])[:, None]
+    got = _run(lib, pred, gt, 0, np.arange(n), n, root)
+    vals = got[:2 * n].reshape(n, 2)
+    assert np.isfinite(got).all() and np.array_equal(got[2 * n:], np.ones(n))
+    for i, (name, y, x) in enumerate(cases):
+        want = (pr.p1_pose(y, x, root), pr.p2_pose(y, x))
+        print(f"{name}: p1 {vals[i, 0]:.6e} (oracle {want[0]:.6e}) p2 {vals[i, 1]:.6e} (oracle {want[1]:.6e})")
+        assert abs(vals[i, 0] - want[0]) <= 1e-8 and abs(vals[i, 1] - want[1]) <= 1e-8, name
+        if name.startswith("similarity"):
+            assert vals[i, 1] <= 1e-6, name
+        if name == "mirror":
+            assert vals[i, 1] > 1e-2                                   # no reflections
+        if name in ("zero", "all_equal"):                              # a = 0: every joint on the ground truth's centroid
+            spread = np.linalg.norm(x.astype(np.float64) - x.astype(np.float64).mean(axis=0), axis=-1).mean()
+            assert abs(vals[i, 1] - spread) <= 1e-12
+        if name == "gt_all_equal":
+            assert vals[i, 1] == 0.0
+
+
+def test_deterministic_and_adds(lib):
+    rng = np.random.default_rng(11)
+    b, t, i0, p, j, g = 600, 6, 1, 5, 17, 5
+    gt = _clips(rng, b, t, j)
+    pd, gd = torch.from_numpy(_predictions(rng, gt, i0, p)).to(DEV), torch.from_numpy(gt).to(DEV)
+    grp = torch.from_numpy(rng.integers(0, g, size=b).astype(np.int32)).to(DEV)
+    runs = []
+    for _ in range(2):
+        acc = torch.zeros(2 * g * p + g, dtype=torch.float64, device=DEV)
+        assert _call(lib, pd, gd, i0, grp, g, 0, acc) == 0
+        runs.append(acc.cpu())
+    assert torch.equal(runs[0], runs[1])                               # fixed order: the same bits
+    acc = runs[0].to(DEV)
+    assert _call(lib, pd, gd, i0, grp, g, 0, acc) == 0                 # it ADDS
+    assert torch.equal(acc.cpu(), 2 * runs[0])
+
+
+def test_refusals_launch_nothing(lib):
+    from implementation_phd_lab_vision_amd import protocols
+    b, t, p, j, g = 4, 6, 3, 17, 2
+    pred = torch.zeros(b, p, j, 3, device=DEV)
+    gt = torch.zeros(b, t, j, 3, device=DEV)
+    grp = torch.zeros(b, dtype=torch.int32, device=DEV)
+    acc = torch.full((2 * g * p + g,), 7.0, dtype=torch.float64, device=DEV)
+    good = dict(pred=pred.data_ptr(), gt=gt.data_ptr(), group=grp.data_ptr(), b=b, p=p, t_gt=t, i0=1, joints=j, root=0, n_groups=g,
+                acc=acc.data_ptr())
+    assert lib.r50_op_pose_protocols(*good.values(), _stream()) == 0
+    torch.cuda.synchronize()
+    kept = acc.clone()
+    bad = [dict(b=0), dict(p=0), dict(n_groups=0), dict(joints=0), dict(joints=65), dict(root=-1), dict(root=j), dict(i0=-1),
+           dict(i0=t - p + 1), dict(t_gt=p - 1, i0=0), dict(pred=None), dict(gt=None), dict(group=None), dict(acc=None)]
+    for change in bad:
+        args = dict(good, **change)
+        assert lib.r50_op_pose_protocols(*args.values(), _stream()) != 0, change
+        assert b"r50_op_pose_protocols" in lib.r50_last_error(None)
+    torch.cuda.synchronize()
+    assert torch.equal(acc, kept)
+    with pytest.raises(ValueError, match=r"\[0, 2\)"):                 # the wrapper checks the group values on the host
+        protocols.add_protocol_sums(pred, gt, 1, torch.tensor([0, 1, 2, 0], dtype=torch.int32, device=DEV), g, acc)
+    with pytest.raises(ValueError):
+        protocols.add_protocol_sums(pred, gt, 1, torch.tensor([0, -1, 0, 0], dtype=torch.int32, device=DEV), g, acc)
+    with pytest.raises(ValueError):
+        protocols.add_protocol_sums(torch.zeros(b, p, 65, 3, device=DEV), torch.zeros(b, t, 65, 3, device=DEV), 1, grp, g, acc)
+    torch.cuda.synchronize()
+    assert torch.equal(acc, kept)
+    protocols.add_protocol_sums(pred, gt, 1, grp, g, acc)
+    assert not torch.equal(acc, kept)
+
+
+# ------------------------------------------------------------------ evaluation ------------------------------------------------
+@pytest.fixture(scope="module")
+def trees(tmp_path_factory):
+    base = tmp_path_factory.mktemp("protocols")
+    return rd.make_results_cache(base / "features"), rd.make_preprocessed_tree(base / "videos")
+
+
+def _head(d, nb, seed):
+    from implementation_phd_lab_vision_amd.model import PHDFor3DJoints
+    from oracle import lifting_oracle as lo
+    sd = lo.synthetic_head_state_dict(d, nb, seed)
+    h = PHDFor3DJoints(d, 17, nb)
+    h.load_state_dict(sd)
+    return h.to(DEV).eval(), sd
+
+
+def _oracle_values(joints, gt, i0, ids, n_groups):
+    per_group, all_, clips = pr.values_from_sums(pr.protocol_sums(joints, gt, i0, ids, n_groups), n_groups, joints.shape[1])
+    return per_group, all_, clips
+
+
+def test_evaluate_protocols_against_oracle_and_reference_head(lib, trees):
+    from implementation_phd_lab_vision_amd import protocols
+    from implementation_phd_lab_vision_amd.feature_store import DeviceFeatureStore
+    from oracle import lifting_oracle as lo
+    store = DeviceFeatureStore(str(trees[0]), subjects=[9], test_set=True, device=DEV)
+    names, ids = protocols.action_groups(store.item_actions())
+    assert names == ["act0", "act1", "act2"]
+    head, sd = _head(1024, 2, 6)
+    i_len, p_len, g = 3, 5, len(names)
+    res = protocols.evaluate_protocols(head, store, ids, names, i_len, p_len)
+    assert res["group_names"] == names and res["clips"].tolist() == np.bincount(ids).tolist() and res["clips"].dtype == np.int64
+    assert res["recon"].shape == (g, 2) and res["recon_all"].shape == (2,) and res["future"].shape == (g, p_len, 2)
+    assert res["future_all"].shape == (p_len, 2) and np.allclose(res["recon_mean"], res["recon"].mean(axis=0), rtol=1e-15)
+
+    feats, gt = store.get_batch(list(range(len(store))))[:2]
+    for name, joints, i0 in (("recon", head.joints(feats), 0), ("future", head.rollout(feats, i_len, p_len)[1], i_len)):
+        per_group, all_, clips = _oracle_values(joints.cpu(), gt.cpu(), i0, ids, g)      # the device's own outputs: one batch of 11
+        if name == "recon":
+            per_group, all_ = per_group.mean(axis=1), all_.mean(axis=0)
+        np.testing.assert_allclose(res[name], per_group, rtol=1e-9, atol=0)
+        np.testing.assert_allclose(res[name + "_all"], all_, rtol=1e-9, atol=0)
+
+    ref_joints = lo.forward_reference(sd, feats.cpu())[2]                               # the fp64 reference head
+    ref_future = rollout_reference(sd, feats.cpu(), i_len, p_len)[1]
+    for name, joints, i0 in (("recon", ref_joints, 0), ("future", ref_future, i_len)):
+        per_group, all_, _ = _oracle_values(joints, gt.cpu(), i0, ids, g)
+        if name == "recon":
+            per_group, all_ = per_group.mean(axis=1), all_.mean(axis=0)
+        rel = np.abs(res[name] - per_group) / per_group
+        print(f"{name}: device vs fp64 reference head, largest relative difference {rel.max():.2e}")
+        assert rel.max() <= 5e-3, (name, rel.max())
+        assert (np.abs(res[name + "_all"] - all_) / all_).max() <= 5e-3
+
+    print("head.joints bit-equal across batchings:", torch.equal(head.joints(feats[:2]), head.joints(feats)[:2]),
+          "| rollout:", torch.equal(head.rollout(feats[:7], i_len, p_len)[1], head.rollout(feats, i_len, p_len)[1][:7]))
+    for bs in (2, 7, 256):
+        other = protocols.evaluate_protocols(head, store, ids, names, i_len, p_len, batch_size=bs)
+        assert np.array_equal(other["clips"], res["clips"])
+        for key in ("recon", "recon_all", "recon_mean", "future", "future_all", "future_mean"):
+            np.testing.assert_allclose(other[key], res[key], rtol=1e-12, atol=0, err_msg=f"{bs} {key}")
+
+    recon_only = protocols.evaluate_protocols(head, store, ids, names)                  # no rollout: the same reconstruction sums
+    assert "future" not in recon_only and np.array_equal(recon_only["recon"], res["recon"])
+    padded = protocols.evaluate_protocols(head, store, ids, names + ["zz_empty"])       # a group without clips: NaN, out of the mean
+    assert np.isnan(padded["recon"][-1]).all() and padded["clips"][-1] == 0
+    assert np.array_equal(padded["recon"][:-1], res["recon"]) and np.array_equal(padded["recon_mean"], res["recon_mean"])
+    with pytest.raises(ValueError):
+        protocols.evaluate_protocols(head, store, ids, names, 4, 5)                     # 9 > seq_len 8
+    with pytest.raises(ValueError):
+        protocols.evaluate_protocols(head, store, ids[:-1], names)
+    with pytest.raises(ValueError):
+        protocols.evaluate_protocols(head, store, [3] * len(store), names)
+
+
+# ------------------------------------------------------------------ CLI -------------------------------------------------------
+def _cli(argv):
+    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, "-m", "implementation_phd_lab_vision_amd.results", *argv],
+                       cwd=str(ROOT), env=env, capture_output=True, text=True)
+    assert r.returncode == 0, f"results exited {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    return r.stdout
+
+
+def _same_array(a, b) -> bool:
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    if a.dtype != object:
+        return np.array_equal(a, b)
+    return all(set(x) == set(y) and all(torch.equal(x[k], y[k]) if isinstance(x[k], torch.Tensor) else x[k] == y[k] for k in x)
+               for x, y in zip(a, b))
+
+
+def test_results_cli_protocols(lib, trees, tmp_path):
+    from implementation_phd_lab_vision_amd import protocols, results
+    from implementation_phd_lab_vision_amd.feature_store import DeviceFeatureStore
+    from oracle import lifting_oracle as lo
+    features, videos = trees
+    sd = lo.synthetic_head_state_dict(1024, 2, seed=2)
+    ckpt = tmp_path / "model.pt"
+    torch.save(sd, ckpt)
+    base = ["--features_root", str(features), "--preprocessed_root", str(videos), "--model_path", str(ckpt), "--seq-len", str(rd.SEQ_LEN),
+            "--batch-size", "4", "--save-n", "3", "--video-size", "32", "--video-reader", "tests.results_data:read_video"]
+    rollout = ["--input-len", "3", "--pred-len", "5"]
+    out_off, out_on, out_rec = tmp_path / "off.npz", tmp_path / "on.npz", tmp_path / "rec.npz"
+    so_off = _cli(base + rollout + ["--out", str(out_off)])
+    so_on = _cli(base + rollout + ["--out", str(out_on), "--protocols"])
+    so_rec = _cli(base + ["--out", str(out_rec), "--protocols"])
+
+    store = DeviceFeatureStore(str(features), subjects=[9], test_set=True, device=DEV)
+    head = results.build_head(sd, DEV)
+    names, ids = protocols.action_groups(store.item_actions())
+    res = protocols.evaluate_protocols(head, store, ids, names, 3, 5)
+    lines = results.protocol_lines(res, 3, 5)
+    assert lines[0].startswith("Protocol metrics | clips 11 | actions 3 | all: p1 (mm) ") and len(lines) == 5
+    assert lines[-1].startswith("Rollout protocol metrics | input 3 | pred 5 | clips 11 | p1 (mm) @1: ")
+    on_lines = so_on.replace(str(out_on), str(out_off)).splitlines()
+    for line in lines:
+        assert line in on_lines, line
+    assert not any(l.startswith(("Protocol metrics", "Rollout protocol metrics")) for l in so_off.splitlines())
+    timing = ("Results time",)
+    assert [l for l in on_lines if l not in lines and not l.startswith(timing)] == \
+           [l for l in so_off.splitlines() if not l.startswith(timing)]                  # the rest of stdout as without the flag
+
+    z_off, z_on = np.load(out_off, allow_pickle=True), np.load(out_on, allow_pickle=True)
+    new = {"protocol_actions", "protocol_clips", "protocol_recon", "protocol_recon_all", "protocol_future", "protocol_future_all"}
+    assert set(z_on.files) == set(z_off.files) | new and not new & set(z_off.files)
+    for key in z_off.files:
+        assert _same_array(z_off[key], z_on[key]), key
+    assert z_on["protocol_actions"].dtype.kind == "U" and z_on["protocol_actions"].tolist() == names
+    assert z_on["protocol_clips"].dtype == np.int64 and z_on["protocol_clips"].tolist() == res["clips"].tolist()
+    for key, want in (("protocol_recon", res["recon"]), ("protocol_recon_all", res["recon_all"]), ("protocol_future", res["future"]),
+                      ("protocol_future_all", res["future_all"])):
+        assert z_on[key].dtype == np.float32 and np.array_equal(z_on[key], want.astype(np.float32)), key
+
+    rec = protocols.evaluate_protocols(head, store, ids, names)
+    assert results.protocol_lines(rec, 15, 0) == [l for l in so_rec.splitlines() if l.startswith(("Protocol metrics", "  "))]
+    assert "Rollout" not in so_rec
+    z_rec = np.load(out_rec, allow_pickle=True)
+    assert set(z_rec.files) == {"video", "joints3d", "predicted3djoints", "joints2d", "K", "meta", "test_metrics", "protocol_actions",
+                                "protocol_clips", "protocol_recon", "protocol_recon_all"}
+    assert np.array_equal(z_rec["protocol_recon"], z_on["protocol_recon"]) and np.array_equal(z_rec["protocol_recon_all"], z_on["protocol_recon_all"])
