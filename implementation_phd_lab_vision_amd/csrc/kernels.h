@@ -3944,14 +3944,42 @@ __global__ __launch_bounds__(256) void add_rows_kernel(float* __restrict__ y, in
     }
 }
 
+// Statistics of one GroupNorm slab of n elements (element i read by ld(i)) for a workgroup of 256 threads: the mean, then the biased
+// variance from the centred values (x - mean)^2 in a second pass over the slab -- E[x^2] - mean^2 cancels catastrophically when the
+// slab's mean is large against its spread.  Each pass sums the strided slice i = tid, tid + 256, ... per thread in order, then a fixed
+// tree in red; eps inside the square root (torch.nn.functional.group_norm).  Every GroupNorm kernel of the head (forward and
+// backward, batch- and time-major) calls this one helper with the same element order, so the backward recomputes the forward's
+// exact mean / rstd.  Ends on a barrier: red is free again on return.
+template <typename LD>
+__device__ __forceinline__ void gn_slab_stats(LD ld, int n, float eps, float* red, float& mean, float& rstd) {
+    auto block_sum = [&](float v) -> float {
+        red[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+            __syncthreads();
+        }
+        const float r = red[0];
+        __syncthreads();
+        return r;
+    };
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) s += ld(i);
+    mean = block_sum(s) / (float)n;
+    float ss = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) { const float d = ld(i) - mean; ss += d * d; }
+    const float var = block_sum(ss) / (float)n;
+    rstd = 1.0f / sqrtf(var + eps);
+}
+
 // GroupNorm(groups) + ReLU over x (B, T, C) [channels contiguous], fp32 statistics over the (C/groups x T) slab of one sample
-// and group (biased variance, eps inside the square root: torch.nn.functional.group_norm), then the causal-conv input
-// rows out (B*T, 3C): out[(b,t)][k*C + c] = y[b][max(t-2+k, 0)][c].  One workgroup per (sample, group).
+// and group (gn_slab_stats), then the causal-conv input rows out (B*T, 3C): out[(b,t)][k*C + c] = y[b][max(t-2+k, 0)][c].
+// One workgroup per (sample, group).
 template <int ET>
 __global__ __launch_bounds__(256) void gn_relu_causal3_kernel(const unsigned short* __restrict__ x, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, unsigned short* __restrict__ out,
                                                               int T, int C, int groups, float eps) {
-    __shared__ float red[2][256];
+    __shared__ float red[256];
     const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
     const int cg = C / groups, n = cg * T;
     const unsigned short* xb = x + (size_t)b * T * C + g * cg;
@@ -3960,17 +3988,8 @@ __global__ __launch_bounds__(256) void gn_relu_causal3_kernel(const unsigned sho
         const unsigned u = xb[(size_t)t * C + c];
         return ET == 0 ? bf16_bits_to_f32(u) : (float)__builtin_bit_cast(_Float16, (unsigned short)u);
     };
-    float s = 0.f, ss = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) { const float v = ld(i); s += v; ss += v * v; }
-    red[0][threadIdx.x] = s; red[1][threadIdx.x] = ss;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    const float mean = red[0][0] / (float)n;
-    const float var = fmaxf(red[1][0] / (float)n - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + eps);
+    float mean, rstd;
+    gn_slab_stats(ld, n, eps, red, mean, rstd);
     for (int i = threadIdx.x; i < n; i += 256) {
         const int t = i / cg, c = i - t * cg, ch = g * cg + c;
         float v = (ld(i) - mean) * rstd * gamma[ch] + beta[ch];
@@ -3999,7 +4018,7 @@ template <int ET>
 __global__ __launch_bounds__(256) void gn_relu_causal3_tm_kernel(const unsigned short* __restrict__ x, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, unsigned short* __restrict__ out,
                                                                  int B, int T, int t0, int C, int groups, float eps) {
-    __shared__ float red[2][256];
+    __shared__ float red[256];
     const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
     const int cg = C / groups, n = cg * T;
     const unsigned short* xb = x + (size_t)b * C + g * cg;
@@ -4008,17 +4027,8 @@ __global__ __launch_bounds__(256) void gn_relu_causal3_tm_kernel(const unsigned 
         const unsigned u = xb[(size_t)t * B * C + c];
         return ET == 0 ? bf16_bits_to_f32(u) : (float)__builtin_bit_cast(_Float16, (unsigned short)u);
     };
-    float s = 0.f, ss = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) { const float v = ld(i); s += v; ss += v * v; }
-    red[0][threadIdx.x] = s; red[1][threadIdx.x] = ss;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    const float mean = red[0][0] / (float)n;
-    const float var = fmaxf(red[1][0] / (float)n - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + eps);
+    float mean, rstd;
+    gn_slab_stats(ld, n, eps, red, mean, rstd);
     const size_t ld_out = (size_t)3 * C;
     auto row = [&](int r) -> unsigned short* { return out + ((size_t)(r - t0) * B + b) * ld_out; };
     const int first = t0 >= 2 ? (t0 - 2) * cg : 0;         // frames before t0 - 2 feed no emitted row
@@ -4593,13 +4603,8 @@ __global__ __launch_bounds__(256) void gn_relu_causal3_bwd_kernel(const unsigned
         oa = red[0][0]; oc = red[1][0];
         __syncthreads();
     };
-    float s = 0.f, ss = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) { const int t = i / cg, c = i - t * cg; const float v = ld_e<ET>(xb + (size_t)t * C + c); s += v; ss += v * v; }
-    float S, SS;
-    block_sum2(s, ss, S, SS);
-    const float mean = S / (float)n;
-    const float var = fmaxf(SS / (float)n - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + eps);
+    float mean, rstd;                          // the forward's statistics, recomputed by the same helper in the same order
+    gn_slab_stats([&](int i) { const int t = i / cg, c = i - t * cg; return ld_e<ET>(xb + (size_t)t * C + c); }, n, eps, red[0], mean, rstd);
     auto dy_of = [&](int t, int c, float& xh) -> float {       // dy and xh of slab element (t, c)
         const int ch = g * cg + c;
         xh = (ld_e<ET>(xb + (size_t)t * C + c) - mean) * rstd;
@@ -4676,13 +4681,8 @@ __global__ __launch_bounds__(256) void gn_relu_causal3_tm_bwd_kernel(const unsig
         oa = red[0][0]; oc = red[1][0];
         __syncthreads();
     };
-    float s = 0.f, ss = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) { const int t = i / cg, c = i - t * cg; const float v = ld_e<ET>(xb + (size_t)t * ldx + c); s += v; ss += v * v; }
-    float S, SS;
-    block_sum2(s, ss, S, SS);
-    const float mean = S / (float)n;
-    const float var = fmaxf(SS / (float)n - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + eps);
+    float mean, rstd;                          // the forward's statistics, recomputed by the same helper in the same order
+    gn_slab_stats([&](int i) { const int t = i / cg, c = i - t * cg; return ld_e<ET>(xb + (size_t)t * ldx + c); }, n, eps, red[0], mean, rstd);
     auto row = [&](int r) -> const unsigned short* { return dr + ((size_t)(r - t0) * B + b) * ldr; };
     auto dy_of = [&](int t, int c, float& xh) -> float {       // dy and xh of slab element (t, c)
         const int ch = g * cg + c;
