@@ -4207,6 +4207,39 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const unsigned short* __re
         out[c] = (accumulate ? out[c] : 0.f) + t * scale;
     }
 }
+// colsum_kernel's sums bit for bit, spread over 16x the workgroups (the joint step's bias gradients).
+// colsum_kernel gives one column 16 row chains in ONE workgroup (cols / 64 workgroups: 16 CUs for 1024 columns, 1 for 64) and
+// waits on every load.  Pass 1 gives each (chain g, column c) a lane of its own and keeps 16 loads in flight: part[g][c] = the sum
+// over rows r = g, g + 16, ... ascending, from 0.f, in fp32 -- colsum_kernel's chain.  Pass 2 adds part[0..15][c] in order from 0.f
+// and applies colsum_kernel's epilogue.  Same association, same roundings: the same bits.
+template <int ET>
+__global__ __launch_bounds__(64) void colsum_chain_kernel(const unsigned short* __restrict__ x, long long rows, int cols, int ld,
+                                                          float* __restrict__ part) {
+    constexpr int U = 16;
+    const int c = blockIdx.x * 64 + threadIdx.x, g = blockIdx.y;
+    if (c >= cols) return;
+    const unsigned short* p = x + c;
+    float s = 0.f;
+    long long r = g;
+    for (; r + 16ll * (U - 1) < rows; r += 16ll * U) {
+        float v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) v[k] = ld_e<ET>(p + (r + 16ll * k) * ld);
+#pragma unroll
+        for (int k = 0; k < U; ++k) s += v[k];
+    }
+    for (; r < rows; r += 16) s += ld_e<ET>(p + r * ld);
+    part[(long long)g * cols + c] = s;
+}
+__global__ __launch_bounds__(256) void colsum_chain_sum_kernel(const float* __restrict__ part, int cols, float scale,
+                                                               float* __restrict__ out, int accumulate) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    float t = 0.f;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) t += part[(long long)g * cols + c];
+    out[c] = (accumulate ? out[c] : 0.f) + t * scale;
+}
 __global__ __launch_bounds__(64) void colsum_f32_kernel(const float* __restrict__ x, long long rows, int cols, float scale,
                                                         float* __restrict__ out, int accumulate) {
     const int c = blockIdx.x * 64 + threadIdx.x;
@@ -4512,6 +4545,65 @@ __global__ __launch_bounds__(1024) void future_pose_loss_grad_kernel(const float
     if (threadIdx.x == 0) {
         loss[0] = (float)(red[0][0] / (3.0 * (double)npred));
         loss[1] = (float)(red[1][0] / (double)npred);
+    }
+}
+
+// ---- Joint training: input_proj, f_movie, f_AR and f_3D under one loss --------------------------------
+// Both pose terms of the joint step in one launch.  y, dy: (2*rows, joints, 3) fp32, rows = b*t; rows [0, rows) are the regressor on
+// phi, rows [rows, 2 rows) the regressor on phi_hat; gt: (rows, joints, 3) fp32, shared by both halves.
+//   first half:  dy = 2 (y - gt) / n1 * loss_scale,            n1 = rows*joints*3      (mse_loss_grad_kernel's arithmetic)
+//   second half: dy = 2 (y - gt) / n2 * scale_hat, 0 on frame 0, n2 = b*(t-1)*joints*3  (future_pose_loss_grad_kernel's arithmetic),
+//                scale_hat = loss_scale * lambda_future (rounded once to fp32 on the host, so lambda_future = 1 gives loss_scale's bits)
+// loss = [l3d, mpjpe, l3d_hat, mpjpe_hat].  Each half is its own loop over the joints with pose_metrics_kernel's stride (first half)
+// and future_pose_loss_grad_kernel's (second half): per joint fp32, per-thread fp64 partials over a fixed strided slice, then one
+// fixed fp64 tree for the four sums -- the same bits on every run, no atomics, and the sums of the kernels it stands for.
+__global__ __launch_bounds__(1024) void joint_pose_loss_grad_kernel(const float* __restrict__ y, const float* __restrict__ gt,
+                                                                    long long rows, int t, int joints, float loss_scale, float scale_hat,
+                                                                    float* __restrict__ dy, float* __restrict__ loss) {
+    __shared__ double red[4][1024];
+    const long long nj = rows * joints;
+    const long long npred = (rows / t) * (t - 1) * joints;
+    const float n1 = (float)(3 * nj), n2 = (float)(3 * npred);
+    double s1 = 0.0, e1 = 0.0, s2 = 0.0, e2 = 0.0;
+    for (long long j = threadIdx.x; j < nj; j += 1024) {
+        float d2 = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const float d = y[3 * j + k] - gt[3 * j + k];
+            dy[3 * j + k] = 2.f * d / n1 * loss_scale;
+            d2 += d * d;
+        }
+        s1 += (double)d2;
+        e1 += (double)sqrtf(d2);
+    }
+    const float* yh = y + 3 * nj;
+    float* dyh = dy + 3 * nj;
+    for (long long j = threadIdx.x; j < nj; j += 1024) {
+        const long long r = j / joints;
+        if (r % t == 0) {
+            dyh[3 * j] = 0.f; dyh[3 * j + 1] = 0.f; dyh[3 * j + 2] = 0.f;
+            continue;
+        }
+        float d2 = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const float d = yh[3 * j + k] - gt[3 * j + k];
+            dyh[3 * j + k] = 2.f * d / n2 * scale_hat;
+            d2 += d * d;
+        }
+        s2 += (double)d2;
+        e2 += (double)sqrtf(d2);
+    }
+    red[0][threadIdx.x] = s1; red[1][threadIdx.x] = e1; red[2][threadIdx.x] = s2; red[3][threadIdx.x] = e2;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = (float)(red[0][0] / (3.0 * (double)nj));
+        loss[1] = (float)(red[1][0] / (double)nj);
+        loss[2] = (float)(red[2][0] / (3.0 * (double)npred));
+        loss[3] = (float)(red[3][0] / (double)npred);
     }
 }
 

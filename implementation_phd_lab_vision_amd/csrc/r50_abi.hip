@@ -2378,6 +2378,15 @@ int r50_op_colsum(const void* x, int64_t rows, int cols, int ld, float scale, fl
     return ew_done("r50_op_colsum");
 }
 
+int r50_op_colsum_split(const void* x, int64_t rows, int cols, int ld, float scale, float* part, float* out, int accumulate, int et,
+                        void* stream) {
+    if (!x || !part || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum_split: invalid arguments");
+    R50_ET_LAUNCH(colsum_chain_kernel, dim3((cols + 63) / 64, 16), dim3(64), stream, (const unsigned short*)x, (long long)rows, cols, ld, part);
+    hipLaunchKernelGGL(colsum_chain_sum_kernel, dim3((cols + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, cols, scale, out, accumulate);
+    return ew_done("r50_op_colsum_split");
+}
+
 int r50_op_colsum_f32(const float* x, int64_t rows, int cols, float scale, float* out, int accumulate, void* stream) {
     if (!x || !out || rows < 1 || cols < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum_f32: invalid arguments");
     hipLaunchKernelGGL(colsum_f32_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, (long long)rows, cols, scale, out, accumulate);
@@ -2430,6 +2439,16 @@ int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int
     hipLaunchKernelGGL(future_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, y_hat, gt, (long long)b * t, t, joints,
                        loss_scale, dy, loss2);
     return ew_done("r50_op_future_pose_loss_grad");
+}
+
+int r50_op_joint_pose_loss_grad(const float* y, const float* gt, int b, int t, int joints, float lambda_future, float loss_scale, float* dy,
+                                float* out4, void* stream) {
+    if (!y || !gt || !dy || !out4) return fail(nullptr, R50_ERR_INVALID, "r50_op_joint_pose_loss_grad: null pointer");
+    if (b < 1 || t < 2 || joints < 1 || joints > 64 || (int64_t)b * t > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_joint_pose_loss_grad: invalid arguments (need b >= 1, t >= 2 and 1 <= joints <= 64)");
+    hipLaunchKernelGGL(joint_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, y, gt, (long long)b * t, t, joints,
+                       loss_scale, loss_scale * lambda_future, dy, out4);
+    return ew_done("r50_op_joint_pose_loss_grad");
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }

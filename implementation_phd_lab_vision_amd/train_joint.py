@@ -1,0 +1,600 @@
+"""Joint training of the lifting head on one MI355X: input_proj, f_movie, f_AR and f_3D under one loss (DESIGN.md "f joint",
+INTEGRATION.md section M).  ``python -m implementation_phd_lab_vision_amd.train_joint``.
+
+Phase 1 (train.py) freezes f_AR, as the reference does (src/train.py:375-376); phase 2 and the rollout objective (train_ar.py) train
+f_AR alone on a frozen f_movie.  The paper the reference implements trains the strip encoder and the predictor together, and the
+reference's ``PHDFor3DJoints.forward(feats, predict_future=True)`` returns every output such a loss needs (src/model.py:158-178).
+This project's definition of the joint program, in the reference's idiom (tests/golden/make_golden_train_joint.py runs it on the
+reference module itself)::
+
+    model = PHD(latent_dim, 17, number_blocks)          # weights: a phase-1 / phase-2 / rollout checkpoint's "model", or a state dict
+    for p in model.parameters(): p.requires_grad = True
+    optim = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-2)   # named_parameters() order
+    scaler = torch.amp.GradScaler("cuda")
+    model.train()                                        # every dropout site active: f_movie, f_AR, both f_3D calls
+    with torch.autocast("cuda", dtype=torch.float16):
+        phi, phi_hat, joints_phi, joints_hat = model(feats, predict_future=True)
+        l3d     = (joints_phi - joints3d).pow(2).mean()                       # phase 1's term, all frames
+        l3d_hat = (joints_hat[:, 1:] - joints3d[:, 1:]).pow(2).mean()         # phase 2's terms, frames s >= 1
+        l_lat   = (phi_hat[:, 1:] - phi[:, 1:].detach()).pow(2).mean()
+        loss    = l3d + args.lambda_future * l3d_hat + args.lambda_latent * l_lat
+    scaler.scale(loss).backward(); scaler.step(optim); scaler.update()
+
+The choices that are this project's, not the paper's:
+
+* The latent target is detached, as in phase 2.  f_movie is trained by l3d (through f_3D(phi)) and by l3d_hat and l_lat through
+  f_AR's INPUT; it is never pulled toward f_AR's prediction through the target.  Without the detach, l_lat could shrink by making
+  the strips constant.
+* Everything runs in train mode.  The two calls of f_3D draw independent dropout masks, and the detached target phi carries
+  f_movie's dropout: what ``model.train()`` gives on the reference module.
+* ``--lambda-future`` and ``--lambda-latent`` default to 1.0; no run has measured good values.
+* lambda = 0 still applies AdamW's weight decay to f_AR: f_AR stays in the graph and its gradients are zeros, not None (on the
+  reference module at number_blocks = 2: 48 parameters, f_AR's 24 with all-zero gradients).  The device does the same.
+* The optimizer starts fresh from ``--init``: no checkpoint of another phase holds state for every parameter.
+* ``best.pt`` and early stopping follow val ``mpjpe + mpjpe_hat``, which does not depend on the lambdas, so runs with different
+  weights compare.
+
+``JointTrainableHead`` keeps every parameter in flat fp32 master / 16-bit / gradient buffers in the GEMM layouts of
+``train.TrainableHead`` and ``train_ar.ARTrainableHead``.  One step, eager launches through the C ABI: input_proj and f_movie forward
+(saved; f_movie's last conv2 stores straight into the first half of a stacked (2*B*T, D) strip buffer), f_AR forward (saved), the
+phi_hat shift into the second half, the regressor ONCE over the 2*B*T stacked rows (each half its own dropout masks),
+``r50_op_joint_pose_loss_grad``, the regressor's backward over the stacked rows with weight gradients (bias gradients by
+``r50_op_colsum_split``: ``r50_op_colsum``'s bits, spread over the chip), ``r50_op_ar_latent_grad`` on
+the second half of the strip gradient, f_AR's backward with weight gradients (block 0's gn1 backward plus the skip connection
+gives f_AR's gradient with respect to phi), the gradient of phi = the regressor's first half + f_AR's input gradient, f_movie's
+backward and input_proj's dW, one overflow check over the 16-bit arena; then ``all_reduce_gradients``, ``check_finite``, AdamW,
+the scaler.  No torch autograd, no CPU fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from . import _lib
+from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
+from .train import (DROPOUT_P, AdamW, CosineLR, GradScaler, TrainableHead, _Arena, _BackwardLaunches, all_reduce_gradients,
+                    build_parser as _phase1_parser, dropout_generator, load_checkpoint, save_checkpoint, sync_overflow_flag)
+from .train_ar import ARTrainableHead
+
+LAMBDA_FUTURE = 1.0
+LAMBDA_LATENT = 1.0
+_BLOCK_PARAMS = ("gn1", "conv1.conv", "gn2", "conv2.conv")      # a ResidualBlock registers gn1, conv1, gn2, conv2 (src/model.py:39-44)
+
+
+def joint_trainable_names(number_blocks: int) -> List[str]:
+    """``[n for n, _ in model.named_parameters()]`` of the reference module with every parameter trainable: f_movie's blocks, f_AR's
+    blocks, f_3D's three Linears, input_proj (src/model.py:142-146); ``f_3D.y0`` is a buffer.  The numbering of the optimizer state."""
+    names: List[str] = []
+    for net, nb in (("f_movie", number_blocks), ("f_AR", _AR_BLOCKS)):
+        for i in range(nb):
+            for m in _BLOCK_PARAMS:
+                names += [f"{net}.blocks.{i}.{m}.weight", f"{net}.blocks.{i}.{m}.bias"]
+    for j in (0, 3, 5):
+        names += [f"f_3D.mlp.{j}.weight", f"f_3D.mlp.{j}.bias"]
+    return names + ["input_proj.weight", "input_proj.bias"]
+
+
+class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
+    """``PHDFor3DJoints`` with every parameter trainable in flat fp32 / 16-bit buffers."""
+
+    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
+                 lambda_future: float = LAMBDA_FUTURE, lambda_latent: float = LAMBDA_LATENT):
+        super().__init__(latent_dim, joints_num, number_blocks, precision)
+        if self.number_blocks < 1:
+            raise ValueError("joint training needs at least one f_movie block (its last conv2 stores phi)")
+        self.lambda_future = float(lambda_future)
+        self.lambda_latent = float(lambda_latent)
+        self.flat_master: Optional[torch.Tensor] = None
+        self._layout: List[Tuple[str, int, Tuple[int, ...]]] = []
+        self.last_losses: Dict[str, float] = {}
+
+    def train(self, mode: bool = True):
+        self.training = bool(mode)
+        return self
+
+    # ---- flat parameter buffers (GEMM layout: train.TrainableHead's and train_ar.ARTrainableHead's) ----------------------------
+    def _upload(self) -> None:
+        super()._upload()                      # y0 and every weight eval() needs; the trainable entries are re-pointed below
+        sd, dev = self._sd, self._device
+        d, o = self.latent_dim, self.out_dim
+        items: List[Tuple[str, torch.Tensor]] = []
+        for net, nb in (("f_movie", self.number_blocks), ("f_AR", _AR_BLOCKS)):
+            for i in range(nb):
+                p = f"{net}.blocks.{i}"
+                for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
+                    items += [(f"{p}.{gn}.g", sd[f"{p}.{gn}.weight"]), (f"{p}.{gn}.b", sd[f"{p}.{gn}.bias"]),
+                              (f"{p}.{cv}.w", sd[f"{p}.{cv}.conv.weight"].permute(0, 2, 1).reshape(d, 3 * d)),
+                              (f"{p}.{cv}.b", sd[f"{p}.{cv}.conv.bias"])]
+        w0 = torch.zeros(_REG_HIDDEN, self._dp); w0[:, : d + o] = sd["f_3D.mlp.0.weight"]
+        w5 = torch.zeros(self._op, _REG_HIDDEN); w5[:o] = sd["f_3D.mlp.5.weight"]
+        b5 = torch.zeros(self._op); b5[:o] = sd["f_3D.mlp.5.bias"]
+        items += [("mlp0.w", w0), ("mlp0.b", sd["f_3D.mlp.0.bias"]), ("mlp3.w", sd["f_3D.mlp.3.weight"]),
+                  ("mlp3.b", sd["f_3D.mlp.3.bias"]), ("mlp5.w", w5), ("mlp5.b", b5),
+                  ("input_proj.w", sd["input_proj.weight"]), ("input_proj.b", sd["input_proj.bias"])]
+        self._layout, off = [], 0
+        for name, t in items:
+            assert t.numel() % 64 == 0
+            self._layout.append((name, off, tuple(t.shape)))
+            off += t.numel()
+        self.flat_master = torch.cat([t.reshape(-1).to(torch.float32) for _, t in items]).to(dev)
+        self.flat_w16 = self.flat_master.to(self._dtype)
+        self.flat_grad = torch.zeros_like(self.flat_master)
+        self._off = {name: (o_, shape) for name, o_, shape in self._layout}
+        for name, o_, shape in self._layout:       # weights: the 16-bit copy; biases and GroupNorm parameters: the fp32 master itself
+            n = int(torch.Size(shape).numel())
+            src = self.flat_w16 if name.endswith(".w") else self.flat_master
+            self._dev[name] = src[o_: o_ + n].view(shape)
+        self._wt: Dict[str, torch.Tensor] = {}     # transposed 16-bit weights for the dX products
+        self._refresh_transposes()
+        self._zero_bias = torch.zeros(max(3 * d, 2048, self._dp, _REG_HIDDEN), dtype=torch.float32, device=dev)
+        self._colsum_part = torch.empty(16 * max(d, _REG_HIDDEN, self._op), dtype=torch.float32, device=dev)
+        self._found = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._arena = _Arena(dev, self._dtype)
+
+    def _wgrad(self, name: str, dy: torch.Tensor, x: torch.Tensor, inv_scale: float, accumulate: bool, bias: Optional[str] = None) -> None:
+        """``_BackwardLaunches._wgrad`` with the bias gradient by ``r50_op_colsum_split``: ``r50_op_colsum``'s bits, spread over the
+        chip (one-workgroup-per-64-columns column sums over the stacked 2*B*T rows were the step's largest cost)."""
+        lib = _lib.load_library()
+        dw = self._mm(self._t(dy), self._t(x))                    # (N, Rp) @ (K, Rp)^T -> (N, K)
+        gv = self.grad_view(name)
+        assert tuple(dw.shape) == tuple(gv.shape)
+        _lib.check(lib.r50_op_grad_accum(dw.data_ptr(), inv_scale, gv.data_ptr(), dw.numel(), int(accumulate), self._et, self._stream()),
+                   None, "r50_op_grad_accum")
+        if bias is not None:
+            gb = self.grad_view(bias)
+            assert 16 * dy.shape[1] <= self._colsum_part.numel()
+            _lib.check(lib.r50_op_colsum_split(dy.data_ptr(), dy.shape[0], dy.shape[1], dy.shape[1], inv_scale, self._colsum_part.data_ptr(),
+                                               gb.data_ptr(), int(accumulate), self._et, self._stream()), None, "r50_op_colsum_split")
+
+    def _refresh_transposes(self) -> None:
+        lib = _lib.load_library()
+        for name, _, shape in self._layout:
+            if not name.endswith(".w") or name == "input_proj.w":
+                continue
+            n, k = shape
+            if name not in self._wt:
+                self._wt[name] = torch.zeros((k, n), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
+                       "r50_op_transpose16")
+
+    def trainable_parameter_names(self) -> List[str]:
+        """The names of the optimizer's parameters, in its numbering: ``joint_trainable_names(number_blocks)``."""
+        return joint_trainable_names(self.number_blocks)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The reference's keys and layouts (fp32, CPU): every parameter from the flat master buffer, ``f_3D.y0`` as loaded."""
+        out = {k: v.clone() for k, v in self._sd.items()}
+        out.update(self.flat_to_reference(self.flat_master))
+        return out
+
+    def named_gradients(self) -> Dict[str, torch.Tensor]:
+        """flat_grad under the reference's names and layouts (fp32, CPU), in ``named_parameters()`` order: what ``p.grad`` holds."""
+        return self.flat_to_reference(self.flat_grad)
+
+    def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """A buffer in the flat layout (master, gradient, AdamW moments) under the reference's names and layouts (fp32, CPU), in
+        ``joint_trainable_names`` order.  The phase-1 entries are read as ``TrainableHead`` reads them, f_AR's as
+        ``ARTrainableHead`` does: the layouts are theirs."""
+        out = TrainableHead.flat_to_reference(self, flat)
+        out.update(ARTrainableHead.flat_to_reference(self, flat))
+        return {n: out[n] for n in self.trainable_parameter_names()}
+
+    def flat_from_reference(self, named: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """Inverse of ``flat_to_reference``: a new device buffer in the flat layout, zero in the GEMM padding."""
+        flat = TrainableHead.flat_from_reference(self, named)
+        ar = ARTrainableHead.flat_from_reference(self, named)
+        for name, o_, shape in self._layout:
+            if name.startswith("f_AR."):
+                n = int(torch.Size(shape).numel())
+                flat[o_: o_ + n].copy_(ar[o_: o_ + n])
+        return flat
+
+    def refresh_weights16(self) -> None:
+        """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
+        self.flat_w16.copy_(self.flat_master.to(self._dtype))
+        self._refresh_transposes()
+
+    def make_dropout_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """Byte keep-masks (1 = keep, probability 1 - p) for every dropout site of one joint step, drawn in this order: one per f_movie
+        block and one per f_AR block after its conv1 (src/model.py:52), (B*T, D); one per iteration of f_3D(phi) ("f_3D.i") and then
+        of f_3D(phi_hat) ("f_3D_hat.i") after the regressor's first ReLU (:98), (B*T, 1024).  The f_movie and f_3D(phi) entries are
+        phase 1's sites under phase 1's names."""
+        def bern(*shape):
+            return (torch.rand(*shape, device=self._device, generator=generator) >= DROPOUT_P).to(torch.uint8)
+        masks = {f"f_movie.blocks.{i}": bern(b * t, self.latent_dim) for i in range(self.number_blocks)}
+        masks.update({f"f_AR.blocks.{i}": bern(b * t, self.latent_dim) for i in range(_AR_BLOCKS)})
+        masks.update({f"f_3D.{i}": bern(b * t, _REG_HIDDEN) for i in range(_REG_ITERS)})
+        masks.update({f"f_3D_hat.{i}": bern(b * t, _REG_HIDDEN) for i in range(_REG_ITERS)})
+        return masks
+
+    # ---- launches -------------------------------------------------------------------------------
+    def _check_batch(self, feats: torch.Tensor, joints3d: torch.Tensor) -> Tuple[int, int]:
+        if self.flat_master is None:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') first")
+        if feats.dim() != 3 or feats.shape[-1] != 2048 or feats.device != self._device:
+            raise ValueError("feats: expected (B,T,2048) on the head's device")
+        b, t, _ = feats.shape
+        if tuple(joints3d.shape) != (b, t, self.joints_num, 3) or joints3d.device != self._device:
+            raise ValueError("joints3d: expected (B,T,J,3) on the head's device")
+        if b < 1 or t < 2:
+            raise ValueError("joint training needs clips of at least 2 frames (frame 0 has no prediction)")
+        return b, t
+
+    def _joint_pose_loss(self, y: torch.Tensor, gt: torch.Tensor, b: int, t: int, lambda_future: float, loss_scale: float,
+                         dy: torch.Tensor, out: torch.Tensor) -> None:
+        """out[0:4] = [l3d, mpjpe, l3d_hat, mpjpe_hat]; dy (2*B*T, J*3) fp32 = the gradients of l3d and lambda_future * l3d_hat,
+        * loss_scale (0 on the frame-0 rows of the second half)."""
+        _lib.check(_lib.load_library().r50_op_joint_pose_loss_grad(y.data_ptr(), gt.data_ptr(), b, t, self.joints_num, lambda_future,
+                                                                    loss_scale, dy.data_ptr(), out.data_ptr(), self._stream()), None,
+                   "r50_op_joint_pose_loss_grad")
+
+    def _latent_loss(self, ar: torch.Tensor, phi: torch.Tensor, dphi_hat: torch.Tensor, b: int, t: int, lambda_latent: float,
+                     loss_scale: float, dar: torch.Tensor, out: torch.Tensor) -> None:
+        """out[0] = l_lat; dar (B*T, D) 16-bit = f_AR's output gradient: dphi_hat shifted back + lambda_latent * dl_lat, * loss_scale."""
+        part = torch.empty(b * t, dtype=torch.float32, device=self._device)
+        _lib.check(_lib.load_library().r50_op_ar_latent_grad(ar.data_ptr(), phi.data_ptr(), dphi_hat.data_ptr(), b, t, self.latent_dim,
+                                                              lambda_latent, loss_scale, dar.data_ptr(), out.data_ptr(), part.data_ptr(),
+                                                              self._et, self._stream()), None, "r50_op_ar_latent_grad")
+
+    def _shift_into(self, ar: torch.Tensor, dst: torch.Tensor, b: int, t: int) -> None:
+        """dst = phi_hat: dst[:, 1:] = ar[:, :-1], dst[:, 0] = 0 (src/model.py:165-166)."""
+        d = self.latent_dim
+        v = dst.view(b, t, d)
+        v[:, 0, :].zero_()
+        v[:, 1:, :] = ar.view(b, t, d)[:, :-1, :]
+
+    def forward_backward(self, feats: torch.Tensor, joints3d: torch.Tensor, loss_scale: float = 1.0,
+                         masks: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The joint forward (train mode when ``masks`` is given or ``self.training``; else dropout is identity), the loss
+        l3d + lambda_future * l3d_hat + lambda_latent * l_lat, backward into ``flat_grad`` (UNSCALED: the 16-bit backward runs on
+        loss_scale * loss, the fp32 buffer receives grad / loss_scale).  ``self._found`` is raised when a 16-bit gradient overflowed.
+        Returns (joints_phi (B,T,J,3) fp32, joints_hat (B,T,J,3) fp32, losses = [l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat] fp32 device
+        tensor)."""
+        b, t = self._check_batch(feats, joints3d)
+        if masks is None and self.training:
+            masks = self.make_dropout_masks(b, t)
+        keep_scale = 1.0 / (1.0 - DROPOUT_P)
+        lib = _lib.load_library()
+        rows, d, o = b * t, self.latent_dim, self.out_dim
+        rows2 = 2 * rows
+        inv = 1.0 / loss_scale
+        self._arena.reset()
+        self._found.zero_()
+        with torch.cuda.device(self._device):
+            # ---------------- forward: input_proj and f_movie (phase 1's), saved; phi lands in the strip buffer's first half ----------------
+            f = feats.to(torch.float32).contiguous()
+            x0 = torch.empty((rows, 2048), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(f.data_ptr(), rows, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None, "r50_op_cast_rows")
+            strips = torch.empty((rows2, d), dtype=self._dtype, device=self._device)       # [phi ; phi_hat]
+            phi, phi_hat = strips[:rows], strips[rows:]
+            x = self._gemm(x0, "input_proj", relu=False)
+            saved_movie = []
+            for i in range(self.number_blocks):
+                p = f"f_movie.blocks.{i}"
+                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
+                h = self._gemm(r1, p + ".conv1", relu=False)
+                m = masks[p] if masks is not None else None
+                if m is not None:
+                    self._mask_scale(h, m, keep_scale)
+                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
+                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x, out=phi if i == self.number_blocks - 1 else None)
+                saved_movie.append((x, r1, h, r2, m))
+                x = xo
+            # ---------------- f_AR over phi (phase 2's), saved; the shift into the second half ----------------
+            x, saved_ar = phi, []
+            for i in range(_AR_BLOCKS):
+                p = f"f_AR.blocks.{i}"
+                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
+                h = self._gemm(r1, p + ".conv1", relu=False)
+                m = masks[p] if masks is not None else None
+                if m is not None:
+                    self._mask_scale(h, m, keep_scale)
+                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
+                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x)
+                saved_ar.append((x, r1, h, r2, m))
+                x = xo
+            ar = x
+            self._shift_into(ar, phi_hat, b, t)
+            # ---------------- the regressor once over the 2*B*T stacked rows, each half its own masks ----------------
+            y = self._dev["y0"].view(1, o).expand(rows2, o).contiguous()
+            reg = []
+            for i in range(_REG_ITERS):
+                inp = torch.empty((rows2, self._dp), dtype=self._dtype, device=self._device)
+                _lib.check(lib.r50_op_concat_pad(strips.data_ptr(), d, y.data_ptr(), o, rows2, inp.data_ptr(), self._dp, self._et,
+                                                 self._stream()), None, "r50_op_concat_pad")
+                h1 = self._gemm(inp, "mlp0", relu=True)
+                if masks is not None:
+                    self._mask_scale(h1[:rows], masks[f"f_3D.{i}"], keep_scale)
+                    self._mask_scale(h1[rows:], masks[f"f_3D_hat.{i}"], keep_scale)
+                h2 = self._gemm(h1, "mlp3", relu=True)
+                dy = self._gemm(h2, "mlp5", relu=False)
+                _lib.check(lib.r50_op_add_rows(y.data_ptr(), o, dy.data_ptr(), self._op, rows2, self._et, self._stream()), None, "r50_op_add_rows")
+                reg.append((inp, h1, h2))
+            # ---------------- both pose terms and their gradients ----------------
+            gt = joints3d.to(torch.float32).contiguous()
+            dyacc = torch.empty((rows2, o), dtype=torch.float32, device=self._device)
+            losses = torch.empty(5, dtype=torch.float32, device=self._device)
+            self._joint_pose_loss(y, gt, b, t, self.lambda_future, loss_scale, dyacc, losses)
+            # ---------------- backward: the regressor over the stacked rows, with weight gradients (phase 1's launches) ----------------
+            dstrips = torch.zeros((rows2, d), dtype=torch.float32, device=self._device)   # [dphi from f_3D(phi) ; dphi_hat]
+            g5 = torch.empty((rows2, self._op), dtype=self._dtype, device=self._device)
+            for i in reversed(range(_REG_ITERS)):
+                inp, h1, h2 = reg[i]
+                first = i == _REG_ITERS - 1
+                _lib.check(lib.r50_op_cast_rows(dyacc.data_ptr(), rows2, o, g5.data_ptr(), self._op, self._et, self._stream()), None,
+                           "r50_op_cast_rows")
+                self._wgrad("mlp5.w", g5, h2, inv, not first, bias="mlp5.b")
+                dh2 = self._mm(g5, self._wt["mlp5.w"])                         # (2 rows, H)
+                self._relu_bwd(dh2, h2, 1.0)
+                self._wgrad("mlp3.w", dh2, h1, inv, not first, bias="mlp3.b")
+                dh1 = self._mm(dh2, self._wt["mlp3.w"])
+                self._relu_bwd(dh1, h1, keep_scale if masks is not None else 1.0)
+                self._wgrad("mlp0.w", dh1, inp, inv, not first, bias="mlp0.b")
+                dinp = self._mm(dh1, self._wt["mlp0.w"])                       # (2 rows, Dp) = [dstrip | dy | 0]
+                _lib.check(lib.r50_op_add_rows(dstrips.data_ptr(), d, dinp.data_ptr(), self._dp, rows2, self._et, self._stream()), None,
+                           "r50_op_add_rows")
+                if i > 0:
+                    _lib.check(lib.r50_op_add_rows(dyacc.data_ptr(), o, dinp.data_ptr() + 2 * d, self._dp, rows2, self._et, self._stream()),
+                               None, "r50_op_add_rows")
+            # ---------------- shift backward + latent loss + cast: f_AR's output gradient, in the arena ----------------
+            dx = self._arena.take(rows, d)
+            self._latent_loss(ar, phi, dstrips[rows:], b, t, self.lambda_latent, loss_scale, dx, losses[4:])
+            # ---------------- backward: f_AR blocks, last first (phase 2's launches) ----------------
+            for i in reversed(range(_AR_BLOCKS)):
+                p = f"f_AR.blocks.{i}"
+                xin, r1, h, r2, m = saved_ar[i]
+                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
+                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])
+                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
+                if m is not None:
+                    self._mask_scale(dh, m, keep_scale)
+                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
+                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
+                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)         # + the skip connection: block 0 gives f_AR's d/dphi
+            # ---------------- the gradient of phi: f_3D(phi)'s + f_AR's input gradient ----------------
+            dphi = dstrips[:rows]
+            _lib.check(lib.r50_op_add_rows(dphi.data_ptr(), d, dx.data_ptr(), d, rows, self._et, self._stream()), None, "r50_op_add_rows")
+            dx = torch.empty((rows, d), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(dphi.data_ptr(), rows, d, dx.data_ptr(), d, self._et, self._stream()), None, "r50_op_cast_rows")
+            # ---------------- backward: f_movie blocks, last first, and input_proj's dW (phase 1's launches) ----------------
+            for i in reversed(range(self.number_blocks)):
+                p = f"f_movie.blocks.{i}"
+                xin, r1, h, r2, m = saved_movie[i]
+                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
+                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])
+                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
+                if m is not None:
+                    self._mask_scale(dh, m, keep_scale)
+                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
+                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
+                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)
+            self._wgrad("input_proj.w", dx, x0, inv, False, bias="input_proj.b")
+            for chunk, used in zip(self._arena.chunks, self._arena.used):     # every 16-bit gradient the GEMMs and the latent kernel wrote
+                if used:
+                    _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
+                               "r50_op_check_overflow16")
+        yv = y.view(2, b, t, self.joints_num, 3)
+        return yv[0], yv[1], losses
+
+    def train_step(self, feats: torch.Tensor, joints3d: torch.Tensor, optim: AdamW, scaler: Optional[GradScaler] = None,
+                   masks: Optional[Dict[str, torch.Tensor]] = None, group=None) -> Tuple[float, float, bool]:
+        """One joint step (``TrainableHead.train_step``'s contract): forward + loss, scaled backward, inf check, AdamW over every
+        parameter, scale update.  Returns (loss, mpjpe, skipped); ``last_losses`` holds loss, l3d, mpjpe, l3d_hat, mpjpe_hat and l_lat."""
+        scale = scaler.get_scale() if scaler is not None else 1.0
+        _, _, losses = self.forward_backward(feats, joints3d, scale, masks)
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            all_reduce_gradients(self.flat_grad, group)
+            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
+                       "r50_op_check_finite")
+            sync_overflow_flag(self._found, group)
+            found = bool(self._found.item())
+            if not found:
+                optim.step(self._found)
+                self._refresh_transposes()
+            if scaler is not None:
+                scaler.update(found)
+            l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat = losses.tolist()
+        loss = l3d + self.lambda_future * l3d_hat + self.lambda_latent * l_lat
+        self.last_losses = {"loss": loss, "l3d": l3d, "mpjpe": mpjpe, "l3d_hat": l3d_hat, "mpjpe_hat": mpjpe_hat, "l_lat": l_lat}
+        return loss, mpjpe, found
+
+    def joint_losses(self, feats: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Eval-mode forward of one batch: ([l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat] fp32 device tensor, joints_phi (B,T,J,3) fp32).
+        The launches of ``__call__(feats, predict_future=True)`` (the regressor on phi and on phi_hat separately, as evaluation has
+        always run it), the pose terms by ``r50_op_joint_pose_loss_grad`` and l_lat by ``r50_op_ar_latent_grad`` (their gradients go
+        to scratch).  The second half's sums are ``r50_op_future_pose_loss_grad``'s, so l3d_hat / mpjpe_hat are phase 2's numbers."""
+        b, t = self._check_batch(feats, gt)
+        rows, d, o = b * t, self.latent_dim, self.out_dim
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            f = feats.to(torch.float32).contiguous()
+            x0 = torch.empty((rows, 2048), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(f.data_ptr(), rows, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None, "r50_op_cast_rows")
+            phi = self._temporal_net(self._gemm(x0, "input_proj", relu=False), b, t, "f_movie", self.number_blocks)
+            ar = self._temporal_net(phi, b, t, "f_AR", _AR_BLOCKS)
+            phi_hat = torch.empty_like(phi)
+            self._shift_into(ar, phi_hat, b, t)
+            joints_phi = self._regressor(phi, b, t)
+            joints_hat = self._regressor(phi_hat, b, t)
+            y = torch.cat([joints_phi.reshape(rows, o), joints_hat.reshape(rows, o)])
+            gtc = gt.to(torch.float32).contiguous()
+            losses = torch.empty(5, dtype=torch.float32, device=self._device)
+            self._joint_pose_loss(y, gtc, b, t, 1.0, 1.0, torch.empty((2 * rows, o), dtype=torch.float32, device=self._device), losses)
+            self._latent_loss(ar, phi, torch.zeros((rows, d), dtype=torch.float32, device=self._device), b, t, 1.0, 1.0,
+                              torch.empty((rows, d), dtype=self._dtype, device=self._device), losses[4:])
+        return losses, joints_phi
+
+
+@torch.no_grad()
+def evaluate_joint(head: JointTrainableHead, store, batch_size: int) -> Tuple[float, float, float, float, float, float]:
+    """The joint validation pass: (loss, l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat), each the mean over batches of the per-batch mean,
+    the items of ``store`` in order, ``batch_size`` at a time, the last batch kept even if short (as ``train.evaluate``).  l3d and
+    mpjpe over all frames by ``r50_op_pose_metrics`` (the numbers ``train.evaluate`` reports); l3d_hat, mpjpe_hat and l_lat over
+    frames s >= 1 (the numbers ``train_ar.evaluate_future`` reports); loss = l3d + lambda_future * l3d_hat + lambda_latent * l_lat
+    of the means.  The sums stay on the device and are read once per pass.  The head's mode is restored; its weights are not touched."""
+    was_training = head.training
+    head.train(False)
+    lib = _lib.load_library()
+    dev = head._device
+    try:
+        with torch.cuda.device(dev):
+            acc = torch.zeros(6, dtype=torch.float64, device=dev)        # [sum l3d_hat, sum mpjpe_hat, sum l_lat | l3d, mpjpe, batches]
+            for s in range(0, len(store), batch_size):
+                batch = store.get_batch(list(range(s, min(s + batch_size, len(store)))))
+                gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
+                losses, joints_phi = head.joint_losses(batch[0], gt)
+                acc[:3] += losses[2:].double()
+                _lib.check(lib.r50_op_pose_metrics(joints_phi.data_ptr(), gt.data_ptr(), gt.shape[0] * gt.shape[1], head.joints_num,
+                                                   acc[3:].data_ptr(), head._stream()), None, "r50_op_pose_metrics")
+            l3d_hat, mpjpe_hat, l_lat, l3d, mpjpe, n = acc.tolist()
+    finally:
+        head.train(was_training)
+    n = max(n, 1.0)
+    l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat = l3d / n, mpjpe / n, l3d_hat / n, mpjpe_hat / n, l_lat / n
+    return l3d + head.lambda_future * l3d_hat + head.lambda_latent * l_lat, l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat
+
+
+LOSS_KEYS = ("loss", "l3d", "mpjpe", "l3d_hat", "mpjpe_hat", "l_lat")
+
+
+def train_joint_epoch(head: JointTrainableHead, store, sampler, optim: AdamW, scaler: Optional[GradScaler], seed: int, epoch: int,
+                      log_every: int = 500) -> Tuple[Dict[str, float], int, int]:
+    """``train.train_epoch`` for the joint step: one ``train_step`` per batch of ``sampler`` (its epoch already set), masks from
+    ``make_dropout_masks`` with ``dropout_generator(seed, epoch, it)``.  Returns (the means of ``LOSS_KEYS`` over the batches,
+    applied steps, skipped steps)."""
+    head.train()
+    sums = {k: 0.0 for k in LOSS_KEYS}
+    n_batches = skipped = 0
+    for it, idx in enumerate(sampler):
+        feats, joints3d = store.get_batch(idx)[:2]
+        masks = head.make_dropout_masks(feats.shape[0], feats.shape[1], generator=dropout_generator(seed, epoch, it, head._device))
+        _, _, found = head.train_step(feats, joints3d, optim, scaler, masks=masks)
+        for k in sums:
+            sums[k] += head.last_losses[k]
+        n_batches += 1
+        skipped += int(found)
+        if log_every > 0 and (it + 1) % log_every == 0:
+            print(f"[joint] iter {it + 1:05d}/{len(sampler):05d} | loss {sums['loss'] / n_batches:.6f} | "
+                  f"mpjpe {sums['mpjpe'] / n_batches:.3f} | future mpjpe {sums['mpjpe_hat'] / n_batches:.3f}")
+    return {k: v / max(n_batches, 1) for k, v in sums.items()}, n_batches - skipped, skipped
+
+
+# ---- the driver ---------------------------------------------------------------------------------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    """Phase 1's flags and defaults (``train.build_parser``), ``--outdir ./runs/joint``, plus ``--init``, ``--lambda-future`` and
+    ``--lambda-latent``."""
+    p = argparse.ArgumentParser("Joint training: input_proj, f_movie, f_AR and f_3D under l3d + lambda_future * l3d_hat + lambda_latent * l_lat",
+                                parents=[_phase1_parser()], add_help=False)
+    p.set_defaults(outdir="./runs/joint")
+    p.add_argument("--init", type=str, default=None,
+                   help="phase-1 / phase-2 / rollout checkpoint (its 'model') or plain state dict to start from; required unless --resume "
+                        "names an existing file")
+    p.add_argument("--lambda-future", type=float, default=LAMBDA_FUTURE,
+                   help="weight of the future-pose loss mean((joints_hat - gt)^2) over frames >= 1, >= 0 (no run has measured a good value)")
+    p.add_argument("--lambda-latent", type=float, default=LAMBDA_LATENT,
+                   help="weight of the latent loss mean((phi_hat - phi.detach())^2) over frames >= 1, >= 0 (no run has measured a good value)")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    p = build_parser()
+    args = p.parse_args(argv)
+    if not args.init and not (args.resume and os.path.isfile(args.resume)):
+        p.error("--init is required unless --resume names an existing checkpoint")
+    if not (args.lambda_future >= 0 and args.lambda_latent >= 0):          # also refuses nan
+        p.error("--lambda-future and --lambda-latent must be >= 0")
+    return args
+
+
+def main(argv: Optional[List[str]] = None) -> float:
+    """Joint training on one MI355X.  Per epoch, in ``train.main``'s order: train, evaluate, scheduler step, ``last.pt``, ``best.pt``
+    when val mpjpe + mpjpe_hat improved by more than ``--early-stop-min-delta``, patience counter.  ``--resume`` loads model and
+    optimizer; the head's dimensions come from the checkpoint.  Prints one JSON line per epoch.  Returns the best val
+    mpjpe + mpjpe_hat."""
+    from .feature_store import DeviceFeatureStore
+    from .results import infer_head_dims, load_head_state
+    from .samplers import MixedShardBatchSampler
+
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    os.makedirs(args.outdir, exist_ok=True)
+    train_set = DeviceFeatureStore(args.train, subjects=args.train_subjects, augment=True, device=device)
+    val_set = DeviceFeatureStore(args.val, subjects=args.val_subjects, device=device)
+    sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
+
+    resume = bool(args.resume and os.path.isfile(args.resume))
+    state = load_head_state(args.init if args.init else args.resume)
+    latent_dim, joints_num, number_blocks = infer_head_dims(state)
+    head = JointTrainableHead(latent_dim, joints_num, number_blocks, precision=args.precision, lambda_future=args.lambda_future,
+                              lambda_latent=args.lambda_latent)
+    head.load_state_dict(state, strict=True)
+    head.to(device)
+    optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
+    scaler = GradScaler()
+    schedule = CosineLR(args.lr, args.epochs)
+
+    start_epoch, best_val, no_improve_epochs = 0, float("inf"), 0
+    if resume:
+        ckpt = load_checkpoint(args.resume, head, optim)
+        schedule.load_group(ckpt["optim"])
+        start_epoch = int(ckpt.get("epoch", 0)) + 1
+        best_val = float(ckpt.get("best_val", best_val))
+        print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
+
+    print("===== Joint training (input_proj, f_movie, f_AR, f_3D) =====")
+    print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
+    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
+    print(f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_future: {args.lambda_future} | lambda_latent: {args.lambda_latent} | "
+          f"seed: {args.seed}")
+    print("============================================================")
+    for epoch in range(start_epoch, args.epochs):
+        sampler.set_epoch(epoch)
+        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
+        print(f"\nEpoch {epoch + 1}/{args.epochs}")
+        t0 = time.time()
+        epoch_lr = optim.lr
+        tr, steps, skipped = train_joint_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every)
+        va = dict(zip(LOSS_KEYS, evaluate_joint(head, val_set, args.batch_size)))
+        schedule.step()
+        optim.lr = schedule.lr
+        va_score = va["mpjpe"] + va["mpjpe_hat"]
+        print(f"Train: loss={tr['loss']:.6f} | l3d={tr['l3d']:.6f} | l3d_hat={tr['l3d_hat']:.6f} | l_lat={tr['l_lat']:.6f} | "
+              f"mpjpe={tr['mpjpe']:.3f} | future mpjpe={tr['mpjpe_hat']:.3f}")
+        print(f"Val:   loss={va['loss']:.6f} | l3d={va['l3d']:.6f} | l3d_hat={va['l3d_hat']:.6f} | l_lat={va['l_lat']:.6f} | "
+              f"mpjpe={va['mpjpe']:.3f} | future mpjpe={va['mpjpe_hat']:.3f}")
+        print(f"Epoch time: {time.time() - t0:.2f}s")
+        line = {"epoch": epoch, "lr": epoch_lr}
+        line.update({f"train_{k}": v for k, v in tr.items()})
+        line.update({"steps": steps, "skipped": skipped})
+        line.update({f"val_{k}": v for k, v in va.items()})
+        line["val_mpjpe_sum"] = va_score
+        print(json.dumps(line))
+
+        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
+        if (best_val - va_score) > args.early_stop_min_delta:
+            best_val = va_score
+            no_improve_epochs = 0
+            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
+            print(f"New best val mpjpe + future mpjpe: {best_val:.3f} (saved best.pt)")
+        else:
+            no_improve_epochs += 1
+            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
+                  f"(best {best_val:.3f}, current {va_score:.3f})")
+        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
+            print(f"Early stopping triggered at epoch {epoch + 1}. Best val mpjpe + future mpjpe: {best_val:.3f}")
+            break
+    print("\nDone.")
+    print(f"Best val mpjpe + future mpjpe: {best_val:.3f}")
+    return best_val
+
+
+if __name__ == "__main__":
+    main()

@@ -377,6 +377,21 @@ int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int
 int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
                           void* dar, float* loss_lat, float* row_part, int et, void* stream);
 
+/* Lifting head, joint training (input_proj, f_movie, f_AR and f_3D under one loss).
+ *  r50_op_joint_pose_loss_grad: y, dy (2*b*t, joints, 3) fp32, the regressor's output on [phi ; phi_hat] stacked by rows; gt
+ *    (b, t, joints, 3) fp32.  First half: dy = 2 (y-gt) / n1 * loss_scale, n1 = b*t*joints*3 (r50_op_mse_loss_grad's arithmetic).
+ *    Second half: dy = 2 (y-gt) / n2 * (loss_scale * lambda_future), n2 = b*(t-1)*joints*3, exact 0 on frame 0 of every clip
+ *    (r50_op_future_pose_loss_grad's arithmetic).  out4 = [l3d, mpjpe over all frames, l3d_hat, mpjpe_hat over frames s >= 1].  One
+ *    launch; fp64 sums in a fixed order without atomics (the same bits on every run).  Needs b >= 1, t >= 2, 1 <= joints <= 64;
+ *    checked before any launch.
+ *  r50_op_colsum_split: r50_op_colsum's result bit for bit (the same summation order and roundings), its 16 row chains per column
+ *    spread over 16 x ceil(cols/64) workgroups with loads in flight, then summed in order by a second launch; part: 16*cols floats
+ *    of device scratch.  The joint step's bias gradients, over up to 2*b*t rows. */
+int r50_op_colsum_split(const void* x, int64_t rows, int cols, int ld, float scale, float* part, float* out_f32, int accumulate, int et,
+                        void* stream);
+int r50_op_joint_pose_loss_grad(const float* y, const float* gt, int b, int t, int joints, float lambda_future, float loss_scale, float* dy,
+                                float* out4, void* stream);
+
 /* Lifting head, rollout training (f_AR trained on its own multi-step rollouts).  Time-major buffers: row
  * h*b + b' is frame (or horizon) h of sample b'.
  *  r50_op_gn_relu_causal3_tm_bwd: backward of r50_op_gn_relu_causal3_tm.  dr ((t-t0)*b, 3c) = the gradient of exactly the rows the
