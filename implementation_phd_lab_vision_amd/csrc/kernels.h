@@ -4937,6 +4937,143 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     }
 }
 
+// ---- Geometric pose losses: 3D + 2D reprojection + velocity + bone length in one pass ---------------
+//   uv = (K P)[:2] / clamp((K P)[2], min = eps)   (src/train.py:84-110: the numerator is NOT clamped; below the clamp the
+//                                                   denominator carries no gradient, at (K P)[2] == eps it does)
+//   l3d = mean (p - g)^2,  l2d = mean (uv - g2d)^2,  l_vel = mean ((p[s+1] - p[s]) - (g[s+1] - g[s]))^2 over pairs s >= s0,
+//   l_bone = mean (|p[b] - p[a]| - |g[b] - g[a]|)^2 over the edges (a, b) (src/train.py:50-57; a bone of length 0 gets gradient 0)
+//   dy = sc * d(l3d + lambda_2d l2d + lambda_vel l_vel + lambda_bone l_bone) / dp over the frames s >= s0; +0 on frames < s0.
+// One workgroup of 256 per clip; the clip's predicted and target poses are staged once in LDS (2 * t * joints * 3 floats), every
+// thread owns (frame, joint) items and GATHERS their three dy components: its own 3D and 2D residuals, the two velocity pairs that
+// touch its frame, the bones incident to its joint.  No atomics.  Per-joint arithmetic fp32; the sums are per-thread fp64 partials
+// over a fixed strided slice and a fixed fp64 tree into part[clip][8]; geo_pose_sum_kernel adds the clips in a fixed order.
+// The 3D term is `2.f * d / n3 * sc` (mse_loss_grad_kernel's / future_pose_loss_grad_kernel's expression); a term whose weight is 0 is
+// skipped, not added as zeros, so with all three off dy has those kernels' bits.  c2, cv, cb = 2 * lambda / n of each term, rounded
+// once on the host.  Each bone's loss is counted by the thread that owns its second joint.
+constexpr int GEO_MAX_TJ = 4608;          // t * joints per clip: 24 B of LDS each (108 KB) + 16 KB of reduction space; T 256 x J 18
+constexpr int GEO_MAX_EDGES = 64;
+struct GeoEdges { int ab[GEO_MAX_EDGES]; };      // a | b << 8, by value in the kernel arguments (no device allocation: graph-capturable)
+
+__global__ __launch_bounds__(256) void geo_pose_loss_grad_kernel(const float* __restrict__ y, const float* __restrict__ gt3d,
+                                                                 const float* __restrict__ gt2d, const float* __restrict__ Kmat, int t, int s0,
+                                                                 int joints, GeoEdges ed, int n_edges, int on2d, int onvel, int onbone,
+                                                                 float n3, float sc, float c2, float cv, float cb, float eps,
+                                                                 float* __restrict__ dy, double* __restrict__ part) {
+    extern __shared__ float geo_sm[];
+    __shared__ double red[8][256];
+    const int tj = t * joints, tid = threadIdx.x;
+    const long long base = (long long)blockIdx.x * tj;
+    float* P = geo_sm;
+    float* G = geo_sm + 3 * tj;
+    for (int i = tid; i < 3 * tj; i += 256) { P[i] = y[3 * base + i]; G[i] = gt3d[3 * base + i]; }
+    const float* Kc = Kmat + 9ll * blockIdx.x;
+    const float k00 = Kc[0], k01 = Kc[1], k02 = Kc[2], k10 = Kc[3], k11 = Kc[4], k12 = Kc[5], k20 = Kc[6], k21 = Kc[7], k22 = Kc[8];
+    __syncthreads();
+    const bool extra = on2d || onvel || onbone;
+    double a3 = 0.0, am = 0.0, a2 = 0.0, ar = 0.0, av = 0.0, ab = 0.0, ac = 0.0;
+    for (int i = tid; i < tj; i += 256) {
+        const int s = i / joints, j = i - s * joints;
+        if (s < s0) {
+            if (dy) { dy[3 * (base + i)] = 0.f; dy[3 * (base + i) + 1] = 0.f; dy[3 * (base + i) + 2] = 0.f; }
+            continue;
+        }
+        const float p[3] = {P[3 * i], P[3 * i + 1], P[3 * i + 2]}, g[3] = {G[3 * i], G[3 * i + 1], G[3 * i + 2]};
+        float g3[3], e[3] = {0.f, 0.f, 0.f}, d2 = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const float d = p[k] - g[k];
+            g3[k] = 2.f * d / n3 * sc;
+            d2 += d * d;
+        }
+        a3 += (double)d2; am += (double)sqrtf(d2);
+        // ---- reprojection
+        {
+            const float h0 = k00 * p[0] + k01 * p[1] + k02 * p[2], h1 = k10 * p[0] + k11 * p[1] + k12 * p[2];
+            const float h2 = k20 * p[0] + k21 * p[1] + k22 * p[2];
+            const bool clamped = h2 < eps;
+            const float zc = clamped ? eps : h2;
+            const float u = h0 / zc, v = h1 / zc;
+            const float ru = u - gt2d[2 * (base + i)], rv = v - gt2d[2 * (base + i) + 1];
+            const float r2 = ru * ru + rv * rv;
+            a2 += (double)r2; ar += (double)sqrtf(r2); ac += clamped ? 1.0 : 0.0;
+            if (on2d) {
+                const float q0 = ru / zc, q1 = rv / zc, q2 = clamped ? 0.f : -(q0 * u + q1 * v);
+                e[0] += c2 * (k00 * q0 + k10 * q1 + k20 * q2);
+                e[1] += c2 * (k01 * q0 + k11 * q1 + k21 * q2);
+                e[2] += c2 * (k02 * q0 + k12 * q1 + k22 * q2);
+            }
+        }
+        // ---- velocity: pair (s, s+1) is counted here; pairs (s, s+1) and (s-1, s) both reach this frame's gradient
+        if (s + 1 < t) {
+            const int n = 3 * (i + joints);
+            float w2 = 0.f;
+            for (int k = 0; k < 3; ++k) {
+                const float w = (P[n + k] - p[k]) - (G[n + k] - g[k]);
+                w2 += w * w;
+                if (onvel) e[k] -= cv * w;
+            }
+            av += (double)w2;
+        }
+        if (onvel && s - 1 >= s0) {
+            const int n = 3 * (i - joints);
+            for (int k = 0; k < 3; ++k) e[k] += cv * ((p[k] - P[n + k]) - (g[k] - G[n + k]));
+        }
+        // ---- bones incident to joint j
+        for (int q = 0; q < n_edges; ++q) {
+            const int ea = ed.ab[q] & 255, eb = ed.ab[q] >> 8;
+            if (ea == eb || (ea != j && eb != j)) continue;   // a self-loop has length 0 on both sides: loss 0, gradient 0
+            const int o = 3 * (s * joints + (eb == j ? ea : eb));
+            const float sgn = eb == j ? 1.f : -1.f;          // bone = p[b] - p[a]
+            float bp[3], pl2 = 0.f, gl2 = 0.f;
+            for (int k = 0; k < 3; ++k) {
+                bp[k] = sgn * (p[k] - P[o + k]);
+                const float bg = sgn * (g[k] - G[o + k]);
+                pl2 += bp[k] * bp[k]; gl2 += bg * bg;
+            }
+            const float pl = sqrtf(pl2), df = pl - sqrtf(gl2);
+            if (eb == j) ab += (double)(df * df);
+            if (onbone && pl > 0.f)
+                for (int k = 0; k < 3; ++k) e[k] += sgn * (cb * df * (bp[k] / pl));
+        }
+        if (dy)
+            for (int k = 0; k < 3; ++k) dy[3 * (base + i) + k] = extra ? g3[k] + sc * e[k] : g3[k];
+    }
+    red[0][tid] = a3; red[1][tid] = am; red[2][tid] = a2; red[3][tid] = ar; red[4][tid] = av; red[5][tid] = ab; red[6][tid] = ac;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o)
+            for (int q = 0; q < 7; ++q) red[q][tid] += red[q][tid + o];
+        __syncthreads();
+    }
+    if (tid < 8) part[8ll * blockIdx.x + tid] = tid < 7 ? red[tid][0] : 0.0;
+}
+
+// out8 = [loss, l3d, mpjpe, l2d, reproj_px, l_vel, l_bone, n_clamped] from part (b, 8): 8 x 64 threads, thread (q, lane) adds the
+// clips lane, lane + 64, ... of sum q, then a fixed fp64 tree over the 64 lanes.  nj = included joints b*(t-s0)*joints, nvj = joints
+// of the velocity pairs b*(t-s0-1)*joints, nb = bones b*(t-s0)*n_edges; an empty mean (nvj or nb = 0) is reported as 0.
+__global__ __launch_bounds__(512) void geo_pose_sum_kernel(const double* __restrict__ part, int b, double nj, double nvj, double nb,
+                                                           float l2, float lv, float lb, float* __restrict__ out8) {
+    __shared__ double red[8][64];
+    const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (int c = lane; c < b; c += 64) s += part[8ll * c + q];
+    red[q][lane] = s;
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) {
+        if (lane < o) red[q][lane] += red[q][lane + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double l3d = red[0][0] / (3.0 * nj), l2d = red[2][0] / (2.0 * nj);
+        const double lvel = nvj > 0.0 ? red[4][0] / (3.0 * nvj) : 0.0, lbone = nb > 0.0 ? red[5][0] / nb : 0.0;
+        double loss = l3d;
+        if (l2 != 0.f) loss += (double)l2 * l2d;
+        if (lv != 0.f) loss += (double)lv * lvel;
+        if (lb != 0.f) loss += (double)lb * lbone;
+        out8[0] = (float)loss; out8[1] = (float)l3d; out8[2] = (float)(red[1][0] / nj); out8[3] = (float)l2d;
+        out8[4] = (float)(red[3][0] / nj); out8[5] = (float)lvel; out8[6] = (float)lbone; out8[7] = (float)red[6][0];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Stem, step 1: fp32 NCHW (N,3,224,224) -> bf16 "NHWC4" with a zero border:
 //   xp[n][hp][wp][4], hp = hi + 3 in [0,230), wp = wi + 4 in [0,232); channel 3 = 0.

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "../../include/r50.h"
 
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -2449,6 +2450,56 @@ int r50_op_joint_pose_loss_grad(const float* y, const float* gt, int b, int t, i
     hipLaunchKernelGGL(joint_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, y, gt, (long long)b * t, t, joints,
                        loss_scale, loss_scale * lambda_future, dy, out4);
     return ew_done("r50_op_joint_pose_loss_grad");
+}
+
+int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt2d, const float* K, int b, int t, int s0, int joints,
+                              const int* edges_host, int n_edges, float lambda_2d, float lambda_vel, float lambda_bone, float eps,
+                              float term_scale, float loss_scale, float* dy, double* part, float* out8, void* stream) {
+    const char* me = "r50_op_geo_pose_loss_grad: ";
+    auto bad = [&](const char* why) { return fail(nullptr, R50_ERR_INVALID, std::string(me) + why); };
+    if (!y || !gt3d || !gt2d || !K || !part || !out8) return bad("null pointer (y, gt3d, gt2d, K, part and out8 are required; only dy may be NULL)");
+    if (b < 1) return bad("need b >= 1");
+    if (s0 < 0 || s0 > 1) return bad("need 0 <= s0 <= 1");
+    if (t < 1 || t - s0 < 1) return bad("need t - s0 >= 1");
+    if (joints < 1 || joints > 64) return bad("need 1 <= joints <= 64");
+    if (n_edges < 0 || n_edges > GEO_MAX_EDGES) return bad("need 0 <= n_edges <= 64");
+    if (n_edges > 0 && !edges_host) return bad("null pointer (edges_host with n_edges > 0)");
+    if (!std::isfinite(lambda_2d) || !std::isfinite(lambda_vel) || !std::isfinite(lambda_bone) || lambda_2d < 0.f || lambda_vel < 0.f ||
+        lambda_bone < 0.f)
+        return bad("the lambdas must be finite and >= 0");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return bad("need eps > 0");
+    if (lambda_vel != 0.f && t - s0 < 2) return bad("need t - s0 >= 2 when lambda_vel != 0");
+    if ((int64_t)t * joints > GEO_MAX_TJ) return bad("t * joints exceeds 4608, the most one workgroup stages in LDS (T 256 at J 17 fits)");
+    if ((int64_t)b * t * joints > INT32_MAX / 3) return bad("b * t * joints * 3 exceeds the int range");
+    GeoEdges ed;
+    for (int q = 0; q < GEO_MAX_EDGES; ++q) ed.ab[q] = 0;
+    for (int q = 0; q < n_edges; ++q) {
+        const int ea = edges_host[2 * q], eb = edges_host[2 * q + 1];
+        if (ea < 0 || ea >= joints || eb < 0 || eb >= joints) return bad("every edge index must be in [0, joints)");
+        ed.ab[q] = ea | (eb << 8);
+    }
+    const double nj = (double)b * (t - s0) * joints, nvj = (double)b * (t - s0 - 1) * joints, nb = (double)b * (t - s0) * n_edges;
+    const float c2 = (float)(2.0 * (double)lambda_2d / (2.0 * nj));
+    const float cv = nvj > 0.0 ? (float)(2.0 * (double)lambda_vel / (3.0 * nvj)) : 0.f;
+    const float cb = nb > 0.0 ? (float)(2.0 * (double)lambda_bone / nb) : 0.f;
+    const size_t lds = (size_t)t * joints * 24;
+    static std::atomic<unsigned long long> lds_set{0};      // the kernel's dynamic-LDS ceiling is raised once per device, not per call
+    int dev = 0;
+    hipError_t ea = hipGetDevice(&dev);
+    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(ea));
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+    if (!bit || !(lds_set.load() & bit)) {
+        ea = hipFuncSetAttribute(reinterpret_cast<const void*>(geo_pose_loss_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 GEO_MAX_TJ * 24);
+        if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(ea));
+        lds_set.fetch_or(bit);
+    }
+    hipLaunchKernelGGL(geo_pose_loss_grad_kernel, dim3((unsigned)b), dim3(256), lds, (hipStream_t)stream, y, gt3d, gt2d, K, t, s0, joints, ed,
+                       n_edges, (int)(lambda_2d != 0.f), (int)(lambda_vel != 0.f && nvj > 0.0), (int)(lambda_bone != 0.f && nb > 0.0),
+                       (float)(3ll * (long long)nj), loss_scale * term_scale, c2, cv, cb, eps, dy, part);
+    hipLaunchKernelGGL(geo_pose_sum_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, (const double*)part, b, nj, nvj, nb, lambda_2d,
+                       lambda_vel, lambda_bone, out8);
+    return ew_done("r50_op_geo_pose_loss_grad");
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }

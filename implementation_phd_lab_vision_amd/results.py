@@ -72,6 +72,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--protocols", action="store_true",
                    help="also score root-relative MPJPE (P1) and PA-MPJPE (P2) per action over every test clip, and per horizon "
                         "with --pred-len (INTEGRATION.md section L)")
+    p.add_argument("--geo-metrics", action="store_true",
+                   help="also report the test-subject 2D reprojection loss and pixel error, velocity and bone-length losses and the number of "
+                        "predicted joints at or behind the camera plane, over the same batches (INTEGRATION.md section N)")
     return p
 
 
@@ -278,6 +281,12 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in protocol_lines(protocols, args.input_len, args.pred_len):
             print(line)
 
+    geo = None
+    if args.geo_metrics:                     # the loader's batches again, the terms by r50_op_geo_pose_loss_grad with dy = NULL
+        from .train import GEO_EXTRA_KEYS, GeoWeights, evaluate_geo
+        geo = evaluate_geo(head, test_set, args.batch_size, GeoWeights(), batches=eval_batches)
+        print("Geo metrics | " + " | ".join(f"{key}: {geo[key]:.6f}" for key in GEO_EXTRA_KEYS))
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -297,6 +306,9 @@ def main(argv: Optional[List[str]] = None) -> str:
                  "rollout_lens": np.array([args.input_len, args.pred_len], dtype=np.int64)}
     if protocols is not None:
         extra.update(protocol_arrays(protocols))
+    if geo is not None:
+        extra["geo_metrics"] = np.array([geo[key] for key in GEO_EXTRA_KEYS], dtype=np.float64)
+        extra["geo_metric_names"] = np.array(GEO_EXTRA_KEYS)
     np.savez_compressed(out_path, video=videos, joints3d=joints3d_np, predicted3djoints=pred,
                         joints2d=joints2d[:n_save].cpu().numpy(), K=k[:n_save].to(torch.float32).cpu().numpy(),
                         meta=np.array(list(metas[:n_save]), dtype=object),

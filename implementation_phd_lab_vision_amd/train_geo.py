@@ -1,0 +1,95 @@
+"""Head training with the geometric losses: 2D reprojection, velocity and bone length next to l3d.
+``python -m implementation_phd_lab_vision_amd.train_geo [--stage {phase1,joint}]``.
+
+The reference carries the pieces switched off (src/train.py: ``project_with_K_torch`` :84-110, ``bone_length_loss`` :50-57,
+``H36M_EDGES`` :29-35, ``lambda_vel`` / ``lambda_bone`` on ``train()`` :114, "disable 2D loss during warmup" :227-229, then
+``loss = l3d``).  This project's definition of the program they describe, in the reference's idiom::
+
+    uv      = project_with_K_torch(pred, K)
+    l3d     = (pred - joints3d).pow(2).mean()
+    l2d     = (uv - joints2d).pow(2).mean()
+    l_vel   = ((pred[:, 1:] - pred[:, :-1]) - (joints3d[:, 1:] - joints3d[:, :-1])).pow(2).mean()
+    l_bone  = bone_length_loss(pred, joints3d)
+    loss    = l3d + lambda_2d * l2d + lambda_vel * l_vel + lambda_bone * l_bone         # lambda_2d = 0 in epochs < --warmup-2d-epochs
+
+``--stage phase1`` is ``train``'s driver (f_AR frozen) and ``--stage joint`` is ``train_joint``'s (every parameter; both pose terms
+gain the geometric terms, the second over ``joints_hat[:, 1:]``) with this loss: their parsers plus ``--lambda-vel``,
+``--lambda-bone`` and ``--warmup-2d-epochs``; their epoch order, checkpoints, patience and resume.  ``best.pt`` keeps following val
+MPJPE (``mpjpe + mpjpe_hat`` for ``joint``), which does not depend on the weights, so runs compare.  The loss and its gradient are one
+HIP op, ``r50_op_geo_pose_loss_grad``.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import List, Optional
+
+from . import train, train_joint
+from .train import GeoWeights
+
+STAGES = ("phase1", "joint")
+LAMBDA_VEL = 1.0            # the defaults of the reference's train() signature (src/train.py:114)
+LAMBDA_BONE = 1.0
+WARMUP_2D_EPOCHS = 1
+
+
+def _stage_of(argv: Optional[List[str]]) -> str:
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--stage", choices=STAGES, default="phase1")
+    return pre.parse_known_args(sys.argv[1:] if argv is None else argv)[0].stage
+
+
+def build_parser(stage: str = "phase1") -> argparse.ArgumentParser:
+    """The chosen stage's parser (its flags, defaults and help) plus ``--stage``, ``--lambda-vel``, ``--lambda-bone`` and
+    ``--warmup-2d-epochs``; ``--outdir`` defaults to ./runs/geo and ``--lambda-2d`` takes effect."""
+    if stage not in STAGES:
+        raise ValueError(f"stage: expected one of {STAGES}, got {stage!r}")
+    parent = train.build_parser() if stage == "phase1" else train_joint.build_parser()
+    p = argparse.ArgumentParser(prog="python -m implementation_phd_lab_vision_amd.train_geo",
+                                description=f"Head training with 2D reprojection, velocity and bone-length losses ({stage})",
+                                parents=[parent], add_help=False, conflict_handler="resolve")
+    p.set_defaults(outdir="./runs/geo")
+    p.add_argument("--stage", choices=STAGES, default="phase1", help="phase1: f_AR frozen (train's driver); joint: every parameter "
+                                                                     "(train_joint's driver, needs --init)")
+    p.add_argument("--lambda-2d", type=float, default=train.build_parser().get_default("lambda_2d"),
+                   help="weight of the 2D reprojection loss mean((project(pred, K) - joints2d)^2), pixels^2, >= 0")
+    p.add_argument("--lambda-vel", type=float, default=LAMBDA_VEL,
+                   help="weight of the velocity loss on frame-to-frame differences, >= 0 (no run has measured a good value)")
+    p.add_argument("--lambda-bone", type=float, default=LAMBDA_BONE,
+                   help="weight of the bone-length loss over the 16 edges of the H3.6M skeleton, >= 0 (no run has measured a good value)")
+    p.add_argument("--warmup-2d-epochs", type=int, default=WARMUP_2D_EPOCHS,
+                   help="the 2D term's weight is 0 in epochs < N: a fresh head predicts poses at or behind the camera plane, where the "
+                        "2D gradient is ~1e9 and fp16 steps overflow and are skipped.  The default of 1 is a guess nobody has measured")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    stage = _stage_of(argv)
+    p = build_parser(stage)
+    args = p.parse_args(argv)
+    for name in ("lambda_2d", "lambda_vel", "lambda_bone"):
+        if not (getattr(args, name) >= 0 and getattr(args, name) != float("inf")):          # also refuses nan
+            p.error("--lambda-2d, --lambda-vel and --lambda-bone must be finite and >= 0")
+    if args.warmup_2d_epochs < 0:
+        p.error("--warmup-2d-epochs must be >= 0")
+    if stage == "joint":
+        train_joint.validate_args(p, args)
+    return args
+
+
+def geo_schedule(args: argparse.Namespace):
+    """epoch -> the weights of that epoch: ``--lambda-2d`` from epoch ``--warmup-2d-epochs`` on, 0 before."""
+    def weights(epoch: int) -> GeoWeights:
+        return GeoWeights(args.lambda_2d if epoch >= args.warmup_2d_epochs else 0.0, args.lambda_vel, args.lambda_bone)
+    return weights
+
+
+def main(argv: Optional[List[str]] = None) -> float:
+    """The stage's driver (``train.run`` / ``train_joint.run``) under the composite loss.  Returns the stage's best validation score."""
+    args = parse_args(argv)
+    runner = train.run if args.stage == "phase1" else train_joint.run
+    return runner(args, geo_for_epoch=geo_schedule(args))
+
+
+if __name__ == "__main__":
+    main()

@@ -57,8 +57,9 @@ import torch
 
 from . import _lib
 from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
-from .train import (DROPOUT_P, AdamW, CosineLR, GradScaler, TrainableHead, _Arena, _BackwardLaunches, all_reduce_gradients,
-                    build_parser as _phase1_parser, dropout_generator, load_checkpoint, save_checkpoint, sync_overflow_flag)
+from .train import (DROPOUT_P, GEO_EXTRA_KEYS, GEO_KEYS, AdamW, CosineLR, GeoWeights, GradScaler, TrainableHead, _Arena, _BackwardLaunches,
+                    all_reduce_gradients, build_parser as _phase1_parser, dropout_generator, geo_pose_loss_grad,
+                    load_checkpoint, save_checkpoint, sync_overflow_flag)
 from .train_ar import ARTrainableHead
 
 LAMBDA_FUTURE = 1.0
@@ -233,6 +234,26 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
                                                                     loss_scale, dy.data_ptr(), out.data_ptr(), self._stream()), None,
                    "r50_op_joint_pose_loss_grad")
 
+    _check_geo = TrainableHead._check_geo
+
+    def _geo_pose_loss(self, y: torch.Tensor, gt: torch.Tensor, gt2d: torch.Tensor, kmat: torch.Tensor, b: int, t: int, geo: GeoWeights,
+                       lambda_future: float, loss_scale: float, dy: Optional[torch.Tensor], out: torch.Tensor) -> torch.Tensor:
+        """``_joint_pose_loss`` under section N's composite loss: two ``r50_op_geo_pose_loss_grad`` launches over the stacked rows, the
+        first half at s0 = 0, term_scale = 1, the second at s0 = 1 (frame 0 of phi_hat is zeros), term_scale = lambda_future.
+        out[0:4] as ``_joint_pose_loss`` fills it; returns the two halves' out8 as a (2, 8) fp32 device tensor."""
+        if t < 3 and geo.lambda_vel != 0:
+            raise ValueError("geo: the velocity term of joints_hat[:, 1:] needs clips of at least 3 frames")
+        rows = b * t
+        out16 = torch.empty((2, 8), dtype=torch.float32, device=self._device)
+        yv = y.view(2, rows, self.out_dim)
+        dv = dy.view(2, rows, self.out_dim) if dy is not None else (None, None)
+        geo_pose_loss_grad(yv[0], gt, gt2d, kmat, b, t, self.joints_num, geo, out16[0], dy=dv[0], loss_scale=loss_scale, stream=self._stream())
+        geo_pose_loss_grad(yv[1], gt, gt2d, kmat, b, t, self.joints_num, geo, out16[1], dy=dv[1], s0=1, term_scale=lambda_future,
+                           loss_scale=loss_scale, stream=self._stream())
+        out[0:2].copy_(out16[0, 1:3])
+        out[2:4].copy_(out16[1, 1:3])
+        return out16
+
     def _latent_loss(self, ar: torch.Tensor, phi: torch.Tensor, dphi_hat: torch.Tensor, b: int, t: int, lambda_latent: float,
                      loss_scale: float, dar: torch.Tensor, out: torch.Tensor) -> None:
         """out[0] = l_lat; dar (B*T, D) 16-bit = f_AR's output gradient: dphi_hat shifted back + lambda_latent * dl_lat, * loss_scale."""
@@ -249,13 +270,20 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         v[:, 1:, :] = ar.view(b, t, d)[:, :-1, :]
 
     def forward_backward(self, feats: torch.Tensor, joints3d: torch.Tensor, loss_scale: float = 1.0,
-                         masks: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         masks: Optional[Dict[str, torch.Tensor]] = None, joints2d: Optional[torch.Tensor] = None,
+                         K: Optional[torch.Tensor] = None,
+                         geo: Optional[GeoWeights] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The joint forward (train mode when ``masks`` is given or ``self.training``; else dropout is identity), the loss
         l3d + lambda_future * l3d_hat + lambda_latent * l_lat, backward into ``flat_grad`` (UNSCALED: the 16-bit backward runs on
         loss_scale * loss, the fp32 buffer receives grad / loss_scale).  ``self._found`` is raised when a 16-bit gradient overflowed.
         Returns (joints_phi (B,T,J,3) fp32, joints_hat (B,T,J,3) fp32, losses = [l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat] fp32 device
-        tensor)."""
+        tensor).
+        ``geo`` (with ``joints2d`` (B,T,J,2) and ``K`` (B,3,3) or (3,3)): both pose terms gain section N's geometric terms, loss =
+        l3d + geo(joints_phi) + lambda_future * (l3d_hat + geo(joints_hat[:, 1:])) + lambda_latent * l_lat; two launches of
+        ``r50_op_geo_pose_loss_grad`` take the place of ``r50_op_joint_pose_loss_grad`` and ``self._geo_out16`` holds their numbers."""
         b, t = self._check_batch(feats, joints3d)
+        if geo is not None:
+            gt2d, kmat = self._check_geo(b, t, joints2d, K)
         if masks is None and self.training:
             masks = self.make_dropout_masks(b, t)
         keep_scale = 1.0 / (1.0 - DROPOUT_P)
@@ -319,7 +347,10 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             gt = joints3d.to(torch.float32).contiguous()
             dyacc = torch.empty((rows2, o), dtype=torch.float32, device=self._device)
             losses = torch.empty(5, dtype=torch.float32, device=self._device)
-            self._joint_pose_loss(y, gt, b, t, self.lambda_future, loss_scale, dyacc, losses)
+            if geo is None:
+                self._joint_pose_loss(y, gt, b, t, self.lambda_future, loss_scale, dyacc, losses)
+            else:
+                self._geo_out16 = self._geo_pose_loss(y, gt, gt2d, kmat, b, t, geo, self.lambda_future, loss_scale, dyacc, losses)
             # ---------------- backward: the regressor over the stacked rows, with weight gradients (phase 1's launches) ----------------
             dstrips = torch.zeros((rows2, d), dtype=torch.float32, device=self._device)   # [dphi from f_3D(phi) ; dphi_hat]
             g5 = torch.empty((rows2, self._op), dtype=self._dtype, device=self._device)
@@ -382,11 +413,13 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         return yv[0], yv[1], losses
 
     def train_step(self, feats: torch.Tensor, joints3d: torch.Tensor, optim: AdamW, scaler: Optional[GradScaler] = None,
-                   masks: Optional[Dict[str, torch.Tensor]] = None, group=None) -> Tuple[float, float, bool]:
+                   masks: Optional[Dict[str, torch.Tensor]] = None, group=None, joints2d: Optional[torch.Tensor] = None,
+                   K: Optional[torch.Tensor] = None, geo: Optional[GeoWeights] = None) -> Tuple[float, float, bool]:
         """One joint step (``TrainableHead.train_step``'s contract): forward + loss, scaled backward, inf check, AdamW over every
-        parameter, scale update.  Returns (loss, mpjpe, skipped); ``last_losses`` holds loss, l3d, mpjpe, l3d_hat, mpjpe_hat and l_lat."""
+        parameter, scale update.  Returns (loss, mpjpe, skipped); ``last_losses`` holds loss, l3d, mpjpe, l3d_hat, mpjpe_hat and l_lat,
+        and with ``geo`` also l2d, reproj_px, l_vel, l_bone, n_clamped of each half (the second under ``*_hat``)."""
         scale = scaler.get_scale() if scaler is not None else 1.0
-        _, _, losses = self.forward_backward(feats, joints3d, scale, masks)
+        _, _, losses = self.forward_backward(feats, joints3d, scale, masks, joints2d, K, geo)
         lib = _lib.load_library()
         with torch.cuda.device(self._device):
             all_reduce_gradients(self.flat_grad, group)
@@ -400,16 +433,25 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             if scaler is not None:
                 scaler.update(found)
             l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat = losses.tolist()
+            g16 = self._geo_out16.tolist() if geo is not None else None
         loss = l3d + self.lambda_future * l3d_hat + self.lambda_latent * l_lat
         self.last_losses = {"loss": loss, "l3d": l3d, "mpjpe": mpjpe, "l3d_hat": l3d_hat, "mpjpe_hat": mpjpe_hat, "l_lat": l_lat}
+        if geo is not None:
+            loss = self.last_losses["loss"] = g16[0][0] + self.lambda_future * g16[1][0] + self.lambda_latent * l_lat
+            self.last_losses.update(geo_halves(g16))
         return loss, mpjpe, found
 
-    def joint_losses(self, feats: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def joint_losses(self, feats: torch.Tensor, gt: torch.Tensor, joints2d: Optional[torch.Tensor] = None,
+                     K: Optional[torch.Tensor] = None, geo: Optional[GeoWeights] = None):
         """Eval-mode forward of one batch: ([l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat] fp32 device tensor, joints_phi (B,T,J,3) fp32).
         The launches of ``__call__(feats, predict_future=True)`` (the regressor on phi and on phi_hat separately, as evaluation has
         always run it), the pose terms by ``r50_op_joint_pose_loss_grad`` and l_lat by ``r50_op_ar_latent_grad`` (their gradients go
-        to scratch).  The second half's sums are ``r50_op_future_pose_loss_grad``'s, so l3d_hat / mpjpe_hat are phase 2's numbers."""
+        to scratch).  The second half's sums are ``r50_op_future_pose_loss_grad``'s, so l3d_hat / mpjpe_hat are phase 2's numbers.
+        ``geo``: the pose terms by two ``r50_op_geo_pose_loss_grad`` calls with ``dy = NULL`` instead, and a third value is returned:
+        their out8 as a (2, 8) fp32 device tensor."""
         b, t = self._check_batch(feats, gt)
+        if geo is not None:
+            gt2d, kmat = self._check_geo(b, t, joints2d, K)
         rows, d, o = b * t, self.latent_dim, self.out_dim
         lib = _lib.load_library()
         with torch.cuda.device(self._device):
@@ -425,19 +467,37 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             y = torch.cat([joints_phi.reshape(rows, o), joints_hat.reshape(rows, o)])
             gtc = gt.to(torch.float32).contiguous()
             losses = torch.empty(5, dtype=torch.float32, device=self._device)
-            self._joint_pose_loss(y, gtc, b, t, 1.0, 1.0, torch.empty((2 * rows, o), dtype=torch.float32, device=self._device), losses)
+            out16 = None
+            if geo is None:
+                self._joint_pose_loss(y, gtc, b, t, 1.0, 1.0, torch.empty((2 * rows, o), dtype=torch.float32, device=self._device), losses)
+            else:
+                out16 = self._geo_pose_loss(y, gtc, gt2d, kmat, b, t, geo, 1.0, 1.0, None, losses)
             self._latent_loss(ar, phi, torch.zeros((rows, d), dtype=torch.float32, device=self._device), b, t, 1.0, 1.0,
                               torch.empty((rows, d), dtype=self._dtype, device=self._device), losses[4:])
-        return losses, joints_phi
+        return (losses, joints_phi) if geo is None else (losses, joints_phi, out16)
+
+
+def geo_halves(g16) -> Dict[str, float]:
+    """The geometric numbers of the two halves of a joint step by name: l2d, reproj_px, l_vel, l_bone, n_clamped of joints_phi, and the
+    same under ``*_hat`` of joints_hat[:, 1:]."""
+    out = {k: g16[0][GEO_KEYS.index(k)] for k in GEO_EXTRA_KEYS}
+    out.update({k + "_hat": g16[1][GEO_KEYS.index(k)] for k in GEO_EXTRA_KEYS})
+    return out
+
+
+GEO_JOINT_KEYS = GEO_EXTRA_KEYS + tuple(k + "_hat" for k in GEO_EXTRA_KEYS)
 
 
 @torch.no_grad()
-def evaluate_joint(head: JointTrainableHead, store, batch_size: int) -> Tuple[float, float, float, float, float, float]:
+def evaluate_joint(head: JointTrainableHead, store, batch_size: int,
+                   geo: Optional[GeoWeights] = None) -> Tuple[float, float, float, float, float, float]:
     """The joint validation pass: (loss, l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat), each the mean over batches of the per-batch mean,
     the items of ``store`` in order, ``batch_size`` at a time, the last batch kept even if short (as ``train.evaluate``).  l3d and
     mpjpe over all frames by ``r50_op_pose_metrics`` (the numbers ``train.evaluate`` reports); l3d_hat, mpjpe_hat and l_lat over
     frames s >= 1 (the numbers ``train_ar.evaluate_future`` reports); loss = l3d + lambda_future * l3d_hat + lambda_latent * l_lat
-    of the means.  The sums stay on the device and are read once per pass.  The head's mode is restored; its weights are not touched."""
+    of the means.  The sums stay on the device and are read once per pass.  The head's mode is restored; its weights are not touched.
+    ``geo``: the loss is the composite of section N (each half's geometric terms at the weights of ``geo``), and
+    ``head.last_eval_geo`` holds the means of ``GEO_JOINT_KEYS`` (``n_clamped*``: totals)."""
     was_training = head.training
     head.train(False)
     lib = _lib.load_library()
@@ -445,36 +505,52 @@ def evaluate_joint(head: JointTrainableHead, store, batch_size: int) -> Tuple[fl
     try:
         with torch.cuda.device(dev):
             acc = torch.zeros(6, dtype=torch.float64, device=dev)        # [sum l3d_hat, sum mpjpe_hat, sum l_lat | l3d, mpjpe, batches]
+            acc16 = torch.zeros((2, 8), dtype=torch.float64, device=dev)
             for s in range(0, len(store), batch_size):
                 batch = store.get_batch(list(range(s, min(s + batch_size, len(store)))))
                 gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-                losses, joints_phi = head.joint_losses(batch[0], gt)
+                if geo is None:
+                    losses, joints_phi = head.joint_losses(batch[0], gt)
+                else:
+                    losses, joints_phi, out16 = head.joint_losses(batch[0], gt, batch[2], batch[3], geo)
+                    acc16 += out16.double()
                 acc[:3] += losses[2:].double()
                 _lib.check(lib.r50_op_pose_metrics(joints_phi.data_ptr(), gt.data_ptr(), gt.shape[0] * gt.shape[1], head.joints_num,
                                                    acc[3:].data_ptr(), head._stream()), None, "r50_op_pose_metrics")
             l3d_hat, mpjpe_hat, l_lat, l3d, mpjpe, n = acc.tolist()
+            g16 = acc16.tolist()
     finally:
         head.train(was_training)
     n = max(n, 1.0)
     l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat = l3d / n, mpjpe / n, l3d_hat / n, mpjpe_hat / n, l_lat / n
-    return l3d + head.lambda_future * l3d_hat + head.lambda_latent * l_lat, l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat
+    if geo is None:
+        return l3d + head.lambda_future * l3d_hat + head.lambda_latent * l_lat, l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat
+    means = geo_halves([[v / n for v in half] for half in g16])
+    means["n_clamped"], means["n_clamped_hat"] = g16[0][7], g16[1][7]
+    head.last_eval_geo = means
+    return g16[0][0] / n + head.lambda_future * g16[1][0] / n + head.lambda_latent * l_lat, l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat
 
 
 LOSS_KEYS = ("loss", "l3d", "mpjpe", "l3d_hat", "mpjpe_hat", "l_lat")
 
 
 def train_joint_epoch(head: JointTrainableHead, store, sampler, optim: AdamW, scaler: Optional[GradScaler], seed: int, epoch: int,
-                      log_every: int = 500) -> Tuple[Dict[str, float], int, int]:
+                      log_every: int = 500, geo: Optional[GeoWeights] = None) -> Tuple[Dict[str, float], int, int]:
     """``train.train_epoch`` for the joint step: one ``train_step`` per batch of ``sampler`` (its epoch already set), masks from
     ``make_dropout_masks`` with ``dropout_generator(seed, epoch, it)``.  Returns (the means of ``LOSS_KEYS`` over the batches,
-    applied steps, skipped steps)."""
+    applied steps, skipped steps); with ``geo`` the steps run section N's composite loss and the means include ``GEO_JOINT_KEYS``
+    (``n_clamped*``: totals)."""
     head.train()
-    sums = {k: 0.0 for k in LOSS_KEYS}
+    sums = {k: 0.0 for k in LOSS_KEYS + (GEO_JOINT_KEYS if geo is not None else ())}
     n_batches = skipped = 0
     for it, idx in enumerate(sampler):
-        feats, joints3d = store.get_batch(idx)[:2]
+        batch = store.get_batch(idx)
+        feats, joints3d = batch[:2]
         masks = head.make_dropout_masks(feats.shape[0], feats.shape[1], generator=dropout_generator(seed, epoch, it, head._device))
-        _, _, found = head.train_step(feats, joints3d, optim, scaler, masks=masks)
+        if geo is None:
+            _, _, found = head.train_step(feats, joints3d, optim, scaler, masks=masks)
+        else:
+            _, _, found = head.train_step(feats, joints3d, optim, scaler, masks=masks, joints2d=batch[2], K=batch[3], geo=geo)
         for k in sums:
             sums[k] += head.last_losses[k]
         n_batches += 1
@@ -482,7 +558,7 @@ def train_joint_epoch(head: JointTrainableHead, store, sampler, optim: AdamW, sc
         if log_every > 0 and (it + 1) % log_every == 0:
             print(f"[joint] iter {it + 1:05d}/{len(sampler):05d} | loss {sums['loss'] / n_batches:.6f} | "
                   f"mpjpe {sums['mpjpe'] / n_batches:.3f} | future mpjpe {sums['mpjpe_hat'] / n_batches:.3f}")
-    return {k: v / max(n_batches, 1) for k, v in sums.items()}, n_batches - skipped, skipped
+    return {k: v if k.startswith("n_clamped") else v / max(n_batches, 1) for k, v in sums.items()}, n_batches - skipped, skipped
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------
@@ -502,9 +578,8 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
-    p = build_parser()
-    args = p.parse_args(argv)
+def validate_args(p: argparse.ArgumentParser, args: argparse.Namespace) -> argparse.Namespace:
+    """The joint driver's rules on parsed arguments (``p.error`` on a breach); shared with ``train_geo --stage joint``."""
     if not args.init and not (args.resume and os.path.isfile(args.resume)):
         p.error("--init is required unless --resume names an existing checkpoint")
     if not (args.lambda_future >= 0 and args.lambda_latent >= 0):          # also refuses nan
@@ -512,16 +587,27 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return args
 
 
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    p = build_parser()
+    return validate_args(p, p.parse_args(argv))
+
+
 def main(argv: Optional[List[str]] = None) -> float:
     """Joint training on one MI355X.  Per epoch, in ``train.main``'s order: train, evaluate, scheduler step, ``last.pt``, ``best.pt``
     when val mpjpe + mpjpe_hat improved by more than ``--early-stop-min-delta``, patience counter.  ``--resume`` loads model and
     optimizer; the head's dimensions come from the checkpoint.  Prints one JSON line per epoch.  Returns the best val
     mpjpe + mpjpe_hat."""
+    return run(parse_args(argv))
+
+
+def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
+    """``main``'s body on parsed arguments.  ``geo_for_epoch``: None, or a function epoch -> ``GeoWeights`` (``train_geo``): the epoch
+    then trains and validates under section N's composite loss with those weights, and its JSON line gains the geometric numbers of
+    both halves and ``lambda_2d_active``."""
     from .feature_store import DeviceFeatureStore
     from .results import infer_head_dims, load_head_state
     from .samplers import MixedShardBatchSampler
 
-    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -561,8 +647,11 @@ def main(argv: Optional[List[str]] = None) -> float:
         print(f"\nEpoch {epoch + 1}/{args.epochs}")
         t0 = time.time()
         epoch_lr = optim.lr
-        tr, steps, skipped = train_joint_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every)
-        va = dict(zip(LOSS_KEYS, evaluate_joint(head, val_set, args.batch_size)))
+        geo = geo_for_epoch(epoch) if geo_for_epoch is not None else None
+        tr, steps, skipped = train_joint_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every, geo=geo)
+        va = dict(zip(LOSS_KEYS, evaluate_joint(head, val_set, args.batch_size, geo=geo)))
+        if geo is not None:
+            va.update(head.last_eval_geo)
         schedule.step()
         optim.lr = schedule.lr
         va_score = va["mpjpe"] + va["mpjpe_hat"]
@@ -576,6 +665,8 @@ def main(argv: Optional[List[str]] = None) -> float:
         line.update({"steps": steps, "skipped": skipped})
         line.update({f"val_{k}": v for k, v in va.items()})
         line["val_mpjpe_sum"] = va_score
+        if geo is not None:
+            line["lambda_2d_active"] = geo.lambda_2d
         print(json.dumps(line))
 
         save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)

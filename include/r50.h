@@ -412,6 +412,33 @@ int r50_op_rollout_pose_loss_grad(const float* pred, const float* gt, int b, int
 int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, int t_phi, int i0, int d, float lambda, float loss_scale,
                                float* dfut, float* loss_lat, float* row_part, int et, void* stream);
 
+/* Lifting head, geometric losses (3D + 2D reprojection + velocity + bone length).
+ *  r50_op_geo_pose_loss_grad: y, dy (b*t, joints, 3) fp32 batch-major, gt3d (b,t,joints,3), gt2d (b,t,joints,2), K (b,3,3), all fp32 on
+ *    the device; edges_host: 2*n_edges ints ON THE HOST (they travel as kernel arguments: no allocation, no host read of device
+ *    memory, no synchronisation inside, so the op can be captured in a HIP graph).
+ *      uv     = (K p)[:2] / clamp((K p)[2], min = eps)     (src/train.py:84-110; the numerator is not clamped; below the clamp the
+ *                                                            denominator carries no gradient, at equality it does)
+ *      l3d    = mean (p - g3d)^2                            over b*(t-s0)*joints*3
+ *      l2d    = mean (uv - g2d)^2                           over b*(t-s0)*joints*2, pixels^2
+ *      l_vel  = mean ((p[s+1]-p[s]) - (g[s+1]-g[s]))^2      over the pairs (s, s+1), s >= s0: b*(t-s0-1)*joints*3
+ *      l_bone = mean (|p[e1]-p[e0]| - |g[e1]-g[e0]|)^2      over b*(t-s0)*n_edges (src/train.py:50-57; a predicted bone of length
+ *                                                            exactly 0 gets gradient 0 from that bone)
+ *      loss   = l3d + lambda_2d l2d + lambda_vel l_vel + lambda_bone l_bone
+ *    Frames s < s0 (s0 = 0 or 1) of every clip are left out of every term and every mean; their dy rows are exact +0.
+ *    dy = (loss_scale * term_scale) * d loss / d y, all four terms in one pass.  dy == NULL: losses only (the evaluation form; the same
+ *    out8).  A term whose lambda is exactly 0 adds nothing to dy and is still reported.  With all three lambdas 0 dy is bit-equal to
+ *    r50_op_mse_loss_grad's (s0 = 0) and r50_op_future_pose_loss_grad's (s0 = 1) at term_scale = 1.
+ *    out8 = [loss, l3d, mpjpe, l2d, reproj_px, l_vel, l_bone, n_clamped]: reproj_px = mean |uv - g2d|_2 over the included joints,
+ *    n_clamped = how many of them have (K p)[2] < eps; loss is the sum above without term_scale.  An empty mean (t - s0 == 1 for
+ *    l_vel, n_edges == 0 for l_bone) is reported as 0.  part: 8*b doubles of device scratch.
+ *    One workgroup per clip, gather form, no atomics; per-joint arithmetic fp32, fp64 sums in a fixed order: the same bits on every run.  Refused with a message
+ *    before any launch unless b >= 1, 0 <= s0 <= 1, t - s0 >= 1 (>= 2 when lambda_vel != 0), 1 <= joints <= 64, 0 <= n_edges <= 64,
+ *    every edge index in [0, joints), the lambdas finite and >= 0, eps > 0 and t * joints <= 4608 (what one workgroup stages in LDS;
+ *    T 256 at J 17 fits). */
+int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt2d, const float* K, int b, int t, int s0, int joints,
+                              const int* edges_host, int n_edges, float lambda_2d, float lambda_vel, float lambda_bone, float eps,
+                              float term_scale, float loss_scale, float* dy, double* part, float* out8, void* stream);
+
 /* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
 int r50_op_avgpool(const void* x_nhwc_bf16, int n, int hw, int c, float* y_f32, void* stream);
 
