@@ -4379,10 +4379,12 @@ __host__ __device__ inline void jacobi4_rotate(double (&a)[4][4], double (&v)[4]
     }
 }
 
-// P1 and P2 of one pose: y (prediction) and x (ground truth) point at J x 3 fp32 values, 0 <= root < J.
-__host__ __device__ inline void pose_protocol_errors(const float* __restrict__ y, const float* __restrict__ x, int J, int root, double& p1,
-                                                     double& p2) {
-    double my[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0};
+// The proper similarity fit of one pose: y (prediction) and x (ground truth) point at J x 3 fp32 values.  my / mx = the centroids,
+// r = the rotation and a = the scale of the header comment, so that a r (y_j - my) + mx is the aligned prediction.
+__host__ __device__ inline void pose_similarity_fit(const float* __restrict__ y, const float* __restrict__ x, int J, double (&my)[3],
+                                                    double (&mx)[3], double& a, double (&r)[3][3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) my[c] = mx[c] = 0.0;
     for (int j = 0; j < J; ++j) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -4395,23 +4397,17 @@ __host__ __device__ inline void pose_protocol_errors(const float* __restrict__ y
         my[c] /= (double)J;
         mx[c] /= (double)J;
     }
-    const double yr[3] = {(double)y[3 * root], (double)y[3 * root + 1], (double)y[3 * root + 2]};
-    const double xr[3] = {(double)x[3 * root], (double)x[3 * root + 1], (double)x[3 * root + 2]};
     double s[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-    double sy = 0.0, sx = 0.0, e1 = 0.0;
+    double sy = 0.0, sx = 0.0;
     for (int j = 0; j < J; ++j) {
-        double y0[3], x0[3], d2 = 0.0;
+        double y0[3], x0[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const double yv = (double)y[3 * j + c], xv = (double)x[3 * j + c];
-            const double d = (yv - yr[c]) - (xv - xr[c]);
-            d2 += d * d;
-            y0[c] = yv - my[c];
-            x0[c] = xv - mx[c];
+            y0[c] = (double)y[3 * j + c] - my[c];
+            x0[c] = (double)x[3 * j + c] - mx[c];
             sy += y0[c] * y0[c];
             sx += x0[c] * x0[c];
         }
-        e1 += sqrt(d2);
 #pragma unroll
         for (int u = 0; u < 3; ++u)
 #pragma unroll
@@ -4451,20 +4447,43 @@ __host__ __device__ inline void pose_protocol_errors(const float* __restrict__ y
 #pragma unroll
     for (int u = 0; u < 4; ++u) q[u] /= qn;
     const double w = q[0], qx = q[1], qy = q[2], qz = q[3];
-    const double r[3][3] = {{w * w + qx * qx - qy * qy - qz * qz, 2.0 * (qx * qy - w * qz), 2.0 * (qx * qz + w * qy)},
-                            {2.0 * (qx * qy + w * qz), w * w - qx * qx + qy * qy - qz * qz, 2.0 * (qy * qz - w * qx)},
-                            {2.0 * (qx * qz - w * qy), 2.0 * (qy * qz + w * qx), w * w - qx * qx - qy * qy + qz * qz}};
-    const double a = (sy > 0.0 && sx > 0.0) ? lam / sy : 0.0;
-    double e2 = 0.0;
-    for (int j = 0; j < J; ++j) {
-        const double y0[3] = {(double)y[3 * j] - my[0], (double)y[3 * j + 1] - my[1], (double)y[3 * j + 2] - my[2]};
-        double d2 = 0.0;
+    r[0][0] = w * w + qx * qx - qy * qy - qz * qz; r[0][1] = 2.0 * (qx * qy - w * qz); r[0][2] = 2.0 * (qx * qz + w * qy);
+    r[1][0] = 2.0 * (qx * qy + w * qz); r[1][1] = w * w - qx * qx + qy * qy - qz * qz; r[1][2] = 2.0 * (qy * qz - w * qx);
+    r[2][0] = 2.0 * (qx * qz - w * qy); r[2][1] = 2.0 * (qy * qz + w * qx); r[2][2] = w * w - qx * qx - qy * qy + qz * qz;
+    a = (sy > 0.0 && sx > 0.0) ? lam / sy : 0.0;
+}
+
+// The two per-joint distances of one pose after its fit: d1 = |(y_j - yr) - (x_j - xr)| (P1's term, yr / xr the root joints) and
+// d2 = |a r (y_j - my) + mx - x_j| (P2's term).  yj / xj point at joint j's 3 fp32 values.
+__host__ __device__ inline void pose_joint_distances(const float* __restrict__ yj, const float* __restrict__ xj, const double (&yr)[3],
+                                                     const double (&xr)[3], const double (&my)[3], const double (&mx)[3], double a,
+                                                     const double (&r)[3][3], double& d1, double& d2) {
+    const double y0[3] = {(double)yj[0] - my[0], (double)yj[1] - my[1], (double)yj[2] - my[2]};
+    double s1 = 0.0, s2 = 0.0;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double h = a * (r[c][0] * y0[0] + r[c][1] * y0[1] + r[c][2] * y0[2]) + mx[c] - (double)x[3 * j + c];
-            d2 += h * h;
-        }
-        e2 += sqrt(d2);
+    for (int c = 0; c < 3; ++c) {
+        const double d = ((double)yj[c] - yr[c]) - ((double)xj[c] - xr[c]);
+        s1 += d * d;
+        const double h = a * (r[c][0] * y0[0] + r[c][1] * y0[1] + r[c][2] * y0[2]) + mx[c] - (double)xj[c];
+        s2 += h * h;
+    }
+    d1 = sqrt(s1);
+    d2 = sqrt(s2);
+}
+
+// P1 and P2 of one pose: y (prediction) and x (ground truth) point at J x 3 fp32 values, 0 <= root < J.
+__host__ __device__ inline void pose_protocol_errors(const float* __restrict__ y, const float* __restrict__ x, int J, int root, double& p1,
+                                                     double& p2) {
+    double my[3], mx[3], a, r[3][3];
+    pose_similarity_fit(y, x, J, my, mx, a, r);
+    const double yr[3] = {(double)y[3 * root], (double)y[3 * root + 1], (double)y[3 * root + 2]};
+    const double xr[3] = {(double)x[3 * root], (double)x[3 * root + 1], (double)x[3 * root + 2]};
+    double e1 = 0.0, e2 = 0.0;
+    for (int j = 0; j < J; ++j) {
+        double d1, d2;
+        pose_joint_distances(y + 3 * j, x + 3 * j, yr, xr, my, mx, a, r, d1, d2);
+        e1 += d1;
+        e2 += d2;
     }
     p1 = e1 / (double)J;
     p2 = e2 / (double)J;
@@ -4504,6 +4523,172 @@ __global__ __launch_bounds__(256) void pose_protocols_kernel(const float* __rest
         acc[slot] += red[0][0];
         acc[slot + 1] += red[1][0];
         if (k == 0) acc[2 * (size_t)G * P + g] += red[2][0];
+    }
+}
+
+// ---- Detail metrics ------------------------------------------------------------------------------------------
+// Per joint, per threshold and per motion order, from the same fit.  The thresholds are tau_i = thr_max * i / (n_thr - 1) in fp64,
+// i = 0 .. n_thr-1; a distance d hits tau_i when d < tau_i.
+#define POSE_DETAIL_MAX_THR 1024
+
+// The number of i in [0, n_thr) with d < tau[i], for tau non-decreasing in i (rounding is monotone, so thr_max * i and its quotient by
+// n_thr - 1 are non-decreasing in i) and tau[0] = 0 <= d.  It is n_thr - c with c the smallest index whose tau exceeds d; c is guessed
+// from d / thr_max and then moved by COMPARISONS against the table until tau[c-1] <= d < tau[c], so the count is exactly what the n_thr
+// comparisons give whatever the guess was.  Both loops are bounded by n_thr.  A NaN distance hits nothing.  per_tau = (n_thr - 1) /
+// thr_max, any rounding of it: it only steers the guess.
+__host__ __device__ inline int pose_threshold_hits(double d, const double* tau, int n_thr, double per_tau) {
+    if (!(d < tau[n_thr - 1])) return 0;
+    const double guess = d * per_tau;                                       // 0 <= d < tau[n_thr-1]: about [0, n_thr)
+    int c = guess < (double)(n_thr - 1) ? (int)guess : n_thr - 1;           // (a NaN from 0 * inf takes the second branch)
+    c = c < 1 ? 1 : c;                                                      // tau[0] = 0 is never hit
+    while (c < n_thr - 1 && !(d < tau[c])) ++c;
+    while (c > 1 && d < tau[c - 1]) --c;
+    return n_thr - c;
+}
+
+// |(cur_y - prev_y) - (cur_x - prev_x)| of root-relative joints (3 values each): the velocity error of one joint, metres per frame.
+__host__ __device__ inline double pose_velocity_error(const double (&ry)[3], const double (&rx)[3], const double (&py)[3],
+                                                      const double (&px)[3]) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double d = (ry[c] - py[c]) - (rx[c] - px[c]);
+        s += d * d;
+    }
+    return sqrt(s);
+}
+
+// |(prev_y - 2 cur_y + next_y) - (prev_x - 2 cur_x + next_x)| of root-relative joints: the acceleration error, metres per frame^2.
+__host__ __device__ inline double pose_acceleration_error(const double (&ry)[3], const double (&rx)[3], const double (&py)[3],
+                                                          const double (&px)[3], const double (&ny)[3], const double (&nx)[3]) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double d = ((py[c] - 2.0 * ry[c]) + ny[c]) - ((px[c] - 2.0 * rx[c]) + nx[c]);
+        s += d * d;
+    }
+    return sqrt(s);
+}
+
+// The sum of v over the 64 lanes of a wave in a fixed tree, valid in lane 0.
+__device__ inline double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// The grouped detail sums of one batch, pose_protocols_kernel's indexing: pred (B, P, J, 3) scores frames i0 .. i0+P-1 of gt
+// (B, Tgt, J, 3), group (B) in [0, G).  Workgroup (k, g) = blockIdx.x (k fastest) ADDS, over the clips of group g at frame k,
+//   acc[((g*P + k)*J + j)*2 + {0, 1}]     += the sums of d1, d2 of joint j                                     (section A)
+//   acc[A + (g*P + k)*6 + {0, 1, 2, 3}]   += the hits of d1 over all thresholds, of d1 at thr_max, the same two for d2
+//   acc[A + (g*P + k)*6 + {4, 5}]         += the sums over joints of the velocity error (k >= 1) and the acceleration error
+//                                            (1 <= k <= P-2); nothing where they are undefined               (section B)
+//   acc[A + 6*G*P + g]                    += the clip count, by workgroup (0, g)                               (section C)
+// with A = 2*G*P*J.  Motion differences are taken inside pred (frames k-1, k, k+1 of the P predicted ones) and at the same frames
+// of gt.  In passes of 256 clips, thread t fits clip b = pass*256 + t if it is in group g and keeps the fit in registers; then all
+// threads walk the joints together: each joint's d1 / d2 are summed over the wave by shuffles (a fixed tree) and over the four waves
+// and the passes in LDS in a fixed order, the six scalars of section B stay per thread until one tree at the end.  Every workgroup
+// owns its slots and adds to each once: no atomics, the same bits on every run.  J <= 64, 2 <= n_thr <= POSE_DETAIL_MAX_THR.
+__global__ __launch_bounds__(256) void pose_detail_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                  const int* __restrict__ group, int B, int P, int Tgt, int i0, int J,
+                                                                  int root, int G, int n_thr, double thr_max,
+                                                                  double* __restrict__ acc) {
+    __shared__ double tau[POSE_DETAIL_MAX_THR];
+    __shared__ double wave_part[4][64][2];
+    __shared__ double joint_sum[64][2];
+    __shared__ double red[7][4];
+    const int k = blockIdx.x % P, g = blockIdx.x / P;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const bool has_prev = k >= 1, has_next = k >= 1 && k <= P - 2;
+    for (int i = tid; i < n_thr; i += 256) tau[i] = thr_max * (double)i / (double)(n_thr - 1);
+    if (tid < 2 * J) joint_sum[tid >> 1][tid & 1] = 0.0;
+    __syncthreads();
+    const double per_tau = (double)(n_thr - 1) / thr_max;
+    double hits1 = 0.0, pck1 = 0.0, hits2 = 0.0, pck2 = 0.0, sv = 0.0, sa = 0.0, cnt = 0.0;
+    for (int base = 0; base < B; base += 256) {
+        const int b = base + tid;
+        const bool active = b < B && group[b] == g;
+        const float* y = pred + ((size_t)(active ? b : 0) * P + k) * J * 3;
+        const float* x = gt + ((size_t)(active ? b : 0) * Tgt + i0 + k) * J * 3;
+        const size_t fs = (size_t)J * 3;                                         // one frame
+        double my[3], mx[3], a = 0.0, r[3][3];
+        double yr[3] = {0.0, 0.0, 0.0}, xr[3] = {0.0, 0.0, 0.0}, pyr[3] = {0.0, 0.0, 0.0}, pxr[3] = {0.0, 0.0, 0.0},
+               nyr[3] = {0.0, 0.0, 0.0}, nxr[3] = {0.0, 0.0, 0.0};
+        if (active) {
+            pose_similarity_fit(y, x, J, my, mx, a, r);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                yr[c] = (double)y[3 * root + c];
+                xr[c] = (double)x[3 * root + c];
+                if (has_prev) {
+                    pyr[c] = (double)(y - fs)[3 * root + c];
+                    pxr[c] = (double)(x - fs)[3 * root + c];
+                }
+                if (has_next) {
+                    nyr[c] = (double)(y + fs)[3 * root + c];
+                    nxr[c] = (double)(x + fs)[3 * root + c];
+                }
+            }
+            cnt += 1.0;
+        }
+        for (int j = 0; j < J; ++j) {
+            double d1 = 0.0, d2 = 0.0;
+            if (active) {
+                const float* yj = y + 3 * j;
+                const float* xj = x + 3 * j;
+                pose_joint_distances(yj, xj, yr, xr, my, mx, a, r, d1, d2);
+                hits1 += (double)pose_threshold_hits(d1, tau, n_thr, per_tau);
+                pck1 += d1 < thr_max ? 1.0 : 0.0;
+                hits2 += (double)pose_threshold_hits(d2, tau, n_thr, per_tau);
+                pck2 += d2 < thr_max ? 1.0 : 0.0;
+                if (has_prev) {
+                    double ry[3], rx[3], py[3], px[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        ry[c] = (double)yj[c] - yr[c];
+                        rx[c] = (double)xj[c] - xr[c];
+                        py[c] = (double)(yj - fs)[c] - pyr[c];
+                        px[c] = (double)(xj - fs)[c] - pxr[c];
+                    }
+                    sv += pose_velocity_error(ry, rx, py, px);
+                    if (has_next) {
+                        double ny[3], nx[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            ny[c] = (double)(yj + fs)[c] - nyr[c];
+                            nx[c] = (double)(xj + fs)[c] - nxr[c];
+                        }
+                        sa += pose_acceleration_error(ry, rx, py, px, ny, nx);
+                    }
+                }
+            }
+            d1 = wave_sum_f64(d1);
+            d2 = wave_sum_f64(d2);
+            if (lane == 0) {
+                wave_part[wave][j][0] = d1;
+                wave_part[wave][j][1] = d2;
+            }
+        }
+        __syncthreads();
+        if (tid < 2 * J) {
+            const int j = tid >> 1, m = tid & 1;
+            joint_sum[j][m] += ((wave_part[0][j][m] + wave_part[1][j][m]) + wave_part[2][j][m]) + wave_part[3][j][m];
+        }
+        __syncthreads();
+    }
+    const double mine[7] = {hits1, pck1, hits2, pck2, sv, sa, cnt};
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        const double v = wave_sum_f64(mine[q]);
+        if (lane == 0) red[q][wave] = v;
+    }
+    __syncthreads();
+    const size_t a_end = 2 * (size_t)G * P * J, gk = (size_t)g * P + k;
+    if (tid < 2 * J) acc[gk * J * 2 + tid] += joint_sum[tid >> 1][tid & 1];
+    if (tid < 7) {
+        const double v = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+        if (tid < 6) acc[a_end + gk * 6 + tid] += v;
+        else if (k == 0) acc[a_end + 6 * (size_t)G * P + g] += v;
     }
 }
 

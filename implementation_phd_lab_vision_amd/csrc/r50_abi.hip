@@ -2433,6 +2433,20 @@ int r50_op_pose_protocols(const float* pred, const float* gt, const int* group, 
     return ew_done("r50_op_pose_protocols");
 }
 
+int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
+                               int n_groups, int n_thr, double thr_max, double* acc, void* stream) {
+    if (!pred || !gt || !group || !acc) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_detail_metrics: null pointer");
+    if (b < 1 || p < 1 || n_groups < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || i0 < 0 || (int64_t)i0 + p > t_gt ||
+        (int64_t)p * n_groups > INT32_MAX || (int64_t)b * t_gt > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_detail_metrics: invalid arguments (need b, p, n_groups >= 1, 1 <= joints <= 64, "
+                                              "0 <= root < joints and 0 <= i0, i0 + p <= t_gt)");
+    if (n_thr < 2 || n_thr > POSE_DETAIL_MAX_THR || !std::isfinite(thr_max) || !(thr_max > 0.0))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_detail_metrics: invalid arguments (need 2 <= n_thr <= 1024 and a finite thr_max > 0)");
+    hipLaunchKernelGGL(pose_detail_metrics_kernel, dim3((unsigned)(p * n_groups)), dim3(256), 0, (hipStream_t)stream, pred, gt, group, b, p,
+                       t_gt, i0, joints, root, n_groups, n_thr, thr_max, acc);
+    return ew_done("r50_op_pose_detail_metrics");
+}
+
 int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,
                                  void* stream) {
     if (!y_hat || !gt || !dy || !loss2 || b < 1 || t < 2 || joints < 1 || (int64_t)b * t > INT64_MAX / 3 / joints)

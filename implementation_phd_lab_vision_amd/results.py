@@ -9,7 +9,11 @@ prints MPJPE per horizon, and the ``.npz`` gains ``predicted_future3djoints`` (t
 ``--input-len`` observed frames), ``future_mpjpe`` (P,) and ``rollout_lens`` [I, P].  With ``--protocols`` (default off) it also scores
 the H3.6M protocols per action: ``protocols.evaluate_protocols`` over every test clip once, in store order
 (not the loader's ``drop_last`` batches), prints root-relative MPJPE (P1) and PA-MPJPE (P2) for all clips, the action mean and each
-action (and per horizon with ``--pred-len``), and the ``.npz`` gains the ``protocol_*`` keys.
+action (and per horizon with ``--pred-len``), and the ``.npz`` gains the ``protocol_*`` keys.  With ``--detail-metrics`` (default off)
+it also reports, over the same pass structure, P1 / P2 per joint, PCK at ``--pck-threshold-mm`` and AUC over
+``--auc-steps`` thresholds (both root-relative and after the similarity fit), and the velocity and acceleration errors in mm per frame
+and mm per frame^2, for all clips, the action mean and each action (and per horizon with ``--pred-len``); the ``.npz`` gains the
+``detail_*`` keys.
 
 Two differences from running the reference's script as it stands:
 
@@ -75,6 +79,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--geo-metrics", action="store_true",
                    help="also report the test-subject 2D reprojection loss and pixel error, velocity and bone-length losses and the number of "
                         "predicted joints at or behind the camera plane, over the same batches (INTEGRATION.md section N)")
+    p.add_argument("--detail-metrics", action="store_true",
+                   help="also report P1 / P2 per joint, PCK / AUC and the velocity / acceleration errors per action over every test clip, "
+                        "and per horizon with --pred-len (INTEGRATION.md section O)")
+    p.add_argument("--pck-threshold-mm", type=float, default=150.0, help="PCK threshold and the end of the AUC range, in mm (--detail-metrics)")
+    p.add_argument("--auc-steps", type=int, default=31, help="thresholds of the AUC, 0 .. --pck-threshold-mm evenly (--detail-metrics)")
     return p
 
 
@@ -90,6 +99,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--input-len must be >= 1, got {args.input_len}")
         if args.input_len + args.pred_len > args.seq_len:
             p.error(f"--input-len + --pred-len = {args.input_len + args.pred_len} exceeds --seq-len {args.seq_len}")
+    if args.detail_metrics:
+        if not 2 <= args.auc_steps <= 1024:
+            p.error(f"--auc-steps must lie in [2, 1024], got {args.auc_steps}")
+        if not (np.isfinite(args.pck_threshold_mm) and args.pck_threshold_mm > 0):
+            p.error(f"--pck-threshold-mm must be finite and > 0, got {args.pck_threshold_mm}")
     return args
 
 
@@ -239,6 +253,63 @@ def protocol_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     return out
 
 
+def _pair(v, scale: float) -> str:
+    """``raw / pa`` of a [root-relative, after the similarity fit] pair."""
+    return f"{v[0] * scale:.2f} / pa {v[1] * scale:.2f}"
+
+
+def detail_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--detail-metrics`` from an ``evaluate_detail`` result: the ``Detail metrics`` line (all clips and the
+    action mean: PCK and AUC in percent, raw and after the similarity fit; velocity and acceleration errors in mm per frame and mm per
+    frame^2), one ``Per-joint`` line (P1 / P2 in mm per joint name, all clips), one indented line per action, and with ``pred_len > 0``
+    the ``Rollout detail metrics`` line at horizons 1, 5, 10 and P (``-`` where a motion error is not defined)."""
+    clips = res["clips"]
+    at_mm = f"pck@{res['thr_max'] * 1000.0:g}"
+
+    def summary(which: str, key: str = "") -> str:
+        g = lambda m: res[f"{which}_{m}{key}"]                        # noqa: E731
+        return (f"{at_mm} (%) {_pair(g('pck'), 100.0)} | auc (%) {_pair(g('auc'), 100.0)} | vel (mm/frame) {g('vel') * 1000.0:.2f} "
+                f"| accel (mm/frame^2) {g('acc') * 1000.0:.2f}")
+
+    lines = [f"Detail metrics | clips {int(clips.sum())} | actions {len(res['group_names'])} | all: {summary('recon', '_all')} "
+             f"| action mean: {summary('recon', '_mean')}"]
+    pj = res["recon_per_joint_all"]
+    lines.append("Per-joint p1 / p2 (mm) | " + " | ".join(f"{name} {pj[j, 0] * 1000.0:.2f} / {pj[j, 1] * 1000.0:.2f}"
+                                                           for j, name in enumerate(res["joint_names"])))
+    for i, (name, c) in enumerate(zip(res["group_names"], clips)):
+        row = {m: res[f"recon_{m}"][i] for m in ("pck", "auc", "vel", "acc")}
+        lines.append(f"  {name} | clips {int(c)} | {at_mm} (%) {_pair(row['pck'], 100.0)} | auc (%) {_pair(row['auc'], 100.0)} "
+                     f"| vel (mm/frame) {row['vel'] * 1000.0:.2f} | accel (mm/frame^2) {row['acc'] * 1000.0:.2f}")
+    if pred_len > 0:
+        hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+        num = lambda v, scale: "-" if np.isnan(v) else f"{v * scale:.2f}"                  # noqa: E731
+        parts = []
+        for label, key in ((f"{at_mm} (%)", "pck"), ("auc (%)", "auc")):
+            fa = res[f"future_{key}_all"]
+            parts.append(f"{label} " + " | ".join(f"@{h}: {_pair(fa[h - 1], 100.0)}" for h in hs))
+        for label, key in (("vel (mm/frame)", "vel"), ("accel (mm/frame^2)", "acc")):
+            fa = res[f"future_{key}_all"]
+            parts.append(f"{label} " + " | ".join(f"@{h}: {num(fa[h - 1], 1000.0)}" for h in hs))
+        lines.append(f"Rollout detail metrics | input {input_len} | pred {pred_len} | clips {int(clips.sum())} | " + " | ".join(parts))
+    return lines
+
+
+def detail_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--detail-metrics``: ``detail_actions`` (G,) and ``detail_joint_names`` (J,) str, ``detail_clips`` (G,)
+    int64, and fp32 ``detail_recon_M`` (G, ...) / ``detail_recon_M_all`` (...) for M in per_joint (J, 2), p1p2 (2,), pck (2,), auc (2,),
+    vel (), acc () -- metres, metres per frame, metres per frame^2, shares in [0, 1]; [.., 2] = [root-relative, after the fit]; with a
+    rollout ``detail_future_M`` (G, P, ...) and ``detail_future_M_all`` (P, ...)."""
+    out = {"detail_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "detail_joint_names": np.array([str(n) for n in res["joint_names"]], dtype=str),
+           "detail_clips": np.asarray(res["clips"], dtype=np.int64)}
+    for which in ("recon", "future"):
+        for m in ("per_joint", "p1p2", "pck", "auc", "vel", "acc"):
+            for key in (f"{which}_{m}", f"{which}_{m}_all"):
+                if key in res:
+                    out["detail_" + key] = np.asarray(res[key], dtype=np.float32)
+    return out
+
+
 def main(argv: Optional[List[str]] = None) -> str:
     """``python src/results.py`` on one MI355X.  Returns the path of the written ``.npz``."""
     from .feature_store import DeviceFeatureStore
@@ -287,6 +358,16 @@ def main(argv: Optional[List[str]] = None) -> str:
         geo = evaluate_geo(head, test_set, args.batch_size, GeoWeights(), batches=eval_batches)
         print("Geo metrics | " + " | ".join(f"{key}: {geo[key]:.6f}" for key in GEO_EXTRA_KEYS))
 
+    detail = None
+    if args.detail_metrics:                  # the protocols' pass: every test clip once, in store order
+        from .detail_metrics import evaluate_detail
+        from .protocols import action_groups
+        names, ids = action_groups(test_set.item_actions())
+        detail = evaluate_detail(head, test_set, ids, names, args.input_len if args.pred_len > 0 else 0, args.pred_len,
+                                 n_thr=args.auc_steps, thr_max=args.pck_threshold_mm / 1000.0)
+        for line in detail_lines(detail, args.input_len, args.pred_len):
+            print(line)
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -309,6 +390,8 @@ def main(argv: Optional[List[str]] = None) -> str:
     if geo is not None:
         extra["geo_metrics"] = np.array([geo[key] for key in GEO_EXTRA_KEYS], dtype=np.float64)
         extra["geo_metric_names"] = np.array(GEO_EXTRA_KEYS)
+    if detail is not None:
+        extra.update(detail_npz(detail))
     np.savez_compressed(out_path, video=videos, joints3d=joints3d_np, predicted3djoints=pred,
                         joints2d=joints2d[:n_save].cpu().numpy(), K=k[:n_save].to(torch.float32).cpu().numpy(),
                         meta=np.array(list(metas[:n_save]), dtype=object),

@@ -363,6 +363,27 @@ int r50_op_horizon_metrics(const float* pred, const float* gt, int b, int p, int
 int r50_op_pose_protocols(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
                           int n_groups, double* acc, void* stream);
 
+/* Lifting head, detail metrics per group: per-joint errors, PCK / AUC hit counts and velocity /
+ * acceleration errors, with r50_op_pose_protocols' indexing (pred (b,p,joints,3) fp32 scores frames i0 .. i0+p-1 of gt
+ * (b,t_gt,joints,3) fp32; group (b) int32 device values in [0,n_groups)).  Read as fp32, computed in fp64.  Per clip, scored frame k
+ * and joint j, with ~ for root-relative (pred_j - pred_root): d1 = |~pred_j - ~gt_j| (P1's term); d2 = |a R (pred_j - mu_pred) +
+ * mu_gt - gt_j| with (a, R) the proper similarity fit of r50_op_pose_protocols (P2's term); ev = |(~pred[k] - ~pred[k-1]) -
+ * (~gt[k] - ~gt[k-1])| for k >= 1, in metres per frame; ea = |(~pred[k-1] - 2 ~pred[k] + ~pred[k+1]) - (the same of ~gt)| for
+ * 1 <= k <= p-2, in metres per frame^2: differences are taken inside pred, no frame rate is assumed.  Thresholds tau_i = thr_max * i /
+ * (n_thr - 1), i = 0 .. n_thr-1, in fp64 in that order; d hits tau when d < tau (strict: tau_0 = 0 is never hit, an exact 0 hits
+ * every positive threshold).  With G = n_groups, P = p, J = joints and A = 2*G*P*J it ADDS
+ *   acc[((g*P + k)*J + j)*2 + {0,1}]   += the sums over the clips of group g of d1, d2;
+ *   acc[A + (g*P + k)*6 + {0,1,2,3}]   += over clips and joints: the hits of d1 summed over all n_thr thresholds, the hits of d1 at
+ *                                         thr_max, then the same two of d2 (integer-valued);
+ *   acc[A + (g*P + k)*6 + {4,5}]       += the sums over clips and joints of ev, ea; nothing where they are undefined;
+ *   acc[A + 6*G*P + g]                 += the clips of group g;
+ * acc: 2*G*P*J + 6*G*P + G doubles of device memory.  Needs b, p, n_groups >= 1, 1 <= joints <= 64, 0 <= root < joints, 0 <= i0,
+ * i0 + p <= t_gt, 2 <= n_thr <= 1024, thr_max > 0 and finite, no null pointer; all checked before any launch (a refused call touches
+ * nothing).  One workgroup per (frame, group), one fit per thread, fp64 sums in a fixed order (no atomics: the same bits on every
+ * run). */
+int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
+                               int n_groups, int n_thr, double thr_max, double* acc, void* stream);
+
 /* Lifting head, phase 2 (training f_AR; DESIGN.md "f next #2").  The reference has no phase 2; this
  * project's definition: f_movie / f_3D frozen and run as at inference, loss = l3d_hat + lambda * l_lat over frames s >= 1.
  *  r50_op_future_pose_loss_grad: y_hat, gt, dy (b*t, joints, 3) fp32: dy = 2 (y_hat-gt) / n * loss_scale with n = b*(t-1)*joints*3,
