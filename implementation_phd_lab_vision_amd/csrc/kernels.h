@@ -6065,3 +6065,179 @@ __global__ __launch_bounds__(256) void avgpool_split_kernel(const __bf16* __rest
     *reinterpret_cast<f32x4*>(o) = (f32x4){s[0] * inv_hw, s[1] * inv_hw, s[2] * inv_hw, s[3] * inv_hw};
     *reinterpret_cast<f32x4*>(o + 4) = (f32x4){s[4] * inv_hw, s[5] * inv_hw, s[6] * inv_hw, s[7] * inv_hw};
 }
+
+// ================================================================================================
+// Skeleton drawing (r50_op_draw_skeletons_u8): anti-aliased bones and joints of up to 8 layers blended
+// over uint8 HWC frames.  Gather form: a workgroup of 256 owns one 32x32 pixel tile of one frame, a thread owns 4 consecutive
+// pixels of one row and every byte is written exactly once -- no atomics, the same bits on every run.
+//   staging: wave w takes the layers w, w+4: lane j the joint j, lanes e / e+64 the edges.  The points go to LDS as given (fp32), the
+//   per-edge constants (origin, direction, 1 / len^2) in fp64; a joint or edge with a non-finite coordinate, one of a layer with
+//   A = 0, or one whose box inflated by max(half_width, joint_radius) + 1 misses the tile's pixel centres is left out of the three
+//   64-bit hit masks the wave ballots per layer.  A left-out item is farther than (radius + 1) from every pixel of the tile, so its
+//   coverage there is an exact 0: the cull never changes a byte.
+//   pixels: the hit masks are wave-uniform, so a tile nothing touches costs one load and one store per pixel.  Squared distances in
+//   fp64 from the differences (p - a): at coordinates of a few hundred pixels an fp32 difference carries 3e-5 px, i.e. up to 0.04 grey
+//   levels per layer after the blend, enough to flip one rounding in ten along every bone; in fp64 the coverage is good to a few fp32
+//   ulp (tests/render_reference.py derives the margin) and the kernel stays bound by its 6 bytes per pixel.  One fp32 sqrt per pixel,
+//   layer and kind; the coverage, alpha and blend are fp32 (c = c * (1 - a) + rgb * a, no fused multiply-add), a == 0 is skipped.
+// VEC = 1 (w % 4 == 0, bg and out 4-byte aligned): 4 pixels = 12 bytes move as one 3-dword access; VEC = 0: byte by byte.
+constexpr int DRAW_MAX_EDGES = 128, DRAW_MAX_JOINTS = 64, DRAW_MAX_LAYERS = 8, DRAW_TILE = 32;
+struct DrawEdges { unsigned short ab[DRAW_MAX_EDGES]; };     // a | b << 8, by value in the kernel arguments (no device allocation)
+struct __attribute__((packed, aligned(4))) DrawPx4 { unsigned w0, w1, w2; };
+
+__host__ __device__ inline size_t draw_lds_bytes(int layers, int joints, int n_edges) {
+    return (size_t)layers * ((size_t)n_edges * 40 + 24 + (size_t)joints * 8 + 4);
+}
+
+__device__ __forceinline__ unsigned long long draw_uniform64(unsigned long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ bool draw_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN and +-inf
+
+template <int VEC>
+__global__ __launch_bounds__(256) void draw_skeletons_u8_kernel(const unsigned char* __restrict__ bg, unsigned bg_rgb,
+                                                                const float* __restrict__ pts, const unsigned char* __restrict__ style,
+                                                                DrawEdges ed, int E, int H, int W, int L, int J, int tiles_x, int tiles_y,
+                                                                float half_width, float joint_radius, unsigned char* __restrict__ out) {
+    extern __shared__ double draw_sm[];
+    double* sE = draw_sm;                                                              // [L][E][5]: ax, ay, dx, dy, 1 / len^2
+    unsigned long long* sM = reinterpret_cast<unsigned long long*>(sE + (size_t)L * E * 5);   // [L][3]: edges 0-63, 64-127, joints
+    float* sJ = reinterpret_cast<float*>(sM + (size_t)L * 3);                          // [L][J][2]
+    unsigned* sS = reinterpret_cast<unsigned*>(sJ + (size_t)L * J * 2);                // [L]: R | G << 8 | B << 16 | A << 24
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned bid = blockIdx.x;
+    const int tile_x = (int)(bid % (unsigned)tiles_x), tile_y = (int)((bid / (unsigned)tiles_x) % (unsigned)tiles_y);
+    const long long f = bid / ((unsigned)tiles_x * (unsigned)tiles_y);
+    const int X0 = tile_x * DRAW_TILE, Y0 = tile_y * DRAW_TILE;
+    const float infl = fmaxf(half_width, joint_radius) + 1.f;
+    const float bx0 = (float)X0 - infl, bx1 = (float)min(X0 + DRAW_TILE - 1, W - 1) + infl;      // an item hits when its box meets this one
+    const float by0 = (float)Y0 - infl, by1 = (float)min(Y0 + DRAW_TILE - 1, H - 1) + infl;
+
+    for (int l = wave; l < L; l += 4) {
+        const float* P = pts + ((f * L + l) * J) * 2;
+        const unsigned char* st = style + (f * L + l) * 4;
+        const unsigned rgba = (unsigned)st[0] | ((unsigned)st[1] << 8) | ((unsigned)st[2] << 16) | ((unsigned)st[3] << 24);
+        const bool on = st[3] != 0;
+        bool hit = false;
+        if (lane < J) {
+            const float x = P[2 * lane], y = P[2 * lane + 1];
+            sJ[(l * J + lane) * 2] = x;
+            sJ[(l * J + lane) * 2 + 1] = y;
+            hit = on && draw_finite(x) && draw_finite(y) && x >= bx0 && x <= bx1 && y >= by0 && y <= by1;
+        }
+        const unsigned long long mj = __ballot(hit);
+        unsigned long long me[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int e = lane + 64 * h;
+            hit = false;
+            if (e < E) {
+                const unsigned ab = ed.ab[e];
+                const int ia = (int)(ab & 255u), ib = (int)(ab >> 8);
+                const float ax = P[2 * ia], ay = P[2 * ia + 1], bx = P[2 * ib], by = P[2 * ib + 1];
+                const double dx = (double)bx - (double)ax, dy = (double)by - (double)ay, len2 = dx * dx + dy * dy;
+                double* q = sE + ((size_t)l * E + e) * 5;
+                q[0] = (double)ax; q[1] = (double)ay; q[2] = dx; q[3] = dy;
+                q[4] = len2 > 0.0 ? 1.0 / len2 : 0.0;                                   // coincident end points: t = 0, a point
+                hit = on && draw_finite(ax) && draw_finite(ay) && draw_finite(bx) && draw_finite(by) &&
+                      fmaxf(ax, bx) >= bx0 && fminf(ax, bx) <= bx1 && fmaxf(ay, by) >= by0 && fminf(ay, by) <= by1;
+            }
+            me[h] = __ballot(hit);
+        }
+        if (lane == 0) {
+            sM[l * 3] = me[0]; sM[l * 3 + 1] = me[1]; sM[l * 3 + 2] = mj;
+            sS[l] = rgba;
+        }
+    }
+    __syncthreads();
+
+    const int y = Y0 + (tid >> 3), x0 = X0 + (tid & 7) * 4;
+    if (y >= H || x0 >= W) return;
+    const int npx = VEC ? 4 : min(4, W - x0);
+    const size_t off = ((size_t)(f * H + y) * (size_t)W + (size_t)x0) * 3;
+    float c[12];
+    if (bg) {
+        if (VEC) {
+            const DrawPx4 v = *reinterpret_cast<const DrawPx4*>(bg + off);
+            const unsigned w[3] = {v.w0, v.w1, v.w2};
+#pragma unroll
+            for (int i = 0; i < 12; ++i) c[i] = (float)((w[i >> 2] >> (8 * (i & 3))) & 255u);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) c[i] = i < 3 * npx ? (float)bg[off + i] : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) c[i] = (float)((bg_rgb >> (8 * (2 - i % 3))) & 255u);           // 0xRRGGBB
+    }
+
+    const float re = half_width + 0.5f, rj = joint_radius + 0.5f;
+    const double py = (double)y;
+    for (int l = 0; l < L; ++l) {
+        const unsigned long long m0 = draw_uniform64(sM[l * 3]), m1 = draw_uniform64(sM[l * 3 + 1]), mj = draw_uniform64(sM[l * 3 + 2]);
+        if ((m0 | m1 | mj) == 0ull) continue;
+        double de2[4], dj2[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) de2[k] = dj2[k] = __builtin_inf();
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            unsigned long long m = h ? m1 : m0;
+            while (m) {
+                const int e = __builtin_ctzll(m) + 64 * h;
+                m &= m - 1;
+                const double* q = sE + ((size_t)l * E + e) * 5;
+                const double ax = q[0], ay = q[1], dx = q[2], dy = q[3], inv = q[4];
+                const double ry = py - ay;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double rx = (double)(x0 + k) - ax;
+                    const double t = fmin(fmax((rx * dx + ry * dy) * inv, 0.0), 1.0);
+                    const double qx = rx - t * dx, qy = ry - t * dy;
+                    de2[k] = fmin(de2[k], qx * qx + qy * qy);
+                }
+            }
+        }
+        for (unsigned long long m = mj; m;) {
+            const int j = __builtin_ctzll(m);
+            m &= m - 1;
+            const double jx = (double)sJ[(l * J + j) * 2], ry = py - (double)sJ[(l * J + j) * 2 + 1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double rx = (double)(x0 + k) - jx;
+                dj2[k] = fmin(dj2[k], rx * rx + ry * ry);
+            }
+        }
+        const unsigned rgba = sS[l];
+        const float r = (float)(rgba & 255u), g = (float)((rgba >> 8) & 255u), b = (float)((rgba >> 16) & 255u);
+        const float sa = (float)(rgba >> 24) / 255.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float ae = fminf(fmaxf(re - sqrtf((float)de2[k]), 0.f), 1.f);
+            const float aj = fminf(fmaxf(rj - sqrtf((float)dj2[k]), 0.f), 1.f);
+            const float a = fmaxf(ae, aj) * sa;
+            if (a > 0.f) {
+                const float na = 1.f - a;
+                c[3 * k] = c[3 * k] * na + r * a;
+                c[3 * k + 1] = c[3 * k + 1] * na + g * a;
+                c[3 * k + 2] = c[3 * k + 2] * na + b * a;
+            }
+        }
+    }
+
+    unsigned q[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) q[i] = (unsigned)fminf(fmaxf(floorf(c[i] + 0.5f), 0.f), 255.f);
+    if (VEC) {
+        DrawPx4 v;
+        v.w0 = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+        v.w1 = q[4] | (q[5] << 8) | (q[6] << 16) | (q[7] << 24);
+        v.w2 = q[8] | (q[9] << 8) | (q[10] << 16) | (q[11] << 24);
+        *reinterpret_cast<DrawPx4*>(out + off) = v;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+            if (i < 3 * npx) out[off + i] = (unsigned char)q[i];
+    }
+}

@@ -2258,6 +2258,50 @@ int r50_op_resize_frames_u8(const void* frames, int n, int h, int w, const int* 
     return R50_OK;
 }
 
+// ---- skeleton drawing (kernels.h: draw_skeletons_u8_kernel).  Everything is checked here, before the launch: a refused call touches nothing.
+int r50_op_draw_skeletons_u8(const void* bg, int bg_rgb, const float* pts, const void* style, const int* edges_host, int n_edges, int f,
+                             int h, int w, int layers, int joints, float half_width, float joint_radius, void* out, void* stream) {
+    const char* me = "r50_op_draw_skeletons_u8: ";
+    auto bad = [&](const std::string& why) { return fail(nullptr, R50_ERR_INVALID, std::string(me) + why); };
+    if (!pts || !style || !out) return bad("null pointer (pts, style and out are required; only bg may be NULL)");
+    if (f < 1 || h < 1 || w < 1) return bad("need f, h, w >= 1");
+    if (joints < 1 || joints > DRAW_MAX_JOINTS) return bad("need 1 <= joints <= 64");
+    if (layers < 1 || layers > DRAW_MAX_LAYERS) return bad("need 1 <= layers <= 8");
+    if (n_edges < 0 || n_edges > DRAW_MAX_EDGES) return bad("need 0 <= n_edges <= 128");
+    if (n_edges > 0 && !edges_host) return bad("null pointer (edges_host with n_edges > 0)");
+    if (!std::isfinite(half_width) || !std::isfinite(joint_radius) || half_width < 0.f || joint_radius < 0.f)
+        return bad("half_width and joint_radius must be finite and >= 0");
+    if (bg_rgb < 0 || bg_rgb > 0xFFFFFF) return bad("bg_rgb must be 0xRRGGBB");
+    const long long bytes = (long long)f * h * w * 3;
+    const long long tiles_x = (w + DRAW_TILE - 1) / DRAW_TILE, tiles_y = (h + DRAW_TILE - 1) / DRAW_TILE;
+    if (bytes >= (1ll << 40) || tiles_x * tiles_y * f > INT32_MAX) return bad("f * h * w is too large");
+    if (bg) {
+        const uintptr_t b0 = (uintptr_t)bg, o0 = (uintptr_t)out;
+        if (b0 < o0 + (uintptr_t)bytes && o0 < b0 + (uintptr_t)bytes) return bad("out may not alias bg");
+    }
+    DrawEdges ed;
+    for (int q = 0; q < DRAW_MAX_EDGES; ++q) ed.ab[q] = 0;
+    for (int q = 0; q < n_edges; ++q) {
+        const int ea = edges_host[2 * q], eb = edges_host[2 * q + 1];
+        if (ea < 0 || ea >= joints || eb < 0 || eb >= joints)
+            return bad("edge " + std::to_string(q) + " = (" + std::to_string(ea) + ", " + std::to_string(eb) + ") is outside [0, joints)");
+        ed.ab[q] = (unsigned short)(ea | (eb << 8));
+    }
+    const size_t lds = draw_lds_bytes(layers, joints, n_edges);                        // <= 45,280 B: under the default 64 KB ceiling
+    const bool vec = (w % 4 == 0) && (((uintptr_t)out | (uintptr_t)bg) & 3u) == 0;      // a NULL bg counts as aligned
+    const dim3 grid((unsigned)(tiles_x * tiles_y * f));
+    if (vec)
+        hipLaunchKernelGGL(draw_skeletons_u8_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, (const unsigned char*)bg, (unsigned)bg_rgb,
+                           pts, (const unsigned char*)style, ed, n_edges, h, w, layers, joints, (int)tiles_x, (int)tiles_y, half_width,
+                           joint_radius, (unsigned char*)out);
+    else
+        hipLaunchKernelGGL(draw_skeletons_u8_kernel<0>, grid, dim3(256), lds, (hipStream_t)stream, (const unsigned char*)bg, (unsigned)bg_rgb,
+                           pts, (const unsigned char*)style, ed, n_edges, h, w, layers, joints, (int)tiles_x, (int)tiles_y, half_width,
+                           joint_radius, (unsigned char*)out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(e));
+}
+
 // ---- lifting head pieces (kernels.h: cast_rows_kernel, concat_pad_kernel, gn_relu_causal3_kernel); et: 0 = bf16, 1 = fp16
 int r50_op_cast_rows(const float* src, int64_t rows, int c, void* dst, int cpad, int et, void* stream) {
     if (!src || !dst || rows < 1 || c < 1 || cpad < c || (cpad & 1) || (et != 0 && et != 1))

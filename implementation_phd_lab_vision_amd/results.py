@@ -13,7 +13,11 @@ action (and per horizon with ``--pred-len``), and the ``.npz`` gains the ``proto
 it also reports, over the same pass structure, P1 / P2 per joint, PCK at ``--pck-threshold-mm`` and AUC over
 ``--auc-steps`` thresholds (both root-relative and after the similarity fit), and the velocity and acceleration errors in mm per frame
 and mm per frame^2, for all clips, the action mean and each action (and per horizon with ``--pred-len``); the ``.npz`` gains the
-``detail_*`` keys.
+``detail_*`` keys.  With ``--render DIR`` (default off) the first ``--render-n`` dumped clips are also
+drawn on the device (``render.render_panels``: frame + GT 2D joints | frame + projected GT and prediction | 3D view) and written as
+``DIR/clip_<i>_S<subject>_<action>.png`` (an APNG at ``--render-fps``) and ``DIR/clip_<i>_sheet.png`` (every ``--render-sheet-every``-th
+frame); the frames are the clip's person crop -- ``meta["box"]`` through ``frames.crop_and_resize_video_uint8``, what ``joints2d`` and
+``K`` refer to -- and the ``.npz`` gains ``video_crop`` (n, T, 224, 224, 3).
 
 Two differences from running the reference's script as it stands:
 
@@ -84,6 +88,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "and per horizon with --pred-len (INTEGRATION.md section O)")
     p.add_argument("--pck-threshold-mm", type=float, default=150.0, help="PCK threshold and the end of the AUC range, in mm (--detail-metrics)")
     p.add_argument("--auc-steps", type=int, default=31, help="thresholds of the AUC, 0 .. --pck-threshold-mm evenly (--detail-metrics)")
+    p.add_argument("--render", type=str, default=None, metavar="DIR",
+                   help="also draw the first --render-n dumped clips on the device (pose overlays + 3D view) and write an APNG and a "
+                        "contact sheet per clip under DIR (INTEGRATION.md section P); default off")
+    p.add_argument("--render-n", type=int, default=4, help="clips to render (--render)")
+    p.add_argument("--render-fps", type=float, default=10.0, help="frame rate of the APNGs (--render)")
+    p.add_argument("--render-sheet-every", type=int, default=5, help="the contact sheet holds every this-many-th frame (--render)")
     return p
 
 
@@ -104,6 +114,13 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--auc-steps must lie in [2, 1024], got {args.auc_steps}")
         if not (np.isfinite(args.pck_threshold_mm) and args.pck_threshold_mm > 0):
             p.error(f"--pck-threshold-mm must be finite and > 0, got {args.pck_threshold_mm}")
+    if args.render is not None:
+        if args.render_n < 1:
+            p.error(f"--render-n must be >= 1, got {args.render_n}")
+        if not args.render_fps > 0:
+            p.error(f"--render-fps must be > 0, got {args.render_fps}")
+        if args.render_sheet_every < 1:
+            p.error(f"--render-sheet-every must be >= 1, got {args.render_sheet_every}")
     return args
 
 
@@ -189,10 +206,32 @@ def resolve_video_reader(spec: Optional[str]) -> Callable:
     return reader
 
 
+CROP_SIZE = 224                           # the person crop the shards' joints2d and K refer to (src/dataset.py:107-140)
+
+
+def crop_clip(frames_sel: torch.Tensor, box, b: int) -> Optional[torch.Tensor]:
+    """(T, 224, 224, 3) uint8 on the device: the clip's person crop, ``frames_sel`` (T,H,W,3) on the device through
+    ``frames.crop_and_resize_video_uint8`` with ``meta["box"]`` = [top, left, hh, ww].  None, with one printed notice, when the clip
+    has no usable box: ``None`` (features written with ``--augment``: each variant drew its own crop) or one that does not lie inside
+    the decoded frame."""
+    from .frames import crop_and_resize_video_uint8
+    if box is None:
+        print(f"render: clip {b} has no crop box (features written with --augment): plain background")
+        return None
+    top, left, hh, ww = (int(v) for v in (box.tolist() if isinstance(box, torch.Tensor) else box))
+    h, w = int(frames_sel.shape[1]), int(frames_sel.shape[2])
+    if top < 0 or left < 0 or hh < 1 or ww < 1 or top + hh > h or left + ww > w:
+        print(f"render: clip {b}: the crop box {[top, left, hh, ww]} does not lie inside its {h}x{w} frames: plain background")
+        return None
+    return crop_and_resize_video_uint8(frames_sel, [top, left, hh, ww], CROP_SIZE).permute(0, 2, 3, 1).contiguous()
+
+
 def dump_videos(metas: Sequence[dict], preprocessed_root: str, reader: Callable, seq_len: int, video_size: int,
-                frame_skip_of: Callable[[dict], int], device) -> np.ndarray:
+                frame_skip_of: Callable[[dict], int], device, crops: Optional[list] = None, crop_n: int = 0) -> np.ndarray:
     """(B, seq_len, H, W, 3) uint8: per clip, decode on the host, select (``frame_index_map``), then one
-    ``r50_op_resize_frames_u8`` launch into the batch buffer; ``video_size == 0`` keeps the decoded size (host pad / trim only)."""
+    ``r50_op_resize_frames_u8`` launch into the batch buffer; ``video_size == 0`` keeps the decoded size (host pad / trim only).
+    ``crops`` (a list, with ``crop_n`` > 0): receives, for each of the first ``crop_n`` clips, ``crop_clip`` of the same decoded and
+    selected frames (``--render``: the video is decoded once)."""
     from .frames import resize_frames_uint8
     host_clips, buf = [], None
     if video_size > 0:
@@ -205,12 +244,18 @@ def dump_videos(metas: Sequence[dict], preprocessed_root: str, reader: Callable,
         if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise RuntimeError(f"video reader returned {tuple(frames.shape)} {frames.dtype} for {path}; expected (N,H,W,3) uint8")
         sel = frame_index_map(frames.shape[0], int(meta["start"]), int(meta["end"]), frame_skip_of(meta), seq_len)
-        if buf is None:
+        want_crop = crops is not None and b < crop_n
+        if buf is None and not want_crop:
             host_clips.append(frames[sel].numpy())
             continue
         used = sorted(set(sel))                                   # upload only the frames the map names, once each
         pos = {f: i for i, f in enumerate(used)}
         clip = frames[used].contiguous().to(device)
+        if want_crop:
+            crops.append(crop_clip(clip[[pos[f] for f in sel]], meta.get("box"), b))
+        if buf is None:
+            host_clips.append(frames[sel].numpy())
+            continue
         resize_frames_uint8(clip, [pos[f] for f in sel], video_size, out=buf[b])
     if buf is not None:
         return buf.cpu().numpy()
@@ -375,7 +420,10 @@ def main(argv: Optional[List[str]] = None) -> str:
         frame_skip_of = lambda meta: index_skip                   # noqa: E731
     else:
         frame_skip_of = lambda meta: int(meta.get("frame_skip", 1))   # noqa: E731  (the reference's behaviour, kept on purpose)
-    videos = dump_videos(metas[:n_save], args.preprocessed_root, reader, args.seq_len, args.video_size, frame_skip_of, device)
+    n_render = min(n_save, args.render_n) if args.render is not None else 0
+    crops: List[Optional[torch.Tensor]] = []
+    videos = dump_videos(metas[:n_save], args.preprocessed_root, reader, args.seq_len, args.video_size, frame_skip_of, device,
+                         crops=crops if n_render else None, crop_n=n_render)
     joints3d_np = joints3d[:n_save].cpu().numpy()
 
     out_path = args.out
@@ -392,6 +440,16 @@ def main(argv: Optional[List[str]] = None) -> str:
         extra["geo_metric_names"] = np.array(GEO_EXTRA_KEYS)
     if detail is not None:
         extra.update(detail_npz(detail))
+    if n_render:                             # the person crops, drawn over; a clip without a usable box gets the plain background
+        from . import render
+        plain = torch.tensor(render._rgb_tuple(render.PANEL_BG_RGB), dtype=torch.uint8, device=device)
+        video_crop = torch.stack([c if c is not None else plain.expand(args.seq_len, CROP_SIZE, CROP_SIZE, 3) for c in crops])
+        future = torch.from_numpy(extra["predicted_future3djoints"][:n_render]).to(device) if rollout is not None else None
+        written = render.render_clips(args.render, video_crop, joints2d[:n_render], k[:n_render].to(torch.float32), joints3d[:n_render],
+                                      torch.from_numpy(pred[:n_render]).to(device), future, args.input_len if rollout is not None else 0,
+                                      list(metas[:n_render]), args.render_fps, args.render_sheet_every)
+        extra["video_crop"] = video_crop.cpu().numpy()
+        print(f"Rendered {n_render} clips ({len(written)} files) to: {args.render}")
     np.savez_compressed(out_path, video=videos, joints3d=joints3d_np, predicted3djoints=pred,
                         joints2d=joints2d[:n_save].cpu().numpy(), K=k[:n_save].to(torch.float32).cpu().numpy(),
                         meta=np.array(list(metas[:n_save]), dtype=object),

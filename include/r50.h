@@ -277,6 +277,28 @@ int r50_op_crop_resize_u8(const void* frames_thwc_u8, int t, int h, int w, int t
 int r50_op_resize_frames_u8(const void* frames_nhwc_u8, int n, int h, int w, const int* src_idx, int t, void* out_tssc_u8,
                             int out_size, void* stream);
 
+/* Results rendering (no counterpart in the reference, whose src/visualize_2d.py draws with matplotlib on the
+ * host): anti-aliased skeleton layers blended over uint8 frames.  bg (f,h,w,3) uint8 HWC on the device, or NULL for the uniform colour
+ * bg_rgb = 0xRRGGBB; pts (f,layers,joints,2) fp32 on the device, pixel coordinates, x first: pixel (row i, col j) has its centre at
+ * (x = j, y = i), the convention under which matplotlib overlays `scatter` on `imshow`; style (f,layers,4) uint8 on the device = R, G,
+ * B, A per frame and layer, A = 0 switches the layer off for that frame; edges_host: 2*n_edges ints ON THE HOST, pairs of joint indices
+ * (they travel as kernel arguments: no allocation, no synchronisation); out (f,h,w,3) uint8, which may not overlap bg.
+ * Per pixel p, the layers l = 0 .. layers-1 in order (later layers on top):
+ *   d_e = the smallest distance from p to a segment whose two end points are finite (a segment of zero length is a point),
+ *   d_j = the smallest distance from p to a finite joint; a joint with a NaN or inf coordinate is skipped, and so is every edge at it;
+ *   a   = max(clamp(half_width + 0.5 - d_e, 0, 1), clamp(joint_radius + 0.5 - d_j, 0, 1)) * A / 255,
+ *   c   = c * (1 - a) + rgb * a per channel in fp32, starting from the background byte; out = floor(c + 0.5) clamped to 0..255.
+ * A pixel with a == 0 in every layer leaves as its background byte.  Distances are formed in fp64 from the differences (p - a); the
+ * coverage, alpha and blend are fp32.  Coordinates of magnitude up to 2^20 keep that accuracy; larger finite ones are legal (nothing
+ * is indexed by a coordinate) but unspecified in value.  Gather form, one thread per 4 pixels, no atomics: the same bits on every run.
+ * w % 4 == 0 with bg and out 4-byte aligned takes a 12-byte vector path, anything else a per-byte path; same values.
+ * Refused with a message before any launch unless pts, style and out are non-NULL, f, h, w >= 1, 1 <= joints <= 64,
+ * 1 <= layers <= 8, 0 <= n_edges <= 128 (edges_host non-NULL when n_edges > 0), every edge index in [0, joints), half_width and
+ * joint_radius finite and >= 0, 0 <= bg_rgb <= 0xFFFFFF and out does not overlap bg.  Asynchronous on `stream`. */
+int r50_op_draw_skeletons_u8(const void* bg_fhwc_u8, int bg_rgb, const float* pts_flj2_f32, const void* style_fl4_u8,
+                             const int* edges_host, int n_edges, int f, int h, int w, int layers, int joints, float half_width,
+                             float joint_radius, void* out_fhwc_u8, void* stream);
+
 /* ColorJitter augmentation variant: `_aug_color_jitter` (src/dataset.py:188-197) = torchvision.transforms.v2
  * ColorJitter(brightness=0.3, contrast=0.3, saturation=0.2, hue=0.05) on the float clip in [0,1], followed (normalize != 0) by
  * `frame_tf` = Normalize(ImageNet mean, std) (:242-245).  frames_u8: (t,3,hw) uint8 resized crops on the device (the output of
