@@ -4692,6 +4692,184 @@ __global__ __launch_bounds__(256) void pose_detail_metrics_kernel(const float* _
     }
 }
 
+// ---- Dense evaluation: clips stitched into per-frame sequences -----------------------------------------
+// The maximum of v over the 64 lanes of a wave in a fixed tree, valid in lane 0; a NaN wins and stays.
+__device__ inline double wave_max_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_down(v, off, 64);
+        v = (o > v || o != o) ? o : v;
+    }
+    return v;
+}
+
+#define STITCH_WAVES 4                                                          // output frames per workgroup, one wave each
+
+// Gather form of the fusion of overlapping clips: pred, gt (N, T, J, 3) fp32 seen as N*T rows of C = 3J values; output frame f has the
+// contributors src[offsets[f] .. offsets[f+1]) = rows item*T + t, read in list order.  One wave per output frame (the frame index and
+// so the list are wave-uniform: the list is read by scalar loads), lanes walk the C components in passes of 64.  Per frame, with
+// t_c = src % T and n contributors:
+//   fused[f]   = sum_c w_c p_c / sum_c w_c, w_c = 1 (mode 0) or min(t_c + 1, ramp) (mode 1); mode 2 copies the contributor with the
+//                greatest t_c (the first in list order on a tie) bit for bit;
+//   gt_out[f]  = the first contributor's gt row, copied;
+//   spread[f]  = sqrt(sum_c sum_j |p_cj - m_j|^2 / (J n)), m the unweighted mean (the same in every mode, 0 for n = 1);
+//   gt_gap[f]  = max |gt_c - gt_first| over contributors and components (NaN if any is).
+// All arithmetic in fp64, one rounding to fp32 at each store; every frame is written by its own wave only: no atomics, the same bits
+// on every run.  An empty list (n = 0) writes zeros.  The indices are trusted: the caller checks them on the host.
+__global__ __launch_bounds__(64 * STITCH_WAVES) void stitch_poses_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                         const int* __restrict__ offsets, const int* __restrict__ src,
+                                                                         int F, int J, int T, int mode, int ramp,
+                                                                         float* __restrict__ fused, float* __restrict__ gt_out,
+                                                                         float* __restrict__ spread, float* __restrict__ gt_gap) {
+    const int lane = threadIdx.x & 63;
+    const int f = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * STITCH_WAVES + (threadIdx.x >> 6)));
+    if (f >= F) return;
+    const int C = 3 * J;
+    const int o0 = offsets[f], n = offsets[f + 1] - o0;
+    const int* __restrict__ list = src + o0;
+    const size_t out0 = (size_t)f * C;
+    if (n < 1) {
+        for (int i = lane; i < C; i += 64) fused[out0 + i] = gt_out[out0 + i] = 0.0f;
+        if (lane == 0) spread[f] = gt_gap[f] = 0.0f;
+        return;
+    }
+    int pick = 0;
+    if (mode == 2) {
+        int best = list[0] % T;
+        for (int c = 1; c < n; ++c) {
+            const int tc = list[c] % T;
+            if (tc > best) {
+                best = tc;
+                pick = c;
+            }
+        }
+    }
+    const size_t first = (size_t)list[0] * C, picked = (size_t)list[pick] * C;
+    double ss = 0.0, gap = 0.0;
+    for (int i = lane; i < C; i += 64) {
+        const float g0 = gt[first + i];
+        double sw = 0.0, swp = 0.0, sp = 0.0;
+        for (int c = 0; c < n; ++c) {
+            const int r = list[c];
+            const int tc = r % T;
+            const double w = mode == 1 ? (double)(tc + 1 < ramp ? tc + 1 : ramp) : 1.0;
+            const double p = (double)pred[(size_t)r * C + i];
+            swp += w * p;
+            sw += w;
+            sp += p;
+            const double d = fabs((double)gt[(size_t)r * C + i] - (double)g0);
+            gap = (d > gap || d != d) ? d : gap;
+        }
+        const double m = sp / (double)n;
+        for (int c = 0; c < n; ++c) {
+            const double d = (double)pred[(size_t)list[c] * C + i] - m;
+            ss += d * d;
+        }
+        fused[out0 + i] = mode == 2 ? pred[picked + i] : (float)(swp / sw);
+        gt_out[out0 + i] = g0;
+    }
+    ss = wave_sum_f64(ss);
+    gap = wave_max_f64(gap);
+    if (lane == 0) {
+        spread[f] = (float)sqrt(ss / ((double)J * (double)n));
+        gt_gap[f] = (float)gap;
+    }
+}
+
+// Per-frame errors of stitched sequences, summed per group: fused, gt (F, J, 3) fp32, spread (F), offsets (F+1), and per frame row
+// its sequence seq, its sub-frame index idx and its group in [0, G) (a row with another group value is counted nowhere).  Row r has a
+// velocity term if row r-1 is the previous frame of the same sequence (seq equal, idx one less), an acceleration term if row r+1 is
+// the next one as well; P1, velocity and acceleration errors are per pose (means over joints of pose_joint_distances' d1,
+// pose_velocity_error, pose_acceleration_error of root-relative joints).  Workgroup b owns the rows [b*chunk, (b+1)*chunk), chunk =
+// ceil(F / gridDim.x), and WRITES part[(b*G + g)*8 + {0..7}] = [frames, sum P1, velocity terms, sum velocity error, acceleration
+// terms, sum acceleration error, sum spread, frames with >= 2 contributors] of its rows of group g: one whole pose per thread,
+// per-thread fp64 partials in row order, then a fixed tree over the wave and the four waves; no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void sequence_metrics_kernel(const float* __restrict__ fused, const float* __restrict__ gt,
+                                                               const float* __restrict__ spread, const int* __restrict__ offsets,
+                                                               const int* __restrict__ seq, const int* __restrict__ idx,
+                                                               const int* __restrict__ group, int F, int J, int root, int G,
+                                                               double* __restrict__ part) {
+    __shared__ double red[8][4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const long long chunk = ((long long)F + gridDim.x - 1) / gridDim.x;
+    const long long lo = (long long)blockIdx.x * chunk;
+    const int r0 = (int)(lo < F ? lo : F), r1 = (int)(lo + chunk < F ? lo + chunk : F);
+    const size_t fs = (size_t)J * 3;                                             // one frame
+    const double zero3[3] = {0.0, 0.0, 0.0}, zero33[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    for (int g = 0; g < G; ++g) {
+        double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int r = r0 + tid; r < r1; r += 256) {
+            if (group[r] != g) continue;
+            const bool has_prev = r >= 1 && seq[r - 1] == seq[r] && idx[r - 1] == idx[r] - 1;
+            const bool has_next = has_prev && r + 1 < F && seq[r + 1] == seq[r] && idx[r + 1] == idx[r] + 1;
+            const float* y = fused + (size_t)r * fs;
+            const float* x = gt + (size_t)r * fs;
+            double yr[3], xr[3], pyr[3] = {0.0, 0.0, 0.0}, pxr[3] = {0.0, 0.0, 0.0}, nyr[3] = {0.0, 0.0, 0.0}, nxr[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                yr[c] = (double)y[3 * root + c];
+                xr[c] = (double)x[3 * root + c];
+                if (has_prev) {
+                    pyr[c] = (double)(y - fs)[3 * root + c];
+                    pxr[c] = (double)(x - fs)[3 * root + c];
+                }
+                if (has_next) {
+                    nyr[c] = (double)(y + fs)[3 * root + c];
+                    nxr[c] = (double)(x + fs)[3 * root + c];
+                }
+            }
+            double e1 = 0.0, ev = 0.0, ea = 0.0;
+            for (int j = 0; j < J; ++j) {
+                const float* yj = y + 3 * j;
+                const float* xj = x + 3 * j;
+                double d1, d2;                                                   // d2 (no fit here: scale 0) is not used
+                pose_joint_distances(yj, xj, yr, xr, zero3, zero3, 0.0, zero33, d1, d2);
+                e1 += d1;
+                if (has_prev) {
+                    double ry[3], rx[3], py[3], px[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        ry[c] = (double)yj[c] - yr[c];
+                        rx[c] = (double)xj[c] - xr[c];
+                        py[c] = (double)(yj - fs)[c] - pyr[c];
+                        px[c] = (double)(xj - fs)[c] - pxr[c];
+                    }
+                    ev += pose_velocity_error(ry, rx, py, px);
+                    if (has_next) {
+                        double ny[3], nx[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            ny[c] = (double)(yj + fs)[c] - nyr[c];
+                            nx[c] = (double)(xj + fs)[c] - nxr[c];
+                        }
+                        ea += pose_acceleration_error(ry, rx, py, px, ny, nx);
+                    }
+                }
+            }
+            a[0] += 1.0;
+            a[1] += e1 / (double)J;
+            if (has_prev) {
+                a[2] += 1.0;
+                a[3] += ev / (double)J;
+            }
+            if (has_next) {
+                a[4] += 1.0;
+                a[5] += ea / (double)J;
+            }
+            a[6] += (double)spread[r];
+            a[7] += offsets[r + 1] - offsets[r] >= 2 ? 1.0 : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const double v = wave_sum_f64(a[q]);
+            if (lane == 0) red[q][wave] = v;
+        }
+        __syncthreads();
+        if (tid < 8) part[((size_t)blockIdx.x * G + g) * 8 + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+        __syncthreads();
+    }
+}
+
 // ---- Phase 2: training f_AR (DESIGN.md "f next #2") ----------------------------------------------------
 // Future-pose loss of the phase-2 step: l3d_hat = mean over frames s >= 1 of (y_hat - gt)^2.  Frame 0 has no prediction (phi_hat[:, 0]
 // is the constant 0), so dy = 0 there and dy = 2 (y_hat - gt) / n * loss_scale elsewhere, n = b*(t-1)*joints*3 (the arithmetic of

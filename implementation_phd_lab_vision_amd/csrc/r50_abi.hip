@@ -2491,6 +2491,31 @@ int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* gr
     return ew_done("r50_op_pose_detail_metrics");
 }
 
+int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int joints, const int* offsets, const int* src, int frames, int t,
+                        int mode, int ramp, float* fused, float* gt_out, float* spread, float* gt_gap, void* stream) {
+    if (!pred || !gt || !offsets || !src || !fused || !gt_out || !spread || !gt_gap)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_stitch_poses: null pointer");
+    if (rows < 1 || rows > INT32_MAX || joints < 1 || joints > 64 || frames < 1 || t < 1 || rows % t != 0 || mode < 0 || mode > 2 || ramp < 1)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_stitch_poses: invalid arguments (need 1 <= rows < 2^31 a multiple of t >= 1, "
+                                              "1 <= joints <= 64, frames >= 1, mode in {0,1,2} and ramp >= 1)");
+    hipLaunchKernelGGL(stitch_poses_kernel, dim3((unsigned)((frames + STITCH_WAVES - 1) / STITCH_WAVES)), dim3(64 * STITCH_WAVES), 0,
+                       (hipStream_t)stream, pred, gt, offsets, src, frames, joints, t, mode, ramp, fused, gt_out, spread, gt_gap);
+    return ew_done("r50_op_stitch_poses");
+}
+
+int r50_op_sequence_metrics(const float* fused, const float* gt, const float* spread, const int* offsets, const int* seq, const int* idx,
+                            const int* group, int frames, int joints, int root, int n_groups, double* part, int n_blocks, void* stream) {
+    if (!fused || !gt || !spread || !offsets || !seq || !idx || !group || !part)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_sequence_metrics: null pointer");
+    if (frames < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || n_groups < 1 || n_blocks < 1 ||
+        (int64_t)n_blocks * n_groups > INT32_MAX / 8)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_sequence_metrics: invalid arguments (need frames, n_groups, n_blocks >= 1, "
+                                              "1 <= joints <= 64 and 0 <= root < joints)");
+    hipLaunchKernelGGL(sequence_metrics_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, fused, gt, spread, offsets, seq,
+                       idx, group, frames, joints, root, n_groups, part);
+    return ew_done("r50_op_sequence_metrics");
+}
+
 int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,
                                  void* stream) {
     if (!y_hat || !gt || !dy || !loss2 || b < 1 || t < 2 || joints < 1 || (int64_t)b * t > INT64_MAX / 3 / joints)

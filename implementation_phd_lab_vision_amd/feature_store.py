@@ -76,6 +76,10 @@ class DeviceFeatureStore:
         """Item i's ``action`` from the index entry of its clip (the name as stored, trial suffix included), in item order."""
         return [str(c["action"]) for c, _ in self._items]
 
+    def item_clips(self) -> List[dict]:
+        """Item i's index entry (``subject, action, cam, start, end`` in sub-sampled frame units, ``shard_id``, ``row``), in item order."""
+        return [c for c, _ in self._items]
+
     def __getitem__(self, idx: int):
         """The reference dataset's item (src/dataset_features.py:112-126), tensors on ``self.device``."""
         row = self._row_host[idx]

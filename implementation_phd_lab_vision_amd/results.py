@@ -17,7 +17,11 @@ and mm per frame^2, for all clips, the action mean and each action (and per hori
 drawn on the device (``render.render_panels``: frame + GT 2D joints | frame + projected GT and prediction | 3D view) and written as
 ``DIR/clip_<i>_S<subject>_<action>.png`` (an APNG at ``--render-fps``) and ``DIR/clip_<i>_sheet.png`` (every ``--render-sheet-every``-th
 frame); the frames are the clip's person crop -- ``meta["box"]`` through ``frames.crop_and_resize_video_uint8``, what ``joints2d`` and
-``K`` refer to -- and the ``.npz`` gains ``video_crop`` (n, T, 224, 224, 3).
+``K`` refer to -- and the ``.npz`` gains ``video_crop`` (n, T, 224, 224, 3).  With ``--dense`` (default off)
+the overlapping clips are stitched into one pose per video frame (``sequences.evaluate_dense``, ``--dense-fuse mean | context | last``)
+and every video frame is scored once: the ``Dense |`` lines print P1, P2, the velocity and acceleration errors and the spread of the
+contributors for all frames, the action mean and each action, and the clip-wise P1 / P2 by window position; the ``.npz`` gains the
+``dense_*`` keys and ``--dense-out FILE.npz`` receives the stitched sequences themselves.
 
 Two differences from running the reference's script as it stands:
 
@@ -94,6 +98,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--render-n", type=int, default=4, help="clips to render (--render)")
     p.add_argument("--render-fps", type=float, default=10.0, help="frame rate of the APNGs (--render)")
     p.add_argument("--render-sheet-every", type=int, default=5, help="the contact sheet holds every this-many-th frame (--render)")
+    p.add_argument("--dense", action="store_true",
+                   help="also stitch the overlapping clips into one pose per video frame and score every video frame once, per action "
+                        "(INTEGRATION.md section Q)")
+    p.add_argument("--dense-fuse", choices=("mean", "context", "last"), default="context",
+                   help="how a frame's predictions are fused (--dense): the plain mean, weights growing with the past a window position "
+                        "has seen up to f_movie's receptive field, or the prediction that has seen the most past")
+    p.add_argument("--dense-out", type=str, default=None, metavar="FILE.npz",
+                   help="also write the stitched sequences (seq_keys, seq_start, frame_idx, pred, gt, spread, count) there (--dense)")
     return p
 
 
@@ -121,6 +133,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--render-fps must be > 0, got {args.render_fps}")
         if args.render_sheet_every < 1:
             p.error(f"--render-sheet-every must be >= 1, got {args.render_sheet_every}")
+    if args.dense_out is not None and not args.dense:
+        p.error("--dense-out needs --dense")
     return args
 
 
@@ -355,6 +369,51 @@ def detail_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     return out
 
 
+def dense_lines(res: Dict[str, object]) -> List[str]:
+    """The printed lines of ``--dense`` from an ``evaluate_dense`` result, each starting with ``Dense |``: the summary (all frames and
+    the action mean), one line per action, and the clip-wise P1 / P2 at window positions 1, T/2 and T.  Millimetres."""
+    def summary(key: str) -> str:
+        return (f"p1 (mm) {res['p1' + key] * 1000.0:.2f} | p2 (mm) {res['p2' + key] * 1000.0:.2f} | vel (mm/frame) "
+                f"{res['mpjve' + key] * 1000.0:.2f} | accel (mm/frame^2) {res['accel' + key] * 1000.0:.2f} | spread (mm) "
+                f"{res['spread' + key] * 1000.0:.2f}")
+
+    lines = [f"Dense | fuse {res['fuse']} (ramp {res['ramp']}) | sequences {res['sequences']} | frames {res['frames_all']} of "
+             f"{res['clip_frames']} clip frames | fused from >= 2 clips {res['multi_frames']} | all: {summary('_all')} | action mean: "
+             f"{summary('_mean')}"]
+    for i, name in enumerate(res["group_names"]):
+        lines.append(f"Dense |   {name} | frames {int(res['frames'][i])} | p1 (mm) {res['p1'][i] * 1000.0:.2f} | p2 (mm) "
+                     f"{res['p2'][i] * 1000.0:.2f} | vel (mm/frame) {res['mpjve'][i] * 1000.0:.2f} | accel (mm/frame^2) "
+                     f"{res['accel'][i] * 1000.0:.2f} | spread (mm) {res['spread'][i] * 1000.0:.2f}")
+    p1, p2 = res["position_p1"], res["position_p2"]
+    at = sorted({1, max(len(p1) // 2, 1), len(p1)})
+    lines.append("Dense | clip-wise by window position | p1 (mm) " + " | ".join(f"@{k}: {p1[k - 1] * 1000.0:.2f}" for k in at) +
+                 " | p2 (mm) " + " | ".join(f"@{k}: {p2[k - 1] * 1000.0:.2f}" for k in at))
+    return lines
+
+
+def dense_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--dense``: ``dense_actions`` (G,) str, ``dense_frames`` (G,) int64, ``dense_M`` (G,) and ``dense_M_all`` ()
+    fp32 for M in p1, p2, mpjve, accel, spread (metres, metres per frame, metres per frame^2), ``dense_position_p1`` / ``_p2`` (T,) fp32,
+    ``dense_counts`` int64 [sequences, frames, clip frames, frames fused from >= 2 clips], ``dense_fuse`` str."""
+    out = {"dense_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "dense_frames": np.asarray(res["frames"], dtype=np.int64), "dense_fuse": np.array(str(res["fuse"])),
+           "dense_counts": np.array([res["sequences"], res["frames_all"], res["clip_frames"], res["multi_frames"]], dtype=np.int64),
+           "dense_position_p1": np.asarray(res["position_p1"], dtype=np.float32),
+           "dense_position_p2": np.asarray(res["position_p2"], dtype=np.float32)}
+    for m in ("p1", "p2", "mpjve", "accel", "spread"):
+        out["dense_" + m] = np.asarray(res[m], dtype=np.float32)
+        out["dense_" + m + "_all"] = np.asarray(res[m + "_all"], dtype=np.float32)
+    return out
+
+
+def dense_export(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The arrays of ``--dense-out``: ``seq_keys`` (S, 3) str [subject, action, cam], ``seq_start`` (S+1,), ``frame_idx`` (F,) int32
+    (sub-sampled frame units), ``pred`` and ``gt`` (F, J, 3) fp32 in metres, ``spread`` (F,) fp32, ``count`` (F,) int32 = the clips
+    that showed the frame; sequence s is rows ``seq_start[s]:seq_start[s+1]``."""
+    return {"seq_keys": np.array([[str(v) for v in k] for k in res["seq_keys"]], dtype=str), "seq_start": res["seq_start"],
+            "frame_idx": res["frame_idx"], "pred": res["pred"], "gt": res["gt"], "spread": res["frame_spread"], "count": res["count"]}
+
+
 def main(argv: Optional[List[str]] = None) -> str:
     """``python src/results.py`` on one MI355X.  Returns the path of the written ``.npz``."""
     from .feature_store import DeviceFeatureStore
@@ -413,6 +472,13 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in detail_lines(detail, args.input_len, args.pred_len):
             print(line)
 
+    dense = None
+    if args.dense:                           # every video frame once: the clips of a sequence fused per frame
+        from .sequences import evaluate_dense
+        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse, keep_poses=args.dense_out is not None)
+        for line in dense_lines(dense):
+            print(line)
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -440,6 +506,12 @@ def main(argv: Optional[List[str]] = None) -> str:
         extra["geo_metric_names"] = np.array(GEO_EXTRA_KEYS)
     if detail is not None:
         extra.update(detail_npz(detail))
+    if dense is not None:
+        extra.update(dense_npz(dense))
+        if args.dense_out is not None:
+            os.makedirs(os.path.dirname(args.dense_out) or ".", exist_ok=True)
+            np.savez_compressed(args.dense_out, **dense_export(dense))
+            print(f"Dense | stitched sequences saved to: {args.dense_out}")
     if n_render:                             # the person crops, drawn over; a clip without a usable box gets the plain background
         from . import render
         plain = torch.tensor(render._rgb_tuple(render.PANEL_BG_RGB), dtype=torch.uint8, device=device)

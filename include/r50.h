@@ -406,6 +406,36 @@ int r50_op_pose_protocols(const float* pred, const float* gt, const int* group, 
 int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
                                int n_groups, int n_thr, double thr_max, double* acc, void* stream);
 
+/* Dense evaluation, the fusion of overlapping clips into one pose per video frame: pred, gt
+ * (rows/t, t, joints, 3) fp32 seen as rows = N*t pose rows; output frame f has the contributors src[offsets[f] .. offsets[f+1]), each a
+ * row index item*t + t_c, read in list order; offsets (frames+1) and src int32 device values.  Per frame with n contributors, in fp64
+ * with one rounding to fp32 at each store:
+ *   fused (frames,joints,3)  = sum_c w_c pred_c / sum_c w_c with w_c = 1 (mode 0, mean) or min(t_c + 1, ramp) (mode 1, context); mode 2
+ *                              (last) copies the contributor with the greatest t_c, the first in list order on a tie, bit for bit;
+ *   gt_out (frames,joints,3) = the first contributor's gt row, copied;
+ *   spread (frames)          = sqrt(sum_c sum_j |pred_cj - m_j|^2 / (joints n)), m the unweighted mean: the same in every mode, 0 for n = 1;
+ *   gt_gap (frames)          = the largest |gt_c - gt_first| over contributors and components (0 when the index is right).
+ * An empty list writes zeros.  Needs 1 <= rows < 2^31 a multiple of t >= 1, 1 <= joints <= 64, frames >= 1, mode in {0,1,2}, ramp >= 1,
+ * no null pointer; checked before any launch.  The kernel TRUSTS offsets and src: the caller checks on the host that offsets is
+ * non-decreasing from 0 to the length of src and that every src lies in [0, rows).  Gather form, one wave per output frame, no atomics:
+ * the same bits on every run. */
+int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int joints, const int* offsets, const int* src, int frames, int t,
+                        int mode, int ramp, float* fused, float* gt_out, float* spread, float* gt_gap, void* stream);
+
+/* Dense evaluation, per-frame errors of stitched sequences per group: fused, gt (frames,joints,3) fp32, spread
+ * (frames) fp32, offsets (frames+1), and per frame row its sequence seq, sub-frame index idx and group in [0,n_groups), all int32 device
+ * values (a row with another group value is counted nowhere).  Row r has a velocity term if row r-1 has the same seq and idx[r-1] ==
+ * idx[r] - 1, an acceleration term if row r+1 continues the sequence as well; P1, velocity and acceleration errors are those of
+ * r50_op_pose_detail_metrics, per pose (means over joints, root-relative).  Workgroup b of n_blocks owns the rows [b*chunk, (b+1)*chunk),
+ * chunk = ceil(frames / n_blocks), and WRITES (does not add)
+ *   part[(b*n_groups + g)*8 + {0..7}] = [frames, sum P1, velocity terms, sum velocity error, acceleration terms, sum acceleration error,
+ *                                        sum spread, frames with >= 2 contributors] of its rows of group g;
+ * part: n_blocks*n_groups*8 doubles of device memory; the caller sums the blocks in block order.  Needs frames, n_groups, n_blocks >= 1,
+ * 1 <= joints <= 64, 0 <= root < joints, no null pointer; checked before any launch.  fp64 sums in a fixed order (no atomics: the same
+ * bits on every run). */
+int r50_op_sequence_metrics(const float* fused, const float* gt, const float* spread, const int* offsets, const int* seq, const int* idx,
+                            const int* group, int frames, int joints, int root, int n_groups, double* part, int n_blocks, void* stream);
+
 /* Lifting head, phase 2 (training f_AR; DESIGN.md "f next #2").  The reference has no phase 2; this
  * project's definition: f_movie / f_3D frozen and run as at inference, loss = l3d_hat + lambda * l_lat over frames s >= 1.
  *  r50_op_future_pose_loss_grad: y_hat, gt, dy (b*t, joints, 3) fp32: dy = 2 (y_hat-gt) / n * loss_scale with n = b*(t-1)*joints*3,

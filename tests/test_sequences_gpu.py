@@ -1,0 +1,462 @@
+"""Dense evaluation on the MI355X: ``r50_op_stitch_poses`` and ``r50_op_sequence_metrics`` against the fp64
+loop oracle of ``tests/stitch_reference.py``, ``sequences.evaluate_dense`` stage by stage on small caches, and ``results --dense``.
+
+Tolerances.  ``fused``: both sides add the same fp32 inputs in fp64 in the same order and divide once, so they agree to the last
+rounding of an fp64 value to fp32: 1 fp32 ulp (bit-equal where one contributor, or a copy, makes the value).  ``spread``: one fp32
+store of an fp64 value, 2^-24 relative, under rel 1e-6 + abs 1e-6 max|coordinate|.  Metric sums: fp64 sums of a few hundred terms in
+another order, rel 1e-9 (the bar of the protocols and detail ops).  The CLI run is a fresh child process under a time limit."""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from tests import results_data as rd
+from tests import stitch_reference as ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = Path(__file__).resolve().parents[1]
+T = 8
+# 23 clips of 8 frames in two sequences: strides 1, 3 and 8 and a gap; frames with 1, 2, 3, ... 8 contributors, 91 frames (not a
+# multiple of the 4 waves of a workgroup)
+STARTS_A = [0, 1, 2, 3, 4, 5, 6, 7, 10, 13, 16, 24, 32, 50]
+STARTS_B = [0, 8, 16, 19, 22, 23, 24, 27, 40]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from implementation_phd_lab_vision_amd import _lib
+    _lib.build_library()
+    return _lib.load_library()
+
+
+def _clip(subject, action, cam, start, t=T):
+    return {"subject": subject, "action": action, "cam": cam, "start": start, "end": start + t}
+
+
+def _stitch_clips():
+    clips = [_clip(9, "walk", 1, s) for s in STARTS_A] + [_clip(9, "sit", 2, s) for s in STARTS_B]
+    order = np.random.default_rng(5).permutation(len(clips))
+    return [clips[i] for i in order]
+
+
+def _poses(clips, joints, seed):
+    """pred (N, T, J, 3) random fp32; gt the same pose wherever two clips show one video frame, on a 2^-10 grid (so that + 0.25 is exact)."""
+    rng = np.random.default_rng(seed)
+    pred = (rng.standard_normal((len(clips), T, joints, 3)) * 0.4).astype(np.float32)
+    truth = {}
+    gt = np.zeros_like(pred)
+    for i, c in enumerate(clips):
+        for t in range(T):
+            key = (c["action"], c["start"] + t)
+            if key not in truth:
+                truth[key] = (np.round(rng.standard_normal((joints, 3)) * 512.0) / 1024.0).astype(np.float32)
+            gt[i, t] = truth[key]
+    return pred, gt
+
+
+@pytest.fixture(scope="module")
+def stitch_case():
+    """The table and, per joint count, the inputs: computed once, shared, left unchanged."""
+    clips = _stitch_clips()
+    table = ref.table(clips, T)
+    counts = np.diff(table["offsets"])
+    assert len(clips) == 23 and {1, 2, 3, 8} <= set(counts.tolist()) and len(counts) % 4 != 0 and len(table["seq_keys"]) == 2
+    return {"clips": clips, "offsets": table["offsets"].astype(np.int32), "src": table["src"].astype(np.int32), "counts": counts,
+            "poses": {j: _poses(clips, j, 10 + j) for j in (1, 17, 22)}}
+
+
+def _run_stitch(case, joints, mode, ramp, gt=None, band=3):
+    from implementation_phd_lab_vision_amd import sequences as sq
+    pred, gt0 = case["poses"][joints]
+    gt = gt0 if gt is None else gt
+    f = len(case["counts"])
+    out = [torch.full(s, float("nan"), dtype=torch.float32, device=DEV) for s in ((f + band, joints, 3), (f + band, joints, 3), (f + band,), (f + band,))]
+    got = sq.stitch_poses(torch.from_numpy(pred).to(DEV), torch.from_numpy(gt).to(DEV), (case["offsets"], case["src"]), mode, ramp, out=out)
+    assert all(a.data_ptr() == b.data_ptr() for a, b in zip(got, out))
+    host = [o.cpu().numpy() for o in out]
+    for h in host:
+        assert np.isnan(h[f:]).all() and not np.isnan(h[:f]).any()               # the band after row F is not touched
+    return [h[:f] for h in host]
+
+
+def _assert_within_one_ulp(got32, want64, what):
+    want32 = want64.astype(np.float32)
+    err = np.abs(got32.astype(np.float64) - want32.astype(np.float64))
+    ulp = np.spacing(np.abs(want32)).astype(np.float64)
+    print(f"{what}: max error {float((err / ulp).max()):.2f} ulp, {int((err > 0).sum())} of {err.size} values differ")
+    assert np.all(err <= ulp), what
+
+
+@pytest.mark.parametrize("joints", [1, 17, 22])
+@pytest.mark.parametrize("mode,ramp", [(0, 1), (1, 1), (1, 5), (1, 13), (2, 1)])
+def test_stitch_matches_the_oracle(lib, stitch_case, joints, mode, ramp):
+    pred, gt = stitch_case["poses"][joints]
+    fused, gt_out, spread, gap = _run_stitch(stitch_case, joints, mode, ramp)
+    w_fused, w_gt, w_spread, w_gap = ref.stitch(pred, gt, stitch_case["offsets"], stitch_case["src"], mode, ramp)
+    _assert_within_one_ulp(fused, w_fused, f"fused J={joints} mode={mode} ramp={ramp}")
+    single = stitch_case["counts"] == 1
+    assert single.any() and np.array_equal(fused[single].view(np.uint32), w_fused[single].astype(np.float32).view(np.uint32))
+    if mode == 2:
+        assert np.array_equal(fused.view(np.uint32), w_fused.astype(np.float32).view(np.uint32))
+    assert np.array_equal(gt_out.view(np.uint32), w_gt.view(np.uint32))
+    assert np.all(gap == 0.0) and np.all(w_gap == 0.0)
+    tol = 1e-6 * w_spread + 1e-6 * float(np.abs(pred).max())
+    print(f"spread: max error {float(np.abs(spread - w_spread).max()):.3e}, bound {float(tol.min()):.3e}")
+    assert np.all(np.abs(spread.astype(np.float64) - w_spread) <= tol)
+    assert np.all(spread[single] == 0.0) and np.all(spread[~single] > 0.0)
+    again = _run_stitch(stitch_case, joints, mode, ramp)                            # the same bits on every run
+    for a, b in zip((fused, gt_out, spread, gap), again):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@pytest.mark.parametrize("joints", [1, 22])
+def test_stitch_context_with_ramp_one_is_the_mean(lib, stitch_case, joints):
+    mean, ctx = _run_stitch(stitch_case, joints, 0, 7), _run_stitch(stitch_case, joints, 1, 1)
+    for a, b in zip(mean, ctx):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    names = _run_stitch(stitch_case, joints, "mean", 7)                             # the modes by name
+    assert np.array_equal(mean[0].view(np.uint32), names[0].view(np.uint32))
+    assert not np.array_equal(mean[0], _run_stitch(stitch_case, joints, "context", 13)[0])
+
+
+def test_stitch_reports_a_ground_truth_gap(lib, stitch_case):
+    joints = 17
+    pred, gt = stitch_case["poses"][joints]
+    off, src = stitch_case["offsets"], stitch_case["src"]
+    frame = int(np.flatnonzero(stitch_case["counts"] == 3)[0])
+    row = int(src[off[frame] + 1])                                                  # the second contributor of a frame with three
+    bent = gt.copy()
+    bent.reshape(-1, joints, 3)[row, 11, 2] += np.float32(0.25)
+    fused, gt_out, spread, gap = _run_stitch(stitch_case, joints, 1, 13, gt=bent)
+    want = np.zeros(len(gap), dtype=np.float32)
+    want[frame] = 0.25
+    assert np.array_equal(gap, want)
+    clean = _run_stitch(stitch_case, joints, 1, 13)
+    assert np.array_equal(gt_out, clean[1]) and np.array_equal(fused, clean[0])     # the first contributor's gt; pred untouched
+
+
+def test_stitch_refuses_bad_arguments_on_the_host(lib, stitch_case, monkeypatch):
+    from implementation_phd_lab_vision_amd import sequences as sq
+
+    def no_launch():
+        raise AssertionError("the library was reached: the refusal did not come from the host check")
+
+    monkeypatch.setattr(sq._lib, "load_library", no_launch)
+    pred, gt = (torch.from_numpy(a).to(DEV) for a in stitch_case["poses"][17])
+    off, src = stitch_case["offsets"], stitch_case["src"]
+    rows = pred.shape[0] * T
+    down = off.copy()
+    down[5], down[6] = off[6], off[5]
+    far, neg = src.copy(), src.copy()
+    far[7], neg[3] = rows, -1
+    wide = torch.zeros((2, 4, 65, 3), dtype=torch.float32, device=DEV)
+    small = (np.array([0, 1, 2], dtype=np.int32), np.array([0, 7], dtype=np.int32))
+    for args in ((pred, gt, (down, src), 0, 1), (pred, gt, (off, far), 0, 1), (pred, gt, (off, neg), 0, 1), (wide, wide, small, 0, 1),
+                 (pred, gt, (off, src), 3, 1), (pred, gt, (off, src), "median", 1), (pred, gt, (off, src), 1, 0),
+                 (pred, gt, (off[:-1], src), 0, 1), (pred.cpu(), gt.cpu(), (off, src), 0, 1), (pred.double(), gt.double(), (off, src), 0, 1),
+                 (pred[:, :, :, :2], gt[:, :, :, :2], (off, src), 0, 1), (pred[::2], gt[::2], (off, src), 0, 1)):
+        with pytest.raises(ValueError):
+            sq.stitch_poses(*args)
+    short = [torch.empty(s, dtype=torch.float32, device=DEV) for s in ((5, 17, 3), (5, 17, 3), (5,), (5,))]
+    with pytest.raises(ValueError):
+        sq.stitch_poses(pred, gt, (off, src), 0, 1, out=short)
+
+
+def test_abi_refuses_bad_arguments(lib):
+    x = torch.zeros(64, dtype=torch.float32, device=DEV)
+    i = torch.zeros(8, dtype=torch.int32, device=DEV)
+    d = torch.zeros(64, dtype=torch.float64, device=DEV)
+    p, q, s = x.data_ptr(), i.data_ptr(), torch.cuda.current_stream().cuda_stream
+    for args in ((p, p, 8, 65, q, q, 1, 4, 0, 1, p, p, p, p, s), (p, p, 8, 1, q, q, 1, 4, 3, 1, p, p, p, p, s),
+                 (p, p, 8, 1, q, q, 1, 4, 1, 0, p, p, p, p, s), (p, p, 7, 1, q, q, 1, 4, 0, 1, p, p, p, p, s),
+                 (p, p, 8, 1, q, q, 0, 4, 0, 1, p, p, p, p, s), (p, None, 8, 1, q, q, 1, 4, 0, 1, p, p, p, p, s)):
+        assert lib.r50_op_stitch_poses(*args) != 0 and b"r50_op_stitch_poses" in lib.r50_last_error(None)
+    for args in ((p, p, p, q, q, q, q, 0, 1, 0, 1, d.data_ptr(), 1, s), (p, p, p, q, q, q, q, 1, 65, 0, 1, d.data_ptr(), 1, s),
+                 (p, p, p, q, q, q, q, 1, 2, 2, 1, d.data_ptr(), 1, s), (p, p, p, q, q, q, q, 1, 1, 0, 0, d.data_ptr(), 1, s),
+                 (p, p, p, q, q, q, q, 1, 1, 0, 1, d.data_ptr(), 0, s), (p, p, p, q, q, q, q, 1, 1, 0, 1, None, 1, s)):
+        assert lib.r50_op_sequence_metrics(*args) != 0 and b"r50_op_sequence_metrics" in lib.r50_last_error(None)
+    torch.cuda.synchronize()
+    assert float(x.abs().sum()) == 0.0 and float(d.abs().sum()) == 0.0
+
+
+# ------------------------------------------------------------------ sequence metrics ----------------------------------------------
+def _metric_case(lengths, groups_of_seq, joints, seed, gap_in=None):
+    """Frame rows of sequences of the given lengths (consecutive idx from a random first frame; ``gap_in = (s, k)`` skips one frame
+    before row k of sequence s), random poses, spreads and contributor counts."""
+    rng = np.random.default_rng(seed)
+    seq, idx = [], []
+    for s, n in enumerate(lengths):
+        first = int(rng.integers(0, 50))
+        frames = list(range(first, first + n))
+        if gap_in is not None and gap_in[0] == s:
+            frames = frames[:gap_in[1]] + [f + 1 for f in frames[gap_in[1]:]]
+        seq += [s] * n
+        idx += frames
+    f = len(seq)
+    counts = rng.integers(1, 4, size=f)
+    return {"seq": np.array(seq, dtype=np.int32), "idx": np.array(idx, dtype=np.int32),
+            "group": np.array([groups_of_seq[s] for s in seq], dtype=np.int32),
+            "offsets": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32),
+            "fused": (rng.standard_normal((f, joints, 3)) * 0.5).astype(np.float32),
+            "gt": (rng.standard_normal((f, joints, 3)) * 0.5).astype(np.float32),
+            "spread": rng.random(f).astype(np.float32)}
+
+
+def _run_metrics(case, n_groups, n_blocks=None):
+    from implementation_phd_lab_vision_amd import sequences as sq
+    dev = {k: torch.from_numpy(v).to(DEV) for k, v in case.items()}
+    part = sq.sequence_metrics(dev["fused"], dev["gt"], dev["spread"], dev["offsets"], dev["seq"], dev["idx"], dev["group"], n_groups,
+                               n_blocks=n_blocks)
+    return sq.sum_blocks(part.cpu().numpy()), part
+
+
+def _assert_sums(got, want, what):
+    counts = [0, 2, 4, 7]
+    assert np.array_equal(got[:, counts], want[:, counts]), what
+    sums = [1, 3, 5, 6]
+    err = np.abs(got[:, sums] - want[:, sums])
+    print(f"{what}: max relative error of the sums {float((err / np.maximum(np.abs(want[:, sums]), 1e-300)).max()):.3e}")
+    assert np.all(err <= 1e-9 * np.abs(want[:, sums])), what
+
+
+def test_sequence_metrics_match_the_oracle(lib):
+    lengths = [1, 2, 3, 300, 1, 393]                                                # F = 700: three workgroups of 256 rows
+    case = _metric_case(lengths, [0, 1, 3, 1, 3, 0], 17, seed=21, gap_in=(3, 140))  # group 2 has no frames; one gap
+    assert len(case["seq"]) == 700
+    want = ref.metrics(case["fused"], case["gt"], case["spread"], case["offsets"], case["seq"], case["idx"], case["group"], 4)
+    assert want[2].sum() == 0 and want[:, 2].sum() == 693 and want[:, 4].sum() == 688   # runs of 1, 2, 3, 140, 160, 1, 393 frames
+    got, part = _run_metrics(case, 4)
+    assert tuple(part.shape) == (3, 4, 8)
+    _assert_sums(got, want, "F=700")
+    assert np.all(got[2] == 0.0)
+    again, part2 = _run_metrics(case, 4)
+    assert torch.equal(part, part2)                                                 # the same bits on every run
+    for n_blocks in (1, 7, 1000):                                                   # other splits of the rows: the same sums
+        _assert_sums(_run_metrics(case, 4, n_blocks)[0], want, f"F=700 in {n_blocks} blocks")
+
+
+def test_sequence_metrics_equal_the_detail_op_on_whole_clips(lib):
+    """Every sequence exactly P = 6 consecutive frames: the P1, velocity and acceleration sums are those of
+    ``r50_op_pose_detail_metrics`` on the same data seen as (S, 6, J, 3) (its sums are over joints: J times the per-pose means)."""
+    from implementation_phd_lab_vision_amd import detail_metrics as dm
+    s, p, joints, n_groups = 47, 6, 17, 3
+    groups = [k % n_groups for k in range(s)]
+    case = _metric_case([p] * s, groups, joints, seed=33)
+    got, _ = _run_metrics(case, n_groups)
+    acc = torch.zeros(dm.acc_size(n_groups, p, joints), dtype=torch.float64, device=DEV)
+    dm.add_detail_sums(torch.from_numpy(case["fused"]).to(DEV).view(s, p, joints, 3), torch.from_numpy(case["gt"]).to(DEV).view(s, p, joints, 3),
+                       0, torch.tensor(groups, dtype=torch.int32, device=DEV), n_groups, acc)
+    sums = acc.cpu().numpy()
+    a_end = 2 * n_groups * p * joints
+    sec_a = sums[:a_end].reshape(n_groups, p, joints, 2)
+    sec_b = sums[a_end:a_end + 6 * n_groups * p].reshape(n_groups, p, 6)
+    want = np.stack([sec_a[..., 0].sum(axis=(1, 2)), sec_b[..., 4].sum(axis=1), sec_b[..., 5].sum(axis=1)], axis=1) / joints
+    err = np.abs(got[:, [1, 3, 5]] - want)
+    print(f"vs the detail op: max relative error {float((err / np.abs(want)).max()):.3e}")
+    assert np.all(err <= 1e-9 * np.abs(want))
+    clips = np.bincount(groups, minlength=n_groups)
+    assert np.array_equal(got[:, 0], clips * p) and np.array_equal(got[:, 2], clips * (p - 1)) and np.array_equal(got[:, 4], clips * (p - 2))
+
+
+# ------------------------------------------------------------------ evaluate_dense ------------------------------------------------
+def _write_cache(root, metas, video_truth, seed=0):
+    """A feature cache of the given clips; ``joints3d`` (mm) is cut from ``video_truth[(action, cam)]`` (frames, 17, 3)."""
+    from implementation_phd_lab_vision_amd.shards import ShardPacker
+    g = torch.Generator().manual_seed(seed)
+    packer = ShardPacker(root, n_vars=1, shard_size=4, shuffle_pool=5, shuffle_seed=seed)
+    for meta in metas:
+        k = torch.eye(3)
+        k[0, 0], k[1, 1] = 1000.0 + 100.0 * torch.rand(2, generator=g)
+        k[0, 2], k[1, 2] = 500.0 + 20.0 * torch.rand(2, generator=g)
+        truth = video_truth[(meta["action"], meta["cam"])][meta["start"]:meta["end"]]
+        packer.add_group([{"feat": torch.randn(T, 2048, generator=g).abs(), "joints3d": truth.clone(),
+                           "joints2d": torch.rand(T, 17, 2, generator=g) * 1000.0, "K": k, "meta": dict(meta, aug="orig", box=None)}])
+    packer.finish()
+    packer.write_index(seq_len=T, frame_skip=2, save_fp16=False, augment=False)
+    return Path(root)
+
+
+VIDEO_STARTS = {("act0_1", 1): [0, 4, 8, 12], ("act1", 1): [0, 2, 4], ("act2 2", 2): [5], ("act0_2", 1): [3, 4]}
+
+
+def _cache(root, overlap: bool):
+    g = torch.Generator().manual_seed(77)
+    truth = {key: torch.randn(16 * T, 17, 3, generator=g) * 300.0 for key in VIDEO_STARTS}
+    metas = [{"subject": 9, "action": a, "cam": c, "start": s if overlap else T * s, "end": (s if overlap else T * s) + T}
+             for (a, c), starts in VIDEO_STARTS.items() for s in starts]
+    return _write_cache(root, metas, truth)
+
+
+@pytest.fixture(scope="module")
+def stores(tmp_path_factory):
+    from implementation_phd_lab_vision_amd.feature_store import DeviceFeatureStore
+    base = tmp_path_factory.mktemp("dense")
+    roots = {"results": rd.make_results_cache(base / "results"), "overlap": _cache(base / "overlap", True),
+             "apart": _cache(base / "apart", False)}
+    return {k: DeviceFeatureStore(str(v), subjects=[9], test_set=True, device=DEV) for k, v in roots.items()}, roots
+
+
+@pytest.fixture(scope="module")
+def head(lib):
+    from implementation_phd_lab_vision_amd import results
+    from oracle import lifting_oracle as lo
+    return results.build_head(lo.synthetic_head_state_dict(1024, 2, seed=2), DEV)
+
+
+@pytest.mark.parametrize("which,fuse", [("results", "context"), ("overlap", "mean"), ("overlap", "context"), ("overlap", "last")])
+def test_evaluate_dense_stage_by_stage(lib, stores, head, which, fuse):
+    from implementation_phd_lab_vision_amd import protocols, sequences as sq
+    store = stores[0][which]
+    res = sq.evaluate_dense(head, store, fuse=fuse, keep_poses=True)
+    clips = store.item_clips()
+    table = ref.table(clips, T)
+    batch = store.get_batch(list(range(len(store))))
+    pred = head.joints(batch[0]).cpu().numpy()                                      # the device's own poses
+    gt = batch[1].to(torch.float32).cpu().numpy()
+    ramp = 1 + 4 * head.number_blocks
+    assert ramp == 9 and res["ramp"] == ramp and res["fuse"] == fuse
+    w_fused, w_gt, w_spread, w_gap = ref.stitch(pred, gt, table["offsets"], table["src"], sq.FUSE_MODES[fuse], ramp)
+    assert np.all(w_gap == 0.0)
+    _assert_within_one_ulp(res["pred"], w_fused, f"{which} {fuse} fused")
+    assert np.array_equal(res["gt"], w_gt)
+    assert np.all(np.abs(res["frame_spread"] - w_spread) <= 1e-6 * w_spread + 1e-6 * float(np.abs(pred).max()))
+    counts = np.diff(table["offsets"])
+    assert np.array_equal(res["count"], counts) and np.array_equal(res["frame_idx"], table["idx"])
+    assert np.array_equal(res["seq_start"], table["seq_start"]) and res["seq_keys"] == table["seq_keys"]
+    assert res["clip_frames"] == len(store) * T == int(counts.sum()) and res["multi_frames"] == int((counts >= 2).sum())
+    assert (res["multi_frames"] > 0) == (which == "overlap")
+
+    names = sorted({protocols.action_name(k[1]) for k in table["seq_keys"]})         # the metrics of the device's fused poses
+    assert res["group_names"] == names and (which != "overlap" or names == ["act0", "act1", "act2"])
+    group = np.array([names.index(protocols.action_name(table["seq_keys"][s][1])) for s in table["seq"]], dtype=np.int32)
+    want = ref.metrics(res["pred"], res["gt"], res["frame_spread"], table["offsets"], table["seq"], table["idx"], group, len(names))
+    assert np.array_equal(res["frames"], want[:, 0]) and res["frames_all"] == len(counts)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for key, num, den in (("p1", 1, 0), ("mpjve", 3, 2), ("accel", 5, 4), ("spread", 6, 0)):
+            per = want[:, num] / want[:, den]
+            assert np.allclose(res[key], per, rtol=1e-9, atol=0.0, equal_nan=True), key
+            assert np.isclose(res[key + "_all"], want[:, num].sum() / want[:, den].sum(), rtol=1e-9, atol=0.0), key
+            assert np.isclose(res[key + "_mean"], per[~np.isnan(per)].mean(), rtol=1e-9, atol=0.0), key
+
+    f, n_groups = len(counts), len(names)                                           # P2: the existing op, called directly
+    acc = torch.zeros(3 * n_groups, dtype=torch.float64, device=DEV)
+    protocols.add_protocol_sums(torch.from_numpy(res["pred"]).to(DEV).view(f, 1, 17, 3), torch.from_numpy(res["gt"]).to(DEV).view(f, 1, 17, 3),
+                                0, torch.from_numpy(group).to(DEV), n_groups, acc)
+    sums = acc.cpu().numpy()
+    assert np.array_equal(sums[2 * n_groups:], want[:, 0])
+    assert np.array_equal(res["p2"], sums[:2 * n_groups].reshape(n_groups, 2)[:, 1] / sums[2 * n_groups:])
+    assert np.allclose(res["p1"], sums[:2 * n_groups].reshape(n_groups, 2)[:, 0] / sums[2 * n_groups:], rtol=1e-9, atol=0.0)
+
+    ids = [names.index(protocols.action_name(a)) for a in store.item_actions()]     # the clip-wise errors by window position
+    clipwise = protocols.evaluate_protocols(head, store, ids, names)
+    assert res["position_p1"].shape == res["position_p2"].shape == (T,)
+    assert np.isclose(res["position_p1"].mean(), clipwise["recon_all"][0], rtol=1e-12, atol=0.0)
+    assert np.isclose(res["position_p2"].mean(), clipwise["recon_all"][1], rtol=1e-12, atol=0.0)
+
+
+@pytest.mark.parametrize("which", ["results", "overlap"])
+def test_evaluate_dense_in_chunks(lib, stores, head, which):
+    from implementation_phd_lab_vision_amd import sequences as sq
+    store = stores[0][which]
+    whole = sq.evaluate_dense(head, store, fuse="context", chunk_clips=8192, keep_poses=True)
+    parts = sq.evaluate_dense(head, store, fuse="context", chunk_clips=4, keep_poses=True)
+    assert len(sq.SequenceTable.from_clips(store.item_clips(), T).chunks(4)) > 1
+    for key in ("pred", "gt", "frame_spread"):
+        assert np.array_equal(whole[key].view(np.uint32), parts[key].view(np.uint32)), key
+    for key in ("count", "frame_idx", "seq_start", "frames"):
+        assert np.array_equal(whole[key], parts[key]), key
+    for key in ("p1", "p2", "mpjve", "accel", "spread", "position_p1", "position_p2"):
+        assert np.allclose(whole[key], parts[key], rtol=1e-12, atol=0.0, equal_nan=True), key
+    for key in ("p1_all", "p2_all", "mpjve_all", "accel_all", "spread_all", "p1_mean", "p2_mean"):
+        assert np.isclose(whole[key], parts[key], rtol=1e-12, atol=0.0), key
+
+
+def test_evaluate_dense_without_overlap_is_the_clipwise_evaluation(lib, stores, head):
+    from implementation_phd_lab_vision_amd import protocols, sequences as sq
+    store = stores[0]["apart"]
+    names, ids = protocols.action_groups(store.item_actions())
+    clipwise = protocols.evaluate_protocols(head, store, ids, names)
+    for fuse in ("mean", "context", "last"):
+        res = sq.evaluate_dense(head, store, fuse=fuse)
+        assert res["group_names"] == names and res["multi_frames"] == 0 and res["frames_all"] == res["clip_frames"]
+        assert np.array_equal(res["frames"], clipwise["clips"] * T)
+        assert np.allclose(res["p1"], clipwise["recon"][:, 0], rtol=1e-9, atol=0.0)
+        assert np.allclose(res["p2"], clipwise["recon"][:, 1], rtol=1e-9, atol=0.0)
+        assert res["spread_all"] == 0.0
+
+
+def test_evaluate_dense_refusals(lib, stores, head):
+    from implementation_phd_lab_vision_amd import sequences as sq
+    from implementation_phd_lab_vision_amd.feature_store import DeviceFeatureStore
+    with pytest.raises(ValueError, match="fuse"):
+        sq.evaluate_dense(head, stores[0]["overlap"], fuse="median")
+    with pytest.raises(ValueError, match="augment"):
+        sq.evaluate_dense(head, DeviceFeatureStore(str(stores[1]["overlap"]), subjects=[9], augment=True, device=DEV))
+    # overlapping clips whose shards disagree on a frame's ground truth: the results cache with one spelling of cam per video
+    class OneSpelling:
+        augment = False
+
+        def __init__(self, store):
+            self._store, self.feats = store, store.feats
+
+        def __len__(self):
+            return len(self._store)
+
+        def item_clips(self):
+            return [dict(c, cam=str(c["cam"])[-1]) for c in self._store.item_clips()]
+
+        def get_batch(self, idx):
+            return self._store.get_batch(idx)
+
+    with pytest.raises(ValueError, match="disagree"):
+        sq.evaluate_dense(head, OneSpelling(stores[0]["results"]))
+
+
+# ------------------------------------------------------------------ CLI -------------------------------------------------------------
+def test_cli_dense(lib, stores, tmp_path):
+    from implementation_phd_lab_vision_amd import results, sequences as sq
+    from oracle import lifting_oracle as lo
+    features = stores[1]["results"]
+    videos = rd.make_preprocessed_tree(tmp_path / "videos")
+    sd = lo.synthetic_head_state_dict(1024, 2, seed=2)
+    ckpt = tmp_path / "model.pt"
+    torch.save(sd, ckpt)
+    out, dense_out = tmp_path / "batch.npz", tmp_path / "sub" / "sequences.npz"
+    argv = ["--features_root", str(features), "--preprocessed_root", str(videos), "--model_path", str(ckpt), "--out", str(out),
+            "--seq-len", str(rd.SEQ_LEN), "--batch-size", "4", "--save-n", "2", "--video-size", "32", "--video-reader",
+            "tests.results_data:read_video", "--dense", "--dense-fuse", "last", "--dense-out", str(dense_out)]
+    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-m", "implementation_phd_lab_vision_amd.results", *argv],
+                       cwd=str(ROOT), env=env, capture_output=True, text=True)
+    assert r.returncode == 0, f"results exited {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    lines = [l for l in r.stdout.splitlines() if l.startswith("Dense |")]
+    store = stores[0]["results"]
+    table = sq.SequenceTable.from_clips(store.item_clips(), rd.SEQ_LEN)
+    assert len(lines) == 1 + 3 + 1 + 1 and "fuse last" in lines[0] and f"frames {table.frames} of {rd.N_S9 * rd.SEQ_LEN}" in lines[0]
+    assert all(any(l.startswith(f"Dense |   {a} |") for l in lines) for a in ("act0", "act1", "act2"))
+
+    z = np.load(out, allow_pickle=True)
+    dense_keys = {k for k in z.files if k.startswith("dense_")}
+    assert dense_keys == {"dense_actions", "dense_frames", "dense_fuse", "dense_counts", "dense_position_p1", "dense_position_p2"} | \
+        {f"dense_{m}{s}" for m in ("p1", "p2", "mpjve", "accel", "spread") for s in ("", "_all")}
+    assert set(z.files) - dense_keys == {"video", "joints3d", "predicted3djoints", "joints2d", "K", "meta", "test_metrics"}
+    assert z["dense_actions"].tolist() == ["act0", "act1", "act2"] and str(z["dense_fuse"]) == "last"
+    assert z["dense_counts"].tolist() == [len(table.seq_keys), table.frames, rd.N_S9 * rd.SEQ_LEN, int((np.diff(table.offsets) >= 2).sum())]
+    assert int(z["dense_frames"].sum()) == table.frames and z["dense_position_p1"].shape == (rd.SEQ_LEN,)
+    head = results.build_head(sd, DEV)
+    res = sq.evaluate_dense(head, store, fuse="last", keep_poses=True)
+    assert np.array_equal(z["dense_p1"], res["p1"].astype(np.float32)) and np.array_equal(z["dense_p2"], res["p2"].astype(np.float32))
+
+    e = np.load(dense_out)
+    assert set(e.files) == {"seq_keys", "seq_start", "frame_idx", "pred", "gt", "spread", "count"}
+    f = table.frames
+    assert e["seq_keys"].shape == (len(table.seq_keys), 3) and [tuple(k) for k in e["seq_keys"].tolist()] == [tuple(str(v) for v in k) for k in table.seq_keys]
+    assert np.array_equal(e["seq_start"], table.seq_start) and np.array_equal(e["frame_idx"], table.idx)
+    assert e["pred"].shape == e["gt"].shape == (f, 17, 3) and e["pred"].dtype == np.float32 and e["spread"].shape == e["count"].shape == (f,)
+    assert int(e["count"].sum()) == len(store) * rd.SEQ_LEN
+    assert np.array_equal(e["pred"], res["pred"]) and np.array_equal(e["gt"], res["gt"])
