@@ -121,7 +121,8 @@ int r50_forward_layer(r50_handle* h, const float* x_nchw_f32_dev, int n, const c
  * "tile" (force an igemm tile id for every conv, 0 = tuned table; also turns "fuse_tail" off),
  * measurement knobs, all results bit-identical: "inplace_out" (1 = plain-identity blocks write their output over their input;
  * default 0), and PROCESS-WIDE ones (they apply to every handle of the process): "cu_cap" (workgroups a persistent launch may use,
- * 0 = every CU; for pipelines that share the chip), "tail3_bp" (real pixels per tile of the chained layer3 tail, 0 = automatic), "use_g8" (the
+ * 0 = every CU; for pipelines that share the chip; tests/test_work_distribution_gpu.py holds every persistent kernel and the whole network to
+ * the uncapped bits under caps of 1 .. 100 workgroups), "tail3_bp" (real pixels per tile of the chained layer3 tail, 0 = automatic), "use_g8" (the
  * eight-phase GEMM tiles of gemm8p_kernel for the streaming 1x1 convs: 0 = never, 1 = on the shapes where they measured faster, the default,
  * 2 / 3 = wherever the shape fits, 256 / 224 pixels per tile), "use_s2" (0 = generic tiles for the stride-2 3x3 shapes) and "stem_strip"
  * (pooled-row pairs per strip of the fused stem kernel, 0 = chosen from the batch). */

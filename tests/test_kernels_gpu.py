@@ -18,14 +18,15 @@ def _dev():
     return torch.device("cuda", 0)
 
 
-def _check_bf16(dev_nhwc: torch.Tensor, ref_nchw: torch.Tensor, what: str):
+def _check_bf16(dev_nhwc: torch.Tensor, ref_nchw: torch.Tensor, what: str, mant: int = 7):
+    """The bar stated above; ``mant`` = 10 holds an fp16 tensor to one fp16 ulp instead (same absolute term, same counts)."""
     from oracle.resnet50_oracle import rel_l2
     got = dev_nhwc.float().cpu().permute(0, 3, 1, 2).contiguous()
     ref = ref_nchw.float()
     assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
     assert torch.isfinite(got).all(), f"{what}: non-finite output"
     diff = (got - ref).abs()
-    ulp = ref.abs() * 2.0 ** -7 + 2.0 ** -16 * max(1.0, float(ref.abs().max()))
+    ulp = ref.abs() * 2.0 ** -mant + 2.0 ** -16 * max(1.0, float(ref.abs().max()))
     bad = diff > ulp
     assert not bad.any(), f"{what}: {int(bad.sum())} elements beyond tolerance, max diff {float(diff.max())}"
     frac = float((diff > 0).float().mean())
@@ -91,25 +92,59 @@ def _tiles_for(cout, k=3, pad=1):
     return t + [x | ops.PERSISTENT for x in t if x != ops.TILE_AUTO] + ws
 
 
-@pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: "n%d_%dx%d_c%d-%d_k%ds%dp%d_r%d_res%d" % tuple(int(v) for v in c))
-def test_conv2d_matches_oracle(lib_built, case):
-    from implementation_phd_lab_vision_amd import ops
+def _conv_inputs(case, et=torch.bfloat16):
+    """Seeded inputs of one CONV_CASES row on the device (NHWC / OHWI) and the oracle's fused-op result (NCHW), in bf16 or fp16."""
     from oracle.resnet50_oracle import conv_bias_act_emulated
     n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    g = torch.Generator().manual_seed(hash(case) % (2 ** 31))
-    x = _rand_bf16((n, cin, h, w), g)
-    wt = _rand_bf16((cout, cin, k, k), g, scale=(2.0 / (cin * k * k)) ** 0.5)
+    f16 = et == torch.float16
+    g = torch.Generator().manual_seed(hash(case) % (2 ** 31) + (1 if f16 else 0))
+    x = (torch.randn((n, cin, h, w), generator=g)).to(et)
+    wt = (torch.randn((cout, cin, k, k), generator=g) * (2.0 / (cin * k * k)) ** 0.5).to(et)
     bias = torch.randn(cout, generator=g) * 0.1
     ho = (h + 2 * pad - k) // stride + 1
     wo = (w + 2 * pad - k) // stride + 1
-    res = _rand_bf16((n, cout, ho, wo), g) if has_res else None
+    res = torch.randn((n, cout, ho, wo), generator=g).to(et) if has_res else None
     ref = conv_bias_act_emulated(x.float(), wt.float(), bias, stride, pad, relu,
-                                 residual_bf=res.float() if has_res else None)
+                                 residual_bf=res.float() if has_res else None, fmt="fp16" if f16 else "bf16")
     d = _dev()
     xd = x.permute(0, 2, 3, 1).contiguous().to(d)
     wd = wt.permute(0, 2, 3, 1).contiguous().to(d)
     bd = bias.to(d)
     rd = res.permute(0, 2, 3, 1).contiguous().to(d) if has_res else None
+    return xd, wd, bd, rd, ref, (ho, wo)
+
+
+def _check_fp16(y: torch.Tensor, ref: torch.Tensor, what: str):
+    """The fp16 form of _check_bf16: one fp16 ulp + 2^-19 of scale per element, < 1 % of elements differing, rel-L2 < 2e-4."""
+    from oracle.resnet50_oracle import rel_l2
+    assert y.dtype == torch.float16
+    got = y.float().cpu().permute(0, 3, 1, 2)
+    diff = (got - ref).abs()
+    ulp = ref.abs() * 2.0 ** -10 + 2.0 ** -19 * max(1.0, float(ref.abs().max()))
+    assert torch.isfinite(got).all() and not (diff > ulp).any(), f"{what}: max diff {float(diff.max())}"
+    assert float((diff > 0).float().mean()) < 0.01 and rel_l2(got, ref) < 2e-4, what
+
+
+def _conv_tile_check(case, inputs, tile):
+    """One launch of a CONV_CASES row with tile id `tile` against the oracle, with a poisoned guard band behind the result; returns the output."""
+    from implementation_phd_lab_vision_amd import ops
+    n, h, w, cin, cout, k, stride, pad, relu, has_res = case
+    xd, wd, bd, rd, ref, (ho, wo) = inputs
+    # guard band behind the result: the tile rows past M (ragged last tile) must not be stored anywhere
+    numel = n * ho * wo * cout
+    buf = torch.full((numel + 512 * cout,), -7.0, dtype=xd.dtype, device=xd.device)
+    y = ops.conv2d_bf16(xd, wd, bd, stride=stride, pad=pad, relu=relu, residual=rd, tile=tile, out=buf)
+    torch.cuda.synchronize()
+    _check_bf16(y, ref, f"conv tile={tile}", 10 if xd.dtype == torch.float16 else 7)
+    assert bool((buf[numel:] == -7.0).all()), f"conv tile={tile}: wrote past the end of the output"
+    return y
+
+
+@pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: "n%d_%dx%d_c%d-%d_k%ds%dp%d_r%d_res%d" % tuple(int(v) for v in c))
+def test_conv2d_matches_oracle(lib_built, case):
+    from implementation_phd_lab_vision_amd import ops
+    n, h, w, cin, cout, k, stride, pad, relu, has_res = case
+    xd, wd, bd, rd, ref, (ho, wo) = _conv_inputs(case)
     tiles = _tiles_for(cout, k, pad)
     if n >= 64:                      # the big case is there for the tile STREAM of the persistent kernels: the small tiles add nothing
         tiles = [ops.TILE_AUTO, ops.TILE_256x256 | ops.PERSISTENT, ops.WS | 8, ops.TILE_G8, ops.TILE_G8_224]
@@ -120,13 +155,7 @@ def test_conv2d_matches_oracle(lib_built, case):
     if (k, stride, pad, has_res) == (3, 2, 1, False) and (h, w, cin, cout) in ((56, 56, 128, 128), (28, 28, 256, 256), (14, 14, 512, 512)):
         tiles = tiles + [ops.TILE_S2]
     for tile in tiles:
-        # guard band behind the result: the tile rows past M (ragged last tile) must not be stored anywhere
-        numel = n * ho * wo * cout
-        buf = torch.full((numel + 512 * cout,), -7.0, dtype=torch.bfloat16, device=d)
-        y = ops.conv2d_bf16(xd, wd, bd, stride=stride, pad=pad, relu=relu, residual=rd, tile=tile, out=buf)
-        torch.cuda.synchronize()
-        _check_bf16(y, ref, f"conv tile={tile}")
-        assert bool((buf[numel:] == -7.0).all()), f"conv tile={tile}: wrote past the end of the output"
+        _conv_tile_check(case, (xd, wd, bd, rd, ref, (ho, wo)), tile)
 
 
 G8_SHAPES = [   # n, h (= w), cin, cout, residual: the streaming 1x1 convs of layer3 / layer4 at batch 256 (+ a batch that leaves the last tile ragged)
@@ -164,6 +193,10 @@ def test_gemm8p_tiles_give_the_bits_of_the_generic_tiles(lib_built, shape, et):
 @pytest.mark.parametrize("shape", [(5, 7, 512), (3, 28, 128), (3, 14, 256), (70, 14, 256), (300, 14, 256), (260, 7, 512)],
                          ids=lambda v: "n%d_%dx%d_c%d" % (v[0], v[1], v[1], v[2]))
 def test_xres_kernel_is_batch_invariant_and_stays_inside_its_output(lib_built, shape):
+    _run_xres_batch_invariance(shape)
+
+
+def _run_xres_batch_invariance(shape):
     """conv3x3_xres_kernel (row blocks) with several tiles per workgroup (n = 300 at 14x14: 600 tiles on 256 CUs: the stream of weight stages and
     input chunks crosses tile borders) and with panels / cout tiles left ragged: every image's result is the same bits as when the image is run
     alone, the generic kernel agrees to the bf16 tolerance (its K order differs), and nothing is stored past the output (poisoned guard band).
@@ -186,11 +219,16 @@ def test_xres_kernel_is_batch_invariant_and_stays_inside_its_output(lib_built, s
     gen = ops.conv2d_bf16(x[:2].contiguous(), wt, bias, stride=1, pad=1, relu=True, tile=ops.WS | 8)
     d2 = (gen.float() - y[:2].float()).abs()
     assert float(d2.max()) <= 2.0 ** -6 * max(1.0, float(y[:2].float().abs().max())), float(d2.max())
+    return y
 
 
 @pytest.mark.parametrize("shape", [(1, 56, 128), (70, 56, 128), (300, 56, 128), (5, 28, 256), (300, 28, 256), (3, 14, 512), (300, 14, 512)],
                          ids=lambda v: "n%d_%dx%d_c%d" % (v[0], v[1], v[1], v[2]))
 def test_s2_kernel_is_batch_invariant_and_stays_inside_its_output(lib_built, shape):
+    _run_s2_batch_invariance(shape)
+
+
+def _run_s2_batch_invariance(shape):
     """conv3x3_s2_kernel with several tiles per workgroup (n = 300: 1,200 / 600 tiles on 256 CUs: the plane stream crosses tile borders,
     the loader re-decodes its offsets in mid-stream): every image's result is the same bits as when the image is run alone, and nothing
     is stored past the output (poisoned guard band)."""
@@ -210,11 +248,16 @@ def test_s2_kernel_is_batch_invariant_and_stays_inside_its_output(lib_built, sha
     for i in sorted({0, n // 2, n - 1}):
         alone = ops.conv2d_bf16(x[i:i + 1].contiguous(), wt, bias, stride=2, pad=1, relu=True, tile=ops.TILE_S2)
         assert torch.equal(alone[0], y[i]), f"image {i} of {n} differs from the same image run alone"
+    return y
 
 
 @pytest.mark.parametrize("chain", [False, True], ids=["last_block", "chained_conv1"])
 @pytest.mark.parametrize("n", [1, 3, 70])
 def test_bneck_block2_equals_unfused(lib_built, n, chain):
+    _run_bneck_block2(n, chain)
+
+
+def _run_bneck_block2(n, chain):
     """Layer2 bottleneck body in one launch (conv2 3x3 + conv3 + identity + ReLU [+ next conv1]): block output and next t1 are the
     same bits as the input-resident 3x3 launch followed by the 1x1 igemm launches (n = 70: 280 tiles, more than one per workgroup)."""
     from implementation_phd_lab_vision_amd import ops
@@ -238,11 +281,16 @@ def test_bneck_block2_equals_unfused(lib_built, n, chain):
         assert torch.equal(y1n, y1_ref), f"next conv1 differs: max |diff| {float((y1n.float() - y1_ref.float()).abs().max())}"
     else:
         assert y1n is None
+    return out, y1n
 
 
 @pytest.mark.parametrize("c1", [64, 128])
 @pytest.mark.parametrize("n", [1, 3, 20, 41])
 def test_bneck_block1_equals_unfused(lib_built, n, c1):
+    _run_bneck_block1(n, c1)
+
+
+def _run_bneck_block1(n, c1):
     """Layer1 bottleneck body in one launch: block output and next t1 are the same bits as the resident-weights 3x3 launch followed by
     the 1x1 igemm launches (n = 20: 280 tiles, more than one per workgroup; n = 41: 574 tiles, up to three per workgroup)."""
     from implementation_phd_lab_vision_amd import ops
@@ -263,10 +311,15 @@ def test_bneck_block1_equals_unfused(lib_built, n, c1):
     torch.cuda.synchronize()
     assert torch.equal(out, out_ref), f"block output differs: max |diff| {float((out.float() - out_ref.float()).abs().max())}"
     assert torch.equal(y1n, y1_ref), f"next conv1 differs: max |diff| {float((y1n.float() - y1_ref.float()).abs().max())}"
+    return out, y1n
 
 
 @pytest.mark.parametrize("n", [1, 3, 20, 41])
 def test_bneck_block1_downsample_equals_unfused(lib_built, n):
+    _run_bneck_block1_ds(n)
+
+
+def _run_bneck_block1_ds(n):
     """layer1.0's body in one launch (bneck_block1_kernel<.., DS>): the identity is the downsample conv of the block input, computed in the
     kernel and rounded to bf16 as the separate launch stores it.  Block output and next t1 are the same bits as the resident-weights 3x3 launch,
     the 1x1 downsample launch, the 1x1 conv3 launch with that identity, and the next 1x1 launch."""
@@ -291,12 +344,17 @@ def test_bneck_block1_downsample_equals_unfused(lib_built, n):
     torch.cuda.synchronize()
     assert torch.equal(out, out_ref), f"block output differs: max |diff| {float((out.float() - out_ref.float()).abs().max())}"
     assert torch.equal(y1n, y1_ref), f"next conv1 differs: max |diff| {float((y1n.float() - y1_ref.float()).abs().max())}"
+    return out, y1n
 
 
 @pytest.mark.parametrize("ds", [False, True], ids=["identity", "downsample"])
 @pytest.mark.parametrize("shape,c1", [((2, 7, 9), 64), ((1, 56, 56), 128), ((3, 5, 16), 64), ((5, 56, 56), 64)],
                          ids=lambda v: str(v).replace(" ", ""))
 def test_bneck_tail_matches_oracle_and_unfused(lib_built, shape, c1, ds):
+    _run_bneck_tail(shape, c1, ds)
+
+
+def _run_bneck_tail(shape, c1, ds):
     """Fused layer1 tail (conv3 + identity + ReLU, then the next conv1 + ReLU) against the oracle's two fused-op
     emulations chained, and bit-for-bit against the two igemm launches it replaces.  Pixel counts that are not a
     multiple of 16 exercise the descriptor-clamped last tile; a guard band checks nothing is stored past M."""
@@ -339,10 +397,15 @@ def test_bneck_tail_matches_oracle_and_unfused(lib_built, shape, c1, ds):
     y1_u = ops.conv2d_bf16(out_u, w1d.view(c1, 1, 1, 256), b1d, relu=True, tile=ops.TILE_64x128)
     assert torch.equal(out, out_u), "fused block output differs from the igemm launch it replaces"
     assert torch.equal(y1n, y1_u), "fused next-conv1 output differs from the igemm launch it replaces"
+    return out, y1n
 
 
 @pytest.mark.parametrize("shape", [(2, 7, 9), (1, 28, 28), (3, 5, 16), (9, 28, 28)], ids=lambda v: str(v).replace(" ", ""))
 def test_bneck_tail_layer2_shapes(lib_built, shape):
+    _run_bneck_tail_layer2(shape)
+
+
+def _run_bneck_tail_layer2(shape):
     """Fused layer2 tail (conv3 128->512 + identity + ReLU, next conv1 512->128 + ReLU; channels split over the waves,
     second conv reduced through LDS).  conv3's output must equal the igemm launch bit for bit; the second conv sums
     its K in eight slices, so it is held to the oracle under the bf16 tolerance."""
@@ -369,6 +432,7 @@ def test_bneck_tail_layer2_shapes(lib_built, shape):
     _check_bf16(y1n, y1_ref, "bneck_tail2 y1n")
     out_u = ops.conv2d_bf16(y2d, w3d.view(512, 1, 1, 128), b3d, relu=True, residual=idd, tile=ops.TILE_64x128)
     assert torch.equal(out, out_u), "fused block output differs from the igemm launch it replaces"
+    return out, y1n
 
 
 def _tail3_inputs(n, h, w, seed):
@@ -385,6 +449,14 @@ def _tail3_inputs(n, h, w, seed):
 @pytest.mark.parametrize("shape,bp", [((2, 7, 9), 0), ((1, 14, 14), 0), ((3, 14, 14), 112), ((3, 14, 14), 98), ((20, 14, 14), 7), ((5, 14, 14), 33)],
                          ids=lambda v: str(v).replace(" ", ""))
 def test_bneck_tail_layer3_shapes(lib_built, shape, bp, monkeypatch):
+    if bp:
+        monkeypatch.setenv("R50_TAIL3_BP", str(bp))
+    else:
+        monkeypatch.delenv("R50_TAIL3_BP", raising=False)
+    _run_bneck_tail_layer3(shape, bp)
+
+
+def _run_bneck_tail_layer3(shape, bp):
     """Chained layer3 tail (conv3 256->1024 + identity + ReLU, next conv1 1024->256 + ReLU; weights streamed through the LDS ring,
     the residual as one more K-step against an identity operand, the block output handed to the second GEMM through LDS).
     Against the oracle's two fused-op emulations, and BIT FOR BIT against the two igemm launches it replaces (same summation
@@ -399,10 +471,6 @@ def test_bneck_tail_layer3_shapes(lib_built, shape, bp, monkeypatch):
     idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
     w3d, w1d = w3.view(1024, 256).contiguous().to(d), w1.view(256, 1024).contiguous().to(d)
     b3d, b1d = b3.to(d), b1.to(d)
-    if bp:
-        monkeypatch.setenv("R50_TAIL3_BP", str(bp))
-    else:
-        monkeypatch.delenv("R50_TAIL3_BP", raising=False)
     m = n * h * w
     guard = 4096                                   # poisoned rows behind both outputs: nothing may be stored past M
     out_buf = torch.full((m + guard, 1024), -7.0, dtype=torch.bfloat16, device=d)
@@ -419,6 +487,7 @@ def test_bneck_tail_layer3_shapes(lib_built, shape, bp, monkeypatch):
         _check_bf16(out, out_ref, "bneck_tail3 out")
         y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True)
         _check_bf16(y1n, y1_ref, "bneck_tail3 y1n")
+    return out, y1n
 
 
 def test_bneck_tail_layer3_batch256_equals_unfused(lib_built, monkeypatch):
@@ -439,6 +508,10 @@ def test_bneck_tail_layer3_batch256_equals_unfused(lib_built, monkeypatch):
 
 @pytest.mark.parametrize("n", [1, 3, 37, 256], ids=lambda v: "n%d" % v)
 def test_bneck_cat_chain_equals_the_two_launches(lib_built, n):
+    _run_bneck_cat_chain(n)
+
+
+def _run_bneck_cat_chain(n):
     """layer2.0's transition tail chained with layer2.1.conv1 (bneck_catchain_kernel): conv3 + downsample as one conv over K = [t2 | x at
     stride 2] + ReLU, then the next 1x1 + ReLU out of LDS -- BIT FOR BIT the two-source igemm launch followed by the 1x1 igemm launch it
     replaces (n = 1 / 3: fewer tiles than CUs, ragged tiles; 37: full tiles + a ragged one; 256: the benchmarked 1792 tiles, 7 per workgroup),
@@ -471,10 +544,15 @@ def test_bneck_cat_chain_equals_the_two_launches(lib_built, n):
         _check_bf16(out, ref, "bneck_cat_chain out")
         y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True)
         _check_bf16(y1n, y1_ref, "bneck_cat_chain y1n")
+    return out, y1n
 
 
 @pytest.mark.parametrize("n", [1, 5, 256], ids=lambda v: "n%d" % v)
 def test_layer3_last_block_conv3_through_the_pipelined_tail(lib_built, n):
+    _run_layer3_last_block(n)
+
+
+def _run_layer3_last_block(n):
     """layer3.5: conv3 + identity + ReLU through bneck_tail3p_kernel<.., NOB> (no second GEMM; group B only copies out_c out) -- bit for bit the
     igemm launch with a residual it replaces; nothing written past M."""
     from implementation_phd_lab_vision_amd import ops
@@ -486,6 +564,7 @@ def test_layer3_last_block_conv3_through_the_pipelined_tail(lib_built, n):
     out = ops.conv3_identity_tail3_bf16(y2d, w3d, b3d, idd)
     out_u = ops.conv2d_bf16(y2d, w3d.view(1024, 1, 1, 256), b3d, relu=True, residual=idd)
     assert torch.equal(out, out_u)
+    return out
 
 
 FP16_CASES = [CONV_CASES[i] for i in (1, 2, 3, 5, 6, 10, 12)]
@@ -496,22 +575,8 @@ def test_conv2d_fp16_matches_oracle(lib_built, case):
     """The same kernels with IEEE half as the element type (R50_PREC_FP16), every tile variant: within one fp16 ulp of
     the oracle's fused-op emulation with fp16 rounding points."""
     from implementation_phd_lab_vision_amd import ops
-    from oracle.resnet50_oracle import conv_bias_act_emulated, rel_l2
     n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    g = torch.Generator().manual_seed(hash(case) % (2 ** 31) + 1)
-    x = (torch.randn((n, cin, h, w), generator=g)).to(torch.float16)
-    wt = (torch.randn((cout, cin, k, k), generator=g) * (2.0 / (cin * k * k)) ** 0.5).to(torch.float16)
-    bias = torch.randn(cout, generator=g) * 0.1
-    ho = (h + 2 * pad - k) // stride + 1
-    wo = (w + 2 * pad - k) // stride + 1
-    res = torch.randn((n, cout, ho, wo), generator=g).to(torch.float16) if has_res else None
-    ref = conv_bias_act_emulated(x.float(), wt.float(), bias, stride, pad, relu,
-                                 residual_bf=res.float() if has_res else None, fmt="fp16")
-    d = _dev()
-    xd = x.permute(0, 2, 3, 1).contiguous().to(d)
-    wd = wt.permute(0, 2, 3, 1).contiguous().to(d)
-    bd = bias.to(d)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(d) if has_res else None
+    xd, wd, bd, rd, ref, _ = _conv_inputs(case, torch.float16)
     tiles = _tiles_for(cout, k, pad)
     if n >= 64:                      # the big case is there for the tile STREAM of the persistent kernels: the small tiles add nothing
         tiles = [ops.TILE_AUTO, ops.TILE_256x256 | ops.PERSISTENT, ops.WS | 8, ops.TILE_G8, ops.TILE_G8_224]
@@ -519,12 +584,7 @@ def test_conv2d_fp16_matches_oracle(lib_built, case):
         tiles = tiles + [ops.TILE_C64]
     for tile in tiles:
         y = ops.conv2d_bf16(xd, wd, bd, stride=stride, pad=pad, relu=relu, residual=rd, tile=tile)
-        assert y.dtype == torch.float16
-        got = y.float().cpu().permute(0, 3, 1, 2)
-        diff = (got - ref).abs()
-        ulp = ref.abs() * 2.0 ** -10 + 2.0 ** -19 * max(1.0, float(ref.abs().max()))
-        assert torch.isfinite(got).all() and not (diff > ulp).any(), f"fp16 conv tile={tile}: max diff {float(diff.max())}"
-        assert float((diff > 0).float().mean()) < 0.01 and rel_l2(got, ref) < 2e-4, f"fp16 conv tile={tile}"
+        _check_fp16(y, ref, f"fp16 conv tile={tile}")
 
 
 def test_conv2d_fp16_saturates_instead_of_overflowing(lib_built):
@@ -619,6 +679,10 @@ CAT_CASES = [   # n, h (= w) of the output, c1, h2 (= w2) of the second source, 
 @pytest.mark.parametrize("et", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("case", CAT_CASES, ids=lambda c: "n%d_%dx%d_c%d_src%d_c%d_s%d_o%d_r%d_t%d" % (c[0], c[1], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]))
 def test_conv1x1_two_k_sources(lib_built, case, et):
+    _run_conv1x1_cat(case, et)
+
+
+def _run_conv1x1_cat(case, et):
     """One 1x1 conv over K = [x1 | x2 at stride2] (conv3 + downsample + add + ReLU of a stage's first bottleneck) against a wide
     accumulation of the same sum; a poisoned guard band behind the output must stay untouched."""
     import torch.nn.functional as F
@@ -645,6 +709,7 @@ def test_conv1x1_two_k_sources(lib_built, case, et):
         ops.conv1x1_cat(x1.to("cuda:0"), x2.to("cuda:0"), s2 + 1, wcat.to("cuda:0"), bias.to("cuda:0"))      # geometry mismatch
     with pytest.raises(Exception):
         ops.conv1x1_cat(x1.to("cuda:0"), x2.to("cuda:0"), s2, wcat.to("cuda:0"), bias.to("cuda:0"), tile=1)  # not a role-specialised tile
+    return y
 
 
 FP8_CASES = [   # n, h, w, cin, cout, k, stride, pad, relu, residual, tile
@@ -660,6 +725,10 @@ FP8_CASES = [   # n, h, w, cin, cout, k, stride, pad, relu, residual, tile
 
 @pytest.mark.parametrize("case", FP8_CASES, ids=lambda c: "n%d_%dx%d_c%d_o%d_k%d_s%d_p%d_r%d_res%d_t%d" % tuple(int(v) for v in c))
 def test_conv2d_fp8(lib_built, case):
+    _run_conv2d_fp8(case)
+
+
+def _run_conv2d_fp8(case):
     """fp8 (e4m3) conv on the K = 128 scaled MFMA (BASELINE configs[4], kernel level) against a wide accumulation of the same
     quantised operands, requantised with torch's round-to-nearest-even fp8 conversion."""
     import torch.nn.functional as F
@@ -691,3 +760,4 @@ def test_conv2d_fp8(lib_built, case):
     assert float(got.abs().max()) > 1.0                       # a real signal, not all zeros
     with pytest.raises(Exception):
         ops.conv2d_fp8(xq.to("cuda:0")[..., :64].contiguous(), sx, wq.to("cuda:0")[..., :64].contiguous(), sw, bias.to("cuda:0"), sy)   # cin % 128
+    return y
