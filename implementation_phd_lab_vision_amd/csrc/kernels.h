@@ -3917,6 +3917,24 @@ __global__ __launch_bounds__(256) void cast_rows_kernel(const float* __restrict_
     }
 }
 
+// Windows of one fp32 feature matrix -> element rows: dst row w*t + i = cast(src row starts[w] + i), cast_rows_kernel's rounding.
+// One item = 8 columns: two 16-byte loads (32 contiguous bytes per lane, a wave covers 2 KiB of one row) and one 16-byte store
+// (a wave stores 1 KiB contiguous).  Overlapping windows re-read their rows from L2.  starts is trusted (checked on the host).
+template <int ET>
+__global__ __launch_bounds__(256) void gather_window_rows_kernel(const float* __restrict__ src, const int* __restrict__ starts,
+                                                                 unsigned short* __restrict__ dst, unsigned items, unsigned t, unsigned c8) {
+    // items = b * t * c8 < 2^31 (checked by the launcher): the index arithmetic, two divisions per item, stays in 32 bits
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < items; i += gridDim.x * 256u) {
+        const unsigned r = i / c8, g = i - r * c8;
+        const unsigned w = r / t;
+        const long long srow = (long long)starts[w] + (r - w * t);
+        const float4* p = reinterpret_cast<const float4*>(src + (srow * c8 + g) * 8);
+        const float4 lo = p[0], hi = p[1];
+        const u32x4 o = (u32x4){pack2_e<ET>(lo.x, lo.y), pack2_e<ET>(lo.z, lo.w), pack2_e<ET>(hi.x, hi.y), pack2_e<ET>(hi.z, hi.w)};
+        *reinterpret_cast<u32x4*>(dst + (size_t)i * 8) = o;
+    }
+}
+
 // [phi (rows, d) element | y (rows, ny) fp32 | zeros] -> (rows, dp) element: the regressor's input torch.cat([phi, y]) (:113)
 template <int ET>
 __global__ __launch_bounds__(256) void concat_pad_kernel(const unsigned short* __restrict__ phi, int d, const float* __restrict__ y,
@@ -4773,6 +4791,23 @@ __global__ __launch_bounds__(64 * STITCH_WAVES) void stitch_poses_kernel(const f
     if (lane == 0) {
         spread[f] = (float)sqrt(ss / ((double)J * (double)n));
         gt_gap[f] = (float)gap;
+    }
+}
+
+// Flip test-time augmentation, the merge: out[r,j,k] = 0.5 * (a[r,j,k] + s_k * b[r,perm[j],k]), s = (-1, 1, 1): b holds the poses of the
+// mirrored frames, and negating x and swapping the left/right joints (perm, its own inverse; trusted, checked on the host) takes them
+// back.  One add and one multiply, each rounded on its own: the bits of the torch expression.  A thread reads a[i] before it writes
+// out[i] and nothing else of out, so out may be a.
+__global__ __launch_bounds__(256) void merge_mirrored_poses_kernel(const float* a, const float* __restrict__ b,
+                                                                   const int* __restrict__ perm, float* out, long long rows, int joints) {
+    const int row = joints * 3;
+    const long long total = rows * row;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / row;
+        const int e = (int)(i - r * row);
+        const int j = e / 3, k = e - j * 3;
+        const float m = b[r * row + perm[j] * 3 + k];
+        out[i] = __fmul_rn(0.5f, __fadd_rn(a[i], k == 0 ? -m : m));
     }
 }
 

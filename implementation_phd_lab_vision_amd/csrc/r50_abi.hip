@@ -2503,6 +2503,32 @@ int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int jo
     return ew_done("r50_op_stitch_poses");
 }
 
+int r50_op_gather_window_rows(const float* src, int64_t src_rows, int c, const int* starts, int b, int t, void* dst, int et, void* stream) {
+    if (!src || !starts || !dst) return fail(nullptr, R50_ERR_INVALID, "r50_op_gather_window_rows: null pointer");
+    if (b < 1 || t < 1 || c < 8 || c % 8 != 0 || src_rows < t || src_rows > INT32_MAX || (et != 0 && et != 1) ||
+        ((uintptr_t)src & 15) || ((uintptr_t)dst & 15) || (long long)b * t > INT32_MAX / (c / 8))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_gather_window_rows: invalid arguments (need b >= 1, 1 <= t <= src_rows < 2^31, "
+                                              "c a positive multiple of 8, b * t * c / 8 < 2^31, et in {0,1}, src and dst 16-byte aligned)");
+    const long long items = (long long)b * t * (c / 8);
+    R50_ET_LAUNCH(gather_window_rows_kernel, dim3(ew_grid(items)), dim3(256), stream, src, starts, (unsigned short*)dst, (unsigned)items,
+                  (unsigned)t, (unsigned)(c / 8));
+    return ew_done("r50_op_gather_window_rows");
+}
+
+int r50_op_merge_mirrored_poses(const float* a, const float* b_mirrored, int64_t rows, int joints, const int* perm, float* out,
+                                void* stream) {
+    if (!a || !b_mirrored || !perm || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_merge_mirrored_poses: null pointer");
+    if (rows < 1 || joints < 1 || joints > 64 || rows > INT64_MAX / (3 * 64))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_merge_mirrored_poses: invalid arguments (need rows >= 1 and 1 <= joints <= 64)");
+    const long long bytes = (long long)rows * joints * 3 * (long long)sizeof(float);
+    const char *o0 = (const char*)out, *b0 = (const char*)b_mirrored, *a0 = (const char*)a;
+    if ((o0 < b0 + bytes && b0 < o0 + bytes) || (o0 != a0 && o0 < a0 + bytes && a0 < o0 + bytes))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_merge_mirrored_poses: out overlaps an input (it may be exactly a, nothing else)");
+    hipLaunchKernelGGL(merge_mirrored_poses_kernel, dim3(ew_grid((long long)rows * joints * 3)), dim3(256), 0, (hipStream_t)stream, a,
+                       b_mirrored, perm, out, (long long)rows, joints);
+    return ew_done("r50_op_merge_mirrored_poses");
+}
+
 int r50_op_sequence_metrics(const float* fused, const float* gt, const float* spread, const int* offsets, const int* seq, const int* idx,
                             const int* group, int frames, int joints, int root, int n_groups, double* part, int n_blocks, void* stream) {
     if (!fused || !gt || !spread || !offsets || !seq || !idx || !group || !part)

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -61,6 +62,53 @@ def expected_keys(latent_dim: int, joints_num: int, number_blocks: int) -> Dict[
     keys["f_3D.mlp.5.weight"] = (o, _REG_HIDDEN)
     keys["f_3D.mlp.5.bias"] = (o,)
     return keys
+
+
+def checked_window_starts(starts, src_rows: int, t: int) -> np.ndarray:
+    """``starts`` (a host sequence or a 1-D integer tensor, read back if it lives on the device) as a contiguous int32 host array, after
+    the check ``r50_op_gather_window_rows`` leaves to its caller: at least one start, ``1 <= t <= src_rows`` and every start in
+    ``[0, src_rows - t]``.  Raises ValueError otherwise; touches neither the library nor the GPU when ``starts`` is on the host."""
+    host = starts.detach().cpu().numpy() if isinstance(starts, torch.Tensor) else np.asarray(starts)
+    if host.ndim != 1 or host.size < 1 or host.dtype.kind not in "iu":
+        raise ValueError(f"starts must be a non-empty 1-D integer sequence, got {host.dtype} {host.shape}")
+    if not 1 <= int(t) <= int(src_rows):
+        raise ValueError(f"need 1 <= t <= src_rows (got t={t}, src_rows={src_rows})")
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi > int(src_rows) - int(t):
+        raise ValueError(f"every start must lie in [0, {int(src_rows) - int(t)}] (windows of {t} rows in {src_rows}), got [{lo}, {hi}]")
+    return np.ascontiguousarray(host, dtype=np.int32)
+
+
+def gather_window_rows(src: torch.Tensor, starts, t: int, dtype: torch.dtype = torch.float16,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ``r50_op_gather_window_rows`` launch: ``src`` (N, C) fp32 on an MI355X, ``starts`` B window starts (host sequence or int32
+    device tensor) -> (B*t, C) ``dtype`` (fp16 or bf16), row ``w*t + i`` = the cast of ``src[starts[w] + i]``: the bits of
+    ``r50_op_cast_rows`` on ``src[idx]`` without that fp32 intermediate.  The starts are checked on the host before anything else
+    (the kernel trusts them): a device tensor of starts is read back for that, one blocking device-to-host copy per call, so pass a host
+    sequence where the starts are known on the host.  ``out``: an optional contiguous (B*t, C) destination.  There is no CPU fallback."""
+    if src.dim() != 2 or src.dtype != torch.float32:
+        raise ValueError(f"src must be (N, C) fp32, got {tuple(src.shape)} {src.dtype}")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+    n, c = int(src.shape[0]), int(src.shape[1])
+    if c < 8 or c % 8:
+        raise ValueError(f"C must be a positive multiple of 8, got {c}")
+    host = checked_window_starts(starts, n, t)
+    b, t = int(host.size), int(t)
+    if not src.is_cuda or not src.is_contiguous():
+        raise ValueError("src must be contiguous on the GPU: there is no CPU fallback")
+    dev_starts = starts if isinstance(starts, torch.Tensor) and starts.device == src.device and starts.dtype == torch.int32 \
+        and starts.is_contiguous() else torch.from_numpy(host).to(src.device)
+    if out is None:
+        out = torch.empty((b * t, c), dtype=dtype, device=src.device)
+    elif tuple(out.shape) != (b * t, c) or out.dtype != dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous ({b * t}, {c}) {dtype} tensor on {src.device}")
+    with torch.cuda.device(src.device):
+        rc = _lib.load_library().r50_op_gather_window_rows(src.data_ptr(), n, c, dev_starts.data_ptr(), b, t, out.data_ptr(),
+                                                           1 if dtype == torch.float16 else 0,
+                                                           torch.cuda.current_stream(src.device).cuda_stream)
+    _lib.check(rc, None, "r50_op_gather_window_rows")
+    return out
 
 
 class PHDFor3DJoints:
@@ -269,6 +317,27 @@ class PHDFor3DJoints:
             x0 = torch.empty((b * t, 2048), dtype=self._dtype, device=self._device)
             _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * t, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None,
                        "r50_op_cast_rows")
+            x = self._gemm(x0, "input_proj", relu=False)
+            phi = self._temporal_net(x, b, t, "f_movie", self.number_blocks)
+            return self._regressor(phi, b, t)
+
+    def joints_windows(self, feats_nd: torch.Tensor, starts, t: int) -> torch.Tensor:
+        """``joints`` over B windows of ONE feature matrix: ``feats_nd`` (N, 2048) fp32 on the head's device,
+        ``starts`` B window starts (an int32 device tensor or a host sequence, each in ``[0, N - t]``, checked on the host) -> (B, t, J, 3)
+        fp32.  One ``r50_op_gather_window_rows`` launch takes the place of ``feats_nd[idx]`` (a (B, t, 2048) fp32 copy) and the
+        ``r50_op_cast_rows`` launch on it; the launches after it are those of ``joints``, so the result is bit-equal to
+        ``joints(feats_nd[idx])`` with ``idx[w, i] = starts[w] + i``.  The host check of a DEVICE tensor of starts reads it back first (one
+        blocking device-to-host copy per call); a host sequence costs no synchronisation."""
+        if self._device is None or not self._dev:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') before running the head")
+        if feats_nd.dim() != 2 or feats_nd.shape[-1] != 2048 or feats_nd.dtype != torch.float32:
+            raise ValueError(f"expected (N,2048) fp32 features, got {tuple(feats_nd.shape)} {feats_nd.dtype}")
+        if feats_nd.device != self._device:
+            raise ValueError(f"features are on {feats_nd.device}, head on {self._device}")
+        t = int(t)
+        with torch.cuda.device(self._device):
+            x0 = gather_window_rows(feats_nd.contiguous(), starts, t, self._dtype)
+            b = x0.shape[0] // t
             x = self._gemm(x0, "input_proj", relu=False)
             phi = self._temporal_net(x, b, t, "f_movie", self.number_blocks)
             return self._regressor(phi, b, t)

@@ -1,0 +1,432 @@
+"""Decoded video in, one 3D pose per frame out: the backbone and the lifting head run as one pass.
+
+Every other entry point of the head (``results``, ``evaluate_dense``, ``rollout``, ``render``) reads a Human3.6M feature cache with
+ground truth.  This one takes the frames of any video and a trained ``best.pt``:
+
+    host:    one crop box for the whole video; per chunk the box region of the frames, sliced on the host and uploaded pinned
+    device:  crop_and_resize_video_uint8 -> features_u8          every frame through the backbone ONCE -> feats (N, 2048) fp32
+             joints_windows (r50_op_gather_window_rows + head)   the head's windows (40 frames, stride 5) are views of feats
+             [flip TTA: the same on the mirrored crops, then r50_op_merge_mirrored_poses]
+             stitch_poses                                        the overlapping windows fused into one pose per frame
+             rollout                                             optionally, poses beyond the last frame
+
+A feature cache holds a frame once per clip that covers it, each time under that clip's own crop box; here there is ONE box per video
+(given, or from the 2D joints of all kept frames, or the centred square), so the features of a frame do not depend on the window it
+is read through.  That is a stated deviation from the cache; a per-window box is not offered.
+
+* ``window_starts``            where the windows begin (host).
+* ``merge_mirrored_poses``     the ctypes wrapper of the merge op; ``gather_window_rows`` (model.py) is the other new op.
+* ``VideoPredictor``           ``features`` / ``poses`` / ``forecast`` / ``predict``.
+* ``python -m implementation_phd_lab_vision_amd.predict --frames clip.npy --model_path best.pt --weights resnet50.pth --out DIR``
+
+Video decoding and person detection stay upstream: the input is decoded uint8 frames.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import frames as F
+from .model import gather_window_rows  # noqa: F401  (the pass's other op, re-exported beside merge_mirrored_poses)
+from .protocols import MAX_JOINTS
+from .sequences import FUSE_MODES, SequenceTable, StitchIndex, stitch_poses
+
+FEATURE_DIM = 2048
+OUT_SIZE = 224
+UPLOAD_BYTES = 64 << 20          # pinned staging buffer: the box regions travel in pieces of at most this many bytes
+RESIZE_MODES = {"float": F.RESIZE_FLOAT, "fixed": F.RESIZE_FIXED}
+
+
+# ---- windows ------------------------------------------------------------------------------------------------------------------------
+def window_starts(n: int, seq_len: int, stride: int) -> np.ndarray:
+    """Starts (int32) of the windows over ``n`` frames: ``0, stride, 2 stride, ...`` while a whole window of ``seq_len`` frames fits,
+    plus ``n - seq_len`` if that is not the last of them already, so every frame is covered.  A video shorter than ``seq_len`` is one
+    window of its ``n`` frames (start 0; the window length is ``min(n, seq_len)``)."""
+    n, seq_len, stride = int(n), int(seq_len), int(stride)
+    if n < 1 or seq_len < 1 or stride < 1:
+        raise ValueError(f"need n, seq_len, stride >= 1 (got {n}, {seq_len}, {stride})")
+    if n <= seq_len:
+        return np.zeros(1, dtype=np.int32)
+    starts = list(range(0, n - seq_len + 1, stride))
+    if starts[-1] != n - seq_len:
+        starts.append(n - seq_len)
+    return np.asarray(starts, dtype=np.int32)
+
+
+def window_clips(starts: Sequence[int], t: int, name: str = "video") -> List[dict]:
+    """The windows as index entries of one sequence, what ``SequenceTable.from_clips`` reads."""
+    return [{"subject": 0, "action": str(name), "cam": "0", "start": int(s), "end": int(s) + int(t)} for s in starts]
+
+
+# ---- flip test-time augmentation: the merge ---------------------------------------------------------------------------------------------
+def flip_perm(joints: int, pairs: Sequence[Tuple[int, int]] = F.H36M_FLIP_PAIRS) -> np.ndarray:
+    """The left/right swap as a permutation of ``joints`` indices (int32): the identity with every pair exchanged."""
+    perm = np.arange(int(joints), dtype=np.int32)
+    for l_idx, r_idx in pairs:
+        if not (0 <= l_idx < joints and 0 <= r_idx < joints):
+            raise ValueError(f"flip pair ({l_idx}, {r_idx}) does not fit a skeleton of {joints} joints")
+        perm[l_idx], perm[r_idx] = r_idx, l_idx
+    return perm
+
+
+class MirrorPerm:
+    """A joint permutation checked on the host -- the kernel trusts it -- and uploaded once: 1-D, at most ``MAX_JOINTS`` entries, every
+    entry in range, and its own inverse (``perm[perm[j]] == j``: swapping left and right twice changes nothing)."""
+
+    def __init__(self, perm, device):
+        host = np.asarray(perm.detach().cpu().numpy() if isinstance(perm, torch.Tensor) else perm)
+        if host.ndim != 1 or host.dtype.kind not in "iu" or not 1 <= host.size <= MAX_JOINTS:
+            raise ValueError(f"perm must be a 1-D integer sequence of 1 .. {MAX_JOINTS} joints, got {host.dtype} {host.shape}")
+        host = host.astype(np.int64)
+        if int(host.min()) < 0 or int(host.max()) >= host.size:
+            raise ValueError(f"every perm entry must lie in [0, {host.size}), got [{int(host.min())}, {int(host.max())}]")
+        if not np.array_equal(host[host], np.arange(host.size)):
+            raise ValueError("perm must be its own inverse (perm[perm[j]] == j): a left/right swap")
+        self.joints = int(host.size)
+        self.perm = torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def merge_mirrored_poses(a: torch.Tensor, b_mirrored: torch.Tensor, perm: Union[MirrorPerm, Sequence[int]],
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ``r50_op_merge_mirrored_poses`` launch: ``a`` (R, J, 3) fp32 poses of the frames, ``b_mirrored`` (R, J, 3) the poses of the
+    mirrored frames -> ``0.5 * (a + M(b_mirrored))`` with ``M`` = negate x, swap left and right (``perm``: a ``MirrorPerm`` or the
+    sequence to make one from): the inverse of ``frames.aug_hflip_annotations``.  The bits of that torch expression.  ``out`` may be
+    ``a``.  Everything is checked on the host before the launch.  There is no CPU fallback."""
+    if a.dim() != 3 or a.shape[2] != 3 or tuple(b_mirrored.shape) != tuple(a.shape) or a.dtype != torch.float32 \
+            or b_mirrored.dtype != torch.float32 or a.shape[0] < 1:
+        raise ValueError(f"a and b_mirrored (R,J,3) fp32 with R >= 1 expected, got {tuple(a.shape)} {a.dtype}, "
+                         f"{tuple(b_mirrored.shape)} {b_mirrored.dtype}")
+    if not isinstance(perm, MirrorPerm):
+        perm = MirrorPerm(perm, a.device)
+    rows, joints = int(a.shape[0]), int(a.shape[1])
+    if perm.joints != joints:
+        raise ValueError(f"perm has {perm.joints} joints, the poses {joints}")
+    if out is None:
+        out = torch.empty_like(a)
+    every = (a, b_mirrored, out)
+    if tuple(out.shape) != tuple(a.shape) or out.dtype != torch.float32:
+        raise ValueError(f"out must be {tuple(a.shape)} fp32, got {tuple(out.shape)} {out.dtype}")
+    if a.device.type != "cuda" or any(v.device != a.device for v in every) or perm.perm.device != a.device:
+        raise ValueError("a, b_mirrored, out and perm must be on one GPU: there is no CPU fallback")
+    if not all(v.is_contiguous() for v in every):
+        raise ValueError("a, b_mirrored and out must be contiguous")
+    with torch.cuda.device(a.device):
+        rc = _lib.load_library().r50_op_merge_mirrored_poses(a.data_ptr(), b_mirrored.data_ptr(), rows, joints, perm.perm.data_ptr(),
+                                                             out.data_ptr(), torch.cuda.current_stream(a.device).cuda_stream)
+    _lib.check(rc, None, "r50_op_merge_mirrored_poses")
+    return out
+
+
+# ---- the crop box -------------------------------------------------------------------------------------------------------------------------
+def centred_square(img_h: int, img_w: int) -> torch.Tensor:
+    """``[top, left, side, side]`` int64: the centred square of the shorter side."""
+    side = min(int(img_h), int(img_w))
+    return torch.tensor([(int(img_h) - side) // 2, (int(img_w) - side) // 2, side, side], dtype=torch.int64)
+
+
+def choose_box(img_h: int, img_w: int, box=None, joints2d=None) -> torch.Tensor:
+    """The video's one crop box ``[top, left, hh, ww]`` int64, in order of precedence: ``box`` as given (it must lie inside the image);
+    ``frames.square_crop_from_2d`` over ``joints2d`` (the 2D joints of all kept frames); the centred square of the shorter side."""
+    if box is not None:
+        out = torch.as_tensor(box.tolist() if isinstance(box, (torch.Tensor, np.ndarray)) else list(box), dtype=torch.int64).reshape(-1)
+        if out.numel() != 4:
+            raise ValueError(f"box must be [top, left, hh, ww], got {out.tolist()}")
+        top, left, hh, ww = out.tolist()
+        if top < 0 or left < 0 or hh < 1 or ww < 1 or top + hh > img_h or left + ww > img_w:
+            raise ValueError(f"box {out.tolist()} does not lie inside a {img_h} x {img_w} image")
+        return out
+    if joints2d is not None:
+        return F.square_crop_from_2d(torch.as_tensor(np.asarray(joints2d), dtype=torch.float32), int(img_h), int(img_w))
+    return centred_square(img_h, img_w)
+
+
+# ---- the pass ---------------------------------------------------------------------------------------------------------------------------------
+class VideoPredictor:
+    """``backbone``: a ``ResNet50Backbone`` and ``head``: a ``PHDFor3DJoints``, both on one MI355X.  ``seq_len`` / ``stride``: the head's
+    windows (the features CLI's defaults, what heads are trained on); ``fuse``: how ``stitch_poses`` weighs a frame's windows
+    (``context`` with ramp ``1 + 4 * head.number_blocks``, as ``evaluate_dense``); ``frame_batch`` frames per backbone call,
+    ``window_batch`` windows per head call; ``flip_tta``: every frame a second time mirrored, the two poses merged.  ``stats`` counts
+    what the last ``predict`` (or the calls since construction) sent through: ``backbone_frames``, ``windows``, ``head_rows``."""
+
+    def __init__(self, backbone, head, seq_len: int = 40, stride: int = 5, fuse: str = "context", frame_batch: int = 256,
+                 window_batch: int = 256, resize_mode: int = F.RESIZE_FLOAT, flip_tta: bool = False):
+        if fuse not in FUSE_MODES:
+            raise ValueError(f"fuse must be one of {sorted(FUSE_MODES)}, got {fuse!r}")
+        if int(seq_len) < 1 or int(stride) < 1 or int(frame_batch) < 1 or int(window_batch) < 1:
+            raise ValueError("seq_len, stride, frame_batch and window_batch must be >= 1")
+        if head._device is None or backbone._device != head._device:
+            raise ValueError(f"backbone ({backbone._device}) and head ({head._device}) must be on one GPU")
+        if int(frame_batch) > backbone._max_batch:
+            raise ValueError(f"frame_batch {frame_batch} exceeds the backbone's max_batch {backbone._max_batch}")
+        self.backbone, self.head, self.device = backbone, head, head._device
+        self.seq_len, self.stride, self.fuse = int(seq_len), int(stride), fuse
+        self.frame_batch, self.window_batch = int(frame_batch), int(window_batch)
+        self.resize_mode, self.flip_tta = int(resize_mode), bool(flip_tta)
+        self.ramp = 1 + 4 * int(head.number_blocks)
+        self._perm = MirrorPerm(flip_perm(head.joints_num), self.device) if self.flip_tta else None
+        self._pinned: Optional[torch.Tensor] = None
+        self._uploaded: Optional[torch.cuda.Event] = None
+        self.stats: Dict[str, int] = {"backbone_frames": 0, "windows": 0, "head_rows": 0}
+
+    # ---- frames -> crops -> features -----------------------------------------------------------------------------------------------
+    def _upload_region(self, frames, s: int, m: int, box) -> torch.Tensor:
+        """The box region of ``frames[s:s+m]`` on the device, (m, hh, ww, 3) uint8: sliced on the host into one pinned buffer (only
+        these frames of a memory-mapped file are read), one asynchronous copy."""
+        top, left, hh, ww = box
+        if self._uploaded is not None:
+            self._uploaded.synchronize()                                    # the last copy out of the buffer has finished
+        if self._pinned is None or self._pinned.numel() < m * hh * ww * 3:
+            self._pinned = torch.empty(m * hh * ww * 3, dtype=torch.uint8).pin_memory()
+        stage = self._pinned[: m * hh * ww * 3].view(m, hh, ww, 3)
+        piece = frames[s:s + m, top:top + hh, left:left + ww]
+        if isinstance(piece, torch.Tensor):
+            stage.copy_(piece)
+        else:
+            np.copyto(stage.numpy(), piece)
+        region = stage.to(self.device, non_blocking=True)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record(torch.cuda.current_stream(self.device))
+        return region
+
+    def _crops(self, frames, s: int, m: int, box, dst: torch.Tensor, dst_flip: Optional[torch.Tensor]) -> None:
+        """The resized crops of ``frames[s:s+m]`` into ``dst`` (m, 3, 224, 224) uint8, and mirrored into ``dst_flip``."""
+        hh, ww = box[2], box[3]
+        step = max(1, min(m, UPLOAD_BYTES // (hh * ww * 3)))
+        for o in range(0, m, step):
+            k = min(step, m - o)
+            region = self._upload_region(frames, s + o, k, box)
+            F.crop_and_resize_video_uint8(region, [0, 0, hh, ww], OUT_SIZE, self.resize_mode, out=dst[o:o + k])
+            if dst_flip is not None:
+                F.crop_and_resize_video_uint8(region, [0, 0, hh, ww], OUT_SIZE, self.resize_mode, hflip=True, out=dst_flip[o:o + k])
+
+    @staticmethod
+    def _check_frames(frames) -> Tuple[int, int, int]:
+        if len(frames.shape) != 4 or frames.shape[3] != 3 or frames.shape[0] < 1 or str(frames.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"frames must be (N,H,W,3) uint8 with N >= 1, got {frames.dtype} {tuple(frames.shape)}")
+        if isinstance(frames, torch.Tensor) and frames.device.type != "cpu":
+            raise ValueError("frames must be on the host: the box region is uploaded chunk by chunk")
+        return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+
+    @torch.no_grad()
+    def features(self, frames, box):
+        """``frames``: host (N,H,W,3) uint8 array or tensor (a memory-mapped ``.npy`` is read chunk by chunk), ``box`` ``[top,left,hh,ww]``
+        inside the image -> ``feats`` (N, 2048) fp32 on the device; with ``flip_tta`` ``(feats, feats_flipped)``.  Every frame goes
+        through the backbone once (twice with ``flip_tta``), in calls of ``frame_batch`` frames."""
+        n, h, w = self._check_frames(frames)
+        box = [int(v) for v in choose_box(h, w, box=box).tolist()]
+        fb = min(self.frame_batch, n)
+        with torch.cuda.device(self.device):
+            feats = torch.empty((n, FEATURE_DIM), dtype=torch.float32, device=self.device)
+            flipped = torch.empty_like(feats) if self.flip_tta else None
+            u8 = torch.empty((fb, 3, OUT_SIZE, OUT_SIZE), dtype=torch.uint8, device=self.device)
+            u8_flip = torch.empty_like(u8) if self.flip_tta else None
+            for s in range(0, n, fb):
+                m = min(fb, n - s)
+                self._crops(frames, s, m, box, u8[:m], u8_flip[:m] if self.flip_tta else None)
+                self.backbone.features_u8(u8[:m], out=feats[s:s + m])
+                self.stats["backbone_frames"] += m
+                if self.flip_tta:
+                    self.backbone.features_u8(u8_flip[:m], out=flipped[s:s + m])
+                    self.stats["backbone_frames"] += m
+        return (feats, flipped) if self.flip_tta else feats
+
+    # ---- features -> windows -> one pose per frame -----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def poses(self, feats: torch.Tensor, feats_flipped: Optional[torch.Tensor] = None, name: str = "video"):
+        """``feats`` (N, 2048) fp32 on the device [and the mirrored frames' ``feats_flipped``] -> ``(joints3d (N, J, 3) fp32, spread (N,)
+        fp32, count (N,) int32)`` on the device: ``head.joints_windows`` over ``window_starts`` in batches of ``window_batch`` [merged
+        with the mirrored pass], then one ``stitch_poses`` launch.  ``count`` = how many windows cover a frame, ``spread`` = how far
+        their poses lie apart (0 where ``count`` is 1)."""
+        if self.flip_tta != (feats_flipped is not None):
+            raise ValueError("feats_flipped goes with flip_tta, and only with it")
+        if feats.dim() != 2 or (feats_flipped is not None and tuple(feats_flipped.shape) != tuple(feats.shape)):
+            raise ValueError("feats [and feats_flipped] must be (N, 2048)")
+        n = int(feats.shape[0])
+        starts = window_starts(n, self.seq_len, self.stride)
+        t, w, joints = min(n, self.seq_len), int(starts.size), int(self.head.joints_num)
+        table = SequenceTable.from_clips(window_clips(starts, t, name), t)
+        with torch.cuda.device(self.device):
+            pred = torch.empty((w, t, joints, 3), dtype=torch.float32, device=self.device)
+            for s in range(0, w, self.window_batch):
+                st = starts[s:s + self.window_batch]
+                p = self.head.joints_windows(feats, st, t)
+                self.stats["head_rows"] += int(st.size) * t
+                if feats_flipped is not None:
+                    q = self.head.joints_windows(feats_flipped, st, t)
+                    self.stats["head_rows"] += int(st.size) * t
+                    merge_mirrored_poses(p.view(-1, joints, 3), q.view(-1, joints, 3), self._perm,
+                                         out=pred[s:s + st.size].view(-1, joints, 3))
+                else:
+                    pred[s:s + st.size] = p
+            self.stats["windows"] += w
+            # the stitch op wants a ground truth beside the prediction: the prediction itself, so gt_gap is 0 by construction
+            fused, _, spread, _ = stitch_poses(pred, pred, StitchIndex(table.offsets, table.src, w * t, self.device), self.fuse, self.ramp)
+            count = torch.from_numpy(np.diff(table.offsets).astype(np.int32)).to(self.device)
+        return fused, spread, count
+
+    @torch.no_grad()
+    def forecast(self, feats: torch.Tensor, input_len: int = 15, pred_len: int = 25) -> torch.Tensor:
+        """(P, J, 3) fp32 poses of the ``pred_len`` frames after the video's last: ``head.rollout`` on its last ``input_len`` frames."""
+        n = int(feats.shape[0])
+        if n < int(input_len):
+            raise ValueError(f"forecast needs at least input_len = {input_len} frames, the video has {n}")
+        return self.head.rollout(feats[None, n - int(input_len):n], int(input_len), int(pred_len))[1][0]
+
+    @torch.no_grad()
+    def predict(self, frames, box=None, joints2d=None, cam: Optional[dict] = None, frame_skip: int = 1, input_len: int = 15,
+                pred_len: int = 0, name: str = "video") -> Dict[str, object]:
+        """The whole pass over every ``frame_skip``-th frame.  ``box``: see ``choose_box`` (``joints2d`` (N, J, 2) pixels of the whole
+        frames, of ALL frames; the kept ones are used).  Returns host numpy arrays: ``joints3d`` (n, J, 3), ``spread`` (n,), ``count``
+        (n,), ``frame_idx`` (n,) the original frame numbers, ``box`` (4,), ``future3d`` (P, J, 3) if ``pred_len > 0``, ``K`` (3, 3) of
+        the resized crop if ``cam`` = ``{"f": .., "c": ..}`` was given, and ``stats``."""
+        total, h, w = self._check_frames(frames)
+        if int(frame_skip) < 1:
+            raise ValueError(f"frame_skip must be >= 1, got {frame_skip}")
+        frame_idx = np.arange(0, total, int(frame_skip), dtype=np.int64)
+        kept = frames[::int(frame_skip)] if int(frame_skip) > 1 else frames
+        if joints2d is not None:
+            joints2d = np.asarray(joints2d)
+            if joints2d.shape[0] != total:
+                raise ValueError(f"joints2d covers {joints2d.shape[0]} frames, the video has {total}")
+            joints2d = joints2d[frame_idx]
+        box_t = choose_box(h, w, box=box, joints2d=joints2d)
+        self.stats = {"backbone_frames": 0, "windows": 0, "head_rows": 0}
+        got = self.features(kept, box_t)
+        feats, flipped = got if self.flip_tta else (got, None)
+        joints3d, spread, count = self.poses(feats, flipped, name)
+        out: Dict[str, object] = {"joints3d": joints3d.cpu().numpy(), "spread": spread.cpu().numpy(), "count": count.cpu().numpy(),
+                                  "frame_idx": frame_idx, "box": box_t.numpy().copy()}
+        if int(pred_len) > 0:
+            out["future3d"] = self.forecast(feats, input_len, pred_len).cpu().numpy()
+        if cam is not None:
+            out["K"] = F.adjust_camera_after_crop_and_resize(cam, box_t, OUT_SIZE).numpy()
+        out["stats"] = dict(self.stats)
+        return out
+
+    @torch.no_grad()
+    def crops(self, frames, box, first: int, count: int, step: int = 1) -> torch.Tensor:
+        """The resized crops of the frames ``first, first + step, ..`` (``count`` of them) as pictures: (count, 224, 224, 3) uint8 on the
+        device (what ``render`` draws on).  The frames are a strided slice, so they travel in the same few pieces as in ``features``."""
+        total, h, w = self._check_frames(frames)
+        first, count, step = int(first), int(count), int(step)
+        if count < 1 or step < 1 or first < 0 or first + (count - 1) * step >= total:
+            raise ValueError(f"frames {first}, {first + step}, .. ({count} of them) do not lie inside a video of {total} frames")
+        box = [int(v) for v in choose_box(h, w, box=box).tolist()]
+        with torch.cuda.device(self.device):
+            chw = torch.empty((count, 3, OUT_SIZE, OUT_SIZE), dtype=torch.uint8, device=self.device)
+            self._crops(frames[first:first + (count - 1) * step + 1:step], 0, count, box, chw, None)
+            return chw.permute(0, 2, 3, 1).contiguous()
+
+
+# ---- command line ---------------------------------------------------------------------------------------------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser("Decoded video frames in, one 3D pose per frame out (backbone + lifting head on one MI355X)")
+    p.add_argument("--frames", type=str, nargs="+", required=True, metavar="FILE",
+                   help=".npy of (N,H,W,3) uint8 frames (memory-mapped), or .npz with `frames` and optionally `box` [top,left,hh,ww], "
+                        "`joints2d` (N,J,2) and the camera's `f`, `c`")
+    p.add_argument("--model_path", type=str, required=True, help="head checkpoint (its dimensions are read from it)")
+    p.add_argument("--weights", type=str, default=None, help="local torchvision-layout ResNet-50 checkpoint")
+    p.add_argument("--synthetic-weights", action="store_true", help="seeded RANDOM backbone weights: for benchmarks / tests only")
+    p.add_argument("--weights-seed", type=int, default=0)
+    p.add_argument("--precision", choices=["bf16", "fp16", "bf16w2", "fp32x", "fp8"], default="bf16", help="backbone precision")
+    p.add_argument("--head-precision", choices=("fp16", "bf16"), default="fp16", help="16-bit type of the head's GEMMs")
+    p.add_argument("--seq-len", type=int, default=40, help="frames per head window")
+    p.add_argument("--stride", type=int, default=5, help="frames between window starts")
+    p.add_argument("--frame-skip", type=int, default=2, help="every this-many-th frame is used: the cadence heads are trained at")
+    p.add_argument("--fuse", choices=sorted(FUSE_MODES), default="context", help="how a frame's windows are fused")
+    p.add_argument("--flip-tta", action="store_true", help="flip test-time augmentation: every frame also mirrored, the poses merged")
+    p.add_argument("--input-len", type=int, default=15, help="observed frames of the forecast")
+    p.add_argument("--pred-len", type=int, default=0, help="poses to forecast beyond the last frame (0: none)")
+    p.add_argument("--box", type=int, nargs=4, default=None, metavar=("TOP", "LEFT", "H", "W"), help="crop box (overrides the file's)")
+    p.add_argument("--resize-mode", choices=sorted(RESIZE_MODES), default="float", help="bilinear resize arithmetic")
+    p.add_argument("--frame-batch", type=int, default=256, help="frames per backbone call")
+    p.add_argument("--window-batch", type=int, default=256, help="windows per head call")
+    p.add_argument("--out", type=str, required=True, metavar="DIR", help="one NAME_poses.npz per input")
+    p.add_argument("--render", action="store_true", help="also NAME_render/: an APNG and a contact sheet of the last frames")
+    p.add_argument("--render-frames", type=int, default=120, help="how many of the last frames to render")
+    p.add_argument("--render-fps", type=float, default=10.0)
+    p.add_argument("--device", type=str, default="cuda")
+    return p
+
+
+def load_input(path: str) -> Dict[str, object]:
+    """``frames`` (memory-mapped for a ``.npy``) and whatever annotations the file holds: ``box``, ``joints2d``, ``cam``."""
+    if path.endswith(".npz"):
+        z = np.load(path, allow_pickle=False)
+        if "frames" not in z.files:
+            raise ValueError(f"{path}: no `frames` array in the file (it holds {sorted(z.files)}); expected (N,H,W,3) uint8 frames")
+        item: Dict[str, object] = {"frames": z["frames"]}
+        for key in ("box", "joints2d"):
+            if key in z.files:
+                item[key] = z[key]
+        if ("f" in z.files) != ("c" in z.files):
+            raise ValueError(f"{path}: the camera needs both `f` and `c`")
+        if "f" in z.files:
+            item["cam"] = {"f": z["f"], "c": z["c"]}
+        return item
+    if path.endswith(".npy"):
+        return {"frames": np.load(path, mmap_mode="r")}
+    raise ValueError(f"{path}: expected a .npy or .npz file")
+
+
+def render_prediction(outdir: str, predictor: VideoPredictor, frames, res: Dict[str, object], n_frames: int, fps: float) -> List[str]:
+    """The last ``n_frames`` kept frames with their poses, then the forecast (if any) on the plain background, through ``render``."""
+    from . import render as R
+    dev = predictor.device
+    n = int(res["joints3d"].shape[0])
+    r = max(1, min(int(n_frames), n))
+    idx = res["frame_idx"]
+    pics = predictor.crops(frames, res["box"], int(idx[n - r]), r, int(idx[1] - idx[0]) if n > 1 else 1)
+    pred = torch.from_numpy(res["joints3d"][n - r:]).to(dev)
+    future = None
+    if "future3d" in res:
+        future = torch.from_numpy(res["future3d"]).to(dev)[None]
+        blank = torch.tensor(R._rgb_tuple(R.PANEL_BG_RGB), dtype=torch.uint8, device=dev).expand(future.shape[1], OUT_SIZE, OUT_SIZE, 3)
+        pics = torch.cat([pics, blank])
+        # placeholders, never drawn: render_panels puts future3d in the prediction layer of every frame t >= input_len = r
+        pred = torch.cat([pred, torch.zeros_like(future[0])])
+    k = torch.from_numpy(res["K"]).to(dev)[None] if "K" in res else None
+    return R.render_clips(outdir, pics[None], None, k, None, pred[None], future, r, None, fps)
+
+
+def main(argv: Optional[List[str]] = None) -> List[str]:
+    args = build_parser().parse_args(argv)
+    device = torch.device(args.device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.R50Error("predict runs on an MI355X only; there is no CPU fallback")
+    from .backbone import ResNet50Backbone
+    from .preprocess_resnet_features import _resolve_weights
+    from .results import build_head, load_head_state
+    items = [load_input(p) for p in args.frames]
+    state_dict, source = _resolve_weights(args)
+    print(f"backbone weights: {source}")
+    backbone = ResNet50Backbone(state_dict=state_dict, max_batch=args.frame_batch, precision=args.precision).to(device).eval()
+    head = build_head(load_head_state(args.model_path), backbone._device, args.head_precision)
+    predictor = VideoPredictor(backbone, head, args.seq_len, args.stride, args.fuse, args.frame_batch, args.window_batch,
+                               RESIZE_MODES[args.resize_mode], args.flip_tta)
+    os.makedirs(args.out, exist_ok=True)
+    written: List[str] = []
+    for path, item in zip(args.frames, items):
+        name = os.path.splitext(os.path.basename(path))[0]
+        res = predictor.predict(item["frames"], box=args.box if args.box is not None else item.get("box"), joints2d=item.get("joints2d"),
+                                cam=item.get("cam"), frame_skip=args.frame_skip, input_len=args.input_len, pred_len=args.pred_len, name=name)
+        stats = res.pop("stats")
+        out_path = os.path.join(args.out, name + "_poses.npz")
+        np.savez(out_path, **res, **{k: np.int64(v) for k, v in stats.items()})
+        written.append(out_path)
+        print(f"{name}: {res['joints3d'].shape[0]} poses from {stats['backbone_frames']} backbone frames, {stats['windows']} windows "
+              f"({stats['head_rows']} head rows) -> {out_path}")
+        if args.render:
+            written += render_prediction(os.path.join(args.out, name + "_render"), predictor, item["frames"], res, args.render_frames,
+                                         args.render_fps)
+    backbone.close()
+    return written
+
+
+if __name__ == "__main__":
+    main()

@@ -141,7 +141,8 @@ def _styles(n: int, t: int, layers: Sequence[Tuple[Tuple[int, int, int], torch.T
     return st.reshape(n * t, len(layers), 4).to(device)
 
 
-def render_panels(frames_u8: Optional[torch.Tensor], joints2d: torch.Tensor, K: torch.Tensor, gt3d: torch.Tensor, pred3d: torch.Tensor,
+def render_panels(frames_u8: Optional[torch.Tensor], joints2d: Optional[torch.Tensor], K: Optional[torch.Tensor],
+                  gt3d: Optional[torch.Tensor], pred3d: torch.Tensor,
                   future3d: Optional[torch.Tensor] = None, input_len: int = 0, *, size: Optional[int] = None,
                   edges: Sequence[Sequence[int]] = H36M_EDGES, root: int = 0, gt_rgb=GT_RGB, pred_rgb=PRED_RGB, future_rgb=FUTURE_RGB,
                   gt_alpha: int = 255, ref_alpha: int = 153, pred_alpha: int = 255, bg_rgb=PANEL_BG_RGB, half_width: float = 1.0,
@@ -156,9 +157,14 @@ def render_panels(frames_u8: Optional[torch.Tensor], joints2d: torch.Tensor, K: 
 
     ``frames_u8`` (N,T,S,S,3) uint8 on the device, or None: then panels 0 and 1 get ``bg_rgb`` too (``size`` gives S, default 224).
     With ``future3d`` (N,P,J,3) the prediction layer of the frames ``t >= input_len`` carries the rollout's poses in ``future_rgb``, and
-    the frames ``t >= input_len + P`` have it switched off.  gt3d / pred3d (N,T,J,3), K (N,3,3), all on the device."""
-    n, t, j = int(gt3d.shape[0]), int(gt3d.shape[1]), int(gt3d.shape[2])
-    dev = gt3d.device
+    the frames ``t >= input_len + P`` have it switched off.  gt3d / pred3d (N,T,J,3), K (N,3,3), all on the device.
+
+    A prediction without annotations (``predict``): ``joints2d``, ``K`` and ``gt3d`` may each be None.  A layer whose input is missing is
+    left out (panel 0 without ``joints2d`` is the bare frame, and so is panel 1 without ``K``: nothing can be projected), and without
+    ``gt3d`` the 3D view is centred on the prediction's own root joint.  With all three given nothing changes."""
+    shape_of = gt3d if gt3d is not None else pred3d
+    n, t, j = int(shape_of.shape[0]), int(shape_of.shape[1]), int(shape_of.shape[2])
+    dev = shape_of.device
     if frames_u8 is not None:
         if frames_u8.dim() != 5 or frames_u8.shape[:2] != (n, t) or frames_u8.shape[2] != frames_u8.shape[3] or frames_u8.shape[4] != 3:
             raise ValueError(f"render_panels: frames_u8 must be (N,T,S,S,3), got {tuple(frames_u8.shape)}")
@@ -166,7 +172,9 @@ def render_panels(frames_u8: Optional[torch.Tensor], joints2d: torch.Tensor, K: 
         bg = frames_u8.reshape(n * t, s, s, 3).contiguous()
     else:
         s, bg = int(size or 224), None
-    gt3d, pred3d, joints2d = gt3d.float(), pred3d.float(), joints2d.float()
+    pred3d = pred3d.float()
+    gt3d = gt3d.float() if gt3d is not None else None
+    joints2d = joints2d.float() if joints2d is not None else None
     pred_col = torch.tensor(_rgb_tuple(pred_rgb), dtype=torch.uint8).repeat(t, 1)
     pred_a = torch.full((t,), int(pred_alpha), dtype=torch.uint8)
     if future3d is not None:
@@ -183,13 +191,24 @@ def render_panels(frames_u8: Optional[torch.Tensor], joints2d: torch.Tensor, K: 
         return torch.stack([q.reshape(n * t, j, 2) for q in pts], dim=1).to(torch.float32).contiguous()
 
     kw = dict(bg_rgb=bg_rgb, hw=(s, s))
-    p0 = draw_skeletons(bg, layers(joints2d), _styles(n, t, [(gt_c, gt_a)], dev), edges, half_width, joint_radius, **kw)
-    p1 = draw_skeletons(bg, layers(project(gt3d, K, eps), project(pred3d, K, eps)), _styles(n, t, [(gt_c, ref_a), (pred_col, pred_a)], dev),
-                        edges, half_width, joint_radius, **kw)
-    centre = gt3d[:, :, root]
+
+    def panel(back, *drawn):
+        """One launch over ``back`` with the (points, rgb, alpha) layers whose points are there; with none, ``back`` as it is."""
+        drawn = [d for d in drawn if d[0] is not None]
+        if not drawn:
+            if back is not None:
+                return back.clone()
+            return torch.tensor(_rgb_tuple(bg_rgb), dtype=torch.uint8, device=dev).expand(n * t, s, s, 3).contiguous()
+        return draw_skeletons(back, layers(*[d[0] for d in drawn]), _styles(n, t, [d[1:] for d in drawn], dev), edges, half_width,
+                              joint_radius, **kw)
+
+    p0 = panel(bg, (joints2d, gt_c, gt_a))
+    p1 = panel(bg, (project(gt3d, K, eps) if gt3d is not None and K is not None else None, gt_c, ref_a),
+               (project(pred3d, K, eps) if K is not None else None, pred_col, pred_a))
+    centre = (gt3d if gt3d is not None else pred3d)[:, :, root]
     view = dict(azim_deg=azim_deg, elev_deg=elev_deg, size=s, half_extent_m=half_extent_m)
-    p2 = draw_skeletons(None, layers(view_points(gt3d, centre, **view), view_points(pred3d, centre, **view)),
-                        _styles(n, t, [(gt_c, gt_a), (pred_col, pred_a)], dev), edges, half_width, joint_radius, **kw)
+    p2 = panel(None, (view_points(gt3d, centre, **view) if gt3d is not None else None, gt_c, gt_a),
+               (view_points(pred3d, centre, **view), pred_col, pred_a))
     return torch.cat([p0, p1, p2], dim=2).reshape(n, t, s, 3 * s, 3)
 
 
@@ -285,7 +304,7 @@ def clip_stem(i: int, meta) -> str:
 def render_clips(outdir, frames_u8: Optional[torch.Tensor], joints2d, K, gt3d, pred3d, future3d=None, input_len: int = 0,
                  metas: Optional[Sequence] = None, fps: float = 10.0, sheet_every: int = 5, **panel_kw) -> List[str]:
     """``render_panels`` over n clips, then per clip ``<stem>.png`` (an APNG of the T frames) and ``clip_<i>_sheet.png`` (the contact
-    sheet) under ``outdir``.  Returns the written paths."""
+    sheet) under ``outdir``.  ``joints2d``, ``K`` and ``gt3d`` may be None, as in ``render_panels``.  Returns the written paths."""
     os.makedirs(outdir, exist_ok=True)
     panels = render_panels(frames_u8, joints2d, K, gt3d, pred3d, future3d, input_len, **panel_kw).cpu().numpy()
     written = []

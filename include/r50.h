@@ -437,6 +437,25 @@ int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int jo
 int r50_op_sequence_metrics(const float* fused, const float* gt, const float* spread, const int* offsets, const int* seq, const int* idx,
                             const int* group, int frames, int joints, int root, int n_groups, double* part, int n_blocks, void* stream);
 
+/* Video in, poses out: the two device steps of the pass that nothing else provides.
+ *  r50_op_gather_window_rows: the head's windows are views of one feature matrix.  src_f32 (src_rows, c) fp32, starts (b) int32
+ *    device values, dst (b*t, c) elements (et 0 = bf16, 1 = fp16): dst row w*t + i = the cast of src row starts[w] + i, with
+ *    r50_op_cast_rows' rounding and saturation, so the result is bit-equal to r50_op_cast_rows of the gathered fp32 rows without that
+ *    (b*t, c) fp32 intermediate.  Windows may overlap and repeat.  Needs b >= 1, 1 <= t <= src_rows < 2^31, c a positive multiple of
+ *    8, b * t * c / 8 < 2^31, src and dst 16-byte aligned, no null pointer; checked before any launch.  The kernel TRUSTS starts: the
+ *    caller checks on the host that every start lies in [0, src_rows - t].  Each lane moves 8 columns: two 16-byte loads, one 16-byte
+ *    store; grid-stride.
+ *  r50_op_merge_mirrored_poses: flip test-time augmentation.  a, out (rows, joints, 3) fp32 = the poses of the frames as they are,
+ *    b_mirrored the poses of the horizontally mirrored frames; perm (joints) int32 device values, the left/right joint swap.
+ *    out[r,j,k] = 0.5f * (a[r,j,k] + s_k * b_mirrored[r,perm[j],k]), s = (-1, 1, 1): the add and the multiply are two fp32
+ *    operations, each rounded to nearest even.  Needs rows >= 1, 1 <= joints <= 64, no null pointer, out either exactly a or
+ *    overlapping neither input; checked before any launch.  The kernel TRUSTS perm: the caller checks on the host that every entry
+ *    lies in [0, joints) and that perm[perm[j]] == j.  No atomics: the same bits on every run. */
+int r50_op_gather_window_rows(const float* src_f32, int64_t src_rows, int c, const int* starts, int b, int t, void* dst, int et,
+                              void* stream);
+int r50_op_merge_mirrored_poses(const float* a, const float* b_mirrored, int64_t rows, int joints, const int* perm, float* out,
+                                void* stream);
+
 /* Lifting head, phase 2 (training f_AR; DESIGN.md "f next #2").  The reference has no phase 2; this
  * project's definition: f_movie / f_3D frozen and run as at inference, loss = l3d_hat + lambda * l_lat over frames s >= 1.
  *  r50_op_future_pose_loss_grad: y_hat, gt, dy (b*t, joints, 3) fp32: dy = 2 (y_hat-gt) / n * loss_scale with n = b*(t-1)*joints*3,

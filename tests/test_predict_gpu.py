@@ -1,0 +1,286 @@
+"""``predict`` on the MI355X: the two new ops against the ops and torch expressions they stand for, bit for
+bit; ``joints_windows`` against ``joints`` on the gathered rows; the whole pass against the window-by-window composition written out
+here; the edge lengths, the forecast and the command line.  Every comparison is exact: the pass reorders no floating-point sum."""
+import numpy as np
+import pytest
+import torch
+
+from implementation_phd_lab_vision_amd import frames as F
+from implementation_phd_lab_vision_amd import model, predict
+from implementation_phd_lab_vision_amd.sequences import SequenceTable, stitch_poses
+from tests import png_reader
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+N, T, STRIDE, BOX = 23, 8, 3, [5, 3, 40, 38]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from implementation_phd_lab_vision_amd import _lib
+    _lib.build_library()
+    return _lib.load_library()
+
+
+def _s():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _bits(t):
+    return t.view(torch.int16)
+
+
+def _ties(dt, n, g):
+    """n fp32 values exactly halfway between two adjacent finite 16-bit values (what test_cast_rows_rounds_to_nearest_even feeds)."""
+    fp16 = dt == torch.float16
+    bits = torch.randint(0x0400 if fp16 else 0x0080, 0x7bfe if fp16 else 0x7f7e, (n,), generator=g, dtype=torch.int32)
+    lo, hi = bits.to(torch.int16).view(dt).float(), (bits + 1).to(torch.int16).view(dt).float()
+    return (lo + hi) / 2 * torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
+
+
+def _cast_source(dt, rows, c, g):
+    """(rows, c) fp32: a third exact rounding ties, then the saturating values of test_cast_rows_saturates_..., the rest normal draws."""
+    x = torch.randn(rows, c, generator=g) * 3
+    flat = x.view(-1)
+    k = flat.numel() // 3
+    flat[:k] = _ties(dt, k, g)
+    big = [65504.0, 65519.0, 65520.0, 1e5, 3e38, float("inf")]
+    special = torch.tensor(big + [-v for v in big] + [65503.0, 1e38, 0.0, -0.0])
+    flat[k:k + special.numel()] = special
+    return x[torch.randperm(rows, generator=g)].contiguous()
+
+
+def _cast_rows(lib, x, dt):
+    out = torch.empty(x.shape, dtype=dt, device=x.device)
+    rc = lib.r50_op_cast_rows(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), x.shape[1], 1 if dt == torch.float16 else 0, _s())
+    assert rc == 0, lib.r50_last_error(None)
+    return out
+
+
+# ---------------------------------------------------------------- 1. the gather op ---------------------------------------------------
+@pytest.mark.parametrize("c", [8, 2048])
+@pytest.mark.parametrize("prec", ["fp16", "bf16"])
+def test_gather_window_rows_equals_cast_rows_of_the_gathered_rows(lib, prec, c):
+    """7 source rows, windows of 3 starting at [0, 4, 4, 2, 1]: the first row, the last legal start, a duplicate, overlaps.  The
+    destination lies between two guards of t rows each, which must keep their poison."""
+    dt, t, starts = DTYPES[prec], 3, [0, 4, 4, 2, 1]
+    g = torch.Generator().manual_seed(c + (dt == torch.float16))
+    src = _cast_source(dt, 7, c, g).to(DEV)
+    idx = (torch.tensor(starts)[:, None] + torch.arange(t)[None]).reshape(-1).to(DEV)
+    want = _cast_rows(lib, src[idx].contiguous(), dt)
+    rows = len(starts) * t
+    poison = 0x7b7b
+    for st in (starts, torch.tensor(starts, dtype=torch.int32, device=DEV)):
+        buf = torch.empty((rows + 2 * t, c), dtype=dt, device=DEV)
+        _bits(buf).fill_(poison)
+        got = model.gather_window_rows(src, st, t, dt, out=buf[t:t + rows])
+        torch.cuda.synchronize()
+        assert got.data_ptr() == buf[t].data_ptr()
+        assert torch.equal(_bits(got), _bits(want)), "gather differs from cast_rows(src[idx])"
+        assert bool((_bits(buf[:t]) == poison).all()) and bool((_bits(buf[t + rows:]) == poison).all()), "wrote outside the destination"
+    fresh = model.gather_window_rows(src, starts, t, dt)
+    assert tuple(fresh.shape) == (rows, c) and torch.equal(_bits(fresh), _bits(want))
+
+
+def test_gather_window_rows_stride_loop_runs_more_than_once(lib):
+    """The launcher sizes the grid with ew_grid (csrc/r50_abi.hip): at most 256 * 32 workgroups of 256 lanes, one lane per 8 columns.
+    2731 windows of 3 rows of 2048 columns are 2 097 408 items, more than those 2 097 152 lanes: the stride loop runs twice for some."""
+    dt, t, c, b = torch.float16, 3, 2048, 2731
+    assert b * t * c // 8 > 256 * 32 * 256
+    g = torch.Generator().manual_seed(5)
+    src = _cast_source(dt, 7, c, g).to(DEV)
+    starts = torch.randint(0, 5, (b,), generator=g, dtype=torch.int32)
+    starts[0], starts[-1] = 4, 0
+    idx = (starts.long()[:, None] + torch.arange(t)[None]).reshape(-1).to(DEV)
+    want = _cast_rows(lib, src[idx].contiguous(), dt)
+    buf = torch.empty((b * t + 2 * t, c), dtype=dt, device=DEV)
+    _bits(buf).fill_(0x7b7b)
+    got = model.gather_window_rows(src, starts.numpy(), t, dt, out=buf[t:t + b * t])
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(got), _bits(want))
+    assert bool((_bits(buf[:t]) == 0x7b7b).all()) and bool((_bits(buf[t + b * t:]) == 0x7b7b).all())
+
+
+def test_gather_window_rows_refuses_bad_arguments(lib):
+    src = torch.zeros(7, 8, device=DEV)
+    st = torch.zeros(1, dtype=torch.int32, device=DEV)
+    dst = torch.empty(3, 8, dtype=torch.float16, device=DEV)
+    for args in ((7, 12, 1, 3, 1), (7, 8, 0, 3, 1), (7, 8, 1, 0, 1), (7, 8, 1, 8, 1), (7, 8, 1, 3, 2)):                 # src_rows, c, b, t, et
+        rc = lib.r50_op_gather_window_rows(src.data_ptr(), args[0], args[1], st.data_ptr(), args[2], args[3], dst.data_ptr(), args[4], _s())
+        assert rc == -1 and b"r50_op_gather_window_rows" in lib.r50_last_error(None)
+    assert lib.r50_op_gather_window_rows(src.data_ptr(), 7, 2048, st.data_ptr(), 1 << 21, 4, dst.data_ptr(), 1, _s()) == -1      # 2^31 items
+    assert lib.r50_op_gather_window_rows(src.data_ptr() + 4, 6, 8, st.data_ptr(), 1, 3, dst.data_ptr(), 1, _s()) == -1      # misaligned
+    assert lib.r50_op_gather_window_rows(None, 7, 8, st.data_ptr(), 1, 3, dst.data_ptr(), 1, _s()) == -1
+
+
+# ---------------------------------------------------------------- 2. the merge op ----------------------------------------------------
+def _mirror(b, perm):
+    m = b[:, torch.as_tensor(perm, dtype=torch.long)].clone()
+    m[..., 0] = -m[..., 0]
+    return m
+
+
+@pytest.mark.parametrize("joints", [17, 1])
+def test_merge_mirrored_poses_is_the_torch_expression(lib, joints):
+    perm = predict.flip_perm(17) if joints == 17 else np.zeros(1, dtype=np.int32)
+    g = torch.Generator().manual_seed(joints)
+    a, b = torch.randn(5, joints, 3, generator=g), torch.randn(5, joints, 3, generator=g)
+    want = 0.5 * (a + _mirror(b, perm))
+    ad, bd = a.to(DEV), b.to(DEV)
+    got = predict.merge_mirrored_poses(ad, bd, perm)
+    assert torch.equal(got.cpu(), want) and torch.equal(ad.cpu(), a) and torch.equal(bd.cpu(), b)
+    held = predict.MirrorPerm(perm, DEV)
+    alias = ad.clone()
+    assert predict.merge_mirrored_poses(alias, bd, held, out=alias) is alias
+    assert torch.equal(alias.cpu(), want), "out = a gives another result"
+    zero = torch.zeros_like(bd)
+    once = 2.0 * predict.merge_mirrored_poses(zero, bd, held)                     # 0.5 * (0 + M(b)), doubled: M(b) itself
+    assert torch.equal(once.cpu(), _mirror(b, perm))
+    assert torch.equal((2.0 * predict.merge_mirrored_poses(zero, once, held)).cpu(), b), "the mirror applied twice is not the identity"
+    rc = lib.r50_op_merge_mirrored_poses(ad.data_ptr(), bd.data_ptr(), 5, joints, held.perm.data_ptr(), bd.data_ptr(), _s())
+    assert rc == -1 and b"overlaps" in lib.r50_last_error(None)
+    assert lib.r50_op_merge_mirrored_poses(ad.data_ptr(), bd.data_ptr(), 5, 65, held.perm.data_ptr(), alias.data_ptr(), _s()) == -1
+
+
+def test_merge_inverts_the_hflip_annotations():
+    g = torch.Generator().manual_seed(2)
+    j3d = torch.randn(6, 17, 3, generator=g)
+    flipped, _, _ = F.aug_hflip_annotations(j3d, torch.zeros(6, 17, 2), torch.eye(3))
+    got = predict.merge_mirrored_poses(j3d.to(DEV), flipped.to(DEV), predict.flip_perm(17))
+    assert torch.equal(got.cpu(), j3d)                                             # 0.5 * (x + x)
+
+
+# ---------------------------------------------------------------- 3.-6. the head and the pass --------------------------------------------
+def _head(precision):
+    from oracle.lifting_oracle import synthetic_head_state_dict
+    return model.PHDFor3DJoints(64, 17, 2, precision=precision).load_state_dict(synthetic_head_state_dict(64, 2, seed=1)).to(DEV).eval()
+
+
+@pytest.fixture(scope="module")
+def head():
+    return _head("fp16")
+
+
+@pytest.fixture(scope="module")
+def backbone(lib):
+    from implementation_phd_lab_vision_amd.backbone import ResNet50Backbone
+    from implementation_phd_lab_vision_amd.weights import synthetic_state_dict
+    bb = ResNet50Backbone(state_dict=synthetic_state_dict(0), max_batch=16).to(DEV).eval()
+    yield bb
+    bb.close()
+
+
+@pytest.fixture(scope="module")
+def video():
+    return torch.randint(0, 256, (N, 64, 48, 3), generator=torch.Generator().manual_seed(7), dtype=torch.uint8)
+
+
+@pytest.fixture(scope="module")
+def feats():
+    return torch.randn(N, 2048, generator=torch.Generator().manual_seed(8)).abs().to(DEV)
+
+
+def _window_idx(starts, t):
+    return torch.as_tensor(np.asarray(starts), dtype=torch.long)[:, None] + torch.arange(t)[None]
+
+
+@pytest.mark.parametrize("prec", ["fp16", "bf16"])
+def test_joints_windows_equals_joints_of_the_gathered_rows(lib, feats, prec):
+    head = _head(prec)
+    starts = predict.window_starts(N, T, STRIDE)
+    want = head.joints(feats[_window_idx(starts, T).to(DEV)])
+    assert tuple(want.shape) == (6, T, 17, 3)
+    assert torch.equal(head.joints_windows(feats, starts, T), want)
+    assert torch.equal(head.joints_windows(feats, torch.from_numpy(starts).to(DEV), T), want)
+    with pytest.raises(ValueError):
+        head.joints_windows(feats, [N - T + 1], T)
+
+
+def _naive(backbone, head, video, flip):
+    """The pass window by window: each window's frames through crop + backbone on their own, the head on each window, one stitch."""
+    dev_frames = video.to(DEV)
+    starts = predict.window_starts(N, T, STRIDE)
+    perm = predict.flip_perm(17)
+    pred = torch.empty((len(starts), T, 17, 3), dtype=torch.float32, device=DEV)
+    for w, s in enumerate(starts):
+        clip = dev_frames[s:s + T].contiguous()
+        p = head.joints(backbone.features_from_video(clip, BOX, F.RESIZE_FLOAT)[None])[0]
+        if flip:
+            mirrored = backbone.features_u8(F.crop_and_resize_video_uint8(clip, BOX, 224, F.RESIZE_FLOAT, hflip=True))
+            p = 0.5 * (p + _mirror(head.joints(mirrored[None])[0], perm))
+        pred[w] = p
+    table = SequenceTable.from_clips(predict.window_clips(starts, T), T)
+    fused, _, spread, _ = stitch_poses(pred, pred.clone(), (table.offsets, table.src), "context", 1 + 4 * head.number_blocks)
+    return fused.cpu().numpy(), spread.cpu().numpy(), np.diff(table.offsets).astype(np.int32)
+
+
+@pytest.mark.parametrize("flip", [False, True], ids=["plain", "flip_tta"])
+def test_predict_equals_the_window_by_window_composition(backbone, head, video, flip):
+    want3d, want_spread, want_count = _naive(backbone, head, video, flip)
+    p = predict.VideoPredictor(backbone, head, seq_len=T, stride=STRIDE, frame_batch=10, window_batch=4, flip_tta=flip)
+    for frames in (video, video.numpy()):
+        res = p.predict(frames, box=BOX)
+        assert res["joints3d"].shape == (N, 17, 3) and res["joints3d"].dtype == np.float32
+        assert np.array_equal(res["joints3d"], want3d), "the pass differs from the window-by-window composition"
+        assert np.array_equal(res["spread"], want_spread) and np.array_equal(res["count"], want_count)
+        assert res["stats"] == {"backbone_frames": 2 * N if flip else N, "windows": 6, "head_rows": (2 if flip else 1) * 6 * T}
+        assert res["frame_idx"].tolist() == list(range(N)) and res["box"].tolist() == BOX and "future3d" not in res and "K" not in res
+        assert res["count"].min() == 1 and res["count"].max() > 1
+        assert np.all(res["spread"][res["count"] == 1] == 0.0) and np.all(res["spread"][res["count"] > 1] > 0.0)
+
+
+def test_predict_frame_skip_camera_and_default_box(backbone, head, video):
+    p = predict.VideoPredictor(backbone, head, seq_len=T, stride=STRIDE, frame_batch=16)
+    cam = {"f": np.array([1100.0, 1150.0], np.float32), "c": np.array([24.0, 30.0], np.float32)}
+    res = p.predict(video, cam=cam, frame_skip=2, input_len=4, pred_len=3)
+    assert res["frame_idx"].tolist() == list(range(0, N, 2)) and res["box"].tolist() == [8, 0, 48, 48]
+    assert res["joints3d"].shape == (12, 17, 3) and res["future3d"].shape == (3, 17, 3) and res["stats"]["backbone_frames"] == 12
+    assert np.array_equal(res["K"], F.adjust_camera_after_crop_and_resize(cam, torch.tensor([8, 0, 48, 48])).numpy())
+    again = p.predict(video[::2].contiguous(), box=[8, 0, 48, 48], input_len=4, pred_len=3)
+    assert np.array_equal(again["joints3d"], res["joints3d"]) and np.array_equal(again["future3d"], res["future3d"])
+
+
+@pytest.mark.parametrize("n", [5, 8])
+def test_edge_lengths_are_one_window(backbone, head, feats, n):
+    p = predict.VideoPredictor(backbone, head, seq_len=T, stride=STRIDE, frame_batch=16)
+    joints3d, spread, count = p.poses(feats[:n].contiguous())
+    assert torch.equal(joints3d, head.joints(feats[None, :n])[0])
+    assert count.tolist() == [1] * n and spread.tolist() == [0.0] * n and p.stats == {"backbone_frames": 0, "windows": 1, "head_rows": n}
+
+
+def test_forecast_is_the_rollout_of_the_last_frames(backbone, head, feats):
+    p = predict.VideoPredictor(backbone, head, seq_len=T, stride=STRIDE, frame_batch=16)
+    got = p.forecast(feats, 4, 3)
+    assert tuple(got.shape) == (3, 17, 3) and torch.equal(got, head.rollout(feats[None, N - 4:N], 4, 3)[1][0])
+    with pytest.raises(ValueError, match="input_len"):
+        p.forecast(feats[:3], 4, 3)
+
+
+# ---------------------------------------------------------------- 7. the command line ------------------------------------------------
+def test_cli_writes_poses_and_pictures(tmp_path, backbone, head, video):
+    from oracle.lifting_oracle import synthetic_head_state_dict
+    cam = {"f": np.array([1100.0, 1150.0], np.float32), "c": np.array([24.0, 30.0], np.float32)}
+    np.savez(tmp_path / "walk.npz", frames=video.numpy(), **cam)
+    torch.save(synthetic_head_state_dict(64, 2, seed=1), tmp_path / "head.pt")
+    argv = ["--frames", str(tmp_path / "walk.npz"), "--model_path", str(tmp_path / "head.pt"), "--synthetic-weights", "--seq-len", str(T),
+            "--stride", str(STRIDE), "--frame-batch", "16", "--pred-len", "3", "--input-len", "4", "--render", "--render-frames", "6"]
+    runs = [predict.main(argv + ["--out", str(tmp_path / d)]) for d in ("a", "b")]
+    assert [f.replace(str(tmp_path / "a"), "") for f in runs[0]] == [f.replace(str(tmp_path / "b"), "") for f in runs[1]]
+    assert len(runs[0]) == 3 and runs[0][0] == str(tmp_path / "a" / "walk_poses.npz")
+    for first, second in zip(*runs):
+        assert open(first, "rb").read() == open(second, "rb").read(), f"{first} differs between two runs"
+    want = predict.VideoPredictor(backbone, head, seq_len=T, stride=STRIDE, frame_batch=16).predict(
+        video.numpy(), cam=cam, frame_skip=2, input_len=4, pred_len=3)
+    z = np.load(runs[0][0])
+    assert sorted(z.files) == sorted(["joints3d", "spread", "count", "frame_idx", "box", "future3d", "K", "backbone_frames", "windows", "head_rows"])
+    for key in ("joints3d", "spread", "count", "frame_idx", "box", "future3d", "K"):
+        assert z[key].shape == want[key].shape and np.array_equal(z[key], want[key]), key
+    assert z["joints3d"].shape == (12, 17, 3) and z["future3d"].shape == (3, 17, 3) and z["K"].shape == (3, 3)
+    assert {k: int(z[k]) for k in ("backbone_frames", "windows", "head_rows")} == want["stats"]
+    anim, info = png_reader.decode(runs[0][1])
+    assert info["animated"] and anim.shape == (9, 224, 3 * 224, 3)                       # 6 frames of the video, then the 3 forecast poses
+    sheet, _ = png_reader.decode(runs[0][2])
+    assert sheet.shape == (1, 2 * 224, 3 * 224, 3) and np.array_equal(sheet[0, :224], anim[0]) and np.array_equal(sheet[0, 224:], anim[5])
+    assert anim[0, :, 448:].reshape(-1, 3).std(axis=0).max() > 0                         # the 3D view holds the predicted skeleton
+    assert anim[8, :, :224].reshape(-1, 3).std(axis=0).max() == 0                        # a forecast frame: no picture behind it
