@@ -209,9 +209,12 @@ class ResNet50Backbone:
         from .frames import crop_and_resize_video_uint8
         return self.features_u8(crop_and_resize_video_uint8(frames_thwc_u8, box, 224, mode))
 
-    def layer(self, x: torch.Tensor, name: str) -> torch.Tensor:
+    def layer(self, x: torch.Tensor, name: str, pair: bool = False) -> torch.Tensor:
         """Debug hook: named intermediate activation, NHWC (per-layer parity tests).  bf16 tensor in the bf16
-        modes, fp16 tensor in fp16 mode; in fp32x mode the (head, tail) pair is recombined into an fp32 tensor."""
+        modes, fp16 tensor in fp16 mode; in fp32x mode the (head, tail) pair is recombined into an fp32 tensor, or with
+        ``pair=True`` returned as the device holds it: (N,H,W,2*C) bf16 = ``[head(C) | tail(C)]`` per pixel."""
+        if pair and self._precision != PREC_FP32X:
+            raise ValueError("pair=True: only the fp32x precision holds (head, tail) activations")
         x = self._check_input(x)
         n = x.shape[0]
         lib = _lib.load_library()
@@ -224,6 +227,8 @@ class ResNet50Backbone:
         d = [int(v) for v in dims]
         t = buf[: d[0] * d[1] * d[2] * d[3]].view(*d)
         if self._precision == PREC_FP32X:
+            if pair:
+                return t
             c = d[3] // 2
             return t[..., :c].float() + t[..., c:].float()
         if self._precision == PREC_FP16:          # same bytes, the other 16-bit format
@@ -231,22 +236,33 @@ class ResNet50Backbone:
         return t
 
     def packed_params(self, conv_key: str):
-        """Debug hook: (folded bf16 weights in (cout,k,k,cin) order, folded fp32 bias) as the device holds them."""
+        """Debug hook: (folded bf16 weights in (cout,k,k,cin) order, folded fp32 bias) as the device holds them.  In the pair
+        precisions a bottleneck conv gives (w_head, w_tail, bias): the two (cout,k,k,cin) planes of the packed rows, ``[w_head |
+        w_tail]`` in bf16w2 and ``[w_head | w_head | w_tail]`` in fp32x (whose two head copies must agree).  "conv1" is the stem
+        kernel's image in every precision (in fp32x the head image only: the tail image is not served)."""
         from .weights import conv_specs
         spec = {c[0]: c for c in conv_specs()}[conv_key]
         _ck, _bk, cin, cout, k, _s, _p = spec
         lib = _lib.load_library()
         n = C.c_int64()
-        wbytes = 7 * 64 * 64 if conv_key == "conv1" else cout * k * k * cin * 2
+        planes = {PREC_FP32X: 3, PREC_BF16W2: 2}.get(self._precision, 1) if conv_key != "conv1" else 1
+        wbytes = 7 * 64 * 64 if conv_key == "conv1" else cout * k * k * cin * 2 * planes
         w = torch.empty(wbytes // 2, dtype=torch.bfloat16)
         _lib.check(lib.r50_get_packed(self._handle, conv_key.encode(), 0, w.data_ptr(), wbytes, C.byref(n)),
                    self._handle, "r50_get_packed")
+        if planes > 1 and int(n.value) != wbytes:
+            raise _lib.R50Error(f"r50_get_packed({conv_key}): {int(n.value)} bytes, expected {wbytes}")
         b = torch.empty(cout, dtype=torch.float32)
         _lib.check(lib.r50_get_packed(self._handle, conv_key.encode(), 1, b.data_ptr(), cout * 4, C.byref(n)),
                    self._handle, "r50_get_packed")
-        if conv_key != "conv1":
-            w = w.view(cout, k, k, cin)
-        return w, b
+        if conv_key == "conv1":
+            return w, b
+        if planes == 1:
+            return w.view(cout, k, k, cin), b
+        rows = w.view(cout, k, k, planes, cin)
+        if planes == 3 and not torch.equal(rows[..., 0, :].view(torch.int16), rows[..., 1, :].view(torch.int16)):
+            raise _lib.R50Error(f"r50_get_packed({conv_key}): the two w_head copies of the fp32x rows differ")
+        return rows[..., 0, :].contiguous(), rows[..., planes - 1, :].contiguous(), b
 
     # ---- options / profiling ----------------------------------------------------------------
     def set_option(self, key: str, value: int) -> None:

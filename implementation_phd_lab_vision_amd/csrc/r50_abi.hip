@@ -2067,6 +2067,32 @@ static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, con
     return R50_OK;
 }
 
+// The two pair precisions at kernel level: the ConvArgs run_conv builds for R50_PREC_BF16W2 / R50_PREC_FP32X, through the same launcher.
+int r50_op_conv2d_w2(const void* x, int n, int h, int w, int cin, const void* w_pair, const float* bias, const void* res, void* y,
+                     int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
+    ConvArgs a;
+    int rc = fill_conv_args(a, x, n, h, w, cin, w_pair, bias, res, y, cout, ksize, stride, pad, relu, false, true);
+    if (rc) return fail(nullptr, rc, "r50_op_conv2d_w2: invalid arguments");
+    // only igemm_bf16_kernel and igemm_ws_kernel wrap the X chunk index (ConvArgs::x_wrap): the shape-specialised kernels walk K on their own
+    if (tile == kTileC64 || tile == kTileXres || tile == kTileS2 || tile == kTileG8 || tile == kTileG8N7)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_w2: tile id " + std::to_string(tile) + " does not read the weight pair");
+    hipError_t e = launch_igemm(a, tile, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
+                                     std::string("r50_op_conv2d_w2: ") + hipGetErrorString(e));
+    return R50_OK;
+}
+
+int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const void* w_trip, const float* bias, const void* res_pair,
+                        void* y_pair, int cout, int ksize, int stride, int pad, int relu, void* stream) {
+    ConvArgs a;
+    int rc = fill_conv_args(a, x_pair, n, h, w, cin, w_trip, bias, res_pair, y_pair, cout, ksize, stride, pad, relu, true, false);
+    if (rc) return fail(nullptr, rc, "r50_op_conv2d_split: invalid arguments");
+    hipError_t e = launch_igemm(a, 0, (hipStream_t)stream, true);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
+                                     std::string("r50_op_conv2d_split: ") + hipGetErrorString(e));
+    return R50_OK;
+}
+
 int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias_scaled, const void* res, void* y,
                       int cout, int ksize, int stride, int pad, int relu, float oscale, float rscale, int tile, void* stream) {
     if (cin <= 0 || cin % 128) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_fp8: cin must be a multiple of 128");

@@ -81,6 +81,67 @@ def conv2d_bf16(x: torch.Tensor, w_ohwi: torch.Tensor, bias: torch.Tensor, strid
     return y
 
 
+def _pair_out(out: Optional[torch.Tensor], shape, device, name: str) -> torch.Tensor:
+    numel = shape[0] * shape[1] * shape[2] * shape[3]
+    if out is None:
+        return torch.empty(shape, dtype=torch.bfloat16, device=device)
+    _need(out, torch.bfloat16, "out")
+    if out.numel() < numel:
+        raise ValueError(f"{name}: out buffer too small")
+    return out.view(-1)[:numel].view(shape)
+
+
+def conv2d_w2(x: torch.Tensor, w_pair: torch.Tensor, bias: torch.Tensor, stride: int = 1, pad: int = 0, relu: bool = True,
+              residual: Optional[torch.Tensor] = None, tile: int = TILE_AUTO, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One conv launch of the bf16w2 precision (``r50_op_conv2d_w2``): x (N,H,W,Cin) bf16, w_pair (Cout,k,k,2*Cin) bf16 =
+    ``[w_head | w_tail]`` per tap, bias (Cout) fp32 -> (N,Ho,Wo,Cout) bf16.  ``tile`` / ``out`` as in ``conv2d_bf16``; the
+    shape-specialised tile ids (TILE_C64, TILE_XRES, TILE_S2, TILE_G8, TILE_G8_224) are refused."""
+    _need(x, torch.bfloat16, "x"); _need(w_pair, torch.bfloat16, "w_pair"); _need(bias, torch.float32, "bias")
+    n, h, w, cin = x.shape
+    cout, k, k2, cin2 = w_pair.shape
+    if k != k2 or cin2 != 2 * cin or bias.numel() != cout:
+        raise ValueError("conv2d_w2: inconsistent shapes")
+    ho = (h + 2 * pad - k) // stride + 1
+    wo = (w + 2 * pad - k) // stride + 1
+    y = _pair_out(out, (n, ho, wo, cout), x.device, "conv2d_w2")
+    if residual is not None:
+        _need(residual, torch.bfloat16, "residual")
+        if residual.shape != y.shape:
+            raise ValueError("conv2d_w2: residual shape mismatch")
+    with torch.cuda.device(x.device):
+        rc = _lib.load_library().r50_op_conv2d_w2(x.data_ptr(), n, h, w, cin, w_pair.data_ptr(), bias.data_ptr(),
+                                                  residual.data_ptr() if residual is not None else None, y.data_ptr(),
+                                                  cout, k, stride, pad, int(relu), int(tile), _stream(x))
+    _lib.check(rc, None, "r50_op_conv2d_w2")
+    return y
+
+
+def conv2d_split(x_pair: torch.Tensor, w_trip: torch.Tensor, bias: torch.Tensor, stride: int = 1, pad: int = 0, relu: bool = True,
+                 residual_pair: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One conv launch of the fp32x precision (``r50_op_conv2d_split``): x_pair (N,H,W,2*Cin) bf16 = ``[head | tail]`` per pixel,
+    w_trip (Cout,k,k,3*Cin) bf16 = ``[w_head | w_head | w_tail]`` per tap, bias (Cout) fp32, residual_pair (N,Ho,Wo,2*Cout)
+    -> (N,Ho,Wo,2*Cout) bf16 = ``[head | tail]``.  ``out`` as in ``conv2d_bf16``.  The launcher picks the tile from Cout."""
+    _need(x_pair, torch.bfloat16, "x_pair"); _need(w_trip, torch.bfloat16, "w_trip"); _need(bias, torch.float32, "bias")
+    n, h, w, cin2 = x_pair.shape
+    cout, k, k2, cin3 = w_trip.shape
+    if k != k2 or cin2 % 2 or cin3 != 3 * (cin2 // 2) or bias.numel() != cout:
+        raise ValueError("conv2d_split: inconsistent shapes")
+    cin = cin2 // 2
+    ho = (h + 2 * pad - k) // stride + 1
+    wo = (w + 2 * pad - k) // stride + 1
+    y = _pair_out(out, (n, ho, wo, 2 * cout), x_pair.device, "conv2d_split")
+    if residual_pair is not None:
+        _need(residual_pair, torch.bfloat16, "residual_pair")
+        if residual_pair.shape != y.shape:
+            raise ValueError("conv2d_split: residual shape mismatch")
+    with torch.cuda.device(x_pair.device):
+        rc = _lib.load_library().r50_op_conv2d_split(x_pair.data_ptr(), n, h, w, cin, w_trip.data_ptr(), bias.data_ptr(),
+                                                     residual_pair.data_ptr() if residual_pair is not None else None, y.data_ptr(),
+                                                     cout, k, stride, pad, int(relu), _stream(x_pair))
+    _lib.check(rc, None, "r50_op_conv2d_split")
+    return y
+
+
 FP8 = torch.float8_e4m3fn        # OCP e4m3: what gfx950's fp8 MFMA and conversions use
 FP8_MAX = 448.0
 

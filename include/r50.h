@@ -142,7 +142,11 @@ int r50_profile_entry(r50_handle* h, int i, const char** name, int64_t* launches
 
 /* Debug hook: copy the folded+packed parameters of one conv back to the host (BN-fold parity
  * tests).  conv_key e.g. "layer2.0.downsample.0"; what: 0 = bf16 weights in (cout,k,k,cin) order
- * (stem: the kernel's [kh][row][8][4] image), 1 = fp32 folded bias. */
+ * (stem: the kernel's [kh][row][8][4] image), 1 = fp32 folded bias.
+ * Bytes of what = 0 for a bottleneck conv, by precision: bf16 / fp16 cout*k*k*cin*2; R50_PREC_BF16W2 twice that, rows
+ * (cout,k,k,[w_head(cin) | w_tail(cin)]); R50_PREC_FP32X three times, rows (cout,k,k,[w_head | w_head | w_tail]); R50_PREC_FP8 from layer2
+ * on cout*k*k*cin (one e4m3 byte per weight).  "conv1" (the stem): 7*64*64 bytes in every precision -- in R50_PREC_FP32X that is the
+ * head image only, the tail image is not served. */
 int r50_get_packed(r50_handle* h, const char* conv_key, int what, void* dst_host, int64_t capacity_bytes,
                    int64_t* bytes_out);
 
@@ -170,7 +174,25 @@ int r50_op_conv2d_f16(const void* x_nhwc_f16, int n, int h, int w, int cin, cons
                   const float* bias_f32, const void* residual_nhwc_f16, void* y_nhwc_f16,
                   int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
 
-/* fp8 convolution (BASELINE configs[4]: CDNA4 fp8 MFMA), kernel level.  OCP e4m3 activations, weights and output, fp32 accumulation on
+/* The two (head, tail) pair precisions at kernel level (debug hooks for per-kernel parity tests): the conv launches of R50_PREC_BF16W2 and
+ * R50_PREC_FP32X with caller-owned buffers, built and launched exactly as the network's own convs are.  bf16 only; head = bf16(v),
+ * tail = bf16(v - head).  Arguments are checked as in r50_op_conv2d.
+ *  r50_op_conv2d_w2: x (n,h,w,cin) bf16; w_pair (cout,k,k,2*cin) = [w_head(cin) | w_tail(cin)] per tap, the packed layout of bf16w2
+ *    mode; bias, residual, y and `tile` as in r50_op_conv2d: y = bf16(act(x . w_head + x . w_tail + bias [+ residual])), one fp32
+ *    accumulator.  Only the generic, persistent and role-specialised tile ids read a weight pair: the shape-specialised ids (80, 81, 82,
+ *    83, 84) are refused with R50_ERR_INVALID before any launch.
+ *  r50_op_conv2d_split: x_pair (n,h,w,2*cin) = [head(cin) | tail(cin)] per pixel; w_trip (cout,k,k,3*cin) = [w_head | w_head | w_tail]
+ *    per tap, the packed layout of fp32x mode; residual_pair / y_pair (n,ho,wo,2*cout) = [head(cout) | tail(cout)] per pixel:
+ *    v = act(x_head . w_head + x_tail . w_head + x_head . w_tail + bias [+ r_head + r_tail]) in fp32, stored as the pair of v.  No tile
+ *    argument: 64 couts x 128 pixels when cout % 128 != 0, else 128 x 128, as in the network. */
+int r50_op_conv2d_w2(const void* x_nhwc_bf16, int n, int h, int w, int cin, const void* w_pair_bf16, const float* bias_f32,
+                     const void* residual_nhwc_bf16, void* y_nhwc_bf16, int cout, int ksize, int stride, int pad, int relu, int tile,
+                     void* stream);
+int r50_op_conv2d_split(const void* x_pair_bf16, int n, int h, int w, int cin, const void* w_trip_bf16, const float* bias_f32,
+                        const void* residual_pair_bf16, void* y_pair_bf16, int cout, int ksize, int stride, int pad, int relu,
+                        void* stream);
+
+/* fp8 convolution (BASELINE configs[4]: CDNA4 fp8 MFMA), kernel level. OCP e4m3 activations, weights and output, fp32 accumulation on
  * v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales).  x (n,h,w,cin) fp8, w (cout,k,k,cin) fp8, residual / y (n,ho,wo,cout) fp8;
  * with per-tensor scales sx, sw, sr, sy (real value = stored value x scale):
  *   y = fp8( act( acc * oscale + residual * rscale ) ),  acc = bias_scaled + sum x*w,
