@@ -10,7 +10,9 @@ The reference (src/train.py:114-176,370-393)::
     scaler.scale(loss).backward(); scaler.step(optim); scaler.update()
 
 ``TrainableHead`` keeps the model surface of ``model.PHDFor3DJoints`` (constructor, ``load_state_dict`` / ``state_dict`` with the
-reference's keys) and adds ``train_step(feats, joints3d, optim, scaler)``.  Arithmetic on the device, through the C ABI:
+reference's keys) and adds ``train_step(feats, joints3d, optim, scaler)``; its flat buffers, the backward's launch helpers and the tail
+of a step are ``trainable.FlatTrainableHead``'s, shared with phase 2 (train_ar.py) and the joint stage (train_joint.py), as the epoch
+loop below (``open_run`` / ``fit``) is.  Arithmetic on the device, through the C ABI:
 
 * forward as in model.py plus the two ``nn.Dropout(0.5)`` sites (src/model.py:44,52 and :98), applied with byte masks;
 * backward: every dX = dY W and dW = dY^T X is an igemm MFMA launch (``r50_op_conv2d(_f16)``) on operands made K-contiguous by
@@ -52,9 +54,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .model import _GN_EPS, _GROUPS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints, _round_up, expected_keys
-
-DROPOUT_P = 0.5        # ResidualBlock(dropout=0.5), JointRegressor(dropout=0.5): src/model.py:39,87
+from .model import _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints, expected_keys
+from .trainable import (DROPOUT_P, FlatItem, FlatTrainableHead, _Arena, all_reduce_gradients, block_items, input_proj_items,  # noqa: F401
+                        regressor_items, sync_overflow_flag)
 
 # ---- geometric losses ---------------------------------------------------------------------------------
 # The 16-edge tree of the 17-joint H3.6M layout (src/train.py:29-35): hip -> right leg, left leg, spine -> head, left arm, right arm.
@@ -232,134 +234,24 @@ def trainable_names(number_blocks: int) -> List[str]:
     return names + ["input_proj.weight", "input_proj.bias"]
 
 
-def all_reduce_gradients(flat_grad: torch.Tensor, group=None) -> None:
-    """Average the flat gradient buffer over the ranks: one all-reduce per step (RCCL over xGMI on GPUs; gloo in the CPU tests)."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()):
-        return
-    world = dist.get_world_size(group)
-    if world == 1:
-        return
-    dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=group)
-    flat_grad.mul_(1.0 / world)
+def phase1_items(number_blocks: int) -> List[FlatItem]:
+    """Phase 1's flat buffer, in order: input_proj, f_movie's blocks (each gn1, gn2, conv1, conv2), the regressor."""
+    items = input_proj_items()
+    for i in range(number_blocks):
+        items += block_items(f"f_movie.blocks.{i}", ("gn1", "gn2", "conv1", "conv2"))
+    return items + regressor_items()
 
 
-def sync_overflow_flag(found: torch.Tensor, group=None) -> None:
-    """Make the skip decision of a data-parallel step GLOBAL: MAX-reduce the found-overflow flag over the ranks, so every
-    replica skips (and backs its loss scale off) or steps together.  Needed because an fp16 overflow on ONE rank is a
-    saturated 65504 -- finite -- so after the gradient all-reduce the averaged buffer is finite everywhere and only the
-    overflowing rank's own arena check fires.  The reference's ``nn.DataParallel`` has one scaler and one optimizer
-    (src/train.py:382-393) and cannot disagree with itself; this is the one-process-per-GPU equivalent."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return
-    dist.all_reduce(found, op=dist.ReduceOp.MAX, group=group)
+class TrainableHead(FlatTrainableHead):
+    """``PHDFor3DJoints`` with the phase-1 trainable parameters (input_proj, f_movie, f_3D) in flat fp32 / 16-bit buffers.
+    ``last_losses``: ``GEO_KEYS`` of the last train_step that was given ``geo``."""
 
-
-class _Arena:
-    """Bump allocator for the backward pass's GEMM outputs: one 16-bit buffer, so ONE overflow check covers every gradient the matrix
-    cores produced in a step (and nothing is allocated per step once the first step has sized it)."""
-
-    def __init__(self, device, dtype):
-        self.device, self.dtype = device, dtype
-        self.chunks: List[torch.Tensor] = []
-        self.used: List[int] = []
-
-    def reset(self) -> None:
-        total = sum(self.used)
-        if len(self.chunks) != 1 or self.chunks[0].numel() < total:
-            self.chunks = [torch.empty(max(total, 1 << 20), dtype=self.dtype, device=self.device)]
-        self.used = [0]
-
-    def take(self, rows: int, cols: int) -> torch.Tensor:
-        n = _round_up(rows * cols, 64)
-        if self.used[-1] + n > self.chunks[-1].numel():
-            self.chunks.append(torch.empty(max(n, 1 << 22), dtype=self.dtype, device=self.device))
-            self.used.append(0)
-        o = self.used[-1]
-        self.used[-1] = o + n
-        return self.chunks[-1][o: o + rows * cols].view(rows, cols)
-
-
-class _BackwardLaunches:
-    """The launches of a lifting-head backward pass, shared by the phase-1 (``TrainableHead``) and phase-2 (``train_ar.ARTrainableHead``)
-    heads.  The head provides ``flat_grad`` / ``_off`` (its flat gradient layout), ``_arena``, ``_zero_bias`` and the ``PHDFor3DJoints``
-    members (device, element type, stream, weights)."""
-
-    def grad_view(self, name: str) -> torch.Tensor:
-        o_, shape = self._off[name]
-        return self.flat_grad[o_: o_ + int(torch.Size(shape).numel())].view(shape)
-
-    # ---- launch helpers -----------------------------------------------------------------------
-    def _mm(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-        """x (R, K) @ w (N, K)^T -> (R, N), 16-bit out, fp32 accumulation, no bias: one igemm launch."""
-        rows, k = x.shape
-        n = w.shape[0]
-        assert w.shape[1] == k and x.is_contiguous() and w.is_contiguous() and k % 64 == 0 and n % 64 == 0
-        y = self._arena.take(rows, n)
-        lib = _lib.load_library()
-        fn = lib.r50_op_conv2d_f16 if self._et else lib.r50_op_conv2d
-        _lib.check(fn(x.data_ptr(), rows, 1, 1, k, w.data_ptr(), self._zero_bias.data_ptr(), None, y.data_ptr(), n, 1, 1, 0, 0, 0,
-                      self._stream()), None, "r50_op_conv2d (lifting head backward)")
-        return y
-
-    def _t(self, x: torch.Tensor) -> torch.Tensor:
-        """(R, C) -> (C, Rp) transposed, Rp = R rounded up to 64 with zero padding (the K of a dW product)."""
-        rows, cols = x.shape
-        rp = _round_up(rows, 64)
-        out = torch.zeros((cols, rp), dtype=self._dtype, device=self._device) if rp != rows else \
-            torch.empty((cols, rp), dtype=self._dtype, device=self._device)
-        _lib.check(_lib.load_library().r50_op_transpose16(x.data_ptr(), rows, cols, out.data_ptr(), rp, self._stream()), None,
-                   "r50_op_transpose16")
-        return out
-
-    def _wgrad(self, name: str, dy: torch.Tensor, x: torch.Tensor, inv_scale: float, accumulate: bool, bias: Optional[str] = None) -> None:
-        """flat_grad[name] (N, K) [+]= inv_scale * dy (R, N)^T x (R, K); flat_grad[bias] (N) [+]= inv_scale * column sums of dy."""
-        lib = _lib.load_library()
-        dw = self._mm(self._t(dy), self._t(x))                    # (N, Rp) @ (K, Rp)^T -> (N, K)
-        gv = self.grad_view(name)
-        assert tuple(dw.shape) == tuple(gv.shape)
-        _lib.check(lib.r50_op_grad_accum(dw.data_ptr(), inv_scale, gv.data_ptr(), dw.numel(), int(accumulate), self._et, self._stream()),
-                   None, "r50_op_grad_accum")
-        if bias is not None:
-            gb = self.grad_view(bias)
-            _lib.check(lib.r50_op_colsum(dy.data_ptr(), dy.shape[0], dy.shape[1], dy.shape[1], inv_scale, gb.data_ptr(), int(accumulate),
-                                         self._et, self._stream()), None, "r50_op_colsum")
-
-    def _mask_scale(self, x: torch.Tensor, mask: torch.Tensor, scale: float) -> None:
-        assert mask.dtype == torch.uint8 and mask.numel() == x.numel() and mask.is_contiguous()
-        _lib.check(_lib.load_library().r50_op_mask_scale(x.data_ptr(), mask.data_ptr(), scale, x.numel(), self._et, self._stream()), None,
-                   "r50_op_mask_scale")
-
-    def _relu_bwd(self, dy: torch.Tensor, act: torch.Tensor, scale: float) -> None:
-        _lib.check(_lib.load_library().r50_op_relu_bwd(dy.data_ptr(), act.data_ptr(), scale, dy.numel(), self._et, self._stream()), None,
-                   "r50_op_relu_bwd")
-
-    def _gn_bwd(self, dr: torch.Tensor, x: torch.Tensor, b: int, t: int, prefix: str, add: Optional[torch.Tensor], inv_scale: float) -> torch.Tensor:
-        d = self.latent_dim
-        lib = _lib.load_library()
-        dx = torch.empty((b * t, d), dtype=self._dtype, device=self._device)
-        part = torch.empty((2, b, d), dtype=torch.float32, device=self._device)
-        _lib.check(lib.r50_op_gn_relu_causal3_bwd(dr.data_ptr(), x.data_ptr(), b, t, d, _GROUPS, self._dev[prefix + ".g"].data_ptr(),
-                                                  self._dev[prefix + ".b"].data_ptr(), _GN_EPS, add.data_ptr() if add is not None else None,
-                                                  dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), self._et, self._stream()), None,
-                   "r50_op_gn_relu_causal3_bwd")
-        for j, suffix in ((0, ".g"), (1, ".b")):
-            _lib.check(lib.r50_op_colsum_f32(part[j].data_ptr(), b, d, inv_scale, self.grad_view(prefix + suffix).data_ptr(), 0,
-                                             self._stream()), None, "r50_op_colsum_f32")
-        return dx
-
-
-class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
-    """``PHDFor3DJoints`` with the phase-1 trainable parameters (input_proj, f_movie, f_3D) in flat fp32 / 16-bit buffers."""
+    _no_transpose = frozenset({"input_proj.w"})
 
     def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16"):
         super().__init__(latent_dim, joints_num, number_blocks, precision)
-        self.flat_master: Optional[torch.Tensor] = None
-        self._layout: List[Tuple[str, int, Tuple[int, ...]]] = []
         self._use_graphs = False
         self._graphs: Dict[tuple, tuple] = {}
-        self.last_losses: Dict[str, float] = {}         # GEO_KEYS of the last train_step that was given ``geo``
         self._geo_out8: Optional[torch.Tensor] = None
 
     def enable_graphs(self, on: bool = True) -> "TrainableHead":
@@ -368,132 +260,17 @@ class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
         self._use_graphs = bool(on)
         return self
 
-    def train(self, mode: bool = True):
-        self.training = bool(mode)
-        return self
-
-    # ---- flat parameter buffers (GEMM layout) -------------------------------------------------
-    def _upload(self) -> None:
-        super()._upload()                      # f_AR and y0 (frozen) + everything eval() needs; trainable entries are re-pointed below
-        sd, dev = self._sd, self._device
-        d, o = self.latent_dim, self.out_dim
-        items: List[Tuple[str, torch.Tensor]] = [("input_proj.w", sd["input_proj.weight"]), ("input_proj.b", sd["input_proj.bias"])]
-        for i in range(self.number_blocks):
-            p = f"f_movie.blocks.{i}"
-            for gn in ("gn1", "gn2"):
-                items += [(f"{p}.{gn}.g", sd[f"{p}.{gn}.weight"]), (f"{p}.{gn}.b", sd[f"{p}.{gn}.bias"])]
-            for cv in ("conv1", "conv2"):
-                items += [(f"{p}.{cv}.w", sd[f"{p}.{cv}.conv.weight"].permute(0, 2, 1).reshape(d, 3 * d)),
-                          (f"{p}.{cv}.b", sd[f"{p}.{cv}.conv.bias"])]
-        w0 = torch.zeros(_REG_HIDDEN, self._dp); w0[:, : d + o] = sd["f_3D.mlp.0.weight"]
-        w5 = torch.zeros(self._op, _REG_HIDDEN); w5[:o] = sd["f_3D.mlp.5.weight"]
-        b5 = torch.zeros(self._op); b5[:o] = sd["f_3D.mlp.5.bias"]
-        items += [("mlp0.w", w0), ("mlp0.b", sd["f_3D.mlp.0.bias"]), ("mlp3.w", sd["f_3D.mlp.3.weight"]),
-                  ("mlp3.b", sd["f_3D.mlp.3.bias"]), ("mlp5.w", w5), ("mlp5.b", b5)]
-        self._layout, off = [], 0
-        for name, t in items:
-            assert t.numel() % 64 == 0
-            self._layout.append((name, off, tuple(t.shape)))
-            off += t.numel()
-        self.flat_master = torch.cat([t.reshape(-1).to(torch.float32) for _, t in items]).to(dev)
-        self.flat_w16 = self.flat_master.to(self._dtype)
-        self.flat_grad = torch.zeros_like(self.flat_master)
-        self._off = {name: (o_, shape) for name, o_, shape in self._layout}
-        for name, o_, shape in self._layout:       # weights: the 16-bit copy; biases and GroupNorm parameters: the fp32 master itself
-            n = int(torch.Size(shape).numel())
-            src = self.flat_w16 if name.endswith(".w") else self.flat_master
-            self._dev[name] = src[o_: o_ + n].view(shape)
-        self._wt: Dict[str, torch.Tensor] = {}     # transposed 16-bit weights for the dX products
-        self._refresh_transposes()
-        self._zero_bias = torch.zeros(max(3 * d, 2048, self._dp, _REG_HIDDEN), dtype=torch.float32, device=dev)
-        self._found = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._arena = _Arena(dev, self._dtype)
-
-    def _refresh_transposes(self) -> None:
-        lib = _lib.load_library()
-        for name, _, shape in self._layout:
-            if not name.endswith(".w") or name == "input_proj.w":
-                continue
-            n, k = shape
-            if name not in self._wt:
-                self._wt[name] = torch.zeros((k, n), dtype=self._dtype, device=self._device)
-            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
-                       "r50_op_transpose16")
+    def _flat_items(self) -> List[FlatItem]:
+        return phase1_items(self.number_blocks)
 
     def trainable_parameter_names(self) -> List[str]:
         """The names of the optimizer's parameters, in its numbering: ``trainable_names(number_blocks)``."""
         return trainable_names(self.number_blocks)
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """The reference's keys and layouts (fp32, CPU) from the flat master buffer; frozen entries as loaded."""
-        out = {k: v.clone() for k, v in self._sd.items()}
-        out.update(self.flat_to_reference(self.flat_master))
-        return out
-
-    def named_gradients(self) -> Dict[str, torch.Tensor]:
-        """flat_grad under the reference's parameter names and layouts (fp32, CPU): what ``p.grad`` holds after ``backward()``."""
-        return self.flat_to_reference(self.flat_grad)
-
-    def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """A buffer in the flat parameter layout (master, gradient, AdamW moments) under the reference's names and layouts of the
-        trainable parameters (fp32, CPU); the GEMM padding is dropped."""
-        d, o = self.latent_dim, self.out_dim
-        g = lambda name: flat[self._off[name][0]: self._off[name][0] + int(torch.Size(self._off[name][1]).numel())] \
-            .view(self._off[name][1]).cpu()
-        out = {"input_proj.weight": g("input_proj.w"), "input_proj.bias": g("input_proj.b")}
-        for i in range(self.number_blocks):
-            p = f"f_movie.blocks.{i}"
-            for gn in ("gn1", "gn2"):
-                out[f"{p}.{gn}.weight"], out[f"{p}.{gn}.bias"] = g(f"{p}.{gn}.g"), g(f"{p}.{gn}.b")
-            for cv in ("conv1", "conv2"):
-                out[f"{p}.{cv}.conv.weight"] = g(f"{p}.{cv}.w").view(d, 3, d).permute(0, 2, 1).contiguous()
-                out[f"{p}.{cv}.conv.bias"] = g(f"{p}.{cv}.b")
-        out["f_3D.mlp.0.weight"], out["f_3D.mlp.0.bias"] = g("mlp0.w")[:, : d + o].contiguous(), g("mlp0.b")
-        out["f_3D.mlp.3.weight"], out["f_3D.mlp.3.bias"] = g("mlp3.w"), g("mlp3.b")
-        out["f_3D.mlp.5.weight"], out["f_3D.mlp.5.bias"] = g("mlp5.w")[:o].contiguous(), g("mlp5.b")[:o].contiguous()
-        return out
-
-    def flat_from_reference(self, named: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """Inverse of ``flat_to_reference``: a new device buffer in the flat layout, zero in the GEMM padding."""
-        d, o = self.latent_dim, self.out_dim
-        flat = torch.zeros_like(self.flat_master)
-
-        def v(name):
-            o_, shape = self._off[name]
-            return flat[o_: o_ + int(torch.Size(shape).numel())].view(shape)
-
-        def put(dst, key, shape=None):
-            t = named[key].detach().to(torch.float32)
-            if tuple(t.shape) != tuple(shape if shape is not None else dst.shape):
-                raise ValueError(f"{key}: shape {tuple(t.shape)}, expected {tuple(shape if shape is not None else dst.shape)}")
-            dst.copy_(t)
-
-        put(v("input_proj.w"), "input_proj.weight"); put(v("input_proj.b"), "input_proj.bias")
-        for i in range(self.number_blocks):
-            p = f"f_movie.blocks.{i}"
-            for gn in ("gn1", "gn2"):
-                put(v(f"{p}.{gn}.g"), f"{p}.{gn}.weight"); put(v(f"{p}.{gn}.b"), f"{p}.{gn}.bias")
-            for cv in ("conv1", "conv2"):
-                put(v(f"{p}.{cv}.w").view(d, 3, d).permute(0, 2, 1), f"{p}.{cv}.conv.weight")
-                put(v(f"{p}.{cv}.b"), f"{p}.{cv}.conv.bias")
-        put(v("mlp0.w")[:, : d + o], "f_3D.mlp.0.weight"); put(v("mlp0.b"), "f_3D.mlp.0.bias")
-        put(v("mlp3.w"), "f_3D.mlp.3.weight"); put(v("mlp3.b"), "f_3D.mlp.3.bias")
-        put(v("mlp5.w")[:o], "f_3D.mlp.5.weight"); put(v("mlp5.b")[:o], "f_3D.mlp.5.bias")
-        return flat
-
-    def refresh_weights16(self) -> None:
-        """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
-        self.flat_w16.copy_(self.flat_master.to(self._dtype))
-        self._refresh_transposes()
-
-    def make_dropout_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        """Byte keep-masks (1 = keep, probability 1 - p) for the dropout sites of one step: one per f_movie block (src/model.py:52)
-        and one per regressor iteration (:98)."""
-        def bern(*shape):
-            return (torch.rand(*shape, device=self._device, generator=generator) >= DROPOUT_P).to(torch.uint8)
-        masks = {f"f_movie.blocks.{i}": bern(b * t, self.latent_dim) for i in range(self.number_blocks)}
-        masks.update({f"f_3D.{i}": bern(b * t, _REG_HIDDEN) for i in range(_REG_ITERS)})
-        return masks
+    def _dropout_sites(self) -> List[Tuple[str, int]]:
+        """One per f_movie block (src/model.py:52) and one per regressor iteration (:98)."""
+        return [(f"f_movie.blocks.{i}", self.latent_dim) for i in range(self.number_blocks)] + \
+            [(f"f_3D.{i}", _REG_HIDDEN) for i in range(_REG_ITERS)]
 
     # ---- one training step ------------------------------------------------------------------------
     def _check_geo(self, b: int, t: int, joints2d: Optional[torch.Tensor], K: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -516,13 +293,7 @@ class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
         ``geo``: the loss is l3d + lambda_2d l2d + lambda_vel l_vel + lambda_bone l_bone (section N) on ``joints2d`` (B,T,J,2) and
         ``K`` (B,3,3) or (3,3): ``r50_op_geo_pose_loss_grad`` takes the place of ``r50_op_mse_loss_grad``, nothing else changes;
         loss2 = [the composite loss, mpjpe] and ``self._geo_out8`` holds the op's eight numbers on the device."""
-        if self.flat_master is None:
-            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') first")
-        if feats.dim() != 3 or feats.shape[-1] != 2048 or feats.device != self._device:
-            raise ValueError("feats: expected (B,T,2048) on the head's device")
-        b, t, _ = feats.shape
-        if tuple(joints3d.shape) != (b, t, self.joints_num, 3) or joints3d.device != self._device:
-            raise ValueError("joints3d: expected (B,T,J,3) on the head's device")
+        b, t = self._check_batch(feats, joints3d)
         if geo is not None:
             gt2d, kmat = self._check_geo(b, t, joints2d, K)
         if masks is None and self.training:
@@ -539,19 +310,7 @@ class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
             x0 = torch.empty((rows, 2048), dtype=self._dtype, device=self._device)
             _lib.check(lib.r50_op_cast_rows(f.data_ptr(), rows, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None, "r50_op_cast_rows")
             x = self._gemm(x0, "input_proj", relu=False)
-            saved = []
-            for i in range(self.number_blocks):
-                p = f"f_movie.blocks.{i}"
-                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
-                h = self._gemm(r1, p + ".conv1", relu=False)
-                m = masks[p] if masks is not None else None
-                if m is not None:
-                    self._mask_scale(h, m, keep_scale)
-                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
-                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x)
-                saved.append((x, r1, h, r2, m))
-                x = xo
-            phi = x
+            phi, saved = self._blocks_forward_saved("f_movie", self.number_blocks, x, b, t, masks, keep_scale)
             y = self._dev["y0"].view(1, o).expand(rows, o).contiguous()
             reg = []
             for i in range(_REG_ITERS):
@@ -579,42 +338,14 @@ class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
                 loss2 = torch.stack((out8[0], out8[2]))
                 self._geo_out8 = out8
             # ---------------- backward: regressor, last iteration first ----------------
-            dphi = torch.zeros((rows, d), dtype=torch.float32, device=self._device)
-            g5 = torch.empty((rows, self._op), dtype=self._dtype, device=self._device)
-            for i in reversed(range(_REG_ITERS)):
-                inp, h1, h2 = reg[i]
-                first = i == _REG_ITERS - 1
-                _lib.check(lib.r50_op_cast_rows(dyacc.data_ptr(), rows, o, g5.data_ptr(), self._op, self._et, self._stream()), None, "r50_op_cast_rows")
-                self._wgrad("mlp5.w", g5, h2, inv, not first, bias="mlp5.b")
-                dh2 = self._mm(g5, self._wt["mlp5.w"])                         # (rows, H)
-                self._relu_bwd(dh2, h2, 1.0)
-                self._wgrad("mlp3.w", dh2, h1, inv, not first, bias="mlp3.b")
-                dh1 = self._mm(dh2, self._wt["mlp3.w"])
-                self._relu_bwd(dh1, h1, keep_scale if masks is not None else 1.0)
-                self._wgrad("mlp0.w", dh1, inp, inv, not first, bias="mlp0.b")
-                dinp = self._mm(dh1, self._wt["mlp0.w"])                       # (rows, Dp) = [dphi | dy | 0]
-                _lib.check(lib.r50_op_add_rows(dphi.data_ptr(), d, dinp.data_ptr(), self._dp, rows, self._et, self._stream()), None, "r50_op_add_rows")
-                _lib.check(lib.r50_op_add_rows(dyacc.data_ptr(), o, dinp.data_ptr() + 2 * d, self._dp, rows, self._et, self._stream()), None,
-                           "r50_op_add_rows")
+            dphi, _g5 = self._regressor_backward(reg, dyacc, rows, inv, keep_scale if masks is not None else 1.0, weights=True)
             dx = torch.empty((rows, d), dtype=self._dtype, device=self._device)
             _lib.check(lib.r50_op_cast_rows(dphi.data_ptr(), rows, d, dx.data_ptr(), d, self._et, self._stream()), None, "r50_op_cast_rows")
             # ---------------- backward: f_movie blocks, last first ----------------
             for i in reversed(range(self.number_blocks)):
-                p = f"f_movie.blocks.{i}"
-                xin, r1, h, r2, m = saved[i]
-                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
-                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])                   # (rows, 3D)
-                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
-                if m is not None:
-                    self._mask_scale(dh, m, keep_scale)
-                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
-                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
-                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)         # + the skip connection's gradient
+                dx = self._block_backward(f"f_movie.blocks.{i}", saved[i], dx, b, t, inv, keep_scale)
             self._wgrad("input_proj.w", dx, x0, inv, False, bias="input_proj.b")
-            for chunk, used in zip(self._arena.chunks, self._arena.used):     # every 16-bit gradient the GEMMs wrote this step
-                if used:
-                    _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
-                               "r50_op_check_overflow16")
+            self._check_arena()                                               # every 16-bit gradient the GEMMs wrote this step
         return y.view(b, t, self.joints_num, 3), loss2
 
     def _forward_backward_graphed(self, feats: torch.Tensor, joints3d: torch.Tensor, loss_scale: float,
@@ -667,21 +398,10 @@ class TrainableHead(_BackwardLaunches, PHDFor3DJoints):
             _, loss2 = self._forward_backward_graphed(feats, joints3d, scale, joints2d, K, geo)
         else:
             _, loss2 = self.forward_backward(feats, joints3d, scale, masks, joints2d, K, geo)
-        lib = _lib.load_library()
-        with torch.cuda.device(self._device):
-            all_reduce_gradients(self.flat_grad, group)
-            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
-                       "r50_op_check_finite")
-            sync_overflow_flag(self._found, group)        # any rank overflowed -> every rank skips this step
-            found = bool(self._found.item())              # the reference's scaler.step() synchronises on the same flag
-            if not found:
-                optim.step(self._found)
-                self._refresh_transposes()
-            if scaler is not None:
-                scaler.update(found)
-            l = loss2.cpu()
-            if geo is not None:
-                self.last_losses = dict(zip(GEO_KEYS, self._geo_out8.tolist()))
+        found = self._finish_step(optim, scaler, group)
+        l = loss2.cpu()
+        if geo is not None:
+            self.last_losses = dict(zip(GEO_KEYS, self._geo_out8.tolist()))
         return float(l[0]), float(l[1]), found
 
 
@@ -930,10 +650,25 @@ def geo_json(prefix: str, values: Dict[str, float]) -> Dict[str, float]:
     return {f"{prefix}_{k}": values[k] for k in GEO_EXTRA_KEYS}
 
 
-def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
-    """``main``'s body on parsed arguments.  ``geo_for_epoch``: None (phase 1 as the reference runs it), or a function
-    epoch -> ``GeoWeights`` (``train_geo``): the epoch then trains and validates under section N's composite loss with those weights,
-    and its JSON line gains the geometric numbers and ``lambda_2d_active``."""
+@dataclass
+class Run:
+    """What ``open_run`` set up and ``fit`` drives."""
+    device: torch.device
+    train_set: object
+    val_set: object
+    sampler: object
+    head: FlatTrainableHead
+    optim: AdamW
+    scaler: GradScaler
+    schedule: CosineLR
+    start_epoch: int
+    best_val: float
+
+
+def open_run(args: argparse.Namespace, make_head) -> Run:
+    """The set-up every stage's driver shares: the device, ``--outdir``, the train and validation stores in HBM, the sampler,
+    ``make_head(device)`` (the stage's head, loaded and on the device), AdamW / GradScaler / CosineLR, and ``--resume`` (model and
+    optimizer; a missing file is ignored; GradScaler state is not saved), as the reference does."""
     from .feature_store import DeviceFeatureStore
     from .samplers import MixedShardBatchSampler
 
@@ -944,67 +679,104 @@ def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
     train_set = DeviceFeatureStore(args.train, subjects=args.train_subjects, augment=True, device=device)
     val_set = DeviceFeatureStore(args.val, subjects=args.val_subjects, device=device)
     sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
-
-    head = TrainableHead(1024, JOINTS_NUM, 2, precision=args.precision)
-    head.load_state_dict(default_state_dict(1024, JOINTS_NUM, 2, seed=args.seed))
-    head.to(device)
+    head = make_head(device)
     optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
-    scaler = GradScaler()
-    schedule = CosineLR(args.lr, args.epochs)
-
-    start_epoch, best_val, no_improve_epochs = 0, float("inf"), 0
+    run = Run(device, train_set, val_set, sampler, head, optim, GradScaler(), CosineLR(args.lr, args.epochs), 0, float("inf"))
     if args.resume and os.path.isfile(args.resume):
         ckpt = load_checkpoint(args.resume, head, optim)
-        schedule.load_group(ckpt["optim"])
-        start_epoch = int(ckpt.get("epoch", 0)) + 1
-        best_val = float(ckpt.get("best_val", best_val))
-        print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
+        run.schedule.load_group(ckpt["optim"])
+        run.start_epoch = int(ckpt.get("epoch", 0)) + 1
+        run.best_val = float(ckpt.get("best_val", run.best_val))
+        print(f"Resumed from {args.resume} (start_epoch={run.start_epoch}, best_val={run.best_val:.4f})")
+    return run
 
-    print("===== Phase-1 training =====")
-    print(f"Device: {device} ({args.precision})")
-    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
-    print(f"Batch size: {args.batch_size} | LR: {args.lr} | seed: {args.seed}")
-    print("============================")
-    for epoch in range(start_epoch, args.epochs):
-        sampler.set_epoch(epoch)
+
+def head_from_checkpoint(args: argparse.Namespace, cls, **kwargs):
+    """``make_head`` of the stages that start from weights: ``cls`` at the dimensions of ``--init`` (or, without it, ``--resume``),
+    loaded with that state."""
+    from .results import infer_head_dims, load_head_state
+
+    def make_head(device):
+        state = load_head_state(args.init if args.init else args.resume)
+        latent_dim, joints_num, number_blocks = infer_head_dims(state)
+        head = cls(latent_dim, joints_num, number_blocks, precision=args.precision, **kwargs)
+        head.load_state_dict(state, strict=True)
+        return head.to(device)
+    return make_head
+
+
+def fit(run: Run, args: argparse.Namespace, banner: Sequence[str], epoch_fn, score_label: str, epoch_note=None) -> float:
+    """The epoch loop of every stage's driver, in the reference's order (src/train.py:407-465).  Per epoch: the sampler's epoch and
+    the schedule's LR handed to the optimizer, ``epoch_fn(epoch)`` (trains and validates; returns the validation score, the epoch's
+    JSON fields without ``epoch`` and ``lr``, and the ``Train:`` / ``Val:`` lines), the scheduler step (the saved optimizer state
+    carries the scheduler's next LR, as torch's does), the prints and the JSON line, ``last.pt``, ``best.pt`` when the score improved
+    by more than ``--early-stop-min-delta``, the patience counter.  ``epoch_note(epoch)``: text appended to the epoch's header.
+    Returns the best score."""
+    head, optim, schedule, best_val, no_improve_epochs = run.head, run.optim, run.schedule, run.best_val, 0
+    for text in banner:
+        print(text)
+    for epoch in range(run.start_epoch, args.epochs):
+        run.sampler.set_epoch(epoch)
         optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
-        print(f"\nEpoch {epoch + 1}/{args.epochs}")
+        print(f"\nEpoch {epoch + 1}/{args.epochs}" + (epoch_note(epoch) if epoch_note is not None else ""))
         t0 = time.time()
         epoch_lr = optim.lr
-        geo = geo_for_epoch(epoch) if geo_for_epoch is not None else None
-        tr_loss, tr_mpjpe, steps, skipped, *tr_geo = train_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every,
-                                                                 geo=geo)
-        va_loss, va_mpjpe, va_l3d, va_l2d = evaluate(head, val_set, args.batch_size, geo=geo)
+        score, fields, lines = epoch_fn(epoch)
         schedule.step()
-        optim.lr = schedule.lr            # the saved optimizer state carries the scheduler's next LR, as torch's does
-        print(f"Train: loss={tr_loss:.6f} | mpjpe={tr_mpjpe:.3f}")
-        lambda_2d = geo.lambda_2d if geo is not None else args.lambda_2d      # the weight this epoch applied (0 during the 2D warm-up)
-        print(f"Val:   loss={va_loss:.6f} (3d {va_l3d:.6f} + {lambda_2d:.3g}*2d {va_l2d:.6f}) | mpjpe={va_mpjpe:.3f}")
+        optim.lr = schedule.lr
+        for text in lines:
+            print(text)
         print(f"Epoch time: {time.time() - t0:.2f}s")
-        line = {"epoch": epoch, "lr": epoch_lr, "train_loss": tr_loss, "train_mpjpe": tr_mpjpe, "steps": steps,
-                "skipped": skipped, "val_loss": va_loss, "val_mpjpe": va_mpjpe}
-        if geo is not None:
-            line.update(geo_json("train", tr_geo[0]))
-            line.update(geo_json("val", head.last_eval_geo))
-            line["lambda_2d_active"] = geo.lambda_2d
-        print(json.dumps(line))
+        print(json.dumps({"epoch": epoch, "lr": epoch_lr, **fields}))
 
         save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
-        if (best_val - va_mpjpe) > args.early_stop_min_delta:
-            best_val = va_mpjpe
+        if (best_val - score) > args.early_stop_min_delta:
+            best_val = score
             no_improve_epochs = 0
             save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
-            print(f"New best val MPJPE: {best_val:.3f} (saved best.pt)")
+            print(f"New best val {score_label}: {best_val:.3f} (saved best.pt)")
         else:
             no_improve_epochs += 1
             print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
-                  f"(best {best_val:.3f}, current {va_mpjpe:.3f})")
+                  f"(best {best_val:.3f}, current {score:.3f})")
         if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
-            print(f"Early stopping triggered at epoch {epoch + 1}. Best val MPJPE: {best_val:.3f}")
+            print(f"Early stopping triggered at epoch {epoch + 1}. Best val {score_label}: {best_val:.3f}")
             break
     print("\nDone.")
-    print(f"Best val MPJPE: {best_val:.3f}")
+    print(f"Best val {score_label}: {best_val:.3f}")
     return best_val
+
+
+def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
+    """``main``'s body on parsed arguments.  ``geo_for_epoch``: None (phase 1 as the reference runs it), or a function
+    epoch -> ``GeoWeights`` (``train_geo``): the epoch then trains and validates under section N's composite loss with those weights,
+    and its JSON line gains the geometric numbers and ``lambda_2d_active``."""
+    def make_head(device):
+        head = TrainableHead(1024, JOINTS_NUM, 2, precision=args.precision)
+        head.load_state_dict(default_state_dict(1024, JOINTS_NUM, 2, seed=args.seed))
+        return head.to(device)
+
+    r = open_run(args, make_head)
+
+    def epoch_fn(epoch):
+        geo = geo_for_epoch(epoch) if geo_for_epoch is not None else None
+        tr_loss, tr_mpjpe, steps, skipped, *tr_geo = train_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch,
+                                                                 args.log_every, geo=geo)
+        va_loss, va_mpjpe, va_l3d, va_l2d = evaluate(r.head, r.val_set, args.batch_size, geo=geo)
+        lambda_2d = geo.lambda_2d if geo is not None else args.lambda_2d      # the weight this epoch applied (0 during the 2D warm-up)
+        fields = {"train_loss": tr_loss, "train_mpjpe": tr_mpjpe, "steps": steps, "skipped": skipped, "val_loss": va_loss,
+                  "val_mpjpe": va_mpjpe}
+        if geo is not None:
+            fields.update(geo_json("train", tr_geo[0]))
+            fields.update(geo_json("val", r.head.last_eval_geo))
+            fields["lambda_2d_active"] = geo.lambda_2d
+        return va_mpjpe, fields, (f"Train: loss={tr_loss:.6f} | mpjpe={tr_mpjpe:.3f}",
+                                  f"Val:   loss={va_loss:.6f} (3d {va_l3d:.6f} + {lambda_2d:.3g}*2d {va_l2d:.6f}) | mpjpe={va_mpjpe:.3f}")
+
+    return fit(r, args, ("===== Phase-1 training =====", f"Device: {r.device} ({args.precision})",
+                         f"Train clips: {len(r.train_set)} | Val clips: {len(r.val_set)}",
+                         f"Batch size: {args.batch_size} | LR: {args.lr} | seed: {args.seed}", "============================"),
+               epoch_fn, "MPJPE")
 
 
 if __name__ == "__main__":

@@ -59,17 +59,16 @@ runs back through f_AR with ``r50_op_gn_relu_causal3_tm_bwd`` (t0 = L-1 for the 
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import time
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from .model import _AR_BLOCKS, _GN_EPS, _GROUPS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
-from .train import (DROPOUT_P, AdamW, CosineLR, GradScaler, _Arena, _BackwardLaunches, all_reduce_gradients, build_parser as _phase1_parser,
-                    dropout_generator, save_checkpoint, load_checkpoint, sync_overflow_flag, train_epoch)
+from .model import _AR_BLOCKS, _REG_ITERS
+from .train import (DROPOUT_P, AdamW, GradScaler, build_parser as _phase1_parser, dropout_generator, fit, head_from_checkpoint, open_run,
+                    train_epoch)
+from .trainable import FlatItem, FlatTrainableHead, block_items
 
 LAMBDA_LATENT = 1.0
 INPUT_LEN = 15             # src/config.py
@@ -87,142 +86,33 @@ def ar_trainable_names() -> List[str]:
     return names
 
 
-class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
+def ar_items() -> List[FlatItem]:
+    """Phase 2's flat buffer: f_AR's blocks in order, each gn1, conv1, gn2, conv2."""
+    return [item for i in range(_AR_BLOCKS) for item in block_items(f"f_AR.blocks.{i}")]
+
+
+class ARTrainableHead(FlatTrainableHead):
     """``PHDFor3DJoints`` with f_AR trainable (phase 2) in flat fp32 / 16-bit buffers; input_proj, f_movie and f_3D frozen."""
+
+    _frozen_transposes = ("mlp0.w", "mlp3.w", "mlp5.w")        # the frozen regressor's dX products
+    _clip_rule = (2, "phase 2")
 
     def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
                  lambda_latent: float = LAMBDA_LATENT):
         super().__init__(latent_dim, joints_num, number_blocks, precision)
         self.lambda_latent = float(lambda_latent)
-        self.flat_master: Optional[torch.Tensor] = None
-        self._layout: List[Tuple[str, int, Tuple[int, ...]]] = []
-        self.last_losses: Dict[str, float] = {}
 
-    def train(self, mode: bool = True):
-        self.training = bool(mode)
-        return self
-
-    # ---- flat parameter buffers (GEMM layout) -------------------------------------------------
-    def _upload(self) -> None:
-        super()._upload()                      # every weight eval() needs; the f_AR entries are re-pointed into the flat buffers below
-        sd, dev, d = self._sd, self._device, self.latent_dim
-        items: List[Tuple[str, torch.Tensor]] = []
-        for i in range(_AR_BLOCKS):
-            p = f"f_AR.blocks.{i}"
-            for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
-                items += [(f"{p}.{gn}.g", sd[f"{p}.{gn}.weight"]), (f"{p}.{gn}.b", sd[f"{p}.{gn}.bias"]),
-                          (f"{p}.{cv}.w", sd[f"{p}.{cv}.conv.weight"].permute(0, 2, 1).reshape(d, 3 * d)),
-                          (f"{p}.{cv}.b", sd[f"{p}.{cv}.conv.bias"])]
-        self._layout, off = [], 0
-        for name, t in items:
-            assert t.numel() % 64 == 0
-            self._layout.append((name, off, tuple(t.shape)))
-            off += t.numel()
-        self.flat_master = torch.cat([t.reshape(-1).to(torch.float32) for _, t in items]).to(dev)
-        self.flat_w16 = self.flat_master.to(self._dtype)
-        self.flat_grad = torch.zeros_like(self.flat_master)
-        self._off = {name: (o_, shape) for name, o_, shape in self._layout}
-        for name, o_, shape in self._layout:       # weights: the 16-bit copy; biases and GroupNorm parameters: the fp32 master itself
-            n = int(torch.Size(shape).numel())
-            src = self.flat_w16 if name.endswith(".w") else self.flat_master
-            self._dev[name] = src[o_: o_ + n].view(shape)
-        self._wt: Dict[str, torch.Tensor] = {}     # transposed 16-bit weights for the dX products
-        lib = _lib.load_library()
-        for name in ("mlp0.w", "mlp3.w", "mlp5.w"):   # the frozen regressor's, once
-            n, k = self._dev[name].shape
-            self._wt[name] = torch.empty((k, n), dtype=self._dtype, device=dev)
-            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
-                       "r50_op_transpose16")
-        self._refresh_transposes()
-        self._zero_bias = torch.zeros(max(3 * d, 2048, self._dp, _REG_HIDDEN), dtype=torch.float32, device=dev)
-        self._found = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._arena = _Arena(dev, self._dtype)
-
-    def _refresh_transposes(self) -> None:
-        lib = _lib.load_library()
-        for name, _, shape in self._layout:
-            if not name.endswith(".w"):
-                continue
-            n, k = shape
-            if name not in self._wt:
-                self._wt[name] = torch.zeros((k, n), dtype=self._dtype, device=self._device)
-            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
-                       "r50_op_transpose16")
+    def _flat_items(self) -> List[FlatItem]:
+        return ar_items()
 
     def trainable_parameter_names(self) -> List[str]:
         return ar_trainable_names()
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """The reference's keys and layouts (fp32, CPU): f_AR from the flat master buffer, every other entry as loaded."""
-        out = {k: v.clone() for k, v in self._sd.items()}
-        out.update(self.flat_to_reference(self.flat_master))
-        return out
-
-    def named_gradients(self) -> Dict[str, torch.Tensor]:
-        """flat_grad under the reference's names and layouts (fp32, CPU): what ``p.grad`` of the f_AR parameters holds."""
-        return self.flat_to_reference(self.flat_grad)
-
-    def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """A buffer in the flat layout (master, gradient, AdamW moments) under the reference's f_AR names and layouts (fp32, CPU)."""
-        d = self.latent_dim
-
-        def g(name):
-            o_, shape = self._off[name]
-            return flat[o_: o_ + int(torch.Size(shape).numel())].view(shape).cpu()
-        out = {}
-        for i in range(_AR_BLOCKS):
-            p = f"f_AR.blocks.{i}"
-            for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
-                out[f"{p}.{gn}.weight"], out[f"{p}.{gn}.bias"] = g(f"{p}.{gn}.g"), g(f"{p}.{gn}.b")
-                out[f"{p}.{cv}.conv.weight"] = g(f"{p}.{cv}.w").view(d, 3, d).permute(0, 2, 1).contiguous()
-                out[f"{p}.{cv}.conv.bias"] = g(f"{p}.{cv}.b")
-        return out
-
-    def flat_from_reference(self, named: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """Inverse of ``flat_to_reference``: a new device buffer in the flat layout."""
-        d = self.latent_dim
-        flat = torch.zeros_like(self.flat_master)
-
-        def put(name, key, view=lambda v: v):
-            o_, shape = self._off[name]
-            dst = view(flat[o_: o_ + int(torch.Size(shape).numel())].view(shape))
-            t = named[key].detach().to(torch.float32)
-            if tuple(t.shape) != tuple(dst.shape):
-                raise ValueError(f"{key}: shape {tuple(t.shape)}, expected {tuple(dst.shape)}")
-            dst.copy_(t)
-
-        for i in range(_AR_BLOCKS):
-            p = f"f_AR.blocks.{i}"
-            for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
-                put(f"{p}.{gn}.g", f"{p}.{gn}.weight"); put(f"{p}.{gn}.b", f"{p}.{gn}.bias")
-                put(f"{p}.{cv}.w", f"{p}.{cv}.conv.weight", lambda v: v.view(d, 3, d).permute(0, 2, 1))
-                put(f"{p}.{cv}.b", f"{p}.{cv}.conv.bias")
-        return flat
-
-    def refresh_weights16(self) -> None:
-        """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
-        self.flat_w16.copy_(self.flat_master.to(self._dtype))
-        self._refresh_transposes()
-
-    def make_dropout_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        """Byte keep-masks (1 = keep, probability 1 - p) for the dropout sites of one phase-2 step: one per f_AR block, after its
-        conv1 (src/model.py:52).  f_movie and f_3D run in eval mode."""
-        return {f"f_AR.blocks.{i}": (torch.rand(b * t, self.latent_dim, device=self._device, generator=generator) >= DROPOUT_P)
-                .to(torch.uint8) for i in range(_AR_BLOCKS)}
+    def _dropout_sites(self) -> List[Tuple[str, int]]:
+        """One per f_AR block, after its conv1 (src/model.py:52).  f_movie and f_3D run in eval mode."""
+        return [(f"f_AR.blocks.{i}", self.latent_dim) for i in range(_AR_BLOCKS)]
 
     # ---- launches -------------------------------------------------------------------------------
-    def _check_batch(self, feats: torch.Tensor, joints3d: torch.Tensor) -> Tuple[int, int]:
-        if self.flat_master is None:
-            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') first")
-        if feats.dim() != 3 or feats.shape[-1] != 2048 or feats.device != self._device:
-            raise ValueError("feats: expected (B,T,2048) on the head's device")
-        b, t, _ = feats.shape
-        if tuple(joints3d.shape) != (b, t, self.joints_num, 3) or joints3d.device != self._device:
-            raise ValueError("joints3d: expected (B,T,J,3) on the head's device")
-        if b < 1 or t < 2:
-            raise ValueError("phase 2 needs clips of at least 2 frames (frame 0 has no prediction)")
-        return b, t
-
     def _phi(self, feats: torch.Tensor, b: int, t: int) -> torch.Tensor:
         """input_proj + f_movie, nothing saved: the teacher phi (B*T, D) 16-bit."""
         lib = _lib.load_library()
@@ -270,19 +160,7 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         with torch.cuda.device(self._device):
             # ---------------- forward: phi (frozen, nothing saved), then f_AR keeping what its backward needs ----------------
             phi = self._phi(feats, b, t)
-            x, saved = phi, []
-            for i in range(_AR_BLOCKS):
-                p = f"f_AR.blocks.{i}"
-                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
-                h = self._gemm(r1, p + ".conv1", relu=False)
-                m = masks[p] if masks is not None else None
-                if m is not None:
-                    self._mask_scale(h, m, keep_scale)
-                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
-                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x)
-                saved.append((x, r1, h, r2, m))
-                x = xo
-            ar = x
+            ar, saved = self._blocks_forward_saved("f_AR", _AR_BLOCKS, phi, b, t, masks, keep_scale)
             phi_hat = self._shift(ar, b, t)
             # ---------------- the frozen regressor on phi_hat (eval mode: no dropout) ----------------
             y = self._dev["y0"].view(1, o).expand(rows, o).contiguous()
@@ -295,47 +173,21 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
                 h2 = self._gemm(h1, "mlp3", relu=True)
                 dy = self._gemm(h2, "mlp5", relu=False)
                 _lib.check(lib.r50_op_add_rows(y.data_ptr(), o, dy.data_ptr(), self._op, rows, self._et, self._stream()), None, "r50_op_add_rows")
-                reg.append((h1, h2))
+                reg.append((None, h1, h2))
             # ---------------- future-pose loss and its gradient ----------------
             gt = joints3d.to(torch.float32).contiguous()
             dyacc = torch.empty((rows, o), dtype=torch.float32, device=self._device)
             losses = torch.empty(3, dtype=torch.float32, device=self._device)
             self._pose_loss(y, gt, b, t, loss_scale, dyacc, losses)
             # ---------------- backward through the regressor: dX only (its weights are frozen) ----------------
-            dphi_hat = torch.zeros((rows, d), dtype=torch.float32, device=self._device)
-            g5 = torch.empty((rows, self._op), dtype=self._dtype, device=self._device)
-            for i in reversed(range(_REG_ITERS)):
-                h1, h2 = reg[i]
-                _lib.check(lib.r50_op_cast_rows(dyacc.data_ptr(), rows, o, g5.data_ptr(), self._op, self._et, self._stream()), None, "r50_op_cast_rows")
-                dh2 = self._mm(g5, self._wt["mlp5.w"])                         # (rows, H)
-                self._relu_bwd(dh2, h2, 1.0)
-                dh1 = self._mm(dh2, self._wt["mlp3.w"])
-                self._relu_bwd(dh1, h1, 1.0)
-                dinp = self._mm(dh1, self._wt["mlp0.w"])                       # (rows, Dp) = [dphi_hat | dy | 0]
-                _lib.check(lib.r50_op_add_rows(dphi_hat.data_ptr(), d, dinp.data_ptr(), self._dp, rows, self._et, self._stream()), None,
-                           "r50_op_add_rows")
-                if i > 0:
-                    _lib.check(lib.r50_op_add_rows(dyacc.data_ptr(), o, dinp.data_ptr() + 2 * d, self._dp, rows, self._et, self._stream()),
-                               None, "r50_op_add_rows")
+            dphi_hat, _g5 = self._regressor_backward(reg, dyacc, rows, inv, 1.0, weights=False)
             # ---------------- shift backward + latent loss + cast: f_AR's output gradient, in the arena ----------------
             dx = self._arena.take(rows, d)
             self._latent_loss(ar, phi, dphi_hat, b, t, self.lambda_latent, loss_scale, dx, losses)
             # ---------------- backward: f_AR blocks, last first (phase 1's f_movie launches) ----------------
             for i in reversed(range(_AR_BLOCKS)):
-                p = f"f_AR.blocks.{i}"
-                xin, r1, h, r2, m = saved[i]
-                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
-                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])                   # (rows, 3D)
-                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
-                if m is not None:
-                    self._mask_scale(dh, m, keep_scale)
-                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
-                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
-                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)         # + the skip connection's gradient (unused after block 0)
-            for chunk, used in zip(self._arena.chunks, self._arena.used):     # every 16-bit gradient the GEMMs and the latent kernel wrote
-                if used:
-                    _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
-                               "r50_op_check_overflow16")
+                dx = self._block_backward(f"f_AR.blocks.{i}", saved[i], dx, b, t, inv, keep_scale)     # after block 0: d/dphi, unused (f_movie is frozen)
+            self._check_arena()                                                  # every 16-bit gradient the GEMMs and the latent kernel wrote
         return y.view(b, t, self.joints_num, 3), losses
 
     def train_step(self, feats: torch.Tensor, joints3d: torch.Tensor, optim: AdamW, scaler: Optional[GradScaler] = None,
@@ -344,19 +196,8 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         contract).  Returns (loss, mpjpe_hat, skipped); ``last_losses`` holds loss, l3d_hat, l_lat and mpjpe_hat of the step."""
         scale = scaler.get_scale() if scaler is not None else 1.0
         _, losses = self.forward_backward(feats, joints3d, scale, masks)
-        lib = _lib.load_library()
-        with torch.cuda.device(self._device):
-            all_reduce_gradients(self.flat_grad, group)
-            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
-                       "r50_op_check_finite")
-            sync_overflow_flag(self._found, group)
-            found = bool(self._found.item())
-            if not found:
-                optim.step(self._found)
-                self._refresh_transposes()
-            if scaler is not None:
-                scaler.update(found)
-            l3d_hat, mpjpe_hat, l_lat = losses.tolist()
+        found = self._finish_step(optim, scaler, group)
+        l3d_hat, mpjpe_hat, l_lat = losses.tolist()
         loss = l3d_hat + self.lambda_latent * l_lat
         self.last_losses = {"loss": loss, "l3d_hat": l3d_hat, "l_lat": l_lat, "mpjpe_hat": mpjpe_hat}
         return loss, mpjpe_hat, found
@@ -368,29 +209,6 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         conv1 at rollout step j; drawn in (step, block) order."""
         return [{f"f_AR.blocks.{i}": (torch.rand((input_len + j) * b, self.latent_dim, device=self._device, generator=generator)
                                       >= DROPOUT_P).to(torch.uint8) for i in range(_AR_BLOCKS)} for j in range(k)]
-
-    def _gn_bwd_tm(self, dr: torch.Tensor, x: torch.Tensor, b: int, t: int, t0: int, prefix: str, add: Optional[torch.Tensor],
-                   inv_scale: float, accumulate: bool) -> torch.Tensor:
-        """``r50_op_gn_relu_causal3_tm_bwd``: dx (t*b, D) time-major; the GroupNorm parameter gradients [+]= into flat_grad."""
-        d = self.latent_dim
-        lib = _lib.load_library()
-        dx = torch.empty((b * t, d), dtype=self._dtype, device=self._device)
-        part = torch.empty((2, b, d), dtype=torch.float32, device=self._device)
-        _lib.check(lib.r50_op_gn_relu_causal3_tm_bwd(dr.data_ptr(), x.data_ptr(), b, t, t0, d, _GROUPS, self._dev[prefix + ".g"].data_ptr(),
-                                                     self._dev[prefix + ".b"].data_ptr(), _GN_EPS, add.data_ptr() if add is not None else None,
-                                                     dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), self._et, self._stream()), None,
-                   "r50_op_gn_relu_causal3_tm_bwd")
-        for j, suffix in ((0, ".g"), (1, ".b")):
-            _lib.check(lib.r50_op_colsum_f32(part[j].data_ptr(), b, d, inv_scale, self.grad_view(prefix + suffix).data_ptr(),
-                                             int(accumulate), self._stream()), None, "r50_op_colsum_f32")
-        return dx
-
-    def _check_arena(self) -> None:
-        lib = _lib.load_library()
-        for chunk, used in zip(self._arena.chunks, self._arena.used):
-            if used:
-                _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
-                           "r50_op_check_overflow16")
 
     def rollout_forward_backward(self, feats: torch.Tensor, joints3d: torch.Tensor, input_len: int, k: int, loss_scale: float = 1.0,
                                  masks: Optional[List[Dict[str, torch.Tensor]]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -469,6 +287,7 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
                        "r50_op_rollout_pose_loss_grad")
             dseq = torch.zeros(((i_len + k) * b, d), dtype=torch.float32, device=self._device)
             dfut = dseq[i_len * b:]
+            # ``_regressor_backward(weights=False)``'s launches, written out because they add into dseq's predicted rows, not a new buffer
             g5 = torch.empty((rows, self._op), dtype=self._dtype, device=self._device)
             for i in reversed(range(_REG_ITERS)):
                 h1, h2 = reg[i]
@@ -503,19 +322,19 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
                     if i == last:
                         self._wgrad(p + ".conv2.w", dnew, r2, inv, acc, bias=p + ".conv2.b")
                         dr2 = self._mm(dnew, self._wt[p + ".conv2.w"])         # (B, 3D)
-                        dh = self._gn_bwd_tm(dr2, h, b, n, n - 1, p + ".gn2", None, inv, acc)
+                        dh = self._gn_bwd(dr2, h, b, n, p + ".gn2", None, inv, n - 1, acc)
                         skip = torch.zeros((n * b, d), dtype=self._dtype, device=self._device)
                         skip[(n - 1) * b:].copy_(dnew)                          # the residual reaches frame L-1 only
                     else:
                         self._wgrad(p + ".conv2.w", dx, r2, inv, acc, bias=p + ".conv2.b")
                         dr2 = self._mm(dx, self._wt[p + ".conv2.w"])
-                        dh = self._gn_bwd_tm(dr2, h, b, n, 0, p + ".gn2", None, inv, acc)
+                        dh = self._gn_bwd(dr2, h, b, n, p + ".gn2", None, inv, 0, acc)
                         skip = dx
                     if m is not None:
                         self._mask_scale(dh, m, keep_scale)
                     self._wgrad(p + ".conv1.w", dh, r1, inv, acc, bias=p + ".conv1.b")
                     dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
-                    dx = self._gn_bwd_tm(dr1, xin, b, n, 0, p + ".gn1", skip, inv, acc)
+                    dx = self._gn_bwd(dr1, xin, b, n, p + ".gn1", skip, inv, 0, acc)
                 if j > 0:                                                      # rows of predicted strips; the observed ones are frozen
                     _lib.check(lib.r50_op_add_rows(dseq[i_len * b:].data_ptr(), d, dx[i_len * b:].data_ptr(), d, (n - i_len) * b, self._et,
                                                    self._stream()), None, "r50_op_add_rows")
@@ -529,19 +348,8 @@ class ARTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         scale update.  Returns (loss, mpjpe, skipped); ``last_losses`` holds loss, l3d, l_lat and mpjpe of the step."""
         scale = scaler.get_scale() if scaler is not None else 1.0
         _, losses = self.rollout_forward_backward(feats, joints3d, input_len, k, scale, masks)
-        lib = _lib.load_library()
-        with torch.cuda.device(self._device):
-            all_reduce_gradients(self.flat_grad, group)
-            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
-                       "r50_op_check_finite")
-            sync_overflow_flag(self._found, group)
-            found = bool(self._found.item())
-            if not found:
-                optim.step(self._found)
-                self._refresh_transposes()
-            if scaler is not None:
-                scaler.update(found)
-            l3d, mpjpe, l_lat = losses.tolist()
+        found = self._finish_step(optim, scaler, group)
+        l3d, mpjpe, l_lat = losses.tolist()
         loss = l3d + self.lambda_latent * l_lat
         self.last_losses = {"loss": loss, "l3d": l3d, "l_lat": l_lat, "mpjpe": mpjpe}
         return loss, mpjpe, found
@@ -666,12 +474,12 @@ def train_rollout_epoch(head: ARTrainableHead, store, sampler, optim: AdamW, sca
 
 
 def main(argv: Optional[List[str]] = None) -> float:
-    """Phase 2 on one MI355X.  Per epoch, in ``train.main``'s order: train, evaluate, scheduler step, ``last.pt``, ``best.pt`` when the
-    validation future MPJPE improved by more than ``--early-stop-min-delta``, patience counter.  ``--resume`` loads model and
-    optimizer; the head's dimensions come from the checkpoint.  Prints one JSON line per epoch.  Returns the best val future MPJPE."""
+    """Phase 2 on one MI355X.  Per epoch, in ``train.main``'s order (``train.fit``): train, evaluate, scheduler step, ``last.pt``,
+    ``best.pt`` when the validation score improved by more than ``--early-stop-min-delta``, patience counter.  The score is the
+    validation future MPJPE; with ``--objective rollout`` training runs k(e) rollout steps and the score is the ``mpjpe_mean`` of
+    ``forecast.evaluate_rollout`` at the full P.  ``--resume`` loads model and optimizer; the head's dimensions come from the
+    checkpoint.  Prints one JSON line per epoch.  Returns the best score."""
     from .feature_store import DeviceFeatureStore
-    from .results import infer_head_dims, load_head_state
-    from .samplers import MixedShardBatchSampler
 
     args = parse_args(argv)
     rollout = getattr(args, "objective", "teacher") == "rollout"
@@ -679,125 +487,41 @@ def main(argv: Optional[List[str]] = None) -> float:
         clip_len = int(DeviceFeatureStore(args.val, subjects=args.val_subjects, max_clips=1, device="cpu").feats.shape[1])
         if args.input_len + args.pred_len > clip_len:
             raise ValueError(f"--input-len + --pred-len = {args.input_len + args.pred_len} exceeds the stores' clip length {clip_len}")
-    if not torch.cuda.is_available():
-        raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
-    device = torch.device("cuda", torch.cuda.current_device())
-    os.makedirs(args.outdir, exist_ok=True)
-    train_set = DeviceFeatureStore(args.train, subjects=args.train_subjects, augment=True, device=device)
-    val_set = DeviceFeatureStore(args.val, subjects=args.val_subjects, device=device)
-    sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
+    r = open_run(args, head_from_checkpoint(args, ARTrainableHead, lambda_latent=args.lambda_latent))
+    title = "===== Phase-2 training (f_AR), rollout objective =====" if rollout else "===== Phase-2 training (f_AR) ====="
+    banner = [title, f"Device: {r.device} ({args.precision}) | head: latent {r.head.latent_dim}, {r.head.number_blocks} f_movie blocks",
+              f"Train clips: {len(r.train_set)} | Val clips: {len(r.val_set)}",
+              f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_latent: {args.lambda_latent} | seed: {args.seed}"]
+    if not rollout:
+        def epoch_fn(epoch):
+            tr_loss, tr_mpjpe_hat, steps, skipped = train_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch,
+                                                                args.log_every)
+            va_l3d_hat, va_mpjpe_hat, va_l_lat, va_mpjpe = evaluate_future(r.head, r.val_set, args.batch_size)
+            return va_mpjpe_hat, {"train_loss": tr_loss, "train_mpjpe_hat": tr_mpjpe_hat, "steps": steps, "skipped": skipped,
+                                  "val_l3d_hat": va_l3d_hat, "val_mpjpe_hat": va_mpjpe_hat, "val_l_lat": va_l_lat, "val_mpjpe": va_mpjpe}, \
+                (f"Train: loss={tr_loss:.6f} | future mpjpe={tr_mpjpe_hat:.3f}",
+                 f"Val:   l3d_hat={va_l3d_hat:.6f} | l_lat={va_l_lat:.6f} | future mpjpe={va_mpjpe_hat:.3f} | mpjpe={va_mpjpe:.3f}")
 
-    resume = bool(args.resume and os.path.isfile(args.resume))
-    state = load_head_state(args.init if args.init else args.resume)
-    latent_dim, joints_num, number_blocks = infer_head_dims(state)
-    head = ARTrainableHead(latent_dim, joints_num, number_blocks, precision=args.precision, lambda_latent=args.lambda_latent)
-    head.load_state_dict(state, strict=True)
-    head.to(device)
-    optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
-    scaler = GradScaler()
-    schedule = CosineLR(args.lr, args.epochs)
+        return fit(r, args, banner + ["=" * len(title)], epoch_fn, "future MPJPE")
 
-    start_epoch, best_val, no_improve_epochs = 0, float("inf"), 0
-    if resume:
-        ckpt = load_checkpoint(args.resume, head, optim)
-        schedule.load_group(ckpt["optim"])
-        start_epoch = int(ckpt.get("epoch", 0)) + 1
-        best_val = float(ckpt.get("best_val", best_val))
-        print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
-
-    if rollout:
-        return _main_rollout(args, head, optim, scaler, schedule, train_set, val_set, sampler, start_epoch, best_val, device,
-                             latent_dim, number_blocks)
-    print("===== Phase-2 training (f_AR) =====")
-    print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
-    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
-    print(f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_latent: {args.lambda_latent} | seed: {args.seed}")
-    print("===================================")
-    for epoch in range(start_epoch, args.epochs):
-        sampler.set_epoch(epoch)
-        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
-        print(f"\nEpoch {epoch + 1}/{args.epochs}")
-        t0 = time.time()
-        epoch_lr = optim.lr
-        tr_loss, tr_mpjpe_hat, steps, skipped = train_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every)
-        va_l3d_hat, va_mpjpe_hat, va_l_lat, va_mpjpe = evaluate_future(head, val_set, args.batch_size)
-        schedule.step()
-        optim.lr = schedule.lr
-        print(f"Train: loss={tr_loss:.6f} | future mpjpe={tr_mpjpe_hat:.3f}")
-        print(f"Val:   l3d_hat={va_l3d_hat:.6f} | l_lat={va_l_lat:.6f} | future mpjpe={va_mpjpe_hat:.3f} | mpjpe={va_mpjpe:.3f}")
-        print(f"Epoch time: {time.time() - t0:.2f}s")
-        print(json.dumps({"epoch": epoch, "lr": epoch_lr, "train_loss": tr_loss, "train_mpjpe_hat": tr_mpjpe_hat, "steps": steps,
-                          "skipped": skipped, "val_l3d_hat": va_l3d_hat, "val_mpjpe_hat": va_mpjpe_hat, "val_l_lat": va_l_lat,
-                          "val_mpjpe": va_mpjpe}))
-
-        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
-        if (best_val - va_mpjpe_hat) > args.early_stop_min_delta:
-            best_val = va_mpjpe_hat
-            no_improve_epochs = 0
-            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
-            print(f"New best val future MPJPE: {best_val:.3f} (saved best.pt)")
-        else:
-            no_improve_epochs += 1
-            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
-                  f"(best {best_val:.3f}, current {va_mpjpe_hat:.3f})")
-        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
-            print(f"Early stopping triggered at epoch {epoch + 1}. Best val future MPJPE: {best_val:.3f}")
-            break
-    print("\nDone.")
-    print(f"Best val future MPJPE: {best_val:.3f}")
-    return best_val
-
-
-def _main_rollout(args, head, optim, scaler, schedule, train_set, val_set, sampler, start_epoch, best_val, device, latent_dim,
-                  number_blocks) -> float:
-    """``main``'s epoch loop for the rollout objective: training with k(e) steps, validation by ``forecast.evaluate_rollout`` at the
-    full P, ``best.pt`` and early stopping on the validation rollout's mpjpe_mean."""
     from .forecast import evaluate_rollout
     i_len, p_len, c = args.input_len, args.pred_len, args.curriculum_steps
-    no_improve_epochs = 0
-    print("===== Phase-2 training (f_AR), rollout objective =====")
-    print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
-    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
-    print(f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_latent: {args.lambda_latent} | seed: {args.seed}")
-    print(f"Input len: {i_len} | pred len: {p_len} | curriculum steps: {c}")
-    print("======================================================")
-    for epoch in range(start_epoch, args.epochs):
-        k = curriculum_k(epoch, p_len, c)
-        sampler.set_epoch(epoch)
-        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
-        print(f"\nEpoch {epoch + 1}/{args.epochs} (k = {k})")
-        t0 = time.time()
-        epoch_lr = optim.lr
-        tr_loss, tr_mpjpe, steps, skipped, tr = train_rollout_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, i_len, k,
-                                                                    args.log_every)
-        va = evaluate_rollout(head, val_set, i_len, p_len, args.batch_size)
-        schedule.step()
-        optim.lr = schedule.lr
-        va_mean = va["mpjpe_mean"]
-        print(f"Train: loss={tr_loss:.6f} | l3d={tr['l3d']:.6f} | l_lat={tr['l_lat']:.6f} | mpjpe={tr_mpjpe:.3f}")
-        print(f"Val:   rollout mpjpe @1={va['mpjpe'][0]:.3f} | @{min(10, p_len)}={va['mpjpe'][min(10, p_len) - 1]:.3f} | "
-              f"@{p_len}={va['mpjpe'][-1]:.3f} | mean={va_mean:.3f}")
-        print(f"Epoch time: {time.time() - t0:.2f}s")
-        print(json.dumps({"epoch": epoch, "lr": epoch_lr, "k": k, "train_loss": tr_loss, "train_l3d": tr["l3d"], "train_l_lat": tr["l_lat"],
-                          "train_mpjpe": tr_mpjpe, "steps": steps, "skipped": skipped, "val_mpjpe_1": va["mpjpe"][0],
-                          "val_mpjpe_10": va["mpjpe"][min(10, p_len) - 1], f"val_mpjpe_{p_len}": va["mpjpe"][-1], "val_mpjpe_mean": va_mean}))
 
-        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
-        if (best_val - va_mean) > args.early_stop_min_delta:
-            best_val = va_mean
-            no_improve_epochs = 0
-            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
-            print(f"New best val rollout MPJPE: {best_val:.3f} (saved best.pt)")
-        else:
-            no_improve_epochs += 1
-            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
-                  f"(best {best_val:.3f}, current {va_mean:.3f})")
-        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
-            print(f"Early stopping triggered at epoch {epoch + 1}. Best val rollout MPJPE: {best_val:.3f}")
-            break
-    print("\nDone.")
-    print(f"Best val rollout MPJPE: {best_val:.3f}")
-    return best_val
+    def rollout_epoch_fn(epoch):
+        k = curriculum_k(epoch, p_len, c)
+        tr_loss, tr_mpjpe, steps, skipped, tr = train_rollout_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch,
+                                                                    i_len, k, args.log_every)
+        va = evaluate_rollout(r.head, r.val_set, i_len, p_len, args.batch_size)
+        va_mean = va["mpjpe_mean"]
+        return va_mean, {"k": k, "train_loss": tr_loss, "train_l3d": tr["l3d"], "train_l_lat": tr["l_lat"], "train_mpjpe": tr_mpjpe,
+                         "steps": steps, "skipped": skipped, "val_mpjpe_1": va["mpjpe"][0], "val_mpjpe_10": va["mpjpe"][min(10, p_len) - 1],
+                         f"val_mpjpe_{p_len}": va["mpjpe"][-1], "val_mpjpe_mean": va_mean}, \
+            (f"Train: loss={tr_loss:.6f} | l3d={tr['l3d']:.6f} | l_lat={tr['l_lat']:.6f} | mpjpe={tr_mpjpe:.3f}",
+             f"Val:   rollout mpjpe @1={va['mpjpe'][0]:.3f} | @{min(10, p_len)}={va['mpjpe'][min(10, p_len) - 1]:.3f} | "
+             f"@{p_len}={va['mpjpe'][-1]:.3f} | mean={va_mean:.3f}")
+
+    return fit(r, args, banner + [f"Input len: {i_len} | pred len: {p_len} | curriculum steps: {c}", "=" * len(title)], rollout_epoch_fn,
+               "rollout MPJPE", epoch_note=lambda epoch: f" (k = {curriculum_k(epoch, p_len, c)})")
 
 
 if __name__ == "__main__":

@@ -48,19 +48,16 @@ the scaler.  No torch autograd, no CPU fallback.
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import time
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints
-from .train import (DROPOUT_P, GEO_EXTRA_KEYS, GEO_KEYS, AdamW, CosineLR, GeoWeights, GradScaler, TrainableHead, _Arena, _BackwardLaunches,
-                    all_reduce_gradients, build_parser as _phase1_parser, dropout_generator, geo_pose_loss_grad,
-                    load_checkpoint, save_checkpoint, sync_overflow_flag)
-from .train_ar import ARTrainableHead
+from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS
+from .train import (DROPOUT_P, GEO_EXTRA_KEYS, GEO_KEYS, AdamW, GeoWeights, GradScaler, TrainableHead, build_parser as _phase1_parser,
+                    dropout_generator, fit, geo_pose_loss_grad, head_from_checkpoint, open_run)
+from .trainable import FlatItem, FlatTrainableHead, block_items, input_proj_items, regressor_items
 
 LAMBDA_FUTURE = 1.0
 LAMBDA_LATENT = 1.0
@@ -80,8 +77,20 @@ def joint_trainable_names(number_blocks: int) -> List[str]:
     return names + ["input_proj.weight", "input_proj.bias"]
 
 
-class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
+def joint_items(number_blocks: int) -> List[FlatItem]:
+    """The joint flat buffer, in order: f_movie's blocks, f_AR's blocks (each gn1, conv1, gn2, conv2), the regressor, input_proj."""
+    items: List[FlatItem] = []
+    for net, nb in (("f_movie", number_blocks), ("f_AR", _AR_BLOCKS)):
+        for i in range(nb):
+            items += block_items(f"{net}.blocks.{i}")
+    return items + regressor_items() + input_proj_items()
+
+
+class JointTrainableHead(FlatTrainableHead):
     """``PHDFor3DJoints`` with every parameter trainable in flat fp32 / 16-bit buffers."""
+
+    _no_transpose = frozenset({"input_proj.w"})
+    _clip_rule = (2, "joint training")
 
     def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
                  lambda_future: float = LAMBDA_FUTURE, lambda_latent: float = LAMBDA_LATENT):
@@ -90,142 +99,34 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             raise ValueError("joint training needs at least one f_movie block (its last conv2 stores phi)")
         self.lambda_future = float(lambda_future)
         self.lambda_latent = float(lambda_latent)
-        self.flat_master: Optional[torch.Tensor] = None
-        self._layout: List[Tuple[str, int, Tuple[int, ...]]] = []
-        self.last_losses: Dict[str, float] = {}
 
-    def train(self, mode: bool = True):
-        self.training = bool(mode)
-        return self
-
-    # ---- flat parameter buffers (GEMM layout: train.TrainableHead's and train_ar.ARTrainableHead's) ----------------------------
-    def _upload(self) -> None:
-        super()._upload()                      # y0 and every weight eval() needs; the trainable entries are re-pointed below
-        sd, dev = self._sd, self._device
-        d, o = self.latent_dim, self.out_dim
-        items: List[Tuple[str, torch.Tensor]] = []
-        for net, nb in (("f_movie", self.number_blocks), ("f_AR", _AR_BLOCKS)):
-            for i in range(nb):
-                p = f"{net}.blocks.{i}"
-                for gn, cv in (("gn1", "conv1"), ("gn2", "conv2")):
-                    items += [(f"{p}.{gn}.g", sd[f"{p}.{gn}.weight"]), (f"{p}.{gn}.b", sd[f"{p}.{gn}.bias"]),
-                              (f"{p}.{cv}.w", sd[f"{p}.{cv}.conv.weight"].permute(0, 2, 1).reshape(d, 3 * d)),
-                              (f"{p}.{cv}.b", sd[f"{p}.{cv}.conv.bias"])]
-        w0 = torch.zeros(_REG_HIDDEN, self._dp); w0[:, : d + o] = sd["f_3D.mlp.0.weight"]
-        w5 = torch.zeros(self._op, _REG_HIDDEN); w5[:o] = sd["f_3D.mlp.5.weight"]
-        b5 = torch.zeros(self._op); b5[:o] = sd["f_3D.mlp.5.bias"]
-        items += [("mlp0.w", w0), ("mlp0.b", sd["f_3D.mlp.0.bias"]), ("mlp3.w", sd["f_3D.mlp.3.weight"]),
-                  ("mlp3.b", sd["f_3D.mlp.3.bias"]), ("mlp5.w", w5), ("mlp5.b", b5),
-                  ("input_proj.w", sd["input_proj.weight"]), ("input_proj.b", sd["input_proj.bias"])]
-        self._layout, off = [], 0
-        for name, t in items:
-            assert t.numel() % 64 == 0
-            self._layout.append((name, off, tuple(t.shape)))
-            off += t.numel()
-        self.flat_master = torch.cat([t.reshape(-1).to(torch.float32) for _, t in items]).to(dev)
-        self.flat_w16 = self.flat_master.to(self._dtype)
-        self.flat_grad = torch.zeros_like(self.flat_master)
-        self._off = {name: (o_, shape) for name, o_, shape in self._layout}
-        for name, o_, shape in self._layout:       # weights: the 16-bit copy; biases and GroupNorm parameters: the fp32 master itself
-            n = int(torch.Size(shape).numel())
-            src = self.flat_w16 if name.endswith(".w") else self.flat_master
-            self._dev[name] = src[o_: o_ + n].view(shape)
-        self._wt: Dict[str, torch.Tensor] = {}     # transposed 16-bit weights for the dX products
-        self._refresh_transposes()
-        self._zero_bias = torch.zeros(max(3 * d, 2048, self._dp, _REG_HIDDEN), dtype=torch.float32, device=dev)
-        self._colsum_part = torch.empty(16 * max(d, _REG_HIDDEN, self._op), dtype=torch.float32, device=dev)
-        self._found = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._arena = _Arena(dev, self._dtype)
-
-    def _wgrad(self, name: str, dy: torch.Tensor, x: torch.Tensor, inv_scale: float, accumulate: bool, bias: Optional[str] = None) -> None:
-        """``_BackwardLaunches._wgrad`` with the bias gradient by ``r50_op_colsum_split``: ``r50_op_colsum``'s bits, spread over the
-        chip (one-workgroup-per-64-columns column sums over the stacked 2*B*T rows were the step's largest cost)."""
-        lib = _lib.load_library()
-        dw = self._mm(self._t(dy), self._t(x))                    # (N, Rp) @ (K, Rp)^T -> (N, K)
-        gv = self.grad_view(name)
-        assert tuple(dw.shape) == tuple(gv.shape)
-        _lib.check(lib.r50_op_grad_accum(dw.data_ptr(), inv_scale, gv.data_ptr(), dw.numel(), int(accumulate), self._et, self._stream()),
-                   None, "r50_op_grad_accum")
-        if bias is not None:
-            gb = self.grad_view(bias)
-            assert 16 * dy.shape[1] <= self._colsum_part.numel()
-            _lib.check(lib.r50_op_colsum_split(dy.data_ptr(), dy.shape[0], dy.shape[1], dy.shape[1], inv_scale, self._colsum_part.data_ptr(),
-                                               gb.data_ptr(), int(accumulate), self._et, self._stream()), None, "r50_op_colsum_split")
-
-    def _refresh_transposes(self) -> None:
-        lib = _lib.load_library()
-        for name, _, shape in self._layout:
-            if not name.endswith(".w") or name == "input_proj.w":
-                continue
-            n, k = shape
-            if name not in self._wt:
-                self._wt[name] = torch.zeros((k, n), dtype=self._dtype, device=self._device)
-            _lib.check(lib.r50_op_transpose16(self._dev[name].data_ptr(), n, k, self._wt[name].data_ptr(), n, self._stream()), None,
-                       "r50_op_transpose16")
+    def _flat_items(self) -> List[FlatItem]:
+        return joint_items(self.number_blocks)
 
     def trainable_parameter_names(self) -> List[str]:
         """The names of the optimizer's parameters, in its numbering: ``joint_trainable_names(number_blocks)``."""
         return joint_trainable_names(self.number_blocks)
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """The reference's keys and layouts (fp32, CPU): every parameter from the flat master buffer, ``f_3D.y0`` as loaded."""
-        out = {k: v.clone() for k, v in self._sd.items()}
-        out.update(self.flat_to_reference(self.flat_master))
-        return out
-
-    def named_gradients(self) -> Dict[str, torch.Tensor]:
-        """flat_grad under the reference's names and layouts (fp32, CPU), in ``named_parameters()`` order: what ``p.grad`` holds."""
-        return self.flat_to_reference(self.flat_grad)
-
-    def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """A buffer in the flat layout (master, gradient, AdamW moments) under the reference's names and layouts (fp32, CPU), in
-        ``joint_trainable_names`` order.  The phase-1 entries are read as ``TrainableHead`` reads them, f_AR's as
-        ``ARTrainableHead`` does: the layouts are theirs."""
-        out = TrainableHead.flat_to_reference(self, flat)
-        out.update(ARTrainableHead.flat_to_reference(self, flat))
-        return {n: out[n] for n in self.trainable_parameter_names()}
-
-    def flat_from_reference(self, named: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """Inverse of ``flat_to_reference``: a new device buffer in the flat layout, zero in the GEMM padding."""
-        flat = TrainableHead.flat_from_reference(self, named)
-        ar = ARTrainableHead.flat_from_reference(self, named)
-        for name, o_, shape in self._layout:
-            if name.startswith("f_AR."):
-                n = int(torch.Size(shape).numel())
-                flat[o_: o_ + n].copy_(ar[o_: o_ + n])
-        return flat
-
-    def refresh_weights16(self) -> None:
-        """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
-        self.flat_w16.copy_(self.flat_master.to(self._dtype))
-        self._refresh_transposes()
-
-    def make_dropout_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        """Byte keep-masks (1 = keep, probability 1 - p) for every dropout site of one joint step, drawn in this order: one per f_movie
-        block and one per f_AR block after its conv1 (src/model.py:52), (B*T, D); one per iteration of f_3D(phi) ("f_3D.i") and then
-        of f_3D(phi_hat) ("f_3D_hat.i") after the regressor's first ReLU (:98), (B*T, 1024).  The f_movie and f_3D(phi) entries are
+    def _dropout_sites(self) -> List[Tuple[str, int]]:
+        """One per f_movie block and one per f_AR block after its conv1 (src/model.py:52); one per iteration of f_3D(phi) ("f_3D.i")
+        and then of f_3D(phi_hat) ("f_3D_hat.i") after the regressor's first ReLU (:98).  The f_movie and f_3D(phi) entries are
         phase 1's sites under phase 1's names."""
-        def bern(*shape):
-            return (torch.rand(*shape, device=self._device, generator=generator) >= DROPOUT_P).to(torch.uint8)
-        masks = {f"f_movie.blocks.{i}": bern(b * t, self.latent_dim) for i in range(self.number_blocks)}
-        masks.update({f"f_AR.blocks.{i}": bern(b * t, self.latent_dim) for i in range(_AR_BLOCKS)})
-        masks.update({f"f_3D.{i}": bern(b * t, _REG_HIDDEN) for i in range(_REG_ITERS)})
-        masks.update({f"f_3D_hat.{i}": bern(b * t, _REG_HIDDEN) for i in range(_REG_ITERS)})
-        return masks
+        return [(f"{net}.blocks.{i}", self.latent_dim) for net, nb in (("f_movie", self.number_blocks), ("f_AR", _AR_BLOCKS))
+                for i in range(nb)] + [(f"{site}.{i}", _REG_HIDDEN) for site in ("f_3D", "f_3D_hat") for i in range(_REG_ITERS)]
+
+    def _upload(self) -> None:
+        super()._upload()
+        self._colsum_part = torch.empty(16 * max(self.latent_dim, _REG_HIDDEN, self._op), dtype=torch.float32, device=self._device)
+
+    def _bias_grad(self, dy: torch.Tensor, gb: torch.Tensor, inv_scale: float, accumulate: bool) -> None:
+        """By ``r50_op_colsum_split``: ``r50_op_colsum``'s bits, spread over the chip (one-workgroup-per-64-columns column sums over
+        the stacked 2*B*T rows were the step's largest cost)."""
+        assert 16 * dy.shape[1] <= self._colsum_part.numel()
+        _lib.check(_lib.load_library().r50_op_colsum_split(dy.data_ptr(), dy.shape[0], dy.shape[1], dy.shape[1], inv_scale,
+                                                            self._colsum_part.data_ptr(), gb.data_ptr(), int(accumulate), self._et,
+                                                            self._stream()), None, "r50_op_colsum_split")
 
     # ---- launches -------------------------------------------------------------------------------
-    def _check_batch(self, feats: torch.Tensor, joints3d: torch.Tensor) -> Tuple[int, int]:
-        if self.flat_master is None:
-            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') first")
-        if feats.dim() != 3 or feats.shape[-1] != 2048 or feats.device != self._device:
-            raise ValueError("feats: expected (B,T,2048) on the head's device")
-        b, t, _ = feats.shape
-        if tuple(joints3d.shape) != (b, t, self.joints_num, 3) or joints3d.device != self._device:
-            raise ValueError("joints3d: expected (B,T,J,3) on the head's device")
-        if b < 1 or t < 2:
-            raise ValueError("joint training needs clips of at least 2 frames (frame 0 has no prediction)")
-        return b, t
-
     def _joint_pose_loss(self, y: torch.Tensor, gt: torch.Tensor, b: int, t: int, lambda_future: float, loss_scale: float,
                          dy: torch.Tensor, out: torch.Tensor) -> None:
         """out[0:4] = [l3d, mpjpe, l3d_hat, mpjpe_hat]; dy (2*B*T, J*3) fp32 = the gradients of l3d and lambda_future * l3d_hat,
@@ -301,32 +202,9 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             strips = torch.empty((rows2, d), dtype=self._dtype, device=self._device)       # [phi ; phi_hat]
             phi, phi_hat = strips[:rows], strips[rows:]
             x = self._gemm(x0, "input_proj", relu=False)
-            saved_movie = []
-            for i in range(self.number_blocks):
-                p = f"f_movie.blocks.{i}"
-                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
-                h = self._gemm(r1, p + ".conv1", relu=False)
-                m = masks[p] if masks is not None else None
-                if m is not None:
-                    self._mask_scale(h, m, keep_scale)
-                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
-                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x, out=phi if i == self.number_blocks - 1 else None)
-                saved_movie.append((x, r1, h, r2, m))
-                x = xo
+            _, saved_movie = self._blocks_forward_saved("f_movie", self.number_blocks, x, b, t, masks, keep_scale, out_last=phi)
             # ---------------- f_AR over phi (phase 2's), saved; the shift into the second half ----------------
-            x, saved_ar = phi, []
-            for i in range(_AR_BLOCKS):
-                p = f"f_AR.blocks.{i}"
-                r1 = self._gn_relu_rows(x, b, t, p + ".gn1")
-                h = self._gemm(r1, p + ".conv1", relu=False)
-                m = masks[p] if masks is not None else None
-                if m is not None:
-                    self._mask_scale(h, m, keep_scale)
-                r2 = self._gn_relu_rows(h, b, t, p + ".gn2")
-                xo = self._gemm(r2, p + ".conv2", relu=False, residual=x)
-                saved_ar.append((x, r1, h, r2, m))
-                x = xo
-            ar = x
+            ar, saved_ar = self._blocks_forward_saved("f_AR", _AR_BLOCKS, phi, b, t, masks, keep_scale)
             self._shift_into(ar, phi_hat, b, t)
             # ---------------- the regressor once over the 2*B*T stacked rows, each half its own masks ----------------
             y = self._dev["y0"].view(1, o).expand(rows2, o).contiguous()
@@ -352,41 +230,14 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             else:
                 self._geo_out16 = self._geo_pose_loss(y, gt, gt2d, kmat, b, t, geo, self.lambda_future, loss_scale, dyacc, losses)
             # ---------------- backward: the regressor over the stacked rows, with weight gradients (phase 1's launches) ----------------
-            dstrips = torch.zeros((rows2, d), dtype=torch.float32, device=self._device)   # [dphi from f_3D(phi) ; dphi_hat]
-            g5 = torch.empty((rows2, self._op), dtype=self._dtype, device=self._device)
-            for i in reversed(range(_REG_ITERS)):
-                inp, h1, h2 = reg[i]
-                first = i == _REG_ITERS - 1
-                _lib.check(lib.r50_op_cast_rows(dyacc.data_ptr(), rows2, o, g5.data_ptr(), self._op, self._et, self._stream()), None,
-                           "r50_op_cast_rows")
-                self._wgrad("mlp5.w", g5, h2, inv, not first, bias="mlp5.b")
-                dh2 = self._mm(g5, self._wt["mlp5.w"])                         # (2 rows, H)
-                self._relu_bwd(dh2, h2, 1.0)
-                self._wgrad("mlp3.w", dh2, h1, inv, not first, bias="mlp3.b")
-                dh1 = self._mm(dh2, self._wt["mlp3.w"])
-                self._relu_bwd(dh1, h1, keep_scale if masks is not None else 1.0)
-                self._wgrad("mlp0.w", dh1, inp, inv, not first, bias="mlp0.b")
-                dinp = self._mm(dh1, self._wt["mlp0.w"])                       # (2 rows, Dp) = [dstrip | dy | 0]
-                _lib.check(lib.r50_op_add_rows(dstrips.data_ptr(), d, dinp.data_ptr(), self._dp, rows2, self._et, self._stream()), None,
-                           "r50_op_add_rows")
-                if i > 0:
-                    _lib.check(lib.r50_op_add_rows(dyacc.data_ptr(), o, dinp.data_ptr() + 2 * d, self._dp, rows2, self._et, self._stream()),
-                               None, "r50_op_add_rows")
+            relu1_scale = keep_scale if masks is not None else 1.0
+            dstrips, _g5 = self._regressor_backward(reg, dyacc, rows2, inv, relu1_scale, weights=True)     # [dphi from f_3D(phi) ; dphi_hat]
             # ---------------- shift backward + latent loss + cast: f_AR's output gradient, in the arena ----------------
             dx = self._arena.take(rows, d)
             self._latent_loss(ar, phi, dstrips[rows:], b, t, self.lambda_latent, loss_scale, dx, losses[4:])
             # ---------------- backward: f_AR blocks, last first (phase 2's launches) ----------------
             for i in reversed(range(_AR_BLOCKS)):
-                p = f"f_AR.blocks.{i}"
-                xin, r1, h, r2, m = saved_ar[i]
-                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
-                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])
-                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
-                if m is not None:
-                    self._mask_scale(dh, m, keep_scale)
-                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
-                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
-                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)         # + the skip connection: block 0 gives f_AR's d/dphi
+                dx = self._block_backward(f"f_AR.blocks.{i}", saved_ar[i], dx, b, t, inv, keep_scale)     # + the skip connection: block 0 gives f_AR's d/dphi
             # ---------------- the gradient of phi: f_3D(phi)'s + f_AR's input gradient ----------------
             dphi = dstrips[:rows]
             _lib.check(lib.r50_op_add_rows(dphi.data_ptr(), d, dx.data_ptr(), d, rows, self._et, self._stream()), None, "r50_op_add_rows")
@@ -394,21 +245,9 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
             _lib.check(lib.r50_op_cast_rows(dphi.data_ptr(), rows, d, dx.data_ptr(), d, self._et, self._stream()), None, "r50_op_cast_rows")
             # ---------------- backward: f_movie blocks, last first, and input_proj's dW (phase 1's launches) ----------------
             for i in reversed(range(self.number_blocks)):
-                p = f"f_movie.blocks.{i}"
-                xin, r1, h, r2, m = saved_movie[i]
-                self._wgrad(p + ".conv2.w", dx, r2, inv, False, bias=p + ".conv2.b")
-                dr2 = self._mm(dx, self._wt[p + ".conv2.w"])
-                dh = self._gn_bwd(dr2, h, b, t, p + ".gn2", None, inv)
-                if m is not None:
-                    self._mask_scale(dh, m, keep_scale)
-                self._wgrad(p + ".conv1.w", dh, r1, inv, False, bias=p + ".conv1.b")
-                dr1 = self._mm(dh, self._wt[p + ".conv1.w"])
-                dx = self._gn_bwd(dr1, xin, b, t, p + ".gn1", dx, inv)
+                dx = self._block_backward(f"f_movie.blocks.{i}", saved_movie[i], dx, b, t, inv, keep_scale)
             self._wgrad("input_proj.w", dx, x0, inv, False, bias="input_proj.b")
-            for chunk, used in zip(self._arena.chunks, self._arena.used):     # every 16-bit gradient the GEMMs and the latent kernel wrote
-                if used:
-                    _lib.check(lib.r50_op_check_overflow16(chunk.data_ptr(), used, self._found.data_ptr(), self._et, self._stream()), None,
-                               "r50_op_check_overflow16")
+            self._check_arena()                                               # every 16-bit gradient the GEMMs and the latent kernel wrote
         yv = y.view(2, b, t, self.joints_num, 3)
         return yv[0], yv[1], losses
 
@@ -420,20 +259,9 @@ class JointTrainableHead(_BackwardLaunches, PHDFor3DJoints):
         and with ``geo`` also l2d, reproj_px, l_vel, l_bone, n_clamped of each half (the second under ``*_hat``)."""
         scale = scaler.get_scale() if scaler is not None else 1.0
         _, _, losses = self.forward_backward(feats, joints3d, scale, masks, joints2d, K, geo)
-        lib = _lib.load_library()
-        with torch.cuda.device(self._device):
-            all_reduce_gradients(self.flat_grad, group)
-            _lib.check(lib.r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(), self._stream()), None,
-                       "r50_op_check_finite")
-            sync_overflow_flag(self._found, group)
-            found = bool(self._found.item())
-            if not found:
-                optim.step(self._found)
-                self._refresh_transposes()
-            if scaler is not None:
-                scaler.update(found)
-            l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat = losses.tolist()
-            g16 = self._geo_out16.tolist() if geo is not None else None
+        found = self._finish_step(optim, scaler, group)
+        l3d, mpjpe, l3d_hat, mpjpe_hat, l_lat = losses.tolist()
+        g16 = self._geo_out16.tolist() if geo is not None else None
         loss = l3d + self.lambda_future * l3d_hat + self.lambda_latent * l_lat
         self.last_losses = {"loss": loss, "l3d": l3d, "mpjpe": mpjpe, "l3d_hat": l3d_hat, "mpjpe_hat": mpjpe_hat, "l_lat": l_lat}
         if geo is not None:
@@ -604,87 +432,33 @@ def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
     """``main``'s body on parsed arguments.  ``geo_for_epoch``: None, or a function epoch -> ``GeoWeights`` (``train_geo``): the epoch
     then trains and validates under section N's composite loss with those weights, and its JSON line gains the geometric numbers of
     both halves and ``lambda_2d_active``."""
-    from .feature_store import DeviceFeatureStore
-    from .results import infer_head_dims, load_head_state
-    from .samplers import MixedShardBatchSampler
+    r = open_run(args, head_from_checkpoint(args, JointTrainableHead, lambda_future=args.lambda_future, lambda_latent=args.lambda_latent))
 
-    if not torch.cuda.is_available():
-        raise _lib.R50Error("the training driver runs on an MI355X only; there is no CPU fallback")
-    device = torch.device("cuda", torch.cuda.current_device())
-    os.makedirs(args.outdir, exist_ok=True)
-    train_set = DeviceFeatureStore(args.train, subjects=args.train_subjects, augment=True, device=device)
-    val_set = DeviceFeatureStore(args.val, subjects=args.val_subjects, device=device)
-    sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
-
-    resume = bool(args.resume and os.path.isfile(args.resume))
-    state = load_head_state(args.init if args.init else args.resume)
-    latent_dim, joints_num, number_blocks = infer_head_dims(state)
-    head = JointTrainableHead(latent_dim, joints_num, number_blocks, precision=args.precision, lambda_future=args.lambda_future,
-                              lambda_latent=args.lambda_latent)
-    head.load_state_dict(state, strict=True)
-    head.to(device)
-    optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
-    scaler = GradScaler()
-    schedule = CosineLR(args.lr, args.epochs)
-
-    start_epoch, best_val, no_improve_epochs = 0, float("inf"), 0
-    if resume:
-        ckpt = load_checkpoint(args.resume, head, optim)
-        schedule.load_group(ckpt["optim"])
-        start_epoch = int(ckpt.get("epoch", 0)) + 1
-        best_val = float(ckpt.get("best_val", best_val))
-        print(f"Resumed from {args.resume} (start_epoch={start_epoch}, best_val={best_val:.4f})")
-
-    print("===== Joint training (input_proj, f_movie, f_AR, f_3D) =====")
-    print(f"Device: {device} ({args.precision}) | head: latent {latent_dim}, {number_blocks} f_movie blocks")
-    print(f"Train clips: {len(train_set)} | Val clips: {len(val_set)}")
-    print(f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_future: {args.lambda_future} | lambda_latent: {args.lambda_latent} | "
-          f"seed: {args.seed}")
-    print("============================================================")
-    for epoch in range(start_epoch, args.epochs):
-        sampler.set_epoch(epoch)
-        optim.lr, optim.initial_lr = schedule.lr, schedule.initial_lr
-        print(f"\nEpoch {epoch + 1}/{args.epochs}")
-        t0 = time.time()
-        epoch_lr = optim.lr
+    def epoch_fn(epoch):
         geo = geo_for_epoch(epoch) if geo_for_epoch is not None else None
-        tr, steps, skipped = train_joint_epoch(head, train_set, sampler, optim, scaler, args.seed, epoch, args.log_every, geo=geo)
-        va = dict(zip(LOSS_KEYS, evaluate_joint(head, val_set, args.batch_size, geo=geo)))
+        tr, steps, skipped = train_joint_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch, args.log_every, geo=geo)
+        va = dict(zip(LOSS_KEYS, evaluate_joint(r.head, r.val_set, args.batch_size, geo=geo)))
         if geo is not None:
-            va.update(head.last_eval_geo)
-        schedule.step()
-        optim.lr = schedule.lr
+            va.update(r.head.last_eval_geo)
         va_score = va["mpjpe"] + va["mpjpe_hat"]
-        print(f"Train: loss={tr['loss']:.6f} | l3d={tr['l3d']:.6f} | l3d_hat={tr['l3d_hat']:.6f} | l_lat={tr['l_lat']:.6f} | "
-              f"mpjpe={tr['mpjpe']:.3f} | future mpjpe={tr['mpjpe_hat']:.3f}")
-        print(f"Val:   loss={va['loss']:.6f} | l3d={va['l3d']:.6f} | l3d_hat={va['l3d_hat']:.6f} | l_lat={va['l_lat']:.6f} | "
-              f"mpjpe={va['mpjpe']:.3f} | future mpjpe={va['mpjpe_hat']:.3f}")
-        print(f"Epoch time: {time.time() - t0:.2f}s")
-        line = {"epoch": epoch, "lr": epoch_lr}
-        line.update({f"train_{k}": v for k, v in tr.items()})
-        line.update({"steps": steps, "skipped": skipped})
-        line.update({f"val_{k}": v for k, v in va.items()})
-        line["val_mpjpe_sum"] = va_score
+        fields = {f"train_{k}": v for k, v in tr.items()}
+        fields.update({"steps": steps, "skipped": skipped})
+        fields.update({f"val_{k}": v for k, v in va.items()})
+        fields["val_mpjpe_sum"] = va_score
         if geo is not None:
-            line["lambda_2d_active"] = geo.lambda_2d
-        print(json.dumps(line))
+            fields["lambda_2d_active"] = geo.lambda_2d
+        return va_score, fields, (
+            f"Train: loss={tr['loss']:.6f} | l3d={tr['l3d']:.6f} | l3d_hat={tr['l3d_hat']:.6f} | l_lat={tr['l_lat']:.6f} | "
+            f"mpjpe={tr['mpjpe']:.3f} | future mpjpe={tr['mpjpe_hat']:.3f}",
+            f"Val:   loss={va['loss']:.6f} | l3d={va['l3d']:.6f} | l3d_hat={va['l3d_hat']:.6f} | l_lat={va['l_lat']:.6f} | "
+            f"mpjpe={va['mpjpe']:.3f} | future mpjpe={va['mpjpe_hat']:.3f}")
 
-        save_checkpoint(os.path.join(args.outdir, "last.pt"), head, optim, epoch, best_val, args)
-        if (best_val - va_score) > args.early_stop_min_delta:
-            best_val = va_score
-            no_improve_epochs = 0
-            save_checkpoint(os.path.join(args.outdir, "best.pt"), head, optim, epoch, best_val, args)
-            print(f"New best val mpjpe + future mpjpe: {best_val:.3f} (saved best.pt)")
-        else:
-            no_improve_epochs += 1
-            print(f"No improvement for {no_improve_epochs}/{args.early_stop_patience} epochs "
-                  f"(best {best_val:.3f}, current {va_score:.3f})")
-        if args.early_stop_patience > 0 and no_improve_epochs >= args.early_stop_patience:
-            print(f"Early stopping triggered at epoch {epoch + 1}. Best val mpjpe + future mpjpe: {best_val:.3f}")
-            break
-    print("\nDone.")
-    print(f"Best val mpjpe + future mpjpe: {best_val:.3f}")
-    return best_val
+    return fit(r, args, ("===== Joint training (input_proj, f_movie, f_AR, f_3D) =====",
+                         f"Device: {r.device} ({args.precision}) | head: latent {r.head.latent_dim}, {r.head.number_blocks} f_movie blocks",
+                         f"Train clips: {len(r.train_set)} | Val clips: {len(r.val_set)}",
+                         f"Batch size: {args.batch_size} | LR: {args.lr} | lambda_future: {args.lambda_future} | "
+                         f"lambda_latent: {args.lambda_latent} | seed: {args.seed}",
+                         "============================================================"), epoch_fn, "mpjpe + future mpjpe")
 
 
 if __name__ == "__main__":
