@@ -5335,6 +5335,103 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     }
 }
 
+// ---- Global-norm gradient clipping and EMA weights ---------------------------------------------------
+// grad_norm_part_kernel: part[w] = sum of g[i]^2 over workgroup w's slice [w * slice, min((w + 1) * slice, n)), in fp64 (the product
+// of two fp32 values is exact there).  The launcher fixes the workgroup count and `slice` (a multiple of 4, so every slice starts on
+// a 16-byte boundary of an aligned g) from n alone.  A thread walks its slice in rounds of GRAD_NORM_ROUND elements, one 16-byte load
+// per round (scalar loads where the slice's end cuts the vector); its fp64 partial, then a fixed xor-shuffle tree over the wave and a
+// fixed order over the four waves through LDS.  No atomics: the same bits on every run and every device.
+constexpr int GRAD_NORM_ROUND = 256 * 4;             // elements one workgroup reads per round
+constexpr int GRAD_NORM_GRANULE = 4 * GRAD_NORM_ROUND;    // a slice is not made shorter than this ...
+constexpr int GRAD_NORM_MAX_WG = 2048;               // ... until this many workgroups exist; then the slices grow
+
+__device__ __forceinline__ double grad_norm_block_sum(double acc, double* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_norm_part_kernel(const float* __restrict__ g, long long n, long long slice,
+                                                             double* __restrict__ part) {
+    __shared__ double red[4];
+    const long long lo = (long long)blockIdx.x * slice;
+    const long long hi = lo + slice < n ? lo + slice : n;
+    double acc = 0.0;
+    for (long long i = lo + 4ll * threadIdx.x; i < hi; i += GRAD_NORM_ROUND) {
+        if (i + 4 <= hi) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc += (double)x[k] * (double)x[k];
+        } else {
+            for (long long j = i; j < hi; ++j) acc += (double)g[j] * (double)g[j];
+        }
+    }
+    const double s = grad_norm_block_sum(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// grad_norm_finish_kernel (one workgroup): sum = part[0..w) in a fixed order (thread t adds t, t + 256, ...; then the tree above).
+// Not finite (some g is inf / nan: an fp64 sum of fp32 squares cannot overflow otherwise): found[0] = 1, clip2 = {1, float(sqrt(sum))}.
+// Else norm = sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) in fp64 (torch.nn.utils.clip_grad_norm_; max_norm <= 0: coef = 1),
+// clip2 = {float(coef), float(norm)}, and, when found[0] is still 0, stats4 = {steps, steps with coef < 1, sum of norms, largest norm}
+// moves.  found is never cleared here.
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ part, int w, float max_norm, int* found,
+                                                               float* __restrict__ clip2, double* __restrict__ stats4) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < w; i += 256) acc += part[i];
+    const double sum = grad_norm_block_sum(acc, red);
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(sum);
+    if (!(sum <= 1.7976931348623157e308)) {              // inf or nan
+        found[0] = 1;
+        clip2[0] = 1.f; clip2[1] = (float)norm;
+        return;
+    }
+    double coef = 1.0;
+    if (max_norm > 0.f) {
+        coef = (double)max_norm / (norm + 1e-6);
+        if (coef > 1.0) coef = 1.0;
+    }
+    clip2[0] = (float)coef; clip2[1] = (float)norm;
+    if (found[0] == 0) {
+        stats4[0] += 1.0;
+        if (coef < 1.0) stats4[1] += 1.0;
+        stats4[2] += norm;
+        if (norm > stats4[3]) stats4[3] = norm;
+    }
+}
+
+// adamw_kernel with the gradient scaled by clip[0] on the way in (clip null: as it is) and, when ema is given, the lerp form of
+// torch.optim.swa_utils.get_ema_multi_avg_fn on the new parameter: ema += w * (p_new - ema).  g is NOT written: the buffer keeps
+// the unclipped gradient.  The AdamW expressions are adamw_kernel's, so with clip and ema null the bits are its bits.
+template <int ET>
+__global__ __launch_bounds__(256) void adamw_clip_ema_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                             const float* __restrict__ g, unsigned short* __restrict__ p16, long long n,
+                                                             float lr, float b1, float b2, float eps, float wd, float bc1, float sqrt_bc2,
+                                                             const int* __restrict__ found, const float* __restrict__ clip,
+                                                             float* __restrict__ ema, float w) {
+    if (found && found[0]) return;
+    const float step_size = lr / bc1;
+    const float c = clip ? clip[0] : 1.f;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float gi = clip ? __fmul_rn(g[i], c) : g[i];
+        float pi = p[i] * (1.f - lr * wd);
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        const float denom = sqrtf(vi) / sqrt_bc2 + eps;
+        pi -= step_size * (mi / denom);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        p16[i] = st_e<ET>(pi);
+        if (ema) {
+            const float e = ema[i];
+            ema[i] = __fadd_rn(e, __fmul_rn(w, __fsub_rn(pi, e)));
+        }
+    }
+}
+
 // ---- Geometric pose losses: 3D + 2D reprojection + velocity + bone length in one pass ---------------
 //   uv = (K P)[:2] / clamp((K P)[2], min = eps)   (src/train.py:84-110: the numerator is NOT clamped; below the clamp the
 //                                                   denominator carries no gradient, at (K P)[2] == eps it does)

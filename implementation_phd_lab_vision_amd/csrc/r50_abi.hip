@@ -2736,6 +2736,40 @@ int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_
     return ew_done("r50_op_adamw");
 }
 
+// The schedule of grad_norm_part_kernel, from n alone: W = min(ceil(n / GRAD_NORM_GRANULE), GRAD_NORM_MAX_WG) workgroups, each a
+// slice of ceil(n / W) elements rounded up to a multiple of 4.
+static int grad_norm_workgroups(long long n) {
+    return (int)std::min<long long>((n + GRAD_NORM_GRANULE - 1) / GRAD_NORM_GRANULE, GRAD_NORM_MAX_WG);
+}
+
+int r50_op_grad_norm(const float* g, int64_t n, float max_norm, double* part, int n_part, int* found, float* clip2, double* stats4,
+                     void* stream) {
+    if (!g || !part || !found || !clip2 || !stats4) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: null pointer");
+    if (n < 1 || n > (1ll << 40)) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: need 1 <= n <= 2^40");
+    if (max_norm != max_norm) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: max_norm is nan");
+    const int w = grad_norm_workgroups(n);
+    if (n_part < w)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: part holds " + std::to_string(n_part) + " doubles, n = " + std::to_string(n) +
+                                                  " needs " + std::to_string(w));
+    if (!aligned16(g)) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: g must be 16-byte aligned");
+    const long long slice = (((long long)n + w - 1) / w + 3) / 4 * 4;
+    hipLaunchKernelGGL(grad_norm_part_kernel, dim3(w), dim3(256), 0, (hipStream_t)stream, g, (long long)n, slice, part);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)part, w, max_norm, found, clip2,
+                       stats4);
+    return ew_done("r50_op_grad_norm");
+}
+
+int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int step, const int* found_inf, const float* clip, float* ema, float ema_weight, int et,
+                          void* stream) {
+    if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_adamw_clip_ema: invalid arguments");
+    const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
+    R50_ET_LAUNCH(adamw_clip_ema_kernel, dim3(ew_grid(n)), dim3(256), stream, p, m, v, g, (unsigned short*)p16, (long long)n, lr, beta1, beta2,
+                  eps, weight_decay, (float)bc1, (float)std::sqrt(bc2), found_inf, clip, ema, ema_weight);
+    return ew_done("r50_op_adamw_clip_ema");
+}
+
 int64_t r50_stem_scratch_bytes(int n) { return (int64_t)STEM_W_BYTES + (int64_t)n * STEM_HP * STEM_WP * 8; }
 
 int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_dev, void* scratch, void* y, void* stream) {

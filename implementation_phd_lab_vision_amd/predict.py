@@ -330,6 +330,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help=".npy of (N,H,W,3) uint8 frames (memory-mapped), or .npz with `frames` and optionally `box` [top,left,hh,ww], "
                         "`joints2d` (N,J,2) and the camera's `f`, `c`")
     p.add_argument("--model_path", type=str, required=True, help="head checkpoint (its dimensions are read from it)")
+    p.add_argument("--weights-from", choices=("auto", "model", "ema"), default="auto",
+                   help="which weights of --model_path to use: auto = the EMA weights when the checkpoint has them, else the raw ones")
     p.add_argument("--weights", type=str, default=None, help="local torchvision-layout ResNet-50 checkpoint")
     p.add_argument("--synthetic-weights", action="store_true", help="seeded RANDOM backbone weights: for benchmarks / tests only")
     p.add_argument("--weights-seed", type=int, default=0)
@@ -406,7 +408,7 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     state_dict, source = _resolve_weights(args)
     print(f"backbone weights: {source}")
     backbone = ResNet50Backbone(state_dict=state_dict, max_batch=args.frame_batch, precision=args.precision).to(device).eval()
-    head = build_head(load_head_state(args.model_path), backbone._device, args.head_precision)
+    head = build_head(load_head_state(args.model_path, args.weights_from), backbone._device, args.head_precision)
     predictor = VideoPredictor(backbone, head, args.seq_len, args.stride, args.fuse, args.frame_batch, args.window_batch,
                                RESIZE_MODES[args.resize_mode], args.flip_tta)
     os.makedirs(args.out, exist_ok=True)

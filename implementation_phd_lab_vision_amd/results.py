@@ -65,6 +65,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch-size", type=int, default=16)
     p.add_argument("--num-workers", type=int, default=4, help="accepted, no effect: the feature store is resident in HBM")
     p.add_argument("--model_path", type=str, required=True)
+    p.add_argument("--weights-from", choices=WEIGHT_SOURCES, default="auto",
+                   help="which weights of --model_path to evaluate: auto = the EMA weights when the checkpoint has them, else the raw ones")
     p.add_argument("--out", type=str, default="outputs/batch_result_S9.npz")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--save-n", type=int, default=16, help="How many samples from the batch to save")
@@ -170,10 +172,23 @@ def infer_head_dims(state: Dict[str, torch.Tensor]) -> Tuple[int, int, int]:
     return latent_dim, joints_num, (max(blocks) + 1 if blocks else 0)
 
 
-def load_head_state(path: str) -> Dict[str, torch.Tensor]:
+WEIGHT_SOURCES = ("auto", "model", "ema")
+
+
+def load_head_state(path: str, which: str = "auto") -> Dict[str, torch.Tensor]:
     """The state dict of a checkpoint: ``ckpt["model"]`` of a training checkpoint (``train.save_checkpoint``, src/train.py:61-76),
-    or the file itself when it is a plain state dict (src/results.py:181-182).  ``weights_only=True``."""
+    or the file itself when it is a plain state dict (src/results.py:181-182).  ``weights_only=True``.
+    ``which``: a run with ``--ema-decay`` also saves its averaged weights, ``ckpt["ema"]["model"]``.
+    "auto" returns them when the file has them (they are what selected ``best.pt``) and the raw weights otherwise; "model" the raw
+    weights whatever else is there; "ema" the averaged ones, ``ValueError`` when the file has none."""
+    if which not in WEIGHT_SOURCES:
+        raise ValueError(f"which: expected one of {WEIGHT_SOURCES}, got {which!r}")
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    has_ema = isinstance(ckpt, dict) and isinstance(ckpt.get("ema"), dict) and "model" in ckpt["ema"]
+    if which == "ema" and not has_ema:
+        raise ValueError(f"{path}: no EMA weights in this file (it was not written by a run with --ema-decay)")
+    if has_ema and which != "model":
+        return ckpt["ema"]["model"]
     return ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
 
 
@@ -432,7 +447,7 @@ def main(argv: Optional[List[str]] = None) -> str:
         raise SystemExit(f"results: the test set has {len(test_set)} clips, fewer than one batch of {args.batch_size} "
                          "(the loader drops the last incomplete batch); lower --batch-size")
     index_skip = int(torch.load(os.path.join(args.features_root, "index.pt"), map_location="cpu", weights_only=True).get("frame_skip", 1))
-    head = build_head(load_head_state(args.model_path), device, args.precision)
+    head = build_head(load_head_state(args.model_path, args.weights_from), device, args.precision)
     print(f"Head: latent_dim={head.latent_dim} joints={head.joints_num} blocks={head.number_blocks} ({args.precision}) | "
           f"test clips: {len(test_set)}")
 

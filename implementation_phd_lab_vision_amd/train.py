@@ -22,6 +22,9 @@ loop below (``open_run`` / ``fit``) is.  Arithmetic on the device, through the C
 * ``AdamW`` / ``GradScaler``: one flat fp32 parameter / moment / gradient buffer, one ``r50_op_adamw`` launch per step, skipped on
   the device when ``r50_op_check_finite`` raised the flag; the scale follows torch.amp.GradScaler's rule (x0.5 on overflow, x2
   after 2000 clean steps).
+* optional (``AdamW.max_grad_norm`` / ``AdamW.ema``, ``--clip-grad-norm`` / ``--ema-decay``): clipping by
+  the global gradient norm, ``r50_op_grad_norm`` in the finite check's place, and EMA weights kept by ``r50_op_adamw_clip_ema`` in the
+  optimizer's launch; with both off the step's launches are the ones above.
 * f_AR is frozen and its output does not enter the loss (:158-161), so the training step does not run it.
 * multi-GPU: one process per GPU, ``all_reduce_gradients`` averages the flat gradient buffer with ONE RCCL all-reduce per step
   (35.8 M parameters x 4 B = 67.6 MB at train.py's configuration; 16.9 M trainable) instead of nn.DataParallel's scatter /
@@ -55,8 +58,8 @@ import torch
 
 from . import _lib
 from .model import _REG_HIDDEN, _REG_ITERS, PHDFor3DJoints, expected_keys
-from .trainable import (DROPOUT_P, FlatItem, FlatTrainableHead, _Arena, all_reduce_gradients, block_items, input_proj_items,  # noqa: F401
-                        regressor_items, sync_overflow_flag)
+from .trainable import (DROPOUT_P, FlatItem, FlatTrainableHead, WeightEMA, _Arena, all_reduce_gradients, block_items,  # noqa: F401
+                        input_proj_items, regressor_items, sync_overflow_flag)
 
 # ---- geometric losses ---------------------------------------------------------------------------------
 # The 16-edge tree of the 17-joint H3.6M layout (src/train.py:29-35): hip -> right leg, left leg, spine -> head, left arm, right arm.
@@ -159,11 +162,28 @@ class AdamW:
         self.step_count = 0
         self.exp_avg = torch.zeros_like(head.flat_master)
         self.exp_avg_sq = torch.zeros_like(head.flat_master)
+        self.max_grad_norm: Optional[float] = None      # section S: clip the global gradient norm to this (``_finish_step`` reads it)
+        self.ema: Optional[WeightEMA] = None            # section S: averaged weights, updated inside the optimizer's launch
 
     def step(self, found_inf_flag: Optional[torch.Tensor]) -> None:
-        """One update from ``head.flat_grad`` (already unscaled).  The step counter advances only when the update is applied."""
+        """One update from ``head.flat_grad`` (already unscaled).  The step counter advances only when the update is applied.
+        With ``max_grad_norm`` and / or ``ema`` set the launch is ``r50_op_adamw_clip_ema``: the gradient is read times the coefficient
+        ``r50_op_grad_norm`` left in the head's clip buffer (``flat_grad`` itself is NOT changed: ``named_gradients()`` stays the
+        unclipped gradient), and the EMA buffer moves by ``ema.weight()`` towards the new parameters."""
         h = self.head
         self.step_count += 1
+        if self.max_grad_norm is not None or self.ema is not None:
+            ema = self.ema
+            rc = _lib.load_library().r50_op_adamw_clip_ema(
+                h.flat_master.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), h.flat_grad.data_ptr(), h.flat_w16.data_ptr(),
+                h.flat_master.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
+                found_inf_flag.data_ptr() if found_inf_flag is not None else None,
+                h._clip2.data_ptr() if self.max_grad_norm is not None else None, ema.flat.data_ptr() if ema is not None else None,
+                ema.weight() if ema is not None else 0.0, h._et, h._stream())
+            _lib.check(rc, None, "r50_op_adamw_clip_ema")
+            if ema is not None:
+                ema.updates += 1
+            return
         rc = _lib.load_library().r50_op_adamw(h.flat_master.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                                               h.flat_grad.data_ptr(), h.flat_w16.data_ptr(), h.flat_master.numel(), self.lr,
                                               self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
@@ -598,17 +618,29 @@ def train_epoch(head: TrainableHead, store, sampler, optim: AdamW, scaler: Optio
 
 def save_checkpoint(path: str, head: TrainableHead, optim: AdamW, epoch: int, best_val: float, args) -> None:
     """src/train.py:61-76: {"epoch", "best_val", "model" (the reference's state-dict keys), "optim" (torch.optim.AdamW's
-    layout), "args"}.  Tensors, numbers, strings and lists only: it loads with ``torch.load(weights_only=True)``."""
+    layout), "args"}.  Tensors, numbers, strings and lists only: it loads with ``torch.load(weights_only=True)``.
+    With ``optim.ema`` set (section S) one more key, "ema": ``WeightEMA.state_dict()``; "model" stays the raw weights."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save({"epoch": epoch, "best_val": best_val, "model": head.state_dict(), "optim": optim.state_dict(),
-                "args": dict(vars(args)) if isinstance(args, argparse.Namespace) else dict(args)}, path)
+    ckpt = {"epoch": epoch, "best_val": best_val, "model": head.state_dict(), "optim": optim.state_dict(),
+            "args": dict(vars(args)) if isinstance(args, argparse.Namespace) else dict(args)}
+    if optim.ema is not None:
+        ckpt["ema"] = optim.ema.state_dict()
+    torch.save(ckpt, path)
 
 
 def load_checkpoint(path: str, head: TrainableHead, optim: AdamW) -> dict:
-    """Load a checkpoint of ``save_checkpoint`` (or of the reference) into ``head`` and ``optim``; returns the whole dict."""
+    """Load a checkpoint of ``save_checkpoint`` (or of the reference) into ``head`` and ``optim``; returns the whole dict.  With
+    ``optim.ema`` set, the file's "ema" is loaded into it; a file without one (a run that had no EMA) starts the average from the
+    loaded raw weights."""
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     head.load_state_dict(ckpt["model"], strict=True)
     optim.load_state_dict(ckpt["optim"])
+    if optim.ema is not None:
+        if "ema" in ckpt:
+            optim.ema.load_state_dict(ckpt["ema"])
+        else:
+            optim.ema.flat.copy_(head.flat_master)
+            optim.ema.updates = 0
     return ckpt
 
 
@@ -634,7 +666,33 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0, help="seeds the initial weights and the dropout masks")
     p.add_argument("--train-subjects", type=int, nargs="+", default=list(TRAIN_SUBJECTS))
     p.add_argument("--val-subjects", type=int, nargs="+", default=list(VAL_SUBJECTS))
+    # Gradient clipping and EMA weights.  No defaults: a run without these flags has the namespace -- and
+    # the "args" its checkpoints record -- it had before they existed.  Read them with clip_ema_options().
+    p.add_argument("--clip-grad-norm", type=float, default=argparse.SUPPRESS, metavar="FLOAT",
+                   help="clip the global L2 norm of the gradient to this (torch.nn.utils.clip_grad_norm_), > 0 (default: no clipping)")
+    p.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, metavar="FLOAT",
+                   help="keep an exponential moving average of the weights with this decay, in (0, 1); validation, best.pt and early "
+                        "stopping then follow the averaged weights (default: no EMA)")
+    p.add_argument("--ema-no-warmup", action="store_true", default=argparse.SUPPRESS,
+                   help="with --ema-decay: use the decay from the first update on instead of min(decay, (1 + u) / (10 + u))")
     return p
+
+
+def clip_ema_options(args: argparse.Namespace) -> Tuple[Optional[float], Optional[float], bool]:
+    """(--clip-grad-norm or None, --ema-decay or None, EMA warm-up on) of any stage's parsed arguments."""
+    return getattr(args, "clip_grad_norm", None), getattr(args, "ema_decay", None), not getattr(args, "ema_no_warmup", False)
+
+
+def validate_clip_ema(p: argparse.ArgumentParser, args: argparse.Namespace) -> argparse.Namespace:
+    """Section S's rules on parsed arguments (``p.error`` on a breach); every stage's driver calls it."""
+    clip, decay, _ = clip_ema_options(args)
+    if clip is not None and not (clip > 0 and clip != float("inf")):          # also refuses nan
+        p.error("--clip-grad-norm must be finite and > 0")
+    if decay is not None and not 0.0 < decay < 1.0:
+        p.error("--ema-decay must lie in (0, 1)")
+    if hasattr(args, "ema_no_warmup") and decay is None:
+        p.error("--ema-no-warmup applies together with --ema-decay only")
+    return args
 
 
 def main(argv: Optional[List[str]] = None) -> float:
@@ -642,12 +700,38 @@ def main(argv: Optional[List[str]] = None) -> float:
     scheduler step, ``last.pt``, ``best.pt`` when val MPJPE improved by more than ``--early-stop-min-delta``, patience counter.
     ``--resume`` loads model and optimizer (a missing file is ignored; GradScaler state is not saved), as the reference does.
     Also prints one JSON line per epoch.  Returns the best val MPJPE."""
-    return run(build_parser().parse_args(argv))
+    p = build_parser()
+    return run(validate_clip_ema(p, p.parse_args(argv)))
 
 
 def geo_json(prefix: str, values: Dict[str, float]) -> Dict[str, float]:
     """The geometric numbers of one pass for the per-epoch JSON line: ``{prefix}_{l2d, reproj_px, l_vel, l_bone, n_clamped}``."""
     return {f"{prefix}_{k}": values[k] for k in GEO_EXTRA_KEYS}
+
+
+def validate_with_ema(run: "Run", validate):
+    """The validation of one epoch.  ``validate()`` runs the stage's validation pass on the head's current weights and returns
+    (score, JSON fields, the ``Val:`` line).  Without EMA that is the result.  With it (section S) the pass runs twice, once on the
+    raw weights and once inside ``head.swapped_weights(ema.flat)``: the averaged weights' score and fields are returned (they select
+    ``best.pt`` and drive early stopping), the raw weights' numbers follow under the same keys with a ``_raw`` suffix, and both lines
+    are kept."""
+    if run.optim.ema is None:
+        score, fields, line = validate()
+        return score, fields, (line,)
+    _, raw_fields, raw_line = validate()
+    with run.head.swapped_weights(run.optim.ema.flat):
+        score, fields, line = validate()
+    fields = dict(fields)
+    fields.update({f"{k}_raw": v for k, v in raw_fields.items()})
+    return score, fields, (line.replace("Val:  ", "Val:   [EMA]", 1), raw_line.replace("Val:  ", "Val:   [raw]", 1))
+
+
+def clip_fields(run: "Run") -> Dict[str, float]:
+    """The epoch's gradient-norm numbers for its JSON line (empty without ``--clip-grad-norm``); resets the device counters."""
+    if run.optim.max_grad_norm is None:
+        return {}
+    st = run.head.clip_stats(reset=True)
+    return {k: st[k] for k in ("grad_norm_mean", "grad_norm_max", "clipped_frac")}
 
 
 @dataclass
@@ -668,7 +752,8 @@ class Run:
 def open_run(args: argparse.Namespace, make_head) -> Run:
     """The set-up every stage's driver shares: the device, ``--outdir``, the train and validation stores in HBM, the sampler,
     ``make_head(device)`` (the stage's head, loaded and on the device), AdamW / GradScaler / CosineLR, and ``--resume`` (model and
-    optimizer; a missing file is ignored; GradScaler state is not saved), as the reference does."""
+    optimizer; a missing file is ignored; GradScaler state is not saved), as the reference does.  ``--clip-grad-norm`` and
+    ``--ema-decay`` (section S) become ``optim.max_grad_norm`` and ``optim.ema``; ``--resume`` then restores the EMA too."""
     from .feature_store import DeviceFeatureStore
     from .samplers import MixedShardBatchSampler
 
@@ -681,6 +766,10 @@ def open_run(args: argparse.Namespace, make_head) -> Run:
     sampler = MixedShardBatchSampler(train_set, batch_size=args.batch_size, shuffle=True, drop_last=True, seed=0)
     head = make_head(device)
     optim = AdamW(head, lr=args.lr, weight_decay=1e-2)
+    clip, decay, warmup = clip_ema_options(args)
+    optim.max_grad_norm = clip
+    if decay is not None:
+        optim.ema = WeightEMA(head, decay, warmup)
     run = Run(device, train_set, val_set, sampler, head, optim, GradScaler(), CosineLR(args.lr, args.epochs), 0, float("inf"))
     if args.resume and os.path.isfile(args.resume):
         ckpt = load_checkpoint(args.resume, head, optim)
@@ -697,7 +786,7 @@ def head_from_checkpoint(args: argparse.Namespace, cls, **kwargs):
     from .results import infer_head_dims, load_head_state
 
     def make_head(device):
-        state = load_head_state(args.init if args.init else args.resume)
+        state = load_head_state(args.init, getattr(args, "weights_from", "auto")) if args.init else load_head_state(args.resume, "model")
         latent_dim, joints_num, number_blocks = infer_head_dims(state)
         head = cls(latent_dim, joints_num, number_blocks, precision=args.precision, **kwargs)
         head.load_state_dict(state, strict=True)
@@ -762,16 +851,25 @@ def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
         geo = geo_for_epoch(epoch) if geo_for_epoch is not None else None
         tr_loss, tr_mpjpe, steps, skipped, *tr_geo = train_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch,
                                                                  args.log_every, geo=geo)
-        va_loss, va_mpjpe, va_l3d, va_l2d = evaluate(r.head, r.val_set, args.batch_size, geo=geo)
         lambda_2d = geo.lambda_2d if geo is not None else args.lambda_2d      # the weight this epoch applied (0 during the 2D warm-up)
-        fields = {"train_loss": tr_loss, "train_mpjpe": tr_mpjpe, "steps": steps, "skipped": skipped, "val_loss": va_loss,
-                  "val_mpjpe": va_mpjpe}
+
+        def validate():
+            va_loss, va_mpjpe, va_l3d, va_l2d = evaluate(r.head, r.val_set, args.batch_size, geo=geo)
+            va = {"val_loss": va_loss, "val_mpjpe": va_mpjpe}
+            if geo is not None:
+                va.update(geo_json("val", r.head.last_eval_geo))
+            return va_mpjpe, va, f"Val:   loss={va_loss:.6f} (3d {va_l3d:.6f} + {lambda_2d:.3g}*2d {va_l2d:.6f}) | mpjpe={va_mpjpe:.3f}"
+
+        score, va_fields, va_lines = validate_with_ema(r, validate)
+        fields = {"train_loss": tr_loss, "train_mpjpe": tr_mpjpe, "steps": steps, "skipped": skipped, "val_loss": va_fields.pop("val_loss"),
+                  "val_mpjpe": va_fields.pop("val_mpjpe")}
         if geo is not None:
             fields.update(geo_json("train", tr_geo[0]))
-            fields.update(geo_json("val", r.head.last_eval_geo))
+        fields.update(va_fields)
+        if geo is not None:
             fields["lambda_2d_active"] = geo.lambda_2d
-        return va_mpjpe, fields, (f"Train: loss={tr_loss:.6f} | mpjpe={tr_mpjpe:.3f}",
-                                  f"Val:   loss={va_loss:.6f} (3d {va_l3d:.6f} + {lambda_2d:.3g}*2d {va_l2d:.6f}) | mpjpe={va_mpjpe:.3f}")
+        fields.update(clip_fields(r))
+        return score, fields, (f"Train: loss={tr_loss:.6f} | mpjpe={tr_mpjpe:.3f}",) + va_lines
 
     return fit(r, args, ("===== Phase-1 training =====", f"Device: {r.device} ({args.precision})",
                          f"Train clips: {len(r.train_set)} | Val clips: {len(r.val_set)}",

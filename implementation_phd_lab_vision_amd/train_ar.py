@@ -67,7 +67,7 @@ import torch
 from . import _lib
 from .model import _AR_BLOCKS, _REG_ITERS
 from .train import (DROPOUT_P, AdamW, GradScaler, build_parser as _phase1_parser, dropout_generator, fit, head_from_checkpoint, open_run,
-                    train_epoch)
+                    train_epoch, clip_fields, validate_clip_ema, validate_with_ema)
 from .trainable import FlatItem, FlatTrainableHead, block_items
 
 LAMBDA_LATENT = 1.0
@@ -408,6 +408,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="phase-1 checkpoint (its 'model') or plain state dict to start from; required unless --resume names an existing file")
     p.add_argument("--lambda-latent", type=float, default=LAMBDA_LATENT,
                    help="weight of the latent loss mean((phi_hat - phi)^2) over frames >= 1 (no run has measured a good value)")
+    p.add_argument("--weights-from", choices=("auto", "model", "ema"), default=argparse.SUPPRESS,
+                   help="which weights of --init to start from: auto (default) = its EMA weights when it has them, else the raw ones")
     # The rollout objective's flags.  Their defaults are applied by parse_args only for --objective rollout,
     # so a teacher run's namespace -- and the "args" its checkpoints record -- is what it was before these flags existed.
     p.add_argument("--objective", choices=("teacher", "rollout"), default=argparse.SUPPRESS,
@@ -426,7 +428,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     """The driver's arguments.  With ``--objective rollout`` the namespace holds objective, input_len, pred_len and
     curriculum_steps (defaults ``ROLLOUT_DEFAULTS``); without it, none of them."""
     p = build_parser()
-    args = p.parse_args(argv)
+    args = validate_clip_ema(p, p.parse_args(argv))
     if not args.init and not (args.resume and os.path.isfile(args.resume)):
         p.error("--init is required unless --resume names an existing checkpoint")
     if getattr(args, "objective", "teacher") == "rollout":
@@ -496,11 +498,15 @@ def main(argv: Optional[List[str]] = None) -> float:
         def epoch_fn(epoch):
             tr_loss, tr_mpjpe_hat, steps, skipped = train_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch,
                                                                 args.log_every)
-            va_l3d_hat, va_mpjpe_hat, va_l_lat, va_mpjpe = evaluate_future(r.head, r.val_set, args.batch_size)
-            return va_mpjpe_hat, {"train_loss": tr_loss, "train_mpjpe_hat": tr_mpjpe_hat, "steps": steps, "skipped": skipped,
-                                  "val_l3d_hat": va_l3d_hat, "val_mpjpe_hat": va_mpjpe_hat, "val_l_lat": va_l_lat, "val_mpjpe": va_mpjpe}, \
-                (f"Train: loss={tr_loss:.6f} | future mpjpe={tr_mpjpe_hat:.3f}",
-                 f"Val:   l3d_hat={va_l3d_hat:.6f} | l_lat={va_l_lat:.6f} | future mpjpe={va_mpjpe_hat:.3f} | mpjpe={va_mpjpe:.3f}")
+
+            def validate():
+                va_l3d_hat, va_mpjpe_hat, va_l_lat, va_mpjpe = evaluate_future(r.head, r.val_set, args.batch_size)
+                return va_mpjpe_hat, {"val_l3d_hat": va_l3d_hat, "val_mpjpe_hat": va_mpjpe_hat, "val_l_lat": va_l_lat, "val_mpjpe": va_mpjpe}, \
+                    f"Val:   l3d_hat={va_l3d_hat:.6f} | l_lat={va_l_lat:.6f} | future mpjpe={va_mpjpe_hat:.3f} | mpjpe={va_mpjpe:.3f}"
+
+            score, va_fields, va_lines = validate_with_ema(r, validate)
+            return score, {"train_loss": tr_loss, "train_mpjpe_hat": tr_mpjpe_hat, "steps": steps, "skipped": skipped, **va_fields,
+                           **clip_fields(r)}, (f"Train: loss={tr_loss:.6f} | future mpjpe={tr_mpjpe_hat:.3f}",) + va_lines
 
         return fit(r, args, banner + ["=" * len(title)], epoch_fn, "future MPJPE")
 
@@ -511,14 +517,19 @@ def main(argv: Optional[List[str]] = None) -> float:
         k = curriculum_k(epoch, p_len, c)
         tr_loss, tr_mpjpe, steps, skipped, tr = train_rollout_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch,
                                                                     i_len, k, args.log_every)
-        va = evaluate_rollout(r.head, r.val_set, i_len, p_len, args.batch_size)
-        va_mean = va["mpjpe_mean"]
-        return va_mean, {"k": k, "train_loss": tr_loss, "train_l3d": tr["l3d"], "train_l_lat": tr["l_lat"], "train_mpjpe": tr_mpjpe,
-                         "steps": steps, "skipped": skipped, "val_mpjpe_1": va["mpjpe"][0], "val_mpjpe_10": va["mpjpe"][min(10, p_len) - 1],
-                         f"val_mpjpe_{p_len}": va["mpjpe"][-1], "val_mpjpe_mean": va_mean}, \
-            (f"Train: loss={tr_loss:.6f} | l3d={tr['l3d']:.6f} | l_lat={tr['l_lat']:.6f} | mpjpe={tr_mpjpe:.3f}",
-             f"Val:   rollout mpjpe @1={va['mpjpe'][0]:.3f} | @{min(10, p_len)}={va['mpjpe'][min(10, p_len) - 1]:.3f} | "
-             f"@{p_len}={va['mpjpe'][-1]:.3f} | mean={va_mean:.3f}")
+
+        def validate():
+            va = evaluate_rollout(r.head, r.val_set, i_len, p_len, args.batch_size)
+            va_mean = va["mpjpe_mean"]
+            return va_mean, {"val_mpjpe_1": va["mpjpe"][0], "val_mpjpe_10": va["mpjpe"][min(10, p_len) - 1],
+                             f"val_mpjpe_{p_len}": va["mpjpe"][-1], "val_mpjpe_mean": va_mean}, \
+                (f"Val:   rollout mpjpe @1={va['mpjpe'][0]:.3f} | @{min(10, p_len)}={va['mpjpe'][min(10, p_len) - 1]:.3f} | "
+                 f"@{p_len}={va['mpjpe'][-1]:.3f} | mean={va_mean:.3f}")
+
+        score, va_fields, va_lines = validate_with_ema(r, validate)
+        return score, {"k": k, "train_loss": tr_loss, "train_l3d": tr["l3d"], "train_l_lat": tr["l_lat"], "train_mpjpe": tr_mpjpe,
+                       "steps": steps, "skipped": skipped, **va_fields, **clip_fields(r)}, \
+            (f"Train: loss={tr_loss:.6f} | l3d={tr['l3d']:.6f} | l_lat={tr['l_lat']:.6f} | mpjpe={tr_mpjpe:.3f}",) + va_lines
 
     return fit(r, args, banner + [f"Input len: {i_len} | pred len: {p_len} | curriculum steps: {c}", "=" * len(title)], rollout_epoch_fn,
                "rollout MPJPE", epoch_note=lambda epoch: f" (k = {curriculum_k(epoch, p_len, c)})")

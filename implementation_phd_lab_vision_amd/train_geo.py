@@ -73,8 +73,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if args.warmup_2d_epochs < 0:
         p.error("--warmup-2d-epochs must be >= 0")
     if stage == "joint":
-        train_joint.validate_args(p, args)
-    return args
+        return train_joint.validate_args(p, args)
+    return train.validate_clip_ema(p, args)
 
 
 def geo_schedule(args: argparse.Namespace):

@@ -56,7 +56,7 @@ import torch
 from . import _lib
 from .model import _AR_BLOCKS, _REG_HIDDEN, _REG_ITERS
 from .train import (DROPOUT_P, GEO_EXTRA_KEYS, GEO_KEYS, AdamW, GeoWeights, GradScaler, TrainableHead, build_parser as _phase1_parser,
-                    dropout_generator, fit, geo_pose_loss_grad, head_from_checkpoint, open_run)
+                    dropout_generator, fit, geo_pose_loss_grad, head_from_checkpoint, open_run, clip_fields, validate_clip_ema, validate_with_ema)
 from .trainable import FlatItem, FlatTrainableHead, block_items, input_proj_items, regressor_items
 
 LAMBDA_FUTURE = 1.0
@@ -403,6 +403,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="weight of the future-pose loss mean((joints_hat - gt)^2) over frames >= 1, >= 0 (no run has measured a good value)")
     p.add_argument("--lambda-latent", type=float, default=LAMBDA_LATENT,
                    help="weight of the latent loss mean((phi_hat - phi.detach())^2) over frames >= 1, >= 0 (no run has measured a good value)")
+    p.add_argument("--weights-from", choices=("auto", "model", "ema"), default=argparse.SUPPRESS,
+                   help="which weights of --init to start from: auto (default) = its EMA weights when it has them, else the raw ones")
     return p
 
 
@@ -412,7 +414,7 @@ def validate_args(p: argparse.ArgumentParser, args: argparse.Namespace) -> argpa
         p.error("--init is required unless --resume names an existing checkpoint")
     if not (args.lambda_future >= 0 and args.lambda_latent >= 0):          # also refuses nan
         p.error("--lambda-future and --lambda-latent must be >= 0")
-    return args
+    return validate_clip_ema(p, args)
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -437,21 +439,28 @@ def run(args: argparse.Namespace, geo_for_epoch=None) -> float:
     def epoch_fn(epoch):
         geo = geo_for_epoch(epoch) if geo_for_epoch is not None else None
         tr, steps, skipped = train_joint_epoch(r.head, r.train_set, r.sampler, r.optim, r.scaler, args.seed, epoch, args.log_every, geo=geo)
-        va = dict(zip(LOSS_KEYS, evaluate_joint(r.head, r.val_set, args.batch_size, geo=geo)))
-        if geo is not None:
-            va.update(r.head.last_eval_geo)
-        va_score = va["mpjpe"] + va["mpjpe_hat"]
+
+        def validate():
+            va = dict(zip(LOSS_KEYS, evaluate_joint(r.head, r.val_set, args.batch_size, geo=geo)))
+            if geo is not None:
+                va.update(r.head.last_eval_geo)
+            va_score = va["mpjpe"] + va["mpjpe_hat"]
+            va_fields = {f"val_{k}": v for k, v in va.items()}
+            va_fields["val_mpjpe_sum"] = va_score
+            return va_score, va_fields, (
+                f"Val:   loss={va['loss']:.6f} | l3d={va['l3d']:.6f} | l3d_hat={va['l3d_hat']:.6f} | l_lat={va['l_lat']:.6f} | "
+                f"mpjpe={va['mpjpe']:.3f} | future mpjpe={va['mpjpe_hat']:.3f}")
+
+        va_score, va_fields, va_lines = validate_with_ema(r, validate)
         fields = {f"train_{k}": v for k, v in tr.items()}
         fields.update({"steps": steps, "skipped": skipped})
-        fields.update({f"val_{k}": v for k, v in va.items()})
-        fields["val_mpjpe_sum"] = va_score
+        fields.update(va_fields)
         if geo is not None:
             fields["lambda_2d_active"] = geo.lambda_2d
+        fields.update(clip_fields(r))
         return va_score, fields, (
             f"Train: loss={tr['loss']:.6f} | l3d={tr['l3d']:.6f} | l3d_hat={tr['l3d_hat']:.6f} | l_lat={tr['l_lat']:.6f} | "
-            f"mpjpe={tr['mpjpe']:.3f} | future mpjpe={tr['mpjpe_hat']:.3f}",
-            f"Val:   loss={va['loss']:.6f} | l3d={va['l3d']:.6f} | l3d_hat={va['l3d_hat']:.6f} | l_lat={va['l_lat']:.6f} | "
-            f"mpjpe={va['mpjpe']:.3f} | future mpjpe={va['mpjpe_hat']:.3f}")
+            f"mpjpe={tr['mpjpe']:.3f} | future mpjpe={tr['mpjpe_hat']:.3f}",) + va_lines
 
     return fit(r, args, ("===== Joint training (input_proj, f_movie, f_AR, f_3D) =====",
                          f"Device: {r.device} ({args.precision}) | head: latent {r.head.latent_dim}, {r.head.number_blocks} f_movie blocks",

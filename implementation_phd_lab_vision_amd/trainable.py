@@ -6,11 +6,13 @@ parameter sits in the buffer RCCL reduces), which 16-bit weights need no transpo
 its clips must look like; it keeps its own ``forward_backward`` and loss.  Everything else is here, once: ``_upload``, the
 reference-layout round trip (``flat_to_reference`` / ``flat_from_reference``), the GEMM / weight-gradient / GroupNorm-backward launch
 helpers, the residual blocks' saved forward and per-block backward, the regressor's backward, the arena's overflow sweep and ``_finish_step``
-(all-reduce, finite check, AdamW, scale update).  PyTorch is used for device memory, the stream, the dropout masks' random bits and
+(all-reduce, finite check -- or, with clipping on, the global gradient norm that contains it --, AdamW, scale update), and ``WeightEMA``,
+the averaged weights the optimizer's launch keeps next to the raw ones.  PyTorch is used for device memory, the stream, the dropout masks' random bits and
 torch.distributed.  No CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -127,6 +129,42 @@ def sync_overflow_flag(found: torch.Tensor, group=None) -> None:
     dist.all_reduce(found, op=dist.ReduceOp.MAX, group=group)
 
 
+GRAD_NORM_MAX_PARTS = 2048        # r50_op_grad_norm never launches more workgroups than this (include/r50.h)
+
+
+class WeightEMA:
+    """Exponential moving average of a head's trainable parameters, in the flat layout: what
+    ``torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay))`` keeps, ``ema += w * (p - ema)`` after every
+    APPLIED optimizer step, computed inside the optimizer's launch (``r50_op_adamw_clip_ema``).  ``warmup``: the effective decay of
+    update ``u`` (0-based) is min(decay, (1 + u) / (10 + u)), so early averages are not dominated by the initial weights.
+    ``flat``: the averaged parameters (a clone of ``head.flat_master`` at construction); ``updates``: applied updates so far."""
+
+    def __init__(self, head: "FlatTrainableHead", decay: float, warmup: bool = True):
+        if not 0.0 < float(decay) < 1.0:
+            raise ValueError(f"decay must lie in (0, 1), got {decay!r}")
+        if head.flat_master is None:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') on the head first")
+        self.head, self.decay, self.warmup = head, float(decay), bool(warmup)
+        self.flat = head.flat_master.clone()
+        self.updates = 0
+
+    def weight(self) -> float:
+        """The lerp weight of the next update, 1 - (effective decay): the host scalar handed to the kernel."""
+        if not self.warmup:
+            return 1.0 - self.decay
+        return 1.0 - min(self.decay, (1.0 + self.updates) / (10.0 + self.updates))
+
+    def state_dict(self) -> dict:
+        """{"decay", "warmup", "updates", "model"}: ``model`` is ``head.state_dict()`` with the trainable entries from ``flat``."""
+        model = {k: v.clone() for k, v in self.head._sd.items()}
+        model.update(self.head.flat_to_reference(self.flat))
+        return {"decay": self.decay, "warmup": self.warmup, "updates": self.updates, "model": model}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.decay, self.warmup, self.updates = float(state["decay"]), bool(state["warmup"]), int(state["updates"])
+        self.flat.copy_(self.head.flat_from_reference({n: state["model"][n] for n in self.head.trainable_parameter_names()}))
+
+
 class _Arena:
     """Bump allocator for the backward pass's GEMM outputs: one 16-bit buffer, so ONE overflow check covers every gradient the matrix
     cores produced in a step (and nothing is allocated per step once the first step has sized it)."""
@@ -205,6 +243,10 @@ class FlatTrainableHead(PHDFor3DJoints):
         self._zero_bias = torch.zeros(max(3 * d, 2048, self._dp, _REG_HIDDEN), dtype=torch.float32, device=dev)
         self._found = torch.zeros(1, dtype=torch.int32, device=dev)
         self._arena = _Arena(dev, self._dtype)
+        # r50_op_grad_norm's buffers (section S; read only when clipping is on): per-workgroup partial sums, {coef, norm}, the statistics
+        self._norm_part = torch.zeros(GRAD_NORM_MAX_PARTS, dtype=torch.float64, device=dev)
+        self._clip2 = torch.ones(2, dtype=torch.float32, device=dev)
+        self._stats4 = torch.zeros(4, dtype=torch.float64, device=dev)
 
     def _transpose_weights(self, names: Sequence[str]) -> None:
         lib = _lib.load_library()
@@ -223,6 +265,35 @@ class FlatTrainableHead(PHDFor3DJoints):
         """The 16-bit weights and their transposes from ``flat_master`` (after its values were replaced from outside)."""
         self.flat_w16.copy_(self.flat_master.to(self._dtype))
         self._refresh_transposes()
+
+    @contextlib.contextmanager
+    def swapped_weights(self, flat: torch.Tensor):
+        """Run the body on the weights of ``flat`` (a buffer in the flat parameter layout, e.g. ``WeightEMA.flat``): the contents of
+        ``flat_master`` and ``flat`` are exchanged and the 16-bit weights and transposes refreshed; on exit they are exchanged back and
+        refreshed again.  The exchanges are exact copies, so the raw master returns bit for bit."""
+        if flat.shape != self.flat_master.shape or flat.dtype != torch.float32 or flat.device != self.flat_master.device:
+            raise ValueError("swapped_weights: expected an fp32 buffer in the flat parameter layout on the head's device")
+
+        def exchange():
+            keep = self.flat_master.clone()
+            self.flat_master.copy_(flat)
+            flat.copy_(keep)
+            self.refresh_weights16()
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
+
+    def clip_stats(self, reset: bool = True) -> Dict[str, float]:
+        """What ``r50_op_grad_norm`` counted over the applied steps since the last reset (one host read; call it once per epoch):
+        ``grad_norm_mean`` and ``grad_norm_max`` of the unclipped global norm, ``clipped_frac`` = the share of steps with coef < 1,
+        ``steps``.  Skipped steps are not counted."""
+        steps, clipped, norm_sum, norm_max = self._stats4.tolist()
+        if reset:
+            self._stats4.zero_()
+        return {"grad_norm_mean": norm_sum / max(steps, 1.0), "grad_norm_max": norm_max, "clipped_frac": clipped / max(steps, 1.0),
+                "steps": int(steps)}
 
     def flat_to_reference(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """A buffer in the flat parameter layout (master, gradient, AdamW moments) under the reference's names and layouts of the
@@ -411,11 +482,21 @@ class FlatTrainableHead(PHDFor3DJoints):
     def _finish_step(self, optim, scaler, group) -> bool:
         """From the gradient all-reduce to the scale update: average ``flat_grad`` over the ranks, raise the flag on a non-finite
         entry, agree on it over the ranks, read it (the reference's scaler.step() synchronises on the same flag), apply AdamW and
-        refresh the transposes unless it is raised, update the loss scale.  Returns the flag: True = the step was skipped."""
+        refresh the transposes unless it is raised, update the loss scale.  Returns the flag: True = the step was skipped.
+        With ``optim.max_grad_norm`` set, one ``r50_op_grad_norm`` call takes the finite check's place: the same read of ``flat_grad``
+        also gives the global L2 norm and the clip coefficient ``optim.step`` applies (after the all-reduce, so every rank computes the
+        same bits).  ``flat_grad`` keeps the UNCLIPPED gradient."""
         with torch.cuda.device(self._device):
             all_reduce_gradients(self.flat_grad, group)
-            _lib.check(_lib.load_library().r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(),
-                                                                self._stream()), None, "r50_op_check_finite")
+            max_norm = getattr(optim, "max_grad_norm", None)
+            if max_norm is None:
+                _lib.check(_lib.load_library().r50_op_check_finite(self.flat_grad.data_ptr(), self.flat_grad.numel(), self._found.data_ptr(),
+                                                                    self._stream()), None, "r50_op_check_finite")
+            else:
+                _lib.check(_lib.load_library().r50_op_grad_norm(self.flat_grad.data_ptr(), self.flat_grad.numel(), float(max_norm),
+                                                                 self._norm_part.data_ptr(), self._norm_part.numel(), self._found.data_ptr(),
+                                                                 self._clip2.data_ptr(), self._stats4.data_ptr(), self._stream()), None,
+                           "r50_op_grad_norm")
             sync_overflow_flag(self._found, group)        # any rank overflowed -> every rank skips this step
             found = bool(self._found.item())
             if not found:

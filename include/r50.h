@@ -385,6 +385,27 @@ int r50_op_check_overflow16(const void* x, int64_t n, int* found, int et, void* 
 int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, const int* found_inf, int et, void* stream);
 
+/* Global-norm gradient clipping and EMA weights: the tail of a step when either is switched on.
+ *  r50_op_grad_norm: the L2 norm of g (n fp32), GradScaler's finite check and `torch.nn.utils.clip_grad_norm_`'s coefficient in ONE
+ *    read of g; it takes the place of r50_op_check_finite.  Two launches.  The first forms part[w], the fp64 sum of squares of
+ *    workgroup w's contiguous slice: W = min(ceil(n / 4096), 2048) workgroups, slices of ceil(n / W) rounded up to a multiple of 4
+ *    -- a function of n alone, never of the device -- per-thread fp64 partials over a fixed stride (the product of two fp32 values is
+ *    exact in fp64), a fixed shuffle / LDS tree, no atomics.  The second (one workgroup) adds part[0..W) in a fixed order.  A sum that
+ *    is not finite sets found[0] = 1 (exactly when r50_op_check_finite would: an fp64 sum of at most 2^40 fp32 squares cannot
+ *    overflow) and writes clip2 = {1, float(sqrt(sum))}; found is never cleared.  Otherwise norm = sqrt(sum),
+ *    coef = min(1, max_norm / (norm + 1e-6)) in fp64 (max_norm <= 0: coef = 1, norm and flag only), clip2 = {float(coef),
+ *    float(norm)}, and, when found[0] is still 0, stats4 = {steps, steps with coef < 1, sum of norms, largest norm} (device doubles,
+ *    zeroed by the caller) moves.  part: n_part >= W doubles of scratch; g 16-byte aligned.  The same bits on every run.
+ *  r50_op_adamw_clip_ema: r50_op_adamw with g[i] * clip[0] (one fp32 product) in the place of g[i] when clip is not NULL, and, when
+ *    ema is not NULL, ema[i] += ema_weight * (p_new[i] - ema[i]) (each operation rounded once: the lerp form of
+ *    `torch.optim.swa_utils.get_ema_multi_avg_fn`).  With both NULL the bits are r50_op_adamw's.  Skipped as a whole when
+ *    found_inf[0] != 0.  g is NOT written: it keeps the unclipped gradient. */
+int r50_op_grad_norm(const float* g, int64_t n, float max_norm, double* part, int n_part, int* found, float* clip2, double* stats4,
+                     void* stream);
+int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int step, const int* found_inf, const float* clip, float* ema, float ema_weight, int et,
+                          void* stream);
+
 /* Lifting head, evaluation (`evaluate()`, src/train.py:219-280): pred, gt (rows, joints, 3) fp32 -> acc[0] += mean((pred-gt)^2)
  * (l3d, :259), acc[1] += mean over the rows*joints joints of |pred-gt|_2 (MPJPE, :42-45), acc[2] += 1; acc: 3 doubles of device
  * memory, so the mean over per-batch means is acc[0..1] / acc[2].  fp32 per joint, fp64 sums in a fixed order (no atomics: the
