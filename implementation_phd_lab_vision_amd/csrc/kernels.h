@@ -4710,6 +4710,176 @@ __global__ __launch_bounds__(256) void pose_detail_metrics_kernel(const float* _
     }
 }
 
+// ---- Forecast error after dynamic time warping ------------------------------------------------------------
+// Per clip, Y_0..Y_{P-1} the predicted poses and X_0..X_{Q-1} the ground truth's frames i0 .. i0+Q-1: C1[i][j] / C2[i][j] = P1 / P2 of
+// (Y_i, X_j), one pose_protocol_errors per cell giving both.  band < 0 allows every cell, band >= 0 the cells with |i - j| <= band
+// (band >= |P - Q|, the launcher's check, keeps (P-1, Q-1) reachable).  Per metric a closed-ended DP: D[0][0] = C[0][0], D[i][j] =
+// C[i][j] + the best predecessor among (i-1,j-1), (i-1,j), (i,j-1) that exist and are allowed, taken in that order, a later one
+// replacing the current one only if strictly smaller: ties go diagonal, then up, then left, and a NaN never replaces anything.  The
+// path is the backtrack of the stored choices from (P-1, Q-1) to (0, 0), max(P, Q) <= L <= P+Q-1 cells.  Every loop is bounded by P,
+// Q, P*Q or P+Q: non-finite input gives non-finite sums, never a hang.
+#define DTW_MAX_LEN 64
+
+__host__ __device__ inline bool dtw_allowed(int i, int j, int band) {
+    const int d = i - j;
+    return band < 0 || (d < 0 ? -d : d) <= band;
+}
+
+// Dynamic LDS of dtw_align_kernel in bytes: both cost matrices, three rolling diagonals per metric, the per-row sums, the backtracked
+// paths and one choice byte per cell and metric, in the order the kernel carves them (doubles, ints, shorts, bytes).
+__host__ __device__ inline size_t dtw_lds_bytes(int P, int Q) {
+    const size_t pq = (size_t)P * Q;
+    return 8 * (2 * pq + 2 * 3 * DTW_MAX_LEN + 2 * (size_t)P) + 4 * (4 * (size_t)P + 4) + 2 * (2 * (size_t)(P + Q)) + 2 * pq;
+}
+
+// One workgroup of 256 threads per clip b = blockIdx.x: pred (B, P, J, 3), gt (B, Tgt, J, 3) fp32, 1 <= P, Q <= DTW_MAX_LEN.
+//  cost:      thread t fits the cells t, t+256, ... (row-major, i*Q + j) and stores both metrics' costs in LDS; a cell outside the band is
+//             never read and gets no fit.
+//  DP:        anti-diagonal wavefront, diagonal s = i + j: wave m in {0, 1} runs metric m, its lane i owns cell (i, s-i) and reads
+//             the diagonals s-1 and s-2 (three rolling buffers indexed by i); one workgroup barrier per diagonal, reached by all waves.
+//  backtrack: lane 0 of wave m walks metric m's choices and adds each cell to its row's cost_sum / cells / lag_sum (of i - j) in LDS.
+// WRITES clip_out[(b*2 + m)*(2 + 3P) + ..] = [total, L, cost_sum[P], cells[P], lag_sum[P]] and, if path_out is not null,
+// path_out[((b*2 + m)*(P+Q-1) + n)*2 + {0, 1}] = the n-th path cell (i, j) from (0, 0) onward, -1 past L.  No atomics: every
+// workgroup owns its outputs, the same bits on every run.
+__global__ __launch_bounds__(256) void dtw_align_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int P, int Tgt, int i0,
+                                                        int Q, int J, int root, int band, double* __restrict__ clip_out,
+                                                        int* __restrict__ path_out) {
+    extern __shared__ double dtw_sm[];
+    const int b = blockIdx.x, tid = threadIdx.x, PQ = P * Q, NP = P + Q - 1;
+    double* cost = dtw_sm;                                                  // [2][P*Q]
+    double* diag = cost + 2 * (size_t)PQ;                                   // [2][3][DTW_MAX_LEN]
+    double* cost_sum = diag + 2 * 3 * DTW_MAX_LEN;                          // [2][P]
+    int* cells = (int*)(cost_sum + 2 * P);                                  // [2][P]
+    int* lag_sum = cells + 2 * P;                                           // [2][P]
+    int* path_len = lag_sum + 2 * P;                                        // [2] (+ 2 of padding)
+    unsigned short* path = (unsigned short*)(path_len + 4);                 // [2][P+Q], (i << 8) | j from the end of the path
+    unsigned char* choice = (unsigned char*)(path + 2 * (P + Q));           // [2][P*Q]: 0 diagonal, 1 up, 2 left, 3 the origin
+
+    const float* yb = pred + (size_t)b * P * J * 3;
+    const float* xb = gt + ((size_t)b * Tgt + i0) * J * 3;
+    for (int c = tid; c < PQ; c += 256) {
+        const int i = c / Q, j = c - i * Q;
+        double e1 = 0.0, e2 = 0.0;
+        if (dtw_allowed(i, j, band)) pose_protocol_errors(yb + (size_t)i * J * 3, xb + (size_t)j * J * 3, J, root, e1, e2);
+        cost[c] = e1;
+        cost[PQ + c] = e2;
+    }
+    for (int k = tid; k < 2 * P; k += 256) {
+        cost_sum[k] = 0.0;
+        cells[k] = 0;
+        lag_sum[k] = 0;
+    }
+    __syncthreads();
+
+    const int m = tid >> 6, i = tid & 63;
+    const bool lane_on = m < 2 && i < P;
+    for (int s = 0; s < NP; ++s) {
+        const int j = s - i;
+        if (lane_on && j >= 0 && j < Q && dtw_allowed(i, j, band)) {
+            const double* d1 = diag + (m * 3 + (s + 2) % 3) * DTW_MAX_LEN;  // diagonal s-1
+            const double* d2 = diag + (m * 3 + (s + 1) % 3) * DTW_MAX_LEN;  // diagonal s-2
+            double best = 0.0;
+            unsigned char ch = 3;
+            if (i >= 1 && j >= 1) {
+                best = d2[i - 1];
+                ch = 0;
+            }
+            if (i >= 1 && dtw_allowed(i - 1, j, band)) {
+                const double v = d1[i - 1];
+                if (ch == 3 || v < best) {
+                    best = v;
+                    ch = 1;
+                }
+            }
+            if (j >= 1 && dtw_allowed(i, j - 1, band)) {
+                const double v = d1[i];
+                if (ch == 3 || v < best) {
+                    best = v;
+                    ch = 2;
+                }
+            }
+            const double c = cost[m * PQ + i * Q + j];
+            diag[(m * 3 + s % 3) * DTW_MAX_LEN + i] = ch == 3 ? c : c + best;
+            choice[m * PQ + i * Q + j] = ch;
+        }
+        __syncthreads();
+    }
+
+    if (m < 2 && i == 0) {
+        int bi = P - 1, bj = Q - 1, n = 0;
+        while (n < NP) {
+            const int idx = bi * Q + bj;
+            cost_sum[m * P + bi] += cost[m * PQ + idx];
+            cells[m * P + bi] += 1;
+            lag_sum[m * P + bi] += bi - bj;
+            path[m * (P + Q) + n] = (unsigned short)((bi << 8) | bj);
+            ++n;
+            if (bi == 0 && bj == 0) break;
+            const unsigned char ch = choice[m * PQ + idx];
+            if (ch != 2 && bi > 0) --bi;
+            if (ch != 1 && bj > 0) --bj;
+        }
+        path_len[m] = n;
+    }
+    __syncthreads();
+
+    const int R = 2 + 3 * P;
+    double* rec = clip_out + (size_t)b * 2 * R;
+    for (int k = tid; k < 2 * R; k += 256) {
+        const int mm = k / R, v = k - mm * R;
+        double val;
+        if (v == 0) val = diag[(mm * 3 + (NP - 1) % 3) * DTW_MAX_LEN + P - 1];
+        else if (v == 1) val = (double)path_len[mm];
+        else if (v < 2 + P) val = cost_sum[mm * P + v - 2];
+        else if (v < 2 + 2 * P) val = (double)cells[mm * P + v - 2 - P];
+        else val = (double)lag_sum[mm * P + v - 2 - 2 * P];
+        rec[k] = val;
+    }
+    if (path_out) {
+        int* po = path_out + (size_t)b * 2 * NP * 2;
+        for (int k = tid; k < 2 * NP; k += 256) {
+            const int mm = k / NP, n = k - mm * NP, len = path_len[mm];
+            int pi = -1, pj = -1;
+            if (n < len) {
+                const int code = path[mm * (P + Q) + len - 1 - n];
+                pi = code >> 8;
+                pj = code & 255;
+            }
+            po[2 * k] = pi;
+            po[2 * k + 1] = pj;
+        }
+    }
+}
+
+// The grouped sums of one batch's DTW records: one workgroup per group g = blockIdx.x ADDS, with V = 1 + 2P,
+//   acc[(g*2 + m)*V + 0]         += the sum over the clips of group g of total / L
+//   acc[(g*2 + m)*V + 1 + k]     += the sum of cost_sum[k] / cells[k]
+//   acc[(g*2 + m)*V + 1 + P + k] += the sum of lag_sum[k] / cells[k]
+//   acc[2*G*V + g]               += the clip count.
+// Wave w takes the slots w, w+4, ...: its lane l sums the clips l, l+64, ... of the group in clip order, then one fixed shuffle tree
+// over the wave.  Every slot is added to once by one lane: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void dtw_group_sums_kernel(const double* __restrict__ clip_out, const int* __restrict__ group, int B,
+                                                             int P, int G, double* __restrict__ acc) {
+    const int g = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, V = 1 + 2 * P, R = 2 + 3 * P;
+    for (int slot = wave; slot <= 2 * V; slot += 4) {                        // slot 2V is the clip count
+        const int m = slot / V, v = slot - m * V;
+        double s = 0.0;
+        for (int b = lane; b < B; b += 64) {
+            if (group[b] != g) continue;
+            if (slot == 2 * V) {
+                s += 1.0;
+                continue;
+            }
+            const double* rec = clip_out + ((size_t)b * 2 + m) * R;
+            if (v == 0) s += rec[0] / rec[1];
+            else if (v <= P) s += rec[2 + v - 1] / rec[2 + P + v - 1];
+            else s += rec[2 + 2 * P + v - 1 - P] / rec[2 + P + v - 1 - P];
+        }
+        s = wave_sum_f64(s);
+        if (lane == 0) acc[slot == 2 * V ? 2 * (size_t)G * V + g : ((size_t)g * 2 + m) * V + v] += s;
+    }
+}
+
 // ---- Dense evaluation: clips stitched into per-frame sequences -----------------------------------------
 // The maximum of v over the 64 lanes of a wave in a fixed tree, valid in lane 0; a NaN wins and stays.
 __device__ inline double wave_max_f64(double v) {

@@ -2517,6 +2517,28 @@ int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* gr
     return ew_done("r50_op_pose_detail_metrics");
 }
 
+int r50_op_dtw_protocols(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int q, int joints, int root,
+                         int band, int n_groups, double* clip_out, int* path_out, double* acc, void* stream) {
+    if (!pred || !gt || !group || !clip_out || !acc) return fail(nullptr, R50_ERR_INVALID, "r50_op_dtw_protocols: null pointer");
+    if (b < 1 || p < 1 || p > DTW_MAX_LEN || q < 1 || q > DTW_MAX_LEN || n_groups < 1 || joints < 1 || joints > 64 || root < 0 ||
+        root >= joints || i0 < 0 || (int64_t)i0 + q > t_gt || (int64_t)b * t_gt > INT32_MAX)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_dtw_protocols: invalid arguments (need b, n_groups >= 1, 1 <= p, q <= 64, "
+                                              "1 <= joints <= 64, 0 <= root < joints and 0 <= i0, i0 + q <= t_gt)");
+    if (band >= 0 && band < (p > q ? p - q : q - p))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_dtw_protocols: invalid arguments (a band >= 0 must be >= |p - q|)");
+    const size_t lds = dtw_lds_bytes(p, q);
+    if (lds > 65536) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dtw_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds);
+        if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_dtw_protocols: ") + hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(dtw_align_kernel, dim3((unsigned)b), dim3(256), lds, (hipStream_t)stream, pred, gt, p, t_gt, i0, q, joints, root, band,
+                       clip_out, path_out);
+    hipLaunchKernelGGL(dtw_group_sums_kernel, dim3((unsigned)n_groups), dim3(256), 0, (hipStream_t)stream, clip_out, group, b, p, n_groups,
+                       acc);
+    return ew_done("r50_op_dtw_protocols");
+}
+
 int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int joints, const int* offsets, const int* src, int frames, int t,
                         int mode, int ramp, float* fused, float* gt_out, float* spread, float* gt_gap, void* stream) {
     if (!pred || !gt || !offsets || !src || !fused || !gt_out || !spread || !gt_gap)

@@ -21,7 +21,10 @@ frame); the frames are the clip's person crop -- ``meta["box"]`` through ``frame
 the overlapping clips are stitched into one pose per video frame (``sequences.evaluate_dense``, ``--dense-fuse mean | context | last``)
 and every video frame is scored once: the ``Dense |`` lines print P1, P2, the velocity and acceleration errors and the spread of the
 contributors for all frames, the action mean and each action, and the clip-wise P1 / P2 by window position; the ``.npz`` gains the
-``dense_*`` keys and ``--dense-out FILE.npz`` receives the stitched sequences themselves.
+``dense_*`` keys and ``--dense-out FILE.npz`` receives the stitched sequences themselves.  With ``--dtw`` (default off; needs
+``--pred-len``) the forecasts are also scored after dynamic time warping (``dtw.evaluate_dtw``,
+``--dtw-band N``): the ``DTW metrics`` lines print the warped P1 / P2 beside the unwarped ones for all clips and each action, and the
+warped error and the lag in frames per horizon; the ``.npz`` gains the ``dtw_*`` keys.
 
 Two differences from running the reference's script as it stands:
 
@@ -108,6 +111,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "has seen up to f_movie's receptive field, or the prediction that has seen the most past")
     p.add_argument("--dense-out", type=str, default=None, metavar="FILE.npz",
                    help="also write the stitched sequences (seq_keys, seq_start, frame_idx, pred, gt, spread, count) there (--dense)")
+    p.add_argument("--dtw", action="store_true",
+                   help="also score the forecast after dynamic time warping: warped P1 / P2 beside the unwarped ones per action, and the "
+                        "warped error and the lag in frames per horizon (needs --pred-len; INTEGRATION.md section T)")
+    p.add_argument("--dtw-band", type=int, default=-1, metavar="N",
+                   help="only warp within |i - j| <= N frames (--dtw); negative = no band (default)")
     return p
 
 
@@ -137,6 +145,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--render-sheet-every must be >= 1, got {args.render_sheet_every}")
     if args.dense_out is not None and not args.dense:
         p.error("--dense-out needs --dense")
+    if args.dtw and args.pred_len <= 0:
+        p.error("--dtw needs --pred-len > 0: it scores the forecast")
+    if args.dtw and args.pred_len > 64:
+        p.error(f"--dtw warps at most 64 predicted frames, got --pred-len {args.pred_len}")
     return args
 
 
@@ -421,6 +433,37 @@ def dense_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     return out
 
 
+def dtw_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--dtw`` from an ``evaluate_dtw`` result: the ``DTW metrics`` line (all clips: the warped P1 / P2 and, after
+    ``plain``, the unwarped horizon means of the same rollouts), one indented line per action, and the ``DTW horizons`` line with the
+    warped error in mm and the lag in frames (signed: positive = the prediction is slow) at horizons 1, 5, 10 and P."""
+    clips = res["clips"]
+    da, pa = res["dtw_all"], res["plain_all"]
+    band = "none" if res["band"] < 0 else str(int(res["band"]))
+    lines = [f"DTW metrics | input {input_len} | pred {pred_len} | band {band} | clips {int(clips.sum())} | all: p1 (mm) {da[0] * 1000.0:.2f} "
+             f"| p2 (mm) {da[1] * 1000.0:.2f} | plain p1 (mm) {pa[0] * 1000.0:.2f} | p2 (mm) {pa[1] * 1000.0:.2f}"]
+    for name, c, (p1, p2) in zip(res["group_names"], clips, res["dtw"]):
+        lines.append(f"  {name} | clips {int(c)} | dtw p1 (mm) {p1 * 1000.0:.2f} | dtw p2 (mm) {p2 * 1000.0:.2f}")
+    hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+    fa, la = res["dtw_future_all"], res["lag_all"]
+    parts = [f"p{m + 1} (mm) " + " | ".join(f"@{h}: {fa[h - 1, m] * 1000.0:.2f}" for h in hs) for m in (0, 1)]
+    parts += [f"lag p{m + 1} (frames) " + " | ".join(f"@{h}: {la[h - 1, m]:+.2f}" for h in hs) for m in (0, 1)]
+    lines.append("DTW horizons | " + " | ".join(parts))
+    return lines
+
+
+def dtw_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--dtw``: ``dtw_actions`` (G,) str, ``dtw_clips`` (G,) int64, ``dtw_band`` () int64, and fp32 ``dtw`` (G, 2),
+    ``dtw_all`` (2,), ``dtw_future`` (G, P, 2), ``dtw_future_all`` (P, 2) in metres and ``dtw_lag`` (G, P, 2), ``dtw_lag_all`` (P, 2) in
+    frames; [.., 2] = [p1, p2]."""
+    out = {"dtw_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "dtw_clips": np.asarray(res["clips"], dtype=np.int64), "dtw_band": np.array(int(res["band"]), dtype=np.int64)}
+    for key, src in (("dtw", "dtw"), ("dtw_all", "dtw_all"), ("dtw_future", "dtw_future"), ("dtw_future_all", "dtw_future_all"),
+                     ("dtw_lag", "lag"), ("dtw_lag_all", "lag_all")):
+        out[key] = np.asarray(res[src], dtype=np.float32)
+    return out
+
+
 def dense_export(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     """The arrays of ``--dense-out``: ``seq_keys`` (S, 3) str [subject, action, cam], ``seq_start`` (S+1,), ``frame_idx`` (F,) int32
     (sub-sampled frame units), ``pred`` and ``gt`` (F, J, 3) fp32 in metres, ``spread`` (F,) fp32, ``count`` (F,) int32 = the clips
@@ -494,6 +537,15 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in dense_lines(dense):
             print(line)
 
+    dtw = None
+    if args.dtw:                             # the protocols' pass over the forecasts: every test clip once, in store order
+        from .dtw import evaluate_dtw
+        from .protocols import action_groups
+        names, ids = action_groups(test_set.item_actions())
+        dtw = evaluate_dtw(head, test_set, ids, names, args.input_len, args.pred_len, band=args.dtw_band)
+        for line in dtw_lines(dtw, args.input_len, args.pred_len):
+            print(line)
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -527,6 +579,8 @@ def main(argv: Optional[List[str]] = None) -> str:
             os.makedirs(os.path.dirname(args.dense_out) or ".", exist_ok=True)
             np.savez_compressed(args.dense_out, **dense_export(dense))
             print(f"Dense | stitched sequences saved to: {args.dense_out}")
+    if dtw is not None:
+        extra.update(dtw_arrays(dtw))
     if n_render:                             # the person crops, drawn over; a clip without a usable box gets the plain background
         from . import render
         plain = torch.tensor(render._rgb_tuple(render.PANEL_BG_RGB), dtype=torch.uint8, device=device)

@@ -450,6 +450,29 @@ int r50_op_pose_protocols(const float* pred, const float* gt, const int* group, 
 int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
                                int n_groups, int n_thr, double thr_max, double* acc, void* stream);
 
+/* Lifting head, forecast error after dynamic time warping per group: pred (b,p,joints,3) fp32 holds the
+ * predicted poses Y_0..Y_{p-1} of each clip, X_0..X_{q-1} are frames i0 .. i0+q-1 of gt (b,t_gt,joints,3) fp32; group (b) int32 device
+ * values in [0,n_groups).  Read as fp32, computed in fp64.  Per clip two cost matrices, C1[i][j] = P1 and C2[i][j] = P2 of (Y_i, X_j)
+ * as r50_op_pose_protocols defines them, one similarity fit per cell giving both.  band < 0 allows every cell, band >= 0 the cells
+ * with |i - j| <= band; a band >= 0 below |p - q| is refused.  Per metric a closed-ended DP: D[0][0] = C[0][0], D[i][j] = C[i][j] +
+ * the best predecessor among (i-1,j-1), (i-1,j), (i,j-1) that exist and are allowed, taken in that order, a later candidate replacing
+ * the current one only if strictly smaller: ties go diagonal, then up, then left, and a NaN never replaces anything.  The path is the
+ * backtrack of the stored choices from (p-1,q-1) to (0,0); its length L lies in [max(p,q), p+q-1].  Every loop is bounded by p, q,
+ * p*q or p+q: non-finite input gives non-finite sums, never a hang.  Per clip and metric m (0 = P1, 1 = P2): total = D[p-1][q-1]; L;
+ * cost_sum[k] = the sum of C[i][j], cells[k] = the count and lag_sum[k] = the sum of (i - j) over the path cells with i = k.  The DTW
+ * error of a clip is total / L, at horizon k cost_sum[k] / cells[k]; the lag at horizon k is lag_sum[k] / cells[k] frames, positive
+ * when the prediction runs behind the ground truth's clock (it is slow).
+ *   clip_out (b, 2, 2 + 3p) doubles, always WRITTEN: [total, L, cost_sum[p], cells[p], lag_sum[p]] per clip and metric;
+ *   path_out may be null; otherwise (b, 2, p+q-1, 2) int32, WRITTEN: the path's (i, j) pairs from (0,0) onward, -1 past L;
+ *   acc: n_groups*2*(1 + 2p) + n_groups doubles; with V = 1 + 2p it ADDS over the clips of group g
+ *     acc[(g*2 + m)*V + 0] += total / L,  acc[(g*2 + m)*V + 1 + k] += cost_sum[k] / cells[k],
+ *     acc[(g*2 + m)*V + 1 + p + k] += lag_sum[k] / cells[k],  acc[2*n_groups*V + g] += the clips of group g.
+ * Needs b, n_groups >= 1, 1 <= p, q <= 64, 1 <= joints <= 64, 0 <= root < joints, 0 <= i0, i0 + q <= t_gt, no null pointer but
+ * path_out; all checked before any launch (a refused call touches nothing).  Two launches on stream: one workgroup per clip (cost
+ * matrices, DP state and choices in LDS), then one workgroup per group; fixed summation order, no atomics: the same bits on every run. */
+int r50_op_dtw_protocols(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int q, int joints, int root,
+                         int band, int n_groups, double* clip_out, int* path_out, double* acc, void* stream);
+
 /* Dense evaluation, the fusion of overlapping clips into one pose per video frame: pred, gt
  * (rows/t, t, joints, 3) fp32 seen as rows = N*t pose rows; output frame f has the contributors src[offsets[f] .. offsets[f+1]), each a
  * row index item*t + t_c, read in list order; offsets (frames+1) and src int32 device values.  Per frame with n contributors, in fp64
