@@ -3,6 +3,7 @@
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
 #include "kernels.h"
+#include "launch_plan.h"
 #include "../../include/r50.h"
 
 #include <atomic>
@@ -15,6 +16,10 @@
 #include <vector>
 
 namespace {
+
+using namespace launch_plan;
+static_assert(kBf16 == R50_PREC_BF16 && kFp32x == R50_PREC_FP32X && kBf16w2 == R50_PREC_BF16W2 && kFp16 == R50_PREC_FP16 && kFp8 == R50_PREC_FP8,
+              "launch_plan.h restates the precisions of r50.h");
 
 thread_local std::string g_err;   // errors raised without a handle (r50_create, r50_op_*)
 
@@ -33,9 +38,8 @@ struct EvRec {
     double flops, bytes;
 };
 
-struct ConvLayer {
+struct ConvLayer : ConvShape {
     std::string conv_key, bn_key;
-    int cin, cout, ks, stride, pad;
     __bf16* w = nullptr;    // device, (cout, ks, ks, cin)
     float* bias = nullptr;  // device
     // fp8 mode, layer2-4: w holds e4m3 bytes with real value = byte value x wscale; bias_scaled = bias / (sx * wscale) once the
@@ -124,30 +128,15 @@ inline uint16_t f32_to_bf16_rne(float f) {
     return (uint16_t)(u >> 16);
 }
 
-constexpr int kStages[4][3] = {{64, 3, 1}, {128, 4, 2}, {256, 6, 2}, {512, 3, 2}};
-constexpr size_t kFp8FirstConv = 11;     // convs[1..10] = layer1 (4 + 3 + 3); fp8 mode quantises from layer2.0.conv1 on
 constexpr float kBnEps = 1e-5f;
 
-std::vector<ConvLayer> make_specs() {
+std::vector<ConvLayer> make_specs() {       // the table of launch_plan.h, with room for the weights
     std::vector<ConvLayer> v;
-    auto add = [&](const std::string& c, const std::string& b, int cin, int cout, int ks, int s, int p) {
+    for (const ConvSpec& spec : conv_specs()) {
         ConvLayer L;
-        L.conv_key = c; L.bn_key = b; L.cin = cin; L.cout = cout; L.ks = ks; L.stride = s; L.pad = p;
+        static_cast<ConvShape&>(L) = spec.shape;
+        L.conv_key = spec.conv_key; L.bn_key = spec.bn_key;
         v.push_back(L);
-    };
-    add("conv1", "bn1", 3, 64, 7, 2, 3);
-    int inpl = 64;
-    for (int si = 0; si < 4; ++si) {
-        const int planes = kStages[si][0], blocks = kStages[si][1], stride = kStages[si][2];
-        for (int b = 0; b < blocks; ++b) {
-            const int s = (b == 0) ? stride : 1;
-            const std::string p = "layer" + std::to_string(si + 1) + "." + std::to_string(b);
-            add(p + ".conv1", p + ".bn1", inpl, planes, 1, 1, 0);
-            add(p + ".conv2", p + ".bn2", planes, planes, 3, s, 1);
-            add(p + ".conv3", p + ".bn3", planes, planes * 4, 1, 1, 0);
-            if (b == 0) add(p + ".downsample.0", p + ".downsample.1", inpl, planes * 4, 1, s, 0);
-            inpl = planes * 4;
-        }
     }
     return v;
 }
@@ -319,6 +308,27 @@ int g_num_cus = 0;
 // share the chip (each stream's launches then take their share of the CUs and run beside the other streams' launches).
 int g_cu_cap = [] { const char* v = std::getenv("R50_CU_CAP"); return v ? std::atoi(v) : 0; }();
 int cu_budget(int device_cus) { return (g_cu_cap > 0 && g_cu_cap < device_cus) ? g_cu_cap : device_cus; }
+int num_cus() {          // 0: the device could not be queried
+    if (g_num_cus == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+        g_num_cus = cu_budget(prop.multiProcessorCount);
+    }
+    return g_num_cus;
+}
+
+// A persistent kernel: at most one workgroup per CU of the budget, the workgroups stream `tiles` tiles.  The dynamic-LDS attribute is set on
+// every launch: it is per device, and a process may hold handles on several devices.
+template <typename K, typename... Args>
+hipError_t launch_persistent(K kern, long long tiles, int threads, size_t lds, hipStream_t s, Args... args) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    const int cus = num_cus();
+    if (cus == 0) return hipErrorInvalidDevice;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < cus ? tiles : cus)), dim3(threads), lds, s, args...);
+    return hipGetLastError();
+}
 
 template <int ET, int BC, int BP, int WC, int WP, int NSTAGE, bool SPLIT = false>
 hipError_t launch_igemm_t(ConvArgs a, bool persistent, hipStream_t s) {
@@ -335,12 +345,8 @@ hipError_t launch_igemm_t(ConvArgs a, bool persistent, hipStream_t s) {
     }
     int grid = a.n_blocks;
     if (persistent) {
-        if (g_num_cus == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-            g_num_cus = cu_budget(prop.multiProcessorCount);
-        }
+        const int cus = num_cus();
+        if (cus == 0) return hipErrorInvalidDevice;
         // resident workgroups per CU (LDS / registers / wave slots).  No workgroup waits on another one,
         // so an optimistic answer only queues the surplus workgroups; it cannot deadlock.
         static int per_cu = 0;
@@ -349,7 +355,7 @@ hipError_t launch_igemm_t(ConvArgs a, bool persistent, hipStream_t s) {
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, WC * WP * 64, lds) != hipSuccess || n < 1) n = 1;
             per_cu = n;
         }
-        if (grid > g_num_cus * per_cu) grid = g_num_cus * per_cu;
+        if (grid > cus * per_cu) grid = cus * per_cu;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WC * WP * 64), lds, s, a);
     return hipGetLastError();
@@ -378,18 +384,7 @@ hipError_t launch_igemm_ws_t(ConvArgs a, hipStream_t s) {
     a.div_ctiles = make_fast_div((unsigned)a.n_ctiles);
     constexpr int kRowsPerPass = NLOAD * 8;
     const size_t lds = (size_t)NSTAGE * (BC + (BP + kRowsPerPass - 1) / kRowsPerPass * kRowsPerPass) * 128;
-    auto kern = igemm_ws_kernel<ET, BC, BP, CWC, CWP, NLOAD, NSTAGE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
-    int grid = a.n_blocks < g_num_cus ? a.n_blocks : g_num_cus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3((CWC * CWP + NLOAD) * 64), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(igemm_ws_kernel<ET, BC, BP, CWC, CWP, NLOAD, NSTAGE>, a.n_blocks, (CWC * CWP + NLOAD) * 64, lds, s, a);
 }
 
 // layer1 conv2 shape (3x3 s1 p1, 64 -> 64, 56x56): filter bank resident in LDS (kernels.h: conv3x3_c64_kernel); tile id 64+16
@@ -402,17 +397,7 @@ template <int ET>
 hipError_t launch_conv3x3_c64(const ConvArgs& a, hipStream_t s) {
     if (!is_c64_shape(a)) return hipErrorInvalidValue;
     constexpr size_t lds = 9 * 64 * 128 + 2 * 352 * 128;      // 163,840 = all of the CU's LDS
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<ET>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
-    const int tiles = a.N * 14;
-    hipLaunchKernelGGL(conv3x3_c64_kernel<ET>, dim3(tiles < g_num_cus ? tiles : g_num_cus), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(conv3x3_c64_kernel<ET>, a.N * 14, 512, lds, s, a);
 }
 
 // conv2 of the non-first blocks of layer2 / layer3 / layer4 (3x3 s1 p1, Cin = Cout): input-resident kernel (kernels.h: conv3x3_xres_kernel);
@@ -430,20 +415,9 @@ hipError_t launch_conv3x3_xres_t(ConvArgs a, hipStream_t s) {
     constexpr int PPT = IW == 7 ? 17 * 16 : NI * (TR + 2) * PW, XBUF = (PPT + 31) / 32 * 32 * 128;
     constexpr size_t lds = 2 * (size_t)XBUF + NST * (size_t)BC * 128;
     static_assert(lds <= 163840, "LDS budget");
-    auto kern = conv3x3_xres_kernel<ET, NI, TR, IW, IH>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     a.n_ctiles = a.Cout / BC;
     a.n_blocks = ((a.N + NI - 1) / NI) * (IH / TR) * a.n_ctiles;
-    const int grid = a.n_blocks < g_num_cus ? a.n_blocks : g_num_cus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(768), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(conv3x3_xres_kernel<ET, NI, TR, IW, IH>, a.n_blocks, 768, lds, s, a);
 }
 template <int ET>
 hipError_t launch_conv3x3_xres(const ConvArgs& a, hipStream_t s) {
@@ -468,20 +442,9 @@ bool is_s2_shape(const ConvArgs& a) {
 template <int ET, int TR, int OW, int OH>
 hipError_t launch_conv3x3_s2_t(ConvArgs a, hipStream_t s) {
     constexpr size_t lds = 3 * 32768 + 3 * 128 * 128;
-    auto kern = conv3x3_s2_kernel<ET, 128, TR, OW, OH>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     a.n_ctiles = a.Cout / 128;
     a.n_blocks = (OW == 7 ? (a.N + 3) / 4 : a.N * (OH / TR)) * a.n_ctiles;
-    const int grid = a.n_blocks < g_num_cus ? a.n_blocks : g_num_cus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(768), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(conv3x3_s2_kernel<ET, 128, TR, OW, OH>, a.n_blocks, 768, lds, s, a);
 }
 template <int ET>
 hipError_t launch_conv3x3_s2(const ConvArgs& a, hipStream_t s) {
@@ -503,21 +466,10 @@ template <int ET, int NR, bool DUAL>
 hipError_t launch_gemm8p_t(ConvArgs a, hipStream_t s) {
     constexpr int BP = 32 * NR;
     constexpr size_t lds = 2 * 4 * 16384;
-    auto kern = gemm8p_kernel<ET, NR, DUAL>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     a.n_ctiles = a.Cout / 256;
     a.n_blocks = a.n_ctiles * ((a.M + BP - 1) / BP);
     a.div_ctiles = make_fast_div((unsigned)a.n_ctiles);
-    const int grid = a.n_blocks < g_num_cus ? a.n_blocks : g_num_cus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(gemm8p_kernel<ET, NR, DUAL>, a.n_blocks, 512, lds, s, a);
 }
 template <int ET>
 hipError_t launch_gemm8p(const ConvArgs& a, int tile, hipStream_t s) {
@@ -723,19 +675,26 @@ void prof_end(r50_handle* h, hipStream_t s, EvRec& r) {
     (void)hipEventRecord(r.b, s);
     h->ev_pending.push_back(r);
 }
+// One launch between its profiling brackets.  A failure reads "<what>: <hip error>", or "<what> (<key><key_suffix>): <hip error>" with a conv key.
+const std::string kNoKey;
+template <typename F>
+int profiled(r50_handle* h, hipStream_t s, int cls, double flops, double bytes, int layer, const char* what, const std::string& key, F&& launch,
+             const char* key_suffix = "") {
+    EvRec r{};
+    prof_begin(h, s, r, cls, flops, bytes, layer);
+    const hipError_t e = launch();
+    prof_end(h, s, r);
+    if (e == hipSuccess) return R50_OK;
+    return fail(h, R50_ERR_HIP, what + (key.empty() ? std::string() : " (" + key + key_suffix + ")") + ": " + hipGetErrorString(e));
+}
 
 // conv3 (64 -> 256) + identity + ReLU + next conv1 (256 -> c1) in one launch (kernels.h: bneck_tail_kernel).
 // wd/bd non-null: `res` is the block INPUT (m,64) and the identity is the downsample conv computed in the kernel.
 template <int ET, int C1, bool DS, int NT>
 hipError_t launch_bneck_tail_t(const TailArgs& a, hipStream_t s) {
     const size_t lds = 256 * 128 * (DS ? 2 : 1) + (size_t)C1 * 512 + 256 * 4 * (DS ? 2 : 1) + (size_t)C1 * 4;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bneck_tail_kernel<ET, C1, DS, NT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
     const long long tiles = ((long long)a.M + 15) / 16;
-    const int grid = (int)std::min<long long>((tiles + NT / 64 - 1) / (NT / 64), (long long)g_num_cus);
-    hipLaunchKernelGGL((bneck_tail_kernel<ET, C1, DS, NT>), dim3(grid), dim3(NT), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(bneck_tail_kernel<ET, C1, DS, NT>, (tiles + NT / 64 - 1) / (NT / 64), NT, lds, s, a);
 }
 
 #ifndef TAIL_NT_DS
@@ -752,12 +711,6 @@ hipError_t launch_bneck_tail(const void* y2, long long m, const void* w3, const 
     a.y2 = (const __bf16*)y2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
     a.wd = (const __bf16*)wd; a.bd = bd;
     a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.M = (int)m;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     // 4 waves per CU stream best (more waves lower the HBM rate); the downsample variant has 1.5x the MFMA work
     if (et == 1) {
         if (wd) return c1 == 64 ? launch_bneck_tail_t<1, 64, true, TAIL_NT_DS>(a, s) : launch_bneck_tail_t<1, 128, true, TAIL_NT_DS>(a, s);
@@ -774,20 +727,8 @@ hipError_t launch_bneck_tail2(const void* y2, long long m, const void* w3, const
     Tail2Args a;
     a.y2 = (const __bf16*)y2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
     a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.M = (int)m;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
-    const long long steps = (m + 15) / 16;
-    const int grid = (int)std::min<long long>(steps, (long long)g_num_cus);
     const size_t lds = 2 * 8 * 8 * 1024 + 512 * 4 + 2 * 4096;
-    auto kern = et == 1 ? bneck_tail2_kernel<1> : bneck_tail2_kernel<0>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(et == 1 ? bneck_tail2_kernel<1> : bneck_tail2_kernel<0>, (m + 15) / 16, 512, lds, s, a);
 }
 
 // layer3 shapes: conv3 (256 -> 1024) + identity + ReLU chained with the next conv1 (1024 -> 256) (kernels.h: bneck_tail3_kernel)
@@ -810,12 +751,8 @@ hipError_t launch_bneck_tail3(const void* y2, long long m, const void* wp, const
     if (no_next) { b1 = b3; y1n = out; }       // conv3 + identity + ReLU only (group B copies out): b1 / y1n are not used
     if (bp_override == 0) bp_override = g_tail3_bp;
     if (!y2 || !wp || !b3 || !res || !out || !b1 || !y1n || m <= 0 || m * 2048 >= (1ll << 31)) return hipErrorInvalidValue;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
+    const int cus = num_cus();
+    if (cus == 0) return hipErrorInvalidDevice;
     Tail3Args a;
     a.y2 = (const __bf16*)y2; a.wp = (const __bf16*)wp; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
     a.b1 = b1; a.y1n = (__bf16*)y1n; a.M = (int)m;
@@ -823,26 +760,22 @@ hipError_t launch_bneck_tail3(const void* y2, long long m, const void* wp, const
     a.dbg = g_dbg;
 #endif
     constexpr int rows = 112;
-    const long long rounds = ((m + rows - 1) / rows + g_num_cus - 1) / g_num_cus;
-    long long bp = (m + rounds * g_num_cus - 1) / (rounds * g_num_cus);
+    const long long rounds = ((m + rows - 1) / rows + cus - 1) / cus;
+    long long bp = (m + rounds * cus - 1) / (rounds * cus);
     if (bp < 49) bp = 49;
     if (bp > rows) bp = rows;
     // more than one round of tiles: FULL tiles (batch 256: 448 tiles of 112 instead of 512 of 98 in 112 rows).  An eighth of the MFMA columns of a
     // 98-pixel tile multiply padding; the ragged last round that full tiles leave is filled by the other lane's launches (bench.py --lanes 2:
     // +0.9 % frames/s, two same-box pairs; neutral with one lane)
-    if ((m + rows - 1) / rows > g_num_cus) bp = rows;
+    if ((m + rows - 1) / rows > cus) bp = rows;
     if (bp_override >= 1 && bp_override <= rows) bp = bp_override;
     a.bp = (int)bp;
     a.n_tiles = (int)((m + bp - 1) / bp);
-    const int grid = a.n_tiles < g_num_cus ? a.n_tiles : g_num_cus;
     const size_t ldsp = 8 * (size_t)rows * 128 + 256 * 4 + 1024 * 4;      // t2 (4 slots) + out_c (2 x 2) + b1 + b3
     void (*kp)(const Tail3Args);
     if (no_next) kp = et == 1 ? bneck_tail3p_kernel<1, 112, true> : bneck_tail3p_kernel<0, 112, true>;
     else kp = et == 1 ? bneck_tail3p_kernel<1, 112> : bneck_tail3p_kernel<0, 112>;
-    hipError_t ep = hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-    if (ep != hipSuccess) return ep;
-    hipLaunchKernelGGL(kp, dim3(grid), dim3(512), ldsp, s, a);
-    return hipGetLastError();
+    return launch_persistent(kp, a.n_tiles, 512, ldsp, s, a);
 }
 
 // layer2.0 transition tail: conv3 + downsample (one conv over K = [t2 | x at stride 2]) + ReLU chained with the next block's conv1
@@ -859,12 +792,8 @@ hipError_t launch_bneck_catchain(const void* t2, const void* x, int n, int ow, c
     if (!t2 || !x || !wp || !bcat || !out || !b1 || !y1n || n <= 0 || ow != 28) return hipErrorInvalidValue;
     const long long m = (long long)n * ow * ow;
     if (m * 1024 >= (1ll << 31) || (long long)n * 4 * ow * ow * 512 >= (1ll << 31)) return hipErrorInvalidValue;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
+    const int cus = num_cus();
+    if (cus == 0) return hipErrorInvalidDevice;
     CatChainArgs a;
     a.t2 = (const __bf16*)t2; a.x = (const __bf16*)x; a.wp = (const __bf16*)wp; a.b3 = bcat; a.out = (__bf16*)out; a.b1 = b1; a.y1n = (__bf16*)y1n;
     a.M = (int)m; a.x_bytes = (unsigned)((long long)n * (x_sub ? 1 : 4) * ow * ow * 512); a.x_sub = x_sub ? 1 : 0;
@@ -874,16 +803,11 @@ hipError_t launch_bneck_catchain(const void* t2, const void* x, int n, int ow, c
     // full 112-pixel tiles when there is more than one round of them (batch 256: 1792 tiles = 7 per CU), else spread over the chip
     const long long full = (m + 111) / 112;
     long long bp = 112;
-    if (full <= g_num_cus) { bp = (m + g_num_cus - 1) / g_num_cus; if (bp < 16) bp = 16; if (bp > 112) bp = 112; }
+    if (full <= cus) { bp = (m + cus - 1) / cus; if (bp < 16) bp = 16; if (bp > 112) bp = 112; }
     a.bp = (int)bp;
     a.n_tiles = (int)((m + bp - 1) / bp);
-    const int grid = a.n_tiles < g_num_cus ? a.n_tiles : g_num_cus;
     const size_t lds = 10 * 112 * 128 + 128 * 4 + 512 * 4 + 16;        // operand slots + out_c + b1 + b3 + 4 sync words
-    auto kern = et == 1 ? bneck_catchain_kernel<1, 28> : bneck_catchain_kernel<0, 28>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(et == 1 ? bneck_catchain_kernel<1, 28> : bneck_catchain_kernel<0, 28>, a.n_tiles, 512, lds, s, a);
 }
 
 // layer2.1-.3 bottleneck body in one launch (kernels.h: bneck_block2_kernel): conv2 + conv3 + identity + ReLU [+ the next block's conv1]
@@ -891,24 +815,14 @@ hipError_t launch_bneck_block2(const void* t1, int n, const void* w2, const floa
                                void* out, const void* w1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
     if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || n <= 0 || (long long)n * 784 * 1024 >= (1ll << 31)) return hipErrorInvalidValue;
     if ((w1 == nullptr) != (b1 == nullptr) || (w1 == nullptr) != (y1n == nullptr)) return hipErrorInvalidValue;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     Block2Args a;
     a.t1 = (const __bf16*)t1; a.w2 = (const __bf16*)w2; a.b2 = b2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res;
     a.out = (__bf16*)out; a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.N = n; a.n_tiles = 4 * n;
-    const int grid = a.n_tiles < g_num_cus ? a.n_tiles : g_num_cus;
     const size_t lds = (w1 ? 3 * 208 * 128 + 224 * 128 : 4 * 208 * 128) + 3 * 16384 + 768 * 4;       // 160,768 / 158,720 (kernels.h: LDS map)
     void (*kern)(const Block2Args);
     if (w1) kern = et == 1 ? bneck_block2_kernel<1, 128> : bneck_block2_kernel<0, 128>;
     else kern = et == 1 ? bneck_block2_kernel<1, 0> : bneck_block2_kernel<0, 0>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(768), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(kern, a.n_tiles, 768, lds, s, a);
 }
 
 // layer1.1 / .2 bottleneck body in one launch (kernels.h: bneck_block1_kernel): conv2 + conv3 + identity + ReLU + the next conv1 (c1 = 64 or 128)
@@ -918,26 +832,16 @@ hipError_t launch_bneck_block1(const void* t1, int n, const void* w2, const floa
     if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || n <= 0 || (long long)n * 3136 * 512 >= (1ll << 31)) return hipErrorInvalidValue;
     if (c1 != 64 && c1 != 128) return hipErrorInvalidValue;
     if ((wd == nullptr) != (bd == nullptr) || (wd && c1 != 64)) return hipErrorInvalidValue;       // downsample form: layer1.0 (next conv1 256 -> 64)
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     Block1Args a;
     a.t1 = (const __bf16*)t1; a.w2 = (const __bf16*)w2; a.b2 = b2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res;
     a.out = (__bf16*)out; a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.N = n; a.n_tiles = 14 * n;
     a.wd = (const __bf16*)wd; a.bd = bd; a.out_sub = out_sub ? 1 : 0;
-    const int grid = a.n_tiles < g_num_cus ? a.n_tiles : g_num_cus;
     constexpr size_t lds = 11 * 32 * 128 + 3 * 224 * 128 + 3 * 8192 + (448 + 256) * 4;       // 158,464 (kernels.h: LDS map; bd behind b1)
     void (*kern)(const Block1Args);
     if (wd) kern = et == 1 ? bneck_block1_kernel<1, 64, true> : bneck_block1_kernel<0, 64, true>;
     else if (c1 == 64) kern = et == 1 ? bneck_block1_kernel<1, 64> : bneck_block1_kernel<0, 64>;
     else kern = et == 1 ? bneck_block1_kernel<1, 128> : bneck_block1_kernel<0, 128>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(768), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent(kern, a.n_tiles, 768, lds, s, a);
 }
 
 // q_inv > 0: write the output as e4m3 = fp8(16-bit result * q_inv) (role-specialised tiles only; *q_done reports whether that happened)
@@ -949,7 +853,6 @@ int run_conv(r50_handle* h, const ConvLayer& L, const __bf16* x, int n, int hh, 
     int rc = fill_conv_args(a, x, n, hh, ww, L.cin, L.w, L.bias, res, y, L.cout, L.ks, L.stride, L.pad, relu, split, w2);
     if (rc) return fail(h, rc, "conv args invalid for " + L.conv_key);
     a.et = (h->precision == R50_PREC_FP16) ? 1 : 0;
-    EvRec r{};
     const double flops = 2.0 * a.M * (double)a.Cout * L.ks * L.ks * L.cin;       // algorithmic (not the 3x of split mode)
     const double bytes = 2.0 * ((double)n * hh * ww * L.cin + (double)a.M * a.Cout * (res ? 2 : 1) + (double)a.Cout * L.ks * L.ks * L.cin);
     int tile = h->tile_override;
@@ -961,12 +864,8 @@ int run_conv(r50_handle* h, const ConvLayer& L, const __bf16* x, int n, int hh, 
             if (q_done) *q_done = true;
         }
     }
-    prof_begin(h, s, r, PC_IGEMM, flops, bytes, (int)(&L - &h->convs[0]));
-    hipError_t e = launch_igemm(a, tile, s, split);
-    prof_end(h, s, r);
-    if (e != hipSuccess) return fail(h, R50_ERR_HIP, "igemm launch (" + L.conv_key + "): " + hipGetErrorString(e));
     *ho = a.Ho; *wo = a.Wo;
-    return R50_OK;
+    return profiled(h, s, PC_IGEMM, flops, bytes, (int)(&L - &h->convs[0]), "igemm launch", L.conv_key, [&] { return launch_igemm(a, tile, s, split); });
 }
 
 // 1x1 conv over two K sources: y = act([W1 | W2] . [x1 ; x2 at stride2] + bias).  x1 (n,h,w,c1) at the output resolution,
@@ -1004,14 +903,10 @@ int run_conv_cat(r50_handle* h, int si, const ConvLayer& c3, const ConvLayer& cd
     int rc = fill_conv_args_cat(a, t2, n, h2, w2, c3.cin, xin, hin, win, cd.cin, cd.stride, h->cat_w[si], h->cat_bias[si], y, c3.cout, 1);
     if (rc) return fail(h, rc, "two-source conv args invalid for " + c3.conv_key);
     a.et = (h->precision == R50_PREC_FP16) ? 1 : 0;
-    EvRec r{};
     const double flops = 2.0 * a.M * (double)a.Cout * a.Ktot;
     const double bytes = 2.0 * ((double)a.M * (c3.cin + cd.cin) + (double)a.M * a.Cout + (double)a.Cout * a.Ktot);
-    prof_begin(h, s, r, PC_IGEMM, flops, bytes, (int)(&c3 - &h->convs[0]));
-    hipError_t e = launch_igemm(a, cat_tile(a, 0), s, false);
-    prof_end(h, s, r);
-    if (e != hipSuccess) return fail(h, R50_ERR_HIP, "igemm launch (" + c3.conv_key + " + downsample): " + hipGetErrorString(e));
-    return R50_OK;
+    return profiled(h, s, PC_IGEMM, flops, bytes, (int)(&c3 - &h->convs[0]), "igemm launch", c3.conv_key,
+                    [&] { return launch_igemm(a, cat_tile(a, 0), s, false); }, " + downsample");
 }
 
 template <typename TIN>
@@ -1033,18 +928,11 @@ hipError_t launch_stem_conv(const void* xp, const void* wpk, const float* bias, 
 // batch, 1/2/4/7/14/28 = that many pairs per strip: r50_set_option("stem_strip") or R50_STEM_STRIP in the environment (A/B).
 // (Removed in round 4: the per-pair kernel of round 1 and the strip kernel of rounds 2-3, whose phases ran in turn.)
 static int g_stem_strip = [] { const char* v = std::getenv("R50_STEM_STRIP"); const int g = v ? std::atoi(v) : 0; return g > 0 && 28 % g == 0 ? g : 0; }();
-bool stem_strip_enabled() { return true; }
 // c1_w / c1_bias / y1 non-null: layer1.0.conv1 (+ bias + ReLU) of the pooled output into y1 in the same launch
 template <typename TIN>
 hipError_t launch_stem_fused(const TIN* x, const void* wpk, const float* bias, void* y, int n, hipStream_t s,
                              const float* u8_table, int et = 0, const void* c1_w = nullptr, const float* c1_bias = nullptr,
                              void* y1 = nullptr) {
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        g_num_cus = cu_budget(prop.multiProcessorCount);
-    }
     // G = the longest strip that still gives the chip ~200 workgroups (28 = the whole image from batch 200 up)
     int G = 1;
     if (g_stem_strip > 0) G = g_stem_strip;
@@ -1053,21 +941,17 @@ hipError_t launch_stem_fused(const TIN* x, const void* wpk, const float* bias, v
             if (n * (28 / cand) >= 200) { G = cand; break; }
     const bool c1 = c1_w && c1_bias && y1;
     const int strips = n * (28 / G);
-    const int grid = strips < g_num_cus ? strips : g_num_cus;
     // 16-B (fp32) / 4-B (uint8) loads of 4 pixels: image rows start at multiples of 896 / 224 bytes from the frame pointer
     if (reinterpret_cast<uintptr_t>(x) & (sizeof(TIN) == 1 ? 3u : 15u)) return hipErrorInvalidValue;
     auto kern = c1 ? (et == 1 ? stem_fused3_kernel<1, TIN, true> : stem_fused3_kernel<0, TIN, true>)
                    : (et == 1 ? stem_fused3_kernel<1, TIN, false> : stem_fused3_kernel<0, TIN, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SF3_LDS_BYTES);
-    if (e != hipSuccess) return e;
 #if defined(R50_STAMP)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SF3_THREADS), SF3_LDS_BYTES, s, x, (const char*)wpk, bias, (__bf16*)y, strips, G, u8_table,
-                       (const __bf16*)c1_w, c1_bias, (__bf16*)y1, g_dbg);
+    return launch_persistent(kern, strips, SF3_THREADS, SF3_LDS_BYTES, s, x, (const char*)wpk, bias, (__bf16*)y, strips, G, u8_table,
+                             (const __bf16*)c1_w, c1_bias, (__bf16*)y1, g_dbg);
 #else
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SF3_THREADS), SF3_LDS_BYTES, s, x, (const char*)wpk, bias, (__bf16*)y, strips, G, u8_table,
-                       (const __bf16*)c1_w, c1_bias, (__bf16*)y1);
+    return launch_persistent(kern, strips, SF3_THREADS, SF3_LDS_BYTES, s, x, (const char*)wpk, bias, (__bf16*)y, strips, G, u8_table,
+                             (const __bf16*)c1_w, c1_bias, (__bf16*)y1);
 #endif
-    return hipGetLastError();
 }
 template <typename TIN>
 hipError_t launch_stem_split(const TIN* x, char* xp_head, char* xp_tail, const char* w_head, const char* w_tail,
@@ -1126,15 +1010,10 @@ int run_conv_fp8(r50_handle* h, const ConvLayer& L, const void* x, int n, int hh
     if (rc) return fail(h, rc, "fp8 conv args invalid for " + L.conv_key);
     a.y_bytes = (unsigned)((long long)a.M * L.cout);
     a.et = 2; a.oscale = sx * L.wscale / sy; a.rscale = sr / sy;
-    EvRec r{};
     const double flops = 2.0 * a.M * (double)a.Cout * L.ks * L.ks * L.cin;
     const double bytes = (double)n * hh * ww * L.cin + (double)a.M * a.Cout * (res ? 2 : 1) + (double)a.Cout * L.ks * L.ks * L.cin;
-    prof_begin(h, s, r, PC_IGEMM, flops, bytes, (int)(&L - &h->convs[0]));
-    hipError_t e = launch_igemm_fp8(a, 0, s);
-    prof_end(h, s, r);
-    if (e != hipSuccess) return fail(h, R50_ERR_HIP, "fp8 igemm launch (" + L.conv_key + "): " + hipGetErrorString(e));
     *ho = a.Ho; *wo = a.Wo;
-    return R50_OK;
+    return profiled(h, s, PC_IGEMM, flops, bytes, (int)(&L - &h->convs[0]), "fp8 igemm launch", L.conv_key, [&] { return launch_igemm_fp8(a, 0, s); });
 }
 
 // buf[cur] holds layer1's output (n,56,56,256) as 16-bit elements: quantise it, run layer2-4 in fp8, pool.
@@ -1144,16 +1023,16 @@ int run_fp8_part(r50_handle* h, __bf16* const* buf, int cur, int n, float* out, 
     const float* sc = h->fp8_scales.data();
     int k = 0;
     float s_in = sc[k++];
-    EvRec r{};
     int nxt = (cur + 1) % 5;
+    int rc;
     if (!already_fp8) {
         const long long n4 = (long long)n * 56 * 56 * 256 / 4;
-        prof_begin(h, s, r, PC_MAXPOOL, 0, (double)n4 * 12);
-        hipLaunchKernelGGL(quant_to_fp8_kernel<0>, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256 * 64)), dim3(256), 0, s,
-                           (const unsigned short*)buf[cur], (unsigned*)buf[nxt], n4, 1.0f / s_in);
-        prof_end(h, s, r);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("quant_to_fp8: ") + hipGetErrorString(e));
+        rc = profiled(h, s, PC_MAXPOOL, 0, (double)n4 * 12, -1, "quant_to_fp8", kNoKey, [&] {
+            hipLaunchKernelGGL(quant_to_fp8_kernel<0>, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256 * 64)), dim3(256), 0, s,
+                               (const unsigned short*)buf[cur], (unsigned*)buf[nxt], n4, 1.0f / s_in);
+            return hipGetLastError();
+        });
+        if (rc) return rc;
         cur = nxt;
     }
     int hh = 56, ww = 56;
@@ -1165,7 +1044,7 @@ int run_fp8_part(r50_handle* h, __bf16* const* buf, int cur, int n, float* out, 
                 if (i != cur) fr[nf++] = i;
             const ConvLayer &c1 = h->convs[li], &c2 = h->convs[li + 1], &c3 = h->convs[li + 2];
             const float s_t1 = sc[k++], s_t2 = sc[k++];
-            int h1, w1, h2, w2, h3, w3, rc;
+            int h1, w1, h2, w2, h3, w3;
             if ((rc = run_conv_fp8(h, c1, buf[cur], n, hh, ww, nullptr, buf[fr[0]], 1, s_in, 1.f, s_t1, s, &h1, &w1))) return rc;
             if ((rc = run_conv_fp8(h, c2, buf[fr[0]], n, h1, w1, nullptr, buf[fr[1]], 1, s_t1, 1.f, s_t2, s, &h2, &w2))) return rc;
             const void* idn = buf[cur];
@@ -1189,328 +1068,237 @@ int run_fp8_part(r50_handle* h, __bf16* const* buf, int cur, int n, float* out, 
                 a.y_bytes = (unsigned)((long long)a.M * c3.cout);
                 a.et = 2; a.oscale = h->cat_acc_scale[si] / s_out; a.rscale = 0.f;
                 const double flops = 2.0 * a.M * (double)a.Cout * (c3.cin + cd.cin);
-                prof_begin(h, s, r, PC_IGEMM, flops, (double)a.M * (c3.cin + cd.cin + a.Cout) + (double)a.Cout * (c3.cin + cd.cin), (int)(&c3 - &h->convs[0]));
-                hipError_t e = launch_igemm_fp8(a, 0, s);
-                prof_end(h, s, r);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "fp8 two-source igemm launch (" + c3.conv_key + "): " + hipGetErrorString(e));
+                rc = profiled(h, s, PC_IGEMM, flops, (double)a.M * (c3.cin + cd.cin + a.Cout) + (double)a.Cout * (c3.cin + cd.cin), (int)(&c3 - &h->convs[0]),
+                              "fp8 two-source igemm launch", c3.conv_key, [&] { return launch_igemm_fp8(a, 0, s); });
+                if (rc) return rc;
                 h3 = h2; w3 = w2;
             } else if ((rc = run_conv_fp8(h, c3, buf[fr[1]], n, h2, w2, idn, buf[fr[3]], 1, s_t2, s_idn, s_out, s, &h3, &w3))) return rc;
             cur = fr[3]; hh = h3; ww = w3; s_in = s_out;
             li += (b == 0) ? 4 : 3;
         }
-    prof_begin(h, s, r, PC_AVGPOOL, 0, (double)n * (hh * ww * 2048.0 + 2048.0 * 4));
-    hipLaunchKernelGGL(avgpool_fp8_kernel, dim3((n * 256 + 255) / 256), dim3(256), 0, s, (const unsigned char*)buf[cur], out, n, hh * ww, 2048,
-                       s_in / (float)(hh * ww));
-    prof_end(h, s, r);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("avgpool_fp8: ") + hipGetErrorString(e));
-    return R50_OK;
+    return profiled(h, s, PC_AVGPOOL, 0, (double)n * (hh * ww * 2048.0 + 2048.0 * 4), -1, "avgpool_fp8", kNoKey, [&] {
+        hipLaunchKernelGGL(avgpool_fp8_kernel, dim3((n * 256 + 255) / 256), dim3(256), 0, s, (const unsigned char*)buf[cur], out, n, hh * ww, 2048,
+                           s_in / (float)(hh * ww));
+        return hipGetLastError();
+    });
 }
 
-// Runs `n` frames (n <= max_batch) through the stack.  If `tap` is non-null, stops once the named
-// activation is available and reports it through tap_ptr / dims.
+PlanInputs plan_inputs(const r50_handle* h, const char* tap) {
+    PlanInputs in;
+    in.precision = h->precision;
+    in.fused_stem = h->fused_stem; in.fuse_stem_c1 = h->fuse_stem_c1; in.fuse_tail = h->fuse_tail; in.fuse_tail3 = h->fuse_tail3;
+    in.fuse_tail3_last = h->fuse_tail3_last; in.fuse_ds_cat = h->fuse_ds_cat; in.fuse_cat_chain = h->fuse_cat_chain; in.sub_out = h->sub_out;
+    in.fuse_block1 = h->fuse_block1; in.fuse_block2 = h->fuse_block2; in.inplace_out = h->inplace_out; in.overlap_ds = h->overlap_ds;
+    in.fuse_fp8_handover = h->fuse_fp8_handover; in.tile_override = h->tile_override; in.profile = h->profile;
+    for (int i = 0; i < 4; ++i) in.cat_w[i] = h->cat_w[i] != nullptr;
+    for (int b = 0; b < 8; ++b) in.tail3_wp[b] = h->tail3_wp[b] != nullptr;
+    in.catchain_wp = h->catchain_wp != nullptr;
+    in.fp8_scales_complete = (int)h->fp8_scales.size() == R50_FP8_NUM_SCALES;
+    in.tap = tap;
+    for (int i = 0; i < kNumConvs; ++i) in.convs[i] = h->convs[i];
+    return in;
+}
+
+// Runs `n` frames (n <= max_batch) through the stack: plans the launches (launch_plan.h) and executes the plan.  If `tap` is
+// non-null, stops once the named activation is available and reports it through tap_ptr / dims.
 template <typename TIN>
 int run_stack(r50_handle* h, const TIN* x, int n, float* out, hipStream_t s, const char* tap,
               const __bf16** tap_ptr, int64_t dims[4], int slot0 = 0) {
     // slot0: first frame slot of the workspace this call may use (concurrent calls on different streams
     // work on disjoint frame ranges of the same buffers)
+    const StackPlan plan = plan_stack(plan_inputs(h, tap));
     const bool split = (h->precision == R50_PREC_FP32X);
     const int et = (h->precision == R50_PREC_FP16) ? 1 : 0;      // element type of weights / activations (kernels.h)
     const int cmul = split ? 2 : 1;            // channels per pixel multiplier of every activation tensor
     __bf16* buf[5];
     for (int i = 0; i < 5; ++i) buf[i] = h->buf[i] + (size_t)slot0 * 112 * 112 * 64 * cmul;
     char* stem_xp = h->stem_xp + (size_t)slot0 * STEM_HP * STEM_WP * 8 * cmul;
-    auto hit = [&](const std::string& name, const __bf16* p, int hh, int ww, int c) {
-        if (tap && name == tap) {
-            *tap_ptr = p; dims[0] = n; dims[1] = hh; dims[2] = ww; dims[3] = c * cmul;
-            return true;
-        }
-        return false;
+    auto report = [&](const __bf16* p, int hh, int ww, int c) {
+        *tap_ptr = p; dims[0] = n; dims[1] = hh; dims[2] = ww; dims[3] = c * cmul;
+        return R50_OK;
     };
-    EvRec r{};
-    hipError_t e;
-    bool stem_c1 = false;       // layer1.0.conv1 already computed by the stem kernel (into buf[2])
-    if (split) {
-        char* xp_tail = stem_xp + (size_t)n * STEM_HP * STEM_WP * 8;
-        prof_begin(h, s, r, PC_STEM_CONV, 2.0 * n * 112 * 112 * 64 * 147.0, (double)n * (3.0 * 224 * 224 * 4 + 112.0 * 112 * 128 * 2));
-        e = launch_stem_split(x, stem_xp, xp_tail, h->stem_w, h->stem_w + STEM_W_BYTES, h->convs[0].bias, buf[0], n, s);
-        prof_end(h, s, r);
-        if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("stem (split): ") + hipGetErrorString(e));
-    } else if (h->fused_stem && !(tap && std::string(tap) == "stem")) {
-        // conv1 + bn1 + relu + maxpool in one kernel: frame in, (n,56,56,64) out
-        // ... and, in the strip version, layer1.0.conv1 (1x1, 64 -> 64) of the pooled rows into buf[2] while they are still in LDS
-        const ConvLayer& l1c1 = h->convs[1];
-        stem_c1 = h->fuse_stem_c1 && stem_strip_enabled() && (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16 || h->precision == R50_PREC_FP8) &&
-                  h->tile_override == 0 && l1c1.ks == 1 && l1c1.stride == 1 && l1c1.cin == 64 && l1c1.cout == 64;
-        prof_begin(h, s, r, PC_STEM_CONV, 2.0 * n * 112 * 112 * 64 * 147.0 + (stem_c1 ? 2.0 * n * 56 * 56 * 64 * 64 : 0.0),
-                   (double)n * (3.0 * 224 * 224 * 4 + 56.0 * 56 * 64 * 2 * (stem_c1 ? 2 : 1)));
-        e = launch_stem_fused(x, h->stem_w, h->convs[0].bias, buf[1], n, s, h->u8_table, et, stem_c1 ? l1c1.w : nullptr,
-                              stem_c1 ? l1c1.bias : nullptr, stem_c1 ? buf[2] : nullptr);
-        prof_end(h, s, r);
-        if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("stem_fused: ") + hipGetErrorString(e));
-        goto after_pool;
-    } else {
-        prof_begin(h, s, r, PC_STEM_PACK, 0, (double)n * (3.0 * 224 * 224 * 4 + (double)STEM_HP * STEM_WP * 8));
-        e = launch_stem_pack(x, stem_xp, n, s, et);
-        prof_end(h, s, r);
-        if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("stem_pack: ") + hipGetErrorString(e));
-
-        prof_begin(h, s, r, PC_STEM_CONV, 2.0 * n * 112 * 112 * 64 * 147.0,
-                   (double)n * ((double)STEM_HP * STEM_WP * 8 + 112.0 * 112 * 64 * 2));
-        e = launch_stem_conv(stem_xp, h->stem_w, h->convs[0].bias, buf[0], n, s, et);
-        prof_end(h, s, r);
-        if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("stem_conv: ") + hipGetErrorString(e));
+    int rc = R50_OK;
+    const bool stem_c1 = plan.stem == Stem::FusedConv1;       // layer1.0.conv1 is computed by the stem kernel (into buf[2])
+    switch (plan.stem) {
+        case Stem::Split: {
+            char* xp_tail = stem_xp + (size_t)n * STEM_HP * STEM_WP * 8;
+            rc = profiled(h, s, PC_STEM_CONV, 2.0 * n * 112 * 112 * 64 * 147.0, (double)n * (3.0 * 224 * 224 * 4 + 112.0 * 112 * 128 * 2), -1, "stem (split)", kNoKey,
+                          [&] { return launch_stem_split(x, stem_xp, xp_tail, h->stem_w, h->stem_w + STEM_W_BYTES, h->convs[0].bias, buf[0], n, s); });
+            break;
+        }
+        case Stem::Fused: case Stem::FusedConv1: {
+            // conv1 + bn1 + relu + maxpool in one kernel: frame in, (n,56,56,64) out
+            // ... and layer1.0.conv1 (1x1, 64 -> 64) of the pooled rows into buf[2] while they are still in LDS
+            const ConvLayer& l1c1 = h->convs[1];
+            rc = profiled(h, s, PC_STEM_CONV, 2.0 * n * 112 * 112 * 64 * 147.0 + (stem_c1 ? 2.0 * n * 56 * 56 * 64 * 64 : 0.0),
+                          (double)n * (3.0 * 224 * 224 * 4 + 56.0 * 56 * 64 * 2 * (stem_c1 ? 2 : 1)), -1, "stem_fused", kNoKey, [&] {
+                              return launch_stem_fused(x, h->stem_w, h->convs[0].bias, buf[1], n, s, h->u8_table, et, stem_c1 ? l1c1.w : nullptr,
+                                                       stem_c1 ? l1c1.bias : nullptr, stem_c1 ? buf[2] : nullptr);
+                          });
+            break;
+        }
+        case Stem::PackConv:
+            rc = profiled(h, s, PC_STEM_PACK, 0, (double)n * (3.0 * 224 * 224 * 4 + (double)STEM_HP * STEM_WP * 8), -1, "stem_pack", kNoKey,
+                          [&] { return launch_stem_pack(x, stem_xp, n, s, et); });
+            if (rc) return rc;
+            rc = profiled(h, s, PC_STEM_CONV, 2.0 * n * 112 * 112 * 64 * 147.0, (double)n * ((double)STEM_HP * STEM_WP * 8 + 112.0 * 112 * 64 * 2), -1, "stem_conv",
+                          kNoKey, [&] { return launch_stem_conv(stem_xp, h->stem_w, h->convs[0].bias, buf[0], n, s, et); });
+            break;
     }
-    if (hit("stem", buf[0], 112, 112, 64)) return R50_OK;
-
-    prof_begin(h, s, r, PC_MAXPOOL, 0, (double)n * (112.0 * 112 + 56.0 * 56) * 64 * 2 * cmul);
-    e = split ? launch_maxpool_split(buf[0], buf[1], n, 112, 112, 64, s) : launch_maxpool(buf[0], buf[1], n, 112, 112, 64, s, et);
-    prof_end(h, s, r);
-    if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("maxpool: ") + hipGetErrorString(e));
-after_pool:
-    if (hit("pool", buf[1], 56, 56, 64)) return R50_OK;
+    if (rc) return rc;
+    if (plan.stem == Stem::Split || plan.stem == Stem::PackConv) {
+        if (plan.tap == TapAt::Stem) return report(buf[0], 112, 112, 64);
+        rc = profiled(h, s, PC_MAXPOOL, 0, (double)n * (112.0 * 112 + 56.0 * 56) * 64 * 2 * cmul, -1, "maxpool", kNoKey, [&] {
+            return split ? launch_maxpool_split(buf[0], buf[1], n, 112, 112, 64, s) : launch_maxpool(buf[0], buf[1], n, 112, 112, 64, s, et);
+        });
+        if (rc) return rc;
+    }
+    if (plan.tap == TapAt::Pool) return report(buf[1], 56, 56, 64);
 
     int cur = 1, hh = 56, ww = 56;
-    int pre_t1 = stem_c1 ? 2 : -1;      // buffer that already holds the coming block's conv1 output (fused tail / stem), or -1
+    int pre_t1 = stem_c1 ? 2 : -1;      // buffer that already holds the coming block's conv1 output (Conv1::Ready), or -1
     bool layer1_out_fp8 = false;        // fp8 mode: layer1's output was written as e4m3 by its last conv's epilogue
-    bool cur_sub = false;               // buf[cur] holds only the even rows / columns of the block output (layer1.2 with option "sub_out")
-    size_t li = 1;
-    for (int si = 0; si < 4; ++si) {
-        const int blocks = kStages[si][1];
-        if (si == 1 && h->precision == R50_PREC_FP8) {
-            if (tap) return fail(h, R50_ERR_INVALID, "fp8 mode: activations beyond layer1 are e4m3 tensors, taps stop at layer1.2");
-            return run_fp8_part(h, buf, cur, n, out, s, layer1_out_fp8);
-        }
-        for (int b = 0; b < blocks; ++b) {
-            int fr[4], nf = 0;
-            if (pre_t1 >= 0) fr[nf++] = pre_t1;          // conv1 of this block was computed by the previous block's fused tail
-            for (int i = 0; i < 5; ++i)
-                if (i != cur && i != pre_t1) fr[nf++] = i;
-            const bool have_t1 = (pre_t1 >= 0);
-            pre_t1 = -1;
-            if (cur_sub && !(si == 1 && b == 0)) return fail(h, R50_ERR_STATE, "internal: a sub-sampled block output reached a block that reads the full tensor");
-            const std::string p = "layer" + std::to_string(si + 1) + "." + std::to_string(b);
-            const ConvLayer& c1 = h->convs[li];
-            const ConvLayer& c2 = h->convs[li + 1];
-            const ConvLayer& c3 = h->convs[li + 2];
-            int h1, w1, h2, w2, h3, w3;
-            // The downsample branch of a stage's first block only depends on the block input: it runs on a side
-            // stream beside conv1 -> conv2 (fills the partially occupied last round of those launches).  Not while
-            // profiling (event brackets of two streams would interleave) and not when a tap is requested.
-            // layer1: conv3 + identity + ReLU and the next block's conv1 share one pass over the pixels; in the first
-            // block the identity (downsample conv of the block input) is computed inside that kernel as well
-            const size_t li_next = li + ((b == 0) ? 4 : 3);
-            const ConvLayer* nx = (li_next < h->convs.size()) ? &h->convs[li_next] : nullptr;
-            const bool nx_is_fp8 = (h->precision == R50_PREC_FP8 && li_next >= kFp8FirstConv);     // the next conv1's weights are e4m3 bytes
-            const bool fuse_ok = !split && !nx_is_fp8 && (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16 || h->precision == R50_PREC_FP8) && h->fuse_tail && h->tile_override == 0 && nx && c3.ks == 1 && c3.stride == 1 &&
-                                 nx->ks == 1 && nx->stride == 1;
-            const bool fuse2 = fuse_ok && c3.cin == 128 && c3.cout == 512 && nx->cin == 512 && nx->cout == 128;   // layer2 shapes
-            const bool fuse3 = fuse_ok && h->fuse_tail3 && b > 0 && b < 8 && h->tail3_wp[b] && c3.cin == 256 && c3.cout == 1024 && nx->cin == 1024 && nx->cout == 256;   // layer3 shapes (plain identity)
-            const ConvLayer* cdp = (b == 0) ? &h->convs[li + 3] : nullptr;
-            // layer2.0 / 3.0 / 4.0: conv3 + downsample + add + ReLU as ONE 1x1 conv over K = [t2 | block input at the block's stride]
-            // against [W3 | Wd]: the downsample tensor is never written or read back, and there is one launch instead of two.
-            // It takes precedence over the layer2 tail fusion in layer2.0 (whose identity would be that downsample tensor).
-            const bool cat_ds = (b == 0) && si >= 1 && !split && h->fuse_ds_cat && h->cat_w[si] && h->tile_override == 0 &&
-                                cdp && cdp->ks == 1 && c3.ks == 1 && !(tap && p + ".ds" == tap);
-            const bool fuse = !cat_ds && ((fuse_ok && c3.cin == 64 && c3.cout == 256 && nx->cin == 256 && (nx->cout == 64 || nx->cout == 128)) ||
-                                          fuse2 || fuse3);
-            const bool fuse_ds = fuse && cdp && cdp->ks == 1 && cdp->stride == 1 && cdp->cin == 64 && cdp->cout == 256 &&
-                                 !(tap && p + ".ds" == tap);
-            const bool ds_side = (b == 0) && h->overlap_ds && !h->profile && !tap && !fuse_ds && !cat_ds;
-            hipStream_t sd = s;
-            const __bf16* idn = buf[cur];
-            int rc;
-            if (ds_side) {
-                if (!h->ds_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->ds_stream, hipStreamNonBlocking));
-                if (!h->ev_ds_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_ds_fork, hipEventDisableTiming));
-                if (!h->ev_ds_join) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_ds_join, hipEventDisableTiming));
-                sd = h->ds_stream;
-                HIP_TRY(h, hipEventRecord(h->ev_ds_fork, s));          // block input complete
-                HIP_TRY(h, hipStreamWaitEvent(sd, h->ev_ds_fork, 0));
-                const ConvLayer& cd = h->convs[li + 3];
-                int hd, wd;
-                rc = run_conv(h, cd, buf[cur], n, hh, ww, nullptr, buf[fr[2]], 0, sd, &hd, &wd);
-                if (rc) return rc;
-                HIP_TRY(h, hipEventRecord(h->ev_ds_join, sd));
-                idn = buf[fr[2]];
-            }
-            // layer2.1-.3: the bottleneck body from conv2 on is ONE launch (kernels.h: bneck_block2_kernel) -- t2 never leaves the CU, and
-            // in .1 / .2 the next block's conv1 is chained through LDS as in the fused tails.  Same bits as the launches it replaces.
-            const bool block2 = h->fuse_block2 && h->fuse_tail && !split && !tap && si == 1 && b > 0 && h->tile_override == 0 && !ds_side &&
-                                (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16) && hh == 28 && ww == 28 && c1.cout == 128 &&
-                                c2.ks == 3 && c2.stride == 1 && c2.pad == 1 && c2.cin == 128 && c2.cout == 128 && c3.ks == 1 && c3.cin == 128 && c3.cout == 512;
-            // layer1.1 (and, option "fuse_block1" = 2, layer1.2): the same for the 56x56 / 64-channel body (kernels.h: bneck_block1_kernel)
-            const bool nx64 = nx && nx->ks == 1 && nx->stride == 1 && nx->cin == 256 && (nx->cout == 64 || (nx->cout == 128 && h->fuse_block1 >= 2));
-            const bool block1 = h->fuse_block1 && h->fuse_tail && !split && !tap && si == 0 && b > 0 && h->tile_override == 0 && nx64 &&
-                                (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16 || (h->precision == R50_PREC_FP8 && nx->cout == 64)) &&
-                                hh == 56 && ww == 56 && c1.cout == 64 && c2.ks == 3 && c2.stride == 1 && c2.pad == 1 && c2.cin == 64 && c2.cout == 64 &&
-                                c3.ks == 1 && c3.cin == 64 && c3.cout == 256;
-            // layer1.0 (option "fuse_block1" = 3, the default since round 3's second session): the same body kernel with the downsample conv
-            // of the block input as the identity (bneck_block1_kernel<.., DS>): conv3x3_c64 + fused tail (t2 written and read back) become one launch
-            const bool block1_ds = h->fuse_block1 >= 3 && h->fuse_tail && !split && !tap && si == 0 && b == 0 && h->tile_override == 0 && cdp && nx &&
-                                   (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16 || h->precision == R50_PREC_FP8) && hh == 56 && ww == 56 &&
-                                   c1.cout == 64 && c2.ks == 3 && c2.stride == 1 && c2.pad == 1 && c2.cin == 64 && c2.cout == 64 && c3.ks == 1 && c3.cin == 64 &&
-                                   c3.cout == 256 && cdp->ks == 1 && cdp->stride == 1 && cdp->cin == 64 && cdp->cout == 256 && nx->ks == 1 && nx->stride == 1 &&
-                                   nx->cin == 256 && nx->cout == 64 && !nx_is_fp8;
-            if (block1_ds) {
-                if (!have_t1) {
-                    rc = run_conv(h, c1, buf[cur], n, hh, ww, nullptr, buf[fr[0]], 1, s, &h1, &w1);
-                    if (rc) return rc;
-                }
-                const double m = (double)n * 3136.0;
-                EvRec rb{};
-                prof_begin(h, s, rb, PC_BLOCK2, 2.0 * m * (64.0 * 576 + 2 * 256.0 * 64 + 64.0 * 256),
-                           2.0 * (m * (64.0 + 64 + 256 + 64) + 64.0 * 576 + 2 * 256.0 * 64 + 64.0 * 256), (int)(&c2 - &h->convs[0]));
-                e = launch_bneck_block1(buf[fr[0]], n, c2.w, c2.bias, c3.w, c3.bias, buf[cur], buf[fr[3]], nx->w, 64, nx->bias, buf[fr[1]], s, et,
-                                        cdp->w, cdp->bias);
-                prof_end(h, s, rb);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "bneck_block1 (downsample) launch (" + c2.conv_key + "): " + hipGetErrorString(e));
-                pre_t1 = fr[1];
-                cur = fr[3];
-                li += 4;
-                continue;
-            }
-            if (block1) {
-                if (!have_t1) {
-                    rc = run_conv(h, c1, buf[cur], n, hh, ww, nullptr, buf[fr[0]], 1, s, &h1, &w1);
-                    if (rc) return rc;
-                }
-                const double m = (double)n * 3136.0;
-                EvRec rb{};
-                // layer1.2: the block output is read again only at its even rows and columns (layer2.0's stride-2 downsample conv, inside the chained
-                // transition tail; layer2.0.conv1 is computed in this launch): write just those -- 103 MB instead of 411 MB at batch 256.  Only when
-                // the consumer that understands the compact tensor is the one that will run (the conditions of the catchain branch below).
-                const bool sub = h->sub_out && nx->cout == 128 && b == blocks - 1 && h->fuse_ds_cat && h->cat_w[1] && h->fuse_cat_chain && h->catchain_wp &&
-                                 (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16);
-                prof_begin(h, s, rb, PC_BLOCK2, 2.0 * m * (64.0 * 576 + 256.0 * 64 + (double)nx->cout * 256),
-                           2.0 * (m * (64.0 + 256 + (sub ? 64.0 : 256.0) + nx->cout) + 64.0 * 576 + 256.0 * 64 + (double)nx->cout * 256), (int)(&c2 - &h->convs[0]));
-                e = launch_bneck_block1(buf[fr[0]], n, c2.w, c2.bias, c3.w, c3.bias, buf[cur], buf[fr[3]], nx->w, nx->cout, nx->bias, buf[fr[1]], s, et,
-                                        nullptr, nullptr, sub);
-                cur_sub = sub;
-                prof_end(h, s, rb);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "bneck_block1 launch (" + c2.conv_key + "): " + hipGetErrorString(e));
-                pre_t1 = fr[1];
-                cur = fr[3];
-                li += 3;
-                continue;
-            }
-            if (block2) {
-                if (!have_t1) {
-                    rc = run_conv(h, c1, buf[cur], n, hh, ww, nullptr, buf[fr[0]], 1, s, &h1, &w1);
-                    if (rc) return rc;
-                }
-                const bool chain = nx && nx->ks == 1 && nx->stride == 1 && nx->cin == 512 && nx->cout == 128;
-                const double m = (double)n * 784.0;
-                EvRec rb{};
-                prof_begin(h, s, rb, PC_BLOCK2, 2.0 * m * (128.0 * 1152 + 512.0 * 128 + (chain ? 128.0 * 512 : 0.0)),
-                           2.0 * (m * (128.0 + 512 + 512 + (chain ? 128.0 : 0.0)) + 128.0 * 1152 + 512.0 * 128 + (chain ? 128.0 * 512 : 0.0)),
-                           (int)(&c2 - &h->convs[0]));
-                e = launch_bneck_block2(buf[fr[0]], n, c2.w, c2.bias, c3.w, c3.bias, buf[cur], buf[fr[3]], chain ? nx->w : nullptr,
-                                        chain ? nx->bias : nullptr, chain ? buf[fr[1]] : nullptr, s, et);
-                prof_end(h, s, rb);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "bneck_block2 launch (" + c2.conv_key + "): " + hipGetErrorString(e));
-                if (chain) pre_t1 = fr[1];
-                cur = fr[3];
-                li += 3;
-                continue;
-            }
-            if (have_t1) {
-                h1 = hh; w1 = ww;
-            } else {
-                rc = run_conv(h, c1, buf[cur], n, hh, ww, nullptr, buf[fr[0]], 1, s, &h1, &w1);
-                if (rc) return rc;
-            }
-            if (hit(p + ".t1", buf[fr[0]], h1, w1, c1.cout)) return R50_OK;
-            rc = run_conv(h, c2, buf[fr[0]], n, h1, w1, nullptr, buf[fr[1]], 1, s, &h2, &w2);
+    for (int i = 0; i < plan.n_blocks; ++i) {
+        const BlockPlan& bp = plan.blocks[i];
+        int fr[4], nf = 0;
+        if (pre_t1 >= 0) fr[nf++] = pre_t1;
+        for (int j = 0; j < 5; ++j)
+            if (j != cur && j != pre_t1) fr[nf++] = j;
+        pre_t1 = -1;
+        const ConvLayer &c1 = h->convs[bp.li], &c2 = h->convs[bp.li + 1], &c3 = h->convs[bp.li + 2];
+        const ConvLayer* nx = (bp.li_next < kNumConvs) ? &h->convs[bp.li_next] : nullptr;
+        const ConvLayer* cdp = (bp.b == 0) ? &h->convs[bp.li + 3] : nullptr;
+        int h1 = hh, w1 = ww, h2, w2, h3, w3;
+        const __bf16* idn = buf[cur];
+        if (bp.ds_side) {
+            if (!h->ds_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->ds_stream, hipStreamNonBlocking));
+            if (!h->ev_ds_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_ds_fork, hipEventDisableTiming));
+            if (!h->ev_ds_join) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_ds_join, hipEventDisableTiming));
+            const hipStream_t sd = h->ds_stream;
+            HIP_TRY(h, hipEventRecord(h->ev_ds_fork, s));          // block input complete
+            HIP_TRY(h, hipStreamWaitEvent(sd, h->ev_ds_fork, 0));
+            int hd, wd;
+            rc = run_conv(h, *cdp, buf[cur], n, hh, ww, nullptr, buf[fr[2]], 0, sd, &hd, &wd);
             if (rc) return rc;
-            if (hit(p + ".t2", buf[fr[1]], h2, w2, c2.cout)) return R50_OK;
-            if (b == 0 && !ds_side && !fuse_ds && !cat_ds) {
-                const ConvLayer& cd = h->convs[li + 3];
-                int hd, wd;
-                rc = run_conv(h, cd, buf[cur], n, hh, ww, nullptr, buf[fr[2]], 0, s, &hd, &wd);
-                if (rc) return rc;
-                if (hit(p + ".ds", buf[fr[2]], hd, wd, cd.cout)) return R50_OK;
-                idn = buf[fr[2]];
-            }
-            if (ds_side) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_ds_join, 0));   // conv3 needs the downsample output
-            // Plain-identity blocks write the block output IN PLACE over the block input: every element of the identity is read (by the
-            // lane / wave / workgroup that produces the output element at the same address) before that output element is stored, nobody
-            // else reads the block input any more (conv1 ran earlier), and a DRAM page that has just been read is written while it is
-            // still open -- a device add_ (read + write the same addresses) streams 9 % faster than a copy on this chip
-            // (profiles/r02_hbm_copy_probe.txt).
-            const bool inplace = h->inplace_out && !split && b > 0 && idn == buf[cur] && !cat_ds && !fuse_ds &&
-                                 !(h->precision == R50_PREC_FP8 && si == 0 && b == blocks - 1);      // (the fp8 hand-over writes 1-byte elements)
-            __bf16* const outb = inplace ? buf[cur] : buf[fr[3]];
-            if (fuse) {
-                const long long m = (long long)n * h2 * w2;
-                EvRec rt{};
-                prof_begin(h, s, rt, fuse3 ? PC_TAIL3 : PC_TAIL, 2.0 * m * ((double)c3.cout * c3.cin * (fuse_ds ? 2 : 1) + (double)nx->cout * nx->cin),
-                           2.0 * (m * ((double)c3.cin + (fuse_ds ? c3.cin : c3.cout) + c3.cout + nx->cout) +
-                                  (double)c3.cout * c3.cin * (fuse_ds ? 2 : 1) + (double)nx->cin * nx->cout),
-                           (int)(&c3 - &h->convs[0]));
-                if (fuse3)
-                    e = launch_bneck_tail3(buf[fr[1]], m, h->tail3_wp[b], c3.bias, idn, outb, nx->bias, buf[fr[0]], s, et);
-                else if (fuse2)
-                    e = launch_bneck_tail2(buf[fr[1]], m, c3.w, c3.bias, idn, outb, nx->w, nx->bias, buf[fr[0]], s, et);
-                else
-                    e = launch_bneck_tail(buf[fr[1]], m, c3.w, c3.bias, fuse_ds ? buf[cur] : idn, fuse_ds ? cdp->w : nullptr,
-                                          fuse_ds ? cdp->bias : nullptr, outb, nx->w, nx->cout, nx->bias, buf[fr[0]], s, et);
-                prof_end(h, s, rt);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "bneck_tail launch (" + c3.conv_key + "): " + hipGetErrorString(e));
-                h3 = h2; w3 = w2;
-                pre_t1 = fr[0];
-            } else if (cat_ds && h->fuse_cat_chain && h->catchain_wp && si == 1 && fuse_ok && !tap && h2 == 28 && w2 == 28 && hh == 56 && ww == 56 &&
-                       (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16) && c3.cin == 128 && c3.cout == 512 && cdp->cin == 256 &&
-                       cdp->stride == 2 && nx->cin == 512 && nx->cout == 128) {
-                // layer2.0: the two-source conv3 + downsample GEMM chained with layer2.1.conv1 through LDS (kernels.h: bneck_catchain_kernel);
-                // same bits as the two-source igemm launch followed by the 1x1 launch
-                const double m = (double)n * 784.0;
-                EvRec rt{};
-                prof_begin(h, s, rt, PC_CATCHAIN, 2.0 * m * (512.0 * 384 + 128.0 * 512), 2.0 * (m * (128.0 + 256 + 512 + 128) + 512.0 * 384 + 128.0 * 512),
-                           (int)(&c3 - &h->convs[0]));
-                e = launch_bneck_catchain(buf[fr[1]], buf[cur], n, 28, h->catchain_wp, h->cat_bias[1], outb, nx->bias, buf[fr[0]], s, et, cur_sub);
-                cur_sub = false;
-                prof_end(h, s, rt);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "bneck_catchain launch (" + c3.conv_key + "): " + hipGetErrorString(e));
-                h3 = h2; w3 = w2;
-                pre_t1 = fr[0];
-            } else if (cat_ds) {
-                rc = run_conv_cat(h, si, c3, *cdp, buf[fr[1]], buf[cur], n, h2, w2, hh, ww, outb, s);
-                if (rc) return rc;
-                h3 = h2; w3 = w2;
-            } else if (si == 2 && b == blocks - 1 && b < 8 && h->tail3_wp[b] && h->fuse_tail3 && h->fuse_tail3_last && h->fuse_tail && !split && !tap && h->tile_override == 0 &&
-                       (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16) && c3.ks == 1 && c3.cin == 256 && c3.cout == 1024 && idn == buf[cur]) {
-                // layer3.5: conv3 + identity + ReLU through the pipelined tail kernel without a second GEMM (its next conv1, layer4.0's 1024 -> 512, does
-                // not fit the chain): same bits as the igemm launch, whose K = 256 tiles alternate between an MFMA phase and an epilogue phase
-                const long long m = (long long)n * h2 * w2;
-                EvRec rt{};
-                prof_begin(h, s, rt, PC_TAIL3, 2.0 * m * (double)c3.cout * c3.cin, 2.0 * (m * ((double)c3.cin + 2.0 * c3.cout) + (double)c3.cout * c3.cin),
-                           (int)(&c3 - &h->convs[0]));
-                e = launch_bneck_tail3(buf[fr[1]], m, h->tail3_wp[b], c3.bias, idn, outb, nullptr, nullptr, s, et, 0, /*no_next=*/true);
-                prof_end(h, s, rt);
-                if (e != hipSuccess) return fail(h, R50_ERR_HIP, "bneck_tail3 (no next conv1) launch (" + c3.conv_key + "): " + hipGetErrorString(e));
-                h3 = h2; w3 = w2;
-            } else {
-                // fp8 mode, layer1's last conv: the hand-over to the fp8 stack (quantisation with the first activation scale) is folded into
-                // this conv's epilogue -- the 16-bit tensor is neither written nor read back (unless a tap asks for it)
-                const bool handover = (h->precision == R50_PREC_FP8 && h->fuse_fp8_handover && si == 0 && b == blocks - 1 && !tap &&
-                                       (int)h->fp8_scales.size() == R50_FP8_NUM_SCALES);
-                rc = run_conv(h, c3, buf[fr[1]], n, h2, w2, idn, outb, 1, s, &h3, &w3, handover ? 1.0f / h->fp8_scales[0] : 0.f,
-                              handover ? &layer1_out_fp8 : nullptr);
-                if (rc) return rc;
-            }
-            if (!inplace) cur = fr[3];
-            hh = h3; ww = w3;
-            if (hit(p, buf[cur], hh, ww, c3.cout)) return R50_OK;
-            li += (b == 0) ? 4 : 3;
+            HIP_TRY(h, hipEventRecord(h->ev_ds_join, sd));
+            idn = buf[fr[2]];
         }
+        if (bp.conv1 == Conv1::Launch) {
+            rc = run_conv(h, c1, buf[cur], n, hh, ww, nullptr, buf[fr[0]], 1, s, &h1, &w1);
+            if (rc) return rc;
+        }
+        // conv2 .. block output in ONE launch: t1 in buf[fr[0]], the block input as the identity, the output into buf[fr[3]], the next block's
+        // conv1 output (chain_next) into buf[fr[1]].  Same bits as the launches it replaces.
+        switch (bp.body) {
+            case Body::Conv2: break;
+            case Body::Block1Ds: {      // layer1.0: the downsample conv of the block input is the identity (bneck_block1_kernel<.., DS>)
+                const double m = (double)n * 3136.0;
+                rc = profiled(h, s, PC_BLOCK2, 2.0 * m * (64.0 * 576 + 2 * 256.0 * 64 + 64.0 * 256),
+                              2.0 * (m * (64.0 + 64 + 256 + 64) + 64.0 * 576 + 2 * 256.0 * 64 + 64.0 * 256), bp.li + 1, "bneck_block1 (downsample) launch", c2.conv_key, [&] {
+                                  return launch_bneck_block1(buf[fr[0]], n, c2.w, c2.bias, c3.w, c3.bias, buf[cur], buf[fr[3]], nx->w, 64, nx->bias, buf[fr[1]], s, et,
+                                                             cdp->w, cdp->bias);
+                              });
+                break;
+            }
+            case Body::Block1: {        // layer1.1 / .2 (bneck_block1_kernel).  sub_out: only the even rows and columns of the output are stored, all that
+                                        // its one reader, layer2.0's chained tail, looks at -- 103 MB instead of 411 MB at batch 256
+                const double m = (double)n * 3136.0;
+                rc = profiled(h, s, PC_BLOCK2, 2.0 * m * (64.0 * 576 + 256.0 * 64 + (double)nx->cout * 256),
+                              2.0 * (m * (64.0 + 256 + (bp.sub_out ? 64.0 : 256.0) + nx->cout) + 64.0 * 576 + 256.0 * 64 + (double)nx->cout * 256), bp.li + 1,
+                              "bneck_block1 launch", c2.conv_key, [&] {
+                                  return launch_bneck_block1(buf[fr[0]], n, c2.w, c2.bias, c3.w, c3.bias, buf[cur], buf[fr[3]], nx->w, nx->cout, nx->bias, buf[fr[1]], s,
+                                                             et, nullptr, nullptr, bp.sub_out);
+                              });
+                break;
+            }
+            case Body::Block2: {        // layer2.1-.3 (bneck_block2_kernel); .3 has no next conv1 that fits the chain
+                const bool chain = bp.chain_next;
+                const double m = (double)n * 784.0;
+                rc = profiled(h, s, PC_BLOCK2, 2.0 * m * (128.0 * 1152 + 512.0 * 128 + (chain ? 128.0 * 512 : 0.0)),
+                              2.0 * (m * (128.0 + 512 + 512 + (chain ? 128.0 : 0.0)) + 128.0 * 1152 + 512.0 * 128 + (chain ? 128.0 * 512 : 0.0)), bp.li + 1,
+                              "bneck_block2 launch", c2.conv_key, [&] {
+                                  return launch_bneck_block2(buf[fr[0]], n, c2.w, c2.bias, c3.w, c3.bias, buf[cur], buf[fr[3]], chain ? nx->w : nullptr,
+                                                             chain ? nx->bias : nullptr, chain ? buf[fr[1]] : nullptr, s, et);
+                              });
+                break;
+            }
+        }
+        if (bp.body != Body::Conv2) {
+            if (rc) return rc;
+            if (bp.chain_next) pre_t1 = fr[1];
+            cur = fr[3];
+            continue;
+        }
+        if (bp.tap == TapAt::T1) return report(buf[fr[0]], h1, w1, c1.cout);
+        rc = run_conv(h, c2, buf[fr[0]], n, h1, w1, nullptr, buf[fr[1]], 1, s, &h2, &w2);
+        if (rc) return rc;
+        if (bp.tap == TapAt::T2) return report(buf[fr[1]], h2, w2, c2.cout);
+        if (bp.ds_separate) {
+            int hd, wd;
+            rc = run_conv(h, *cdp, buf[cur], n, hh, ww, nullptr, buf[fr[2]], 0, s, &hd, &wd);
+            if (rc) return rc;
+            if (bp.tap == TapAt::Ds) return report(buf[fr[2]], hd, wd, cdp->cout);
+            idn = buf[fr[2]];
+        }
+        if (bp.ds_side) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_ds_join, 0));   // conv3 needs the downsample output
+        // inplace: a DRAM page that has just been read is written while it is still open -- a device add_ (read + write the same addresses)
+        // streams 9 % faster than a copy on this chip (profiles/r02_hbm_copy_probe.txt)
+        __bf16* const outb = bp.inplace ? buf[cur] : buf[fr[3]];
+        const long long m = (long long)n * h2 * w2;
+        const int layer = bp.li + 2;
+        h3 = h2; w3 = w2;
+        switch (bp.tail) {
+            case Tail::Tail1: case Tail::Tail2: case Tail::Tail3:       // conv3 + identity + ReLU and the next block's conv1 in one pass over the pixels; Tail1 with
+                                                                        // fuse_ds: the identity (downsample conv of the block input) is computed in the kernel as well
+                rc = profiled(h, s, bp.tail == Tail::Tail3 ? PC_TAIL3 : PC_TAIL, 2.0 * m * ((double)c3.cout * c3.cin * (bp.fuse_ds ? 2 : 1) + (double)nx->cout * nx->cin),
+                              2.0 * (m * ((double)c3.cin + (bp.fuse_ds ? c3.cin : c3.cout) + c3.cout + nx->cout) +
+                                     (double)c3.cout * c3.cin * (bp.fuse_ds ? 2 : 1) + (double)nx->cin * nx->cout),
+                              layer, "bneck_tail launch", c3.conv_key, [&] {
+                                  if (bp.tail == Tail::Tail3) return launch_bneck_tail3(buf[fr[1]], m, h->tail3_wp[bp.b], c3.bias, idn, outb, nx->bias, buf[fr[0]], s, et);
+                                  if (bp.tail == Tail::Tail2) return launch_bneck_tail2(buf[fr[1]], m, c3.w, c3.bias, idn, outb, nx->w, nx->bias, buf[fr[0]], s, et);
+                                  return launch_bneck_tail(buf[fr[1]], m, c3.w, c3.bias, bp.fuse_ds ? buf[cur] : idn, bp.fuse_ds ? cdp->w : nullptr,
+                                                           bp.fuse_ds ? cdp->bias : nullptr, outb, nx->w, nx->cout, nx->bias, buf[fr[0]], s, et);
+                              });
+                break;
+            case Tail::CatChain: {      // layer2.0: the two-source conv3 + downsample GEMM chained with layer2.1.conv1 through LDS (bneck_catchain_kernel);
+                                        // same bits as the two-source igemm launch followed by the 1x1 launch
+                const double md = (double)n * 784.0;
+                rc = profiled(h, s, PC_CATCHAIN, 2.0 * md * (512.0 * 384 + 128.0 * 512), 2.0 * (md * (128.0 + 256 + 512 + 128) + 512.0 * 384 + 128.0 * 512), layer,
+                              "bneck_catchain launch", c3.conv_key, [&] {
+                                  return launch_bneck_catchain(buf[fr[1]], buf[cur], n, 28, h->catchain_wp, h->cat_bias[1], outb, nx->bias, buf[fr[0]], s, et, bp.x_sub);
+                              });
+                break;
+            }
+            case Tail::Cat:             // the downsample tensor is never written or read back, and there is one launch instead of two
+                rc = run_conv_cat(h, bp.si, c3, *cdp, buf[fr[1]], buf[cur], n, h2, w2, hh, ww, outb, s);
+                break;
+            case Tail::Tail3NoNext:     // same bits as the igemm launch, whose K = 256 tiles alternate between an MFMA phase and an epilogue phase
+                rc = profiled(h, s, PC_TAIL3, 2.0 * m * (double)c3.cout * c3.cin, 2.0 * (m * ((double)c3.cin + 2.0 * c3.cout) + (double)c3.cout * c3.cin), layer,
+                              "bneck_tail3 (no next conv1) launch", c3.conv_key, [&] {
+                                  return launch_bneck_tail3(buf[fr[1]], m, h->tail3_wp[bp.b], c3.bias, idn, outb, nullptr, nullptr, s, et, 0, /*no_next=*/true);
+                              });
+                break;
+            case Tail::Conv3:           // handover: the 16-bit tensor is neither written nor read back, the fp8 stack's input comes out of this conv's epilogue
+                rc = run_conv(h, c3, buf[fr[1]], n, h2, w2, idn, outb, 1, s, &h3, &w3, bp.handover ? 1.0f / h->fp8_scales[0] : 0.f,
+                              bp.handover ? &layer1_out_fp8 : nullptr);
+                break;
+        }
+        if (rc) return rc;
+        if (bp.chain_next) pre_t1 = fr[0];
+        if (!bp.inplace) cur = fr[3];
+        hh = h3; ww = w3;
+        if (bp.tap == TapAt::Out) return report(buf[cur], hh, ww, c3.cout);
     }
-    if (tap) return fail(h, R50_ERR_INVALID, std::string("unknown layer name: ") + tap);
-    prof_begin(h, s, r, PC_AVGPOOL, 0, (double)n * (hh * ww * 2048.0 * 2 + 2048.0 * 4));
-    e = split ? launch_avgpool_split(buf[cur], out, n, hh * ww, 2048, s) : launch_avgpool(buf[cur], out, n, hh * ww, 2048, s, et);
-    prof_end(h, s, r);
-    if (e != hipSuccess) return fail(h, R50_ERR_HIP, std::string("avgpool: ") + hipGetErrorString(e));
-    return R50_OK;
+    switch (plan.stop) {
+        case Stop::Fp8TapRefused: return fail(h, R50_ERR_INVALID, "fp8 mode: activations beyond layer1 are e4m3 tensors, taps stop at layer1.2");
+        case Stop::Fp8Part: return run_fp8_part(h, buf, cur, n, out, s, layer1_out_fp8);
+        case Stop::UnknownTap: return fail(h, R50_ERR_INVALID, std::string("unknown layer name: ") + tap);
+        case Stop::Tap: return fail(h, R50_ERR_STATE, "internal: the planned tap was not reached");
+        case Stop::Avgpool: break;
+    }
+    return profiled(h, s, PC_AVGPOOL, 0, (double)n * (hh * ww * 2048.0 * 2 + 2048.0 * 4), -1, "avgpool", kNoKey, [&] {
+        return split ? launch_avgpool_split(buf[cur], out, n, hh * ww, 2048, s) : launch_avgpool(buf[cur], out, n, hh * ww, 2048, s, et);
+    });
 }
 
 void free_weights(r50_handle* h) {        // the buffers a sharer reads through its owner
@@ -1553,9 +1341,6 @@ void free_all(r50_handle* h, bool keep_weights = false) {
     h->ev_pending.clear(); h->ev_free.clear();
 }
 
-}  // namespace
-
-namespace {
 template <typename TIN>
 int forward_impl(r50_handle* h, const TIN* x, int n, float* out, void* stream) {
     if (!h) return fail(nullptr, R50_ERR_INVALID, "r50_forward: null handle");
@@ -1592,6 +1377,48 @@ int forward_impl(r50_handle* h, const TIN* x, int n, float* out, void* stream) {
         }
     }
     return R50_OK;
+}
+
+// Every option: where it lives (a field of the handle, or a process-wide knob shared with the r50_op_* hooks), the values r50_set_option
+// accepts and whether r50_get_option serves it.  "max_batch" and "workspace_bytes" are read-only and live in r50_get_option alone.
+enum OptionKind { OPT_BOOL, OPT_RANGE, OPT_ANY, OPT_STEM_STRIP };     // BOOL: stored as value ? 1 : 0; RANGE: lo <= value <= hi or range_error; ANY: stored as it comes
+struct Option {
+    const char* key;
+    int r50_handle::*field;
+    int* global;
+    OptionKind kind;
+    int64_t lo, hi;
+    const char* range_error;
+    bool gettable;
+};
+const Option kOptions[] = {
+    {"micro_batch", &r50_handle::micro_batch, nullptr, OPT_RANGE, 0, INT64_MAX, "micro_batch < 0", true},
+    {"profile", &r50_handle::profile, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"tile", &r50_handle::tile_override, nullptr, OPT_ANY, 0, 0, nullptr, true},
+    {"fused_stem", &r50_handle::fused_stem, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_tail", &r50_handle::fuse_tail, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_tail3", &r50_handle::fuse_tail3, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_cat_chain", &r50_handle::fuse_cat_chain, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"sub_out", &r50_handle::sub_out, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_tail3_last", &r50_handle::fuse_tail3_last, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"tail3_bp", nullptr, &g_tail3_bp, OPT_RANGE, 0, 112, "tail3_bp must be 0 .. 112", true},
+    {"fuse_fp8_handover", &r50_handle::fuse_fp8_handover, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_stem_c1", &r50_handle::fuse_stem_c1, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_ds_cat", &r50_handle::fuse_ds_cat, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"stem_strip", nullptr, &g_stem_strip, OPT_STEM_STRIP, 0, 28, "stem_strip must be 0 or a divisor of 28", true},
+    {"overlap_ds", &r50_handle::overlap_ds, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"streams", &r50_handle::n_streams, nullptr, OPT_RANGE, 1, 4, "streams must be in [1,4]", true},
+    {"inplace_out", &r50_handle::inplace_out, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_block2", &r50_handle::fuse_block2, nullptr, OPT_BOOL, 0, 1, nullptr, true},
+    {"fuse_block1", &r50_handle::fuse_block1, nullptr, OPT_RANGE, 0, 3, "fuse_block1 must be 0 .. 3", true},
+    {"use_g8", nullptr, &g_use_g8, OPT_RANGE, 0, 3, "use_g8 must be 0 .. 3", true},
+    {"use_s2", nullptr, &g_use_s2, OPT_ANY, 0, 0, nullptr, false},        // 0 = generic tiles for the stride-2 3x3 shapes
+    {"cu_cap", nullptr, &g_cu_cap, OPT_RANGE, 0, 4096, "cu_cap must be in [0,4096]", true},
+};
+const Option* find_option(const char* key) {
+    for (const Option& o : kOptions)
+        if (std::strcmp(o.key, key) == 0) return &o;
+    return nullptr;
 }
 
 }  // namespace
@@ -1681,7 +1508,7 @@ int r50_share_weights(r50_handle* h, r50_handle* from) {
     if (from->owner) from = from->owner;
     if (h->device != from->device || h->precision != from->precision)
         return fail(h, R50_ERR_INVALID, "r50_share_weights: device and precision of the two handles must be the same");
-    if (h->precision != R50_PREC_BF16 && h->precision != R50_PREC_FP16)
+    if (!is16(h->precision))
         return fail(h, R50_ERR_INVALID, "r50_share_weights: bf16 / fp16 handles only (the fp8 mode rewrites weight buffers per handle when its scales are set)");
     (void)hipSetDevice(h->device);
     if (h->stem_w) (void)hipFree(h->stem_w);                  // allocated by r50_create
@@ -1725,7 +1552,7 @@ int r50_load_weights(r50_handle* h, const r50_tensor_desc* tensors, int n_tensor
     std::vector<float> wf, bf;
     std::vector<uint16_t> pk;
     // [W3 | Wd] and b3 + bd of layer2.0 / layer3.0 / layer4.0 (16-bit precisions): convs are stored c1, c2, c3, ds per first block
-    const bool want_cat = (h->precision == R50_PREC_BF16 || h->precision == R50_PREC_FP16);
+    const bool want_cat = is16(h->precision);
     std::map<size_t, std::pair<std::vector<uint16_t>, std::vector<float>>> kept;       // conv index -> (packed weights, bias)
     for (size_t i = 0; i < h->convs.size(); ++i) {
         ConvLayer& L = h->convs[i];
@@ -1912,63 +1739,22 @@ int r50_forward_layer(r50_handle* h, const float* x, int n, const char* layer, v
 
 int r50_set_option(r50_handle* h, const char* key, int64_t value) {
     if (!h || !key) return fail(h, R50_ERR_INVALID, "r50_set_option: null argument");
-    const std::string k(key);
-    if (k == "micro_batch") { if (value < 0) return fail(h, R50_ERR_INVALID, "micro_batch < 0"); h->micro_batch = (int)value; }
-    else if (k == "profile") h->profile = value ? 1 : 0;
-    else if (k == "tile") h->tile_override = (int)value;
-    else if (k == "fused_stem") h->fused_stem = value ? 1 : 0;
-    else if (k == "fuse_tail") h->fuse_tail = value ? 1 : 0;
-    else if (k == "fuse_tail3") h->fuse_tail3 = value ? 1 : 0;
-    else if (k == "fuse_cat_chain") h->fuse_cat_chain = value ? 1 : 0;
-    else if (k == "sub_out") h->sub_out = value ? 1 : 0;
-    else if (k == "fuse_tail3_last") h->fuse_tail3_last = value ? 1 : 0;
-    else if (k == "tail3_bp") { if (value < 0 || value > 112) return fail(h, R50_ERR_INVALID, "tail3_bp must be 0 .. 112"); g_tail3_bp = (int)value; }
-    else if (k == "fuse_fp8_handover") h->fuse_fp8_handover = value ? 1 : 0;
-    else if (k == "fuse_stem_c1") h->fuse_stem_c1 = value ? 1 : 0;
-    else if (k == "fuse_ds_cat") h->fuse_ds_cat = value ? 1 : 0;
-    else if (k == "stem_strip") {          // process-wide (the launcher is shared by the handle and the r50_op_* hooks)
-        if (!(value == 0 || (value > 0 && 28 % value == 0))) return fail(h, R50_ERR_INVALID, "stem_strip must be 0 or a divisor of 28");
-        g_stem_strip = (int)value;
-    }
-    else if (k == "overlap_ds") h->overlap_ds = value ? 1 : 0;
-    else if (k == "streams") { if (value < 1 || value > 4) return fail(h, R50_ERR_INVALID, "streams must be in [1,4]"); h->n_streams = (int)value; }
-    else if (k == "inplace_out") h->inplace_out = value ? 1 : 0;
-    else if (k == "fuse_block2") h->fuse_block2 = value ? 1 : 0;
-    else if (k == "fuse_block1") { if (value < 0 || value > 3) return fail(h, R50_ERR_INVALID, "fuse_block1 must be 0 .. 3"); h->fuse_block1 = (int)value; }
-    else if (k == "use_g8") { if (value < 0 || value > 3) return fail(h, R50_ERR_INVALID, "use_g8 must be 0 .. 3"); g_use_g8 = (int)value; }   // process-wide A/B knob
-    else if (k == "use_s2") g_use_s2 = (int)value;                     // process-wide A/B knob: 0 = generic tiles for the stride-2 3x3 shapes
-    else if (k == "cu_cap") { if (value < 0 || value > 4096) return fail(h, R50_ERR_INVALID, "cu_cap must be in [0,4096]"); g_cu_cap = (int)value; g_num_cus = 0; }
-    else return fail(h, R50_ERR_INVALID, "r50_set_option: unknown key " + k);
+    const Option* o = find_option(key);
+    if (!o) return fail(h, R50_ERR_INVALID, std::string("r50_set_option: unknown key ") + key);
+    if (o->kind == OPT_RANGE && (value < o->lo || value > o->hi)) return fail(h, R50_ERR_INVALID, o->range_error);
+    if (o->kind == OPT_STEM_STRIP && !(value == 0 || (value > 0 && 28 % value == 0))) return fail(h, R50_ERR_INVALID, o->range_error);
+    (o->field ? h->*(o->field) : *o->global) = (o->kind == OPT_BOOL) ? (value ? 1 : 0) : (int)value;
+    if (o->global == &g_cu_cap) g_num_cus = 0;       // the budget is worked out again at the next launch
     return R50_OK;
 }
 
 int r50_get_option(r50_handle* h, const char* key, int64_t* value) {
     if (!h || !key || !value) return fail(h, R50_ERR_INVALID, "r50_get_option: null argument");
-    const std::string k(key);
-    if (k == "micro_batch") *value = h->micro_batch;
-    else if (k == "profile") *value = h->profile;
-    else if (k == "tile") *value = h->tile_override;
-    else if (k == "streams") *value = h->n_streams;
-    else if (k == "cu_cap") *value = g_cu_cap;
-    else if (k == "inplace_out") *value = h->inplace_out;
-    else if (k == "fuse_block2") *value = h->fuse_block2;
-    else if (k == "fuse_block1") *value = h->fuse_block1;
-    else if (k == "fused_stem") *value = h->fused_stem;
-    else if (k == "fuse_tail") *value = h->fuse_tail;
-    else if (k == "fuse_tail3") *value = h->fuse_tail3;
-    else if (k == "tail3_bp") *value = g_tail3_bp;
-    else if (k == "use_g8") *value = g_use_g8;
-    else if (k == "fuse_cat_chain") *value = h->fuse_cat_chain;
-    else if (k == "sub_out") *value = h->sub_out;
-    else if (k == "fuse_tail3_last") *value = h->fuse_tail3_last;
-    else if (k == "fuse_fp8_handover") *value = h->fuse_fp8_handover;
-    else if (k == "fuse_stem_c1") *value = h->fuse_stem_c1;
-    else if (k == "fuse_ds_cat") *value = h->fuse_ds_cat;
-    else if (k == "stem_strip") *value = g_stem_strip;
-    else if (k == "overlap_ds") *value = h->overlap_ds;
-    else if (k == "max_batch") *value = h->max_batch;
-    else if (k == "workspace_bytes") *value = (int64_t)(5 * h->buf_bytes + (size_t)h->max_batch * STEM_HP * STEM_WP * 8);
-    else return fail(h, R50_ERR_INVALID, "r50_get_option: unknown key " + k);
+    const Option* o = find_option(key);
+    if (o && o->gettable) *value = o->field ? h->*(o->field) : *o->global;
+    else if (std::strcmp(key, "max_batch") == 0) *value = h->max_batch;
+    else if (std::strcmp(key, "workspace_bytes") == 0) *value = (int64_t)(5 * h->buf_bytes + (size_t)h->max_batch * STEM_HP * STEM_WP * 8);
+    else return fail(h, R50_ERR_INVALID, std::string("r50_get_option: unknown key ") + key);
     return R50_OK;
 }
 
@@ -2042,6 +1828,11 @@ extern "C" __attribute__((visibility("default"))) void r50_debug_buffer(void* p)
 
 static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                         void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
+// what an r50_op_* hook returns for its launch: hipErrorInvalidValue is the launcher refusing the arguments
+static int op_status(hipError_t e, const char* op) {
+    if (e == hipSuccess) return R50_OK;
+    return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP, std::string(op) + ": " + hipGetErrorString(e));
+}
 
 int r50_op_conv2d(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                   void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
@@ -2077,9 +1868,7 @@ int r50_op_conv2d_w2(const void* x, int n, int h, int w, int cin, const void* w_
     if (tile == kTileC64 || tile == kTileXres || tile == kTileS2 || tile == kTileG8 || tile == kTileG8N7)
         return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_w2: tile id " + std::to_string(tile) + " does not read the weight pair");
     hipError_t e = launch_igemm(a, tile, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_conv2d_w2: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_conv2d_w2");
 }
 
 int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const void* w_trip, const float* bias, const void* res_pair,
@@ -2088,9 +1877,7 @@ int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const 
     int rc = fill_conv_args(a, x_pair, n, h, w, cin, w_trip, bias, res_pair, y_pair, cout, ksize, stride, pad, relu, true, false);
     if (rc) return fail(nullptr, rc, "r50_op_conv2d_split: invalid arguments");
     hipError_t e = launch_igemm(a, 0, (hipStream_t)stream, true);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_conv2d_split: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_conv2d_split");
 }
 
 int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias_scaled, const void* res, void* y,
@@ -2103,9 +1890,7 @@ int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* w
     a.y_bytes = (unsigned)((long long)a.M * cout);       // one byte per output element
     a.et = 2; a.oscale = oscale; a.rscale = rscale;
     hipError_t e = launch_igemm_fp8(a, tile, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_conv2d_fp8: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_conv2d_fp8");
 }
 
 int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* x2, int h2, int w2, int c2, int stride2, const void* wcat,
@@ -2115,9 +1900,7 @@ int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* 
     if (rc || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv1x1_cat: invalid arguments");
     a.et = et;
     hipError_t e = launch_igemm(a, cat_tile(a, tile), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_conv1x1_cat: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_conv1x1_cat");
 }
 
 int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const float* b3, const void* res, const void* wd,
@@ -2148,26 +1931,20 @@ int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const
         if (e == hipSuccess) e = ef;
     }
     else e = hipErrorInvalidValue;
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_bneck_tail: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_bneck_tail");
 }
 
 int r50_op_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, const float* b1, void* y1n, void* stream) {
     const hipError_t e = launch_bneck_block2(t1, n, w2, b2, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_bneck_block2: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_bneck_block2");
 }
 
 int r50_op_bneck_block1_ds(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* x, const void* wd,
                            const float* bd, void* out, const void* w1, const float* b1, void* y1n, void* stream) {
     if (!wd || !bd) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_block1_ds: null downsample weights");
     const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, x, out, w1, 64, b1, y1n, (hipStream_t)stream, 0, wd, bd);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_bneck_block1_ds: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_bneck_block1_ds");
 }
 
 int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const void* wcat, const float* bcat, void* out, const void* w1,
@@ -2181,17 +1958,13 @@ int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const v
     if (e == hipSuccess) e = launch_bneck_catchain(t2, x, n, ow, wp, bcat, out, b1, y1n, (hipStream_t)stream);
     const hipError_t ef = hipFreeAsync(wp, (hipStream_t)stream);
     if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_bneck_cat_chain: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_bneck_cat_chain");
 }
 
 int r50_op_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
     const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, res, out, w1, c1, b1, y1n, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP,
-                                     std::string("r50_op_bneck_block1: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op_status(e, "r50_op_bneck_block1");
 }
 
 // Weight precision of ATen's native uint8 bilinear resize (antialias off) along one axis: the largest p with
