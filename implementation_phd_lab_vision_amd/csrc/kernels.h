@@ -6721,3 +6721,321 @@ __global__ __launch_bounds__(256) void draw_skeletons_u8_kernel(const unsigned c
             if (i < 3 * npx) out[off + i] = (unsigned char)q[i];
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Forecast baselines: nearest-neighbour search over movie strips, and the three trivial predictors.
+//
+// nn_search_kernel: for each of nq <= NN_MAX_Q queries the k database rows with the smallest score s(q, x) = x_norm2[x] - 2 (q . x),
+// ascending by (s, index).  Database rows are the MFMA A operand, queries the B operand: an accumulator lane holds four consecutive
+// database rows of one query.  Persistent: workgroup g walks the chunks g, g + grid, ... of CH = 16 RB database rows (RB = 2 up to
+// d = 1024: 64 KB per chunk; RB = 1 above).  Wave 4 is the LOADER: it stages chunk i+1 into the other of two LDS buffers by LDS-DMA
+// (a row is d/8 16-byte pieces, piece c of row r at piece c ^ (r & mask) with mask = 7 when d/8 is a multiple of 8, else 3; the XOR is on
+// the source offset, the destination is lane-linear) while waves 0..3, the CONSUMERS, work on chunk i:
+//     loader:    issue(0) ; { s_waitcnt vmcnt(0) ; s_barrier ; issue(i+1) }           per chunk i
+//     consumers:            {                      s_barrier ; compute(i) }
+// so a buffer is read only after its loader's wait and a barrier the reader has passed, and restaged only after a barrier every reader
+// of it has reached.  The descriptor of a chunk covers its valid rows only: rows past n read as zeros and are masked out by index.
+// Consumer wave w owns the queries of the tiles w, w + 4, ... (64 queries each, four 16-query blocks): against the resident chunk it
+// runs K in ascending steps of 32 into ONE accumulator per (row block, query block) -- the score of a pair depends on the two rows'
+// values alone, not on the row's position, nq or the grid -- with the query fragments read from L2 through a ring of NN_PD steps.
+// The running top-k of a query is k (score, index) pairs in LDS that only its owner wave touches: a candidate is compared with the
+// list's last entry, and only on a hit (rare after the first chunks) inserted, the four lanes that share a query taking turns.  The
+// order on (score, index) is strict and total, so a list does not depend on the order of insertion, and the merged result does not
+// depend on how the rows were split over workgroups.  After the walk each workgroup writes its nq x k lists to the workspace;
+// nn_merge_kernel (one wave per query) merges the workgroups' lists and writes idx and dist2 = max(0, |q|^2 + s), |q|^2 summed in fp64.
+// No atomics anywhere.
+// ------------------------------------------------------------------------------------------------
+constexpr int NN_MAX_Q = 256;            // queries per launch (the launcher splits a larger nq)
+constexpr int NN_MAX_K = 8;
+constexpr int NN_QT = 4;                 // 16-query blocks per consumer pass
+constexpr int NN_PD = 4;                 // K steps of query fragments in flight
+constexpr int NN_THREADS = 320;          // 4 consumer waves + 1 loader wave
+constexpr int NN_IDX_NONE = 0x7fffffff;
+
+__device__ __forceinline__ bool nn_less(float sa, int ia, float sb, int ib) { return sa < sb || (sa == sb && ia < ib); }
+
+template <int ET>
+__device__ __forceinline__ void nn_square_add8(u32x4 v, double& acc) {    // eight 16-bit values, in element order
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const double lo = (double)unpack_lo_e<ET>(v[e]), hi = (double)unpack_hi_e<ET>(v[e]);
+        acc += lo * lo;
+        acc += hi * hi;
+    }
+}
+
+// |row|^2 of a 16-bit row of d values (d % 8 == 0) by one wave: lane l sums the pieces l, l + 64, ... in fp64, then a fixed xor tree.
+template <int ET>
+__device__ __forceinline__ double nn_row_norm2(const unsigned short* row, int d, int lane) {
+    double acc = 0.0;
+    for (int p = lane; p < d / 8; p += 64) nn_square_add8<ET>(*reinterpret_cast<const u32x4*>(row + (size_t)p * 8), acc);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    return acc;
+}
+
+template <int ET>
+__global__ __launch_bounds__(256) void row_norm2_kernel(const unsigned short* x, int n, int d, float* out) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const double v = nn_row_norm2<ET>(x + (size_t)row * d, d, lane);
+    if (lane == 0) out[row] = (float)v;
+}
+
+template <int ET, int RB>
+__global__ __launch_bounds__(NN_THREADS) void nn_search_kernel(const unsigned short* q, int nq, const unsigned short* x, int n, int d,
+                                                               const float* x_norm2, int k, float* ws_score, int* ws_idx) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int CH = 16 * RB;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cpr = d >> 3;                                   // 16-byte pieces per row
+    const int row_bytes = d * 2;
+    const int buf_bytes = CH * row_bytes;
+    const int swz = (cpr & 7) ? 3 : 7;
+    const int n_qtiles = (nq + 63) >> 6;
+    float* ls = reinterpret_cast<float*>(smem + 2 * buf_bytes);           // [n_qtiles*64][k]
+    int* li = reinterpret_cast<int*>(ls + n_qtiles * 64 * k);
+    const int grid = gridDim.x;
+    const int n_chunks = (n + CH - 1) / CH;
+    const int my = (n_chunks - (int)blockIdx.x + grid - 1) / grid;       // >= 1: grid <= n_chunks
+
+    if (wave == 4) {
+        // ---------------- loader ----------------
+        const int q64 = 64 / cpr, m64 = 64 % cpr;
+        const int n_dma = buf_bytes >> 10;                    // 1 KB per wave instruction; CH * d / 512 is whole
+        auto issue = [&](int i) {
+            const int row0 = ((int)blockIdx.x + i * grid) * CH;
+            const int rows = (n - row0 < CH) ? n - row0 : CH;
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<unsigned short*>(x + (size_t)row0 * d), 0, rows * row_bytes, 0x00020000);
+            char* dst = smem + (i & 1) * buf_bytes;
+            int r = lane / cpr, pc = lane % cpr;
+            for (int j = 0; j < n_dma; ++j) {
+                const unsigned voff = (unsigned)(r * row_bytes + ((pc ^ (r & swz)) << 4));
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_AS void*)(dst + (j << 10)), 16, voff, 0, 0, 0);
+                r += q64;
+                pc += m64;
+                if (pc >= cpr) { pc -= cpr; ++r; }
+            }
+        };
+        issue(0);
+        for (int i = 0; i < my; ++i) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (i + 1 < my) issue(i + 1);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return;
+    }
+
+    // ---------------- consumers ----------------
+    const int fr = lane & 15, fq = lane >> 4;
+    const int ns = d >> 5;                                    // K steps of 32
+    for (int t = wave; t < n_qtiles; t += 4)                  // own lists: every entry "nothing yet"
+        for (int e = lane; e < 64 * k; e += 64) {
+            ls[t * 64 * k + e] = __builtin_inff();
+            li[t * 64 * k + e] = NN_IDX_NONE;
+        }
+    const __amdgpu_buffer_rsrc_t rsrc_q =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(q), 0, nq * row_bytes, 0x00020000);
+
+    for (int i = 0; i < my; ++i) {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const char* buf = smem + (i & 1) * buf_bytes;
+        const int row0 = ((int)blockIdx.x + i * grid) * CH;
+        for (int t = wave; t < n_qtiles; t += 4) {
+            const int q0 = t * 64;
+            f32x4 acc[RB][NN_QT];
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                for (int qt = 0; qt < NN_QT; ++qt) acc[rb][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            // a query past nq has voffset >= the descriptor's size: it reads as zeros (the step's displacement is in soffset, unchecked,
+            // and only issued for steps < ns)
+            unsigned q_voff[NN_QT];
+#pragma unroll
+            for (int qt = 0; qt < NN_QT; ++qt) q_voff[qt] = (unsigned)((q0 + qt * 16 + fr) * row_bytes + fq * 16);
+            u32x4 bq[NN_PD][NN_QT];
+#pragma unroll
+            for (int u = 0; u < NN_PD; ++u)
+                if (u < ns)
+#pragma unroll
+                    for (int qt = 0; qt < NN_QT; ++qt) bq[u][qt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, q_voff[qt], u * 64, 0);
+            for (int s0 = 0; s0 < ns; s0 += NN_PD) {
+#pragma unroll
+                for (int u = 0; u < NN_PD; ++u) {
+                    const int s = s0 + u;
+                    if (s < ns) {
+                        bf16x8 af[RB];
+#pragma unroll
+                        for (int rb = 0; rb < RB; ++rb) {
+                            const int r = rb * 16 + fr;
+                            af[rb] = *reinterpret_cast<const bf16x8*>(buf + r * row_bytes + (((s * 4 + fq) ^ (r & swz)) << 4));
+                        }
+#pragma unroll
+                        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                            for (int qt = 0; qt < NN_QT; ++qt)
+                                acc[rb][qt] = mfma_e<ET>(af[rb], __builtin_bit_cast(bf16x8, bq[u][qt]), acc[rb][qt]);
+                        if (s + NN_PD < ns) {
+                            const int sofs = __builtin_amdgcn_readfirstlane((s + NN_PD) * 64);
+#pragma unroll
+                            for (int qt = 0; qt < NN_QT; ++qt) bq[u][qt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, q_voff[qt], sofs, 0);
+                        }
+                    }
+                }
+            }
+            // ---- selection: lane (fr, fq) holds rows row0 + rb*16 + fq*4 + e of query q0 + qt*16 + fr ----
+            float xn[RB][4];
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int row = row0 + rb * 16 + fq * 4 + e;
+                    xn[rb][e] = row < n ? x_norm2[row] : 0.f;
+                }
+#pragma unroll
+            for (int qt = 0; qt < NN_QT; ++qt) {
+                const int qi = q0 + qt * 16 + fr;
+                float* lsq = ls + qi * k;
+                int* liq = li + qi * k;
+                float sc[RB][4];
+                const float worst_s = lsq[k - 1];
+                const int worst_i = liq[k - 1];
+                unsigned hits = 0u;                           // bit rb*4 + e: that candidate beats the list's last entry
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int row = row0 + rb * 16 + fq * 4 + e;
+                        sc[rb][e] = xn[rb][e] - 2.0f * acc[rb][qt][e];
+                        if (row < n && qi < nq && nn_less(sc[rb][e], row, worst_s, worst_i)) hits |= 1u << (rb * 4 + e);
+                    }
+                if (__builtin_amdgcn_ballot_w64(hits != 0u) == 0ull) continue;
+                for (int f = 0; f < 4; ++f) {                 // the four lanes that share a query take turns
+                    const bool mine = fq == f && hits != 0u;
+                    if (__builtin_amdgcn_ballot_w64(mine) == 0ull) continue;
+                    if (mine) {
+                        float cur_s = lsq[k - 1];             // a lane before this one may have tightened the list: a candidate that
+                        int cur_i = liq[k - 1];               // missed the older, looser entry still misses
+#pragma unroll
+                        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const int row = row0 + rb * 16 + fq * 4 + e;
+                                const float s = sc[rb][e];
+                                if (((hits >> (rb * 4 + e)) & 1u) && nn_less(s, row, cur_s, cur_i)) {
+                                    int j = k - 1;
+                                    while (j > 0 && nn_less(s, row, lsq[j - 1], liq[j - 1])) {
+                                        lsq[j] = lsq[j - 1];
+                                        liq[j] = liq[j - 1];
+                                        --j;
+                                    }
+                                    lsq[j] = s;
+                                    liq[j] = row;
+                                    cur_s = lsq[k - 1];
+                                    cur_i = liq[k - 1];
+                                }
+                            }
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int t = wave; t < n_qtiles; t += 4)
+        for (int e = lane; e < 64 * k; e += 64) {
+            const int qi = t * 64 + e / k;
+            if (qi < nq) {
+                const size_t o = ((size_t)blockIdx.x * nq + qi) * k + e % k;
+                ws_score[o] = ls[t * 64 * k + e];
+                ws_idx[o] = li[t * 64 * k + e];
+            }
+        }
+#else
+    (void)q; (void)nq; (void)x; (void)n; (void)d; (void)x_norm2; (void)k; (void)ws_score; (void)ws_idx;
+#endif
+}
+
+// One wave per query: lane l keeps the best k of the lists of workgroups l, l + 64, ... (sorted registers), then k rounds pick the
+// smallest head among the lanes.  Indices are unique across workgroups (a row belongs to one chunk), so every round has one winner;
+// only "nothing yet" entries can tie, and k <= n keeps them out of the output.
+template <int ET>
+__global__ __launch_bounds__(64) void nn_merge_kernel(const float* ws_score, const int* ws_idx, int n_wg, int nq, int k,
+                                                      const unsigned short* q, int d, int* idx_out, float* dist2_out) {
+    const int lane = threadIdx.x;
+    const int qi = blockIdx.x;
+    float s[NN_MAX_K];
+    int ix[NN_MAX_K];
+#pragma unroll
+    for (int j = 0; j < NN_MAX_K; ++j) { s[j] = __builtin_inff(); ix[j] = NN_IDX_NONE; }
+    for (int g = lane; g < n_wg; g += 64) {
+        const size_t o = ((size_t)g * nq + qi) * k;
+        for (int e = 0; e < k; ++e) {
+            float cs = ws_score[o + e];
+            int ci = ws_idx[o + e];
+#pragma unroll
+            for (int j = 0; j < NN_MAX_K; ++j)
+                if (nn_less(cs, ci, s[j], ix[j])) {
+                    const float ts = s[j]; const int ti = ix[j];
+                    s[j] = cs; ix[j] = ci; cs = ts; ci = ti;
+                }
+        }
+    }
+    const float qn = (float)nn_row_norm2<ET>(q + (size_t)qi * d, d, lane);
+    for (int r = 0; r < k; ++r) {
+        float bs = s[0];
+        int bi = ix[0];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float os = __shfl_xor(bs, m, 64);
+            const int oi = __shfl_xor(bi, m, 64);
+            if (nn_less(os, oi, bs, bi)) { bs = os; bi = oi; }
+        }
+        if (ix[0] == bi && s[0] == bs) {                      // the winner pops its head
+#pragma unroll
+            for (int j = 0; j + 1 < NN_MAX_K; ++j) { s[j] = s[j + 1]; ix[j] = ix[j + 1]; }
+            s[NN_MAX_K - 1] = __builtin_inff();
+            ix[NN_MAX_K - 1] = NN_IDX_NONE;
+        }
+        if (lane == 0) {
+            idx_out[(size_t)qi * k + r] = bi;
+            dist2_out[(size_t)qi * k + r] = fmaxf(0.f, qn + bs);
+        }
+    }
+}
+
+// The three trivial forecasts, gather form: one thread per output coordinate (b, h, j, c).  a1, a0 (b, joints, 3): the poses at the last
+// and second-to-last observed frame; nn_row (b, k) int32 rows of dbj (n_db, t_db, joints, 3), TRUSTED to lie in [0, n_db).
+__global__ __launch_bounds__(256) void baseline_forecasts_kernel(const float* a1, const float* a0, const int* nn_row, const float* dbj, int b,
+                                                                 int k, int t_db, int joints, int root, int input_len, int pred_len,
+                                                                 float* const_pose, float* const_vel, float* nn) {
+    const long long total = (long long)b * pred_len * joints * 3;
+    const int pose = joints * 3;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long long)gridDim.x * 256) {
+        const int jc = (int)(o % pose);
+        const int h = (int)((o / pose) % pred_len);
+        const int bi = (int)(o / ((long long)pose * pred_len));
+        const int c = jc % 3;
+        const float v1 = a1[(size_t)bi * pose + jc];
+        if (const_pose) const_pose[o] = v1;
+        if (const_vel) const_vel[o] = fmaf((float)(h + 1), v1 - a0[(size_t)bi * pose + jc], v1);
+        if (nn) {
+            float sum = 0.f;
+            for (int i = 0; i < k; ++i) {
+                const float* clip = dbj + (size_t)nn_row[bi * k + i] * t_db * pose;
+                const float term = clip[(size_t)(input_len + h) * pose + jc] - clip[(size_t)(input_len - 1) * pose + root * 3 + c];
+                sum = i == 0 ? term : sum + term;
+            }
+            nn[o] = a1[(size_t)bi * pose + root * 3 + c] + __fdiv_rn(sum, (float)k);
+        }
+    }
+}

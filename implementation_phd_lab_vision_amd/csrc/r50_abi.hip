@@ -2592,4 +2592,81 @@ int r50_op_avgpool(const void* x, int n, int hw, int c, float* y, void* stream) 
     return R50_OK;
 }
 
+// ---- forecast baselines (kernels.h: row_norm2_kernel, nn_search_kernel, nn_merge_kernel, baseline_forecasts_kernel) ----
+constexpr int kNnMaxWgs = 512;           // workgroups whose lists the workspace holds (the grid is the CU budget, at most this)
+static int nn_chunk_rows(int d) { return d <= 1024 ? 32 : 16; }
+
+size_t r50_op_nn_search_workspace(int nq, int n, int k) {
+    if (nq < 1 || n < 1 || k < 1 || k > NN_MAX_K) return 0;
+    const long long chunks = ((long long)n + 15) / 16;                   // the smallest chunk any d uses
+    const long long wgs = std::min<long long>(chunks, kNnMaxWgs);
+    return (size_t)wgs * (size_t)std::min(nq, NN_MAX_Q) * (size_t)k * 8;
+}
+
+int r50_op_row_norm2(const void* x, int n, int d, int et, float* out, void* stream) {
+    if (!x || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: null pointer");
+    if (n < 1 || d < 8 || d % 8 != 0 || (et != 0 && et != 1) || ((uintptr_t)x & 15u))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: invalid arguments (need n >= 1, d a positive multiple of 8, x 16-byte aligned)");
+    R50_ET_LAUNCH(row_norm2_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), stream, (const unsigned short*)x, n, d, out);
+    return ew_done("r50_op_row_norm2");
+}
+
+int r50_op_nn_search(const void* q, int nq, const void* x, int n, int d, int et, const float* x_norm2, int k, int* idx_out, float* dist2_out,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    const char* me = "r50_op_nn_search: ";
+    if (!q || !x || !x_norm2 || !idx_out || !dist2_out || !workspace) return fail(nullptr, R50_ERR_INVALID, std::string(me) + "null pointer");
+    if (nq < 1 || n < 1 || n > (1 << 30) || k < 1 || k > NN_MAX_K || k > n || d < 32 || d > 2048 || d % 32 != 0 || (et != 0 && et != 1))
+        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (need nq >= 1, 1 <= k <= 8, k <= n <= 2^30, d % 32 == 0 and "
+                                                                "32 <= d <= 2048)");
+    if (((uintptr_t)q | (uintptr_t)x) & 15u) return fail(nullptr, R50_ERR_INVALID, std::string(me) + "q and x must be 16-byte aligned");
+    if (workspace_bytes < r50_op_nn_search_workspace(nq, n, k))
+        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "the workspace is smaller than r50_op_nn_search_workspace asks for");
+    const int cus = num_cus();
+    if (cus == 0) return fail(nullptr, R50_ERR_HIP, std::string(me) + "the device could not be queried");
+    const int ch = nn_chunk_rows(d);
+    const int n_chunks = (n + ch - 1) / ch;
+    const int grid = std::min(std::min(n_chunks, cus), kNnMaxWgs);
+    hipStream_t s = (hipStream_t)stream;
+    float* ws_score = (float*)workspace;
+    for (int q0 = 0; q0 < nq; q0 += NN_MAX_Q) {                          // one walk of the database per 256 queries
+        const int nql = std::min(nq - q0, NN_MAX_Q);
+        int* ws_idx = (int*)(ws_score + (size_t)grid * nql * k);
+        const size_t lds = (size_t)2 * ch * d * 2 + (size_t)((nql + 63) / 64 * 64) * k * 8;
+        const unsigned short* ql = (const unsigned short*)q + (size_t)q0 * d;
+#define R50_NN_LAUNCH(ET, RB)                                                                                                       \
+        do {                                                                                                                        \
+            auto kern = nn_search_kernel<ET, RB>;                                                                                   \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(e));                          \
+            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NN_THREADS), lds, s, ql, nql, (const unsigned short*)x, n, d, x_norm2, k, \
+                               ws_score, ws_idx);                                                                                   \
+        } while (0)
+        if (et) { if (ch == 32) R50_NN_LAUNCH(1, 2); else R50_NN_LAUNCH(1, 1); }
+        else { if (ch == 32) R50_NN_LAUNCH(0, 2); else R50_NN_LAUNCH(0, 1); }
+#undef R50_NN_LAUNCH
+        R50_ET_LAUNCH(nn_merge_kernel, dim3((unsigned)nql), dim3(64), stream, (const float*)ws_score, (const int*)ws_idx, grid, nql, k, ql, d,
+                      idx_out + (size_t)q0 * k, dist2_out + (size_t)q0 * k);
+    }
+    return ew_done("r50_op_nn_search");
+}
+
+int r50_op_baseline_forecasts(const float* a1, const float* a0, const int* nn_row, const float* dbj, int64_t n_db, int b, int k, int t_db,
+                              int joints, int root, int input_len, int pred_len, float* const_pose, float* const_vel, float* nn,
+                              void* stream) {
+    const char* me = "r50_op_baseline_forecasts: ";
+    if (!a1 || (const_vel && !a0) || (nn && (!nn_row || !dbj)) || (!const_pose && !const_vel && !nn))
+        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "null pointer (a1 always; a0 with const_vel; nn_row and dbj with nn; at least one "
+                                                                "output)");
+    if (b < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || pred_len < 1 || input_len < 1 ||
+        (int64_t)b * pred_len * joints > INT32_MAX / 3)
+        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (need b, pred_len, input_len >= 1, 1 <= joints <= 64, "
+                                                                "0 <= root < joints)");
+    if (nn && (k < 1 || k > NN_MAX_K || n_db < 1 || t_db < 1 || (int64_t)input_len + pred_len > t_db || (int64_t)b * k > INT32_MAX))
+        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (with nn: 1 <= k <= 8, n_db >= 1 and input_len + pred_len "
+                                                                "<= t_db)");
+    hipLaunchKernelGGL(baseline_forecasts_kernel, dim3(ew_grid((long long)b * pred_len * joints * 3)), dim3(256), 0, (hipStream_t)stream, a1,
+                       a0, nn_row, dbj, b, k, t_db, joints, root, input_len, pred_len, const_pose, const_vel, nn);
+    return ew_done("r50_op_baseline_forecasts");
+}
+
 }  // extern "C"

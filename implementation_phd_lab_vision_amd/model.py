@@ -343,6 +343,32 @@ class PHDFor3DJoints:
             return self._regressor(phi, b, t)
 
     @torch.no_grad()
+    def observe(self, feats: torch.Tensor, input_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """What the head knows after ``input_len`` observed frames: ``input_proj`` + ``f_movie`` + ``f_3D`` over
+        ``feats[:, :input_len]`` ONLY -- GroupNorm's statistics span time, so a slice of a full-length pass is not the same thing.  The
+        launches are those ``rollout`` makes for the observed part and those of ``joints(feats[:, :input_len])``.  Returns (phi
+        (B, I, D) 16-bit: the strips ``rollout`` puts in front of its sequence buffer; joints (B, I, J, 3) fp32, bit-equal to
+        ``joints(feats[:, :input_len])``)."""
+        if self._device is None or not self._dev:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') before running the head")
+        if feats.dim() != 3 or feats.shape[-1] != 2048:
+            raise ValueError(f"expected (B,T,2048) features, got {tuple(feats.shape)}")
+        if feats.device != self._device:
+            raise ValueError(f"features are on {feats.device}, head on {self._device}")
+        b, t, _ = feats.shape
+        i_len = int(input_len)
+        if b < 1 or not 1 <= i_len <= t:
+            raise ValueError(f"observe needs B >= 1 and 1 <= input_len <= T (got B={b}, input_len={i_len}, T={t})")
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            f = feats[:, :i_len].to(torch.float32).contiguous()
+            x0 = torch.empty((b * i_len, 2048), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * i_len, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None,
+                       "r50_op_cast_rows")
+            phi = self._temporal_net(self._gemm(x0, "input_proj", relu=False), b, i_len, "f_movie", self.number_blocks)
+            return phi.view(b, i_len, self.latent_dim), self._regressor(phi, b, i_len)
+
+    @torch.no_grad()
     def rollout(self, feats: torch.Tensor, input_len: int = 15, pred_len: int = 25) -> Tuple[torch.Tensor, torch.Tensor]:
         """Autoregressive forecast: f_movie over the first ``input_len`` frames only, then ``pred_len``
         times the next strip ``f_AR(seq)[:, -1]`` appended to ``seq``, then f_3D on the appended strips.  Returns (future_phi

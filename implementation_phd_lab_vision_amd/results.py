@@ -24,7 +24,11 @@ contributors for all frames, the action mean and each action, and the clip-wise 
 ``dense_*`` keys and ``--dense-out FILE.npz`` receives the stitched sequences themselves.  With ``--dtw`` (default off; needs
 ``--pred-len``) the forecasts are also scored after dynamic time warping (``dtw.evaluate_dtw``,
 ``--dtw-band N``): the ``DTW metrics`` lines print the warped P1 / P2 beside the unwarped ones for all clips and each action, and the
-warped error and the lag in frames per horizon; the ``.npz`` gains the ``dtw_*`` keys.
+warped error and the lag in frames per horizon; the ``.npz`` gains the ``dtw_*`` keys.  With ``--baselines`` (default off; needs
+``--pred-len``) trivial forecasts are scored on the same clips (``baselines.evaluate_baselines``): the last
+pose held, the last step continued, and the future of the nearest training clip in movie-strip space (``--nn-subjects``, ``--nn-k``);
+the ``Baselines`` lines print each predictor's MPJPE / P1 / P2 per horizon beside the model's and the model's skill against it; the
+``.npz`` gains the ``baseline_*`` and ``nn_*`` keys.
 
 Two differences from running the reference's script as it stands:
 
@@ -57,6 +61,7 @@ from . import _lib
 SEQ_LEN = 40                              # src/config.py
 INPUT_LEN = 15                            # src/config.py: the rollout's observed frames (--input-len)
 TEST_SUBJECTS = [9]                       # hard-coded at src/results.py:159
+BASELINE_NAMES = ("const_pose", "const_vel", "nn")   # baselines.BASELINES (--baselines)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -116,6 +121,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "warped error and the lag in frames per horizon (needs --pred-len; INTEGRATION.md section T)")
     p.add_argument("--dtw-band", type=int, default=-1, metavar="N",
                    help="only warp within |i - j| <= N frames (--dtw); negative = no band (default)")
+    p.add_argument("--baselines", nargs="*", choices=BASELINE_NAMES, default=argparse.SUPPRESS, metavar="NAME",
+                   help="also score trivial forecasts on the same clips (needs --pred-len; INTEGRATION.md section U): const_pose, const_vel "
+                        "and nn (the future of the nearest training clip in movie-strip space); a bare flag means all three")
+    p.add_argument("--baseline-anchor", choices=("pred", "gt"), default=argparse.SUPPRESS,
+                   help="the pose the baselines start from (--baselines): the head's own reconstruction of the last observed frames "
+                        "(pred, default) or the ground truth (gt)")
+    p.add_argument("--nn-k", type=int, default=argparse.SUPPRESS, metavar="K", help="neighbours averaged by the nn baseline, 1..8 (default 1)")
+    p.add_argument("--nn-subjects", type=int, nargs="+", default=argparse.SUPPRESS,
+                   help="subjects whose clips the nn baseline searches (default: train.TRAIN_SUBJECTS); must not overlap --test-subjects")
+    p.add_argument("--nn-features-root", type=str, default=argparse.SUPPRESS, metavar="DIR",
+                   help="feature cache of the nn baseline's database (default: --features_root)")
+    p.add_argument("--nn-max-clips", type=int, default=argparse.SUPPRESS, metavar="N", help="use only the first N database clips (nn baseline)")
     return p
 
 
@@ -149,7 +166,33 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
         p.error(f"--dtw warps at most 64 predicted frames, got --pred-len {args.pred_len}")
+    if hasattr(args, "baselines"):
+        if args.pred_len <= 0:
+            p.error("--baselines needs --pred-len > 0: it scores forecasts")
+        which = baseline_options(args)[0]
+        if "const_vel" in which and args.input_len < 2:
+            p.error("--baselines const_vel needs --input-len >= 2: it continues the last observed step")
+        if not 1 <= getattr(args, "nn_k", 1) <= 8:
+            p.error(f"--nn-k must lie in [1, 8], got {args.nn_k}")
+        if getattr(args, "nn_max_clips", 1) < 1:
+            p.error(f"--nn-max-clips must be >= 1, got {args.nn_max_clips}")
+        if "nn" in which:
+            from .train import TRAIN_SUBJECTS
+            both = sorted(set(getattr(args, "nn_subjects", TRAIN_SUBJECTS)) & set(args.test_subjects))
+            if both:
+                p.error(f"--nn-subjects overlaps --test-subjects in {both}: a query would retrieve itself")
+    else:
+        for flag in ("baseline_anchor", "nn_k", "nn_subjects", "nn_features_root", "nn_max_clips"):
+            if hasattr(args, flag):
+                p.error(f"--{flag.replace('_', '-')} needs --baselines")
     return args
+
+
+def baseline_options(args: argparse.Namespace) -> Tuple[Tuple[str, ...], str, int]:
+    """(which, anchor, nn_k) of parsed arguments that carry ``--baselines``: a bare flag means all three, in BASELINE_NAMES order and
+    without repeats."""
+    given = set(args.baselines) if args.baselines else set(BASELINE_NAMES)
+    return tuple(n for n in BASELINE_NAMES if n in given), getattr(args, "baseline_anchor", "pred"), int(getattr(args, "nn_k", 1))
 
 
 # ---- host pieces ------------------------------------------------------------------------------------------------------------
@@ -464,6 +507,42 @@ def dtw_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     return out
 
 
+def baseline_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--baselines`` from an ``evaluate_baselines`` result: the ``Baselines`` header, then one indented line per
+    predictor, ``model`` first: MPJPE, P1 and P2 in mm at horizons 1, 5, 10 and P and their mean over the horizons, and for each
+    baseline the model's skill ``1 - model / baseline`` on the P1 mean (positive: the model beats it)."""
+    hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+    head = (f"Baselines | input {input_len} | pred {pred_len} | clips {int(np.sum(res['clips']))} | anchor {res['anchor']} | predictors "
+            f"{len(res['names'])}")
+    if "nn" in res["names"]:
+        head += f" | nn k {int(res['nn_k'])} | nn strip dist2 mean {res['nn_dist2_mean']:.6g}"
+    lines = [head]
+    model_p1 = float(np.mean(res["model"]["p1"]))
+    for name in res["names"]:
+        row = res[name]
+        parts = [f"{key} (mm) " + " | ".join(f"@{h}: {row[key][h - 1] * 1000.0:.2f}" for h in hs) + f" | mean: {np.mean(row[key]) * 1000.0:.2f}"
+                 for key in ("mpjpe", "p1", "p2")]
+        line = f"  {name} | " + " | ".join(parts)
+        if name != "model":
+            base_p1 = float(np.mean(row["p1"]))
+            line += f" | model skill on p1: {(1.0 - model_p1 / base_p1) if base_p1 > 0 else float('nan'):+.4f}"
+        lines.append(line)
+    return lines
+
+
+def baseline_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--baselines``: ``baseline_names`` (Nb,) str, ``model`` first; fp32 ``baseline_mpjpe``, ``baseline_p1``,
+    ``baseline_p2`` (Nb, P) in metres; ``baseline_actions`` (G,) str; ``baseline_per_action`` (Nb, G, P, 2) fp32 [p1, p2];
+    ``baseline_anchor`` str.  (``main`` adds ``nn_index``, ``nn_dist2`` and ``nn_future3djoints`` of the dumped clips.)"""
+    names = list(res["names"])
+    out = {"baseline_names": np.array(names, dtype=str), "baseline_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "baseline_anchor": np.array(str(res["anchor"])),
+           "baseline_per_action": np.stack([np.asarray(res[n]["per_action"], dtype=np.float32) for n in names])}
+    for key in ("mpjpe", "p1", "p2"):
+        out["baseline_" + key] = np.stack([np.asarray(res[n][key], dtype=np.float32) for n in names])
+    return out
+
+
 def dense_export(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     """The arrays of ``--dense-out``: ``seq_keys`` (S, 3) str [subject, action, cam], ``seq_start`` (S+1,), ``frame_idx`` (F,) int32
     (sub-sampled frame units), ``pred`` and ``gt`` (F, J, 3) fp32 in metres, ``spread`` (F,) fp32, ``count`` (F,) int32 = the clips
@@ -546,6 +625,31 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in dtw_lines(dtw, args.input_len, args.pred_len):
             print(line)
 
+    base, base_db = None, None
+    if hasattr(args, "baselines"):           # the protocols' pass again: the trivial forecasts beside the model's, every test clip once
+        from .baselines import StripDatabase, evaluate_baselines
+        from .protocols import action_groups
+        which, anchor, nn_k = baseline_options(args)
+        if "nn" in which:
+            from .train import TRAIN_SUBJECTS
+            nn_subjects = list(getattr(args, "nn_subjects", TRAIN_SUBJECTS))
+            both = sorted(set(nn_subjects) & set(args.test_subjects))
+            if both:
+                raise SystemExit(f"results: the nn baseline's subjects overlap --test-subjects in {both}: a query would retrieve itself")
+            train_set = DeviceFeatureStore(getattr(args, "nn_features_root", args.features_root), subjects=nn_subjects,
+                                           max_clips=getattr(args, "nn_max_clips", None), device=device)
+            if int(train_set.feats.shape[1]) < args.input_len + args.pred_len:
+                raise SystemExit(f"results: the nn baseline's clips have {int(train_set.feats.shape[1])} frames, fewer than --input-len + "
+                                 f"--pred-len = {args.input_len + args.pred_len}")
+            if len(train_set) < nn_k:
+                raise SystemExit(f"results: the nn baseline's database has {len(train_set)} clips, fewer than --nn-k {nn_k}")
+            base_db = StripDatabase.build(head, train_set, args.input_len)
+            print(f"Baselines | nn database: {len(base_db)} clips of subjects {nn_subjects}")
+        names, ids = action_groups(test_set.item_actions())
+        base = evaluate_baselines(head, test_set, base_db, ids, names, args.input_len, args.pred_len, which, nn_k=nn_k, anchor=anchor)
+        for line in baseline_lines(base, args.input_len, args.pred_len):
+            print(line)
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -581,6 +685,14 @@ def main(argv: Optional[List[str]] = None) -> str:
             print(f"Dense | stitched sequences saved to: {args.dense_out}")
     if dtw is not None:
         extra.update(dtw_arrays(dtw))
+    if base is not None:
+        extra.update(baseline_arrays(base))
+        if base_db is not None:              # the dumped clips' retrieval: which training clips, how far, and the future they give
+            from .baselines import forecast_batch
+            fb = forecast_batch(head, base_db, feats[:n_save], joints3d[:n_save].to(torch.float32).contiguous(), args.input_len,
+                                args.pred_len, ("nn",), baseline_options(args)[2], baseline_options(args)[1])
+            extra.update(nn_index=fb["nn_index"].cpu().numpy(), nn_dist2=fb["nn_dist2"].cpu().numpy(),
+                         nn_future3djoints=fb["nn"].cpu().numpy())
     if n_render:                             # the person crops, drawn over; a clip without a usable box gets the plain background
         from . import render
         plain = torch.tensor(render._rgb_tuple(render.PANEL_BG_RGB), dtype=torch.uint8, device=device)

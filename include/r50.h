@@ -22,6 +22,7 @@
 #ifndef R50_H_
 #define R50_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -597,6 +598,39 @@ int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, i
 int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt2d, const float* K, int b, int t, int s0, int joints,
                               const int* edges_host, int n_edges, float lambda_2d, float lambda_vel, float lambda_bone, float eps,
                               float term_scale, float loss_scale, float* dy, double* part, float* out8, void* stream);
+
+/* Forecast baselines: the nearest-neighbour search over 16-bit rows and the three trivial predictors.
+ *  r50_op_row_norm2: x (n, d) 16-bit rows (et 0 = bf16, 1 = fp16) -> out (n) fp32 = |x_i|^2, summed in fp64 in a fixed order (one wave
+ *    per row) and rounded once.  Needs n >= 1, d a positive multiple of 8, x 16-byte aligned, no null pointer.
+ *  r50_op_nn_search: for each of the nq rows of q (nq, d) the k rows of x (n, d) with the smallest score
+ *        s(q, x) = x_norm2[x] - 2 (q . x),
+ *    the dot product on v_mfma_f32_16x16x32_{f16,bf16} with fp32 accumulation, K in ascending steps of 32 into one accumulator: the
+ *    score of a pair depends on the two rows' values (and x_norm2[x]) alone, not on the row's position in x, on nq or on the grid.  The
+ *    order is ascending by (s, index), the smaller index first at equal s: strict and total.  idx_out (nq, k) int32 and dist2_out
+ *    (nq, k) fp32 = max(0, |q|^2 + s), |q|^2 as r50_op_row_norm2 computes it, are WRITTEN.  Needs nq >= 1, 1 <= k <= 8, k <= n <= 2^30,
+ *    d % 32 == 0, 32 <= d <= 2048, q and x 16-byte aligned, no null pointer, workspace_bytes >= r50_op_nn_search_workspace of the same
+ *    nq, n, k; all checked before any launch (a refused call touches nothing).  Inputs are taken to be finite.  Per 256 queries two
+ *    launches on stream: a persistent kernel sized by the CU budget (the "cu_cap" option) whose workgroups walk database chunks of 32
+ *    rows (16 above d = 1024) staged once into LDS by LDS-DMA and keep a running top-k per query, then one wave per query merging the
+ *    workgroups' lists.  No distance matrix is stored.  No atomics; the order being total, the result is the same bits on every run and
+ *    under every CU budget.
+ *  r50_op_nn_search_workspace: the bytes of device scratch the search needs (0 for arguments the search would refuse).
+ *  r50_op_baseline_forecasts: a1, a0 (b, joints, 3) fp32 = the poses at the last and second-to-last observed frame; nn_row (b, k) int32
+ *    device values, rows of dbj (n_db, t_db, joints, 3) fp32.  Any of three (b, pred_len, joints, 3) fp32 outputs is WRITTEN, NULL = not
+ *    wanted, for h = 0 .. pred_len-1:
+ *        const_pose[b,h] = a1[b]
+ *        const_vel[b,h]  = fma(h + 1, a1[b] - a0[b], a1[b])                                    (one subtraction, one fma per coordinate)
+ *        nn[b,h]         = a1[b,root] + (sum_i (dbj[nn_row[b,i], input_len + h] - dbj[nn_row[b,i], input_len - 1, root])) / k
+ *    the sum over i = 0 .. k-1 left to right in fp32, one correctly rounded division.  Needs b, pred_len, input_len >= 1, 1 <= joints
+ *    <= 64, 0 <= root < joints, a1 and at least one output; a0 with const_vel; with nn: nn_row, dbj, 1 <= k <= 8, n_db >= 1 and
+ *    input_len + pred_len <= t_db; checked before any launch.  The kernel TRUSTS nn_row: the caller guarantees every value lies in
+ *    [0, n_db).  One launch, gather form, no atomics. */
+int r50_op_row_norm2(const void* x, int n, int d, int et, float* out, void* stream);
+size_t r50_op_nn_search_workspace(int nq, int n, int k);
+int r50_op_nn_search(const void* q, int nq, const void* x, int n, int d, int et, const float* x_norm2, int k, int* idx_out, float* dist2_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int r50_op_baseline_forecasts(const float* a1, const float* a0, const int* nn_row, const float* dbj, int64_t n_db, int b, int k, int t_db,
+                              int joints, int root, int input_len, int pred_len, float* const_pose, float* const_vel, float* nn, void* stream);
 
 /* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
 int r50_op_avgpool(const void* x_nhwc_bf16, int n, int hw, int c, float* y_f32, void* stream);
