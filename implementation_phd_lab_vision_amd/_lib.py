@@ -1,4 +1,4 @@
-"""ctypes binding of libr50hip.so (C ABI: include/r50.h).
+"""ctypes binding of libr50hip.so (C ABI: include/r50.h and include/r50_hal.h).
 
 This is the stub a maintainer of the reference would add to call the MI355X path from
 src/preprocess_resnet_features.py.  There is NO fallback: if the shared
@@ -28,10 +28,11 @@ class TensorDesc(C.Structure):
 
 
 def _source_digest() -> str:
-    """sha256 over everything the shared library is built from: csrc/*, include/r50.h and the compiler flags."""
+    """sha256 over everything the shared library is built from: csrc/*, include/r50.h, include/r50_hal.h and the compiler flags."""
     import hashlib
     hsh = hashlib.sha256()
-    files = sorted(p for p in CSRC.iterdir() if p.suffix in (".hip", ".h", ".hpp", ".cpp")) + [PKG_DIR.parent / "include" / "r50.h"]
+    files = sorted(p for p in CSRC.iterdir() if p.suffix in (".hip", ".h", ".hpp", ".cpp")) + \
+        [PKG_DIR.parent / "include" / "r50.h", PKG_DIR.parent / "include" / "r50_hal.h"]
     for f in files:
         hsh.update(f.name.encode() + b"\0")
         hsh.update(f.read_bytes())
@@ -180,11 +181,17 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# include/r50_hal.h (the hallucinator): a table of its own, so that _SIGNATURES stays the mirror of r50.h
+_SIGNATURES_HAL = {
+    "r50_op_hal_latent_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
 def load_library() -> C.CDLL:
-    """dlopen libr50hip.so and declare every prototype of include/r50.h.  Raises if it is absent."""
+    """dlopen libr50hip.so and declare every prototype of include/r50.h and include/r50_hal.h.  Raises if it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -196,7 +203,7 @@ def load_library() -> C.CDLL:
         raise R50Error(f"{LIB_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
                        "There is no CPU/PyTorch fallback for this path.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_HAL}.items():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

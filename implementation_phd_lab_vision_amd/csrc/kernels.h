@@ -7039,3 +7039,45 @@ __global__ __launch_bounds__(256) void baseline_forecasts_kernel(const float* a1
         }
     }
 }
+
+// The hallucinator's latent loss + its output gradient, one pass over h (rows, d): ar_latent_grad_kernel without the shift,
+//   dh[r]   = cast16(dh_reg[r] + coef * (h[r] - phi[r])),   coef = lambda * 2 / (rows * d) * loss_scale
+//   part[r] = sum over d of (h[r] - phi[r])^2
+// i.e. the gradient of lambda * mean((h - phi)^2) added to the regressor's dX (fp32, already times loss_scale) and the cast to the
+// 16-bit arena together.  h, phi, dh: et elements; dh_reg fp32.  One workgroup of 128 (two waves) per row, 8 elements per lane per
+// iteration: 16-byte loads of h / phi, two of dh_reg, one 16-byte store; d % 8 == 0, rows 16-byte aligned.  The row sum is a fixed
+// wave64 butterfly then the two waves in order; sum_parts_kernel adds the rows in a fixed order.  Every row reads and writes its own
+// d elements only.
+template <int ET>
+__global__ __launch_bounds__(128) void hal_latent_grad_kernel(const unsigned short* __restrict__ h, const unsigned short* __restrict__ phi,
+                                                              const float* __restrict__ dh_reg, int d, float coef,
+                                                              unsigned short* __restrict__ dh, float* __restrict__ part) {
+    __shared__ float red[2];
+    const long long r = blockIdx.x;
+    const int nv = d >> 3;
+    u32x4* out = reinterpret_cast<u32x4*>(dh + r * d);
+    const u32x4* a = reinterpret_cast<const u32x4*>(h + r * d);
+    const u32x4* p = reinterpret_cast<const u32x4*>(phi + r * d);
+    const f32x4* g = reinterpret_cast<const f32x4*>(dh_reg + r * d);
+    float ss = 0.f;
+    for (int v = threadIdx.x; v < nv; v += 128) {
+        const u32x4 av = a[v], pv = p[v];
+        const f32x4 g0 = g[2 * v], g1 = g[2 * v + 1];
+        const float gg[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
+        unsigned o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float dl = unpack_lo_e<ET>(av[k]) - unpack_lo_e<ET>(pv[k]);
+            const float du = unpack_hi_e<ET>(av[k]) - unpack_hi_e<ET>(pv[k]);
+            ss += dl * dl;
+            ss += du * du;
+            o[k] = pack2_e<ET>(gg[2 * k] + coef * dl, gg[2 * k + 1] + coef * du);
+        }
+        out[v] = (u32x4){o[0], o[1], o[2], o[3]};
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) part[r] = red[0] + red[1];
+}

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
+#include "../../include/r50_hal.h"
 
 #include <atomic>
 #include <cmath>
@@ -2451,6 +2452,23 @@ int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat
                   dphi_hat, t, d, coef, (unsigned short*)dar, row_part);
     hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, rows, 1.0 / n_l, loss_lat);
     return ew_done("r50_op_ar_latent_grad");
+}
+
+int r50_op_hal_latent_grad(const void* h, const void* phi, const float* dh_reg, int64_t rows, int d, float lambda, float loss_scale,
+                           void* dh, float* loss_lat, float* row_part, int et, void* stream) {
+    if (!h || !phi || !dh_reg || !dh || !loss_lat || !row_part)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: null pointer");
+    if (rows < 1 || rows > INT32_MAX) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: need 1 <= rows (within int range)");
+    if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: d must be a positive multiple of 8");
+    if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: et must be 0 (bf16) or 1 (fp16)");
+    if (!aligned16(h) || !aligned16(phi) || !aligned16(dh_reg) || !aligned16(dh))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: h, phi, dh_reg and dh must be 16-byte aligned");
+    const double n_l = (double)rows * d;
+    const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
+    R50_ET_LAUNCH(hal_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)h, (const unsigned short*)phi,
+                  dh_reg, d, coef, (unsigned short*)dh, row_part);
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, (long long)rows, 1.0 / n_l, loss_lat);
+    return ew_done("r50_op_hal_latent_grad");
 }
 
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,

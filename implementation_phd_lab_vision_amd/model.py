@@ -41,8 +41,17 @@ def _round_up(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 
 
-def expected_keys(latent_dim: int, joints_num: int, number_blocks: int) -> Dict[str, Tuple[int, ...]]:
-    """state-dict keys and shapes of the reference module (src/model.py:127-143)."""
+HAL_KEYS = ("f_hal.fc1.weight", "f_hal.fc1.bias", "f_hal.fc2.weight", "f_hal.fc2.bias")      # Hallucinator's parameters, in registration order
+
+
+def has_hallucinator(state_keys) -> bool:
+    """Whether a state dict (or any collection of its keys) carries the hallucinator f_hal."""
+    return HAL_KEYS[0] in state_keys
+
+
+def expected_keys(latent_dim: int, joints_num: int, number_blocks: int, hallucinator: bool = False) -> Dict[str, Tuple[int, ...]]:
+    """state-dict keys and shapes of the reference module (src/model.py:127-143); with ``hallucinator`` also f_hal's four
+    (section V: ``model.f_hal = Hallucinator(latent_dim)``, registered after the reference's modules)."""
     d, o = latent_dim, joints_num * 3
     keys: Dict[str, Tuple[int, ...]] = {"input_proj.weight": (d, 2048), "input_proj.bias": (d,)}
     for net, nb in (("f_movie", number_blocks), ("f_AR", _AR_BLOCKS)):
@@ -61,6 +70,10 @@ def expected_keys(latent_dim: int, joints_num: int, number_blocks: int) -> Dict[
     keys["f_3D.mlp.3.bias"] = (_REG_HIDDEN,)
     keys["f_3D.mlp.5.weight"] = (o, _REG_HIDDEN)
     keys["f_3D.mlp.5.bias"] = (o,)
+    if hallucinator:
+        for fc in ("fc1", "fc2"):
+            keys[f"f_hal.{fc}.weight"] = (d, d)
+            keys[f"f_hal.{fc}.bias"] = (d,)
     return keys
 
 
@@ -114,7 +127,8 @@ def gather_window_rows(src: torch.Tensor, starts, t: int, dtype: torch.dtype = t
 class PHDFor3DJoints:
     """``PHDFor3DJoints(latent_dim, joints_num, number_blocks)`` of src/model.py in eval mode on one MI355X."""
 
-    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16"):
+    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
+                 hallucinator: bool = False):
         if latent_dim % 64 or latent_dim % _GROUPS:
             raise ValueError("latent_dim must be a multiple of 64 (GEMM granularity) and of 32 (GroupNorm groups)")
         if precision not in ("fp16", "bf16"):
@@ -123,6 +137,7 @@ class PHDFor3DJoints:
         self.joints_num = int(joints_num)
         self.number_blocks = int(number_blocks)
         self.out_dim = self.joints_num * 3
+        self.hallucinator = bool(hallucinator)                 # f_hal (section V): four more keys, ``hallucinate`` / ``hallucinated_rollout``
         self._et = 1 if precision == "fp16" else 0
         self._dtype = torch.float16 if precision == "fp16" else torch.bfloat16
         self._sd: Optional[Dict[str, torch.Tensor]] = None
@@ -132,7 +147,7 @@ class PHDFor3DJoints:
 
     # ---- nn.Module-like surface -------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
-        want = expected_keys(self.latent_dim, self.joints_num, self.number_blocks)
+        want = expected_keys(self.latent_dim, self.joints_num, self.number_blocks, self.hallucinator)
         missing = [k for k in want if k not in state_dict]
         unexpected = [k for k in state_dict if k not in want]
         if missing or (strict and unexpected):
@@ -203,6 +218,10 @@ class PHDFor3DJoints:
         w["mlp3.w"], w["mlp3.b"] = elem(sd["f_3D.mlp.3.weight"]), f32(sd["f_3D.mlp.3.bias"])
         w["mlp5.w"], w["mlp5.b"] = elem(w5), f32(b5)
         w["y0"] = f32(sd["f_3D.y0"])
+        if self.hallucinator:                                                    # (D, D) = (cout, 1, 1, cin), as input_proj
+            for fc in ("fc1", "fc2"):
+                w[f"f_hal.{fc}.w"] = elem(sd[f"f_hal.{fc}.weight"])
+                w[f"f_hal.{fc}.b"] = f32(sd[f"f_hal.{fc}.bias"])
         self._dev = w
 
     # ---- launches ---------------------------------------------------------------------------
@@ -392,7 +411,6 @@ class PHDFor3DJoints:
             raise ValueError(f"rollout needs B >= 1 and 1 <= input_len <= T (got B={b}, input_len={i_len}, T={t})")
         if p_len < 1:
             raise ValueError(f"rollout needs pred_len >= 1 (got {p_len})")
-        d = self.latent_dim
         lib = _lib.load_library()
         with torch.cuda.device(self._device):
             f = feats[:, :i_len].to(torch.float32).contiguous()
@@ -400,23 +418,83 @@ class PHDFor3DJoints:
             _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * i_len, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None,
                        "r50_op_cast_rows")
             phi = self._temporal_net(self._gemm(x0, "input_proj", relu=False), b, i_len, "f_movie", self.number_blocks)
-            seq = torch.empty(((i_len + p_len) * b, d), dtype=self._dtype, device=self._device)
-            seq[: i_len * b].view(i_len, b, d).copy_(phi.view(b, i_len, d).transpose(0, 1))        # batch-major -> time-major
-            last = _AR_BLOCKS - 1
-            for k in range(p_len):
-                n = i_len + k
-                x = seq[: n * b]
-                for i in range(_AR_BLOCKS):
-                    p = f"f_AR.blocks.{i}"
-                    h = self._gemm(self._gn_relu_rows_tm(x, b, n, 0, p + ".gn1"), p + ".conv1", relu=False)
-                    if i < last:
-                        x = self._gemm(self._gn_relu_rows_tm(h, b, n, 0, p + ".gn2"), p + ".conv2", relu=False, residual=x)
-                    else:
-                        self._gemm(self._gn_relu_rows_tm(h, b, n, n - 1, p + ".gn2"), p + ".conv2", relu=False,
-                                   residual=x[(n - 1) * b:], out=seq[n * b: (n + 1) * b])
-            future = seq[i_len * b:]                                                      # (P*B, D) time-major
-            joints = self._regressor(future, p_len, b)                                    # (P, B, J, 3)
-            return future.view(p_len, b, d).transpose(0, 1).float(), joints.transpose(0, 1).contiguous()
+            return self._rollout_from(phi, b, i_len, p_len)
+
+    def _rollout_from(self, phi_rows: torch.Tensor, b: int, i_len: int, p_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``rollout`` after its observed strips: ``phi_rows`` (b*i_len, D) 16-bit, batch-major -> (future_phi (B, P, D) fp32,
+        future_joints (B, P, J, 3) fp32).  The caller has selected the head's device."""
+        d = self.latent_dim
+        seq = torch.empty(((i_len + p_len) * b, d), dtype=self._dtype, device=self._device)
+        seq[: i_len * b].view(i_len, b, d).copy_(phi_rows.view(b, i_len, d).transpose(0, 1))       # batch-major -> time-major
+        last = _AR_BLOCKS - 1
+        for k in range(p_len):
+            n = i_len + k
+            x = seq[: n * b]
+            for i in range(_AR_BLOCKS):
+                p = f"f_AR.blocks.{i}"
+                h = self._gemm(self._gn_relu_rows_tm(x, b, n, 0, p + ".gn1"), p + ".conv1", relu=False)
+                if i < last:
+                    x = self._gemm(self._gn_relu_rows_tm(h, b, n, 0, p + ".gn2"), p + ".conv2", relu=False, residual=x)
+                else:
+                    self._gemm(self._gn_relu_rows_tm(h, b, n, n - 1, p + ".gn2"), p + ".conv2", relu=False,
+                               residual=x[(n - 1) * b:], out=seq[n * b: (n + 1) * b])
+        future = seq[i_len * b:]                                                      # (P*B, D) time-major
+        joints = self._regressor(future, p_len, b)                                    # (P, B, J, 3)
+        return future.view(p_len, b, d).transpose(0, 1).float(), joints.transpose(0, 1).contiguous()
+
+    # ---- the hallucinator f_hal (INTEGRATION.md section V) ----------------------------------------
+    def _check_hal(self, feats: torch.Tensor, what: str) -> None:
+        if not self.hallucinator:
+            raise _lib.R50Error(f"{what} needs a head built with hallucinator=True (a checkpoint of train_hal carries f_hal.*)")
+        if self._device is None or not self._dev:
+            raise _lib.R50Error("call .load_state_dict(...) and .to('cuda:N') before running the head")
+        if feats.dim() != 3 or feats.shape[-1] != 2048:
+            raise ValueError(f"expected (B,T,2048) features, got {tuple(feats.shape)}")
+        if feats.device != self._device:
+            raise ValueError(f"features are on {feats.device}, head on {self._device}")
+
+    def _hal_rows(self, x0: torch.Tensor) -> torch.Tensor:
+        """``x + fc2(relu(fc1(x)))`` with ``x = input_proj(x0)``, row by row: three GEMM launches, (R, 2048) -> (R, D) 16-bit."""
+        x = self._gemm(x0, "input_proj", relu=False)
+        h1 = self._gemm(x, "f_hal.fc1", relu=True)
+        return self._gemm(h1, "f_hal.fc2", relu=False, residual=x)
+
+    @torch.no_grad()
+    def hallucinate(self, feats: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The movie strip and the 3D pose of every frame from that frame ALONE: ``phi_tilde = f_hal(input_proj(feats))`` and
+        ``f_3D(phi_tilde)``.  Returns (phi_tilde (B, T, D) fp32, joints (B, T, J, 3) fp32).  The launches: cast, input_proj, f_hal's two
+        GEMMs (ReLU, then the skip connection as the residual epilogue), the regressor.  No GroupNorm and no launch that sees more than
+        a row, so the result of a frame does not depend on the frames around it."""
+        self._check_hal(feats, "hallucinate")
+        b, t, _ = feats.shape
+        if b * t == 0:
+            raise ValueError("empty batch")
+        lib = _lib.load_library()
+        with torch.cuda.device(self._device):
+            f = feats.to(torch.float32).contiguous()
+            x0 = torch.empty((b * t, 2048), dtype=self._dtype, device=self._device)
+            _lib.check(lib.r50_op_cast_rows(f.data_ptr(), b * t, 2048, x0.data_ptr(), 2048, self._et, self._stream()), None,
+                       "r50_op_cast_rows")
+            phi_tilde = self._hal_rows(x0)
+            return phi_tilde.view(b, t, self.latent_dim).float(), self._regressor(phi_tilde, b, t)
+
+    @torch.no_grad()
+    def hallucinated_rollout(self, feats: torch.Tensor, frame: int, pred_len: int = 25) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The forecast from ONE frame: ``rollout`` with input_len = 1 whose only observed strip is f_hal's for ``feats[:, frame]``
+        instead of f_movie's.  Returns (future_phi (B, P, D) fp32, future_joints (B, P, J, 3) fp32): the ``pred_len`` strips after
+        ``frame`` and f_3D on them.  Only ``feats[:, frame]`` is read: one ``r50_op_gather_window_rows`` launch (t = 1) picks and casts
+        it, then input_proj and f_hal over B rows and ``rollout``'s launches on its time-major buffer."""
+        self._check_hal(feats, "hallucinated_rollout")
+        b, t, _ = feats.shape
+        fr, p_len = int(frame), int(pred_len)
+        if b < 1 or not 0 <= fr < t:
+            raise ValueError(f"hallucinated_rollout needs B >= 1 and 0 <= frame < T (got B={b}, frame={fr}, T={t})")
+        if p_len < 1:
+            raise ValueError(f"hallucinated_rollout needs pred_len >= 1 (got {p_len})")
+        with torch.cuda.device(self._device):
+            src = feats.to(torch.float32).contiguous().view(b * t, 2048)
+            x0 = gather_window_rows(src, [w * t + fr for w in range(b)], 1, self._dtype)
+            return self._rollout_from(self._hal_rows(x0), b, 1, p_len)
 
 
 PHD = PHDFor3DJoints       # the name src/train.py imports it under

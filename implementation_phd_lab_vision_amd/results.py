@@ -28,7 +28,10 @@ warped error and the lag in frames per horizon; the ``.npz`` gains the ``dtw_*``
 ``--pred-len``) trivial forecasts are scored on the same clips (``baselines.evaluate_baselines``): the last
 pose held, the last step continued, and the future of the nearest training clip in movie-strip space (``--nn-subjects``, ``--nn-k``);
 the ``Baselines`` lines print each predictor's MPJPE / P1 / P2 per horizon beside the model's and the model's skill against it; the
-``.npz`` gains the ``baseline_*`` and ``nn_*`` keys.
+``.npz`` gains the ``baseline_*`` and ``nn_*`` keys.  With ``--hallucinate`` (default off; needs a checkpoint of ``train_hal``;
+INTEGRATION.md section V) the head is also scored from single frames (``hallucinate.evaluate_hallucinator``): the ``Hallucinator`` lines
+print the reconstruction of every frame from that frame alone beside the one with temporal context and, with ``--pred-len``, the
+forecast from the last observed frame alone beside the rollout's, per horizon and per action; the ``.npz`` gains the ``hal_*`` keys.
 
 Two differences from running the reference's script as it stands:
 
@@ -133,6 +136,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--nn-features-root", type=str, default=argparse.SUPPRESS, metavar="DIR",
                    help="feature cache of the nn baseline's database (default: --features_root)")
     p.add_argument("--nn-max-clips", type=int, default=argparse.SUPPRESS, metavar="N", help="use only the first N database clips (nn baseline)")
+    p.add_argument("--hallucinate", action="store_true", default=argparse.SUPPRESS,
+                   help="also score the hallucinator f_hal on the same clips (INTEGRATION.md section V): every frame's pose from that frame "
+                        "alone beside the one with temporal context and, with --pred-len, the forecast from the last observed frame "
+                        "alone beside the rollout's; needs a checkpoint written by train_hal")
     return p
 
 
@@ -248,10 +255,11 @@ def load_head_state(path: str, which: str = "auto") -> Dict[str, torch.Tensor]:
 
 
 def build_head(state: Dict[str, torch.Tensor], device, precision: str = "fp16"):
-    """A ``model.PHDFor3DJoints`` with the checkpoint's own dimensions, loaded strictly, on ``device``, in eval mode."""
-    from .model import PHDFor3DJoints
+    """A ``model.PHDFor3DJoints`` with the checkpoint's own dimensions, loaded strictly, on ``device``, in eval mode.  A state with
+    the hallucinator's keys (``f_hal.*``) gives a head with f_hal."""
+    from .model import PHDFor3DJoints, has_hallucinator
     latent_dim, joints_num, number_blocks = infer_head_dims(state)
-    head = PHDFor3DJoints(latent_dim, joints_num, number_blocks, precision=precision)
+    head = PHDFor3DJoints(latent_dim, joints_num, number_blocks, precision=precision, hallucinator=has_hallucinator(state))
     head.load_state_dict(state, strict=True)
     return head.to(device).eval()
 
@@ -569,7 +577,11 @@ def main(argv: Optional[List[str]] = None) -> str:
         raise SystemExit(f"results: the test set has {len(test_set)} clips, fewer than one batch of {args.batch_size} "
                          "(the loader drops the last incomplete batch); lower --batch-size")
     index_skip = int(torch.load(os.path.join(args.features_root, "index.pt"), map_location="cpu", weights_only=True).get("frame_skip", 1))
-    head = build_head(load_head_state(args.model_path, args.weights_from), device, args.precision)
+    state = load_head_state(args.model_path, args.weights_from)
+    if hasattr(args, "hallucinate"):
+        from .hallucinate import require_hallucinator
+        require_hallucinator(state)
+    head = build_head(state, device, args.precision)
     print(f"Head: latent_dim={head.latent_dim} joints={head.joints_num} blocks={head.number_blocks} ({args.precision}) | "
           f"test clips: {len(test_set)}")
 
@@ -650,6 +662,15 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in baseline_lines(base, args.input_len, args.pred_len):
             print(line)
 
+    hal = None
+    if hasattr(args, "hallucinate"):         # the protocols' pass once more: from single frames beside with temporal context
+        from .hallucinate import evaluate_hallucinator, hallucinate_lines
+        from .protocols import action_groups
+        names, ids = action_groups(test_set.item_actions())
+        hal = evaluate_hallucinator(head, test_set, ids, names, args.input_len if args.pred_len > 0 else 0, args.pred_len)
+        for line in hallucinate_lines(hal):
+            print(line)
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -693,6 +714,9 @@ def main(argv: Optional[List[str]] = None) -> str:
                                 args.pred_len, ("nn",), baseline_options(args)[2], baseline_options(args)[1])
             extra.update(nn_index=fb["nn_index"].cpu().numpy(), nn_dist2=fb["nn_dist2"].cpu().numpy(),
                          nn_future3djoints=fb["nn"].cpu().numpy())
+    if hal is not None:
+        from .hallucinate import hallucinate_arrays
+        extra.update(hallucinate_arrays(hal))
     if n_render:                             # the person crops, drawn over; a clip without a usable box gets the plain background
         from . import render
         plain = torch.tensor(render._rgb_tuple(render.PANEL_BG_RGB), dtype=torch.uint8, device=device)

@@ -268,8 +268,9 @@ class TrainableHead(FlatTrainableHead):
 
     _no_transpose = frozenset({"input_proj.w"})
 
-    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16"):
-        super().__init__(latent_dim, joints_num, number_blocks, precision)
+    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
+                 hallucinator: bool = False):
+        super().__init__(latent_dim, joints_num, number_blocks, precision, hallucinator)
         self._use_graphs = False
         self._graphs: Dict[tuple, tuple] = {}
         self._geo_out8: Optional[torch.Tensor] = None
@@ -782,13 +783,16 @@ def open_run(args: argparse.Namespace, make_head) -> Run:
 
 def head_from_checkpoint(args: argparse.Namespace, cls, **kwargs):
     """``make_head`` of the stages that start from weights: ``cls`` at the dimensions of ``--init`` (or, without it, ``--resume``),
-    loaded with that state."""
+    loaded with that state.  A state that carries the hallucinator (``f_hal.*``) gets a head built with
+    ``hallucinator=True``: the stage leaves those four tensors as they are and its checkpoints keep them."""
+    from .model import has_hallucinator
     from .results import infer_head_dims, load_head_state
 
     def make_head(device):
         state = load_head_state(args.init, getattr(args, "weights_from", "auto")) if args.init else load_head_state(args.resume, "model")
         latent_dim, joints_num, number_blocks = infer_head_dims(state)
-        head = cls(latent_dim, joints_num, number_blocks, precision=args.precision, **kwargs)
+        extra = {"hallucinator": True} if has_hallucinator(state) else {}
+        head = cls(latent_dim, joints_num, number_blocks, precision=args.precision, **kwargs, **extra)
         head.load_state_dict(state, strict=True)
         return head.to(device)
     return make_head

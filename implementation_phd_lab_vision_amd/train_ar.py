@@ -98,8 +98,8 @@ class ARTrainableHead(FlatTrainableHead):
     _clip_rule = (2, "phase 2")
 
     def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
-                 lambda_latent: float = LAMBDA_LATENT):
-        super().__init__(latent_dim, joints_num, number_blocks, precision)
+                 lambda_latent: float = LAMBDA_LATENT, hallucinator: bool = False):
+        super().__init__(latent_dim, joints_num, number_blocks, precision, hallucinator)
         self.lambda_latent = float(lambda_latent)
 
     def _flat_items(self) -> List[FlatItem]:

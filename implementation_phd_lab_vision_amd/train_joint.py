@@ -93,8 +93,8 @@ class JointTrainableHead(FlatTrainableHead):
     _clip_rule = (2, "joint training")
 
     def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
-                 lambda_future: float = LAMBDA_FUTURE, lambda_latent: float = LAMBDA_LATENT):
-        super().__init__(latent_dim, joints_num, number_blocks, precision)
+                 lambda_future: float = LAMBDA_FUTURE, lambda_latent: float = LAMBDA_LATENT, hallucinator: bool = False):
+        super().__init__(latent_dim, joints_num, number_blocks, precision, hallucinator)
         if self.number_blocks < 1:
             raise ValueError("joint training needs at least one f_movie block (its last conv2 stores phi)")
         self.lambda_future = float(lambda_future)

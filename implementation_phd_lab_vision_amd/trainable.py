@@ -198,12 +198,13 @@ class FlatTrainableHead(PHDFor3DJoints):
     _frozen_transposes: Tuple[str, ...] = ()       # frozen weights a dX product reads: transposed once at upload
     _clip_rule: Optional[Tuple[int, str]] = None   # (minimum clip length, the stage's wording in the error); None: any (B, T)
 
-    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16"):
-        super().__init__(latent_dim, joints_num, number_blocks, precision)
+    def __init__(self, latent_dim: int = 2048, joints_num: int = 17, number_blocks: int = 3, precision: str = "fp16",
+                 hallucinator: bool = False):
+        super().__init__(latent_dim, joints_num, number_blocks, precision, hallucinator)
         self.flat_master: Optional[torch.Tensor] = None
         self._layout: List[Tuple[str, int, Tuple[int, ...]]] = []
         self.last_losses: Dict[str, float] = {}
-        self._ref_shapes = expected_keys(self.latent_dim, self.joints_num, self.number_blocks)
+        self._ref_shapes = expected_keys(self.latent_dim, self.joints_num, self.number_blocks, self.hallucinator)
 
     # ---- what a subclass says ---------------------------------------------------------------------
     def _flat_items(self) -> List[FlatItem]:
