@@ -1,11 +1,13 @@
-// Host side of libr50hip.so: C ABI declared in include/r50.h.
+// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h and include/r50_smooth.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
 #include "kernels.h"
+#include "smooth_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
+#include "../../include/r50_smooth.h"
 
 #include <atomic>
 #include <cmath>
@@ -2469,6 +2471,89 @@ int r50_op_hal_latent_grad(const void* h, const void* phi, const float* dh_reg, 
                   dh_reg, d, coef, (unsigned short*)dh, row_part);
     hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, (long long)rows, 1.0 / n_l, loss_lat);
     return ew_done("r50_op_hal_latent_grad");
+}
+
+// ---- temporal smoothing and constant bone lengths (include/r50_smooth.h, smooth_kernels.h) ----
+static bool overlaps(const void* a, const void* b, long long bytes) {
+    const char *a0 = (const char*)a, *b0 = (const char*)b;
+    return a0 < b0 + bytes && b0 < a0 + bytes;
+}
+static const long long kSmoothMaxRows = INT32_MAX / (3 * SMOOTH_MAX_J);
+
+// The edge list of the bone ops, checked: on success `ed` and `is_child` are filled, else the reason is returned.
+static const char* check_bone_edges(const int* edges, int E, int J, BoneEdges& ed, unsigned long long& is_child) {
+    if (E < 1 || E > J - 1) return "need 1 <= E <= J - 1";
+    is_child = 0;
+    for (int q = 0; q < SMOOTH_MAX_J; ++q) ed.parent[q] = ed.child[q] = 0;
+    for (int q = 0; q < E; ++q) {
+        const int pa = edges[2 * q], ch = edges[2 * q + 1];
+        if (pa < 0 || pa >= J || ch < 0 || ch >= J) return "every edge index must be in [0, J)";
+        if (pa == ch) return "an edge needs two different joints";
+        if ((is_child >> ch) & 1ull) return "a joint may be the child of one edge only";
+        is_child |= 1ull << ch;
+        ed.parent[q] = (unsigned char)pa;
+        ed.child[q] = (unsigned char)ch;
+    }
+    unsigned long long placed = 0;
+    for (int q = 0; q < E; ++q) {
+        const int pa = ed.parent[q];
+        if (((is_child >> pa) & 1ull) && !((placed >> pa) & 1ull)) return "every edge must come after the edge that places its parent";
+        placed |= 1ull << ed.child[q];
+    }
+    return nullptr;
+}
+
+int r50_op_fir_sequences(const float* x, const int* seg_start, const int* row_seg, int64_t F, int G, int J, const double* coef, int W,
+                         float* out, int* short_rows, void* stream) {
+    if (!x || !seg_start || !row_seg || !coef || !out || !short_rows) return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || G < 1 || G > F || J < 1 || J > SMOOTH_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: invalid arguments (need 1 <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (W < 1 || W > SMOOTH_MAX_W || W % 2 == 0) return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: W must be odd and in [1, 63]");
+    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: out overlaps x");
+    hipLaunchKernelGGL(fir_sequences_kernel, dim3((unsigned)((F + FIR_ROWS - 1) / FIR_ROWS)), dim3(256), 0, (hipStream_t)stream, x, seg_start,
+                       row_seg, (int)F, G, 3 * J, coef, W, out, short_rows);
+    return ew_done("r50_op_fir_sequences");
+}
+
+int r50_op_one_euro_sequences(const float* x, const int* seg_start, int64_t F, int G, int J, double rate, double min_cutoff, double beta,
+                              double d_cutoff, float* out, void* stream) {
+    if (!x || !seg_start || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || G < 1 || G > F || J < 1 || J > SMOOTH_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: invalid arguments (need 1 <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (!(rate > 0.0 && min_cutoff > 0.0 && d_cutoff > 0.0 && beta >= 0.0) || !std::isfinite(rate) || !std::isfinite(min_cutoff) ||
+        !std::isfinite(d_cutoff) || !std::isfinite(beta))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: need finite rate, min_cutoff, d_cutoff > 0 and beta >= 0");
+    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: out overlaps x");
+    const int slabs = (3 * J + 63) / 64;
+    hipLaunchKernelGGL(one_euro_sequences_kernel, dim3((unsigned)(((long long)G * slabs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x,
+                       seg_start, G, 3 * J, slabs, rate, min_cutoff, beta, d_cutoff, out);
+    return ew_done("r50_op_one_euro_sequences");
+}
+
+int r50_op_bone_stats(const float* x, const int* seq_start, int64_t F, int S, int J, const int* edges, int E, double* stats, void* stream) {
+    if (!x || !seq_start || !edges || !stats) return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_stats: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 2 || J > SMOOTH_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_stats: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 2 <= J <= 64)");
+    BoneEdges ed;
+    unsigned long long is_child;
+    if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_bone_stats: edges: ") + why);
+    hipLaunchKernelGGL(bone_stats_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, x, seq_start, 3 * J, ed, E, stats);
+    return ew_done("r50_op_bone_stats");
+}
+
+int r50_op_bone_rebuild(const float* x, const int* row_seq, int64_t F, int S, int J, const int* edges, int E, const double* stats, float* out,
+                        void* stream) {
+    if (!x || !row_seq || !edges || !stats || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_rebuild: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 2 || J > SMOOTH_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_rebuild: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 2 <= J <= 64)");
+    BoneEdges ed;
+    unsigned long long is_child;
+    if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_bone_rebuild: edges: ") + why);
+    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_rebuild: out overlaps x");
+    const int rb = bone_rebuild_rows(J);
+    hipLaunchKernelGGL(bone_rebuild_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), bone_rebuild_lds(J), (hipStream_t)stream, x, row_seq,
+                       (int)F, J, ed, E, is_child, stats, out);
+    return ew_done("r50_op_bone_rebuild");
 }
 
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,

@@ -279,11 +279,14 @@ class VideoPredictor:
 
     @torch.no_grad()
     def predict(self, frames, box=None, joints2d=None, cam: Optional[dict] = None, frame_skip: int = 1, input_len: int = 15,
-                pred_len: int = 0, name: str = "video") -> Dict[str, object]:
+                pred_len: int = 0, name: str = "video", post=None) -> Dict[str, object]:
         """The whole pass over every ``frame_skip``-th frame.  ``box``: see ``choose_box`` (``joints2d`` (N, J, 2) pixels of the whole
         frames, of ALL frames; the kept ones are used).  Returns host numpy arrays: ``joints3d`` (n, J, 3), ``spread`` (n,), ``count``
         (n,), ``frame_idx`` (n,) the original frame numbers, ``box`` (4,), ``future3d`` (P, J, 3) if ``pred_len > 0``, ``K`` (3, 3) of
-        the resized crop if ``cam`` = ``{"f": .., "c": ..}`` was given, and ``stats``."""
+        the resized crop if ``cam`` = ``{"f": .., "c": ..}`` was given, and ``stats``.  With ``post`` (a ``smooth.PostProcess``;
+        INTEGRATION.md section W) the fused poses go through it as one sequence of one segment: ``joints3d`` holds the processed poses,
+        ``joints3d_raw`` what it would hold without, ``post`` the settings and ``post_short_rows`` the frames a FIR window longer than
+        the video left as they were; ``future3d`` is left as it is."""
         total, h, w = self._check_frames(frames)
         if int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be >= 1, got {frame_skip}")
@@ -301,6 +304,12 @@ class VideoPredictor:
         joints3d, spread, count = self.poses(feats, flipped, name)
         out: Dict[str, object] = {"joints3d": joints3d.cpu().numpy(), "spread": spread.cpu().numpy(), "count": count.cpu().numpy(),
                                   "frame_idx": frame_idx, "box": box_t.numpy().copy()}
+        if post is not None:
+            n = int(joints3d.shape[0])
+            with torch.cuda.device(self.device):
+                processed, info = post.apply(joints3d, (np.array([0, n], dtype=np.int32), np.arange(n, dtype=np.int32)))
+            out["joints3d_raw"], out["joints3d"] = out["joints3d"], processed.cpu().numpy()
+            out["post"], out["post_short_rows"] = np.array(post.describe()), np.int64(info["short_rows"][0].item())
         if int(pred_len) > 0:
             out["future3d"] = self.forecast(feats, input_len, pred_len).cpu().numpy()
         if cam is not None:
@@ -353,7 +362,31 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--render-frames", type=int, default=120, help="how many of the last frames to render")
     p.add_argument("--render-fps", type=float, default=10.0)
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--smooth", choices=("gauss", "savgol", "one_euro"), default=argparse.SUPPRESS,
+                   help="filter the fused poses along time on the device before they are written and rendered (INTEGRATION.md section W); "
+                        "the file keeps the unprocessed poses as joints3d_raw")
+    p.add_argument("--fix-bones", action="store_true", default=argparse.SUPPRESS,
+                   help="give every bone its mean length over the video, after the filter (INTEGRATION.md section W)")
+    from .smooth import add_parameter_flags
+    add_parameter_flags(p)
     return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    """``build_parser().parse_args`` plus the check that a filter's parameter flags come with that filter (``--smooth``)."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    video_post(args, p.error)
+    return args
+
+
+def video_post(args: argparse.Namespace, error=None):
+    """The ``smooth.PostProcess`` of parsed arguments, or None without ``--smooth`` / ``--fix-bones``."""
+    from .smooth import post_from_args
+
+    def raise_(msg):
+        raise ValueError(msg)
+    return post_from_args(args, getattr(args, "smooth", None), getattr(args, "fix_bones", False), error or raise_)
 
 
 def load_input(path: str) -> Dict[str, object]:
@@ -397,7 +430,8 @@ def render_prediction(outdir: str, predictor: VideoPredictor, frames, res: Dict[
 
 
 def main(argv: Optional[List[str]] = None) -> List[str]:
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
+    post = video_post(args)
     device = torch.device(args.device)
     if device.type != "cuda" or not torch.cuda.is_available():
         raise _lib.R50Error("predict runs on an MI355X only; there is no CPU fallback")
@@ -416,7 +450,8 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     for path, item in zip(args.frames, items):
         name = os.path.splitext(os.path.basename(path))[0]
         res = predictor.predict(item["frames"], box=args.box if args.box is not None else item.get("box"), joints2d=item.get("joints2d"),
-                                cam=item.get("cam"), frame_skip=args.frame_skip, input_len=args.input_len, pred_len=args.pred_len, name=name)
+                                cam=item.get("cam"), frame_skip=args.frame_skip, input_len=args.input_len, pred_len=args.pred_len, name=name,
+                                **({} if post is None else {"post": post}))
         stats = res.pop("stats")
         out_path = os.path.join(args.out, name + "_poses.npz")
         np.savez(out_path, **res, **{k: np.int64(v) for k, v in stats.items()})

@@ -32,6 +32,10 @@ the ``Baselines`` lines print each predictor's MPJPE / P1 / P2 per horizon besid
 INTEGRATION.md section V) the head is also scored from single frames (``hallucinate.evaluate_hallucinator``): the ``Hallucinator`` lines
 print the reconstruction of every frame from that frame alone beside the one with temporal context and, with ``--pred-len``, the
 forecast from the last observed frame alone beside the rollout's, per horizon and per action; the ``.npz`` gains the ``hal_*`` keys.
+With ``--dense-smooth gauss | savgol | one_euro`` and / or ``--dense-fix-bones`` (default off; need ``--dense``; INTEGRATION.md section
+W) the stitched sequences are also filtered along time and rebuilt with constant bone lengths on the device (``smooth.PostProcess``):
+the ``Dense | post`` lines set the processed poses' errors and bone-length deviation beside the raw ones, the ``.npz`` gains the
+``dense_post_*`` keys and ``--dense-out`` gains ``pred_post``.
 
 Two differences from running the reference's script as it stands:
 
@@ -140,7 +144,23 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also score the hallucinator f_hal on the same clips (INTEGRATION.md section V): every frame's pose from that frame "
                         "alone beside the one with temporal context and, with --pred-len, the forecast from the last observed frame "
                         "alone beside the rollout's; needs a checkpoint written by train_hal")
+    p.add_argument("--dense-smooth", choices=("gauss", "savgol", "one_euro"), default=argparse.SUPPRESS,
+                   help="also filter every stitched sequence along time on the device and score the result beside the raw poses "
+                        "(--dense; INTEGRATION.md section W): a Gaussian, a Savitzky-Golay filter, or the causal One-Euro filter")
+    p.add_argument("--dense-fix-bones", action="store_true", default=argparse.SUPPRESS,
+                   help="also give every bone its sequence's mean length, after the filter (--dense; INTEGRATION.md section W)")
+    from .smooth import add_parameter_flags
+    add_parameter_flags(p)
     return p
+
+
+def dense_post(args: argparse.Namespace, error=None):
+    """The ``smooth.PostProcess`` of parsed arguments, or None without ``--dense-smooth`` / ``--dense-fix-bones``."""
+    from .smooth import post_from_args
+
+    def raise_(msg):
+        raise ValueError(msg)
+    return post_from_args(args, getattr(args, "dense_smooth", None), getattr(args, "dense_fix_bones", False), error or raise_)
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -169,6 +189,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--render-sheet-every must be >= 1, got {args.render_sheet_every}")
     if args.dense_out is not None and not args.dense:
         p.error("--dense-out needs --dense")
+    for flag in ("dense_smooth", "dense_fix_bones"):
+        if hasattr(args, flag) and not args.dense:
+            p.error(f"--{flag.replace('_', '-')} needs --dense")
+    dense_post(args, p.error)                # a parameter flag without its filter, or a refused parameter
     if args.dtw and args.pred_len <= 0:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
@@ -469,6 +493,27 @@ def dense_lines(res: Dict[str, object]) -> List[str]:
     return lines
 
 
+def dense_post_lines(res: Dict[str, object]) -> List[str]:
+    """The ``Dense | post`` lines of an ``evaluate_dense`` result that carries ``post``: raw -> processed over all frames and per
+    action, errors in millimetres and the bone-length standard deviation over time of the raw, processed and ground-truth poses."""
+    def pair(m: str, key, i=None) -> str:
+        a, b = res[m + key], res["post_" + m + key]
+        a, b = (a, b) if i is None else (a[i], b[i])
+        return f"{a * 1000.0:.2f} -> {b * 1000.0:.2f}"
+
+    def row(key: str, i=None) -> str:
+        std = [res[f"bone_std_{k}{'_all' if i is None else ''}"] for k in ("raw", "post", "gt")]
+        std = [v if i is None else v[i] for v in std]
+        return (f"p1 (mm) {pair('p1', key, i)} | p2 (mm) {pair('p2', key, i)} | vel (mm/frame) {pair('mpjve', key, i)} | accel (mm/frame^2) "
+                f"{pair('accel', key, i)} | bone std (mm) {std[0]:.3f} -> {std[1]:.3f} (gt {std[2]:.3f})")
+
+    lines = [f"Dense | post {res['post']} | frames copied (segment shorter than the window) {res['post_short_rows']} in "
+             f"{res['post_short_segments']} segments | raw -> processed, all: {row('_all')}"]
+    for i, name in enumerate(res["group_names"]):
+        lines.append(f"Dense | post   {name} | {row('', i)}")
+    return lines
+
+
 def dense_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     """The ``.npz`` keys of ``--dense``: ``dense_actions`` (G,) str, ``dense_frames`` (G,) int64, ``dense_M`` (G,) and ``dense_M_all`` ()
     fp32 for M in p1, p2, mpjve, accel, spread (metres, metres per frame, metres per frame^2), ``dense_position_p1`` / ``_p2`` (T,) fp32,
@@ -481,6 +526,15 @@ def dense_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     for m in ("p1", "p2", "mpjve", "accel", "spread"):
         out["dense_" + m] = np.asarray(res[m], dtype=np.float32)
         out["dense_" + m + "_all"] = np.asarray(res[m + "_all"], dtype=np.float32)
+    if "post" in res:                        # --dense-smooth / --dense-fix-bones: dense_post_M, dense_post_bone_std_{raw,post,gt} (mm), ...
+        out["dense_post"] = np.array(str(res["post"]))
+        out["dense_post_short"] = np.array([res["post_short_rows"], res["post_short_segments"]], dtype=np.int64)
+        for m in ("p1", "p2", "mpjve", "accel"):
+            out["dense_post_" + m] = np.asarray(res["post_" + m], dtype=np.float32)
+            out["dense_post_" + m + "_all"] = np.asarray(res["post_" + m + "_all"], dtype=np.float32)
+        for k in ("raw", "post", "gt"):
+            out["dense_post_bone_std_" + k] = np.asarray(res["bone_std_" + k], dtype=np.float32)
+            out["dense_post_bone_std_" + k + "_all"] = np.asarray(res["bone_std_" + k + "_all"], dtype=np.float32)
     return out
 
 
@@ -555,8 +609,11 @@ def dense_export(res: Dict[str, object]) -> Dict[str, np.ndarray]:
     """The arrays of ``--dense-out``: ``seq_keys`` (S, 3) str [subject, action, cam], ``seq_start`` (S+1,), ``frame_idx`` (F,) int32
     (sub-sampled frame units), ``pred`` and ``gt`` (F, J, 3) fp32 in metres, ``spread`` (F,) fp32, ``count`` (F,) int32 = the clips
     that showed the frame; sequence s is rows ``seq_start[s]:seq_start[s+1]``."""
-    return {"seq_keys": np.array([[str(v) for v in k] for k in res["seq_keys"]], dtype=str), "seq_start": res["seq_start"],
-            "frame_idx": res["frame_idx"], "pred": res["pred"], "gt": res["gt"], "spread": res["frame_spread"], "count": res["count"]}
+    out = {"seq_keys": np.array([[str(v) for v in k] for k in res["seq_keys"]], dtype=str), "seq_start": res["seq_start"],
+           "frame_idx": res["frame_idx"], "pred": res["pred"], "gt": res["gt"], "spread": res["frame_spread"], "count": res["count"]}
+    if "pred_post" in res:                   # --dense-smooth / --dense-fix-bones: the processed poses beside the raw ones, and what made them
+        out["pred_post"], out["post"] = res["pred_post"], np.array(str(res["post"]))
+    return out
 
 
 def main(argv: Optional[List[str]] = None) -> str:
@@ -624,8 +681,10 @@ def main(argv: Optional[List[str]] = None) -> str:
     dense = None
     if args.dense:                           # every video frame once: the clips of a sequence fused per frame
         from .sequences import evaluate_dense
-        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse, keep_poses=args.dense_out is not None)
-        for line in dense_lines(dense):
+        post = dense_post(args)
+        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse, keep_poses=args.dense_out is not None,
+                               **({} if post is None else {"post": post}))
+        for line in dense_lines(dense) + (dense_post_lines(dense) if post is not None else []):
             print(line)
 
     dtw = None

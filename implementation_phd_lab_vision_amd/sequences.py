@@ -270,7 +270,7 @@ def metric_values(sums: np.ndarray, p2_sums: np.ndarray) -> Dict[str, object]:
 
 @torch.no_grad()
 def evaluate_dense(head, store, fuse: str = "context", batch_size: int = 256, chunk_clips: int = 8192,
-                   keep_poses: bool = False) -> Dict[str, object]:
+                   keep_poses: bool = False, post=None) -> Dict[str, object]:
     """Every video frame of ``store`` (a ``DeviceFeatureStore`` without ``augment``) scored once: ``head.joints`` over every clip, the
     clips of each sequence fused per frame (``fuse``: ``mean``, ``context`` with ramp ``1 + 4 * head.number_blocks``, ``last``) and the
     fused frames scored per action.  Sequences are taken in runs of at most ``chunk_clips`` clips (a sequence is never split); per run
@@ -282,6 +282,17 @@ def evaluate_dense(head, store, fuse: str = "context", batch_size: int = 256, ch
         clip_frames = clips * T, multi_frames (frames with >= 2 contributors), sequences, fuse, ramp
         position_p1 (T,), position_p2 (T,): the clip-wise errors by window position over all clips
         with keep_poses: seq_keys [S], seq_start (S+1,), frame_idx (F,), pred (F, J, 3), gt (F, J, 3), frame_spread (F,), count (F,)
+
+    With ``post`` (a ``smooth.PostProcess``) each run's fused poses also go through ``post.apply`` -- a
+    sequence is never split across runs, so this is exact -- and the processed poses are scored by the same metrics and protocols
+    launches next to the raw ones; still one read of the sums per pass.  The result gains, for M in ``p1``, ``p2``, ``mpjve``, ``accel``::
+
+        post_M (G,), post_M_all, post_M_mean, post (what was applied, whether it is causal and its look-ahead R)
+        bone_std_raw, bone_std_post, bone_std_gt (G,) and *_all: the bone-length standard deviation over time in mm (smooth.bone_std_mm)
+        post_short_rows, post_short_segments: frames the FIR copied because their segment is shorter than its window
+        with keep_poses: pred_post (F, J, 3)
+
+    Without ``post`` the pass is what it was: the same launches, the same bits.
 
     Raises ValueError if any frame's contributors disagree on the ground truth (a wrong index)."""
     if getattr(store, "augment", False):
@@ -299,11 +310,16 @@ def evaluate_dense(head, store, fuse: str = "context", batch_size: int = 256, ch
     n_groups, joints, ramp = len(group_names), int(head.joints_num), 1 + 4 * int(head.number_blocks)
     dev = head._device
     parts, kept = [], []
+    post_parts, post_stats, post_short = [], [], []
+    if post is not None:
+        from . import smooth
+    chunks = table.chunks(chunk_clips)
     with torch.cuda.device(dev):
         acc_pos = torch.zeros(2 * t + 1, dtype=torch.float64, device=dev)             # the protocols op over the clips, one group
         acc_p2 = torch.zeros(3 * n_groups, dtype=torch.float64, device=dev)            # the protocols op over the stitched frames, P = 1
         gap = torch.zeros(1, dtype=torch.float64, device=dev)
-        for chunk in table.chunks(chunk_clips):
+        acc_p2_post = torch.zeros(3 * n_groups, dtype=torch.float64, device=dev) if post is not None else None
+        for chunk in chunks:
             tbl, n = chunk.table, len(chunk.items)
             pred = torch.empty((n, t, joints, 3), dtype=torch.float32, device=dev)
             gt = torch.empty((n, t, joints, 3), dtype=torch.float32, device=dev)
@@ -320,12 +336,24 @@ def evaluate_dense(head, store, fuse: str = "context", batch_size: int = 256, ch
             protocols._launch(fused.view(f, 1, joints, 3), gt_out.view(f, 1, joints, 3), 0, group, n_groups, acc_p2, ROOT_JOINT)
             protocols._launch(pred, gt, 0, torch.zeros(n, dtype=torch.int32, device=dev), 1, acc_pos, ROOT_JOINT)
             gap = torch.maximum(gap, gt_gap.max().to(torch.float64).reshape(1))     # a NaN stays
+            fused_post = None
+            if post is not None:
+                fused_post, info = post.apply(fused, tbl)
+                dt = info["tables"]
+                post_parts.append(sequence_metrics(fused_post, gt_out, spread, index.offsets, torch.from_numpy(tbl.seq).to(dev),
+                                                   torch.from_numpy(tbl.idx).to(dev), group, n_groups).reshape(-1))
+                protocols._launch(fused_post.view(f, 1, joints, 3), gt_out.view(f, 1, joints, 3), 0, group, n_groups, acc_p2_post, ROOT_JOINT)
+                post_stats.append(torch.stack([smooth.bone_stats(v, dt, post.edges) for v in (fused, fused_post, gt_out)]).reshape(-1))
+                post_short.append(info["short_rows"].to(torch.float64))
             if keep_poses:
-                kept.append((fused, gt_out, spread))
-        host = torch.cat([acc_pos, acc_p2, gap] + parts).cpu().numpy()
+                kept.append((fused, gt_out, spread) + ((fused_post,) if post is not None else ()))
+        n_part = sum(int(v.numel()) for v in parts)
+        host = torch.cat([acc_pos, acc_p2, gap] + parts + ([acc_p2_post] + post_parts + post_stats + post_short if post is not None else [])
+                         ).cpu().numpy()
         if keep_poses:
-            poses = [torch.cat([k[i] for k in kept]).cpu().numpy() for i in range(3)]
-    pos, p2, worst, part = np.split(host, [2 * t + 1, 2 * t + 1 + 3 * n_groups, 2 * t + 2 + 3 * n_groups])
+            poses = [torch.cat([k[i] for k in kept]).cpu().numpy() for i in range(3 if post is None else 4)]
+    head_n = 2 * t + 2 + 3 * n_groups
+    pos, p2, worst, part, tail = np.split(host, [2 * t + 1, 2 * t + 1 + 3 * n_groups, head_n, head_n + n_part])
     if not worst[0] == 0.0:
         raise ValueError(f"contributors of one video frame disagree on its ground truth by up to {worst[0]} m: the index entries do not "
                          "name the frames the shards hold")
@@ -337,4 +365,28 @@ def evaluate_dense(head, store, fuse: str = "context", batch_size: int = 256, ch
     if keep_poses:
         out.update(seq_keys=list(table.seq_keys), seq_start=table.seq_start.copy(), frame_idx=table.idx.copy(), pred=poses[0], gt=poses[1],
                    frame_spread=poses[2], count=np.diff(table.offsets).astype(np.int32))
+    if post is not None:
+        n_edges = len(post.edges)
+        n_stats = 3 * len(table.seq_keys) * n_edges * smooth.STAT_SLOTS
+        p2_post, part_post, stats, short = np.split(tail, [3 * n_groups, 3 * n_groups + n_part, 3 * n_groups + n_part + n_stats])
+        vals = metric_values(sum_blocks(part_post.reshape(-1, n_groups, METRIC_SLOTS)), p2_post[:2 * n_groups].reshape(n_groups, 2)[:, 1])
+        for m in ("p1", "p2", "mpjve", "accel"):
+            for suffix in ("", "_all", "_mean"):
+                out["post_" + m + suffix] = vals[m + suffix]
+        # the runs hold whole sequences in table order: run c's block is (3, S_c, E, 2)
+        by_kind, at = [[], [], []], 0
+        for chunk in chunks:
+            n = len(chunk.table.seq_keys) * n_edges * smooth.STAT_SLOTS
+            for k in range(3):
+                by_kind[k].append(stats[at + k * n: at + (k + 1) * n].reshape(-1, n_edges, smooth.STAT_SLOTS))
+            at += 3 * n
+        seq_rows = np.diff(table.seq_start)
+        for k, name in enumerate(("raw", "post", "gt")):
+            per, over = smooth.bone_std_mm(np.concatenate(by_kind[k]), seq_rows, seq_group, n_groups)
+            out["bone_std_" + name], out["bone_std_" + name + "_all"] = per, over
+        short = short.reshape(-1, 2).sum(axis=0)
+        out["post_short_rows"], out["post_short_segments"] = int(round(short[0])), int(round(short[1]))
+        out["post"] = post.describe()
+        if keep_poses:
+            out["pred_post"] = poses[3]
     return out
