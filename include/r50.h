@@ -212,7 +212,9 @@ int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* 
 
 /* Stem: fp32 NCHW frames -> conv 7x7 s2 p3 (+folded bn1 bias) + ReLU -> (n,112,112,64) bf16 NHWC.
  * w_oihw_f32: (64,3,7,7) fp32 *already folded*, host pointer; bias_f32: device pointer (64).
- * scratch_dev: at least r50_stem_scratch_bytes(n) bytes of device memory. */
+ * scratch_dev: at least r50_stem_scratch_bytes(n) bytes of device memory.
+ * Holds the host: the weights are packed into a host temporary, uploaded on `stream`, and the call synchronises `stream` once before
+ * it launches (r50_forward does not: a handle keeps its packed stem weights on the device). */
 int64_t r50_stem_scratch_bytes(int n);
 int r50_op_stem(const float* x_nchw_f32_dev, int n, const float* w_oihw_f32_host,
                 const float* bias_f32_dev, void* scratch_dev, void* y_nhwc_bf16, void* stream);
@@ -297,7 +299,9 @@ int r50_op_crop_resize_u8(const void* frames_thwc_u8, int t, int h, int w, int t
  * contiguous (may be one clip's slice of a (B,t,out_size,out_size,3) buffer).  Arithmetic of `_resize_video_hw` (:81-93): fp32
  * u8 / 255 (IEEE division), bilinear with align_corners=False and no antialias as F.interpolate's CPU path evaluates it for 3
  * channels, clamp(0,1) * 255, truncated to uint8 (not rounded: unlike both R50_RESIZE_* modes).  Any out_size >= 1.  src_idx is
- * read back once to check every index lies in [0,n) (R50_ERR_INVALID otherwise): the call synchronises `stream` once. */
+ * read back once to check every index lies in [0,n) (R50_ERR_INVALID otherwise): the call synchronises `stream` once, so it
+ * holds the host until everything queued on `stream` before it has run.  Of the r50_op_* entry points only this one and r50_op_stem
+ * do (tests/test_stream_order_gpu.py, BLOCKS_HOST). */
 int r50_op_resize_frames_u8(const void* frames_nhwc_u8, int n, int h, int w, const int* src_idx, int t, void* out_tssc_u8,
                             int out_size, void* stream);
 
