@@ -1,4 +1,4 @@
-"""ctypes binding of libr50hip.so (C ABI: include/r50.h, include/r50_hal.h and include/r50_smooth.h).
+"""ctypes binding of libr50hip.so (C ABI: include/r50.h, include/r50_hal.h, include/r50_smooth.h and include/r50_multiview.h).
 
 This is the stub a maintainer of the reference would add to call the MI355X path from
 src/preprocess_resnet_features.py.  There is NO fallback: if the shared
@@ -28,12 +28,13 @@ class TensorDesc(C.Structure):
 
 
 def _source_digest() -> str:
-    """sha256 over everything the shared library is built from: csrc/*, include/r50.h, include/r50_hal.h, include/r50_smooth.h and the
-    compiler flags."""
+    """sha256 over everything the shared library is built from: csrc/*, include/r50.h, include/r50_hal.h, include/r50_smooth.h,
+    include/r50_multiview.h and the compiler flags."""
     import hashlib
     hsh = hashlib.sha256()
     files = sorted(p for p in CSRC.iterdir() if p.suffix in (".hip", ".h", ".hpp", ".cpp")) + \
-        [PKG_DIR.parent / "include" / "r50.h", PKG_DIR.parent / "include" / "r50_hal.h", PKG_DIR.parent / "include" / "r50_smooth.h"]
+        [PKG_DIR.parent / "include" / "r50.h", PKG_DIR.parent / "include" / "r50_hal.h", PKG_DIR.parent / "include" / "r50_smooth.h",
+         PKG_DIR.parent / "include" / "r50_multiview.h"]
     for f in files:
         hsh.update(f.name.encode() + b"\0")
         hsh.update(f.read_bytes())
@@ -199,11 +200,20 @@ _SIGNATURES_SMOOTH = {
                                       C.c_void_p]),
 }
 
+# include/r50_multiview.h (the cameras of a take fused into one pose per frame): likewise
+_SIGNATURES_MULTIVIEW = {
+    "r50_op_view_rigid_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p]),
+    "r50_op_view_fuse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
 def load_library() -> C.CDLL:
-    """dlopen libr50hip.so and declare every prototype of include/r50.h, include/r50_hal.h and include/r50_smooth.h.  Raises if it is absent."""
+    """dlopen libr50hip.so and declare every prototype of include/r50.h, include/r50_hal.h, include/r50_smooth.h and include/r50_multiview.h.
+    Raises if it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -215,7 +225,7 @@ def load_library() -> C.CDLL:
         raise R50Error(f"{LIB_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
                        "There is no CPU/PyTorch fallback for this path.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_HAL, **_SIGNATURES_SMOOTH}.items():
+    for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_HAL, **_SIGNATURES_SMOOTH, **_SIGNATURES_MULTIVIEW}.items():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,13 +1,15 @@
-// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h and include/r50_smooth.h.
+// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h and include/r50_multiview.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
 #include "kernels.h"
 #include "smooth_kernels.h"
+#include "multiview_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
 #include "../../include/r50_smooth.h"
+#include "../../include/r50_multiview.h"
 
 #include <atomic>
 #include <cmath>
@@ -2554,6 +2556,29 @@ int r50_op_bone_rebuild(const float* x, const int* row_seq, int64_t F, int S, in
     hipLaunchKernelGGL(bone_rebuild_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), bone_rebuild_lds(J), (hipStream_t)stream, x, row_seq,
                        (int)F, J, ed, E, is_child, stats, out);
     return ew_done("r50_op_bone_rebuild");
+}
+
+// ---- the cameras of a take in one frame of reference, fused (include/r50_multiview.h, multiview_kernels.h) ----
+int r50_op_view_rigid_fit(const float* y, const float* x, int64_t rows_y, int64_t rows_x, int J, const int* pair_start, const int* match,
+                          int P, double* fit, void* stream) {
+    if (!y || !x || !pair_start || !match || !fit) return fail(nullptr, R50_ERR_INVALID, "r50_op_view_rigid_fit: null pointer");
+    if (rows_y < 1 || rows_y > kSmoothMaxRows || rows_x < 1 || rows_x > kSmoothMaxRows || J < 1 || J > VIEW_MAX_J || P < 1)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_view_rigid_fit: invalid arguments (need 1 <= rows_y, rows_x < 2^31 / 192, 1 <= J <= 64 and P >= 1)");
+    hipLaunchKernelGGL(view_rigid_fit_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, y, x, J, pair_start, match, fit);
+    return ew_done("r50_op_view_rigid_fit");
+}
+
+int r50_op_view_fuse(const float* pose, int64_t F, int J, const int* peer_start, const int* peer_row, const int* peer_fit, const double* fit,
+                     int P, int mode, float* fused, float* disagreement, void* stream) {
+    if (!pose || !peer_start || !peer_row || !peer_fit || !fit || !fused || !disagreement)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || J < 1 || J > VIEW_MAX_J || P < 0)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: invalid arguments (need 1 <= F < 2^31 / 192, 1 <= J <= 64 and P >= 0)");
+    if (mode < 0 || mode > 2) return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: mode must be 0 (mean), 1 (median) or 2 (others)");
+    if (overlaps(pose, fused, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: fused overlaps pose");
+    hipLaunchKernelGGL(view_fuse_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pose, (int)F, J, peer_start,
+                       peer_row, peer_fit, fit, mode, fused, disagreement);
+    return ew_done("r50_op_view_fuse");
 }
 
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,

@@ -35,7 +35,10 @@ forecast from the last observed frame alone beside the rollout's, per horizon an
 With ``--dense-smooth gauss | savgol | one_euro`` and / or ``--dense-fix-bones`` (default off; need ``--dense``; INTEGRATION.md section
 W) the stitched sequences are also filtered along time and rebuilt with constant bone lengths on the device (``smooth.PostProcess``):
 the ``Dense | post`` lines set the processed poses' errors and bone-length deviation beside the raw ones, the ``.npz`` gains the
-``dense_post_*`` keys and ``--dense-out`` gains ``pred_post``.
+``dense_post_*`` keys and ``--dense-out`` gains ``pred_post``.  With ``--multiview`` (default off; needs ``--dense``)
+the cameras of every take are brought into one frame of reference and fused into one pose per frame (``multiview.evaluate_multiview``,
+``--multiview-fit gt | pred``, ``--multiview-fuse mean | median | others``): ``Dense | multiview`` lines, ``dense_mv_*`` keys, and
+``--dense-out`` gains ``pred_mv``, ``frame_disagreement``, ``views`` and ``mv_pair_*``.
 
 Two differences from running the reference's script as it stands:
 
@@ -151,6 +154,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also give every bone its sequence's mean length, after the filter (--dense; INTEGRATION.md section W)")
     from .smooth import add_parameter_flags
     add_parameter_flags(p)
+    from .multiview import add_flags as add_multiview_flags
+    add_multiview_flags(p)
     return p
 
 
@@ -193,6 +198,14 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         if hasattr(args, flag) and not args.dense:
             p.error(f"--{flag.replace('_', '-')} needs --dense")
     dense_post(args, p.error)                # a parameter flag without its filter, or a refused parameter
+    from .multiview import OPTION_FLAGS as MULTIVIEW_FLAGS
+    if hasattr(args, "multiview") and not args.dense:
+        p.error("--multiview needs --dense")
+    for flag in MULTIVIEW_FLAGS:
+        if hasattr(args, flag) and not hasattr(args, "multiview"):
+            p.error(f"--{flag.replace('_', '-')} needs --multiview")
+    if not getattr(args, "multiview_gt_tol_mm", 1.0) > 0:
+        p.error(f"--multiview-gt-tol-mm must be > 0, got {args.multiview_gt_tol_mm}")
     if args.dtw and args.pred_len <= 0:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
@@ -678,14 +691,19 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in detail_lines(detail, args.input_len, args.pred_len):
             print(line)
 
-    dense = None
+    dense, multi = None, None
     if args.dense:                           # every video frame once: the clips of a sequence fused per frame
         from .sequences import evaluate_dense
-        post = dense_post(args)
-        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse, keep_poses=args.dense_out is not None,
+        from . import multiview as mv
+        post, mv_options = dense_post(args), mv.options_from_args(args)
+        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse, keep_poses=args.dense_out is not None or mv_options is not None,
                                **({} if post is None else {"post": post}))
         for line in dense_lines(dense) + (dense_post_lines(dense) if post is not None else []):
             print(line)
+        if mv_options is not None:           # the cameras of every take fused, scored beside the single views (section X)
+            multi = mv.evaluate_multiview(dense, device, **mv_options)
+            for line in mv.multiview_lines(dense, multi):
+                print(line)
 
     dtw = None
     if args.dtw:                             # the protocols' pass over the forecasts: every test clip once, in store order
@@ -759,9 +777,11 @@ def main(argv: Optional[List[str]] = None) -> str:
         extra.update(detail_npz(detail))
     if dense is not None:
         extra.update(dense_npz(dense))
+        if multi is not None:
+            extra.update(mv.multiview_npz(multi))
         if args.dense_out is not None:
             os.makedirs(os.path.dirname(args.dense_out) or ".", exist_ok=True)
-            np.savez_compressed(args.dense_out, **dense_export(dense))
+            np.savez_compressed(args.dense_out, **dense_export(dense), **({} if multi is None else mv.multiview_export(multi)))
             print(f"Dense | stitched sequences saved to: {args.dense_out}")
     if dtw is not None:
         extra.update(dtw_arrays(dtw))
