@@ -1,15 +1,18 @@
-// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h and include/r50_multiview.h.
+// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h and
+// include/r50_kinematics.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
 #include "kernels.h"
 #include "smooth_kernels.h"
 #include "multiview_kernels.h"
+#include "kinematics_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
 #include "../../include/r50_smooth.h"
 #include "../../include/r50_multiview.h"
+#include "../../include/r50_kinematics.h"
 
 #include <atomic>
 #include <cmath>
@@ -2556,6 +2559,111 @@ int r50_op_bone_rebuild(const float* x, const int* row_seq, int64_t F, int S, in
     hipLaunchKernelGGL(bone_rebuild_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), bone_rebuild_lds(J), (hipStream_t)stream, x, row_seq,
                        (int)F, J, ed, E, is_child, stats, out);
     return ew_done("r50_op_bone_rebuild");
+}
+
+// ---- joint rotations on a rigid skeleton (include/r50_kinematics.h, kinematics_kernels.h) ----
+// The host skeleton tables, checked: on success `sk` is filled, else the reason is returned.
+static const char* check_kin_skeleton(int J, const int* edges, int E, const int* frames, int NF, const double* rest_dirs, const double* sign,
+                                      KinSkeleton& sk) {
+    if (E != J - 1) return "edges: need E == J - 1 (one root)";
+    if (NF < 0 || NF > J) return "frames: need 0 <= NF <= J";
+    std::memset(&sk, 0, sizeof(sk));
+    unsigned long long is_child = 0;
+    if (E > 0) {
+        BoneEdges ed;
+        if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return why;
+        for (int q = 0; q < E; ++q) sk.parent[q] = ed.parent[q], sk.child[q] = ed.child[q];
+    }
+    int children[KIN_MAX_J] = {0};
+    sk.root = -1;
+    for (int j = 0; j < J; ++j) {
+        sk.par_of[j] = 255;
+        if (!((is_child >> j) & 1ull)) sk.root = j;                                 // E == J - 1 distinct children: exactly one
+    }
+    for (int q = 0; q < E; ++q) {
+        sk.par_of[sk.child[q]] = sk.parent[q];
+        if (++children[sk.parent[q]] == 1) sk.arg[sk.parent[q]] = sk.child[q];
+    }
+    for (int j = 0; j < J; ++j) sk.kind[j] = children[j] == 1 ? KIN_AIM : KIN_INHERIT;
+    unsigned long long framed = 0;
+    for (int q = 0; q < NF; ++q) {
+        const int* f = frames + 5 * q;
+        for (int k = 0; k < 5; ++k)
+            if (f[k] < 0 || f[k] >= J) return "frames: every index must be in [0, J)";
+        if (f[1] == f[2] || f[3] == f[4]) return "frames: a0 != a1 and b0 != b1 are needed";
+        if ((framed >> f[0]) & 1ull) return "frames: a joint may be framed once only";
+        framed |= 1ull << f[0];
+        sk.kind[f[0]] = KIN_FRAMED;
+        sk.arg[f[0]] = (unsigned char)q;
+        for (int k = 0; k < 4; ++k) sk.fr[q][k] = (unsigned char)f[1 + k];
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!(sign[k] == 1.0 || sign[k] == -1.0)) return "sign: every entry must be +1 or -1";
+        sk.sign[k] = sign[k];
+    }
+    if (sign[0] * sign[1] * sign[2] != 1.0) return "sign: the product must be +1";
+    for (int j = 0; j < J; ++j) {
+        if (j == sk.root) continue;
+        const double* v = rest_dirs + 3 * j;
+        const double n2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+        if (!(std::fabs(n2 - 1.0) <= 1e-12)) return "rest_dirs: a unit vector is needed for every joint but the root";
+        for (int k = 0; k < 3; ++k) sk.dirs[j][k] = v[k];
+    }
+    return nullptr;
+}
+
+struct KinRange { const void* p; long long bytes; };
+static bool kin_any_overlap(const KinRange* in, int n_in, const KinRange* out, int n_out) {
+    for (int o = 0; o < n_out; ++o) {
+        const char* o0 = (const char*)out[o].p;
+        for (int i = 0; i < n_in + o; ++i) {                                       // every input, and every earlier output
+            const KinRange& r = i < n_in ? in[i] : out[i - n_in];
+            const char* r0 = (const char*)r.p;
+            if (o0 < r0 + r.bytes && r0 < o0 + out[o].bytes) return true;
+        }
+    }
+    return false;
+}
+
+int r50_op_rest_offsets(const float* x, const int* seq_start, int64_t F, int S, int J, const int* edges, int E, const int* frames, int NF,
+                        const double* rest_dirs, const double* sign, double* rest, void* stream) {
+    if (!x || !seq_start || !rest_dirs || !sign || !rest || (!edges && E > 0) || (!frames && NF > 0))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rest_offsets: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > KIN_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_rest_offsets: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
+    KinSkeleton sk;
+    if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk))
+        return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_rest_offsets: ") + why);
+    const KinRange in[2] = {{x, F * 3 * J * (long long)sizeof(float)}, {seq_start, ((long long)S + 1) * (long long)sizeof(int)}};
+    const KinRange out[1] = {{rest, (long long)S * 3 * J * (long long)sizeof(double)}};
+    if (kin_any_overlap(in, 2, out, 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_rest_offsets: rest overlaps an input");
+    hipLaunchKernelGGL(rest_offsets_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, x, seq_start, J, sk, rest);
+    return ew_done("r50_op_rest_offsets");
+}
+
+int r50_op_pose_rotations(const float* x, const int* row_seq, int64_t F, int S, int J, const int* edges, int E, const int* frames, int NF,
+                          const double* rest_dirs, const double* sign, const double* rest, float* quat, float* euler, float* rigid,
+                          float* resid, int* flags, void* stream) {
+    if (!x || !row_seq || !rest_dirs || !sign || !rest || !quat || !euler || !rigid || !resid || !flags || (!edges && E > 0) ||
+        (!frames && NF > 0))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > KIN_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
+    KinSkeleton sk;
+    if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk))
+        return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_rotations: ") + why);
+    if (!aligned16(quat)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: quat must be 16-byte aligned");
+    const long long fj = F * J * (long long)sizeof(float);
+    const KinRange in[3] = {{x, 3 * fj}, {row_seq, F * (long long)sizeof(int)}, {rest, (long long)S * 3 * J * (long long)sizeof(double)}};
+    const KinRange out[5] = {{quat, 4 * fj}, {euler, 3 * fj}, {rigid, 3 * fj}, {resid, F * (long long)sizeof(float)},
+                             {flags, F * (long long)sizeof(int)}};
+    if (kin_any_overlap(in, 3, out, 5)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: an output overlaps an input or another output");
+    const size_t lds = pose_rot_lds(J);
+    if (lds > 65536) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: the LDS budget does not hold");
+    const int rb = pose_rot_rows(J);
+    hipLaunchKernelGGL(pose_rotations_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), lds, (hipStream_t)stream, x, row_seq, (int)F, J,
+                       sk, rest, quat, euler, rigid, resid, flags);
+    return ew_done("r50_op_pose_rotations");
 }
 
 // ---- the cameras of a take in one frame of reference, fused (include/r50_multiview.h, multiview_kernels.h) ----

@@ -369,6 +369,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="give every bone its mean length over the video, after the filter (INTEGRATION.md section W)")
     from .smooth import add_parameter_flags
     add_parameter_flags(p)
+    p.add_argument("--bvh", action="store_true", default=argparse.SUPPRESS,
+                   help="also joint rotations on a rigid skeleton (INTEGRATION.md section Y): NAME.bvh beside NAME_poses.npz, which gains "
+                        "the rotations, the rest offsets and the rigid reconstruction")
+    from .kinematics import add_bvh_flags
+    add_bvh_flags(p)
     return p
 
 
@@ -377,6 +382,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p = build_parser()
     args = p.parse_args(argv)
     video_post(args, p.error)
+    from .kinematics import bvh_options
+    for flag in ("bvh_fps", "bvh_scale"):
+        if hasattr(args, flag) and not hasattr(args, "bvh"):
+            p.error(f"--{flag.replace('_', '-')} needs --bvh")
+    bvh_options(args, p.error)
     return args
 
 
@@ -438,11 +448,18 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     from .backbone import ResNet50Backbone
     from .preprocess_resnet_features import _resolve_weights
     from .results import build_head, load_head_state
+    head_state = load_head_state(args.model_path, args.weights_from)
+    bvh = hasattr(args, "bvh")
+    if bvh:
+        from . import kinematics
+        from .results import infer_head_dims
+        kinematics.skeleton_for(infer_head_dims(head_state)[1])    # another joint count has no built-in skeleton: refused before any launch
+        bvh_fps, bvh_scale = kinematics.bvh_options(args, None)
     items = [load_input(p) for p in args.frames]
     state_dict, source = _resolve_weights(args)
     print(f"backbone weights: {source}")
     backbone = ResNet50Backbone(state_dict=state_dict, max_batch=args.frame_batch, precision=args.precision).to(device).eval()
-    head = build_head(load_head_state(args.model_path, args.weights_from), backbone._device, args.head_precision)
+    head = build_head(head_state, backbone._device, args.head_precision)
     predictor = VideoPredictor(backbone, head, args.seq_len, args.stride, args.fuse, args.frame_batch, args.window_batch,
                                RESIZE_MODES[args.resize_mode], args.flip_tta)
     os.makedirs(args.out, exist_ok=True)
@@ -454,10 +471,18 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
                                 **({} if post is None else {"post": post}))
         stats = res.pop("stats")
         out_path = os.path.join(args.out, name + "_poses.npz")
+        rigid_note = ""
+        if bvh:                              # after the optional --smooth / --fix-bones: the poses the file holds, as one sequence
+            res.update(kinematics.video_rotations(res["joints3d"], device))
+            rigid_note = (f", rigid skeleton: mean residual {float(res['rigid_residual'].mean()):.6f} "
+                          f"({int(np.count_nonzero(res['rigid_flags']))} flagged frames)")
         np.savez(out_path, **res, **{k: np.int64(v) for k, v in stats.items()})
         written.append(out_path)
         print(f"{name}: {res['joints3d'].shape[0]} poses from {stats['backbone_frames']} backbone frames, {stats['windows']} windows "
-              f"({stats['head_rows']} head rows) -> {out_path}")
+              f"({stats['head_rows']} head rows) -> {out_path}" + rigid_note)
+        if bvh:
+            written.append(kinematics.write_video_bvh(os.path.join(args.out, name + ".bvh"), res, None, bvh_fps, bvh_scale))
+            print(f"{name}: BVH written to: {written[-1]}")
         if args.render:
             written += render_prediction(os.path.join(args.out, name + "_render"), predictor, item["frames"], res, args.render_frames,
                                          args.render_fps)

@@ -38,7 +38,10 @@ the ``Dense | post`` lines set the processed poses' errors and bone-length devia
 ``dense_post_*`` keys and ``--dense-out`` gains ``pred_post``.  With ``--multiview`` (default off; needs ``--dense``)
 the cameras of every take are brought into one frame of reference and fused into one pose per frame (``multiview.evaluate_multiview``,
 ``--multiview-fit gt | pred``, ``--multiview-fuse mean | median | others``): ``Dense | multiview`` lines, ``dense_mv_*`` keys, and
-``--dense-out`` gains ``pred_mv``, ``frame_disagreement``, ``views`` and ``mv_pair_*``.
+``--dense-out`` gains ``pred_mv``, ``frame_disagreement``, ``views`` and ``mv_pair_*``.  With ``--dense-rigid`` (default off; needs
+``--dense``) every stitched sequence is also fitted with joint rotations on a rigid skeleton
+(``kinematics.evaluate_rigid``): ``Dense | rigid`` lines set the rigid reconstruction's errors beside the poses', the ``.npz`` gains the
+``dense_rigid_*`` keys, and ``--dense-bvh DIR`` writes one BVH file per sequence.
 
 Two differences from running the reference's script as it stands:
 
@@ -156,6 +159,13 @@ def build_parser() -> argparse.ArgumentParser:
     add_parameter_flags(p)
     from .multiview import add_flags as add_multiview_flags
     add_multiview_flags(p)
+    p.add_argument("--dense-rigid", action="store_true", default=argparse.SUPPRESS,
+                   help="also fit joint rotations on a rigid skeleton to every stitched sequence and score the rigid reconstruction "
+                        "beside the poses it was fitted to (--dense; INTEGRATION.md section Y)")
+    p.add_argument("--dense-bvh", type=str, default=argparse.SUPPRESS, metavar="DIR",
+                   help="write one BVH file per sequence into DIR (--dense-rigid)")
+    from .kinematics import add_bvh_flags
+    add_bvh_flags(p)
     return p
 
 
@@ -206,6 +216,15 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--{flag.replace('_', '-')} needs --multiview")
     if not getattr(args, "multiview_gt_tol_mm", 1.0) > 0:
         p.error(f"--multiview-gt-tol-mm must be > 0, got {args.multiview_gt_tol_mm}")
+    if hasattr(args, "dense_rigid") and not args.dense:
+        p.error("--dense-rigid needs --dense")
+    if hasattr(args, "dense_bvh") and not hasattr(args, "dense_rigid"):
+        p.error("--dense-bvh needs --dense-rigid")
+    for flag in ("bvh_fps", "bvh_scale"):
+        if hasattr(args, flag) and not hasattr(args, "dense_bvh"):
+            p.error(f"--{flag.replace('_', '-')} needs --dense-bvh")
+    from .kinematics import bvh_options
+    bvh_options(args, p.error)
     if args.dtw and args.pred_len <= 0:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
@@ -691,12 +710,17 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in detail_lines(detail, args.input_len, args.pred_len):
             print(line)
 
-    dense, multi = None, None
+    dense, multi, rigid = None, None, None
     if args.dense:                           # every video frame once: the clips of a sequence fused per frame
         from .sequences import evaluate_dense
         from . import multiview as mv
         post, mv_options = dense_post(args), mv.options_from_args(args)
-        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse, keep_poses=args.dense_out is not None or mv_options is not None,
+        want_rigid = hasattr(args, "dense_rigid")
+        if want_rigid:
+            from . import kinematics
+            kinematics.skeleton_for(int(head.joints_num))        # refused before the pass if there is no skeleton for the head's joints
+        dense = evaluate_dense(head, test_set, fuse=args.dense_fuse,
+                               keep_poses=args.dense_out is not None or mv_options is not None or want_rigid,
                                **({} if post is None else {"post": post}))
         for line in dense_lines(dense) + (dense_post_lines(dense) if post is not None else []):
             print(line)
@@ -704,6 +728,13 @@ def main(argv: Optional[List[str]] = None) -> str:
             multi = mv.evaluate_multiview(dense, device, **mv_options)
             for line in mv.multiview_lines(dense, multi):
                 print(line)
+        if want_rigid:                       # joint rotations on a rigid skeleton, the reconstruction scored beside the poses (section Y)
+            rigid = kinematics.evaluate_rigid(dense, None, device, keep=hasattr(args, "dense_bvh"))
+            for line in kinematics.rigid_lines(dense, rigid):
+                print(line)
+            if hasattr(args, "dense_bvh"):
+                files = kinematics.write_dense_bvh(args.dense_bvh, dense, rigid, None, *kinematics.bvh_options(args, None))
+                print(f"Dense | rigid   {len(files)} BVH files written to: {args.dense_bvh}")
 
     dtw = None
     if args.dtw:                             # the protocols' pass over the forecasts: every test clip once, in store order
@@ -779,6 +810,8 @@ def main(argv: Optional[List[str]] = None) -> str:
         extra.update(dense_npz(dense))
         if multi is not None:
             extra.update(mv.multiview_npz(multi))
+        if rigid is not None:
+            extra.update(kinematics.rigid_npz(rigid))
         if args.dense_out is not None:
             os.makedirs(os.path.dirname(args.dense_out) or ".", exist_ok=True)
             np.savez_compressed(args.dense_out, **dense_export(dense), **({} if multi is None else mv.multiview_export(multi)))
