@@ -21,13 +21,12 @@ forecasts are one gather launch (``r50_op_baseline_forecasts``); the scorers are
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
-from . import protocols
+from . import _lib, clip_pass, protocols
 from .forecast import add_horizon_metrics, metrics_from_sums
 from .protocols import ROOT_JOINT
 
@@ -168,8 +167,7 @@ class StripDatabase:
         dev = head._device
         with torch.cuda.device(dev):
             keys = torch.empty((len(store), head.latent_dim), dtype=head._dtype, device=dev)
-            for s in range(0, len(store), batch_size):
-                e = min(s + batch_size, len(store))
+            for s, e in clip_pass.spans(len(store), batch_size):
                 keys[s:e].copy_(head.observe(store.get_batch(list(range(s, e)))[0], i_len)[0][:, i_len - 1])
             joints = store.joints3d if store.joints3d.dtype == torch.float32 and store.joints3d.is_contiguous() \
                 else store.joints3d.to(torch.float32).contiguous()
@@ -222,40 +220,24 @@ def evaluate_baselines(head, store, db: Optional[StripDatabase], groups: Sequenc
     if anchor not in ANCHORS:
         raise ValueError(f"anchor: expected one of {ANCHORS}, got {anchor!r}")
     n_groups = len(group_names)
-    i_len, p_len = int(input_len), int(pred_len)
-    seq_len = int(store.feats.shape[1])
-    if len(groups) != len(store):
-        raise ValueError(f"groups has {len(groups)} ids for {len(store)} items")
-    if n_groups < 1:
-        raise ValueError("no groups")
-    ids = np.asarray(groups, dtype=np.int64)
-    if ids.size and (ids.min() < 0 or ids.max() >= n_groups):
-        raise ValueError(f"group ids must lie in [0, {n_groups})")
-    if i_len < 1 or p_len < 1 or i_len + p_len > seq_len:
-        raise ValueError(f"need input_len, pred_len >= 1 and input_len + pred_len <= seq_len {seq_len} (got {i_len}, {p_len})")
+    ids, i_len, p_len, _ = clip_pass.check(store, input_len, pred_len, batch_size, groups, n_groups)
     if "const_vel" in which and i_len < 2:
         raise ValueError("const_vel needs input_len >= 2: it continues the last observed step")
     if "nn" in which and (db is None or not 1 <= int(nn_k) <= min(MAX_K, len(db))):
         raise ValueError(f"nn needs a StripDatabase and 1 <= nn_k <= min({MAX_K}, its clips)")
-    if batch_size < 1:
-        raise ValueError("batch_size must be >= 1")
     names = ("model",) + which
     dev = head._device
     n_h, n_p = 2 * p_len + 1, 2 * n_groups * p_len + n_groups
     with torch.cuda.device(dev):
-        gdev = torch.tensor(ids, dtype=torch.int32, device=dev)
         acc_h = torch.zeros((len(names), n_h), dtype=torch.float64, device=dev)
         acc_p = torch.zeros((len(names), n_p), dtype=torch.float64, device=dev)
         dist = torch.zeros(1, dtype=torch.float64, device=dev)
-        for s in range(0, len(store), batch_size):
-            e = min(s + batch_size, len(store))
-            batch = store.get_batch(list(range(s, e)))
-            gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-            preds = forecast_batch(head, db, batch[0], gt, i_len, p_len, which, nn_k, anchor)
-            preds["model"] = head.rollout(batch[0], i_len, p_len)[1]
+        for feats, gt, group in clip_pass.batches(head, store, batch_size, ids):
+            preds = forecast_batch(head, db, feats, gt, i_len, p_len, which, nn_k, anchor)
+            preds["model"] = head.rollout(feats, i_len, p_len)[1]
             for r, name in enumerate(names):
                 add_horizon_metrics(preds[name], gt, i_len, acc_h[r])
-                protocols._launch(preds[name], gt, i_len, gdev[s:e], n_groups, acc_p[r], ROOT_JOINT)
+                protocols._launch(preds[name], gt, i_len, group, n_groups, acc_p[r], ROOT_JOINT)
             if "nn" in which:
                 dist += preds["nn_dist2"].double().sum()
         sums = torch.cat([acc_h.reshape(-1), acc_p.reshape(-1), dist]).cpu().numpy()
@@ -266,4 +248,40 @@ def evaluate_baselines(head, store, db: Optional[StripDatabase], groups: Sequenc
         out[name] = {"mpjpe": np.asarray(hm["mpjpe"], dtype=np.float64), "p1": all_[:, 0].copy(), "p2": all_[:, 1].copy(), "per_action": per}
         out["clips"] = clips.round().astype(np.int64)
     out["nn_dist2_mean"] = float(sums[-1]) / (len(store) * int(nn_k)) if "nn" in which else float("nan")
+    return out
+
+
+def baseline_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--baselines`` from an ``evaluate_baselines`` result: the ``Baselines`` header, then one indented line per
+    predictor, ``model`` first: MPJPE, P1 and P2 in mm at horizons 1, 5, 10 and P and their mean over the horizons, and for each
+    baseline the model's skill ``1 - model / baseline`` on the P1 mean (positive: the model beats it)."""
+    hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+    head = (f"Baselines | input {input_len} | pred {pred_len} | clips {int(np.sum(res['clips']))} | anchor {res['anchor']} | predictors "
+            f"{len(res['names'])}")
+    if "nn" in res["names"]:
+        head += f" | nn k {int(res['nn_k'])} | nn strip dist2 mean {res['nn_dist2_mean']:.6g}"
+    lines = [head]
+    model_p1 = float(np.mean(res["model"]["p1"]))
+    for name in res["names"]:
+        row = res[name]
+        parts = [f"{key} (mm) " + " | ".join(f"@{h}: {row[key][h - 1] * 1000.0:.2f}" for h in hs) + f" | mean: {np.mean(row[key]) * 1000.0:.2f}"
+                 for key in ("mpjpe", "p1", "p2")]
+        line = f"  {name} | " + " | ".join(parts)
+        if name != "model":
+            base_p1 = float(np.mean(row["p1"]))
+            line += f" | model skill on p1: {(1.0 - model_p1 / base_p1) if base_p1 > 0 else float('nan'):+.4f}"
+        lines.append(line)
+    return lines
+
+
+def baseline_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--baselines``: ``baseline_names`` (Nb,) str, ``model`` first; fp32 ``baseline_mpjpe``, ``baseline_p1``,
+    ``baseline_p2`` (Nb, P) in metres; ``baseline_actions`` (G,) str; ``baseline_per_action`` (Nb, G, P, 2) fp32 [p1, p2];
+    ``baseline_anchor`` str.  (``main`` adds ``nn_index``, ``nn_dist2`` and ``nn_future3djoints`` of the dumped clips.)"""
+    names = list(res["names"])
+    out = {"baseline_names": np.array(names, dtype=str), "baseline_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "baseline_anchor": np.array(str(res["anchor"])),
+           "baseline_per_action": np.stack([np.asarray(res[n]["per_action"], dtype=np.float32) for n in names])}
+    for key in ("mpjpe", "p1", "p2"):
+        out["baseline_" + key] = np.stack([np.asarray(res[n][key], dtype=np.float32) for n in names])
     return out

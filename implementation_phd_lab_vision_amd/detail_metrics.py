@@ -23,8 +23,8 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import _lib
-from .protocols import MAX_JOINTS, ROOT_JOINT
+from . import _lib, clip_pass, protocols
+from .protocols import ROOT_JOINT
 
 MAX_THRESHOLDS = 1024                         # r50_op_pose_detail_metrics' limit on n_thr
 N_THR = 31                                    # MPI-INF-3DHP: AUC over 0 .. 150 mm in 31 steps
@@ -50,29 +50,13 @@ def acc_size(n_groups: int, p: int, joints: int) -> int:
 def _launch(pred: torch.Tensor, gt: torch.Tensor, i0: int, group: torch.Tensor, n_groups: int, acc: torch.Tensor, root: int, n_thr: int,
             thr_max: float) -> None:
     """Shape, dtype and device checks (those of ``protocols._launch``), then one launch; the group VALUES are the caller's to check."""
-    if pred.dim() != 4 or gt.dim() != 4:
-        raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) expected, got {tuple(pred.shape)}, {tuple(gt.shape)}")
-    b, p, j, _ = pred.shape
-    t = gt.shape[1]
-    if tuple(gt.shape) != (b, t, j, 3) or pred.shape[3] != 3 or pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) fp32 expected, got {tuple(pred.shape)} {pred.dtype}, {tuple(gt.shape)} {gt.dtype}")
-    if not 1 <= j <= MAX_JOINTS or not 0 <= root < j:
-        raise ValueError(f"need 1 <= J <= {MAX_JOINTS} and 0 <= root < J (got J={j}, root={root})")
+    b, p, t, j = protocols.check_poses(pred, gt, root)
     if b < 1 or p < 1 or i0 < 0 or i0 + p > t:
         raise ValueError(f"need B, P >= 1 and 0 <= i0, i0 + P <= T (got B={b}, P={p}, i0={i0}, T={t})")
-    if n_groups < 1:
-        raise ValueError("n_groups must be >= 1")
     if not 2 <= n_thr <= MAX_THRESHOLDS or not (np.isfinite(thr_max) and thr_max > 0):
         raise ValueError(f"need 2 <= n_thr <= {MAX_THRESHOLDS} and a finite thr_max > 0 (got {n_thr}, {thr_max})")
-    if group.dtype != torch.int32 or tuple(group.shape) != (b,):
-        raise ValueError(f"group must be ({b},) int32, got {tuple(group.shape)} {group.dtype}")
-    n_acc = acc_size(n_groups, p, j)
-    if acc.dtype != torch.float64 or acc.numel() != n_acc or not acc.is_contiguous():
-        raise ValueError(f"acc must be {n_acc} contiguous fp64 values")
-    if pred.device.type != "cuda" or not (pred.device == gt.device == group.device == acc.device):
-        raise ValueError("pred, gt, group and acc must be on one GPU: there is no CPU fallback")
-    if not (pred.is_contiguous() and gt.is_contiguous() and group.is_contiguous()):
-        raise ValueError("pred, gt and group must be contiguous")
+    protocols.check_group_acc(b, group, n_groups, acc, acc_size(n_groups, p, j))
+    protocols.check_one_gpu(pred, gt, group, acc)
     rc = _lib.load_library().r50_op_pose_detail_metrics(pred.data_ptr(), gt.data_ptr(), group.data_ptr(), b, p, t, int(i0), j, int(root),
                                                         int(n_groups), int(n_thr), float(thr_max), acc.data_ptr(),
                                                         torch.cuda.current_stream(pred.device).cuda_stream)
@@ -86,10 +70,7 @@ def add_detail_sums(pred: torch.Tensor, gt: torch.Tensor, i0: int, group: torch.
     Layout, with A = 2*G*P*J: ``acc[((g*P + k)*J + j)*2 + {0,1}]`` += the d1, d2 sums; ``acc[A + (g*P + k)*6 + {0,1,2,3}]`` += the hits
     of d1 over all thresholds, of d1 at thr_max, the same two of d2; ``acc[A + (g*P + k)*6 + {4,5}]`` += the velocity and acceleration
     error sums over joints where defined; ``acc[A + 6*G*P + g]`` += the clips of g."""
-    if isinstance(group, torch.Tensor) and group.numel() > 0 and group.dtype == torch.int32:
-        lo, hi = (int(v) for v in torch.stack([group.min(), group.max()]).cpu())
-        if lo < 0 or hi >= n_groups:
-            raise ValueError(f"group ids must lie in [0, {n_groups}), got [{lo}, {hi}]")
+    protocols.check_group_values(group, n_groups)
     _launch(pred, gt, int(i0), group, int(n_groups), acc, int(root), int(n_thr), float(thr_max))
 
 
@@ -142,33 +123,16 @@ def evaluate_detail(head, store, groups: Sequence[int], group_names: Sequence[st
     A group without clips gets NaN and stays out of the means.  ``head``'s mode and weights are not touched.  One launch per batch
     and span, the sums read back once per pass."""
     n_groups = len(group_names)
-    i_len, p_len = int(input_len), int(pred_len)
-    seq_len = int(store.feats.shape[1])
-    if len(groups) != len(store):
-        raise ValueError(f"groups has {len(groups)} ids for {len(store)} items")
-    if n_groups < 1:
-        raise ValueError("no groups")
-    ids = np.asarray(groups, dtype=np.int64)
-    if ids.size and (ids.min() < 0 or ids.max() >= n_groups):
-        raise ValueError(f"group ids must lie in [0, {n_groups})")
-    if p_len < 0 or (p_len > 0 and (i_len < 1 or i_len + p_len > seq_len)):
-        raise ValueError(f"need pred_len >= 0 and, with pred_len > 0, 1 <= input_len and input_len + pred_len <= seq_len {seq_len} "
-                         f"(got {i_len}, {p_len})")
-    if batch_size < 1:
-        raise ValueError("batch_size must be >= 1")
+    ids, i_len, p_len, seq_len = clip_pass.check(store, input_len, pred_len, batch_size, groups, n_groups, forecast_required=False)
     joints = int(head.joints_num)
     dev = head._device
     with torch.cuda.device(dev):
-        gdev = torch.tensor(ids, dtype=torch.int32, device=dev)
         acc_r = torch.zeros(acc_size(n_groups, seq_len, joints), dtype=torch.float64, device=dev)
         acc_f = torch.zeros(acc_size(n_groups, p_len, joints) if p_len else 0, dtype=torch.float64, device=dev)
-        for s in range(0, len(store), batch_size):
-            e = min(s + batch_size, len(store))
-            batch = store.get_batch(list(range(s, e)))
-            gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-            _launch(head.joints(batch[0]), gt, 0, gdev[s:e], n_groups, acc_r, ROOT_JOINT, n_thr, thr_max)
+        for feats, gt, group in clip_pass.batches(head, store, batch_size, ids):
+            _launch(head.joints(feats), gt, 0, group, n_groups, acc_r, ROOT_JOINT, n_thr, thr_max)
             if p_len:
-                _launch(head.rollout(batch[0], i_len, p_len)[1], gt, i_len, gdev[s:e], n_groups, acc_f, ROOT_JOINT, n_thr, thr_max)
+                _launch(head.rollout(feats, i_len, p_len)[1], gt, i_len, group, n_groups, acc_f, ROOT_JOINT, n_thr, thr_max)
         sums = torch.cat([acc_r, acc_f]).cpu().numpy()
     rec = values(sums[:acc_r.numel()], n_groups, seq_len, joints, n_thr)
     has = rec["clips"] > 0
@@ -185,4 +149,61 @@ def evaluate_detail(head, store, groups: Sequence[int], group_names: Sequence[st
             out[f"future_{m}"] = fut[m]
             out[f"future_{m}_all"] = fut[m + "_all"]
             out[f"future_{m}_mean"] = fut[m][has].mean(axis=0)
+    return out
+
+
+def _pair(v, scale: float) -> str:
+    """``raw / pa`` of a [root-relative, after the similarity fit] pair."""
+    return f"{v[0] * scale:.2f} / pa {v[1] * scale:.2f}"
+
+
+def detail_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--detail-metrics`` from an ``evaluate_detail`` result: the ``Detail metrics`` line (all clips and the
+    action mean: PCK and AUC in percent, raw and after the similarity fit; velocity and acceleration errors in mm per frame and mm per
+    frame^2), one ``Per-joint`` line (P1 / P2 in mm per joint name, all clips), one indented line per action, and with ``pred_len > 0``
+    the ``Rollout detail metrics`` line at horizons 1, 5, 10 and P (``-`` where a motion error is not defined)."""
+    clips = res["clips"]
+    at_mm = f"pck@{res['thr_max'] * 1000.0:g}"
+
+    def summary(which: str, key: str = "") -> str:
+        g = lambda m: res[f"{which}_{m}{key}"]                        # noqa: E731
+        return (f"{at_mm} (%) {_pair(g('pck'), 100.0)} | auc (%) {_pair(g('auc'), 100.0)} | vel (mm/frame) {g('vel') * 1000.0:.2f} "
+                f"| accel (mm/frame^2) {g('acc') * 1000.0:.2f}")
+
+    lines = [f"Detail metrics | clips {int(clips.sum())} | actions {len(res['group_names'])} | all: {summary('recon', '_all')} "
+             f"| action mean: {summary('recon', '_mean')}"]
+    pj = res["recon_per_joint_all"]
+    lines.append("Per-joint p1 / p2 (mm) | " + " | ".join(f"{name} {pj[j, 0] * 1000.0:.2f} / {pj[j, 1] * 1000.0:.2f}"
+                                                           for j, name in enumerate(res["joint_names"])))
+    for i, (name, c) in enumerate(zip(res["group_names"], clips)):
+        row = {m: res[f"recon_{m}"][i] for m in ("pck", "auc", "vel", "acc")}
+        lines.append(f"  {name} | clips {int(c)} | {at_mm} (%) {_pair(row['pck'], 100.0)} | auc (%) {_pair(row['auc'], 100.0)} "
+                     f"| vel (mm/frame) {row['vel'] * 1000.0:.2f} | accel (mm/frame^2) {row['acc'] * 1000.0:.2f}")
+    if pred_len > 0:
+        hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+        num = lambda v, scale: "-" if np.isnan(v) else f"{v * scale:.2f}"                  # noqa: E731
+        parts = []
+        for label, key in ((f"{at_mm} (%)", "pck"), ("auc (%)", "auc")):
+            fa = res[f"future_{key}_all"]
+            parts.append(f"{label} " + " | ".join(f"@{h}: {_pair(fa[h - 1], 100.0)}" for h in hs))
+        for label, key in (("vel (mm/frame)", "vel"), ("accel (mm/frame^2)", "acc")):
+            fa = res[f"future_{key}_all"]
+            parts.append(f"{label} " + " | ".join(f"@{h}: {num(fa[h - 1], 1000.0)}" for h in hs))
+        lines.append(f"Rollout detail metrics | input {input_len} | pred {pred_len} | clips {int(clips.sum())} | " + " | ".join(parts))
+    return lines
+
+
+def detail_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--detail-metrics``: ``detail_actions`` (G,) and ``detail_joint_names`` (J,) str, ``detail_clips`` (G,)
+    int64, and fp32 ``detail_recon_M`` (G, ...) / ``detail_recon_M_all`` (...) for M in per_joint (J, 2), p1p2 (2,), pck (2,), auc (2,),
+    vel (), acc () -- metres, metres per frame, metres per frame^2, shares in [0, 1]; [.., 2] = [root-relative, after the fit]; with a
+    rollout ``detail_future_M`` (G, P, ...) and ``detail_future_M_all`` (P, ...)."""
+    out = {"detail_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "detail_joint_names": np.array([str(n) for n in res["joint_names"]], dtype=str),
+           "detail_clips": np.asarray(res["clips"], dtype=np.int64)}
+    for which in ("recon", "future"):
+        for m in ("per_joint", "p1p2", "pck", "auc", "vel", "acc"):
+            for key in (f"{which}_{m}", f"{which}_{m}_all"):
+                if key in res:
+                    out["detail_" + key] = np.asarray(res[key], dtype=np.float32)
     return out

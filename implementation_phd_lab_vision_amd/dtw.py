@@ -24,14 +24,13 @@ workgroup per group) adds into an fp64 device accumulator that is read once per 
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
-from . import protocols
-from .protocols import MAX_JOINTS, ROOT_JOINT
+from . import _lib, clip_pass, protocols
+from .protocols import ROOT_JOINT
 
 MAX_LEN = 64                                  # r50_op_dtw_protocols' limit on P and Q
 
@@ -45,34 +44,19 @@ def _launch(pred: torch.Tensor, gt: torch.Tensor, i0: int, q: int, group: torch.
             root: int, clip_out: Optional[torch.Tensor], path_out: Optional[torch.Tensor]) -> torch.Tensor:
     """Shape, dtype and device checks (in the style of ``protocols._launch``), then one call; the group VALUES are the caller's to have
     checked.  Returns the per-clip records (``clip_out``, or a fresh tensor)."""
-    if pred.dim() != 4 or gt.dim() != 4:
-        raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) expected, got {tuple(pred.shape)}, {tuple(gt.shape)}")
-    b, p, j, _ = pred.shape
-    t = gt.shape[1]
-    if tuple(gt.shape) != (b, t, j, 3) or pred.shape[3] != 3 or pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) fp32 expected, got {tuple(pred.shape)} {pred.dtype}, {tuple(gt.shape)} {gt.dtype}")
-    if not 1 <= j <= MAX_JOINTS or not 0 <= root < j:
-        raise ValueError(f"need 1 <= J <= {MAX_JOINTS} and 0 <= root < J (got J={j}, root={root})")
+    b, p, t, j = protocols.check_poses(pred, gt, root)
     if b < 1 or not 1 <= p <= MAX_LEN or not 1 <= q <= MAX_LEN or i0 < 0 or i0 + q > t:
         raise ValueError(f"need B >= 1, 1 <= P, Q <= {MAX_LEN} and 0 <= i0, i0 + Q <= T (got B={b}, P={p}, Q={q}, i0={i0}, T={t})")
     if 0 <= band < abs(p - q):
         raise ValueError(f"a band >= 0 must be >= |P - Q| = {abs(p - q)}, got {band}")
-    if n_groups < 1:
-        raise ValueError("n_groups must be >= 1")
-    if group.dtype != torch.int32 or tuple(group.shape) != (b,):
-        raise ValueError(f"group must be ({b},) int32, got {tuple(group.shape)} {group.dtype}")
-    if acc.dtype != torch.float64 or acc.numel() != acc_size(n_groups, p) or not acc.is_contiguous():
-        raise ValueError(f"acc must be {acc_size(n_groups, p)} contiguous fp64 values")
+    protocols.check_group_acc(b, group, n_groups, acc, acc_size(n_groups, p))
     if clip_out is not None and (clip_out.dtype != torch.float64 or tuple(clip_out.shape) != (b, 2, 2 + 3 * p)
                                  or not clip_out.is_contiguous() or clip_out.device != pred.device):
         raise ValueError(f"clip_out must be ({b}, 2, {2 + 3 * p}) contiguous fp64 on pred's device")
     if path_out is not None and (path_out.dtype != torch.int32 or tuple(path_out.shape) != (b, 2, p + q - 1, 2)
                                  or not path_out.is_contiguous() or path_out.device != pred.device):
         raise ValueError(f"path_out must be ({b}, 2, {p + q - 1}, 2) contiguous int32 on pred's device")
-    if pred.device.type != "cuda" or not (pred.device == gt.device == group.device == acc.device):
-        raise ValueError("pred, gt, group and acc must be on one GPU: there is no CPU fallback")
-    if not (pred.is_contiguous() and gt.is_contiguous() and group.is_contiguous()):
-        raise ValueError("pred, gt and group must be contiguous")
+    protocols.check_one_gpu(pred, gt, group, acc)
     if clip_out is None:
         clip_out = torch.empty((b, 2, 2 + 3 * p), dtype=torch.float64, device=pred.device)
     rc = _lib.load_library().r50_op_dtw_protocols(pred.data_ptr(), gt.data_ptr(), group.data_ptr(), b, p, t, int(i0), int(q), j, int(root),
@@ -92,10 +76,7 @@ def add_dtw_sums(pred: torch.Tensor, gt: torch.Tensor, i0: int, q: int, group: t
     ``acc[(g*2 + m)*V + 1 + P + k]`` += lag_sum[k] / cells[k], ``acc[2*G*V + g]`` += the clips of g.  ``clip_out`` (B, 2, 2 + 3P) fp64
     receives ``[total, L, cost_sum[P], cells[P], lag_sum[P]]`` per clip and metric and is returned (a fresh tensor when None);
     ``path_out`` (B, 2, P+Q-1, 2) int32, if given, the paths' (i, j) pairs from (0, 0) onward, -1 past L."""
-    if isinstance(group, torch.Tensor) and group.numel() > 0 and group.dtype == torch.int32:
-        lo, hi = (int(v) for v in torch.stack([group.min(), group.max()]).cpu())
-        if lo < 0 or hi >= n_groups:
-            raise ValueError(f"group ids must lie in [0, {n_groups}), got [{lo}, {hi}]")
+    protocols.check_group_values(group, n_groups)
     return _launch(pred, gt, int(i0), int(q), group, int(n_groups), acc, int(band), int(root), clip_out, path_out)
 
 
@@ -132,32 +113,15 @@ def evaluate_dtw(head, store, groups: Sequence[int], group_names: Sequence[str],
 
     A group without clips gets NaN and stays out of the mean.  The accumulators are read back once per pass."""
     n_groups = len(group_names)
-    i_len, p_len = int(input_len), int(pred_len)
-    seq_len = int(store.feats.shape[1])
-    if len(groups) != len(store):
-        raise ValueError(f"groups has {len(groups)} ids for {len(store)} items")
-    if n_groups < 1:
-        raise ValueError("no groups")
-    ids = np.asarray(groups, dtype=np.int64)
-    if ids.size and (ids.min() < 0 or ids.max() >= n_groups):
-        raise ValueError(f"group ids must lie in [0, {n_groups})")
-    if not 1 <= p_len <= MAX_LEN or i_len < 1 or i_len + p_len > seq_len:
-        raise ValueError(f"need 1 <= pred_len <= {MAX_LEN}, 1 <= input_len and input_len + pred_len <= seq_len {seq_len} "
-                         f"(got {i_len}, {p_len})")
-    if batch_size < 1:
-        raise ValueError("batch_size must be >= 1")
+    ids, i_len, p_len, _ = clip_pass.check(store, input_len, pred_len, batch_size, groups, n_groups, max_pred_len=MAX_LEN)
     dev = head._device
     with torch.cuda.device(dev):
-        gdev = torch.tensor(ids, dtype=torch.int32, device=dev)
         acc = torch.zeros(acc_size(n_groups, p_len), dtype=torch.float64, device=dev)
         acc_plain = torch.zeros(2 * n_groups * p_len + n_groups, dtype=torch.float64, device=dev)
-        for s in range(0, len(store), batch_size):
-            e = min(s + batch_size, len(store))
-            batch = store.get_batch(list(range(s, e)))
-            gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-            pred = head.rollout(batch[0], i_len, p_len)[1]
-            _launch(pred, gt, i_len, p_len, gdev[s:e], n_groups, acc, int(band), ROOT_JOINT, None, None)
-            protocols._launch(pred, gt, i_len, gdev[s:e], n_groups, acc_plain, ROOT_JOINT)
+        for feats, gt, group in clip_pass.batches(head, store, batch_size, ids):
+            pred = head.rollout(feats, i_len, p_len)[1]
+            _launch(pred, gt, i_len, p_len, group, n_groups, acc, int(band), ROOT_JOINT, None, None)
+            protocols._launch(pred, gt, i_len, group, n_groups, acc_plain, ROOT_JOINT)
         sums = torch.cat([acc, acc_plain]).cpu().numpy()
     d, da, f, fa, lag, la, clips = _values(sums[:acc.numel()], n_groups, p_len)
     plain_all = protocols._values(sums[acc.numel():], n_groups, p_len)[1]
@@ -165,3 +129,34 @@ def evaluate_dtw(head, store, groups: Sequence[int], group_names: Sequence[str],
     return {"group_names": list(group_names), "clips": clips.round().astype(np.int64), "band": int(band), "dtw": d, "dtw_all": da,
             "dtw_mean": d[has].mean(axis=0), "dtw_future": f, "dtw_future_all": fa, "lag": lag, "lag_all": la,
             "plain_future_all": plain_all, "plain_all": plain_all.mean(axis=0)}
+
+
+def dtw_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--dtw`` from an ``evaluate_dtw`` result: the ``DTW metrics`` line (all clips: the warped P1 / P2 and, after
+    ``plain``, the unwarped horizon means of the same rollouts), one indented line per action, and the ``DTW horizons`` line with the
+    warped error in mm and the lag in frames (signed: positive = the prediction is slow) at horizons 1, 5, 10 and P."""
+    clips = res["clips"]
+    da, pa = res["dtw_all"], res["plain_all"]
+    band = "none" if res["band"] < 0 else str(int(res["band"]))
+    lines = [f"DTW metrics | input {input_len} | pred {pred_len} | band {band} | clips {int(clips.sum())} | all: p1 (mm) {da[0] * 1000.0:.2f} "
+             f"| p2 (mm) {da[1] * 1000.0:.2f} | plain p1 (mm) {pa[0] * 1000.0:.2f} | p2 (mm) {pa[1] * 1000.0:.2f}"]
+    for name, c, (p1, p2) in zip(res["group_names"], clips, res["dtw"]):
+        lines.append(f"  {name} | clips {int(c)} | dtw p1 (mm) {p1 * 1000.0:.2f} | dtw p2 (mm) {p2 * 1000.0:.2f}")
+    hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+    fa, la = res["dtw_future_all"], res["lag_all"]
+    parts = [f"p{m + 1} (mm) " + " | ".join(f"@{h}: {fa[h - 1, m] * 1000.0:.2f}" for h in hs) for m in (0, 1)]
+    parts += [f"lag p{m + 1} (frames) " + " | ".join(f"@{h}: {la[h - 1, m]:+.2f}" for h in hs) for m in (0, 1)]
+    lines.append("DTW horizons | " + " | ".join(parts))
+    return lines
+
+
+def dtw_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--dtw``: ``dtw_actions`` (G,) str, ``dtw_clips`` (G,) int64, ``dtw_band`` () int64, and fp32 ``dtw`` (G, 2),
+    ``dtw_all`` (2,), ``dtw_future`` (G, P, 2), ``dtw_future_all`` (P, 2) in metres and ``dtw_lag`` (G, P, 2), ``dtw_lag_all`` (P, 2) in
+    frames; [.., 2] = [p1, p2]."""
+    out = {"dtw_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "dtw_clips": np.asarray(res["clips"], dtype=np.int64), "dtw_band": np.array(int(res["band"]), dtype=np.int64)}
+    for key, src in (("dtw", "dtw"), ("dtw_all", "dtw_all"), ("dtw_future", "dtw_future"), ("dtw_future_all", "dtw_future_all"),
+                     ("dtw_lag", "lag"), ("dtw_lag_all", "lag_all")):
+        out[key] = np.asarray(res[src], dtype=np.float32)
+    return out

@@ -17,7 +17,8 @@ from typing import Dict, List, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, clip_pass
+from .protocols import check_poses
 
 INPUT_LEN = 15             # src/config.py
 PRED_LEN = 25
@@ -40,10 +41,7 @@ def metrics_from_sums(acc: Sequence[float], pred_len: int, joints: int) -> Dict[
 def add_horizon_metrics(pred: torch.Tensor, gt: torch.Tensor, input_len: int, acc: torch.Tensor) -> None:
     """acc (2P+1) fp64 on the device += the sums of one batch: pred (B, P, J, 3) fp32 predicts frames input_len .. input_len+P-1 of
     gt (B, T, J, 3) fp32."""
-    b, p, j, _ = pred.shape
-    t = gt.shape[1]
-    if tuple(gt.shape) != (b, t, j, 3) or pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) fp32 expected, got {tuple(pred.shape)} {pred.dtype}, {tuple(gt.shape)} {gt.dtype}")
+    b, p, t, j = check_poses(pred, gt)
     if acc.dtype != torch.float64 or acc.numel() != 2 * p + 1 or not acc.is_contiguous():
         raise ValueError(f"acc must be {2 * p + 1} contiguous fp64 values")
     if not (pred.is_contiguous() and gt.is_contiguous()) or not (pred.device == gt.device == acc.device):
@@ -59,21 +57,11 @@ def evaluate_rollout(head, store, input_len: int = INPUT_LEN, pred_len: int = PR
     kept even if short.  Returns ``{"mpjpe": [P], "l3d": [P], "mpjpe_mean": float, "clips": int}`` (metres, as the store's joints).
     The default of 256 clips is deliberate: at 32 clips the per-step GEMMs have 480-1248 rows, under a third of the chip's CUs.
     ``head`` is any ``PHDFor3DJoints`` (a training head included); its mode and weights are not touched."""
-    i_len, p_len = int(input_len), int(pred_len)
-    seq_len = int(store.feats.shape[1])
-    if i_len < 1 or p_len < 1:
-        raise ValueError(f"evaluate_rollout needs input_len >= 1 and pred_len >= 1 (got {i_len}, {p_len})")
-    if i_len + p_len > seq_len:
-        raise ValueError(f"input_len + pred_len = {i_len + p_len} exceeds the store's seq_len {seq_len}")
-    if batch_size < 1:
-        raise ValueError("batch_size must be >= 1")
+    _, i_len, p_len, _ = clip_pass.check(store, input_len, pred_len, batch_size)
     dev = head._device
     with torch.cuda.device(dev):
         acc = torch.zeros(2 * p_len + 1, dtype=torch.float64, device=dev)
-        for s in range(0, len(store), batch_size):
-            batch = store.get_batch(list(range(s, min(s + batch_size, len(store)))))
-            gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-            _, joints = head.rollout(batch[0], i_len, p_len)
-            add_horizon_metrics(joints, gt, i_len, acc)
+        for feats, gt, _ in clip_pass.batches(head, store, batch_size):
+            add_horizon_metrics(head.rollout(feats, i_len, p_len)[1], gt, i_len, acc)
         sums = acc.tolist()
     return metrics_from_sums(sums, p_len, head.joints_num)

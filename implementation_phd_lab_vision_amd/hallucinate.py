@@ -17,7 +17,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import protocols
+from . import clip_pass, protocols
 from .forecast import add_horizon_metrics, metrics_from_sums
 from .protocols import ROOT_JOINT
 
@@ -47,23 +47,10 @@ def evaluate_hallucinator(head, store, groups: Sequence[int], group_names: Seque
     ``recon["model"]`` is ``joints(feats)``, ``recon["hal"]`` is ``hallucinate(feats)[1]``; the forecast's ``model`` rows are
     ``evaluate_baselines``' ``model`` rows exactly (the same launches into the same sums).  The head's mode and weights are not
     touched."""
+    n_groups = len(group_names)
+    ids, i_len, p_len, seq_len = clip_pass.check(store, input_len, pred_len, batch_size, groups, n_groups, forecast_required=False)
     if not getattr(head, "hallucinator", False):
         raise ValueError(NO_HALLUCINATOR)
-    n_groups = len(group_names)
-    i_len, p_len = int(input_len), int(pred_len)
-    seq_len = int(store.feats.shape[1])
-    if len(groups) != len(store):
-        raise ValueError(f"groups has {len(groups)} ids for {len(store)} items")
-    if n_groups < 1:
-        raise ValueError("no groups")
-    ids = np.asarray(groups, dtype=np.int64)
-    if ids.size and (ids.min() < 0 or ids.max() >= n_groups):
-        raise ValueError(f"group ids must lie in [0, {n_groups})")
-    if p_len < 0 or (p_len > 0 and (i_len < 1 or i_len + p_len > seq_len)):
-        raise ValueError(f"need pred_len >= 0 and, with pred_len > 0, 1 <= input_len and input_len + pred_len <= seq_len {seq_len} "
-                         f"(got {i_len}, {p_len})")
-    if batch_size < 1:
-        raise ValueError("batch_size must be >= 1")
     dev = head._device
 
     def sizes(p: int):
@@ -72,22 +59,18 @@ def evaluate_hallucinator(head, store, groups: Sequence[int], group_names: Seque
     rh, rp = sizes(seq_len)
     fh, fp = sizes(p_len) if p_len else (0, 0)
     with torch.cuda.device(dev):
-        gdev = torch.tensor(ids, dtype=torch.int32, device=dev)
         acc = {"rh": torch.zeros((2, rh), dtype=torch.float64, device=dev), "rp": torch.zeros((2, rp), dtype=torch.float64, device=dev),
                "fh": torch.zeros((2, fh), dtype=torch.float64, device=dev), "fp": torch.zeros((2, fp), dtype=torch.float64, device=dev)}
-        for s in range(0, len(store), batch_size):
-            e = min(s + batch_size, len(store))
-            batch = store.get_batch(list(range(s, e)))
-            gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-            recon = {"model": head.joints(batch[0]), "hal": head.hallucinate(batch[0])[1]}
+        for feats, gt, group in clip_pass.batches(head, store, batch_size, ids):
+            recon = {"model": head.joints(feats), "hal": head.hallucinate(feats)[1]}
             for r, name in enumerate(NAMES):
                 add_horizon_metrics(recon[name], gt, 0, acc["rh"][r])
-                protocols._launch(recon[name], gt, 0, gdev[s:e], n_groups, acc["rp"][r], ROOT_JOINT)
+                protocols._launch(recon[name], gt, 0, group, n_groups, acc["rp"][r], ROOT_JOINT)
             if p_len:
-                preds = {"model": head.rollout(batch[0], i_len, p_len)[1], "hal": head.hallucinated_rollout(batch[0], i_len - 1, p_len)[1]}
+                preds = {"model": head.rollout(feats, i_len, p_len)[1], "hal": head.hallucinated_rollout(feats, i_len - 1, p_len)[1]}
                 for r, name in enumerate(NAMES):
                     add_horizon_metrics(preds[name], gt, i_len, acc["fh"][r])
-                    protocols._launch(preds[name], gt, i_len, gdev[s:e], n_groups, acc["fp"][r], ROOT_JOINT)
+                    protocols._launch(preds[name], gt, i_len, group, n_groups, acc["fp"][r], ROOT_JOINT)
         host = {k: v.cpu().numpy() for k, v in acc.items()}
 
     def rows(hsum: np.ndarray, psum: np.ndarray, p: int) -> Dict[str, np.ndarray]:
@@ -109,7 +92,7 @@ def _ratio(a: float, b: float) -> str:
 
 
 def hallucinate_lines(res: Dict[str, object]) -> List[str]:
-    """The printed lines of ``--hallucinate`` from an ``evaluate_hallucinator`` result, after ``results.baseline_lines``: the
+    """The printed lines of ``--hallucinate`` from an ``evaluate_hallucinator`` result, after ``baselines.baseline_lines``: the
     ``Hallucinator`` header; per predictor (``model`` = with temporal context, ``hal`` = from one frame) the reconstruction's MPJPE / P1 /
     P2 in mm, the mean over the clip's frames, ``hal`` with the ratio hal / model on P1; one line per action; and with a forecast the
     same per horizon (1, 5, 10, P and the mean) and per action.  Millimetres."""

@@ -19,12 +19,12 @@ kernel solves each pose's fit in Horn's quaternion form with a bounded fp64 Jaco
 from __future__ import annotations
 
 import re
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, clip_pass
 
 ROOT_JOINT = 0                                # the pelvis (src/dataset.py: joint 0 is the root)
 MAX_JOINTS = 64                               # r50_op_pose_protocols' limit
@@ -45,29 +45,53 @@ def action_groups(names: Sequence) -> Tuple[List[str], List[int]]:
     return group_names, [pos[a] for a in actions]
 
 
-def _launch(pred: torch.Tensor, gt: torch.Tensor, i0: int, group: torch.Tensor, n_groups: int, acc: torch.Tensor, root: int) -> None:
-    """Shape, dtype and device checks, then one launch; the group VALUES are the caller's to have checked."""
+def check_poses(pred: torch.Tensor, gt: torch.Tensor, root: Optional[int] = None) -> Tuple[int, int, int, int]:
+    """The first checks of every op that scores pred (B, P, J, 3) against gt (B, T, J, 3): rank, shapes and fp32 and, with ``root``, the
+    grouped pose ops' ``J <= MAX_JOINTS`` and ``0 <= root < J``.  Returns (B, P, T, J)."""
     if pred.dim() != 4 or gt.dim() != 4:
         raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) expected, got {tuple(pred.shape)}, {tuple(gt.shape)}")
     b, p, j, _ = pred.shape
     t = gt.shape[1]
     if tuple(gt.shape) != (b, t, j, 3) or pred.shape[3] != 3 or pred.dtype != torch.float32 or gt.dtype != torch.float32:
         raise ValueError(f"pred (B,P,J,3) and gt (B,T,J,3) fp32 expected, got {tuple(pred.shape)} {pred.dtype}, {tuple(gt.shape)} {gt.dtype}")
-    if not 1 <= j <= MAX_JOINTS or not 0 <= root < j:
+    if root is not None and (not 1 <= j <= MAX_JOINTS or not 0 <= root < j):
         raise ValueError(f"need 1 <= J <= {MAX_JOINTS} and 0 <= root < J (got J={j}, root={root})")
-    if b < 1 or p < 1 or i0 < 0 or i0 + p > t:
-        raise ValueError(f"need B, P >= 1 and 0 <= i0, i0 + P <= T (got B={b}, P={p}, i0={i0}, T={t})")
+    return b, p, t, j
+
+
+def check_group_acc(b: int, group: torch.Tensor, n_groups: int, acc: torch.Tensor, n_acc: int) -> None:
+    """The grouped pose ops' checks after their own limits: ``n_groups``, group (B,) int32 and acc ``n_acc`` contiguous fp64."""
     if n_groups < 1:
         raise ValueError("n_groups must be >= 1")
     if group.dtype != torch.int32 or tuple(group.shape) != (b,):
         raise ValueError(f"group must be ({b},) int32, got {tuple(group.shape)} {group.dtype}")
-    n_acc = 2 * n_groups * p + n_groups
     if acc.dtype != torch.float64 or acc.numel() != n_acc or not acc.is_contiguous():
         raise ValueError(f"acc must be {n_acc} contiguous fp64 values")
+
+
+def check_one_gpu(pred: torch.Tensor, gt: torch.Tensor, group: torch.Tensor, acc: torch.Tensor) -> None:
+    """The grouped pose ops' last checks, after their own output buffers: one GPU, then contiguity."""
     if pred.device.type != "cuda" or not (pred.device == gt.device == group.device == acc.device):
         raise ValueError("pred, gt, group and acc must be on one GPU: there is no CPU fallback")
     if not (pred.is_contiguous() and gt.is_contiguous() and group.is_contiguous()):
         raise ValueError("pred, gt and group must be contiguous")
+
+
+def check_group_values(group, n_groups: int) -> None:
+    """The host-side check of the ``add_*_sums`` wrappers: every value of an int32 ``group`` lies in [0, n_groups) (one read)."""
+    if isinstance(group, torch.Tensor) and group.numel() > 0 and group.dtype == torch.int32:
+        lo, hi = (int(v) for v in torch.stack([group.min(), group.max()]).cpu())
+        if lo < 0 or hi >= n_groups:
+            raise ValueError(f"group ids must lie in [0, {n_groups}), got [{lo}, {hi}]")
+
+
+def _launch(pred: torch.Tensor, gt: torch.Tensor, i0: int, group: torch.Tensor, n_groups: int, acc: torch.Tensor, root: int) -> None:
+    """Shape, dtype and device checks, then one launch; the group VALUES are the caller's to have checked."""
+    b, p, t, j = check_poses(pred, gt, root)
+    if b < 1 or p < 1 or i0 < 0 or i0 + p > t:
+        raise ValueError(f"need B, P >= 1 and 0 <= i0, i0 + P <= T (got B={b}, P={p}, i0={i0}, T={t})")
+    check_group_acc(b, group, n_groups, acc, 2 * n_groups * p + n_groups)
+    check_one_gpu(pred, gt, group, acc)
     rc = _lib.load_library().r50_op_pose_protocols(pred.data_ptr(), gt.data_ptr(), group.data_ptr(), b, p, t, int(i0), j, int(root),
                                                    int(n_groups), acc.data_ptr(), torch.cuda.current_stream(pred.device).cuda_stream)
     _lib.check(rc, None, "r50_op_pose_protocols")
@@ -78,10 +102,7 @@ def add_protocol_sums(pred: torch.Tensor, gt: torch.Tensor, i0: int, group: torc
     """acc (2*G*P + G) fp64 on the device += the sums of one batch: pred (B, P, J, 3) fp32 scores frames i0 .. i0+P-1 of gt
     (B, T, J, 3) fp32; group (B,) int32 on the device, each value in [0, n_groups) (checked on the host before the launch: one
     read).  ``acc[(g*P + k)*2 + 0]`` += the P1 sum, ``acc[(g*P + k)*2 + 1]`` += the P2 sum, ``acc[2*G*P + g]`` += the clips of g."""
-    if isinstance(group, torch.Tensor) and group.numel() > 0 and group.dtype == torch.int32:
-        lo, hi = (int(v) for v in torch.stack([group.min(), group.max()]).cpu())
-        if lo < 0 or hi >= n_groups:
-            raise ValueError(f"group ids must lie in [0, {n_groups}), got [{lo}, {hi}]")
+    check_group_values(group, n_groups)
     _launch(pred, gt, int(i0), group, int(n_groups), acc, int(root))
 
 
@@ -111,32 +132,15 @@ def evaluate_protocols(head, store, groups: Sequence[int], group_names: Sequence
     A group without clips gets NaN and stays out of the means.  ``head`` is any ``PHDFor3DJoints``; its mode and weights are not
     touched.  The sums are read back once per pass."""
     n_groups = len(group_names)
-    i_len, p_len = int(input_len), int(pred_len)
-    seq_len = int(store.feats.shape[1])
-    if len(groups) != len(store):
-        raise ValueError(f"groups has {len(groups)} ids for {len(store)} items")
-    if n_groups < 1:
-        raise ValueError("no groups")
-    ids = np.asarray(groups, dtype=np.int64)
-    if ids.size and (ids.min() < 0 or ids.max() >= n_groups):
-        raise ValueError(f"group ids must lie in [0, {n_groups})")
-    if p_len < 0 or (p_len > 0 and (i_len < 1 or i_len + p_len > seq_len)):
-        raise ValueError(f"need pred_len >= 0 and, with pred_len > 0, 1 <= input_len and input_len + pred_len <= seq_len {seq_len} "
-                         f"(got {i_len}, {p_len})")
-    if batch_size < 1:
-        raise ValueError("batch_size must be >= 1")
+    ids, i_len, p_len, seq_len = clip_pass.check(store, input_len, pred_len, batch_size, groups, n_groups, forecast_required=False)
     dev = head._device
     with torch.cuda.device(dev):
-        gdev = torch.tensor(ids, dtype=torch.int32, device=dev)
         acc_r = torch.zeros(2 * n_groups * seq_len + n_groups, dtype=torch.float64, device=dev)
         acc_f = torch.zeros(2 * n_groups * p_len + n_groups if p_len else 0, dtype=torch.float64, device=dev)
-        for s in range(0, len(store), batch_size):
-            e = min(s + batch_size, len(store))
-            batch = store.get_batch(list(range(s, e)))
-            gt = batch[1].to(device=dev, dtype=torch.float32).contiguous()
-            _launch(head.joints(batch[0]), gt, 0, gdev[s:e], n_groups, acc_r, ROOT_JOINT)
+        for feats, gt, group in clip_pass.batches(head, store, batch_size, ids):
+            _launch(head.joints(feats), gt, 0, group, n_groups, acc_r, ROOT_JOINT)
             if p_len:
-                _launch(head.rollout(batch[0], i_len, p_len)[1], gt, i_len, gdev[s:e], n_groups, acc_f, ROOT_JOINT)
+                _launch(head.rollout(feats, i_len, p_len)[1], gt, i_len, group, n_groups, acc_f, ROOT_JOINT)
         sums = torch.cat([acc_r, acc_f]).cpu().numpy()
     rec, rec_all, clips = _values(sums[:acc_r.numel()], n_groups, seq_len)
     has = clips > 0
@@ -146,4 +150,37 @@ def evaluate_protocols(head, store, groups: Sequence[int], group_names: Sequence
     if p_len:
         fut, fut_all, _ = _values(sums[acc_r.numel():], n_groups, p_len)
         out.update(future=fut, future_all=fut_all, future_mean=fut[has].mean(axis=0))
+    return out
+
+
+def protocol_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
+    """The printed lines of ``--protocols`` from an ``evaluate_protocols`` result: the ``Protocol metrics`` line (all clips and the
+    action mean), one indented line per action, and with ``pred_len > 0`` the ``Rollout protocol metrics`` line (all clips, horizons
+    1, 5, 10 and P as the ``Rollout metrics`` line).  Millimetres."""
+    clips = res["clips"]
+    ra, rm = res["recon_all"], res["recon_mean"]
+    lines = [f"Protocol metrics | clips {int(clips.sum())} | actions {len(res['group_names'])} | all: p1 (mm) {ra[0] * 1000.0:.2f} "
+             f"| p2 (mm) {ra[1] * 1000.0:.2f} | action mean: p1 (mm) {rm[0] * 1000.0:.2f} | p2 (mm) {rm[1] * 1000.0:.2f}"]
+    for name, c, (p1, p2) in zip(res["group_names"], clips, res["recon"]):
+        lines.append(f"  {name} | clips {int(c)} | p1 (mm) {p1 * 1000.0:.2f} | p2 (mm) {p2 * 1000.0:.2f}")
+    if pred_len > 0:
+        fa = res["future_all"]
+        hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
+        at = [" | ".join(f"@{h}: {fa[h - 1, m] * 1000.0:.2f}" for h in hs) for m in (0, 1)]
+        lines.append(f"Rollout protocol metrics | input {input_len} | pred {pred_len} | clips {int(clips.sum())} | p1 (mm) {at[0]} "
+                     f"| p2 (mm) {at[1]}")
+    return lines
+
+
+def protocol_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--protocols``: ``protocol_actions`` (G,) str, ``protocol_clips`` (G,) int64, ``protocol_recon`` (G, 2)
+    and ``protocol_recon_all`` (2,) fp32 [p1, p2] in metres; with a rollout ``protocol_future`` (G, P, 2), ``protocol_future_all``
+    (P, 2)."""
+    out = {"protocol_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "protocol_clips": np.asarray(res["clips"], dtype=np.int64),
+           "protocol_recon": np.asarray(res["recon"], dtype=np.float32),
+           "protocol_recon_all": np.asarray(res["recon_all"], dtype=np.float32)}
+    if "future" in res:
+        out["protocol_future"] = np.asarray(res["future"], dtype=np.float32)
+        out["protocol_future_all"] = np.asarray(res["future_all"], dtype=np.float32)
     return out

@@ -41,7 +41,8 @@ the cameras of every take are brought into one frame of reference and fused into
 ``--dense-out`` gains ``pred_mv``, ``frame_disagreement``, ``views`` and ``mv_pair_*``.  With ``--dense-rigid`` (default off; needs
 ``--dense``) every stitched sequence is also fitted with joint rotations on a rigid skeleton
 (``kinematics.evaluate_rigid``): ``Dense | rigid`` lines set the rigid reconstruction's errors beside the poses', the ``.npz`` gains the
-``dense_rigid_*`` keys, and ``--dense-bvh DIR`` writes one BVH file per sequence.
+``dense_rigid_*`` keys, and ``--dense-bvh DIR`` writes one BVH file per sequence.  Every report's printed lines and ``.npz`` keys
+(``*_lines``, ``*_arrays`` / ``*_npz``) are defined in the module that computes it; ``main`` only calls them in order.
 
 Two differences from running the reference's script as it stands:
 
@@ -413,244 +414,10 @@ def dump_videos(metas: Sequence[dict], preprocessed_root: str, reader: Callable,
     return np.stack(host_clips, axis=0)
 
 
-def protocol_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
-    """The printed lines of ``--protocols`` from an ``evaluate_protocols`` result: the ``Protocol metrics`` line (all clips and the
-    action mean), one indented line per action, and with ``pred_len > 0`` the ``Rollout protocol metrics`` line (all clips, horizons
-    1, 5, 10 and P as the ``Rollout metrics`` line).  Millimetres."""
-    clips = res["clips"]
-    ra, rm = res["recon_all"], res["recon_mean"]
-    lines = [f"Protocol metrics | clips {int(clips.sum())} | actions {len(res['group_names'])} | all: p1 (mm) {ra[0] * 1000.0:.2f} "
-             f"| p2 (mm) {ra[1] * 1000.0:.2f} | action mean: p1 (mm) {rm[0] * 1000.0:.2f} | p2 (mm) {rm[1] * 1000.0:.2f}"]
-    for name, c, (p1, p2) in zip(res["group_names"], clips, res["recon"]):
-        lines.append(f"  {name} | clips {int(c)} | p1 (mm) {p1 * 1000.0:.2f} | p2 (mm) {p2 * 1000.0:.2f}")
-    if pred_len > 0:
-        fa = res["future_all"]
-        hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
-        at = [" | ".join(f"@{h}: {fa[h - 1, m] * 1000.0:.2f}" for h in hs) for m in (0, 1)]
-        lines.append(f"Rollout protocol metrics | input {input_len} | pred {pred_len} | clips {int(clips.sum())} | p1 (mm) {at[0]} "
-                     f"| p2 (mm) {at[1]}")
-    return lines
-
-
-def protocol_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
-    """The ``.npz`` keys of ``--protocols``: ``protocol_actions`` (G,) str, ``protocol_clips`` (G,) int64, ``protocol_recon`` (G, 2)
-    and ``protocol_recon_all`` (2,) fp32 [p1, p2] in metres; with a rollout ``protocol_future`` (G, P, 2), ``protocol_future_all``
-    (P, 2)."""
-    out = {"protocol_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
-           "protocol_clips": np.asarray(res["clips"], dtype=np.int64),
-           "protocol_recon": np.asarray(res["recon"], dtype=np.float32),
-           "protocol_recon_all": np.asarray(res["recon_all"], dtype=np.float32)}
-    if "future" in res:
-        out["protocol_future"] = np.asarray(res["future"], dtype=np.float32)
-        out["protocol_future_all"] = np.asarray(res["future_all"], dtype=np.float32)
-    return out
-
-
-def _pair(v, scale: float) -> str:
-    """``raw / pa`` of a [root-relative, after the similarity fit] pair."""
-    return f"{v[0] * scale:.2f} / pa {v[1] * scale:.2f}"
-
-
-def detail_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
-    """The printed lines of ``--detail-metrics`` from an ``evaluate_detail`` result: the ``Detail metrics`` line (all clips and the
-    action mean: PCK and AUC in percent, raw and after the similarity fit; velocity and acceleration errors in mm per frame and mm per
-    frame^2), one ``Per-joint`` line (P1 / P2 in mm per joint name, all clips), one indented line per action, and with ``pred_len > 0``
-    the ``Rollout detail metrics`` line at horizons 1, 5, 10 and P (``-`` where a motion error is not defined)."""
-    clips = res["clips"]
-    at_mm = f"pck@{res['thr_max'] * 1000.0:g}"
-
-    def summary(which: str, key: str = "") -> str:
-        g = lambda m: res[f"{which}_{m}{key}"]                        # noqa: E731
-        return (f"{at_mm} (%) {_pair(g('pck'), 100.0)} | auc (%) {_pair(g('auc'), 100.0)} | vel (mm/frame) {g('vel') * 1000.0:.2f} "
-                f"| accel (mm/frame^2) {g('acc') * 1000.0:.2f}")
-
-    lines = [f"Detail metrics | clips {int(clips.sum())} | actions {len(res['group_names'])} | all: {summary('recon', '_all')} "
-             f"| action mean: {summary('recon', '_mean')}"]
-    pj = res["recon_per_joint_all"]
-    lines.append("Per-joint p1 / p2 (mm) | " + " | ".join(f"{name} {pj[j, 0] * 1000.0:.2f} / {pj[j, 1] * 1000.0:.2f}"
-                                                           for j, name in enumerate(res["joint_names"])))
-    for i, (name, c) in enumerate(zip(res["group_names"], clips)):
-        row = {m: res[f"recon_{m}"][i] for m in ("pck", "auc", "vel", "acc")}
-        lines.append(f"  {name} | clips {int(c)} | {at_mm} (%) {_pair(row['pck'], 100.0)} | auc (%) {_pair(row['auc'], 100.0)} "
-                     f"| vel (mm/frame) {row['vel'] * 1000.0:.2f} | accel (mm/frame^2) {row['acc'] * 1000.0:.2f}")
-    if pred_len > 0:
-        hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
-        num = lambda v, scale: "-" if np.isnan(v) else f"{v * scale:.2f}"                  # noqa: E731
-        parts = []
-        for label, key in ((f"{at_mm} (%)", "pck"), ("auc (%)", "auc")):
-            fa = res[f"future_{key}_all"]
-            parts.append(f"{label} " + " | ".join(f"@{h}: {_pair(fa[h - 1], 100.0)}" for h in hs))
-        for label, key in (("vel (mm/frame)", "vel"), ("accel (mm/frame^2)", "acc")):
-            fa = res[f"future_{key}_all"]
-            parts.append(f"{label} " + " | ".join(f"@{h}: {num(fa[h - 1], 1000.0)}" for h in hs))
-        lines.append(f"Rollout detail metrics | input {input_len} | pred {pred_len} | clips {int(clips.sum())} | " + " | ".join(parts))
-    return lines
-
-
-def detail_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
-    """The ``.npz`` keys of ``--detail-metrics``: ``detail_actions`` (G,) and ``detail_joint_names`` (J,) str, ``detail_clips`` (G,)
-    int64, and fp32 ``detail_recon_M`` (G, ...) / ``detail_recon_M_all`` (...) for M in per_joint (J, 2), p1p2 (2,), pck (2,), auc (2,),
-    vel (), acc () -- metres, metres per frame, metres per frame^2, shares in [0, 1]; [.., 2] = [root-relative, after the fit]; with a
-    rollout ``detail_future_M`` (G, P, ...) and ``detail_future_M_all`` (P, ...)."""
-    out = {"detail_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
-           "detail_joint_names": np.array([str(n) for n in res["joint_names"]], dtype=str),
-           "detail_clips": np.asarray(res["clips"], dtype=np.int64)}
-    for which in ("recon", "future"):
-        for m in ("per_joint", "p1p2", "pck", "auc", "vel", "acc"):
-            for key in (f"{which}_{m}", f"{which}_{m}_all"):
-                if key in res:
-                    out["detail_" + key] = np.asarray(res[key], dtype=np.float32)
-    return out
-
-
-def dense_lines(res: Dict[str, object]) -> List[str]:
-    """The printed lines of ``--dense`` from an ``evaluate_dense`` result, each starting with ``Dense |``: the summary (all frames and
-    the action mean), one line per action, and the clip-wise P1 / P2 at window positions 1, T/2 and T.  Millimetres."""
-    def summary(key: str) -> str:
-        return (f"p1 (mm) {res['p1' + key] * 1000.0:.2f} | p2 (mm) {res['p2' + key] * 1000.0:.2f} | vel (mm/frame) "
-                f"{res['mpjve' + key] * 1000.0:.2f} | accel (mm/frame^2) {res['accel' + key] * 1000.0:.2f} | spread (mm) "
-                f"{res['spread' + key] * 1000.0:.2f}")
-
-    lines = [f"Dense | fuse {res['fuse']} (ramp {res['ramp']}) | sequences {res['sequences']} | frames {res['frames_all']} of "
-             f"{res['clip_frames']} clip frames | fused from >= 2 clips {res['multi_frames']} | all: {summary('_all')} | action mean: "
-             f"{summary('_mean')}"]
-    for i, name in enumerate(res["group_names"]):
-        lines.append(f"Dense |   {name} | frames {int(res['frames'][i])} | p1 (mm) {res['p1'][i] * 1000.0:.2f} | p2 (mm) "
-                     f"{res['p2'][i] * 1000.0:.2f} | vel (mm/frame) {res['mpjve'][i] * 1000.0:.2f} | accel (mm/frame^2) "
-                     f"{res['accel'][i] * 1000.0:.2f} | spread (mm) {res['spread'][i] * 1000.0:.2f}")
-    p1, p2 = res["position_p1"], res["position_p2"]
-    at = sorted({1, max(len(p1) // 2, 1), len(p1)})
-    lines.append("Dense | clip-wise by window position | p1 (mm) " + " | ".join(f"@{k}: {p1[k - 1] * 1000.0:.2f}" for k in at) +
-                 " | p2 (mm) " + " | ".join(f"@{k}: {p2[k - 1] * 1000.0:.2f}" for k in at))
-    return lines
-
-
-def dense_post_lines(res: Dict[str, object]) -> List[str]:
-    """The ``Dense | post`` lines of an ``evaluate_dense`` result that carries ``post``: raw -> processed over all frames and per
-    action, errors in millimetres and the bone-length standard deviation over time of the raw, processed and ground-truth poses."""
-    def pair(m: str, key, i=None) -> str:
-        a, b = res[m + key], res["post_" + m + key]
-        a, b = (a, b) if i is None else (a[i], b[i])
-        return f"{a * 1000.0:.2f} -> {b * 1000.0:.2f}"
-
-    def row(key: str, i=None) -> str:
-        std = [res[f"bone_std_{k}{'_all' if i is None else ''}"] for k in ("raw", "post", "gt")]
-        std = [v if i is None else v[i] for v in std]
-        return (f"p1 (mm) {pair('p1', key, i)} | p2 (mm) {pair('p2', key, i)} | vel (mm/frame) {pair('mpjve', key, i)} | accel (mm/frame^2) "
-                f"{pair('accel', key, i)} | bone std (mm) {std[0]:.3f} -> {std[1]:.3f} (gt {std[2]:.3f})")
-
-    lines = [f"Dense | post {res['post']} | frames copied (segment shorter than the window) {res['post_short_rows']} in "
-             f"{res['post_short_segments']} segments | raw -> processed, all: {row('_all')}"]
-    for i, name in enumerate(res["group_names"]):
-        lines.append(f"Dense | post   {name} | {row('', i)}")
-    return lines
-
-
-def dense_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
-    """The ``.npz`` keys of ``--dense``: ``dense_actions`` (G,) str, ``dense_frames`` (G,) int64, ``dense_M`` (G,) and ``dense_M_all`` ()
-    fp32 for M in p1, p2, mpjve, accel, spread (metres, metres per frame, metres per frame^2), ``dense_position_p1`` / ``_p2`` (T,) fp32,
-    ``dense_counts`` int64 [sequences, frames, clip frames, frames fused from >= 2 clips], ``dense_fuse`` str."""
-    out = {"dense_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
-           "dense_frames": np.asarray(res["frames"], dtype=np.int64), "dense_fuse": np.array(str(res["fuse"])),
-           "dense_counts": np.array([res["sequences"], res["frames_all"], res["clip_frames"], res["multi_frames"]], dtype=np.int64),
-           "dense_position_p1": np.asarray(res["position_p1"], dtype=np.float32),
-           "dense_position_p2": np.asarray(res["position_p2"], dtype=np.float32)}
-    for m in ("p1", "p2", "mpjve", "accel", "spread"):
-        out["dense_" + m] = np.asarray(res[m], dtype=np.float32)
-        out["dense_" + m + "_all"] = np.asarray(res[m + "_all"], dtype=np.float32)
-    if "post" in res:                        # --dense-smooth / --dense-fix-bones: dense_post_M, dense_post_bone_std_{raw,post,gt} (mm), ...
-        out["dense_post"] = np.array(str(res["post"]))
-        out["dense_post_short"] = np.array([res["post_short_rows"], res["post_short_segments"]], dtype=np.int64)
-        for m in ("p1", "p2", "mpjve", "accel"):
-            out["dense_post_" + m] = np.asarray(res["post_" + m], dtype=np.float32)
-            out["dense_post_" + m + "_all"] = np.asarray(res["post_" + m + "_all"], dtype=np.float32)
-        for k in ("raw", "post", "gt"):
-            out["dense_post_bone_std_" + k] = np.asarray(res["bone_std_" + k], dtype=np.float32)
-            out["dense_post_bone_std_" + k + "_all"] = np.asarray(res["bone_std_" + k + "_all"], dtype=np.float32)
-    return out
-
-
-def dtw_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
-    """The printed lines of ``--dtw`` from an ``evaluate_dtw`` result: the ``DTW metrics`` line (all clips: the warped P1 / P2 and, after
-    ``plain``, the unwarped horizon means of the same rollouts), one indented line per action, and the ``DTW horizons`` line with the
-    warped error in mm and the lag in frames (signed: positive = the prediction is slow) at horizons 1, 5, 10 and P."""
-    clips = res["clips"]
-    da, pa = res["dtw_all"], res["plain_all"]
-    band = "none" if res["band"] < 0 else str(int(res["band"]))
-    lines = [f"DTW metrics | input {input_len} | pred {pred_len} | band {band} | clips {int(clips.sum())} | all: p1 (mm) {da[0] * 1000.0:.2f} "
-             f"| p2 (mm) {da[1] * 1000.0:.2f} | plain p1 (mm) {pa[0] * 1000.0:.2f} | p2 (mm) {pa[1] * 1000.0:.2f}"]
-    for name, c, (p1, p2) in zip(res["group_names"], clips, res["dtw"]):
-        lines.append(f"  {name} | clips {int(c)} | dtw p1 (mm) {p1 * 1000.0:.2f} | dtw p2 (mm) {p2 * 1000.0:.2f}")
-    hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
-    fa, la = res["dtw_future_all"], res["lag_all"]
-    parts = [f"p{m + 1} (mm) " + " | ".join(f"@{h}: {fa[h - 1, m] * 1000.0:.2f}" for h in hs) for m in (0, 1)]
-    parts += [f"lag p{m + 1} (frames) " + " | ".join(f"@{h}: {la[h - 1, m]:+.2f}" for h in hs) for m in (0, 1)]
-    lines.append("DTW horizons | " + " | ".join(parts))
-    return lines
-
-
-def dtw_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
-    """The ``.npz`` keys of ``--dtw``: ``dtw_actions`` (G,) str, ``dtw_clips`` (G,) int64, ``dtw_band`` () int64, and fp32 ``dtw`` (G, 2),
-    ``dtw_all`` (2,), ``dtw_future`` (G, P, 2), ``dtw_future_all`` (P, 2) in metres and ``dtw_lag`` (G, P, 2), ``dtw_lag_all`` (P, 2) in
-    frames; [.., 2] = [p1, p2]."""
-    out = {"dtw_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
-           "dtw_clips": np.asarray(res["clips"], dtype=np.int64), "dtw_band": np.array(int(res["band"]), dtype=np.int64)}
-    for key, src in (("dtw", "dtw"), ("dtw_all", "dtw_all"), ("dtw_future", "dtw_future"), ("dtw_future_all", "dtw_future_all"),
-                     ("dtw_lag", "lag"), ("dtw_lag_all", "lag_all")):
-        out[key] = np.asarray(res[src], dtype=np.float32)
-    return out
-
-
-def baseline_lines(res: Dict[str, object], input_len: int, pred_len: int) -> List[str]:
-    """The printed lines of ``--baselines`` from an ``evaluate_baselines`` result: the ``Baselines`` header, then one indented line per
-    predictor, ``model`` first: MPJPE, P1 and P2 in mm at horizons 1, 5, 10 and P and their mean over the horizons, and for each
-    baseline the model's skill ``1 - model / baseline`` on the P1 mean (positive: the model beats it)."""
-    hs = sorted({h for h in (1, 5, 10, pred_len) if h <= pred_len})
-    head = (f"Baselines | input {input_len} | pred {pred_len} | clips {int(np.sum(res['clips']))} | anchor {res['anchor']} | predictors "
-            f"{len(res['names'])}")
-    if "nn" in res["names"]:
-        head += f" | nn k {int(res['nn_k'])} | nn strip dist2 mean {res['nn_dist2_mean']:.6g}"
-    lines = [head]
-    model_p1 = float(np.mean(res["model"]["p1"]))
-    for name in res["names"]:
-        row = res[name]
-        parts = [f"{key} (mm) " + " | ".join(f"@{h}: {row[key][h - 1] * 1000.0:.2f}" for h in hs) + f" | mean: {np.mean(row[key]) * 1000.0:.2f}"
-                 for key in ("mpjpe", "p1", "p2")]
-        line = f"  {name} | " + " | ".join(parts)
-        if name != "model":
-            base_p1 = float(np.mean(row["p1"]))
-            line += f" | model skill on p1: {(1.0 - model_p1 / base_p1) if base_p1 > 0 else float('nan'):+.4f}"
-        lines.append(line)
-    return lines
-
-
-def baseline_arrays(res: Dict[str, object]) -> Dict[str, np.ndarray]:
-    """The ``.npz`` keys of ``--baselines``: ``baseline_names`` (Nb,) str, ``model`` first; fp32 ``baseline_mpjpe``, ``baseline_p1``,
-    ``baseline_p2`` (Nb, P) in metres; ``baseline_actions`` (G,) str; ``baseline_per_action`` (Nb, G, P, 2) fp32 [p1, p2];
-    ``baseline_anchor`` str.  (``main`` adds ``nn_index``, ``nn_dist2`` and ``nn_future3djoints`` of the dumped clips.)"""
-    names = list(res["names"])
-    out = {"baseline_names": np.array(names, dtype=str), "baseline_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
-           "baseline_anchor": np.array(str(res["anchor"])),
-           "baseline_per_action": np.stack([np.asarray(res[n]["per_action"], dtype=np.float32) for n in names])}
-    for key in ("mpjpe", "p1", "p2"):
-        out["baseline_" + key] = np.stack([np.asarray(res[n][key], dtype=np.float32) for n in names])
-    return out
-
-
-def dense_export(res: Dict[str, object]) -> Dict[str, np.ndarray]:
-    """The arrays of ``--dense-out``: ``seq_keys`` (S, 3) str [subject, action, cam], ``seq_start`` (S+1,), ``frame_idx`` (F,) int32
-    (sub-sampled frame units), ``pred`` and ``gt`` (F, J, 3) fp32 in metres, ``spread`` (F,) fp32, ``count`` (F,) int32 = the clips
-    that showed the frame; sequence s is rows ``seq_start[s]:seq_start[s+1]``."""
-    out = {"seq_keys": np.array([[str(v) for v in k] for k in res["seq_keys"]], dtype=str), "seq_start": res["seq_start"],
-           "frame_idx": res["frame_idx"], "pred": res["pred"], "gt": res["gt"], "spread": res["frame_spread"], "count": res["count"]}
-    if "pred_post" in res:                   # --dense-smooth / --dense-fix-bones: the processed poses beside the raw ones, and what made them
-        out["pred_post"], out["post"] = res["pred_post"], np.array(str(res["post"]))
-    return out
-
-
 def main(argv: Optional[List[str]] = None) -> str:
     """``python src/results.py`` on one MI355X.  Returns the path of the written ``.npz``."""
     from .feature_store import DeviceFeatureStore
+    from .protocols import action_groups
     from .train import evaluate
 
     args = parse_args(argv)
@@ -686,10 +453,11 @@ def main(argv: Optional[List[str]] = None) -> str:
         at = " | ".join(f"@{k}: {mm[k - 1] * 1000.0:.2f}" for k in sorted({h for h in (1, 5, 10, args.pred_len) if h <= args.pred_len}))
         print(f"Rollout metrics | input {args.input_len} | pred {args.pred_len} | clips {rollout['clips']} | mpjpe (mm) {at} "
               f"| mean: {rollout['mpjpe_mean'] * 1000.0:.2f}")
+    if args.protocols or args.detail_metrics or args.dtw or hasattr(args, "baselines") or hasattr(args, "hallucinate"):
+        names, ids = action_groups(test_set.item_actions())      # the per-action reports' groups, shared by all of them
     protocols = None
     if args.protocols:                       # every test clip once, in store order (not the loader's drop_last batches)
-        from .protocols import action_groups, evaluate_protocols
-        names, ids = action_groups(test_set.item_actions())
+        from .protocols import evaluate_protocols, protocol_arrays, protocol_lines
         protocols = evaluate_protocols(head, test_set, ids, names, args.input_len if args.pred_len > 0 else 0, args.pred_len)
         for line in protocol_lines(protocols, args.input_len, args.pred_len):
             print(line)
@@ -702,9 +470,7 @@ def main(argv: Optional[List[str]] = None) -> str:
 
     detail = None
     if args.detail_metrics:                  # the protocols' pass: every test clip once, in store order
-        from .detail_metrics import evaluate_detail
-        from .protocols import action_groups
-        names, ids = action_groups(test_set.item_actions())
+        from .detail_metrics import detail_lines, detail_npz, evaluate_detail
         detail = evaluate_detail(head, test_set, ids, names, args.input_len if args.pred_len > 0 else 0, args.pred_len,
                                  n_thr=args.auc_steps, thr_max=args.pck_threshold_mm / 1000.0)
         for line in detail_lines(detail, args.input_len, args.pred_len):
@@ -712,7 +478,7 @@ def main(argv: Optional[List[str]] = None) -> str:
 
     dense, multi, rigid = None, None, None
     if args.dense:                           # every video frame once: the clips of a sequence fused per frame
-        from .sequences import evaluate_dense
+        from .sequences import dense_export, dense_lines, dense_npz, dense_post_lines, evaluate_dense
         from . import multiview as mv
         post, mv_options = dense_post(args), mv.options_from_args(args)
         want_rigid = hasattr(args, "dense_rigid")
@@ -738,17 +504,14 @@ def main(argv: Optional[List[str]] = None) -> str:
 
     dtw = None
     if args.dtw:                             # the protocols' pass over the forecasts: every test clip once, in store order
-        from .dtw import evaluate_dtw
-        from .protocols import action_groups
-        names, ids = action_groups(test_set.item_actions())
+        from .dtw import dtw_arrays, dtw_lines, evaluate_dtw
         dtw = evaluate_dtw(head, test_set, ids, names, args.input_len, args.pred_len, band=args.dtw_band)
         for line in dtw_lines(dtw, args.input_len, args.pred_len):
             print(line)
 
     base, base_db = None, None
     if hasattr(args, "baselines"):           # the protocols' pass again: the trivial forecasts beside the model's, every test clip once
-        from .baselines import StripDatabase, evaluate_baselines
-        from .protocols import action_groups
+        from .baselines import StripDatabase, baseline_arrays, baseline_lines, evaluate_baselines
         which, anchor, nn_k = baseline_options(args)
         if "nn" in which:
             from .train import TRAIN_SUBJECTS
@@ -765,7 +528,6 @@ def main(argv: Optional[List[str]] = None) -> str:
                 raise SystemExit(f"results: the nn baseline's database has {len(train_set)} clips, fewer than --nn-k {nn_k}")
             base_db = StripDatabase.build(head, train_set, args.input_len)
             print(f"Baselines | nn database: {len(base_db)} clips of subjects {nn_subjects}")
-        names, ids = action_groups(test_set.item_actions())
         base = evaluate_baselines(head, test_set, base_db, ids, names, args.input_len, args.pred_len, which, nn_k=nn_k, anchor=anchor)
         for line in baseline_lines(base, args.input_len, args.pred_len):
             print(line)
@@ -773,8 +535,6 @@ def main(argv: Optional[List[str]] = None) -> str:
     hal = None
     if hasattr(args, "hallucinate"):         # the protocols' pass once more: from single frames beside with temporal context
         from .hallucinate import evaluate_hallucinator, hallucinate_lines
-        from .protocols import action_groups
-        names, ids = action_groups(test_set.item_actions())
         hal = evaluate_hallucinator(head, test_set, ids, names, args.input_len if args.pred_len > 0 else 0, args.pred_len)
         for line in hallucinate_lines(hal):
             print(line)

@@ -390,3 +390,81 @@ def evaluate_dense(head, store, fuse: str = "context", batch_size: int = 256, ch
         if keep_poses:
             out["pred_post"] = poses[3]
     return out
+
+
+def dense_lines(res: Dict[str, object]) -> List[str]:
+    """The printed lines of ``--dense`` from an ``evaluate_dense`` result, each starting with ``Dense |``: the summary (all frames and
+    the action mean), one line per action, and the clip-wise P1 / P2 at window positions 1, T/2 and T.  Millimetres."""
+    def summary(key: str) -> str:
+        return (f"p1 (mm) {res['p1' + key] * 1000.0:.2f} | p2 (mm) {res['p2' + key] * 1000.0:.2f} | vel (mm/frame) "
+                f"{res['mpjve' + key] * 1000.0:.2f} | accel (mm/frame^2) {res['accel' + key] * 1000.0:.2f} | spread (mm) "
+                f"{res['spread' + key] * 1000.0:.2f}")
+
+    lines = [f"Dense | fuse {res['fuse']} (ramp {res['ramp']}) | sequences {res['sequences']} | frames {res['frames_all']} of "
+             f"{res['clip_frames']} clip frames | fused from >= 2 clips {res['multi_frames']} | all: {summary('_all')} | action mean: "
+             f"{summary('_mean')}"]
+    for i, name in enumerate(res["group_names"]):
+        lines.append(f"Dense |   {name} | frames {int(res['frames'][i])} | p1 (mm) {res['p1'][i] * 1000.0:.2f} | p2 (mm) "
+                     f"{res['p2'][i] * 1000.0:.2f} | vel (mm/frame) {res['mpjve'][i] * 1000.0:.2f} | accel (mm/frame^2) "
+                     f"{res['accel'][i] * 1000.0:.2f} | spread (mm) {res['spread'][i] * 1000.0:.2f}")
+    p1, p2 = res["position_p1"], res["position_p2"]
+    at = sorted({1, max(len(p1) // 2, 1), len(p1)})
+    lines.append("Dense | clip-wise by window position | p1 (mm) " + " | ".join(f"@{k}: {p1[k - 1] * 1000.0:.2f}" for k in at) +
+                 " | p2 (mm) " + " | ".join(f"@{k}: {p2[k - 1] * 1000.0:.2f}" for k in at))
+    return lines
+
+
+def dense_post_lines(res: Dict[str, object]) -> List[str]:
+    """The ``Dense | post`` lines of an ``evaluate_dense`` result that carries ``post``: raw -> processed over all frames and per
+    action, errors in millimetres and the bone-length standard deviation over time of the raw, processed and ground-truth poses."""
+    def pair(m: str, key, i=None) -> str:
+        a, b = res[m + key], res["post_" + m + key]
+        a, b = (a, b) if i is None else (a[i], b[i])
+        return f"{a * 1000.0:.2f} -> {b * 1000.0:.2f}"
+
+    def row(key: str, i=None) -> str:
+        std = [res[f"bone_std_{k}{'_all' if i is None else ''}"] for k in ("raw", "post", "gt")]
+        std = [v if i is None else v[i] for v in std]
+        return (f"p1 (mm) {pair('p1', key, i)} | p2 (mm) {pair('p2', key, i)} | vel (mm/frame) {pair('mpjve', key, i)} | accel (mm/frame^2) "
+                f"{pair('accel', key, i)} | bone std (mm) {std[0]:.3f} -> {std[1]:.3f} (gt {std[2]:.3f})")
+
+    lines = [f"Dense | post {res['post']} | frames copied (segment shorter than the window) {res['post_short_rows']} in "
+             f"{res['post_short_segments']} segments | raw -> processed, all: {row('_all')}"]
+    for i, name in enumerate(res["group_names"]):
+        lines.append(f"Dense | post   {name} | {row('', i)}")
+    return lines
+
+
+def dense_npz(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The ``.npz`` keys of ``--dense``: ``dense_actions`` (G,) str, ``dense_frames`` (G,) int64, ``dense_M`` (G,) and ``dense_M_all`` ()
+    fp32 for M in p1, p2, mpjve, accel, spread (metres, metres per frame, metres per frame^2), ``dense_position_p1`` / ``_p2`` (T,) fp32,
+    ``dense_counts`` int64 [sequences, frames, clip frames, frames fused from >= 2 clips], ``dense_fuse`` str."""
+    out = {"dense_actions": np.array([str(n) for n in res["group_names"]], dtype=str),
+           "dense_frames": np.asarray(res["frames"], dtype=np.int64), "dense_fuse": np.array(str(res["fuse"])),
+           "dense_counts": np.array([res["sequences"], res["frames_all"], res["clip_frames"], res["multi_frames"]], dtype=np.int64),
+           "dense_position_p1": np.asarray(res["position_p1"], dtype=np.float32),
+           "dense_position_p2": np.asarray(res["position_p2"], dtype=np.float32)}
+    for m in ("p1", "p2", "mpjve", "accel", "spread"):
+        out["dense_" + m] = np.asarray(res[m], dtype=np.float32)
+        out["dense_" + m + "_all"] = np.asarray(res[m + "_all"], dtype=np.float32)
+    if "post" in res:                        # --dense-smooth / --dense-fix-bones: dense_post_M, dense_post_bone_std_{raw,post,gt} (mm), ...
+        out["dense_post"] = np.array(str(res["post"]))
+        out["dense_post_short"] = np.array([res["post_short_rows"], res["post_short_segments"]], dtype=np.int64)
+        for m in ("p1", "p2", "mpjve", "accel"):
+            out["dense_post_" + m] = np.asarray(res["post_" + m], dtype=np.float32)
+            out["dense_post_" + m + "_all"] = np.asarray(res["post_" + m + "_all"], dtype=np.float32)
+        for k in ("raw", "post", "gt"):
+            out["dense_post_bone_std_" + k] = np.asarray(res["bone_std_" + k], dtype=np.float32)
+            out["dense_post_bone_std_" + k + "_all"] = np.asarray(res["bone_std_" + k + "_all"], dtype=np.float32)
+    return out
+
+
+def dense_export(res: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The arrays of ``--dense-out``: ``seq_keys`` (S, 3) str [subject, action, cam], ``seq_start`` (S+1,), ``frame_idx`` (F,) int32
+    (sub-sampled frame units), ``pred`` and ``gt`` (F, J, 3) fp32 in metres, ``spread`` (F,) fp32, ``count`` (F,) int32 = the clips
+    that showed the frame; sequence s is rows ``seq_start[s]:seq_start[s+1]``."""
+    out = {"seq_keys": np.array([[str(v) for v in k] for k in res["seq_keys"]], dtype=str), "seq_start": res["seq_start"],
+           "frame_idx": res["frame_idx"], "pred": res["pred"], "gt": res["gt"], "spread": res["frame_spread"], "count": res["count"]}
+    if "pred_post" in res:                   # --dense-smooth / --dense-fix-bones: the processed poses beside the raw ones, and what made them
+        out["pred_post"], out["post"] = res["pred_post"], np.array(str(res["post"]))
+    return out

@@ -78,9 +78,9 @@ def _numbers(line, key):
 
 
 def test_lines_and_arrays_from_a_hand_made_result():
-    from implementation_phd_lab_vision_amd import results
+    from implementation_phd_lab_vision_amd import baselines
     res = _hand_made()
-    lines = results.baseline_lines(res, 3, 12)
+    lines = baselines.baseline_lines(res, 3, 12)
     assert len(lines) == 4 and lines[0] == ("Baselines | input 3 | pred 12 | clips 11 | anchor gt | predictors 3 | nn k 2 | "
                                             "nn strip dist2 mean 123.457")
     assert [l.split(" | ")[0] for l in lines[1:]] == ["  model", "  const_pose", "  nn"]
@@ -96,10 +96,10 @@ def test_lines_and_arrays_from_a_hand_made_result():
         else:
             skill = 1.0 - res["model"]["p1"].mean() / res[name]["p1"].mean()
             assert line.endswith(f" | model skill on p1: {skill:+.4f}")
-    short = results.baseline_lines({**res, "names": ("model", "const_pose")}, 3, 4)
+    short = baselines.baseline_lines({**res, "names": ("model", "const_pose")}, 3, 4)
     assert "nn k" not in short[0] and "@10" not in short[1] and "@4: " in short[1] and len(short) == 3
 
-    z = results.baseline_arrays(res)
+    z = baselines.baseline_arrays(res)
     assert set(z) == {"baseline_names", "baseline_mpjpe", "baseline_p1", "baseline_p2", "baseline_actions", "baseline_per_action",
                       "baseline_anchor"}
     assert z["baseline_names"].tolist() == list(res["names"]) and z["baseline_actions"].tolist() == ["sit", "walk"]

@@ -433,7 +433,7 @@ def test_results_cli_baselines(world, trees, tmp_path):
 
     db = baselines.StripDatabase.build(head, train, I_LEN)
     res = baselines.evaluate_baselines(head, test, db, ids, names, I_LEN, P_LEN, baselines.BASELINES, nn_k=2)
-    lines = results.baseline_lines(res, I_LEN, P_LEN)
+    lines = baselines.baseline_lines(res, I_LEN, P_LEN)
     on_lines = so_on.replace(str(out_on), str(out_off)).splitlines()
     for line in lines:
         assert line in on_lines, line

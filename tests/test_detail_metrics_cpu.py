@@ -213,7 +213,7 @@ def _fake_result(p_len, joints=J):
 
 def test_detail_lines_and_npz():
     res = _fake_result(0)
-    lines = results.detail_lines(res, 15, 0)
+    lines = dm.detail_lines(res, 15, 0)
     assert len(lines) == 4
     pa, aa = res["recon_pck_all"] * 100.0, res["recon_auc_all"] * 100.0
     assert lines[0].startswith(f"Detail metrics | clips 4 | actions 2 | all: pck@150 (%) {pa[0]:.2f} / pa {pa[1]:.2f} | auc (%) {aa[0]:.2f} "
@@ -224,7 +224,7 @@ def test_detail_lines_and_npz():
     assert lines[1].endswith(f"r_wrist {pj[16, 0]:.2f} / {pj[16, 1]:.2f}") and lines[1].count(" | ") == 17
     assert lines[2].startswith("  Directions | clips 3 | pck@150 (%) ") and lines[3].startswith("  Walking | clips 1 | pck@150 (%) ")
     assert f"vel (mm/frame) {res['recon_vel'][1] * 1000.0:.2f} | accel (mm/frame^2) {res['recon_acc'][1] * 1000.0:.2f}" in lines[3]
-    arr = results.detail_npz(res)
+    arr = dm.detail_npz(res)
     floats = {f"detail_recon_{m}{s}" for m in dm.METRICS for s in ("", "_all")}
     assert set(arr) == {"detail_actions", "detail_joint_names", "detail_clips"} | floats
     assert arr["detail_actions"].dtype.kind == "U" and arr["detail_actions"].tolist() == ["Directions", "Walking"]
@@ -235,22 +235,22 @@ def test_detail_lines_and_npz():
     assert arr["detail_recon_per_joint"].shape == (2, J, 2) and arr["detail_recon_vel_all"].shape == ()
 
     res = _fake_result(12)
-    lines = results.detail_lines(res, 3, 12)
+    lines = dm.detail_lines(res, 3, 12)
     assert len(lines) == 5 and lines[-1].startswith("Rollout detail metrics | input 3 | pred 12 | clips 4 | pck@150 (%) @1: ")
     fv, fp = res["future_vel_all"] * 1000.0, res["future_pck_all"] * 100.0
     assert f"vel (mm/frame) @1: - | @5: {fv[4]:.2f} | @10: {fv[9]:.2f} | @12: {fv[11]:.2f} | accel (mm/frame^2) @1: - | @5: " in lines[-1]
     assert lines[-1].endswith("| @12: -") and f"@10: {fp[9, 0]:.2f} / pa {fp[9, 1]:.2f}" in lines[-1] and "@25" not in lines[-1]
-    arr = results.detail_npz(res)
+    arr = dm.detail_npz(res)
     assert set(arr) == {"detail_actions", "detail_joint_names", "detail_clips"} | floats | {k.replace("recon", "future") for k in floats}
     assert arr["detail_future_per_joint"].shape == (2, 12, J, 2) and arr["detail_future_vel_all"].shape == (12,)
     assert all(arr[k].dtype == np.float32 for k in arr if k.startswith("detail_future_"))
     res["thr_max"] = 0.1
-    assert "pck@100 (%)" in results.detail_lines(res, 3, 12)[0]
+    assert "pck@100 (%)" in dm.detail_lines(res, 3, 12)[0]
 
 
 def test_other_joint_counts_print_indices():
     res = _fake_result(0, joints=3)
-    line = results.detail_lines(res, 15, 0)[1]
+    line = dm.detail_lines(res, 15, 0)[1]
     pj = res["recon_per_joint_all"] * 1000.0
     assert line == "Per-joint p1 / p2 (mm) | " + " | ".join(f"{j} {pj[j, 0]:.2f} / {pj[j, 1]:.2f}" for j in range(3))
-    assert results.detail_npz(res)["detail_joint_names"].tolist() == ["0", "1", "2"]
+    assert dm.detail_npz(res)["detail_joint_names"].tolist() == ["0", "1", "2"]

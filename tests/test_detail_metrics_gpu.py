@@ -320,7 +320,7 @@ def test_results_cli_detail_metrics(lib, trees, tmp_path):
     head = results.build_head(sd, DEV)
     names, ids = protocols.action_groups(store.item_actions())
     res = detail_metrics.evaluate_detail(head, store, ids, names, 3, 5)
-    lines = results.detail_lines(res, 3, 5)
+    lines = detail_metrics.detail_lines(res, 3, 5)
     assert lines[0].startswith("Detail metrics | clips 11 | actions 3 | all: pck@150 (%) ") and len(lines) == 6
     assert lines[1].startswith("Per-joint p1 / p2 (mm) | pelvis 0.00 / ")
     assert lines[-1].startswith("Rollout detail metrics | input 3 | pred 5 | clips 11 | pck@150 (%) @1: ")
@@ -333,7 +333,7 @@ def test_results_cli_detail_metrics(lib, trees, tmp_path):
            [l for l in so_off.splitlines() if not l.startswith(timing)]                  # the rest of stdout as without the flag
 
     z_off, z_on, z_100 = (np.load(f, allow_pickle=True) for f in (out_off, out_on, out_100))
-    want = results.detail_npz(res)
+    want = detail_metrics.detail_npz(res)
     assert set(z_on.files) == set(z_off.files) | set(want) and not set(want) & set(z_off.files)
     assert all(k.startswith("detail_") for k in want) and not any(k.startswith("detail_") for k in z_off.files)
     for key in z_off.files:

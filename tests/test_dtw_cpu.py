@@ -179,7 +179,7 @@ def _fake_result(p_len, band=-1):
 
 def test_dtw_lines_and_arrays():
     res = _fake_result(12)
-    lines = results.dtw_lines(res, 3, 12)
+    lines = dtw.dtw_lines(res, 3, 12)
     assert lines[0] == ("DTW metrics | input 3 | pred 12 | band none | clips 4 | all: p1 (mm) 55.00 | p2 (mm) 42.50 | plain p1 (mm) 80.10 "
                         "| p2 (mm) 60.20")
     assert lines[1:3] == ["  Directions | clips 3 | dtw p1 (mm) 50.00 | dtw p2 (mm) 40.00",
@@ -190,10 +190,10 @@ def test_dtw_lines_and_arrays():
     assert f"lag p1 (frames) @1: {la[0, 0]:+.2f} | @5: {la[4, 0]:+.2f}" in lines[3] and f"lag p2 (frames) @1: {la[0, 1]:+.2f}" in lines[3]
     assert "@25" not in lines[3] and lines[3].count("@") == 16
     assert " -0." in lines[3] and " +" in lines[3]                      # the lag carries its sign
-    assert "band 4 |" in results.dtw_lines(_fake_result(3, band=4), 2, 3)[0]
-    assert results.dtw_lines(_fake_result(3), 2, 3)[-1].count("@") == 8                  # horizons 1 and 3, four series
+    assert "band 4 |" in dtw.dtw_lines(_fake_result(3, band=4), 2, 3)[0]
+    assert dtw.dtw_lines(_fake_result(3), 2, 3)[-1].count("@") == 8                  # horizons 1 and 3, four series
 
-    arr = results.dtw_arrays(res)
+    arr = dtw.dtw_arrays(res)
     assert set(arr) == {"dtw_actions", "dtw_clips", "dtw", "dtw_all", "dtw_future", "dtw_future_all", "dtw_lag", "dtw_lag_all", "dtw_band"}
     assert arr["dtw_actions"].dtype.kind == "U" and arr["dtw_actions"].tolist() == ["Directions", "Walking"]
     assert arr["dtw_clips"].dtype == np.int64 and arr["dtw_band"].dtype == np.int64 and int(arr["dtw_band"]) == -1

@@ -396,7 +396,7 @@ def test_results_cli_dtw(lib, trees, tmp_path):
     head = results.build_head(sd, DEV)
     names, ids = protocols.action_groups(store.item_actions())
     res = dtw.evaluate_dtw(head, store, ids, names, 3, 5)
-    lines = results.dtw_lines(res, 3, 5)
+    lines = dtw.dtw_lines(res, 3, 5)
     assert lines[0].startswith("DTW metrics | input 3 | pred 5 | band none | clips 11 | all: p1 (mm) ") and len(lines) == 5
     assert lines[-1].startswith("DTW horizons | p1 (mm) @1: ") and "lag p2 (frames) @1: " in lines[-1]
     on_lines = so_on.replace(str(out_on), str(out_off)).splitlines()

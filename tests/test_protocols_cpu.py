@@ -134,26 +134,26 @@ def _fake_result(p_len):
 
 
 def test_protocol_lines_and_arrays():
-    lines = results.protocol_lines(_fake_result(0), 15, 0)
+    lines = protocols.protocol_lines(_fake_result(0), 15, 0)
     assert lines[0] == ("Protocol metrics | clips 4 | actions 2 | all: p1 (mm) 55.00 | p2 (mm) 42.50 | action mean: p1 (mm) 60.00 "
                         "| p2 (mm) 45.00")
     assert lines[1:] == ["  Directions | clips 3 | p1 (mm) 50.00 | p2 (mm) 40.00", "  Walking | clips 1 | p1 (mm) 70.00 | p2 (mm) 50.00"]
-    arr = results.protocol_arrays(_fake_result(0))
+    arr = protocols.protocol_arrays(_fake_result(0))
     assert set(arr) == {"protocol_actions", "protocol_clips", "protocol_recon", "protocol_recon_all"}
     assert arr["protocol_actions"].dtype.kind == "U" and arr["protocol_actions"].tolist() == ["Directions", "Walking"]
     assert arr["protocol_clips"].dtype == np.int64 and arr["protocol_recon"].dtype == np.float32 and arr["protocol_recon"].shape == (2, 2)
     assert arr["protocol_recon_all"].shape == (2,) and arr["protocol_recon_all"].dtype == np.float32
 
     res = _fake_result(12)
-    lines = results.protocol_lines(res, 3, 12)
+    lines = protocols.protocol_lines(res, 3, 12)
     assert len(lines) == 4 and lines[-1].startswith("Rollout protocol metrics | input 3 | pred 12 | clips 4 | p1 (mm) @1: ")
     fa = res["future_all"] * 1000.0
     assert f"@10: {fa[9, 0]:.2f} | @12: {fa[11, 0]:.2f} | p2 (mm) @1: {fa[0, 1]:.2f}" in lines[-1]
     assert "@5: " in lines[-1] and "@25" not in lines[-1]
-    arr = results.protocol_arrays(res)
+    arr = protocols.protocol_arrays(res)
     assert arr["protocol_future"].shape == (2, 12, 2) and arr["protocol_future_all"].shape == (12, 2)
     assert arr["protocol_future"].dtype == arr["protocol_future_all"].dtype == np.float32
-    assert results.protocol_lines(_fake_result(3), 2, 3)[-1].count("@") == 4                # horizons 1 and 3, for p1 and p2
+    assert protocols.protocol_lines(_fake_result(3), 2, 3)[-1].count("@") == 4                # horizons 1 and 3, for p1 and p2
 
 
 def test_add_protocol_sums_refuses_cpu_tensors():

@@ -290,7 +290,7 @@ def test_results_cli_protocols(lib, trees, tmp_path):
     head = results.build_head(sd, DEV)
     names, ids = protocols.action_groups(store.item_actions())
     res = protocols.evaluate_protocols(head, store, ids, names, 3, 5)
-    lines = results.protocol_lines(res, 3, 5)
+    lines = protocols.protocol_lines(res, 3, 5)
     assert lines[0].startswith("Protocol metrics | clips 11 | actions 3 | all: p1 (mm) ") and len(lines) == 5
     assert lines[-1].startswith("Rollout protocol metrics | input 3 | pred 5 | clips 11 | p1 (mm) @1: ")
     on_lines = so_on.replace(str(out_on), str(out_off)).splitlines()
@@ -313,7 +313,7 @@ def test_results_cli_protocols(lib, trees, tmp_path):
         assert z_on[key].dtype == np.float32 and np.array_equal(z_on[key], want.astype(np.float32)), key
 
     rec = protocols.evaluate_protocols(head, store, ids, names)
-    assert results.protocol_lines(rec, 15, 0) == [l for l in so_rec.splitlines() if l.startswith(("Protocol metrics", "  "))]
+    assert protocols.protocol_lines(rec, 15, 0) == [l for l in so_rec.splitlines() if l.startswith(("Protocol metrics", "  "))]
     assert "Rollout" not in so_rec
     z_rec = np.load(out_rec, allow_pickle=True)
     assert set(z_rec.files) == {"video", "joints3d", "predicted3djoints", "joints2d", "K", "meta", "test_metrics", "protocol_actions",
