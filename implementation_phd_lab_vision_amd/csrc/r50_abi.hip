@@ -1,5 +1,5 @@
-// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h and
-// include/r50_kinematics.h.
+// Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h,
+// include/r50_kinematics.h and include/r50_refine.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
@@ -7,12 +7,14 @@
 #include "smooth_kernels.h"
 #include "multiview_kernels.h"
 #include "kinematics_kernels.h"
+#include "refine_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
 #include "../../include/r50_smooth.h"
 #include "../../include/r50_multiview.h"
 #include "../../include/r50_kinematics.h"
+#include "../../include/r50_refine.h"
 
 #include <atomic>
 #include <cmath>
@@ -2664,6 +2666,99 @@ int r50_op_pose_rotations(const float* x, const int* row_seq, int64_t F, int S, 
     hipLaunchKernelGGL(pose_rotations_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), lds, (hipStream_t)stream, x, row_seq, (int)F, J,
                        sk, rest, quat, euler, rigid, resid, flags);
     return ew_done("r50_op_pose_rotations");
+}
+
+// ---- 2D-guided refinement of stitched sequences (include/r50_refine.h, refine_kernels.h) ----
+// The optional edge list of the fit ops: E == 0 means no bones (edges is not read); otherwise it is checked as the bone ops check theirs.
+static const char* check_fit_edges(const int* edges, int E, int J, BoneEdges& ed) {
+    for (int q = 0; q < SMOOTH_MAX_J; ++q) ed.parent[q] = ed.child[q] = 0;
+    if (E == 0) return nullptr;
+    if (!edges) return "edges is null with E > 0";
+    unsigned long long is_child;
+    return check_bone_edges(edges, E, J, ed, is_child);
+}
+
+int r50_op_pose_fit_sweeps(const float* x0, const float* rays, const float* conf, const int* seg_start, const int* row_seg, const int* row_seq,
+                           int64_t F, int G, int S, int J, const int* edges, int E, const double* bone_len, double lambda_2d, double lambda_3d,
+                           double lambda_acc, double lambda_bone, double omega, double z_min, int iters, double* workspace, float* out,
+                           void* stream) {
+    if (!x0 || !rays || !seg_start || !row_seg || !row_seq || !workspace || !out)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || G < 1 || G > F || S < 1 || S > G || J < 1 || J > FIT_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID,
+                    "r50_op_pose_fit_sweeps: invalid arguments (need 1 <= S <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (!(std::isfinite(lambda_3d) && lambda_3d > 0.0))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: lambda_3d must be finite and > 0 (it keeps H positive definite)");
+    if (!(std::isfinite(lambda_2d) && lambda_2d >= 0.0 && std::isfinite(lambda_acc) && lambda_acc >= 0.0 && std::isfinite(lambda_bone) &&
+          lambda_bone >= 0.0))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: lambda_2d, lambda_acc and lambda_bone must be finite and >= 0");
+    if (!(omega > 0.0 && omega <= 0.75)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: need 0 < omega <= 0.75");
+    if (!(std::isfinite(z_min) && z_min > 0.0)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: z_min must be finite and > 0");
+    if (iters < 0 || iters > 1000) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: need 0 <= iters <= 1000");
+    if (E < 0) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: edges: need E >= 0");
+    BoneEdges ed;
+    if (const char* why = check_fit_edges(edges, E, J, ed)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_fit_sweeps: edges: ") + why);
+    if (lambda_bone != 0.0 && (E < 1 || !bone_len))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: lambda_bone != 0 needs edges and bone_len");
+    const long long fj = F * J * (long long)sizeof(float);
+    const KinRange in[4] = {{x0, 3 * fj}, {rays, 2 * fj}, {conf ? (const void*)conf : (const void*)x0, conf ? fj : 0},
+                            {bone_len && lambda_bone != 0.0 ? (const void*)bone_len : (const void*)x0,
+                             bone_len && lambda_bone != 0.0 ? (long long)S * E * (long long)sizeof(double) : 0}};
+    const KinRange outs[2] = {{workspace, 2 * F * 3 * J * (long long)sizeof(double)}, {out, 3 * fj}};
+    if (kin_any_overlap(in, 4, outs, 2))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: out or workspace overlaps an input, or each other");
+    if (pose_fit_lds(J) > 65536) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: the LDS budget does not hold");
+    hipStream_t st = (hipStream_t)stream;
+    if (iters == 0) {
+        hipError_t e = hipMemcpyAsync(out, x0, (size_t)(3 * fj), hipMemcpyDeviceToDevice, st);
+        return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_pose_fit_sweeps: ") + hipGetErrorString(e));
+    }
+    FitAdjacency adj;
+    std::memset(&adj, 0, sizeof(adj));
+    int n = 0;
+    for (int j = 0; j < J; ++j) {                                                  // per joint, its edges in edge-list order
+        adj.start[j] = (unsigned char)n;
+        for (int q = 0; q < E; ++q) {
+            if (ed.parent[q] != j && ed.child[q] != j) continue;
+            adj.edge[n] = (unsigned char)q;
+            adj.other[n] = ed.parent[q] == j ? ed.child[q] : ed.parent[q];
+            ++n;
+        }
+    }
+    for (int j = J; j <= FIT_MAX_J; ++j) adj.start[j] = (unsigned char)n;
+    const FitParams pr = {lambda_2d, lambda_3d, lambda_acc, lambda_bone, omega, z_min};
+    double* buf[2] = {workspace, workspace + (size_t)F * 3 * J};
+    const int f = (int)F;
+    for (int k = 0; k < iters; ++k) {                                              // sweep k reads buf[(k - 1) & 1] and writes buf[k & 1]
+        const double* src = k == 0 ? nullptr : buf[(k - 1) & 1];
+        double* dst = buf[k & 1];
+        const bool lastk = k == iters - 1;
+        if (k == 0 && lastk) launch_fit_sweep<true, true>(x0, src, rays, conf, seg_start, row_seg, row_seq, f, J, adj, E, bone_len, pr, dst, out, st);
+        else if (k == 0) launch_fit_sweep<true, false>(x0, src, rays, conf, seg_start, row_seg, row_seq, f, J, adj, E, bone_len, pr, dst, out, st);
+        else if (lastk) launch_fit_sweep<false, true>(x0, src, rays, conf, seg_start, row_seg, row_seq, f, J, adj, E, bone_len, pr, dst, out, st);
+        else launch_fit_sweep<false, false>(x0, src, rays, conf, seg_start, row_seg, row_seq, f, J, adj, E, bone_len, pr, dst, out, st);
+    }
+    return ew_done("r50_op_pose_fit_sweeps");
+}
+
+int r50_op_pose_fit_energy(const float* x, const float* x0, const float* rays, const float* conf, const int* seq_start, const int* row_seg,
+                           int64_t F, int S, int J, const int* edges, int E, const double* bone_len, double z_min, double* energy,
+                           void* stream) {
+    if (!x || !x0 || !rays || !seq_start || !row_seg || !energy) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > FIT_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (!(std::isfinite(z_min) && z_min > 0.0)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: z_min must be finite and > 0");
+    if (E < 0) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: edges: need E >= 0");
+    BoneEdges ed;
+    if (const char* why = check_fit_edges(edges, E, J, ed)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_fit_energy: edges: ") + why);
+    if (bone_len && E < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: bone_len needs edges");
+    const long long fj = F * J * (long long)sizeof(float);
+    const KinRange in[2] = {{x, 3 * fj}, {x0, 3 * fj}};
+    const KinRange outs[1] = {{energy, (long long)S * FIT_ENERGY_SLOTS * (long long)sizeof(double)}};
+    if (kin_any_overlap(in, 2, outs, 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: energy overlaps an input");
+    hipLaunchKernelGGL(pose_fit_energy_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, x, x0, rays, conf, seq_start, row_seg, J, ed,
+                       E, bone_len, z_min, energy);
+    return ew_done("r50_op_pose_fit_energy");
 }
 
 // ---- the cameras of a take in one frame of reference, fused (include/r50_multiview.h, multiview_kernels.h) ----

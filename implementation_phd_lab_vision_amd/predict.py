@@ -279,15 +279,21 @@ class VideoPredictor:
 
     @torch.no_grad()
     def predict(self, frames, box=None, joints2d=None, cam: Optional[dict] = None, frame_skip: int = 1, input_len: int = 15,
-                pred_len: int = 0, name: str = "video", post=None) -> Dict[str, object]:
+                pred_len: int = 0, name: str = "video", post=None, refine=None, conf2d=None) -> Dict[str, object]:
         """The whole pass over every ``frame_skip``-th frame.  ``box``: see ``choose_box`` (``joints2d`` (N, J, 2) pixels of the whole
         frames, of ALL frames; the kept ones are used).  Returns host numpy arrays: ``joints3d`` (n, J, 3), ``spread`` (n,), ``count``
         (n,), ``frame_idx`` (n,) the original frame numbers, ``box`` (4,), ``future3d`` (P, J, 3) if ``pred_len > 0``, ``K`` (3, 3) of
         the resized crop if ``cam`` = ``{"f": .., "c": ..}`` was given, and ``stats``.  With ``post`` (a ``smooth.PostProcess``;
         INTEGRATION.md section W) the fused poses go through it as one sequence of one segment: ``joints3d`` holds the processed poses,
         ``joints3d_raw`` what it would hold without, ``post`` the settings and ``post_short_rows`` the frames a FIR window longer than
-        the video left as they were; ``future3d`` is left as it is."""
+        the video left as they were; ``future3d`` is left as it is.  With ``refine`` (a ``refine.RefineSettings``; INTEGRATION.md
+        section Z; it needs ``joints2d`` and ``cam``, and reads ``conf2d`` (N, J) if given) the fused poses are first fitted to the 2D
+        joints as one sequence of one segment: ``joints3d`` holds the fitted poses (the input of ``post``, if any), ``joints3d_unrefined``
+        what it would hold without, ``refine`` the settings, ``refine_energy_before`` / ``refine_energy_after`` (1, 6) the energy op's
+        terms.  Without ``refine`` every launch and key is what it was."""
         total, h, w = self._check_frames(frames)
+        if refine is not None and (joints2d is None or cam is None):
+            raise ValueError("the 2D fit needs joints2d and the camera's f and c")
         if int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be >= 1, got {frame_skip}")
         frame_idx = np.arange(0, total, int(frame_skip), dtype=np.int64)
@@ -297,13 +303,28 @@ class VideoPredictor:
             if joints2d.shape[0] != total:
                 raise ValueError(f"joints2d covers {joints2d.shape[0]} frames, the video has {total}")
             joints2d = joints2d[frame_idx]
+        if refine is not None:
+            from . import refine as R
+            rays = R.video_rays(joints2d, cam, int(self.head.joints_num))          # refused here, before any launch, if they do not fit
+            if conf2d is not None:
+                conf2d = np.asarray(conf2d)
+                if conf2d.shape[0] != total:
+                    raise ValueError(f"conf2d covers {conf2d.shape[0]} frames, the video has {total}")
+                conf2d = conf2d[frame_idx]
         box_t = choose_box(h, w, box=box, joints2d=joints2d)
         self.stats = {"backbone_frames": 0, "windows": 0, "head_rows": 0}
         got = self.features(kept, box_t)
         feats, flipped = got if self.flip_tta else (got, None)
         joints3d, spread, count = self.poses(feats, flipped, name)
+        unrefined = None
+        if refine is not None:
+            with torch.cuda.device(self.device):
+                unrefined, (joints3d, fit) = joints3d, R.refine_video(joints3d, rays, conf2d, refine)
         out: Dict[str, object] = {"joints3d": joints3d.cpu().numpy(), "spread": spread.cpu().numpy(), "count": count.cpu().numpy(),
                                   "frame_idx": frame_idx, "box": box_t.numpy().copy()}
+        if refine is not None:
+            out["joints3d_unrefined"], out["refine"] = unrefined.cpu().numpy(), np.array(refine.describe())
+            out["refine_energy_before"], out["refine_energy_after"] = fit["energy_before"].cpu().numpy(), fit["energy_after"].cpu().numpy()
         if post is not None:
             n = int(joints3d.shape[0])
             with torch.cuda.device(self.device):
@@ -374,6 +395,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "the rotations, the rest offsets and the rigid reconstruction")
     from .kinematics import add_bvh_flags
     add_bvh_flags(p)
+    p.add_argument("--refine-2d", action="store_true", default=argparse.SUPPRESS,
+                   help="fit the fused poses to the input's 2D joints under a temporal prior before --smooth / --fix-bones / --bvh "
+                        "(INTEGRATION.md section Z); the .npz input must hold `joints2d` and the camera's `f`, `c` (`conf2d` (N,J) is "
+                        "read if present); the file keeps the unfitted poses as joints3d_unrefined")
+    from .refine import add_parameter_flags as add_refine_flags
+    add_refine_flags(p)
     return p
 
 
@@ -387,6 +414,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         if hasattr(args, flag) and not hasattr(args, "bvh"):
             p.error(f"--{flag.replace('_', '-')} needs --bvh")
     bvh_options(args, p.error)
+    video_refine(args, p.error)
     return args
 
 
@@ -399,14 +427,23 @@ def video_post(args: argparse.Namespace, error=None):
     return post_from_args(args, getattr(args, "smooth", None), getattr(args, "fix_bones", False), error or raise_)
 
 
+def video_refine(args: argparse.Namespace, error=None):
+    """The ``refine.RefineSettings`` of parsed arguments, or None without ``--refine-2d``."""
+    from .refine import settings_from_args
+
+    def raise_(msg):
+        raise ValueError(msg)
+    return settings_from_args(args, hasattr(args, "refine_2d"), "--refine-2d", error or raise_)
+
+
 def load_input(path: str) -> Dict[str, object]:
-    """``frames`` (memory-mapped for a ``.npy``) and whatever annotations the file holds: ``box``, ``joints2d``, ``cam``."""
+    """``frames`` (memory-mapped for a ``.npy``) and whatever annotations the file holds: ``box``, ``joints2d``, ``conf2d``, ``cam``."""
     if path.endswith(".npz"):
         z = np.load(path, allow_pickle=False)
         if "frames" not in z.files:
             raise ValueError(f"{path}: no `frames` array in the file (it holds {sorted(z.files)}); expected (N,H,W,3) uint8 frames")
         item: Dict[str, object] = {"frames": z["frames"]}
-        for key in ("box", "joints2d"):
+        for key in ("box", "joints2d", "conf2d"):
             if key in z.files:
                 item[key] = z[key]
         if ("f" in z.files) != ("c" in z.files):
@@ -442,6 +479,7 @@ def render_prediction(outdir: str, predictor: VideoPredictor, frames, res: Dict[
 def main(argv: Optional[List[str]] = None) -> List[str]:
     args = parse_args(argv)
     post = video_post(args)
+    fit = video_refine(args)
     device = torch.device(args.device)
     if device.type != "cuda" or not torch.cuda.is_available():
         raise _lib.R50Error("predict runs on an MI355X only; there is no CPU fallback")
@@ -456,6 +494,10 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
         kinematics.skeleton_for(infer_head_dims(head_state)[1])    # another joint count has no built-in skeleton: refused before any launch
         bvh_fps, bvh_scale = kinematics.bvh_options(args, None)
     items = [load_input(p) for p in args.frames]
+    if fit is not None:                      # refused before the backbone is built
+        for path, item in zip(args.frames, items):
+            if "joints2d" not in item or "cam" not in item:
+                raise ValueError(f"{path}: --refine-2d needs `joints2d` and the camera's `f` and `c` in the input .npz")
     state_dict, source = _resolve_weights(args)
     print(f"backbone weights: {source}")
     backbone = ResNet50Backbone(state_dict=state_dict, max_batch=args.frame_batch, precision=args.precision).to(device).eval()
@@ -468,7 +510,8 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
         name = os.path.splitext(os.path.basename(path))[0]
         res = predictor.predict(item["frames"], box=args.box if args.box is not None else item.get("box"), joints2d=item.get("joints2d"),
                                 cam=item.get("cam"), frame_skip=args.frame_skip, input_len=args.input_len, pred_len=args.pred_len, name=name,
-                                **({} if post is None else {"post": post}))
+                                **({} if post is None else {"post": post}),
+                                **({} if fit is None else {"refine": fit, "conf2d": item.get("conf2d")}))
         stats = res.pop("stats")
         out_path = os.path.join(args.out, name + "_poses.npz")
         rigid_note = ""

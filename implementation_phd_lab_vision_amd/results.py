@@ -167,6 +167,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="write one BVH file per sequence into DIR (--dense-rigid)")
     from .kinematics import add_bvh_flags
     add_bvh_flags(p)
+    p.add_argument("--dense-refine", action="store_true", default=argparse.SUPPRESS,
+                   help="also fit every stitched sequence to the cache's 2D joints under a temporal prior and score the result beside the "
+                        "raw poses (--dense; INTEGRATION.md section Z); the cache's 2D joints are ground truth: an upper bound")
+    p.add_argument("--dense-refine-noise-px", type=float, default=argparse.SUPPRESS, metavar="PX",
+                   help="add seeded Gaussian noise of PX pixels of the 224 crop to the 2D joints (--dense-refine; default 0)")
+    p.add_argument("--dense-refine-seed", type=int, default=argparse.SUPPRESS, metavar="N", help="seed of that noise (default 0)")
+    from .refine import add_parameter_flags as add_refine_flags
+    add_refine_flags(p)
     return p
 
 
@@ -177,6 +185,15 @@ def dense_post(args: argparse.Namespace, error=None):
     def raise_(msg):
         raise ValueError(msg)
     return post_from_args(args, getattr(args, "dense_smooth", None), getattr(args, "dense_fix_bones", False), error or raise_)
+
+
+def dense_refine(args: argparse.Namespace, error=None):
+    """The ``refine.RefineSettings`` of parsed arguments, or None without ``--dense-refine``."""
+    from .refine import settings_from_args
+
+    def raise_(msg):
+        raise ValueError(msg)
+    return settings_from_args(args, hasattr(args, "dense_refine"), "--dense-refine", error or raise_)
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -226,6 +243,14 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--{flag.replace('_', '-')} needs --dense-bvh")
     from .kinematics import bvh_options
     bvh_options(args, p.error)
+    if hasattr(args, "dense_refine") and not args.dense:
+        p.error("--dense-refine needs --dense")
+    for flag in ("dense_refine_noise_px", "dense_refine_seed"):
+        if hasattr(args, flag) and not hasattr(args, "dense_refine"):
+            p.error(f"--{flag.replace('_', '-')} needs --dense-refine")
+    if not (np.isfinite(getattr(args, "dense_refine_noise_px", 0.0)) and getattr(args, "dense_refine_noise_px", 0.0) >= 0.0):
+        p.error(f"--dense-refine-noise-px must be finite and >= 0, got {args.dense_refine_noise_px}")
+    dense_refine(args, p.error)              # a parameter flag without --dense-refine, or a refused parameter
     if args.dtw and args.pred_len <= 0:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
@@ -476,17 +501,18 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in detail_lines(detail, args.input_len, args.pred_len):
             print(line)
 
-    dense, multi, rigid = None, None, None
+    dense, multi, rigid, fitted = None, None, None, None
     if args.dense:                           # every video frame once: the clips of a sequence fused per frame
         from .sequences import dense_export, dense_lines, dense_npz, dense_post_lines, evaluate_dense
         from . import multiview as mv
         post, mv_options = dense_post(args), mv.options_from_args(args)
         want_rigid = hasattr(args, "dense_rigid")
+        fit = dense_refine(args)
         if want_rigid:
             from . import kinematics
             kinematics.skeleton_for(int(head.joints_num))        # refused before the pass if there is no skeleton for the head's joints
         dense = evaluate_dense(head, test_set, fuse=args.dense_fuse,
-                               keep_poses=args.dense_out is not None or mv_options is not None or want_rigid,
+                               keep_poses=args.dense_out is not None or mv_options is not None or want_rigid or fit is not None,
                                **({} if post is None else {"post": post}))
         for line in dense_lines(dense) + (dense_post_lines(dense) if post is not None else []):
             print(line)
@@ -501,6 +527,12 @@ def main(argv: Optional[List[str]] = None) -> str:
             if hasattr(args, "dense_bvh"):
                 files = kinematics.write_dense_bvh(args.dense_bvh, dense, rigid, None, *kinematics.bvh_options(args, None))
                 print(f"Dense | rigid   {len(files)} BVH files written to: {args.dense_bvh}")
+        if fit is not None:                  # the stitched poses fitted to the cache's 2D joints, scored beside the raw ones (section Z)
+            from . import refine
+            fitted = refine.evaluate_refine(dense, test_set, device, fit, getattr(args, "dense_refine_noise_px", 0.0),
+                                            getattr(args, "dense_refine_seed", 0), keep=args.dense_out is not None)
+            for line in refine.refine_lines(dense, fitted):
+                print(line)
 
     dtw = None
     if args.dtw:                             # the protocols' pass over the forecasts: every test clip once, in store order
@@ -572,9 +604,12 @@ def main(argv: Optional[List[str]] = None) -> str:
             extra.update(mv.multiview_npz(multi))
         if rigid is not None:
             extra.update(kinematics.rigid_npz(rigid))
+        if fitted is not None:
+            extra.update(refine.refine_npz(fitted))
         if args.dense_out is not None:
             os.makedirs(os.path.dirname(args.dense_out) or ".", exist_ok=True)
-            np.savez_compressed(args.dense_out, **dense_export(dense), **({} if multi is None else mv.multiview_export(multi)))
+            np.savez_compressed(args.dense_out, **dense_export(dense), **({} if multi is None else mv.multiview_export(multi)),
+                                **({} if fitted is None else refine.refine_export(fitted)))
             print(f"Dense | stitched sequences saved to: {args.dense_out}")
     if dtw is not None:
         extra.update(dtw_arrays(dtw))

@@ -1,0 +1,245 @@
+"""2D-guided refinement without a GPU: the sixth public header include/r50_refine.h bound, exported and
+guard-banded; every refusal of its ops before any launch; the parsers; ``rays_from_pixels`` and ``dense_rays`` on a cache whose 2D joints
+are the projection of its 3D joints; and the conditions the issue puts on the numpy definition of tests/refine_reference.py."""
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from tests import refine_reference as RR
+from tests.test_kinematics_cpu import PREDICT_KEYS, RESULTS_KEYS
+
+ROOT = Path(__file__).resolve().parents[1]
+HEADER = ROOT / "include" / "r50_refine.h"
+OPS = {"r50_op_pose_fit_sweeps", "r50_op_pose_fit_energy"}
+
+
+def _prototypes():
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    protos = re.findall(r"^\s*(?:int|int64_t|size_t)\s+(r50_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.M | re.S)
+    assert protos, "no prototypes parsed from include/r50_refine.h"
+    return [(name, len([a for a in args.split(",") if a.strip()])) for name, args in protos]
+
+
+def test_every_prototype_of_the_refine_header_is_bound_exported_and_guard_banded(lib_built):
+    from implementation_phd_lab_vision_amd import _lib
+    from tests import test_refine_gpu as T
+    protos = _prototypes()
+    names = [n for n, _ in protos]
+    assert set(names) == OPS == set(_lib._SIGNATURES_REFINE) and len(names) == len(set(names))
+    assert set(re.findall(r"\b(r50_op_[a-z0-9_]+)", HEADER.read_text())) == OPS, "the header names only its own two ops, comments included"
+    covered = set()
+    for row in T.ROWS_REFINE:
+        covered.update(row.ops)
+    assert covered == OPS and len({row.id for row in T.ROWS_REFINE}) == len(T.ROWS_REFINE)
+    others = [(ROOT / "include" / h).read_text() for h in ("r50.h", "r50_hal.h", "r50_smooth.h", "r50_multiview.h", "r50_kinematics.h")]
+    tables = (_lib._SIGNATURES, _lib._SIGNATURES_HAL, _lib._SIGNATURES_SMOOTH, _lib._SIGNATURES_MULTIVIEW, _lib._SIGNATURES_KINEMATICS)
+    for name, arity in protos:
+        assert len(_lib._SIGNATURES_REFINE[name][1]) == arity, name
+        assert hasattr(lib_built, name), f"{name} declared in r50_refine.h but not exported by libr50hip.so"
+        assert getattr(lib_built, name).argtypes == _lib._SIGNATURES_REFINE[name][1]
+        assert not any(name in table for table in tables)
+        assert name not in _lib.EXPORTED_SYMBOLS and not any(name in text for text in others)
+    assert "r50_refine.h" in (ROOT / "implementation_phd_lab_vision_amd" / "_lib.py").read_text().split("def _source_digest")[1].split("def ")[0]
+    abi = (ROOT / "implementation_phd_lab_vision_amd" / "csrc" / "r50_abi.hip").read_text()
+    assert '#include "refine_kernels.h"' in abi and "r50_refine.h" in abi
+
+
+def test_every_refusal_returns_before_any_launch(lib_built):
+    """No device is needed: each call is refused on its arguments, with the op's name in the message.  The pointers are made-up addresses
+    that nothing dereferences."""
+    import ctypes
+    x0, rays, conf, seg_start, row_seg, row_seq, lens, ws, out, x, energy = (0x1000000 * k for k in range(1, 12))
+    ints = lambda v: (ctypes.c_int * len(v))(*v)                                    # noqa: E731
+    edges = ints([v for e in RR.EDGES17 for v in e])
+    bad_order = ints([1, 2, 0, 1] + list(edges)[4:])
+    twice = ints([0, 1, 0, 1] + list(edges)[4:])
+    out_of_range = ints([0, 17] + list(edges)[2:])
+    loop = ints([3, 3] + list(edges)[2:])
+    f, j = 12, 17
+    n_bytes = f * j * 3 * 4
+    inf, nan = float("inf"), float("nan")
+
+    def refused(name, rc, why):
+        assert rc == -1, (name, why, rc)                                                # R50_ERR_INVALID: refused, not a launch that failed
+        assert name.encode() in lib_built.r50_last_error(None), (name, why)
+
+    ok = dict(x0=x0, rays=rays, conf=conf, seg_start=seg_start, row_seg=row_seg, row_seq=row_seq, F=f, G=3, S=2, J=j, edges=edges, E=16,
+              lens=lens, l2d=1.0, l3d=1.0, lacc=1.0, lbone=1.0, omega=0.6, z_min=0.1, iters=5, ws=ws, out=out)
+    bad = (dict(x0=None), dict(rays=None), dict(seg_start=None), dict(row_seg=None), dict(row_seq=None), dict(ws=None), dict(out=None),
+           dict(F=0), dict(F=-1), dict(F=2 ** 31 // 192 + 1), dict(G=0), dict(G=13), dict(S=0), dict(S=4), dict(J=0), dict(J=65),
+           dict(l3d=0.0), dict(l3d=-1.0), dict(l3d=inf), dict(l3d=nan), dict(l2d=-1.0), dict(l2d=inf), dict(l2d=nan), dict(lacc=-0.5),
+           dict(lacc=nan), dict(lbone=-1.0), dict(lbone=inf), dict(omega=0.0), dict(omega=0.76), dict(omega=0.8), dict(omega=-0.1),
+           dict(omega=nan), dict(z_min=0.0), dict(z_min=-1.0), dict(z_min=nan), dict(z_min=inf), dict(iters=-1), dict(iters=1001),
+           dict(E=-1), dict(E=17), dict(edges=None), dict(edges=bad_order), dict(edges=twice), dict(edges=out_of_range), dict(edges=loop),
+           dict(lens=None), dict(E=0, edges=None),                                      # lambda_bone != 0 without lengths or edges
+           dict(out=x0), dict(out=x0 + n_bytes - 4), dict(out=x0 - n_bytes + 4), dict(out=rays), dict(out=conf), dict(ws=x0),
+           dict(ws=x0 - 2 * 2 * n_bytes + 8), dict(out=ws), dict(out=ws + 2 * 2 * n_bytes - 8), dict(ws=lens))
+    for kw in bad:
+        a = dict(ok, **kw)
+        refused("r50_op_pose_fit_sweeps",
+                lib_built.r50_op_pose_fit_sweeps(a["x0"], a["rays"], a["conf"], a["seg_start"], a["row_seg"], a["row_seq"], a["F"], a["G"], a["S"],
+                                                 a["J"], a["edges"], a["E"], a["lens"], a["l2d"], a["l3d"], a["lacc"], a["lbone"], a["omega"],
+                                                 a["z_min"], a["iters"], a["ws"], a["out"], None), kw)
+    ok = dict(x=x, x0=x0, rays=rays, conf=conf, seq_start=seg_start, row_seg=row_seg, F=f, S=2, J=j, edges=edges, E=16, lens=lens, z_min=0.1,
+              energy=energy)
+    bad = (dict(x=None), dict(x0=None), dict(rays=None), dict(seq_start=None), dict(row_seg=None), dict(energy=None), dict(F=0),
+           dict(F=2 ** 31 // 192 + 1), dict(S=0), dict(S=13), dict(J=0), dict(J=65), dict(z_min=0.0), dict(z_min=nan), dict(z_min=inf),
+           dict(E=-1), dict(E=17), dict(edges=None), dict(edges=bad_order), dict(edges=twice), dict(edges=out_of_range), dict(edges=loop),
+           dict(E=0, edges=None), dict(energy=x), dict(energy=x0 + n_bytes - 8), dict(energy=x - 2 * 6 * 8 + 8))
+    for kw in bad:
+        a = dict(ok, **kw)
+        refused("r50_op_pose_fit_energy",
+                lib_built.r50_op_pose_fit_energy(a["x"], a["x0"], a["rays"], a["conf"], a["seq_start"], a["row_seg"], a["F"], a["S"], a["J"],
+                                                 a["edges"], a["E"], a["lens"], a["z_min"], a["energy"], None), kw)
+
+
+def test_parsers_flag_rules_and_unchanged_default_namespaces(capsys):
+    from implementation_phd_lab_vision_amd import predict, refine, results
+    base_p = ["--frames", "a.npz", "--model_path", "m", "--out", "o"]
+    base_r = ["--features_root", "f", "--preprocessed_root", "v", "--model_path", "m"]
+    assert sorted(vars(predict.parse_args(base_p))) == PREDICT_KEYS
+    assert sorted(vars(results.parse_args(base_r))) == RESULTS_KEYS
+    assert sorted(vars(results.parse_args(base_r + ["--dense"]))) == RESULTS_KEYS
+    a = predict.parse_args(base_p + ["--refine-2d"])
+    assert a.refine_2d is True and sorted(vars(a)) == sorted(PREDICT_KEYS + ["refine_2d"])
+    assert predict.video_refine(a) == refine.RefineSettings() and predict.video_refine(predict.parse_args(base_p)) is None
+    d = refine.RefineSettings()
+    assert (d.iters, d.lambda_2d, d.lambda_3d, d.lambda_acc, d.lambda_bone, d.omega, d.z_min) == (50, 1.0, 1.0, 1.0, 0.0, 0.6, 0.1)
+    a = predict.parse_args(base_p + ["--refine-2d", "--refine-iters", "7", "--refine-lambda-2d", "2", "--refine-lambda-3d", "0.5",
+                                     "--refine-lambda-acc", "3", "--refine-lambda-bone", "0.25", "--refine-omega", "0.7", "--refine-z-min", "0.2"])
+    s = predict.video_refine(a)
+    assert (s.iters, s.lambda_2d, s.lambda_3d, s.lambda_acc, s.lambda_bone, s.omega, s.z_min) == (7, 2.0, 0.5, 3.0, 0.25, 0.7, 0.2)
+    assert "iters=7" in s.describe() and "bone=0.25 z_min=0.2 over 16 edges" in s.describe() and "edges" not in d.describe()
+    a = results.parse_args(base_r + ["--dense", "--dense-refine"])
+    assert a.dense_refine is True and sorted(vars(a)) == sorted(RESULTS_KEYS + ["dense_refine"]) and results.dense_refine(a) == d
+    a = results.parse_args(base_r + ["--dense", "--dense-refine", "--dense-refine-noise-px", "2", "--dense-refine-seed", "3", "--refine-iters", "0"])
+    assert (a.dense_refine_noise_px, a.dense_refine_seed, results.dense_refine(a).iters) == (2.0, 3, 0)
+    for bad in (["--refine-iters", "5"], ["--refine-omega", "0.5"], ["--refine-2d", "--refine-omega", "0.8"], ["--refine-2d", "--refine-omega", "0"],
+                ["--refine-2d", "--refine-lambda-3d", "0"], ["--refine-2d", "--refine-lambda-2d", "-1"], ["--refine-2d", "--refine-iters", "1001"],
+                ["--refine-2d", "--refine-iters", "-1"], ["--refine-2d", "--refine-z-min", "0"], ["--refine-2d", "--refine-lambda-acc", "nan"]):
+        with pytest.raises(SystemExit):
+            predict.parse_args(base_p + bad)
+    for bad in (["--dense-refine"], ["--dense", "--refine-iters", "5"], ["--dense", "--dense-refine-noise-px", "2"],
+                ["--dense", "--dense-refine-seed", "2"], ["--dense", "--dense-refine", "--dense-refine-noise-px", "-1"],
+                ["--dense", "--dense-refine", "--refine-omega", "0.9"]):
+        with pytest.raises(SystemExit):
+            results.parse_args(base_r + bad)
+    err = capsys.readouterr().err
+    assert "--dense-refine needs --dense" in err and "--refine-iters needs --refine-2d" in err and "--refine-iters needs --dense-refine" in err
+    for kw in (dict(iters=1.5), dict(omega=0.75000001), dict(lambda_3d=0.0), dict(lambda_bone=float("inf")), dict(z_min=0.0),
+               dict(lambda_bone=1.0, edges=((1, 2), (0, 1)))):
+        with pytest.raises(ValueError):
+            refine.RefineSettings(**kw)
+    refine.RefineSettings(omega=0.75, iters=1000, lambda_2d=0.0, lambda_acc=0.0)
+
+
+def test_rays_from_pixels_and_its_refusals():
+    from implementation_phd_lab_vision_amd import refine
+    rng = np.random.default_rng(3)
+    uv = rng.uniform(0.0, 1000.0, (5, 17, 2))
+    k = np.array([[1100.0, 0.0, 510.0], [0.0, 1200.0, 490.0], [0.0, 0.0, 1.0]])
+    want = ((uv - [510.0, 490.0]) / [1100.0, 1200.0]).astype(np.float32)
+    assert np.array_equal(refine.rays_from_pixels(uv, k), want)
+    assert np.array_equal(refine.rays_from_pixels(uv, ([1100.0, 1200.0], [510.0, 490.0])), want)
+    assert np.array_equal(refine.rays_from_pixels(torch.from_numpy(uv), (torch.tensor([[1100.0, 1200.0]]), np.array([[510.0], [490.0]]))), want)
+    ks = np.stack([k, k * [[2.0, 1.0, 1.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0]]])
+    both = refine.rays_from_pixels(np.stack([uv, uv]), ks)                           # a K per clip
+    assert np.array_equal(both[0], want) and np.array_equal(both[1, ..., 1], want[..., 1]) and not np.array_equal(both[1, ..., 0], want[..., 0])
+    skew, row, neg = k.copy(), k.copy(), k.copy()
+    skew[0, 1], row[2, 0], neg[0, 0] = 0.5, 1e-3, -1100.0
+    for bad in (skew, row, neg, k[:2], np.eye(4)):
+        with pytest.raises(ValueError):
+            refine.rays_from_pixels(uv, bad)
+    with pytest.raises(ValueError, match="skew"):
+        refine.rays_from_pixels(uv, skew)
+    with pytest.raises(ValueError, match=r"\[0, 0, 1\]"):
+        refine.rays_from_pixels(uv, row)
+    for bad in (([1100.0], [510.0, 490.0]), ([1100.0, 0.0], [510.0, 490.0]), ([1100.0, float("nan")], [510.0, 490.0])):
+        with pytest.raises(ValueError):
+            refine.rays_from_pixels(uv, bad)
+    with pytest.raises(ValueError):
+        refine.rays_from_pixels(uv[..., :1], k)
+    with pytest.raises(ValueError):
+        refine.rays_from_pixels(uv, np.stack([k] * 4))                              # four cameras, five leading entries
+    with pytest.raises(ValueError, match="no CPU fallback"):                        # poses on the host: refused, not computed there
+        refine.refine_sequences(torch.zeros(4, 17, 3), torch.zeros(4, 17, 2), None, (np.array([0, 4]), np.arange(4)), refine.RefineSettings())
+    with pytest.raises(ValueError, match="keep_poses"):
+        refine.evaluate_refine({"group_names": ["walk"]}, None)
+
+
+def test_dense_rays_take_the_first_contributing_clip_and_give_the_ground_truth_back(tmp_path):
+    """A cache whose ``joints2d`` is the projection of ``joints3d`` through each clip's own ``K`` (tests/refine_reference.py builds it; the
+    other synthetic caches hold random 2D joints): the rays times the ground-truth depth are the ground-truth x and y, whichever clip a
+    frame is read through, to the fp32 rounding of the pixels and of the rays."""
+    from implementation_phd_lab_vision_amd import refine
+    from implementation_phd_lab_vision_amd.feature_store import DeviceFeatureStore
+    from implementation_phd_lab_vision_amd.sequences import SequenceTable
+    root = RR.make_projected_cache(tmp_path / "features")
+    store = DeviceFeatureStore(str(root), subjects=[9], test_set=True, device="cpu")
+    t = int(store.feats.shape[1])
+    table = SequenceTable.from_clips(store.item_clips(), t)
+    gt = np.zeros((table.frames, 17, 3), dtype=np.float32)
+    all_gt = store.get_batch(list(range(len(store))))[1].numpy()
+    first = table.src[table.offsets[:-1]]
+    gt[:] = all_gt.reshape(-1, 17, 3)[first]
+    dense = {"pred": gt, "seq_start": table.seq_start, "frame_idx": table.idx}
+    rays = refine.dense_rays(store, dense)
+    assert rays.shape == (table.frames, 17, 2) and rays.dtype == np.float32
+    assert np.diff(table.offsets).max() >= 2 and (first // t).max() > 0              # frames with several clips; more than one clip used
+    back = rays.astype(np.float64) * gt[..., 2:3].astype(np.float64)
+    # a pixel near 1000 rounds by 2^-24 * 1000 = 6e-5 px, over a focal length of at least 1000 and times a depth of at most 6 m: 3.6e-7 m;
+    # the ray's own fp32 rounding, 2^-24 * 0.25 * 6 m = 9e-8 m; the ground truth's, 6e-8: 5.1e-7 m in all
+    err = np.abs(back - gt[..., :2]).max()
+    print(f"dense_rays: rays * depth against the ground truth's xy: {err:.3e} m (bar 5.1e-7)")
+    assert err <= 5.1e-7
+    # the same rays from ANY contributor, so the choice of the first is a convention, not a source of error
+    last = table.src[table.offsets[1:] - 1]
+    uv = store.get_batch(list(range(len(store))))[2].numpy().reshape(-1, 17, 2)[last].astype(np.float64)
+    k = store.get_batch((last // t).tolist())[3].numpy().astype(np.float64)
+    other = (uv - k[:, None, :2, 2]) / np.stack([k[:, 0, 0], k[:, 1, 1]], axis=-1)[:, None]
+    assert np.abs(other - rays).max() <= 2.0 ** -24 * 1000.0 / 1000.0 * 2 + 2.0 ** -24
+    with pytest.raises(ValueError, match="not computed from this store"):
+        refine.dense_rays(store, dict(dense, pred=gt[:-1]))
+
+
+@pytest.mark.parametrize("noise_px", [0.0, 2.0], ids=["exact2d", "noise2px"])
+def test_the_reference_descends_and_the_error_only_falls(noise_px):
+    """The issue's conditions on the definition, on its seeded sequence (300 rows, two segments, J 17, defaults, 50 sweeps): the energy
+    never rises by more than 1e-12 of itself, and the mean joint error against the ground truth falls at every sweep."""
+    c = RR.prototype_sequence(0, noise_px=noise_px)
+    trace = []
+    RR.refine(c["x0"], c["rays"], None, c["seq_start"], c["idx"], iters=50, trace=trace)
+    assert len(trace) == 51 and len(set(RR.row_tables(c["seq_start"], c["idx"])[1])) == 2
+    en = [RR.total(RR.energy(x, c["x0"], c["rays"], None, c["seq_start"], c["idx"])) for x in trace]
+    err = [float(np.linalg.norm(x - c["gt"], axis=2).mean()) for x in trace]
+    root = [float(np.linalg.norm((x - x[:, :1]) - (c["gt"] - c["gt"][:, :1]), axis=2).mean()) for x in trace]
+    print(f"noise {noise_px} px: energy {en[0]:.4f} -> {en[-1]:.4f} (last relative change {(en[-2] - en[-1]) / en[-1]:.1e}), mean joint error "
+          f"{err[0] * 1000:.1f} -> {err[-1] * 1000:.1f} mm, root-relative {root[0] * 1000:.1f} -> {root[-1] * 1000:.1f} mm")
+    assert all(en[k + 1] <= en[k] * (1.0 + 1e-12) for k in range(50))
+    assert all(err[k + 1] < err[k] for k in range(50))
+    assert err[-1] < 0.75 * err[0]
+
+
+def test_the_reference_exact_cases_and_the_step_bound():
+    c = RR.ragged_case(5, 17, True)
+    x0 = c["x0"]
+    same = RR.refine(x0, c["rays"], c["conf"], c["seq_start"], c["idx"], iters=3, l2d=0.0, lacc=0.0)
+    assert np.array_equal(same, x0.astype(np.float64))
+    only2d = RR.refine(x0, c["rays"], c["conf"], c["seq_start"], c["idx"], iters=3, lacc=0.0)
+    off = c["conf"] == 0.0
+    assert off.any() and np.array_equal(only2d[off], x0.astype(np.float64)[off]) and not np.array_equal(only2d[~off], x0.astype(np.float64)[~off])
+    # omega = 0.8 is past the bound of the analysis: the high-frequency mode of a long segment grows
+    p = RR.prototype_sequence(0)
+    en = [RR.total(RR.energy(RR.refine(p["x0"], p["rays"], None, p["seq_start"], p["idx"], iters=k, omega=0.8, l2d=0.0, l3d=1e-3), p["x0"],
+                             p["rays"], None, p["seq_start"], p["idx"]), l2d=0.0, l3d=1e-3) for k in (0, 40, 80)]
+    assert en[2] > en[1] > en[0]
+
+
+def test_the_product_never_imports_the_oracle():
+    pkg = ROOT / "implementation_phd_lab_vision_amd"
+    for path in [pkg / "refine.py", pkg / "predict.py", pkg / "results.py", ROOT / "scripts" / "bench_refine.py"]:
+        text = path.read_text()
+        assert "refine_reference" not in text and "from tests" not in text and "import tests" not in text, path
