@@ -3779,6 +3779,49 @@ __device__ __forceinline__ void resize_taps(int i, int in_size, int out_size, in
     }
 }
 
+// Copy `nd` dwords of a source row, from the address `s` at or below the crop's first byte, to LDS.  The last dword may reach up to 3
+// bytes past the row: it stays inside the buffer except at its very end (`end`), where the tail is read byte by byte.
+__device__ __forceinline__ void resize_stage_row(const unsigned* s, int nd, const unsigned char* end, unsigned* l) {
+    for (int i = threadIdx.x; i < nd; i += 256) {
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(s + i);
+        l[i] = (p + 4 <= end) ? s[i] : (unsigned)p[0] | ((p + 1 < end ? (unsigned)p[1] : 0u) << 8) | ((p + 2 < end ? (unsigned)p[2] : 0u) << 16);
+    }
+}
+
+// Four consecutive output pixels xq * 4 .. xq * 4 + 3 of channel c from the two staged rows, packed into one dword; `mirror`: pixel x
+// takes what the plain resize puts at out - 1 - x.  (wy0, wy1): the row's vertical taps from resize_taps.
+__device__ __forceinline__ unsigned resize_quad(const unsigned char* row0, const unsigned char* row1, int xq, int c, int ww, int out, int px,
+                                                int py, bool float_mode, bool mirror, int wy0, int wy1) {
+    const int rx = 1 << (px - 1), ry = 1 << (py - 1);
+    unsigned packed = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int xo = xq * 4 + q;
+        int x0, wx0, wx1;
+        resize_taps(mirror ? out - 1 - xo : xo, ww, out, px, float_mode, x0, wx0, wx1);
+        const int x1 = min(x0 + 1, ww - 1);                       // float mode: same second index (index0 + (index0 < size-1))
+        int v;
+        if (float_mode) {
+            // ATen cpu_upsample_linear_channels_last: out = p00*w00 + p01*w01 + p10*w10 + p11*w11 with w_ij = h_i * w_j
+            // (fp32; the CPU build contracts some of it into FMAs -- this association is the closest match found)
+            const float lx0 = __int_as_float(wx0), lx1 = __int_as_float(wx1), ly0 = __int_as_float(wy0), ly1 = __int_as_float(wy1);
+            const float w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1;
+            const float p00 = (float)row0[x0 * 3 + c], p01 = (float)row0[x1 * 3 + c];
+            const float p10 = (float)row1[x0 * 3 + c], p11 = (float)row1[x1 * 3 + c];
+            const float s0f = __fmaf_rn(p01, w01, p00 * w00), s1f = __fmaf_rn(p11, w11, p10 * w10);
+            v = (int)rintf(s0f + s1f);                                  // torch.round = half to even; then .to(uint8)
+        } else {
+            int h0 = (wx0 * (int)row0[x0 * 3 + c] + wx1 * (int)row0[x1 * 3 + c] + rx) >> px;
+            int h1 = (wx0 * (int)row1[x0 * 3 + c] + wx1 * (int)row1[x1 * 3 + c] + rx) >> px;
+            h0 = min(max(h0, 0), 255); h1 = min(max(h1, 0), 255);        // the uint8 intermediate image
+            v = (wy0 * h0 + wy1 * h1 + ry) >> py;
+        }
+        v = min(max(v, 0), 255);
+        packed |= (unsigned)v << (8 * q);
+    }
+    return packed;
+}
+
 // One workgroup = one output row of one frame.  The two source rows it needs (the crop's width, 3 bytes per pixel) are
 // copied to LDS with coalesced 4-byte loads (a thread reading its 12 tap bytes straight from global memory ran at
 // 1.3 TB/s of useful traffic); then 56 threads x 3 channels... every thread produces 4 consecutive output pixels of one
@@ -3803,49 +3846,15 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const ResizeArgs a)
     const int nd0 = (sh0 + row_bytes + 3) >> 2, nd1 = (sh1 + row_bytes + 3) >> 2;
     unsigned* l0 = reinterpret_cast<unsigned*>(rs_smem);
     unsigned* l1 = reinterpret_cast<unsigned*>(rs_smem + row_pad);
-    // the last dword of a copy may reach up to 3 bytes past the row: it stays inside the frame buffer except at the very end
-    // of the tensor, where the tail is read byte by byte
     const unsigned char* tensor_end = a.src + (size_t)a.T * a.H * a.W * 3;
-    for (int i = threadIdx.x; i < nd0; i += 256) {
-        const unsigned char* p = reinterpret_cast<const unsigned char*>(s0 + i);
-        l0[i] = (p + 4 <= tensor_end) ? s0[i] : (unsigned)p[0] | ((p + 1 < tensor_end ? (unsigned)p[1] : 0u) << 8) | ((p + 2 < tensor_end ? (unsigned)p[2] : 0u) << 16);
-    }
-    for (int i = threadIdx.x; i < nd1; i += 256) {
-        const unsigned char* p = reinterpret_cast<const unsigned char*>(s1 + i);
-        l1[i] = (p + 4 <= tensor_end) ? s1[i] : (unsigned)p[0] | ((p + 1 < tensor_end ? (unsigned)p[1] : 0u) << 8) | ((p + 2 < tensor_end ? (unsigned)p[2] : 0u) << 16);
-    }
+    resize_stage_row(s0, nd0, tensor_end, l0);
+    resize_stage_row(s1, nd1, tensor_end, l1);
     __syncthreads();
     const unsigned char* row0 = rs_smem + sh0;
     const unsigned char* row1 = rs_smem + row_pad + sh1;
-    const int rx = 1 << (a.px - 1), ry = 1 << (a.py - 1);
     for (int item = threadIdx.x; item < quads * 3; item += 256) {
         const int c = item / quads, xq = item - c * quads;
-        unsigned packed = 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int xo = xq * 4 + q;
-            int x0, wx0, wx1;
-            resize_taps(a.hflip ? a.out - 1 - xo : xo, a.ww, a.out, a.px, a.float_mode != 0, x0, wx0, wx1);
-            const int x1 = min(x0 + 1, a.ww - 1);                       // float mode: same second index (index0 + (index0 < size-1))
-            int v;
-            if (a.float_mode) {
-                // ATen cpu_upsample_linear_channels_last: out = p00*w00 + p01*w01 + p10*w10 + p11*w11 with w_ij = h_i * w_j
-                // (fp32; the CPU build contracts some of it into FMAs -- this association is the closest match found)
-                const float lx0 = __int_as_float(wx0), lx1 = __int_as_float(wx1), ly0 = __int_as_float(wy0), ly1 = __int_as_float(wy1);
-                const float w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1;
-                const float p00 = (float)row0[x0 * 3 + c], p01 = (float)row0[x1 * 3 + c];
-                const float p10 = (float)row1[x0 * 3 + c], p11 = (float)row1[x1 * 3 + c];
-                const float s0f = __fmaf_rn(p01, w01, p00 * w00), s1f = __fmaf_rn(p11, w11, p10 * w10);
-                v = (int)rintf(s0f + s1f);                                  // torch.round = half to even; then .to(uint8)
-            } else {
-                int h0 = (wx0 * (int)row0[x0 * 3 + c] + wx1 * (int)row0[x1 * 3 + c] + rx) >> a.px;
-                int h1 = (wx0 * (int)row1[x0 * 3 + c] + wx1 * (int)row1[x1 * 3 + c] + rx) >> a.px;
-                h0 = min(max(h0, 0), 255); h1 = min(max(h1, 0), 255);        // the uint8 intermediate image
-                v = (wy0 * h0 + wy1 * h1 + ry) >> a.py;
-            }
-            v = min(max(v, 0), 255);
-            packed |= (unsigned)v << (8 * q);
-        }
+        const unsigned packed = resize_quad(row0, row1, xq, c, a.ww, a.out, a.px, a.py, a.float_mode != 0, a.hflip != 0, wy0, wy1);
         const size_t plane = (size_t)a.out * a.out;
         *reinterpret_cast<unsigned*>(a.dst + ((size_t)t * 3 + c) * plane + (size_t)yo * a.out + xq * 4) = packed;
     }

@@ -1,5 +1,5 @@
 // Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h,
-// include/r50_kinematics.h and include/r50_refine.h.
+// include/r50_kinematics.h, include/r50_refine.h and include/r50_track.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
@@ -8,6 +8,7 @@
 #include "multiview_kernels.h"
 #include "kinematics_kernels.h"
 #include "refine_kernels.h"
+#include "track_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
@@ -15,6 +16,7 @@
 #include "../../include/r50_multiview.h"
 #include "../../include/r50_kinematics.h"
 #include "../../include/r50_refine.h"
+#include "../../include/r50_track.h"
 
 #include <atomic>
 #include <cmath>
@@ -2040,6 +2042,40 @@ int r50_op_crop_resize_u8(const void* frames, int t, int h, int w, int top, int 
     hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(t * out_size)), dim3(256), lds, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_u8: ") + hipGetErrorString(e));
+    return R50_OK;
+}
+
+// ---- one box per output frame (include/r50_track.h, track_kernels.h, INTEGRATION.md section AA) ----
+int r50_track_weight_precision(int in_size, int out_size) {
+    if (in_size < 1 || out_size < 1) return -1;
+    return resize_weight_precision(in_size, out_size);
+}
+
+int r50_op_crop_resize_boxes_u8(const void* src, int64_t src_bytes, const int64_t* table, int t, int max_ww, void* out, void* out_flip,
+                                int out_size, int mode, void* stream) {
+    if (!src || !table || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: null pointer");
+    if (((uintptr_t)src & 3) || ((uintptr_t)out & 3) || ((uintptr_t)out_flip & 3) || ((uintptr_t)table & 7) || out_flip == out)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: src, out and out_flip must be 4-byte aligned (the table 8-byte), and out_flip is not out");
+    if (t < 1 || src_bytes < 1 || src_bytes >= (1ll << 40) || out_size < 4 || (out_size & 3) || out_size > 4096)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: invalid arguments (need t >= 1, 1 <= src_bytes < 2^40, out_size % 4 == 0 in [4, 4096])");
+    if (mode != R50_RESIZE_FLOAT && mode != R50_RESIZE_FIXED) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: unknown mode");
+    if (max_ww < 1 || max_ww > (160 * 1024 - 12) / 6 || (long long)t * out_size >= (1ll << 31))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: crop too wide");
+    const size_t lds = 2 * (size_t)((max_ww * 3 + 6) & ~3);            // two source rows of the widest crop, dword-padded
+    if (lds > 160 * 1024) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: crop too wide");
+    if (out_flip) {                                                     // the two outputs are written by one launch: they may not share a byte
+        const long long n = (long long)t * 3 * out_size * out_size;
+        const char *o = (const char*)out, *f = (const char*)out_flip;
+        if (o < f + n && f < o + n) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: out_flip overlaps out");
+    }
+    TrackArgs a;
+    a.src = (const unsigned char*)src; a.src_bytes = (long long)src_bytes; a.table = (const long long*)table;
+    a.dst = (unsigned char*)out; a.dst_flip = (unsigned char*)out_flip; a.out = out_size; a.float_mode = (mode == R50_RESIZE_FLOAT);
+    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(crop_resize_boxes_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_boxes_u8: ") + hipGetErrorString(ea));
+    hipLaunchKernelGGL(crop_resize_boxes_u8_kernel, dim3((unsigned)(t * out_size)), dim3(256), lds, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_boxes_u8: ") + hipGetErrorString(e));
     return R50_OK;
 }
 

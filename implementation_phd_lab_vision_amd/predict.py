@@ -12,7 +12,8 @@ ground truth.  This one takes the frames of any video and a trained ``best.pt``:
 
 A feature cache holds a frame once per clip that covers it, each time under that clip's own crop box; here there is ONE box per video
 (given, or from the 2D joints of all kept frames, or the centred square), so the features of a frame do not depend on the window it
-is read through.  That is a stated deviation from the cache; a per-window box is not offered.
+is read through.  That is a stated deviation from the cache.  ``--track`` (track.py, INTEGRATION.md section AA) narrows it: a box per
+FRAME, that of the clip the cache would hold around the frame, still with every frame through the backbone once.
 
 * ``window_starts``            where the windows begin (host).
 * ``merge_mirrored_poses``     the ctypes wrapper of the merge op; ``gather_window_rows`` (model.py) is the other new op.
@@ -204,6 +205,47 @@ class VideoPredictor:
             if dst_flip is not None:
                 F.crop_and_resize_video_uint8(region, [0, 0, hh, ww], OUT_SIZE, self.resize_mode, hflip=True, out=dst_flip[o:o + k])
 
+    def _crops_tracked(self, frames, s: int, m: int, boxes: np.ndarray, dst: torch.Tensor, dst_flip: Optional[torch.Tensor]) -> None:
+        """``_crops`` with a box per frame (INTEGRATION.md section AA): ``boxes[s:s+m]`` (int64 ``[top,left,hh,ww]``, checked) are the boxes
+        of ``frames[s:s+m]``.  Per chunk of at most ``UPLOAD_BYTES`` of pixels the host packs each frame's own box region back to back
+        behind the chunk's table rows in the pinned buffer; one asynchronous copy carries both, one launch resizes the chunk into ``dst``
+        and, mirrored, into ``dst_flip``.  Nothing waits but the next chunk's packing, on the upload event, as in ``_upload_region``."""
+        from . import track as TR
+        o = 0
+        while o < m:
+            k, nbytes = 0, 0
+            while o + k < m:
+                need = 3 * int(boxes[s + o + k, 2]) * int(boxes[s + o + k, 3])
+                if k and nbytes + need > UPLOAD_BYTES:
+                    break
+                nbytes, k = nbytes + need, k + 1
+            box = boxes[s + o:s + o + k]
+            sizes = 3 * box[:, 2] * box[:, 3]
+            offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+            local = np.stack([np.zeros(k, np.int64), np.zeros(k, np.int64), box[:, 2], box[:, 3]], axis=1)   # each region is its own image
+            table = TR.BoxTable(offsets, box[:, 2:4], local, nbytes, OUT_SIZE, self.resize_mode)
+            head = k * TR.TABLE_COLS * 8                                    # the table rows lead: the pixels start 8-byte aligned
+            if self._uploaded is not None:
+                self._uploaded.synchronize()                                # the last copy out of the buffer has finished
+            if self._pinned is None or self._pinned.numel() < head + nbytes:
+                self._pinned = torch.empty(head + nbytes, dtype=torch.uint8).pin_memory()
+            stage = self._pinned[:head + nbytes]
+            stage[:head].view(torch.int64).view(k, TR.TABLE_COLS).copy_(torch.from_numpy(table.host))
+            for i in range(k):
+                top, left, hh, ww = (int(v) for v in box[i])
+                piece = frames[s + o + i, top:top + hh, left:left + ww]
+                region = stage[head + int(offsets[i]):head + int(offsets[i]) + int(sizes[i])].view(hh, ww, 3)
+                if isinstance(piece, torch.Tensor):
+                    region.copy_(piece)
+                else:
+                    np.copyto(region.numpy(), piece)
+            chunk = stage.to(self.device, non_blocking=True)
+            self._uploaded = torch.cuda.Event()
+            self._uploaded.record(torch.cuda.current_stream(self.device))
+            TR.crop_resize_boxes_u8(chunk[head:], table, out=dst[o:o + k], out_flip=None if dst_flip is None else dst_flip[o:o + k],
+                                    table_dev=chunk[:head].view(torch.int64).view(k, TR.TABLE_COLS))
+            o += k
+
     @staticmethod
     def _check_frames(frames) -> Tuple[int, int, int]:
         if len(frames.shape) != 4 or frames.shape[3] != 3 or frames.shape[0] < 1 or str(frames.dtype).split(".")[-1] != "uint8":
@@ -213,12 +255,17 @@ class VideoPredictor:
         return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
 
     @torch.no_grad()
-    def features(self, frames, box):
+    def features(self, frames, box, boxes=None):
         """``frames``: host (N,H,W,3) uint8 array or tensor (a memory-mapped ``.npy`` is read chunk by chunk), ``box`` ``[top,left,hh,ww]``
         inside the image -> ``feats`` (N, 2048) fp32 on the device; with ``flip_tta`` ``(feats, feats_flipped)``.  Every frame goes
-        through the backbone once (twice with ``flip_tta``), in calls of ``frame_batch`` frames."""
+        through the backbone once (twice with ``flip_tta``), in calls of ``frame_batch`` frames.  With ``boxes`` (N, 4), one box per
+        frame, each inside the image, ``box`` is not used and the crops come from ``_crops_tracked``."""
         n, h, w = self._check_frames(frames)
-        box = [int(v) for v in choose_box(h, w, box=box).tolist()]
+        if boxes is not None:
+            from .track import check_boxes
+            boxes = check_boxes(boxes, n, h, w)
+        else:
+            box = [int(v) for v in choose_box(h, w, box=box).tolist()]
         fb = min(self.frame_batch, n)
         with torch.cuda.device(self.device):
             feats = torch.empty((n, FEATURE_DIM), dtype=torch.float32, device=self.device)
@@ -227,7 +274,10 @@ class VideoPredictor:
             u8_flip = torch.empty_like(u8) if self.flip_tta else None
             for s in range(0, n, fb):
                 m = min(fb, n - s)
-                self._crops(frames, s, m, box, u8[:m], u8_flip[:m] if self.flip_tta else None)
+                if boxes is not None:
+                    self._crops_tracked(frames, s, m, boxes, u8[:m], u8_flip[:m] if self.flip_tta else None)
+                else:
+                    self._crops(frames, s, m, box, u8[:m], u8_flip[:m] if self.flip_tta else None)
                 self.backbone.features_u8(u8[:m], out=feats[s:s + m])
                 self.stats["backbone_frames"] += m
                 if self.flip_tta:
@@ -279,7 +329,7 @@ class VideoPredictor:
 
     @torch.no_grad()
     def predict(self, frames, box=None, joints2d=None, cam: Optional[dict] = None, frame_skip: int = 1, input_len: int = 15,
-                pred_len: int = 0, name: str = "video", post=None, refine=None, conf2d=None) -> Dict[str, object]:
+                pred_len: int = 0, name: str = "video", post=None, refine=None, conf2d=None, track=None, boxes=None) -> Dict[str, object]:
         """The whole pass over every ``frame_skip``-th frame.  ``box``: see ``choose_box`` (``joints2d`` (N, J, 2) pixels of the whole
         frames, of ALL frames; the kept ones are used).  Returns host numpy arrays: ``joints3d`` (n, J, 3), ``spread`` (n,), ``count``
         (n,), ``frame_idx`` (n,) the original frame numbers, ``box`` (4,), ``future3d`` (P, J, 3) if ``pred_len > 0``, ``K`` (3, 3) of
@@ -290,8 +340,17 @@ class VideoPredictor:
         section Z; it needs ``joints2d`` and ``cam``, and reads ``conf2d`` (N, J) if given) the fused poses are first fitted to the 2D
         joints as one sequence of one segment: ``joints3d`` holds the fitted poses (the input of ``post``, if any), ``joints3d_unrefined``
         what it would hold without, ``refine`` the settings, ``refine_energy_before`` / ``refine_energy_after`` (1, 6) the energy op's
-        terms.  Without ``refine`` every launch and key is what it was."""
+        terms.  Without ``refine`` every launch and key is what it was.  With ``track`` (a ``track.TrackSettings``; INTEGRATION.md section
+        AA) every kept frame gets its own box, ``track.track_boxes`` over the kept frames' ``joints2d``; ``boxes`` (N, 4), one box per
+        frame of the whole video from a person detector, is used as given instead, each inside the image, and takes precedence over
+        ``joints2d``.  Either way the crops come from one ``r50_op_crop_resize_boxes_u8`` launch per chunk, and the result gains
+        ``boxes`` (n, 4) and ``track`` (the settings); ``box`` stays what ``choose_box`` gives the untracked pass (from ``joints2d`` that
+        may be a square larger than the image, which the untracked pass would refuse and the tracked pass does not use), and ``K`` is
+        (n, 3, 3), one per frame.  ``refine`` is untouched by it: its rays come from full-image pixels.  Without ``track`` and ``boxes`` every
+        launch and key is what it was."""
         total, h, w = self._check_frames(frames)
+        if track is not None and boxes is None and joints2d is None:
+            raise ValueError("a box track needs boxes or joints2d")
         if refine is not None and (joints2d is None or cam is None):
             raise ValueError("the 2D fit needs joints2d and the camera's f and c")
         if int(frame_skip) < 1:
@@ -312,8 +371,13 @@ class VideoPredictor:
                     raise ValueError(f"conf2d covers {conf2d.shape[0]} frames, the video has {total}")
                 conf2d = conf2d[frame_idx]
         box_t = choose_box(h, w, box=box, joints2d=joints2d)
+        if boxes is not None:
+            from .track import check_boxes
+            boxes = check_boxes(boxes, total, h, w)[frame_idx]
+        elif track is not None:
+            boxes = track.boxes(joints2d, h, w).numpy()
         self.stats = {"backbone_frames": 0, "windows": 0, "head_rows": 0}
-        got = self.features(kept, box_t)
+        got = self.features(kept, box_t, boxes) if boxes is not None else self.features(kept, box_t)
         feats, flipped = got if self.flip_tta else (got, None)
         joints3d, spread, count = self.poses(feats, flipped, name)
         unrefined = None
@@ -333,23 +397,35 @@ class VideoPredictor:
             out["post"], out["post_short_rows"] = np.array(post.describe()), np.int64(info["short_rows"][0].item())
         if int(pred_len) > 0:
             out["future3d"] = self.forecast(feats, input_len, pred_len).cpu().numpy()
-        if cam is not None:
+        if boxes is not None:
+            out["boxes"], out["track"] = boxes.copy(), np.array("boxes as given" if track is None else track.describe())
+        if cam is not None and boxes is not None:
+            out["K"] = np.stack([F.adjust_camera_after_crop_and_resize(cam, torch.from_numpy(b), OUT_SIZE).numpy() for b in boxes])
+        elif cam is not None:
             out["K"] = F.adjust_camera_after_crop_and_resize(cam, box_t, OUT_SIZE).numpy()
         out["stats"] = dict(self.stats)
         return out
 
     @torch.no_grad()
-    def crops(self, frames, box, first: int, count: int, step: int = 1) -> torch.Tensor:
+    def crops(self, frames, box, first: int, count: int, step: int = 1, boxes=None) -> torch.Tensor:
         """The resized crops of the frames ``first, first + step, ..`` (``count`` of them) as pictures: (count, 224, 224, 3) uint8 on the
-        device (what ``render`` draws on).  The frames are a strided slice, so they travel in the same few pieces as in ``features``."""
+        device (what ``render`` draws on).  The frames are a strided slice, so they travel in the same few pieces as in ``features``.
+        ``boxes`` (count, 4): one box per picture instead of ``box``."""
         total, h, w = self._check_frames(frames)
         first, count, step = int(first), int(count), int(step)
         if count < 1 or step < 1 or first < 0 or first + (count - 1) * step >= total:
             raise ValueError(f"frames {first}, {first + step}, .. ({count} of them) do not lie inside a video of {total} frames")
-        box = [int(v) for v in choose_box(h, w, box=box).tolist()]
+        if boxes is not None:
+            from .track import check_boxes
+            boxes = check_boxes(boxes, count, h, w)
+        else:
+            box = [int(v) for v in choose_box(h, w, box=box).tolist()]
         with torch.cuda.device(self.device):
             chw = torch.empty((count, 3, OUT_SIZE, OUT_SIZE), dtype=torch.uint8, device=self.device)
-            self._crops(frames[first:first + (count - 1) * step + 1:step], 0, count, box, chw, None)
+            if boxes is not None:
+                self._crops_tracked(frames[first:first + (count - 1) * step + 1:step], 0, count, boxes, chw, None)
+            else:
+                self._crops(frames[first:first + (count - 1) * step + 1:step], 0, count, box, chw, None)
             return chw.permute(0, 2, 3, 1).contiguous()
 
 
@@ -358,7 +434,7 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser("Decoded video frames in, one 3D pose per frame out (backbone + lifting head on one MI355X)")
     p.add_argument("--frames", type=str, nargs="+", required=True, metavar="FILE",
                    help=".npy of (N,H,W,3) uint8 frames (memory-mapped), or .npz with `frames` and optionally `box` [top,left,hh,ww], "
-                        "`joints2d` (N,J,2) and the camera's `f`, `c`")
+                        "`boxes` (N,4) for --track, `joints2d` (N,J,2) and the camera's `f`, `c`")
     p.add_argument("--model_path", type=str, required=True, help="head checkpoint (its dimensions are read from it)")
     p.add_argument("--weights-from", choices=("auto", "model", "ema"), default="auto",
                    help="which weights of --model_path to use: auto = the EMA weights when the checkpoint has them, else the raw ones")
@@ -401,6 +477,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "read if present); the file keeps the unfitted poses as joints3d_unrefined")
     from .refine import add_parameter_flags as add_refine_flags
     add_refine_flags(p)
+    p.add_argument("--track", action="store_true", default=argparse.SUPPRESS,
+                   help="a crop box per frame that follows the person (INTEGRATION.md section AA): the .npz input's `boxes` (N,4) as "
+                        "given, else the box of the clip around each frame from its `joints2d`; the file gains `boxes` and a K per frame")
+    p.add_argument("--track-window", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="frames of the clip around a frame whose joints give its box (default: --seq-len); needs --track")
+    p.add_argument("--track-smooth", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="frames of the running mean over the boxes' extents (default: the track window; 1: none); needs --track")
     return p
 
 
@@ -415,6 +498,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--{flag.replace('_', '-')} needs --bvh")
     bvh_options(args, p.error)
     video_refine(args, p.error)
+    video_track(args, p.error)
     return args
 
 
@@ -436,14 +520,33 @@ def video_refine(args: argparse.Namespace, error=None):
     return settings_from_args(args, hasattr(args, "refine_2d"), "--refine-2d", error or raise_)
 
 
+def video_track(args: argparse.Namespace, error=None):
+    """The ``track.TrackSettings`` of parsed arguments (the window defaults to ``--seq-len``), or None without ``--track``."""
+    from .track import TrackSettings
+
+    def raise_(msg):
+        raise ValueError(msg)
+    error = error or raise_
+    for flag in ("track_window", "track_smooth"):
+        if hasattr(args, flag) and not hasattr(args, "track"):
+            error(f"--{flag.replace('_', '-')} needs --track")
+    if not hasattr(args, "track"):
+        return None
+    try:
+        return TrackSettings(getattr(args, "track_window", args.seq_len), getattr(args, "track_smooth", None))
+    except ValueError as exc:
+        error(f"--track: {exc}")
+
+
 def load_input(path: str) -> Dict[str, object]:
-    """``frames`` (memory-mapped for a ``.npy``) and whatever annotations the file holds: ``box``, ``joints2d``, ``conf2d``, ``cam``."""
+    """``frames`` (memory-mapped for a ``.npy``) and whatever annotations the file holds: ``box``, ``boxes``, ``joints2d``, ``conf2d``,
+    ``cam``."""
     if path.endswith(".npz"):
         z = np.load(path, allow_pickle=False)
         if "frames" not in z.files:
             raise ValueError(f"{path}: no `frames` array in the file (it holds {sorted(z.files)}); expected (N,H,W,3) uint8 frames")
         item: Dict[str, object] = {"frames": z["frames"]}
-        for key in ("box", "joints2d", "conf2d"):
+        for key in ("box", "boxes", "joints2d", "conf2d"):
             if key in z.files:
                 item[key] = z[key]
         if ("f" in z.files) != ("c" in z.files):
@@ -463,7 +566,9 @@ def render_prediction(outdir: str, predictor: VideoPredictor, frames, res: Dict[
     n = int(res["joints3d"].shape[0])
     r = max(1, min(int(n_frames), n))
     idx = res["frame_idx"]
-    pics = predictor.crops(frames, res["box"], int(idx[n - r]), r, int(idx[1] - idx[0]) if n > 1 else 1)
+    tracked = "boxes" in res
+    pics = predictor.crops(frames, res["box"], int(idx[n - r]), r, int(idx[1] - idx[0]) if n > 1 else 1,
+                           **({"boxes": res["boxes"][n - r:]} if tracked else {}))
     pred = torch.from_numpy(res["joints3d"][n - r:]).to(dev)
     future = None
     if "future3d" in res:
@@ -473,6 +578,10 @@ def render_prediction(outdir: str, predictor: VideoPredictor, frames, res: Dict[
         # placeholders, never drawn: render_panels puts future3d in the prediction layer of every frame t >= input_len = r
         pred = torch.cat([pred, torch.zeros_like(future[0])])
     k = torch.from_numpy(res["K"]).to(dev)[None] if "K" in res else None
+    if k is not None and tracked:                # a K per frame, (1, T, 3, 3); the forecast's placeholders keep the last frame's
+        k = k[:, n - r:]
+        if future is not None:
+            k = torch.cat([k, k[:, -1:].expand(1, int(future.shape[1]), 3, 3)], dim=1)
     return R.render_clips(outdir, pics[None], None, k, None, pred[None], future, r, None, fps)
 
 
@@ -480,6 +589,7 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     args = parse_args(argv)
     post = video_post(args)
     fit = video_refine(args)
+    follow = video_track(args)
     device = torch.device(args.device)
     if device.type != "cuda" or not torch.cuda.is_available():
         raise _lib.R50Error("predict runs on an MI355X only; there is no CPU fallback")
@@ -498,6 +608,10 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
         for path, item in zip(args.frames, items):
             if "joints2d" not in item or "cam" not in item:
                 raise ValueError(f"{path}: --refine-2d needs `joints2d` and the camera's `f` and `c` in the input .npz")
+    if follow is not None:                   # likewise
+        for path, item in zip(args.frames, items):
+            if "boxes" not in item and "joints2d" not in item:
+                raise ValueError(f"{path}: --track needs `boxes` (N,4) or `joints2d` (N,J,2) in the input .npz")
     state_dict, source = _resolve_weights(args)
     print(f"backbone weights: {source}")
     backbone = ResNet50Backbone(state_dict=state_dict, max_batch=args.frame_batch, precision=args.precision).to(device).eval()
@@ -511,7 +625,8 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
         res = predictor.predict(item["frames"], box=args.box if args.box is not None else item.get("box"), joints2d=item.get("joints2d"),
                                 cam=item.get("cam"), frame_skip=args.frame_skip, input_len=args.input_len, pred_len=args.pred_len, name=name,
                                 **({} if post is None else {"post": post}),
-                                **({} if fit is None else {"refine": fit, "conf2d": item.get("conf2d")}))
+                                **({} if fit is None else {"refine": fit, "conf2d": item.get("conf2d")}),
+                                **({} if follow is None else {"track": follow, "boxes": item.get("boxes")}))
         stats = res.pop("stats")
         out_path = os.path.join(args.out, name + "_poses.npz")
         rigid_note = ""

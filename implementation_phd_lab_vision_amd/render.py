@@ -157,7 +157,8 @@ def render_panels(frames_u8: Optional[torch.Tensor], joints2d: Optional[torch.Te
 
     ``frames_u8`` (N,T,S,S,3) uint8 on the device, or None: then panels 0 and 1 get ``bg_rgb`` too (``size`` gives S, default 224).
     With ``future3d`` (N,P,J,3) the prediction layer of the frames ``t >= input_len`` carries the rollout's poses in ``future_rgb``, and
-    the frames ``t >= input_len + P`` have it switched off.  gt3d / pred3d (N,T,J,3), K (N,3,3), all on the device.
+    the frames ``t >= input_len + P`` have it switched off.  gt3d / pred3d (N,T,J,3), K (N,3,3) or, a camera per frame (``predict
+    --track``), (N,T,3,3), all on the device.
 
     A prediction without annotations (``predict``): ``joints2d``, ``K`` and ``gt3d`` may each be None.  A layer whose input is missing is
     left out (panel 0 without ``joints2d`` is the bare frame, and so is panel 1 without ``K``: nothing can be projected), and without
