@@ -101,6 +101,12 @@ def resize_bilinear_u8_float_restated(img: np.ndarray, out_h: int, out_w: int) -
     """numpy restatement of the fp32 route with the operation order the HIP kernel uses (source index as one fma,
     w_ij = h_i * w_j, two fma-paired sums, round half to even).  Equals ``resize_bilinear_u8_float`` (= torch) on all but
     a few bytes per million: the CPU kernel's FMA contraction is a property of the torch build."""
+    return np.clip(np.rint(resize_bilinear_u8_float_restated_sum(img, out_h, out_w)), 0, 255).astype(np.uint8)
+
+
+def resize_bilinear_u8_float_restated_sum(img: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
+    """The restatement's fp32 sum ``s0 + s1`` before it is rounded to a byte: where it lies next to a half-integer, another
+    association of the same four products (torch's CPU kernel) may round the other way."""
     f32 = np.float32
     img = np.asarray(img, dtype=np.uint8).astype(np.float32)
     h, w = img.shape[-2:]
@@ -129,7 +135,7 @@ def resize_bilinear_u8_float_restated(img: np.ndarray, out_h: int, out_w: int) -
     b = lambda a: np.broadcast_to(a, p00.shape)
     s0 = fma(p01, b(w01), (p00 * w00).astype(np.float32))
     s1 = fma(p11, b(w11), (p10 * w10).astype(np.float32))
-    return np.clip(np.rint((s0 + s1).astype(np.float32)), 0, 255).astype(np.uint8)
+    return (s0 + s1).astype(np.float32)
 
 
 def crop_and_resize_video_uint8(frames_thwc: np.ndarray, box, out_size: int = 224, fixed_point: bool = False) -> np.ndarray:

@@ -58,6 +58,66 @@ def test_extreme_factors_and_normalized_output(lib_built):
         frames.aug_color_jitter_u8(u8, None)                                # host tensor: no CPU fallback
 
 
+def _jitter_into(lib, u8, p, normalize, out):
+    """``r50_op_color_jitter_u8`` into a destination the caller has prepared (``frames.aug_color_jitter_u8`` allocates its own)."""
+    import ctypes
+    t, _, h, w = u8.shape
+    dev = u8.to(DEV)
+    means = torch.empty(t, dtype=torch.float32, device=DEV)
+    rc = lib.r50_op_color_jitter_u8(dev.data_ptr(), t, h * w, (ctypes.c_int * 4)(*p["fn_idx"]), float(p["brightness"]), float(p["contrast"]),
+                                    float(p["saturation"]), float(p["hue"]), int(normalize), out.data_ptr(), means.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.r50_last_error(None)
+    torch.cuda.synchronize()
+    return out.cpu()
+
+
+GRID_ELEMENTS = 8192 * 256            # the element-wise kernels' grid is capped at 8192 workgroups of 256; beyond that they grid-stride
+
+
+@pytest.mark.parametrize("normalize", [0, 1])
+def test_a_real_clip_takes_the_grid_stride_round(lib_built, normalize):
+    """t = 14 at 224 x 224 is 2,107,392 elements: the last 10,240 belong to the second round of ``cj_from_u8_kernel`` and
+    ``cj_normalize_kernel``.  The destination starts out as NaN, and the bar is applied to the second round's elements on their own, so
+    that a skipped round can hide neither in an uninitialised buffer nor in a maximum over the whole tensor."""
+    from oracle import colorjitter_oracle as cj
+    u8 = _clip(5, t=14)
+    n = u8.numel()
+    assert n == 2_107_392 and n - GRID_ELEMENTS == 10_240
+    p = {"fn_idx": [2, 0, 3, 1], "brightness": 1.15, "contrast": 0.85, "saturation": 1.1, "hue": 0.03}
+    out = torch.full((14, 3, 224, 224), float("nan"), dtype=torch.float32, device=DEV)
+    got = _jitter_into(lib_built, u8, p, normalize, out)
+    want = cj.color_jitter_variant_u8(u8, p) if normalize else cj.color_jitter(u8.float() / 255, p)
+    bar = 3e-5 if normalize else 5e-6
+    err = (got - want).abs().view(-1)
+    assert not torch.isnan(got).any(), f"{int(torch.isnan(got).sum())} elements were never written"
+    first, second = float(err[:GRID_ELEMENTS].max()), float(err[GRID_ELEMENTS:].max())
+    print(f"color jitter t 14, normalize {normalize}: max |d| {first:.3g} in the first round, {second:.3g} in the second")
+    assert second < bar, second
+    assert first < bar, first
+
+
+@pytest.mark.parametrize("thw", [(3, 7, 9), (2, 1, 1)], ids=lambda v: "%dx%dx%d" % v)
+def test_ragged_frames_match_the_oracle(lib_built, thw):
+    """``hw`` = 63 and 1: no multiple of 256, less than one workgroup; ``cj_gray_mean_kernel`` runs its 1024 threads over 63 elements, then
+    over 1.  The per-frame contrast mean reaches every element of the final output, which is held to the oracle under the usual bars."""
+    from implementation_phd_lab_vision_amd import frames
+    from oracle import colorjitter_oracle as cj
+    t, h, w = thw
+    u8 = torch.randint(0, 256, (t, 3, h, w), generator=torch.Generator().manual_seed(7 + h * w), dtype=torch.uint8)
+    u8[0, :, 0, 0] = u8[0, 0, 0, 0]                                            # one gray pixel: the eqc branch of the hue step
+    for k, order in enumerate(([1, 0, 2, 3], [3, 2, 1, 0], [0, 3, 2, 1])):      # contrast first, in the middle, last
+        p = cj.sample_params(torch.Generator().manual_seed(200 + k))
+        p["fn_idx"] = list(order)
+        assert p["hue"] != 0.0 and p["contrast"] != 1.0
+        got = frames.aug_color_jitter_u8(u8.to(DEV), p, normalize=False).cpu()
+        want = cj.color_jitter(u8.float() / 255, p)
+        assert got.shape == want.shape == (t, 3, h, w)
+        assert float((got - want).abs().max()) < 5e-6, (order, float((got - want).abs().max()))
+        got_n = frames.aug_color_jitter_u8(u8.to(DEV), p).cpu()
+        assert float((got_n - cj.color_jitter_variant_u8(u8, p)).abs().max()) < 3e-5, order
+
+
 def test_jittered_clip_through_the_backbone(lib_built):
     """The variant's features equal the features of the oracle's jittered frames (same backbone, fp32 entry)."""
     from implementation_phd_lab_vision_amd import frames

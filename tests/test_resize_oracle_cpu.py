@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import resize_oracle as ro
+from tests import resize_cases as RC
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "producer_golden.pt")
 SIZES = [(231, 231), (500, 500), (100, 100), (224, 224), (225, 223), (1, 1), (2, 3), (448, 448), (449, 449), (1000, 1002),
@@ -38,6 +39,45 @@ def test_float_restatement_close_to_torch_float_route(hw):
     a, b = ro.resize_bilinear_u8_float(x, 224, 224), ro.resize_bilinear_u8_float_restated(x, 224, 224)
     d = np.abs(a.astype(np.int32) - b.astype(np.int32))
     assert d.max() <= 1 and (d > 0).mean() <= 1e-4
+
+
+@pytest.mark.parametrize("case", RC.CASES, ids=RC.case_id)
+def test_fixed_point_restatement_equals_aten_over_the_domain(case):
+    """The case list of tests/resize_cases.py (non-square sources, outputs other than 224, the identity on one axis only, up-scaling
+    on one axis with down-scaling on the other): the fixed-point restatement is torch's uint8 kernel bit for bit, so the kernels can
+    be held to it exactly on those cases."""
+    if "AVX" not in torch.backends.cpu.get_cpu_capability():
+        pytest.skip("torch has no native uint8 bilinear kernel on this CPU (it would convert to float itself)")
+    hh, ww, out = case
+    x = RC.image(hh, ww, out).permute(0, 3, 1, 2)                      # channels-last memory, as a crop of a decoded clip is
+    ref = F.interpolate(x, size=[out, out], mode="bilinear", align_corners=False, antialias=False).numpy()
+    assert np.array_equal(ro.resize_bilinear_u8(x.numpy(), out, out), ref)
+    assert np.array_equal(F.interpolate(x.contiguous(), size=[out, out], mode="bilinear", align_corners=False, antialias=False).numpy(), ref)
+
+
+# Distance of the restatement's unrounded fp32 sum from a half-integer below which torch's float route may round the other way.  The two
+# routes sum the same four products in another association, with or without contraction: at most three roundings at magnitude below
+# 256, each at most half an ulp (2^-17).  2^-14 is 4 ulp; the largest distance measured over this case list is 1 ulp (2^-16), and
+# 2 ulp (2^-15) over a wider grid of 15 source sizes x 9 output sizes.
+TIE_BAND = 2.0 ** -14
+
+
+@pytest.mark.parametrize("case", RC.CASES, ids=RC.case_id)
+def test_float_restatement_differs_from_torch_only_at_ties_over_the_domain(case):
+    """Up-scaling from a tiny source makes exact rounding ties common (0.7 % of the bytes at 40x8 -> 12), so a share of the bytes says
+    nothing here.  Instead: at most 1 LSB, and only where the restatement's unrounded sum lies within ``TIE_BAND`` of a half-integer."""
+    hh, ww, out = case
+    x = RC.crop_nchw(RC.image(hh, ww, out))
+    a, b = ro.resize_bilinear_u8_float(x, out, out), ro.resize_bilinear_u8_float_restated(x, out, out)
+    s = ro.resize_bilinear_u8_float_restated_sum(x, out, out)
+    assert s.dtype == np.float32 and np.array_equal(np.clip(np.rint(s), 0, 255).astype(np.uint8), b)
+    d = np.abs(a.astype(np.int32) - b.astype(np.int32))
+    dist = np.abs((s.astype(np.float64) - np.floor(s.astype(np.float64))) - 0.5)[d > 0]
+    worst = float(dist.max()) if dist.size else 0.0
+    print(f"float routes {hh}x{ww} -> {out}: {int((d > 0).sum())} of {d.size} bytes differ, largest distance from a half-integer "
+          f"{worst:.3g} (= {worst * 2 ** 16:.2f} ulp of 2^-16)")
+    assert int(d.max()) <= 1
+    assert worst <= TIE_BAND
 
 
 def test_crop_and_resize_matches_reference_expression():

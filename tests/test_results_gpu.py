@@ -33,11 +33,16 @@ def trees(tmp_path_factory):
     return rd.make_results_cache(base / "features"), rd.make_preprocessed_tree(base / "videos")
 
 
-def _torch_resize(frames_nhwc_u8: torch.Tensor, size: int) -> torch.Tensor:
-    """``_resize_video_hw`` (src/results.py:81-93) restated with torch ops on the CPU."""
+def _torch_resize_f32(frames_nhwc_u8: torch.Tensor, size: int) -> torch.Tensor:
+    """``_resize_video_hw`` (src/results.py:81-93) restated with torch ops on the CPU, up to (not including) the ``.byte()``: the fp32
+    value in [0, 255] that is then truncated, (n, size, size, 3)."""
     v = frames_nhwc_u8.permute(0, 3, 1, 2).float() / 255.0
     v = F.interpolate(v, size=(size, size), mode="bilinear", align_corners=False)
-    return (v.clamp(0, 1) * 255.0).byte().permute(0, 2, 3, 1).contiguous()
+    return (v.clamp(0, 1) * 255.0).permute(0, 2, 3, 1).contiguous()
+
+
+def _torch_resize(frames_nhwc_u8: torch.Tensor, size: int) -> torch.Tensor:
+    return _torch_resize_f32(frames_nhwc_u8, size).byte()
 
 
 # ------------------------------------------------------------------ kernel ----------------------------------------------------
@@ -60,6 +65,35 @@ def test_resize_kernel_matches_torch_cpu(lib, h, w, n, size):
         assert bad == 0
     else:
         assert int(diff.max()) <= 1 and bad <= 1e-4 * diff.numel()
+
+
+# Distance of torch's own fp32 value (before ``.byte()`` truncates it) from an integer below which the kernel may land on the other side.
+# The kernel evaluates the same expression as torch's CPU loop with its own contraction: at most three roundings of values in [0, 1]
+# (half an ulp each, 2^-25), scaled by 255 (3 * 255 * 2^-25 < 2^-15.4), plus the rounding of the product with 255 (half an ulp below
+# 256, 2^-17): below 2^-15 in all.  2^-14 is twice that.
+INTEGER_BAND = 2.0 ** -14
+
+
+@pytest.mark.parametrize("h,w,n,size", [(2, 3, 2, 224), (1, 1, 2, 8), (7, 1, 2, 12), (1, 7, 2, 12), (500, 131, 2, 344), (40, 8, 2, 448)])
+def test_resize_kernel_differs_from_torch_only_next_to_an_integer(lib, h, w, n, size):
+    """Up-scaling from a tiny source, one-pixel rows and columns, a non-square source: values that sit exactly on an integer before the
+    truncation are common there (the source bytes themselves come back), so a share of the bytes says nothing.  Instead: at most 1,
+    and only where torch's own value before the truncation lies within ``INTEGER_BAND`` of an integer."""
+    from implementation_phd_lab_vision_amd.frames import resize_frames_uint8
+    g = torch.Generator().manual_seed(h * 7 + w + size)
+    frames = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, generator=g)
+    idx = [n - 1, 0] + list(range(n))
+    got = resize_frames_uint8(frames.to(DEV), torch.tensor(idx, dtype=torch.int32), size).cpu()
+    before = _torch_resize_f32(frames[idx], size)
+    want = before.byte()
+    assert got.shape == want.shape == (len(idx), size, size, 3) and got.dtype == torch.uint8
+    diff = (got.int() - want.int()).abs()
+    dist = (before.double() - before.double().round()).abs()[diff > 0]
+    worst = float(dist.max()) if dist.numel() else 0.0
+    print(f"resize {n}x{h}x{w} -> {size}: {int((diff > 0).sum())} of {diff.numel()} bytes differ from torch's CPU path (max {int(diff.max())}), "
+          f"largest distance of torch's value from an integer there {worst:.3g}")
+    assert int(diff.max()) <= 1
+    assert worst <= INTEGER_BAND
 
 
 def test_resize_kernel_writes_only_its_slice(lib):
