@@ -1,5 +1,5 @@
 // Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h,
-// include/r50_kinematics.h, include/r50_refine.h and include/r50_track.h.
+// include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h and include/r50_resample.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
@@ -9,6 +9,7 @@
 #include "kinematics_kernels.h"
 #include "refine_kernels.h"
 #include "track_kernels.h"
+#include "resample_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
@@ -17,6 +18,7 @@
 #include "../../include/r50_kinematics.h"
 #include "../../include/r50_refine.h"
 #include "../../include/r50_track.h"
+#include "../../include/r50_resample.h"
 
 #include <atomic>
 #include <cmath>
@@ -2702,6 +2704,31 @@ int r50_op_pose_rotations(const float* x, const int* row_seq, int64_t F, int S, 
     hipLaunchKernelGGL(pose_rotations_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), lds, (hipStream_t)stream, x, row_seq, (int)F, J,
                        sk, rest, quat, euler, rigid, resid, flags);
     return ew_done("r50_op_pose_rotations");
+}
+
+// ---- a pose at any time stamp (include/r50_resample.h, resample_kernels.h, INTEGRATION.md section AB) ----
+int r50_op_resample_sequences(const float* x, const int* idx, const int* seq_start, int64_t F, int S, int J, const double* out_time,
+                              const int* out_seq, const int* out_left, int64_t G, int kind, int max_gap, float* y, int* flags,
+                              void* stream) {
+    if (!x || !idx || !seq_start || !out_time || !out_seq || !out_left || !y || !flags)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: null pointer");
+    if (F < 1 || F > kSmoothMaxRows || G < 1 || G > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > RESAMPLE_MAX_J)
+        return fail(nullptr, R50_ERR_INVALID,
+                    "r50_op_resample_sequences: invalid arguments (need 1 <= S <= F < 2^31 / 192, 1 <= G < 2^31 / 192 and 1 <= J <= 64)");
+    if (kind != R50_RESAMPLE_LINEAR && kind != R50_RESAMPLE_CUBIC)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: kind must be 0 (linear) or 1 (cubic)");
+    if (max_gap < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: max_gap must be >= 1");
+    if ((uintptr_t)out_time & 7u) return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: out_time must be 8-byte aligned");
+    const long long row = 3 * J * (long long)sizeof(float), word = (long long)sizeof(int);
+    const KinRange in[6] = {{x, F * row}, {idx, F * word}, {seq_start, ((long long)S + 1) * word}, {out_time, G * (long long)sizeof(double)},
+                            {out_seq, G * word}, {out_left, G * word}};
+    const KinRange out[2] = {{y, G * row}, {flags, G * word}};
+    if (kin_any_overlap(in, 6, out, 2))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: y or flags overlaps an input or the other output");
+    const long long total = G * 3 * J;
+    hipLaunchKernelGGL(resample_sequences_kernel, dim3((unsigned)((total + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK)), dim3(RESAMPLE_BLOCK), 0,
+                       (hipStream_t)stream, x, idx, seq_start, 3 * J, out_time, out_seq, out_left, (int)G, kind, max_gap, y, flags);
+    return ew_done("r50_op_resample_sequences");
 }
 
 // ---- 2D-guided refinement of stitched sequences (include/r50_refine.h, refine_kernels.h) ----

@@ -13,7 +13,8 @@ ground truth.  This one takes the frames of any video and a trained ``best.pt``:
 A feature cache holds a frame once per clip that covers it, each time under that clip's own crop box; here there is ONE box per video
 (given, or from the 2D joints of all kept frames, or the centred square), so the features of a frame do not depend on the window it
 is read through.  That is a stated deviation from the cache.  ``--track`` (track.py, INTEGRATION.md section AA) narrows it: a box per
-FRAME, that of the clip the cache would hold around the frame, still with every frame through the backbone once.
+FRAME, that of the clip the cache would hold around the frame, still with every frame through the backbone once.  ``--resample STEP``
+(resample.py, INTEGRATION.md section AB) adds, after every other stage, poses every STEP video frames interpolated from the kept ones.
 
 * ``window_starts``            where the windows begin (host).
 * ``merge_mirrored_poses``     the ctypes wrapper of the merge op; ``gather_window_rows`` (model.py) is the other new op.
@@ -329,7 +330,8 @@ class VideoPredictor:
 
     @torch.no_grad()
     def predict(self, frames, box=None, joints2d=None, cam: Optional[dict] = None, frame_skip: int = 1, input_len: int = 15,
-                pred_len: int = 0, name: str = "video", post=None, refine=None, conf2d=None, track=None, boxes=None) -> Dict[str, object]:
+                pred_len: int = 0, name: str = "video", post=None, refine=None, conf2d=None, track=None, boxes=None,
+                resample=None) -> Dict[str, object]:
         """The whole pass over every ``frame_skip``-th frame.  ``box``: see ``choose_box`` (``joints2d`` (N, J, 2) pixels of the whole
         frames, of ALL frames; the kept ones are used).  Returns host numpy arrays: ``joints3d`` (n, J, 3), ``spread`` (n,), ``count``
         (n,), ``frame_idx`` (n,) the original frame numbers, ``box`` (4,), ``future3d`` (P, J, 3) if ``pred_len > 0``, ``K`` (3, 3) of
@@ -347,6 +349,13 @@ class VideoPredictor:
         ``boxes`` (n, 4) and ``track`` (the settings); ``box`` stays what ``choose_box`` gives the untracked pass (from ``joints2d`` that
         may be a square larger than the image, which the untracked pass would refuse and the tracked pass does not use), and ``K`` is
         (n, 3, 3), one per frame.  ``refine`` is untouched by it: its rays come from full-image pixels.  Without ``track`` and ``boxes`` every
+        launch and key is what it was.  With ``resample`` (a ``resample.ResampleSettings``; INTEGRATION.md section AB) the poses the
+        file holds (after ``refine`` and ``post``) are also interpolated at the times ``0, step, 2 step, .. <= frame_idx[-1]`` in video
+        frames, as one sequence with ``max_gap = frame_skip``: the result gains ``resampled3d`` (m, J, 3), ``resampled_time`` (m,) fp64,
+        ``resampled_flags`` (m,) and ``resample`` (the settings); ``joints3d`` stays aligned with ``frame_idx``.  Interpolated positions
+        shorten bones between knots: where ``post`` fixes the bone lengths, ``resampled3d`` goes through ``smooth.fix_bone_lengths``
+        once more; otherwise the result gains ``bone_std_mm`` and ``resampled_bone_std_mm`` (``smooth.bone_stats`` over the H36M edges, a
+        17-joint head only), the spread of the bone lengths over time at the knots and after resampling.  Without ``resample`` every
         launch and key is what it was."""
         total, h, w = self._check_frames(frames)
         if track is not None and boxes is None and joints2d is None:
@@ -395,6 +404,9 @@ class VideoPredictor:
                 processed, info = post.apply(joints3d, (np.array([0, n], dtype=np.int32), np.arange(n, dtype=np.int32)))
             out["joints3d_raw"], out["joints3d"] = out["joints3d"], processed.cpu().numpy()
             out["post"], out["post_short_rows"] = np.array(post.describe()), np.int64(info["short_rows"][0].item())
+            joints3d = processed
+        if resample is not None:
+            out.update(self._resampled(joints3d, frame_idx, int(frame_skip), resample, post))
         if int(pred_len) > 0:
             out["future3d"] = self.forecast(feats, input_len, pred_len).cpu().numpy()
         if boxes is not None:
@@ -405,6 +417,25 @@ class VideoPredictor:
             out["K"] = F.adjust_camera_after_crop_and_resize(cam, box_t, OUT_SIZE).numpy()
         out["stats"] = dict(self.stats)
         return out
+
+    def _resampled(self, joints3d: torch.Tensor, frame_idx: np.ndarray, frame_skip: int, settings, post) -> Dict[str, object]:
+        """The keys ``predict`` gains with ``resample``: see there."""
+        from . import resample as RS
+        from . import smooth
+        with torch.cuda.device(self.device):
+            y, flags, tau = RS.resample_video(joints3d, frame_idx, frame_skip, settings)
+            m, joints = int(y.shape[0]), int(y.shape[1])
+            one = lambda rows: (np.array([0, rows], dtype=np.int32), np.arange(rows, dtype=np.int32))          # noqa: E731
+            extra: Dict[str, object] = {}
+            if post is not None and post.fix_bones:
+                y, _ = smooth.fix_bone_lengths(y, smooth.DeviceTables(*one(m), self.device), post.edges)
+            elif int(np.max(smooth.H36M_EDGES)) < joints:
+                for key, poses in (("bone_std_mm", joints3d), ("resampled_bone_std_mm", y)):
+                    rows = int(poses.shape[0])
+                    stats = smooth.bone_stats(poses.contiguous(), smooth.DeviceTables(*one(rows), self.device)).cpu().numpy()
+                    extra[key] = np.float64(smooth.bone_std_mm(stats, np.array([rows]), np.array([0]), 1)[1])
+            return {"resampled3d": y.cpu().numpy(), "resampled_time": tau, "resampled_flags": flags.cpu().numpy(),
+                    "resample": np.array(settings.describe()), **extra}
 
     @torch.no_grad()
     def crops(self, frames, box, first: int, count: int, step: int = 1, boxes=None) -> torch.Tensor:
@@ -484,6 +515,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="frames of the clip around a frame whose joints give its box (default: --seq-len); needs --track")
     p.add_argument("--track-smooth", type=int, default=argparse.SUPPRESS, metavar="N",
                    help="frames of the running mean over the boxes' extents (default: the track window; 1: none); needs --track")
+    from .resample import add_video_flags
+    add_video_flags(p)
     return p
 
 
@@ -499,6 +532,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     bvh_options(args, p.error)
     video_refine(args, p.error)
     video_track(args, p.error)
+    video_resample(args, p.error)
     return args
 
 
@@ -536,6 +570,15 @@ def video_track(args: argparse.Namespace, error=None):
         return TrackSettings(getattr(args, "track_window", args.seq_len), getattr(args, "track_smooth", None))
     except ValueError as exc:
         error(f"--track: {exc}")
+
+
+def video_resample(args: argparse.Namespace, error=None):
+    """The ``resample.ResampleSettings`` of parsed arguments, or None without ``--resample``."""
+    from .resample import settings_from_args
+
+    def raise_(msg):
+        raise ValueError(msg)
+    return settings_from_args(args, error or raise_)
 
 
 def load_input(path: str) -> Dict[str, object]:
@@ -590,6 +633,7 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     post = video_post(args)
     fit = video_refine(args)
     follow = video_track(args)
+    again = video_resample(args)
     device = torch.device(args.device)
     if device.type != "cuda" or not torch.cuda.is_available():
         raise _lib.R50Error("predict runs on an MI355X only; there is no CPU fallback")
@@ -626,12 +670,13 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
                                 cam=item.get("cam"), frame_skip=args.frame_skip, input_len=args.input_len, pred_len=args.pred_len, name=name,
                                 **({} if post is None else {"post": post}),
                                 **({} if fit is None else {"refine": fit, "conf2d": item.get("conf2d")}),
-                                **({} if follow is None else {"track": follow, "boxes": item.get("boxes")}))
+                                **({} if follow is None else {"track": follow, "boxes": item.get("boxes")}),
+                                **({} if again is None else {"resample": again}))
         stats = res.pop("stats")
         out_path = os.path.join(args.out, name + "_poses.npz")
         rigid_note = ""
-        if bvh:                              # after the optional --smooth / --fix-bones: the poses the file holds, as one sequence
-            res.update(kinematics.video_rotations(res["joints3d"], device))
+        if bvh:                              # after the optional --smooth / --fix-bones / --resample: the poses the file holds, as one sequence
+            res.update(kinematics.video_rotations(res["joints3d" if again is None else "resampled3d"], device))
             rigid_note = (f", rigid skeleton: mean residual {float(res['rigid_residual'].mean()):.6f} "
                           f"({int(np.count_nonzero(res['rigid_flags']))} flagged frames)")
         np.savez(out_path, **res, **{k: np.int64(v) for k, v in stats.items()})
@@ -639,7 +684,9 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
         print(f"{name}: {res['joints3d'].shape[0]} poses from {stats['backbone_frames']} backbone frames, {stats['windows']} windows "
               f"({stats['head_rows']} head rows) -> {out_path}" + rigid_note)
         if bvh:
-            written.append(kinematics.write_video_bvh(os.path.join(args.out, name + ".bvh"), res, None, bvh_fps, bvh_scale))
+            # resampled poses lie STEP video frames apart, the kept ones FRAME_SKIP: the frame time is STEP / (FRAME_SKIP * bvh_fps)
+            fps = bvh_fps if again is None else bvh_fps * args.frame_skip / again.step
+            written.append(kinematics.write_video_bvh(os.path.join(args.out, name + ".bvh"), res, None, fps, bvh_scale))
             print(f"{name}: BVH written to: {written[-1]}")
         if args.render:
             written += render_prediction(os.path.join(args.out, name + "_render"), predictor, item["frames"], res, args.render_frames,

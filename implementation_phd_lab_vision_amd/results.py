@@ -41,7 +41,9 @@ the cameras of every take are brought into one frame of reference and fused into
 ``--dense-out`` gains ``pred_mv``, ``frame_disagreement``, ``views`` and ``mv_pair_*``.  With ``--dense-rigid`` (default off; needs
 ``--dense``) every stitched sequence is also fitted with joint rotations on a rigid skeleton
 (``kinematics.evaluate_rigid``): ``Dense | rigid`` lines set the rigid reconstruction's errors beside the poses', the ``.npz`` gains the
-``dense_rigid_*`` keys, and ``--dense-bvh DIR`` writes one BVH file per sequence.  Every report's printed lines and ``.npz`` keys
+``dense_rigid_*`` keys, and ``--dense-bvh DIR`` writes one BVH file per sequence.  With ``--dense-holdout K`` (default off; needs
+``--dense``; INTEGRATION.md section AB) only every K-th row of a stitched sequence is kept and the rows in between are interpolated
+(``resample.evaluate_holdout``): ``Dense | holdout`` lines, ``dense_holdout_*`` keys, ``pred_holdout`` in ``--dense-out``.  Every report's printed lines and ``.npz`` keys
 (``*_lines``, ``*_arrays`` / ``*_npz``) are defined in the module that computes it; ``main`` only calls them in order.
 
 Two differences from running the reference's script as it stands:
@@ -175,6 +177,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dense-refine-seed", type=int, default=argparse.SUPPRESS, metavar="N", help="seed of that noise (default 0)")
     from .refine import add_parameter_flags as add_refine_flags
     add_refine_flags(p)
+    p.add_argument("--dense-holdout", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help="also keep only every K-th row of every stitched sequence (K >= 2) and every segment's last row, rebuild the rows in "
+                        "between by interpolation and score them beside the full-rate poses (--dense; INTEGRATION.md section AB): what a "
+                        "backbone that sees every K-th frame would cost")
+    p.add_argument("--dense-holdout-kind", choices=("cubic", "linear"), default=argparse.SUPPRESS,
+                   help="how --dense-holdout interpolates (default cubic)")
     return p
 
 
@@ -251,6 +259,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if not (np.isfinite(getattr(args, "dense_refine_noise_px", 0.0)) and getattr(args, "dense_refine_noise_px", 0.0) >= 0.0):
         p.error(f"--dense-refine-noise-px must be finite and >= 0, got {args.dense_refine_noise_px}")
     dense_refine(args, p.error)              # a parameter flag without --dense-refine, or a refused parameter
+    if hasattr(args, "dense_holdout") and not args.dense:
+        p.error("--dense-holdout needs --dense")
+    if hasattr(args, "dense_holdout_kind") and not hasattr(args, "dense_holdout"):
+        p.error("--dense-holdout-kind needs --dense-holdout")
+    if getattr(args, "dense_holdout", 2) < 2:
+        p.error(f"--dense-holdout keeps every K-th row with K >= 2, got {args.dense_holdout}")
     if args.dtw and args.pred_len <= 0:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
@@ -501,7 +515,7 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in detail_lines(detail, args.input_len, args.pred_len):
             print(line)
 
-    dense, multi, rigid, fitted = None, None, None, None
+    dense, multi, rigid, fitted, holdout = None, None, None, None, None
     if args.dense:                           # every video frame once: the clips of a sequence fused per frame
         from .sequences import dense_export, dense_lines, dense_npz, dense_post_lines, evaluate_dense
         from . import multiview as mv
@@ -512,7 +526,8 @@ def main(argv: Optional[List[str]] = None) -> str:
             from . import kinematics
             kinematics.skeleton_for(int(head.joints_num))        # refused before the pass if there is no skeleton for the head's joints
         dense = evaluate_dense(head, test_set, fuse=args.dense_fuse,
-                               keep_poses=args.dense_out is not None or mv_options is not None or want_rigid or fit is not None,
+                               keep_poses=args.dense_out is not None or mv_options is not None or want_rigid or fit is not None
+                               or hasattr(args, "dense_holdout"),
                                **({} if post is None else {"post": post}))
         for line in dense_lines(dense) + (dense_post_lines(dense) if post is not None else []):
             print(line)
@@ -532,6 +547,12 @@ def main(argv: Optional[List[str]] = None) -> str:
             fitted = refine.evaluate_refine(dense, test_set, device, fit, getattr(args, "dense_refine_noise_px", 0.0),
                                             getattr(args, "dense_refine_seed", 0), keep=args.dense_out is not None)
             for line in refine.refine_lines(dense, fitted):
+                print(line)
+        if hasattr(args, "dense_holdout"):   # every K-th row kept, the rows in between interpolated and scored (section AB)
+            from . import resample
+            holdout = resample.evaluate_holdout(dense, args.dense_holdout, getattr(args, "dense_holdout_kind", "cubic"), device,
+                                                keep=args.dense_out is not None)
+            for line in resample.holdout_lines(dense, holdout):
                 print(line)
 
     dtw = None
@@ -606,10 +627,13 @@ def main(argv: Optional[List[str]] = None) -> str:
             extra.update(kinematics.rigid_npz(rigid))
         if fitted is not None:
             extra.update(refine.refine_npz(fitted))
+        if holdout is not None:
+            extra.update(resample.holdout_npz(holdout))
         if args.dense_out is not None:
             os.makedirs(os.path.dirname(args.dense_out) or ".", exist_ok=True)
             np.savez_compressed(args.dense_out, **dense_export(dense), **({} if multi is None else mv.multiview_export(multi)),
-                                **({} if fitted is None else refine.refine_export(fitted)))
+                                **({} if fitted is None else refine.refine_export(fitted)),
+                                **({} if holdout is None else resample.holdout_export(holdout)))
             print(f"Dense | stitched sequences saved to: {args.dense_out}")
     if dtw is not None:
         extra.update(dtw_arrays(dtw))
