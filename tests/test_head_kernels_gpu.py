@@ -531,8 +531,8 @@ def _gemm_check(got16, ref64, et, what):
     assert rel < 1e-3, f"{what}: rel-L2 {rel}"
 
 
-def _run_gemm(et, shape, tiles):
-    from implementation_phd_lab_vision_amd import ops
+def _gemm_tensors(et, shape):
+    """The seeded host tensors of one HEAD_GEMMS / BIG_GEMMS row: x (rows, K), w (cout, K), bias, residual (rows, cout) or None."""
     rows, k, cout, relu, has_res, kind = shape[:6]
     dt = R.DTYPE[et]
     g = torch.Generator().manual_seed(rows + 3 * k + 7 * cout + 11 * len(kind) + et)
@@ -542,10 +542,22 @@ def _run_gemm(et, shape, tiles):
         x[:, shape[6]:] = 0
         w[:, shape[6]:] = 0
     bias = torch.randn(cout, generator=g) * 0.1 if kind == "fwd" else torch.zeros(cout)
-    res = torch.randn(rows, cout, generator=g).to(dt).to(DEV) if has_res else None
+    res = torch.randn(rows, cout, generator=g).to(dt) if has_res else None
+    return x, w, bias, res
+
+
+def _run_gemm(et, shape, tiles, tensors=None):
+    """Every tile id of `tiles` on one row against the fp64 product; ``tensors``: host tensors in _gemm_tensors' order instead of the
+    seeded ones.  Returns the outputs, one (rows, cout) tensor per tile."""
+    from implementation_phd_lab_vision_amd import ops
+    rows, k, cout, relu, has_res, kind = shape[:6]
+    dt = R.DTYPE[et]
+    x, w, bias, res = tensors or _gemm_tensors(et, shape)
+    res = res.to(DEV) if has_res else None
     xd, wd, bd = x.to(DEV), w.to(DEV), bias.to(DEV)
     ref = R.gemm_ref(xd, wd, bd, res, relu)                                     # fp64, on the device
     numel = rows * cout
+    outs = []
     for tile in tiles:
         buf = torch.full((numel + 512 * cout,), -7.0, dtype=dt, device=DEV)
         y = ops.conv2d_bf16(xd.view(rows, 1, 1, k), wd.view(cout, 1, 1, k), bd, relu=relu,
@@ -553,6 +565,8 @@ def _run_gemm(et, shape, tiles):
         torch.cuda.synchronize()
         _gemm_check(y.view(rows, cout), ref, et, f"rows {rows} K {k} cout {cout} tile {tile}")
         assert bool((buf[numel:] == -7.0).all()), f"tile {tile}: wrote past the end of the output"
+        outs.append(y.view(rows, cout))
+    return outs
 
 
 def _gemm_id(s):

@@ -142,9 +142,16 @@ def _conv_tile_check(case, inputs, tile):
 
 @pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: "n%d_%dx%d_c%d-%d_k%ds%dp%d_r%d_res%d" % tuple(int(v) for v in c))
 def test_conv2d_matches_oracle(lib_built, case):
+    xd, wd, bd, rd, ref, (ho, wo) = _conv_inputs(case)
+    for tile in _conv_tiles(case):
+        _conv_tile_check(case, (xd, wd, bd, rd, ref, (ho, wo)), tile)
+
+
+def _conv_tiles(case):
+    """Every tile id one CONV_CASES row runs under: the generic, persistent and role-specialised ones its cout allows, plus the
+    shape-specialised kernels on their shapes."""
     from implementation_phd_lab_vision_amd import ops
     n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    xd, wd, bd, rd, ref, (ho, wo) = _conv_inputs(case)
     tiles = _tiles_for(cout, k, pad)
     if n >= 64:                      # the big case is there for the tile STREAM of the persistent kernels: the small tiles add nothing
         tiles = [ops.TILE_AUTO, ops.TILE_256x256 | ops.PERSISTENT, ops.WS | 8, ops.TILE_G8, ops.TILE_G8_224]
@@ -154,8 +161,7 @@ def test_conv2d_matches_oracle(lib_built, case):
         tiles = tiles + [ops.TILE_XRES]
     if (k, stride, pad, has_res) == (3, 2, 1, False) and (h, w, cin, cout) in ((56, 56, 128, 128), (28, 28, 256, 256), (14, 14, 512, 512)):
         tiles = tiles + [ops.TILE_S2]
-    for tile in tiles:
-        _conv_tile_check(case, (xd, wd, bd, rd, ref, (ho, wo)), tile)
+    return tiles
 
 
 G8_SHAPES = [   # n, h (= w), cin, cout, residual: the streaming 1x1 convs of layer3 / layer4 at batch 256 (+ a batch that leaves the last tile ragged)
@@ -257,20 +263,27 @@ def test_bneck_block2_equals_unfused(lib_built, n, chain):
     _run_bneck_block2(n, chain)
 
 
-def _run_bneck_block2(n, chain):
-    """Layer2 bottleneck body in one launch (conv2 3x3 + conv3 + identity + ReLU [+ next conv1]): block output and next t1 are the
-    same bits as the input-resident 3x3 launch followed by the 1x1 igemm launches (n = 70: 280 tiles, more than one per workgroup)."""
-    from implementation_phd_lab_vision_amd import ops
+def _block2_tensors(n):
+    """The seeded host tensors of _run_bneck_block2 (NHWC / OHWI): t1, idn, w2, w3, w1, b2, b3, b1."""
     g = torch.Generator().manual_seed(4100 + n)
+    t1 = _rand_bf16((n, 28, 28, 128), g).clamp_(min=0)
+    idn = _rand_bf16((n, 28, 28, 512), g).clamp_(min=0)
+    w2 = _rand_bf16((128, 3, 3, 128), g, scale=(2.0 / 1152) ** 0.5)
+    w3 = _rand_bf16((512, 1, 1, 128), g, scale=(2.0 / 128) ** 0.5)
+    w1 = _rand_bf16((128, 1, 1, 512), g, scale=(2.0 / 512) ** 0.5)
+    b2 = torch.randn(128, generator=g) * 0.1
+    b3 = torch.randn(512, generator=g) * 0.1
+    b1 = torch.randn(128, generator=g) * 0.1
+    return t1, idn, w2, w3, w1, b2, b3, b1
+
+
+def _run_bneck_block2(n, chain, tensors=None):
+    """Layer2 bottleneck body in one launch (conv2 3x3 + conv3 + identity + ReLU [+ next conv1]): block output and next t1 are the
+    same bits as the input-resident 3x3 launch followed by the 1x1 igemm launches (n = 70: 280 tiles, more than one per workgroup).
+    ``tensors``: host tensors in _block2_tensors' order and layout instead of the seeded ones."""
+    from implementation_phd_lab_vision_amd import ops
     d = _dev()
-    t1 = _rand_bf16((n, 28, 28, 128), g).clamp_(min=0).to(d)
-    idn = _rand_bf16((n, 28, 28, 512), g).clamp_(min=0).to(d)
-    w2 = _rand_bf16((128, 3, 3, 128), g, scale=(2.0 / 1152) ** 0.5).to(d)
-    w3 = _rand_bf16((512, 1, 1, 128), g, scale=(2.0 / 128) ** 0.5).to(d)
-    w1 = _rand_bf16((128, 1, 1, 512), g, scale=(2.0 / 512) ** 0.5).to(d)
-    b2 = (torch.randn(128, generator=g) * 0.1).to(d)
-    b3 = (torch.randn(512, generator=g) * 0.1).to(d)
-    b1 = (torch.randn(128, generator=g) * 0.1).to(d)
+    t1, idn, w2, w3, w1, b2, b3, b1 = (t.to(d) for t in (tensors or _block2_tensors(n)))
     t2 = ops.conv2d_bf16(t1, w2, b2, stride=1, pad=1, relu=True, tile=ops.TILE_XRES)
     out_ref = ops.conv2d_bf16(t2, w3, b3, stride=1, pad=0, relu=True, residual=idn)
     y1_ref = ops.conv2d_bf16(out_ref, w1, b1, stride=1, pad=0, relu=True)
@@ -290,20 +303,27 @@ def test_bneck_block1_equals_unfused(lib_built, n, c1):
     _run_bneck_block1(n, c1)
 
 
-def _run_bneck_block1(n, c1):
-    """Layer1 bottleneck body in one launch: block output and next t1 are the same bits as the resident-weights 3x3 launch followed by
-    the 1x1 igemm launches (n = 20: 280 tiles, more than one per workgroup; n = 41: 574 tiles, up to three per workgroup)."""
-    from implementation_phd_lab_vision_amd import ops
+def _block1_tensors(n, c1):
+    """The seeded host tensors of _run_bneck_block1 (NHWC / OHWI): t1, idn, w2, w3, w1, b2, b3, b1."""
     g = torch.Generator().manual_seed(5100 + n + c1)
+    t1 = _rand_bf16((n, 56, 56, 64), g).clamp_(min=0)
+    idn = _rand_bf16((n, 56, 56, 256), g).clamp_(min=0)
+    w2 = _rand_bf16((64, 3, 3, 64), g, scale=(2.0 / 576) ** 0.5)
+    w3 = _rand_bf16((256, 1, 1, 64), g, scale=(2.0 / 64) ** 0.5)
+    w1 = _rand_bf16((c1, 1, 1, 256), g, scale=(2.0 / 256) ** 0.5)
+    b2 = torch.randn(64, generator=g) * 0.1
+    b3 = torch.randn(256, generator=g) * 0.1
+    b1 = torch.randn(c1, generator=g) * 0.1
+    return t1, idn, w2, w3, w1, b2, b3, b1
+
+
+def _run_bneck_block1(n, c1, tensors=None):
+    """Layer1 bottleneck body in one launch: block output and next t1 are the same bits as the resident-weights 3x3 launch followed by
+    the 1x1 igemm launches (n = 20: 280 tiles, more than one per workgroup; n = 41: 574 tiles, up to three per workgroup).
+    ``tensors``: host tensors in _block1_tensors' order and layout instead of the seeded ones."""
+    from implementation_phd_lab_vision_amd import ops
     d = _dev()
-    t1 = _rand_bf16((n, 56, 56, 64), g).clamp_(min=0).to(d)
-    idn = _rand_bf16((n, 56, 56, 256), g).clamp_(min=0).to(d)
-    w2 = _rand_bf16((64, 3, 3, 64), g, scale=(2.0 / 576) ** 0.5).to(d)
-    w3 = _rand_bf16((256, 1, 1, 64), g, scale=(2.0 / 64) ** 0.5).to(d)
-    w1 = _rand_bf16((c1, 1, 1, 256), g, scale=(2.0 / 256) ** 0.5).to(d)
-    b2 = (torch.randn(64, generator=g) * 0.1).to(d)
-    b3 = (torch.randn(256, generator=g) * 0.1).to(d)
-    b1 = (torch.randn(c1, generator=g) * 0.1).to(d)
+    t1, idn, w2, w3, w1, b2, b3, b1 = (t.to(d) for t in (tensors or _block1_tensors(n, c1)))
     t2 = ops.conv2d_bf16(t1, w2, b2, stride=1, pad=1, relu=True, tile=ops.TILE_C64)
     out_ref = ops.conv2d_bf16(t2, w3, b3, stride=1, pad=0, relu=True, residual=idn)
     y1_ref = ops.conv2d_bf16(out_ref, w1, b1, stride=1, pad=0, relu=True)
@@ -319,23 +339,30 @@ def test_bneck_block1_downsample_equals_unfused(lib_built, n):
     _run_bneck_block1_ds(n)
 
 
-def _run_bneck_block1_ds(n):
+def _block1_ds_tensors(n):
+    """The seeded host tensors of _run_bneck_block1_ds (NHWC / OHWI): t1, x, w2, w3, wd, w1, b2, b3, bd, b1."""
+    g = torch.Generator().manual_seed(5300 + n)
+    t1 = _rand_bf16((n, 56, 56, 64), g).clamp_(min=0)
+    x = _rand_bf16((n, 56, 56, 64), g).clamp_(min=0)
+    w2 = _rand_bf16((64, 3, 3, 64), g, scale=(2.0 / 576) ** 0.5)
+    w3 = _rand_bf16((256, 1, 1, 64), g, scale=(2.0 / 64) ** 0.5)
+    wd = _rand_bf16((256, 1, 1, 64), g, scale=(1.0 / 64) ** 0.5)
+    w1 = _rand_bf16((64, 1, 1, 256), g, scale=(2.0 / 256) ** 0.5)
+    b2 = torch.randn(64, generator=g) * 0.1
+    b3 = torch.randn(256, generator=g) * 0.1
+    bd = torch.randn(256, generator=g) * 0.1
+    b1 = torch.randn(64, generator=g) * 0.1
+    return t1, x, w2, w3, wd, w1, b2, b3, bd, b1
+
+
+def _run_bneck_block1_ds(n, tensors=None):
     """layer1.0's body in one launch (bneck_block1_kernel<.., DS>): the identity is the downsample conv of the block input, computed in the
     kernel and rounded to bf16 as the separate launch stores it.  Block output and next t1 are the same bits as the resident-weights 3x3 launch,
-    the 1x1 downsample launch, the 1x1 conv3 launch with that identity, and the next 1x1 launch."""
+    the 1x1 downsample launch, the 1x1 conv3 launch with that identity, and the next 1x1 launch.
+    ``tensors``: host tensors in _block1_ds_tensors' order and layout instead of the seeded ones."""
     from implementation_phd_lab_vision_amd import ops
-    g = torch.Generator().manual_seed(5300 + n)
     d = _dev()
-    t1 = _rand_bf16((n, 56, 56, 64), g).clamp_(min=0).to(d)
-    x = _rand_bf16((n, 56, 56, 64), g).clamp_(min=0).to(d)
-    w2 = _rand_bf16((64, 3, 3, 64), g, scale=(2.0 / 576) ** 0.5).to(d)
-    w3 = _rand_bf16((256, 1, 1, 64), g, scale=(2.0 / 64) ** 0.5).to(d)
-    wd = _rand_bf16((256, 1, 1, 64), g, scale=(1.0 / 64) ** 0.5).to(d)
-    w1 = _rand_bf16((64, 1, 1, 256), g, scale=(2.0 / 256) ** 0.5).to(d)
-    b2 = (torch.randn(64, generator=g) * 0.1).to(d)
-    b3 = (torch.randn(256, generator=g) * 0.1).to(d)
-    bd = (torch.randn(256, generator=g) * 0.1).to(d)
-    b1 = (torch.randn(64, generator=g) * 0.1).to(d)
+    t1, x, w2, w3, wd, w1, b2, b3, bd, b1 = (t.to(d) for t in (tensors or _block1_ds_tensors(n)))
     t2 = ops.conv2d_bf16(t1, w2, b2, stride=1, pad=1, relu=True, tile=ops.TILE_C64)
     idn = ops.conv2d_bf16(x, wd, bd, stride=1, pad=0, relu=False)
     out_ref = ops.conv2d_bf16(t2, w3, b3, stride=1, pad=0, relu=True, residual=idn)
@@ -354,12 +381,8 @@ def test_bneck_tail_matches_oracle_and_unfused(lib_built, shape, c1, ds):
     _run_bneck_tail(shape, c1, ds)
 
 
-def _run_bneck_tail(shape, c1, ds):
-    """Fused layer1 tail (conv3 + identity + ReLU, then the next conv1 + ReLU) against the oracle's two fused-op
-    emulations chained, and bit-for-bit against the two igemm launches it replaces.  Pixel counts that are not a
-    multiple of 16 exercise the descriptor-clamped last tile; a guard band checks nothing is stored past M."""
-    from implementation_phd_lab_vision_amd import ops
-    from oracle.resnet50_oracle import conv_bias_act_emulated
+def _tail_tensors(shape, c1, ds):
+    """The seeded host tensors of _run_bneck_tail (NCHW / OIHW): y2, w3, b3, w1, b1, then idn -- or, with ds, xin, wd, bd."""
     n, h, w = shape
     g = torch.Generator().manual_seed(1000 + n * h * w + c1)
     y2 = _rand_bf16((n, 64, h, w), g)
@@ -367,14 +390,29 @@ def _run_bneck_tail(shape, c1, ds):
     b3 = torch.randn(256, generator=g) * 0.1
     w1 = _rand_bf16((c1, 256, 1, 1), g, scale=(2.0 / 256) ** 0.5)
     b1 = torch.randn(c1, generator=g) * 0.1
+    if ds:
+        xin = _rand_bf16((n, 64, h, w), g)
+        wd = _rand_bf16((256, 64, 1, 1), g, scale=(1.0 / 64) ** 0.5)
+        bd = torch.randn(256, generator=g) * 0.1
+        return y2, w3, b3, w1, b1, xin, wd, bd
+    return y2, w3, b3, w1, b1, _rand_bf16((n, 256, h, w), g)
+
+
+def _run_bneck_tail(shape, c1, ds, tensors=None):
+    """Fused layer1 tail (conv3 + identity + ReLU, then the next conv1 + ReLU) against the oracle's two fused-op
+    emulations chained, and bit-for-bit against the two igemm launches it replaces.  Pixel counts that are not a
+    multiple of 16 exercise the descriptor-clamped last tile; a guard band checks nothing is stored past M.
+    ``tensors``: host tensors in _tail_tensors' order and layout instead of the seeded ones."""
+    from implementation_phd_lab_vision_amd import ops
+    from oracle.resnet50_oracle import conv_bias_act_emulated
+    n, h, w = shape
+    y2, w3, b3, w1, b1, *rest = tensors or _tail_tensors(shape, c1, ds)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     w3d, w1d = w3.view(256, 64).contiguous().to(d), w1.view(c1, 256).contiguous().to(d)
     b3d, b1d = b3.to(d), b1.to(d)
     if ds:      # first block of the stage: identity = downsample(block input), computed inside the kernel
-        xin = _rand_bf16((n, 64, h, w), g)
-        wd = _rand_bf16((256, 64, 1, 1), g, scale=(1.0 / 64) ** 0.5)
-        bd = torch.randn(256, generator=g) * 0.1
+        xin, wd, bd = rest
         idn = conv_bias_act_emulated(xin.float(), wd.float(), bd, 1, 0, False)
         xind = xin.permute(0, 2, 3, 1).contiguous().to(d)
         wdd, bdd = wd.view(256, 64).contiguous().to(d), bd.to(d)
@@ -383,7 +421,7 @@ def _run_bneck_tail(shape, c1, ds):
         idn = idd.float().cpu().permute(0, 3, 1, 2)        # chain the oracle from the device's identity (see below)
         out, y1n = ops.bneck_tail_bf16(y2d, w3d, b3d, xind, w1d, b1d, wd=wdd, bd=bdd)
     else:
-        idn = _rand_bf16((n, 256, h, w), g)
+        idn, = rest
         idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
         out, y1n = ops.bneck_tail_bf16(y2d, w3d, b3d, idd, w1d, b1d)
     out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float())
@@ -405,12 +443,8 @@ def test_bneck_tail_layer2_shapes(lib_built, shape):
     _run_bneck_tail_layer2(shape)
 
 
-def _run_bneck_tail_layer2(shape):
-    """Fused layer2 tail (conv3 128->512 + identity + ReLU, next conv1 512->128 + ReLU; channels split over the waves,
-    second conv reduced through LDS).  conv3's output must equal the igemm launch bit for bit; the second conv sums
-    its K in eight slices, so it is held to the oracle under the bf16 tolerance."""
-    from implementation_phd_lab_vision_amd import ops
-    from oracle.resnet50_oracle import conv_bias_act_emulated
+def _tail2_tensors(shape):
+    """The seeded host tensors of _run_bneck_tail_layer2 (NCHW / OIHW): y2, w3, b3, idn, w1, b1."""
     n, h, w = shape
     g = torch.Generator().manual_seed(2000 + n * h * w)
     y2 = _rand_bf16((n, 128, h, w), g)
@@ -419,6 +453,18 @@ def _run_bneck_tail_layer2(shape):
     idn = _rand_bf16((n, 512, h, w), g)
     w1 = _rand_bf16((128, 512, 1, 1), g, scale=(2.0 / 512) ** 0.5)
     b1 = torch.randn(128, generator=g) * 0.1
+    return y2, w3, b3, idn, w1, b1
+
+
+def _run_bneck_tail_layer2(shape, tensors=None):
+    """Fused layer2 tail (conv3 128->512 + identity + ReLU, next conv1 512->128 + ReLU; channels split over the waves,
+    second conv reduced through LDS).  conv3's output must equal the igemm launch bit for bit; the second conv sums
+    its K in eight slices, so it is held to the oracle under the bf16 tolerance.
+    ``tensors``: host tensors in _tail2_tensors' order and layout instead of the seeded ones."""
+    from implementation_phd_lab_vision_amd import ops
+    from oracle.resnet50_oracle import conv_bias_act_emulated
+    n, h, w = shape
+    y2, w3, b3, idn, w1, b1 = tensors or _tail2_tensors(shape)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
@@ -456,16 +502,17 @@ def test_bneck_tail_layer3_shapes(lib_built, shape, bp, monkeypatch):
     _run_bneck_tail_layer3(shape, bp)
 
 
-def _run_bneck_tail_layer3(shape, bp):
+def _run_bneck_tail_layer3(shape, bp, tensors=None):
     """Chained layer3 tail (conv3 256->1024 + identity + ReLU, next conv1 1024->256 + ReLU; weights streamed through the LDS ring,
     the residual as one more K-step against an identity operand, the block output handed to the second GEMM through LDS).
     Against the oracle's two fused-op emulations, and BIT FOR BIT against the two igemm launches it replaces (same summation
     orders).  bp = real pixels per tile: ragged tiles, several tiles per workgroup (bp 7: 560 tiles), full 112-pixel tiles and 98.
-    The kernel is bneck_tail3p_kernel (two-group pipeline); rounds 2-3's bneck_tail3_kernel and the 98-row form were removed in round 4."""
+    The kernel is bneck_tail3p_kernel (two-group pipeline); rounds 2-3's bneck_tail3_kernel and the 98-row form were removed in round 4.
+    ``tensors``: host tensors in _tail3_inputs' order and layout instead of the seeded ones."""
     from implementation_phd_lab_vision_amd import ops
     from oracle.resnet50_oracle import conv_bias_act_emulated
     n, h, w = shape
-    y2, w3, b3, idn, w1, b1 = _tail3_inputs(n, h, w, 3000 + n * h * w + bp)
+    y2, w3, b3, idn, w1, b1 = tensors or _tail3_inputs(n, h, w, 3000 + n * h * w + bp)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
@@ -511,13 +558,8 @@ def test_bneck_cat_chain_equals_the_two_launches(lib_built, n):
     _run_bneck_cat_chain(n)
 
 
-def _run_bneck_cat_chain(n):
-    """layer2.0's transition tail chained with layer2.1.conv1 (bneck_catchain_kernel): conv3 + downsample as one conv over K = [t2 | x at
-    stride 2] + ReLU, then the next 1x1 + ReLU out of LDS -- BIT FOR BIT the two-source igemm launch followed by the 1x1 igemm launch it
-    replaces (n = 1 / 3: fewer tiles than CUs, ragged tiles; 37: full tiles + a ragged one; 256: the benchmarked 1792 tiles, 7 per workgroup),
-    nothing stored past M; the small cases also against the oracle's emulation."""
-    from implementation_phd_lab_vision_amd import ops
-    from oracle.resnet50_oracle import conv_bias_act_emulated
+def _cat_chain_tensors(n):
+    """The seeded host tensors of _run_bneck_cat_chain (NCHW / OIHW): t2, x, w3, wd, bcat, w1, b1."""
     g = torch.Generator().manual_seed(5100 + n)
     t2 = _rand_bf16((n, 128, 28, 28), g)
     x = _rand_bf16((n, 256, 56, 56), g)
@@ -526,6 +568,18 @@ def _run_bneck_cat_chain(n):
     bcat = torch.randn(512, generator=g) * 0.1
     w1 = _rand_bf16((128, 512, 1, 1), g, scale=(2.0 / 512) ** 0.5)
     b1 = torch.randn(128, generator=g) * 0.1
+    return t2, x, w3, wd, bcat, w1, b1
+
+
+def _run_bneck_cat_chain(n, tensors=None):
+    """layer2.0's transition tail chained with layer2.1.conv1 (bneck_catchain_kernel): conv3 + downsample as one conv over K = [t2 | x at
+    stride 2] + ReLU, then the next 1x1 + ReLU out of LDS -- BIT FOR BIT the two-source igemm launch followed by the 1x1 igemm launch it
+    replaces (n = 1 / 3: fewer tiles than CUs, ragged tiles; 37: full tiles + a ragged one; 256: the benchmarked 1792 tiles, 7 per workgroup),
+    nothing stored past M; the small cases also against the oracle's emulation.
+    ``tensors``: host tensors in _cat_chain_tensors' order and layout instead of the seeded ones."""
+    from implementation_phd_lab_vision_amd import ops
+    from oracle.resnet50_oracle import conv_bias_act_emulated
+    t2, x, w3, wd, bcat, w1, b1 = tensors or _cat_chain_tensors(n)
     d = _dev()
     t2d = t2.permute(0, 2, 3, 1).contiguous().to(d)
     xd = x.permute(0, 2, 3, 1).contiguous().to(d)
@@ -552,11 +606,12 @@ def test_layer3_last_block_conv3_through_the_pipelined_tail(lib_built, n):
     _run_layer3_last_block(n)
 
 
-def _run_layer3_last_block(n):
+def _run_layer3_last_block(n, tensors=None):
     """layer3.5: conv3 + identity + ReLU through bneck_tail3p_kernel<.., NOB> (no second GEMM; group B only copies out_c out) -- bit for bit the
-    igemm launch with a residual it replaces; nothing written past M."""
+    igemm launch with a residual it replaces; nothing written past M.
+    ``tensors``: host tensors in _tail3_inputs' order and layout instead of the seeded ones."""
     from implementation_phd_lab_vision_amd import ops
-    y2, w3, b3, idn, _w1, _b1 = _tail3_inputs(n, 14, 14, 4100 + n)
+    y2, w3, b3, idn, _w1, _b1 = tensors or _tail3_inputs(n, 14, 14, 4100 + n)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
@@ -682,17 +737,25 @@ def test_conv1x1_two_k_sources(lib_built, case, et):
     _run_conv1x1_cat(case, et)
 
 
-def _run_conv1x1_cat(case, et):
-    """One 1x1 conv over K = [x1 | x2 at stride2] (conv3 + downsample + add + ReLU of a stage's first bottleneck) against a wide
-    accumulation of the same sum; a poisoned guard band behind the output must stay untouched."""
-    import torch.nn.functional as F
-    from implementation_phd_lab_vision_amd import ops
+def _cat_tensors(case, et):
+    """The seeded host tensors of _run_conv1x1_cat (NHWC, wcat (cout, c1 + c2)): x1, x2, wcat, bias."""
     n, h, c1, h2, c2, s2, cout, relu, tile = case
     g = torch.Generator().manual_seed(h * 131 + c2)
     x1 = (torch.randn(n, h, h, c1, generator=g)).to(et)
     x2 = (torch.randn(n, h2, h2, c2, generator=g)).to(et)
     wcat = (torch.randn(cout, c1 + c2, generator=g) * (1.0 / (c1 + c2)) ** 0.5).to(et)
     bias = torch.randn(cout, generator=g) * 0.1
+    return x1, x2, wcat, bias
+
+
+def _run_conv1x1_cat(case, et, tensors=None):
+    """One 1x1 conv over K = [x1 | x2 at stride2] (conv3 + downsample + add + ReLU of a stage's first bottleneck) against a wide
+    accumulation of the same sum; a poisoned guard band behind the output must stay untouched.
+    ``tensors``: host tensors in _cat_tensors' order and layout instead of the seeded ones."""
+    import torch.nn.functional as F
+    from implementation_phd_lab_vision_amd import ops
+    n, h, c1, h2, c2, s2, cout, relu, tile = case
+    x1, x2, wcat, bias = tensors or _cat_tensors(case, et)
     y = ops.conv1x1_cat(x1.to("cuda:0"), x2.to("cuda:0"), s2, wcat.to("cuda:0"), bias.to("cuda:0"), relu=relu, tile=tile)
     ref = F.conv2d(x1.double().permute(0, 3, 1, 2), wcat[:, :c1].double().view(cout, c1, 1, 1))
     ref = ref + F.conv2d(x2.double().permute(0, 3, 1, 2), wcat[:, c1:].double().view(cout, c2, 1, 1), stride=s2)
@@ -728,10 +791,8 @@ def test_conv2d_fp8(lib_built, case):
     _run_conv2d_fp8(case)
 
 
-def _run_conv2d_fp8(case):
-    """fp8 (e4m3) conv on the K = 128 scaled MFMA (BASELINE configs[4], kernel level) against a wide accumulation of the same
-    quantised operands, requantised with torch's round-to-nearest-even fp8 conversion."""
-    import torch.nn.functional as F
+def _fp8_tensors(case):
+    """The seeded host tensors of _run_conv2d_fp8 (NHWC / OHWI e4m3): xq, wq, bias, rq or None, and the scales (sx, sw, sr, sy)."""
     from implementation_phd_lab_vision_amd import ops
     n, h, w, cin, cout, k, stride, pad, relu, has_res, tile = case
     g = torch.Generator().manual_seed(cin * 7 + cout + k)
@@ -741,16 +802,34 @@ def _run_conv2d_fp8(case):
     bias = torch.randn(cout, generator=g) * 0.1
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     rq = (torch.randn(n, ho, wo, cout, generator=g) / sr * 0.5).clamp(-448, 448).to(ops.FP8) if has_res else None
-    y = ops.conv2d_fp8(xq.to("cuda:0"), sx, wq.to("cuda:0"), sw, bias.to("cuda:0"), sy, stride=stride, pad=pad, relu=bool(relu),
-                       residual=rq.to("cuda:0") if has_res else None, sr=sr, tile=tile)
-    assert y.dtype == ops.FP8 and tuple(y.shape) == (n, ho, wo, cout)
+    return xq, wq, bias, rq, (sx, sw, sr, sy)
+
+
+def fp8_reference(xq, wq, bias, rq, scales, stride, pad, relu):
+    """The fp64 value of one fp8 conv before its requantisation, in units of sy (NCHW): act(sx*sw * sum(x*w) + bias + sr*residual) / sy."""
+    import torch.nn.functional as F
+    sx, sw, sr, sy = scales
     ref = F.conv2d(xq.double().permute(0, 3, 1, 2) * sx, wq.double().permute(0, 3, 1, 2) * sw, stride=stride, padding=pad)
     ref = ref + bias.double().view(1, -1, 1, 1)
-    if has_res:
+    if rq is not None:
         ref = ref + rq.double().permute(0, 3, 1, 2) * sr
     if relu:
         ref = F.relu(ref)
-    ref_q = (ref / sy).clamp(-448, 448).float().to(ops.FP8).float()
+    return ref / sy
+
+
+def _run_conv2d_fp8(case, tensors=None):
+    """fp8 (e4m3) conv on the K = 128 scaled MFMA (BASELINE configs[4], kernel level) against a wide accumulation of the same
+    quantised operands, requantised with torch's round-to-nearest-even fp8 conversion.
+    ``tensors``: host tensors and scales in _fp8_tensors' order and layout instead of the seeded ones."""
+    from implementation_phd_lab_vision_amd import ops
+    n, h, w, cin, cout, k, stride, pad, relu, has_res, tile = case
+    xq, wq, bias, rq, (sx, sw, sr, sy) = tensors or _fp8_tensors(case)
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    y = ops.conv2d_fp8(xq.to("cuda:0"), sx, wq.to("cuda:0"), sw, bias.to("cuda:0"), sy, stride=stride, pad=pad, relu=bool(relu),
+                       residual=rq.to("cuda:0") if has_res else None, sr=sr, tile=tile)
+    assert y.dtype == ops.FP8 and tuple(y.shape) == (n, ho, wo, cout)
+    ref_q = fp8_reference(xq, wq, bias, rq, (sx, sw, sr, sy), stride, pad, relu).clamp(-448, 448).float().to(ops.FP8).float()
     got = y.float().cpu().permute(0, 3, 1, 2)
     assert torch.isfinite(got).all()
     diff = (got - ref_q).abs()
