@@ -1917,18 +1917,24 @@ int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* 
     return op_status(e, "r50_op_conv1x1_cat");
 }
 
+// Element type of the op-level hooks that have no argument for it (the fused tails, bodies and chain, the stem, the two pools): they run
+// the bf16 instantiations unless R50_OP_ET=1 is in the environment, which selects the IEEE-half ones a handle in R50_PREC_FP16 launches
+// (every tensor and weight is then fp16).  A test knob like R50_TAIL3_BP, read per call.
+static int op_et() { const char* v = std::getenv("R50_OP_ET"); return (v && std::atoi(v) == 1) ? 1 : 0; }
+
 int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const float* b3, const void* res, const void* wd,
                       const float* bd, void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
     hipError_t e;
-    if (cmid == 64) e = launch_bneck_tail(y2, m, w3, b3, res, wd, bd, out, w1, c1, b1, y1n, (hipStream_t)stream);
-    else if (cmid == 128 && c1 == 128 && !wd && !bd) e = launch_bneck_tail2(y2, m, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream);
+    const int et = op_et();
+    if (cmid == 64) e = launch_bneck_tail(y2, m, w3, b3, res, wd, bd, out, w1, c1, b1, y1n, (hipStream_t)stream, et);
+    else if (cmid == 128 && c1 == 128 && !wd && !bd) e = launch_bneck_tail2(y2, m, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, et);
     else if (cmid == 256 && c1 == 0 && !w1 && !b1 && !y1n && !wd && !bd) {
         // conv3 + identity + ReLU alone through the pipelined layer3 tail (the form layer3.5 runs in the network): W3 stands in for the unused W1 slices
         void* wp_scratch = nullptr;
         if (hipMallocAsync(&wp_scratch, kTail3PackedBytes, (hipStream_t)stream) != hipSuccess || !wp_scratch)
             return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_tail: hipMallocAsync");
         e = pack_tail3_weights(w3, w3, wp_scratch, (hipStream_t)stream);
-        if (e == hipSuccess) e = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, nullptr, nullptr, (hipStream_t)stream, 0, 0, /*no_next=*/true);
+        if (e == hipSuccess) e = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, nullptr, nullptr, (hipStream_t)stream, et, 0, /*no_next=*/true);
         const hipError_t ef = hipFreeAsync(wp_scratch, (hipStream_t)stream);
         if (e == hipSuccess) e = ef;
     }
@@ -1940,7 +1946,7 @@ int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const
         if (hipMallocAsync(&wp_scratch, kTail3PackedBytes, (hipStream_t)stream) != hipSuccess || !wp_scratch)
             return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_tail: hipMallocAsync");
         e = pack_tail3_weights(w3, w1, wp_scratch, (hipStream_t)stream);
-        if (e == hipSuccess) e = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, b1, y1n, (hipStream_t)stream, 0, v ? std::atoi(v) : 0);
+        if (e == hipSuccess) e = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, b1, y1n, (hipStream_t)stream, et, v ? std::atoi(v) : 0);
         const hipError_t ef = hipFreeAsync(wp_scratch, (hipStream_t)stream);
         if (e == hipSuccess) e = ef;
     }
@@ -1950,14 +1956,14 @@ int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const
 
 int r50_op_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, const float* b1, void* y1n, void* stream) {
-    const hipError_t e = launch_bneck_block2(t1, n, w2, b2, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream);
+    const hipError_t e = launch_bneck_block2(t1, n, w2, b2, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, op_et());
     return op_status(e, "r50_op_bneck_block2");
 }
 
 int r50_op_bneck_block1_ds(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* x, const void* wd,
                            const float* bd, void* out, const void* w1, const float* b1, void* y1n, void* stream) {
     if (!wd || !bd) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_block1_ds: null downsample weights");
-    const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, x, out, w1, 64, b1, y1n, (hipStream_t)stream, 0, wd, bd);
+    const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, x, out, w1, 64, b1, y1n, (hipStream_t)stream, op_et(), wd, bd);
     return op_status(e, "r50_op_bneck_block1_ds");
 }
 
@@ -1969,7 +1975,7 @@ int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const v
     if (hipMallocAsync(&wp, kCatChainPackedBytes, (hipStream_t)stream) != hipSuccess || !wp)
         return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_cat_chain: hipMallocAsync");
     hipError_t e = pack_catchain_weights(wcat, w1, wp, (hipStream_t)stream);
-    if (e == hipSuccess) e = launch_bneck_catchain(t2, x, n, ow, wp, bcat, out, b1, y1n, (hipStream_t)stream);
+    if (e == hipSuccess) e = launch_bneck_catchain(t2, x, n, ow, wp, bcat, out, b1, y1n, (hipStream_t)stream, op_et());
     const hipError_t ef = hipFreeAsync(wp, (hipStream_t)stream);
     if (e == hipSuccess) e = ef;
     return op_status(e, "r50_op_bneck_cat_chain");
@@ -1977,7 +1983,7 @@ int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const v
 
 int r50_op_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
-    const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, res, out, w1, c1, b1, y1n, (hipStream_t)stream);
+    const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, res, out, w1, c1, b1, y1n, (hipStream_t)stream, op_et());
     return op_status(e, "r50_op_bneck_block1");
 }
 
@@ -2964,25 +2970,26 @@ int64_t r50_stem_scratch_bytes(int n) { return (int64_t)STEM_W_BYTES + (int64_t)
 int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_dev, void* scratch, void* y, void* stream) {
     if (!x || !w_host || !bias_dev || !scratch || !y || n < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_stem: invalid arguments");
     std::vector<uint16_t> pk;
-    pack_stem(w_host, pk);
+    const int et = op_et();
+    pack_stem(w_host, pk, et == 1 ? 2 : 0);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(nullptr, hipMemcpyAsync(scratch, pk.data(), STEM_W_BYTES, hipMemcpyHostToDevice, s));
     HIP_TRY(nullptr, hipStreamSynchronize(s));   // pk is a host temporary
     char* xp = (char*)scratch + STEM_W_BYTES;
-    HIP_TRY(nullptr, launch_stem_pack(x, xp, n, s));
-    HIP_TRY(nullptr, launch_stem_conv(xp, scratch, bias_dev, y, n, s));
+    HIP_TRY(nullptr, launch_stem_pack(x, xp, n, s, et));
+    HIP_TRY(nullptr, launch_stem_conv(xp, scratch, bias_dev, y, n, s, et));
     return R50_OK;
 }
 
 int r50_op_maxpool(const void* x, int n, int h, int w, int c, void* y, void* stream) {
     if (!x || !y || n < 1 || h < 1 || w < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_maxpool: invalid arguments");
-    HIP_TRY(nullptr, launch_maxpool(x, y, n, h, w, c, (hipStream_t)stream));
+    HIP_TRY(nullptr, launch_maxpool(x, y, n, h, w, c, (hipStream_t)stream, op_et()));
     return R50_OK;
 }
 
 int r50_op_avgpool(const void* x, int n, int hw, int c, float* y, void* stream) {
     if (!x || !y || n < 1 || hw < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: invalid arguments");
-    HIP_TRY(nullptr, launch_avgpool(x, y, n, hw, c, (hipStream_t)stream));
+    HIP_TRY(nullptr, launch_avgpool(x, y, n, hw, c, (hipStream_t)stream, op_et()));
     return R50_OK;
 }
 

@@ -6,6 +6,8 @@ AdaptiveAvgPool2d((1,1)).  Tensors are bf16 NHWC on an MI355X; used by the per-k
 """
 from __future__ import annotations
 
+import contextlib
+import os
 from typing import Optional
 
 import torch
@@ -196,6 +198,27 @@ def conv1x1_cat(x1: torch.Tensor, x2: torch.Tensor, stride2: int, wcat: torch.Te
     return y
 
 
+def _et16(t: torch.Tensor, name: str):
+    """The 16-bit element type of an op whose C hook takes none: bf16, or fp16 -- the hook then runs its IEEE-half kernels (``_op_et``)."""
+    if t.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{name}: expected bfloat16 or float16, got {t.dtype}")
+    return t.dtype
+
+
+@contextlib.contextmanager
+def _op_et(et):
+    """R50_OP_ET (include/r50.h) around one call of a hook without an element-type argument: 1 for fp16 tensors, unset for bf16."""
+    old = os.environ.pop("R50_OP_ET", None)
+    if et == torch.float16:
+        os.environ["R50_OP_ET"] = "1"
+    try:
+        yield
+    finally:
+        os.environ.pop("R50_OP_ET", None)
+        if old is not None:
+            os.environ["R50_OP_ET"] = old
+
+
 def bneck_tail_bf16(y2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, identity: torch.Tensor, w1: torch.Tensor,
                     b1: torch.Tensor, wd: Optional[torch.Tensor] = None, bd: Optional[torch.Tensor] = None,
                     out: Optional[torch.Tensor] = None, y1n: Optional[torch.Tensor] = None):
@@ -205,8 +228,9 @@ def bneck_tail_bf16(y2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, identi
     kernel, weights streamed through LDS).  ``out`` / ``y1n``: optional preallocated outputs.  ``identity`` is the
     (...,4*cmid) identity tensor, or -- cmid = 64 with the folded downsample weights ``wd`` (256,64) / ``bd`` --
     the (...,64) block input."""
+    et = _et16(y2, "y2")
     for t, n in ((y2, "y2"), (w3, "w3"), (identity, "identity"), (w1, "w1")):
-        _need(t, torch.bfloat16, n)
+        _need(t, et, n)
     _need(b3, torch.float32, "b3"); _need(b1, torch.float32, "b1")
     cmid = y2.shape[-1]
     cout = 4 * cmid
@@ -216,20 +240,20 @@ def bneck_tail_bf16(y2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, identi
     if (wd is None) != (bd is None):
         raise ValueError("bneck_tail_bf16: wd and bd go together")
     if wd is not None:
-        _need(wd, torch.bfloat16, "wd"); _need(bd, torch.float32, "bd")
+        _need(wd, et, "wd"); _need(bd, torch.float32, "bd")
         if tuple(wd.shape) != (cout, cmid) or bd.numel() != cout:
             raise ValueError("bneck_tail_bf16: inconsistent downsample shapes")
     if identity.shape[-1] != cid or identity.numel() != m * cid or tuple(w3.shape) != (cout, cmid) \
             or tuple(w1.shape) != (c1, cout) or b3.numel() != cout or b1.numel() != c1:
         raise ValueError("bneck_tail_bf16: inconsistent shapes")
     if out is None:
-        out = torch.empty(tuple(y2.shape[:-1]) + (cout,), dtype=torch.bfloat16, device=y2.device)
+        out = torch.empty(tuple(y2.shape[:-1]) + (cout,), dtype=et, device=y2.device)
     if y1n is None:
-        y1n = torch.empty(tuple(y2.shape[:-1]) + (c1,), dtype=torch.bfloat16, device=y2.device)
-    _need(out, torch.bfloat16, "out"); _need(y1n, torch.bfloat16, "y1n")
+        y1n = torch.empty(tuple(y2.shape[:-1]) + (c1,), dtype=et, device=y2.device)
+    _need(out, et, "out"); _need(y1n, et, "y1n")
     if out.numel() != m * cout or y1n.numel() != m * c1:
         raise ValueError("bneck_tail_bf16: output tensors have the wrong size")
-    with torch.cuda.device(y2.device):
+    with torch.cuda.device(y2.device), _op_et(et):
         rc = _lib.load_library().r50_op_bneck_tail(y2.data_ptr(), m, cmid, w3.data_ptr(), b3.data_ptr(), identity.data_ptr(),
                                                    wd.data_ptr() if wd is not None else None,
                                                    bd.data_ptr() if bd is not None else None,
@@ -241,14 +265,15 @@ def bneck_tail_bf16(y2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, identi
 def conv3_identity_tail3_bf16(y2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, identity: torch.Tensor) -> torch.Tensor:
     """``relu(conv3(y2) + b3 + identity)`` of a layer3 block (y2 (...,256), w3 (1024,256), identity (...,1024)) through the pipelined tail kernel
     WITHOUT a next conv1 (``r50_op_bneck_tail`` with c1 = 0): the form the stage's last block, layer3.5, runs in."""
+    et = _et16(y2, "y2")
     for t, n in ((y2, "y2"), (w3, "w3"), (identity, "identity")):
-        _need(t, torch.bfloat16, n)
+        _need(t, et, n)
     _need(b3, torch.float32, "b3")
     m = y2.numel() // 256
     if y2.shape[-1] != 256 or tuple(w3.shape) != (1024, 256) or identity.numel() != m * 1024 or b3.numel() != 1024:
         raise ValueError("conv3_identity_tail3_bf16: inconsistent shapes")
-    out = torch.empty(tuple(y2.shape[:-1]) + (1024,), dtype=torch.bfloat16, device=y2.device)
-    with torch.cuda.device(y2.device):
+    out = torch.empty(tuple(y2.shape[:-1]) + (1024,), dtype=et, device=y2.device)
+    with torch.cuda.device(y2.device), _op_et(et):
         rc = _lib.load_library().r50_op_bneck_tail(y2.data_ptr(), m, 256, w3.data_ptr(), b3.data_ptr(), identity.data_ptr(), None, None,
                                                    out.data_ptr(), None, 0, None, None, _stream(y2))
     _lib.check(rc, None, "r50_op_bneck_tail")
@@ -259,8 +284,9 @@ def bneck_block2_bf16(t1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: 
                       w1: Optional[torch.Tensor] = None, b1: Optional[torch.Tensor] = None):
     """Layer2 bottleneck body in one launch (``r50_op_bneck_block2``): t1 (N,28,28,128), identity (N,28,28,512) bf16 NHWC; w2 (128,3,3,128),
     w3 (512,128), w1 (128,512) bf16, K contiguous; biases fp32.  Returns (block output (N,28,28,512), next t1 (N,28,28,128) or None)."""
+    et = _et16(t1, "t1")
     for t, name in ((t1, "t1"), (w2, "w2"), (w3, "w3"), (identity, "identity")):
-        _need(t, torch.bfloat16, name)
+        _need(t, et, name)
     _need(b2, torch.float32, "b2"); _need(b3, torch.float32, "b3")
     n = t1.shape[0]
     if tuple(t1.shape) != (n, 28, 28, 128) or tuple(identity.shape) != (n, 28, 28, 512) or tuple(w2.shape) != (128, 3, 3, 128) \
@@ -268,14 +294,14 @@ def bneck_block2_bf16(t1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: 
         raise ValueError("bneck_block2_bf16: inconsistent shapes")
     if (w1 is None) != (b1 is None):
         raise ValueError("bneck_block2_bf16: w1 and b1 go together")
-    out = torch.empty((n, 28, 28, 512), dtype=torch.bfloat16, device=t1.device)
+    out = torch.empty((n, 28, 28, 512), dtype=et, device=t1.device)
     y1n = None
     if w1 is not None:
-        _need(w1, torch.bfloat16, "w1"); _need(b1, torch.float32, "b1")
+        _need(w1, et, "w1"); _need(b1, torch.float32, "b1")
         if tuple(w1.shape) != (128, 512) or b1.numel() != 128:
             raise ValueError("bneck_block2_bf16: inconsistent next-conv1 shapes")
-        y1n = torch.empty((n, 28, 28, 128), dtype=torch.bfloat16, device=t1.device)
-    with torch.cuda.device(t1.device):
+        y1n = torch.empty((n, 28, 28, 128), dtype=et, device=t1.device)
+    with torch.cuda.device(t1.device), _op_et(et):
         rc = _lib.load_library().r50_op_bneck_block2(t1.data_ptr(), n, w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(),
                                                      identity.data_ptr(), out.data_ptr(),
                                                      w1.data_ptr() if w1 is not None else None, b1.data_ptr() if b1 is not None else None,
@@ -288,17 +314,18 @@ def bneck_block1_ds_bf16(t1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w
                          wd: torch.Tensor, bd: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor):
     """layer1.0's bottleneck body in one launch (``r50_op_bneck_block1_ds``): t1 (N,56,56,64), block input x (N,56,56,64) bf16 NHWC; w2 (64,3,3,64),
     w3 (256,64), wd (256,64), w1 (64,256) bf16; biases fp32.  Returns (block output (N,56,56,256), next t1 (N,56,56,64))."""
+    et = _et16(t1, "t1")
     for t, name in ((t1, "t1"), (w2, "w2"), (w3, "w3"), (x, "x"), (wd, "wd"), (w1, "w1")):
-        _need(t, torch.bfloat16, name)
+        _need(t, et, name)
     for t, name in ((b2, "b2"), (b3, "b3"), (bd, "bd"), (b1, "b1")):
         _need(t, torch.float32, name)
     n = t1.shape[0]
     if tuple(t1.shape) != (n, 56, 56, 64) or tuple(x.shape) != (n, 56, 56, 64) or tuple(w2.shape) != (64, 3, 3, 64) or tuple(w3.shape) != (256, 64) \
             or tuple(wd.shape) != (256, 64) or tuple(w1.shape) != (64, 256) or b2.numel() != 64 or b3.numel() != 256 or bd.numel() != 256 or b1.numel() != 64:
         raise ValueError("bneck_block1_ds_bf16: inconsistent shapes")
-    out = torch.empty((n, 56, 56, 256), dtype=torch.bfloat16, device=t1.device)
-    y1n = torch.empty((n, 56, 56, 64), dtype=torch.bfloat16, device=t1.device)
-    with torch.cuda.device(t1.device):
+    out = torch.empty((n, 56, 56, 256), dtype=et, device=t1.device)
+    y1n = torch.empty((n, 56, 56, 64), dtype=et, device=t1.device)
+    with torch.cuda.device(t1.device), _op_et(et):
         rc = _lib.load_library().r50_op_bneck_block1_ds(t1.data_ptr(), n, w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), x.data_ptr(),
                                                         wd.data_ptr(), bd.data_ptr(), out.data_ptr(), w1.data_ptr(), b1.data_ptr(), y1n.data_ptr(),
                                                         _stream(t1))
@@ -310,16 +337,17 @@ def bneck_cat_chain_bf16(t2: torch.Tensor, x: torch.Tensor, wcat: torch.Tensor, 
     """layer2.0's transition tail chained with layer2.1.conv1 in one launch (``r50_op_bneck_cat_chain``): t2 (N,28,28,128), block input x
     (N,56,56,256) bf16 NHWC; wcat (512,384) = [W3 | Wd], w1 (128,512) bf16, K contiguous; bcat = b3 + bd, b1 fp32.
     Returns (block output (N,28,28,512), next t1 (N,28,28,128))."""
+    et = _et16(t2, "t2")
     for t, name in ((t2, "t2"), (x, "x"), (wcat, "wcat"), (w1, "w1")):
-        _need(t, torch.bfloat16, name)
+        _need(t, et, name)
     _need(bcat, torch.float32, "bcat"); _need(b1, torch.float32, "b1")
     n = t2.shape[0]
     if tuple(t2.shape) != (n, 28, 28, 128) or tuple(x.shape) != (n, 56, 56, 256) or tuple(wcat.shape) != (512, 384) or tuple(w1.shape) != (128, 512) \
             or bcat.numel() != 512 or b1.numel() != 128:
         raise ValueError("bneck_cat_chain_bf16: inconsistent shapes")
-    out = torch.empty((n, 28, 28, 512), dtype=torch.bfloat16, device=t2.device)
-    y1n = torch.empty((n, 28, 28, 128), dtype=torch.bfloat16, device=t2.device)
-    with torch.cuda.device(t2.device):
+    out = torch.empty((n, 28, 28, 512), dtype=et, device=t2.device)
+    y1n = torch.empty((n, 28, 28, 128), dtype=et, device=t2.device)
+    with torch.cuda.device(t2.device), _op_et(et):
         rc = _lib.load_library().r50_op_bneck_cat_chain(t2.data_ptr(), x.data_ptr(), n, 28, wcat.data_ptr(), bcat.data_ptr(), out.data_ptr(),
                                                         w1.data_ptr(), b1.data_ptr(), y1n.data_ptr(), _stream(t2))
     _lib.check(rc, None, "r50_op_bneck_cat_chain")
@@ -330,8 +358,9 @@ def bneck_block1_bf16(t1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: 
                       w1: torch.Tensor, b1: torch.Tensor):
     """Layer1 bottleneck body in one launch (``r50_op_bneck_block1``): t1 (N,56,56,64), identity (N,56,56,256) bf16 NHWC; w2 (64,3,3,64),
     w3 (256,64), w1 (c1,256) bf16 with c1 in {64, 128}; biases fp32.  Returns (block output (N,56,56,256), next t1 (N,56,56,c1))."""
+    et = _et16(t1, "t1")
     for t, name in ((t1, "t1"), (w2, "w2"), (w3, "w3"), (identity, "identity"), (w1, "w1")):
-        _need(t, torch.bfloat16, name)
+        _need(t, et, name)
     _need(b2, torch.float32, "b2"); _need(b3, torch.float32, "b3"); _need(b1, torch.float32, "b1")
     n = t1.shape[0]
     c1 = w1.shape[0]
@@ -339,9 +368,9 @@ def bneck_block1_bf16(t1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: 
             or tuple(w3.shape) != (256, 64) or tuple(w1.shape) != (c1, 256) or c1 not in (64, 128) or b2.numel() != 64 or b3.numel() != 256 \
             or b1.numel() != c1:
         raise ValueError("bneck_block1_bf16: inconsistent shapes")
-    out = torch.empty((n, 56, 56, 256), dtype=torch.bfloat16, device=t1.device)
-    y1n = torch.empty((n, 56, 56, c1), dtype=torch.bfloat16, device=t1.device)
-    with torch.cuda.device(t1.device):
+    out = torch.empty((n, 56, 56, 256), dtype=et, device=t1.device)
+    y1n = torch.empty((n, 56, 56, c1), dtype=et, device=t1.device)
+    with torch.cuda.device(t1.device), _op_et(et):
         rc = _lib.load_library().r50_op_bneck_block1(t1.data_ptr(), n, w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(),
                                                      identity.data_ptr(), out.data_ptr(), w1.data_ptr(), c1, b1.data_ptr(), y1n.data_ptr(),
                                                      _stream(t1))
@@ -349,9 +378,12 @@ def bneck_block1_bf16(t1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: 
     return out, y1n
 
 
-def stem_bf16(x_nchw: torch.Tensor, w_folded_oihw: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+def stem_bf16(x_nchw: torch.Tensor, w_folded_oihw: torch.Tensor, bias: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
     """conv1 7x7 s2 p3 + folded bn1 + ReLU: (N,3,224,224) fp32 NCHW -> (N,112,112,64) bf16 NHWC.
-    ``w_folded_oihw``: (64,3,7,7) fp32 on the HOST (already BN-folded); ``bias``: (64) fp32 on the GPU."""
+    ``w_folded_oihw``: (64,3,7,7) fp32 on the HOST (already BN-folded); ``bias``: (64) fp32 on the GPU.  ``dtype`` float16: the
+    IEEE-half stem (weights and output in fp16)."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"stem_bf16: dtype {dtype}")
     _need(x_nchw, torch.float32, "x"); _need(bias, torch.float32, "bias")
     if tuple(x_nchw.shape[1:]) != (3, 224, 224) or tuple(w_folded_oihw.shape) != (64, 3, 7, 7):
         raise ValueError("stem_bf16: bad shapes")
@@ -359,8 +391,8 @@ def stem_bf16(x_nchw: torch.Tensor, w_folded_oihw: torch.Tensor, bias: torch.Ten
     n = x_nchw.shape[0]
     lib = _lib.load_library()
     scratch = torch.empty(lib.r50_stem_scratch_bytes(n), dtype=torch.uint8, device=x_nchw.device)
-    y = torch.empty((n, 112, 112, 64), dtype=torch.bfloat16, device=x_nchw.device)
-    with torch.cuda.device(x_nchw.device):
+    y = torch.empty((n, 112, 112, 64), dtype=dtype, device=x_nchw.device)
+    with torch.cuda.device(x_nchw.device), _op_et(dtype):
         rc = lib.r50_op_stem(x_nchw.data_ptr(), n, w_host.data_ptr(), bias.data_ptr(), scratch.data_ptr(),
                              y.data_ptr(), _stream(x_nchw))
     _lib.check(rc, None, "r50_op_stem")
@@ -369,10 +401,11 @@ def stem_bf16(x_nchw: torch.Tensor, w_folded_oihw: torch.Tensor, bias: torch.Ten
 
 def maxpool_bf16(x: torch.Tensor) -> torch.Tensor:
     """MaxPool2d(3, stride 2, pad 1) on (N,H,W,C) bf16."""
-    _need(x, torch.bfloat16, "x")
+    et = _et16(x, "x")
+    _need(x, et, "x")
     n, h, w, c = x.shape
-    y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
+    y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=et, device=x.device)
+    with torch.cuda.device(x.device), _op_et(et):
         rc = _lib.load_library().r50_op_maxpool(x.data_ptr(), n, h, w, c, y.data_ptr(), _stream(x))
     _lib.check(rc, None, "r50_op_maxpool")
     return y
@@ -380,10 +413,11 @@ def maxpool_bf16(x: torch.Tensor) -> torch.Tensor:
 
 def avgpool_bf16(x: torch.Tensor) -> torch.Tensor:
     """AdaptiveAvgPool2d((1,1)) + flatten(1) on (N,H,W,C) bf16 -> (N,C) fp32."""
-    _need(x, torch.bfloat16, "x")
+    et = _et16(x, "x")
+    _need(x, et, "x")
     n, h, w, c = x.shape
     y = torch.empty((n, c), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
+    with torch.cuda.device(x.device), _op_et(et):
         rc = _lib.load_library().r50_op_avgpool(x.data_ptr(), n, h * w, c, y.data_ptr(), _stream(x))
     _lib.check(rc, None, "r50_op_avgpool")
     return y

@@ -216,6 +216,10 @@ int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* 
  * Holds the host: the weights are packed into a host temporary, uploaded on `stream`, and the call synchronises `stream` once before
  * it launches (r50_forward does not: a handle keeps its packed stem weights on the device). */
 int64_t r50_stem_scratch_bytes(int n);
+/* Element type of the hooks that have no argument for it -- r50_op_stem, r50_op_maxpool, r50_op_avgpool, r50_op_bneck_tail,
+ * r50_op_bneck_block1, r50_op_bneck_block1_ds, r50_op_bneck_block2, r50_op_bneck_cat_chain: bf16, as their parameter names say.  With
+ * R50_OP_ET=1 in the environment (a test knob, read per call) they run the IEEE-half instantiations that a handle in R50_PREC_FP16
+ * launches: every 16-bit tensor and weight matrix is then fp16 (the stem packs its fp32 weights to fp16), same layouts. */
 int r50_op_stem(const float* x_nchw_f32_dev, int n, const float* w_oihw_f32_host,
                 const float* bias_f32_dev, void* scratch_dev, void* y_nhwc_bf16, void* stream);
 

@@ -4,7 +4,11 @@
   order), fp16 unsaturated; small regime: nothing rounded; wide regime: >= 1 % ties of each parity wherever there are 1000 outputs;
 * mutants of the reference (one product removed, two K channels of the last K slice swapped, one halo tap taken from the neighbouring
   image) change at least one element in the small regime; a double rounding changes the wide regime;
-* torch's CPU conversions to bf16 / fp16 / e4m3, which the references round with, send the constructed ties to even.
+* torch's CPU conversions to bf16 / fp16 / e4m3, which the references round with, send the constructed ties to even -- on the
+  subnormal grids of fp16 and e4m3 too (every multiple of 2^-27 up to 2^-14, of 2^-12 up to 2^-6), and fp16 saturates at the clamp;
+* the low and high regimes (the ends of fp16 and e4m3) meet ``assert_edge_precondition`` in every case, both operand sides carry the
+  subnormal values somewhere in every case list, and six mutants of the reference -- subnormal activations / weights / outputs flushed
+  to zero, subnormal outputs truncated, the conversion without its clamp, the clamp at 65520 -- change every case.
 """
 import math
 
@@ -103,6 +107,156 @@ def test_avgpool_reference_is_the_exact_sum_times_the_fp32_reciprocal(shape):
     for r in range(h * w):                                   # the kernel's order: rows added one by one in fp32
         s += x.view(n, h * w, c)[:, r].float()
     assert torch.equal(s * torch.tensor(1.0 / (h * w), dtype=torch.float32), ref)
+
+
+# ---- the ends of fp16 and e4m3: conditions, and mutants of the reference that every case must tell from it
+_EDGE = pytest.mark.parametrize("regime", L.EDGE_REGIMES)
+SIDES = ("x", "w")
+
+
+def side_of(i: int) -> str:
+    """The operand that carries the subnormal values of a list's i-th low case: the sides rotate over every case list."""
+    return SIDES[i % 2]
+
+
+def _flush(t, fmt):
+    return torch.where(t.abs() < L.FORMATS[fmt].min_normal, torch.zeros_like(t), t)
+
+
+def _output_mutants(st, regime):
+    """What a wrong epilogue would store, from the exact value: (name, tensor)."""
+    f = L.FORMATS[st.fmt]
+    if regime == "low":
+        sub = st.pre.abs() < f.min_normal
+        trunc = torch.where(sub, torch.trunc(st.pre.double() / f.sub_step).float() * f.sub_step, st.ref)
+        return [("subnormal outputs flushed to zero", _flush(st.ref, st.fmt)), ("subnormal outputs truncated toward zero", trunc)]
+    return [("conversion without the clamp", st.pre.to(torch.float16).float()),
+            ("clamp at 65520", st.pre.clamp(-65520.0, 65520.0).to(torch.float16).float())]
+
+
+def _hold_edge(stages, regime):
+    """The regime's conditions, and its two output mutants change the stage that meets them."""
+    stages = stages if isinstance(stages, list) else [stages]
+    for s in stages:
+        print(regime, s.report())
+        print(regime, s.edge_report())
+    L.assert_edge_precondition(stages, regime)
+    hit = [s for s in stages if regime == "high" or L.low_output_condition(s)]
+    for s in hit:
+        for name, mut in _output_mutants(s, regime):
+            assert int((mut != s.ref).sum()) >= 1, f"{s.name}: {name} went unnoticed"
+        if regime == "high":
+            assert bool(torch.isinf(_output_mutants(s, regime)[0][1]).any()) and bool(torch.isinf(_output_mutants(s, regime)[1][1]).any())
+    assert hit
+
+
+@_EDGE
+@pytest.mark.parametrize("i", range(len(CONV_CASES) + 1))
+def test_conv_cases_meet_the_edge_conditions(i, regime):
+    case = (CONV_CASES + [(1, 4, 4, 64, 64, 1, 1, 0, True, False)])[i]
+    (x, wt, bias, res), st = L.conv_case(case, "fp16", regime, side_of(i))
+    _hold_edge(st, regime)
+    assert L.representable(x, "fp16") and L.representable(wt, "fp16") and (res is None or L.representable(res, "fp16"))
+    if regime == "low":       # the operands are the wide regime's integers at other units
+        (xw, ww, _, _), _ = L.conv_case(case, "fp16", "wide")
+        un = L.units_of("low", "fp16", side_of(i))
+        assert torch.equal(x / un.ux, xw / L.UX) and torch.equal(wt / un.uw, ww / L.UW)
+
+
+@_EDGE
+@pytest.mark.parametrize("i", range(len(CAT_CASES)))
+def test_cat_cases_meet_the_edge_conditions(i, regime):
+    _hold_edge(L.cat_case(CAT_CASES[i], "fp16", regime, side_of(i))[1], regime)
+
+
+@pytest.mark.parametrize("case", FP8_CASES, ids=str)
+def test_fp8_cases_meet_the_low_conditions(case):
+    tensors, st = L.fp8_case(case, "low")
+    _hold_edge(st, "low")
+    xq, wq, bias, rq, (sx, sw, sr, sy) = tensors
+    assert all(math.frexp(s)[0] == 0.5 for s in (sx, sw, sr, sy)), "fp8 scales must be powers of two"
+    for t in (xq, wq) + (() if rq is None else (rq,)):       # nonzero values on both sides of 2^-6, all on 2^-9
+        a = t.float().abs()
+        assert bool(((a > 0) & (a < 2.0 ** -6)).any()) and bool((a >= 2.0 ** -6).any()) and bool((a * 512 == (a * 512).round()).all())
+    a = st.pre.abs()
+    assert bool(((a > 0) & (a < 2.0 ** -6)).any()) and bool((a >= 2.0 ** -6).any()) and float(st.ref.abs().max()) > 1.0
+
+
+@_EDGE
+@pytest.mark.parametrize("i", range(len(HEAD_GEMMS)))
+def test_gemm_cases_meet_the_edge_conditions(i, regime):
+    _hold_edge(L.gemm_case(HEAD_GEMMS[i], "fp16", regime, side=side_of(i))[1], regime)
+
+
+@pytest.mark.parametrize("name", L.LOW_CHAINS)
+def test_chain_cases_meet_the_low_conditions(name):
+    """fp16: the chain's inputs are normal, every stored intermediate is subnormal and meets the output condition, and the stage that
+    re-reads it names it as the operand that carries the subnormal values."""
+    tensors, stages = L.CHAIN_CASES[name][2]("low", "fp16")
+    _hold_edge(stages, "low")
+    for t in tensors:
+        if t is not None and t.dtype == torch.float16:
+            a = t.float().abs()
+            assert bool(torch.isfinite(a).all())
+    first = stages[0]
+    assert not first.operands or first.name == "out"          # a first stage's only subnormal operand is a stored identity
+    assert all(L.low_output_condition(s) for s in stages), [s.edge_report() for s in stages]
+    assert set(L.LOW_CHAINS) <= set(L.CHAIN_CASES)
+    assert {L.CHAIN_CASES[n][0] for n in L.LOW_CHAINS} == {L.CHAIN_CASES[n][0] for n in L.CHAIN_CASES}, "a fused kernel has no low case"
+
+
+@pytest.mark.parametrize("regime,side", [("low", "x"), ("low", "w"), ("high", "x")])
+def test_stem_case_meets_the_edge_conditions(regime, side):
+    _hold_edge(L.stem_case(1, regime, "fp16", side)[1], regime)
+
+
+@pytest.mark.parametrize("shape", L.AVGPOOL_SHAPES)
+def test_avgpool_low_reference_is_the_exact_sum_of_subnormal_addends(shape):
+    x, ref = L.avgpool_case(shape, "fp16", 2.0 ** -24)
+    n, h, w, c = shape
+    a = x.float().abs()
+    assert x.dtype == torch.float16 and bool((a[a > 0] < 2.0 ** -14).all()) and float((a > 0).float().mean()) > 0.9
+    s = torch.zeros((n, c), dtype=torch.float32)
+    for r in range(h * w):                                   # the kernel's order: rows added one by one in fp32
+        s += x.view(n, h * w, c)[:, r].float()
+    assert torch.equal(s * torch.tensor(1.0 / (h * w), dtype=torch.float32), ref)
+
+
+def test_both_operand_sides_carry_the_subnormal_values_in_every_case_list():
+    for cases in (CONV_CASES, CAT_CASES, HEAD_GEMMS):
+        assert {side_of(i) for i in range(len(cases))} == set(SIDES)
+
+
+def test_no_edge_regime_for_bf16():
+    for regime in L.EDGE_REGIMES:
+        with pytest.raises(ValueError):
+            L.conv_case(CONV_CASES[0], "bf16", regime)
+
+
+def _conv_ref(x, w, bias, res, case, fmt="fp16"):
+    n, h, wd, cin, cout, k, stride, pad, relu, has_res = case
+    return conv_bias_act_emulated(x, w, bias, stride, pad, relu, residual_bf=res, fmt=fmt)
+
+
+@pytest.mark.parametrize("side", SIDES)
+@pytest.mark.parametrize("case", CONV_CASES, ids=P.case_id)
+def test_mutant_subnormal_operands_flushed_before_the_product(case, side):
+    """Activations (side x) or weights (side w) below 2^-14 read as zero, what an MFMA that flushes its f16 inputs would do."""
+    (x, wt, bias, res), st = L.conv_case(case, "fp16", "low", side)
+    mut = _conv_ref(_flush(x, "fp16"), wt, bias, res, case) if side == "x" else _conv_ref(x, _flush(wt, "fp16"), bias, res, case)
+    assert int((mut != st.ref).sum()) >= 1, f"flushed subnormal {side} operands went unnoticed"
+
+
+@pytest.mark.parametrize("which", ["x", "w"])
+@pytest.mark.parametrize("case", FP8_CASES, ids=str)
+def test_mutant_subnormal_fp8_operands_flushed_before_the_product(case, which):
+    from tests.test_kernels_gpu import fp8_reference
+    n, h, w, cin, cout, k, stride, pad, relu, has_res, _tile = case
+    (xq, wq, bias, rq, scales), st = L.fp8_case(case, "low")
+    xq, wq = xq.float(), wq.float()
+    xq, wq = (_flush(xq, "e4m3"), wq) if which == "x" else (xq, _flush(wq, "e4m3"))
+    mut = L.fp8_round(fp8_reference(xq, wq, bias, rq, scales, stride, pad, bool(relu)))
+    assert int((mut != st.ref).sum()) >= 1, f"flushed subnormal fp8 {which} operands went unnoticed"
 
 
 # ---- the references are the oracle's own functions
@@ -225,3 +379,52 @@ def test_cpu_conversions_round_ties_to_even(fmt):
     kept = got.view(torch.int32)[tie]
     assert int(tie.sum()) > 0 and not bool(((kept >> f.drop) & 1).any()), "a tie went to an odd neighbour"
     assert bool((pre[tie] < 0).any()) and bool((pre[tie] > 0).any())
+    if fmt != "bf16":                    # the bottom of the format: the whole subnormal grid; fp16: the clamp at the top
+        _conversions_round_the_subnormal_grid_to_even(fmt, {"fp16": 2.0 ** -27, "e4m3": 2.0 ** -12}[fmt])
+    if fmt == "fp16":
+        _conversion_to_fp16_saturates_at_the_clamp()
+
+
+def _same_bits(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _conversions_round_the_subnormal_grid_to_even(fmt, fine):
+    """Every multiple of 2^-27 up to 2^-14 (fp16) / of 2^-12 up to 2^-6 (e4m3), both signs, and values below half the smallest
+    subnormal: torch's conversion and ``round_to`` agree with the integer arithmetic on the bit pattern, sign of zero included, and
+    with plain integer rounding of the quotient by the grid step; the ties go to the even multiple."""
+    f = L.FORMATS[fmt]
+    k = torch.arange(0, int(f.min_normal / fine) + 1, dtype=torch.float64)
+    mag = torch.cat([k * fine, torch.tensor([f.sub_step / 2, f.sub_step / 2 * (1 - 2.0 ** -20), f.sub_step / 2 * (1 + 2.0 ** -20), f.sub_step * 2.0 ** -40,
+                                             f.min_normal * (1 - 2.0 ** -20), f.min_normal * (1 + 2.0 ** -20)], dtype=torch.float64)])
+    pre = torch.cat([mag, -mag]).to(torch.float32)
+    assert bool((pre.double() == torch.cat([mag, -mag])).all())
+    want = L.rne_by_integer_arithmetic(pre, fmt)
+    got = pre.to(f.dtype).to(torch.float32)
+    assert _same_bits(got, want), L.describe_mismatch(got, L.Exact("grid", pre, want, 0.0, fine, fmt))
+    assert _same_bits(L.round_to(pre, fmt), want)
+    q = pre[: k.numel()].double() / f.sub_step                       # the plain statement of the same rounding, on the enumerated part
+    fl = q.floor()
+    rne = torch.where(q - fl > 0.5, fl + 1, torch.where(q - fl < 0.5, fl, fl + fl.remainder(2.0)))
+    assert torch.equal(want[: k.numel()].double(), rne * f.sub_step)
+    dn, up = L.tie_shares(pre, fmt, "subnormal")
+    assert dn > 0.05 and up > 0.05 and L.tie_shares(pre[pre.abs() < f.min_normal], fmt) == (0.0, 0.0)
+    tie = (q - fl == 0.5)
+    assert int(tie.sum()) == (1024 if fmt == "fp16" else 8) and bool((want[: k.numel()][tie].double() / f.sub_step).remainder(2.0).eq(0).all())
+
+
+def _conversion_to_fp16_saturates_at_the_clamp():
+    """``round_to`` (clamp, then convert) and the integer arithmetic give +-65504 from 65504 upward, infinity included; the values
+    the high regime plants are among them; the unclamped conversion makes an infinity from 65520 on."""
+    mag = torch.tensor([65472.0, 65488.0, 65503.99, 65504.0, 65504.01, 65512.0, 65519.996, 65520.0, 65528.0, 65536.0, 1e5, 3e38, float("inf")])
+    pre = torch.cat([mag, -mag])
+    want = L.rne_by_integer_arithmetic(pre, "fp16")
+    assert _same_bits(L.round_to(pre, "fp16"), want)
+    assert torch.equal(want[:3], torch.tensor([65472.0, 65472.0, 65504.0])) and bool((want[3:13] == 65504.0).all()) and bool((want[16:] == -65504.0).all())
+    raw = pre.to(torch.float16).float()
+    assert bool(torch.isfinite(raw[:7]).all()) and bool(torch.isinf(raw[7:13]).all())
+    for v in L.HIGH_PLANTS:
+        assert v in mag.tolist()
+    w8 = L.rne_by_integer_arithmetic(torch.tensor([447.0, 448.0, 463.9, 464.0, 480.0, 1e4, -464.0]), "e4m3")
+    assert torch.equal(w8, torch.tensor([448.0, 448.0, 448.0, 448.0, 448.0, 448.0, -448.0]))
+    assert torch.equal(L.round_to(torch.tensor([447.0, 464.0, -464.0, 1e4]), "e4m3"), torch.tensor([448.0, 448.0, -448.0, 448.0]))

@@ -5,6 +5,11 @@ the preconditions hold for every case here and that a dropped, swapped or mispla
 
 The launches are the ones tests/test_kernels_gpu.py and tests/test_head_kernels_gpu.py drive (their runners take the lattice tensors
 instead of their seeded ones, and still assert what they always assert); fused chains are compared end to end from the inputs.
+
+The ``low`` and ``high`` regimes move the same integer cases to the ends of fp16 and e4m3 (subnormal operands and outputs; outputs
+across +-65504): what the f16 / f8 MFMA reads of a subnormal operand, what ``v_cvt_pk_f16_f32`` / ``v_cvt_pk_fp8_f32`` store on the
+subnormal grid, and the clamp in front of the fp16 conversion, still at zero tolerance.  A failure counts flushes (0 where the reference
+is not), infinities and results one grid step off apart (``exact_lattice.describe_mismatch``).
 """
 import pytest
 import torch
@@ -40,11 +45,20 @@ def _nhwc_dev(t_nchw, fmt="bf16"):
     return t_nchw.permute(0, 2, 3, 1).contiguous().to(L.FORMATS[fmt].dtype).to(DEV)
 
 
-def _conv_launches(case, fmt, regime, tiles):
+def _side(i):
+    """The operand that carries the subnormal values of a list's i-th low case (tests/test_exact_lattice_cpu.py: side_of)."""
+    return "xw"[i % 2]
+
+
+def _conv_launches(case, fmt, regime, tiles, side="x"):
     from implementation_phd_lab_vision_amd import ops
     n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    (x, wt, bias, res), st = L.conv_case(case, fmt, regime)
-    L.assert_exact_precondition(st, regime, tie_floor=st.pre.numel() >= 1000)
+    (x, wt, bias, res), st = L.conv_case(case, fmt, regime, side)
+    if regime in L.EDGE_REGIMES:
+        L.assert_edge_precondition(st, regime)
+        print(st.edge_report())
+    else:
+        L.assert_exact_precondition(st, regime, tie_floor=st.pre.numel() >= 1000)
     xd, wd, bd = _nhwc_dev(x, fmt), _nhwc_dev(wt, fmt), bias.to(DEV)
     rd = _nhwc_dev(res, fmt) if has_res else None
     ref = st.ref.permute(0, 2, 3, 1).contiguous().to(xd.dtype).to(DEV)
@@ -73,6 +87,16 @@ def test_foundation_smallest_fp8_case(lib_built, regime):
     _fp8(FP8_CASES[0], regime)
 
 
+@pytest.mark.parametrize("regime", L.EDGE_REGIMES)
+def test_foundation_one_mfma_tile_at_the_ends_of_fp16(lib_built, regime):
+    from implementation_phd_lab_vision_amd import ops
+    _conv_launches((1, 4, 4, 64, 64, 1, 1, 0, True, False), "fp16", regime, [ops.TILE_AUTO])
+
+
+def test_foundation_smallest_fp8_case_at_the_bottom_of_e4m3(lib_built):
+    _fp8(FP8_CASES[0], "low")
+
+
 # ---- plain convs: every row x every tile id the one-ulp test runs for it x both types x both regimes, one reference per test
 @pytest.mark.parametrize("regime", L.REGIMES)
 @pytest.mark.parametrize("fmt", FMTS)
@@ -82,7 +106,26 @@ def test_conv2d_every_tile_is_exact(lib_built, case, fmt, regime):
     _conv_launches(case, fmt, regime, _conv_tiles(case))
 
 
+@pytest.mark.parametrize("regime", L.EDGE_REGIMES)
+@pytest.mark.parametrize("i", range(len(CONV_CASES)), ids=lambda i: "%d_%s" % (i, _conv_id(CONV_CASES[i])))
+def test_conv2d_every_tile_is_exact_at_the_ends_of_fp16(lib_built, i, regime):
+    from tests.test_kernels_gpu import _conv_tiles
+    _conv_launches(CONV_CASES[i], "fp16", regime, _conv_tiles(CONV_CASES[i]), _side(i))
+
+
 # ---- two-source 1x1
+@pytest.mark.parametrize("regime", L.EDGE_REGIMES)
+@pytest.mark.parametrize("i", range(len(CAT_CASES)))
+def test_conv1x1_two_k_sources_is_exact_at_the_ends_of_fp16(lib_built, i, regime):
+    from tests.test_kernels_gpu import _run_conv1x1_cat
+    case = CAT_CASES[i]
+    tensors, st = L.cat_case(case, "fp16", regime, _side(i))
+    L.assert_edge_precondition(st, regime)
+    print(st.edge_report())
+    y = _run_conv1x1_cat(case, torch.float16, tensors)
+    _assert_nhwc_exact(y, st, f"conv1x1_cat {case} fp16 {regime}")
+
+
 @pytest.mark.parametrize("regime", L.REGIMES)
 @pytest.mark.parametrize("fmt", FMTS)
 @pytest.mark.parametrize("case", CAT_CASES, ids=lambda c: "n%d_%dx%d_c%d_src%d_c%d_s%d_o%d_r%d_t%d" % ((c[0], c[1]) + tuple(int(v) for v in c[1:])))
@@ -98,7 +141,11 @@ def test_conv1x1_two_k_sources_is_exact(lib_built, case, fmt, regime):
 def _fp8(case, regime):
     from tests.test_kernels_gpu import _run_conv2d_fp8
     tensors, st = L.fp8_case(case, regime)
-    L.assert_exact_precondition(st, regime)
+    if regime == "low":
+        L.assert_edge_precondition(st, regime)
+        print(st.edge_report())
+    else:
+        L.assert_exact_precondition(st, regime)
     if regime == "wide":
         sat = float((st.pre.abs() >= 448.0).float().mean())
         print(f"saturating outputs {100 * sat:.2f} %")
@@ -111,6 +158,11 @@ def _fp8(case, regime):
 @pytest.mark.parametrize("case", FP8_CASES, ids=lambda c: "n%d_%dx%d_c%d_o%d_k%d_s%d_p%d_r%d_res%d_t%d" % tuple(int(v) for v in c))
 def test_conv2d_fp8_is_exact(lib_built, case, regime):
     _fp8(case, regime)
+
+
+@pytest.mark.parametrize("case", FP8_CASES, ids=lambda c: "n%d_%dx%d_c%d_o%d_k%d_s%d_p%d_r%d_res%d_t%d" % tuple(int(v) for v in c))
+def test_conv2d_fp8_is_exact_at_the_bottom_of_e4m3(lib_built, case):
+    _fp8(case, "low")
 
 
 # ---- pair modes
@@ -218,3 +270,68 @@ def test_head_gemm_every_tile_is_exact(lib_built, shape, et, regime):
         if not _same_bits(y, st.ref):
             L.assert_bits_equal(y.float(), st, f"gemm {_gemm_id(shape)} {fmt} {regime} tile={tile}")
             raise AssertionError(f"gemm tile={tile}: bit patterns differ from the exact reference")
+
+
+@pytest.mark.parametrize("regime", L.EDGE_REGIMES)
+@pytest.mark.parametrize("i", range(len(HEAD_GEMMS)), ids=lambda i: "%d_%s" % (i, _gemm_id(HEAD_GEMMS[i])))
+def test_head_gemm_every_tile_is_exact_at_the_ends_of_fp16(lib_built, i, regime):
+    """fwd, dx and dw rows: under the trainers' loss scaling the backward products are the ones that live in fp16's subnormal range."""
+    from tests.test_head_kernels_gpu import _run_gemm
+    from tests.test_kernels_gpu import _tiles_for
+    shape = HEAD_GEMMS[i]
+    tensors, st = L.gemm_case(shape, "fp16", regime, device=DEV, side=_side(i))
+    L.assert_edge_precondition(st, regime)
+    print(st.report())
+    print(st.edge_report())
+    tiles = _tiles_for(shape[2], k=1, pad=0)
+    for tile, y in zip(tiles, _run_gemm(1, shape, tiles, tensors)):
+        if not _same_bits(y, st.ref):
+            L.assert_bits_equal(y.float(), st, f"gemm {_gemm_id(shape)} fp16 {regime} tile={tile}")
+            raise AssertionError(f"gemm tile={tile}: bit patterns differ from the exact reference")
+
+
+# ---- fused chains, stem and average pool in fp16 (the op-level hooks run their IEEE-half kernels for fp16 tensors: ops._op_et)
+@pytest.mark.parametrize("name", L.LOW_CHAINS)
+def test_fused_chain_is_exact_at_the_bottom_of_fp16(lib_built, name, monkeypatch):
+    """The first stage runs on normal operands and stores subnormal intermediates; the next stage re-reads what the kernel stored
+    itself, from LDS or HBM, as an MFMA operand.  The reference rounds every stored intermediate onto the subnormal grid."""
+    import tests.test_kernels_gpu as K
+    runner, args, build = L.CHAIN_CASES[name]
+    if runner == "_run_bneck_tail_layer3" and args[1]:
+        monkeypatch.setenv("R50_TAIL3_BP", str(args[1]))
+    else:
+        monkeypatch.delenv("R50_TAIL3_BP", raising=False)
+    tensors, stages = build("low", "fp16")
+    L.assert_edge_precondition(stages, "low")
+    for s in stages:
+        print(s.edge_report())
+    got = getattr(K, runner)(*args, tensors=tensors)
+    got = got if isinstance(got, tuple) else (got,)
+    by_name = {s.name: s for s in stages}
+    for y, key in zip(got, ("out", "y1n")):
+        if y is not None and key in by_name:
+            assert y.dtype == torch.float16
+            _assert_nhwc_exact(y, by_name[key], f"{name} fp16 low {key}")
+    assert got[0] is not None
+
+
+@pytest.mark.parametrize("regime,side", [("low", "x"), ("low", "w"), ("high", "x")])
+def test_stem_is_exact_at_the_ends_of_fp16(lib_built, regime, side):
+    from implementation_phd_lab_vision_amd import ops
+    (x, wf, bias), st = L.stem_case(1, regime, "fp16", side)
+    L.assert_edge_precondition(st, regime)
+    print(st.edge_report())
+    y = ops.stem_bf16(x.to(DEV), wf, bias.to(DEV), dtype=torch.float16)
+    torch.cuda.synchronize()
+    _assert_nhwc_exact(y, st, f"stem n=1 fp16 {regime} {side}")
+
+
+@pytest.mark.parametrize("shape", L.AVGPOOL_SHAPES)
+def test_avgpool_is_exact_on_fp16_subnormal_addends(lib_built, shape):
+    from implementation_phd_lab_vision_amd import ops
+    x, ref = L.avgpool_case(shape, "fp16", 2.0 ** -24)
+    a = x.float().abs()
+    assert bool((a[a > 0] < 2.0 ** -14).all()) and bool((ref != 0).any())
+    y = ops.avgpool_bf16(x.to(DEV))
+    assert _same_bits(y, ref), f"{int((y.cpu() != ref).sum())} of {ref.numel()} means differ from float32(sum) * float32(1 / HW); zeros where the " \
+                               f"reference has none: {int(((y.cpu() == 0) & (ref != 0)).sum())}"

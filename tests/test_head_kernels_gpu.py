@@ -174,10 +174,15 @@ def test_gn_constant_slabs(lib, et, shape):
 
 # ---------------------------------------------------------------- b. casts and row ops ----------------------------------------------
 def _ties(et, n, g):
-    """n fp32 values exactly halfway between two adjacent finite 16-bit values (both parities of the lower neighbour)."""
+    """n fp32 values exactly halfway between two adjacent finite 16-bit values (both parities of the lower neighbour).  fp16: every
+    fourth one lies on the subnormal grid, between the bit patterns 0x0000 .. 0x03ff and their successors (0x0000: half the smallest
+    subnormal, which goes to +-0; 0x03ff: the tie with the smallest normal)."""
     dt = R.DTYPE[et]
     lim = 0x7bfe if et else 0x7f7e                                              # below the largest finite magnitude
     bits = torch.randint(0x0400 if et else 0x0080, lim, (n,), generator=g, dtype=torch.int32)
+    if et:
+        sub = torch.randint(0x0000, 0x0400, (n,), generator=g, dtype=torch.int32)
+        bits = torch.where(torch.arange(n) % 4 == 3, sub, bits)
     lo = bits.to(torch.int16).view(dt).float()
     hi = (bits + 1).to(torch.int16).view(dt).float()
     sign = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
@@ -189,13 +194,23 @@ def _cast_input(et, rows, c, g):
     flat = x.view(-1)
     k = flat.numel() // 3
     flat[:k] = _ties(et, k, g)
+    # the bottom of fp16, both signs: around the smallest normal 2^-14, around half the smallest subnormal 2^-25 (below it and at it:
+    # +-0, the sign kept; above it: +-2^-24), and far below; for bf16 these are ordinary normal values
+    e = 2.0 ** -12
+    edge = torch.tensor([2.0 ** -14 * (1 - e), 2.0 ** -14, 2.0 ** -14 * (1 + e), 2.0 ** -14 * (1 - 2.0 ** -11), 2.0 ** -24, 1.5 * 2.0 ** -24,
+                         2.0 ** -25 * (1 - e), 2.0 ** -25, 2.0 ** -25 * (1 + e), 2.0 ** -26, 2.0 ** -30, 2.0 ** -40])
+    edge = torch.cat([edge, -edge])
+    m = min((flat.numel() - k) // 2, 20 * edge.numel())
+    flat[k: k + m] = edge.repeat(m // edge.numel() + 1)[:m]
     return x
 
 
 @pytest.mark.parametrize("et", [1, 0], ids=["fp16", "bf16"])
 @pytest.mark.parametrize("shape", [(40, 2048, 2048), (40, 51, 64), (33, 33, 34), (1, 1, 2)], ids=lambda s: "r%d_c%d_cp%d" % s)
 def test_cast_rows_rounds_to_nearest_even(lib, et, shape):
-    """fp32 (rows, c) -> 16-bit (rows, cpad): round to nearest even, a third of the inputs exact ties; zero columns c..cpad-1."""
+    """fp32 (rows, c) -> 16-bit (rows, cpad): round to nearest even, a third of the inputs exact ties (fp16: a quarter of them on the
+    subnormal grid), values around fp16's smallest normal and around half its smallest subnormal (+-0 with the sign kept, or +-2^-24);
+    zero columns c..cpad-1."""
     rows, c, cpad = shape
     dt = R.DTYPE[et]
     g = torch.Generator().manual_seed(rows * 7 + c + et)
@@ -273,12 +288,18 @@ def test_add_rows(lib, et, dp):
     y = torch.randn(rows, ny, generator=g)
     dy = (torch.randn(rows, dp, generator=g) * 0.1).to(dt)
     dy[:, ny:] = float("nan")                                                   # must not leak into y
+    # a quarter of the sums cancel into fp16's subnormal range: two normal addends, y = -dy + k 2^-24 (exact in fp32: |dy| < 1), so the
+    # exact sum k 2^-24, k in -1023 .. 1023, must come out as it is (k = 0: +0)
+    kk = torch.randint(-1023, 1024, (rows, ny), generator=g)
+    cancel = (torch.rand(rows, ny, generator=g) < 0.25) & (dy[:, :ny].float().abs() < 1) & (dy[:, :ny].float().abs() >= 2.0 ** -14)
+    y = torch.where(cancel, (-dy[:, :ny].double() + kk.double() * 2.0 ** -24).float(), y)
+    assert int(cancel.sum()) > 100 and bool(((y.double() + dy[:, :ny].double())[cancel] == kk.double()[cancel] * 2.0 ** -24).all())
     buf = torch.full((rows * ny + 64,), 7.0, device=DEV)
     buf[: rows * ny] = y.view(-1).to(DEV)
     dyd = dy.to(DEV)
     _ok(lib, lib.r50_op_add_rows(buf.data_ptr(), ny, dyd.data_ptr(), dp, rows, et, _s()), "add_rows")
     want = (y.double() + dy[:, :ny].double()).float()
-    assert torch.equal(buf[: rows * ny].cpu().view(rows, ny), want)
+    assert torch.equal(buf[: rows * ny].cpu().view(rows, ny).view(torch.int32), want.view(torch.int32))
     assert bool((buf[rows * ny:] == 7.0).all())
 
 

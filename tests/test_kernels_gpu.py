@@ -35,6 +35,11 @@ def _check_bf16(dev_nhwc: torch.Tensor, ref_nchw: torch.Tensor, what: str, mant:
     assert r < 1e-3, f"{what}: rel-L2 {r}"
 
 
+def _fmt_of(t: torch.Tensor):
+    """(oracle fmt, mantissa bits of _check_bf16) of a runner's 16-bit tensors: the fused kernels run in bf16 or in fp16."""
+    return ("fp16", 10) if t.dtype == torch.float16 else ("bf16", 7)
+
+
 def _rand_bf16(shape, gen, scale=1.0):
     return (torch.randn(shape, generator=gen) * scale).to(torch.bfloat16)
 
@@ -407,30 +412,31 @@ def _run_bneck_tail(shape, c1, ds, tensors=None):
     from oracle.resnet50_oracle import conv_bias_act_emulated
     n, h, w = shape
     y2, w3, b3, w1, b1, *rest = tensors or _tail_tensors(shape, c1, ds)
+    fmt, mant = _fmt_of(y2)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     w3d, w1d = w3.view(256, 64).contiguous().to(d), w1.view(c1, 256).contiguous().to(d)
     b3d, b1d = b3.to(d), b1.to(d)
     if ds:      # first block of the stage: identity = downsample(block input), computed inside the kernel
         xin, wd, bd = rest
-        idn = conv_bias_act_emulated(xin.float(), wd.float(), bd, 1, 0, False)
+        idn = conv_bias_act_emulated(xin.float(), wd.float(), bd, 1, 0, False, fmt=fmt)
         xind = xin.permute(0, 2, 3, 1).contiguous().to(d)
         wdd, bdd = wd.view(256, 64).contiguous().to(d), bd.to(d)
         idd = ops.conv2d_bf16(xind, wdd.view(256, 1, 1, 64), bdd, relu=False, tile=ops.TILE_64x128)
-        _check_bf16(idd, idn, "downsample identity")
+        _check_bf16(idd, idn, "downsample identity", mant)
         idn = idd.float().cpu().permute(0, 3, 1, 2)        # chain the oracle from the device's identity (see below)
         out, y1n = ops.bneck_tail_bf16(y2d, w3d, b3d, xind, w1d, b1d, wd=wdd, bd=bdd)
     else:
         idn, = rest
         idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
         out, y1n = ops.bneck_tail_bf16(y2d, w3d, b3d, idd, w1d, b1d)
-    out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float())
+    out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float(), fmt=fmt)
     torch.cuda.synchronize()
-    _check_bf16(out, out_ref, "bneck_tail out")
+    _check_bf16(out, out_ref, "bneck_tail out", mant)
     # the second GEMM reads the DEVICE's bf16 block output, so chain the oracle from it (one-ulp flips of `out`
     # are legal and would otherwise be amplified into a false mismatch of y1n)
-    y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True)
-    _check_bf16(y1n, y1_ref, "bneck_tail y1n")
+    y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True, fmt=fmt)
+    _check_bf16(y1n, y1_ref, "bneck_tail y1n", mant)
     out_u = ops.conv2d_bf16(y2d, w3d.view(256, 1, 1, 64), b3d, relu=True, residual=idd, tile=ops.TILE_64x128)
     y1_u = ops.conv2d_bf16(out_u, w1d.view(c1, 1, 1, 256), b1d, relu=True, tile=ops.TILE_64x128)
     assert torch.equal(out, out_u), "fused block output differs from the igemm launch it replaces"
@@ -465,6 +471,7 @@ def _run_bneck_tail_layer2(shape, tensors=None):
     from oracle.resnet50_oracle import conv_bias_act_emulated
     n, h, w = shape
     y2, w3, b3, idn, w1, b1 = tensors or _tail2_tensors(shape)
+    fmt, mant = _fmt_of(y2)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
@@ -472,10 +479,10 @@ def _run_bneck_tail_layer2(shape, tensors=None):
     b3d, b1d = b3.to(d), b1.to(d)
     out, y1n = ops.bneck_tail_bf16(y2d, w3d, b3d, idd, w1d, b1d)
     torch.cuda.synchronize()
-    out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float())
-    _check_bf16(out, out_ref, "bneck_tail2 out")
-    y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True)
-    _check_bf16(y1n, y1_ref, "bneck_tail2 y1n")
+    out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float(), fmt=fmt)
+    _check_bf16(out, out_ref, "bneck_tail2 out", mant)
+    y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True, fmt=fmt)
+    _check_bf16(y1n, y1_ref, "bneck_tail2 y1n", mant)
     out_u = ops.conv2d_bf16(y2d, w3d.view(512, 1, 1, 128), b3d, relu=True, residual=idd, tile=ops.TILE_64x128)
     assert torch.equal(out, out_u), "fused block output differs from the igemm launch it replaces"
     return out, y1n
@@ -513,6 +520,7 @@ def _run_bneck_tail_layer3(shape, bp, tensors=None):
     from oracle.resnet50_oracle import conv_bias_act_emulated
     n, h, w = shape
     y2, w3, b3, idn, w1, b1 = tensors or _tail3_inputs(n, h, w, 3000 + n * h * w + bp)
+    fmt, mant = _fmt_of(y2)
     d = _dev()
     y2d = y2.permute(0, 2, 3, 1).contiguous().to(d)
     idd = idn.permute(0, 2, 3, 1).contiguous().to(d)
@@ -520,8 +528,8 @@ def _run_bneck_tail_layer3(shape, bp, tensors=None):
     b3d, b1d = b3.to(d), b1.to(d)
     m = n * h * w
     guard = 4096                                   # poisoned rows behind both outputs: nothing may be stored past M
-    out_buf = torch.full((m + guard, 1024), -7.0, dtype=torch.bfloat16, device=d)
-    y1_buf = torch.full((m + guard, 256), -7.0, dtype=torch.bfloat16, device=d)
+    out_buf = torch.full((m + guard, 1024), -7.0, dtype=y2.dtype, device=d)
+    y1_buf = torch.full((m + guard, 256), -7.0, dtype=y2.dtype, device=d)
     out, y1n = ops.bneck_tail_bf16(y2d, w3d, b3d, idd, w1d, b1d, out=out_buf[:m].view(n, h, w, 1024), y1n=y1_buf[:m].view(n, h, w, 256))
     torch.cuda.synchronize()
     assert bool((out_buf[m:] == -7.0).all()) and bool((y1_buf[m:] == -7.0).all()), "stored past M"
@@ -530,10 +538,10 @@ def _run_bneck_tail_layer3(shape, bp, tensors=None):
     assert torch.equal(out, out_u), "chained block output differs from the igemm launch it replaces"
     assert torch.equal(y1n, y1_u), "chained next-conv1 output differs from the igemm launch it replaces"
     if m <= 1000:
-        out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float())
-        _check_bf16(out, out_ref, "bneck_tail3 out")
-        y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True)
-        _check_bf16(y1n, y1_ref, "bneck_tail3 y1n")
+        out_ref = conv_bias_act_emulated(y2.float(), w3.float(), b3, 1, 0, True, residual_bf=idn.float(), fmt=fmt)
+        _check_bf16(out, out_ref, "bneck_tail3 out", mant)
+        y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True, fmt=fmt)
+        _check_bf16(y1n, y1_ref, "bneck_tail3 y1n", mant)
     return out, y1n
 
 
@@ -580,6 +588,7 @@ def _run_bneck_cat_chain(n, tensors=None):
     from implementation_phd_lab_vision_amd import ops
     from oracle.resnet50_oracle import conv_bias_act_emulated
     t2, x, w3, wd, bcat, w1, b1 = tensors or _cat_chain_tensors(n)
+    fmt, mant = _fmt_of(t2)
     d = _dev()
     t2d = t2.permute(0, 2, 3, 1).contiguous().to(d)
     xd = x.permute(0, 2, 3, 1).contiguous().to(d)
@@ -594,10 +603,10 @@ def _run_bneck_cat_chain(n, tensors=None):
     assert torch.equal(y1n, y1_u), "chained next-conv1 output differs from the igemm launch"
     if n <= 3:
         xs = x[:, :, ::2, ::2]
-        ref = conv_bias_act_emulated(torch.cat([t2, xs], dim=1).float(), torch.cat([w3, wd], dim=1).float(), bcat, 1, 0, True)
-        _check_bf16(out, ref, "bneck_cat_chain out")
-        y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True)
-        _check_bf16(y1n, y1_ref, "bneck_cat_chain y1n")
+        ref = conv_bias_act_emulated(torch.cat([t2, xs], dim=1).float(), torch.cat([w3, wd], dim=1).float(), bcat, 1, 0, True, fmt=fmt)
+        _check_bf16(out, ref, "bneck_cat_chain out", mant)
+        y1_ref = conv_bias_act_emulated(out.float().cpu().permute(0, 3, 1, 2), w1.float(), b1, 1, 0, True, fmt=fmt)
+        _check_bf16(y1n, y1_ref, "bneck_cat_chain y1n", mant)
     return out, y1n
 
 
@@ -705,6 +714,33 @@ def test_maxpool_bit_exact(lib_built, shape):
     assert torch.equal(y.float().cpu(), ref)
 
 
+@pytest.mark.parametrize("et", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_maxpool_bit_exact_on_subnormals_and_signed_zeros(lib_built, et):
+    """The same pool on an input of subnormals of both signs (bf16: bit patterns 0x0001 .. 0x007f, fp32 subnormals once unpacked; fp16:
+    0x0001 .. 0x03ff), +0, -0 and the smallest normals, in equal shares: the maximum is one of the inputs, bit for bit -- a max or a
+    conversion that flushed subnormals would return 0 or the wrong sign.  Only the sign of a zero maximum is left open (max(+0, -0))."""
+    from implementation_phd_lab_vision_amd import ops
+    import torch.nn.functional as F
+    shape = (2, 7, 9, 16)
+    first_normal = 0x0080 if et == torch.bfloat16 else 0x0400
+    g = torch.Generator().manual_seed(12)
+    bits = torch.randint(0x0001, first_normal, shape, generator=g, dtype=torch.int32)             # subnormal magnitudes
+    kind = torch.randint(0, 4, shape, generator=g)
+    bits = torch.where(kind == 2, torch.zeros_like(bits), bits)                                    # zeros
+    bits = torch.where(kind == 3, torch.randint(first_normal, 4 * first_normal, shape, generator=g, dtype=torch.int32), bits)
+    bits = bits | (torch.randint(0, 2, shape, generator=g, dtype=torch.int32) << 15)
+    x = bits.to(torch.int16).view(et)
+    tiny = torch.tensor(first_normal, dtype=torch.int16).view(et).double()
+    assert bool((x == 0).any()) and bool(((x.double().abs() > 0) & (x.double().abs() < tiny)).any()) and bool((x.double().abs() >= tiny).any())
+    ref = F.max_pool2d(x.double().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).contiguous()
+    y = ops.maxpool_bf16(x.to(_dev())).cpu()
+    assert y.dtype == et
+    assert torch.equal(y.double(), ref), f"{int((y.double() != ref).sum())} of {ref.numel()} maxima differ; zeros where the reference has none: " \
+                                         f"{int(((y.double() == 0) & (ref != 0)).sum())}"
+    nz = ref != 0
+    assert torch.equal(y.view(torch.int16)[nz], ref.to(et).view(torch.int16)[nz]) and int(nz.sum()) > ref.numel() // 2
+
+
 @pytest.mark.parametrize("shape", [(4, 7, 7, 2048), (1, 3, 3, 8)])
 def test_avgpool_matches_oracle(lib_built, shape):
     from implementation_phd_lab_vision_amd import ops
@@ -762,7 +798,10 @@ def _run_conv1x1_cat(case, et, tensors=None):
     ref = ref + bias.double().view(1, -1, 1, 1)
     if relu:
         ref = F.relu(ref)
-    ref = ref.float().to(et).float()
+    ref = ref.float()
+    if et == torch.float16:
+        ref = ref.clamp(-65504.0, 65504.0)                 # the fp16 conversion saturates (test_conv2d_fp16_saturates_instead_of_overflowing)
+    ref = ref.to(et).float()
     got = y.float().cpu().permute(0, 3, 1, 2)
     diff = (got - ref).abs()
     ulp = ref.abs() * (2.0 ** -7 if et == torch.bfloat16 else 2.0 ** -10) + 2.0 ** -16 * max(1.0, float(ref.abs().max()))
