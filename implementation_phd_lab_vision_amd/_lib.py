@@ -1,5 +1,5 @@
 """ctypes binding of libr50hip.so (C ABI: include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h,
-include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h and include/r50_resample.h).
+include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h, include/r50_resample.h and include/r50_bootstrap.h).
 
 This is the stub a maintainer of the reference would add to call the MI355X path from
 src/preprocess_resnet_features.py.  There is NO fallback: if the shared
@@ -30,15 +30,15 @@ class TensorDesc(C.Structure):
 
 def _source_digest() -> str:
     """sha256 over everything the shared library is built from: csrc/*, include/r50.h, include/r50_hal.h, include/r50_smooth.h,
-    include/r50_multiview.h, include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h, include/r50_resample.h and the compiler
-    flags."""
+    include/r50_multiview.h, include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h, include/r50_resample.h, include/r50_bootstrap.h and the
+    compiler flags."""
     import hashlib
     hsh = hashlib.sha256()
     files = sorted(p for p in CSRC.iterdir() if p.suffix in (".hip", ".h", ".hpp", ".cpp")) + \
         [PKG_DIR.parent / "include" / "r50.h", PKG_DIR.parent / "include" / "r50_hal.h", PKG_DIR.parent / "include" / "r50_smooth.h",
          PKG_DIR.parent / "include" / "r50_multiview.h", PKG_DIR.parent / "include" / "r50_kinematics.h",
          PKG_DIR.parent / "include" / "r50_refine.h", PKG_DIR.parent / "include" / "r50_track.h",
-         PKG_DIR.parent / "include" / "r50_resample.h"]
+         PKG_DIR.parent / "include" / "r50_resample.h", PKG_DIR.parent / "include" / "r50_bootstrap.h"]
     for f in files:
         hsh.update(f.name.encode() + b"\0")
         hsh.update(f.read_bytes())
@@ -243,12 +243,18 @@ _SIGNATURES_RESAMPLE = {
                                             C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/r50_bootstrap.h (the stratified cluster bootstrap of per-unit sums, INTEGRATION.md section AC): likewise
+_SIGNATURES_BOOTSTRAP = {
+    "r50_op_bootstrap_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
 def load_library() -> C.CDLL:
     """dlopen libr50hip.so and declare every prototype of include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h,
-    include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h and include/r50_resample.h.  Raises if it is absent."""
+    include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h, include/r50_resample.h and include/r50_bootstrap.h.  Raises if it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -261,7 +267,8 @@ def load_library() -> C.CDLL:
                        "There is no CPU/PyTorch fallback for this path.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_HAL, **_SIGNATURES_SMOOTH, **_SIGNATURES_MULTIVIEW,
-                              **_SIGNATURES_KINEMATICS, **_SIGNATURES_REFINE, **_SIGNATURES_TRACK, **_SIGNATURES_RESAMPLE}.items():
+                              **_SIGNATURES_KINEMATICS, **_SIGNATURES_REFINE, **_SIGNATURES_TRACK, **_SIGNATURES_RESAMPLE,
+                              **_SIGNATURES_BOOTSTRAP}.items():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,5 @@
 // Host side of libr50hip.so: C ABI declared in include/r50.h, include/r50_hal.h, include/r50_smooth.h, include/r50_multiview.h,
-// include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h and include/r50_resample.h.
+// include/r50_kinematics.h, include/r50_refine.h, include/r50_track.h, include/r50_resample.h and include/r50_bootstrap.h.
 // Builds the static ResNet-50 [:-1] schedule (upstream torchvision models/resnet.py, the module
 // list the reference cuts at src/preprocess_resnet_features.py:207-209), folds BN, packs weights
 // and launches the gfx950 kernels of kernels.h.
@@ -10,6 +10,7 @@
 #include "refine_kernels.h"
 #include "track_kernels.h"
 #include "resample_kernels.h"
+#include "bootstrap_kernels.h"
 #include "launch_plan.h"
 #include "../../include/r50.h"
 #include "../../include/r50_hal.h"
@@ -19,6 +20,7 @@
 #include "../../include/r50_refine.h"
 #include "../../include/r50_track.h"
 #include "../../include/r50_resample.h"
+#include "../../include/r50_bootstrap.h"
 
 #include <atomic>
 #include <cmath>
@@ -2735,6 +2737,36 @@ int r50_op_resample_sequences(const float* x, const int* idx, const int* seq_sta
     hipLaunchKernelGGL(resample_sequences_kernel, dim3((unsigned)((total + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK)), dim3(RESAMPLE_BLOCK), 0,
                        (hipStream_t)stream, x, idx, seq_start, 3 * J, out_time, out_seq, out_left, (int)G, kind, max_gap, y, flags);
     return ew_done("r50_op_resample_sequences");
+}
+
+// ---- stratified cluster bootstrap of per-unit sums (include/r50_bootstrap.h, bootstrap_kernels.h, INTEGRATION.md section AC) ----
+int r50_op_bootstrap_sums(const double* v, const int* stratum_start, int64_t U, int G, int M, int64_t r0, int64_t R, uint64_t seed,
+                          int window, double* out, int* counts, void* stream) {
+    if (!v || !stratum_start || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: null pointer");
+    if (U < 1 || G < 1 || M < 1 || R < 1 || G > U || U > R50_BOOTSTRAP_MAX_UNITS || M > R50_BOOTSTRAP_MAX_COLUMNS)
+        return fail(nullptr, R50_ERR_INVALID,
+                    "r50_op_bootstrap_sums: invalid arguments (need 1 <= G <= U <= 2^24, 1 <= M <= 4096 and R >= 1)");
+    if (r0 < 0 || r0 > INT64_MAX - R) return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: need r0 >= 0 and r0 + R within int64");
+    const long long limit = 1ll << 40;
+    if (R >= limit || R > (limit - 1) / ((long long)G * M) || R > (limit - 1) / U)   // by division: the products may overflow
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: R * G * M and R * U must stay below 2^40");
+    if (window < 1 || window > R50_BOOTSTRAP_MAX_WINDOW)
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: window must lie in [1, 32768]");
+    if (((uintptr_t)v & 7u) || ((uintptr_t)out & 7u) || ((uintptr_t)counts & 3u))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: v and out must be 8-byte aligned (counts 4-byte)");
+    const KinRange in[2] = {{v, U * M * (long long)sizeof(double)}, {stratum_start, ((long long)G + 1) * (long long)sizeof(int)}};
+    const KinRange outs[2] = {{out, R * G * M * (long long)sizeof(double)}, {counts, R * U * (long long)sizeof(int)}};
+    if (kin_any_overlap(in, 2, outs, counts ? 2 : 1))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: out or counts overlaps an input or the other output");
+    const long long grid_z = (R + BOOT_GRID_Y - 1) / BOOT_GRID_Y;
+    if (grid_z > 65535) return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: R exceeds the launch grid (65535 * 65535 replicates)");
+    const size_t lds = sizeof(int) * (size_t)std::min<long long>(window, U);
+    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(bootstrap_sums_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_bootstrap_sums: ") + hipGetErrorString(ea));
+    hipLaunchKernelGGL(bootstrap_sums_kernel, dim3((unsigned)G, (unsigned)std::min<long long>(R, BOOT_GRID_Y), (unsigned)grid_z), dim3(BOOT_BLOCK),
+                       lds, (hipStream_t)stream, v, stratum_start, (long long)U, G, M, (long long)r0, (long long)R, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), window, out, counts);
+    return ew_done("r50_op_bootstrap_sums");
 }
 
 // ---- 2D-guided refinement of stitched sequences (include/r50_refine.h, refine_kernels.h) ----

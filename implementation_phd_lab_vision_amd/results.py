@@ -43,7 +43,11 @@ the cameras of every take are brought into one frame of reference and fused into
 (``kinematics.evaluate_rigid``): ``Dense | rigid`` lines set the rigid reconstruction's errors beside the poses', the ``.npz`` gains the
 ``dense_rigid_*`` keys, and ``--dense-bvh DIR`` writes one BVH file per sequence.  With ``--dense-holdout K`` (default off; needs
 ``--dense``; INTEGRATION.md section AB) only every K-th row of a stitched sequence is kept and the rows in between are interpolated
-(``resample.evaluate_holdout``): ``Dense | holdout`` lines, ``dense_holdout_*`` keys, ``pred_holdout`` in ``--dense-out``.  Every report's printed lines and ``.npz`` keys
+(``resample.evaluate_holdout``): ``Dense | holdout`` lines, ``dense_holdout_*`` keys, ``pred_holdout`` in ``--dense-out``.  With
+``--bootstrap R`` (default off; INTEGRATION.md section AC) the P1 / P2 numbers get percentile intervals and standard errors from R
+replicates of a stratified cluster bootstrap (``bootstrap.evaluate_bootstrap``: whole sequences, takes or clips resampled inside each
+action), and with ``--compare MODEL_PATH`` a paired comparison of the two checkpoints: ``Bootstrap | ...`` lines, ``bootstrap_*`` keys.
+Every report's printed lines and ``.npz`` keys
 (``*_lines``, ``*_arrays`` / ``*_npz``) are defined in the module that computes it; ``main`` only calls them in order.
 
 Two differences from running the reference's script as it stands:
@@ -183,6 +187,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "backbone that sees every K-th frame would cost")
     p.add_argument("--dense-holdout-kind", choices=("cubic", "linear"), default=argparse.SUPPRESS,
                    help="how --dense-holdout interpolates (default cubic)")
+    p.add_argument("--bootstrap", type=int, default=argparse.SUPPRESS, metavar="R",
+                   help="also give P1 / P2 (per action, and per horizon with --pred-len) a percentile interval and a standard error from R "
+                        "replicates of a stratified cluster bootstrap: whole units resampled with replacement inside each action "
+                        "(INTEGRATION.md section AC)")
+    p.add_argument("--bootstrap-unit", choices=("sequence", "take", "clip"), default=argparse.SUPPRESS,
+                   help="what --bootstrap resamples: a sequence (subject, action with trial, camera; default), a take (all cameras of one "
+                        "motion) or single clips (overlapping clips are dependent: this understates the uncertainty)")
+    p.add_argument("--bootstrap-seed", type=int, default=argparse.SUPPRESS, metavar="N", help="seed of the replicates, 0 .. 2^64 - 1 (default 0)")
+    p.add_argument("--bootstrap-level", type=float, default=argparse.SUPPRESS, metavar="L", help="coverage of the intervals (default 0.95)")
+    p.add_argument("--compare", type=str, default=argparse.SUPPRESS, metavar="MODEL_PATH",
+                   help="a second checkpoint (--bootstrap): both models are scored on the same resampled units, and the lines give "
+                        "A, B, B - A with its interval and the share of replicates in which B is better")
+    p.add_argument("--compare-weights-from", choices=WEIGHT_SOURCES, default=argparse.SUPPRESS,
+                   help="which weights of --compare to evaluate (default auto, as --weights-from)")
     return p
 
 
@@ -265,6 +283,17 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--dense-holdout-kind needs --dense-holdout")
     if getattr(args, "dense_holdout", 2) < 2:
         p.error(f"--dense-holdout keeps every K-th row with K >= 2, got {args.dense_holdout}")
+    for flag in ("bootstrap_unit", "bootstrap_seed", "bootstrap_level", "compare"):
+        if hasattr(args, flag) and not hasattr(args, "bootstrap"):
+            p.error(f"--{flag.replace('_', '-')} needs --bootstrap")
+    if hasattr(args, "compare_weights_from") and not hasattr(args, "compare"):
+        p.error("--compare-weights-from needs --compare")
+    if getattr(args, "bootstrap", 1) < 1:
+        p.error(f"--bootstrap takes the number of replicates R >= 1, got {args.bootstrap}")
+    if not 0 <= getattr(args, "bootstrap_seed", 0) < 1 << 64:
+        p.error(f"--bootstrap-seed must lie in [0, 2^64), got {args.bootstrap_seed}")
+    if not 0.0 < getattr(args, "bootstrap_level", 0.95) < 1.0:
+        p.error(f"--bootstrap-level must lie in (0, 1), got {args.bootstrap_level}")
     if args.dtw and args.pred_len <= 0:
         p.error("--dtw needs --pred-len > 0: it scores the forecast")
     if args.dtw and args.pred_len > 64:
@@ -592,6 +621,20 @@ def main(argv: Optional[List[str]] = None) -> str:
         for line in hallucinate_lines(hal):
             print(line)
 
+    boot = None
+    if hasattr(args, "bootstrap"):           # intervals on P1 / P2 from whole resampled units; two checkpoints on the same units (section AC)
+        from . import bootstrap as bs
+        other = None
+        if hasattr(args, "compare"):
+            other = build_head(load_head_state(args.compare, getattr(args, "compare_weights_from", "auto")), device, args.precision)
+            if int(other.joints_num) != int(head.joints_num):
+                raise SystemExit(f"results: --compare has {int(other.joints_num)} joints, --model_path {int(head.joints_num)}")
+        boot = bs.evaluate_bootstrap(head, test_set, None, args.bootstrap, getattr(args, "bootstrap_unit", "sequence"),
+                                     getattr(args, "bootstrap_seed", 0), getattr(args, "bootstrap_level", 0.95),
+                                     args.input_len if args.pred_len > 0 else 0, args.pred_len, compare=other)
+        for line in bs.bootstrap_lines(boot):
+            print(line)
+
     feats, joints3d, joints2d, k, metas = test_set.get_batch(dump_idx)
     n_save = min(feats.shape[0], args.save_n)
     pred = head.joints(feats)[:n_save].cpu().numpy()
@@ -648,6 +691,8 @@ def main(argv: Optional[List[str]] = None) -> str:
     if hal is not None:
         from .hallucinate import hallucinate_arrays
         extra.update(hallucinate_arrays(hal))
+    if boot is not None:
+        extra.update(bs.bootstrap_npz(boot))
     if n_render:                             # the person crops, drawn over; a clip without a usable box gets the plain background
         from . import render
         plain = torch.tensor(render._rgb_tuple(render.PANEL_BG_RGB), dtype=torch.uint8, device=device)

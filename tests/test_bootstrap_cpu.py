@@ -1,0 +1,318 @@
+"""The stratified cluster bootstrap (INTEGRATION.md section AC) without a GPU: Philox4x32-10 known answers and the properties of the numpy
+restatement tests/bootstrap_reference.py that the GPU comparison stands on; the ninth public header include/r50_bootstrap.h bound,
+exported and guard-banded; every refusal of the C entry before any launch; ``UnitTable``; ``statistics`` on the CPU against the
+restatement; the parsers."""
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from tests import bootstrap_reference as BR
+from tests.test_kinematics_cpu import RESULTS_KEYS
+
+ROOT = Path(__file__).resolve().parents[1]
+HEADER = ROOT / "include" / "r50_bootstrap.h"
+OPS = {"r50_op_bootstrap_sums"}
+STRATA = np.array([0, 1, 6, 76], dtype=np.int32)                                    # strata of 1, 5 and 70 units
+STAT_SEED, STAT_REPS = 0, 4096                                                       # checked on the CPU before it was committed
+
+
+# ---- Philox and the mapping --------------------------------------------------------------------------------------------------------------
+def _hex(words):
+    return " ".join(f"{int(w):08x}" for w in words)
+
+
+def test_philox4x32_10_known_answers():
+    """The first and the third row are the published known answers of Random123's kat_vectors; the second was computed with two
+    independent implementations and is not an independent check."""
+    assert _hex(BR.philox4x32_10([0, 0, 0, 0], [0, 0])) == "6627e8d5 e169c58d bc57ac4c 9b00dbd8"
+    assert _hex(BR.philox4x32_10([0xFFFFFFFF] * 4, [0xFFFFFFFF] * 2)) == "408f276d 41c83b0e a20bc7c6 6d5451fd"
+    assert _hex(BR.philox4x32_10([0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344], [0xA4093822, 0x299F31D0])) == \
+        "d16cfe09 94fdcceb 5001e420 24126ea1"
+    both = BR.philox4x32_10([[0, 0, 0, 0], [0xFFFFFFFF] * 4], [[0, 0], [0xFFFFFFFF] * 2])      # vectorised over lanes, a key per lane
+    assert _hex(both[0]) == "6627e8d5 e169c58d bc57ac4c 9b00dbd8" and _hex(both[1]) == "408f276d 41c83b0e a20bc7c6 6d5451fd"
+
+
+def test_the_mapping_stays_inside_its_stratum_and_the_counts_add_up():
+    for seed, r0 in ((0, 0), (0xFEDCBA9876543210, 0), (7, 2 ** 32 - 3)):
+        for rho in range(r0, r0 + 6):
+            units = BR.draw_units(STRATA, rho, seed)
+            assert units[0] == 0                                                     # n_g = 1 always names its unit
+            for g in range(3):
+                a, b = int(STRATA[g]), int(STRATA[g + 1])
+                assert np.all((units[a:b] >= a) & (units[a:b] < b))
+        c = BR.counts(STRATA, r0, 6, seed)
+        assert c.dtype == np.int32 and np.all(c[:, 0] == 1)
+        for g in range(3):
+            assert np.all(c[:, STRATA[g]:STRATA[g + 1]].sum(axis=1) == STRATA[g + 1] - STRATA[g])
+    # a replicate is a function of (seed, rho) alone: cutting [0, 6) anywhere gives the same rows, another seed or replicate other ones
+    whole = BR.counts(STRATA, 0, 6, 5)
+    assert np.array_equal(np.concatenate([BR.counts(STRATA, 0, 2, 5), BR.counts(STRATA, 2, 4, 5)]), whole)
+    assert not np.array_equal(whole[0], whole[1]) and not np.array_equal(whole, BR.counts(STRATA, 0, 6, 6))
+    assert not np.array_equal(BR.counts(STRATA, 2 ** 32, 1, 5), BR.counts(STRATA, 0, 1, 5))    # the high word of rho is in the counter
+
+
+def test_statistical_sanity_of_the_restatement():
+    """Only the restatement: the GPU equals it exactly.  A unit's multiplicity in one replicate is Binomial(n, 1/n): mean 1, variance
+    1 - 1/n, so the mean over R independent replicates has sigma = sqrt((1 - 1/n) / R).  A unit is absent with probability
+    (1 - 1/n)^n; the absences of the units of one replicate are negatively associated, so sqrt(p (1 - p) / (R n)), the sigma of R n
+    independent cells, bounds the share's sigma from above."""
+    c = BR.counts(STRATA, 0, STAT_REPS, STAT_SEED)
+    for g, n in ((1, 5), (2, 70)):
+        sigma = np.sqrt((1.0 - 1.0 / n) / STAT_REPS)
+        z = np.abs(c[:, STRATA[g]:STRATA[g + 1]].mean(axis=0) - 1.0) / sigma
+        print(f"stratum of {n}: the per-unit mean count is at most {z.max():.2f} sigma from 1")
+        assert z.max() < 5.0
+    p = (1.0 - 1.0 / 70.0) ** 70
+    share = float((c[:, 6:] == 0).mean())
+    sigma = np.sqrt(p * (1.0 - p) / (STAT_REPS * 70))
+    print(f"absent share {share:.6f} against {p:.6f}: {abs(share - p) / sigma:.2f} sigma")
+    assert abs(share - p) < 5.0 * sigma
+
+
+def test_the_restated_sums_skip_absent_units_and_round_every_step():
+    v = np.array([[1e300, 1.0], [-1e300, 2.0 ** -60], [1.0, 1.0], [np.inf, 3.0]])
+    ss = np.array([0, 4], dtype=np.int32)
+    c = np.array([[1, 1, 1, 0], [2, 0, 0, 0], [0, 0, 0, 2]], dtype=np.int32)
+    out = BR.sums(v, ss, c)
+    assert out[0, 0, 0] == 1.0 and out[0, 0, 1] == (1.0 + 2.0 ** -60) + 1.0          # (1e300 - 1e300) + 1; the absent inf never enters
+    assert out[1, 0, 0] == 2e300 and out[1, 0, 1] == 2.0                             # the multiplicity multiplies, once
+    assert out[2, 0, 0] == np.inf and out[2, 0, 1] == 6.0
+    assert np.array_equal(BR.point_sums(v[:3], np.array([0, 1, 3], dtype=np.int32)), np.array([[1e300, 1.0], [-1e300 + 1.0, 1.0 + 2.0 ** -60]]))
+
+
+# ---- the header and the C entry ----------------------------------------------------------------------------------------------------------
+def _prototypes():
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    protos = re.findall(r"^\s*(?:int|int64_t|size_t)\s+(r50_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.M | re.S)
+    assert protos, "no prototypes parsed from include/r50_bootstrap.h"
+    return [(name, len([a for a in args.split(",") if a.strip()])) for name, args in protos]
+
+
+def test_every_prototype_of_the_bootstrap_header_is_bound_exported_and_guard_banded(lib_built):
+    from implementation_phd_lab_vision_amd import _lib
+    from tests import test_bootstrap_guard_bands_gpu as T
+    protos = _prototypes()
+    names = [n for n, _ in protos]
+    assert set(names) == OPS == set(_lib._SIGNATURES_BOOTSTRAP) and len(names) == len(set(names))
+    covered = set()
+    for row in T.ROWS_BOOTSTRAP:
+        covered.update(row.ops)
+    assert covered == OPS and len({row.id for row in T.ROWS_BOOTSTRAP}) == len(T.ROWS_BOOTSTRAP)
+    others = [(ROOT / "include" / h).read_text() for h in ("r50.h", "r50_hal.h", "r50_smooth.h", "r50_multiview.h", "r50_kinematics.h",
+                                                            "r50_refine.h", "r50_track.h", "r50_resample.h")]
+    tables = (_lib._SIGNATURES, _lib._SIGNATURES_HAL, _lib._SIGNATURES_SMOOTH, _lib._SIGNATURES_MULTIVIEW, _lib._SIGNATURES_KINEMATICS,
+              _lib._SIGNATURES_REFINE, _lib._SIGNATURES_TRACK, _lib._SIGNATURES_RESAMPLE)
+    for name, arity in protos:
+        assert len(_lib._SIGNATURES_BOOTSTRAP[name][1]) == arity, name
+        assert hasattr(lib_built, name), f"{name} declared in r50_bootstrap.h but not exported by libr50hip.so"
+        assert getattr(lib_built, name).argtypes == _lib._SIGNATURES_BOOTSTRAP[name][1]
+        assert not any(name in table for table in tables)
+        assert name not in _lib.EXPORTED_SYMBOLS and not any(name in text for text in others)
+    assert "r50_bootstrap.h" in (ROOT / "implementation_phd_lab_vision_amd" / "_lib.py").read_text().split("def _source_digest")[1].split("def ")[0]
+    abi = (ROOT / "implementation_phd_lab_vision_amd" / "csrc" / "r50_abi.hip").read_text()
+    assert '#include "bootstrap_kernels.h"' in abi and "r50_bootstrap.h" in abi
+    assert "2^-32" in HEADER.read_text()                                             # the mapping's deviation from 1 / n_g is stated there
+
+
+def test_every_refusal_of_the_c_entry_returns_before_any_launch(lib_built):
+    """No device is needed: each call is refused on its arguments.  The pointers are made-up addresses that nothing dereferences."""
+    v, starts, out, counts = (0x10000000 * k for k in range(1, 5))
+    ok = dict(v=v, starts=starts, U=76, G=3, M=7, r0=0, R=10, seed=5, window=16, out=out, counts=counts)
+    bad = [(dict(**{name: None}), "null pointer") for name in ("v", "starts", "out")]
+    bad += [(kw, "invalid arguments") for kw in (dict(U=0), dict(U=-1), dict(G=0), dict(G=-2), dict(M=0), dict(M=-1), dict(R=0), dict(R=-5),
+                                                 dict(G=77), dict(U=(1 << 24) + 1, out=1 << 50, counts=None), dict(M=4097))]
+    bad += [(kw, "r0") for kw in (dict(r0=-1), dict(r0=2 ** 63 - 10, R=11), dict(r0=2 ** 63 - 1, R=1))]
+    bad += [(kw, "2^40") for kw in (dict(R=1 << 40, U=1, G=1, M=1), dict(R=(1 << 40) // 21 + 1), dict(R=(1 << 40) // 76 + 1, M=1, G=1),
+                                    dict(R=2 ** 62))]
+    bad += [(kw, "window") for kw in (dict(window=0), dict(window=-1), dict(window=32769))]
+    bad += [(kw, "aligned") for kw in (dict(v=v + 4), dict(out=out + 4), dict(out=out + 1), dict(counts=counts + 2))]
+    bad += [(kw, "overlaps") for kw in (dict(out=v), dict(out=v + 76 * 7 * 8 - 8), dict(out=v - 10 * 3 * 7 * 8 + 8), dict(out=starts + 8),
+                                        dict(counts=v + 16), dict(counts=starts), dict(counts=starts + 12), dict(counts=out),
+                                        dict(counts=out + 10 * 3 * 7 * 8 - 4), dict(out=counts + 10 * 76 * 4 - 8), dict(counts=v - 10 * 76 * 4 + 4))]
+    call = lambda a: lib_built.r50_op_bootstrap_sums(a["v"], a["starts"], a["U"], a["G"], a["M"], a["r0"], a["R"], a["seed"], a["window"],   # noqa: E731
+                                                     a["out"], a["counts"], None)
+    for kw, why in bad:
+        rc = call(dict(ok, **kw))
+        assert rc == -1, (kw, rc)                                                    # R50_ERR_INVALID: refused, not a launch that failed
+        msg = lib_built.r50_last_error(None)
+        assert b"r50_op_bootstrap_sums" in msg and why.encode() in msg, (kw, msg)
+
+
+# ---- UnitTable -----------------------------------------------------------------------------------------------------------------------------
+def _entry(subject, action, cam, start):
+    return {"subject": subject, "action": action, "cam": cam, "start": start, "end": start + 8}
+
+
+CLIPS = [_entry(9, "Walking_1", "cam_2", 0), _entry(9, "Directions 1", 1, 4), _entry(9, "Walking_1", "cam_1", 0), _entry(9, "Walking", "cam_1", 0),
+         _entry(9, "Directions 1", 1, 0), _entry(11, "Walking_1", "cam_1", 5), _entry(9, "Walking_1", "cam_2", 5), _entry(9, "Eating", 3, 0),
+         _entry(9, "Directions", 1, 0)]
+
+
+def test_unit_table_kinds_sort_order_and_refusals():
+    from implementation_phd_lab_vision_amd import bootstrap as bs
+    t = bs.UnitTable.from_clips(CLIPS)                                               # sequences: (subject, action with trial, cam)
+    assert t.unit == "sequence" and t.stratum_names == ["Directions", "Eating", "Walking"]          # the trial suffix is stripped
+    assert t.unit_keys == [(9, "Directions", "1"), (9, "Directions 1", "1"), (9, "Eating", "3"), (9, "Walking", "cam_1"),
+                           (9, "Walking_1", "cam_1"), (9, "Walking_1", "cam_2"), (11, "Walking_1", "cam_1")]
+    assert t.stratum_start.tolist() == [0, 2, 3, 7] and t.stratum_start.dtype == np.int32
+    assert t.unit_of_clip.tolist() == [5, 1, 4, 3, 1, 6, 5, 2, 0] and t.unit_of_clip.dtype == np.int32
+    assert (t.units, t.strata, t.clips, t.largest_stratum) == (7, 3, 9, 4) and t.stratum_of_unit.tolist() == [0, 0, 1, 2, 2, 2, 2]
+    take = bs.UnitTable.from_clips(CLIPS, "take")                                    # all cameras of (subject, action with trial)
+    assert take.unit_keys == [(9, "Directions"), (9, "Directions 1"), (9, "Eating"), (9, "Walking"), (9, "Walking_1"), (11, "Walking_1")]
+    assert take.stratum_start.tolist() == [0, 2, 3, 6] and take.unit_of_clip.tolist() == [4, 1, 4, 3, 1, 5, 4, 2, 0]
+    clip = bs.UnitTable.from_clips(CLIPS, "clip")
+    assert clip.units == 9 and clip.stratum_start.tolist() == [0, 3, 4, 9] and sorted(clip.unit_of_clip.tolist()) == list(range(9))
+    assert clip.unit_of_clip.tolist() == [6, 2, 5, 4, 1, 8, 7, 3, 0]                 # by (stratum, sequence key, start)
+    v = bs.unit_rows(np.arange(18, dtype=np.float64).reshape(9, 2), t)
+    assert v[:, -1].tolist() == [1, 2, 1, 1, 1, 2, 1] and v[1, :2].tolist() == [2 + 8, 3 + 9] and v[5, :2].tolist() == [0 + 12, 1 + 13]
+    assert np.array_equal(bs.point_sums(v, t), BR.point_sums(v, t.stratum_start))
+    sized = bs.UnitTable.from_sizes([1, 5, 70])
+    assert sized.stratum_start.tolist() == STRATA.tolist() and sized.units == 76
+    for bad in (dict(clips=[]), dict(clips=CLIPS, unit="frame")):
+        with pytest.raises(ValueError):
+            bs.UnitTable.from_clips(**bad)
+    with pytest.raises(ValueError, match="2\\^24"):
+        bs.UnitTable.from_sizes([1 << 24, 1])
+    for sizes in ([], [3, 0]):
+        with pytest.raises(ValueError):
+            bs.UnitTable.from_sizes(sizes)
+    with pytest.raises(ValueError, match="stratum_start"):
+        bs.UnitTable("clip", np.arange(3, dtype=np.int32), np.array([0, 2, 2, 3], dtype=np.int32), ["a", "b", "c"], [(0,), (1,), (2,)])
+    with pytest.raises(ValueError, match="unit_of_clip"):
+        bs.UnitTable("clip", np.array([0, 0, 2], dtype=np.int32), np.array([0, 3], dtype=np.int32), ["a"], [(0,), (1,), (2,)])
+    with pytest.raises(ValueError, match="scores"):
+        bs.unit_rows(np.zeros((8, 2)), t)
+
+
+def test_the_wrapper_refuses_before_it_touches_a_device():
+    import torch
+    from implementation_phd_lab_vision_amd import bootstrap as bs
+    t = bs.UnitTable.from_sizes([1, 5, 70])
+    v = torch.zeros((76, 3), dtype=torch.float64)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        bs.bootstrap_sums(v, t, 4, 0)
+    for bad, match in ((dict(v=v.float()), "fp64"), (dict(v=v[0]), "fp64"), (dict(v=v[:75]), "rows"), (dict(v=torch.zeros((76, 4097), dtype=torch.float64)), "columns"),
+                       (dict(R=0), "R >= 1"), (dict(r0=-1), "r0 >= 0"), (dict(R=1 << 40), "2\\^40"), (dict(seed=-1), "seed"), (dict(seed=1 << 64), "seed"),
+                       (dict(window=0), "window"), (dict(window=32769), "window"), (dict(table=t.stratum_start), "UnitTable")):
+        a = dict(dict(v=v, table=t, R=4, seed=0), **bad)
+        with pytest.raises(ValueError, match=match):
+            bs.bootstrap_sums(**a)
+
+
+# ---- statistics ----------------------------------------------------------------------------------------------------------------------------
+def test_the_order_statistic_rule():
+    from implementation_phd_lab_vision_amd import bootstrap as bs
+    assert bs.order_indices(1, 0.95) == (0, 0) and bs.order_indices(2, 0.95) == (0, 1)
+    assert bs.order_indices(1000, 0.95) == (24, 974) and bs.order_indices(1000, 0.90) == (49, 949) and bs.order_indices(40, 0.95) == (0, 38)
+    for reps in (1, 2, 3, 40, 1000, 10000):
+        for level in (0.5, 0.9, 0.95, 0.99):
+            assert bs.order_indices(reps, level) == BR.order_indices(reps, level)
+
+
+@pytest.mark.parametrize("reps", [1, 2, 1000])
+def test_statistics_against_the_restatement_on_a_hand_made_replicate_table(reps):
+    """On the CPU (the function is plain torch): the order statistics, the point values and ``p_better`` equal the restatement exactly,
+    the elementwise steps being IEEE and the sums over strata sequential in both; the two standard errors are reductions over R whose
+    order is the library's, so they are held to 64 ulp * log2(R + 1) relative (a pairwise or a sequential sum of R squares stays far
+    inside)."""
+    import torch
+    from implementation_phd_lab_vision_amd import bootstrap as bs
+    rng = np.random.default_rng(reps)
+    g, k = 3, 2
+    s = rng.uniform(1.0, 2.0, size=(reps, g, 2 * k + 1))
+    s[..., -1] = rng.integers(1, 9, size=(reps, g))
+    s[: reps // 4, :, k:2 * k] = s[: reps // 4, :, :k]                              # ties: B == A in a quarter of the replicates
+    point = s[0] * 1.01
+    point[:, -1] = s[0, :, -1]
+    want = BR.statistics(s, point, 0.95, pairs=k)
+    got = bs.statistics(torch.from_numpy(s), torch.from_numpy(point), 0.95, pairs=k)
+    assert set(got) == set(want) and got["point"].shape == (g + 2, 2 * k) and got["p_better"].shape == (g + 2, k)
+    for name in ("point", "lo", "hi", "diff", "diff_lo", "diff_hi", "p_better", "p_two_sided"):
+        assert np.array_equal(got[name], want[name]), name
+    bound = 64 * np.finfo(np.float64).eps * np.log2(reps + 1)
+    for name in ("se", "diff_se"):
+        if reps == 1:
+            assert np.isnan(got[name]).all() and np.isnan(want[name]).all()
+        else:
+            assert np.all(np.abs(got[name] - want[name]) <= bound * np.abs(want[name])), name
+    if reps >= 4:
+        assert np.all(got["p_better"][:, 0] >= 0.125 - 1e-12) and (got["p_better"] * reps * 2 == np.round(got["p_better"] * reps * 2)).all()
+    plain = bs.statistics(torch.from_numpy(s), torch.from_numpy(point), 0.95)
+    assert set(plain) == {"point", "se", "lo", "hi"} and np.array_equal(plain["lo"], want["lo"])
+    # ddof 1, and the rows: all = sum of sums over sum of counts, the action mean = the plain mean over strata
+    if reps == 2:
+        all0 = (s[:, 0, 0] + s[:, 1, 0] + s[:, 2, 0]) / (s[:, 0, -1] + s[:, 1, -1] + s[:, 2, -1])
+        assert np.isclose(got["se"][0, 0], abs(all0[0] - all0[1]) / np.sqrt(2.0), rtol=1e-12)
+        mean0 = (s[0, 0, 0] / s[0, 0, -1] + s[0, 1, 0] / s[0, 1, -1] + s[0, 2, 0] / s[0, 2, -1]) / 3.0
+        assert min(got["lo"][1, 0], got["hi"][1, 0]) <= mean0 <= max(got["lo"][1, 0], got["hi"][1, 0])
+    for bad in (dict(level=0.0), dict(level=1.0), dict(pairs=1)):
+        with pytest.raises(ValueError):
+            bs.statistics(torch.from_numpy(s), torch.from_numpy(point), **{"level": 0.95, **bad})
+
+
+def test_a_model_against_itself_is_a_tie_everywhere():
+    import torch
+    from implementation_phd_lab_vision_amd import bootstrap as bs
+    rng = np.random.default_rng(3)
+    a = rng.uniform(1.0, 2.0, size=(50, 3, 2))
+    s = np.concatenate([a, a, rng.integers(1, 9, size=(50, 3, 1)).astype(np.float64)], axis=2)
+    got = bs.statistics(torch.from_numpy(s), torch.from_numpy(s[0]), 0.95, pairs=2)
+    assert np.all(got["diff"] == 0) and np.all(got["diff_lo"] == 0) and np.all(got["diff_hi"] == 0) and np.all(got["p_better"] == 0.5)
+    assert np.all(got["p_two_sided"] == 1.0) and np.all(got["diff_se"] == 0)
+
+
+def test_lines_and_keys_of_a_hand_made_result():
+    from implementation_phd_lab_vision_amd import bootstrap as bs
+    z = np.full((4, 2), 0.05)
+    res = {"metrics": ["p1", "p2"], "rows": ["all", "action mean", "act0", "act1"], "unit": "sequence", "reps": 100, "seed": 7, "level": 0.95,
+           "units": np.array([2, 3]), "clips": np.array([5, 6]), "point": z, "se": z / 50, "lo": z - 0.002, "hi": z + 0.002,
+           "design_effect": 2.5, "clip_interval": np.array([0.049, 0.051])}
+    lines = bs.bootstrap_lines(res)
+    assert len(lines) == 6 and all(line.lstrip().startswith("Bootstrap | ") for line in lines)
+    assert lines[0] == "Bootstrap | unit sequence | units 5 | strata 2 | clips 11 | replicates 100 | seed 7 | level 0.95"
+    assert lines[1] == "Bootstrap | all | p1 (mm) 50.00 [48.00, 52.00] se 1.00 | p2 (mm) 50.00 [48.00, 52.00] se 1.00"
+    assert lines[3].startswith("  Bootstrap | act0 | units 2 | clips 5 | p1 (mm)") and "design effect" in lines[5] and "2.50" in lines[5]
+    keys = bs.bootstrap_npz(res)
+    assert set(keys) == {"bootstrap_metrics", "bootstrap_rows", "bootstrap_units", "bootstrap_clips", "bootstrap_settings", "bootstrap_unit",
+                         "bootstrap_point", "bootstrap_se", "bootstrap_lo", "bootstrap_hi", "bootstrap_design_effect"}
+    res.update(b_point=z, b_se=z, b_lo=z, b_hi=z, diff=z * 0, diff_se=z * 0, diff_lo=z * 0, diff_hi=z * 0, p_better=z * 10, p_two_sided=z * 20)
+    paired = bs.bootstrap_lines(res)
+    assert "paired: B - A" in paired[0] and "A 50.00 B 50.00 B-A 0.00 [0.00, 0.00] p_better 0.500 p 1.000" in paired[1]
+    assert {"bootstrap_b_point", "bootstrap_diff", "bootstrap_diff_lo", "bootstrap_p_better", "bootstrap_p_two_sided"} <= set(bs.bootstrap_npz(res))
+
+
+# ---- the parsers ---------------------------------------------------------------------------------------------------------------------------
+def test_parser_flag_rules_and_unchanged_default_namespace(capsys):
+    from implementation_phd_lab_vision_amd import results
+    base = ["--features_root", "f", "--preprocessed_root", "v", "--model_path", "m"]
+    assert sorted(vars(results.parse_args(base))) == RESULTS_KEYS
+    assert sorted(vars(results.parse_args(base + ["--pred-len", "5", "--protocols"]))) == RESULTS_KEYS
+    a = results.parse_args(base + ["--bootstrap", "1000"])
+    assert a.bootstrap == 1000 and sorted(vars(a)) == sorted(RESULTS_KEYS + ["bootstrap"])
+    for flag, value, want in (("--bootstrap-unit", "take", "take"), ("--bootstrap-seed", "18446744073709551615", 2 ** 64 - 1),
+                              ("--bootstrap-level", "0.9", 0.9), ("--compare", "other.pt", "other.pt")):
+        a = results.parse_args(base + ["--bootstrap", "10", flag, value])
+        key = flag[2:].replace("-", "_")
+        assert getattr(a, key) == want and sorted(vars(a)) == sorted(RESULTS_KEYS + ["bootstrap", key])
+    a = results.parse_args(base + ["--bootstrap", "10", "--compare", "o.pt", "--compare-weights-from", "ema"])
+    assert sorted(vars(a)) == sorted(RESULTS_KEYS + ["bootstrap", "compare", "compare_weights_from"]) and a.compare_weights_from == "ema"
+    for bad in (["--compare", "o.pt"], ["--bootstrap-unit", "take"], ["--bootstrap-seed", "1"], ["--bootstrap-level", "0.9"],
+                ["--bootstrap", "10", "--compare-weights-from", "ema"], ["--bootstrap", "0"], ["--bootstrap", "-4"], ["--bootstrap", "2.5"],
+                ["--bootstrap", "10", "--bootstrap-unit", "frame"], ["--bootstrap", "10", "--bootstrap-seed", "-1"],
+                ["--bootstrap", "10", "--bootstrap-seed", "18446744073709551616"], ["--bootstrap", "10", "--bootstrap-level", "1"],
+                ["--bootstrap", "10", "--bootstrap-level", "0"], ["--bootstrap", "10", "--bootstrap-level", "nan"]):
+        with pytest.raises(SystemExit):
+            results.parse_args(base + bad)
+    err = capsys.readouterr().err
+    for text in ("--compare needs --bootstrap", "--bootstrap-unit needs --bootstrap", "--bootstrap-seed needs --bootstrap",
+                 "--bootstrap-level needs --bootstrap", "--compare-weights-from needs --compare", "R >= 1", "[0, 2^64)", "(0, 1)"):
+        assert text in err, text
+
+
+def test_the_product_never_imports_the_test_restatement():
+    pkg = ROOT / "implementation_phd_lab_vision_amd"
+    for path in [pkg / "bootstrap.py", pkg / "results.py", ROOT / "scripts" / "bench_bootstrap.py"]:
+        text = path.read_text()
+        assert "bootstrap_reference" not in text and "from tests" not in text and "import tests" not in text, path
