@@ -3839,8 +3839,10 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const ResizeArgs a)
     const size_t g0 = ((size_t)(a.top + y0) * a.W + a.left) * 3, g1 = ((size_t)(a.top + y1) * a.W + a.left) * 3;
     const int row_bytes = a.ww * 3;
     const int row_pad = (row_bytes + 3 + 3) & ~3;                     // room for the leading misalignment
-    // copy [g & ~3, g + row_bytes) of both rows as dwords; sh = g & 3 is where the crop starts inside the copy
-    const int sh0 = (int)(g0 & 3), sh1 = (int)(g1 & 3);
+    // copy [p & ~3, p + row_bytes) of both rows as dwords, p = the ADDRESS of the crop's first byte; sh = p & 3 is where the crop starts
+    // inside the copy.  (Taken from the address, not from the offset g: a frame of H * W * 3 bytes need not be a multiple of 4, and the
+    // frames pointer needs no alignment, so only the address makes every dword load an aligned one.)
+    const int sh0 = (int)((size_t)(f + g0) & 3), sh1 = (int)((size_t)(f + g1) & 3);
     const unsigned* s0 = reinterpret_cast<const unsigned*>(f + (g0 - sh0));
     const unsigned* s1 = reinterpret_cast<const unsigned*>(f + (g1 - sh1));
     const int nd0 = (sh0 + row_bytes + 3) >> 2, nd1 = (sh1 + row_bytes + 3) >> 2;

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -127,6 +128,18 @@ int fail(r50_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
     g_err = msg;
     return code;
+}
+
+// Pointer alignment (include/r50.h, "Pointer alignment"): every device pointer annotated R50_ALIGNED(n) in a header is checked with
+// need_aligned, under the header's parameter name, before the entry point's first launch, copy or attribute call: after its null checks,
+// or as its first statement where those live in the launcher (NULL, allowed or not, counts as aligned, so a null pointer is still
+// answered by the null check).  Returns 0, or R50_ERR_INVALID with a message that names the parameter and the bytes.
+struct AlignedArg { const void* p; const char* name; unsigned bytes; };
+int need_aligned(r50_handle* h, const char* op, std::initializer_list<AlignedArg> args) {
+    for (const AlignedArg& a : args)
+        if ((uintptr_t)a.p & (uintptr_t)(a.bytes - 1u))
+            return fail(h, R50_ERR_INVALID, std::string(op) + ": " + a.name + " must be " + std::to_string(a.bytes) + "-byte aligned");
+    return 0;
 }
 
 #define HIP_TRY(h, expr)                                                                          \
@@ -1363,6 +1376,10 @@ int forward_impl(r50_handle* h, const TIN* x, int n, float* out, void* stream) {
     if (!h->loaded) return fail(h, R50_ERR_STATE, "r50_forward: weights not loaded");
     if (!x || !out) return fail(h, R50_ERR_INVALID, "r50_forward: null buffer");
     if (n < 0) return fail(h, R50_ERR_INVALID, "r50_forward: n < 0");
+    // the fused stem loads 4 pixels at a time (16 bytes of fp32, 4 of uint8); the average pool stores f32x4
+    if (int rc_al = need_aligned(h, sizeof(TIN) == 1 ? "r50_forward_u8" : "r50_forward",
+                                 {{x, sizeof(TIN) == 1 ? "x_nchw_u8_dev" : "x_nchw_f32_dev", sizeof(TIN) == 1 ? 4u : 16u}, {out, "out_f32_dev", 16}}))
+        return rc_al;
     HIP_TRY(h, hipSetDevice(h->device));
     int chunk = h->max_batch;
     if (h->micro_batch > 0 && h->micro_batch < chunk) chunk = h->micro_batch;
@@ -1743,6 +1760,7 @@ int r50_forward_layer(r50_handle* h, const float* x, int n, const char* layer, v
     if (!h->loaded) return fail(h, R50_ERR_STATE, "r50_forward_layer: weights not loaded");
     if (!x || !out || !layer || !dims_out) return fail(h, R50_ERR_INVALID, "r50_forward_layer: null argument");
     if (n < 1 || n > h->max_batch) return fail(h, R50_ERR_INVALID, "r50_forward_layer: n must be in [1,max_batch]");
+    if (int rc_al = need_aligned(h, "r50_forward_layer", {{x, "x_nchw_f32_dev", 16}, {out, "out_bf16_nhwc_dev", 2}})) return rc_al;
     HIP_TRY(h, hipSetDevice(h->device));
     const __bf16* p = nullptr;
     int rc = run_stack(h, x, n, nullptr, (hipStream_t)stream, layer, &p, dims_out);
@@ -1852,11 +1870,17 @@ static int op_status(hipError_t e, const char* op) {
 
 int r50_op_conv2d(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                   void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d", {{x, "x_nhwc_bf16", 16}, {wt, "w_ohwi_bf16", 16}, {bias, "bias_f32", 16},
+                                                 {res, "residual_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}}))
+        return rc_al;
     return op_conv2d_et(0, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu, tile, stream);
 }
 
 int r50_op_conv2d_f16(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                       void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_f16", {{x, "x_nhwc_f16", 16}, {wt, "w_ohwi_f16", 16}, {bias, "bias_f32", 16},
+                                                 {res, "residual_nhwc_f16", 16}, {y, "y_nhwc_f16", 16}}))
+        return rc_al;
     return op_conv2d_et(1, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu, tile, stream);
 }
 
@@ -1877,6 +1901,9 @@ static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, con
 // The two pair precisions at kernel level: the ConvArgs run_conv builds for R50_PREC_BF16W2 / R50_PREC_FP32X, through the same launcher.
 int r50_op_conv2d_w2(const void* x, int n, int h, int w, int cin, const void* w_pair, const float* bias, const void* res, void* y,
                      int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_w2", {{x, "x_nhwc_bf16", 16}, {w_pair, "w_pair_bf16", 16}, {bias, "bias_f32", 16},
+                                                 {res, "residual_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}}))
+        return rc_al;
     ConvArgs a;
     int rc = fill_conv_args(a, x, n, h, w, cin, w_pair, bias, res, y, cout, ksize, stride, pad, relu, false, true);
     if (rc) return fail(nullptr, rc, "r50_op_conv2d_w2: invalid arguments");
@@ -1889,6 +1916,9 @@ int r50_op_conv2d_w2(const void* x, int n, int h, int w, int cin, const void* w_
 
 int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const void* w_trip, const float* bias, const void* res_pair,
                         void* y_pair, int cout, int ksize, int stride, int pad, int relu, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_split", {{x_pair, "x_pair_bf16", 16}, {w_trip, "w_trip_bf16", 16}, {bias, "bias_f32", 16},
+                                                 {res_pair, "residual_pair_bf16", 16}, {y_pair, "y_pair_bf16", 16}}))
+        return rc_al;
     ConvArgs a;
     int rc = fill_conv_args(a, x_pair, n, h, w, cin, w_trip, bias, res_pair, y_pair, cout, ksize, stride, pad, relu, true, false);
     if (rc) return fail(nullptr, rc, "r50_op_conv2d_split: invalid arguments");
@@ -1898,6 +1928,9 @@ int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const 
 
 int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias_scaled, const void* res, void* y,
                       int cout, int ksize, int stride, int pad, int relu, float oscale, float rscale, int tile, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_fp8", {{x, "x_nhwc_fp8", 16}, {wt, "w_ohwi_fp8", 16}, {bias_scaled, "bias_scaled_f32", 16},
+                                                 {res, "residual_nhwc_fp8", 16}, {y, "y_nhwc_fp8", 16}}))
+        return rc_al;
     if (cin <= 0 || cin % 128) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_fp8: cin must be a multiple of 128");
     ConvArgs a;
     // the loaders move bytes: described in 2-byte units, an fp8 tensor with cin channels is a 16-bit tensor with cin / 2
@@ -1911,6 +1944,9 @@ int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* w
 
 int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* x2, int h2, int w2, int c2, int stride2, const void* wcat,
                        const float* bias, void* y, int cout, int relu, int tile, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_conv1x1_cat", {{x1, "x1", 16}, {x2, "x2", 16}, {wcat, "wcat", 16},
+                                                 {bias, "bias_f32", 16}, {y, "y", 16}}))
+        return rc_al;
     ConvArgs a;
     int rc = fill_conv_args_cat(a, x1, n, h, w, c1, x2, h2, w2, c2, stride2, wcat, bias, y, cout, relu);
     if (rc || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv1x1_cat: invalid arguments");
@@ -1926,6 +1962,9 @@ static int op_et() { const char* v = std::getenv("R50_OP_ET"); return (v && std:
 
 int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const float* b3, const void* res, const void* wd,
                       const float* bd, void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_tail", {{y2, "y2_bf16", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16}, {res, "identity_bf16", 16}, {wd, "wd_bf16", 16},
+                                                 {bd, "bd", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc_al;
     hipError_t e;
     const int et = op_et();
     if (cmid == 64) e = launch_bneck_tail(y2, m, w3, b3, res, wd, bd, out, w1, c1, b1, y1n, (hipStream_t)stream, et);
@@ -1958,12 +1997,18 @@ int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const
 
 int r50_op_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, const float* b1, void* y1n, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_block2", {{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16},
+                                                 {res, "identity_bf16", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc_al;
     const hipError_t e = launch_bneck_block2(t1, n, w2, b2, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, op_et());
     return op_status(e, "r50_op_bneck_block2");
 }
 
 int r50_op_bneck_block1_ds(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* x, const void* wd,
                            const float* bd, void* out, const void* w1, const float* b1, void* y1n, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_block1_ds", {{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16}, {x, "x_bf16", 16},
+                                                 {wd, "wd_bf16", 16}, {bd, "bd", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc_al;
     if (!wd || !bd) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_block1_ds: null downsample weights");
     const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, x, out, w1, 64, b1, y1n, (hipStream_t)stream, op_et(), wd, bd);
     return op_status(e, "r50_op_bneck_block1_ds");
@@ -1971,6 +2016,9 @@ int r50_op_bneck_block1_ds(const void* t1, int n, const void* w2, const float* b
 
 int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const void* wcat, const float* bcat, void* out, const void* w1,
                            const float* b1, void* y1n, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_cat_chain", {{t2, "t2_bf16", 16}, {x, "x_bf16", 16}, {wcat, "wcat_bf16", 16}, {bcat, "bcat", 16},
+                                                 {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc_al;
     // plain weight matrices in, packed per call into a buffer allocated and freed in the caller's stream order (as r50_op_bneck_tail does)
     void* wp = nullptr;
     if (!wcat || !w1) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_cat_chain: null weights");
@@ -1985,6 +2033,9 @@ int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const v
 
 int r50_op_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_block1", {{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16},
+                                                 {res, "identity_bf16", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc_al;
     const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, res, out, w1, c1, b1, y1n, (hipStream_t)stream, op_et());
     return op_status(e, "r50_op_bneck_block1");
 }
@@ -2028,6 +2079,7 @@ static int resize_weight_precision(int in_size, int out_size) {
 
 int r50_op_crop_resize_u8(const void* frames, int t, int h, int w, int top, int left, int hh, int ww, void* out, int out_size,
                           int mode, int flags, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_crop_resize_u8", {{out, "out_tchw_u8", 4}})) return rc_al;
     if (!frames || !out || t < 1 || h < 1 || w < 1 || hh < 1 || ww < 1 || top < 0 || left < 0 || top + hh > h || left + ww > w ||
         out_size < 4 || (out_size & 3) || out_size > 4096 || (long long)t * h * w * 3 >= (1ll << 40))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_u8: invalid arguments (the box must lie inside the frame; out_size % 4 == 0)");
@@ -2064,8 +2116,10 @@ int r50_track_weight_precision(int in_size, int out_size) {
 int r50_op_crop_resize_boxes_u8(const void* src, int64_t src_bytes, const int64_t* table, int t, int max_ww, void* out, void* out_flip,
                                 int out_size, int mode, void* stream) {
     if (!src || !table || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: null pointer");
-    if (((uintptr_t)src & 3) || ((uintptr_t)out & 3) || ((uintptr_t)out_flip & 3) || ((uintptr_t)table & 7) || out_flip == out)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: src, out and out_flip must be 4-byte aligned (the table 8-byte), and out_flip is not out");
+    if (int rc_al = need_aligned(nullptr, "r50_op_crop_resize_boxes_u8",
+                                 {{src, "src_u8", 4}, {out, "out_tchw_u8", 4}, {out_flip, "out_flip_tchw_u8", 4}, {table, "table_dev", 8}}))
+        return rc_al;
+    if (out_flip == out) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: out_flip is not out");
     if (t < 1 || src_bytes < 1 || src_bytes >= (1ll << 40) || out_size < 4 || (out_size & 3) || out_size > 4096)
         return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: invalid arguments (need t >= 1, 1 <= src_bytes < 2^40, out_size % 4 == 0 in [4, 4096])");
     if (mode != R50_RESIZE_FLOAT && mode != R50_RESIZE_FIXED) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: unknown mode");
@@ -2159,6 +2213,7 @@ int r50_op_draw_skeletons_u8(const void* bg, int bg_rgb, const float* pts, const
 
 // ---- lifting head pieces (kernels.h: cast_rows_kernel, concat_pad_kernel, gn_relu_causal3_kernel); et: 0 = bf16, 1 = fp16
 int r50_op_cast_rows(const float* src, int64_t rows, int c, void* dst, int cpad, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_cast_rows", {{dst, "dst", 4}})) return rc_al;
     if (!src || !dst || rows < 1 || c < 1 || cpad < c || (cpad & 1) || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_cast_rows: invalid arguments");
     const long long pairs = rows * (cpad / 2);
@@ -2170,6 +2225,7 @@ int r50_op_cast_rows(const float* src, int64_t rows, int c, void* dst, int cpad,
 }
 
 int r50_op_concat_pad(const void* phi, int d, const float* y, int ny, int64_t rows, void* dst, int dp, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_concat_pad", {{phi, "phi", 2}, {dst, "dst", 2}})) return rc_al;
     if (!phi || !y || !dst || rows < 1 || d < 1 || ny < 0 || dp < d + ny || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_concat_pad: invalid arguments");
     const long long total = rows * dp;
@@ -2181,6 +2237,7 @@ int r50_op_concat_pad(const void* phi, int d, const float* y, int ny, int64_t ro
 }
 
 int r50_op_add_rows(float* y, int ny, const void* dy, int dp, int64_t rows, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_add_rows", {{dy, "dy", 2}})) return rc_al;
     if (!y || !dy || rows < 1 || ny < 1 || dp < ny || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_add_rows: invalid arguments");
     const long long total = rows * ny;
@@ -2193,6 +2250,7 @@ int r50_op_add_rows(float* y, int ny, const void* dy, int dp, int64_t rows, int 
 
 int r50_op_gn_relu_causal3(const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta, float eps,
                            void* out, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3", {{x, "x", 2}, {out, "out", 2}})) return rc_al;
     if (!x || !gamma || !beta || !out || b < 1 || t < 1 || c < 1 || groups < 1 || c % groups || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3: invalid arguments");
     if (et) hipLaunchKernelGGL(gn_relu_causal3_kernel<1>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, t, c, groups, eps);
@@ -2203,6 +2261,7 @@ int r50_op_gn_relu_causal3(const void* x, int b, int t, int c, int groups, const
 
 int r50_op_gn_relu_causal3_tm(const void* x, int b, int t, int t0, int c, int groups, const float* gamma, const float* beta, float eps,
                               void* out, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3_tm", {{x, "x", 2}, {out, "out", 2}})) return rc_al;
     if (!x || !gamma || !beta || !out || b < 1 || t < 1 || t0 < 0 || t0 >= t || c < 1 || groups < 1 || c % groups ||
         (et != 0 && et != 1) || (int64_t)b * groups > INT32_MAX || (int64_t)t * (c / groups) > INT32_MAX)
         return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_tm: invalid arguments (need 0 <= t0 < t, c % groups == 0)");
@@ -2254,6 +2313,7 @@ static int ew_done(const char* what) {
     } while (0)
 
 int r50_op_transpose16(const void* src, int rows, int cols, void* dst, int ld, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_transpose16", {{src, "src", 2}, {dst, "dst", 2}})) return rc_al;
     if (!src || !dst || rows < 1 || cols < 1 || ld < rows) return fail(nullptr, R50_ERR_INVALID, "r50_op_transpose16: invalid arguments");
     hipLaunchKernelGGL(transpose16_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)src, (unsigned short*)dst, rows, cols, ld);
@@ -2261,18 +2321,21 @@ int r50_op_transpose16(const void* src, int rows, int cols, void* dst, int ld, v
 }
 
 int r50_op_mask_scale(void* x, const void* mask_u8, float scale, int64_t n, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_mask_scale", {{x, "x", 2}})) return rc_al;
     if (!x || !mask_u8 || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_mask_scale: invalid arguments");
     R50_ET_LAUNCH(mask_scale_kernel, dim3(ew_grid(n)), dim3(256), stream, (unsigned short*)x, (const unsigned char*)mask_u8, scale, (long long)n);
     return ew_done("r50_op_mask_scale");
 }
 
 int r50_op_relu_bwd(void* dy, const void* act, float scale, int64_t n, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_relu_bwd", {{dy, "dy", 2}, {act, "act", 2}})) return rc_al;
     if (!dy || !act || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_relu_bwd: invalid arguments");
     R50_ET_LAUNCH(relu_bwd_kernel, dim3(ew_grid(n)), dim3(256), stream, (unsigned short*)dy, (const unsigned short*)act, scale, (long long)n);
     return ew_done("r50_op_relu_bwd");
 }
 
 int r50_op_colsum(const void* x, int64_t rows, int cols, int ld, float scale, float* out, int accumulate, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_colsum", {{x, "x", 2}})) return rc_al;
     if (!x || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum: invalid arguments");
     R50_ET_LAUNCH(colsum_kernel, dim3((cols + 63) / 64), dim3(1024), stream, (const unsigned short*)x, (long long)rows, cols, ld, scale, out, accumulate);
     return ew_done("r50_op_colsum");
@@ -2280,6 +2343,7 @@ int r50_op_colsum(const void* x, int64_t rows, int cols, int ld, float scale, fl
 
 int r50_op_colsum_split(const void* x, int64_t rows, int cols, int ld, float scale, float* part, float* out, int accumulate, int et,
                         void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_colsum_split", {{x, "x", 2}})) return rc_al;
     if (!x || !part || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum_split: invalid arguments");
     R50_ET_LAUNCH(colsum_chain_kernel, dim3((cols + 63) / 64, 16), dim3(64), stream, (const unsigned short*)x, (long long)rows, cols, ld, part);
@@ -2294,6 +2358,7 @@ int r50_op_colsum_f32(const float* x, int64_t rows, int cols, float scale, float
 }
 
 int r50_op_grad_accum(const void* src, float scale, float* dst, int64_t n, int accumulate, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_grad_accum", {{src, "src", 2}})) return rc_al;
     if (!src || !dst || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_accum: invalid arguments");
     R50_ET_LAUNCH(grad_accum_kernel, dim3(ew_grid(n)), dim3(256), stream, (const unsigned short*)src, scale, dst, (long long)n, accumulate);
     return ew_done("r50_op_grad_accum");
@@ -2383,9 +2448,10 @@ int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int jo
 int r50_op_gather_window_rows(const float* src, int64_t src_rows, int c, const int* starts, int b, int t, void* dst, int et, void* stream) {
     if (!src || !starts || !dst) return fail(nullptr, R50_ERR_INVALID, "r50_op_gather_window_rows: null pointer");
     if (b < 1 || t < 1 || c < 8 || c % 8 != 0 || src_rows < t || src_rows > INT32_MAX || (et != 0 && et != 1) ||
-        ((uintptr_t)src & 15) || ((uintptr_t)dst & 15) || (long long)b * t > INT32_MAX / (c / 8))
+        (long long)b * t > INT32_MAX / (c / 8))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_gather_window_rows: invalid arguments (need b >= 1, 1 <= t <= src_rows < 2^31, "
-                                              "c a positive multiple of 8, b * t * c / 8 < 2^31, et in {0,1}, src and dst 16-byte aligned)");
+                                              "c a positive multiple of 8, b * t * c / 8 < 2^31, et in {0,1})");
+    if (int rc_al = need_aligned(nullptr, "r50_op_gather_window_rows", {{src, "src_f32", 16}, {dst, "dst", 16}})) return rc_al;
     const long long items = (long long)b * t * (c / 8);
     R50_ET_LAUNCH(gather_window_rows_kernel, dim3(ew_grid(items)), dim3(256), stream, src, starts, (unsigned short*)dst, (unsigned)items,
                   (unsigned)t, (unsigned)(c / 8));
@@ -2488,8 +2554,6 @@ int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt
     return ew_done("r50_op_geo_pose_loss_grad");
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
                           void* dar, float* loss_lat, float* row_part, int et, void* stream) {
     if (!ar || !phi || !dphi_hat || !dar || !loss_lat || !row_part)
@@ -2498,8 +2562,8 @@ int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat
         return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: need b >= 1, t >= 2 (b*t within int range)");
     if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: d must be a positive multiple of 8");
     if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: et must be 0 (bf16) or 1 (fp16)");
-    if (!aligned16(ar) || !aligned16(phi) || !aligned16(dphi_hat) || !aligned16(dar))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: ar, phi, dphi_hat and dar must be 16-byte aligned");
+    if (int rc_al = need_aligned(nullptr, "r50_op_ar_latent_grad", {{ar, "ar", 16}, {phi, "phi", 16}, {dphi_hat, "dphi_hat", 16}, {dar, "dar", 16}}))
+        return rc_al;
     const long long rows = (long long)b * t;
     const double n_l = (double)b * (t - 1) * d;
     const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
@@ -2516,8 +2580,8 @@ int r50_op_hal_latent_grad(const void* h, const void* phi, const float* dh_reg, 
     if (rows < 1 || rows > INT32_MAX) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: need 1 <= rows (within int range)");
     if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: d must be a positive multiple of 8");
     if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: et must be 0 (bf16) or 1 (fp16)");
-    if (!aligned16(h) || !aligned16(phi) || !aligned16(dh_reg) || !aligned16(dh))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: h, phi, dh_reg and dh must be 16-byte aligned");
+    if (int rc_al = need_aligned(nullptr, "r50_op_hal_latent_grad", {{h, "h", 16}, {phi, "phi", 16}, {dh_reg, "dh_reg", 16}, {dh, "dh", 16}}))
+        return rc_al;
     const double n_l = (double)rows * d;
     const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
     R50_ET_LAUNCH(hal_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)h, (const unsigned short*)phi,
@@ -2700,7 +2764,7 @@ int r50_op_pose_rotations(const float* x, const int* row_seq, int64_t F, int S, 
     KinSkeleton sk;
     if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk))
         return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_rotations: ") + why);
-    if (!aligned16(quat)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: quat must be 16-byte aligned");
+    if (int rc_al = need_aligned(nullptr, "r50_op_pose_rotations", {{quat, "quat", 16}})) return rc_al;
     const long long fj = F * J * (long long)sizeof(float);
     const KinRange in[3] = {{x, 3 * fj}, {row_seq, F * (long long)sizeof(int)}, {rest, (long long)S * 3 * J * (long long)sizeof(double)}};
     const KinRange out[5] = {{quat, 4 * fj}, {euler, 3 * fj}, {rigid, 3 * fj}, {resid, F * (long long)sizeof(float)},
@@ -2887,6 +2951,7 @@ int r50_op_view_fuse(const float* pose, int64_t F, int J, const int* peer_start,
 
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,
                                float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3_bwd", {{dr, "dr", 2}, {x, "x", 2}, {add, "add", 2}, {dx, "dx", 2}})) return rc_al;
     if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part || b < 1 || t < 1 || c < 1 || groups < 1 || c % groups ||
         c / groups > 256 || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_bwd: invalid arguments");
@@ -2899,6 +2964,9 @@ int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int 
 int r50_op_gn_relu_causal3_tm_bwd(const void* dr, const void* x, int b, int t, int t0, int c, int groups, const float* gamma,
                                   const float* beta, float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et,
                                   void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3_tm_bwd", {{dr, "dr", 2}, {x, "x", 2},
+                                                 {add, "add", 2}, {dx, "dx", 2}}))
+        return rc_al;
     if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part)
         return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_tm_bwd: null pointer");
     if (b < 1 || t < 1 || t0 < 0 || t0 >= t || c < 1 || groups < 1 || c % groups || c / groups > 256 || (et != 0 && et != 1) ||
@@ -2931,8 +2999,7 @@ int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, i
         return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: need b, k >= 1 and 0 <= i0, i0 + k <= t_phi");
     if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: d must be a positive multiple of 8");
     if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: et must be 0 (bf16) or 1 (fp16)");
-    if (!aligned16(fut) || !aligned16(phi) || !aligned16(dfut))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: fut, phi and dfut must be 16-byte aligned");
+    if (int rc_al = need_aligned(nullptr, "r50_op_rollout_latent_grad", {{fut, "fut", 16}, {phi, "phi", 16}, {dfut, "dfut", 16}})) return rc_al;
     const long long rows = (long long)b * k;
     const double n_l = (double)rows * d;
     const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
@@ -2949,6 +3016,7 @@ int r50_op_check_finite(const float* g, int64_t n, int* found, void* stream) {
 }
 
 int r50_op_check_overflow16(const void* x, int64_t n, int* found, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_check_overflow16", {{x, "x", 2}})) return rc_al;
     if (!x || !found || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_check_overflow16: invalid arguments");
     R50_ET_LAUNCH(check_overflow16_kernel, dim3(ew_grid(n)), dim3(256), stream, (const unsigned short*)x, (long long)n, found);
     return ew_done("r50_op_check_overflow16");
@@ -2956,6 +3024,7 @@ int r50_op_check_overflow16(const void* x, int64_t n, int* found, int et, void* 
 
 int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, const int* found_inf, int et, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_adamw", {{p16, "p16", 2}})) return rc_al;
     if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_adamw: invalid arguments");
     const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
     R50_ET_LAUNCH(adamw_kernel, dim3(ew_grid(n)), dim3(256), stream, p, m, v, g, (unsigned short*)p16, (long long)n, lr, beta1, beta2, eps,
@@ -2978,7 +3047,7 @@ int r50_op_grad_norm(const float* g, int64_t n, float max_norm, double* part, in
     if (n_part < w)
         return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: part holds " + std::to_string(n_part) + " doubles, n = " + std::to_string(n) +
                                                   " needs " + std::to_string(w));
-    if (!aligned16(g)) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: g must be 16-byte aligned");
+    if (int rc_al = need_aligned(nullptr, "r50_op_grad_norm", {{g, "g", 16}})) return rc_al;
     const long long slice = (((long long)n + w - 1) / w + 3) / 4 * 4;
     hipLaunchKernelGGL(grad_norm_part_kernel, dim3(w), dim3(256), 0, (hipStream_t)stream, g, (long long)n, slice, part);
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)part, w, max_norm, found, clip2,
@@ -2989,6 +3058,7 @@ int r50_op_grad_norm(const float* g, int64_t n, float max_norm, double* part, in
 int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, const int* found_inf, const float* clip, float* ema, float ema_weight, int et,
                           void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_adamw_clip_ema", {{p16, "p16", 2}})) return rc_al;
     if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, "r50_op_adamw_clip_ema: invalid arguments");
     const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
@@ -3000,6 +3070,9 @@ int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* p1
 int64_t r50_stem_scratch_bytes(int n) { return (int64_t)STEM_W_BYTES + (int64_t)n * STEM_HP * STEM_WP * 8; }
 
 int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_dev, void* scratch, void* y, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_stem", {{bias_dev, "bias_f32_dev", 16}, {scratch, "scratch_dev", 16},
+                                                 {y, "y_nhwc_bf16", 16}}))
+        return rc_al;
     if (!x || !w_host || !bias_dev || !scratch || !y || n < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_stem: invalid arguments");
     std::vector<uint16_t> pk;
     const int et = op_et();
@@ -3014,12 +3087,14 @@ int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_de
 }
 
 int r50_op_maxpool(const void* x, int n, int h, int w, int c, void* y, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_maxpool", {{x, "x_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}})) return rc_al;
     if (!x || !y || n < 1 || h < 1 || w < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_maxpool: invalid arguments");
     HIP_TRY(nullptr, launch_maxpool(x, y, n, h, w, c, (hipStream_t)stream, op_et()));
     return R50_OK;
 }
 
 int r50_op_avgpool(const void* x, int n, int hw, int c, float* y, void* stream) {
+    if (int rc_al = need_aligned(nullptr, "r50_op_avgpool", {{x, "x_nhwc_bf16", 16}, {y, "y_f32", 16}})) return rc_al;
     if (!x || !y || n < 1 || hw < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: invalid arguments");
     HIP_TRY(nullptr, launch_avgpool(x, y, n, hw, c, (hipStream_t)stream, op_et()));
     return R50_OK;
@@ -3038,8 +3113,9 @@ size_t r50_op_nn_search_workspace(int nq, int n, int k) {
 
 int r50_op_row_norm2(const void* x, int n, int d, int et, float* out, void* stream) {
     if (!x || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: null pointer");
-    if (n < 1 || d < 8 || d % 8 != 0 || (et != 0 && et != 1) || ((uintptr_t)x & 15u))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: invalid arguments (need n >= 1, d a positive multiple of 8, x 16-byte aligned)");
+    if (n < 1 || d < 8 || d % 8 != 0 || (et != 0 && et != 1))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: invalid arguments (need n >= 1, d a positive multiple of 8)");
+    if (int rc_al = need_aligned(nullptr, "r50_op_row_norm2", {{x, "x", 16}})) return rc_al;
     R50_ET_LAUNCH(row_norm2_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), stream, (const unsigned short*)x, n, d, out);
     return ew_done("r50_op_row_norm2");
 }
@@ -3051,7 +3127,7 @@ int r50_op_nn_search(const void* q, int nq, const void* x, int n, int d, int et,
     if (nq < 1 || n < 1 || n > (1 << 30) || k < 1 || k > NN_MAX_K || k > n || d < 32 || d > 2048 || d % 32 != 0 || (et != 0 && et != 1))
         return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (need nq >= 1, 1 <= k <= 8, k <= n <= 2^30, d % 32 == 0 and "
                                                                 "32 <= d <= 2048)");
-    if (((uintptr_t)q | (uintptr_t)x) & 15u) return fail(nullptr, R50_ERR_INVALID, std::string(me) + "q and x must be 16-byte aligned");
+    if (int rc_al = need_aligned(nullptr, "r50_op_nn_search", {{q, "q", 16}, {x, "x", 16}, {workspace, "workspace", 4}})) return rc_al;
     if (workspace_bytes < r50_op_nn_search_workspace(nq, n, k))
         return fail(nullptr, R50_ERR_INVALID, std::string(me) + "the workspace is smaller than r50_op_nn_search_workspace asks for");
     const int cus = num_cus();

@@ -18,12 +18,30 @@
  *                    (what src/dataset.py:242-245,429 produces and :295 reshapes)
  *           features fp32 (n,2048) row-major (= backbone(x).flatten(1), :296)
  *           internal activations bf16 NHWC.
+ *
+ * Pointer alignment ("Pointer alignment").  Every DEVICE pointer of this ABI (r50.h and the r50_*.h family headers)
+ * has a required alignment in bytes:
+ *   - R50_ALIGNED(n) in front of the parameter's name: the address must be a multiple of n.  n is the widest access the kernels make
+ *     through that pointer (a 16-byte buffer or vector load, a packed 4-byte store, ...); where a kernel reads p + row * pitch with such an
+ *     access, the entry point's size checks (cin, c, d, cpad, ld multiples) make every row start a multiple of n as well.
+ *   - every `void*` / `const void*` device pointer carries one: it has no natural alignment, its element type depends on the op or on `et`.
+ *   - a typed pointer (float*, double*, int*, int64_t*) without one needs the natural alignment of its type, and the op works at every
+ *     such address.
+ * Every entry point checks its annotated pointers after the null checks and before its first launch, copy or attribute call: a pointer
+ * below its alignment returns R50_ERR_INVALID, r50_last_error() names the parameter and the bytes, and nothing was touched.  NULL, where
+ * NULL is allowed, counts as aligned.  A contiguous slice of a larger tensor is therefore a legal operand down to the stated alignment.
+ * HOST pointers (named *_host, descriptors, out-parameters such as dims_out) need only their type's natural alignment; `stream` and
+ * handles are not operands.  tests/test_alignment_gpu.py runs every op with every operand at exactly an odd multiple of its requirement.
  */
 #ifndef R50_H_
 #define R50_H_
 
 #include <stddef.h>
 #include <stdint.h>
+
+#ifndef R50_ALIGNED
+#define R50_ALIGNED(n)      /* read by people and by tests/alignment.py: the device pointer that follows must be a multiple of n bytes */
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -84,21 +102,22 @@ int r50_share_weights(r50_handle* h, r50_handle* from);
 
 /* Replaces: backbone(x).flatten(1) (:242,296).  Asynchronous on `stream` (a hipStream_t; NULL =
  * default stream).  x_nchw_f32_dev: (n,3,224,224) fp32 on the device; out_f32_dev: (n,2048).
- * n may exceed max_batch: the call then loops over chunks of max_batch frames. */
-int r50_forward(r50_handle* h, const float* x_nchw_f32_dev, int n, float* out_f32_dev, void* stream);
+ * n may exceed max_batch: the call then loops over chunks of max_batch frames.  x is R50_ALIGNED(16) (r50_forward_u8: 4): the fused stem
+ * loads 4 pixels at a time; out is R50_ALIGNED(16): the average pool stores f32x4. */
+int r50_forward(r50_handle* h, const float* R50_ALIGNED(16) x_nchw_f32_dev, int n, float* R50_ALIGNED(16) out_f32_dev, void* stream);
 
 /* Same path, one step further upstream: frames as the resized uint8 crops the reference
  * holds right before `frames.to(torch.float32) / 255.0` (src/dataset.py:141-150) and `Normalize(mean, std)`
  * (:242-245), i.e. uint8 NCHW (n,3,224,224).  The three fp32 operations ((u8/255) - mean[c]) / std[c] are done
  * in the stem kernel, bit-identical to the host path; the boundary moves 150,528 B per frame instead of 602,112. */
-int r50_forward_u8(r50_handle* h, const uint8_t* x_nchw_u8_dev, int n, float* out_f32_dev, void* stream);
+int r50_forward_u8(r50_handle* h, const uint8_t* R50_ALIGNED(4) x_nchw_u8_dev, int n, float* R50_ALIGNED(16) out_f32_dev, void* stream);
 
 /* Debug hook for per-layer parity tests (no reference counterpart; equivalent to a forward hook
  * on the nn.Sequential).  Runs the network on x (n <= max_batch) and copies the named bf16 NHWC
  * activation into out_bf16_nhwc_dev.  Names: "stem", "pool", "layer{1..4}.{b}",
  * "layer{i}.{b}.t1", ".t2", ".ds".  dims_out receives {N,H,W,C}. */
-int r50_forward_layer(r50_handle* h, const float* x_nchw_f32_dev, int n, const char* layer,
-                      void* out_bf16_nhwc_dev, int64_t out_capacity_bytes, int64_t dims_out[4],
+int r50_forward_layer(r50_handle* h, const float* R50_ALIGNED(16) x_nchw_f32_dev, int n, const char* layer,
+                      void* R50_ALIGNED(2) out_bf16_nhwc_dev, int64_t out_capacity_bytes, int64_t dims_out[4],
                       void* stream);
 
 /* Options: "micro_batch" (frames per pass through the layer stack, 0 = whole batch),
@@ -162,17 +181,21 @@ void r50_destroy(r50_handle* h);             /* replaces: del backbone */
 const char* r50_version(void);
 
 /* ---- Op-level entry points (per-kernel parity tests; each mirrors one nn.Module of the
- * reference's Sequential, upstream torchvision models/resnet.py).  bf16 NHWC device buffers. ---- */
+ * reference's Sequential, upstream torchvision models/resnet.py).  bf16 NHWC device buffers.
+ * Alignment of the convolution, bottleneck, stem and pool hooks: every tensor, weight and bias pointer is R50_ALIGNED(16).  The loaders
+ * move 16 bytes per lane through buffer descriptors built on x, w, residual and y (LDS-direct loads included), the shape-specialised
+ * and fused kernels read w / w1 / w3 / wd as 16-byte vectors, and the epilogues read the bias as f32x4; the channel checks (cin, cout
+ * multiples of 64, 128 for fp8; c % 8 for the pools) make every pixel row a multiple of 16 bytes as well. ---- */
 
 /* conv2d(k x k, stride, pad, bias=folded BN) [+ residual] [+ ReLU].  w_ohwi_bf16: (cout,k,k,cin)
  * bf16; bias fp32 (cout); residual/y: (n,ho,wo,cout) bf16.  cin % 64 == 0, cout % 64 == 0,
  * k in {1,3}.  tile: 0 = auto, else a tile-config id.  */
-int r50_op_conv2d(const void* x_nhwc_bf16, int n, int h, int w, int cin, const void* w_ohwi_bf16,
-                  const float* bias_f32, const void* residual_nhwc_bf16, void* y_nhwc_bf16,
+int r50_op_conv2d(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_ohwi_bf16,
+                  const float* R50_ALIGNED(16) bias_f32, const void* R50_ALIGNED(16) residual_nhwc_bf16, void* R50_ALIGNED(16) y_nhwc_bf16,
                   int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
 /* The same with IEEE-half tensors (R50_PREC_FP16's element type). */
-int r50_op_conv2d_f16(const void* x_nhwc_f16, int n, int h, int w, int cin, const void* w_ohwi_f16,
-                  const float* bias_f32, const void* residual_nhwc_f16, void* y_nhwc_f16,
+int r50_op_conv2d_f16(const void* R50_ALIGNED(16) x_nhwc_f16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_ohwi_f16,
+                  const float* R50_ALIGNED(16) bias_f32, const void* R50_ALIGNED(16) residual_nhwc_f16, void* R50_ALIGNED(16) y_nhwc_f16,
                   int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
 
 /* The two (head, tail) pair precisions at kernel level (debug hooks for per-kernel parity tests): the conv launches of R50_PREC_BF16W2 and
@@ -186,11 +209,11 @@ int r50_op_conv2d_f16(const void* x_nhwc_f16, int n, int h, int w, int cin, cons
  *    per tap, the packed layout of fp32x mode; residual_pair / y_pair (n,ho,wo,2*cout) = [head(cout) | tail(cout)] per pixel:
  *    v = act(x_head . w_head + x_tail . w_head + x_head . w_tail + bias [+ r_head + r_tail]) in fp32, stored as the pair of v.  No tile
  *    argument: 64 couts x 128 pixels when cout % 128 != 0, else 128 x 128, as in the network. */
-int r50_op_conv2d_w2(const void* x_nhwc_bf16, int n, int h, int w, int cin, const void* w_pair_bf16, const float* bias_f32,
-                     const void* residual_nhwc_bf16, void* y_nhwc_bf16, int cout, int ksize, int stride, int pad, int relu, int tile,
+int r50_op_conv2d_w2(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_pair_bf16, const float* R50_ALIGNED(16) bias_f32,
+                     const void* R50_ALIGNED(16) residual_nhwc_bf16, void* R50_ALIGNED(16) y_nhwc_bf16, int cout, int ksize, int stride, int pad, int relu, int tile,
                      void* stream);
-int r50_op_conv2d_split(const void* x_pair_bf16, int n, int h, int w, int cin, const void* w_trip_bf16, const float* bias_f32,
-                        const void* residual_pair_bf16, void* y_pair_bf16, int cout, int ksize, int stride, int pad, int relu,
+int r50_op_conv2d_split(const void* R50_ALIGNED(16) x_pair_bf16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_trip_bf16, const float* R50_ALIGNED(16) bias_f32,
+                        const void* R50_ALIGNED(16) residual_pair_bf16, void* R50_ALIGNED(16) y_pair_bf16, int cout, int ksize, int stride, int pad, int relu,
                         void* stream);
 
 /* fp8 convolution (BASELINE configs[4]: CDNA4 fp8 MFMA), kernel level. OCP e4m3 activations, weights and output, fp32 accumulation on
@@ -199,16 +222,16 @@ int r50_op_conv2d_split(const void* x_pair_bf16, int n, int h, int w, int cin, c
  *   y = fp8( act( acc * oscale + residual * rscale ) ),  acc = bias_scaled + sum x*w,
  *   bias_scaled = bias / (sx*sw) (device fp32), oscale = sx*sw/sy, rscale = sr/sy; conversion saturates at +-448.
  * cin % 128 == 0, cout % 64 == 0 (128 / 256 for the wider tiles), k in {1,3}.  tile: 0 = auto or a role-specialised tile id (64|...). */
-int r50_op_conv2d_fp8(const void* x_nhwc_fp8, int n, int h, int w, int cin, const void* w_ohwi_fp8, const float* bias_scaled_f32,
-                      const void* residual_nhwc_fp8, void* y_nhwc_fp8, int cout, int ksize, int stride, int pad, int relu,
+int r50_op_conv2d_fp8(const void* R50_ALIGNED(16) x_nhwc_fp8, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_ohwi_fp8, const float* R50_ALIGNED(16) bias_scaled_f32,
+                      const void* R50_ALIGNED(16) residual_nhwc_fp8, void* R50_ALIGNED(16) y_nhwc_fp8, int cout, int ksize, int stride, int pad, int relu,
                       float oscale, float rscale, int tile, void* stream);
 
 /* 1x1 conv over TWO K sources, the form the library runs conv3 + downsample + add + ReLU of a stage's first bottleneck in
  * (torchvision Bottleneck.forward: `out = conv3(out); identity = downsample(x); out += identity; relu`): y = act([W1 | W2] .
  * [x1 ; x2 sampled at stride2] + bias).  x1 (n,h,w,c1) at the output resolution, x2 (n,h2,w2,c2) with (h2-1)/stride2+1 == h;
  * wcat (cout, c1+c2) K-major; c1, c2, cout multiples of 64.  tile: 0 = auto or a role-specialised tile id (64|...). et: 0 bf16, 1 fp16. */
-int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* x2, int h2, int w2, int c2, int stride2,
-                       const void* wcat, const float* bias_f32, void* y, int cout, int relu, int tile, int et, void* stream);
+int r50_op_conv1x1_cat(const void* R50_ALIGNED(16) x1, int n, int h, int w, int c1, const void* R50_ALIGNED(16) x2, int h2, int w2, int c2, int stride2,
+                       const void* R50_ALIGNED(16) wcat, const float* R50_ALIGNED(16) bias_f32, void* R50_ALIGNED(16) y, int cout, int relu, int tile, int et, void* stream);
 
 /* Stem: fp32 NCHW frames -> conv 7x7 s2 p3 (+folded bn1 bias) + ReLU -> (n,112,112,64) bf16 NHWC.
  * w_oihw_f32: (64,3,7,7) fp32 *already folded*, host pointer; bias_f32: device pointer (64).
@@ -221,10 +244,10 @@ int64_t r50_stem_scratch_bytes(int n);
  * R50_OP_ET=1 in the environment (a test knob, read per call) they run the IEEE-half instantiations that a handle in R50_PREC_FP16
  * launches: every 16-bit tensor and weight matrix is then fp16 (the stem packs its fp32 weights to fp16), same layouts. */
 int r50_op_stem(const float* x_nchw_f32_dev, int n, const float* w_oihw_f32_host,
-                const float* bias_f32_dev, void* scratch_dev, void* y_nhwc_bf16, void* stream);
+                const float* R50_ALIGNED(16) bias_f32_dev, void* R50_ALIGNED(16) scratch_dev, void* R50_ALIGNED(16) y_nhwc_bf16, void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on bf16 NHWC; c % 8 == 0. */
-int r50_op_maxpool(const void* x_nhwc_bf16, int n, int h, int w, int c, void* y_nhwc_bf16, void* stream);
+int r50_op_maxpool(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w, int c, void* R50_ALIGNED(16) y_nhwc_bf16, void* stream);
 
 /* Bottleneck tail in one launch: conv3 1x1 (cmid -> 4*cmid) + bn3 + identity + ReLU -> out (m,4*cmid), and the
  * next block's conv1 1x1 (4*cmid -> c1) + bn1 + ReLU -> y1n (m,c1).  Replaces, for two consecutive torchvision
@@ -241,9 +264,9 @@ int r50_op_maxpool(const void* x_nhwc_bf16, int n, int h, int w, int c, void* y_
  * bit again.  cmid = 256 with c1 = 0 and w1 = b1 = y1n = NULL: conv3 + identity + ReLU ALONE through the same pipelined kernel (the form the
  * stage's last block, layer3.5, runs in; bit for bit a 1x1 r50_op_conv2d with a residual).  (Environment R50_TAIL3_BP = 1..112: pixels per tile
  * of the cmid = 256 kernel; a test knob.) */
-int r50_op_bneck_tail(const void* y2_bf16, int64_t m, int cmid, const void* w3_bf16, const float* b3,
-                      const void* identity_bf16, const void* wd_bf16, const float* bd, void* out_bf16, const void* w1_bf16,
-                      int c1, const float* b1, void* y1n_bf16, void* stream);
+int r50_op_bneck_tail(const void* R50_ALIGNED(16) y2_bf16, int64_t m, int cmid, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
+                      const void* R50_ALIGNED(16) identity_bf16, const void* R50_ALIGNED(16) wd_bf16, const float* R50_ALIGNED(16) bd, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16,
+                      int c1, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* A whole bottleneck BODY of layer2 (blocks .1-.3, 28x28, 128 mid channels) in one launch: t2 = relu(conv2_3x3(t1) + b2) stays in LDS,
  * out = relu(w3 . t2 + b3 + identity) and, when w1 / b1 / y1n are given, y1n = relu(w1 . out + b1) (the next block's conv1) --
@@ -251,16 +274,16 @@ int r50_op_bneck_tail(const void* y2_bf16, int64_t m, int cmid, const void* w3_b
  * nn.Sequential).  t1 (n,28,28,128), identity / out (n,28,28,512), y1n (n,28,28,128) bf16 NHWC; w2 (128,3,3,128), w3 (512,128),
  * w1 (128,512) folded bf16, K contiguous; biases fp32.  Bit for bit what r50_op_conv2d (3x3, input-resident tile) followed by two
  * r50_op_conv2d 1x1 launches give.  w1 = b1 = y1n = NULL: no next conv1 (the stage's last block). */
-int r50_op_bneck_block2(const void* t1_bf16, int n, const void* w2_bf16, const float* b2, const void* w3_bf16, const float* b3,
-                        const void* identity_bf16, void* out_bf16, const void* w1_bf16, const float* b1, void* y1n_bf16, void* stream);
+int r50_op_bneck_block2(const void* R50_ALIGNED(16) t1_bf16, int n, const void* R50_ALIGNED(16) w2_bf16, const float* R50_ALIGNED(16) b2, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
+                        const void* R50_ALIGNED(16) identity_bf16, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* layer1.0, the stage's first bottleneck, from its second conv on in one launch: as r50_op_bneck_block1 with c1 = 64, but the identity is the
  * DOWNSAMPLE conv of the block input computed in the kernel -- identity = bf16(wd . x + bd), rounded exactly as a separate 1x1 launch stores
  * it (torchvision `Bottleneck.forward`: `identity = self.downsample(x)`).  x (n,56,56,64) the block input, wd (256,64), bd (256).  Bit for bit
  * what the resident-weights 3x3 launch followed by r50_op_bneck_tail (cmid 64, wd / bd given) give. */
-int r50_op_bneck_block1_ds(const void* t1_bf16, int n, const void* w2_bf16, const float* b2, const void* w3_bf16, const float* b3,
-                           const void* x_bf16, const void* wd_bf16, const float* bd, void* out_bf16, const void* w1_bf16, const float* b1,
-                           void* y1n_bf16, void* stream);
+int r50_op_bneck_block1_ds(const void* R50_ALIGNED(16) t1_bf16, int n, const void* R50_ALIGNED(16) w2_bf16, const float* R50_ALIGNED(16) b2, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
+                           const void* R50_ALIGNED(16) x_bf16, const void* R50_ALIGNED(16) wd_bf16, const float* R50_ALIGNED(16) bd, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16, const float* R50_ALIGNED(16) b1,
+                           void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* The TRANSITION tail of layer2.0 chained with layer2.1.conv1 in one launch: out = relu([W3 | Wd] . [t2 ; x at stride 2] + (b3 + bd)) -- conv3,
  * the downsample conv, the add and the ReLU of torchvision's first Bottleneck of a stage (`out = relu(bn3(conv3(out)) + downsample(x))`,
@@ -268,14 +291,14 @@ int r50_op_bneck_block1_ds(const void* t1_bf16, int n, const void* w2_bf16, cons
  * y1n = relu(w1 . out + b1), the next block's conv1.  t2 (n,ow,ow,128), x (n,2ow,2ow,256), out (n,ow,ow,512), y1n (n,ow,ow,128) bf16 NHWC;
  * wcat (512, 128 + 256) = [W3 | Wd], w1 (128,512) folded bf16, K contiguous; bcat = b3 + bd, b1 fp32.  ow = 28.  Bit for bit what
  * r50_op_conv1x1_cat followed by a 1x1 r50_op_conv2d give. */
-int r50_op_bneck_cat_chain(const void* t2_bf16, const void* x_bf16, int n, int ow, const void* wcat_bf16, const float* bcat, void* out_bf16,
-                           const void* w1_bf16, const float* b1, void* y1n_bf16, void* stream);
+int r50_op_bneck_cat_chain(const void* R50_ALIGNED(16) t2_bf16, const void* R50_ALIGNED(16) x_bf16, int n, int ow, const void* R50_ALIGNED(16) wcat_bf16, const float* R50_ALIGNED(16) bcat, void* R50_ALIGNED(16) out_bf16,
+                           const void* R50_ALIGNED(16) w1_bf16, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* The same for layer1 (blocks .1 / .2, 56x56, 64 mid channels): t1 (n,56,56,64), identity / out (n,56,56,256), w2 (64,3,3,64), w3 (256,64),
  * w1 (c1,256) with c1 = 64 (the next layer1 block's conv1) or 128 (layer2.0.conv1), y1n (n,56,56,c1).  Bit for bit what the
  * resident-weights 3x3 launch followed by two r50_op_conv2d 1x1 launches give. */
-int r50_op_bneck_block1(const void* t1_bf16, int n, const void* w2_bf16, const float* b2, const void* w3_bf16, const float* b3,
-                        const void* identity_bf16, void* out_bf16, const void* w1_bf16, int c1, const float* b1, void* y1n_bf16, void* stream);
+int r50_op_bneck_block1(const void* R50_ALIGNED(16) t1_bf16, int n, const void* R50_ALIGNED(16) w2_bf16, const float* R50_ALIGNED(16) b2, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
+                        const void* R50_ALIGNED(16) identity_bf16, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16, int c1, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* Frame producer, the step before the path: crop box + bilinear resize of a decoded clip on the
  * device.  Replaces `_crop_and_resize_video_uint8` (src/dataset.py:141-149) up to, not including, the `/255`:
@@ -286,7 +309,8 @@ int r50_op_bneck_block1(const void* t1_bf16, int n, const void* w2_bf16, const f
  * mode R50_RESIZE_FIXED: ATen's native uint8 kernel (what the v2 API runs on an AVX2 CPU): two-pass int16 fixed
  * point with a uint8 intermediate, bit-exact.  The box comes from `_compute_square_crop_from_2d` (:75-104; host
  * code, mirrored in frames.py) and must lie inside the frame; out_size % 4 == 0.  Device pointers; asynchronous on
- * `stream` (indices and weights are computed in the kernel).
+ * `stream` (indices and weights are computed in the kernel).  frames may sit at any byte address (each source row is staged as dwords
+ * from the 4-byte boundary at or below the ADDRESS of its first byte); out is stored one dword per 4 pixels: R50_ALIGNED(4).
  * flags: the two augmentation variants that are index permutations, applied to the output exactly as
  * the reference applies them to the resized clip: R50_AUG_HFLIP = `torch.flip(video, dims=[-1])` (`_aug_hflip`, :158-166),
  * R50_AUG_TREV = `torch.flip(video, dims=[0])` (`_aug_temporal_reverse`, :199-207); joints / intrinsics are host code. */
@@ -294,8 +318,8 @@ int r50_op_bneck_block1(const void* t1_bf16, int n, const void* w2_bf16, const f
 #define R50_RESIZE_FIXED 1
 #define R50_AUG_HFLIP 1
 #define R50_AUG_TREV 2
-int r50_op_crop_resize_u8(const void* frames_thwc_u8, int t, int h, int w, int top, int left, int hh, int ww,
-                          void* out_tchw_u8, int out_size, int mode, int flags, void* stream);
+int r50_op_crop_resize_u8(const void* R50_ALIGNED(1) frames_thwc_u8, int t, int h, int w, int top, int left, int hh, int ww,
+                          void* R50_ALIGNED(4) out_tchw_u8, int out_size, int mode, int flags, void* stream);
 
 /* Results dump (`src/results.py`): whole-frame resize of one clip's video.  frames (n,h,w,3) uint8 HWC on the device, the decoded
  * frames the clip names; src_idx (t) int32 on the device, output frame i = frames[src_idx[i]] (the host folds `[::skip][start:end]`
@@ -306,7 +330,7 @@ int r50_op_crop_resize_u8(const void* frames_thwc_u8, int t, int h, int w, int t
  * read back once to check every index lies in [0,n) (R50_ERR_INVALID otherwise): the call synchronises `stream` once, so it
  * holds the host until everything queued on `stream` before it has run.  Of the r50_op_* entry points only this one and r50_op_stem
  * do (tests/test_stream_order_gpu.py, BLOCKS_HOST). */
-int r50_op_resize_frames_u8(const void* frames_nhwc_u8, int n, int h, int w, const int* src_idx, int t, void* out_tssc_u8,
+int r50_op_resize_frames_u8(const void* R50_ALIGNED(1) frames_nhwc_u8, int n, int h, int w, const int* src_idx, int t, void* R50_ALIGNED(1) out_tssc_u8,
                             int out_size, void* stream);
 
 /* Results rendering (no counterpart in the reference, whose src/visualize_2d.py draws with matplotlib on the
@@ -324,12 +348,13 @@ int r50_op_resize_frames_u8(const void* frames_nhwc_u8, int n, int h, int w, con
  * coverage, alpha and blend are fp32.  Coordinates of magnitude up to 2^20 keep that accuracy; larger finite ones are legal (nothing
  * is indexed by a coordinate) but unspecified in value.  Gather form, one thread per 4 pixels, no atomics: the same bits on every run.
  * w % 4 == 0 with bg and out 4-byte aligned takes a 12-byte vector path, anything else a per-byte path; same values.
+ * bg, style and out may sit at any byte address (R50_ALIGNED(1)): style is read byte by byte.
  * Refused with a message before any launch unless pts, style and out are non-NULL, f, h, w >= 1, 1 <= joints <= 64,
  * 1 <= layers <= 8, 0 <= n_edges <= 128 (edges_host non-NULL when n_edges > 0), every edge index in [0, joints), half_width and
  * joint_radius finite and >= 0, 0 <= bg_rgb <= 0xFFFFFF and out does not overlap bg.  Asynchronous on `stream`. */
-int r50_op_draw_skeletons_u8(const void* bg_fhwc_u8, int bg_rgb, const float* pts_flj2_f32, const void* style_fl4_u8,
+int r50_op_draw_skeletons_u8(const void* R50_ALIGNED(1) bg_fhwc_u8, int bg_rgb, const float* pts_flj2_f32, const void* R50_ALIGNED(1) style_fl4_u8,
                              const int* edges_host, int n_edges, int f, int h, int w, int layers, int joints, float half_width,
-                             float joint_radius, void* out_fhwc_u8, void* stream);
+                             float joint_radius, void* R50_ALIGNED(1) out_fhwc_u8, void* stream);
 
 /* ColorJitter augmentation variant: `_aug_color_jitter` (src/dataset.py:188-197) = torchvision.transforms.v2
  * ColorJitter(brightness=0.3, contrast=0.3, saturation=0.2, hue=0.05) on the float clip in [0,1], followed (normalize != 0) by
@@ -337,7 +362,7 @@ int r50_op_draw_skeletons_u8(const void* bg_fhwc_u8, int bg_rgb, const float* pt
  * r50_op_crop_resize_u8); order4: the sampled permutation of {0 brightness, 1 contrast, 2 saturation, 3 hue} (HOST pointer); the
  * four factors as sampled (host code: frames.sample_color_jitter_params); out_f32: (t,3,hw) fp32, what r50_forward takes;
  * scratch_means: t floats of device memory (per-frame grayscale mean of adjust_contrast).  Asynchronous on `stream`. */
-int r50_op_color_jitter_u8(const void* frames_u8, int t, int hw, const int* order4_host, float brightness, float contrast,
+int r50_op_color_jitter_u8(const void* R50_ALIGNED(1) frames_u8, int t, int hw, const int* order4_host, float brightness, float contrast,
                            float saturation, float hue, int normalize, float* out_f32, float* scratch_means, void* stream);
 
 /* Lifting head, forward (first step): the non-GEMM pieces of `PHDFor3DJoints.forward` (src/model.py:146-178);
@@ -349,20 +374,23 @@ int r50_op_color_jitter_u8(const void* frames_u8, int t, int hw, const int* orde
  *  r50_op_gn_relu_causal3: x (b,t,c) element -> GroupNorm(groups, eps) + ReLU (`ResidualBlock`, :47-55) -> the input rows of
  *    the following `CausalConv1d` (kernel 3, replicate left padding, :20-35): out (b*t, 3c), row (b,t) =
  *    [y(t-2) | y(t-1) | y(t)] with indices clamped at 0.
- *  r50_op_add_rows: y (rows,ny) fp32 += dy (rows,dp) element, first ny columns (`y = y + dy`, :114-115). */
-int r50_op_cast_rows(const float* src_f32, int64_t rows, int c, void* dst, int cpad, int et, void* stream);
-int r50_op_concat_pad(const void* phi, int d, const float* y_f32, int ny, int64_t rows, void* dst, int dp, int et, void* stream);
-int r50_op_add_rows(float* y_f32, int ny, const void* dy, int dp, int64_t rows, int et, void* stream);
-int r50_op_gn_relu_causal3(const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta, float eps,
-                           void* out, int et, void* stream);
+ *  r50_op_add_rows: y (rows,ny) fp32 += dy (rows,dp) element, first ny columns (`y = y + dy`, :114-115).
+ * Alignment: these kernels, and the element-wise, GroupNorm and reduction ops of the training step below, read and write 16-bit tensors
+ * one element at a time (R50_ALIGNED(2)) -- except r50_op_cast_rows, which stores one 4-byte pair per two columns: dst is
+ * R50_ALIGNED(4), and cpad is even so that every row of dst starts on a 4-byte boundary too. */
+int r50_op_cast_rows(const float* src_f32, int64_t rows, int c, void* R50_ALIGNED(4) dst, int cpad, int et, void* stream);
+int r50_op_concat_pad(const void* R50_ALIGNED(2) phi, int d, const float* y_f32, int ny, int64_t rows, void* R50_ALIGNED(2) dst, int dp, int et, void* stream);
+int r50_op_add_rows(float* y_f32, int ny, const void* R50_ALIGNED(2) dy, int dp, int64_t rows, int et, void* stream);
+int r50_op_gn_relu_causal3(const void* R50_ALIGNED(2) x, int b, int t, int c, int groups, const float* gamma, const float* beta, float eps,
+                           void* R50_ALIGNED(2) out, int et, void* stream);
 
 /* Lifting head, autoregressive rollout: f_AR over a TIME-MAJOR sequence that grows by one frame per step.
  *  r50_op_gn_relu_causal3_tm: r50_op_gn_relu_causal3 on x (t,b,c) time-major, statistics over all t rows of each sample and
  *    group, emitting only the rows t' in [t0, t): out ((t-t0)*b, 3c), row (t'-t0)*b + b' = [y(t'-2) | y(t'-1) | y(t')] of sample b',
  *    indices clamped at 0.  0 <= t0 < t.  With t0 = 0 the values are bit-equal to r50_op_gn_relu_causal3 on the batch-major
  *    transpose (same grid, summation order and tree); t0 = t-1 emits the last row of each sample only. */
-int r50_op_gn_relu_causal3_tm(const void* x, int b, int t, int t0, int c, int groups, const float* gamma, const float* beta, float eps,
-                              void* out, int et, void* stream);
+int r50_op_gn_relu_causal3_tm(const void* R50_ALIGNED(2) x, int b, int t, int t0, int c, int groups, const float* gamma, const float* beta, float eps,
+                              void* R50_ALIGNED(2) out, int et, void* stream);
 
 /* Lifting head, backward + optimizer: the training step of `train()` (src/train.py:137-176: fp16 autocast forward, `l3d` MSE
  * loss, GradScaler, AdamW).  Every matrix product of the backward pass (dX = dY W, dW = dY^T X) is an r50_op_conv2d(_f16) launch
@@ -380,18 +408,18 @@ int r50_op_gn_relu_causal3_tm(const void* x, int b, int t, int t0, int c, int gr
  *    of this library saturates instead of producing inf, so that is what an overflowed gradient looks like.
  *  r50_op_adamw: `torch.optim.AdamW` (:389) over flat fp32 p / m / v / g, step >= 1; skipped when found_inf[0] != 0; p16 = the
  *    refreshed 16-bit copy of p the GEMMs read. */
-int r50_op_transpose16(const void* src, int rows, int cols, void* dst, int ld, void* stream);
-int r50_op_mask_scale(void* x, const void* mask_u8, float scale, int64_t n, int et, void* stream);
-int r50_op_relu_bwd(void* dy, const void* act, float scale, int64_t n, int et, void* stream);
-int r50_op_colsum(const void* x, int64_t rows, int cols, int ld, float scale, float* out_f32, int accumulate, int et, void* stream);
+int r50_op_transpose16(const void* R50_ALIGNED(2) src, int rows, int cols, void* R50_ALIGNED(2) dst, int ld, void* stream);
+int r50_op_mask_scale(void* R50_ALIGNED(2) x, const void* R50_ALIGNED(1) mask_u8, float scale, int64_t n, int et, void* stream);
+int r50_op_relu_bwd(void* R50_ALIGNED(2) dy, const void* R50_ALIGNED(2) act, float scale, int64_t n, int et, void* stream);
+int r50_op_colsum(const void* R50_ALIGNED(2) x, int64_t rows, int cols, int ld, float scale, float* out_f32, int accumulate, int et, void* stream);
 int r50_op_colsum_f32(const float* x, int64_t rows, int cols, float scale, float* out_f32, int accumulate, void* stream);
-int r50_op_grad_accum(const void* src, float scale, float* dst_f32, int64_t n, int accumulate, int et, void* stream);
+int r50_op_grad_accum(const void* R50_ALIGNED(2) src, float scale, float* dst_f32, int64_t n, int accumulate, int et, void* stream);
 int r50_op_mse_loss_grad(const float* y, const float* gt, int64_t n, float loss_scale, float* dy, float* loss2, void* stream);
-int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,
-                               float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et, void* stream);
+int r50_op_gn_relu_causal3_bwd(const void* R50_ALIGNED(2) dr, const void* R50_ALIGNED(2) x, int b, int t, int c, int groups, const float* gamma, const float* beta,
+                               float eps, const void* R50_ALIGNED(2) add, void* R50_ALIGNED(2) dx, float* dgamma_part, float* dbeta_part, int et, void* stream);
 int r50_op_check_finite(const float* g, int64_t n, int* found, void* stream);
-int r50_op_check_overflow16(const void* x, int64_t n, int* found, int et, void* stream);
-int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
+int r50_op_check_overflow16(const void* R50_ALIGNED(2) x, int64_t n, int* found, int et, void* stream);
+int r50_op_adamw(float* p, float* m, float* v, const float* g, void* R50_ALIGNED(2) p16, int64_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, const int* found_inf, int et, void* stream);
 
 /* Global-norm gradient clipping and EMA weights: the tail of a step when either is switched on.
@@ -409,9 +437,9 @@ int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_
  *    ema is not NULL, ema[i] += ema_weight * (p_new[i] - ema[i]) (each operation rounded once: the lerp form of
  *    `torch.optim.swa_utils.get_ema_multi_avg_fn`).  With both NULL the bits are r50_op_adamw's.  Skipped as a whole when
  *    found_inf[0] != 0.  g is NOT written: it keeps the unclipped gradient. */
-int r50_op_grad_norm(const float* g, int64_t n, float max_norm, double* part, int n_part, int* found, float* clip2, double* stats4,
+int r50_op_grad_norm(const float* R50_ALIGNED(16) g, int64_t n, float max_norm, double* part, int n_part, int* found, float* clip2, double* stats4,
                      void* stream);
-int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
+int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* R50_ALIGNED(2) p16, int64_t n, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, const int* found_inf, const float* clip, float* ema, float ema_weight, int et,
                           void* stream);
 
@@ -526,7 +554,7 @@ int r50_op_sequence_metrics(const float* fused, const float* gt, const float* sp
  *    operations, each rounded to nearest even.  Needs rows >= 1, 1 <= joints <= 64, no null pointer, out either exactly a or
  *    overlapping neither input; checked before any launch.  The kernel TRUSTS perm: the caller checks on the host that every entry
  *    lies in [0, joints) and that perm[perm[j]] == j.  No atomics: the same bits on every run. */
-int r50_op_gather_window_rows(const float* src_f32, int64_t src_rows, int c, const int* starts, int b, int t, void* dst, int et,
+int r50_op_gather_window_rows(const float* R50_ALIGNED(16) src_f32, int64_t src_rows, int c, const int* starts, int b, int t, void* R50_ALIGNED(16) dst, int et,
                               void* stream);
 int r50_op_merge_mirrored_poses(const float* a, const float* b_mirrored, int64_t rows, int joints, const int* perm, float* out,
                                 void* stream);
@@ -542,8 +570,8 @@ int r50_op_merge_mirrored_poses(const float* a, const float* b_mirrored, int64_t
  * Both reductions sum in a fixed order without atomics: the same bits on every run.  Arguments are checked before any launch. */
 int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,
                                  void* stream);
-int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
-                          void* dar, float* loss_lat, float* row_part, int et, void* stream);
+int r50_op_ar_latent_grad(const void* R50_ALIGNED(16) ar, const void* R50_ALIGNED(16) phi, const float* R50_ALIGNED(16) dphi_hat, int b, int t, int d, float lambda, float loss_scale,
+                          void* R50_ALIGNED(16) dar, float* loss_lat, float* row_part, int et, void* stream);
 
 /* Lifting head, joint training (input_proj, f_movie, f_AR and f_3D under one loss).
  *  r50_op_joint_pose_loss_grad: y, dy (2*b*t, joints, 3) fp32, the regressor's output on [phi ; phi_hat] stacked by rows; gt
@@ -555,7 +583,7 @@ int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat
  *  r50_op_colsum_split: r50_op_colsum's result bit for bit (the same summation order and roundings), its 16 row chains per column
  *    spread over 16 x ceil(cols/64) workgroups with loads in flight, then summed in order by a second launch; part: 16*cols floats
  *    of device scratch.  The joint step's bias gradients, over up to 2*b*t rows. */
-int r50_op_colsum_split(const void* x, int64_t rows, int cols, int ld, float scale, float* part, float* out_f32, int accumulate, int et,
+int r50_op_colsum_split(const void* R50_ALIGNED(2) x, int64_t rows, int cols, int ld, float scale, float* part, float* out_f32, int accumulate, int et,
                         void* stream);
 int r50_op_joint_pose_loss_grad(const float* y, const float* gt, int b, int t, int joints, float lambda_future, float loss_scale, float* dy,
                                 float* out4, void* stream);
@@ -572,13 +600,13 @@ int r50_op_joint_pose_loss_grad(const float* y, const float* gt, int b, int t, i
  *    dfut (k*b, d) fp32 += lambda * 2 (fut - phi) / n_l * loss_scale, n_l = k*b*d; loss_lat[0] = mean (fut - phi)^2; row_part: k*b
  *    floats of device scratch.  d % 8 == 0; fut, phi and dfut 16-byte aligned.
  * The reductions sum in a fixed order without atomics: the same bits on every run.  Arguments are checked before any launch. */
-int r50_op_gn_relu_causal3_tm_bwd(const void* dr, const void* x, int b, int t, int t0, int c, int groups, const float* gamma,
-                                  const float* beta, float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et,
+int r50_op_gn_relu_causal3_tm_bwd(const void* R50_ALIGNED(2) dr, const void* R50_ALIGNED(2) x, int b, int t, int t0, int c, int groups, const float* gamma,
+                                  const float* beta, float eps, const void* R50_ALIGNED(2) add, void* R50_ALIGNED(2) dx, float* dgamma_part, float* dbeta_part, int et,
                                   void* stream);
 int r50_op_rollout_pose_loss_grad(const float* pred, const float* gt, int b, int k, int t_gt, int i0, int joints, float loss_scale,
                                   float* dy, float* loss2, void* stream);
-int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, int t_phi, int i0, int d, float lambda, float loss_scale,
-                               float* dfut, float* loss_lat, float* row_part, int et, void* stream);
+int r50_op_rollout_latent_grad(const void* R50_ALIGNED(16) fut, const void* R50_ALIGNED(16) phi, int b, int k, int t_phi, int i0, int d, float lambda, float loss_scale,
+                               float* R50_ALIGNED(16) dfut, float* loss_lat, float* row_part, int et, void* stream);
 
 /* Lifting head, geometric losses (3D + 2D reprojection + velocity + bone length).
  *  r50_op_geo_pose_loss_grad: y, dy (b*t, joints, 3) fp32 batch-major, gt3d (b,t,joints,3), gt2d (b,t,joints,2), K (b,3,3), all fp32 on
@@ -616,7 +644,8 @@ int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt
  *    score of a pair depends on the two rows' values (and x_norm2[x]) alone, not on the row's position in x, on nq or on the grid.  The
  *    order is ascending by (s, index), the smaller index first at equal s: strict and total.  idx_out (nq, k) int32 and dist2_out
  *    (nq, k) fp32 = max(0, |q|^2 + s), |q|^2 as r50_op_row_norm2 computes it, are WRITTEN.  Needs nq >= 1, 1 <= k <= 8, k <= n <= 2^30,
- *    d % 32 == 0, 32 <= d <= 2048, q and x 16-byte aligned, no null pointer, workspace_bytes >= r50_op_nn_search_workspace of the same
+ *    d % 32 == 0, 32 <= d <= 2048, q and x 16-byte aligned (the workspace 4-byte: fp32 scores and int32 indices), no null pointer,
+ *    workspace_bytes >= r50_op_nn_search_workspace of the same
  *    nq, n, k; all checked before any launch (a refused call touches nothing).  Inputs are taken to be finite.  Per 256 queries two
  *    launches on stream: a persistent kernel sized by the CU budget (the "cu_cap" option) whose workgroups walk database chunks of 32
  *    rows (16 above d = 1024) staged once into LDS by LDS-DMA and keep a running top-k per query, then one wave per query merging the
@@ -633,15 +662,15 @@ int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt
  *    <= 64, 0 <= root < joints, a1 and at least one output; a0 with const_vel; with nn: nn_row, dbj, 1 <= k <= 8, n_db >= 1 and
  *    input_len + pred_len <= t_db; checked before any launch.  The kernel TRUSTS nn_row: the caller guarantees every value lies in
  *    [0, n_db).  One launch, gather form, no atomics. */
-int r50_op_row_norm2(const void* x, int n, int d, int et, float* out, void* stream);
+int r50_op_row_norm2(const void* R50_ALIGNED(16) x, int n, int d, int et, float* out, void* stream);
 size_t r50_op_nn_search_workspace(int nq, int n, int k);
-int r50_op_nn_search(const void* q, int nq, const void* x, int n, int d, int et, const float* x_norm2, int k, int* idx_out, float* dist2_out,
-                     void* workspace, size_t workspace_bytes, void* stream);
+int r50_op_nn_search(const void* R50_ALIGNED(16) q, int nq, const void* R50_ALIGNED(16) x, int n, int d, int et, const float* x_norm2, int k, int* idx_out, float* dist2_out,
+                     void* R50_ALIGNED(4) workspace, size_t workspace_bytes, void* stream);
 int r50_op_baseline_forecasts(const float* a1, const float* a0, const int* nn_row, const float* dbj, int64_t n_db, int b, int k, int t_db,
                               int joints, int root, int input_len, int pred_len, float* const_pose, float* const_vel, float* nn, void* stream);
 
 /* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
-int r50_op_avgpool(const void* x_nhwc_bf16, int n, int hw, int c, float* y_f32, void* stream);
+int r50_op_avgpool(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int hw, int c, float* R50_ALIGNED(16) y_f32, void* stream);
 
 #ifdef __cplusplus
 }

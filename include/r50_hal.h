@@ -12,6 +12,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#ifndef R50_ALIGNED
+#define R50_ALIGNED(n)      /* r50.h, "Pointer alignment": the device pointer that follows must be a multiple of n bytes */
+#endif
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -26,8 +30,8 @@ extern "C" {
  *    h, phi, dh_reg and dh 16-byte aligned, et 0 or 1; checked before any launch (a refused call touches nothing).  Two launches: one
  *    workgroup of 128 per row (16-byte loads and stores, a row touches its own d elements only), then one workgroup adding the rows
  *    in a fixed order.  No atomics: the same bits on every run. */
-int r50_op_hal_latent_grad(const void* h, const void* phi, const float* dh_reg, int64_t rows, int d, float lambda, float loss_scale,
-                           void* dh, float* loss_lat, float* row_part, int et, void* stream);
+int r50_op_hal_latent_grad(const void* R50_ALIGNED(16) h, const void* R50_ALIGNED(16) phi, const float* R50_ALIGNED(16) dh_reg, int64_t rows, int d, float lambda, float loss_scale,
+                           void* R50_ALIGNED(16) dh, float* loss_lat, float* row_part, int et, void* stream);
 
 #ifdef __cplusplus
 }

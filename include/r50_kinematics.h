@@ -46,6 +46,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#ifndef R50_ALIGNED
+#define R50_ALIGNED(n)      /* r50.h, "Pointer alignment": the device pointer that follows must be a multiple of n bytes */
+#endif
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -65,7 +69,7 @@ int r50_op_rest_offsets(const float* x, const int* seq_start, int64_t F, int S, 
  *    LDS budget: 8 (RB + 1) 12 J bytes of fp64 + 4 RB (3 J | 1) bytes of fp32 + 64 bytes of parents <= 64 KiB
  *    (61,536 at J = 64, 60,448 at J = 17). */
 int r50_op_pose_rotations(const float* x, const int* row_seq, int64_t F, int S, int J, const int* edges, int E, const int* frames, int NF,
-                          const double* rest_dirs, const double* sign, const double* rest, float* quat, float* euler, float* rigid,
+                          const double* rest_dirs, const double* sign, const double* rest, float* R50_ALIGNED(16) quat, float* euler, float* rigid,
                           float* resid, int* flags, void* stream);
 
 #ifdef __cplusplus

@@ -23,6 +23,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#ifndef R50_ALIGNED
+#define R50_ALIGNED(n)      /* r50.h, "Pointer alignment": the device pointer that follows must be a multiple of n bytes */
+#endif
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -45,8 +49,8 @@ int r50_track_weight_precision(int in_size, int out_size);
  *    overlapping out in any byte; src_bytes < 1;
  *    t < 1; out_size < 4, > 4096 or not a multiple of 4; an unknown mode; max_ww < 1 or LDS beyond 160 KB; t * out_size >= 2^31.
  *    Asynchronous on `stream`, no host read, no allocation, no atomics: the same bits on every run. */
-int r50_op_crop_resize_boxes_u8(const void* src_u8, int64_t src_bytes, const int64_t* table_dev, int t, int max_ww,
-                                void* out_tchw_u8, void* out_flip_tchw_u8, int out_size, int mode, void* stream);
+int r50_op_crop_resize_boxes_u8(const void* R50_ALIGNED(4) src_u8, int64_t src_bytes, const int64_t* table_dev, int t, int max_ww,
+                                void* R50_ALIGNED(4) out_tchw_u8, void* R50_ALIGNED(4) out_flip_tchw_u8, int out_size, int mode, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,10 @@ Two fills, because neither sees everything:
   0x7B in every byte  large, finite and positive: bf16 / fp32 ~ 1.3e36, fp16 61,280, fp64 ~ 6.5e286, e4m3 352, int32 ~ 2.07e9 (an index far
                       out of range), uint8 123.  It survives ReLU, fmax and fmin.
 
-The front band's length is a multiple of 4096 bytes, so the payload keeps the alignment the allocator gave the arena.
+The front band's length is a multiple of 4096 bytes, so with ``shift=0`` the payload keeps the alignment the allocator gave the arena.
+``shift`` (bytes, a multiple of the element size) moves the payload that far behind the front band -- ``[front band | shift bytes of fill |
+payload | rest of the page(s), fill | back band]`` -- which is how tests/alignment.py places an operand at exactly the least alignment its
+op admits ("Pointer alignment").  The gap counts as front band for ``bands_of`` / ``assert_bands_intact``.
 """
 from typing import Iterable, Sequence, Tuple
 
@@ -29,35 +32,39 @@ def _round_up(v: int, m: int) -> int:
     return -(-v // m) * m
 
 
-def _place(nbytes: int, fill: int, band: int, device) -> torch.Tensor:
+def _place(nbytes: int, fill: int, band: int, device, shift: int = 0, element_size: int = 1) -> torch.Tensor:
     if band <= 0 or band % PAGE:
         raise ValueError("band length must be a positive multiple of 4096 bytes")
     if fill not in range(256):
         raise ValueError("fill is one byte")
-    return torch.full((band + _round_up(max(nbytes, 1), PAGE) + band,), fill, dtype=torch.uint8, device=device)
+    if shift < 0 or shift % element_size:
+        raise ValueError("shift must be a non-negative multiple of the element size")
+    return torch.full((band + _round_up(max(shift + nbytes, 1), PAGE) + band,), fill, dtype=torch.uint8, device=device)
 
 
-def guarded(t: torch.Tensor, fill: int, band: int = BAND, device=None) -> torch.Tensor:
-    """A contiguous tensor with ``t``'s shape, dtype and bytes (on ``device``, default ``t``'s) between two bands of ``fill`` bytes."""
+def guarded(t: torch.Tensor, fill: int, band: int = BAND, device=None, shift: int = 0) -> torch.Tensor:
+    """A contiguous tensor with ``t``'s shape, dtype and bytes (on ``device``, default ``t``'s) between two bands of ``fill`` bytes, its first
+    byte ``shift`` bytes behind the front band."""
     device = t.device if device is None else torch.device(device)
     src = t.detach().contiguous()
     nbytes = src.numel() * src.element_size()
-    arena = _place(nbytes, fill, band, device)
-    view = arena[band: band + nbytes].view(src.dtype).view(src.shape)
+    arena = _place(nbytes, fill, band, device, shift, src.element_size())
+    view = arena[band + shift: band + shift + nbytes].view(src.dtype).view(src.shape)
     view.copy_(src)
     return view
 
 
-def guarded_empty(shape: Sequence[int], dtype: torch.dtype, fill: int, band: int = BAND, device="cpu") -> torch.Tensor:
-    """An output or workspace of ``shape`` / ``dtype`` between two bands; the payload is pre-filled with ``fill`` as well, so an element the
-    kernel leaves unwritten, or reads before writing it, differs between the fills."""
+def guarded_empty(shape: Sequence[int], dtype: torch.dtype, fill: int, band: int = BAND, device="cpu", shift: int = 0) -> torch.Tensor:
+    """An output or workspace of ``shape`` / ``dtype`` between two bands (``shift`` as in ``guarded``); the payload is pre-filled with ``fill``
+    as well, so an element the kernel leaves unwritten, or reads before writing it, differs between the fills."""
     shape = tuple(int(s) for s in shape)
     numel = 1
     for s in shape:
         numel *= s
-    nbytes = numel * torch.empty((), dtype=dtype).element_size()
-    arena = _place(nbytes, fill, band, torch.device(device))
-    return arena[band: band + nbytes].view(dtype).view(shape)
+    size = torch.empty((), dtype=dtype).element_size()
+    nbytes = numel * size
+    arena = _place(nbytes, fill, band, torch.device(device), shift, size)
+    return arena[band + shift: band + shift + nbytes].view(dtype).view(shape)
 
 
 def bands_of(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

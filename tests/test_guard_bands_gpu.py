@@ -22,9 +22,11 @@ asserted to be at least twice that.  Shapes come from the existing case lists, w
 row whose shape no other test runs carries a `check`, that family's own oracle check with its own bar, applied to the plain run.
 
 What this cannot see: a stray uint8 read under a zero weight (the frame ops' rows are there for the nonzero-weight reads and for the
-writes); misaligned operands (every payload keeps the allocator's alignment); and the activation arena inside an r50_handle: the
+writes); and the activation arena inside an r50_handle: the
 header has no op-level uint8 stem, so uint8 frames reach the stem through r50_forward_u8 alone, where x and out are guarded (at n = 1 and
 n = 3) and the stem's own output and scratch, like every other activation of the network, are the handle's and are not.  tests/test_guard_bands_cpu.py proves the harness on toy kernels and holds this table complete.
+Every payload here keeps the allocator's alignment; operands at the least alignment each op admits are tests/test_alignment_gpu.py's
+(the same rows between the same bands, shifted; DESIGN.md section 4, "Pointer alignment").
 """
 import ctypes
 import functools
