@@ -8,12 +8,12 @@ before any launch.  Here:
   the header reader   ``prototypes()`` parses every prototype of include/r50*.h: per entry point and parameter the pointee size, the
                       annotation and the requirement (the annotation, else the pointee size).  The header is the only source of a
                       requirement: the tests keep no table of their own.
-  the recording proxy ``recording(arena)`` stands in front of the ctypes library for one run (it replaces ``_lib.load_library`` and the
-                      cached ``_lib()`` accessors of the guard-band tables).  It forwards every call and notes, for each integer argument
+  the recording proxy ``recording(arena)`` stands in front of the ctypes library for one run (it replaces ``_lib.load_library``, which the
+                      wrappers and the tables' ``lib()`` of tests/guard_bands.py both call every time).  It forwards every call and notes, for each integer argument
                       that falls inside an arena operand's bytes, (operand, entry point, parameter, offset into the operand, pointer).  So
                       the 200-odd table rows need no annotation of their own: a plain run tells which C parameter each operand is.
   ``requirements``    per operand, the largest requirement over the parameters it was passed as, with the offset it was passed at.
-  ``ShiftedArena``    the interface of ``Arena`` (tests/test_guard_bands_gpu.py); every operand between 0x7B bands, ``shift`` bytes behind
+  ``ShiftedArena``    the interface of ``Arena`` (tests/guard_bands.py); every operand between 0x7B bands, ``shift`` bytes behind
                       the front band (tests/guard_bands.py).  mode "least": the pointer the op receives is an odd multiple of its
                       requirement A (p % A == 0 and p % 2A == A; the odd multiple cycles 1, 3, 5, 7 over a row's operands, for A = 1 the
                       shift cycles 1, 2, 3), asserted afterwards on what the proxy saw.  mode "below": one victim operand sits A/2 off an
@@ -166,35 +166,19 @@ class RecordingLib:
         return call
 
 
-def _accessors():
-    """The cached ``_lib()`` accessors of the guard-band table modules: (module, attribute) of every lru_cache'd module-level function that
-    returns ``load_library()``."""
-    import sys
-    found = []
-    for mod_name, mod in list(sys.modules.items()):
-        if not mod_name.startswith("tests.") or mod is None:
-            continue
-        for attr, val in list(vars(mod).items()):
-            inner = getattr(val, "__wrapped__", None)
-            if inner is not None and hasattr(val, "cache_clear") and "load_library" in getattr(inner, "__code__", type("c", (), {"co_names": ()})).co_names:
-                found.append((mod, attr))
-    return found
-
-
 @contextlib.contextmanager
 def recording(arena, stop_at: Optional[str] = None, lib=None):
-    """For the duration: every path to the library (``_lib.load_library`` and the tables' accessors) gives a ``RecordingLib`` on ``arena``."""
+    """For the duration ``_lib.load_library`` gives a ``RecordingLib`` on ``arena``: the one path to the library, for the Python wrappers
+    and for the tables' ``lib()`` (tests/guard_bands.py) alike."""
     from implementation_phd_lab_vision_amd import _lib as L
     real = L.load_library() if lib is None else lib
     proxy = RecordingLib(real, arena, stop_at)
-    saved = [(L, "load_library", L.load_library)] + [(m, a, getattr(m, a)) for m, a in _accessors()]
+    saved = L.load_library
     try:
-        for obj, attr, _old in saved:
-            setattr(obj, attr, lambda proxy=proxy: proxy)
+        L.load_library = lambda: proxy
         yield proxy
     finally:
-        for obj, attr, old in saved:
-            setattr(obj, attr, old)
+        L.load_library = saved
 
 
 class Requirement(NamedTuple):
@@ -236,7 +220,7 @@ def displaced(pointer: int, a: int) -> bool:
 
 
 def make_shifted_arena(base, device):
-    """``ShiftedArena`` over ``base`` (the ``Arena`` class of tests/test_guard_bands_gpu.py; a CPU stand-in in tests/test_alignment_cpu.py)."""
+    """``ShiftedArena`` over ``base`` (the ``Arena`` class of tests/guard_bands.py; a CPU stand-in in tests/test_alignment_cpu.py)."""
 
     class ShiftedArena(base):
         def __init__(self, reqs: Dict[str, Requirement], mode: str = "least", victim: Optional[str] = None, fill: int = G.FILL_BIG):

@@ -488,7 +488,7 @@ def fp8_case(case, regime: str):
     e4m3) and its rounding point, in units of sy.  wide: the scale sx sw / sy puts the outputs' std near 250, so that part of them
     saturates at 448 and the rest is spread over the binades where e4m3 rounds; small: every output is an integer up to 16.
     low: ``fp8_low_case``."""
-    from tests.test_kernels_gpu import fp8_reference
+    from tests.kernel_cases import fp8_reference
     if regime == "low":
         return fp8_low_case(case)
     n, h, w, cin, cout, k, stride, pad, relu, has_res, _tile = case
@@ -526,7 +526,7 @@ def fp8_low_case(case):
     ``lattice``'s sparse draw with about two non-zero products per output (the small regime's way to stay in range).  sr / sy = 2^-3
     puts the residual on the same 2^-12; the bias is on it as well, and channel 0's bias adds 1.25 sy, a column of outputs in e4m3's
     normal range (|v| in [1, 2): step 2^-3)."""
-    from tests.test_kernels_gpu import fp8_reference
+    from tests.kernel_cases import fp8_reference
     n, h, w, cin, cout, k, stride, pad, relu, has_res, _tile = case
     g = torch.Generator().manual_seed(seed_of("fp8", case, "low"))
     kk = cin * k * k

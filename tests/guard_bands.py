@@ -17,7 +17,8 @@ The front band's length is a multiple of 4096 bytes, so with ``shift=0`` the pay
 payload | rest of the page(s), fill | back band]`` -- which is how tests/alignment.py places an operand at exactly the least alignment its
 op admits ("Pointer alignment").  The gap counts as front band for ``bands_of`` / ``assert_bands_intact``.
 """
-from typing import Iterable, Sequence, Tuple
+import functools
+from typing import Callable, Iterable, NamedTuple, Sequence, Tuple
 
 import torch
 
@@ -25,7 +26,7 @@ FILL_NAN = 0xFF
 FILL_BIG = 0x7B
 FILLS = (FILL_NAN, FILL_BIG)
 PAGE = 4096
-BAND = 4 << 20          # bytes per band; tests/test_guard_bands_gpu.py asserts per case that this is twice what the kernel could reach
+BAND = 4 << 20          # bytes per band; ``Arena.reach`` asserts per row that this is twice what the kernel could reach
 
 
 def _round_up(v: int, m: int) -> int:
@@ -119,3 +120,174 @@ def holds_fill(t: torch.Tensor, fill: int) -> int:
     size = t.element_size()
     pat = torch.full((size,), fill, dtype=torch.uint8).view(_INT_OF_SIZE[size])[0]
     return int((bits(t) == pat.to(t.device)).sum())
+
+
+# ---- the row catalogue's harness: what a table module of tests/rows/ is written with, and what every harness runs its rows through
+DEV = "cuda:0"
+BF, HF, F32, F64, I32, U8 = torch.bfloat16, torch.float16, torch.float32, torch.float64, torch.int32, torch.uint8
+
+
+@functools.lru_cache(maxsize=None)
+def _built():
+    from implementation_phd_lab_vision_amd import _lib as L
+    L.build_library()          # once per process: it hashes the sources
+    return L
+
+
+def lib():
+    """The library, built once per process.  ``load_library`` is looked up on every call (it caches the handle itself), so that
+    tests/alignment.py's ``recording`` can stand in front of it by replacing that one name."""
+    return _built().load_library()
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def ok(rc, what):
+    assert rc == 0, f"{what}: {lib().r50_last_error(None)}"
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class Row(NamedTuple):
+    family: str
+    id: str
+    ops: Tuple[str, ...]
+    make: Callable          # () -> payloads (built once per row, shared by the three runs, never modified)
+    launch: Callable        # (arena, payloads) -> None
+    check: Callable = None  # (plain arena, payloads) -> None: the family's own oracle check, for a shape no other test runs
+    scrub: Callable = None  # (payloads) -> None: for a row with state of its own (a backbone handle): overwrite what a run leaves in it
+
+
+class Arena:
+    """The operands of one run: plain tensors (fill None) or guarded ones."""
+
+    def __init__(self, fill):
+        self.fill = fill
+        self.operands = []          # (name, tensor): everything whose bands are checked
+        self.results = {}           # name -> tensor: outputs and in-outs, compared across the runs
+        self.defined = {}           # name -> True where the op defines every element
+        self.reached = 0
+
+    def _put(self, name, t):
+        assert name not in dict(self.operands), f"operand name {name} used twice"
+        self.operands.append((name, t))
+        return t
+
+    def inp(self, name, t):
+        if self.fill is None:
+            return self._put(name, t.detach().to(DEV, copy=True).contiguous())
+        g = guarded(t, self.fill, device=DEV)
+        assert g.is_cuda and g.storage_offset() * g.element_size() == BAND and g.data_ptr() % 256 == 0, f"`{name}`: {g.device}, at {g.data_ptr():#x}"
+        return self._put(name, g)
+
+    def inout(self, name, t):
+        self.results[name] = self.inp(name, t)
+        return self.results[name]
+
+    def out(self, name, shape, dtype, defined=True):
+        if self.fill is None:
+            t = torch.zeros(tuple(shape), dtype=U8, device=DEV).view(dtype) if dtype == torch.float8_e4m3fn else \
+                torch.zeros(tuple(shape), dtype=dtype, device=DEV)
+        else:
+            t = guarded_empty(shape, dtype, self.fill, device=DEV)
+        self.results[name] = self._put(name, t)
+        self.defined[name] = defined
+        return t
+
+    def ws(self, name, shape, dtype):
+        if self.fill is None:
+            return self._put(name, torch.zeros(tuple(shape), dtype=dtype, device=DEV))
+        return self._put(name, guarded_empty(shape, dtype, self.fill, device=DEV))
+
+    def host_check(self, fn):
+        """A look at a result on the host in the middle of a row.  Here: at once.  (tests/stream_order.py's arena puts it off until its run
+        is over, so that the look does not hold the host.)"""
+        fn()
+
+    def between_calls(self, fn):
+        """Between two calls of a row that go through one stateful object on the same inputs.  Here: nothing (each run is compared with the
+        others as a whole).  tests/stream_order.py's arena runs ``fn``, which puts another batch through the object."""
+
+    def reach(self, nbytes):
+        """How far (bytes) this call's unchecked address arithmetic could land off an operand; the band must be twice that."""
+        self.reached = max(self.reached, int(nbytes))
+        assert BAND >= 2 * int(nbytes), f"guard band of {BAND} bytes is less than twice the reach {nbytes}"
+
+
+def _checks_fill(t, fill):
+    """Element sizes of two bytes and more: no legitimate output is the all-fill pattern.  One byte: only e4m3's NaN."""
+    return t.element_size() >= 2 or (t.dtype == torch.float8_e4m3fn and fill == FILL_NAN)
+
+
+def close_payloads(payloads) -> None:
+    for v in payloads if isinstance(payloads, tuple) else ():
+        if hasattr(v, "close"):
+            v.close()              # a backbone handle
+
+
+def run_row(row):
+    payloads = row.make()
+    try:
+        _three_runs(row, payloads)
+    finally:
+        close_payloads(payloads)
+
+
+def _three_runs(row, payloads):
+    runs = {}
+    for fill in (None,) + FILLS:
+        a = Arena(fill)
+        row.launch(a, payloads)
+        torch.cuda.synchronize()
+        assert a.reached > 0, f"{row.id}: the row does not state its reach"
+        what = f"{row.id} fill {'plain' if fill is None else hex(fill)}"
+        if fill is not None:
+            assert_bands_intact(a.operands, fill, what)
+            for name, t in a.results.items():
+                if a.defined.get(name) and _checks_fill(t, fill):
+                    n = holds_fill(t, fill)
+                    assert n == 0, f"{what}: {n} of {t.numel()} elements of output `{name}` still hold the fill pattern"
+        runs[fill] = a
+    plain = runs[None]
+    assert plain.results, f"{row.id}: no output"
+    if row.check is not None:
+        row.check(plain, payloads)
+    for fill in FILLS:
+        assert list(runs[fill].results) == list(plain.results), \
+            f"{row.id} fill {fill:#x}: results {list(runs[fill].results)}, the plain run's {list(plain.results)}"
+        for name, t in runs[fill].results.items():
+            a, b = bits(t), bits(plain.results[name])
+            if not torch.equal(a, b):
+                bad = torch.nonzero((a != b).view(-1))
+                raise AssertionError(f"{row.id} fill {fill:#x}: `{name}` differs from the plain run in {bad.numel()} of {a.numel()} "
+                                     f"elements, the first at flat index {int(bad[0])}")
+
+
+# ---- toy "kernels" in plain torch on ``as_strided`` views: what the harness is proved on (tests/test_guard_bands_cpu.py on the CPU,
+# tests/test_guard_bands_gpu.py on device arenas)
+def _shifted(x: torch.Tensor, by: int) -> torch.Tensor:
+    """x's window moved by `by` elements: the view an index mistake of that size reads or writes."""
+    return x.as_strided(x.shape, x.stride(), x.storage_offset() + by)
+
+
+def _toy_reads_one_before(x, out):
+    """y[i] = x[i] + 1 * x[i-1] over the whole operand: at i = 0 it reads one element in front of x."""
+    out.copy_(x + _shifted(x, -1))
+
+
+def _toy_reads_one_before_then_relu(x, out):
+    """The same, then ReLU the way the kernels' fmax treats NaN: max(NaN, 0) = 0."""
+    v = x + _shifted(x, -1)
+    out.copy_(torch.where(torch.isnan(v), torch.zeros_like(v), v).clamp_min(0))
+
+
+def _toy_writes_one_past(x, out):
+    _shifted(out, 1).copy_(x)
+    out[0] = x[0]
+
+
+PAYLOAD = torch.tensor([-1.5, 2.0, 0.25, -3.0, 7.0])       # x[0] < 0: the true pre-activation of y[0] is negative

@@ -4,7 +4,7 @@ tests/test_repeatability_cpu.py.
 DESIGN.md, include/r50*.h and the kernel comments promise "the same bits on every run".  Every other test launches a row once on an idle
 chip, synchronises and compares: a wait count one stage short, or a barrier on the wrong side of a fragment read, gives the right bits
 whenever the LDS-DMA happens to land in time, which on an idle chip with one launch in flight is nearly always.  Here a row of the
-guard-band tables (``ALL_ROWS`` of tests/test_alignment_gpu.py: ``make`` / ``launch`` / ``scrub``) runs R times per mode and every run is
+guard-band tables (``ALL_ROWS`` of tests/rows/: ``make`` / ``launch`` / ``scrub``) runs R times per mode and every run is
 held, bit for bit, to the plain run -- the run every other test holds to its fp64 or oracle reference, so bit equality carries those bars
 over and no shape or tolerance of its own enters.
 
@@ -60,7 +60,6 @@ and the CPU test holds that list to the source as well.
 What this cannot see: a race whose window none of the four modes opens; the contention of a D2H copy or an RCCL gather; and the cap on
 workgroups (tests/test_work_distribution_gpu.py) combined with noise.
 """
-import functools
 import re
 import threading
 import time
@@ -70,10 +69,10 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from tests import guard_bands as G
+from tests.guard_bands import DEV, Arena
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "implementation_phd_lab_vision_amd" / "csrc"
-DEV = "cuda:0"
 
 MODES = ("quiet", "noise_mem", "noise_mfma", "twin")
 NOISE_MODES = ("noise_mem", "noise_mfma")
@@ -289,91 +288,75 @@ def enough_overlap(flags: Sequence[bool]) -> bool:
 # ------------------------------------------------------------------------------------------------------------------------------
 # arenas (GPU; nothing below runs at import)
 # ------------------------------------------------------------------------------------------------------------------------------
-def _arena_base():
-    from tests.test_guard_bands_gpu import Arena
-    return Arena
+class SpecArena(Arena):
+    """The plain run (ordinary tensors) that also notes every operand the row asks for, in order."""
+
+    def __init__(self):
+        super().__init__(None)
+        self.spec = []                      # (kind, name, payload | (shape, dtype))
+
+    def inp(self, name, t):
+        self.spec.append(("inp", name, t))
+        return super().inp(name, t)
+
+    def inout(self, name, t):
+        r = super().inout(name, t)          # goes through ``inp``
+        self.spec[-1] = ("inout", name, t)
+        return r
+
+    def out(self, name, shape, dtype, defined=True):
+        self.spec.append(("out", name, (tuple(int(v) for v in shape), dtype)))
+        return super().out(name, shape, dtype, defined)
+
+    def ws(self, name, shape, dtype):
+        self.spec.append(("ws", name, (tuple(int(v) for v in shape), dtype)))
+        return super().ws(name, shape, dtype)
 
 
-@functools.lru_cache(maxsize=None)
-def _arena_classes():
-    Arena = _arena_base()
+class ReplayArena(Arena):
+    """One run's operands, all built at construction from a ``SpecArena``'s list: between 0xFF bands, outputs and workspaces
+    pre-filled with 0xFF.  ``row.launch`` finds them by name; nothing is copied or allocated while it runs."""
 
-    class SpecArena(Arena):
-        """The plain run (ordinary tensors) that also notes every operand the row asks for, in order."""
+    def __init__(self, spec):
+        super().__init__(G.FILL_NAN)
+        self.ready = {}
+        for kind, name, v in spec:
+            assert name not in self.ready, f"operand name {name} used twice"
+            if kind in ("inp", "inout"):
+                self.ready[name] = (kind, G.guarded(v, self.fill, device=DEV))
+            else:
+                self.ready[name] = (kind, G.guarded_empty(v[0], v[1], self.fill, device=DEV))
+        self._deferred = []
 
-        def __init__(self):
-            super().__init__(None)
-            self.spec = []                      # (kind, name, payload | (shape, dtype))
+    def _take(self, kind, name, shape, dtype):
+        assert name in self.ready, f"the row asked for operand `{name}`, which its plain run did not (or asked twice)"
+        had, t = self.ready.pop(name)
+        assert had == kind and tuple(t.shape) == tuple(int(v) for v in shape) and t.dtype == dtype, \
+            f"operand `{name}`: {kind} {tuple(shape)} {dtype} now, {had} {tuple(t.shape)} {t.dtype} in the plain run"
+        return self._put(name, t)
 
-        def inp(self, name, t):
-            self.spec.append(("inp", name, t))
-            return super().inp(name, t)
+    def inp(self, name, t):
+        return self._take("inp", name, t.shape, t.dtype)
 
-        def inout(self, name, t):
-            r = super().inout(name, t)          # goes through ``inp``
-            self.spec[-1] = ("inout", name, t)
-            return r
+    def inout(self, name, t):
+        self.results[name] = self._take("inout", name, t.shape, t.dtype)
+        return self.results[name]
 
-        def out(self, name, shape, dtype, defined=True):
-            self.spec.append(("out", name, (tuple(int(v) for v in shape), dtype)))
-            return super().out(name, shape, dtype, defined)
+    def out(self, name, shape, dtype, defined=True):
+        self.results[name] = self._take("out", name, shape, dtype)
+        self.defined[name] = defined
+        return self.results[name]
 
-        def ws(self, name, shape, dtype):
-            self.spec.append(("ws", name, (tuple(int(v) for v in shape), dtype)))
-            return super().ws(name, shape, dtype)
+    def ws(self, name, shape, dtype):
+        return self._take("ws", name, shape, dtype)
 
-    class ReplayArena(Arena):
-        """One run's operands, all built at construction from a ``SpecArena``'s list: between 0xFF bands, outputs and workspaces
-        pre-filled with 0xFF.  ``row.launch`` finds them by name; nothing is copied or allocated while it runs."""
+    def host_check(self, fn):
+        self._deferred.append(fn)           # a look on the host would hold it in the middle of the window
 
-        def __init__(self, spec):
-            super().__init__(G.FILL_NAN)
-            self.ready = {}
-            for kind, name, v in spec:
-                assert name not in self.ready, f"operand name {name} used twice"
-                if kind in ("inp", "inout"):
-                    self.ready[name] = (kind, G.guarded(v, self.fill, device=DEV))
-                else:
-                    self.ready[name] = (kind, G.guarded_empty(v[0], v[1], self.fill, device=DEV))
-            self._deferred = []
-
-        def _take(self, kind, name, shape, dtype):
-            assert name in self.ready, f"the row asked for operand `{name}`, which its plain run did not (or asked twice)"
-            had, t = self.ready.pop(name)
-            assert had == kind and tuple(t.shape) == tuple(int(v) for v in shape) and t.dtype == dtype, \
-                f"operand `{name}`: {kind} {tuple(shape)} {dtype} now, {had} {tuple(t.shape)} {t.dtype} in the plain run"
-            return self._put(name, t)
-
-        def inp(self, name, t):
-            return self._take("inp", name, t.shape, t.dtype)
-
-        def inout(self, name, t):
-            self.results[name] = self._take("inout", name, t.shape, t.dtype)
-            return self.results[name]
-
-        def out(self, name, shape, dtype, defined=True):
-            self.results[name] = self._take("out", name, shape, dtype)
-            self.defined[name] = defined
-            return self.results[name]
-
-        def ws(self, name, shape, dtype):
-            return self._take("ws", name, shape, dtype)
-
-        def host_check(self, fn):
-            self._deferred.append(fn)           # a look on the host would hold it in the middle of the window
-
-        def finish(self):
-            assert not self.ready, f"operands of the plain run that this run never asked for: {sorted(self.ready)}"
-            for fn in self._deferred:
-                fn()
-
-    return SpecArena, ReplayArena
-
-
-def close_payloads(payloads) -> None:
-    for v in payloads if isinstance(payloads, tuple) else ():
-        if hasattr(v, "close"):
-            v.close()                           # a backbone handle
+    def finish(self):
+        assert not self.ready, f"operands of the plain run that this run never asked for: {sorted(self.ready)}"
+        for fn in self._deferred:
+            fn()
 
 
 def carries_state(row, payloads) -> bool:
@@ -382,7 +365,6 @@ def carries_state(row, payloads) -> bool:
 
 def plain_run(row, payloads):
     """The plain run on the current (default) stream: the ``SpecArena`` with the reference bits and the operand list."""
-    SpecArena, _ = _arena_classes()
     plain = SpecArena()
     row.launch(plain, payloads)
     torch.cuda.synchronize()
@@ -398,7 +380,6 @@ def _event():
 
 def timed_run(row, payloads, spec) -> Tuple[float, float]:
     """(device ms between events around one replayed run on the default stream, host ms ``row.launch`` took)."""
-    _, ReplayArena = _arena_classes()
     a = ReplayArena(spec)
     torch.cuda.synchronize()
     s, e = _event(), _event()
@@ -486,7 +467,7 @@ def burst_ms(lib, rows) -> float:
             plain = plain_run(row, payloads)
             dev_ms, _host = timed_run(row, payloads, plain.spec)
         finally:
-            close_payloads(payloads)
+            G.close_payloads(payloads)
         _SESSION["burst"] = max(NOISE_MS, BURST_FACTOR * dev_ms)
         print(f"repeatability: {row.id} takes {dev_ms:.3f} ms on the device; a noise burst lasts {_SESSION['burst']:.2f} ms")
     return _SESSION["burst"]
@@ -500,7 +481,6 @@ class Runs(NamedTuple):
 
 
 def run_quiet(row, payloads, spec, reps) -> Runs:
-    _, ReplayArena = _arena_classes()
     arenas = [ReplayArena(spec) for _ in range(reps)]
     torch.cuda.synchronize()
     for a in arenas:
@@ -513,7 +493,6 @@ def run_quiet(row, payloads, spec, reps) -> Runs:
 
 
 def run_noisy(row, payloads, spec, reps, mode, lib, burst) -> Runs:
-    _, ReplayArena = _arena_classes()
     side, beside = streams(lib)
     noise = noise_for(mode, lib)
     arenas = [ReplayArena(spec) for _ in range(reps)]
@@ -559,7 +538,6 @@ def run_twin(row, payloads, payloads2, spec, reps, lib, host_ms, two_threads=Fal
     whose op synchronises the host before it launches: one thread would enqueue the second copy only when the first has left its
     synchronisation and launched, that is when the first copy is all but over."""
     from tests import stream_order as SO
-    _, ReplayArena = _arena_classes()
     sa, sb = streams(lib)
     pairs = [(ReplayArena(spec), ReplayArena(spec)) for _ in range(reps)]
     gate = max(1, int(SO.calibrate(1.0) * (GATE_MS + 1.5 * 2 * host_ms + (THREAD_GATE_MS if two_threads else 0.0))))

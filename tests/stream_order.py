@@ -1,9 +1,10 @@
-"""Ops on a side stream with late inputs -- test infrastructure for tests/test_stream_order_gpu.py.
+"""Ops on a side stream with late inputs -- test infrastructure for tests/test_stream_order_gpu.py and the per-header
+tests/test_*_stream_order_gpu.py.
 
 Every other op test runs on the legacy null stream with inputs that were complete before the call, and synchronises the device before it
 looks.  That hides a launch that ignores its ``stream`` argument (it lands on the stream the test uses anyway), a fork to an internal
 non-blocking stream without its event, and a host synchronisation inside an op.  ``LateArena`` has the interface of ``Arena`` in
-tests/test_guard_bands_gpu.py, so every ``launch(arena, payloads)`` of the guard-band tables runs unchanged, but:
+tests/guard_bands.py, so every ``launch(arena, payloads)`` of the guard-band tables runs unchanged, but:
 
   * the row runs on a side stream ``S`` of torch's pool (``with torch.cuda.stream(S)``);
   * every input is NOT there yet when the op is enqueued: the operand holds a stale value (NaN in every float format, 255 as uint8, 0 in
@@ -26,16 +27,19 @@ Measured on an MI355X, one session, host time from the first ``inp`` to ``launch
 the slowest is head_gemm row ``fp16-dw_m1024_k64_n3072`` with 2.37 ms (three igemm tiles, staging included); every other row is below
 2.3 ms.  Four times that is 9.5 ms, so the sleep stays at the 50 ms it started with (21 times the slowest row; the cap is 200 ms).
 ``choose_stream`` and ``choose_second_stream`` both took the first candidate in that session.  The rows that held the host, each for the
-whole 50 ms, are the three ``BLOCKS_HOST`` of tests/test_stream_order_gpu.py admits: ``resize_frames_u8`` (reads ``src_idx`` back) and
+whole 50 ms, are the three ``BLOCKS_HOST`` below admits: ``resize_frames_u8`` (reads ``src_idx`` back) and
 ``stem-n1`` / ``stem-n3`` (``r50_op_stem`` uploads a host temporary).
 """
 import functools
+import json
+import re
 import time
 
 import torch
 
 from tests import guard_bands as G
-from tests.test_guard_bands_gpu import DEV, Arena
+from tests.guard_bands import DEV, Arena
+from tests.helpers import GOLDEN
 
 U8 = torch.uint8
 INDEX_TYPES = (torch.int32, torch.int64)
@@ -254,3 +258,120 @@ def choose_second_stream(lib):
         else:
             raise AssertionError(f"choose_second_stream: none of {MAX_CANDIDATES} pool streams ran beside the chosen side stream")
     return _CHOSEN["second"]
+
+
+# ---- which rows may hold the host -------------------------------------------------------------------------------------------
+# Rows (by id) or ops (by name: every row that launches it) that may hold the host until the side stream's sleep has ended.  The run on
+# the MI355X added nothing to what reading r50_abi.hip gives: these three rows of 167 held the host (50 ms each, the whole sleep), no other
+# row more than 2.4 ms.  hipMallocAsync / hipFreeAsync in r50_op_bneck_tail and r50_op_bneck_cat_chain do not hold it.
+BLOCKS_HOST = {
+    "r50_op_resize_frames_u8": "copies src_idx to the host and synchronises the stream before it launches",
+    "r50_op_stem": "uploads the packed host weights and synchronises the stream (the packed image is a host temporary)",
+}
+
+# backbone_launch_plan.json counts launches by kind; the op-level entry point(s) of each kind.  "conv1" and "stem_pack" are the stem's two
+# kernels, which r50_forward launches from the handle's resident weights: the op-level r50_op_stem is a test entry point that packs and uploads
+# host weights on every call, and no per-step path calls it.
+PLAN_KIND_OPS = {"avgpool": ("r50_op_avgpool",), "bneck_block2": ("r50_op_bneck_block2",), "bneck_catchain": ("r50_op_bneck_cat_chain",),
+                 "bneck_tail": ("r50_op_bneck_tail",), "bneck_tail3": ("r50_op_bneck_tail",), "conv1": (), "stem_pack": (),
+                 "igemm": ("r50_op_conv2d", "r50_op_conv2d_f16", "r50_op_conv2d_w2", "r50_op_conv2d_split", "r50_op_conv2d_fp8", "r50_op_conv1x1_cat",
+                           "r50_op_bneck_block1", "r50_op_bneck_block1_ds"),
+                 "maxpool": ("r50_op_maxpool",)}
+
+
+def hot_path_ops():
+    """The ops of the per-step hot paths: every op a recorded train step launches (the fp16 head's GEMMs are recorded under
+    ``r50_op_conv2d``), every launch kind of the backbone's plan, and the forward itself."""
+    train = json.loads((GOLDEN / "train_launch_sequences.json").read_text())
+    ops = {re.match(r"r50_op_\w+", what).group(0) for seq in train["sequences"].values() for what in seq}
+    ops.add("r50_op_conv2d_f16")
+    plan = json.loads((GOLDEN / "backbone_launch_plan.json").read_text())
+    kinds = {k for prec in plan["plans"].values() for entry in prec.values() for k in entry["launches"]}
+    assert kinds <= set(PLAN_KIND_OPS), f"launch kinds without an op: {sorted(kinds - set(PLAN_KIND_OPS))}"
+    for k in kinds:
+        ops.update(PLAN_KIND_OPS[k])
+    return ops | {"r50_forward", "r50_forward_u8"}
+
+
+def may_block(row):
+    return row.id in BLOCKS_HOST or any(op in BLOCKS_HOST for op in row.ops)
+
+
+def check_blocking_table(rows):
+    """The conditions on ``BLOCKS_HOST`` over ``rows``, the rows that run late (also asserted without a GPU by tests/test_stream_order_cpu.py)."""
+    ids, ops = {row.id for row in rows}, {op for row in rows for op in row.ops}
+    for key, reason in BLOCKS_HOST.items():
+        assert key in ids or key in ops, f"BLOCKS_HOST names `{key}`, which is neither a row nor an op of a row"
+        assert reason.strip(), f"BLOCKS_HOST[{key}] gives no reason"
+    hot = hot_path_ops()
+    listed = [row for row in rows if may_block(row)]
+    for row in listed:
+        bad = sorted(set(row.ops) & hot)
+        assert not bad, f"BLOCKS_HOST admits row {row.id}, which launches hot-path op(s) {bad}: an op of a per-step path must not hold the host"
+    assert len(listed) * 10 <= len(rows), f"BLOCKS_HOST admits {len(listed)} of {len(rows)} rows: more than 10 %"
+
+
+# ---- the runners: a row, and a Python entry point, late on the side stream against the default stream -----------------------
+def run_row_late(row):
+    side, _ = choose_stream(G.lib())
+    payloads = row.make()
+    try:
+        plain = Arena(None)
+        row.launch(plain, payloads)
+        torch.cuda.synchronize()
+        if row.scrub is not None:
+            row.scrub(payloads)        # a handle's buffers must not still hold what these very payloads left there
+        late = LateArena(side, calibrate())
+        with torch.cuda.stream(side):
+            row.launch(late, payloads)
+            late.finish()
+    finally:
+        G.close_payloads(payloads)
+    print(f"stream_order row {row.id}: host {late.enqueue_ms:.2f} ms from the first inp to launch returning, blocked {late.blocked}")
+    assert plain.results and list(late.results) == list(plain.results), f"{row.id}: result names differ between the runs"
+    for name, want in plain.results.items():
+        assert_same_bits(row.id, name, "snapshot", late.snapshots[name], want)
+        assert_same_bits(row.id, name, "final tensor", late.results[name], want)
+        if late.defined.get(name) and G._checks_fill(want, late.fill):
+            n = G.holds_fill(late.snapshots[name], late.fill)
+            assert n == 0, f"{row.id}: {n} of {want.numel()} elements of output `{name}` still hold the poison in the snapshot"
+    if late.blocked and not may_block(row):
+        raise AssertionError(f"{row.id}: the host was held until the side stream's sleep had ended ({late.enqueue_ms:.1f} ms): either it "
+                             "synchronises the host, or the sleep is too short: see calibrate()")
+    if may_block(row) and not late.blocked:
+        raise AssertionError(f"{row.id}: listed in BLOCKS_HOST, but it did not hold the host: the entry is stale")
+
+
+def _tensors_of(result):
+    """name -> tensor for whatever a wrapper returned: a tensor, a tuple of tensors (None entries left out) or a dict."""
+    if isinstance(result, torch.Tensor):
+        return {"result": result}
+    if isinstance(result, dict):
+        return {str(k): v for k, v in result.items() if isinstance(v, torch.Tensor)}
+    return {f"result[{i}]": v for i, v in enumerate(result) if isinstance(v, torch.Tensor)}
+
+
+def side_against_default(what, call, inputs, scrub=None):
+    """``call(late, tensors)`` once on the default stream (late = None) and once under ``with torch.cuda.stream(S)`` (late = the ``LateArena``)
+    with every tensor of ``inputs`` produced late on ``S``: behind the sleep, by a device copy from staging.  Whatever tensors it returns are
+    snapshot on ``S`` right after the call; snapshot bits == final bits == default-stream bits.  Returns the late arena (``blocked`` tells
+    whether the wrapper held the host, which a wrapper that reads a result on the host does by design).  ``scrub()`` runs between the two:
+    an object with cached workspaces (a head, a backbone handle) gets another batch, so that a launch which read a workspace too early
+    would not find there what the same inputs left a moment ago."""
+    side, _ = choose_stream(G.lib())
+    want = _tensors_of(call(None, {k: v.to(DEV) for k, v in inputs.items()}))
+    torch.cuda.synchronize()
+    if scrub is not None:
+        scrub()
+        torch.cuda.synchronize()
+    late = LateArena(side, calibrate())
+    with torch.cuda.stream(side):
+        got = _tensors_of(call(late, {k: late.inp(k, v) for k, v in inputs.items()}))
+        late.results.update(got)
+        late.finish()
+    assert want and list(got) == list(want), f"{what}: result names differ between the runs"
+    for name, w in want.items():
+        assert_same_bits(what, name, "snapshot", late.snapshots[name], w)
+        assert_same_bits(what, name, "final tensor", late.results[name], w)
+    print(f"stream_order wrapper {what}: host {late.enqueue_ms:.2f} ms, blocked {late.blocked}")
+    return late

@@ -108,10 +108,10 @@ def test_the_stated_alignments_agree_with_the_annotations():
 
 
 def test_every_entry_point_of_a_table_row_is_declared():
-    from tests import test_alignment_gpu as T
+    from tests.rows import ALL_ROWS
     protos = AL.prototypes()
-    assert len(T.ALL_ROWS) >= 200
-    for row in T.ALL_ROWS:
+    assert len(ALL_ROWS) >= 200
+    for row in ALL_ROWS:
         for op in row.ops:
             assert op in protos, f"row {row.id} names {op}, which no header declares"
             assert any(p.device for p in protos[op]), f"row {row.id}: {op} has no device operand"
@@ -193,7 +193,7 @@ def _toy_run(arena, how):
 
 
 def _cpu_arenas():
-    from tests.test_guard_bands_gpu import Arena
+    from tests.guard_bands import Arena
 
     class CpuArena(Arena):
         def inp(self, name, t):

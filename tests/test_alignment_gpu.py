@@ -1,6 +1,6 @@
 """Every op with every operand at exactly the least alignment its header admits, and refused below it.
 
-The harness is tests/alignment.py (read its docstring first).  Every row of every guard-band table runs
+The harness is tests/alignment.py (read its docstring first).  Every row of every guard-band table (``ALL_ROWS`` of tests/rows/) runs
 
   least    once plainly under the recording proxy -- which yields, from include/r50*.h alone, each operand's requirement A, and the
            reference bits -- and once with every operand between 0x7B bands at an odd multiple of its A (u8 operands, A = 1, at byte shifts
@@ -21,35 +21,16 @@ import torch
 
 from tests import alignment as AL
 from tests import guard_bands as G
-from tests.test_bootstrap_guard_bands_gpu import ROWS_BOOTSTRAP
-from tests.test_frames_domain_gpu import ROWS_FRAMES_DOMAIN
-from tests.test_guard_bands_gpu import DEV, ROWS, Arena, _checks_fill
-from tests.test_hal_guard_bands_gpu import ROWS_HAL
-from tests.test_kinematics_gpu import ROWS_KINEMATICS
-from tests.test_multiview_guard_bands_gpu import ROWS_MULTIVIEW
-from tests.test_refine_gpu import ROWS_REFINE
-from tests.test_resample_guard_bands_gpu import ROWS_RESAMPLE
-from tests.test_smooth_guard_bands_gpu import ROWS_SMOOTH
-from tests.test_track_guard_bands_gpu import ROWS_TRACK
+from tests.guard_bands import DEV, Arena, _checks_fill, close_payloads
+from tests.rows import ALL_ROWS
 
 pytestmark = pytest.mark.gpu
 
-TABLES = (("r50", ROWS), ("hal", ROWS_HAL), ("smooth", ROWS_SMOOTH), ("track", ROWS_TRACK), ("multiview", ROWS_MULTIVIEW),
-          ("resample", ROWS_RESAMPLE), ("bootstrap", ROWS_BOOTSTRAP), ("refine", ROWS_REFINE), ("kinematics", ROWS_KINEMATICS),
-          ("frames_domain", ROWS_FRAMES_DOMAIN))
-ALL_ROWS = [row for _name, table in TABLES for row in table]
-assert len({row.id for row in ALL_ROWS}) == len(ALL_ROWS), "row ids must be unique over the tables"
 R50_ERR_INVALID = -1
 SKIPPED, REFUSED = [], {}        # row ids the refusal test skipped / row id -> operands refused, for the share printed at the end
 
 ShiftedArena = AL.make_shifted_arena(Arena, DEV)
 _rows = pytest.mark.parametrize("row", ALL_ROWS, ids=[r.id for r in ALL_ROWS])
-
-
-def _close(payloads):
-    for v in payloads if isinstance(payloads, tuple) else ():
-        if hasattr(v, "close"):
-            v.close()              # a backbone handle
 
 
 def _plain(row, payloads):
@@ -77,7 +58,7 @@ def test_least_aligned_operands_give_the_plain_bits(row):
             row.launch(least, payloads)
         torch.cuda.synchronize()
     finally:
-        _close(payloads)
+        close_payloads(payloads)
     what = f"{row.id} least-aligned"
     # every operand was in fact displaced, on the pointers the library received
     got = AL.requirements(proxy.seen)
@@ -157,7 +138,7 @@ def test_a_pointer_below_its_alignment_is_refused(row):
                 row.scrub(payloads)
         REFUSED[row.id] = len(victims)
     finally:
-        _close(payloads)
+        close_payloads(payloads)
 
 
 def test_the_share_of_rows_without_a_refusal():

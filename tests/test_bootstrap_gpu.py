@@ -14,7 +14,7 @@ import torch
 
 from tests import bootstrap_reference as BR
 from tests import results_data as rd
-from tests.test_bootstrap_guard_bands_gpu import unit_rows
+from tests.rows.bootstrap import unit_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

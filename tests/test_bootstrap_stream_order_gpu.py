@@ -1,4 +1,4 @@
-"""The rows of tests/test_bootstrap_guard_bands_gpu.py late on a side stream, with the harness of tests/test_stream_order_gpu.py: each row
+"""The rows of tests/rows/bootstrap.py late on a side stream, with the harness of tests/stream_order.py: each row
 runs once plainly on the default stream and once on the side stream while its unit rows and its stratum table are still stale; snapshot
 bits == final bits == plain bits, and the op does not hold the host.  Then the Python entry points: ``bootstrap_sums`` +
 ``statistics_device`` with late unit rows (no host synchronisation at all), and ``evaluate_bootstrap`` with a late feature store: the
@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_bootstrap_guard_bands_gpu import ROWS_BOOTSTRAP, unit_rows
-from tests.test_stream_order_gpu import run_row_late, side_against_default
+from tests.rows.bootstrap import ROWS_BOOTSTRAP, unit_rows
+from tests.stream_order import run_row_late, side_against_default
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -12,6 +12,7 @@ import torch
 
 from tests.clip_ema_reference import ClipAdamWEMA
 from tests.train_driver_data import make_feature_cache
+from tests.kernel_cases import _lerp_fp32, _ulps  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -74,10 +75,6 @@ class NormBuffers:
         torch.cuda.synchronize()
         assert torch.all(self.part[self.w:] == POISON), "the guard behind part was written"
         return self.clip2.cpu().numpy().copy()
-
-
-def _ulps(got, want32):
-    return abs(float(got) - float(want32)) / float(np.spacing(np.abs(np.float32(want32))))
 
 
 @pytest.mark.parametrize("n", NORM_SIZES)
@@ -199,12 +196,6 @@ def _adamw_clip_ema(lib, b, g, step, found, et, clip=None, ema=False, w=0.0):
     _lib.check(lib.r50_op_adamw_clip_ema(b.p.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), g.data_ptr(), b.p16.data_ptr(), b.n, *HYPER, step,
                                          found.data_ptr(), clip.data_ptr() if clip is not None else None,
                                          b.ema.data_ptr() if ema else None, w, et, _stream()), None, "r50_op_adamw_clip_ema")
-
-
-def _lerp_fp32(e, p_new, w):
-    """e + w * (p_new - e), each operation rounded once to fp32 (separate torch kernels: nothing contracts)."""
-    w32 = torch.tensor(w, dtype=torch.float32, device=e.device)
-    return e + w32 * (p_new - e)
 
 
 @pytest.mark.parametrize("n", (64, 320, 256 * 8192 + 192))                 # the last: a second grid-stride round

@@ -4,6 +4,7 @@ import itertools
 
 import pytest
 import torch
+from tests.kernel_cases import _clip  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -14,14 +15,6 @@ def lib_built():
     from implementation_phd_lab_vision_amd import _lib
     _lib.build_library()
     return _lib.load_library()
-
-
-def _clip(seed, t=3, h=224, w=224):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(0, 256, (t, 3, h, w), generator=g, dtype=torch.uint8)
-    x[0, :, :8] = 255; x[0, :, 8:16] = 0                        # saturated / black / gray rows: the eqc and clamp branches
-    x[0, :, 16:24] = x[0, :1, 16:24]
-    return x
 
 
 def test_every_op_order_matches_the_oracle(lib_built):

@@ -18,6 +18,7 @@ import torch
 
 from tests import dtw_reference as dr
 from tests import results_data as rd
+from tests.kernel_cases import _case_inputs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -58,17 +59,6 @@ def _run(lib, pred, gt, i0, q, group, n_groups, root=0, band=-1, acc=None, paths
     assert rc == 0, lib.r50_last_error(None)
     torch.cuda.synchronize()
     return clip_out, path_out, acc
-
-
-def _case_inputs(case):
-    """(pred for P1 (no similarity), pred for P2 (a per-clip similarity on top), gt, group) of one seeded case."""
-    b, p, q, t_gt, i0, j, n_groups, root, band = case
-    rng = np.random.default_rng(1000 * b + 10 * p + q)
-    gt = dr.walk_clips(rng, b, t_gt, j)
-    plain = dr.slowed_predictions(rng, gt, i0, p, q, similarity=False)
-    fitted = dr.slowed_predictions(rng, gt, i0, p, q, similarity=True)
-    used = rng.permutation(n_groups)[:max(1, n_groups - 2)] if n_groups > 2 else np.arange(n_groups)   # some groups stay empty
-    return plain, fitted, gt, rng.choice(used, size=b)
 
 
 _ORACLE = {}

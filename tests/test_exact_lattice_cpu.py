@@ -250,7 +250,7 @@ def test_mutant_subnormal_operands_flushed_before_the_product(case, side):
 @pytest.mark.parametrize("which", ["x", "w"])
 @pytest.mark.parametrize("case", FP8_CASES, ids=str)
 def test_mutant_subnormal_fp8_operands_flushed_before_the_product(case, which):
-    from tests.test_kernels_gpu import fp8_reference
+    from tests.kernel_cases import fp8_reference
     n, h, w, cin, cout, k, stride, pad, relu, has_res, _tile = case
     (xq, wq, bias, rq, scales), st = L.fp8_case(case, "low")
     xq, wq = xq.float(), wq.float()

@@ -13,10 +13,8 @@ pins the oracle to torch on the same cases.  Every comparison is exact; no kerne
   (f) byte offsets past 2^32  in one 2^32 + 2^20 byte allocation that is never filled
   (g) ``predict``             under a non-square box: the crops and the camera with two different zooms
 
-and the rows ``ROWS_FRAMES_DOMAIN`` between poisoned guard bands (tests/test_guard_bands_gpu.py's harness) and late on a side stream
-(tests/test_stream_order_gpu.py's)."""
-import functools
-
+and the rows ``ROWS_FRAMES_DOMAIN`` of tests/rows/frames_domain.py between poisoned guard bands (tests/guard_bands.py's harness) and late
+on a side stream (tests/stream_order.py's)."""
 import numpy as np
 import pytest
 import torch
@@ -26,15 +24,14 @@ from implementation_phd_lab_vision_amd import frames as F
 from implementation_phd_lab_vision_amd import predict, track
 from oracle import resize_oracle as ro
 from tests import resize_cases as RC
-from tests.test_guard_bands_gpu import Arena, Row, run_row  # noqa: F401  (Arena: the type ``launch`` receives)
-from tests.test_stream_order_gpu import run_row_late
+from tests.guard_bands import run_row
+from tests.rows.frames_domain import MODE_IDS, MODES, ROWS_FRAMES_DOMAIN, _table_want, _want
+from tests.stream_order import run_row_late
 from tests.test_track_gpu import CAM, STRIDE, T as SEQ, backbone, head, video  # noqa: F401  (fixtures: the synthetic backbone, head, walker)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U8 = torch.uint8
-MODES = [F.RESIZE_FLOAT, F.RESIZE_FIXED]
-MODE_IDS = ["float", "fixed"]
 POISON = 0x7B
 HAS_AVX = "AVX" in torch.backends.cpu.get_cpu_capability()
 
@@ -44,16 +41,6 @@ def lib():
     from implementation_phd_lab_vision_amd import _lib
     _lib.build_library()
     return _lib.load_library()
-
-
-@functools.lru_cache(maxsize=None)
-def _want(hh, ww, out, mode):
-    """The oracle's (T, 3, out, out) result for ``RC.image(hh, ww, out)``: computed once per case and mode, shared, never modified."""
-    x = RC.crop_nchw(RC.image(hh, ww, out))
-    got = ro.resize_bilinear_u8(x, out, out) if mode == F.RESIZE_FIXED else ro.resize_bilinear_u8_float_restated(x, out, out)
-    t = torch.from_numpy(np.ascontiguousarray(got))
-    assert t.shape == (RC.T, 3, out, out) and t.dtype == U8
-    return t
 
 
 def _where(got, want):
@@ -131,10 +118,6 @@ def test_out_slice_of_a_poisoned_batch_buffer(lib, mode):
 
 
 # ---------------------------------------------------------------- (e): the tracked kernel ---------------------------------------------------
-def _table_want(case, out, mode):
-    return torch.stack([_want(hh, ww, out, mode)[fi] for (hh, ww), fi in case["frames"]])
-
-
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("tail", [1, 2, 3], ids=lambda v: f"tail{v}")
 @pytest.mark.parametrize("out", RC.OUTS)
@@ -243,77 +226,6 @@ def test_predict_under_a_non_square_box(backbone, head, video):  # noqa: F811
 
 
 # ---------------------------------------------------------------- guard bands and stream order ----------------------------------------------
-ROWS_FRAMES_DOMAIN = []
-
-
-@functools.lru_cache(maxsize=None)
-def _clib():
-    from implementation_phd_lab_vision_amd import _lib as L
-    L.build_library()
-    return L.load_library()
-
-
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _producer_make(hh, ww, out):
-    return RC.embed(RC.image(hh, ww, out, t=2), *RC.placements(hh, ww)[0][1:])
-
-
-def _producer_launch(out, mode):
-    def launch(a, pay):
-        clip, (top, left, hh, ww) = pay
-        t, h, w, _ = clip.shape
-        a.reach(2 * w * 3 + 8)                                       # two source rows, plus the dword rounding at either end
-        f = a.inp("frames", clip)
-        for flags in (0, 3):
-            o = a.out(f"out[flags {flags}]", (t, 3, out, out), U8)
-            rc = _clib().r50_op_crop_resize_u8(f.data_ptr(), t, h, w, top, left, hh, ww, o.data_ptr(), out, mode, flags, _s())
-            assert rc == 0, _clib().r50_last_error(None)
-    return launch
-
-
-def _producer_check(out, mode):
-    def check(plain, pay):
-        clip, (top, left, hh, ww) = pay
-        x = np.transpose(clip.numpy(), (0, 3, 1, 2))[:, :, top:top + hh, left:left + ww]
-        want = ro.resize_bilinear_u8(x, out, out) if mode == F.RESIZE_FIXED else ro.resize_bilinear_u8_float_restated(x, out, out)
-        want = torch.from_numpy(np.ascontiguousarray(want))
-        assert torch.equal(plain.results["out[flags 0]"].cpu(), want)
-        assert torch.equal(plain.results["out[flags 3]"].cpu(), torch.flip(want, dims=[0, -1]))
-    return check
-
-
-def _table_make(out, mode, tail):
-    c = RC.packed_table(out, tail)
-    table = track.BoxTable(c["offsets"], c["sizes"], c["boxes"], c["src_bytes"], out, mode)
-    return dict(case=c, buf=c["buf"], table=torch.from_numpy(table.host), t=table.t, max_ww=table.max_ww, src_bytes=c["src_bytes"], out=out, mode=mode)
-
-
-def _table_launch(a, pay):
-    a.reach(2 * pay["case"]["max_w"] * 3 + 8)                         # two source rows of the widest image, plus the dword rounding
-    src, table = a.inp("src", pay["buf"]), a.inp("table", pay["table"])
-    shape = (pay["t"], 3, pay["out"], pay["out"])
-    o, of = a.out("out", shape, U8), a.out("out_flip", shape, U8)
-    rc = _clib().r50_op_crop_resize_boxes_u8(src.data_ptr(), pay["src_bytes"], table.data_ptr(), pay["t"], pay["max_ww"], o.data_ptr(), of.data_ptr(),
-                                             pay["out"], pay["mode"], _s())
-    assert rc == 0, _clib().r50_last_error(None)
-
-
-def _table_check(plain, pay):
-    want = _table_want(pay["case"], pay["out"], pay["mode"])
-    assert torch.equal(plain.results["out"].cpu(), want) and torch.equal(plain.results["out_flip"].cpu(), torch.flip(want, dims=[-1]))
-
-
-for _mode, _name in zip(MODES, MODE_IDS):
-    for _hh, _ww, _out in ((40, 8, 12), (1033, 691, 344)):
-        ROWS_FRAMES_DOMAIN.append(Row("frames_domain", f"crop_resize_u8-{_hh}x{_ww}_to_{_out}-{_name}", ("r50_op_crop_resize_u8",),
-                                      functools.partial(_producer_make, _hh, _ww, _out), _producer_launch(_out, _mode), _producer_check(_out, _mode)))
-    ROWS_FRAMES_DOMAIN.append(Row("frames_domain", f"crop_resize_boxes_u8-every_source-out12-{_name}-flip", ("r50_op_crop_resize_boxes_u8",),
-                                  functools.partial(_table_make, 12, _mode, 3), _table_launch, _table_check))
-
-
 @pytest.mark.parametrize("row", ROWS_FRAMES_DOMAIN, ids=[r.id for r in ROWS_FRAMES_DOMAIN])
 def test_frames_domain_between_guard_bands(row):
     run_row(row)

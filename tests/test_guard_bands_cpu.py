@@ -1,6 +1,6 @@
 """The guard-band harness (tests/guard_bands.py) proved on the CPU: three toy "kernels" in plain torch on ``as_strided`` views of the arena
 show what the harness detects and why it needs two fills; the fills' bit patterns are checked per dtype; and every op of include/r50.h
-must have a row in tests/test_guard_bands_gpu.py (or a reason not to)."""
+must have a row in tests/rows/r50.py (or a reason not to)."""
 import math
 import re
 from pathlib import Path
@@ -9,30 +9,10 @@ import pytest
 import torch
 
 from tests import guard_bands as G
+from tests.guard_bands import PAYLOAD, _shifted, _toy_reads_one_before, _toy_reads_one_before_then_relu, _toy_writes_one_past  # noqa: F401
 
 ROOT = Path(__file__).resolve().parents[1]
 SMALL = 2 * G.PAGE                      # band length of the toy runs
-
-
-def _shifted(x: torch.Tensor, by: int) -> torch.Tensor:
-    """x's window moved by `by` elements: the view an index mistake of that size reads or writes."""
-    return x.as_strided(x.shape, x.stride(), x.storage_offset() + by)
-
-
-def _toy_reads_one_before(x, out):
-    """y[i] = x[i] + 1 * x[i-1] over the whole operand: at i = 0 it reads one element in front of x."""
-    out.copy_(x + _shifted(x, -1))
-
-
-def _toy_reads_one_before_then_relu(x, out):
-    """The same, then ReLU the way the kernels' fmax treats NaN: max(NaN, 0) = 0."""
-    v = x + _shifted(x, -1)
-    out.copy_(torch.where(torch.isnan(v), torch.zeros_like(v), v).clamp_min(0))
-
-
-def _toy_writes_one_past(x, out):
-    _shifted(out, 1).copy_(x)
-    out[0] = x[0]
 
 
 def _three_runs(kernel, payload, dtype=torch.float32):
@@ -53,9 +33,6 @@ def _three_runs(kernel, payload, dtype=torch.float32):
 
 def _same_bits(a, b):
     return torch.equal(G.bits(a), G.bits(b))
-
-
-PAYLOAD = torch.tensor([-1.5, 2.0, 0.25, -3.0, 7.0])       # x[0] < 0: the true pre-activation of y[0] is negative
 
 
 def test_a_read_in_front_of_the_operand_is_caught_by_both_fills():
@@ -151,9 +128,9 @@ def _header_ops():
 
 
 def test_every_op_of_the_header_has_a_guard_band_row():
-    """A new op fails here until tests/test_guard_bands_gpu.py runs it between guard bands.  NOT_GUARDED is for entry points that take no
+    """A new op fails here until a row of tests/rows/r50.py runs it between guard bands.  NOT_GUARDED is for entry points that take no
     device operand, and for nothing else."""
-    from tests import test_guard_bands_gpu as T
+    from tests.rows import r50 as T
     covered = set()
     for row in T.ROWS:
         covered.update(row.ops)

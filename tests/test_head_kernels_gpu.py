@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import head_kernels_reference as R
+from tests.kernel_cases import HEAD_GEMMS, _gn_inputs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -50,17 +51,6 @@ GN_CASES = [(et, r, s) for et in (1, 0) for r in GN_RATIOS[et] for s in GN_SHAPE
 def _gn_id(case):
     et, r, (b, t, c, g) = case
     return f"{'fp16' if et else 'bf16'}-ratio{r}-b{b}t{t}c{c}g{g}"
-
-
-def _gn_inputs(et, ratio, shape):
-    """x (b, t, c) 16-bit: per (sample, group) a std in [0.5, 2] and a mean of +-ratio * std."""
-    b, t, c, groups = shape
-    g = torch.Generator().manual_seed(1000 * ratio + 10 * t + c + groups + et)
-    sig = 0.5 + 1.5 * torch.rand(b, 1, groups, 1, generator=g)
-    sign = torch.where(torch.rand(b, 1, groups, 1, generator=g) < 0.5, -1.0, 1.0)
-    x = (ratio * sig * sign + sig * torch.randn(b, t, groups, c // groups, generator=g)).reshape(b, t, c).to(R.DTYPE[et])
-    gamma, beta = 1 + 0.1 * torch.randn(c, generator=g), 0.1 * torch.randn(c, generator=g)
-    return x, gamma, beta, g
 
 
 @pytest.mark.parametrize("case", GN_CASES, ids=_gn_id)
@@ -505,30 +495,6 @@ def test_adamw_against_fp64_torch(lib, et, n):
 
 
 # ---------------------------------------------------------------- f. the head's GEMMs -------------------------------------------------
-# rows, K, cout, relu, residual, kind: r50_op_conv2d(_f16) with n = rows, h = w = 1, as model.py / train.py launch them.  "fwd": bias, ReLU
-# and residual as the forward sets them; "dx" / "dw": the backward's products (zero bias, no epilogue), dW with K = B*T rounded up to 64
-# and the padding columns zero (the last field of a "dw" entry: B*T).
-HEAD_GEMMS = [
-    (1280, 2048, 1024, False, False, "fwd"),      # input_proj, B 32 x T 40
-    (1280, 3072, 1024, False, False, "fwd"),      # causal conv1 (K = 3D)
-    (1280, 3072, 1024, False, True, "fwd"),       # causal conv2 + residual
-    (1280, 1088, 1024, True, False, "fwd"),       # regressor mlp0 (K = D + 51 padded to 1088), ReLU
-    (1280, 1024, 1024, True, False, "fwd"),       # mlp3
-    (1280, 1024, 64, False, False, "fwd"),        # mlp5 (51 outputs padded to 64)
-    (32, 3072, 1024, False, True, "fwd"),         # rollout: the last block's conv2 over the new frame's B rows
-    (480, 3072, 1024, False, False, "fwd"),       # rollout at B 32: 15 observed frames
-    (1248, 3072, 1024, False, True, "fwd"),       # rollout at B 32: 39 frames
-    (32, 1088, 1024, True, False, "fwd"),         # the regressor over one horizon's B rows
-    (1280, 64, 1024, False, False, "dx"),         # dX of mlp5 (K = 64)
-    (1280, 1024, 1088, False, False, "dx"),       # dX of mlp0 (cout = 1088: 64-wide tiles only)
-    (1280, 1024, 3072, False, False, "dx"),       # dX of a causal conv
-    (1024, 1280, 2048, False, False, "dw", 1280),  # dW of input_proj: K = B*T = 1280
-    (1024, 1280, 3072, False, False, "dw", 1280),  # dW of a causal conv
-    (64, 1280, 1024, False, False, "dw", 1280),   # dW of mlp5
-    (1024, 1280, 3072, False, False, "dw", 1248),  # dW over 39 x 32 rollout rows, zero-padded to 1280
-    (1024, 512, 3072, False, False, "dw", 480),   # dW over 15 x 32 rollout rows, zero-padded to 512
-    (1024, 64, 3072, False, False, "dw", 32),     # dW of the last conv2: 32 rows zero-padded to 64
-]
 BIG_GEMMS = [                                     # B 256 x T 40: the automatic tile and the big tiles
     (10240, 3072, 1024, False, True, "fwd"),
     (10240, 2048, 1024, False, False, "fwd"),

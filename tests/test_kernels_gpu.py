@@ -10,12 +10,10 @@ tensor rel-L2 must be < 1e-3.
 """
 import pytest
 import torch
+from tests.kernel_cases import (  # noqa: F401
+    CAT_CASES, CONV_CASES, FP8_CASES, _conv_inputs, _dev, _rand_bf16, _tail3_inputs, _tiles_for, fp8_reference)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    return torch.device("cuda", 0)
 
 
 def _check_bf16(dev_nhwc: torch.Tensor, ref_nchw: torch.Tensor, what: str, mant: int = 7):
@@ -38,85 +36,6 @@ def _check_bf16(dev_nhwc: torch.Tensor, ref_nchw: torch.Tensor, what: str, mant:
 def _fmt_of(t: torch.Tensor):
     """(oracle fmt, mantissa bits of _check_bf16) of a runner's 16-bit tensors: the fused kernels run in bf16 or in fp16."""
     return ("fp16", 10) if t.dtype == torch.float16 else ("bf16", 7)
-
-
-def _rand_bf16(shape, gen, scale=1.0):
-    return (torch.randn(shape, generator=gen) * scale).to(torch.bfloat16)
-
-
-CONV_CASES = [
-    # n, h, w, cin, cout, k, stride, pad, relu, residual
-    (2, 8, 8, 64, 64, 1, 1, 0, True, False),
-    (3, 5, 5, 64, 256, 1, 1, 0, True, True),       # M = 75: ragged pixel tail, residual epilogue
-    (2, 8, 8, 256, 512, 1, 2, 0, False, False),    # strided 1x1 (downsample), no ReLU
-    (3, 7, 7, 64, 64, 3, 1, 1, True, False),       # 3x3, padding edges, M = 147
-    (2, 9, 9, 128, 128, 3, 2, 1, True, False),     # 3x3 stride 2, odd size
-    (1, 14, 14, 256, 256, 3, 1, 1, True, True),
-    (2, 7, 7, 512, 512, 3, 1, 1, True, False),     # layer4 conv2 shape, K = 4608
-    (2, 7, 7, 2048, 512, 1, 1, 0, True, False),    # K = 2048
-    (1, 56, 56, 64, 256, 1, 1, 0, True, True),     # layer1 conv3 at full spatial size
-    (1, 1, 1, 64, 64, 3, 1, 1, True, False),       # single pixel: every tap but the centre is padding
-    (3, 5, 9, 128, 256, 3, 1, 1, True, True),      # non-square, 3 images: halo rows cross image borders
-    (2, 14, 14, 256, 256, 3, 1, 1, True, False),
-    (3, 56, 56, 64, 64, 3, 1, 1, True, False),     # layer1 conv2: resident-weights kernel (TILE_C64); 42 tiles, image borders
-    (1, 56, 56, 64, 64, 3, 1, 1, False, False),
-    # input-resident 3x3 kernel (TILE_XRES): image counts that leave panels empty (7x7: four images per tile), row bands (28x28),
-    # several tiles per workgroup is covered at batch 256 by tests/test_benchmarked_config_gpu.py
-    (5, 7, 7, 512, 512, 3, 1, 1, True, False),
-    (3, 28, 28, 128, 128, 3, 1, 1, True, False),
-    (3, 14, 14, 256, 256, 3, 1, 1, False, False),
-    # polyphase stride-2 3x3 kernel (TILE_S2: conv2 of layer2.0 / layer3.0): four row bands per image at 56 -> 28 (top / bottom borders in
-    # different bands), one image per tile at 28 -> 14, two cout tiles; every generic tile runs the same case beside it
-    (3, 56, 56, 128, 128, 3, 2, 1, True, False),
-    (2, 28, 28, 256, 256, 3, 2, 1, True, False),
-    (1, 28, 28, 256, 256, 3, 2, 1, False, False),
-    (5, 14, 14, 512, 512, 3, 2, 1, True, False),   # 14 -> 7: four images per tile (two pairs), the second tile holds one image
-    # eight-phase GEMM tiles (TILE_G8 / TILE_G8_224, 1x1): several pixel tiles with a ragged last one and two cout tiles, K = 512 (8 K-tiles)
-    # with a residual; K = 64 (ONE K-tile per tile: the stream's prologue, vmcnt(0) path); a strided source; 300 tiles on 256 CUs (tile stream)
-    (5, 14, 14, 512, 512, 1, 1, 0, True, True),
-    (3, 9, 9, 64, 256, 1, 1, 0, False, False),
-    (3, 12, 12, 256, 256, 1, 2, 0, True, False),
-    (75, 32, 32, 128, 256, 1, 1, 0, True, True),
-]
-
-
-def _tiles_for(cout, k=3, pad=1):
-    from implementation_phd_lab_vision_amd import ops
-    t = [ops.TILE_AUTO, ops.TILE_64x128, ops.TILE_64x256]
-    if cout % 128 == 0:
-        t += [ops.TILE_128x128, ops.TILE_128x64, ops.TILE_128x256_P3, ops.TILE_128x128_P3]
-    if cout % 256 == 0:
-        t += [ops.TILE_256x128_P3, ops.TILE_256x256, ops.TILE_256x256_B, ops.TILE_256x208, ops.TILE_256x224]
-    ws = [ops.WS | 9]
-    if cout % 128 == 0:
-        ws += [ops.WS | 1, ops.WS | 4, ops.WS | 8]
-    if cout % 256 == 0:
-        ws += [ops.WS | 3]
-    if cout % 256 == 0 and k == 1 and pad == 0:
-        ws += [ops.TILE_G8, ops.TILE_G8_224]
-    return t + [x | ops.PERSISTENT for x in t if x != ops.TILE_AUTO] + ws
-
-
-def _conv_inputs(case, et=torch.bfloat16):
-    """Seeded inputs of one CONV_CASES row on the device (NHWC / OHWI) and the oracle's fused-op result (NCHW), in bf16 or fp16."""
-    from oracle.resnet50_oracle import conv_bias_act_emulated
-    n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    f16 = et == torch.float16
-    g = torch.Generator().manual_seed(hash(case) % (2 ** 31) + (1 if f16 else 0))
-    x = (torch.randn((n, cin, h, w), generator=g)).to(et)
-    wt = (torch.randn((cout, cin, k, k), generator=g) * (2.0 / (cin * k * k)) ** 0.5).to(et)
-    bias = torch.randn(cout, generator=g) * 0.1
-    ho = (h + 2 * pad - k) // stride + 1
-    wo = (w + 2 * pad - k) // stride + 1
-    res = torch.randn((n, cout, ho, wo), generator=g).to(et) if has_res else None
-    ref = conv_bias_act_emulated(x.float(), wt.float(), bias, stride, pad, relu,
-                                 residual_bf=res.float() if has_res else None, fmt="fp16" if f16 else "bf16")
-    d = _dev()
-    xd = x.permute(0, 2, 3, 1).contiguous().to(d)
-    wd = wt.permute(0, 2, 3, 1).contiguous().to(d)
-    bd = bias.to(d)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(d) if has_res else None
-    return xd, wd, bd, rd, ref, (ho, wo)
 
 
 def _check_fp16(y: torch.Tensor, ref: torch.Tensor, what: str):
@@ -488,17 +407,6 @@ def _run_bneck_tail_layer2(shape, tensors=None):
     return out, y1n
 
 
-def _tail3_inputs(n, h, w, seed):
-    g = torch.Generator().manual_seed(seed)
-    y2 = _rand_bf16((n, 256, h, w), g)
-    w3 = _rand_bf16((1024, 256, 1, 1), g, scale=(2.0 / 256) ** 0.5)
-    b3 = torch.randn(1024, generator=g) * 0.1
-    idn = _rand_bf16((n, 1024, h, w), g)
-    w1 = _rand_bf16((256, 1024, 1, 1), g, scale=(2.0 / 1024) ** 0.5)
-    b1 = torch.randn(256, generator=g) * 0.1
-    return y2, w3, b3, idn, w1, b1
-
-
 @pytest.mark.parametrize("shape,bp", [((2, 7, 9), 0), ((1, 14, 14), 0), ((3, 14, 14), 112), ((3, 14, 14), 98), ((20, 14, 14), 7), ((5, 14, 14), 33)],
                          ids=lambda v: str(v).replace(" ", ""))
 def test_bneck_tail_layer3_shapes(lib_built, shape, bp, monkeypatch):
@@ -752,21 +660,6 @@ def test_avgpool_matches_oracle(lib_built, shape):
     assert torch.allclose(y, ref, rtol=1e-5, atol=1e-6), float((y - ref).abs().max())
 
 
-CAT_CASES = [   # n, h (= w) of the output, c1, h2 (= w2) of the second source, c2, stride2, cout, relu, tile
-    (2, 4, 128, 8, 256, 2, 512, True, 0),          # layer2.0 shape family: K = 128 + 256
-    (3, 7, 256, 14, 512, 2, 1024, True, 0),        # layer3.0: M = 147 (ragged), K = 768
-    (2, 7, 512, 13, 1024, 2, 2048, True, 0),       # layer4.0 with an odd source size: (13 - 1) // 2 + 1 == 7
-    (1, 5, 64, 5, 64, 1, 64, False, 64 | 9),       # stride 1, no ReLU, 64-cout tile
-    (2, 6, 128, 11, 192, 2, 256, True, 64 | 1),    # 128x128 role-specialised tile, c2 not a power of two
-    (2, 6, 128, 11, 192, 2, 256, True, 64 | 4),    # 128x224, 4 consumer waves
-    (2, 6, 128, 11, 192, 2, 256, True, 64 | 3),    # 256x128
-    (2, 6, 128, 11, 192, 2, 256, True, 83),        # eight-phase GEMM tile (gemm8p_kernel, two K sources), one ragged tile
-    (9, 7, 256, 14, 512, 2, 1024, True, 83),       # layer3.0 family: M = 441 (two pixel tiles, the second ragged) x four cout tiles, K = 4 + 8 K-tiles
-    (9, 7, 256, 14, 512, 2, 1024, False, 84),      # the 224-pixel form
-    (6, 7, 512, 13, 1024, 2, 2048, True, 84),      # layer4.0 family, odd source size
-]
-
-
 @pytest.mark.parametrize("et", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("case", CAT_CASES, ids=lambda c: "n%d_%dx%d_c%d_src%d_c%d_s%d_o%d_r%d_t%d" % (c[0], c[1], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]))
 def test_conv1x1_two_k_sources(lib_built, case, et):
@@ -814,17 +707,6 @@ def _run_conv1x1_cat(case, et, tensors=None):
     return y
 
 
-FP8_CASES = [   # n, h, w, cin, cout, k, stride, pad, relu, residual, tile
-    (2, 8, 8, 128, 128, 1, 1, 0, True, False, 0),
-    (3, 5, 5, 256, 256, 1, 1, 0, True, True, 64 | 3),      # M = 75: ragged pixel tail, residual epilogue, 256x128 tile
-    (2, 8, 8, 256, 512, 1, 2, 0, False, False, 64 | 8),    # strided 1x1, no ReLU (negative outputs)
-    (3, 7, 7, 128, 128, 3, 1, 1, True, False, 64 | 1),     # 3x3: zero padding taps, K = 1152
-    (2, 9, 9, 128, 64, 3, 2, 1, True, False, 64 | 9),      # 3x3 stride 2, 64-cout tile
-    (1, 14, 14, 256, 256, 3, 1, 1, True, True, 64 | 4),    # layer3 conv2 shape with a residual, 4-consumer tile
-    (2, 7, 7, 1024, 256, 1, 1, 0, True, False, 64 | 8),    # K = 1024: 8 row-steps
-]
-
-
 @pytest.mark.parametrize("case", FP8_CASES, ids=lambda c: "n%d_%dx%d_c%d_o%d_k%d_s%d_p%d_r%d_res%d_t%d" % tuple(int(v) for v in c))
 def test_conv2d_fp8(lib_built, case):
     _run_conv2d_fp8(case)
@@ -842,19 +724,6 @@ def _fp8_tensors(case):
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     rq = (torch.randn(n, ho, wo, cout, generator=g) / sr * 0.5).clamp(-448, 448).to(ops.FP8) if has_res else None
     return xq, wq, bias, rq, (sx, sw, sr, sy)
-
-
-def fp8_reference(xq, wq, bias, rq, scales, stride, pad, relu):
-    """The fp64 value of one fp8 conv before its requantisation, in units of sy (NCHW): act(sx*sw * sum(x*w) + bias + sr*residual) / sy."""
-    import torch.nn.functional as F
-    sx, sw, sr, sy = scales
-    ref = F.conv2d(xq.double().permute(0, 3, 1, 2) * sx, wq.double().permute(0, 3, 1, 2) * sw, stride=stride, padding=pad)
-    ref = ref + bias.double().view(1, -1, 1, 1)
-    if rq is not None:
-        ref = ref + rq.double().permute(0, 3, 1, 2) * sr
-    if relu:
-        ref = F.relu(ref)
-    return ref / sy
 
 
 def _run_conv2d_fp8(case, tensors=None):

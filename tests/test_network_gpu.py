@@ -12,31 +12,15 @@ Tolerances:
 * vs the fp32 reference restatement (the reference's CPU numerics): per-frame rel-L2 < 1e-2 — the
   cost of bf16 itself (the reference's own GPU path runs bf16 autocast, :290-294).
 """
-import functools
-
 import pytest
 import torch
+from tests.network_oracles import (  # noqa: F401
+    check_features_bf16, check_features_bf16w2, check_features_fp16, check_features_fp32x, check_features_fp8, oracle_bf16, oracle_bf16w2, oracle_fp16, oracle_fp32x, oracle_fp8)
 
 pytestmark = pytest.mark.gpu
 
 TAPS = ["stem", "pool", "layer1.0.t1", "layer1.0.t2", "layer1.0.ds", "layer1.0", "layer1.2", "layer2.0.t2",
         "layer2.0.ds", "layer2.0", "layer2.3", "layer3.0", "layer3.5", "layer4.0.t2", "layer4.0", "layer4.2"]
-
-
-# The CPU oracles of each precision's fixture: computed once per session and shared (read-only) by every test module that needs them.
-@functools.lru_cache(maxsize=None)
-def oracle_bf16():
-    from implementation_phd_lab_vision_amd.weights import synthetic_frames, synthetic_state_dict
-    from oracle import resnet50_oracle as O
-    sd = synthetic_state_dict(0)
-    x = synthetic_frames(4, seed=1234)
-    taps = {}
-    feats_emu = O.forward_bf16_emulated(sd, x, taps=taps, fused_ds=True)
-    taps32 = {}
-    O.forward_bf16_emulated(sd, x, taps=taps32, acc_dtype=torch.float32, fused_ds=True)
-    drift = {k: O.rel_l2(taps32[k], taps[k]) for k in taps}
-    feats_ref = O.forward_reference(sd, x).flatten(1)
-    return sd, x, taps, drift, feats_emu, feats_ref
 
 
 @pytest.fixture(scope="module")
@@ -116,18 +100,6 @@ def test_features_match_oracles(setup):
     check_features_bf16(bb, x, feats_emu, feats_ref)
 
 
-def check_features_bf16(bb, x, feats_emu, feats_ref):
-    from oracle.resnet50_oracle import per_row_rel_l2
-    out = bb(x.to("cuda:0"))
-    assert tuple(out.shape) == (4, 2048, 1, 1) and out.dtype == torch.float32 and out.is_cuda
-    f = out.flatten(1).cpu()
-    assert torch.isfinite(f).all()
-    r_emu = per_row_rel_l2(f, feats_emu)
-    r_ref = per_row_rel_l2(f, feats_ref)
-    assert float(r_emu.max()) < 3e-3, r_emu
-    assert float(r_ref.max()) < 1e-2, r_ref
-
-
 def test_batch_split_invariance(setup):
     """Frames are independent: chunking by max_batch / micro_batch must not change a single bit."""
     bb, x, _, _, _ = setup
@@ -159,17 +131,6 @@ def test_empty_and_errors(setup):
 # (= the reference's CPU numerics, autocast disabled, src/preprocess_resnet_features.py:239-241).
 # Tolerance: per-frame rel-L2 < 1e-3 on features, rel-L2 < 1e-3 on every named activation (measured ~1e-5).
 # ---------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def oracle_fp32x():
-    from implementation_phd_lab_vision_amd.weights import synthetic_frames, synthetic_state_dict
-    from oracle import resnet50_oracle as O
-    sd = synthetic_state_dict(0)
-    x = synthetic_frames(3, seed=77)
-    taps = {}
-    feats_ref = O.forward_reference(sd, x, dtype=torch.float64, taps=taps).flatten(1)
-    return sd, x, taps, feats_ref
-
-
 @pytest.fixture(scope="module")
 def setup_fp32x(lib_built):
     from implementation_phd_lab_vision_amd.backbone import ResNet50Backbone
@@ -181,14 +142,6 @@ def setup_fp32x(lib_built):
 def test_fp32x_features_within_1e3_of_fp32_reference(setup_fp32x):
     bb, x, _taps, feats_ref = setup_fp32x
     check_features_fp32x(bb, x, feats_ref)
-
-
-def check_features_fp32x(bb, x, feats_ref):
-    from oracle.resnet50_oracle import per_row_rel_l2
-    f = bb(x.to("cuda:0")).flatten(1).cpu()
-    assert torch.isfinite(f).all()
-    r = per_row_rel_l2(f, feats_ref)
-    assert float(r.max()) < 1e-3, r
 
 
 def test_fp32x_named_activations(setup_fp32x):
@@ -361,28 +314,6 @@ def test_features_do_not_depend_on_batch_composition(lib_built):
     assert torch.equal(bb.features(x.flip(0)), big.flip(0))
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_bf16w2():
-    from implementation_phd_lab_vision_amd.weights import synthetic_frames, synthetic_state_dict
-    from oracle import resnet50_oracle as O
-    sd = synthetic_state_dict(0)
-    x = synthetic_frames(3, seed=11)
-    ref = O.forward_reference(sd, x, dtype=torch.float64).float()
-    taps = {}
-    emu = O.forward_bf16_emulated(sd, x, taps=taps, weight_terms=2)
-    return sd, x, ref, emu, taps
-
-
-def check_features_bf16w2(bb, x, ref, emu):
-    from oracle import resnet50_oracle as O
-    got = bb.features(x.to("cuda:0")).cpu()
-    assert torch.isfinite(got).all()
-    r_ref = O.per_row_rel_l2(got, ref)
-    r_emu = O.per_row_rel_l2(got, emu)
-    assert float(r_ref.max()) < 1e-3, f"bf16w2 vs fp64 reference: {r_ref.tolist()}"
-    assert float(r_emu.max()) < 1e-3, f"bf16w2 vs its emulation: {r_emu.tolist()}"
-
-
 def test_bf16w2_precision_meets_1e3_of_the_fp32_reference(lib_built):
     """bf16w2: bf16 activations, every bottleneck conv weight a bf16 (head, tail) pair, two MFMA products per conv.  The
     bf16 error of this network is weight-rounding dominated (oracle: fp32 weights + bf16 activations 8e-4, bf16 weights +
@@ -396,28 +327,6 @@ def test_bf16w2_precision_meets_1e3_of_the_fp32_reference(lib_built):
     # and a mid-network tap against the emulation's tap
     t = bb.layer(x.to("cuda:0"), "layer2.1").float().cpu().permute(0, 3, 1, 2)
     assert O.rel_l2(t, taps["layer2.1"]) < 2e-3
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_fp16():
-    from implementation_phd_lab_vision_amd.weights import synthetic_frames, synthetic_state_dict
-    from oracle import resnet50_oracle as O
-    sd = synthetic_state_dict(0)
-    x = synthetic_frames(3, seed=12)
-    ref = O.forward_reference(sd, x, dtype=torch.float64).float()
-    taps = {}
-    emu = O.forward_bf16_emulated(sd, x, taps=taps, fmt="fp16", fused_ds=True)
-    return sd, x, ref, emu, taps
-
-
-def check_features_fp16(bb, x, ref, emu):
-    from oracle import resnet50_oracle as O
-    got = bb.features(x.to("cuda:0")).cpu()
-    assert torch.isfinite(got).all()
-    r_ref, r_emu = O.per_row_rel_l2(got, ref), O.per_row_rel_l2(got, emu)
-    assert float(r_ref.max()) < 1e-3, f"fp16 vs fp64 reference: {r_ref.tolist()}"
-    assert float(r_ref.max()) < 5e-4, f"fp16 should sit well inside the tolerance: {r_ref.tolist()}"
-    assert float(r_emu.max()) < 3e-4, f"fp16 vs its emulation: {r_emu.tolist()}"
 
 
 def test_fp16_precision(lib_built):
@@ -471,31 +380,6 @@ def test_fp8_weights_are_torchs_e4m3_of_the_folded_weights(setup_fp8):
         assert n.value == want.numel()
         # +0 and -0 both occur for tiny weights of either sign; compare values
         assert torch.equal(got.view(torch.float8_e4m3fn).float(), want.view(torch.float8_e4m3fn).float()), key
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_fp8(scales):
-    """fp8 emulation (for one tuple of activation scales) and fp32 reference features of the fp8 fixture's frames."""
-    from implementation_phd_lab_vision_amd.weights import synthetic_frames, synthetic_state_dict
-    from oracle import resnet50_oracle as O
-    sd = synthetic_state_dict(0)
-    x = synthetic_frames(4, seed=1234)
-    return sd, x, O.forward_fp8_emulated(sd, x, list(scales)), O.forward_reference(sd, x).flatten(1)
-
-
-def check_features_fp8(bb, x, emu, ref):
-    from oracle import resnet50_oracle as O
-    assert len(bb.fp8_scales) == 43 and all(s > 0 for s in bb.fp8_scales)
-    f = bb(x.to("cuda:0")).flatten(1).cpu()
-    assert tuple(f.shape) == (4, 2048) and torch.isfinite(f).all()
-    r_emu = O.per_row_rel_l2(f, emu)
-    r_ref = O.per_row_rel_l2(f, ref)
-    e_ref = O.per_row_rel_l2(emu, ref)
-    # one e4m3 step is 6 %: a sum that lands on the other side of a rounding tie moves an activation by that much, and 39 chained
-    # convs spread such flips; the device must stay as close to the emulation as the emulation's own error scale allows
-    assert float(r_emu.max()) < 2.5e-2, r_emu
-    assert float(r_ref.max()) < 1.5 * float(e_ref.max()) + 1e-2, (r_ref, e_ref)
-    return f
 
 
 def test_fp8_features_match_the_fp8_emulation(setup_fp8):

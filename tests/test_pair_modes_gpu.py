@@ -31,17 +31,13 @@ import pytest
 import torch
 
 from tests import pair_reference as P
+from tests.kernel_cases import _out_shape, _refused_ids, _split_case, _w2_case  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 GUARD = -7.0
 _MEASURED = []          # (what, rel-L2) of every fp32x launch checked in this session; printed by each fp32x test before it asserts
-
-
-def _refused_ids():
-    from implementation_phd_lab_vision_amd import ops
-    return [ops.TILE_C64, ops.TILE_XRES, ops.TILE_S2, ops.TILE_G8, ops.TILE_G8_224]
 
 
 def _same_values(a: torch.Tensor, b: torch.Tensor) -> bool:
@@ -69,37 +65,6 @@ def _check_fp32x(y_pair_nhwc: torch.Tensor, ref_nchw_f64: torch.Tensor, what: st
 # ------------------------------------------------------------------------------------------------------------------------------
 # op level
 # ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _w2_case(case):
-    """bf16w2 inputs of one case on the device and its oracle, computed once and shared (read-only)."""
-    from oracle.resnet50_oracle import bf16_round, conv_bias_act_emulated
-    n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    x, wt, bias, res = P.pair_case_inputs(case)
-    x = bf16_round(x)
-    res = bf16_round(res) if has_res else None
-    ref = conv_bias_act_emulated(x, wt, bias, stride, pad, relu, residual_bf=res, weight_terms=2)
-    xd = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous().to(DEV)
-    rd = res.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous().to(DEV) if has_res else None
-    return xd, P.pack_ohwi_w2(wt).to(DEV), bias.to(DEV), rd, ref
-
-
-@functools.lru_cache(maxsize=None)
-def _split_case(case):
-    """fp32x inputs of one case on the device and its oracle, computed once and shared (read-only)."""
-    n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    x, wt, bias, res = P.pair_case_inputs(case)
-    xp, wp = P.split_pair(x), P.split_pair(wt)
-    rp = P.split_pair(res) if has_res else None
-    ref = P.fp32x_conv(xp, wp, bias, stride, pad, relu, rp)
-    rd = P.nhwc_pair(*rp).to(DEV) if has_res else None
-    return P.nhwc_pair(*xp).to(DEV), P.pack_ohwi_split(wt).to(DEV), bias.to(DEV), rd, ref
-
-
-def _out_shape(case):
-    n, h, w, cin, cout, k, stride, pad, relu, has_res = case
-    return n, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1, cout
-
-
 @pytest.mark.parametrize("case", P.PAIR_CASES, ids=P.case_id)
 def test_w2_conv_every_tile_matches_oracle(lib_built, case):
     """Every generic, persistent and role-specialised tile id on a weight pair with a populated tail, guard band behind the output."""

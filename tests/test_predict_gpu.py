@@ -9,6 +9,7 @@ from implementation_phd_lab_vision_amd import frames as F
 from implementation_phd_lab_vision_amd import model, predict
 from implementation_phd_lab_vision_amd.sequences import SequenceTable, stitch_poses
 from tests import png_reader
+from tests.kernel_cases import _cast_source, _ties  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -29,26 +30,6 @@ def _s():
 
 def _bits(t):
     return t.view(torch.int16)
-
-
-def _ties(dt, n, g):
-    """n fp32 values exactly halfway between two adjacent finite 16-bit values (what test_cast_rows_rounds_to_nearest_even feeds)."""
-    fp16 = dt == torch.float16
-    bits = torch.randint(0x0400 if fp16 else 0x0080, 0x7bfe if fp16 else 0x7f7e, (n,), generator=g, dtype=torch.int32)
-    lo, hi = bits.to(torch.int16).view(dt).float(), (bits + 1).to(torch.int16).view(dt).float()
-    return (lo + hi) / 2 * torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
-
-
-def _cast_source(dt, rows, c, g):
-    """(rows, c) fp32: a third exact rounding ties, then the saturating values of test_cast_rows_saturates_..., the rest normal draws."""
-    x = torch.randn(rows, c, generator=g) * 3
-    flat = x.view(-1)
-    k = flat.numel() // 3
-    flat[:k] = _ties(dt, k, g)
-    big = [65504.0, 65519.0, 65520.0, 1e5, 3e38, float("inf")]
-    special = torch.tensor(big + [-v for v in big] + [65503.0, 1e38, 0.0, -0.0])
-    flat[k:k + special.numel()] = special
-    return x[torch.randperm(rows, generator=g)].contiguous()
 
 
 def _cast_rows(lib, x, dt):

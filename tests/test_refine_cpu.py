@@ -25,7 +25,7 @@ def _prototypes():
 
 def test_every_prototype_of_the_refine_header_is_bound_exported_and_guard_banded(lib_built):
     from implementation_phd_lab_vision_amd import _lib
-    from tests import test_refine_gpu as T
+    from tests.rows import refine as T
     protos = _prototypes()
     names = [n for n, _ in protos]
     assert set(names) == OPS == set(_lib._SIGNATURES_REFINE) and len(names) == len(set(names))

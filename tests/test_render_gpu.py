@@ -13,6 +13,7 @@ import torch
 from tests import png_reader
 from tests import render_reference as rr
 from tests import results_data as rd
+from tests.kernel_cases import _assert_matches  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,13 +33,6 @@ def _draw(bg, pts, style, edges, half_width, joint_radius, **kw):
     out = draw_skeletons(None if bg is None else torch.from_numpy(bg).to(DEV), torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float32)).to(DEV),
                          torch.from_numpy(style).to(DEV), edges, half_width, joint_radius, **kw)
     return out.cpu().numpy()
-
-
-def _assert_matches(got, ref, layers, what):
-    mx, bad, near = rr.check_against(got, ref, rr.margin(layers))
-    differ = int((got != ref[0]).sum())
-    print(f"{what}: max |diff| {mx}, {differ} bytes differ ({bad} outside the margin), {near} of {got.size} bytes within the margin")
-    assert got.shape == ref[0].shape and mx <= 1 and bad == 0
 
 
 @pytest.fixture(scope="module")

@@ -39,7 +39,7 @@ def test_the_pipelines_listed_by_hand_are_what_the_list_says():
 
 def test_every_hand_synced_kernel_is_reached_by_a_row():
     from tests import alignment as AL
-    from tests.test_alignment_gpu import ALL_ROWS
+    from tests.rows import ALL_ROWS
     protos = AL.prototypes()
     for kernel, entry_points in RP.HAND_SYNCED.items():
         assert entry_points, f"{kernel}: no entry point"

@@ -1,7 +1,7 @@
 """Every op holds its bits run after run, alone and under contention.
 
 The harness is tests/repeatability.py (read its docstring first).  Every row of every guard-band table (``ALL_ROWS`` of
-tests/test_alignment_gpu.py) runs once plainly and then R times per mode, from the same payloads, every run with fresh 0xFF-poisoned
+tests/rows/) runs once plainly and then R times per mode, from the same payloads, every run with fresh 0xFF-poisoned
 outputs between 0xFF bands:
 
   hot rows    the rows whose ``ops`` reach a hand-synchronised kernel (``repeatability.HAND_SYNCED``), and the op-level stem: R = 16 in
@@ -17,7 +17,7 @@ A repetition under noise counts only if the burst ended after the row did, a twi
 intersect.  A hot row in which more than a quarter of the repetitions did not overlap fails with that reason, in every mode; a plain row
 fails if none of its twin repetitions overlapped (at R = 2 a quarter is less than one repetition): a row that never ran beside its twin
 says nothing about a shared workspace.  A row whose op synchronises the host before it launches (``BLOCKS_HOST`` of
-tests/test_stream_order_gpu.py: ``r50_op_stem``, ``r50_op_resize_frames_u8``) gets a host thread per copy, under the same bars.  For
+tests/stream_order.py: ``r50_op_stem``, ``r50_op_resize_frames_u8``) gets a host thread per copy, under the same bars.  For
 those rows the interval of a copy spans its upload or read-back, the host synchronisation and the kernels: the events show that the
 two calls were inside the library at the same time and how far apart they ended (printed), not that the kernels themselves coincided.
 ``test_every_mode_overlapped`` prints the shares.
@@ -30,8 +30,9 @@ import pytest
 
 from tests import guard_bands as G
 from tests import repeatability as RP
-from tests.test_alignment_gpu import ALL_ROWS
-from tests.test_guard_bands_gpu import _checks_fill, _lib
+from tests.guard_bands import _checks_fill, close_payloads
+from tests.rows import ALL_ROWS
+from tests.stream_order import may_block
 
 pytestmark = pytest.mark.gpu
 
@@ -63,14 +64,13 @@ def knobs_read_zero_when_a_test_ends(knob_handle):
 
 
 def holds_host(row):
-    """The row's op synchronises the host before it launches (``BLOCKS_HOST`` of tests/test_stream_order_gpu.py, which that file holds
+    """The row's op synchronises the host before it launches (``BLOCKS_HOST`` of tests/stream_order.py, which tests/test_stream_order_gpu.py holds
     exact: a row outside it that holds the host fails there, and so does a stale entry)."""
-    from tests.test_stream_order_gpu import may_block
     return may_block(row)
 
 
 def hold_row(row, mode, reps, hot):
-    lib = _lib()
+    lib = G.lib()
     payloads, payloads2 = row.make(), None
     try:
         plain = RP.plain_run(row, payloads)
@@ -88,8 +88,8 @@ def hold_row(row, mode, reps, hot):
             runs = RP.run_twin(row, payloads, payloads if payloads2 is None else payloads2, plain.spec, reps, lib, host_ms,
                                two_threads=holds_host(row))
     finally:
-        RP.close_payloads(payloads)
-        RP.close_payloads(payloads2)
+        close_payloads(payloads)
+        close_payloads(payloads2)
     what = f"{row.id} {mode}"
     for label, a in runs.arenas:
         a.finish()

@@ -25,7 +25,7 @@ def _prototypes():
 
 def test_every_prototype_of_the_resample_header_is_bound_exported_and_guard_banded(lib_built):
     from implementation_phd_lab_vision_amd import _lib
-    from tests import test_resample_guard_bands_gpu as T
+    from tests.rows import resample as T
     protos = _prototypes()
     names = [n for n, _ in protos]
     assert set(names) == OPS == set(_lib._SIGNATURES_RESAMPLE) and len(names) == len(set(names))

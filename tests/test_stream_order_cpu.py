@@ -1,4 +1,4 @@
-"""tests/test_stream_order_gpu.py runs every row of the three guard-band tables late on a side stream: held complete here, without a GPU,
+"""tests/test_stream_order_gpu.py runs every row of the tables ``r50``, ``smooth`` and ``hal`` of tests/rows/ late on a side stream: held complete here, without a GPU,
 as tests/test_guard_bands_cpu.py holds the guard-band table complete for the header."""
 import torch
 
@@ -20,12 +20,12 @@ def _parametrised_rows(T):
 
 
 def test_every_guard_band_row_runs_late_on_a_side_stream():
-    from tests import test_guard_bands_gpu as TG
-    from tests import test_hal_guard_bands_gpu as TH
-    from tests import test_smooth_guard_bands_gpu as TS
     from tests import test_stream_order_gpu as T
-    tables = TG.ROWS + TS.ROWS_SMOOTH + TH.ROWS_HAL
-    assert len(tables) > 150 and TS.ROWS_SMOOTH and TH.ROWS_HAL
+    from tests.rows.hal import ROWS_HAL
+    from tests.rows.r50 import ROWS
+    from tests.rows.smooth import ROWS_SMOOTH
+    tables = ROWS + ROWS_SMOOTH + ROWS_HAL
+    assert len(tables) > 150 and ROWS_SMOOTH and ROWS_HAL
     by_test = _parametrised_rows(T)
     run = [r for rows in by_test.values() for r in rows]
     assert len(run) == len(tables) and all(any(r is t for t in tables) for r in run), "the parametrisation is not built from the three row tables"
@@ -40,14 +40,15 @@ def test_every_guard_band_row_runs_late_on_a_side_stream():
 
 
 def test_the_blocking_table_names_rows_or_ops_and_keeps_off_the_hot_paths():
+    from tests import stream_order as SO
     from tests import test_stream_order_gpu as T
-    T.check_blocking_table()
-    hot = T.hot_path_ops()
+    SO.check_blocking_table(T.ALL_ROWS)
+    hot = SO.hot_path_ops()
     assert {"r50_op_cast_rows", "r50_op_conv2d", "r50_op_conv2d_f16", "r50_op_gn_relu_causal3", "r50_op_bneck_tail", "r50_op_bneck_block2",
             "r50_op_avgpool", "r50_forward"} <= hot
     ops = {op for row in T.ALL_ROWS for op in row.ops}
     assert hot <= ops, f"hot-path ops without a row: {sorted(hot - ops)}"
-    assert "r50_op_resize_frames_u8" in T.BLOCKS_HOST and "r50_op_stem" in T.BLOCKS_HOST       # they synchronise: read r50_abi.hip
+    assert "r50_op_resize_frames_u8" in SO.BLOCKS_HOST and "r50_op_stem" in SO.BLOCKS_HOST       # they synchronise: read r50_abi.hip
 
 
 def test_stale_values_of_every_operand_type():

@@ -4,8 +4,8 @@ The harness is tests/stream_order.py (read its docstring first).  Here:
 
   controls   the harness sees, on the stream ``choose_stream`` returned, a launch misdirected to stream 0 and a missing join, and passes an
              honest call.  They run first: the table tests use the stream they validate.
-  the table  every row of tests/test_guard_bands_gpu.py (ROWS), tests/test_smooth_guard_bands_gpu.py (ROWS_SMOOTH) and
-             tests/test_hal_guard_bands_gpu.py (ROWS_HAL) runs once plainly on the default stream and once in a ``LateArena`` on the side
+  the table  every row of the tables ``r50``, ``smooth`` and ``hal`` of tests/rows/ (the other headers' rows run late from their own
+             test files) runs once plainly on the default stream and once in a ``LateArena`` on the side
              stream, from the same payloads.  Every op claims the same bits on every run, so for every result: snapshot bits == final
              bits == plain bits, and no defined output holds the poison.  No tolerance enters.
   blocking   ``BLOCKS_HOST`` lists the rows that may hold the host until the sleep has ended.  A row outside it that does fails; an
@@ -18,82 +18,28 @@ prove); for a row in ``BLOCKS_HOST``, the launches after the op's internal synch
 wrappers, whatever follows a host read: ``add_protocol_sums`` / ``add_detail_sums`` / ``add_dtw_sums`` (they read ``group`` before they
 launch) and, in ``train_step``, everything after step 1's overflow-flag read.  There only the bits on a side stream are held.
 """
-import json
-import re
-
 import pytest
 import torch
 
 from tests import guard_bands as G
 from tests import stream_order as SO
-from tests.helpers import GOLDEN
-from tests.test_guard_bands_gpu import DEV, ROWS, Arena, _checks_fill, _lib
-from tests.test_hal_guard_bands_gpu import ROWS_HAL
-from tests.test_smooth_guard_bands_gpu import ROWS_SMOOTH
+from tests.guard_bands import DEV, lib
+from tests.rows import TABLES as EVERY_TABLE
+from tests.stream_order import check_blocking_table, run_row_late, side_against_default
 
 pytestmark = pytest.mark.gpu
 
-TABLES = (("r50", ROWS), ("smooth", ROWS_SMOOTH), ("hal", ROWS_HAL))
+TABLES = tuple((name, dict(EVERY_TABLE)[name]) for name in ("r50", "smooth", "hal"))
 ALL_ROWS = [row for _name, table in TABLES for row in table]
 FAMILIES = sorted({row.family for row in ALL_ROWS})
-
-# Rows (by id) or ops (by name: every row that launches it) that may hold the host until the side stream's sleep has ended.  The run on
-# the MI355X added nothing to what reading r50_abi.hip gives: these three rows of 167 held the host (50 ms each, the whole sleep), no other
-# row more than 2.4 ms.  hipMallocAsync / hipFreeAsync in r50_op_bneck_tail and r50_op_bneck_cat_chain do not hold it.
-BLOCKS_HOST = {
-    "r50_op_resize_frames_u8": "copies src_idx to the host and synchronises the stream before it launches",
-    "r50_op_stem": "uploads the packed host weights and synchronises the stream (the packed image is a host temporary)",
-}
-
-# backbone_launch_plan.json counts launches by kind; the op-level entry point(s) of each kind.  "conv1" and "stem_pack" are the stem's two
-# kernels, which r50_forward launches from the handle's resident weights: the op-level r50_op_stem is a test entry point that packs and uploads
-# host weights on every call, and no per-step path calls it.
-PLAN_KIND_OPS = {"avgpool": ("r50_op_avgpool",), "bneck_block2": ("r50_op_bneck_block2",), "bneck_catchain": ("r50_op_bneck_cat_chain",),
-                 "bneck_tail": ("r50_op_bneck_tail",), "bneck_tail3": ("r50_op_bneck_tail",), "conv1": (), "stem_pack": (),
-                 "igemm": ("r50_op_conv2d", "r50_op_conv2d_f16", "r50_op_conv2d_w2", "r50_op_conv2d_split", "r50_op_conv2d_fp8", "r50_op_conv1x1_cat",
-                           "r50_op_bneck_block1", "r50_op_bneck_block1_ds"),
-                 "maxpool": ("r50_op_maxpool",)}
-
-
-def hot_path_ops():
-    """The ops of the per-step hot paths: every op a recorded train step launches (the fp16 head's GEMMs are recorded under
-    ``r50_op_conv2d``), every launch kind of the backbone's plan, and the forward itself."""
-    train = json.loads((GOLDEN / "train_launch_sequences.json").read_text())
-    ops = {re.match(r"r50_op_\w+", what).group(0) for seq in train["sequences"].values() for what in seq}
-    ops.add("r50_op_conv2d_f16")
-    plan = json.loads((GOLDEN / "backbone_launch_plan.json").read_text())
-    kinds = {k for prec in plan["plans"].values() for entry in prec.values() for k in entry["launches"]}
-    assert kinds <= set(PLAN_KIND_OPS), f"launch kinds without an op: {sorted(kinds - set(PLAN_KIND_OPS))}"
-    for k in kinds:
-        ops.update(PLAN_KIND_OPS[k])
-    return ops | {"r50_forward", "r50_forward_u8"}
-
-
-def may_block(row):
-    return row.id in BLOCKS_HOST or any(op in BLOCKS_HOST for op in row.ops)
-
-
-def check_blocking_table():
-    """The conditions on ``BLOCKS_HOST`` (also asserted without a GPU by tests/test_stream_order_cpu.py)."""
-    ids, ops = {row.id for row in ALL_ROWS}, {op for row in ALL_ROWS for op in row.ops}
-    for key, reason in BLOCKS_HOST.items():
-        assert key in ids or key in ops, f"BLOCKS_HOST names `{key}`, which is neither a row nor an op of a row"
-        assert reason.strip(), f"BLOCKS_HOST[{key}] gives no reason"
-    hot = hot_path_ops()
-    listed = [row for row in ALL_ROWS if may_block(row)]
-    for row in listed:
-        bad = sorted(set(row.ops) & hot)
-        assert not bad, f"BLOCKS_HOST admits row {row.id}, which launches hot-path op(s) {bad}: an op of a per-step path must not hold the host"
-    assert len(listed) * 10 <= len(ALL_ROWS), f"BLOCKS_HOST admits {len(listed)} of {len(ALL_ROWS)} rows: more than 10 %"
-
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # a. controls (first in the module: the table tests use the stream they validate)
 # ------------------------------------------------------------------------------------------------------------------------------
 def test_control_a_launch_misdirected_to_stream_0_shows():
-    side, tried = SO.choose_stream(_lib())
+    side, tried = SO.choose_stream(lib())
     print(f"choose_stream: {tried} candidate(s) tried")
-    late, want = SO.cast_rows_probe(_lib(), side, SO.calibrate(), "stream0")
+    late, want = SO.cast_rows_probe(lib(), side, SO.calibrate(), "stream0")
     snap = late.snapshots["dst"]
     assert not late.blocked
     assert torch.isnan(snap).any(), "the op ran on stream 0 during the sleep and still saw its input"
@@ -101,10 +47,10 @@ def test_control_a_launch_misdirected_to_stream_0_shows():
 
 
 def test_control_a_missing_join_shows():
-    side, _ = SO.choose_stream(_lib())
-    second, tried = SO.choose_second_stream(_lib())
+    side, _ = SO.choose_stream(lib())
+    second, tried = SO.choose_second_stream(lib())
     print(f"choose_second_stream: {tried} candidate(s) tried")
-    late, want = SO.cast_rows_probe(_lib(), side, SO.calibrate(), "no_join", other=second)
+    late, want = SO.cast_rows_probe(lib(), side, SO.calibrate(), "no_join", other=second)
     snap = late.snapshots["dst"]
     assert not late.blocked
     assert G.holds_fill(snap, late.fill) == snap.numel(), "the snapshot on the side stream already holds what the unjoined stream wrote"
@@ -112,8 +58,8 @@ def test_control_a_missing_join_shows():
 
 
 def test_control_an_honest_call_passes():
-    side, _ = SO.choose_stream(_lib())
-    late, want = SO.cast_rows_probe(_lib(), side, SO.calibrate(), "honest")
+    side, _ = SO.choose_stream(lib())
+    late, want = SO.cast_rows_probe(lib(), side, SO.calibrate(), "honest")
     assert not late.blocked, "the host was held until the sleep ended: the sleep is too short, see calibrate()"
     assert torch.equal(G.bits(late.snapshots["dst"]), want) and torch.equal(G.bits(late.results["dst"]), want)
 
@@ -121,38 +67,6 @@ def test_control_an_honest_call_passes():
 # ------------------------------------------------------------------------------------------------------------------------------
 # b. + c. every row, late on the side stream; which rows hold the host
 # ------------------------------------------------------------------------------------------------------------------------------
-def run_row_late(row):
-    side, _ = SO.choose_stream(_lib())
-    payloads = row.make()
-    try:
-        plain = Arena(None)
-        row.launch(plain, payloads)
-        torch.cuda.synchronize()
-        if row.scrub is not None:
-            row.scrub(payloads)        # a handle's buffers must not still hold what these very payloads left there
-        late = SO.LateArena(side, SO.calibrate())
-        with torch.cuda.stream(side):
-            row.launch(late, payloads)
-            late.finish()
-    finally:
-        for v in payloads if isinstance(payloads, tuple) else ():
-            if hasattr(v, "close"):
-                v.close()              # a backbone handle
-    print(f"stream_order row {row.id}: host {late.enqueue_ms:.2f} ms from the first inp to launch returning, blocked {late.blocked}")
-    assert plain.results and list(late.results) == list(plain.results), f"{row.id}: result names differ between the runs"
-    for name, want in plain.results.items():
-        SO.assert_same_bits(row.id, name, "snapshot", late.snapshots[name], want)
-        SO.assert_same_bits(row.id, name, "final tensor", late.results[name], want)
-        if late.defined.get(name) and _checks_fill(want, late.fill):
-            n = G.holds_fill(late.snapshots[name], late.fill)
-            assert n == 0, f"{row.id}: {n} of {want.numel()} elements of output `{name}` still hold the poison in the snapshot"
-    if late.blocked and not may_block(row):
-        raise AssertionError(f"{row.id}: the host was held until the side stream's sleep had ended ({late.enqueue_ms:.1f} ms): either it "
-                             "synchronises the host, or the sleep is too short: see calibrate()")
-    if may_block(row) and not late.blocked:
-        raise AssertionError(f"{row.id}: listed in BLOCKS_HOST, but it did not hold the host: the entry is stale")
-
-
 def _rows_of(family):
     rows = [r for r in ALL_ROWS if r.family == family]
     return pytest.mark.parametrize("row", rows, ids=[r.id for r in rows])
@@ -172,47 +86,12 @@ for _family in FAMILIES:
 
 
 def test_the_blocking_table_keeps_its_conditions():
-    check_blocking_table()
+    check_blocking_table(ALL_ROWS)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # e. the Python entry points: side stream with late tensor inputs against the default stream, bit-equal
 # ------------------------------------------------------------------------------------------------------------------------------
-def _tensors_of(result):
-    """name -> tensor for whatever a wrapper returned: a tensor, a tuple of tensors (None entries left out) or a dict."""
-    if isinstance(result, torch.Tensor):
-        return {"result": result}
-    if isinstance(result, dict):
-        return {str(k): v for k, v in result.items() if isinstance(v, torch.Tensor)}
-    return {f"result[{i}]": v for i, v in enumerate(result) if isinstance(v, torch.Tensor)}
-
-
-def side_against_default(what, call, inputs, scrub=None):
-    """``call(late, tensors)`` once on the default stream (late = None) and once under ``with torch.cuda.stream(S)`` (late = the ``LateArena``)
-    with every tensor of ``inputs`` produced late on ``S``: behind the sleep, by a device copy from staging.  Whatever tensors it returns are
-    snapshot on ``S`` right after the call; snapshot bits == final bits == default-stream bits.  Returns the late arena (``blocked`` tells
-    whether the wrapper held the host, which a wrapper that reads a result on the host does by design).  ``scrub()`` runs between the two:
-    an object with cached workspaces (a head, a backbone handle) gets another batch, so that a launch which read a workspace too early
-    would not find there what the same inputs left a moment ago."""
-    side, _ = SO.choose_stream(_lib())
-    want = _tensors_of(call(None, {k: v.to(DEV) for k, v in inputs.items()}))
-    torch.cuda.synchronize()
-    if scrub is not None:
-        scrub()
-        torch.cuda.synchronize()
-    late = SO.LateArena(side, SO.calibrate())
-    with torch.cuda.stream(side):
-        got = _tensors_of(call(late, {k: late.inp(k, v) for k, v in inputs.items()}))
-        late.results.update(got)
-        late.finish()
-    assert want and list(got) == list(want), f"{what}: result names differ between the runs"
-    for name, w in want.items():
-        SO.assert_same_bits(what, name, "snapshot", late.snapshots[name], w)
-        SO.assert_same_bits(what, name, "final tensor", late.results[name], w)
-    print(f"stream_order wrapper {what}: host {late.enqueue_ms:.2f} ms, blocked {late.blocked}")
-    return late
-
-
 @pytest.mark.parametrize("precision", ["fp16", "bf16"])
 def test_head_forward_and_rollout_on_a_side_stream(precision):
     from tests.test_rollout_gpu import _head
@@ -327,7 +206,7 @@ def test_evaluation_wrappers_on_a_side_stream():
     from implementation_phd_lab_vision_amd import baselines, detail_metrics, dtw, protocols, sequences, smooth
     from tests import baselines_reference as br
     from tests import detail_reference as dr
-    from tests.test_guard_bands_gpu import _detail_make, _dtw_make, _seq_make, _stitch_make
+    from tests.rows.r50 import _detail_make, _dtw_make, _seq_make, _stitch_make
     F64 = torch.float64
 
     b, p, t_gt, i0, j, ng, root, n_thr = case = (5, 3, 7, 2, 17, 4, 0, 31)

@@ -1,4 +1,4 @@
-"""The op of include/r50_track.h between poisoned guard bands, with the harness of tests/test_guard_bands_gpu.py: each row runs plain,
+"""The op of include/r50_track.h between poisoned guard bands, with the harness of tests/guard_bands.py on the rows of tests/rows/track.py: each row runs plain,
 between 0xFF bands and between 0x7B bands from the same payloads; both outputs hold the same bits in the three runs and every band of
 every operand (the byte buffer, the table and both outputs) is intact.  The rows: the ragged table of tests/track_reference.py (7
 images of different sizes at byte offsets of every residue mod 4; the last image ends the buffer 1, 2 or 3 bytes past a dword boundary
@@ -6,59 +6,12 @@ and its box ends at the last byte, so the byte-wise tail read runs right in fron
 and without ``out_flip``.
 
 tests/test_track_cpu.py holds this table complete for the header, as tests/test_guard_bands_cpu.py does for include/r50.h."""
-import functools
-
 import pytest
-import torch
 
-from tests import track_reference as TR
-from tests.test_guard_bands_gpu import Arena, Row, run_row  # noqa: F401  (Arena: the type ``launch`` receives)
+from tests.guard_bands import run_row
+from tests.rows.track import ROWS_TRACK
 
 pytestmark = pytest.mark.gpu
-U8 = torch.uint8
-
-ROWS_TRACK = []
-
-
-@functools.lru_cache(maxsize=None)
-def _lib():
-    from implementation_phd_lab_vision_amd import _lib as L
-    L.build_library()
-    return L.load_library()
-
-
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _make(out_size, mode, tail):
-    from implementation_phd_lab_vision_amd.track import BoxTable
-    c = TR.ragged_case(out_size, tail)
-    table = BoxTable(c["offsets"], c["sizes"], c["boxes"], c["src_bytes"], out_size, mode)
-    return dict(buf=c["buf"], table=torch.from_numpy(table.host), t=table.t, max_ww=table.max_ww, src_bytes=c["src_bytes"], out=out_size,
-                mode=mode)
-
-
-def _launch(flip):
-    def launch(a, pay):
-        # the widest image's two staged rows plus the dword rounding at either end: what a wrong row or column index could reach
-        a.reach(2 * 80 * 3 + 8)
-        src, table = a.inp("src", pay["buf"]), a.inp("table", pay["table"])
-        shape = (pay["t"], 3, pay["out"], pay["out"])
-        out = a.out("out", shape, U8)
-        out_flip = a.out("out_flip", shape, U8) if flip else None
-        rc = _lib().r50_op_crop_resize_boxes_u8(src.data_ptr(), pay["src_bytes"], table.data_ptr(), pay["t"], pay["max_ww"], out.data_ptr(),
-                                                None if out_flip is None else out_flip.data_ptr(), pay["out"], pay["mode"], _s())
-        assert rc == 0, _lib().r50_last_error(None)
-    return launch
-
-
-for _out in (8, 224):
-    for _mode, _name in ((0, "float"), (1, "fixed")):
-        for _flip in (False, True):
-            for _tail in TR.TAILS:
-                ROWS_TRACK.append(Row("track", f"crop_resize_boxes_u8-ragged-out{_out}-{_name}-tail{_tail}" + ("-flip" if _flip else ""),
-                                      ("r50_op_crop_resize_boxes_u8",), functools.partial(_make, _out, _mode, _tail), _launch(_flip)))
 
 
 @pytest.mark.parametrize("row", ROWS_TRACK, ids=[r.id for r in ROWS_TRACK])

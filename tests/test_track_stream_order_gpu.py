@@ -1,10 +1,10 @@
-"""The rows of tests/test_track_guard_bands_gpu.py late on a side stream, with the harness of tests/test_stream_order_gpu.py: each row
+"""The rows of tests/rows/track.py late on a side stream, with the harness of tests/stream_order.py: each row
 runs once plainly on the default stream and once on the side stream while its byte buffer and its table are still stale; snapshot bits
 == final bits == plain bits, and the op does not hold the host."""
 import pytest
 
-from tests.test_stream_order_gpu import run_row_late
-from tests.test_track_guard_bands_gpu import ROWS_TRACK
+from tests.rows.track import ROWS_TRACK
+from tests.stream_order import run_row_late
 
 pytestmark = pytest.mark.gpu
 

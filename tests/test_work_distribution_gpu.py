@@ -17,6 +17,7 @@ import contextlib
 
 import pytest
 import torch
+from tests.network_oracles import _oracle_bar  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -561,26 +562,6 @@ def test_fused_stem_uint8_frames(cap, precision):
 
 # ---- 3. whole network -------------------------------------------------------------------------------------------------------------
 NET_CAPS = (1, 5, 32, 100)
-
-
-def _oracle_bar(precision, bb):
-    """That precision's features check of tests/test_network_gpu.py, on its fixture's frames and with its limits."""
-    from tests import test_network_gpu as T
-    if precision == "bf16":
-        _sd, x, _taps, _drift, feats_emu, feats_ref = T.oracle_bf16()
-        T.check_features_bf16(bb, x, feats_emu, feats_ref)
-    elif precision == "fp16":
-        _sd, x, ref, emu, _taps = T.oracle_fp16()
-        T.check_features_fp16(bb, x, ref, emu)
-    elif precision == "bf16w2":
-        _sd, x, ref, emu, _taps = T.oracle_bf16w2()
-        T.check_features_bf16w2(bb, x, ref, emu)
-    elif precision == "fp32x":
-        _sd, x, _taps, feats_ref = T.oracle_fp32x()
-        T.check_features_fp32x(bb, x, feats_ref)
-    else:
-        _sd, x, emu, ref = T.oracle_fp8(tuple(bb.fp8_scales))
-        T.check_features_fp8(bb, x, emu, ref)
 
 
 @pytest.mark.parametrize("precision", ["bf16", "fp16", "fp8", "bf16w2", "fp32x"])
