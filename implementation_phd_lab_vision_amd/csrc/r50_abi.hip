@@ -142,6 +142,26 @@ int need_aligned(r50_handle* h, const char* op, std::initializer_list<AlignedArg
     return 0;
 }
 
+// Size limits (include/r50.h states them per entry point; DESIGN.md section 4, "Size limits"): fill_conv_args and the launchers check them
+// with size_over, which notes the quantity, its value and the bound; the entry point's (or the network's) fail() message carries the note
+// (size_why takes it), so a refusal names the op, the quantity and the bound.
+thread_local std::string t_size_why;
+bool size_over(const char* quantity, long long value, long long bound, const char* bound_text) {
+    if (value < bound) return false;
+    t_size_why = std::string(quantity) + " = " + std::to_string(value) + " must be < " + bound_text;
+    return true;
+}
+std::string size_why(const std::string& otherwise = std::string()) {
+    std::string s = t_size_why.empty() ? otherwise : t_size_why;
+    t_size_why.clear();
+    return s;
+}
+std::string size_suffix() {          // ": <the note>" behind a message that already names the op, or nothing
+    const std::string s = size_why();
+    return s.empty() ? s : ": " + s;
+}
+constexpr long long k2p31 = 1ll << 31;
+
 #define HIP_TRY(h, expr)                                                                          \
     do {                                                                                          \
         hipError_t e_ = (expr);                                                                   \
@@ -654,9 +674,8 @@ int fill_conv_args(ConvArgs& a, const void* x, int n, int h, int w, int cin, con
     if (a.Ho <= 0 || a.Wo <= 0) return R50_ERR_INVALID;
     a.ks = ks; a.stride = stride; a.pad = pad; a.relu = relu;
     const long long M = (long long)n * a.Ho * a.Wo;
-    // 32-bit index budget of the kernel: byte offsets of x / y stay below 2^32 elements*2
-    if (M > (1ll << 30) || (long long)n * h * w * cin > (1ll << 31) - 1 || M * cout > (1ll << 31) - 1)
-        return R50_ERR_INVALID;
+    // 32-bit index budget of the kernel: pixel indices fit the FastDiv range (the byte checks below are the tighter ones in every mode)
+    if (size_over("output pixels n*ho*wo", M, (1ll << 30) + 1, "2^30 + 1")) return R50_ERR_INVALID;
     a.M = (int)M; a.HoWo = a.Ho * a.Wo;
     // split mode: X is [head(cin) | tail(cin)] per pixel, K per tap is 3*cin, Y is [head(cout) | tail(cout)]
     a.x_cstride = split ? 2 * cin : cin;
@@ -668,9 +687,12 @@ int fill_conv_args(ConvArgs& a, const void* x, int n, int h, int w, int cin, con
     a.n_ctiles = 0; a.n_blocks = 0;
     // buffer descriptors of the kernel (kernels.h): every offset must stay below 2^31
     const long long x_bytes = (long long)n * h * w * a.x_cstride * 2;
-    a.x_back = (pad * w + pad) * a.x_cstride * 2;
-    if (x_bytes + a.x_back >= (1ll << 31) || (long long)cout * a.Ktot * 2 >= (1ll << 31) || M * a.y_cstride * 2 >= (1ll << 31))
+    const long long x_back = ((long long)pad * w + pad) * a.x_cstride * 2;
+    if (size_over("x bytes + back reach, n*h*w*cx*2 + (pad*w+pad)*cx*2 (cx = channels per x pixel),", x_bytes + x_back, k2p31, "2^31") ||
+        size_over("w bytes, cout*K*2 (K = weight elements per cout),", (long long)cout * ks * ks * kmul * cin * 2, k2p31, "2^31") ||
+        size_over("y bytes, n*ho*wo*cy*2 (cy = channels per y pixel),", M * a.y_cstride * 2, k2p31, "2^31"))
         return R50_ERR_INVALID;
+    a.x_back = (int)x_back;
     a.x_records = (unsigned)(x_bytes + a.x_back);
     a.w_bytes = (unsigned)((long long)cout * a.Ktot * 2);
     a.y_bytes = (unsigned)(M * a.y_cstride * 2);
@@ -714,7 +736,7 @@ int profiled(r50_handle* h, hipStream_t s, int cls, double flops, double bytes, 
     const hipError_t e = launch();
     prof_end(h, s, r);
     if (e == hipSuccess) return R50_OK;
-    return fail(h, R50_ERR_HIP, what + (key.empty() ? std::string() : " (" + key + key_suffix + ")") + ": " + hipGetErrorString(e));
+    return fail(h, R50_ERR_HIP, what + (key.empty() ? std::string() : " (" + key + key_suffix + ")") + ": " + hipGetErrorString(e) + size_suffix());
 }
 
 // conv3 (64 -> 256) + identity + ReLU + next conv1 (256 -> c1) in one launch (kernels.h: bneck_tail_kernel).
@@ -734,7 +756,8 @@ hipError_t launch_bneck_tail_t(const TailArgs& a, hipStream_t s) {
 #endif
 hipError_t launch_bneck_tail(const void* y2, long long m, const void* w3, const float* b3, const void* res, const void* wd,
                              const float* bd, void* out, const void* w1, int c1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
-    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0 || m * 512 >= (1ll << 31)) return hipErrorInvalidValue;
+    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0) return hipErrorInvalidValue;
+    if (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*256*2,", m * 512, k2p31, "2^31")) return hipErrorInvalidValue;
     if ((c1 != 64 && c1 != 128) || ((wd == nullptr) != (bd == nullptr))) return hipErrorInvalidValue;
     TailArgs a;
     a.y2 = (const __bf16*)y2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
@@ -752,7 +775,8 @@ hipError_t launch_bneck_tail(const void* y2, long long m, const void* w3, const 
 // layer2 shapes: conv3 (128 -> 512) + identity + ReLU + next conv1 (512 -> 128) (kernels.h: bneck_tail2_kernel)
 hipError_t launch_bneck_tail2(const void* y2, long long m, const void* w3, const float* b3, const void* res, void* out,
                               const void* w1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
-    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0 || m * 1024 >= (1ll << 31)) return hipErrorInvalidValue;
+    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0) return hipErrorInvalidValue;
+    if (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*512*2,", m * 1024, k2p31, "2^31")) return hipErrorInvalidValue;
     Tail2Args a;
     a.y2 = (const __bf16*)y2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
     a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.M = (int)m;
@@ -779,7 +803,8 @@ hipError_t launch_bneck_tail3(const void* y2, long long m, const void* wp, const
                               const float* b1, void* y1n, hipStream_t s, int et = 0, int bp_override = 0, bool no_next = false) {
     if (no_next) { b1 = b3; y1n = out; }       // conv3 + identity + ReLU only (group B copies out): b1 / y1n are not used
     if (bp_override == 0) bp_override = g_tail3_bp;
-    if (!y2 || !wp || !b3 || !res || !out || !b1 || !y1n || m <= 0 || m * 2048 >= (1ll << 31)) return hipErrorInvalidValue;
+    if (!y2 || !wp || !b3 || !res || !out || !b1 || !y1n || m <= 0) return hipErrorInvalidValue;
+    if (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*1024*2,", m * 2048, k2p31, "2^31")) return hipErrorInvalidValue;
     const int cus = num_cus();
     if (cus == 0) return hipErrorInvalidDevice;
     Tail3Args a;
@@ -820,7 +845,9 @@ hipError_t launch_bneck_catchain(const void* t2, const void* x, int n, int ow, c
                                  const float* b1, void* y1n, hipStream_t s, int et = 0, bool x_sub = false) {
     if (!t2 || !x || !wp || !bcat || !out || !b1 || !y1n || n <= 0 || ow != 28) return hipErrorInvalidValue;
     const long long m = (long long)n * ow * ow;
-    if (m * 1024 >= (1ll << 31) || (long long)n * 4 * ow * ow * 512 >= (1ll << 31)) return hipErrorInvalidValue;
+    if (size_over("out bytes, n*ow*ow*512*2,", m * 1024, k2p31, "2^31") ||
+        size_over("x bytes, n*(2*ow)*(2*ow)*256*2,", (long long)n * 4 * ow * ow * 512, k2p31, "2^31"))
+        return hipErrorInvalidValue;
     const int cus = num_cus();
     if (cus == 0) return hipErrorInvalidDevice;
     CatChainArgs a;
@@ -842,7 +869,8 @@ hipError_t launch_bneck_catchain(const void* t2, const void* x, int n, int ow, c
 // layer2.1-.3 bottleneck body in one launch (kernels.h: bneck_block2_kernel): conv2 + conv3 + identity + ReLU [+ the next block's conv1]
 hipError_t launch_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                                void* out, const void* w1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
-    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || n <= 0 || (long long)n * 784 * 1024 >= (1ll << 31)) return hipErrorInvalidValue;
+    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || n <= 0) return hipErrorInvalidValue;
+    if (size_over("out bytes, n*28*28*512*2,", (long long)n * 784 * 1024, k2p31, "2^31")) return hipErrorInvalidValue;
     if ((w1 == nullptr) != (b1 == nullptr) || (w1 == nullptr) != (y1n == nullptr)) return hipErrorInvalidValue;
     Block2Args a;
     a.t1 = (const __bf16*)t1; a.w2 = (const __bf16*)w2; a.b2 = b2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res;
@@ -858,7 +886,8 @@ hipError_t launch_bneck_block2(const void* t1, int n, const void* w2, const floa
 hipError_t launch_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                                void* out, const void* w1, int c1, const float* b1, void* y1n, hipStream_t s, int et = 0,
                                const void* wd = nullptr, const float* bd = nullptr, bool out_sub = false) {
-    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || n <= 0 || (long long)n * 3136 * 512 >= (1ll << 31)) return hipErrorInvalidValue;
+    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || n <= 0) return hipErrorInvalidValue;
+    if (size_over("out bytes, n*56*56*256*2,", (long long)n * 3136 * 512, k2p31, "2^31")) return hipErrorInvalidValue;
     if (c1 != 64 && c1 != 128) return hipErrorInvalidValue;
     if ((wd == nullptr) != (bd == nullptr) || (wd && c1 != 64)) return hipErrorInvalidValue;       // downsample form: layer1.0 (next conv1 256 -> 64)
     Block1Args a;
@@ -880,7 +909,7 @@ int run_conv(r50_handle* h, const ConvLayer& L, const __bf16* x, int n, int hh, 
     const bool split = (h->precision == R50_PREC_FP32X);
     const bool w2 = (h->precision == R50_PREC_BF16W2);
     int rc = fill_conv_args(a, x, n, hh, ww, L.cin, L.w, L.bias, res, y, L.cout, L.ks, L.stride, L.pad, relu, split, w2);
-    if (rc) return fail(h, rc, "conv args invalid for " + L.conv_key);
+    if (rc) return fail(h, rc, "conv args invalid for " + L.conv_key + size_suffix());
     a.et = (h->precision == R50_PREC_FP16) ? 1 : 0;
     const double flops = 2.0 * a.M * (double)a.Cout * L.ks * L.ks * L.cin;       // algorithmic (not the 3x of split mode)
     const double bytes = 2.0 * ((double)n * hh * ww * L.cin + (double)a.M * a.Cout * (res ? 2 : 1) + (double)a.Cout * L.ks * L.ks * L.cin);
@@ -906,7 +935,9 @@ int fill_conv_args_cat(ConvArgs& a, const void* x1, int n, int h, int w, int c1,
     int rc = fill_conv_args(a, x1, n, h, w, c1, wcat, bias, nullptr, y, cout, 1, 1, 0, relu);
     if (rc) return rc;
     const long long x2_bytes = (long long)n * h2 * w2 * c2 * 2;
-    if (x2_bytes >= (1ll << 31) || (long long)cout * (c1 + c2) * 2 >= (1ll << 31)) return R50_ERR_INVALID;
+    if (size_over("x2 bytes, n*h2*w2*c2*2,", x2_bytes, k2p31, "2^31") ||
+        size_over("wcat bytes, cout*(c1+c2)*2,", ((long long)c1 + c2) * cout * 2, k2p31, "2^31"))
+        return R50_ERR_INVALID;
     a.Cin = c1 + c2;
     a.cin_chunks = (c1 + c2) / 64; a.nk = a.cin_chunks; a.Ktot = c1 + c2;
     a.w_bytes = (unsigned)((long long)cout * a.Ktot * 2);
@@ -930,7 +961,7 @@ int run_conv_cat(r50_handle* h, int si, const ConvLayer& c3, const ConvLayer& cd
                  int hin, int win, __bf16* y, hipStream_t s) {
     ConvArgs a;
     int rc = fill_conv_args_cat(a, t2, n, h2, w2, c3.cin, xin, hin, win, cd.cin, cd.stride, h->cat_w[si], h->cat_bias[si], y, c3.cout, 1);
-    if (rc) return fail(h, rc, "two-source conv args invalid for " + c3.conv_key);
+    if (rc) return fail(h, rc, "two-source conv args invalid for " + c3.conv_key + size_suffix());
     a.et = (h->precision == R50_PREC_FP16) ? 1 : 0;
     const double flops = 2.0 * a.M * (double)a.Cout * a.Ktot;
     const double bytes = 2.0 * ((double)a.M * (c3.cin + cd.cin) + (double)a.M * a.Cout + (double)a.Cout * a.Ktot);
@@ -1036,7 +1067,7 @@ int run_conv_fp8(r50_handle* h, const ConvLayer& L, const void* x, int n, int hh
                  float sr, float sy, hipStream_t s, int* ho, int* wo) {
     ConvArgs a;
     int rc = fill_conv_args(a, x, n, hh, ww, L.cin / 2, L.w, L.bias_scaled, res, y, L.cout, L.ks, L.stride, L.pad, relu);
-    if (rc) return fail(h, rc, "fp8 conv args invalid for " + L.conv_key);
+    if (rc) return fail(h, rc, "fp8 conv args invalid for " + L.conv_key + size_suffix());
     a.y_bytes = (unsigned)((long long)a.M * L.cout);
     a.et = 2; a.oscale = sx * L.wscale / sy; a.rscale = sr / sy;
     const double flops = 2.0 * a.M * (double)a.Cout * L.ks * L.ks * L.cin;
@@ -1093,7 +1124,7 @@ int run_fp8_part(r50_handle* h, __bf16* const* buf, int cur, int n, float* out, 
                 ConvArgs a;
                 rc = fill_conv_args_cat(a, buf[fr[1]], n, h2, w2, c3.cin / 2, buf[cur], hh, ww, cd.cin / 2, cd.stride, h->cat_w[si], h->cat_bias[si],
                                         buf[fr[3]], c3.cout, 1);
-                if (rc) return fail(h, rc, "fp8 two-source conv args invalid for " + c3.conv_key);
+                if (rc) return fail(h, rc, "fp8 two-source conv args invalid for " + c3.conv_key + size_suffix());
                 a.y_bytes = (unsigned)((long long)a.M * c3.cout);
                 a.et = 2; a.oscale = h->cat_acc_scale[si] / s_out; a.rscale = 0.f;
                 const double flops = 2.0 * a.M * (double)a.Cout * (c3.cin + cd.cin);
@@ -1865,7 +1896,7 @@ static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, con
 // what an r50_op_* hook returns for its launch: hipErrorInvalidValue is the launcher refusing the arguments
 static int op_status(hipError_t e, const char* op) {
     if (e == hipSuccess) return R50_OK;
-    return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP, std::string(op) + ": " + hipGetErrorString(e));
+    return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP, std::string(op) + ": " + size_why(hipGetErrorString(e)));
 }
 
 int r50_op_conv2d(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
@@ -1888,7 +1919,7 @@ static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, con
                         void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
     ConvArgs a;
     int rc = fill_conv_args(a, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d: invalid arguments");
+    if (rc) return fail(nullptr, rc, std::string(et == 1 ? "r50_op_conv2d_f16: " : "r50_op_conv2d: ") + size_why("invalid arguments"));
     a.et = et;
 #if defined(R50_STAMP)
     a.dbg = g_dbg;
@@ -1906,7 +1937,7 @@ int r50_op_conv2d_w2(const void* x, int n, int h, int w, int cin, const void* w_
         return rc_al;
     ConvArgs a;
     int rc = fill_conv_args(a, x, n, h, w, cin, w_pair, bias, res, y, cout, ksize, stride, pad, relu, false, true);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d_w2: invalid arguments");
+    if (rc) return fail(nullptr, rc, "r50_op_conv2d_w2: " + size_why("invalid arguments"));
     // only igemm_bf16_kernel and igemm_ws_kernel wrap the X chunk index (ConvArgs::x_wrap): the shape-specialised kernels walk K on their own
     if (tile == kTileC64 || tile == kTileXres || tile == kTileS2 || tile == kTileG8 || tile == kTileG8N7)
         return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_w2: tile id " + std::to_string(tile) + " does not read the weight pair");
@@ -1921,7 +1952,7 @@ int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const 
         return rc_al;
     ConvArgs a;
     int rc = fill_conv_args(a, x_pair, n, h, w, cin, w_trip, bias, res_pair, y_pair, cout, ksize, stride, pad, relu, true, false);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d_split: invalid arguments");
+    if (rc) return fail(nullptr, rc, "r50_op_conv2d_split: " + size_why("invalid arguments"));
     hipError_t e = launch_igemm(a, 0, (hipStream_t)stream, true);
     return op_status(e, "r50_op_conv2d_split");
 }
@@ -1935,7 +1966,7 @@ int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* w
     ConvArgs a;
     // the loaders move bytes: described in 2-byte units, an fp8 tensor with cin channels is a 16-bit tensor with cin / 2
     int rc = fill_conv_args(a, x, n, h, w, cin / 2, wt, bias_scaled, res, y, cout, ksize, stride, pad, relu);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d_fp8: invalid arguments");
+    if (rc) return fail(nullptr, rc, "r50_op_conv2d_fp8 (sizes as 16-bit pairs: cx = cin/2, cy = cout): " + size_why("invalid arguments"));
     a.y_bytes = (unsigned)((long long)a.M * cout);       // one byte per output element
     a.et = 2; a.oscale = oscale; a.rscale = rscale;
     hipError_t e = launch_igemm_fp8(a, tile, (hipStream_t)stream);
@@ -1949,7 +1980,7 @@ int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* 
         return rc_al;
     ConvArgs a;
     int rc = fill_conv_args_cat(a, x1, n, h, w, c1, x2, h2, w2, c2, stride2, wcat, bias, y, cout, relu);
-    if (rc || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv1x1_cat: invalid arguments");
+    if (rc || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv1x1_cat: " + size_why("invalid arguments"));
     a.et = et;
     hipError_t e = launch_igemm(a, cat_tile(a, tile), (hipStream_t)stream);
     return op_status(e, "r50_op_conv1x1_cat");
@@ -1967,6 +1998,10 @@ int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const
         return rc_al;
     hipError_t e;
     const int et = op_et();
+    // the size limit before anything is queued (the cmid = 256 forms pack their weights on the stream first): out is the largest tensor
+    if ((cmid == 64 || cmid == 128 || cmid == 256) && m > 0 &&
+        (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*4*cmid*2,", m * 8 * cmid, k2p31, "2^31")))
+        return op_status(hipErrorInvalidValue, "r50_op_bneck_tail");
     if (cmid == 64) e = launch_bneck_tail(y2, m, w3, b3, res, wd, bd, out, w1, c1, b1, y1n, (hipStream_t)stream, et);
     else if (cmid == 128 && c1 == 128 && !wd && !bd) e = launch_bneck_tail2(y2, m, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, et);
     else if (cmid == 256 && c1 == 0 && !w1 && !b1 && !y1n && !wd && !bd) {
@@ -2022,6 +2057,10 @@ int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const v
     // plain weight matrices in, packed per call into a buffer allocated and freed in the caller's stream order (as r50_op_bneck_tail does)
     void* wp = nullptr;
     if (!wcat || !w1) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_cat_chain: null weights");
+    // the size limits before anything is queued (the weights are packed on the stream first)
+    if (n > 0 && ow == 28 && (size_over("out bytes, n*ow*ow*512*2,", (long long)n * ow * ow * 1024, k2p31, "2^31") ||
+                              size_over("x bytes, n*(2*ow)*(2*ow)*256*2,", (long long)n * 4 * ow * ow * 512, k2p31, "2^31")))
+        return op_status(hipErrorInvalidValue, "r50_op_bneck_cat_chain");
     if (hipMallocAsync(&wp, kCatChainPackedBytes, (hipStream_t)stream) != hipSuccess || !wp)
         return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_cat_chain: hipMallocAsync");
     hipError_t e = pack_catchain_weights(wcat, w1, wp, (hipStream_t)stream);
@@ -3074,6 +3113,8 @@ int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_de
                                                  {y, "y_nhwc_bf16", 16}}))
         return rc_al;
     if (!x || !w_host || !bias_dev || !scratch || !y || n < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_stem: invalid arguments");
+    // stem_conv_kernel runs one workgroup per (image, 4 output rows): the grid is an int (every offset inside both kernels is 64-bit)
+    if (size_over("workgroups n*28", (long long)n * (112 / STEM_ROWS_PER_WG), k2p31, "2^31")) return fail(nullptr, R50_ERR_INVALID, "r50_op_stem: " + size_why());
     std::vector<uint16_t> pk;
     const int et = op_et();
     pack_stem(w_host, pk, et == 1 ? 2 : 0);
@@ -3089,6 +3130,9 @@ int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_de
 int r50_op_maxpool(const void* x, int n, int h, int w, int c, void* y, void* stream) {
     if (int rc_al = need_aligned(nullptr, "r50_op_maxpool", {{x, "x_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}})) return rc_al;
     if (!x || !y || n < 1 || h < 1 || w < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_maxpool: invalid arguments");
+    // maxpool3x3s2_kernel counts and addresses in 64 bits (a grid-stride loop over at most 2^14 workgroups): the limit is the byte offset itself
+    if ((__int128)n * h * w * c * 2 >= ((__int128)1 << 63))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_maxpool: x bytes, n*h*w*c*2, must be < 2^63");
     HIP_TRY(nullptr, launch_maxpool(x, y, n, h, w, c, (hipStream_t)stream, op_et()));
     return R50_OK;
 }
@@ -3096,6 +3140,11 @@ int r50_op_maxpool(const void* x, int n, int h, int w, int c, void* y, void* str
 int r50_op_avgpool(const void* x, int n, int hw, int c, float* y, void* stream) {
     if (int rc_al = need_aligned(nullptr, "r50_op_avgpool", {{x, "x_nhwc_bf16", 16}, {y, "y_f32", 16}})) return rc_al;
     if (!x || !y || n < 1 || hw < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: invalid arguments");
+    // avgpool_kernel: one thread per (image, 8 channels), numbered in an int over a grid rounded up to 256 threads; the row offsets are 64-bit
+    if (size_over("threads n*(c/8) + 255", (long long)n * (c / 8) + 255, k2p31, "2^31"))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: " + size_why());
+    if ((__int128)n * hw * c * 2 >= ((__int128)1 << 63))
+        return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: x bytes, n*hw*c*2, must be < 2^63");
     HIP_TRY(nullptr, launch_avgpool(x, y, n, hw, c, (hipStream_t)stream, op_et()));
     return R50_OK;
 }

@@ -185,15 +185,24 @@ const char* r50_version(void);
  * Alignment of the convolution, bottleneck, stem and pool hooks: every tensor, weight and bias pointer is R50_ALIGNED(16).  The loaders
  * move 16 bytes per lane through buffer descriptors built on x, w, residual and y (LDS-direct loads included), the shape-specialised
  * and fused kernels read w / w1 / w3 / wd as 16-byte vectors, and the epilogues read the bias as f32x4; the channel checks (cin, cout
- * multiples of 64, 128 for fp8; c % 8 for the pools) make every pixel row a multiple of 16 bytes as well. ---- */
+ * multiples of 64, 128 for fp8; c % 8 for the pools) make every pixel row a multiple of 16 bytes as well.
+ * Size limits ("Size limits").  The matrix-core kernels address every activation tensor through a buffer descriptor and
+ * 32-bit byte offsets, and mark a padded tap with the offset 2^31, which the descriptor's range check turns into zeros: a tensor's bytes
+ * (for x plus the reach of a padded tap behind its last pixel) must stay BELOW 2^31.  Each entry point states its limits in terms of its
+ * arguments ("Size limits:" in its comment; products are exact integers, ho / wo the output height / width).  One step beyond a limit
+ * returns R50_ERR_INVALID before anything is queued on the stream, r50_last_error() names the op, the quantity with its value, and the
+ * bound, and no operand was touched.  tests/test_size_limits_gpu.py runs every entry point exactly at its limit and one image beyond. ---- */
 
 /* conv2d(k x k, stride, pad, bias=folded BN) [+ residual] [+ ReLU].  w_ohwi_bf16: (cout,k,k,cin)
  * bf16; bias fp32 (cout); residual/y: (n,ho,wo,cout) bf16.  cin % 64 == 0, cout % 64 == 0,
- * k in {1,3}.  tile: 0 = auto, else a tile-config id.  */
+ * k in {1,3}.  tile: 0 = auto, else a tile-config id.
+ * Size limits: n*ho*wo <= 2^30; n*h*w*cin*2 + (pad*w+pad)*cin*2 < 2^31 (x bytes, plus what a padded tap reaches behind them);
+ * n*ho*wo*cout*2 < 2^31 (y, and the residual); cout*k*k*cin*2 < 2^31 (w).  The same for every tile id.  */
 int r50_op_conv2d(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_ohwi_bf16,
                   const float* R50_ALIGNED(16) bias_f32, const void* R50_ALIGNED(16) residual_nhwc_bf16, void* R50_ALIGNED(16) y_nhwc_bf16,
                   int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
-/* The same with IEEE-half tensors (R50_PREC_FP16's element type). */
+/* The same with IEEE-half tensors (R50_PREC_FP16's element type).  Size limits: those of r50_op_conv2d, term for term (n*ho*wo <= 2^30, and
+ * below 2^31: n*h*w*cin*2 + (pad*w+pad)*cin*2, n*ho*wo*cout*2, cout*k*k*cin*2). */
 int r50_op_conv2d_f16(const void* R50_ALIGNED(16) x_nhwc_f16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_ohwi_f16,
                   const float* R50_ALIGNED(16) bias_f32, const void* R50_ALIGNED(16) residual_nhwc_f16, void* R50_ALIGNED(16) y_nhwc_f16,
                   int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
@@ -208,7 +217,10 @@ int r50_op_conv2d_f16(const void* R50_ALIGNED(16) x_nhwc_f16, int n, int h, int 
  *  r50_op_conv2d_split: x_pair (n,h,w,2*cin) = [head(cin) | tail(cin)] per pixel; w_trip (cout,k,k,3*cin) = [w_head | w_head | w_tail]
  *    per tap, the packed layout of fp32x mode; residual_pair / y_pair (n,ho,wo,2*cout) = [head(cout) | tail(cout)] per pixel:
  *    v = act(x_head . w_head + x_tail . w_head + x_head . w_tail + bias [+ r_head + r_tail]) in fp32, stored as the pair of v.  No tile
- *    argument: 64 couts x 128 pixels when cout % 128 != 0, else 128 x 128, as in the network. */
+ *    argument: 64 couts x 128 pixels when cout % 128 != 0, else 128 x 128, as in the network.
+ *  Size limits, r50_op_conv2d_w2: n*ho*wo <= 2^30; n*h*w*cin*2 + (pad*w+pad)*cin*2 < 2^31; n*ho*wo*cout*2 < 2^31; cout*k*k*2*cin*2 < 2^31 (the pair).
+ *  Size limits, r50_op_conv2d_split: every pixel is a pair, so half the images: n*ho*wo <= 2^30; n*h*w*2*cin*2 + (pad*w+pad)*2*cin*2 < 2^31;
+ *    n*ho*wo*2*cout*2 < 2^31; cout*k*k*3*cin*2 < 2^31. */
 int r50_op_conv2d_w2(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_pair_bf16, const float* R50_ALIGNED(16) bias_f32,
                      const void* R50_ALIGNED(16) residual_nhwc_bf16, void* R50_ALIGNED(16) y_nhwc_bf16, int cout, int ksize, int stride, int pad, int relu, int tile,
                      void* stream);
@@ -221,7 +233,9 @@ int r50_op_conv2d_split(const void* R50_ALIGNED(16) x_pair_bf16, int n, int h, i
  * with per-tensor scales sx, sw, sr, sy (real value = stored value x scale):
  *   y = fp8( act( acc * oscale + residual * rscale ) ),  acc = bias_scaled + sum x*w,
  *   bias_scaled = bias / (sx*sw) (device fp32), oscale = sx*sw/sy, rscale = sr/sy; conversion saturates at +-448.
- * cin % 128 == 0, cout % 64 == 0 (128 / 256 for the wider tiles), k in {1,3}.  tile: 0 = auto or a role-specialised tile id (64|...). */
+ * cin % 128 == 0, cout % 64 == 0 (128 / 256 for the wider tiles), k in {1,3}.  tile: 0 = auto or a role-specialised tile id (64|...).
+ * Size limits (one byte per element; the launcher describes the tensors as 16-bit pairs and keeps the 16-bit rule for y, which is therefore
+ * held to half of what its bytes would allow): n*ho*wo <= 2^30; n*h*w*cin + (pad*w+pad)*cin < 2^31; n*ho*wo*cout*2 < 2^31; cout*k*k*cin < 2^31. */
 int r50_op_conv2d_fp8(const void* R50_ALIGNED(16) x_nhwc_fp8, int n, int h, int w, int cin, const void* R50_ALIGNED(16) w_ohwi_fp8, const float* R50_ALIGNED(16) bias_scaled_f32,
                       const void* R50_ALIGNED(16) residual_nhwc_fp8, void* R50_ALIGNED(16) y_nhwc_fp8, int cout, int ksize, int stride, int pad, int relu,
                       float oscale, float rscale, int tile, void* stream);
@@ -229,7 +243,9 @@ int r50_op_conv2d_fp8(const void* R50_ALIGNED(16) x_nhwc_fp8, int n, int h, int 
 /* 1x1 conv over TWO K sources, the form the library runs conv3 + downsample + add + ReLU of a stage's first bottleneck in
  * (torchvision Bottleneck.forward: `out = conv3(out); identity = downsample(x); out += identity; relu`): y = act([W1 | W2] .
  * [x1 ; x2 sampled at stride2] + bias).  x1 (n,h,w,c1) at the output resolution, x2 (n,h2,w2,c2) with (h2-1)/stride2+1 == h;
- * wcat (cout, c1+c2) K-major; c1, c2, cout multiples of 64.  tile: 0 = auto or a role-specialised tile id (64|...). et: 0 bf16, 1 fp16. */
+ * wcat (cout, c1+c2) K-major; c1, c2, cout multiples of 64.  tile: 0 = auto or a role-specialised tile id (64|...). et: 0 bf16, 1 fp16.
+ * Size limits: n*h*w <= 2^30; n*h*w*c1*2 < 2^31 (x1); n*h2*w2*c2*2 < 2^31 (x2, usually the largest); n*h*w*cout*2 < 2^31 (y);
+ * cout*(c1+c2)*2 < 2^31 (wcat). */
 int r50_op_conv1x1_cat(const void* R50_ALIGNED(16) x1, int n, int h, int w, int c1, const void* R50_ALIGNED(16) x2, int h2, int w2, int c2, int stride2,
                        const void* R50_ALIGNED(16) wcat, const float* R50_ALIGNED(16) bias_f32, void* R50_ALIGNED(16) y, int cout, int relu, int tile, int et, void* stream);
 
@@ -237,7 +253,9 @@ int r50_op_conv1x1_cat(const void* R50_ALIGNED(16) x1, int n, int h, int w, int 
  * w_oihw_f32: (64,3,7,7) fp32 *already folded*, host pointer; bias_f32: device pointer (64).
  * scratch_dev: at least r50_stem_scratch_bytes(n) bytes of device memory.
  * Holds the host: the weights are packed into a host temporary, uploaded on `stream`, and the call synchronises `stream` once before
- * it launches (r50_forward does not: a handle keeps its packed stem weights on the device). */
+ * it launches (r50_forward does not: a handle keeps its packed stem weights on the device).
+ * Size limits: n*28 < 2^31 -- one workgroup per image and four output rows, counted in an int; every offset inside the two kernels is 64-bit,
+ * so no tensor's bytes bound n (run with y across 2^31 elements and 2^32 bytes: DESIGN.md section 4, "Size limits"). */
 int64_t r50_stem_scratch_bytes(int n);
 /* Element type of the hooks that have no argument for it -- r50_op_stem, r50_op_maxpool, r50_op_avgpool, r50_op_bneck_tail,
  * r50_op_bneck_block1, r50_op_bneck_block1_ds, r50_op_bneck_block2, r50_op_bneck_cat_chain: bf16, as their parameter names say.  With
@@ -246,7 +264,9 @@ int64_t r50_stem_scratch_bytes(int n);
 int r50_op_stem(const float* x_nchw_f32_dev, int n, const float* w_oihw_f32_host,
                 const float* R50_ALIGNED(16) bias_f32_dev, void* R50_ALIGNED(16) scratch_dev, void* R50_ALIGNED(16) y_nhwc_bf16, void* stream);
 
-/* MaxPool2d(3, stride 2, pad 1) on bf16 NHWC; c % 8 == 0. */
+/* MaxPool2d(3, stride 2, pad 1) on bf16 NHWC; c % 8 == 0.
+ * Size limits: n*h*w*c*2 < 2^63 -- the kernel counts and addresses in 64 bits (a grid-stride loop), so only the byte offset itself bounds it;
+ * run across 2^31 input elements and 2^32 input bytes ("Size limits"). */
 int r50_op_maxpool(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w, int c, void* R50_ALIGNED(16) y_nhwc_bf16, void* stream);
 
 /* Bottleneck tail in one launch: conv3 1x1 (cmid -> 4*cmid) + bn3 + identity + ReLU -> out (m,4*cmid), and the
@@ -263,7 +283,9 @@ int r50_op_maxpool(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int h, int w,
  * (c1 = 256, layer3: the chained kernel, weights packed into fragment order per call by this hook) is bit for
  * bit again.  cmid = 256 with c1 = 0 and w1 = b1 = y1n = NULL: conv3 + identity + ReLU ALONE through the same pipelined kernel (the form the
  * stage's last block, layer3.5, runs in; bit for bit a 1x1 r50_op_conv2d with a residual).  (Environment R50_TAIL3_BP = 1..112: pixels per tile
- * of the cmid = 256 kernel; a test knob.) */
+ * of the cmid = 256 kernel; a test knob.)
+ * Size limits: m*4*cmid*2 < 2^31 -- the bytes of `out`, the largest tensor of every form (with the downsample, and with c1 = 0, too): m*512 < 2^31
+ * for cmid 64, m*1024 for cmid 128, m*2048 for cmid 256.  Any m up to that, a multiple of the pixel tile or not. */
 int r50_op_bneck_tail(const void* R50_ALIGNED(16) y2_bf16, int64_t m, int cmid, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
                       const void* R50_ALIGNED(16) identity_bf16, const void* R50_ALIGNED(16) wd_bf16, const float* R50_ALIGNED(16) bd, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16,
                       int c1, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
@@ -273,14 +295,16 @@ int r50_op_bneck_tail(const void* R50_ALIGNED(16) y2_bf16, int64_t m, int cmid, 
  * `Bottleneck.forward` of torchvision's ResNet-50 from its second conv on (src/preprocess_resnet_features.py:296 calls it through
  * nn.Sequential).  t1 (n,28,28,128), identity / out (n,28,28,512), y1n (n,28,28,128) bf16 NHWC; w2 (128,3,3,128), w3 (512,128),
  * w1 (128,512) folded bf16, K contiguous; biases fp32.  Bit for bit what r50_op_conv2d (3x3, input-resident tile) followed by two
- * r50_op_conv2d 1x1 launches give.  w1 = b1 = y1n = NULL: no next conv1 (the stage's last block). */
+ * r50_op_conv2d 1x1 launches give.  w1 = b1 = y1n = NULL: no next conv1 (the stage's last block).
+ * Size limits: n*28*28*512*2 < 2^31 (identity / out, the largest tensors), with or without w1. */
 int r50_op_bneck_block2(const void* R50_ALIGNED(16) t1_bf16, int n, const void* R50_ALIGNED(16) w2_bf16, const float* R50_ALIGNED(16) b2, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
                         const void* R50_ALIGNED(16) identity_bf16, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* layer1.0, the stage's first bottleneck, from its second conv on in one launch: as r50_op_bneck_block1 with c1 = 64, but the identity is the
  * DOWNSAMPLE conv of the block input computed in the kernel -- identity = bf16(wd . x + bd), rounded exactly as a separate 1x1 launch stores
  * it (torchvision `Bottleneck.forward`: `identity = self.downsample(x)`).  x (n,56,56,64) the block input, wd (256,64), bd (256).  Bit for bit
- * what the resident-weights 3x3 launch followed by r50_op_bneck_tail (cmid 64, wd / bd given) give. */
+ * what the resident-weights 3x3 launch followed by r50_op_bneck_tail (cmid 64, wd / bd given) give.
+ * Size limits: n*56*56*256*2 < 2^31 (out, the largest tensor), as r50_op_bneck_block1. */
 int r50_op_bneck_block1_ds(const void* R50_ALIGNED(16) t1_bf16, int n, const void* R50_ALIGNED(16) w2_bf16, const float* R50_ALIGNED(16) b2, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
                            const void* R50_ALIGNED(16) x_bf16, const void* R50_ALIGNED(16) wd_bf16, const float* R50_ALIGNED(16) bd, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16, const float* R50_ALIGNED(16) b1,
                            void* R50_ALIGNED(16) y1n_bf16, void* stream);
@@ -290,13 +314,15 @@ int r50_op_bneck_block1_ds(const void* R50_ALIGNED(16) t1_bf16, int n, const voi
  * src/preprocess_resnet_features.py:296 through nn.Sequential) as one 1x1 conv over two K sources, as r50_op_conv1x1_cat computes it -- and
  * y1n = relu(w1 . out + b1), the next block's conv1.  t2 (n,ow,ow,128), x (n,2ow,2ow,256), out (n,ow,ow,512), y1n (n,ow,ow,128) bf16 NHWC;
  * wcat (512, 128 + 256) = [W3 | Wd], w1 (128,512) folded bf16, K contiguous; bcat = b3 + bd, b1 fp32.  ow = 28.  Bit for bit what
- * r50_op_conv1x1_cat followed by a 1x1 r50_op_conv2d give. */
+ * r50_op_conv1x1_cat followed by a 1x1 r50_op_conv2d give.
+ * Size limits: n*(2*ow)*(2*ow)*256*2 < 2^31 (x, the decisive one) and n*ow*ow*512*2 < 2^31 (out). */
 int r50_op_bneck_cat_chain(const void* R50_ALIGNED(16) t2_bf16, const void* R50_ALIGNED(16) x_bf16, int n, int ow, const void* R50_ALIGNED(16) wcat_bf16, const float* R50_ALIGNED(16) bcat, void* R50_ALIGNED(16) out_bf16,
                            const void* R50_ALIGNED(16) w1_bf16, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
 /* The same for layer1 (blocks .1 / .2, 56x56, 64 mid channels): t1 (n,56,56,64), identity / out (n,56,56,256), w2 (64,3,3,64), w3 (256,64),
  * w1 (c1,256) with c1 = 64 (the next layer1 block's conv1) or 128 (layer2.0.conv1), y1n (n,56,56,c1).  Bit for bit what the
- * resident-weights 3x3 launch followed by two r50_op_conv2d 1x1 launches give. */
+ * resident-weights 3x3 launch followed by two r50_op_conv2d 1x1 launches give.
+ * Size limits: n*56*56*256*2 < 2^31 (identity / out, the largest tensors), for either c1. */
 int r50_op_bneck_block1(const void* R50_ALIGNED(16) t1_bf16, int n, const void* R50_ALIGNED(16) w2_bf16, const float* R50_ALIGNED(16) b2, const void* R50_ALIGNED(16) w3_bf16, const float* R50_ALIGNED(16) b3,
                         const void* R50_ALIGNED(16) identity_bf16, void* R50_ALIGNED(16) out_bf16, const void* R50_ALIGNED(16) w1_bf16, int c1, const float* R50_ALIGNED(16) b1, void* R50_ALIGNED(16) y1n_bf16, void* stream);
 
@@ -669,7 +695,9 @@ int r50_op_nn_search(const void* R50_ALIGNED(16) q, int nq, const void* R50_ALIG
 int r50_op_baseline_forecasts(const float* a1, const float* a0, const int* nn_row, const float* dbj, int64_t n_db, int b, int k, int t_db,
                               int joints, int root, int input_len, int pred_len, float* const_pose, float* const_vel, float* nn, void* stream);
 
-/* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0. */
+/* AdaptiveAvgPool2d((1,1)) + flatten(1): (n,hw,c) bf16 -> (n,c) fp32; c % 8 == 0.
+ * Size limits: n*(c/8) + 255 < 2^31 -- one thread per image and 8 channels, numbered in an int over a grid rounded up to 256 threads -- and
+ * n*hw*c*2 < 2^63 (the row offsets are 64-bit); run across 2^31 input elements and 2^32 input bytes ("Size limits"). */
 int r50_op_avgpool(const void* R50_ALIGNED(16) x_nhwc_bf16, int n, int hw, int c, float* R50_ALIGNED(16) y_f32, void* stream);
 
 #ifdef __cplusplus

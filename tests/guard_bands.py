@@ -68,6 +68,28 @@ def guarded_empty(shape: Sequence[int], dtype: torch.dtype, fill: int, band: int
     return arena[band + shift: band + shift + nbytes].view(dtype).view(shape)
 
 
+RANDOM_CHUNK = 1 << 26      # elements drawn at a time by ``guarded_random``
+
+
+def guarded_random(shape: Sequence[int], dtype: torch.dtype, fill: int, generator: torch.Generator, scale: float = 1.0,
+                   limit: float = None, band: int = BAND, device="cpu", shift: int = 0) -> torch.Tensor:
+    """Device-side placement of an operand too large to stage through the host (``guarded`` copies a tensor that already exists, which a
+    2 GiB operand would hold twice): ``guarded_empty`` whose payload is then drawn where it lies, ``RANDOM_CHUNK`` elements at a time, as
+    ``scale`` x standard normal values from ``generator`` (a generator of that device), clamped to +-``limit`` if given, rounded to
+    ``dtype``.  Normal draws have no period: a read that wraps by 2^31 or 2^32 bytes sees other data."""
+    t = guarded_empty(shape, dtype, fill, band, device, shift)
+    flat = t.view(-1)
+    for i in range(0, flat.numel(), RANDOM_CHUNK):
+        part = flat[i: i + RANDOM_CHUNK]
+        r = torch.randn(part.numel(), generator=generator, device=t.device, dtype=torch.float32)
+        if scale != 1.0:
+            r.mul_(scale)
+        if limit is not None:
+            r.clamp_(-limit, limit)
+        part.copy_(r.to(dtype))
+    return t
+
+
 def bands_of(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """The (front, back) bands of a tensor made by ``guarded`` / ``guarded_empty`` (or of a view of one: its bands are then everything in
     front of and behind the view's own bytes), as uint8 views of the arena."""

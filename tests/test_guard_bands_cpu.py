@@ -117,6 +117,29 @@ def test_guarded_keeps_bytes_shape_and_alignment(dtype):
         G.guarded(src, G.FILL_NAN, band=1000)                           # would misalign the operand
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32, torch.float8_e4m3fn], ids=str)
+def test_guarded_random_draws_the_payload_in_place_between_intact_bands(dtype, monkeypatch):
+    """The device-side placement of tests/test_size_limits_gpu.py, here on the CPU and with a chunk smaller than the payload: bands as
+    ``guarded`` makes them, every chunk drawn (none left holding the fill), no value repeated with a period, the same draw from the same
+    seed under either fill, the clamp honoured."""
+    monkeypatch.setattr(G, "RANDOM_CHUNK", 1000)
+    draws = {}
+    for fill in G.FILLS:
+        g = torch.Generator().manual_seed(5)
+        t = G.guarded_random((3, 29, 37), dtype, fill, g, scale=2.0, limit=3.0, band=SMALL)
+        assert t.shape == (3, 29, 37) and t.dtype == dtype and t.is_contiguous()
+        G.assert_bands_intact([("t", t)], fill, "guarded_random")
+        front, _ = G.bands_of(t)
+        assert front.numel() == SMALL and t.data_ptr() % 64 == 0
+        v = t.float()
+        assert bool(torch.isfinite(v).all()) and float(v.abs().max()) <= 3.0 and float(v.abs().max()) > 2.0
+        flat = v.view(-1)
+        assert not torch.equal(flat[:1000], flat[1000:2000]) and not torch.equal(flat[:1024], flat[1024:2048])
+        assert len(torch.unique(flat[-219:])) > 8             # the last, short chunk was drawn too
+        draws[fill] = G.bits(t).clone()
+    assert torch.equal(draws[G.FILL_NAN], draws[G.FILL_BIG])
+
+
 def _header_ops():
     """Every r50_op_* prototype of include/r50.h, the two forward entry points and the stem's scratch-size query."""
     text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "r50.h").read_text(), flags=re.S)
