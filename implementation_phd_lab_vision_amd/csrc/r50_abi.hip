@@ -130,37 +130,72 @@ int fail(r50_handle* h, int code, const std::string& msg) {
     return code;
 }
 
-// Pointer alignment (include/r50.h, "Pointer alignment"): every device pointer annotated R50_ALIGNED(n) in a header is checked with
-// need_aligned, under the header's parameter name, before the entry point's first launch, copy or attribute call: after its null checks,
-// or as its first statement where those live in the launcher (NULL, allowed or not, counts as aligned, so a null pointer is still
-// answered by the null check).  Returns 0, or R50_ERR_INVALID with a message that names the parameter and the bytes.
-struct AlignedArg { const void* p; const char* name; unsigned bytes; };
-int need_aligned(r50_handle* h, const char* op, std::initializer_list<AlignedArg> args) {
-    for (const AlignedArg& a : args)
-        if ((uintptr_t)a.p & (uintptr_t)(a.bytes - 1u))
-            return fail(h, R50_ERR_INVALID, std::string(op) + ": " + a.name + " must be " + std::to_string(a.bytes) + "-byte aligned");
-    return 0;
-}
+// What fill_conv_args* and every launch_* function answer, by value: launched; refused before anything was queued (a size rule's refusal
+// carries the quantity, its value and the bound; any other refusal carries no note); or what HIP said.  No string is built unless a
+// message is: profiled() and Op::done() below are the two places that turn a Launch into a status and a text.
+struct Launch {
+    enum Kind { Launched, Refused, Hip } kind = Launched;
+    hipError_t hip = hipSuccess;                                // Hip: the runtime's status
+    const char *quantity = nullptr, *bound = nullptr;           // Refused by a size rule: "<quantity> = <value> must be < <bound>"
+    long long value = 0;
+    Launch(hipError_t e = hipSuccess) : kind(e == hipSuccess ? Launched : Hip), hip(e) {}
+    static Launch refused() { Launch r; r.kind = Refused; return r; }
+    bool ok() const { return kind == Launched; }
+    std::string note(const char* unnoted = "") const {             // a size rule's note, else `unnoted`
+        return quantity ? std::string(quantity) + " = " + std::to_string(value) + " must be < " + bound : std::string(unnoted);
+    }
+    std::string suffix() const { return quantity ? ": " + note() : std::string(); }     // behind a message that already names the op
+    const char* hip_text() const { return hipGetErrorString(kind == Refused ? hipErrorInvalidValue : hip); }
+};
 
 // Size limits (include/r50.h states them per entry point; DESIGN.md section 4, "Size limits"): fill_conv_args and the launchers check them
-// with size_over, which notes the quantity, its value and the bound; the entry point's (or the network's) fail() message carries the note
-// (size_why takes it), so a refusal names the op, the quantity and the bound.
-thread_local std::string t_size_why;
-bool size_over(const char* quantity, long long value, long long bound, const char* bound_text) {
+// with size_over, which turns `r` into the refusal that names the quantity, its value and the bound.
+bool size_over(Launch& r, const char* quantity, long long value, long long bound, const char* bound_text) {
     if (value < bound) return false;
-    t_size_why = std::string(quantity) + " = " + std::to_string(value) + " must be < " + bound_text;
+    r = Launch::refused();
+    r.quantity = quantity; r.value = value; r.bound = bound_text;
     return true;
 }
-std::string size_why(const std::string& otherwise = std::string()) {
-    std::string s = t_size_why.empty() ? otherwise : t_size_why;
-    t_size_why.clear();
-    return s;
-}
-std::string size_suffix() {          // ": <the note>" behind a message that already names the op, or nothing
-    const std::string s = size_why();
-    return s.empty() ? s : ": " + s;
-}
 constexpr long long k2p31 = 1ll << 31;
+
+// The frame of an entry point: its name, once, and the three ways it answers.  Every r50_op_* hook makes one (`h` stays null: the text goes
+// to r50_last_error(NULL)); r50_forward* make one with their handle for the alignment check.
+//   aligned   Pointer alignment (include/r50.h): every device pointer annotated R50_ALIGNED(n) in a header is checked under the header's
+//             parameter name before the entry point's first launch, copy or attribute call: after its null checks, or as its first
+//             statement where those live in the launcher (NULL, allowed or not, counts as aligned, so a null pointer is still answered
+//             by the null check).  0, or R50_ERR_INVALID with a message that names the parameter and the bytes.
+//   refuse    R50_ERR_INVALID, "<name>: <why>".
+//   done      the launcher's answer, or the runtime's last error: R50_OK, or "<name>: <the size note, else the HIP error string>".  A
+//             launcher's refusal is R50_ERR_INVALID, and so is hipErrorInvalidValue from the runtime inside a launcher (DESIGN.md
+//             section 4 records that conflation); every other failure is R50_ERR_HIP.
+//   hip_failed  R50_ERR_HIP, "<name>: <what>", where no HIP status says more.
+struct AlignedArg { const void* p; const char* name; unsigned bytes; };
+struct Op {
+    const char* name;
+    r50_handle* h = nullptr;
+    int aligned(std::initializer_list<AlignedArg> args) const {
+        for (const AlignedArg& a : args)
+            if ((uintptr_t)a.p & (uintptr_t)(a.bytes - 1u)) return refuse(std::string(a.name) + " must be " + std::to_string(a.bytes) + "-byte aligned");
+        return 0;
+    }
+    int refuse(const std::string& why) const { return fail(h, R50_ERR_INVALID, std::string(name) + ": " + why); }
+    int hip_failed(const char* what) const { return fail(h, R50_ERR_HIP, std::string(name) + ": " + what); }
+    int done(hipError_t e = hipGetLastError()) const { return e != hipSuccess ? hip_failed(hipGetErrorString(e)) : R50_OK; }
+    int done(const Launch& r) const {
+        if (r.ok()) return R50_OK;
+        if (r.kind == Launch::Hip && r.hip != hipErrorInvalidValue) return done(r.hip);
+        return refuse(r.note(r.hip_text()));
+    }
+};
+
+// Element-type dispatch: the <1, rest...> (IEEE half) or <0, rest...> (bf16) instantiation of a kernel or launcher template, as a pointer;
+// and the launch of the one the element type selects.
+#define R50_BY_ET(et, tmpl, ...) ((et) == 1 ? tmpl<1, ##__VA_ARGS__> : tmpl<0, ##__VA_ARGS__>)
+#define R50_ET_LAUNCH(et, kern, grid, block, lds, stream, ...) \
+    hipLaunchKernelGGL(R50_BY_ET(et, kern), grid, block, lds, (hipStream_t)(stream), __VA_ARGS__)
+
+// Workgroups of 256 threads for n elements, at least one and at most `cap` (the kernels walk the rest in a grid-stride loop)
+unsigned ew_grid(long long n, long long cap = 256 * 32) { return (unsigned)std::min<long long>(std::max<long long>((n + 255) / 256, 1), cap); }
 
 #define HIP_TRY(h, expr)                                                                          \
     do {                                                                                          \
@@ -370,7 +405,7 @@ int num_cus() {          // 0: the device could not be queried
 // A persistent kernel: at most one workgroup per CU of the budget, the workgroups stream `tiles` tiles.  The dynamic-LDS attribute is set on
 // every launch: it is per device, and a process may hold handles on several devices.
 template <typename K, typename... Args>
-hipError_t launch_persistent(K kern, long long tiles, int threads, size_t lds, hipStream_t s, Args... args) {
+Launch launch_persistent(K kern, long long tiles, int threads, size_t lds, hipStream_t s, Args... args) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int cus = num_cus();
@@ -380,7 +415,7 @@ hipError_t launch_persistent(K kern, long long tiles, int threads, size_t lds, h
 }
 
 template <int ET, int BC, int BP, int WC, int WP, int NSTAGE, bool SPLIT = false>
-hipError_t launch_igemm_t(ConvArgs a, bool persistent, hipStream_t s) {
+Launch launch_igemm_t(ConvArgs a, bool persistent, hipStream_t s) {
     a.n_ctiles = a.Cout / BC;
     a.n_blocks = a.n_ctiles * ((a.M + BP - 1) / BP);
     a.div_ctiles = make_fast_div((unsigned)a.n_ctiles);
@@ -427,7 +462,7 @@ constexpr TunedTile kTuned[] = {
 constexpr int kWsBit = 64;
 
 template <int ET, int BC, int BP, int CWC, int CWP, int NLOAD, int NSTAGE>
-hipError_t launch_igemm_ws_t(ConvArgs a, hipStream_t s) {
+Launch launch_igemm_ws_t(ConvArgs a, hipStream_t s) {
     a.n_ctiles = a.Cout / BC;
     a.n_blocks = a.n_ctiles * ((a.M + BP - 1) / BP);
     a.div_ctiles = make_fast_div((unsigned)a.n_ctiles);
@@ -443,8 +478,8 @@ bool is_c64_shape(const ConvArgs& a) {
            a.x_cstride == 64 && a.y_cstride == 64 && a.Ktot == 576;
 }
 template <int ET>
-hipError_t launch_conv3x3_c64(const ConvArgs& a, hipStream_t s) {
-    if (!is_c64_shape(a)) return hipErrorInvalidValue;
+Launch launch_conv3x3_c64(const ConvArgs& a, hipStream_t s) {
+    if (!is_c64_shape(a)) return Launch::refused();
     constexpr size_t lds = 9 * 64 * 128 + 2 * 352 * 128;      // 163,840 = all of the CU's LDS
     return launch_persistent(conv3x3_c64_kernel<ET>, a.N * 14, 512, lds, s, a);
 }
@@ -458,7 +493,7 @@ bool is_xres_shape(const ConvArgs& a) {
     return (a.H == 14 && a.Cin == 256) || (a.H == 7 && a.Cin == 512) || (a.H == 28 && a.Cin == 128);
 }
 template <int ET, int NI, int TR, int IW, int IH>
-hipError_t launch_conv3x3_xres_t(ConvArgs a, hipStream_t s) {
+Launch launch_conv3x3_xres_t(ConvArgs a, hipStream_t s) {
     constexpr int BC = 128, NST = 3;
     constexpr int PW = IW == 28 ? 32 : 16;
     constexpr int PPT = IW == 7 ? 17 * 16 : NI * (TR + 2) * PW, XBUF = (PPT + 31) / 32 * 32 * 128;
@@ -469,8 +504,8 @@ hipError_t launch_conv3x3_xres_t(ConvArgs a, hipStream_t s) {
     return launch_persistent(conv3x3_xres_kernel<ET, NI, TR, IW, IH>, a.n_blocks, 768, lds, s, a);
 }
 template <int ET>
-hipError_t launch_conv3x3_xres(const ConvArgs& a, hipStream_t s) {
-    if (!is_xres_shape(a)) return hipErrorInvalidValue;
+Launch launch_conv3x3_xres(const ConvArgs& a, hipStream_t s) {
+    if (!is_xres_shape(a)) return Launch::refused();
     // The row-block form (kernels.h): 128 couts x 196 pixels per tile, one tap per step, ring of three 16-KB weight stages, static loader schedule.
     // 14x14: one image per tile (512 tiles = two full rounds at batch 256); 28x28: a 7-row band; 7x7: four images (two pairs per 16-position row).
     // Rounds 2-3 carried eleven more schedules of this kernel (13-block addressing, mid-step barriers, rings of 4-5 stages, staggered SIMD partners,
@@ -489,15 +524,15 @@ bool is_s2_shape(const ConvArgs& a) {
     return (a.H == 56 && a.Cin == 128) || (a.H == 28 && a.Cin == 256) || (a.H == 14 && a.Cin == 512);
 }
 template <int ET, int TR, int OW, int OH>
-hipError_t launch_conv3x3_s2_t(ConvArgs a, hipStream_t s) {
+Launch launch_conv3x3_s2_t(ConvArgs a, hipStream_t s) {
     constexpr size_t lds = 3 * 32768 + 3 * 128 * 128;
     a.n_ctiles = a.Cout / 128;
     a.n_blocks = (OW == 7 ? (a.N + 3) / 4 : a.N * (OH / TR)) * a.n_ctiles;
     return launch_persistent(conv3x3_s2_kernel<ET, 128, TR, OW, OH>, a.n_blocks, 768, lds, s, a);
 }
 template <int ET>
-hipError_t launch_conv3x3_s2(const ConvArgs& a, hipStream_t s) {
-    if (!is_s2_shape(a)) return hipErrorInvalidValue;
+Launch launch_conv3x3_s2(const ConvArgs& a, hipStream_t s) {
+    if (!is_s2_shape(a)) return Launch::refused();
     if (a.H == 56) return launch_conv3x3_s2_t<ET, 7, 28, 28>(a, s);
     if (a.H == 14) return launch_conv3x3_s2_t<ET, 7, 7, 7>(a, s);          // four images per tile (two pairs)
     return launch_conv3x3_s2_t<ET, 14, 14, 14>(a, s);
@@ -512,7 +547,7 @@ bool is_g8_shape(const ConvArgs& a) {
            a.y_cstride == a.Cout && a.nk >= 1 && (a.x2 ? (a.stride == 1 && a.cc1 >= 1 && a.cc1 < a.nk) : a.x_cstride == a.Cin);
 }
 template <int ET, int NR, bool DUAL>
-hipError_t launch_gemm8p_t(ConvArgs a, hipStream_t s) {
+Launch launch_gemm8p_t(ConvArgs a, hipStream_t s) {
     constexpr int BP = 32 * NR;
     constexpr size_t lds = 2 * 4 * 16384;
     a.n_ctiles = a.Cout / 256;
@@ -521,8 +556,8 @@ hipError_t launch_gemm8p_t(ConvArgs a, hipStream_t s) {
     return launch_persistent(gemm8p_kernel<ET, NR, DUAL>, a.n_blocks, 512, lds, s, a);
 }
 template <int ET>
-hipError_t launch_gemm8p(const ConvArgs& a, int tile, hipStream_t s) {
-    if (!is_g8_shape(a)) return hipErrorInvalidValue;
+Launch launch_gemm8p(const ConvArgs& a, int tile, hipStream_t s) {
+    if (!is_g8_shape(a)) return Launch::refused();
     if (a.x2) return tile == kTileG8N7 ? launch_gemm8p_t<ET, 7, true>(a, s) : launch_gemm8p_t<ET, 8, true>(a, s);
     return tile == kTileG8N7 ? launch_gemm8p_t<ET, 7, false>(a, s) : launch_gemm8p_t<ET, 8, false>(a, s);
 }
@@ -596,14 +631,14 @@ int auto_tile(const ConvArgs& a) {
 }
 
 template <int ET>
-hipError_t launch_igemm_et(const ConvArgs& a, int tile, hipStream_t s, bool split) {
-    if (split && ET != 0) return hipErrorInvalidValue;
+Launch launch_igemm_et(const ConvArgs& a, int tile, hipStream_t s, bool split) {
+    if (split && ET != 0) return Launch::refused();
     if (split) {       // fp32-class mode: two tile shapes are enough (it is the accuracy path, not the fast one)
         if (a.Cout % 128) return launch_igemm_t<0, 64, 128, 1, 4, 2, true>(a, false, s);
         return launch_igemm_t<0, 128, 128, 2, 2, 2, true>(a, false, s);
     }
     if (tile == 0) tile = auto_tile(a);
-    if (a.x2 && (!(tile & kWsBit) || tile == kTileC64 || tile == kTileXres || tile == kTileS2)) return hipErrorInvalidValue;     // two K sources: igemm_ws_kernel / gemm8p_kernel only
+    if (a.x2 && (!(tile & kWsBit) || tile == kTileC64 || tile == kTileXres || tile == kTileS2)) return Launch::refused();     // two K sources: igemm_ws_kernel / gemm8p_kernel only
     if (tile == kTileG8 || tile == kTileG8N7) return launch_gemm8p<ET>(a, tile, s);
     const bool pers = (tile & kPersistBit) != 0;
     if (tile == kTileC64) return launch_conv3x3_c64<ET>(a, s);
@@ -612,70 +647,71 @@ hipError_t launch_igemm_et(const ConvArgs& a, int tile, hipStream_t s, bool spli
     if (tile & kWsBit) {
         // <couts, pixels, consumer waves (couts x pixels), loader waves, LDS stages>
         switch (tile & (kPersistBit - 1)) {
-            case 1: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<ET, 128, 128, 2, 2, 4, 4>(a, s);
-            case 3: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_ws_t<ET, 256, 128, 4, 2, 4, 3>(a, s);
-            case 4: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<ET, 128, 224, 2, 2, 4, 3>(a, s);
-            case 8: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<ET, 128, 224, 4, 2, 4, 3>(a, s);
+            case 1: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<ET, 128, 128, 2, 2, 4, 4>(a, s);
+            case 3: if (a.Cout % 256) return Launch::refused(); return launch_igemm_ws_t<ET, 256, 128, 4, 2, 4, 3>(a, s);
+            case 4: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<ET, 128, 224, 2, 2, 4, 3>(a, s);
+            case 8: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<ET, 128, 224, 4, 2, 4, 3>(a, s);
             case 9: return launch_igemm_ws_t<ET, 64, 224, 2, 2, 4, 4>(a, s);
             // 208 = 13 x 16 pixels: M = 2^10 * 49 k gives 484 (layer3, 2 cout tiles) or 244 (layer4, 4 cout tiles) tiles of 13 blocks
             // where 224-wide tiles give 448 / 224 of 14: the same number of rounds on 256 CUs, 7 % less work per round
-            case 10: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<ET, 128, 208, 4, 1, 4, 3>(a, s);
-            default: return hipErrorInvalidValue;
+            case 10: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<ET, 128, 208, 4, 1, 4, 3>(a, s);
+            default: return Launch::refused();
         }
     }
     switch (tile & (kPersistBit - 1)) {
-        case 1: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_t<ET, 128, 128, 2, 2, 2>(a, pers, s);
+        case 1: if (a.Cout % 128) return Launch::refused(); return launch_igemm_t<ET, 128, 128, 2, 2, 2>(a, pers, s);
         case 2: return launch_igemm_t<ET, 64, 128, 1, 4, 2>(a, pers, s);
         case 3: return launch_igemm_t<ET, 64, 256, 1, 4, 2>(a, pers, s);
-        case 5: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_t<ET, 128, 64, 2, 2, 2>(a, pers, s);
-        case 6: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_t<ET, 256, 128, 4, 2, 3>(a, pers, s);
-        case 7: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_t<ET, 128, 256, 2, 4, 3>(a, pers, s);
-        case 8: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_t<ET, 128, 128, 2, 4, 3>(a, pers, s);
-        case 9: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_t<ET, 256, 256, 4, 2, 2>(a, pers, s);
-        case 10: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_t<ET, 256, 256, 2, 4, 2>(a, pers, s);
-        case 11: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_t<ET, 256, 208, 8, 1, 2>(a, pers, s);
-        case 12: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_t<ET, 256, 224, 4, 2, 2>(a, pers, s);
-        default: return hipErrorInvalidValue;
+        case 5: if (a.Cout % 128) return Launch::refused(); return launch_igemm_t<ET, 128, 64, 2, 2, 2>(a, pers, s);
+        case 6: if (a.Cout % 256) return Launch::refused(); return launch_igemm_t<ET, 256, 128, 4, 2, 3>(a, pers, s);
+        case 7: if (a.Cout % 128) return Launch::refused(); return launch_igemm_t<ET, 128, 256, 2, 4, 3>(a, pers, s);
+        case 8: if (a.Cout % 128) return Launch::refused(); return launch_igemm_t<ET, 128, 128, 2, 4, 3>(a, pers, s);
+        case 9: if (a.Cout % 256) return Launch::refused(); return launch_igemm_t<ET, 256, 256, 4, 2, 2>(a, pers, s);
+        case 10: if (a.Cout % 256) return Launch::refused(); return launch_igemm_t<ET, 256, 256, 2, 4, 2>(a, pers, s);
+        case 11: if (a.Cout % 256) return Launch::refused(); return launch_igemm_t<ET, 256, 208, 8, 1, 2>(a, pers, s);
+        case 12: if (a.Cout % 256) return Launch::refused(); return launch_igemm_t<ET, 256, 224, 4, 2, 2>(a, pers, s);
+        default: return Launch::refused();
     }
 }
 
-hipError_t launch_igemm(const ConvArgs& a, int tile, hipStream_t s, bool split = false) {
-    return a.et == 1 ? launch_igemm_et<1>(a, tile, s, split) : launch_igemm_et<0>(a, tile, s, split);
+Launch launch_igemm(const ConvArgs& a, int tile, hipStream_t s, bool split = false) {
+    return R50_BY_ET(a.et, launch_igemm_et)(a, tile, s, split);
 }
 
 // fp8 (e4m3) operands: role-specialised kernel only, element type 2 (kernels.h)
-hipError_t launch_igemm_fp8(const ConvArgs& a, int tile, hipStream_t s) {
+Launch launch_igemm_fp8(const ConvArgs& a, int tile, hipStream_t s) {
     if (tile == 0) {
         tile = kWsBit | 9;
         // 128x224 with 8 consumer waves is the fastest or within 2 % of it at 16 of the 18 layer2-4 shapes (scripts/time_conv_fp8.py)
         for (int c : {kWsBit | 8, kWsBit | 3, kWsBit | 1})
             if (tiles_of(a, c) >= 200) { tile = c; break; }
     }
-    if (!(tile & kWsBit) || tile == kTileC64) return hipErrorInvalidValue;
+    if (!(tile & kWsBit) || tile == kTileC64) return Launch::refused();
     switch (tile & (kPersistBit - 1)) {
-        case 1: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<2, 128, 128, 2, 2, 4, 4>(a, s);
-        case 3: if (a.Cout % 256) return hipErrorInvalidValue; return launch_igemm_ws_t<2, 256, 128, 4, 2, 4, 3>(a, s);
-        case 4: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<2, 128, 224, 2, 2, 4, 3>(a, s);
-        case 8: if (a.Cout % 128) return hipErrorInvalidValue; return launch_igemm_ws_t<2, 128, 224, 4, 2, 4, 3>(a, s);
+        case 1: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<2, 128, 128, 2, 2, 4, 4>(a, s);
+        case 3: if (a.Cout % 256) return Launch::refused(); return launch_igemm_ws_t<2, 256, 128, 4, 2, 4, 3>(a, s);
+        case 4: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<2, 128, 224, 2, 2, 4, 3>(a, s);
+        case 8: if (a.Cout % 128) return Launch::refused(); return launch_igemm_ws_t<2, 128, 224, 4, 2, 4, 3>(a, s);
         case 9: return launch_igemm_ws_t<2, 64, 224, 2, 2, 4, 4>(a, s);
-        default: return hipErrorInvalidValue;
+        default: return Launch::refused();
     }
 }
 
-int fill_conv_args(ConvArgs& a, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias,
-                   const void* res, void* y, int cout, int ks, int stride, int pad, int relu, bool split = false, bool w2 = false) {
-    if (!x || !wt || !bias || !y) return R50_ERR_INVALID;
-    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cin % 64 || cout <= 0 || cout % 64) return R50_ERR_INVALID;
-    if (!(ks == 1 || ks == 3) || stride < 1 || pad < 0 || 2 * pad > ks - 1) return R50_ERR_INVALID;
+Launch fill_conv_args(ConvArgs& a, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias,
+                      const void* res, void* y, int cout, int ks, int stride, int pad, int relu, bool split = false, bool w2 = false) {
+    Launch r;
+    if (!x || !wt || !bias || !y) return Launch::refused();
+    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cin % 64 || cout <= 0 || cout % 64) return Launch::refused();
+    if (!(ks == 1 || ks == 3) || stride < 1 || pad < 0 || 2 * pad > ks - 1) return Launch::refused();
     a.x = (const __bf16*)x; a.w = (const __bf16*)wt; a.bias = bias; a.res = (const __bf16*)res; a.y = (__bf16*)y;
     a.N = n; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout;
     a.Ho = (h + 2 * pad - ks) / stride + 1;
     a.Wo = (w + 2 * pad - ks) / stride + 1;
-    if (a.Ho <= 0 || a.Wo <= 0) return R50_ERR_INVALID;
+    if (a.Ho <= 0 || a.Wo <= 0) return Launch::refused();
     a.ks = ks; a.stride = stride; a.pad = pad; a.relu = relu;
     const long long M = (long long)n * a.Ho * a.Wo;
     // 32-bit index budget of the kernel: pixel indices fit the FastDiv range (the byte checks below are the tighter ones in every mode)
-    if (size_over("output pixels n*ho*wo", M, (1ll << 30) + 1, "2^30 + 1")) return R50_ERR_INVALID;
+    if (size_over(r, "output pixels n*ho*wo", M, (1ll << 30) + 1, "2^30 + 1")) return r;
     a.M = (int)M; a.HoWo = a.Ho * a.Wo;
     // split mode: X is [head(cin) | tail(cin)] per pixel, K per tap is 3*cin, Y is [head(cout) | tail(cout)]
     a.x_cstride = split ? 2 * cin : cin;
@@ -688,10 +724,10 @@ int fill_conv_args(ConvArgs& a, const void* x, int n, int h, int w, int cin, con
     // buffer descriptors of the kernel (kernels.h): every offset must stay below 2^31
     const long long x_bytes = (long long)n * h * w * a.x_cstride * 2;
     const long long x_back = ((long long)pad * w + pad) * a.x_cstride * 2;
-    if (size_over("x bytes + back reach, n*h*w*cx*2 + (pad*w+pad)*cx*2 (cx = channels per x pixel),", x_bytes + x_back, k2p31, "2^31") ||
-        size_over("w bytes, cout*K*2 (K = weight elements per cout),", (long long)cout * ks * ks * kmul * cin * 2, k2p31, "2^31") ||
-        size_over("y bytes, n*ho*wo*cy*2 (cy = channels per y pixel),", M * a.y_cstride * 2, k2p31, "2^31"))
-        return R50_ERR_INVALID;
+    if (size_over(r, "x bytes + back reach, n*h*w*cx*2 + (pad*w+pad)*cx*2 (cx = channels per x pixel),", x_bytes + x_back, k2p31, "2^31") ||
+        size_over(r, "w bytes, cout*K*2 (K = weight elements per cout),", (long long)cout * ks * ks * kmul * cin * 2, k2p31, "2^31") ||
+        size_over(r, "y bytes, n*ho*wo*cy*2 (cy = channels per y pixel),", M * a.y_cstride * 2, k2p31, "2^31"))
+        return r;
     a.x_back = (int)x_back;
     a.x_records = (unsigned)(x_bytes + a.x_back);
     a.w_bytes = (unsigned)((long long)cout * a.Ktot * 2);
@@ -705,7 +741,7 @@ int fill_conv_args(ConvArgs& a, const void* x, int n, int h, int w, int cin, con
 #if defined(R50_STAMP)
     a.dbg = nullptr;
 #endif
-    return R50_OK;
+    return r;
 }
 
 // profiling brackets
@@ -733,19 +769,29 @@ int profiled(r50_handle* h, hipStream_t s, int cls, double flops, double bytes, 
              const char* key_suffix = "") {
     EvRec r{};
     prof_begin(h, s, r, cls, flops, bytes, layer);
-    const hipError_t e = launch();
+    const Launch l = launch();
     prof_end(h, s, r);
-    if (e == hipSuccess) return R50_OK;
-    return fail(h, R50_ERR_HIP, what + (key.empty() ? std::string() : " (" + key + key_suffix + ")") + ": " + hipGetErrorString(e) + size_suffix());
+    if (l.ok()) return R50_OK;
+    return fail(h, R50_ERR_HIP, what + (key.empty() ? std::string() : " (" + key + key_suffix + ")") + ": " + l.hip_text() + l.suffix());
 }
 
 // conv3 (64 -> 256) + identity + ReLU + next conv1 (256 -> c1) in one launch (kernels.h: bneck_tail_kernel).
 // wd/bd non-null: `res` is the block INPUT (m,64) and the identity is the downsample conv computed in the kernel.
-template <int ET, int C1, bool DS, int NT>
-hipError_t launch_bneck_tail_t(const TailArgs& a, hipStream_t s) {
+template <int C1, bool DS, int NT>
+Launch launch_bneck_tail_t(int et, const TailArgs& a, hipStream_t s) {
     const size_t lds = 256 * 128 * (DS ? 2 : 1) + (size_t)C1 * 512 + 256 * 4 * (DS ? 2 : 1) + (size_t)C1 * 4;
     const long long tiles = ((long long)a.M + 15) / 16;
-    return launch_persistent(bneck_tail_kernel<ET, C1, DS, NT>, (tiles + NT / 64 - 1) / (NT / 64), NT, lds, s, a);
+    return launch_persistent(R50_BY_ET(et, bneck_tail_kernel, C1, DS, NT), (tiles + NT / 64 - 1) / (NT / 64), NT, lds, s, a);
+}
+
+// The size rules of r50_op_bneck_tail and r50_op_bneck_cat_chain (include/r50.h), once: for the launchers, and for the two hooks' own check
+// before they queue the weight packing.  `out` is the largest tensor of a tail in every form.
+bool tail_over(Launch& r, long long m, int cmid) {
+    return size_over(r, "pixels m", m, k2p31, "2^31") || size_over(r, "out bytes, m*4*cmid*2,", m * 8 * cmid, k2p31, "2^31");
+}
+bool catchain_over(Launch& r, int n, int ow) {
+    return size_over(r, "out bytes, n*ow*ow*512*2,", (long long)n * ow * ow * 1024, k2p31, "2^31") ||
+           size_over(r, "x bytes, n*(2*ow)*(2*ow)*256*2,", (long long)n * 4 * ow * ow * 512, k2p31, "2^31");
 }
 
 #ifndef TAIL_NT_DS
@@ -754,34 +800,30 @@ hipError_t launch_bneck_tail_t(const TailArgs& a, hipStream_t s) {
 #ifndef TAIL_NT_C128
 #define TAIL_NT_C128 256
 #endif
-hipError_t launch_bneck_tail(const void* y2, long long m, const void* w3, const float* b3, const void* res, const void* wd,
+Launch launch_bneck_tail(const void* y2, long long m, const void* w3, const float* b3, const void* res, const void* wd,
                              const float* bd, void* out, const void* w1, int c1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
-    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0) return hipErrorInvalidValue;
-    if (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*256*2,", m * 512, k2p31, "2^31")) return hipErrorInvalidValue;
-    if ((c1 != 64 && c1 != 128) || ((wd == nullptr) != (bd == nullptr))) return hipErrorInvalidValue;
+    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0) return Launch::refused();
+    if (Launch r; tail_over(r, m, 64)) return r;
+    if ((c1 != 64 && c1 != 128) || ((wd == nullptr) != (bd == nullptr))) return Launch::refused();
     TailArgs a;
     a.y2 = (const __bf16*)y2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
     a.wd = (const __bf16*)wd; a.bd = bd;
     a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.M = (int)m;
     // 4 waves per CU stream best (more waves lower the HBM rate); the downsample variant has 1.5x the MFMA work
-    if (et == 1) {
-        if (wd) return c1 == 64 ? launch_bneck_tail_t<1, 64, true, TAIL_NT_DS>(a, s) : launch_bneck_tail_t<1, 128, true, TAIL_NT_DS>(a, s);
-        return c1 == 64 ? launch_bneck_tail_t<1, 64, false, 256>(a, s) : launch_bneck_tail_t<1, 128, false, TAIL_NT_C128>(a, s);
-    }
-    if (wd) return c1 == 64 ? launch_bneck_tail_t<0, 64, true, TAIL_NT_DS>(a, s) : launch_bneck_tail_t<0, 128, true, TAIL_NT_DS>(a, s);
-    return c1 == 64 ? launch_bneck_tail_t<0, 64, false, 256>(a, s) : launch_bneck_tail_t<0, 128, false, TAIL_NT_C128>(a, s);
+    if (wd) return (c1 == 64 ? launch_bneck_tail_t<64, true, TAIL_NT_DS> : launch_bneck_tail_t<128, true, TAIL_NT_DS>)(et, a, s);
+    return (c1 == 64 ? launch_bneck_tail_t<64, false, 256> : launch_bneck_tail_t<128, false, TAIL_NT_C128>)(et, a, s);
 }
 
 // layer2 shapes: conv3 (128 -> 512) + identity + ReLU + next conv1 (512 -> 128) (kernels.h: bneck_tail2_kernel)
-hipError_t launch_bneck_tail2(const void* y2, long long m, const void* w3, const float* b3, const void* res, void* out,
+Launch launch_bneck_tail2(const void* y2, long long m, const void* w3, const float* b3, const void* res, void* out,
                               const void* w1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
-    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0) return hipErrorInvalidValue;
-    if (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*512*2,", m * 1024, k2p31, "2^31")) return hipErrorInvalidValue;
+    if (!y2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || m <= 0) return Launch::refused();
+    if (Launch r; tail_over(r, m, 128)) return r;
     Tail2Args a;
     a.y2 = (const __bf16*)y2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res; a.out = (__bf16*)out;
     a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.M = (int)m;
     const size_t lds = 2 * 8 * 8 * 1024 + 512 * 4 + 2 * 4096;
-    return launch_persistent(et == 1 ? bneck_tail2_kernel<1> : bneck_tail2_kernel<0>, (m + 15) / 16, 512, lds, s, a);
+    return launch_persistent(R50_BY_ET(et, bneck_tail2_kernel), (m + 15) / 16, 512, lds, s, a);
 }
 
 // layer3 shapes: conv3 (256 -> 1024) + identity + ReLU chained with the next conv1 (1024 -> 256) (kernels.h: bneck_tail3_kernel)
@@ -799,12 +841,12 @@ hipError_t pack_tail3_weights(const void* w3, const void* w1, void* wp, hipStrea
 // bneck_tail3p_kernel (two-group pipeline, 112 LDS rows per slot).  Rounds 2-3 also carried bneck_tail3_kernel (consumer + helper waves) and a 98-row
 // form of the pipeline: both measured slower (profiles/r03_tail3p_variants.txt) and were removed in round 4 (git history has them).
 int g_tail3_bp = 0;        // option "tail3_bp": real pixels per tile of the chained layer3 tail (0 = whole rounds of the chip / full tiles)
-hipError_t launch_bneck_tail3(const void* y2, long long m, const void* wp, const float* b3, const void* res, void* out,
+Launch launch_bneck_tail3(const void* y2, long long m, const void* wp, const float* b3, const void* res, void* out,
                               const float* b1, void* y1n, hipStream_t s, int et = 0, int bp_override = 0, bool no_next = false) {
     if (no_next) { b1 = b3; y1n = out; }       // conv3 + identity + ReLU only (group B copies out): b1 / y1n are not used
     if (bp_override == 0) bp_override = g_tail3_bp;
-    if (!y2 || !wp || !b3 || !res || !out || !b1 || !y1n || m <= 0) return hipErrorInvalidValue;
-    if (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*1024*2,", m * 2048, k2p31, "2^31")) return hipErrorInvalidValue;
+    if (!y2 || !wp || !b3 || !res || !out || !b1 || !y1n || m <= 0) return Launch::refused();
+    if (Launch r; tail_over(r, m, 256)) return r;
     const int cus = num_cus();
     if (cus == 0) return hipErrorInvalidDevice;
     Tail3Args a;
@@ -826,10 +868,8 @@ hipError_t launch_bneck_tail3(const void* y2, long long m, const void* wp, const
     a.bp = (int)bp;
     a.n_tiles = (int)((m + bp - 1) / bp);
     const size_t ldsp = 8 * (size_t)rows * 128 + 256 * 4 + 1024 * 4;      // t2 (4 slots) + out_c (2 x 2) + b1 + b3
-    void (*kp)(const Tail3Args);
-    if (no_next) kp = et == 1 ? bneck_tail3p_kernel<1, 112, true> : bneck_tail3p_kernel<0, 112, true>;
-    else kp = et == 1 ? bneck_tail3p_kernel<1, 112> : bneck_tail3p_kernel<0, 112>;
-    return launch_persistent(kp, a.n_tiles, 512, ldsp, s, a);
+    return launch_persistent(no_next ? R50_BY_ET(et, bneck_tail3p_kernel, 112, true) : R50_BY_ET(et, bneck_tail3p_kernel, 112), a.n_tiles, 512,
+                             ldsp, s, a);
 }
 
 // layer2.0 transition tail: conv3 + downsample (one conv over K = [t2 | x at stride 2]) + ReLU chained with the next block's conv1
@@ -841,13 +881,11 @@ hipError_t pack_catchain_weights(const void* wcat, const void* w1, void* wp, hip
     return hipGetLastError();
 }
 // x_sub: x is the compact (N, ow, ow, 256) tensor of the block input's even rows and columns (what bneck_block1_kernel writes with out_sub)
-hipError_t launch_bneck_catchain(const void* t2, const void* x, int n, int ow, const void* wp, const float* bcat, void* out,
+Launch launch_bneck_catchain(const void* t2, const void* x, int n, int ow, const void* wp, const float* bcat, void* out,
                                  const float* b1, void* y1n, hipStream_t s, int et = 0, bool x_sub = false) {
-    if (!t2 || !x || !wp || !bcat || !out || !b1 || !y1n || n <= 0 || ow != 28) return hipErrorInvalidValue;
+    if (!t2 || !x || !wp || !bcat || !out || !b1 || !y1n || n <= 0 || ow != 28) return Launch::refused();
     const long long m = (long long)n * ow * ow;
-    if (size_over("out bytes, n*ow*ow*512*2,", m * 1024, k2p31, "2^31") ||
-        size_over("x bytes, n*(2*ow)*(2*ow)*256*2,", (long long)n * 4 * ow * ow * 512, k2p31, "2^31"))
-        return hipErrorInvalidValue;
+    if (Launch r; catchain_over(r, n, ow)) return r;
     const int cus = num_cus();
     if (cus == 0) return hipErrorInvalidDevice;
     CatChainArgs a;
@@ -863,42 +901,36 @@ hipError_t launch_bneck_catchain(const void* t2, const void* x, int n, int ow, c
     a.bp = (int)bp;
     a.n_tiles = (int)((m + bp - 1) / bp);
     const size_t lds = 10 * 112 * 128 + 128 * 4 + 512 * 4 + 16;        // operand slots + out_c + b1 + b3 + 4 sync words
-    return launch_persistent(et == 1 ? bneck_catchain_kernel<1, 28> : bneck_catchain_kernel<0, 28>, a.n_tiles, 512, lds, s, a);
+    return launch_persistent(R50_BY_ET(et, bneck_catchain_kernel, 28), a.n_tiles, 512, lds, s, a);
 }
 
 // layer2.1-.3 bottleneck body in one launch (kernels.h: bneck_block2_kernel): conv2 + conv3 + identity + ReLU [+ the next block's conv1]
-hipError_t launch_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
+Launch launch_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                                void* out, const void* w1, const float* b1, void* y1n, hipStream_t s, int et = 0) {
-    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || n <= 0) return hipErrorInvalidValue;
-    if (size_over("out bytes, n*28*28*512*2,", (long long)n * 784 * 1024, k2p31, "2^31")) return hipErrorInvalidValue;
-    if ((w1 == nullptr) != (b1 == nullptr) || (w1 == nullptr) != (y1n == nullptr)) return hipErrorInvalidValue;
+    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || n <= 0) return Launch::refused();
+    if (Launch r; size_over(r, "out bytes, n*28*28*512*2,", (long long)n * 784 * 1024, k2p31, "2^31")) return r;
+    if ((w1 == nullptr) != (b1 == nullptr) || (w1 == nullptr) != (y1n == nullptr)) return Launch::refused();
     Block2Args a;
     a.t1 = (const __bf16*)t1; a.w2 = (const __bf16*)w2; a.b2 = b2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res;
     a.out = (__bf16*)out; a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.N = n; a.n_tiles = 4 * n;
     const size_t lds = (w1 ? 3 * 208 * 128 + 224 * 128 : 4 * 208 * 128) + 3 * 16384 + 768 * 4;       // 160,768 / 158,720 (kernels.h: LDS map)
-    void (*kern)(const Block2Args);
-    if (w1) kern = et == 1 ? bneck_block2_kernel<1, 128> : bneck_block2_kernel<0, 128>;
-    else kern = et == 1 ? bneck_block2_kernel<1, 0> : bneck_block2_kernel<0, 0>;
-    return launch_persistent(kern, a.n_tiles, 768, lds, s, a);
+    return launch_persistent(w1 ? R50_BY_ET(et, bneck_block2_kernel, 128) : R50_BY_ET(et, bneck_block2_kernel, 0), a.n_tiles, 768, lds, s, a);
 }
 
 // layer1.1 / .2 bottleneck body in one launch (kernels.h: bneck_block1_kernel): conv2 + conv3 + identity + ReLU + the next conv1 (c1 = 64 or 128)
-hipError_t launch_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
+Launch launch_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                                void* out, const void* w1, int c1, const float* b1, void* y1n, hipStream_t s, int et = 0,
                                const void* wd = nullptr, const float* bd = nullptr, bool out_sub = false) {
-    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || n <= 0) return hipErrorInvalidValue;
-    if (size_over("out bytes, n*56*56*256*2,", (long long)n * 3136 * 512, k2p31, "2^31")) return hipErrorInvalidValue;
-    if (c1 != 64 && c1 != 128) return hipErrorInvalidValue;
-    if ((wd == nullptr) != (bd == nullptr) || (wd && c1 != 64)) return hipErrorInvalidValue;       // downsample form: layer1.0 (next conv1 256 -> 64)
+    if (!t1 || !w2 || !b2 || !w3 || !b3 || !res || !out || !w1 || !b1 || !y1n || n <= 0) return Launch::refused();
+    if (Launch r; size_over(r, "out bytes, n*56*56*256*2,", (long long)n * 3136 * 512, k2p31, "2^31")) return r;
+    if (c1 != 64 && c1 != 128) return Launch::refused();
+    if ((wd == nullptr) != (bd == nullptr) || (wd && c1 != 64)) return Launch::refused();       // downsample form: layer1.0 (next conv1 256 -> 64)
     Block1Args a;
     a.t1 = (const __bf16*)t1; a.w2 = (const __bf16*)w2; a.b2 = b2; a.w3 = (const __bf16*)w3; a.b3 = b3; a.res = (const __bf16*)res;
     a.out = (__bf16*)out; a.w1 = (const __bf16*)w1; a.b1 = b1; a.y1n = (__bf16*)y1n; a.N = n; a.n_tiles = 14 * n;
     a.wd = (const __bf16*)wd; a.bd = bd; a.out_sub = out_sub ? 1 : 0;
     constexpr size_t lds = 11 * 32 * 128 + 3 * 224 * 128 + 3 * 8192 + (448 + 256) * 4;       // 158,464 (kernels.h: LDS map; bd behind b1)
-    void (*kern)(const Block1Args);
-    if (wd) kern = et == 1 ? bneck_block1_kernel<1, 64, true> : bneck_block1_kernel<0, 64, true>;
-    else if (c1 == 64) kern = et == 1 ? bneck_block1_kernel<1, 64> : bneck_block1_kernel<0, 64>;
-    else kern = et == 1 ? bneck_block1_kernel<1, 128> : bneck_block1_kernel<0, 128>;
+    auto kern = wd ? R50_BY_ET(et, bneck_block1_kernel, 64, true) : c1 == 64 ? R50_BY_ET(et, bneck_block1_kernel, 64) : R50_BY_ET(et, bneck_block1_kernel, 128);
     return launch_persistent(kern, a.n_tiles, 768, lds, s, a);
 }
 
@@ -908,8 +940,8 @@ int run_conv(r50_handle* h, const ConvLayer& L, const __bf16* x, int n, int hh, 
     ConvArgs a;
     const bool split = (h->precision == R50_PREC_FP32X);
     const bool w2 = (h->precision == R50_PREC_BF16W2);
-    int rc = fill_conv_args(a, x, n, hh, ww, L.cin, L.w, L.bias, res, y, L.cout, L.ks, L.stride, L.pad, relu, split, w2);
-    if (rc) return fail(h, rc, "conv args invalid for " + L.conv_key + size_suffix());
+    if (const Launch r = fill_conv_args(a, x, n, hh, ww, L.cin, L.w, L.bias, res, y, L.cout, L.ks, L.stride, L.pad, relu, split, w2); !r.ok())
+        return fail(h, R50_ERR_INVALID, "conv args invalid for " + L.conv_key + r.suffix());
     a.et = (h->precision == R50_PREC_FP16) ? 1 : 0;
     const double flops = 2.0 * a.M * (double)a.Cout * L.ks * L.ks * L.cin;       // algorithmic (not the 3x of split mode)
     const double bytes = 2.0 * ((double)n * hh * ww * L.cin + (double)a.M * a.Cout * (res ? 2 : 1) + (double)a.Cout * L.ks * L.ks * L.cin);
@@ -928,22 +960,22 @@ int run_conv(r50_handle* h, const ConvLayer& L, const __bf16* x, int n, int hh, 
 
 // 1x1 conv over two K sources: y = act([W1 | W2] . [x1 ; x2 at stride2] + bias).  x1 (n,h,w,c1) at the output resolution,
 // x2 (n,h2,w2,c2) sampled at (ho*stride2, wo*stride2); wcat (cout, c1 + c2) K-major.  Role-specialised kernel only.
-int fill_conv_args_cat(ConvArgs& a, const void* x1, int n, int h, int w, int c1, const void* x2, int h2, int w2, int c2, int stride2,
-                       const void* wcat, const float* bias, void* y, int cout, int relu) {
-    if (!x2 || c2 <= 0 || c2 % 64 || stride2 < 1 || h2 < 1 || w2 < 1) return R50_ERR_INVALID;
-    if ((h2 - 1) / stride2 + 1 != h || (w2 - 1) / stride2 + 1 != w) return R50_ERR_INVALID;
-    int rc = fill_conv_args(a, x1, n, h, w, c1, wcat, bias, nullptr, y, cout, 1, 1, 0, relu);
-    if (rc) return rc;
+Launch fill_conv_args_cat(ConvArgs& a, const void* x1, int n, int h, int w, int c1, const void* x2, int h2, int w2, int c2, int stride2,
+                          const void* wcat, const float* bias, void* y, int cout, int relu) {
+    if (!x2 || c2 <= 0 || c2 % 64 || stride2 < 1 || h2 < 1 || w2 < 1) return Launch::refused();
+    if ((h2 - 1) / stride2 + 1 != h || (w2 - 1) / stride2 + 1 != w) return Launch::refused();
+    Launch r = fill_conv_args(a, x1, n, h, w, c1, wcat, bias, nullptr, y, cout, 1, 1, 0, relu);
+    if (!r.ok()) return r;
     const long long x2_bytes = (long long)n * h2 * w2 * c2 * 2;
-    if (size_over("x2 bytes, n*h2*w2*c2*2,", x2_bytes, k2p31, "2^31") ||
-        size_over("wcat bytes, cout*(c1+c2)*2,", ((long long)c1 + c2) * cout * 2, k2p31, "2^31"))
-        return R50_ERR_INVALID;
+    if (size_over(r, "x2 bytes, n*h2*w2*c2*2,", x2_bytes, k2p31, "2^31") ||
+        size_over(r, "wcat bytes, cout*(c1+c2)*2,", ((long long)c1 + c2) * cout * 2, k2p31, "2^31"))
+        return r;
     a.Cin = c1 + c2;
     a.cin_chunks = (c1 + c2) / 64; a.nk = a.cin_chunks; a.Ktot = c1 + c2;
     a.w_bytes = (unsigned)((long long)cout * a.Ktot * 2);
     a.x2 = (const __bf16*)x2; a.H2 = h2; a.W2 = w2; a.stride2 = stride2; a.x2_cstride = c2; a.cc1 = c1 / 64;
     a.x2_records = (unsigned)x2_bytes;
-    return R50_OK;
+    return r;
 }
 int cat_tile(const ConvArgs& a, int tile) {          // tile id for a two-source conv: role-specialised variants only
     if (tile == 0) {
@@ -960,8 +992,9 @@ int cat_tile(const ConvArgs& a, int tile) {          // tile id for a two-source
 int run_conv_cat(r50_handle* h, int si, const ConvLayer& c3, const ConvLayer& cd, const __bf16* t2, const __bf16* xin, int n, int h2, int w2,
                  int hin, int win, __bf16* y, hipStream_t s) {
     ConvArgs a;
-    int rc = fill_conv_args_cat(a, t2, n, h2, w2, c3.cin, xin, hin, win, cd.cin, cd.stride, h->cat_w[si], h->cat_bias[si], y, c3.cout, 1);
-    if (rc) return fail(h, rc, "two-source conv args invalid for " + c3.conv_key + size_suffix());
+    if (const Launch r = fill_conv_args_cat(a, t2, n, h2, w2, c3.cin, xin, hin, win, cd.cin, cd.stride, h->cat_w[si], h->cat_bias[si], y, c3.cout, 1);
+        !r.ok())
+        return fail(h, R50_ERR_INVALID, "two-source conv args invalid for " + c3.conv_key + r.suffix());
     a.et = (h->precision == R50_PREC_FP16) ? 1 : 0;
     const double flops = 2.0 * a.M * (double)a.Cout * a.Ktot;
     const double bytes = 2.0 * ((double)a.M * (c3.cin + cd.cin) + (double)a.M * a.Cout + (double)a.Cout * a.Ktot);
@@ -970,18 +1003,14 @@ int run_conv_cat(r50_handle* h, int si, const ConvLayer& c3, const ConvLayer& cd
 }
 
 template <typename TIN>
-hipError_t launch_stem_pack(const TIN* x, void* xp, int n, hipStream_t s, int et = 0) {
-    const long long total = (long long)n * STEM_HP * STEM_WP;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    if (et == 1) hipLaunchKernelGGL((stem_pack_kernel<1, TIN>), dim3((unsigned)blocks), dim3(256), 0, s, x, (u32x2*)xp, n);
-    else hipLaunchKernelGGL((stem_pack_kernel<0, TIN>), dim3((unsigned)blocks), dim3(256), 0, s, x, (u32x2*)xp, n);
+Launch launch_stem_pack(const TIN* x, void* xp, int n, hipStream_t s, int et = 0) {
+    hipLaunchKernelGGL(R50_BY_ET(et, stem_pack_kernel, TIN), dim3(ew_grid((long long)n * STEM_HP * STEM_WP, 256 * 64)), dim3(256), 0, s, x,
+                       (u32x2*)xp, n);
     return hipGetLastError();
 }
-hipError_t launch_stem_conv(const void* xp, const void* wpk, const float* bias, void* y, int n, hipStream_t s, int et = 0) {
-    auto kern = et == 1 ? stem_conv_kernel<1> : stem_conv_kernel<0>;
-    hipLaunchKernelGGL(kern, dim3(n * (112 / STEM_ROWS_PER_WG)), dim3(256), STEM_LDS_BYTES, s,
-                       (const char*)xp, (const char*)wpk, bias, (__bf16*)y);
+Launch launch_stem_conv(const void* xp, const void* wpk, const float* bias, void* y, int n, hipStream_t s, int et = 0) {
+    R50_ET_LAUNCH(et, stem_conv_kernel, dim3(n * (112 / STEM_ROWS_PER_WG)), dim3(256), STEM_LDS_BYTES, s,
+                  (const char*)xp, (const char*)wpk, bias, (__bf16*)y);
     return hipGetLastError();
 }
 // fused stem (stem_fused3_kernel): a workgroup walks a strip of G consecutive pooled-row pairs of one image.  Strip length 0 = chosen from the
@@ -990,7 +1019,7 @@ hipError_t launch_stem_conv(const void* xp, const void* wpk, const float* bias, 
 static int g_stem_strip = [] { const char* v = std::getenv("R50_STEM_STRIP"); const int g = v ? std::atoi(v) : 0; return g > 0 && 28 % g == 0 ? g : 0; }();
 // c1_w / c1_bias / y1 non-null: layer1.0.conv1 (+ bias + ReLU) of the pooled output into y1 in the same launch
 template <typename TIN>
-hipError_t launch_stem_fused(const TIN* x, const void* wpk, const float* bias, void* y, int n, hipStream_t s,
+Launch launch_stem_fused(const TIN* x, const void* wpk, const float* bias, void* y, int n, hipStream_t s,
                              const float* u8_table, int et = 0, const void* c1_w = nullptr, const float* c1_bias = nullptr,
                              void* y1 = nullptr) {
     // G = the longest strip that still gives the chip ~200 workgroups (28 = the whole image from batch 200 up)
@@ -1002,9 +1031,8 @@ hipError_t launch_stem_fused(const TIN* x, const void* wpk, const float* bias, v
     const bool c1 = c1_w && c1_bias && y1;
     const int strips = n * (28 / G);
     // 16-B (fp32) / 4-B (uint8) loads of 4 pixels: image rows start at multiples of 896 / 224 bytes from the frame pointer
-    if (reinterpret_cast<uintptr_t>(x) & (sizeof(TIN) == 1 ? 3u : 15u)) return hipErrorInvalidValue;
-    auto kern = c1 ? (et == 1 ? stem_fused3_kernel<1, TIN, true> : stem_fused3_kernel<0, TIN, true>)
-                   : (et == 1 ? stem_fused3_kernel<1, TIN, false> : stem_fused3_kernel<0, TIN, false>);
+    if (reinterpret_cast<uintptr_t>(x) & (sizeof(TIN) == 1 ? 3u : 15u)) return Launch::refused();
+    auto kern = c1 ? R50_BY_ET(et, stem_fused3_kernel, TIN, true) : R50_BY_ET(et, stem_fused3_kernel, TIN, false);
 #if defined(R50_STAMP)
     return launch_persistent(kern, strips, SF3_THREADS, SF3_LDS_BYTES, s, x, (const char*)wpk, bias, (__bf16*)y, strips, G, u8_table,
                              (const __bf16*)c1_w, c1_bias, (__bf16*)y1, g_dbg);
@@ -1014,12 +1042,10 @@ hipError_t launch_stem_fused(const TIN* x, const void* wpk, const float* bias, v
 #endif
 }
 template <typename TIN>
-hipError_t launch_stem_split(const TIN* x, char* xp_head, char* xp_tail, const char* w_head, const char* w_tail,
+Launch launch_stem_split(const TIN* x, char* xp_head, char* xp_tail, const char* w_head, const char* w_tail,
                              const float* bias, void* y, int n, hipStream_t s) {
-    const long long total = (long long)n * STEM_HP * STEM_WP;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(stem_pack_split_kernel<TIN>, dim3((unsigned)blocks), dim3(256), 0, s, x, (u32x2*)xp_head, (u32x2*)xp_tail, n);
+    hipLaunchKernelGGL(stem_pack_split_kernel<TIN>, dim3(ew_grid((long long)n * STEM_HP * STEM_WP, 256 * 64)), dim3(256), 0, s, x, (u32x2*)xp_head,
+                       (u32x2*)xp_tail, n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_conv_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1029,36 +1055,27 @@ hipError_t launch_stem_split(const TIN* x, char* xp_head, char* xp_tail, const c
                        (const char*)xp_head, (const char*)xp_tail, w_head, w_tail, bias, (__bf16*)y);
     return hipGetLastError();
 }
-hipError_t launch_maxpool_split(const void* x, void* y, int n, int h, int w, int c, hipStream_t s) {
+Launch launch_maxpool_split(const void* x, void* y, int n, int h, int w, int c, hipStream_t s) {
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    const long long total = (long long)n * ho * wo * (c / 8);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(maxpool3x3s2_split_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const __bf16*)x, (__bf16*)y, n, h, w,
-                       c, ho, wo);
+    hipLaunchKernelGGL(maxpool3x3s2_split_kernel, dim3(ew_grid((long long)n * ho * wo * (c / 8), 256 * 64)), dim3(256), 0, s, (const __bf16*)x,
+                       (__bf16*)y, n, h, w, c, ho, wo);
     return hipGetLastError();
 }
-hipError_t launch_avgpool_split(const void* x, float* y, int n, int hw, int c, hipStream_t s) {
+Launch launch_avgpool_split(const void* x, float* y, int n, int hw, int c, hipStream_t s) {
     const int total = n * (c / 8);
     hipLaunchKernelGGL(avgpool_split_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const __bf16*)x, y, n, hw, c,
                        1.0f / (float)hw);
     return hipGetLastError();
 }
-hipError_t launch_maxpool(const void* x, void* y, int n, int h, int w, int c, hipStream_t s, int et = 0) {
+Launch launch_maxpool(const void* x, void* y, int n, int h, int w, int c, hipStream_t s, int et = 0) {
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    const long long total = (long long)n * ho * wo * (c / 8);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    auto kern = et == 1 ? maxpool3x3s2_kernel<1> : maxpool3x3s2_kernel<0>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, (const __bf16*)x, (__bf16*)y,
-                       n, h, w, c, ho, wo);
+    R50_ET_LAUNCH(et, maxpool3x3s2_kernel, dim3(ew_grid((long long)n * ho * wo * (c / 8), 256 * 64)), dim3(256), 0, s, (const __bf16*)x,
+                  (__bf16*)y, n, h, w, c, ho, wo);
     return hipGetLastError();
 }
-hipError_t launch_avgpool(const void* x, float* y, int n, int hw, int c, hipStream_t s, int et = 0) {
+Launch launch_avgpool(const void* x, float* y, int n, int hw, int c, hipStream_t s, int et = 0) {
     const int total = n * (c / 8);
-    auto kern = et == 1 ? avgpool_kernel<1> : avgpool_kernel<0>;
-    hipLaunchKernelGGL(kern, dim3((total + 255) / 256), dim3(256), 0, s, (const __bf16*)x, y, n, hw, c,
-                       1.0f / (float)hw);
+    R50_ET_LAUNCH(et, avgpool_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const __bf16*)x, y, n, hw, c, 1.0f / (float)hw);
     return hipGetLastError();
 }
 
@@ -1066,8 +1083,8 @@ hipError_t launch_avgpool(const void* x, float* y, int n, int hw, int c, hipStre
 int run_conv_fp8(r50_handle* h, const ConvLayer& L, const void* x, int n, int hh, int ww, const void* res, void* y, int relu, float sx,
                  float sr, float sy, hipStream_t s, int* ho, int* wo) {
     ConvArgs a;
-    int rc = fill_conv_args(a, x, n, hh, ww, L.cin / 2, L.w, L.bias_scaled, res, y, L.cout, L.ks, L.stride, L.pad, relu);
-    if (rc) return fail(h, rc, "fp8 conv args invalid for " + L.conv_key + size_suffix());
+    if (const Launch r = fill_conv_args(a, x, n, hh, ww, L.cin / 2, L.w, L.bias_scaled, res, y, L.cout, L.ks, L.stride, L.pad, relu); !r.ok())
+        return fail(h, R50_ERR_INVALID, "fp8 conv args invalid for " + L.conv_key + r.suffix());
     a.y_bytes = (unsigned)((long long)a.M * L.cout);
     a.et = 2; a.oscale = sx * L.wscale / sy; a.rscale = sr / sy;
     const double flops = 2.0 * a.M * (double)a.Cout * L.ks * L.ks * L.cin;
@@ -1088,7 +1105,7 @@ int run_fp8_part(r50_handle* h, __bf16* const* buf, int cur, int n, float* out, 
     if (!already_fp8) {
         const long long n4 = (long long)n * 56 * 56 * 256 / 4;
         rc = profiled(h, s, PC_MAXPOOL, 0, (double)n4 * 12, -1, "quant_to_fp8", kNoKey, [&] {
-            hipLaunchKernelGGL(quant_to_fp8_kernel<0>, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256 * 64)), dim3(256), 0, s,
+            hipLaunchKernelGGL(quant_to_fp8_kernel<0>, dim3(ew_grid(n4, 256 * 64)), dim3(256), 0, s,
                                (const unsigned short*)buf[cur], (unsigned*)buf[nxt], n4, 1.0f / s_in);
             return hipGetLastError();
         });
@@ -1122,9 +1139,9 @@ int run_fp8_part(r50_handle* h, __bf16* const* buf, int cur, int n, float* out, 
             if (cat_ds) {
                 const ConvLayer& cd = h->convs[li + 3];
                 ConvArgs a;
-                rc = fill_conv_args_cat(a, buf[fr[1]], n, h2, w2, c3.cin / 2, buf[cur], hh, ww, cd.cin / 2, cd.stride, h->cat_w[si], h->cat_bias[si],
-                                        buf[fr[3]], c3.cout, 1);
-                if (rc) return fail(h, rc, "fp8 two-source conv args invalid for " + c3.conv_key + size_suffix());
+                if (const Launch r = fill_conv_args_cat(a, buf[fr[1]], n, h2, w2, c3.cin / 2, buf[cur], hh, ww, cd.cin / 2, cd.stride, h->cat_w[si],
+                                                        h->cat_bias[si], buf[fr[3]], c3.cout, 1); !r.ok())
+                    return fail(h, R50_ERR_INVALID, "fp8 two-source conv args invalid for " + c3.conv_key + r.suffix());
                 a.y_bytes = (unsigned)((long long)a.M * c3.cout);
                 a.et = 2; a.oscale = h->cat_acc_scale[si] / s_out; a.rscale = 0.f;
                 const double flops = 2.0 * a.M * (double)a.Cout * (c3.cin + cd.cin);
@@ -1408,9 +1425,9 @@ int forward_impl(r50_handle* h, const TIN* x, int n, float* out, void* stream) {
     if (!x || !out) return fail(h, R50_ERR_INVALID, "r50_forward: null buffer");
     if (n < 0) return fail(h, R50_ERR_INVALID, "r50_forward: n < 0");
     // the fused stem loads 4 pixels at a time (16 bytes of fp32, 4 of uint8); the average pool stores f32x4
-    if (int rc_al = need_aligned(h, sizeof(TIN) == 1 ? "r50_forward_u8" : "r50_forward",
-                                 {{x, sizeof(TIN) == 1 ? "x_nchw_u8_dev" : "x_nchw_f32_dev", sizeof(TIN) == 1 ? 4u : 16u}, {out, "out_f32_dev", 16}}))
-        return rc_al;
+    const Op op{sizeof(TIN) == 1 ? "r50_forward_u8" : "r50_forward", h};
+    if (int rc = op.aligned({{x, sizeof(TIN) == 1 ? "x_nchw_u8_dev" : "x_nchw_f32_dev", sizeof(TIN) == 1 ? 4u : 16u}, {out, "out_f32_dev", 16}}))
+        return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     int chunk = h->max_batch;
     if (h->micro_batch > 0 && h->micro_batch < chunk) chunk = h->micro_batch;
@@ -1791,7 +1808,8 @@ int r50_forward_layer(r50_handle* h, const float* x, int n, const char* layer, v
     if (!h->loaded) return fail(h, R50_ERR_STATE, "r50_forward_layer: weights not loaded");
     if (!x || !out || !layer || !dims_out) return fail(h, R50_ERR_INVALID, "r50_forward_layer: null argument");
     if (n < 1 || n > h->max_batch) return fail(h, R50_ERR_INVALID, "r50_forward_layer: n must be in [1,max_batch]");
-    if (int rc_al = need_aligned(h, "r50_forward_layer", {{x, "x_nchw_f32_dev", 16}, {out, "out_bf16_nhwc_dev", 2}})) return rc_al;
+    const Op op{"r50_forward_layer", h};
+    if (int rc = op.aligned({{x, "x_nchw_f32_dev", 16}, {out, "out_bf16_nhwc_dev", 2}})) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const __bf16* p = nullptr;
     int rc = run_stack(h, x, n, nullptr, (hipStream_t)stream, layer, &p, dims_out);
@@ -1891,99 +1909,97 @@ int r50_get_packed(r50_handle* h, const char* conv_key, int what, void* dst_host
 extern "C" __attribute__((visibility("default"))) void r50_debug_buffer(void* p) { g_dbg = (unsigned long long*)p; }
 #endif
 
-static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
+static int op_conv2d_et(const Op& op, int et, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                         void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream);
-// what an r50_op_* hook returns for its launch: hipErrorInvalidValue is the launcher refusing the arguments
-static int op_status(hipError_t e, const char* op) {
-    if (e == hipSuccess) return R50_OK;
-    return fail(nullptr, e == hipErrorInvalidValue ? R50_ERR_INVALID : R50_ERR_HIP, std::string(op) + ": " + size_why(hipGetErrorString(e)));
-}
 
 int r50_op_conv2d(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                   void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d", {{x, "x_nhwc_bf16", 16}, {wt, "w_ohwi_bf16", 16}, {bias, "bias_f32", 16},
-                                                 {res, "residual_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}}))
-        return rc_al;
-    return op_conv2d_et(0, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu, tile, stream);
+    const Op op{"r50_op_conv2d"};
+    if (int rc = op.aligned({{x, "x_nhwc_bf16", 16}, {wt, "w_ohwi_bf16", 16}, {bias, "bias_f32", 16},
+                             {res, "residual_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}}))
+        return rc;
+    return op_conv2d_et(op, 0, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu, tile, stream);
 }
 
 int r50_op_conv2d_f16(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                       void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_f16", {{x, "x_nhwc_f16", 16}, {wt, "w_ohwi_f16", 16}, {bias, "bias_f32", 16},
-                                                 {res, "residual_nhwc_f16", 16}, {y, "y_nhwc_f16", 16}}))
-        return rc_al;
-    return op_conv2d_et(1, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu, tile, stream);
+    const Op op{"r50_op_conv2d_f16"};
+    if (int rc = op.aligned({{x, "x_nhwc_f16", 16}, {wt, "w_ohwi_f16", 16}, {bias, "bias_f32", 16},
+                             {res, "residual_nhwc_f16", 16}, {y, "y_nhwc_f16", 16}}))
+        return rc;
+    return op_conv2d_et(op, 1, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu, tile, stream);
 }
 
-static int op_conv2d_et(int et, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
+static int op_conv2d_et(const Op& op, int et, const void* x, int n, int h, int w, int cin, const void* wt, const float* bias, const void* res,
                         void* y, int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
     ConvArgs a;
-    int rc = fill_conv_args(a, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu);
-    if (rc) return fail(nullptr, rc, std::string(et == 1 ? "r50_op_conv2d_f16: " : "r50_op_conv2d: ") + size_why("invalid arguments"));
+    if (const Launch r = fill_conv_args(a, x, n, h, w, cin, wt, bias, res, y, cout, ksize, stride, pad, relu); !r.ok())
+        return op.refuse(r.note("invalid arguments"));
     a.et = et;
 #if defined(R50_STAMP)
     a.dbg = g_dbg;
 #endif
-    hipError_t e = launch_igemm(a, tile, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_conv2d: ") + hipGetErrorString(e));
-    return R50_OK;
+    // these two hooks answer the launcher's refusal (a tile id that does not fit the shape) with R50_ERR_HIP; the other convolution hooks,
+    // through done(), with R50_ERR_INVALID
+    const Launch r = launch_igemm(a, tile, (hipStream_t)stream);
+    return r.ok() ? R50_OK : op.hip_failed(r.hip_text());
 }
 
 // The two pair precisions at kernel level: the ConvArgs run_conv builds for R50_PREC_BF16W2 / R50_PREC_FP32X, through the same launcher.
 int r50_op_conv2d_w2(const void* x, int n, int h, int w, int cin, const void* w_pair, const float* bias, const void* res, void* y,
                      int cout, int ksize, int stride, int pad, int relu, int tile, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_w2", {{x, "x_nhwc_bf16", 16}, {w_pair, "w_pair_bf16", 16}, {bias, "bias_f32", 16},
-                                                 {res, "residual_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}}))
-        return rc_al;
+    const Op op{"r50_op_conv2d_w2"};
+    if (int rc = op.aligned({{x, "x_nhwc_bf16", 16}, {w_pair, "w_pair_bf16", 16}, {bias, "bias_f32", 16},
+                             {res, "residual_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}}))
+        return rc;
     ConvArgs a;
-    int rc = fill_conv_args(a, x, n, h, w, cin, w_pair, bias, res, y, cout, ksize, stride, pad, relu, false, true);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d_w2: " + size_why("invalid arguments"));
+    if (const Launch r = fill_conv_args(a, x, n, h, w, cin, w_pair, bias, res, y, cout, ksize, stride, pad, relu, false, true); !r.ok())
+        return op.refuse(r.note("invalid arguments"));
     // only igemm_bf16_kernel and igemm_ws_kernel wrap the X chunk index (ConvArgs::x_wrap): the shape-specialised kernels walk K on their own
     if (tile == kTileC64 || tile == kTileXres || tile == kTileS2 || tile == kTileG8 || tile == kTileG8N7)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_w2: tile id " + std::to_string(tile) + " does not read the weight pair");
-    hipError_t e = launch_igemm(a, tile, (hipStream_t)stream);
-    return op_status(e, "r50_op_conv2d_w2");
+        return op.refuse("tile id " + std::to_string(tile) + " does not read the weight pair");
+    return op.done(launch_igemm(a, tile, (hipStream_t)stream));
 }
 
 int r50_op_conv2d_split(const void* x_pair, int n, int h, int w, int cin, const void* w_trip, const float* bias, const void* res_pair,
                         void* y_pair, int cout, int ksize, int stride, int pad, int relu, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_split", {{x_pair, "x_pair_bf16", 16}, {w_trip, "w_trip_bf16", 16}, {bias, "bias_f32", 16},
-                                                 {res_pair, "residual_pair_bf16", 16}, {y_pair, "y_pair_bf16", 16}}))
-        return rc_al;
+    const Op op{"r50_op_conv2d_split"};
+    if (int rc = op.aligned({{x_pair, "x_pair_bf16", 16}, {w_trip, "w_trip_bf16", 16}, {bias, "bias_f32", 16},
+                             {res_pair, "residual_pair_bf16", 16}, {y_pair, "y_pair_bf16", 16}}))
+        return rc;
     ConvArgs a;
-    int rc = fill_conv_args(a, x_pair, n, h, w, cin, w_trip, bias, res_pair, y_pair, cout, ksize, stride, pad, relu, true, false);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d_split: " + size_why("invalid arguments"));
-    hipError_t e = launch_igemm(a, 0, (hipStream_t)stream, true);
-    return op_status(e, "r50_op_conv2d_split");
+    if (const Launch r = fill_conv_args(a, x_pair, n, h, w, cin, w_trip, bias, res_pair, y_pair, cout, ksize, stride, pad, relu, true, false); !r.ok())
+        return op.refuse(r.note("invalid arguments"));
+    return op.done(launch_igemm(a, 0, (hipStream_t)stream, true));
 }
 
 int r50_op_conv2d_fp8(const void* x, int n, int h, int w, int cin, const void* wt, const float* bias_scaled, const void* res, void* y,
                       int cout, int ksize, int stride, int pad, int relu, float oscale, float rscale, int tile, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_conv2d_fp8", {{x, "x_nhwc_fp8", 16}, {wt, "w_ohwi_fp8", 16}, {bias_scaled, "bias_scaled_f32", 16},
-                                                 {res, "residual_nhwc_fp8", 16}, {y, "y_nhwc_fp8", 16}}))
-        return rc_al;
-    if (cin <= 0 || cin % 128) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv2d_fp8: cin must be a multiple of 128");
+    const Op op{"r50_op_conv2d_fp8"};
+    if (int rc = op.aligned({{x, "x_nhwc_fp8", 16}, {wt, "w_ohwi_fp8", 16}, {bias_scaled, "bias_scaled_f32", 16},
+                             {res, "residual_nhwc_fp8", 16}, {y, "y_nhwc_fp8", 16}}))
+        return rc;
+    if (cin <= 0 || cin % 128) return op.refuse("cin must be a multiple of 128");
     ConvArgs a;
     // the loaders move bytes: described in 2-byte units, an fp8 tensor with cin channels is a 16-bit tensor with cin / 2
-    int rc = fill_conv_args(a, x, n, h, w, cin / 2, wt, bias_scaled, res, y, cout, ksize, stride, pad, relu);
-    if (rc) return fail(nullptr, rc, "r50_op_conv2d_fp8 (sizes as 16-bit pairs: cx = cin/2, cy = cout): " + size_why("invalid arguments"));
+    if (const Launch r = fill_conv_args(a, x, n, h, w, cin / 2, wt, bias_scaled, res, y, cout, ksize, stride, pad, relu); !r.ok())
+        return fail(nullptr, R50_ERR_INVALID, std::string(op.name) + " (sizes as 16-bit pairs: cx = cin/2, cy = cout): " + r.note("invalid arguments"));
     a.y_bytes = (unsigned)((long long)a.M * cout);       // one byte per output element
     a.et = 2; a.oscale = oscale; a.rscale = rscale;
-    hipError_t e = launch_igemm_fp8(a, tile, (hipStream_t)stream);
-    return op_status(e, "r50_op_conv2d_fp8");
+    return op.done(launch_igemm_fp8(a, tile, (hipStream_t)stream));
 }
 
 int r50_op_conv1x1_cat(const void* x1, int n, int h, int w, int c1, const void* x2, int h2, int w2, int c2, int stride2, const void* wcat,
                        const float* bias, void* y, int cout, int relu, int tile, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_conv1x1_cat", {{x1, "x1", 16}, {x2, "x2", 16}, {wcat, "wcat", 16},
-                                                 {bias, "bias_f32", 16}, {y, "y", 16}}))
-        return rc_al;
+    const Op op{"r50_op_conv1x1_cat"};
+    if (int rc = op.aligned({{x1, "x1", 16}, {x2, "x2", 16}, {wcat, "wcat", 16},
+                             {bias, "bias_f32", 16}, {y, "y", 16}}))
+        return rc;
     ConvArgs a;
-    int rc = fill_conv_args_cat(a, x1, n, h, w, c1, x2, h2, w2, c2, stride2, wcat, bias, y, cout, relu);
-    if (rc || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_conv1x1_cat: " + size_why("invalid arguments"));
+    if (const Launch r = fill_conv_args_cat(a, x1, n, h, w, c1, x2, h2, w2, c2, stride2, wcat, bias, y, cout, relu); !r.ok() || (et != 0 && et != 1))
+        return op.refuse(r.note("invalid arguments"));
     a.et = et;
-    hipError_t e = launch_igemm(a, cat_tile(a, tile), (hipStream_t)stream);
-    return op_status(e, "r50_op_conv1x1_cat");
+    return op.done(launch_igemm(a, cat_tile(a, tile), (hipStream_t)stream));
 }
 
 // Element type of the op-level hooks that have no argument for it (the fused tails, bodies and chain, the stem, the two pools): they run
@@ -1993,90 +2009,86 @@ static int op_et() { const char* v = std::getenv("R50_OP_ET"); return (v && std:
 
 int r50_op_bneck_tail(const void* y2, int64_t m, int cmid, const void* w3, const float* b3, const void* res, const void* wd,
                       const float* bd, void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_tail", {{y2, "y2_bf16", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16}, {res, "identity_bf16", 16}, {wd, "wd_bf16", 16},
-                                                 {bd, "bd", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
-        return rc_al;
-    hipError_t e;
+    const Op op{"r50_op_bneck_tail"};
+    if (int rc = op.aligned({{y2, "y2_bf16", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16}, {res, "identity_bf16", 16}, {wd, "wd_bf16", 16},
+                             {bd, "bd", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc;
+    Launch r;
     const int et = op_et();
-    // the size limit before anything is queued (the cmid = 256 forms pack their weights on the stream first): out is the largest tensor
-    if ((cmid == 64 || cmid == 128 || cmid == 256) && m > 0 &&
-        (size_over("pixels m", m, k2p31, "2^31") || size_over("out bytes, m*4*cmid*2,", m * 8 * cmid, k2p31, "2^31")))
-        return op_status(hipErrorInvalidValue, "r50_op_bneck_tail");
-    if (cmid == 64) e = launch_bneck_tail(y2, m, w3, b3, res, wd, bd, out, w1, c1, b1, y1n, (hipStream_t)stream, et);
-    else if (cmid == 128 && c1 == 128 && !wd && !bd) e = launch_bneck_tail2(y2, m, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, et);
+    // the size limit before anything is queued (the cmid = 256 forms pack their weights on the stream first)
+    if ((cmid == 64 || cmid == 128 || cmid == 256) && m > 0 && tail_over(r, m, cmid)) return op.done(r);
+    if (cmid == 64) r = launch_bneck_tail(y2, m, w3, b3, res, wd, bd, out, w1, c1, b1, y1n, (hipStream_t)stream, et);
+    else if (cmid == 128 && c1 == 128 && !wd && !bd) r = launch_bneck_tail2(y2, m, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, et);
     else if (cmid == 256 && c1 == 0 && !w1 && !b1 && !y1n && !wd && !bd) {
         // conv3 + identity + ReLU alone through the pipelined layer3 tail (the form layer3.5 runs in the network): W3 stands in for the unused W1 slices
         void* wp_scratch = nullptr;
-        if (hipMallocAsync(&wp_scratch, kTail3PackedBytes, (hipStream_t)stream) != hipSuccess || !wp_scratch)
-            return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_tail: hipMallocAsync");
-        e = pack_tail3_weights(w3, w3, wp_scratch, (hipStream_t)stream);
-        if (e == hipSuccess) e = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, nullptr, nullptr, (hipStream_t)stream, et, 0, /*no_next=*/true);
+        if (hipMallocAsync(&wp_scratch, kTail3PackedBytes, (hipStream_t)stream) != hipSuccess || !wp_scratch) return op.hip_failed("hipMallocAsync");
+        r = pack_tail3_weights(w3, w3, wp_scratch, (hipStream_t)stream);
+        if (r.ok()) r = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, nullptr, nullptr, (hipStream_t)stream, et, 0, /*no_next=*/true);
         const hipError_t ef = hipFreeAsync(wp_scratch, (hipStream_t)stream);
-        if (e == hipSuccess) e = ef;
+        if (r.ok()) r = ef;
     }
     else if (cmid == 256 && c1 == 256 && !wd && !bd) {
         const char* v = std::getenv("R50_TAIL3_BP");          // test / A-B knob of this debug hook: real pixels per tile (1..112); unset = automatic
         // the hook takes plain weight matrices: packed here, per call, into a buffer allocated AND freed in the caller's stream order on the
         // caller's current device (a process-wide scratch buffer would be shared by callers on other streams / devices: round-2 ADVICE)
         void* wp_scratch = nullptr;
-        if (hipMallocAsync(&wp_scratch, kTail3PackedBytes, (hipStream_t)stream) != hipSuccess || !wp_scratch)
-            return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_tail: hipMallocAsync");
-        e = pack_tail3_weights(w3, w1, wp_scratch, (hipStream_t)stream);
-        if (e == hipSuccess) e = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, b1, y1n, (hipStream_t)stream, et, v ? std::atoi(v) : 0);
+        if (hipMallocAsync(&wp_scratch, kTail3PackedBytes, (hipStream_t)stream) != hipSuccess || !wp_scratch) return op.hip_failed("hipMallocAsync");
+        r = pack_tail3_weights(w3, w1, wp_scratch, (hipStream_t)stream);
+        if (r.ok()) r = launch_bneck_tail3(y2, m, wp_scratch, b3, res, out, b1, y1n, (hipStream_t)stream, et, v ? std::atoi(v) : 0);
         const hipError_t ef = hipFreeAsync(wp_scratch, (hipStream_t)stream);
-        if (e == hipSuccess) e = ef;
+        if (r.ok()) r = ef;
     }
-    else e = hipErrorInvalidValue;
-    return op_status(e, "r50_op_bneck_tail");
+    else r = Launch::refused();
+    return op.done(r);
 }
 
 int r50_op_bneck_block2(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, const float* b1, void* y1n, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_block2", {{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16},
-                                                 {res, "identity_bf16", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
-        return rc_al;
-    const hipError_t e = launch_bneck_block2(t1, n, w2, b2, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, op_et());
-    return op_status(e, "r50_op_bneck_block2");
+    const Op op{"r50_op_bneck_block2"};
+    if (int rc = op.aligned({{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16},
+                             {res, "identity_bf16", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc;
+    return op.done(launch_bneck_block2(t1, n, w2, b2, w3, b3, res, out, w1, b1, y1n, (hipStream_t)stream, op_et()));
 }
 
 int r50_op_bneck_block1_ds(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* x, const void* wd,
                            const float* bd, void* out, const void* w1, const float* b1, void* y1n, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_block1_ds", {{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16}, {x, "x_bf16", 16},
-                                                 {wd, "wd_bf16", 16}, {bd, "bd", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
-        return rc_al;
-    if (!wd || !bd) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_block1_ds: null downsample weights");
-    const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, x, out, w1, 64, b1, y1n, (hipStream_t)stream, op_et(), wd, bd);
-    return op_status(e, "r50_op_bneck_block1_ds");
+    const Op op{"r50_op_bneck_block1_ds"};
+    if (int rc = op.aligned({{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16}, {x, "x_bf16", 16},
+                             {wd, "wd_bf16", 16}, {bd, "bd", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc;
+    if (!wd || !bd) return op.refuse("null downsample weights");
+    return op.done(launch_bneck_block1(t1, n, w2, b2, w3, b3, x, out, w1, 64, b1, y1n, (hipStream_t)stream, op_et(), wd, bd));
 }
 
 int r50_op_bneck_cat_chain(const void* t2, const void* x, int n, int ow, const void* wcat, const float* bcat, void* out, const void* w1,
                            const float* b1, void* y1n, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_cat_chain", {{t2, "t2_bf16", 16}, {x, "x_bf16", 16}, {wcat, "wcat_bf16", 16}, {bcat, "bcat", 16},
-                                                 {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
-        return rc_al;
+    const Op op{"r50_op_bneck_cat_chain"};
+    if (int rc = op.aligned({{t2, "t2_bf16", 16}, {x, "x_bf16", 16}, {wcat, "wcat_bf16", 16}, {bcat, "bcat", 16},
+                             {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc;
     // plain weight matrices in, packed per call into a buffer allocated and freed in the caller's stream order (as r50_op_bneck_tail does)
     void* wp = nullptr;
-    if (!wcat || !w1) return fail(nullptr, R50_ERR_INVALID, "r50_op_bneck_cat_chain: null weights");
+    if (!wcat || !w1) return op.refuse("null weights");
     // the size limits before anything is queued (the weights are packed on the stream first)
-    if (n > 0 && ow == 28 && (size_over("out bytes, n*ow*ow*512*2,", (long long)n * ow * ow * 1024, k2p31, "2^31") ||
-                              size_over("x bytes, n*(2*ow)*(2*ow)*256*2,", (long long)n * 4 * ow * ow * 512, k2p31, "2^31")))
-        return op_status(hipErrorInvalidValue, "r50_op_bneck_cat_chain");
-    if (hipMallocAsync(&wp, kCatChainPackedBytes, (hipStream_t)stream) != hipSuccess || !wp)
-        return fail(nullptr, R50_ERR_HIP, "r50_op_bneck_cat_chain: hipMallocAsync");
-    hipError_t e = pack_catchain_weights(wcat, w1, wp, (hipStream_t)stream);
-    if (e == hipSuccess) e = launch_bneck_catchain(t2, x, n, ow, wp, bcat, out, b1, y1n, (hipStream_t)stream, op_et());
+    Launch r;
+    if (n > 0 && ow == 28 && catchain_over(r, n, ow)) return op.done(r);
+    if (hipMallocAsync(&wp, kCatChainPackedBytes, (hipStream_t)stream) != hipSuccess || !wp) return op.hip_failed("hipMallocAsync");
+    r = pack_catchain_weights(wcat, w1, wp, (hipStream_t)stream);
+    if (r.ok()) r = launch_bneck_catchain(t2, x, n, ow, wp, bcat, out, b1, y1n, (hipStream_t)stream, op_et());
     const hipError_t ef = hipFreeAsync(wp, (hipStream_t)stream);
-    if (e == hipSuccess) e = ef;
-    return op_status(e, "r50_op_bneck_cat_chain");
+    if (r.ok()) r = ef;
+    return op.done(r);
 }
 
 int r50_op_bneck_block1(const void* t1, int n, const void* w2, const float* b2, const void* w3, const float* b3, const void* res,
                         void* out, const void* w1, int c1, const float* b1, void* y1n, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_bneck_block1", {{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16},
-                                                 {res, "identity_bf16", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
-        return rc_al;
-    const hipError_t e = launch_bneck_block1(t1, n, w2, b2, w3, b3, res, out, w1, c1, b1, y1n, (hipStream_t)stream, op_et());
-    return op_status(e, "r50_op_bneck_block1");
+    const Op op{"r50_op_bneck_block1"};
+    if (int rc = op.aligned({{t1, "t1_bf16", 16}, {w2, "w2_bf16", 16}, {b2, "b2", 16}, {w3, "w3_bf16", 16}, {b3, "b3", 16},
+                             {res, "identity_bf16", 16}, {out, "out_bf16", 16}, {w1, "w1_bf16", 16}, {b1, "b1", 16}, {y1n, "y1n_bf16", 16}}))
+        return rc;
+    return op.done(launch_bneck_block1(t1, n, w2, b2, w3, b3, res, out, w1, c1, b1, y1n, (hipStream_t)stream, op_et()));
 }
 
 // Weight precision of ATen's native uint8 bilinear resize (antialias off) along one axis: the largest p with
@@ -2118,12 +2130,13 @@ static int resize_weight_precision(int in_size, int out_size) {
 
 int r50_op_crop_resize_u8(const void* frames, int t, int h, int w, int top, int left, int hh, int ww, void* out, int out_size,
                           int mode, int flags, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_crop_resize_u8", {{out, "out_tchw_u8", 4}})) return rc_al;
+    const Op op{"r50_op_crop_resize_u8"};
+    if (int rc = op.aligned({{out, "out_tchw_u8", 4}})) return rc;
     if (!frames || !out || t < 1 || h < 1 || w < 1 || hh < 1 || ww < 1 || top < 0 || left < 0 || top + hh > h || left + ww > w ||
         out_size < 4 || (out_size & 3) || out_size > 4096 || (long long)t * h * w * 3 >= (1ll << 40))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_u8: invalid arguments (the box must lie inside the frame; out_size % 4 == 0)");
-    if (mode != R50_RESIZE_FLOAT && mode != R50_RESIZE_FIXED) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_u8: unknown mode");
-    if (flags & ~(R50_AUG_HFLIP | R50_AUG_TREV)) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_u8: unknown flags");
+        return op.refuse("invalid arguments (the box must lie inside the frame; out_size % 4 == 0)");
+    if (mode != R50_RESIZE_FLOAT && mode != R50_RESIZE_FIXED) return op.refuse("unknown mode");
+    if (flags & ~(R50_AUG_HFLIP | R50_AUG_TREV)) return op.refuse("unknown flags");
     ResizeArgs a;
     a.hflip = (flags & R50_AUG_HFLIP) ? 1 : 0;
     a.trev = (flags & R50_AUG_TREV) ? 1 : 0;
@@ -2132,18 +2145,16 @@ int r50_op_crop_resize_u8(const void* frames, int t, int h, int w, int top, int 
     if (!a.float_mode) {
         a.px = resize_weight_precision(ww, out_size);
         a.py = resize_weight_precision(hh, out_size);
-        if (a.px < 1 || a.py < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_u8: degenerate weights");
+        if (a.px < 1 || a.py < 1) return op.refuse("degenerate weights");
     }
     a.src = (const unsigned char*)frames; a.dst = (unsigned char*)out;
     a.T = t; a.H = h; a.W = w; a.top = top; a.left = left; a.hh = hh; a.ww = ww; a.out = out_size;
     const size_t lds = 2 * (size_t)((ww * 3 + 6) & ~3);                // two source rows of the crop, dword-padded
-    if (lds > 160 * 1024 || (long long)t * out_size >= (1ll << 31)) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_u8: crop too wide");
+    if (lds > 160 * 1024 || (long long)t * out_size >= (1ll << 31)) return op.refuse("crop too wide");
     hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(crop_resize_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_u8: ") + hipGetErrorString(ea));
+    if (ea != hipSuccess) return op.done(ea);
     hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(t * out_size)), dim3(256), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_u8: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op.done();
 }
 
 // ---- one box per output frame (include/r50_track.h, track_kernels.h, INTEGRATION.md section AA) ----
@@ -2154,176 +2165,152 @@ int r50_track_weight_precision(int in_size, int out_size) {
 
 int r50_op_crop_resize_boxes_u8(const void* src, int64_t src_bytes, const int64_t* table, int t, int max_ww, void* out, void* out_flip,
                                 int out_size, int mode, void* stream) {
-    if (!src || !table || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: null pointer");
-    if (int rc_al = need_aligned(nullptr, "r50_op_crop_resize_boxes_u8",
-                                 {{src, "src_u8", 4}, {out, "out_tchw_u8", 4}, {out_flip, "out_flip_tchw_u8", 4}, {table, "table_dev", 8}}))
-        return rc_al;
-    if (out_flip == out) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: out_flip is not out");
+    const Op op{"r50_op_crop_resize_boxes_u8"};
+    if (!src || !table || !out) return op.refuse("null pointer");
+    if (int rc = op.aligned({{src, "src_u8", 4}, {out, "out_tchw_u8", 4}, {out_flip, "out_flip_tchw_u8", 4}, {table, "table_dev", 8}})) return rc;
+    if (out_flip == out) return op.refuse("out_flip is not out");
     if (t < 1 || src_bytes < 1 || src_bytes >= (1ll << 40) || out_size < 4 || (out_size & 3) || out_size > 4096)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: invalid arguments (need t >= 1, 1 <= src_bytes < 2^40, out_size % 4 == 0 in [4, 4096])");
-    if (mode != R50_RESIZE_FLOAT && mode != R50_RESIZE_FIXED) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: unknown mode");
-    if (max_ww < 1 || max_ww > (160 * 1024 - 12) / 6 || (long long)t * out_size >= (1ll << 31))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: crop too wide");
+        return op.refuse("invalid arguments (need t >= 1, 1 <= src_bytes < 2^40, out_size % 4 == 0 in [4, 4096])");
+    if (mode != R50_RESIZE_FLOAT && mode != R50_RESIZE_FIXED) return op.refuse("unknown mode");
+    if (max_ww < 1 || max_ww > (160 * 1024 - 12) / 6 || (long long)t * out_size >= (1ll << 31)) return op.refuse("crop too wide");
     const size_t lds = 2 * (size_t)((max_ww * 3 + 6) & ~3);            // two source rows of the widest crop, dword-padded
-    if (lds > 160 * 1024) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: crop too wide");
+    if (lds > 160 * 1024) return op.refuse("crop too wide");
     if (out_flip) {                                                     // the two outputs are written by one launch: they may not share a byte
         const long long n = (long long)t * 3 * out_size * out_size;
         const char *o = (const char*)out, *f = (const char*)out_flip;
-        if (o < f + n && f < o + n) return fail(nullptr, R50_ERR_INVALID, "r50_op_crop_resize_boxes_u8: out_flip overlaps out");
+        if (o < f + n && f < o + n) return op.refuse("out_flip overlaps out");
     }
     TrackArgs a;
     a.src = (const unsigned char*)src; a.src_bytes = (long long)src_bytes; a.table = (const long long*)table;
     a.dst = (unsigned char*)out; a.dst_flip = (unsigned char*)out_flip; a.out = out_size; a.float_mode = (mode == R50_RESIZE_FLOAT);
     hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(crop_resize_boxes_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_boxes_u8: ") + hipGetErrorString(ea));
+    if (ea != hipSuccess) return op.done(ea);
     hipLaunchKernelGGL(crop_resize_boxes_u8_kernel, dim3((unsigned)(t * out_size)), dim3(256), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_crop_resize_boxes_u8: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op.done();
 }
 
 int r50_op_resize_frames_u8(const void* frames, int n, int h, int w, const int* src_idx, int t, void* out, int out_size, void* stream) {
+    const Op op{"r50_op_resize_frames_u8"};
     if (!frames || !src_idx || !out || n < 1 || h < 1 || w < 1 || t < 1 || out_size < 1 || out_size > 16384 ||
         (long long)n * h * w * 3 >= (1ll << 40) || (long long)t * out_size >= (1ll << 31))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_resize_frames_u8: invalid arguments");
+        return op.refuse("invalid arguments");
     const size_t lds = 2 * (size_t)w * 3;                               // the two full-width source rows
-    if (lds > 160 * 1024) return fail(nullptr, R50_ERR_INVALID, "r50_op_resize_frames_u8: frames too wide");
+    if (lds > 160 * 1024) return op.refuse("frames too wide");
     // the map lives on the device: read it back once (t ints, one stream synchronisation) so no index can reach past the frames
     std::vector<int> idx((size_t)t);
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(nullptr, hipMemcpyAsync(idx.data(), src_idx, (size_t)t * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(nullptr, hipStreamSynchronize(s));
+    if (hipError_t e = hipMemcpyAsync(idx.data(), src_idx, (size_t)t * sizeof(int), hipMemcpyDeviceToHost, s)) return op.done(e);
+    if (hipError_t e = hipStreamSynchronize(s)) return op.done(e);
     for (int i = 0; i < t; ++i)
         if (idx[i] < 0 || idx[i] >= n)
-            return fail(nullptr, R50_ERR_INVALID, "r50_op_resize_frames_u8: src_idx[" + std::to_string(i) + "] = " +
-                                                      std::to_string(idx[i]) + " is outside [0, " + std::to_string(n) + ")");
+            return op.refuse("src_idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [0, " + std::to_string(n) + ")");
     hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(resize_frames_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_resize_frames_u8: ") + hipGetErrorString(ea));
+    if (ea != hipSuccess) return op.done(ea);
     hipLaunchKernelGGL(resize_frames_u8_kernel, dim3((unsigned)(t * out_size)), dim3(256), lds, s, (const unsigned char*)frames, src_idx,
                        h, w, out_size, (unsigned char*)out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_resize_frames_u8: ") + hipGetErrorString(e));
-    return R50_OK;
+    return op.done();
 }
 
 // ---- skeleton drawing (kernels.h: draw_skeletons_u8_kernel).  Everything is checked here, before the launch: a refused call touches nothing.
 int r50_op_draw_skeletons_u8(const void* bg, int bg_rgb, const float* pts, const void* style, const int* edges_host, int n_edges, int f,
                              int h, int w, int layers, int joints, float half_width, float joint_radius, void* out, void* stream) {
-    const char* me = "r50_op_draw_skeletons_u8: ";
-    auto bad = [&](const std::string& why) { return fail(nullptr, R50_ERR_INVALID, std::string(me) + why); };
-    if (!pts || !style || !out) return bad("null pointer (pts, style and out are required; only bg may be NULL)");
-    if (f < 1 || h < 1 || w < 1) return bad("need f, h, w >= 1");
-    if (joints < 1 || joints > DRAW_MAX_JOINTS) return bad("need 1 <= joints <= 64");
-    if (layers < 1 || layers > DRAW_MAX_LAYERS) return bad("need 1 <= layers <= 8");
-    if (n_edges < 0 || n_edges > DRAW_MAX_EDGES) return bad("need 0 <= n_edges <= 128");
-    if (n_edges > 0 && !edges_host) return bad("null pointer (edges_host with n_edges > 0)");
+    const Op op{"r50_op_draw_skeletons_u8"};
+    if (!pts || !style || !out) return op.refuse("null pointer (pts, style and out are required; only bg may be NULL)");
+    if (f < 1 || h < 1 || w < 1) return op.refuse("need f, h, w >= 1");
+    if (joints < 1 || joints > DRAW_MAX_JOINTS) return op.refuse("need 1 <= joints <= 64");
+    if (layers < 1 || layers > DRAW_MAX_LAYERS) return op.refuse("need 1 <= layers <= 8");
+    if (n_edges < 0 || n_edges > DRAW_MAX_EDGES) return op.refuse("need 0 <= n_edges <= 128");
+    if (n_edges > 0 && !edges_host) return op.refuse("null pointer (edges_host with n_edges > 0)");
     if (!std::isfinite(half_width) || !std::isfinite(joint_radius) || half_width < 0.f || joint_radius < 0.f)
-        return bad("half_width and joint_radius must be finite and >= 0");
-    if (bg_rgb < 0 || bg_rgb > 0xFFFFFF) return bad("bg_rgb must be 0xRRGGBB");
+        return op.refuse("half_width and joint_radius must be finite and >= 0");
+    if (bg_rgb < 0 || bg_rgb > 0xFFFFFF) return op.refuse("bg_rgb must be 0xRRGGBB");
     const long long bytes = (long long)f * h * w * 3;
     const long long tiles_x = (w + DRAW_TILE - 1) / DRAW_TILE, tiles_y = (h + DRAW_TILE - 1) / DRAW_TILE;
-    if (bytes >= (1ll << 40) || tiles_x * tiles_y * f > INT32_MAX) return bad("f * h * w is too large");
+    if (bytes >= (1ll << 40) || tiles_x * tiles_y * f > INT32_MAX) return op.refuse("f * h * w is too large");
     if (bg) {
         const uintptr_t b0 = (uintptr_t)bg, o0 = (uintptr_t)out;
-        if (b0 < o0 + (uintptr_t)bytes && o0 < b0 + (uintptr_t)bytes) return bad("out may not alias bg");
+        if (b0 < o0 + (uintptr_t)bytes && o0 < b0 + (uintptr_t)bytes) return op.refuse("out may not alias bg");
     }
     DrawEdges ed;
     for (int q = 0; q < DRAW_MAX_EDGES; ++q) ed.ab[q] = 0;
     for (int q = 0; q < n_edges; ++q) {
         const int ea = edges_host[2 * q], eb = edges_host[2 * q + 1];
         if (ea < 0 || ea >= joints || eb < 0 || eb >= joints)
-            return bad("edge " + std::to_string(q) + " = (" + std::to_string(ea) + ", " + std::to_string(eb) + ") is outside [0, joints)");
+            return op.refuse("edge " + std::to_string(q) + " = (" + std::to_string(ea) + ", " + std::to_string(eb) + ") is outside [0, joints)");
         ed.ab[q] = (unsigned short)(ea | (eb << 8));
     }
     const size_t lds = draw_lds_bytes(layers, joints, n_edges);                        // <= 45,280 B: under the default 64 KB ceiling
     const bool vec = (w % 4 == 0) && (((uintptr_t)out | (uintptr_t)bg) & 3u) == 0;      // a NULL bg counts as aligned
     const dim3 grid((unsigned)(tiles_x * tiles_y * f));
-    if (vec)
-        hipLaunchKernelGGL(draw_skeletons_u8_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, (const unsigned char*)bg, (unsigned)bg_rgb,
-                           pts, (const unsigned char*)style, ed, n_edges, h, w, layers, joints, (int)tiles_x, (int)tiles_y, half_width,
-                           joint_radius, (unsigned char*)out);
-    else
-        hipLaunchKernelGGL(draw_skeletons_u8_kernel<0>, grid, dim3(256), lds, (hipStream_t)stream, (const unsigned char*)bg, (unsigned)bg_rgb,
-                           pts, (const unsigned char*)style, ed, n_edges, h, w, layers, joints, (int)tiles_x, (int)tiles_y, half_width,
-                           joint_radius, (unsigned char*)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(e));
+    R50_ET_LAUNCH(vec, draw_skeletons_u8_kernel, grid, dim3(256), lds, stream, (const unsigned char*)bg, (unsigned)bg_rgb, pts,     // <1>: the 12-byte path
+                  (const unsigned char*)style, ed, n_edges, h, w, layers, joints, (int)tiles_x, (int)tiles_y, half_width, joint_radius,
+                  (unsigned char*)out);
+    return op.done();
 }
 
 // ---- lifting head pieces (kernels.h: cast_rows_kernel, concat_pad_kernel, gn_relu_causal3_kernel); et: 0 = bf16, 1 = fp16
 int r50_op_cast_rows(const float* src, int64_t rows, int c, void* dst, int cpad, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_cast_rows", {{dst, "dst", 4}})) return rc_al;
-    if (!src || !dst || rows < 1 || c < 1 || cpad < c || (cpad & 1) || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_cast_rows: invalid arguments");
-    const long long pairs = rows * (cpad / 2);
-    const unsigned grid = (unsigned)std::min<long long>((pairs + 255) / 256, 256 * 32);
-    if (et) hipLaunchKernelGGL(cast_rows_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (unsigned short*)dst, (long long)rows, c, cpad);
-    else hipLaunchKernelGGL(cast_rows_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (unsigned short*)dst, (long long)rows, c, cpad);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_cast_rows: ") + hipGetErrorString(e));
+    const Op op{"r50_op_cast_rows"};
+    if (int rc = op.aligned({{dst, "dst", 4}})) return rc;
+    if (!src || !dst || rows < 1 || c < 1 || cpad < c || (cpad & 1) || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, cast_rows_kernel, dim3(ew_grid(rows * (cpad / 2))), dim3(256), 0, stream, src, (unsigned short*)dst, (long long)rows, c, cpad);
+    return op.done();
 }
 
 int r50_op_concat_pad(const void* phi, int d, const float* y, int ny, int64_t rows, void* dst, int dp, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_concat_pad", {{phi, "phi", 2}, {dst, "dst", 2}})) return rc_al;
-    if (!phi || !y || !dst || rows < 1 || d < 1 || ny < 0 || dp < d + ny || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_concat_pad: invalid arguments");
-    const long long total = rows * dp;
-    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 256 * 32);
-    if (et) hipLaunchKernelGGL(concat_pad_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)phi, d, y, ny, (unsigned short*)dst, (long long)rows, dp);
-    else hipLaunchKernelGGL(concat_pad_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)phi, d, y, ny, (unsigned short*)dst, (long long)rows, dp);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_concat_pad: ") + hipGetErrorString(e));
+    const Op op{"r50_op_concat_pad"};
+    if (int rc = op.aligned({{phi, "phi", 2}, {dst, "dst", 2}})) return rc;
+    if (!phi || !y || !dst || rows < 1 || d < 1 || ny < 0 || dp < d + ny || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, concat_pad_kernel, dim3(ew_grid(rows * dp)), dim3(256), 0, stream, (const unsigned short*)phi, d, y, ny, (unsigned short*)dst,
+                  (long long)rows, dp);
+    return op.done();
 }
 
 int r50_op_add_rows(float* y, int ny, const void* dy, int dp, int64_t rows, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_add_rows", {{dy, "dy", 2}})) return rc_al;
-    if (!y || !dy || rows < 1 || ny < 1 || dp < ny || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_add_rows: invalid arguments");
-    const long long total = rows * ny;
-    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 256 * 32);
-    if (et) hipLaunchKernelGGL(add_rows_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, ny, (const unsigned short*)dy, dp, (long long)rows);
-    else hipLaunchKernelGGL(add_rows_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, ny, (const unsigned short*)dy, dp, (long long)rows);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_add_rows: ") + hipGetErrorString(e));
+    const Op op{"r50_op_add_rows"};
+    if (int rc = op.aligned({{dy, "dy", 2}})) return rc;
+    if (!y || !dy || rows < 1 || ny < 1 || dp < ny || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, add_rows_kernel, dim3(ew_grid(rows * ny)), dim3(256), 0, stream, y, ny, (const unsigned short*)dy, dp, (long long)rows);
+    return op.done();
 }
 
 int r50_op_gn_relu_causal3(const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta, float eps,
                            void* out, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3", {{x, "x", 2}, {out, "out", 2}})) return rc_al;
+    const Op op{"r50_op_gn_relu_causal3"};
+    if (int rc = op.aligned({{x, "x", 2}, {out, "out", 2}})) return rc;
     if (!x || !gamma || !beta || !out || b < 1 || t < 1 || c < 1 || groups < 1 || c % groups || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3: invalid arguments");
-    if (et) hipLaunchKernelGGL(gn_relu_causal3_kernel<1>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, t, c, groups, eps);
-    else hipLaunchKernelGGL(gn_relu_causal3_kernel<0>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, t, c, groups, eps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_gn_relu_causal3: ") + hipGetErrorString(e));
+        return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, gn_relu_causal3_kernel, dim3((unsigned)(b * groups)), dim3(256), 0, stream, (const unsigned short*)x, gamma, beta,
+                  (unsigned short*)out, t, c, groups, eps);
+    return op.done();
 }
 
 int r50_op_gn_relu_causal3_tm(const void* x, int b, int t, int t0, int c, int groups, const float* gamma, const float* beta, float eps,
                               void* out, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3_tm", {{x, "x", 2}, {out, "out", 2}})) return rc_al;
+    const Op op{"r50_op_gn_relu_causal3_tm"};
+    if (int rc = op.aligned({{x, "x", 2}, {out, "out", 2}})) return rc;
     if (!x || !gamma || !beta || !out || b < 1 || t < 1 || t0 < 0 || t0 >= t || c < 1 || groups < 1 || c % groups ||
         (et != 0 && et != 1) || (int64_t)b * groups > INT32_MAX || (int64_t)t * (c / groups) > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_tm: invalid arguments (need 0 <= t0 < t, c % groups == 0)");
-    if (et) hipLaunchKernelGGL(gn_relu_causal3_tm_kernel<1>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, b, t, t0, c, groups, eps);
-    else hipLaunchKernelGGL(gn_relu_causal3_tm_kernel<0>, dim3((unsigned)(b * groups)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, gamma, beta, (unsigned short*)out, b, t, t0, c, groups, eps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_gn_relu_causal3_tm: ") + hipGetErrorString(e));
+        return op.refuse("invalid arguments (need 0 <= t0 < t, c % groups == 0)");
+    R50_ET_LAUNCH(et, gn_relu_causal3_tm_kernel, dim3((unsigned)(b * groups)), dim3(256), 0, stream, (const unsigned short*)x, gamma, beta,
+                  (unsigned short*)out, b, t, t0, c, groups, eps);
+    return op.done();
 }
 
 // ---- ColorJitter variant (kernels.h: cj_*_kernel) ----
 int r50_op_color_jitter_u8(const void* frames_u8, int t, int hw, const int* order4, float brightness, float contrast, float saturation,
                            float hue, int normalize, float* out_f32, float* scratch_means, void* stream) {
-    if (!frames_u8 || !order4 || !out_f32 || !scratch_means || t < 1 || hw < 1)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_color_jitter_u8: invalid arguments");
+    const Op op{"r50_op_color_jitter_u8"};
+    if (!frames_u8 || !order4 || !out_f32 || !scratch_means || t < 1 || hw < 1) return op.refuse("invalid arguments");
     int seen = 0;
     for (int i = 0; i < 4; ++i) {
-        if (order4[i] < 0 || order4[i] > 3) return fail(nullptr, R50_ERR_INVALID, "r50_op_color_jitter_u8: order entries must be 0..3");
+        if (order4[i] < 0 || order4[i] > 3) return op.refuse("order entries must be 0..3");
         seen |= 1 << order4[i];
     }
-    if (seen != 15) return fail(nullptr, R50_ERR_INVALID, "r50_op_color_jitter_u8: order must be a permutation of 0..3");
+    if (seen != 15) return op.refuse("order must be a permutation of 0..3");
     hipStream_t s = (hipStream_t)stream;
     const long long n = (long long)t * 3 * hw;
-    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 256 * 32);
+    const unsigned grid = ew_grid(n);
     hipLaunchKernelGGL(cj_from_u8_kernel, dim3(grid), dim3(256), 0, s, (const unsigned char*)frames_u8, out_f32, n);
     const float factor[4] = {brightness, contrast, saturation, hue};
     for (int i = 0; i < 4; ++i) {
@@ -2335,238 +2322,235 @@ int r50_op_color_jitter_u8(const void* frames_u8, int t, int hw, const int* orde
     if (normalize)
         hipLaunchKernelGGL(cj_normalize_kernel, dim3(grid), dim3(256), 0, s, out_f32, (long long)t * 3, hw, 0.485f, 0.456f, 0.406f, 0.229f,
                            0.224f, 0.225f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_color_jitter_u8: ") + hipGetErrorString(e));
+    return op.done();
 }
 
 // ---- lifting head, backward + optimizer (kernels.h, "Lifting head, backward + optimizer") ----
-static unsigned ew_grid(long long n) { return (unsigned)std::min<long long>(std::max<long long>((n + 255) / 256, 1), 256 * 32); }
-static int ew_done(const char* what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define R50_ET_LAUNCH(kern, grid, block, stream, ...)                                                              \
-    do {                                                                                                           \
-        if (et) hipLaunchKernelGGL(kern<1>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__);                      \
-        else hipLaunchKernelGGL(kern<0>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__);                         \
-    } while (0)
-
 int r50_op_transpose16(const void* src, int rows, int cols, void* dst, int ld, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_transpose16", {{src, "src", 2}, {dst, "dst", 2}})) return rc_al;
-    if (!src || !dst || rows < 1 || cols < 1 || ld < rows) return fail(nullptr, R50_ERR_INVALID, "r50_op_transpose16: invalid arguments");
+    const Op op{"r50_op_transpose16"};
+    if (int rc = op.aligned({{src, "src", 2}, {dst, "dst", 2}})) return rc;
+    if (!src || !dst || rows < 1 || cols < 1 || ld < rows) return op.refuse("invalid arguments");
     hipLaunchKernelGGL(transpose16_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)src, (unsigned short*)dst, rows, cols, ld);
-    return ew_done("r50_op_transpose16");
+    return op.done();
 }
 
 int r50_op_mask_scale(void* x, const void* mask_u8, float scale, int64_t n, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_mask_scale", {{x, "x", 2}})) return rc_al;
-    if (!x || !mask_u8 || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_mask_scale: invalid arguments");
-    R50_ET_LAUNCH(mask_scale_kernel, dim3(ew_grid(n)), dim3(256), stream, (unsigned short*)x, (const unsigned char*)mask_u8, scale, (long long)n);
-    return ew_done("r50_op_mask_scale");
+    const Op op{"r50_op_mask_scale"};
+    if (int rc = op.aligned({{x, "x", 2}})) return rc;
+    if (!x || !mask_u8 || n < 1 || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, mask_scale_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, (unsigned short*)x, (const unsigned char*)mask_u8, scale, (long long)n);
+    return op.done();
 }
 
 int r50_op_relu_bwd(void* dy, const void* act, float scale, int64_t n, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_relu_bwd", {{dy, "dy", 2}, {act, "act", 2}})) return rc_al;
-    if (!dy || !act || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_relu_bwd: invalid arguments");
-    R50_ET_LAUNCH(relu_bwd_kernel, dim3(ew_grid(n)), dim3(256), stream, (unsigned short*)dy, (const unsigned short*)act, scale, (long long)n);
-    return ew_done("r50_op_relu_bwd");
+    const Op op{"r50_op_relu_bwd"};
+    if (int rc = op.aligned({{dy, "dy", 2}, {act, "act", 2}})) return rc;
+    if (!dy || !act || n < 1 || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, relu_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, (unsigned short*)dy, (const unsigned short*)act, scale, (long long)n);
+    return op.done();
 }
 
 int r50_op_colsum(const void* x, int64_t rows, int cols, int ld, float scale, float* out, int accumulate, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_colsum", {{x, "x", 2}})) return rc_al;
-    if (!x || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum: invalid arguments");
-    R50_ET_LAUNCH(colsum_kernel, dim3((cols + 63) / 64), dim3(1024), stream, (const unsigned short*)x, (long long)rows, cols, ld, scale, out, accumulate);
-    return ew_done("r50_op_colsum");
+    const Op op{"r50_op_colsum"};
+    if (int rc = op.aligned({{x, "x", 2}})) return rc;
+    if (!x || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, colsum_kernel, dim3((cols + 63) / 64), dim3(1024), 0, stream, (const unsigned short*)x, (long long)rows, cols, ld, scale, out,
+                  accumulate);
+    return op.done();
 }
 
 int r50_op_colsum_split(const void* x, int64_t rows, int cols, int ld, float scale, float* part, float* out, int accumulate, int et,
                         void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_colsum_split", {{x, "x", 2}})) return rc_al;
-    if (!x || !part || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum_split: invalid arguments");
-    R50_ET_LAUNCH(colsum_chain_kernel, dim3((cols + 63) / 64, 16), dim3(64), stream, (const unsigned short*)x, (long long)rows, cols, ld, part);
+    const Op op{"r50_op_colsum_split"};
+    if (int rc = op.aligned({{x, "x", 2}})) return rc;
+    if (!x || !part || !out || rows < 1 || cols < 1 || ld < cols || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, colsum_chain_kernel, dim3((cols + 63) / 64, 16), dim3(64), 0, stream, (const unsigned short*)x, (long long)rows, cols, ld, part);
     hipLaunchKernelGGL(colsum_chain_sum_kernel, dim3((cols + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, cols, scale, out, accumulate);
-    return ew_done("r50_op_colsum_split");
+    return op.done();
 }
 
 int r50_op_colsum_f32(const float* x, int64_t rows, int cols, float scale, float* out, int accumulate, void* stream) {
-    if (!x || !out || rows < 1 || cols < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_colsum_f32: invalid arguments");
+    const Op op{"r50_op_colsum_f32"};
+    if (!x || !out || rows < 1 || cols < 1) return op.refuse("invalid arguments");
     hipLaunchKernelGGL(colsum_f32_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, (long long)rows, cols, scale, out, accumulate);
-    return ew_done("r50_op_colsum_f32");
+    return op.done();
 }
 
 int r50_op_grad_accum(const void* src, float scale, float* dst, int64_t n, int accumulate, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_grad_accum", {{src, "src", 2}})) return rc_al;
-    if (!src || !dst || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_accum: invalid arguments");
-    R50_ET_LAUNCH(grad_accum_kernel, dim3(ew_grid(n)), dim3(256), stream, (const unsigned short*)src, scale, dst, (long long)n, accumulate);
-    return ew_done("r50_op_grad_accum");
+    const Op op{"r50_op_grad_accum"};
+    if (int rc = op.aligned({{src, "src", 2}})) return rc;
+    if (!src || !dst || n < 1 || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, grad_accum_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, (const unsigned short*)src, scale, dst, (long long)n, accumulate);
+    return op.done();
 }
 
 int r50_op_mse_loss_grad(const float* y, const float* gt, int64_t n, float loss_scale, float* dy, float* loss2, void* stream) {
-    if (!y || !gt || !dy || !loss2 || n < 3 || n % 3) return fail(nullptr, R50_ERR_INVALID, "r50_op_mse_loss_grad: invalid arguments");
+    const Op op{"r50_op_mse_loss_grad"};
+    if (!y || !gt || !dy || !loss2 || n < 3 || n % 3) return op.refuse("invalid arguments");
     hipLaunchKernelGGL(mse_loss_grad_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, y, gt, (long long)n, loss_scale, dy, loss2);
-    return ew_done("r50_op_mse_loss_grad");
+    return op.done();
 }
 
 int r50_op_pose_metrics(const float* pred, const float* gt, int64_t rows, int joints, double* acc, void* stream) {
-    if (!pred || !gt || !acc || rows < 1 || joints < 1 || rows > INT64_MAX / 3 / joints)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_metrics: invalid arguments");
+    const Op op{"r50_op_pose_metrics"};
+    if (!pred || !gt || !acc || rows < 1 || joints < 1 || rows > INT64_MAX / 3 / joints) return op.refuse("invalid arguments");
     hipLaunchKernelGGL(pose_metrics_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, (long long)(rows * joints), acc);
-    return ew_done("r50_op_pose_metrics");
+    return op.done();
 }
 
 int r50_op_horizon_metrics(const float* pred, const float* gt, int b, int p, int t_gt, int i0, int joints, double* acc, void* stream) {
+    const Op op{"r50_op_horizon_metrics"};
     if (!pred || !gt || !acc || b < 1 || p < 1 || joints < 1 || i0 < 0 || t_gt < 1 || (int64_t)i0 + p > t_gt ||
         (int64_t)b * joints > INT32_MAX || (int64_t)b * t_gt * joints > INT64_MAX / 3)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_horizon_metrics: invalid arguments (need b, p, joints >= 1 and 0 <= i0, i0 + p <= t_gt)");
+        return op.refuse("invalid arguments (need b, p, joints >= 1 and 0 <= i0, i0 + p <= t_gt)");
     hipLaunchKernelGGL(horizon_metrics_kernel, dim3((unsigned)p), dim3(256), 0, (hipStream_t)stream, pred, gt, b, p, t_gt, i0, joints, acc);
-    return ew_done("r50_op_horizon_metrics");
+    return op.done();
 }
 
 int r50_op_pose_protocols(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
                           int n_groups, double* acc, void* stream) {
-    if (!pred || !gt || !group || !acc) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_protocols: null pointer");
+    const Op op{"r50_op_pose_protocols"};
+    if (!pred || !gt || !group || !acc) return op.refuse("null pointer");
     if (b < 1 || p < 1 || n_groups < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || i0 < 0 || (int64_t)i0 + p > t_gt ||
         (int64_t)p * n_groups > INT32_MAX || (int64_t)b * t_gt > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_protocols: invalid arguments (need b, p, n_groups >= 1, 1 <= joints <= 64, "
-                                              "0 <= root < joints and 0 <= i0, i0 + p <= t_gt)");
+        return op.refuse("invalid arguments (need b, p, n_groups >= 1, 1 <= joints <= 64, 0 <= root < joints and 0 <= i0, i0 + p <= t_gt)");
     hipLaunchKernelGGL(pose_protocols_kernel, dim3((unsigned)(p * n_groups)), dim3(256), 0, (hipStream_t)stream, pred, gt, group, b, p,
                        t_gt, i0, joints, root, n_groups, acc);
-    return ew_done("r50_op_pose_protocols");
+    return op.done();
 }
 
 int r50_op_pose_detail_metrics(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int joints, int root,
                                int n_groups, int n_thr, double thr_max, double* acc, void* stream) {
-    if (!pred || !gt || !group || !acc) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_detail_metrics: null pointer");
+    const Op op{"r50_op_pose_detail_metrics"};
+    if (!pred || !gt || !group || !acc) return op.refuse("null pointer");
     if (b < 1 || p < 1 || n_groups < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || i0 < 0 || (int64_t)i0 + p > t_gt ||
         (int64_t)p * n_groups > INT32_MAX || (int64_t)b * t_gt > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_detail_metrics: invalid arguments (need b, p, n_groups >= 1, 1 <= joints <= 64, "
-                                              "0 <= root < joints and 0 <= i0, i0 + p <= t_gt)");
+        return op.refuse("invalid arguments (need b, p, n_groups >= 1, 1 <= joints <= 64, 0 <= root < joints and 0 <= i0, i0 + p <= t_gt)");
     if (n_thr < 2 || n_thr > POSE_DETAIL_MAX_THR || !std::isfinite(thr_max) || !(thr_max > 0.0))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_detail_metrics: invalid arguments (need 2 <= n_thr <= 1024 and a finite thr_max > 0)");
+        return op.refuse("invalid arguments (need 2 <= n_thr <= 1024 and a finite thr_max > 0)");
     hipLaunchKernelGGL(pose_detail_metrics_kernel, dim3((unsigned)(p * n_groups)), dim3(256), 0, (hipStream_t)stream, pred, gt, group, b, p,
                        t_gt, i0, joints, root, n_groups, n_thr, thr_max, acc);
-    return ew_done("r50_op_pose_detail_metrics");
+    return op.done();
 }
 
 int r50_op_dtw_protocols(const float* pred, const float* gt, const int* group, int b, int p, int t_gt, int i0, int q, int joints, int root,
                          int band, int n_groups, double* clip_out, int* path_out, double* acc, void* stream) {
-    if (!pred || !gt || !group || !clip_out || !acc) return fail(nullptr, R50_ERR_INVALID, "r50_op_dtw_protocols: null pointer");
+    const Op op{"r50_op_dtw_protocols"};
+    if (!pred || !gt || !group || !clip_out || !acc) return op.refuse("null pointer");
     if (b < 1 || p < 1 || p > DTW_MAX_LEN || q < 1 || q > DTW_MAX_LEN || n_groups < 1 || joints < 1 || joints > 64 || root < 0 ||
         root >= joints || i0 < 0 || (int64_t)i0 + q > t_gt || (int64_t)b * t_gt > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_dtw_protocols: invalid arguments (need b, n_groups >= 1, 1 <= p, q <= 64, "
-                                              "1 <= joints <= 64, 0 <= root < joints and 0 <= i0, i0 + q <= t_gt)");
-    if (band >= 0 && band < (p > q ? p - q : q - p))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_dtw_protocols: invalid arguments (a band >= 0 must be >= |p - q|)");
+        return op.refuse("invalid arguments (need b, n_groups >= 1, 1 <= p, q <= 64, 1 <= joints <= 64, 0 <= root < joints and "
+                         "0 <= i0, i0 + q <= t_gt)");
+    if (band >= 0 && band < (p > q ? p - q : q - p)) return op.refuse("invalid arguments (a band >= 0 must be >= |p - q|)");
     const size_t lds = dtw_lds_bytes(p, q);
     if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dtw_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_dtw_protocols: ") + hipGetErrorString(e));
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dtw_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+            return op.done(e);
     }
     hipLaunchKernelGGL(dtw_align_kernel, dim3((unsigned)b), dim3(256), lds, (hipStream_t)stream, pred, gt, p, t_gt, i0, q, joints, root, band,
                        clip_out, path_out);
     hipLaunchKernelGGL(dtw_group_sums_kernel, dim3((unsigned)n_groups), dim3(256), 0, (hipStream_t)stream, clip_out, group, b, p, n_groups,
                        acc);
-    return ew_done("r50_op_dtw_protocols");
+    return op.done();
 }
 
 int r50_op_stitch_poses(const float* pred, const float* gt, int64_t rows, int joints, const int* offsets, const int* src, int frames, int t,
                         int mode, int ramp, float* fused, float* gt_out, float* spread, float* gt_gap, void* stream) {
-    if (!pred || !gt || !offsets || !src || !fused || !gt_out || !spread || !gt_gap)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_stitch_poses: null pointer");
+    const Op op{"r50_op_stitch_poses"};
+    if (!pred || !gt || !offsets || !src || !fused || !gt_out || !spread || !gt_gap) return op.refuse("null pointer");
     if (rows < 1 || rows > INT32_MAX || joints < 1 || joints > 64 || frames < 1 || t < 1 || rows % t != 0 || mode < 0 || mode > 2 || ramp < 1)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_stitch_poses: invalid arguments (need 1 <= rows < 2^31 a multiple of t >= 1, "
-                                              "1 <= joints <= 64, frames >= 1, mode in {0,1,2} and ramp >= 1)");
+        return op.refuse("invalid arguments (need 1 <= rows < 2^31 a multiple of t >= 1, 1 <= joints <= 64, frames >= 1, mode in {0,1,2} and "
+                         "ramp >= 1)");
     hipLaunchKernelGGL(stitch_poses_kernel, dim3((unsigned)((frames + STITCH_WAVES - 1) / STITCH_WAVES)), dim3(64 * STITCH_WAVES), 0,
                        (hipStream_t)stream, pred, gt, offsets, src, frames, joints, t, mode, ramp, fused, gt_out, spread, gt_gap);
-    return ew_done("r50_op_stitch_poses");
+    return op.done();
 }
 
 int r50_op_gather_window_rows(const float* src, int64_t src_rows, int c, const int* starts, int b, int t, void* dst, int et, void* stream) {
-    if (!src || !starts || !dst) return fail(nullptr, R50_ERR_INVALID, "r50_op_gather_window_rows: null pointer");
+    const Op op{"r50_op_gather_window_rows"};
+    if (!src || !starts || !dst) return op.refuse("null pointer");
     if (b < 1 || t < 1 || c < 8 || c % 8 != 0 || src_rows < t || src_rows > INT32_MAX || (et != 0 && et != 1) ||
         (long long)b * t > INT32_MAX / (c / 8))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_gather_window_rows: invalid arguments (need b >= 1, 1 <= t <= src_rows < 2^31, "
-                                              "c a positive multiple of 8, b * t * c / 8 < 2^31, et in {0,1})");
-    if (int rc_al = need_aligned(nullptr, "r50_op_gather_window_rows", {{src, "src_f32", 16}, {dst, "dst", 16}})) return rc_al;
+        return op.refuse("invalid arguments (need b >= 1, 1 <= t <= src_rows < 2^31, c a positive multiple of 8, b * t * c / 8 < 2^31, et in {0,1})");
+    if (int rc = op.aligned({{src, "src_f32", 16}, {dst, "dst", 16}})) return rc;
     const long long items = (long long)b * t * (c / 8);
-    R50_ET_LAUNCH(gather_window_rows_kernel, dim3(ew_grid(items)), dim3(256), stream, src, starts, (unsigned short*)dst, (unsigned)items,
+    R50_ET_LAUNCH(et, gather_window_rows_kernel, dim3(ew_grid(items)), dim3(256), 0, stream, src, starts, (unsigned short*)dst, (unsigned)items,
                   (unsigned)t, (unsigned)(c / 8));
-    return ew_done("r50_op_gather_window_rows");
+    return op.done();
 }
 
 int r50_op_merge_mirrored_poses(const float* a, const float* b_mirrored, int64_t rows, int joints, const int* perm, float* out,
                                 void* stream) {
-    if (!a || !b_mirrored || !perm || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_merge_mirrored_poses: null pointer");
+    const Op op{"r50_op_merge_mirrored_poses"};
+    if (!a || !b_mirrored || !perm || !out) return op.refuse("null pointer");
     if (rows < 1 || joints < 1 || joints > 64 || rows > INT64_MAX / (3 * 64))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_merge_mirrored_poses: invalid arguments (need rows >= 1 and 1 <= joints <= 64)");
+        return op.refuse("invalid arguments (need rows >= 1 and 1 <= joints <= 64)");
     const long long bytes = (long long)rows * joints * 3 * (long long)sizeof(float);
     const char *o0 = (const char*)out, *b0 = (const char*)b_mirrored, *a0 = (const char*)a;
     if ((o0 < b0 + bytes && b0 < o0 + bytes) || (o0 != a0 && o0 < a0 + bytes && a0 < o0 + bytes))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_merge_mirrored_poses: out overlaps an input (it may be exactly a, nothing else)");
+        return op.refuse("out overlaps an input (it may be exactly a, nothing else)");
     hipLaunchKernelGGL(merge_mirrored_poses_kernel, dim3(ew_grid((long long)rows * joints * 3)), dim3(256), 0, (hipStream_t)stream, a,
                        b_mirrored, perm, out, (long long)rows, joints);
-    return ew_done("r50_op_merge_mirrored_poses");
+    return op.done();
 }
 
 int r50_op_sequence_metrics(const float* fused, const float* gt, const float* spread, const int* offsets, const int* seq, const int* idx,
                             const int* group, int frames, int joints, int root, int n_groups, double* part, int n_blocks, void* stream) {
-    if (!fused || !gt || !spread || !offsets || !seq || !idx || !group || !part)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_sequence_metrics: null pointer");
+    const Op op{"r50_op_sequence_metrics"};
+    if (!fused || !gt || !spread || !offsets || !seq || !idx || !group || !part) return op.refuse("null pointer");
     if (frames < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || n_groups < 1 || n_blocks < 1 ||
         (int64_t)n_blocks * n_groups > INT32_MAX / 8)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_sequence_metrics: invalid arguments (need frames, n_groups, n_blocks >= 1, "
-                                              "1 <= joints <= 64 and 0 <= root < joints)");
+        return op.refuse("invalid arguments (need frames, n_groups, n_blocks >= 1, 1 <= joints <= 64 and 0 <= root < joints)");
     hipLaunchKernelGGL(sequence_metrics_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, fused, gt, spread, offsets, seq,
                        idx, group, frames, joints, root, n_groups, part);
-    return ew_done("r50_op_sequence_metrics");
+    return op.done();
 }
 
 int r50_op_future_pose_loss_grad(const float* y_hat, const float* gt, int b, int t, int joints, float loss_scale, float* dy, float* loss2,
                                  void* stream) {
+    const Op op{"r50_op_future_pose_loss_grad"};
     if (!y_hat || !gt || !dy || !loss2 || b < 1 || t < 2 || joints < 1 || (int64_t)b * t > INT64_MAX / 3 / joints)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_future_pose_loss_grad: invalid arguments (null pointer, b < 1, t < 2 or joints < 1)");
+        return op.refuse("invalid arguments (null pointer, b < 1, t < 2 or joints < 1)");
     hipLaunchKernelGGL(future_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, y_hat, gt, (long long)b * t, t, joints,
                        loss_scale, dy, loss2);
-    return ew_done("r50_op_future_pose_loss_grad");
+    return op.done();
 }
 
 int r50_op_joint_pose_loss_grad(const float* y, const float* gt, int b, int t, int joints, float lambda_future, float loss_scale, float* dy,
                                 float* out4, void* stream) {
-    if (!y || !gt || !dy || !out4) return fail(nullptr, R50_ERR_INVALID, "r50_op_joint_pose_loss_grad: null pointer");
+    const Op op{"r50_op_joint_pose_loss_grad"};
+    if (!y || !gt || !dy || !out4) return op.refuse("null pointer");
     if (b < 1 || t < 2 || joints < 1 || joints > 64 || (int64_t)b * t > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_joint_pose_loss_grad: invalid arguments (need b >= 1, t >= 2 and 1 <= joints <= 64)");
+        return op.refuse("invalid arguments (need b >= 1, t >= 2 and 1 <= joints <= 64)");
     hipLaunchKernelGGL(joint_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, y, gt, (long long)b * t, t, joints,
                        loss_scale, loss_scale * lambda_future, dy, out4);
-    return ew_done("r50_op_joint_pose_loss_grad");
+    return op.done();
 }
 
 int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt2d, const float* K, int b, int t, int s0, int joints,
                               const int* edges_host, int n_edges, float lambda_2d, float lambda_vel, float lambda_bone, float eps,
                               float term_scale, float loss_scale, float* dy, double* part, float* out8, void* stream) {
-    const char* me = "r50_op_geo_pose_loss_grad: ";
-    auto bad = [&](const char* why) { return fail(nullptr, R50_ERR_INVALID, std::string(me) + why); };
-    if (!y || !gt3d || !gt2d || !K || !part || !out8) return bad("null pointer (y, gt3d, gt2d, K, part and out8 are required; only dy may be NULL)");
-    if (b < 1) return bad("need b >= 1");
-    if (s0 < 0 || s0 > 1) return bad("need 0 <= s0 <= 1");
-    if (t < 1 || t - s0 < 1) return bad("need t - s0 >= 1");
-    if (joints < 1 || joints > 64) return bad("need 1 <= joints <= 64");
-    if (n_edges < 0 || n_edges > GEO_MAX_EDGES) return bad("need 0 <= n_edges <= 64");
-    if (n_edges > 0 && !edges_host) return bad("null pointer (edges_host with n_edges > 0)");
+    const Op op{"r50_op_geo_pose_loss_grad"};
+    if (!y || !gt3d || !gt2d || !K || !part || !out8) return op.refuse("null pointer (y, gt3d, gt2d, K, part and out8 are required; only dy may be NULL)");
+    if (b < 1) return op.refuse("need b >= 1");
+    if (s0 < 0 || s0 > 1) return op.refuse("need 0 <= s0 <= 1");
+    if (t < 1 || t - s0 < 1) return op.refuse("need t - s0 >= 1");
+    if (joints < 1 || joints > 64) return op.refuse("need 1 <= joints <= 64");
+    if (n_edges < 0 || n_edges > GEO_MAX_EDGES) return op.refuse("need 0 <= n_edges <= 64");
+    if (n_edges > 0 && !edges_host) return op.refuse("null pointer (edges_host with n_edges > 0)");
     if (!std::isfinite(lambda_2d) || !std::isfinite(lambda_vel) || !std::isfinite(lambda_bone) || lambda_2d < 0.f || lambda_vel < 0.f ||
         lambda_bone < 0.f)
-        return bad("the lambdas must be finite and >= 0");
-    if (!(eps > 0.f) || !std::isfinite(eps)) return bad("need eps > 0");
-    if (lambda_vel != 0.f && t - s0 < 2) return bad("need t - s0 >= 2 when lambda_vel != 0");
-    if ((int64_t)t * joints > GEO_MAX_TJ) return bad("t * joints exceeds 4608, the most one workgroup stages in LDS (T 256 at J 17 fits)");
-    if ((int64_t)b * t * joints > INT32_MAX / 3) return bad("b * t * joints * 3 exceeds the int range");
+        return op.refuse("the lambdas must be finite and >= 0");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return op.refuse("need eps > 0");
+    if (lambda_vel != 0.f && t - s0 < 2) return op.refuse("need t - s0 >= 2 when lambda_vel != 0");
+    if ((int64_t)t * joints > GEO_MAX_TJ) return op.refuse("t * joints exceeds 4608, the most one workgroup stages in LDS (T 256 at J 17 fits)");
+    if ((int64_t)b * t * joints > INT32_MAX / 3) return op.refuse("b * t * joints * 3 exceeds the int range");
     GeoEdges ed;
     for (int q = 0; q < GEO_MAX_EDGES; ++q) ed.ab[q] = 0;
     for (int q = 0; q < n_edges; ++q) {
         const int ea = edges_host[2 * q], eb = edges_host[2 * q + 1];
-        if (ea < 0 || ea >= joints || eb < 0 || eb >= joints) return bad("every edge index must be in [0, joints)");
+        if (ea < 0 || ea >= joints || eb < 0 || eb >= joints) return op.refuse("every edge index must be in [0, joints)");
         ed.ab[q] = ea | (eb << 8);
     }
     const double nj = (double)b * (t - s0) * joints, nvj = (double)b * (t - s0 - 1) * joints, nb = (double)b * (t - s0) * n_edges;
@@ -2577,12 +2561,12 @@ int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt
     static std::atomic<unsigned long long> lds_set{0};      // the kernel's dynamic-LDS ceiling is raised once per device, not per call
     int dev = 0;
     hipError_t ea = hipGetDevice(&dev);
-    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(ea));
+    if (ea != hipSuccess) return op.done(ea);
     const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
     if (!bit || !(lds_set.load() & bit)) {
         ea = hipFuncSetAttribute(reinterpret_cast<const void*>(geo_pose_loss_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  GEO_MAX_TJ * 24);
-        if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(ea));
+        if (ea != hipSuccess) return op.done(ea);
         lds_set.fetch_or(bit);
     }
     hipLaunchKernelGGL(geo_pose_loss_grad_kernel, dim3((unsigned)b), dim3(256), lds, (hipStream_t)stream, y, gt3d, gt2d, K, t, s0, joints, ed,
@@ -2590,43 +2574,40 @@ int r50_op_geo_pose_loss_grad(const float* y, const float* gt3d, const float* gt
                        (float)(3ll * (long long)nj), loss_scale * term_scale, c2, cv, cb, eps, dy, part);
     hipLaunchKernelGGL(geo_pose_sum_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, (const double*)part, b, nj, nvj, nb, lambda_2d,
                        lambda_vel, lambda_bone, out8);
-    return ew_done("r50_op_geo_pose_loss_grad");
+    return op.done();
 }
 
 int r50_op_ar_latent_grad(const void* ar, const void* phi, const float* dphi_hat, int b, int t, int d, float lambda, float loss_scale,
                           void* dar, float* loss_lat, float* row_part, int et, void* stream) {
-    if (!ar || !phi || !dphi_hat || !dar || !loss_lat || !row_part)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: null pointer");
-    if (b < 1 || t < 2 || (int64_t)b * t > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: need b >= 1, t >= 2 (b*t within int range)");
-    if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: d must be a positive multiple of 8");
-    if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_ar_latent_grad: et must be 0 (bf16) or 1 (fp16)");
-    if (int rc_al = need_aligned(nullptr, "r50_op_ar_latent_grad", {{ar, "ar", 16}, {phi, "phi", 16}, {dphi_hat, "dphi_hat", 16}, {dar, "dar", 16}}))
-        return rc_al;
+    const Op op{"r50_op_ar_latent_grad"};
+    if (!ar || !phi || !dphi_hat || !dar || !loss_lat || !row_part) return op.refuse("null pointer");
+    if (b < 1 || t < 2 || (int64_t)b * t > INT32_MAX) return op.refuse("need b >= 1, t >= 2 (b*t within int range)");
+    if (d < 8 || d % 8) return op.refuse("d must be a positive multiple of 8");
+    if (et != 0 && et != 1) return op.refuse("et must be 0 (bf16) or 1 (fp16)");
+    if (int rc = op.aligned({{ar, "ar", 16}, {phi, "phi", 16}, {dphi_hat, "dphi_hat", 16}, {dar, "dar", 16}})) return rc;
     const long long rows = (long long)b * t;
     const double n_l = (double)b * (t - 1) * d;
     const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
-    R50_ET_LAUNCH(ar_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)ar, (const unsigned short*)phi,
+    R50_ET_LAUNCH(et, ar_latent_grad_kernel, dim3((unsigned)rows), dim3(128), 0, stream, (const unsigned short*)ar, (const unsigned short*)phi,
                   dphi_hat, t, d, coef, (unsigned short*)dar, row_part);
     hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, rows, 1.0 / n_l, loss_lat);
-    return ew_done("r50_op_ar_latent_grad");
+    return op.done();
 }
 
 int r50_op_hal_latent_grad(const void* h, const void* phi, const float* dh_reg, int64_t rows, int d, float lambda, float loss_scale,
                            void* dh, float* loss_lat, float* row_part, int et, void* stream) {
-    if (!h || !phi || !dh_reg || !dh || !loss_lat || !row_part)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: null pointer");
-    if (rows < 1 || rows > INT32_MAX) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: need 1 <= rows (within int range)");
-    if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: d must be a positive multiple of 8");
-    if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_hal_latent_grad: et must be 0 (bf16) or 1 (fp16)");
-    if (int rc_al = need_aligned(nullptr, "r50_op_hal_latent_grad", {{h, "h", 16}, {phi, "phi", 16}, {dh_reg, "dh_reg", 16}, {dh, "dh", 16}}))
-        return rc_al;
+    const Op op{"r50_op_hal_latent_grad"};
+    if (!h || !phi || !dh_reg || !dh || !loss_lat || !row_part) return op.refuse("null pointer");
+    if (rows < 1 || rows > INT32_MAX) return op.refuse("need 1 <= rows (within int range)");
+    if (d < 8 || d % 8) return op.refuse("d must be a positive multiple of 8");
+    if (et != 0 && et != 1) return op.refuse("et must be 0 (bf16) or 1 (fp16)");
+    if (int rc = op.aligned({{h, "h", 16}, {phi, "phi", 16}, {dh_reg, "dh_reg", 16}, {dh, "dh", 16}})) return rc;
     const double n_l = (double)rows * d;
     const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
-    R50_ET_LAUNCH(hal_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)h, (const unsigned short*)phi,
+    R50_ET_LAUNCH(et, hal_latent_grad_kernel, dim3((unsigned)rows), dim3(128), 0, stream, (const unsigned short*)h, (const unsigned short*)phi,
                   dh_reg, d, coef, (unsigned short*)dh, row_part);
     hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, (long long)rows, 1.0 / n_l, loss_lat);
-    return ew_done("r50_op_hal_latent_grad");
+    return op.done();
 }
 
 // ---- temporal smoothing and constant bone lengths (include/r50_smooth.h, smooth_kernels.h) ----
@@ -2661,55 +2642,59 @@ static const char* check_bone_edges(const int* edges, int E, int J, BoneEdges& e
 
 int r50_op_fir_sequences(const float* x, const int* seg_start, const int* row_seg, int64_t F, int G, int J, const double* coef, int W,
                          float* out, int* short_rows, void* stream) {
-    if (!x || !seg_start || !row_seg || !coef || !out || !short_rows) return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: null pointer");
+    const Op op{"r50_op_fir_sequences"};
+    if (!x || !seg_start || !row_seg || !coef || !out || !short_rows) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || G < 1 || G > F || J < 1 || J > SMOOTH_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: invalid arguments (need 1 <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
-    if (W < 1 || W > SMOOTH_MAX_W || W % 2 == 0) return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: W must be odd and in [1, 63]");
-    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_fir_sequences: out overlaps x");
+        return op.refuse("invalid arguments (need 1 <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (W < 1 || W > SMOOTH_MAX_W || W % 2 == 0) return op.refuse("W must be odd and in [1, 63]");
+    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return op.refuse("out overlaps x");
     hipLaunchKernelGGL(fir_sequences_kernel, dim3((unsigned)((F + FIR_ROWS - 1) / FIR_ROWS)), dim3(256), 0, (hipStream_t)stream, x, seg_start,
                        row_seg, (int)F, G, 3 * J, coef, W, out, short_rows);
-    return ew_done("r50_op_fir_sequences");
+    return op.done();
 }
 
 int r50_op_one_euro_sequences(const float* x, const int* seg_start, int64_t F, int G, int J, double rate, double min_cutoff, double beta,
                               double d_cutoff, float* out, void* stream) {
-    if (!x || !seg_start || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: null pointer");
+    const Op op{"r50_op_one_euro_sequences"};
+    if (!x || !seg_start || !out) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || G < 1 || G > F || J < 1 || J > SMOOTH_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: invalid arguments (need 1 <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
+        return op.refuse("invalid arguments (need 1 <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
     if (!(rate > 0.0 && min_cutoff > 0.0 && d_cutoff > 0.0 && beta >= 0.0) || !std::isfinite(rate) || !std::isfinite(min_cutoff) ||
         !std::isfinite(d_cutoff) || !std::isfinite(beta))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: need finite rate, min_cutoff, d_cutoff > 0 and beta >= 0");
-    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_one_euro_sequences: out overlaps x");
+        return op.refuse("need finite rate, min_cutoff, d_cutoff > 0 and beta >= 0");
+    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return op.refuse("out overlaps x");
     const int slabs = (3 * J + 63) / 64;
     hipLaunchKernelGGL(one_euro_sequences_kernel, dim3((unsigned)(((long long)G * slabs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x,
                        seg_start, G, 3 * J, slabs, rate, min_cutoff, beta, d_cutoff, out);
-    return ew_done("r50_op_one_euro_sequences");
+    return op.done();
 }
 
 int r50_op_bone_stats(const float* x, const int* seq_start, int64_t F, int S, int J, const int* edges, int E, double* stats, void* stream) {
-    if (!x || !seq_start || !edges || !stats) return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_stats: null pointer");
+    const Op op{"r50_op_bone_stats"};
+    if (!x || !seq_start || !edges || !stats) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 2 || J > SMOOTH_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_stats: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 2 <= J <= 64)");
+        return op.refuse("invalid arguments (need 1 <= S <= F < 2^31 / 192 and 2 <= J <= 64)");
     BoneEdges ed;
     unsigned long long is_child;
-    if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_bone_stats: edges: ") + why);
+    if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return op.refuse(std::string("edges: ") + why);
     hipLaunchKernelGGL(bone_stats_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, x, seq_start, 3 * J, ed, E, stats);
-    return ew_done("r50_op_bone_stats");
+    return op.done();
 }
 
 int r50_op_bone_rebuild(const float* x, const int* row_seq, int64_t F, int S, int J, const int* edges, int E, const double* stats, float* out,
                         void* stream) {
-    if (!x || !row_seq || !edges || !stats || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_rebuild: null pointer");
+    const Op op{"r50_op_bone_rebuild"};
+    if (!x || !row_seq || !edges || !stats || !out) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 2 || J > SMOOTH_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_rebuild: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 2 <= J <= 64)");
+        return op.refuse("invalid arguments (need 1 <= S <= F < 2^31 / 192 and 2 <= J <= 64)");
     BoneEdges ed;
     unsigned long long is_child;
-    if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_bone_rebuild: edges: ") + why);
-    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_bone_rebuild: out overlaps x");
+    if (const char* why = check_bone_edges(edges, E, J, ed, is_child)) return op.refuse(std::string("edges: ") + why);
+    if (overlaps(x, out, F * 3 * J * (long long)sizeof(float))) return op.refuse("out overlaps x");
     const int rb = bone_rebuild_rows(J);
     hipLaunchKernelGGL(bone_rebuild_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), bone_rebuild_lds(J), (hipStream_t)stream, x, row_seq,
                        (int)F, J, ed, E, is_child, stats, out);
-    return ew_done("r50_op_bone_rebuild");
+    return op.done();
 }
 
 // ---- joint rotations on a rigid skeleton (include/r50_kinematics.h, kinematics_kernels.h) ----
@@ -2778,98 +2763,92 @@ static bool kin_any_overlap(const KinRange* in, int n_in, const KinRange* out, i
 
 int r50_op_rest_offsets(const float* x, const int* seq_start, int64_t F, int S, int J, const int* edges, int E, const int* frames, int NF,
                         const double* rest_dirs, const double* sign, double* rest, void* stream) {
-    if (!x || !seq_start || !rest_dirs || !sign || !rest || (!edges && E > 0) || (!frames && NF > 0))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rest_offsets: null pointer");
+    const Op op{"r50_op_rest_offsets"};
+    if (!x || !seq_start || !rest_dirs || !sign || !rest || (!edges && E > 0) || (!frames && NF > 0)) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > KIN_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rest_offsets: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
+        return op.refuse("invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
     KinSkeleton sk;
-    if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk))
-        return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_rest_offsets: ") + why);
+    if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk)) return op.refuse(std::string("") + why);
     const KinRange in[2] = {{x, F * 3 * J * (long long)sizeof(float)}, {seq_start, ((long long)S + 1) * (long long)sizeof(int)}};
     const KinRange out[1] = {{rest, (long long)S * 3 * J * (long long)sizeof(double)}};
-    if (kin_any_overlap(in, 2, out, 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_rest_offsets: rest overlaps an input");
+    if (kin_any_overlap(in, 2, out, 1)) return op.refuse("rest overlaps an input");
     hipLaunchKernelGGL(rest_offsets_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, x, seq_start, J, sk, rest);
-    return ew_done("r50_op_rest_offsets");
+    return op.done();
 }
 
 int r50_op_pose_rotations(const float* x, const int* row_seq, int64_t F, int S, int J, const int* edges, int E, const int* frames, int NF,
                           const double* rest_dirs, const double* sign, const double* rest, float* quat, float* euler, float* rigid,
                           float* resid, int* flags, void* stream) {
+    const Op op{"r50_op_pose_rotations"};
     if (!x || !row_seq || !rest_dirs || !sign || !rest || !quat || !euler || !rigid || !resid || !flags || (!edges && E > 0) ||
         (!frames && NF > 0))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: null pointer");
+        return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > KIN_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
+        return op.refuse("invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
     KinSkeleton sk;
-    if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk))
-        return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_rotations: ") + why);
-    if (int rc_al = need_aligned(nullptr, "r50_op_pose_rotations", {{quat, "quat", 16}})) return rc_al;
+    if (const char* why = check_kin_skeleton(J, edges, E, frames, NF, rest_dirs, sign, sk)) return op.refuse(std::string("") + why);
+    if (int rc = op.aligned({{quat, "quat", 16}})) return rc;
     const long long fj = F * J * (long long)sizeof(float);
     const KinRange in[3] = {{x, 3 * fj}, {row_seq, F * (long long)sizeof(int)}, {rest, (long long)S * 3 * J * (long long)sizeof(double)}};
     const KinRange out[5] = {{quat, 4 * fj}, {euler, 3 * fj}, {rigid, 3 * fj}, {resid, F * (long long)sizeof(float)},
                              {flags, F * (long long)sizeof(int)}};
-    if (kin_any_overlap(in, 3, out, 5)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: an output overlaps an input or another output");
+    if (kin_any_overlap(in, 3, out, 5)) return op.refuse("an output overlaps an input or another output");
     const size_t lds = pose_rot_lds(J);
-    if (lds > 65536) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_rotations: the LDS budget does not hold");
+    if (lds > 65536) return op.refuse("the LDS budget does not hold");
     const int rb = pose_rot_rows(J);
     hipLaunchKernelGGL(pose_rotations_kernel, dim3((unsigned)((F + rb - 1) / rb)), dim3(64), lds, (hipStream_t)stream, x, row_seq, (int)F, J,
                        sk, rest, quat, euler, rigid, resid, flags);
-    return ew_done("r50_op_pose_rotations");
+    return op.done();
 }
 
 // ---- a pose at any time stamp (include/r50_resample.h, resample_kernels.h, INTEGRATION.md section AB) ----
 int r50_op_resample_sequences(const float* x, const int* idx, const int* seq_start, int64_t F, int S, int J, const double* out_time,
                               const int* out_seq, const int* out_left, int64_t G, int kind, int max_gap, float* y, int* flags,
                               void* stream) {
-    if (!x || !idx || !seq_start || !out_time || !out_seq || !out_left || !y || !flags)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: null pointer");
+    const Op op{"r50_op_resample_sequences"};
+    if (!x || !idx || !seq_start || !out_time || !out_seq || !out_left || !y || !flags) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || G < 1 || G > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > RESAMPLE_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID,
-                    "r50_op_resample_sequences: invalid arguments (need 1 <= S <= F < 2^31 / 192, 1 <= G < 2^31 / 192 and 1 <= J <= 64)");
-    if (kind != R50_RESAMPLE_LINEAR && kind != R50_RESAMPLE_CUBIC)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: kind must be 0 (linear) or 1 (cubic)");
-    if (max_gap < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: max_gap must be >= 1");
-    if ((uintptr_t)out_time & 7u) return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: out_time must be 8-byte aligned");
+        return op.refuse("invalid arguments (need 1 <= S <= F < 2^31 / 192, 1 <= G < 2^31 / 192 and 1 <= J <= 64)");
+    if (kind != R50_RESAMPLE_LINEAR && kind != R50_RESAMPLE_CUBIC) return op.refuse("kind must be 0 (linear) or 1 (cubic)");
+    if (max_gap < 1) return op.refuse("max_gap must be >= 1");
+    if ((uintptr_t)out_time & 7u) return op.refuse("out_time must be 8-byte aligned");
     const long long row = 3 * J * (long long)sizeof(float), word = (long long)sizeof(int);
     const KinRange in[6] = {{x, F * row}, {idx, F * word}, {seq_start, ((long long)S + 1) * word}, {out_time, G * (long long)sizeof(double)},
                             {out_seq, G * word}, {out_left, G * word}};
     const KinRange out[2] = {{y, G * row}, {flags, G * word}};
-    if (kin_any_overlap(in, 6, out, 2))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_resample_sequences: y or flags overlaps an input or the other output");
+    if (kin_any_overlap(in, 6, out, 2)) return op.refuse("y or flags overlaps an input or the other output");
     const long long total = G * 3 * J;
     hipLaunchKernelGGL(resample_sequences_kernel, dim3((unsigned)((total + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK)), dim3(RESAMPLE_BLOCK), 0,
                        (hipStream_t)stream, x, idx, seq_start, 3 * J, out_time, out_seq, out_left, (int)G, kind, max_gap, y, flags);
-    return ew_done("r50_op_resample_sequences");
+    return op.done();
 }
 
 // ---- stratified cluster bootstrap of per-unit sums (include/r50_bootstrap.h, bootstrap_kernels.h, INTEGRATION.md section AC) ----
 int r50_op_bootstrap_sums(const double* v, const int* stratum_start, int64_t U, int G, int M, int64_t r0, int64_t R, uint64_t seed,
                           int window, double* out, int* counts, void* stream) {
-    if (!v || !stratum_start || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: null pointer");
+    const Op op{"r50_op_bootstrap_sums"};
+    if (!v || !stratum_start || !out) return op.refuse("null pointer");
     if (U < 1 || G < 1 || M < 1 || R < 1 || G > U || U > R50_BOOTSTRAP_MAX_UNITS || M > R50_BOOTSTRAP_MAX_COLUMNS)
-        return fail(nullptr, R50_ERR_INVALID,
-                    "r50_op_bootstrap_sums: invalid arguments (need 1 <= G <= U <= 2^24, 1 <= M <= 4096 and R >= 1)");
-    if (r0 < 0 || r0 > INT64_MAX - R) return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: need r0 >= 0 and r0 + R within int64");
+        return op.refuse("invalid arguments (need 1 <= G <= U <= 2^24, 1 <= M <= 4096 and R >= 1)");
+    if (r0 < 0 || r0 > INT64_MAX - R) return op.refuse("need r0 >= 0 and r0 + R within int64");
     const long long limit = 1ll << 40;
     if (R >= limit || R > (limit - 1) / ((long long)G * M) || R > (limit - 1) / U)   // by division: the products may overflow
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: R * G * M and R * U must stay below 2^40");
-    if (window < 1 || window > R50_BOOTSTRAP_MAX_WINDOW)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: window must lie in [1, 32768]");
+        return op.refuse("R * G * M and R * U must stay below 2^40");
+    if (window < 1 || window > R50_BOOTSTRAP_MAX_WINDOW) return op.refuse("window must lie in [1, 32768]");
     if (((uintptr_t)v & 7u) || ((uintptr_t)out & 7u) || ((uintptr_t)counts & 3u))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: v and out must be 8-byte aligned (counts 4-byte)");
+        return op.refuse("v and out must be 8-byte aligned (counts 4-byte)");
     const KinRange in[2] = {{v, U * M * (long long)sizeof(double)}, {stratum_start, ((long long)G + 1) * (long long)sizeof(int)}};
     const KinRange outs[2] = {{out, R * G * M * (long long)sizeof(double)}, {counts, R * U * (long long)sizeof(int)}};
-    if (kin_any_overlap(in, 2, outs, counts ? 2 : 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: out or counts overlaps an input or the other output");
+    if (kin_any_overlap(in, 2, outs, counts ? 2 : 1)) return op.refuse("out or counts overlaps an input or the other output");
     const long long grid_z = (R + BOOT_GRID_Y - 1) / BOOT_GRID_Y;
-    if (grid_z > 65535) return fail(nullptr, R50_ERR_INVALID, "r50_op_bootstrap_sums: R exceeds the launch grid (65535 * 65535 replicates)");
+    if (grid_z > 65535) return op.refuse("R exceeds the launch grid (65535 * 65535 replicates)");
     const size_t lds = sizeof(int) * (size_t)std::min<long long>(window, U);
     hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(bootstrap_sums_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ea != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string("r50_op_bootstrap_sums: ") + hipGetErrorString(ea));
+    if (ea != hipSuccess) return op.done(ea);
     hipLaunchKernelGGL(bootstrap_sums_kernel, dim3((unsigned)G, (unsigned)std::min<long long>(R, BOOT_GRID_Y), (unsigned)grid_z), dim3(BOOT_BLOCK),
                        lds, (hipStream_t)stream, v, stratum_start, (long long)U, G, M, (long long)r0, (long long)R, (uint32_t)seed,
                        (uint32_t)(seed >> 32), window, out, counts);
-    return ew_done("r50_op_bootstrap_sums");
+    return op.done();
 }
 
 // ---- 2D-guided refinement of stitched sequences (include/r50_refine.h, refine_kernels.h) ----
@@ -2886,36 +2865,31 @@ int r50_op_pose_fit_sweeps(const float* x0, const float* rays, const float* conf
                            int64_t F, int G, int S, int J, const int* edges, int E, const double* bone_len, double lambda_2d, double lambda_3d,
                            double lambda_acc, double lambda_bone, double omega, double z_min, int iters, double* workspace, float* out,
                            void* stream) {
-    if (!x0 || !rays || !seg_start || !row_seg || !row_seq || !workspace || !out)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: null pointer");
+    const Op op{"r50_op_pose_fit_sweeps"};
+    if (!x0 || !rays || !seg_start || !row_seg || !row_seq || !workspace || !out) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || G < 1 || G > F || S < 1 || S > G || J < 1 || J > FIT_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID,
-                    "r50_op_pose_fit_sweeps: invalid arguments (need 1 <= S <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
-    if (!(std::isfinite(lambda_3d) && lambda_3d > 0.0))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: lambda_3d must be finite and > 0 (it keeps H positive definite)");
+        return op.refuse("invalid arguments (need 1 <= S <= G <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (!(std::isfinite(lambda_3d) && lambda_3d > 0.0)) return op.refuse("lambda_3d must be finite and > 0 (it keeps H positive definite)");
     if (!(std::isfinite(lambda_2d) && lambda_2d >= 0.0 && std::isfinite(lambda_acc) && lambda_acc >= 0.0 && std::isfinite(lambda_bone) &&
           lambda_bone >= 0.0))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: lambda_2d, lambda_acc and lambda_bone must be finite and >= 0");
-    if (!(omega > 0.0 && omega <= 0.75)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: need 0 < omega <= 0.75");
-    if (!(std::isfinite(z_min) && z_min > 0.0)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: z_min must be finite and > 0");
-    if (iters < 0 || iters > 1000) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: need 0 <= iters <= 1000");
-    if (E < 0) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: edges: need E >= 0");
+        return op.refuse("lambda_2d, lambda_acc and lambda_bone must be finite and >= 0");
+    if (!(omega > 0.0 && omega <= 0.75)) return op.refuse("need 0 < omega <= 0.75");
+    if (!(std::isfinite(z_min) && z_min > 0.0)) return op.refuse("z_min must be finite and > 0");
+    if (iters < 0 || iters > 1000) return op.refuse("need 0 <= iters <= 1000");
+    if (E < 0) return op.refuse("edges: need E >= 0");
     BoneEdges ed;
-    if (const char* why = check_fit_edges(edges, E, J, ed)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_fit_sweeps: edges: ") + why);
-    if (lambda_bone != 0.0 && (E < 1 || !bone_len))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: lambda_bone != 0 needs edges and bone_len");
+    if (const char* why = check_fit_edges(edges, E, J, ed)) return op.refuse(std::string("edges: ") + why);
+    if (lambda_bone != 0.0 && (E < 1 || !bone_len)) return op.refuse("lambda_bone != 0 needs edges and bone_len");
     const long long fj = F * J * (long long)sizeof(float);
     const KinRange in[4] = {{x0, 3 * fj}, {rays, 2 * fj}, {conf ? (const void*)conf : (const void*)x0, conf ? fj : 0},
                             {bone_len && lambda_bone != 0.0 ? (const void*)bone_len : (const void*)x0,
                              bone_len && lambda_bone != 0.0 ? (long long)S * E * (long long)sizeof(double) : 0}};
     const KinRange outs[2] = {{workspace, 2 * F * 3 * J * (long long)sizeof(double)}, {out, 3 * fj}};
-    if (kin_any_overlap(in, 4, outs, 2))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: out or workspace overlaps an input, or each other");
-    if (pose_fit_lds(J) > 65536) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_sweeps: the LDS budget does not hold");
+    if (kin_any_overlap(in, 4, outs, 2)) return op.refuse("out or workspace overlaps an input, or each other");
+    if (pose_fit_lds(J) > 65536) return op.refuse("the LDS budget does not hold");
     hipStream_t st = (hipStream_t)stream;
     if (iters == 0) {
-        hipError_t e = hipMemcpyAsync(out, x0, (size_t)(3 * fj), hipMemcpyDeviceToDevice, st);
-        return e == hipSuccess ? R50_OK : fail(nullptr, R50_ERR_HIP, std::string("r50_op_pose_fit_sweeps: ") + hipGetErrorString(e));
+        return op.done(hipMemcpyAsync(out, x0, (size_t)(3 * fj), hipMemcpyDeviceToDevice, st));
     }
     FitAdjacency adj;
     std::memset(&adj, 0, sizeof(adj));
@@ -2942,133 +2916,138 @@ int r50_op_pose_fit_sweeps(const float* x0, const float* rays, const float* conf
         else if (lastk) launch_fit_sweep<false, true>(x0, src, rays, conf, seg_start, row_seg, row_seq, f, J, adj, E, bone_len, pr, dst, out, st);
         else launch_fit_sweep<false, false>(x0, src, rays, conf, seg_start, row_seg, row_seq, f, J, adj, E, bone_len, pr, dst, out, st);
     }
-    return ew_done("r50_op_pose_fit_sweeps");
+    return op.done();
 }
 
 int r50_op_pose_fit_energy(const float* x, const float* x0, const float* rays, const float* conf, const int* seq_start, const int* row_seg,
                            int64_t F, int S, int J, const int* edges, int E, const double* bone_len, double z_min, double* energy,
                            void* stream) {
-    if (!x || !x0 || !rays || !seq_start || !row_seg || !energy) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: null pointer");
+    const Op op{"r50_op_pose_fit_energy"};
+    if (!x || !x0 || !rays || !seq_start || !row_seg || !energy) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || S < 1 || S > F || J < 1 || J > FIT_MAX_J)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
-    if (!(std::isfinite(z_min) && z_min > 0.0)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: z_min must be finite and > 0");
-    if (E < 0) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: edges: need E >= 0");
+        return op.refuse("invalid arguments (need 1 <= S <= F < 2^31 / 192 and 1 <= J <= 64)");
+    if (!(std::isfinite(z_min) && z_min > 0.0)) return op.refuse("z_min must be finite and > 0");
+    if (E < 0) return op.refuse("edges: need E >= 0");
     BoneEdges ed;
-    if (const char* why = check_fit_edges(edges, E, J, ed)) return fail(nullptr, R50_ERR_INVALID, std::string("r50_op_pose_fit_energy: edges: ") + why);
-    if (bone_len && E < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: bone_len needs edges");
+    if (const char* why = check_fit_edges(edges, E, J, ed)) return op.refuse(std::string("edges: ") + why);
+    if (bone_len && E < 1) return op.refuse("bone_len needs edges");
     const long long fj = F * J * (long long)sizeof(float);
     const KinRange in[2] = {{x, 3 * fj}, {x0, 3 * fj}};
     const KinRange outs[1] = {{energy, (long long)S * FIT_ENERGY_SLOTS * (long long)sizeof(double)}};
-    if (kin_any_overlap(in, 2, outs, 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_pose_fit_energy: energy overlaps an input");
+    if (kin_any_overlap(in, 2, outs, 1)) return op.refuse("energy overlaps an input");
     hipLaunchKernelGGL(pose_fit_energy_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, x, x0, rays, conf, seq_start, row_seg, J, ed,
                        E, bone_len, z_min, energy);
-    return ew_done("r50_op_pose_fit_energy");
+    return op.done();
 }
 
 // ---- the cameras of a take in one frame of reference, fused (include/r50_multiview.h, multiview_kernels.h) ----
 int r50_op_view_rigid_fit(const float* y, const float* x, int64_t rows_y, int64_t rows_x, int J, const int* pair_start, const int* match,
                           int P, double* fit, void* stream) {
-    if (!y || !x || !pair_start || !match || !fit) return fail(nullptr, R50_ERR_INVALID, "r50_op_view_rigid_fit: null pointer");
+    const Op op{"r50_op_view_rigid_fit"};
+    if (!y || !x || !pair_start || !match || !fit) return op.refuse("null pointer");
     if (rows_y < 1 || rows_y > kSmoothMaxRows || rows_x < 1 || rows_x > kSmoothMaxRows || J < 1 || J > VIEW_MAX_J || P < 1)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_view_rigid_fit: invalid arguments (need 1 <= rows_y, rows_x < 2^31 / 192, 1 <= J <= 64 and P >= 1)");
+        return op.refuse("invalid arguments (need 1 <= rows_y, rows_x < 2^31 / 192, 1 <= J <= 64 and P >= 1)");
     hipLaunchKernelGGL(view_rigid_fit_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, y, x, J, pair_start, match, fit);
-    return ew_done("r50_op_view_rigid_fit");
+    return op.done();
 }
 
 int r50_op_view_fuse(const float* pose, int64_t F, int J, const int* peer_start, const int* peer_row, const int* peer_fit, const double* fit,
                      int P, int mode, float* fused, float* disagreement, void* stream) {
-    if (!pose || !peer_start || !peer_row || !peer_fit || !fit || !fused || !disagreement)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: null pointer");
+    const Op op{"r50_op_view_fuse"};
+    if (!pose || !peer_start || !peer_row || !peer_fit || !fit || !fused || !disagreement) return op.refuse("null pointer");
     if (F < 1 || F > kSmoothMaxRows || J < 1 || J > VIEW_MAX_J || P < 0)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: invalid arguments (need 1 <= F < 2^31 / 192, 1 <= J <= 64 and P >= 0)");
-    if (mode < 0 || mode > 2) return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: mode must be 0 (mean), 1 (median) or 2 (others)");
-    if (overlaps(pose, fused, F * 3 * J * (long long)sizeof(float))) return fail(nullptr, R50_ERR_INVALID, "r50_op_view_fuse: fused overlaps pose");
+        return op.refuse("invalid arguments (need 1 <= F < 2^31 / 192, 1 <= J <= 64 and P >= 0)");
+    if (mode < 0 || mode > 2) return op.refuse("mode must be 0 (mean), 1 (median) or 2 (others)");
+    if (overlaps(pose, fused, F * 3 * J * (long long)sizeof(float))) return op.refuse("fused overlaps pose");
     hipLaunchKernelGGL(view_fuse_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pose, (int)F, J, peer_start,
                        peer_row, peer_fit, fit, mode, fused, disagreement);
-    return ew_done("r50_op_view_fuse");
+    return op.done();
 }
 
 int r50_op_gn_relu_causal3_bwd(const void* dr, const void* x, int b, int t, int c, int groups, const float* gamma, const float* beta,
                                float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3_bwd", {{dr, "dr", 2}, {x, "x", 2}, {add, "add", 2}, {dx, "dx", 2}})) return rc_al;
+    const Op op{"r50_op_gn_relu_causal3_bwd"};
+    if (int rc = op.aligned({{dr, "dr", 2}, {x, "x", 2}, {add, "add", 2}, {dx, "dx", 2}})) return rc;
     if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part || b < 1 || t < 1 || c < 1 || groups < 1 || c % groups ||
         c / groups > 256 || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_bwd: invalid arguments");
-    R50_ET_LAUNCH(gn_relu_causal3_bwd_kernel, dim3((unsigned)(b * groups)), dim3(256), stream, (const unsigned short*)dr,
+        return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, gn_relu_causal3_bwd_kernel, dim3((unsigned)(b * groups)), dim3(256), 0, stream, (const unsigned short*)dr,
                   (const unsigned short*)x, gamma, beta, (const unsigned short*)add, (unsigned short*)dx, dgamma_part, dbeta_part, t, c,
                   groups, eps);
-    return ew_done("r50_op_gn_relu_causal3_bwd");
+    return op.done();
 }
 
 int r50_op_gn_relu_causal3_tm_bwd(const void* dr, const void* x, int b, int t, int t0, int c, int groups, const float* gamma,
                                   const float* beta, float eps, const void* add, void* dx, float* dgamma_part, float* dbeta_part, int et,
                                   void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_gn_relu_causal3_tm_bwd", {{dr, "dr", 2}, {x, "x", 2},
-                                                 {add, "add", 2}, {dx, "dx", 2}}))
-        return rc_al;
-    if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_gn_relu_causal3_tm_bwd: null pointer");
+    const Op op{"r50_op_gn_relu_causal3_tm_bwd"};
+    if (int rc = op.aligned({{dr, "dr", 2}, {x, "x", 2},
+                             {add, "add", 2}, {dx, "dx", 2}}))
+        return rc;
+    if (!dr || !x || !gamma || !beta || !dx || !dgamma_part || !dbeta_part) return op.refuse("null pointer");
     if (b < 1 || t < 1 || t0 < 0 || t0 >= t || c < 1 || groups < 1 || c % groups || c / groups > 256 || (et != 0 && et != 1) ||
         (int64_t)b * groups > INT32_MAX || (int64_t)t * (c / groups) > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID,
-                    "r50_op_gn_relu_causal3_tm_bwd: invalid arguments (need b, t >= 1, 0 <= t0 < t, c % groups == 0, c / groups <= 256, et 0 or 1)");
-    R50_ET_LAUNCH(gn_relu_causal3_tm_bwd_kernel, dim3((unsigned)(b * groups)), dim3(256), stream, (const unsigned short*)dr,
+        return op.refuse("invalid arguments (need b, t >= 1, 0 <= t0 < t, c % groups == 0, c / groups <= 256, et 0 or 1)");
+    R50_ET_LAUNCH(et, gn_relu_causal3_tm_bwd_kernel, dim3((unsigned)(b * groups)), dim3(256), 0, stream, (const unsigned short*)dr,
                   (const unsigned short*)x, gamma, beta, (const unsigned short*)add, (unsigned short*)dx, dgamma_part, dbeta_part, b, t, t0,
                   c, groups, eps);
-    return ew_done("r50_op_gn_relu_causal3_tm_bwd");
+    return op.done();
 }
 
 int r50_op_rollout_pose_loss_grad(const float* pred, const float* gt, int b, int k, int t_gt, int i0, int joints, float loss_scale,
                                   float* dy, float* loss2, void* stream) {
-    if (!pred || !gt || !dy || !loss2)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_pose_loss_grad: null pointer");
+    const Op op{"r50_op_rollout_pose_loss_grad"};
+    if (!pred || !gt || !dy || !loss2) return op.refuse("null pointer");
     if (b < 1 || k < 1 || joints < 1 || i0 < 0 || (int64_t)i0 + k > t_gt || (int64_t)b * t_gt > INT32_MAX ||
         (int64_t)k * b * joints > INT64_MAX / 3)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_pose_loss_grad: invalid arguments (need b, k, joints >= 1 and 0 <= i0, i0 + k <= t_gt)");
+        return op.refuse("invalid arguments (need b, k, joints >= 1 and 0 <= i0, i0 + k <= t_gt)");
     hipLaunchKernelGGL(rollout_pose_loss_grad_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, b, k, t_gt, i0, joints,
                        loss_scale, dy, loss2);
-    return ew_done("r50_op_rollout_pose_loss_grad");
+    return op.done();
 }
 
 int r50_op_rollout_latent_grad(const void* fut, const void* phi, int b, int k, int t_phi, int i0, int d, float lambda, float loss_scale,
                                float* dfut, float* loss_lat, float* row_part, int et, void* stream) {
-    if (!fut || !phi || !dfut || !loss_lat || !row_part)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: null pointer");
+    const Op op{"r50_op_rollout_latent_grad"};
+    if (!fut || !phi || !dfut || !loss_lat || !row_part) return op.refuse("null pointer");
     if (b < 1 || k < 1 || i0 < 0 || (int64_t)i0 + k > t_phi || (int64_t)b * k > INT32_MAX || (int64_t)b * t_phi > INT32_MAX)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: need b, k >= 1 and 0 <= i0, i0 + k <= t_phi");
-    if (d < 8 || d % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: d must be a positive multiple of 8");
-    if (et != 0 && et != 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_rollout_latent_grad: et must be 0 (bf16) or 1 (fp16)");
-    if (int rc_al = need_aligned(nullptr, "r50_op_rollout_latent_grad", {{fut, "fut", 16}, {phi, "phi", 16}, {dfut, "dfut", 16}})) return rc_al;
+        return op.refuse("need b, k >= 1 and 0 <= i0, i0 + k <= t_phi");
+    if (d < 8 || d % 8) return op.refuse("d must be a positive multiple of 8");
+    if (et != 0 && et != 1) return op.refuse("et must be 0 (bf16) or 1 (fp16)");
+    if (int rc = op.aligned({{fut, "fut", 16}, {phi, "phi", 16}, {dfut, "dfut", 16}})) return rc;
     const long long rows = (long long)b * k;
     const double n_l = (double)rows * d;
     const float coef = (float)((double)lambda * 2.0 / n_l * (double)loss_scale);
-    R50_ET_LAUNCH(rollout_latent_grad_kernel, dim3((unsigned)rows), dim3(128), stream, (const unsigned short*)fut, (const unsigned short*)phi,
+    R50_ET_LAUNCH(et, rollout_latent_grad_kernel, dim3((unsigned)rows), dim3(128), 0, stream, (const unsigned short*)fut, (const unsigned short*)phi,
                   b, t_phi, i0, d, coef, dfut, row_part);
     hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_part, rows, 1.0 / n_l, loss_lat);
-    return ew_done("r50_op_rollout_latent_grad");
+    return op.done();
 }
 
 int r50_op_check_finite(const float* g, int64_t n, int* found, void* stream) {
-    if (!g || !found || n < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_check_finite: invalid arguments");
+    const Op op{"r50_op_check_finite"};
+    if (!g || !found || n < 1) return op.refuse("invalid arguments");
     hipLaunchKernelGGL(check_finite_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, g, (long long)n, found);
-    return ew_done("r50_op_check_finite");
+    return op.done();
 }
 
 int r50_op_check_overflow16(const void* x, int64_t n, int* found, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_check_overflow16", {{x, "x", 2}})) return rc_al;
-    if (!x || !found || n < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_check_overflow16: invalid arguments");
-    R50_ET_LAUNCH(check_overflow16_kernel, dim3(ew_grid(n)), dim3(256), stream, (const unsigned short*)x, (long long)n, found);
-    return ew_done("r50_op_check_overflow16");
+    const Op op{"r50_op_check_overflow16"};
+    if (int rc = op.aligned({{x, "x", 2}})) return rc;
+    if (!x || !found || n < 1 || (et != 0 && et != 1)) return op.refuse("invalid arguments");
+    R50_ET_LAUNCH(et, check_overflow16_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, (const unsigned short*)x, (long long)n, found);
+    return op.done();
 }
 
 int r50_op_adamw(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, const int* found_inf, int et, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_adamw", {{p16, "p16", 2}})) return rc_al;
-    if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1)) return fail(nullptr, R50_ERR_INVALID, "r50_op_adamw: invalid arguments");
+    const Op op{"r50_op_adamw"};
+    if (int rc = op.aligned({{p16, "p16", 2}})) return rc;
+    if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1)) return op.refuse("invalid arguments");
     const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
-    R50_ET_LAUNCH(adamw_kernel, dim3(ew_grid(n)), dim3(256), stream, p, m, v, g, (unsigned short*)p16, (long long)n, lr, beta1, beta2, eps,
+    R50_ET_LAUNCH(et, adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, p, m, v, g, (unsigned short*)p16, (long long)n, lr, beta1, beta2, eps,
                   weight_decay, (float)bc1, (float)std::sqrt(bc2), found_inf);
-    return ew_done("r50_op_adamw");
+    return op.done();
 }
 
 // The schedule of grad_norm_part_kernel, from n alone: W = min(ceil(n / GRAD_NORM_GRANULE), GRAD_NORM_MAX_WG) workgroups, each a
@@ -3079,74 +3058,71 @@ static int grad_norm_workgroups(long long n) {
 
 int r50_op_grad_norm(const float* g, int64_t n, float max_norm, double* part, int n_part, int* found, float* clip2, double* stats4,
                      void* stream) {
-    if (!g || !part || !found || !clip2 || !stats4) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: null pointer");
-    if (n < 1 || n > (1ll << 40)) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: need 1 <= n <= 2^40");
-    if (max_norm != max_norm) return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: max_norm is nan");
+    const Op op{"r50_op_grad_norm"};
+    if (!g || !part || !found || !clip2 || !stats4) return op.refuse("null pointer");
+    if (n < 1 || n > (1ll << 40)) return op.refuse("need 1 <= n <= 2^40");
+    if (max_norm != max_norm) return op.refuse("max_norm is nan");
     const int w = grad_norm_workgroups(n);
     if (n_part < w)
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_grad_norm: part holds " + std::to_string(n_part) + " doubles, n = " + std::to_string(n) +
-                                                  " needs " + std::to_string(w));
-    if (int rc_al = need_aligned(nullptr, "r50_op_grad_norm", {{g, "g", 16}})) return rc_al;
+        return op.refuse("part holds " + std::to_string(n_part) + " doubles, n = " + std::to_string(n) + " needs " + std::to_string(w));
+    if (int rc = op.aligned({{g, "g", 16}})) return rc;
     const long long slice = (((long long)n + w - 1) / w + 3) / 4 * 4;
     hipLaunchKernelGGL(grad_norm_part_kernel, dim3(w), dim3(256), 0, (hipStream_t)stream, g, (long long)n, slice, part);
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)part, w, max_norm, found, clip2,
                        stats4);
-    return ew_done("r50_op_grad_norm");
+    return op.done();
 }
 
 int r50_op_adamw_clip_ema(float* p, float* m, float* v, const float* g, void* p16, int64_t n, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, const int* found_inf, const float* clip, float* ema, float ema_weight, int et,
                           void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_adamw_clip_ema", {{p16, "p16", 2}})) return rc_al;
-    if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_adamw_clip_ema: invalid arguments");
+    const Op op{"r50_op_adamw_clip_ema"};
+    if (int rc = op.aligned({{p16, "p16", 2}})) return rc;
+    if (!p || !m || !v || !g || !p16 || n < 1 || step < 1 || (et != 0 && et != 1)) return op.refuse("invalid arguments");
     const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
-    R50_ET_LAUNCH(adamw_clip_ema_kernel, dim3(ew_grid(n)), dim3(256), stream, p, m, v, g, (unsigned short*)p16, (long long)n, lr, beta1, beta2,
+    R50_ET_LAUNCH(et, adamw_clip_ema_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, p, m, v, g, (unsigned short*)p16, (long long)n, lr, beta1, beta2,
                   eps, weight_decay, (float)bc1, (float)std::sqrt(bc2), found_inf, clip, ema, ema_weight);
-    return ew_done("r50_op_adamw_clip_ema");
+    return op.done();
 }
 
 int64_t r50_stem_scratch_bytes(int n) { return (int64_t)STEM_W_BYTES + (int64_t)n * STEM_HP * STEM_WP * 8; }
 
 int r50_op_stem(const float* x, int n, const float* w_host, const float* bias_dev, void* scratch, void* y, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_stem", {{bias_dev, "bias_f32_dev", 16}, {scratch, "scratch_dev", 16},
-                                                 {y, "y_nhwc_bf16", 16}}))
-        return rc_al;
-    if (!x || !w_host || !bias_dev || !scratch || !y || n < 1) return fail(nullptr, R50_ERR_INVALID, "r50_op_stem: invalid arguments");
+    const Op op{"r50_op_stem"};
+    if (int rc = op.aligned({{bias_dev, "bias_f32_dev", 16}, {scratch, "scratch_dev", 16},
+                             {y, "y_nhwc_bf16", 16}}))
+        return rc;
+    if (!x || !w_host || !bias_dev || !scratch || !y || n < 1) return op.refuse("invalid arguments");
     // stem_conv_kernel runs one workgroup per (image, 4 output rows): the grid is an int (every offset inside both kernels is 64-bit)
-    if (size_over("workgroups n*28", (long long)n * (112 / STEM_ROWS_PER_WG), k2p31, "2^31")) return fail(nullptr, R50_ERR_INVALID, "r50_op_stem: " + size_why());
+    if (Launch r; size_over(r, "workgroups n*28", (long long)n * (112 / STEM_ROWS_PER_WG), k2p31, "2^31")) return op.done(r);
     std::vector<uint16_t> pk;
     const int et = op_et();
     pack_stem(w_host, pk, et == 1 ? 2 : 0);
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(nullptr, hipMemcpyAsync(scratch, pk.data(), STEM_W_BYTES, hipMemcpyHostToDevice, s));
-    HIP_TRY(nullptr, hipStreamSynchronize(s));   // pk is a host temporary
+    if (hipError_t e = hipMemcpyAsync(scratch, pk.data(), STEM_W_BYTES, hipMemcpyHostToDevice, s)) return op.done(e);
+    if (hipError_t e = hipStreamSynchronize(s)) return op.done(e);   // pk is a host temporary
     char* xp = (char*)scratch + STEM_W_BYTES;
-    HIP_TRY(nullptr, launch_stem_pack(x, xp, n, s, et));
-    HIP_TRY(nullptr, launch_stem_conv(xp, scratch, bias_dev, y, n, s, et));
-    return R50_OK;
+    if (int rc = op.done(launch_stem_pack(x, xp, n, s, et))) return rc;
+    return op.done(launch_stem_conv(xp, scratch, bias_dev, y, n, s, et));
 }
 
 int r50_op_maxpool(const void* x, int n, int h, int w, int c, void* y, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_maxpool", {{x, "x_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}})) return rc_al;
-    if (!x || !y || n < 1 || h < 1 || w < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_maxpool: invalid arguments");
+    const Op op{"r50_op_maxpool"};
+    if (int rc = op.aligned({{x, "x_nhwc_bf16", 16}, {y, "y_nhwc_bf16", 16}})) return rc;
+    if (!x || !y || n < 1 || h < 1 || w < 1 || c < 8 || c % 8) return op.refuse("invalid arguments");
     // maxpool3x3s2_kernel counts and addresses in 64 bits (a grid-stride loop over at most 2^14 workgroups): the limit is the byte offset itself
-    if ((__int128)n * h * w * c * 2 >= ((__int128)1 << 63))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_maxpool: x bytes, n*h*w*c*2, must be < 2^63");
-    HIP_TRY(nullptr, launch_maxpool(x, y, n, h, w, c, (hipStream_t)stream, op_et()));
-    return R50_OK;
+    if ((__int128)n * h * w * c * 2 >= ((__int128)1 << 63)) return op.refuse("x bytes, n*h*w*c*2, must be < 2^63");
+    return op.done(launch_maxpool(x, y, n, h, w, c, (hipStream_t)stream, op_et()));
 }
 
 int r50_op_avgpool(const void* x, int n, int hw, int c, float* y, void* stream) {
-    if (int rc_al = need_aligned(nullptr, "r50_op_avgpool", {{x, "x_nhwc_bf16", 16}, {y, "y_f32", 16}})) return rc_al;
-    if (!x || !y || n < 1 || hw < 1 || c < 8 || c % 8) return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: invalid arguments");
+    const Op op{"r50_op_avgpool"};
+    if (int rc = op.aligned({{x, "x_nhwc_bf16", 16}, {y, "y_f32", 16}})) return rc;
+    if (!x || !y || n < 1 || hw < 1 || c < 8 || c % 8) return op.refuse("invalid arguments");
     // avgpool_kernel: one thread per (image, 8 channels), numbered in an int over a grid rounded up to 256 threads; the row offsets are 64-bit
-    if (size_over("threads n*(c/8) + 255", (long long)n * (c / 8) + 255, k2p31, "2^31"))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: " + size_why());
-    if ((__int128)n * hw * c * 2 >= ((__int128)1 << 63))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_avgpool: x bytes, n*hw*c*2, must be < 2^63");
-    HIP_TRY(nullptr, launch_avgpool(x, y, n, hw, c, (hipStream_t)stream, op_et()));
-    return R50_OK;
+    if (Launch r; size_over(r, "threads n*(c/8) + 255", (long long)n * (c / 8) + 255, k2p31, "2^31")) return op.done(r);
+    if ((__int128)n * hw * c * 2 >= ((__int128)1 << 63)) return op.refuse("x bytes, n*hw*c*2, must be < 2^63");
+    return op.done(launch_avgpool(x, y, n, hw, c, (hipStream_t)stream, op_et()));
 }
 
 // ---- forecast baselines (kernels.h: row_norm2_kernel, nn_search_kernel, nn_merge_kernel, baseline_forecasts_kernel) ----
@@ -3161,26 +3137,24 @@ size_t r50_op_nn_search_workspace(int nq, int n, int k) {
 }
 
 int r50_op_row_norm2(const void* x, int n, int d, int et, float* out, void* stream) {
-    if (!x || !out) return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: null pointer");
-    if (n < 1 || d < 8 || d % 8 != 0 || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, "r50_op_row_norm2: invalid arguments (need n >= 1, d a positive multiple of 8)");
-    if (int rc_al = need_aligned(nullptr, "r50_op_row_norm2", {{x, "x", 16}})) return rc_al;
-    R50_ET_LAUNCH(row_norm2_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), stream, (const unsigned short*)x, n, d, out);
-    return ew_done("r50_op_row_norm2");
+    const Op op{"r50_op_row_norm2"};
+    if (!x || !out) return op.refuse("null pointer");
+    if (n < 1 || d < 8 || d % 8 != 0 || (et != 0 && et != 1)) return op.refuse("invalid arguments (need n >= 1, d a positive multiple of 8)");
+    if (int rc = op.aligned({{x, "x", 16}})) return rc;
+    R50_ET_LAUNCH(et, row_norm2_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, (const unsigned short*)x, n, d, out);
+    return op.done();
 }
 
 int r50_op_nn_search(const void* q, int nq, const void* x, int n, int d, int et, const float* x_norm2, int k, int* idx_out, float* dist2_out,
                      void* workspace, size_t workspace_bytes, void* stream) {
-    const char* me = "r50_op_nn_search: ";
-    if (!q || !x || !x_norm2 || !idx_out || !dist2_out || !workspace) return fail(nullptr, R50_ERR_INVALID, std::string(me) + "null pointer");
+    const Op op{"r50_op_nn_search"};
+    if (!q || !x || !x_norm2 || !idx_out || !dist2_out || !workspace) return op.refuse("null pointer");
     if (nq < 1 || n < 1 || n > (1 << 30) || k < 1 || k > NN_MAX_K || k > n || d < 32 || d > 2048 || d % 32 != 0 || (et != 0 && et != 1))
-        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (need nq >= 1, 1 <= k <= 8, k <= n <= 2^30, d % 32 == 0 and "
-                                                                "32 <= d <= 2048)");
-    if (int rc_al = need_aligned(nullptr, "r50_op_nn_search", {{q, "q", 16}, {x, "x", 16}, {workspace, "workspace", 4}})) return rc_al;
-    if (workspace_bytes < r50_op_nn_search_workspace(nq, n, k))
-        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "the workspace is smaller than r50_op_nn_search_workspace asks for");
+        return op.refuse("invalid arguments (need nq >= 1, 1 <= k <= 8, k <= n <= 2^30, d % 32 == 0 and 32 <= d <= 2048)");
+    if (int rc = op.aligned({{q, "q", 16}, {x, "x", 16}, {workspace, "workspace", 4}})) return rc;
+    if (workspace_bytes < r50_op_nn_search_workspace(nq, n, k)) return op.refuse("the workspace is smaller than r50_op_nn_search_workspace asks for");
     const int cus = num_cus();
-    if (cus == 0) return fail(nullptr, R50_ERR_HIP, std::string(me) + "the device could not be queried");
+    if (cus == 0) return op.hip_failed("the device could not be queried");
     const int ch = nn_chunk_rows(d);
     const int n_chunks = (n + ch - 1) / ch;
     const int grid = std::min(std::min(n_chunks, cus), kNnMaxWgs);
@@ -3191,40 +3165,30 @@ int r50_op_nn_search(const void* q, int nq, const void* x, int n, int d, int et,
         int* ws_idx = (int*)(ws_score + (size_t)grid * nql * k);
         const size_t lds = (size_t)2 * ch * d * 2 + (size_t)((nql + 63) / 64 * 64) * k * 8;
         const unsigned short* ql = (const unsigned short*)q + (size_t)q0 * d;
-#define R50_NN_LAUNCH(ET, RB)                                                                                                       \
-        do {                                                                                                                        \
-            auto kern = nn_search_kernel<ET, RB>;                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return fail(nullptr, R50_ERR_HIP, std::string(me) + hipGetErrorString(e));                          \
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NN_THREADS), lds, s, ql, nql, (const unsigned short*)x, n, d, x_norm2, k, \
-                               ws_score, ws_idx);                                                                                   \
-        } while (0)
-        if (et) { if (ch == 32) R50_NN_LAUNCH(1, 2); else R50_NN_LAUNCH(1, 1); }
-        else { if (ch == 32) R50_NN_LAUNCH(0, 2); else R50_NN_LAUNCH(0, 1); }
-#undef R50_NN_LAUNCH
-        R50_ET_LAUNCH(nn_merge_kernel, dim3((unsigned)nql), dim3(64), stream, (const float*)ws_score, (const int*)ws_idx, grid, nql, k, ql, d,
+        auto kern = ch == 32 ? R50_BY_ET(et, nn_search_kernel, 2) : R50_BY_ET(et, nn_search_kernel, 1);      // rows per block: 2 with 32-row chunks
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+            return op.done(e);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NN_THREADS), lds, s, ql, nql, (const unsigned short*)x, n, d, x_norm2, k, ws_score, ws_idx);
+        R50_ET_LAUNCH(et, nn_merge_kernel, dim3((unsigned)nql), dim3(64), 0, stream, (const float*)ws_score, (const int*)ws_idx, grid, nql, k, ql, d,
                       idx_out + (size_t)q0 * k, dist2_out + (size_t)q0 * k);
     }
-    return ew_done("r50_op_nn_search");
+    return op.done();
 }
 
 int r50_op_baseline_forecasts(const float* a1, const float* a0, const int* nn_row, const float* dbj, int64_t n_db, int b, int k, int t_db,
                               int joints, int root, int input_len, int pred_len, float* const_pose, float* const_vel, float* nn,
                               void* stream) {
-    const char* me = "r50_op_baseline_forecasts: ";
+    const Op op{"r50_op_baseline_forecasts"};
     if (!a1 || (const_vel && !a0) || (nn && (!nn_row || !dbj)) || (!const_pose && !const_vel && !nn))
-        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "null pointer (a1 always; a0 with const_vel; nn_row and dbj with nn; at least one "
-                                                                "output)");
+        return op.refuse("null pointer (a1 always; a0 with const_vel; nn_row and dbj with nn; at least one output)");
     if (b < 1 || joints < 1 || joints > 64 || root < 0 || root >= joints || pred_len < 1 || input_len < 1 ||
         (int64_t)b * pred_len * joints > INT32_MAX / 3)
-        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (need b, pred_len, input_len >= 1, 1 <= joints <= 64, "
-                                                                "0 <= root < joints)");
+        return op.refuse("invalid arguments (need b, pred_len, input_len >= 1, 1 <= joints <= 64, 0 <= root < joints)");
     if (nn && (k < 1 || k > NN_MAX_K || n_db < 1 || t_db < 1 || (int64_t)input_len + pred_len > t_db || (int64_t)b * k > INT32_MAX))
-        return fail(nullptr, R50_ERR_INVALID, std::string(me) + "invalid arguments (with nn: 1 <= k <= 8, n_db >= 1 and input_len + pred_len "
-                                                                "<= t_db)");
+        return op.refuse("invalid arguments (with nn: 1 <= k <= 8, n_db >= 1 and input_len + pred_len <= t_db)");
     hipLaunchKernelGGL(baseline_forecasts_kernel, dim3(ew_grid((long long)b * pred_len * joints * 3)), dim3(256), 0, (hipStream_t)stream, a1,
                        a0, nn_row, dbj, b, k, t_db, joints, root, input_len, pred_len, const_pose, const_vel, nn);
-    return ew_done("r50_op_baseline_forecasts");
+    return op.done();
 }
 
 }  // extern "C"

@@ -84,14 +84,26 @@ def test_annotations_are_powers_of_two_between_the_element_size_and_256():
 
 
 def test_every_annotation_is_enforced_by_name():
-    """csrc/r50_abi.hip checks every annotated pointer that needs more than one byte through need_aligned, under the header's parameter
-    name and with the header's bytes -- so a refusal names the parameter, and no annotated pointer can reach a launch unchecked."""
-    checks = {}
-    for m in re.finditer(r'need_aligned\(\s*\w+\s*,\s*([^{]*?),\s*\{(.*?)\}\s*\)\)', ABI, flags=re.S):
-        fns = re.findall(r'"(r50_\w+)"', m.group(1))
-        for _ptr, name, nbytes in re.findall(r'\{\s*(\w+)\s*,\s*([^,{}]+?)\s*,\s*([^{}]+?)\s*\}', m.group(2)):
+    """csrc/r50_abi.hip checks every annotated pointer that needs more than one byte through its frame's `aligned`, under the header's
+    parameter name and with the header's bytes -- so a refusal names the parameter, and no annotated pointer can reach a launch unchecked.
+    The entry point a check belongs to is the one its frame (`const Op op{"r50_...", ...}`, the nearest one above the check) names; inside
+    the definition of an exported `int r50_...(` that name must be the function's own, and be the only time the body spells it."""
+    frames = [(m.start(), re.findall(r'"(r50_\w+)"', m.group(1))) for m in re.finditer(r'\bconst Op op\{([^;]*?)\};', ABI)]
+    assert len(frames) >= 70 and all(fns for _at, fns in frames)
+    checks, n_checked = {}, 0
+    for m in re.finditer(r'\bop\.aligned\(\s*\{(.*?)\}\s*\)\)', ABI, flags=re.S):
+        fns = [f for at, f in frames if at < m.start()][-1]
+        for _ptr, name, nbytes in re.findall(r'\{\s*(\w+)\s*,\s*([^,{}]+?)\s*,\s*([^{}]+?)\s*\}', m.group(1)):
+            n_checked += 1
             for fn in fns:
                 checks.setdefault(fn, []).append((name, nbytes))
+    print(f"{n_checked} pointers checked by name in r50_abi.hip, for {len(checks)} entry points")
+    assert n_checked >= 142 and len(checks) >= 43            # what the need_aligned calls held before the frames
+    for m in re.finditer(r'^int (r50_\w+)\([^;{}]*\) \{\n(.*?)^\}', ABI, flags=re.S | re.M):
+        fn, body = m.group(1), m.group(2)
+        if "const Op op{" in body:
+            named = re.findall(r'"(r50_\w+)', body)
+            assert named == [fn] if fn.startswith("r50_op_") else set(named) == {fn}, f"{fn}: its body names {named}"
     for fn, p in _device_pointers():
         if p.annotation is None or p.annotation == 1:
             continue
